@@ -14,12 +14,20 @@ mpc_controller/config/quadruped/mpc_opt.py:25-27) for B = 1024 centroidal proble
 (BASELINE configs[1]: nx = nu = 12, N = 50, fp32), inputs resident in HBM.  Independent problems
 shard across GPUs with no data-path collective (weak scaling); for N > 1 every step carries the one exchange of the
 path, the all-gather of the tracking errors.
-Rank 0 prints ONE JSON line.  At N = 1 the line also carries one sibling object per other GPU configuration of
-BASELINE.json, each measured in the same run and each with its own roofline / cpu_baseline / parity:
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, warm-up, the K timed
+steps, the outputs of the last step if --dump-outputs DIR is given, the line.  --full adds everything else next to the
+headline: the cpu_baseline (with the parity of the first solve against the fp64 oracle), the cold-start and large-batch
+variants and, at N = 1, one sibling object per other GPU configuration of BASELINE.json, each measured in the same run
+and each with its own roofline / cpu_baseline / parity:
   "wholebody"        configs[2]: B = 8192 whole-body problems (nx 42, nu 30, N 30)
   "rollouts"         configs[3], per-GPU slice: 8192 pushed 2 s rollouts with discard-and-redo of failed ones
   "mixed_precision"  configs[4]: the whole-body solve with the bf16 Gauss-Newton contraction
 (--headline-only leaves them out).  See DESIGN.md section 6 for the roofline accounting.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32, or float64 where
+the path computes float64; at most 64 MB in all -- larger outputs are cut to a fixed, seeded sample of their rows).  The
+inputs are seeded and the timed steps start from the same initial guess on every run, so two builds can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -40,8 +48,13 @@ MIXED_PRECISION_SHIPPED = 3   # nmpc_dims.precision of the recommended configs[4
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; 20 for --workload wholebody)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default 20; 3 for --workload wholebody)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline and parity, cold-start and large-batch "
+                         "variants, the sibling legs of the other GPU configurations (--no-* and --headline-only trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--workload", choices=("centroidal", "wholebody"), default="centroidal",
                     help="centroidal: BASELINE configs[1], the headline (B = 1024, nx = nu = 12, N = 50); "
                          "wholebody: configs[2] (B = 8192, nx = 42, nu = 30, N = 30)")
@@ -54,9 +67,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cold-start", action="store_true", help="leave out the 15-iteration cold-start and large-batch variants (profiling runs)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="leave out the sibling legs (wholebody / rollouts / mixed_precision) of the default line")
-    ap.add_argument("--wb-batch", type=int, default=8192, help="batch of the wholebody and mixed_precision legs of the default line")
-    ap.add_argument("--rollout-batch", type=int, default=8192, help="rollouts of the rollouts leg of the default line")
+                    help="leave out the sibling legs (wholebody / rollouts / mixed_precision) of the --full line")
+    ap.add_argument("--wb-batch", type=int, default=8192, help="batch of the wholebody and mixed_precision legs of the --full line")
+    ap.add_argument("--rollout-batch", type=int, default=8192, help="rollouts of the rollouts leg of the --full line")
     ap.add_argument("--rollouts", type=int, default=0,
                     help="extra mode (not the headline metric): B rollouts per GPU of 2 s (50 replans) fully "
                          "on the device, tracking error vs the nominal rollout, all-gather over the ranks")
@@ -66,7 +79,13 @@ def parse_args(argv=None):
                     help="extra mode (not the headline metric): inverse dynamics + PD for this many robots")
     ap.add_argument("--database", type=int, default=0,
                     help="extra mode (not the headline metric): mean/std + batch assembly over a state table of this many rows")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    wbm = a.workload == "wholebody" and not (a.rollouts or a.policy or a.database or a.torques)
+    if a.steps is None:
+        a.steps = 20 if wbm else 200      # defaults sized for the 0.5 ms centroidal step
+    if a.warmup is None:
+        a.warmup = 3 if wbm else 20
+    return a
 
 
 def spawn_ranks(n: int) -> int:
@@ -202,6 +221,30 @@ def traffic_record(key):
     return None, None
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def write_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: each array as directory/<name>.npy, float64 kept, everything else as float32.  Over the budget every
+    array keeps the same fraction of its rows, chosen by a fixed seed (the same rows for arrays of the same length)."""
+    host = {}
+    for name, v in arrays.items():
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        host[name] = v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False)
+    total = sum(v.nbytes for v in host.values())
+    slack = 4096 * len(host)                                  # .npy headers
+    if total + slack > budget:
+        keep = (budget - slack) / total
+        for name, v in host.items():
+            if v.ndim and v.shape[0] > 1:
+                n = max(1, int(v.shape[0] * keep))
+                rows = np.sort(np.random.default_rng(0).choice(v.shape[0], n, replace=False))
+                host[name] = v[rows]
+    os.makedirs(directory, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(directory, f"{name}.npy"), v)
+
+
 class SolveSetup:
     """One batch of one workload resident on the device, with its solver: what a timed step needs."""
 
@@ -237,6 +280,10 @@ class SolveSetup:
     def failed(self):
         return int((self.status == 1).sum().item() + (self.status == 4).sum().item())
 
+    def outputs(self):
+        """what the solve call hands its caller: the trajectories (solved in place), status and per-problem stats"""
+        return {"X": self.t["X"], "U": self.t["U"], "status": self.status, "stats": self.stats}
+
     def roofline(self, kernel_ms):
         n_sweeps = self.ipm if self.ipm > 0 else 1
         flops, nbytes = (algorithmic_work_wholebody(self.N, n_sweeps) if self.wbm else
@@ -264,7 +311,8 @@ class SolveSetup:
 
 def timed_steps(setup, steps, warmup, dist=None, exchange=None, ramp=0.25):
     """W untimed steps, then exactly K steps bracketed by barrier + synchronize; returns (wall seconds MAX over ranks,
-    mean solve-call milliseconds from HIP events on the launch stream)."""
+    mean solve-call milliseconds from HIP events on the launch stream).  The W + K steps start from the initial guess,
+    so what the last step computes does not depend on how many passes the clock ramp ran."""
     def step(timed):
         setup.solve(1)
         if exchange:
@@ -278,6 +326,7 @@ def timed_steps(setup, steps, warmup, dist=None, exchange=None, ramp=0.25):
         for _ in range(20 if not setup.wbm else 2):
             setup.solve(1)
         torch.cuda.synchronize()
+    setup.reset_guess()
     for _ in range(warmup):
         step(False)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
@@ -304,7 +353,7 @@ def timed_steps(setup, steps, warmup, dist=None, exchange=None, ramp=0.25):
 
 def wholebody_legs(a, dev, want_cpu):
     """configs[2] and configs[4] at N = 1, on one workload: B whole-body problems (nx 42, nu 30, N 30), a step = warm-start
-    shift + solve (1 SQP x 6 IPM).  Returns the two sibling objects of the default line."""
+    shift + solve (1 SQP x 6 IPM).  Returns the two sibling objects of the --full line."""
     B, N = a.wb_batch, 30
     out = {}
     w = wl.wholebody_trot(B=B, N=N, seed=0)
@@ -397,7 +446,7 @@ def single_solve_latency(dev):
             "reference_budget_ms": 40.0, "path": "LocomotionMPC.optimize -> QuadrupedAcadosSolver.init / solve (views -> pinned buffers -> device -> views)"}
 
 
-def rollout_leg(B, steps, warmup, world, rank, dev, dist, max_attempts=8, fill_batch=2048):
+def rollout_leg(B, steps, warmup, world, rank, dev, dist, max_attempts=8, fill_batch=2048, outputs=None):
     """BASELINE configs[3] per-GPU slice: B perturbed rollouts + the shared nominal one, each 2 s = 50
     replans (first one a 15-iteration cold start); rollouts that end with a solver failure or an unsafe base state are
     discarded and redone with a new push, as the reference re-rolls an early-terminated rollout
@@ -405,7 +454,8 @@ def rollout_leg(B, steps, warmup, world, rank, dev, dist, max_attempts=8, fill_b
     of the valid rollouts against the nominal one, one all-gather of errors and validity per learning iteration,
     OOD weights on every rank.  A redo pass over n < fill_batch rollouts rolls fill_batch // n candidates of each (independent
     pushes, the first that runs to the end is kept -- the distribution of the reference's one-by-one redo): every pass costs fifty
-    replans of latency however few rollouts it holds, and 2048 problems are what the chip holds at once."""
+    replans of latency however few rollouts it holds, and 2048 problems are what the chip holds at once.  `outputs` (a dict)
+    receives what the last step computed."""
     from iterative_learning_nmpc_amd.mpc import BatchedLocomotionMPC, sample_pushes
     from iterative_learning_nmpc_amd.parallel import all_gather_tracking_errors, learning_update, ood_threshold
     from iterative_learning_nmpc_amd.solver import tracking_error
@@ -440,6 +490,8 @@ def rollout_leg(B, steps, warmup, world, rank, dev, dist, max_attempts=8, fill_b
         el = float(tt.item())
     n_replans = S.shape[1]
     flags = mpc.failed
+    if outputs is not None:
+        outputs.update(trajectories=S, failed=flags, tracking_errors=err_all, valid=valid_all, ood=ood, weights=weights)
     n_rolled = int(sum(info["attempt_sizes"]))
     fl = algorithmic_work(12, 12, 16, 16, 50, 6)[0] * n_rolled * (n_replans + 14)   # first replan: 15 SQP iterations
     return {
@@ -463,7 +515,10 @@ def rollout_leg(B, steps, warmup, world, rank, dev, dist, max_attempts=8, fill_b
 
 
 def rollout_mode(a, world, rank, dev, dist):
-    leg = rollout_leg(a.rollouts, a.steps, a.warmup, world, rank, dev, dist)
+    outputs = {}
+    leg = rollout_leg(a.rollouts, a.steps, a.warmup, world, rank, dev, dist, outputs=outputs)
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, outputs)
     if rank == 0:
         roof = leg.pop("roofline")
         print(json.dumps({
@@ -503,11 +558,13 @@ def policy_mode(a, world, rank, dev, dist):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     ms = e0.elapsed_time(e1) / a.steps
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, dict(zip(("loss", "theta", "running_mean", "running_var"), (loss, *pol.get_parameters()))))
     macs = n_in * H + (L - 1) * H * H + H * n_out
     flops = 2.0 * B * (3 * macs - n_in * H)            # forward, weight gradient, data gradient (not for the input layer)
     nbytes = 4.0 * (B * (n_in + 2 * n_out) + 4 * (macs + (L * 3 + 1) * H))   # batch in/out + theta, grad, m, v once each
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         from oracle.policy_oracle import PolicyOracle      # the checker, timed as the reported CPU baseline
         o = PolicyOracle(n_in, n_out, L, H, True, np.float32)
         th, rm, rv = (t.cpu().numpy() for t in pol.get_parameters())
@@ -572,9 +629,11 @@ def database_mode(a, world, rank, dev, dist):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     ms = e0.elapsed_time(e1) / a.steps
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, {"x": x, "y": y})
     nbytes = 2.0 * rows * n_state * 4                      # the table is read once per pass; everything else is KB
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         from oracle.database_oracle import DatabaseOracle  # the checker, timed as the reported CPU baseline
         sample = min(rows, 2_000_000)
         o = DatabaseOracle(sample)
@@ -633,9 +692,11 @@ def torque_mode(a, world, rank, dev, dist):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     ms = e0.elapsed_time(e1) / a.steps
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, {"tau": tau})
     nbytes = 4.0 * B * (5 * n + 12 + 3 * nu)           # q, v, a, q_plan, v_plan, f in; tau_ff out + in, tau out
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         from oracle import torque_oracle as to             # the checker, timed as the reported CPU baseline
         m = to.TreeModel.from_arrays(tree)
         n_s = min(B, 256)
@@ -695,8 +756,6 @@ def main():
 
     wbm = a.workload == "wholebody"
     B, N = (a.batch or (8192 if wbm else 1024)), (30 if wbm else 50)
-    if wbm and a.steps == 200 and a.warmup == 20:      # defaults sized for the 0.5 ms centroidal step
-        a.steps, a.warmup = 20, 3
     su = SolveSetup(wbm, B, N, a.precision, a.sqp, a.ipm, dev, seed=1000 * rank)
     s, w, t = su.s, su.w, su.t
 
@@ -705,7 +764,7 @@ def main():
     # over the ranks (RCCL over xGMI).  At N = 1 there is no exchange and the step is the solve alone.
     from iterative_learning_nmpc_amd.solver import tracking_error
     from iterative_learning_nmpc_amd.parallel import all_gather_tracking_errors
-    ag_ev = []
+    ag_ev, gathered = [], {}
 
     def exchange(timed):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -715,16 +774,20 @@ def main():
         e1.record()
         if timed:
             ag_ev.append((e0, e1, err_all.shape))
+            gathered["tracking_errors"] = err_all
 
-    first = su.first_solve()      # the first solve of the untouched inputs, kept for the parity figure of the cpu_baseline leg
+    # --full: the first solve of the untouched inputs, kept for the parity figure of the cpu_baseline leg
+    first = su.first_solve() if a.full else None
     elapsed, kernel_ms = timed_steps(su, a.steps, a.warmup, dist, exchange if world > 1 else None)
     bad = su.failed()
-    default_run = (not wbm) and a.sqp == 1 and a.precision == 0 and not a.no_cold_start
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, dict(su.outputs(), **gathered))
+    default_run = a.full and (not wbm) and a.sqp == 1 and a.precision == 0 and not a.no_cold_start
 
     # the cold-start variant of the same workload -- the reference's first solve runs 15 SQP
     # iterations (mpc.py:464-473) from the standing initial guess; reported next to the headline, not as it
     cold = None
-    if a.sqp == 1 and a.precision == 0 and not a.no_cold_start:
+    if a.full and a.sqp == 1 and a.precision == 0 and not a.no_cold_start:
         s.set_max_iter(15)
         n_cold = max(2, min(10, a.steps))
         for i in range(n_cold + 1):
@@ -778,10 +841,10 @@ def main():
         if world > 1 and ag_ev:
             out["allgather"] = {"ms": float(np.mean([e0.elapsed_time(e1) for e0, e1, _ in ag_ev])), "backend": dist.get_backend(),
                                 "ranks": world, "gathered_shape": list(ag_ev[0][2]), "per_step": 1}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w, a.ipm, min(B, 256 if wbm else 1024), first if (a.sqp == 1 and a.precision == 0) else None)
     del su
-    # the other GPU configurations of BASELINE.json, measured in the same run (N = 1, default line only)
+    # the other GPU configurations of BASELINE.json, measured in the same run (N = 1, --full line only)
     if world == 1 and default_run and not a.headline_only and not a.batch:
         legs = wholebody_legs(a, dev, not a.no_cpu_baseline)
         out.update(legs)

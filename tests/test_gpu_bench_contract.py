@@ -1,10 +1,12 @@
-"""bench.py's output contract on the GPU: one JSON line with the driver's fields, the roofline object and (default
-run) the cpu_baseline object.  Small batches and few steps: this checks the line, not the numbers."""
+"""bench.py's output contract on the GPU: one JSON line with the driver's fields, the roofline object and (--full
+run) the cpu_baseline object; a plain run's line and the outputs it dumps.  Small batches and few steps: this checks the
+line, not the numbers."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +37,7 @@ def check_common(d, steps, warmup):
 
 
 def test_headline_line_with_cpu_baseline_and_parity():
-    d = run_bench("--steps", "4", "--warmup", "2", "--batch", "64", "--headline-only")
+    d = run_bench("--steps", "4", "--warmup", "2", "--batch", "64", "--headline-only", "--full")
     check_common(d, 4, 2)
     assert "wholebody" not in d and "rollouts" not in d
     assert d["metric"].startswith("MPC solves/sec") and d["unit"] == "solves/s" and d["dtype"] == "f32"
@@ -54,9 +56,9 @@ def test_extra_modes_print_the_same_contract(mode):
 
 
 def test_default_line_carries_every_gpu_configuration():
-    """the default line (what the driver records): the headline of configs[1] plus one sibling object per other GPU
-    configuration of BASELINE.json -- here at reduced leg sizes, the structure is what is checked"""
-    d = run_bench("--steps", "4", "--warmup", "2", "--wb-batch", "64", "--rollout-batch", "96")
+    """the --full line: the headline of configs[1] plus one sibling object per other GPU configuration of BASELINE.json --
+    here at reduced leg sizes, the structure is what is checked"""
+    d = run_bench("--steps", "4", "--warmup", "2", "--wb-batch", "64", "--rollout-batch", "96", "--full")
     check_common(d, 4, 2)
     assert d["config"]["global_batch"] == 1024 and d["large_batch"]["batch"] == 8192
     for key, cfg in (("wholebody", "configs[2]"), ("mixed_precision", "configs[4]")):
@@ -73,6 +75,24 @@ def test_default_line_carries_every_gpu_configuration():
     assert r["valid_rollouts"] + r["zero_weight_rollouts"] == 96 and r["rollouts_run_per_attempt"][0] == 96
     assert set(r["unsafe_state_rollouts"]) == {"roll", "pitch", "height", "velocity_tracking"}
     assert {"invalid", "solver", "collision"} <= set(r["first_attempt"])
+
+
+def test_plain_line_is_lean_and_dumps_the_same_outputs_every_run(tmp_path):
+    """a plain run measures the headline alone; --dump-outputs writes the last step's X, U, status and stats, and two runs
+    with the same arguments write the same arrays"""
+    runs = []
+    for i in range(2):
+        d = run_bench("--steps", "3", "--warmup", "2", "--batch", "64", "--dump-outputs", str(tmp_path / f"run{i}"))
+        check_common(d, 3, 2)
+        assert "cpu_baseline" not in d and d["cold_start"] is None and d["large_batch"] is None
+        assert not {"wholebody", "mixed_precision", "rollouts"} & set(d)
+        runs.append({n: np.load(tmp_path / f"run{i}" / f"{n}.npy") for n in ("X", "U", "status", "stats")})
+    a, b = runs
+    assert a["X"].shape == (64, 51, 12) and a["U"].shape == (64, 50, 12) and a["status"].shape == (64,)
+    assert all(v.dtype == np.float32 for v in a.values()) and np.isfinite(a["X"]).all()
+    assert d["failed_problems"] == 0
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
 
 
 def test_gpus_2_starts_its_own_ranks():
