@@ -5,13 +5,29 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_void_p
+from typing import Optional
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NMPC_HIP_LIB points diagnostics (tools/) at an alternative build of the same C-ABI
 LIB_PATH = os.environ.get("NMPC_HIP_LIB") or os.path.join(_HERE, "libnmpc_hip.so")
 
+# the C-ABI constants of include/nmpc.h (tests/test_abi.py checks them against the header)
 NMPC_OK = 0
-STATUS_NAMES = {0: "ok", 1: "nan", 2: "max_iter", 3: "min_step", 4: "qp_failure"}
+NMPC_STATUS_OK, NMPC_STATUS_NAN, NMPC_STATUS_MAXITER, NMPC_STATUS_MINSTEP, NMPC_STATUS_QP = 0, 1, 2, 3, 4
+STATUS_NAMES = {NMPC_STATUS_OK: "ok", NMPC_STATUS_NAN: "nan", NMPC_STATUS_MAXITER: "max_iter",
+                NMPC_STATUS_MINSTEP: "min_step", NMPC_STATUS_QP: "qp_failure"}
+# bits of a rollout's failed[b]; above NMPC_ROLLOUT_TERM_SHIFT: 1 + the replan that terminated the rollout
+NMPC_ROLLOUT_FLAG_SOLVER = 1
+NMPC_ROLLOUT_FLAG_ROLL = 2
+NMPC_ROLLOUT_FLAG_PITCH = 4
+NMPC_ROLLOUT_FLAG_HEIGHT = 8
+NMPC_ROLLOUT_FLAG_VEL_TRACKING = 16
+NMPC_ROLLOUT_FLAG_COLLISION = 32
+NMPC_ROLLOUT_FLAG_JOINT_LIMIT = 64      # whole-body rollouts only
+NMPC_ROLLOUT_FLAG_MASK = 0xFF
+NMPC_ROLLOUT_TERM_SHIFT = 8
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -136,7 +152,24 @@ class NmpcError(RuntimeError):
     pass
 
 
-def check(rc: int, handle=None, what: str = "") -> None:
+# the last-error call of each family of the C-ABI (the dataset calls keep one error per process and take no handle)
+_LAST_ERROR = {"solve": "nmpc_last_error", "policy": "nmpc_policy_last_error", "torque": "nmpc_torque_last_error",
+               "dataset": "nmpc_dataset_last_error"}
+
+
+def check(rc: int, handle=None, what: str = "", family: str = "solve") -> None:
+    """Raise NmpcError for a non-zero return code, with the library's text of the family's last error."""
     if rc != NMPC_OK:
-        msg = load().nmpc_last_error(handle)
+        last_error = getattr(load(), _LAST_ERROR[family])
+        msg = last_error() if family == "dataset" else last_error(handle)
         raise NmpcError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+
+def ptr(t: Optional[torch.Tensor]) -> Optional[c_void_p]:
+    """a tensor's device address as a pointer argument (None: NULL)"""
+    return None if t is None else c_void_p(t.data_ptr())
+
+
+def stream(device) -> c_void_p:
+    """the current stream of `device` as the stream argument"""
+    return c_void_p(torch.cuda.current_stream(device).cuda_stream)

@@ -17,6 +17,8 @@ from typing import Tuple
 
 import numpy as np
 
+from ._lib import NMPC_ROLLOUT_FLAG_COLLISION, NMPC_ROLLOUT_FLAG_SOLVER
+
 
 class HPIPM_MODE(enum.Enum):
     """Stand-in for contact_tamp's enum (config_abstract.py:5,64); only `speed` is used."""
@@ -203,3 +205,11 @@ def get_quadruped_config(gait_name: str, robot_name: str):
     """(gait, opt, cost) triple, as mpc_controller/config/quadruped/utils.py:8-16."""
     return (GaitConfigFactory.get(gait_name), MPCQuadrupedCyclic(),
             CostConfigFactory.get(robot_name, gait_name))
+
+
+# the rollouts of both controllers (mpc.py, mpc_wholebody.py)
+N_SQP_FIRST = 15             # SQP iterations of the first solve (mpc.py:465)
+# what ends a rollout early and makes the data collection discard and redo it: the controller diverged or the robot lies
+# on the ground (the reference: mpc.diverged / a collision the simulator does not allow, RolloutMPC.py:404,424-437)
+TERMINATE_DEFAULT = NMPC_ROLLOUT_FLAG_SOLVER | NMPC_ROLLOUT_FLAG_COLLISION
+COLLISION_HEIGHT = 0.08      # [decl] base height of a trunk that touches the floor

@@ -18,21 +18,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr, stream
 
 FIELDS = ("states", "vc_goals", "cc_goals", "actions")
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _check(rc, what):
-    if rc:
-        raise _lib.NmpcError(f"{what}: {_lib.load().nmpc_dataset_last_error().decode()}")
 
 
 def column_stats(table: torch.Tensor, rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -43,8 +31,8 @@ def column_stats(table: torch.Tensor, rows: Optional[int] = None) -> Tuple[torch
     cols = table.shape[1]
     out = torch.empty(2, cols, dtype=torch.float64, device=table.device)
     scratch = torch.empty(lib.nmpc_column_stats_scratch(cols), dtype=torch.float64, device=table.device)
-    _check(lib.nmpc_column_stats(_ptr(table), rows, cols, _ptr(out[0]), _ptr(out[1]), _ptr(scratch), _stream(table.device)),
-           "nmpc_column_stats")
+    _lib.check(lib.nmpc_column_stats(ptr(table), rows, cols, ptr(out[0]), ptr(out[1]), ptr(scratch), stream(table.device)),
+               None, "nmpc_column_stats", "dataset")
     return out[0], out[1]
 
 
@@ -95,8 +83,8 @@ class DeviceDatabase:
         for f, a in given.items():
             if a is None:
                 continue
-            _check(lib.nmpc_ring_append(_ptr(a), a.shape[1], n, _ptr(self.tables[f]), self.limit, first_slot,
-                                        _stream(self.device)), "nmpc_ring_append")
+            _lib.check(lib.nmpc_ring_append(ptr(a), a.shape[1], n, ptr(self.tables[f]), self.limit, first_slot,
+                                            stream(self.device)), None, "nmpc_ring_append", "dataset")
             if f in self.has:
                 self.has[f] = True
         grow = min(n, self.limit - self.length)             # room first, then the start moves (:124-131)
@@ -140,10 +128,10 @@ class DeviceDatabase:
             s_mean, s_std = self.states_mean, self.states_std
             if self.goal_type == "cc":
                 g_mean, g_std = self.cc_goals_mean, self.cc_goals_std
-        _check(lib.nmpc_assemble_batch(_ptr(self.tables["states"]), n_state, _ptr(s_mean), _ptr(s_std), 1,
-                                       _ptr(self.tables[goal_field]), n_goal, _ptr(g_mean), _ptr(g_std),
-                                       _ptr(self.tables["actions"]), n_action, self.length, _ptr(idx), idx.numel(),
-                                       _ptr(x), _ptr(y), _stream(self.device)), "nmpc_assemble_batch")
+        _lib.check(lib.nmpc_assemble_batch(ptr(self.tables["states"]), n_state, ptr(s_mean), ptr(s_std), 1,
+                                           ptr(self.tables[goal_field]), n_goal, ptr(g_mean), ptr(g_std),
+                                           ptr(self.tables["actions"]), n_action, self.length, ptr(idx), idx.numel(),
+                                           ptr(x), ptr(y), stream(self.device)), None, "nmpc_assemble_batch", "dataset")
         return x, y
 
     # ------------------------------------------------------------------ files (npz first)

@@ -22,22 +22,17 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .config import get_quadruped_config
+from .config import COLLISION_HEIGHT, N_SQP_FIRST, TERMINATE_DEFAULT, get_quadruped_config
 from .contact_planner import ContactPlanner, RaiberContactPlanner
 from .profiling import print_timings, time_fn
-from .references import _euler_rate_matrix, _hermite, rpy_to_matrix
+from .references import _euler_rate_matrix, _hermite, base_ref_vel_tracking, increment_base_ref_position
 from .solver import BatchedNmpcSolver
-from .workloads import FEET, HIP_OFFSETS, MODEL_CENTROIDAL, model_params
-
-N_SQP_FIRST = 15   # mpc.py:465
-
 # bits of `failed` (include/nmpc.h NMPC_ROLLOUT_FLAG_*); above them 1 + the replan that terminated the rollout
-FLAG_SOLVER, FLAG_ROLL, FLAG_PITCH, FLAG_HEIGHT, FLAG_VEL_TRACKING, FLAG_COLLISION = 1, 2, 4, 8, 16, 32
-FLAG_MASK, TERM_SHIFT = 0xFF, 8
-# what ends a rollout early and makes the data collection discard and redo it: the controller diverged or the robot lies
-# on the ground (the reference: mpc.diverged / a collision the simulator does not allow, RolloutMPC.py:404,424-437)
-TERMINATE_DEFAULT = FLAG_SOLVER | FLAG_COLLISION
-COLLISION_HEIGHT = 0.08      # [decl] base height of a trunk that touches the floor
+from .solver import (NMPC_ROLLOUT_FLAG_COLLISION as FLAG_COLLISION, NMPC_ROLLOUT_FLAG_HEIGHT as FLAG_HEIGHT,
+                     NMPC_ROLLOUT_FLAG_MASK as FLAG_MASK, NMPC_ROLLOUT_FLAG_PITCH as FLAG_PITCH, NMPC_ROLLOUT_FLAG_ROLL as FLAG_ROLL,
+                     NMPC_ROLLOUT_FLAG_SOLVER as FLAG_SOLVER, NMPC_ROLLOUT_FLAG_VEL_TRACKING as FLAG_VEL_TRACKING,
+                     NMPC_ROLLOUT_TERM_SHIFT as TERM_SHIFT)
+from .workloads import FEET, HIP_OFFSETS, MODEL_CENTROIDAL, model_params
 
 
 def sample_pushes(n: int, seed, start: float = 0.0, duration: float = 0.3, magnitude=(50.0, 70.0)) -> dict:
@@ -67,37 +62,6 @@ def state_row_flags(rows: np.ndarray, v_des: np.ndarray, collision_height: float
     f |= np.where(r[:, :, 7] < np.float32(collision_height), FLAG_COLLISION, 0)
     f |= np.where(~(np.abs(r[:, :, 7]) <= np.float32(1e30)), FLAG_SOLVER, 0)
     return np.bitwise_or.reduce(f, axis=1)
-
-
-def base_ref_vel_tracking_batch(q, v_des, w_des, ref_state, t_horizon, nom_height, height_offset=0.0):
-    """Vectorised `compute_base_ref_vel_tracking` (mpc.py:210-272) for q[B,>=4], v_des[B,3],
-    w_des[B,3], ref_state[B,12].  Same roundings: np.round(.,2) on position, builtin round(.,1) on yaw,
-    np.round(.,1) on the commanded velocity; same crossed-bounds clips."""
-    q, v_des, w_des = (np.asarray(a, dtype=np.float64) for a in (q, v_des, w_des))
-    B = q.shape[0]
-    ref = np.zeros((B, 12))
-    ref[:, :2] = np.round(q[:, :2], 2)
-    ref[:, 2] = nom_height + height_offset
-    ref[:, 3] = [round(float(y), 1) for y in q[:, 3]]
-    R = np.stack([rpy_to_matrix(s[3:6][::-1]) for s in ref_state])
-    v_glob = np.round(np.einsum("bij,bj->bi", R, v_des), 1)
-    ref[:, 6:9] = v_glob
-    ref[:, 9:12] = w_des[:, ::-1]
-    ref_e = ref.copy()
-    R_yaw = np.stack([rpy_to_matrix(w * t_horizon) for w in w_des])
-    ref_e[:, 6:9] = np.einsum("bij,bj->bi", R_yaw, ref[:, 6:9])
-    reach = v_glob[:, :2] * t_horizon
-    ref_e[:, :2] = np.clip(ref_state[:, :2] + reach, -ref[:, :2] + 1.2 * reach, ref[:, :2] + 1.2 * reach)
-    yaw_reach = w_des[:, 2] * t_horizon
-    yaw_ref = ref_state[:, 3]
-    ref_e[:, 3] = np.clip(yaw_ref + yaw_reach, -yaw_ref + 1.5 * yaw_reach, yaw_ref + 1.5 * yaw_reach)
-    ref[:, :2] += 0.75 * (ref_e[:, :2] - ref[:, :2])
-    ref[:, 3] += 0.75 * (ref_e[:, 3] - ref[:, 3])
-    ref_e[:, 8] = 0.0
-    ref_e[:, 4:6] = 0.0
-    ref[:, 4:6] = 0.0
-    ref_e[:, 10:12] = 0.0
-    return ref, ref_e
 
 
 class BatchedLocomotionMPC:
@@ -177,28 +141,16 @@ class BatchedLocomotionMPC:
         return self.sim_step % self.replanning_steps == 0
 
     def compute_base_ref_vel_tracking(self, q: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-        return base_ref_vel_tracking_batch(q, self.v_des, self.w_des, self.base_ref_vel_tracking,
-                                           self.config_opt.time_horizon, self.config_gait.nom_height,
-                                           self.height_offset)
+        return base_ref_vel_tracking(q, self.v_des, self.w_des, self.base_ref_vel_tracking, self.config_opt.time_horizon,
+                                     self.config_gait.nom_height, self.height_offset)
 
     def increment_base_ref_position(self, n_steps: int = 1, rows=None) -> None:
-        """mpc.py:204-208, once per simulation step, vectorised over the batch (rows: mask of the rollouts that advance)."""
-        if rows is not None and not rows.all():
-            keep = self.base_ref_vel_tracking[~rows].copy()
-            self.increment_base_ref_position(n_steps)
-            self.base_ref_vel_tracking[~rows] = keep
-            return
-        s = self.base_ref_vel_tracking
+        """mpc.py:204-208, once per simulation step, over the batch (rows: mask of the rollouts that advance)."""
+        rows = slice(None) if rows is None else rows
+        s = self.base_ref_vel_tracking[rows]
         for _ in range(n_steps):
-            cr, sr = np.cos(s[:, 5]), np.sin(s[:, 5])
-            cp, sp = np.cos(s[:, 4]), np.sin(s[:, 4])
-            cy, sy = np.cos(s[:, 3]), np.sin(s[:, 3])
-            v = self.v_des
-            vx = cy * cp * v[:, 0] + (cy * sp * sr - sy * cr) * v[:, 1] + (cy * sp * cr + sy * sr) * v[:, 2]
-            vy = sy * cp * v[:, 0] + (sy * sp * sr + cy * cr) * v[:, 1] + (sy * sp * cr - cy * sr) * v[:, 2]
-            s[:, 0] += np.round(vx, 1) * self.sim_dt
-            s[:, 1] += np.round(vy, 1) * self.sim_dt
-            s[:, 3] += self.w_des[:, 2] * self.sim_dt
+            increment_base_ref_position(s, self.v_des[rows], self.w_des[rows], self.sim_dt)
+        self.base_ref_vel_tracking[rows] = s
 
     # -- one replanning step --------------------------------------------------------------------
     def build_problem(self, x: np.ndarray):
@@ -345,56 +297,38 @@ class BatchedLocomotionMPC:
         S = torch.as_tensor(np.concatenate(rec, axis=1), dtype=torch.float32).to(self.device).contiguous()
         return S, np.asarray(times)
 
-    def _rollout_cfg(self, n_replans: int, start_node: int, first_solve: bool, push: Optional[dict]):
-        import ctypes
-        from . import _lib
-        return _lib.NmpcRolloutCfg(
-            n_replans, self.nodes_per_replan, self.replanning_steps, self.contact_planner.nodes_per_cycle,
-            start_node, int(first_solve), N_SQP_FIRST, self.config_opt.nlp_tol / 10.0,
-            self.config_opt.nlp_tol, self.sim_dt, self.config_opt.time_horizon, self.config_gait.nom_height,
-            self.height_offset, float(push["start"]) if push else 0.0, float(push["duration"]) if push else 0.0,
-            int(self.footsteps), int(self.record_sim_steps),
-            (ctypes.c_float * 8)(*self.raibert.offset_hip_b[:, :2].ravel().tolist()),
-            (ctypes.c_float * 4)(*np.asarray(self.config_gait.stance_ratio, float).tolist()),
-            float(self.config_gait.nominal_period), float(self.raibert.foot_size),
-            int(self.terminate_mask), float(self.collision_height))
-
     def _device_rollout(self, n_replans, start_node, first_solve, push, x, v_des, w_des, ref_state, foot, X, U, status):
         """One nmpc_rollout_batch call on explicit device tensors (x, ref_state, foot, X, U are updated in place).
         Returns (S, failed)."""
-        import ctypes
-        from . import _lib
-        s, dev, B = self.solver, self.device, x.shape[0]
-        period = self.config_gait.nominal_period
+        s, period = self.solver, self.config_gait.nominal_period
         times = np.arange(n_replans) * self.replanning_steps * self.sim_dt
-        phase = np.ascontiguousarray(np.round((times % period) / period, 4), dtype=np.float32)
-        cfg = self._rollout_cfg(n_replans, start_node, first_solve, push)
-        rows_per_replan = self.replanning_steps if self.record_sim_steps else 1
         if getattr(self, "_gait_dev", None) is None:
-            self._gait_dev = torch.as_tensor(np.ascontiguousarray(self.contact_planner.gait_sequence), dtype=torch.int8).to(dev)
-        force = s.to_device(np.asarray(push["force"])) if push else None
-        S = torch.empty(B, n_replans * rows_per_replan, 19, dtype=torch.float32, device=dev)
-        failed = torch.zeros(B, dtype=torch.int32, device=dev)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(s.lib.nmpc_rollout_batch(
-            s._h, B, ctypes.byref(cfg), p(self._gait_dev), p(x), p(v_des), p(w_des), p(ref_state), p(foot), p(force),
-            phase.ctypes.data_as(ctypes.c_void_p), p(X), p(U), p(S), p(status), p(failed),
-            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), s._h, "nmpc_rollout_batch")
-        return S, failed
+            self._gait_dev = s.to_device(self.contact_planner.gait_sequence, torch.int8)
+        return s.rollout(
+            self._gait_dev, x, v_des, w_des, ref_state, foot, s.to_device(np.asarray(push["force"])) if push else None,
+            np.round((times % period) / period, 4), X, U, status,
+            n_replans=n_replans, nodes_per_replan=self.nodes_per_replan, replanning_steps=self.replanning_steps,
+            nodes_per_cycle=self.contact_planner.nodes_per_cycle, start_node=start_node, first_solve=int(first_solve),
+            max_sqp_first=N_SQP_FIRST, nlp_tol_first=self.config_opt.nlp_tol / 10.0, nlp_tol=self.config_opt.nlp_tol,
+            sim_dt=self.sim_dt, time_horizon=self.config_opt.time_horizon, nom_height=self.config_gait.nom_height,
+            height_offset=self.height_offset, push_start=float(push["start"]) if push else 0.0,
+            push_duration=float(push["duration"]) if push else 0.0, footsteps=int(self.footsteps),
+            record_sim_steps=int(self.record_sim_steps), hip_offset=self.raibert.offset_hip_b[:, :2].ravel().tolist(),
+            stance_ratio=np.asarray(self.config_gait.stance_ratio, float).tolist(), nominal_period=float(period),
+            foot_size=float(self.raibert.foot_size), terminate_mask=int(self.terminate_mask),
+            collision_height=float(self.collision_height))
 
     def open_loop_device(self, x0: np.ndarray, trajectory_time: float, push: Optional[dict] = None):
         """`open_loop` with the whole rollout on the device: one C call launches every replanning
         step (references, shift, solve, plant update) on the stream -- no host round trip per replan.
         Same return value as `open_loop`; the controller state (X, U, node, reference) advances alike."""
-        s, B, dev = self.solver, self.batch, self.device
+        s, B = self.solver, self.batch
         dt_replan = self.replanning_steps * self.sim_dt
         n_replans = int(np.floor(trajectory_time / dt_replan + 1e-9))
         if self.foot_pos is None:
             self.foot_pos = np.asarray(x0)[:, None, :3] * [1, 1, 0] + HIP_OFFSETS[None]
         x = s.to_device(x0)
-        v_des = torch.as_tensor(self.v_des, dtype=torch.float64).to(dev).contiguous()
-        w_des = torch.as_tensor(self.w_des, dtype=torch.float64).to(dev).contiguous()
-        ref_state = torch.as_tensor(self.base_ref_vel_tracking, dtype=torch.float64).to(dev).contiguous()
+        v_des, w_des, ref_state = (s.to_device(a, torch.float64) for a in (self.v_des, self.w_des, self.base_ref_vel_tracking))
         foot = s.to_device(self.foot_pos.reshape(B, 12))
         S, failed = self._device_rollout(n_replans, self.current_opt_node, self.first_solve, push, x, v_des, w_des, ref_state,
                                          foot, self.X, self.U, self.status)
@@ -459,9 +393,7 @@ class BatchedLocomotionMPC:
             idx_h = np.repeat(idx.cpu().numpy(), cand)                    # candidate j rolls rollout idx[j // cand]
             push_n = push_sampler(m, attempt)
             x = s.to_device(x0[idx_h])
-            v_des = torch.as_tensor(self.v_des[idx_h], dtype=torch.float64).to(dev).contiguous()
-            w_des = torch.as_tensor(self.w_des[idx_h], dtype=torch.float64).to(dev).contiguous()
-            ref_state = torch.as_tensor(ref0[idx_h], dtype=torch.float64).to(dev).contiguous()
+            v_des, w_des, ref_state = (s.to_device(a[idx_h], torch.float64) for a in (self.v_des, self.w_des, ref0))
             foot = s.to_device(foot0[idx_h].reshape(m, 12))
             Xn = torch.zeros(m, self.n_nodes + 1, 12, dtype=torch.float32, device=dev)
             Un = torch.zeros(m, self.n_nodes, 12, dtype=torch.float32, device=dev)

@@ -23,14 +23,12 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import wholebody as wb
-from .config import get_quadruped_config
+from .config import COLLISION_HEIGHT, N_SQP_FIRST, TERMINATE_DEFAULT, get_quadruped_config
 from .contact_planner import ContactPlanner, RaiberContactPlanner
 from .profiling import print_timings, time_fn
 from .quadruped_solver import QuadrupedAcadosSolver
 from .references import base_ref_cnt_restricted, base_ref_vel_tracking, hermite_upsample, increment_base_ref_position
 from .workloads import FEET
-
-N_SQP_FIRST = 15     # mpc.py:465
 
 
 class LocomotionMPC:
@@ -90,19 +88,11 @@ class LocomotionMPC:
         self.w_des[..., 2] = w_yaw
 
     def increment_base_ref_position(self):                                                  # mpc.py:204-208
-        if self.batch == 1:
-            increment_base_ref_position(self.base_ref_vel_tracking, self.v_des, self.w_des, self.sim_dt)
-        else:
-            for b in range(self.batch):
-                increment_base_ref_position(self.base_ref_vel_tracking[b], self.v_des[b], self.w_des[b], self.sim_dt)
+        increment_base_ref_position(self.base_ref_vel_tracking, self.v_des, self.w_des, self.sim_dt)
 
     def compute_base_ref_vel_tracking(self, q: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:   # mpc.py:210-272
-        T, h = self.config_opt.time_horizon, self.config_gait.nom_height
-        if self.batch == 1:
-            return base_ref_vel_tracking(q, self.v_des, self.w_des, self.base_ref_vel_tracking, T, h, self.height_offset)
-        out = [base_ref_vel_tracking(q[b], self.v_des[b], self.w_des[b], self.base_ref_vel_tracking[b], T, h, self.height_offset)
-               for b in range(self.batch)]
-        return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
+        return base_ref_vel_tracking(q, self.v_des, self.w_des, self.base_ref_vel_tracking, self.config_opt.time_horizon,
+                                     self.config_gait.nom_height, self.height_offset)
 
     def compute_base_ref_cnt_restricted(self, q, contact_locations):                        # mpc.py:274-315
         return base_ref_cnt_restricted(contact_locations, self.config_gait.nom_height, self.height_offset)
@@ -219,7 +209,8 @@ class LocomotionMPC:
         return rows
 
     def open_loop_device(self, q0: np.ndarray, v0: np.ndarray, trajectory_time: float, push: Optional[dict] = None,
-                         record_sim_steps: bool = True, terminate_mask: int = 33, collision_height: float = 0.08):
+                         record_sim_steps: bool = True, terminate_mask: int = TERMINATE_DEFAULT,
+                         collision_height: float = COLLISION_HEIGHT):
         """`open_loop` with the whole rollout on the device (nmpc_wb_rollout_batch): per replan the problem is assembled from
         the plant state by a kernel, solved with the warm-start shift folded in, and the up-sampled plan is followed for
         `replanning_steps` simulation steps -- one host call, no round trip per replan, the whole batch at once.
@@ -228,9 +219,7 @@ class LocomotionMPC:
         "force": [B, 3]}: velocity impulse F dt / m on the base per replanning interval.  The controller's counters,
         reference and solution views advance as in `open_loop`; `self.failed` holds the NMPC_ROLLOUT_FLAG_* bits,
         `self.q_final` / `self.v_final` the plant state."""
-        import ctypes
         import torch
-        from . import _lib
         fs = self.solver
         s = fs._device_solver()
         B, N, dev = self.batch, self.config_opt.n_nodes, s.device
@@ -239,33 +228,26 @@ class LocomotionMPC:
         cfg_o = self.config_opt
         s.set_max_iter(cfg_o.max_iter); s.set_nlp_tol(cfg_o.nlp_tol); s.set_max_qp_iter(cfg_o.max_qp_iter)
         fs._opts.update(max_iter=cfg_o.max_iter, nlp_tol=cfg_o.nlp_tol, qp_tol=cfg_o.qp_tol)
-        cfg = _lib.NmpcWbRolloutCfg(
-            n_replans, self.replanning_steps, self.contact_planner.nodes_per_cycle, int(self.first_solve), int(fs.last_node),
-            N_SQP_FIRST, cfg_o.nlp_tol / 10.0, cfg_o.nlp_tol, self.sim_dt, cfg_o.time_horizon, self.config_gait.nom_height,
-            self.height_offset, float(self.config_gait.step_height), float(push["start"]) if push else 0.0,
-            float(push["duration"]) if push else 0.0, int(record_sim_steps), int(fs.force_reference == "gravity_share"),
-            float(self.config_gait.nominal_period), int(terminate_mask), float(collision_height))
-        t32 = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.float64).reshape(B, -1)), dtype=torch.float32).to(dev).contiguous()
-        t64 = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.float64).reshape(B, -1)), dtype=torch.float64).to(dev).contiguous()
-        q, v = t32(q0), t32(v0)
-        v_des, w_des, ref_state = t64(self.v_des), t64(self.w_des), t64(self.base_ref_vel_tracking)
-        gait = torch.as_tensor(np.ascontiguousarray(self.contact_planner.gait_sequence), dtype=torch.int8).to(dev)
-        peaks = torch.as_tensor(np.ascontiguousarray(self.contact_planner.peak_swing), dtype=torch.int8).to(dev)
-        joint_ref = torch.as_tensor(self.joint_ref, dtype=torch.float32).to(dev).contiguous()
-        force = t32(push["force"]) if push else None
+        by_rollout = lambda a, dtype=torch.float32: s.to_device(np.asarray(a, np.float64).reshape(B, -1), dtype)   # noqa: E731
+        q, v = by_rollout(q0), by_rollout(v0)
+        v_des, w_des, ref_state = (by_rollout(a, torch.float64) for a in (self.v_des, self.w_des, self.base_ref_vel_tracking))
         if getattr(self, "_X_dev", None) is None or self.first_solve:
             self._X_dev = torch.zeros(B, N + 1, 42, dtype=torch.float32, device=dev)
             self._U_dev = torch.zeros(B, N, 30, dtype=torch.float32, device=dev)
-        rows = n_replans * (self.replanning_steps if record_sim_steps else 1)
-        S = torch.empty(B, rows, 44, dtype=torch.float32, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
-        failed = torch.zeros(B, dtype=torch.int32, device=dev)
-        nodes_c = (ctypes.c_int * n_replans)(*nodes)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(s.lib.nmpc_wb_rollout_batch(
-            s._h, B, ctypes.byref(cfg), p(gait), p(peaks), ctypes.cast(nodes_c, ctypes.c_void_p), p(q), p(v), p(v_des), p(w_des),
-            p(ref_state), p(joint_ref), p(force), p(self._X_dev), p(self._U_dev), p(S), p(status), p(failed),
-            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), s._h, "nmpc_wb_rollout_batch")
+        S, failed = s.wb_rollout(
+            s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
+            nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref), by_rollout(push["force"]) if push else None,
+            self._X_dev, self._U_dev, status,
+            n_replans=n_replans, replanning_steps=self.replanning_steps, nodes_per_cycle=self.contact_planner.nodes_per_cycle,
+            first_solve=int(self.first_solve), last_node=int(fs.last_node), max_sqp_first=N_SQP_FIRST,
+            nlp_tol_first=cfg_o.nlp_tol / 10.0, nlp_tol=cfg_o.nlp_tol, sim_dt=self.sim_dt, time_horizon=cfg_o.time_horizon,
+            nom_height=self.config_gait.nom_height, height_offset=self.height_offset,
+            step_height=float(self.config_gait.step_height), push_start=float(push["start"]) if push else 0.0,
+            push_duration=float(push["duration"]) if push else 0.0, record_sim_steps=int(record_sim_steps),
+            force_reference_gravity=int(fs.force_reference == "gravity_share"),
+            nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
+            collision_height=float(collision_height))
         # bookkeeping as open_loop leaves it
         self.first_solve = False
         self.sim_step += steps

@@ -14,14 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+from ._lib import ptr, stream
 
 
 def parameter_layout(n_in, n_out, n_hidden, hidden, batch_norm):
@@ -53,9 +46,7 @@ class DevicePolicy:
         d = _lib.NmpcPolicyDims(*self.dims[:4], int(batch_norm), self.batch_max)
         self._h = ctypes.c_void_p()
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        rc = self.lib.nmpc_policy_create(ctypes.byref(d), idx, ctypes.byref(self._h))
-        if rc:
-            raise _lib.NmpcError(f"nmpc_policy_create: {self.lib.nmpc_policy_last_error(None).decode()}")
+        _lib.check(self.lib.nmpc_policy_create(ctypes.byref(d), idx, ctypes.byref(self._h)), None, "nmpc_policy_create", "policy")
         self.items, self.n_theta = parameter_layout(*self.dims)
         assert self.n_theta == self.lib.nmpc_policy_param_count(self._h)
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -67,10 +58,6 @@ class DevicePolicy:
         if h:
             self.lib.nmpc_policy_destroy(h)
             self._h = None
-
-    def _check(self, rc, what):
-        if rc:
-            raise _lib.NmpcError(f"{what}: {self.lib.nmpc_policy_last_error(self._h).decode()}")
 
     # -- parameters ---------------------------------------------------------------------------------
     def init_weight(self, seed: int = 0):
@@ -93,8 +80,8 @@ class DevicePolicy:
         assert theta.numel() == self.n_theta
         rm = dev(running_mean) if bn else None
         rv = dev(running_var) if bn else None
-        self._check(self.lib.nmpc_policy_set_params(self._h, _ptr(theta), _ptr(rm), _ptr(rv), _stream(self.device)),
-                    "nmpc_policy_set_params")
+        _lib.check(self.lib.nmpc_policy_set_params(self._h, ptr(theta), ptr(rm), ptr(rv), stream(self.device)),
+                   self._h, "nmpc_policy_set_params", "policy")
         torch.cuda.current_stream(self.device).synchronize()      # the staging tensors go out of scope
 
     def get_parameters(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -104,8 +91,8 @@ class DevicePolicy:
         #  the state of a fresh BatchNorm layer, rather than uninitialised memory)
         rm = torch.zeros(L, hidden, dtype=torch.float32, device=self.device)
         rv = torch.ones(L, hidden, dtype=torch.float32, device=self.device)
-        self._check(self.lib.nmpc_policy_get_params(self._h, _ptr(theta), _ptr(rm), _ptr(rv), _stream(self.device)),
-                    "nmpc_policy_get_params")
+        _lib.check(self.lib.nmpc_policy_get_params(self._h, ptr(theta), ptr(rm), ptr(rv), stream(self.device)),
+                   self._h, "nmpc_policy_get_params", "policy")
         return theta, rm, rv
 
     def load_state_dict(self, state: Dict[str, "np.ndarray"]):
@@ -132,7 +119,8 @@ class DevicePolicy:
         B = x.shape[0]
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape == (B, self.dims[0])
         y = torch.empty(B, self.dims[1], dtype=torch.float32, device=self.device)
-        self._check(self.lib.nmpc_policy_forward(self._h, B, _ptr(x), _ptr(y), _stream(self.device)), "nmpc_policy_forward")
+        _lib.check(self.lib.nmpc_policy_forward(self._h, B, ptr(x), ptr(y), stream(self.device)), self._h,
+                   "nmpc_policy_forward", "policy")
         return y
 
     __call__ = forward
@@ -145,8 +133,8 @@ class DevicePolicy:
         assert x.shape == (B, self.dims[0]) and y.shape == (B, self.dims[1])
         pred = torch.empty(B, self.dims[1], dtype=torch.float32, device=self.device) if return_pred else None
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        self._check(self.lib.nmpc_policy_train_step(self._h, B, _ptr(x), _ptr(y), float(lr), _ptr(loss), _ptr(pred),
-                                                    _stream(self.device)), "nmpc_policy_train_step")
+        _lib.check(self.lib.nmpc_policy_train_step(self._h, B, ptr(x), ptr(y), float(lr), ptr(loss), ptr(pred),
+                                                   stream(self.device)), self._h, "nmpc_policy_train_step", "policy")
         return (loss, pred) if return_pred else loss
 
 
@@ -159,9 +147,8 @@ def weighted_sample(weights: torch.Tensor, num_samples: int, seed: int) -> torch
     n = w.numel()
     scratch = torch.empty(n + n // 2048 + 2, dtype=torch.float64, device=w.device)
     idx = torch.empty(num_samples, dtype=torch.int32, device=w.device)
-    rc = lib.nmpc_weighted_sample(_ptr(w), n, int(num_samples), int(seed) & (2 ** 64 - 1), _ptr(scratch), _ptr(idx), _stream(w.device))
-    if rc:
-        raise _lib.NmpcError(f"nmpc_weighted_sample: {lib.nmpc_policy_last_error(None).decode()}")
+    _lib.check(lib.nmpc_weighted_sample(ptr(w), n, int(num_samples), int(seed) & (2 ** 64 - 1), ptr(scratch), ptr(idx),
+                                        stream(w.device)), None, "nmpc_weighted_sample", "policy")
     return idx
 
 
@@ -171,7 +158,6 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 2
     assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()
     dst = torch.empty(idx.numel(), src.shape[1], dtype=torch.float32, device=src.device)
-    rc = lib.nmpc_gather_rows(_ptr(src), src.shape[0], src.shape[1], _ptr(idx), idx.numel(), _ptr(dst), _stream(src.device))
-    if rc:
-        raise _lib.NmpcError(f"nmpc_gather_rows: {lib.nmpc_policy_last_error(None).decode()}")
+    _lib.check(lib.nmpc_gather_rows(ptr(src), src.shape[0], src.shape[1], ptr(idx), idx.numel(), ptr(dst), stream(src.device)),
+               None, "nmpc_gather_rows", "policy")
     return dst

@@ -46,50 +46,66 @@ def euler_derivative_to_local_angular(ypr_euler, v_euler) -> np.ndarray:
     return M @ np.asarray(v_euler)
 
 
+def _rotate_rpy(rpy, v) -> np.ndarray:
+    """rpy_to_matrix(rpy[b]) @ v[b] for rows rpy, v [B, 3], each component summed left to right
+    R[i,0] v0 + R[i,1] v1 + R[i,2] v2 -- the order of the device's restatement (csrc/nmpc_rollout.hip.inc)."""
+    r, p, y = rpy[:, 0], rpy[:, 1], rpy[:, 2]
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    v0, v1, v2 = v[:, 0], v[:, 1], v[:, 2]
+    return np.stack([cy * cp * v0 + (cy * sp * sr - sy * cr) * v1 + (cy * sp * cr + sy * sr) * v2,
+                     sy * cp * v0 + (sy * sp * sr + cy * cr) * v1 + (sy * sp * cr - cy * sr) * v2,
+                     -sp * v0 + cp * sr * v1 + cp * cr * v2], axis=1)
+
+
 def base_ref_vel_tracking(q, v_des, w_des, base_ref_state, t_horizon: float, nom_height: float,
                           height_offset: float = 0.0, interactive: bool = False
                           ) -> Tuple[np.ndarray, np.ndarray]:
-    """Running and terminal 12-dim base references for velocity tracking.
+    """Running and terminal 12-dim base references for velocity tracking, of one row or of a batch of rows
+    (every argument with a leading batch axis; a row is the same as a batch of one).
 
     q              current configuration, q[:3] position, q[3] yaw
     v_des, w_des   commanded base-frame linear velocity and (.., .., yaw-rate)
-    base_ref_state the controller's integrated reference `base_ref_vel_tracking` (12,)
+    base_ref_state the controller's integrated reference `base_ref_vel_tracking` (12,) or [B, 12]
     Keeps the reference's quantisation (np.round to 2 / 1 decimals, builtin round for yaw)
     and its crossed-bounds np.clip, which make the result what it is.
     """
-    q, v_des, w_des = np.asarray(q, float), np.asarray(v_des, float), np.asarray(w_des, float)
-    ref = np.zeros(12)
-    ref[:2] = np.round(q[:2], 2)
-    ref[2] = nom_height + height_offset
-    ref[3] = round(float(q[3]), 1)
-    v_glob = np.round(rpy_to_matrix(base_ref_state[3:6][::-1]) @ v_des, 1)
-    ref[6:9] = v_glob
-    ref[9:12] = w_des[::-1]
+    one = np.ndim(q) == 1
+    q, v_des, w_des, state = (np.atleast_2d(np.asarray(a, float)) for a in (q, v_des, w_des, base_ref_state))
+    ref = np.zeros((q.shape[0], 12))
+    ref[:, :2] = np.round(q[:, :2], 2)
+    ref[:, 2] = nom_height + height_offset
+    ref[:, 3] = [round(float(y), 1) for y in q[:, 3]]
+    v_glob = np.round(_rotate_rpy(state[:, 5:2:-1], v_des), 1)
+    ref[:, 6:9] = v_glob
+    ref[:, 9:12] = w_des[:, ::-1]
 
     ref_e = ref.copy()
-    ref_e[6:9] = rpy_to_matrix(w_des * t_horizon) @ ref[6:9]
+    ref_e[:, 6:9] = _rotate_rpy(w_des * t_horizon, ref[:, 6:9])
     if interactive:
-        pos_ref, yaw_ref = np.round(q[:3], 2), q[3]
+        pos_ref, yaw_ref = np.round(q[:, :3], 2), q[:, 3]
     else:
-        pos_ref, yaw_ref = base_ref_state[:3], base_ref_state[3]
-    reach = v_glob[:2] * t_horizon
-    ref_e[:2] = np.clip(pos_ref[:2] + reach, -ref[:2] + 1.2 * reach, ref[:2] + 1.2 * reach)
-    yaw_reach = w_des[-1] * t_horizon
-    ref_e[3] = np.clip(yaw_ref + yaw_reach, -yaw_ref + 1.5 * yaw_reach, yaw_ref + 1.5 * yaw_reach)
-    ref[:2] += 0.75 * (ref_e[:2] - ref[:2])
-    ref[3] += 0.75 * (ref_e[3] - ref[3])
-    ref_e[8] = 0.0
-    ref_e[4:6] = 0.0
-    ref[4:6] = 0.0
-    ref_e[10:12] = 0.0
-    return ref, ref_e
+        pos_ref, yaw_ref = state[:, :3], state[:, 3]
+    reach = v_glob[:, :2] * t_horizon
+    ref_e[:, :2] = np.clip(pos_ref[:, :2] + reach, -ref[:, :2] + 1.2 * reach, ref[:, :2] + 1.2 * reach)
+    yaw_reach = w_des[:, 2] * t_horizon
+    ref_e[:, 3] = np.clip(yaw_ref + yaw_reach, -yaw_ref + 1.5 * yaw_reach, yaw_ref + 1.5 * yaw_reach)
+    ref[:, :2] += 0.75 * (ref_e[:, :2] - ref[:, :2])
+    ref[:, 3] += 0.75 * (ref_e[:, 3] - ref[:, 3])
+    ref_e[:, 8] = 0.0
+    ref_e[:, 4:6] = 0.0
+    ref[:, 4:6] = 0.0
+    ref_e[:, 10:12] = 0.0
+    return (ref[0], ref_e[0]) if one else (ref, ref_e)
 
 
 def increment_base_ref_position(base_ref_state, v_des, w_des, sim_dt: float) -> None:
-    """Integrate the commanded velocity into the stored reference, in place (mpc.py:204-208)."""
-    v_glob = np.round(rpy_to_matrix(base_ref_state[3:6][::-1]) @ np.asarray(v_des, float), 1)
-    base_ref_state[:2] += v_glob[:2] * sim_dt
-    base_ref_state[3] += w_des[-1] * sim_dt
+    """Integrate the commanded velocity into the stored reference, in place (mpc.py:204-208): one row
+    base_ref_state (12,) or a batch [B, 12] with v_des, w_des [B, 3]."""
+    state = base_ref_state if base_ref_state.ndim == 2 else base_ref_state[None]
+    v_des, w_des = (np.atleast_2d(np.asarray(a, float)) for a in (v_des, w_des))
+    v_glob = np.round(_rotate_rpy(state[:, 5:2:-1], v_des), 1)
+    state[:, :2] += v_glob[:, :2] * sim_dt
+    state[:, 3] += w_des[:, 2] * sim_dt
 
 
 def _hermite(t_knots, y, dy, t_query):

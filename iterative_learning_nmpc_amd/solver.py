@@ -20,16 +20,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr, stream
+# the bits of the `failed` tensors that the rollouts return (include/nmpc.h), for the controllers
+from ._lib import (NMPC_ROLLOUT_FLAG_COLLISION, NMPC_ROLLOUT_FLAG_HEIGHT, NMPC_ROLLOUT_FLAG_MASK,  # noqa: F401
+                   NMPC_ROLLOUT_FLAG_PITCH, NMPC_ROLLOUT_FLAG_ROLL, NMPC_ROLLOUT_FLAG_SOLVER,
+                   NMPC_ROLLOUT_FLAG_VEL_TRACKING, NMPC_ROLLOUT_TERM_SHIFT)
 from .profiling import time_fn
 from .workloads import MODEL_DIMS, MP_NAMES
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream_ptr(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class BatchedNmpcSolver:
@@ -105,7 +102,7 @@ class BatchedNmpcSolver:
         if flags is not None:
             self._chk(flags, (self.batch_max,), "flags", torch.int32)
         self._skip_flags = flags
-        _lib.check(self.lib.nmpc_set_skip(self._h, _ptr(flags), int(mask)), self._h, "nmpc_set_skip")
+        _lib.check(self.lib.nmpc_set_skip(self._h, ptr(flags), int(mask)), self._h, "nmpc_set_skip")
 
     def set_ipm(self, mu0=10.0, sigma=0.2, s_min=1.0, gamma=0.995, tau_min=0.1, merit_rho=1e3):
         _lib.check(self.lib.nmpc_set_ipm(self._h, mu0, sigma, s_min, gamma, tau_min, merit_rho),
@@ -146,8 +143,8 @@ class BatchedNmpcSolver:
         B = X.shape[0]
         self._chk(X, (B, self.n_nodes + 1, self.nx), "X")
         self._chk(U, (B, self.n_nodes, self.nu), "U")
-        _lib.check(self.lib.nmpc_shift_warm_start(self._h, B, int(shift), _ptr(X), _ptr(U),
-                                                  _stream_ptr(self.device)), self._h, "nmpc_shift_warm_start")
+        _lib.check(self.lib.nmpc_shift_warm_start(self._h, B, int(shift), ptr(X), ptr(U),
+                                                  stream(self.device)), self._h, "nmpc_shift_warm_start")
 
     @time_fn("solve")
     def solve(self, x0, yref, yref_e, params, X, U, status=None, stats=None, shift: int = 0
@@ -172,9 +169,9 @@ class BatchedNmpcSolver:
         self._chk(status, (B,), "status", torch.int32)
         self._chk(stats, (B, 4), "stats")
         _lib.check(self.lib.nmpc_shift_solve_batch(
-            self._h, B, int(shift), _ptr(x0), _ptr(yref), int(per_stage), _ptr(yref_e),
-            _ptr(params) if self.np > 0 else None, _ptr(X), _ptr(U), _ptr(status), _ptr(stats),
-            _stream_ptr(self.device)), self._h, "nmpc_shift_solve_batch")
+            self._h, B, int(shift), ptr(x0), ptr(yref), int(per_stage), ptr(yref_e),
+            ptr(params) if self.np > 0 else None, ptr(X), ptr(U), ptr(status), ptr(stats),
+            stream(self.device)), self._h, "nmpc_shift_solve_batch")
         return X, U, status, stats
 
     def riccati(self, Q, R, q, r, A, Bm, d, dx0):
@@ -188,9 +185,63 @@ class BatchedNmpcSolver:
         for t in (Q, R, q, r, A, Bm, d, dx0):
             assert t.is_contiguous() and t.dtype == torch.float32 and t.device.type == "cuda"
         _lib.check(self.lib.nmpc_riccati_batch(
-            self._h, Bsz, nx, nu, _ptr(Q), _ptr(R), _ptr(q), _ptr(r), _ptr(A), _ptr(Bm), _ptr(d),
-            _ptr(dx0), _ptr(dX), _ptr(dU), _ptr(status), _stream_ptr(self.device)), self._h, "nmpc_riccati_batch")
+            self._h, Bsz, nx, nu, ptr(Q), ptr(R), ptr(q), ptr(r), ptr(A), ptr(Bm), ptr(d),
+            ptr(dx0), ptr(dX), ptr(dU), ptr(status), stream(self.device)), self._h, "nmpc_riccati_batch")
         return dX, dU, status
+
+    # -- device-resident rollouts (include/nmpc.h) ----------------------------------------------
+    def rollout(self, gait, x, v_des, w_des, ref_state, foot_pos, push_force, phase, X, U, status, **cfg):
+        """nmpc_rollout_batch: B = x.shape[0] centroidal rollouts from one call.  cfg: every field of nmpc_rollout_cfg by
+        name; phase: host [n_replans].  x, ref_state, foot_pos, X, U and status are updated in place.
+        Returns (S [B, rows, 19], failed [B] int32: NMPC_ROLLOUT_FLAG_* bits)."""
+        c = _cfg(_lib.NmpcRolloutCfg, cfg)
+        B = x.shape[0]
+        self._chk(gait, (4, c.nodes_per_cycle), "gait", torch.int8)
+        self._chk(x, (B, self.nx), "x")
+        self._chk(foot_pos, (B, 12), "foot_pos")
+        S, failed = self._rollout_io(c, B, v_des, w_des, ref_state, push_force, X, U, status, 19)
+        phase = np.ascontiguousarray(phase, dtype=np.float32)
+        assert phase.shape == (c.n_replans,)
+        _lib.check(self.lib.nmpc_rollout_batch(
+            self._h, B, ctypes.byref(c), ptr(gait), ptr(x), ptr(v_des), ptr(w_des), ptr(ref_state), ptr(foot_pos),
+            ptr(push_force), phase.ctypes.data_as(ctypes.c_void_p), ptr(X), ptr(U), ptr(S), ptr(status), ptr(failed),
+            stream(self.device)), self._h, "nmpc_rollout_batch")
+        return S, failed
+
+    def wb_rollout(self, gait, peaks, nodes, q, v, v_des, w_des, ref_state, joint_ref, push_force, X, U, status, **cfg):
+        """nmpc_wb_rollout_batch: B = q.shape[0] whole-body rollouts from one call.  cfg: every field of
+        nmpc_wb_rollout_cfg by name; nodes: host, the optimisation node of each replan.  q, v, ref_state, X, U and status
+        are updated in place.  Returns (S [B, rows, 44], failed [B] int32: NMPC_ROLLOUT_FLAG_* bits)."""
+        c = _cfg(_lib.NmpcWbRolloutCfg, cfg)
+        B = q.shape[0]
+        for t, name in ((gait, "gait"), (peaks, "peaks")):
+            self._chk(t, (4, c.nodes_per_cycle), name, torch.int8)
+        self._chk(q, (B, 18), "q")
+        self._chk(v, (B, 18), "v")
+        self._chk(joint_ref, (12,), "joint_ref")
+        S, failed = self._rollout_io(c, B, v_des, w_des, ref_state, push_force, X, U, status, 44)
+        assert len(nodes) == c.n_replans
+        nodes = (ctypes.c_int * c.n_replans)(*nodes)
+        _lib.check(self.lib.nmpc_wb_rollout_batch(
+            self._h, B, ctypes.byref(c), ptr(gait), ptr(peaks), ctypes.cast(nodes, ctypes.c_void_p), ptr(q), ptr(v),
+            ptr(v_des), ptr(w_des), ptr(ref_state), ptr(joint_ref), ptr(push_force), ptr(X), ptr(U), ptr(S), ptr(status),
+            ptr(failed), stream(self.device)), self._h, "nmpc_wb_rollout_batch")
+        return S, failed
+
+    def _rollout_io(self, c, B, v_des, w_des, ref_state, push_force, X, U, status, row_width):
+        """checks of the arguments both rollout calls share; the outputs S and failed"""
+        N = self.n_nodes
+        self._chk(v_des, (B, 3), "v_des", torch.float64)
+        self._chk(w_des, (B, 3), "w_des", torch.float64)
+        self._chk(ref_state, (B, 12), "ref_state", torch.float64)
+        if push_force is not None:
+            self._chk(push_force, (B, 3), "push_force")
+        self._chk(X, (B, N + 1, self.nx), "X")
+        self._chk(U, (B, N, self.nu), "U")
+        self._chk(status, (B,), "status", torch.int32)
+        rows = c.n_replans * (c.replanning_steps if c.record_sim_steps else 1)
+        S = torch.empty(B, rows, row_width, dtype=torch.float32, device=self.device)
+        return S, torch.zeros(B, dtype=torch.int32, device=self.device)
 
     def debug_tile(self, b: int, k: int, which: int) -> np.ndarray:
         """16x16 stage tile (row, col) of problem b: 0 A~, 1 B~, 2 K~, 3 Acl~ (test hook)."""
@@ -218,6 +269,15 @@ class BatchedNmpcSolver:
         return int(self.lib.nmpc_workspace_bytes(self._h))
 
 
+def _cfg(struct, fields: dict):
+    """a rollout configuration struct from ALL of its fields by name (array fields from sequences)"""
+    names = [f for f, _ in struct._fields_]
+    if set(fields) != set(names):
+        raise TypeError(f"{struct.__name__}: missing {sorted(set(names) - set(fields))}, "
+                        f"unknown {sorted(set(fields) - set(names))}")
+    return struct(**{f: t(*fields[f]) if issubclass(t, ctypes.Array) else fields[f] for f, t in struct._fields_})
+
+
 def tracking_error(S: torch.Tensor, S_nom: torch.Tensor, threshold: float = 4.0,
                    ood_weight: float = 5.0, with_weights: bool = True):
     """err[b,t] = ||S[b,t,1:] - S_nom[t,1:]||_2 and the OOD sampling weights
@@ -229,6 +289,6 @@ def tracking_error(S: torch.Tensor, S_nom: torch.Tensor, threshold: float = 4.0,
         assert t.is_contiguous() and t.dtype == torch.float32 and t.device.type == "cuda"
     err = torch.empty(B, T, dtype=torch.float32, device=S.device)
     w = torch.empty(B, T, dtype=torch.float32, device=S.device) if with_weights else None
-    _lib.check(lib.nmpc_tracking_error(None, B, T, ns, _ptr(S), _ptr(S_nom), _ptr(err), _ptr(w),
-                                       threshold, ood_weight, _stream_ptr(S.device)), None, "nmpc_tracking_error")
+    _lib.check(lib.nmpc_tracking_error(None, B, T, ns, ptr(S), ptr(S_nom), ptr(err), ptr(w),
+                                       threshold, ood_weight, stream(S.device)), None, "nmpc_tracking_error")
     return (err, w) if with_weights else err

@@ -14,14 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
+from ._lib import ptr, stream
 
 
 class BatchedTorqueLayer:
@@ -45,19 +38,13 @@ class BatchedTorqueLayer:
         m.gravity = (ctypes.c_float * 3)(*[float(g) for g in gravity])
         self._h = ctypes.c_void_p()
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        rc = self.lib.nmpc_torque_create(ctypes.byref(m), idx, ctypes.byref(self._h))
-        if rc:
-            raise _lib.NmpcError(f"nmpc_torque_create: {self.lib.nmpc_torque_last_error(None).decode()}")
+        _lib.check(self.lib.nmpc_torque_create(ctypes.byref(m), idx, ctypes.byref(self._h)), None, "nmpc_torque_create", "torque")
         self.n, self.nu, self.n_feet = n, int(n_actuated), nf
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
             self.lib.nmpc_torque_destroy(h)
-
-    def _check(self, rc, what):
-        if rc:
-            raise _lib.NmpcError(f"{what}: {self.lib.nmpc_torque_last_error(self._h).decode()}")
 
     def _in(self, t, width, name):
         t = torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
@@ -73,8 +60,8 @@ class BatchedTorqueLayer:
         if v.shape[0] != B or a.shape[0] != B or (f is not None and f.shape[0] != B):
             raise ValueError("batch sizes differ")
         tau = torch.empty(B, self.nu, dtype=torch.float32, device=self.device)
-        self._check(self.lib.nmpc_id_torques_batch(self._h, B, _ptr(q), _ptr(v), _ptr(a), _ptr(f), _ptr(tau), _stream(self.device)),
-                    "nmpc_id_torques_batch")
+        _lib.check(self.lib.nmpc_id_torques_batch(self._h, B, ptr(q), ptr(v), ptr(a), ptr(f), ptr(tau), stream(self.device)),
+                   self._h, "nmpc_id_torques_batch", "torque")
         return tau
 
     def compute_pd_torques(self, q, v, torques_ff, q_plan, v_plan, Kp: float, Kd: float) -> torch.Tensor:
@@ -83,8 +70,8 @@ class BatchedTorqueLayer:
         qp = self._in(q_plan, (self.n,), "q_plan"); vp = self._in(v_plan, (self.n,), "v_plan")
         ff = None if torques_ff is None else self._in(torques_ff, (self.nu,), "torques_ff")
         tau = torch.empty(q.shape[0], self.nu, dtype=torch.float32, device=self.device)
-        self._check(self.lib.nmpc_pd_torques_batch(self._h, q.shape[0], _ptr(ff), _ptr(q), _ptr(v), _ptr(qp), _ptr(vp), float(Kp),
-                                                   float(Kd), _ptr(tau), _stream(self.device)), "nmpc_pd_torques_batch")
+        _lib.check(self.lib.nmpc_pd_torques_batch(self._h, q.shape[0], ptr(ff), ptr(q), ptr(v), ptr(qp), ptr(vp), float(Kp),
+                                                  float(Kd), ptr(tau), stream(self.device)), self._h, "nmpc_pd_torques_batch", "torque")
         return tau
 
     def pd_target_action(self, tau, q, v, kp: float = 20.0, kd: float = 1.5, actuator_to_joint: Optional[Sequence[int]] = None):
@@ -94,6 +81,7 @@ class BatchedTorqueLayer:
         if perm is not None and (perm.numel() != self.nu or sorted(perm.tolist()) != list(range(self.nu))):
             raise ValueError("actuator_to_joint must be a permutation of range(nu)")
         out = torch.empty_like(tau)
-        self._check(self.lib.nmpc_pd_target_action_batch(self._h, tau.shape[0], _ptr(tau), _ptr(perm), _ptr(q), _ptr(v), float(kp),
-                                                         float(kd), _ptr(out), _stream(self.device)), "nmpc_pd_target_action_batch")
+        _lib.check(self.lib.nmpc_pd_target_action_batch(self._h, tau.shape[0], ptr(tau), ptr(perm), ptr(q), ptr(v), float(kp),
+                                                        float(kd), ptr(out), stream(self.device)),
+                   self._h, "nmpc_pd_target_action_batch", "torque")
         return out

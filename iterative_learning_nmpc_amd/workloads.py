@@ -113,16 +113,12 @@ def centroidal_trot(B: int = 1024, N: int = 50, seed: int = 0, warm: str = "stan
     fz_share = np.moveaxis(contacts[:, :, :N], 1, 2) * ((-mp[5] * mp[1]) / n_stance)[:, :, None]
     yref = np.zeros((B, N, 24))
     yref[:, :, 14::3] = fz_share
-    yref_e = np.zeros((B, 12))
-    base = np.zeros((B, 12))
-    for b in range(B):
-        q = np.zeros(18)
-        q[:6] = x0[b, :6]
-        ref_state = np.zeros(12)
-        ref_state[:2] = x0[b, :2]
-        ref_state[3] = x0[b, 3]
-        base[b], yref_e[b] = base_ref_vel_tracking(q, v_des[b], np.zeros(3), ref_state, T,
-                                                   gait.nom_height)
+    q = np.zeros((B, 18))
+    q[:, :6] = x0[:, :6]
+    ref_state = np.zeros((B, 12))
+    ref_state[:, :2] = x0[:, :2]
+    ref_state[:, 3] = x0[:, 3]
+    base, yref_e = base_ref_vel_tracking(q, v_des, np.zeros((B, 3)), ref_state, T, gait.nom_height)
     yref[:, :, :12] = base[:, None, :]
     W = np.concatenate([cost.W_base, cost.W_cnt_f_reg.ravel()])
     X = np.repeat(x0[:, None, :], N + 1, axis=1)
@@ -191,7 +187,6 @@ def wholebody_trot(B: int = 8192, N: int = 30, seed: int = 0, sigma_joint: float
     contacts = planner.get_contacts_batch(i_node, N + 1).astype(np.float64)      # [B,4,N+1]
 
     inertia = mp[2:5]
-    from .mpc import base_ref_vel_tracking_batch                 # the vectorised restatement of mpc.py:210-272
     x0 = np.concatenate([q0, v0, wb.centroidal_momentum_batch(q0, v0, mp[1], inertia)], axis=1)
     params = np.zeros((B, N + 1, d["np"]))
     params[:, :, 0:4] = np.moveaxis(contacts, 1, 2)
@@ -205,7 +200,7 @@ def wholebody_trot(B: int = 8192, N: int = 30, seed: int = 0, sigma_joint: float
     ref_state = np.zeros((B, 12))
     ref_state[:, :2] = q0[:, :2]
     ref_state[:, 3] = q0[:, 3]
-    base, base_e = base_ref_vel_tracking_batch(q0, v_des, np.zeros((B, 3)), ref_state, T, gait.nom_height)
+    base, base_e = base_ref_vel_tracking(q0, v_des, np.zeros((B, 3)), ref_state, T, gait.nom_height)
     yref = np.zeros((B, N, d["ny"]))
     yref_e = np.zeros((B, d["ny_e"]))
     yref[:, :, 0:12] = base[:, None, :]

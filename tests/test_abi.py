@@ -28,6 +28,16 @@ def test_header_symbols_are_exported_and_bound(lib):
         assert getattr(lib, name) is not None
 
 
+def test_header_constants_are_mirrored():
+    """every NMPC_ROLLOUT_* and NMPC_STATUS_* #define of include/nmpc.h has its value under its own name in _lib"""
+    from iterative_learning_nmpc_amd import _lib
+    header = open(os.path.join(ROOT, "include", "nmpc.h")).read()
+    defines = dict(re.findall(r"^#define\s+(NMPC_(?:ROLLOUT|STATUS)_\w+)\s+(\w+)", header, re.M))
+    assert len(defines) == 14, sorted(defines)
+    for name, value in defines.items():
+        assert getattr(_lib, name, None) == int(value, 0), name
+
+
 def test_model_dims(lib):
     v = [ctypes.c_int() for _ in range(4)]
     assert lib.nmpc_model_dims(1, *[ctypes.byref(x) for x in v]) == 0

@@ -113,6 +113,27 @@ def test_base_references(golden_dir):
     assert ref[6] == 0.2
 
 
+def test_base_references_of_a_batch_are_the_per_row_references():
+    """One implementation for a row and for a batch: the batched base references and reference increment are the per-row
+    calls bit for bit, on random states with non-zero yaw rates (which rotate the terminal velocity)."""
+    rng = np.random.default_rng(7)
+    B = 400
+    q, state = rng.normal(0, 1, (B, 18)), rng.normal(0, 0.5, (B, 12))
+    v_des, w_des = rng.uniform(-0.5, 0.5, (B, 3)), rng.uniform(-1, 1, (B, 3))
+    for interactive in (False, True):
+        ref, ref_e = refs.base_ref_vel_tracking(q, v_des, w_des, state, 1.0, 0.30, 0.02, interactive)
+        assert ref.shape == ref_e.shape == (B, 12)
+        for b in range(B):
+            r, r_e = refs.base_ref_vel_tracking(q[b], v_des[b], w_des[b], state[b], 1.0, 0.30, 0.02, interactive)
+            assert r.tobytes() == ref[b].tobytes() and r_e.tobytes() == ref_e[b].tobytes(), (interactive, b)
+    batch = state.copy()
+    refs.increment_base_ref_position(batch, v_des, w_des, 1.0e-3)
+    for b in range(B):
+        row = state[b].copy()
+        refs.increment_base_ref_position(row, v_des[b], w_des[b], 1.0e-3)
+        assert row.tobytes() == batch[b].tobytes(), b
+
+
 def test_hermite_upsampling(golden_dir):
     g = _load(golden_dir, "references.npz")
     for name in ("a", "b", "c"):
