@@ -283,6 +283,19 @@ int nmpc_wb_rollout_batch(void *handle, int B, const nmpc_wb_rollout_cfg *cfg, c
                           const double *w_des, double *ref_state, const float *joint_ref, const float *push_force,
                           float *X, float *U, float *S, int *status, int *failed, void *stream);
 
+/* Action labels beside the rows of nmpc_wb_rollout_batch.  While A (dev [B][n_rows][12], n_rows as S) is attached, every
+ * following nmpc_wb_rollout_batch of this handle calls nmpc_plan_actions_batch (include/nmpc_torque.h) once per replan,
+ * after the solve and before the plan is followed, on that replan's X, U: rows row0 .. row0 + replanning_steps of A are the
+ * actions that go with the same rows of S.  torque_handle: of nmpc_torque_create, same device, the 18-joint / 12-actuated /
+ * 4-foot tree; zoh: dev int [replanning_steps], the hold index of each step (LocomotionMPC.id_repeat); kp, kd: gains of
+ * the recorded PD target.  A rollout terminated before a replan gets its last written label row repeated (zeros if it has
+ * none); the replan in which it terminates still gets computed labels, as it gets computed rows.  A solver failure leaves
+ * what the arithmetic gives: validity is failed[b]'s to say.  The pointers are read when the rollout runs; the caller
+ * keeps them alive.  A = NULL detaches; with nothing attached the launches of a rollout are exactly what they are without
+ * this call.  A rollout with labels attached needs cfg.record_sim_steps = 1 and arguments nmpc_plan_actions_batch
+ * accepts, otherwise it returns NMPC_E_ARG and launches nothing. */
+int nmpc_wb_rollout_set_actions(void *handle, void *torque_handle, const int *zoh, float kp, float kd, float *A);
+
 /* Problems to leave out of the following *_batch solves of this handle: flags dev int[B_max] (or NULL: none); a problem
  * with flags[b] & mask != 0 is skipped by every kernel -- its X, U, status, stats stay as they are and it costs no
  * time.  The flags are read when the kernels run (stream order), so the caller may update them between calls without

@@ -66,6 +66,28 @@ int nmpc_pd_torques_batch(void *handle, int B, const float *tau_ff, const float 
 int nmpc_pd_target_action_batch(void *handle, int B, const float *tau, const int *perm, const float *q,
                                 const float *v, float kp, float kd, float *action, void *stream);
 
+/* The action labels of one plan of the whole-body model: for rollout b and step j (0 <= j < n_steps) the recorded action
+ * (RolloutMPC.py:228-250) of the expert's torque at simulation step j of the interval that follows the replan,
+ *     A[b][j][i] = (tau[perm[i]] + kd v[6 + i]) / kp + q[6 + i],   tau = id_torques(q, v, a, f)          (mpc.py:583)
+ *   q, v   the plan at t = (j + 1) sim_dt on the cubic Hermite segments of interpolate_trajectory_with_derivatives
+ *          (mpc.py:388-414; fp64 from the fp32 plan, velocities through (v_k, a_max(k-1,0))) -- the expressions, in one
+ *          shared device function, with which the device rollouts record state row j, so a label sits on the state of its row;
+ *   a, f   U[b][zoh[j]]: accelerations U[..][0..18), world-frame foot forces U[..][18..30) as [foot][3] -- the zero-order hold
+ *          a_plan = a_sol[id_repeat], f_plan = f_sol[id_repeat] (mpc.py:142), indexed with the same j as the state, as
+ *          mpc.py:583 does with plan_step.  zoh: dev int [n_steps], filled by the host from id_repeat (entries are clamped to [0, N)).
+ * The plant follows the plan, so the reference's PD term Kp (q_plan - q) + Kd (v_plan - v) (mpc.py:592-599) is zero [decl] and
+ * tau is the inverse-dynamics torque alone; it comes out in joint order [FL, FR, RL, RR], so perm (dev [12], as
+ * nmpc_pd_target_action_batch) is NULL unless the caller wants another order.
+ * X [B][N+1][42], U [B][N][30]: trajectories of NMPC_MODEL_WHOLEBODY with node spacing dt_nodes; skip: dev int [B] or NULL, a
+ * rollout with skip[b] & skip_mask != 0 is left out (its rows of A stay as they are, it costs no time; read in stream order);
+ * A: dev, rollout b's rows start at A + b * a_rows * 12 and the first n_steps of them are written (a_rows >= n_steps; a
+ * dense [B][n_steps][12] has a_rows = n_steps).  One thread per (rollout, step).
+ * NMPC_E_ARG (text in nmpc_torque_last_error): a tree that is not 18 joints / 12 actuated / 4 feet, n_steps < 1, zoh NULL,
+ * kp = 0, n_steps sim_dt beyond the horizon. */
+int nmpc_plan_actions_batch(void *handle, int B, int n_steps, int N, const float *X, const float *U, const int *zoh,
+                            double dt_nodes, double sim_dt, float kp, float kd, const int *perm, const int *skip,
+                            int skip_mask, float *A, int a_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@ SIGNATURES = {
     "nmpc_set_opts": (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_int]),
     "nmpc_set_contact_patterns": (c_int, [c_void_p, c_int]),
     "nmpc_set_skip": (c_int, [c_void_p, c_void_p, c_int]),
+    "nmpc_wb_rollout_set_actions": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p]),
     "nmpc_set_ipm": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float]),
     "nmpc_shift_warm_start": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "nmpc_solve_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -80,6 +81,8 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     "nmpc_pd_target_action_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                             c_void_p, c_void_p]),
+    "nmpc_plan_actions_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_double,
+                                        ctypes.c_double, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "nmpc_debug_read_tile": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float)]),
     "nmpc_debug_set_buffer": (c_int, [c_void_p, c_void_p]),
     "nmpc_debug_read_workspace": (c_int, [c_void_p, c_int, c_size_t, c_size_t, POINTER(c_float)]),

@@ -1,0 +1,50 @@
+"""Rollouts -> database, on the device: the data-collection step of one learning iteration.
+
+The reference rolls the expert out, records (state, goal, action) per simulation step (DAgger/utils/RolloutMPC.py:168-258),
+drops the rollouts that ended early (RolloutMPC.py:424-437) and appends the rest to its database
+(DAgger/utils/database.py:105-154); the out-of-distribution rule then weights what the training step samples
+(Behavior_Cloning/utils/data_collection_force_perturbation.py:138-156).  Here the rollouts are one `open_loop_device`
+with the action labels recorded beside the state rows, and the rows go from that call's buffers into the
+`DeviceDatabase` tables without passing through the host."""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .config import TERMINATE_DEFAULT
+from .parallel import learning_update, ood_threshold
+from .solver import tracking_error
+from .trajectory_io import KD, KP
+
+
+def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = None, nominal: int = 0, ood_weight: float = 5.0,
+                     terminate_mask: int = TERMINATE_DEFAULT, kp: float = KP, kd: float = KD):
+    """One batch of whole-body expert rollouts of `T` seconds into `db`.
+
+    mpc: a `LocomotionMPC` (batch B, command set); layer: the robot's `BatchedTorqueLayer`; db: a `DeviceDatabase` with
+    44-slot states and 12-slot actions; rollout `nominal` is the unperturbed one the others are measured against.
+    Rows of the valid rollouts -- those that no bit of `terminate_mask` ended -- are appended in rollout order with the goal
+    the recorder stores (the commanded v_des, one copy per row).  Returns (err [B, K] tracking errors against the nominal
+    rollout on the reference's own 44-slot row and its own threshold 4.0, weights [B, K] of
+    `parallel.learning_update`: 0 on invalid rollouts, `ood_weight` where err > 4.0, else 1; rows appended).
+    After the call `mpc.actions`, `mpc.failed` and the returned S of the rollout are as `open_loop_device` leaves them
+    (`mpc.states` keeps S)."""
+    S = mpc.open_loop_device(q0, v0, T, push=push, record_sim_steps=True, terminate_mask=terminate_mask, torque_layer=layer,
+                             kp=kp, kd=kd).contiguous()
+    A = mpc.actions
+    mpc.states = S
+    B, K = S.shape[:2]
+    threshold = ood_threshold(S.shape[2])                     # 4.0 on the 44-slot row: the reference's number, no mapping
+    err, _ = tracking_error(S, S[nominal].contiguous(), threshold=threshold, ood_weight=ood_weight)
+    valid = (mpc.failed & int(terminate_mask)) == 0
+    _, weights = learning_update(err, threshold, ood_weight, valid)
+    keep = torch.nonzero(valid).squeeze(1)                    # device index of the valid rollouts, in rollout order
+    n_rows = int(keep.numel()) * K
+    if n_rows:
+        # the goal the recorder stores with every row (trajectory_io.TrajectoryRecorder.vc_goals): the rollout's commanded v_des
+        goals = torch.as_tensor(np.broadcast_to(np.asarray(mpc.v_des, float), (B, 3)).copy(), dtype=torch.float32).to(S.device)
+        db.append(S[keep].reshape(n_rows, S.shape[2]), A[keep].reshape(n_rows, A.shape[2]),
+                  goals[keep].repeat_interleave(K, dim=0))
+    return err, weights, n_rows

@@ -8,7 +8,9 @@
 #include <cstring>
 #include <string>
 
+#include "../../include/nmpc_torque.h"
 #include "nmpc_device_guard.hpp"
+#include "nmpc_torque_plan.hpp"
 #include "nmpc_solve.hip"
 #include "nmpc_wb.hip"
 #include "nmpc_aux.hip.inc"
@@ -34,6 +36,12 @@ struct Handle {
     int all_patterns = 0;    // nmpc_set_contact_patterns: 1 = kernel with a static stage body per contact pattern
     const int* skip = nullptr;   // nmpc_set_skip: problems with skip[b] & skip_mask != 0 are left out of the solves
     int skip_mask = 0;
+    struct {                     // nmpc_wb_rollout_set_actions: label buffer of the whole-body rollouts (A == nullptr: none)
+        void* torque = nullptr;
+        const int* zoh = nullptr;
+        float kp = 0.0f, kd = 0.0f;
+        float* A = nullptr;
+    } labels;
     bool ws_dirty = false;   // a dense-LQ call left foreign padding in the tile workspace
     bool mp_set = false, w_set = false;
     nmpc::ModelParams mp{};
@@ -366,6 +374,16 @@ int nmpc_set_skip(void* handle, const int* flags, int mask) {
     return NMPC_OK;
 }
 
+int nmpc_wb_rollout_set_actions(void* handle, void* torque_handle, const int* zoh, float kp, float kd, float* A) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    h->labels = {};
+    if (A) {
+        h->labels.torque = torque_handle; h->labels.zoh = zoh; h->labels.kp = kp; h->labels.kd = kd; h->labels.A = A;
+    }
+    return NMPC_OK;
+}
+
 int nmpc_set_ipm(void* handle, float mu0, float sigma, float s_min, float gamma, float tau_min,
                  float merit_rho) {
     Handle* h = static_cast<Handle*>(handle);
@@ -575,6 +593,12 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
     if (cfg->replanning_steps * cfg->sim_dt > cfg->time_horizon) return fail(h, NMPC_E_ARG, "replanning interval longer than the horizon");
     for (int i = 0; i < cfg->n_replans; ++i)
         if (nodes[i] < 0 || (i > 0 && nodes[i] < nodes[i - 1])) return fail(h, NMPC_E_ARG, "nodes must be non-negative and non-decreasing");
+    const auto& lab = h->labels;
+    if (lab.A) {
+        if (!cfg->record_sim_steps) return fail(h, NMPC_E_ARG, "action labels go with rows per simulation step: record_sim_steps must be 1");
+        if (const char* why = nmpc_torque::plan_actions_refusal(lab.torque, cfg->replanning_steps, lab.zoh, lab.kp, h->device))
+            return fail(h, NMPC_E_ARG, std::string("action labels: ") + why);
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     nmpc::DeviceGuard guard(h->device);
     HIP_TRY(h, guard.err);
@@ -624,6 +648,15 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
         w.nlp_tol = cold ? cfg->nlp_tol_first : cfg->nlp_tol;
         const int rc = launch_wb(h, w, st);
         if (rc) return rc;
+        if (lab.A) {            // the labels of this replan's plan, beside the rows the advance kernel is about to record
+            const int steps = cfg->replanning_steps;
+            const int lrc = nmpc_plan_actions_batch(lab.torque, B, steps, N, X, U, lab.zoh, r.dt_nodes, r.sim_dt, lab.kp, lab.kd, nullptr,
+                                                    r.term_mask ? failed : nullptr, r.term_mask, lab.A + (size_t)r.row0 * 12, r.n_rows, st);
+            if (lrc) return fail(h, lrc, std::string("nmpc_plan_actions_batch: ") + nmpc_torque_last_error(lab.torque));
+            if (r.term_mask)
+                hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_hold_actions_kernel, dim3((unsigned)(((size_t)B * steps * 12 + 255) / 256)),
+                                   dim3(256), 0, st, B, r.n_rows, r.row0, steps, r.term_mask, failed, lab.A);
+        }
         hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, r);
     }
     HIP_TRY(h, hipGetLastError());

@@ -1,7 +1,8 @@
 // nmpc_torque.hip -- the torque layer on gfx950 (C-ABI: include/nmpc_torque.h).
 //
 // Batched recursive Newton-Euler inverse dynamics with external foot forces (dynamics.py:136-163), the PD
-// law around it (mpc.py:592-599) and the recorded PD-target action (RolloutMPC.py:228-250).  One thread
+// law around it (mpc.py:592-599), the recorded PD-target action (RolloutMPC.py:228-250) and the action labels of a whole
+// plan (plan_actions_kernel: one thread per (rollout, simulation step), the same recursion on the sampled plan).  One thread
 // per robot: the recursion over the tree is serial (a body needs its parent), robots are independent, and
 // a batch of rollouts brings thousands of them.  The model is read through wave-uniform (scalar) loads;
 // the per-body quantities the recursion has to keep (velocity, acceleration, world rotation on the way
@@ -19,6 +20,8 @@
 
 #include "../../include/nmpc.h"
 #include "../../include/nmpc_torque.h"
+#include "nmpc_torque_plan.hpp"
+#include "nmpc_wb_plan.hpp"
 
 namespace nmpc_torque {
 
@@ -168,6 +171,144 @@ __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict
     }
 }
 
+// The same recursion for the label kernel below, its inputs behind an accessor: `in` gives the robot's coordinates q(i), v(i),
+// a(i) of joint i, has_f() and f_at(k), the world-frame force at foot k; out(i, act, tau) takes the torque of actuated joint
+// i = n - nu + act on the way back.  Per-body state in the block's LDS slice [joint][SLOTS][TPB], as above.
+// id_torques_kernel above keeps its own text: routed through this function it compiles to other packed / fused products and
+// rounds differently on tilted trees, and its outputs are held bit for bit.  A change to the recursion goes into both.
+template <class In, class Out>
+__device__ __forceinline__ void id_torques_body(const Model& m, const In& in, const Out& out) {
+    extern __shared__ float body[];                       // [joint][SLOTS][TPB]
+    const int n = m.n;
+    auto at = [&](int joint, int slot) -> float& { return body[(joint * SLOTS + slot) * TPB + threadIdx.x]; };
+    auto get3 = [&](int joint, int slot) { return V3{at(joint, slot), at(joint, slot + 1), at(joint, slot + 2)}; };
+    auto put3 = [&](int joint, int slot, V3 x) { at(joint, slot) = x.x; at(joint, slot + 1) = x.y; at(joint, slot + 2) = x.z; };
+
+    // outward: velocities, accelerations (gravity enters as an acceleration of the world), net force and moment
+    for (int i = 0; i < n; ++i) {
+        M3 R; V3 p;
+        joint_transform(m, i, in.q(i), R, p);
+        const int par = m.parent[i];
+        V3 w_p{0, 0, 0}, vo_p{0, 0, 0}, dw_p{0, 0, 0}, dvo_p{-m.gravity[0], -m.gravity[1], -m.gravity[2]};
+        M3 Rw = R;
+        if (par >= 0) {
+            w_p = get3(par, 0); vo_p = get3(par, 3); dw_p = get3(par, 6); dvo_p = get3(par, 9);
+            M3 Rp;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, 12 + k);
+            Rw = mul(Rp, R);
+        }
+        V3 w = mul_t(R, w_p), vo = mul_t(R, vo_p + cross(w_p, p));
+        V3 dw = mul_t(R, dw_p), dvo = mul_t(R, dvo_p + cross(dw_p, p));
+        const V3 ax = v3(m.axis[i]);
+        const float qd = in.v(i), qdd = in.a(i);
+        if (m.type[i] == 0) {          // S = (axis; 0):  a += S qdd + v x (S qd)
+            dw = dw + qdd * ax + cross(w, qd * ax);
+            dvo = dvo + cross(vo, qd * ax);
+            w = w + qd * ax;
+        } else {                       // S = (0; axis)
+            dvo = dvo + qdd * ax + cross(w, qd * ax);
+            vo = vo + qd * ax;
+        }
+        put3(i, 0, w); put3(i, 3, vo); put3(i, 6, dw); put3(i, 9, dvo);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) at(i, 12 + k) = Rw.m[k];
+        // f = I a + v x* (I v) with the spatial inertia about the body origin
+        const float mass = m.mass[i];
+        const V3 c = v3(m.com[i]);
+        const float* I = m.inertia[i];
+        auto inertia = [&](V3 x) { return V3{I[0] * x.x + I[1] * x.y + I[2] * x.z, I[1] * x.x + I[3] * x.y + I[4] * x.z, I[2] * x.x + I[4] * x.y + I[5] * x.z}; };
+        const V3 h_l = mass * (vo + cross(w, c)), h_n = inertia(w) + cross(c, h_l);
+        const V3 g_l = mass * (dvo + cross(dw, c)), g_n = inertia(dw) + cross(c, g_l);
+        put3(i, 21, g_n + cross(w, h_n) + cross(vo, h_l));      // moment about the body origin
+        put3(i, 24, g_l + cross(w, h_l));                       // force
+    }
+    // contact forces: world-frame force at the foot point of its body (= - J^T f, dynamics.py:158-161)
+    if (in.has_f()) {
+        for (int k = 0; k < m.nf; ++k) {
+            const int j = m.foot_joint[k];
+            M3 Rw;
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Rw.m[e] = at(j, 12 + e);
+            const V3 l = mul_t(Rw, in.f_at(k));
+            put3(j, 24, get3(j, 24) - l);
+            put3(j, 21, get3(j, 21) - cross(v3(m.foot_offset[k]), l));
+        }
+    }
+    // inward: joint torques, forces handed to the parents
+    for (int i = n - 1; i >= 0; --i) {
+        const V3 fn = get3(i, 21), fl = get3(i, 24);
+        const int act = i - (n - m.nu);
+        if (act >= 0) out(i, act, dot(v3(m.axis[i]), m.type[i] == 0 ? fn : fl));
+        const int par = m.parent[i];
+        if (par >= 0) {
+            M3 R; V3 p;
+            joint_transform(m, i, in.q(i), R, p);
+            const V3 l_p = mul(R, fl);
+            put3(par, 24, get3(par, 24) + l_p);
+            put3(par, 21, get3(par, 21) + mul(R, fn) + cross(p, l_p));
+        }
+    }
+}
+
+// The labels of one plan: thread (b, j) samples rollout b's plan at t = (j + 1) sim_dt (nmpc_wb_plan.hpp, the advance kernel's
+// own sampling), holds a, f of node zoh[j], runs the recursion above on them and writes the PD target that reproduces the
+// torque.  The coordinates are evaluated where the recursion asks for them (a Hermite sample is per coordinate), so nothing
+// of q, v, a, f goes through memory or through run-time indexed registers.  tau, q_j, v_j wait in slots 0..2 of their joint
+// (free on the way back) for the actuator permutation.
+struct PlanArgs {
+    int B, n_steps, N, a_rows, skip_mask;
+    double dt_nodes, sim_dt;
+    float kp, kd;
+    const float *X, *U;
+    const int *zoh, *perm, *skip;
+    float* A;
+};
+
+struct PlanIn {
+    nmpc::wb::PlanSample c;
+    const float *Xb, *Ub, *ub;                             // the rollout's plan; ub = U[zoh[j]]
+    __device__ __forceinline__ void qv(int i, float& q, float& v) const {
+        double qd, vd;
+        nmpc::wb::wb_plan_component(c, Xb, Ub, i, qd, vd);
+        q = (float)qd; v = (float)vd;
+    }
+    __device__ __forceinline__ float q(int i) const { float q, v; qv(i, q, v); return q; }
+    __device__ __forceinline__ float v(int i) const { float q, v; qv(i, q, v); return v; }
+    __device__ __forceinline__ float a(int i) const { return ub[nmpc::wb::WA + i]; }
+    __device__ __forceinline__ bool has_f() const { return true; }
+    __device__ __forceinline__ V3 f_at(int k) const { return v3(ub + nmpc::wb::WF + 3 * k); }
+};
+
+__global__ __launch_bounds__(TPB) void plan_actions_kernel(const Model* __restrict__ mp, const PlanArgs p) {
+    extern __shared__ float body[];                       // [joint][SLOTS][TPB]
+    const Model& m = *mp;
+    const size_t e = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (e >= (size_t)p.B * p.n_steps) return;
+    const size_t b = e / p.n_steps;
+    const int j = (int)(e - b * p.n_steps);
+    if (p.skip && (p.skip[b] & p.skip_mask)) return;
+    int hold = p.zoh[j];
+    hold = hold < 0 ? 0 : (hold > p.N - 1 ? p.N - 1 : hold);
+    PlanIn in;
+    in.c = nmpc::wb::wb_plan_sample((j + 1) * p.sim_dt, p.dt_nodes, p.N);
+    in.Xb = p.X + b * (p.N + 1) * nmpc::wb::NX;
+    in.Ub = p.U + b * p.N * nmpc::wb::NU;
+    in.ub = in.Ub + (size_t)hold * nmpc::wb::NU;
+    auto at = [&](int joint, int slot) -> float& { return body[(joint * SLOTS + slot) * TPB + threadIdx.x]; };
+    id_torques_body(m, in, [&](int i, int, float t) {
+        at(i, 0) = t;
+        in.qv(i, at(i, 1), at(i, 2));
+    });
+    const int n = m.n, nu = m.nu;
+    float* Ab = p.A + (b * p.a_rows + j) * nu;
+    for (int i = 0; i < nu; ++i) {
+        int src = p.perm ? p.perm[i] : i;
+        src = src < 0 ? 0 : (src >= nu ? nu - 1 : src);
+        Ab[i] = (at(n - nu + src, 0) + p.kd * at(n - nu + i, 2)) / p.kp + at(n - nu + i, 1);
+    }
+}
+
 __global__ void pd_torques_kernel(int B, int n, int nu, const float* __restrict__ tau_ff, const float* __restrict__ q,
                                   const float* __restrict__ v, const float* __restrict__ q_plan, const float* __restrict__ v_plan,
                                   float kp, float kd, float* __restrict__ tau) {
@@ -212,6 +353,18 @@ int tfail(Torque* t, int code, const std::string& msg) {
 }
 
 }  // namespace
+
+const char* nmpc_torque::plan_actions_refusal(void* handle, int n_steps, const int* zoh, float kp, int device) {
+    const Torque* t = static_cast<const Torque*>(handle);
+    if (!t) return "null torque handle";
+    if (t->host.n != 18 || t->host.nu != 12 || t->host.nf != 4)
+        return "plan labels need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4";
+    if (n_steps < 1) return "n_steps must be at least 1";
+    if (!zoh) return "zoh is NULL";
+    if (!(kp != 0.0f)) return "kp must not be zero";
+    if (device >= 0 && t->device != device) return "the torque handle lives on another device";
+    return nullptr;
+}
 
 extern "C" {
 
@@ -315,6 +468,29 @@ int nmpc_pd_target_action_batch(void* handle, int B, const float* tau, const int
     const size_t n = (size_t)B * t->host.nu;
     hipLaunchKernelGGL(pd_target_action_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        B, t->host.n, t->host.nu, tau, perm, q, v, kp, kd, action);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NMPC_OK : tfail(t, NMPC_E_HIP, hipGetErrorString(e));
+}
+
+int nmpc_plan_actions_batch(void* handle, int B, int n_steps, int N, const float* X, const float* U, const int* zoh, double dt_nodes,
+                            double sim_dt, float kp, float kd, const int* perm, const int* skip, int skip_mask, float* A, int a_rows,
+                            void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return tfail(nullptr, NMPC_E_ARG, "null handle");
+    if (const char* why = plan_actions_refusal(handle, n_steps, zoh, kp, -1)) return tfail(t, NMPC_E_ARG, why);
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || N < 1 || !X || !U || !A) return tfail(t, NMPC_E_ARG, "need B >= 0, N >= 1 and X, U, A");
+    if (a_rows < n_steps) return tfail(t, NMPC_E_ARG, "a_rows must be at least n_steps");
+    if (!(dt_nodes > 0.0) || !(sim_dt > 0.0) || n_steps * sim_dt > N * dt_nodes * (1.0 + 1e-9))
+        return tfail(t, NMPC_E_ARG, "need dt_nodes > 0, sim_dt > 0 and n_steps sim_dt within the horizon N dt_nodes");
+    nmpc::DeviceGuard guard(t->device);
+    PlanArgs p{};
+    p.B = B; p.n_steps = n_steps; p.N = N; p.a_rows = a_rows; p.skip_mask = skip ? skip_mask : 0;
+    p.dt_nodes = dt_nodes; p.sim_dt = sim_dt; p.kp = kp; p.kd = kd;
+    p.X = X; p.U = U; p.zoh = zoh; p.perm = perm; p.skip = p.skip_mask ? skip : nullptr; p.A = A;
+    const size_t pairs = (size_t)B * n_steps, lds = (size_t)t->host.n * SLOTS * TPB * sizeof(float);
+    hipLaunchKernelGGL(plan_actions_kernel, dim3((unsigned)((pairs + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream),
+                       t->dev, p);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? NMPC_OK : tfail(t, NMPC_E_HIP, hipGetErrorString(e));
 }

@@ -17,6 +17,8 @@
 //                                    reference integration (mpc.py:204-208)
 // Included by nmpc_api.hip after nmpc_rollout.hip.inc (shares its fp64 helpers).
 
+#include "nmpc_wb_plan.hpp"
+
 #pragma clang fp contract(off)
 
 namespace nmpc {
@@ -216,22 +218,8 @@ __global__ void nmpc_wb_rollout_advance_kernel(const WbRolloutArgs a) {
     }
     const int st = a.status[b];
     if (st == NMPC_STATUS_NAN || st == NMPC_STATUS_QP) flags |= NMPC_ROLLOUT_FLAG_SOLVER;
-    // the plan at time t of the horizon: positions on Hermite segments through (q_k, v_k), velocities through (v_k, a'_k) with
-    // a'_k = a_{max(k-1, 0)} (the reference prepends the first acceleration row, mpc.py:409-410)
-    auto plan_at = [&](double t, double (&q)[18], double (&v)[18]) {
-        int k = (int)floor(t / a.dt_nodes + 1e-9);
-        if (k > N - 1) k = N - 1;
-        const double h = a.dt_nodes, s = (t - k * h) / h;
-        const double om = 1.0 - s, h00 = (1.0 + 2.0 * s) * om * om, h10 = s * om * om, h01 = s * s * (3.0 - 2.0 * s), h11 = s * s * (s - 1.0);
-        const float* x0 = Xb + (size_t)k * NX;
-        const float* x1 = x0 + NX;
-        const float* a0 = Ub + (size_t)(k > 0 ? k - 1 : 0) * NU;
-        const float* a1 = Ub + (size_t)k * NU;
-        for (int i = 0; i < 18; ++i) {
-            q[i] = h00 * (double)x0[WQ + i] + h10 * h * (double)x0[WV + i] + h01 * (double)x1[WQ + i] + h11 * h * (double)x1[WV + i];
-            v[i] = h00 * (double)x0[WV + i] + h10 * h * (double)a0[WA + i] + h01 * (double)x1[WV + i] + h11 * h * (double)a1[WA + i];
-        }
-    };
+    // the plan at time t of the horizon (nmpc_wb_plan.hpp: the Hermite segments of mpc.py:388-414, shared with the label kernel)
+    auto plan_at = [&](double t, double (&q)[18], double (&v)[18]) { wb_plan_at(Xb, Ub, N, a.dt_nodes, t, q, v); };
     double q[18], v[18];
     if (!a.record_sim_steps) {
         for (int i = 0; i < 18; ++i) { q[i] = qf[i]; v[i] = vf[i]; }
@@ -264,6 +252,18 @@ __global__ void nmpc_wb_rollout_advance_kernel(const WbRolloutArgs a) {
         rs[1] += vy * a.sim_dt;
         rs[3] += wz * a.sim_dt;
     }
+}
+
+// Labels (nmpc_wb_rollout_set_actions) of the rollouts that terminated before this replan: their last written label row,
+// repeated (zeros if they have none) -- what the advance kernel does with their rows of S.  One thread per element.
+__global__ void nmpc_wb_rollout_hold_actions_kernel(int B, int n_rows, int row0, int rows, int term_mask, const int* __restrict__ failed,
+                                                    float* __restrict__ A) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x, per = (size_t)rows * 12;
+    if (e >= (size_t)B * per) return;
+    const size_t b = e / per, r = e - b * per;
+    if (!(failed[b] & term_mask)) return;
+    float* Ab = A + (b * n_rows + row0) * 12;
+    Ab[r] = row0 > 0 ? Ab[(ptrdiff_t)(r % 12) - 12] : 0.0f;
 }
 
 }  // namespace wb

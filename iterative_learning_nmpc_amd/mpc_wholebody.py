@@ -27,6 +27,7 @@ from .config import COLLISION_HEIGHT, N_SQP_FIRST, TERMINATE_DEFAULT, get_quadru
 from .contact_planner import ContactPlanner, RaiberContactPlanner
 from .profiling import print_timings, time_fn
 from .quadruped_solver import QuadrupedAcadosSolver
+from .trajectory_io import KD, KP
 from .references import base_ref_cnt_restricted, base_ref_vel_tracking, hermite_upsample, increment_base_ref_position
 from .workloads import FEET
 
@@ -149,7 +150,7 @@ class LocomotionMPC:
         simulation rate, follow it as if it were the plant.  q0, v0 in the solver's Euler layout.
         Returns q_traj[K(,B),18], one row per simulation step."""
         q, v = np.array(q0, float), np.array(v0, float)
-        sim_time, q_rows, v_rows, time_traj = 0.0, [], [], None
+        sim_time, q_rows, v_rows, a_rows, f_rows, time_traj = 0.0, [], [], [], [], None
         while sim_time <= trajectory_time:
             if sim_time >= (self.current_opt_node + 1) * self.dt_nodes:
                 self.current_opt_node += 1
@@ -170,9 +171,12 @@ class LocomotionMPC:
             q, v = self.q_plan[self.plan_step].copy(), self.v_plan[self.plan_step].copy()
             q_rows.append(q)
             v_rows.append(v)
+            a_rows.append(self.a_plan[..., self.plan_step, :].copy())         # a_plan[plan_step], f_plan[plan_step] (mpc.py:583)
+            f_rows.append(self.f_plan[..., self.plan_step, :, :].copy())
             self._step()
             sim_time = sim_time + self.sim_dt
         self.v_traj = np.stack(v_rows)                       # the velocities that go with the returned rows
+        self.a_traj, self.f_traj = np.stack(a_rows), np.stack(f_rows)   # ... and the held accelerations and forces
         return np.stack(q_rows)
 
     def replan_clock(self, trajectory_time: float):
@@ -210,7 +214,7 @@ class LocomotionMPC:
 
     def open_loop_device(self, q0: np.ndarray, v0: np.ndarray, trajectory_time: float, push: Optional[dict] = None,
                          record_sim_steps: bool = True, terminate_mask: int = TERMINATE_DEFAULT,
-                         collision_height: float = COLLISION_HEIGHT):
+                         collision_height: float = COLLISION_HEIGHT, torque_layer=None, kp: float = KP, kd: float = KD):
         """`open_loop` with the whole rollout on the device (nmpc_wb_rollout_batch): per replan the problem is assembled from
         the plant state by a kernel, solved with the warm-start shift folded in, and the up-sampled plan is followed for
         `replanning_steps` simulation steps -- one host call, no round trip per replan, the whole batch at once.
@@ -218,7 +222,10 @@ class LocomotionMPC:
         runs, or one per replan (the state it starts from) with record_sim_steps=False.  push = {"start", "duration",
         "force": [B, 3]}: velocity impulse F dt / m on the base per replanning interval.  The controller's counters,
         reference and solution views advance as in `open_loop`; `self.failed` holds the NMPC_ROLLOUT_FLAG_* bits,
-        `self.q_final` / `self.v_final` the plant state."""
+        `self.q_final` / `self.v_final` the plant state.
+        torque_layer (a `BatchedTorqueLayer` of the robot; needs rows per simulation step): the expert's action labels are
+        recorded beside the rows -- `self.actions` [B, K, 12] (device), row j = (tau + kd v_j) / kp + q_j of the state in S's
+        row j, tau the inverse-dynamics torque of the plan that row was taken from (`references.plan_rows`)."""
         import torch
         fs = self.solver
         s = fs._device_solver()
@@ -235,19 +242,28 @@ class LocomotionMPC:
             self._X_dev = torch.zeros(B, N + 1, 42, dtype=torch.float32, device=dev)
             self._U_dev = torch.zeros(B, N, 30, dtype=torch.float32, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
-        S, failed = s.wb_rollout(
-            s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
-            nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref), by_rollout(push["force"]) if push else None,
-            self._X_dev, self._U_dev, status,
-            n_replans=n_replans, replanning_steps=self.replanning_steps, nodes_per_cycle=self.contact_planner.nodes_per_cycle,
-            first_solve=int(self.first_solve), last_node=int(fs.last_node), max_sqp_first=N_SQP_FIRST,
-            nlp_tol_first=cfg_o.nlp_tol / 10.0, nlp_tol=cfg_o.nlp_tol, sim_dt=self.sim_dt, time_horizon=cfg_o.time_horizon,
-            nom_height=self.config_gait.nom_height, height_offset=self.height_offset,
-            step_height=float(self.config_gait.step_height), push_start=float(push["start"]) if push else 0.0,
-            push_duration=float(push["duration"]) if push else 0.0, record_sim_steps=int(record_sim_steps),
-            force_reference_gravity=int(fs.force_reference == "gravity_share"),
-            nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
-            collision_height=float(collision_height))
+        A = None
+        if torque_layer is not None:
+            rows = n_replans * (self.replanning_steps if record_sim_steps else 1)
+            A = torch.zeros(B, rows, 12, dtype=torch.float32, device=dev)
+            s.set_rollout_actions(torque_layer, s.to_device(self.id_repeat[:self.replanning_steps], torch.int32), A, kp, kd)
+        try:
+            S, failed = s.wb_rollout(
+                s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
+                nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref), by_rollout(push["force"]) if push else None,
+                self._X_dev, self._U_dev, status,
+                n_replans=n_replans, replanning_steps=self.replanning_steps, nodes_per_cycle=self.contact_planner.nodes_per_cycle,
+                first_solve=int(self.first_solve), last_node=int(fs.last_node), max_sqp_first=N_SQP_FIRST,
+                nlp_tol_first=cfg_o.nlp_tol / 10.0, nlp_tol=cfg_o.nlp_tol, sim_dt=self.sim_dt, time_horizon=cfg_o.time_horizon,
+                nom_height=self.config_gait.nom_height, height_offset=self.height_offset,
+                step_height=float(self.config_gait.step_height), push_start=float(push["start"]) if push else 0.0,
+                push_duration=float(push["duration"]) if push else 0.0, record_sim_steps=int(record_sim_steps),
+                force_reference_gravity=int(fs.force_reference == "gravity_share"),
+                nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
+                collision_height=float(collision_height))
+        finally:
+            if torque_layer is not None:
+                s.set_rollout_actions(None)
         # bookkeeping as open_loop leaves it
         self.first_solve = False
         self.sim_step += steps
@@ -258,6 +274,8 @@ class LocomotionMPC:
         self.base_ref_vel_tracking = ref if self.batch > 1 else ref[0]
         self.failed, self.status_dev = failed, status
         self.q_final, self.v_final = q, v
+        if A is not None:
+            self.actions = A[:, :steps]
         fs.parse_sol(self._X_dev.cpu().numpy().astype(np.float64), self._U_dev.cpu().numpy().astype(np.float64))
         return S[:, :steps] if record_sim_steps else S
 

@@ -8,6 +8,7 @@ Restates (numerically identical, golden vectors in tests/golden/):
   increment_base_ref_position           mpc.py:204-208
   hermite_upsample                      interpolate_trajectory_with_derivatives, mpc.py:388-414
   zero_order_hold_index                 id_repeat, mpc.py:142
+  plan_rows                             what the plant and mpc.py:583 read of a plan at each simulation step [decl: device clock]
   base_ref_cnt_restricted               LocomotionMPC.compute_base_ref_cnt_restricted, mpc.py:274-315
 """
 from __future__ import annotations
@@ -138,6 +139,34 @@ def hermite_upsample(time_traj, positions, velocities, accelerations, n_interp: 
 def zero_order_hold_index(n_interp: int, n_nodes: int) -> np.ndarray:
     """Node index held at each interpolated sample (mpc.py:142)."""
     return np.int32(np.linspace(0, 1, n_interp) * (n_nodes - 1))
+
+
+def plan_rows(X, U, zoh, dt_nodes: float, sim_dt: float):
+    """Row j of a whole-body plan, j = 0 .. len(zoh) - 1: the declared meaning of "the plan at simulation step j of the interval
+    after a replan", in fp64.  X [.., N+1, 42] = [q(18), v(18), h(6)] and U [.., N, 30] = [a(18), f(4x3)] per node, nodes
+    dt_nodes apart.  Returns (q [.., n, 18], v [.., n, 18], a [.., n, 18], f [.., n, 4, 3]):
+      q, v   the plan at t = (j + 1) sim_dt on the cubic Hermite segments of `hermite_upsample` (mpc.py:388-414; velocities
+             through (v_k, a_max(k-1,0))), the segment chosen as the device rollouts choose it (k = floor(t / dt_nodes + 1e-9));
+      a, f   of node zoh[j]: the zero-order hold a_sol[id_repeat], f_sol[id_repeat] (mpc.py:142), indexed with the same j
+             (mpc.py:583 reads q_plan, v_plan, a_plan, f_plan at one plan_step).
+    With dt_nodes N = the horizon and n_interp sim_dt = the horizon these are `hermite_upsample(..)[1:n + 1]` and
+    `np.take(.., id_repeat[:n])` to rounding; where the configured dt_nodes is rounded (N = 30: 0.0333) the host loop's
+    linspace samples drift from (j + 1) sim_dt and this function follows the device's clock [decl]."""
+    X, U, zoh = np.asarray(X, float), np.asarray(U, float), np.asarray(zoh)
+    N, n = U.shape[-2], len(zoh)
+    if X.shape[-2:] != (N + 1, 42) or U.shape[-1] != 30 or zoh.ndim != 1 or (n and (zoh.min() < 0 or zoh.max() >= N)):
+        raise ValueError("plan_rows: need X [.., N+1, 42], U [.., N, 30] and hold indices in [0, N)")
+    h = float(dt_nodes)
+    t = (np.arange(n) + 1) * float(sim_dt)
+    k = np.minimum(np.floor(t / h + 1e-9).astype(int), N - 1)
+    s = ((t - k * h) / h)[:, None]
+    h00, h10, h01, h11 = (1 + 2 * s) * (1 - s) ** 2, s * (1 - s) ** 2, s * s * (3 - 2 * s), s * s * (s - 1)
+    q0, q1, v0, v1 = X[..., k, :18], X[..., k + 1, :18], X[..., k, 18:36], X[..., k + 1, 18:36]
+    a0, a1 = U[..., np.maximum(k - 1, 0), :18], U[..., k, :18]
+    q = h00 * q0 + h10 * h * v0 + h01 * q1 + h11 * h * v1
+    v = h00 * v0 + h10 * h * a0 + h01 * v1 + h11 * h * a1
+    hold = U[..., zoh, :]
+    return q, v, hold[..., :18], hold[..., 18:].reshape(hold.shape[:-1] + (4, 3))
 
 
 def base_ref_cnt_restricted(contact_locations, nom_height: float, height_offset: float = 0.0,

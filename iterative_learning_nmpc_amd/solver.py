@@ -26,6 +26,7 @@ from ._lib import (NMPC_ROLLOUT_FLAG_COLLISION, NMPC_ROLLOUT_FLAG_HEIGHT, NMPC_R
                    NMPC_ROLLOUT_FLAG_PITCH, NMPC_ROLLOUT_FLAG_ROLL, NMPC_ROLLOUT_FLAG_SOLVER,
                    NMPC_ROLLOUT_FLAG_VEL_TRACKING, NMPC_ROLLOUT_TERM_SHIFT)
 from .profiling import time_fn
+from .trajectory_io import KD, KP
 from .workloads import MODEL_DIMS, MP_NAMES
 
 
@@ -103,6 +104,28 @@ class BatchedNmpcSolver:
             self._chk(flags, (self.batch_max,), "flags", torch.int32)
         self._skip_flags = flags
         _lib.check(self.lib.nmpc_set_skip(self._h, ptr(flags), int(mask)), self._h, "nmpc_set_skip")
+
+    def set_rollout_actions(self, layer, zoh: Optional[torch.Tensor] = None, A: Optional[torch.Tensor] = None,
+                            kp: float = KP, kd: float = KD):
+        """nmpc_wb_rollout_set_actions: while A [B, rows, 12] (rows as the S of the rollout) is attached, `wb_rollout` records
+        the expert's action beside every state row -- per replan one `BatchedTorqueLayer.plan_actions` on that replan's plan.
+        layer: the `BatchedTorqueLayer` of the robot; zoh int32 [replanning_steps] on the device: the held node of each step.
+        `set_rollout_actions(None)` detaches.  This object keeps the three alive while they are attached."""
+        if layer is None:
+            self._labels = None
+            _lib.check(self.lib.nmpc_wb_rollout_set_actions(self._h, None, None, 0.0, 0.0, None), self._h, "nmpc_wb_rollout_set_actions")
+            return
+        if not isinstance(A, torch.Tensor) or A.dim() != 3:
+            raise ValueError("A: need a float32 tensor [B, rows, 12] on the GPU")
+        self._chk(A, (A.shape[0], A.shape[1], 12), "A")
+        if not isinstance(zoh, torch.Tensor) or zoh.dim() != 1:
+            raise ValueError("zoh: need an int32 tensor [replanning_steps] on the GPU")
+        self._chk(zoh, (zoh.shape[0],), "zoh", torch.int32)
+        if not bool(((zoh >= 0) & (zoh < self.n_nodes)).all()):
+            raise ValueError(f"zoh: node indices must lie in [0, {self.n_nodes})")
+        self._labels = (layer, zoh, A)
+        _lib.check(self.lib.nmpc_wb_rollout_set_actions(self._h, layer._h, ptr(zoh), float(kp), float(kd), ptr(A)),
+                   self._h, "nmpc_wb_rollout_set_actions")
 
     def set_ipm(self, mu0=10.0, sigma=0.2, s_min=1.0, gamma=0.995, tau_min=0.1, merit_rho=1e3):
         _lib.check(self.lib.nmpc_set_ipm(self._h, mu0, sigma, s_min, gamma, tau_min, merit_rho),
@@ -221,6 +244,11 @@ class BatchedNmpcSolver:
         self._chk(joint_ref, (12,), "joint_ref")
         S, failed = self._rollout_io(c, B, v_des, w_des, ref_state, push_force, X, U, status, 44)
         assert len(nodes) == c.n_replans
+        if getattr(self, "_labels", None) is not None:           # the attached label buffer must be this rollout's size
+            _, zoh, A = self._labels
+            self._chk(A, (B, S.shape[1], 12), "A (set_rollout_actions)")
+            if c.record_sim_steps:
+                self._chk(zoh, (c.replanning_steps,), "zoh (set_rollout_actions)", torch.int32)
         nodes = (ctypes.c_int * c.n_replans)(*nodes)
         _lib.check(self.lib.nmpc_wb_rollout_batch(
             self._h, B, ctypes.byref(c), ptr(gait), ptr(peaks), ctypes.cast(nodes, ctypes.c_void_p), ptr(q), ptr(v),

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr, stream
+from .trajectory_io import KD, KP
 
 
 class BatchedTorqueLayer:
@@ -84,4 +85,37 @@ class BatchedTorqueLayer:
         _lib.check(self.lib.nmpc_pd_target_action_batch(self._h, tau.shape[0], ptr(tau), ptr(perm), ptr(q), ptr(v), float(kp),
                                                         float(kd), ptr(out), stream(self.device)),
                    self._h, "nmpc_pd_target_action_batch", "torque")
+        return out
+
+    def plan_actions(self, X, U, zoh, dt_nodes: float, sim_dt: float, kp: float = KP, kd: float = KD,
+                     actuator_to_joint: Optional[Sequence[int]] = None, skip: Optional[torch.Tensor] = None, skip_mask: int = 0,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """nmpc_plan_actions_batch: the recorded action of every step of the interval that follows a replan.  X [B, N+1, 42],
+        U [B, N, 30]: whole-body plans with node spacing dt_nodes; zoh [n_steps]: the node whose a, f each step holds
+        (`LocomotionMPC.id_repeat[:n_steps]`).  Row j is (id_torques(q, v, a, f) + kd v_j) / kp + q_j with q, v the plan at
+        (j + 1) sim_dt and a, f = U[zoh[j]] -- `references.plan_rows` says which numbers those are.  -> [B, n_steps, 12]
+        (written into `out` if given; rollouts with skip[b] & skip_mask != 0 are left as they are)."""
+        X = torch.as_tensor(X, dtype=torch.float32, device=self.device).contiguous()
+        if X.dim() != 3 or X.shape[1] < 2 or X.shape[2] != 42:
+            raise ValueError(f"X: expected [B, N + 1, 42], got {tuple(X.shape)}")
+        B, N = X.shape[0], X.shape[1] - 1
+        U = self._in(U, (N, 30), "U")
+        if U.shape[0] != B:
+            raise ValueError("batch sizes differ")
+        zoh = torch.as_tensor(zoh, dtype=torch.int32, device=self.device).contiguous()
+        n_steps = zoh.numel()
+        if zoh.dim() != 1 or (n_steps and not bool(((zoh >= 0) & (zoh < N)).all())):
+            raise ValueError(f"zoh: expected node indices [n_steps] in [0, {N})")
+        perm = None if actuator_to_joint is None else torch.as_tensor(list(actuator_to_joint), dtype=torch.int32, device=self.device)
+        if perm is not None and (perm.numel() != self.nu or sorted(perm.tolist()) != list(range(self.nu))):
+            raise ValueError("actuator_to_joint must be a permutation of range(nu)")
+        if skip is not None and (skip.dtype != torch.int32 or tuple(skip.shape) != (B,) or not skip.is_contiguous() or skip.device != X.device):
+            raise ValueError(f"skip: need contiguous int32 ({B},) on {self.device}")
+        if out is None:
+            out = torch.empty(B, n_steps, 12, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (B, n_steps, 12) or not out.is_contiguous() or out.device != X.device:
+            raise ValueError(f"out: need contiguous float32 ({B}, {n_steps}, 12) on {self.device}")
+        _lib.check(self.lib.nmpc_plan_actions_batch(self._h, B, n_steps, N, ptr(X), ptr(U), ptr(zoh), float(dt_nodes), float(sim_dt),
+                                                    float(kp), float(kd), ptr(perm), ptr(skip), int(skip_mask), ptr(out), n_steps,
+                                                    stream(self.device)), self._h, "nmpc_plan_actions_batch", "torque")
         return out
