@@ -66,44 +66,50 @@ int fail(Handle* h, int code, const std::string& msg) {
             return fail(h, NMPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-// the handle's configuration as kernel arguments (pointers and batch size left to the caller)
-nmpc::SolveArgs base_args(const Handle* h) {
-    nmpc::SolveArgs a{};
+// the handle's configuration as kernel arguments (pointers and batch size left to the caller): what both families take ...
+template <class A>
+A handle_args(const Handle* h) {
+    A a{};
     a.mp = h->mp;
     std::memcpy(a.W, h->W, sizeof(a.W));        // the tile-family models have ny <= 32, ny_e <= 16
     std::memcpy(a.We, h->We, sizeof(a.We));
     a.reg = h->reg; a.reg_e = h->reg_e;
+    a.N = h->dims.N;
+    a.max_sqp = h->max_sqp; a.n_ipm = h->n_ipm;
+    a.nlp_tol = h->nlp_tol; a.mu0 = h->mu0; a.sigma = h->sigma; a.s_min = h->s_min;
+    a.gamma = h->gamma; a.tau_min = h->tau_min;
+    a.ws = h->ws;
+    a.skip = h->skip_mask ? h->skip : nullptr; a.skip_mask = h->skip_mask;
+    return a;
+}
+// ... and what each takes alone: the tile family (nmpc_solve.hip)
+nmpc::SolveArgs base_args(const Handle* h) {
+    nmpc::SolveArgs a = handle_args<nmpc::SolveArgs>(h);
     for (int j = 0; j < 16; ++j)
         a.rs_free[j] = (j < h->nu) ? 1.0f / std::sqrt(h->W[h->nx + j] + h->reg) : 1.0f;
-    a.N = h->dims.N;
-    a.max_sqp = h->max_sqp; a.n_ipm = h->n_ipm; a.line_search = h->line_search;
-    a.nlp_tol = h->nlp_tol; a.mu0 = h->mu0; a.sigma = h->sigma; a.s_min = h->s_min;
-    a.gamma = h->gamma; a.tau_min = h->tau_min; a.rho = h->rho;
-    a.ws = h->ws;
+    a.line_search = h->line_search; a.rho = h->rho;
     a.dbg = h->dbg;
-    a.skip = h->skip_mask ? h->skip : nullptr; a.skip_mask = h->skip_mask;
     return a;
 }
 
 template <class M>
 size_t ws_floats_per_problem(int N) { return nmpc::WsLayout<M>(N).stride; }
 
-// whole-body model (nmpc_wb.hip): the handle's configuration as kernel arguments
+// the whole-body model (nmpc_wb.hip)
 nmpc::wb::WbArgs wb_args(const Handle* h) {
-    nmpc::wb::WbArgs a{};
-    a.mp = h->mp;
-    std::memcpy(a.W, h->W, sizeof(a.W));
-    std::memcpy(a.We, h->We, sizeof(a.We));
-    a.reg = h->reg; a.reg_e = h->reg_e;
-    a.N = h->dims.N;
-    a.max_sqp = h->max_sqp; a.n_ipm = h->n_ipm;
+    nmpc::wb::WbArgs a = handle_args<nmpc::wb::WbArgs>(h);
     a.precision = h->dims.precision;
     a.pos_rows = h->pos_rows ? 1 : 0;
-    a.nlp_tol = h->nlp_tol; a.mu0 = h->mu0; a.sigma = h->sigma; a.s_min = h->s_min;
-    a.gamma = h->gamma; a.tau_min = h->tau_min;
-    a.ws = h->ws;
-    a.skip = h->skip_mask ? h->skip : nullptr; a.skip_mask = h->skip_mask;
     return a;
+}
+
+// a dense-LQ call or a change of the weights left foreign values in the tile workspace: back to zeros before the next solve
+int clean_workspace(Handle* h, hipStream_t st) {
+    if (h->ws_dirty) {
+        HIP_TRY(h, hipMemsetAsync(h->ws, 0, h->ws_bytes, st));
+        h->ws_dirty = false;
+    }
+    return NMPC_OK;
 }
 
 int launch_wb(Handle* h, nmpc::wb::WbArgs a, hipStream_t st) {
@@ -211,6 +217,51 @@ int read_tile(Handle* h, int b, int k, int which, float* out) {
         }
         if (which == 3) out[M::NX * 16 + M::NX] = 1.0f;
     }
+    return NMPC_OK;
+}
+// The replan loop of both device rollouts (LocomotionMPC.open_loop, mpc.py:416-462): per replan  prepare -> solve -> advance,
+// all on the caller's stream.  r: the plant's kernel arguments, its own fields, the carve-up of h->roll and the caller's pointers
+// filled in; a: the arguments of its solve with x0 and status.  plan(i) sets what the plant alone knows of replan i (its node)
+// and returns the warm-start shift of its solve; after_solve(i) runs between the solve and the advance kernel.
+template <class Cfg, class R, class A, class Plan, class AfterSolve>
+int run_rollout(Handle* h, int B, const Cfg* cfg, hipStream_t st, R& r, A& a, void (*prepare)(const R),
+                int (*solve)(Handle*, A, hipStream_t), void (*advance)(const R), Plan plan, AfterSolve after_solve) {
+    nmpc::DeviceGuard guard(h->device);
+    HIP_TRY(h, guard.err);
+    if (const int rc = clean_workspace(h, st)) return rc;
+    const int N = h->dims.N;
+    r.B = B; r.N = N; r.npc = cfg->nodes_per_cycle; r.replanning_steps = cfg->replanning_steps; r.n_replans = cfg->n_replans;
+    r.record_sim_steps = cfg->record_sim_steps ? 1 : 0;
+    r.sim_dt = cfg->sim_dt; r.t_horizon = cfg->time_horizon; r.nom_height = cfg->nom_height; r.height_offset = cfg->height_offset;
+    r.dt_nodes = cfg->time_horizon / N;
+    r.nominal_period = cfg->nominal_period; r.collision_height = cfg->collision_height;
+    r.term_mask = cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK;
+    const int rows_per_replan = r.record_sim_steps ? cfg->replanning_steps : 1;
+    r.n_rows = cfg->n_replans * rows_per_replan;
+    a.B = B; a.yref_per_stage = 1;
+    a.yref = r.yref; a.yref_e = r.yref_e; a.params = r.params; a.X = r.X; a.U = r.U; a.stats = nullptr;
+    a.skip = r.term_mask ? r.failed : nullptr; a.skip_mask = r.term_mask;     // terminated rollouts cost no solve
+    const double dt_replan = cfg->replanning_steps * cfg->sim_dt, slack = 0.5 * cfg->sim_dt;
+    for (int i = 0; i < cfg->n_replans; ++i) {
+        const bool cold = cfg->first_solve && i == 0;
+        r.first = cold ? 1 : 0;
+        r.replan_index = i;
+        r.row0 = i * rows_per_replan;
+        // the push window in replanning intervals, half a simulation step of slack on both ends: with plain float compares
+        // 5 * 0.04f = 0.19999999 misses a window that starts at 0.2 (the host loop, in doubles, does not)
+        const double t_now = i * dt_replan;
+        r.push_dt = (r.push_force && cfg->push_duration > 0.0f && t_now >= (double)cfg->push_start - slack &&
+                     t_now < (double)cfg->push_start + (double)cfg->push_duration - slack) ? (float)dt_replan : 0.0f;
+        const int shift = plan(i);
+        hipLaunchKernelGGL(prepare, dim3(B), dim3(64), 0, st, r);
+        a.shift = cold ? 0 : (shift > N ? N : shift);             // warm start folded into the solve
+        a.max_sqp = cold ? cfg->max_sqp_first : h->max_sqp;
+        a.nlp_tol = cold ? cfg->nlp_tol_first : cfg->nlp_tol;
+        if (const int rc = solve(h, a, st)) return rc;
+        if (const int rc = after_solve(i)) return rc;
+        hipLaunchKernelGGL(advance, dim3((B + 63) / 64), dim3(64), 0, st, r);
+    }
+    HIP_TRY(h, hipGetLastError());
     return NMPC_OK;
 }
 }  // namespace
@@ -427,10 +478,7 @@ int nmpc_shift_solve_batch(void* handle, int B, int shift, const float* x0, cons
     hipStream_t st = static_cast<hipStream_t>(stream);
     nmpc::DeviceGuard guard(h->device);
     HIP_TRY(h, guard.err);
-    if (h->ws_dirty) {
-        HIP_TRY(h, hipMemsetAsync(h->ws, 0, h->ws_bytes, st));
-        h->ws_dirty = false;
-    }
+    if (const int rc = clean_workspace(h, st)) return rc;
     if (h->dims.model_id == NMPC_MODEL_WHOLEBODY) {
         nmpc::wb::WbArgs w = wb_args(h);
         w.B = B;
@@ -515,63 +563,28 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
     if (cfg->record_sim_steps &&
         std::fabs(cfg->nodes_per_replan * (cfg->time_horizon / h->dims.N) - cfg->replanning_steps * cfg->sim_dt) > 1e-9)
         return fail(h, NMPC_E_ARG, "per-step recording needs nodes_per_replan * dt_nodes = replanning_steps * sim_dt");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    nmpc::DeviceGuard guard(h->device);
-    HIP_TRY(h, guard.err);
-    if (h->ws_dirty) {
-        HIP_TRY(h, hipMemsetAsync(h->ws, 0, h->ws_bytes, st));
-        h->ws_dirty = false;
-    }
-    const int N = h->dims.N;
-    float* yref = h->roll;
-    float* yref_e = yref + (size_t)h->dims.B_max * N * 24;
-    float* params = yref_e + (size_t)h->dims.B_max * 12;
     nmpc::RolloutArgs r{};
-    r.B = B; r.N = N; r.npc = cfg->nodes_per_cycle;
-    r.nodes_per_replan = cfg->nodes_per_replan; r.replanning_steps = cfg->replanning_steps;
-    r.n_replans = cfg->n_replans;
-    r.sim_dt = cfg->sim_dt; r.t_horizon = cfg->time_horizon; r.nom_height = cfg->nom_height;
-    r.height_offset = cfg->height_offset;
+    r.yref = h->roll;
+    r.yref_e = r.yref + (size_t)h->dims.B_max * h->dims.N * h->ny;
+    r.params = r.yref_e + (size_t)h->dims.B_max * h->nye;
+    r.nodes_per_replan = cfg->nodes_per_replan;
     r.mass = h->mp.mass; r.gz = h->mp.gz;
     r.gait = gait; r.x = x; r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state; r.foot_pos = foot_pos;
-    r.push_force = push_force; r.yref = yref; r.yref_e = yref_e; r.params = params;
-    r.X = X; r.U = U; r.S = S; r.status = status; r.failed = failed;
-    r.footsteps = cfg->footsteps ? 1 : 0; r.record_sim_steps = cfg->record_sim_steps ? 1 : 0;
-    r.term_mask = cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK; r.collision_height = cfg->collision_height;
+    r.push_force = push_force; r.X = X; r.U = U; r.S = S; r.status = status; r.failed = failed;
+    r.footsteps = cfg->footsteps ? 1 : 0;
     std::memcpy(r.hip_offset, cfg->hip_offset, sizeof(r.hip_offset));
     std::memcpy(r.stance_ratio, cfg->stance_ratio, sizeof(r.stance_ratio));
-    r.nominal_period = cfg->nominal_period; r.foot_size = cfg->foot_size;
-    r.dt_nodes = cfg->time_horizon / N;
-    const int rows_per_replan = r.record_sim_steps ? cfg->replanning_steps : 1;
-    r.n_rows = cfg->n_replans * rows_per_replan;
+    r.foot_size = cfg->foot_size;
     nmpc::SolveArgs a = base_args(h);
-    a.B = B; a.yref_per_stage = 1;
-    a.x0 = x; a.yref = yref; a.yref_e = yref_e; a.params = params; a.X = X; a.U = U;
-    a.status = status; a.stats = nullptr;
-    a.skip = r.term_mask ? failed : nullptr; a.skip_mask = r.term_mask;     // terminated rollouts cost no solve
-    const float dt_replan = (float)(cfg->replanning_steps * cfg->sim_dt);
-    for (int i = 0; i < cfg->n_replans; ++i) {
-        const bool cold = cfg->first_solve && i == 0;
-        r.node = cfg->start_node + i * cfg->nodes_per_replan;
-        r.first = cold ? 1 : 0;
-        r.replan_index = i;
-        r.row0 = i * rows_per_replan;
-        r.phase = phase[i];
-        // the push window in replanning intervals, half a simulation step of slack on both ends: with plain float compares
-        // 5 * 0.04f = 0.19999999 misses a window that starts at 0.2 (the host loop, in doubles, does not)
-        const double t_now = i * (cfg->replanning_steps * cfg->sim_dt), slack = 0.5 * cfg->sim_dt;
-        r.push_dt = (push_force && cfg->push_duration > 0.0f && t_now >= (double)cfg->push_start - slack &&
-                     t_now < (double)cfg->push_start + (double)cfg->push_duration - slack) ? dt_replan : 0.0f;
-        hipLaunchKernelGGL(nmpc::nmpc_rollout_prepare_kernel, dim3(B), dim3(64), 0, st, r);
-        a.shift = cold ? 0 : (cfg->nodes_per_replan > N ? N : cfg->nodes_per_replan);   // warm start folded into the solve
-        a.max_sqp = cold ? cfg->max_sqp_first : h->max_sqp;
-        a.nlp_tol = cold ? cfg->nlp_tol_first : cfg->nlp_tol;
-        const int rc = launch_solve<nmpc::Centroidal>(h, a, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(nmpc::nmpc_rollout_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, r);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return NMPC_OK;
+    a.x0 = x; a.status = status;
+    return run_rollout(h, B, cfg, static_cast<hipStream_t>(stream), r, a, nmpc::nmpc_rollout_prepare_kernel,
+                       launch_solve<nmpc::Centroidal>, nmpc::nmpc_rollout_advance_kernel,
+                       [&](int i) {
+                           r.node = cfg->start_node + i * cfg->nodes_per_replan;
+                           r.phase = phase[i];
+                           return cfg->nodes_per_replan;
+                       },
+                       [](int) { return NMPC_OK; });
 }
 
 int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, const signed char* gait, const signed char* peaks,
@@ -600,67 +613,38 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
             return fail(h, NMPC_E_ARG, std::string("action labels: ") + why);
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    nmpc::DeviceGuard guard(h->device);
-    HIP_TRY(h, guard.err);
-    if (h->ws_dirty) {
-        HIP_TRY(h, hipMemsetAsync(h->ws, 0, h->ws_bytes, st));
-        h->ws_dirty = false;
-    }
     auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };       // every array starts on a 16 B boundary (launch_wb checks)
-    float* yref = h->roll;
-    float* yref_e = yref + up4((size_t)h->dims.B_max * N * h->ny);
-    float* params = yref_e + up4((size_t)h->dims.B_max * h->nye);
-    float* x0 = params + up4((size_t)h->dims.B_max * (N + 1) * h->np);
     nmpc::wb::WbRolloutArgs r{};
-    r.B = B; r.N = N; r.npc = cfg->nodes_per_cycle; r.replanning_steps = cfg->replanning_steps; r.n_replans = cfg->n_replans;
-    r.record_sim_steps = cfg->record_sim_steps ? 1 : 0; r.force_gravity = cfg->force_reference_gravity ? 1 : 0;
-    r.sim_dt = cfg->sim_dt; r.t_horizon = cfg->time_horizon; r.nom_height = cfg->nom_height; r.height_offset = cfg->height_offset;
-    r.dt_nodes = cfg->time_horizon / N;
-    r.step_height = cfg->step_height; r.nominal_period = cfg->nominal_period; r.collision_height = cfg->collision_height;
-    r.term_mask = cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK;
+    r.yref = h->roll;
+    r.yref_e = r.yref + up4((size_t)h->dims.B_max * N * h->ny);
+    r.params = r.yref_e + up4((size_t)h->dims.B_max * h->nye);
+    r.x0 = r.params + up4((size_t)h->dims.B_max * (N + 1) * h->np);
+    r.force_gravity = cfg->force_reference_gravity ? 1 : 0;
+    r.step_height = cfg->step_height;
     r.mp = h->mp;
     r.gait = gait; r.peaks = peaks; r.q = q; r.v = v; r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state;
     r.joint_ref = joint_ref; r.push_force = push_force;
-    r.x0 = x0; r.yref = yref; r.yref_e = yref_e; r.params = params; r.X = X; r.U = U; r.S = S; r.status = status; r.failed = failed;
-    const int rows_per_replan = r.record_sim_steps ? cfg->replanning_steps : 1;
-    r.n_rows = cfg->n_replans * rows_per_replan;
+    r.X = X; r.U = U; r.S = S; r.status = status; r.failed = failed;
     nmpc::wb::WbArgs w = wb_args(h);
-    w.B = B; w.yref_per_stage = 1;
-    w.x0 = x0; w.yref = yref; w.yref_e = yref_e; w.params = params; w.X = X; w.U = U; w.status = status; w.stats = nullptr;
-    w.skip = r.term_mask ? failed : nullptr; w.skip_mask = r.term_mask;
-    const double dt_replan = cfg->replanning_steps * cfg->sim_dt, slack = 0.5 * cfg->sim_dt;
+    w.x0 = r.x0; w.status = status;
     int last_node = cfg->last_node;
-    for (int i = 0; i < cfg->n_replans; ++i) {
-        const bool cold = cfg->first_solve && i == 0;
-        r.node = nodes[i];
-        r.first = cold ? 1 : 0;
-        r.replan_index = i;
-        r.row0 = i * rows_per_replan;
-        const double t_now = i * dt_replan;
-        r.push_dt = (push_force && cfg->push_duration > 0.0f && t_now >= (double)cfg->push_start - slack &&
-                     t_now < (double)cfg->push_start + (double)cfg->push_duration - slack) ? (float)dt_replan : 0.0f;
-        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_prepare_kernel, dim3(B), dim3(64), 0, st, r);
-        int shift = cold ? 0 : nodes[i] - last_node;          // warm_start_solver(i_node): start_node = i_node - last_node (solver.py:304-309)
-        if (shift > N) shift = N;
-        last_node = nodes[i];
-        w.shift = shift;
-        w.max_sqp = cold ? cfg->max_sqp_first : h->max_sqp;
-        w.nlp_tol = cold ? cfg->nlp_tol_first : cfg->nlp_tol;
-        const int rc = launch_wb(h, w, st);
-        if (rc) return rc;
-        if (lab.A) {            // the labels of this replan's plan, beside the rows the advance kernel is about to record
-            const int steps = cfg->replanning_steps;
-            const int lrc = nmpc_plan_actions_batch(lab.torque, B, steps, N, X, U, lab.zoh, r.dt_nodes, r.sim_dt, lab.kp, lab.kd, nullptr,
-                                                    r.term_mask ? failed : nullptr, r.term_mask, lab.A + (size_t)r.row0 * 12, r.n_rows, st);
-            if (lrc) return fail(h, lrc, std::string("nmpc_plan_actions_batch: ") + nmpc_torque_last_error(lab.torque));
-            if (r.term_mask)
-                hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_hold_actions_kernel, dim3((unsigned)(((size_t)B * steps * 12 + 255) / 256)),
-                                   dim3(256), 0, st, B, r.n_rows, r.row0, steps, r.term_mask, failed, lab.A);
-        }
-        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, r);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return NMPC_OK;
+    return run_rollout(h, B, cfg, st, r, w, nmpc::wb::nmpc_wb_rollout_prepare_kernel, launch_wb, nmpc::wb::nmpc_wb_rollout_advance_kernel,
+                       [&](int i) {          // warm_start_solver(i_node): start_node = i_node - last_node (solver.py:304-309)
+                           const int shift = nodes[i] - last_node;
+                           r.node = last_node = nodes[i];
+                           return shift;
+                       },
+                       [&](int) {            // the labels of this replan's plan, beside the rows the advance kernel is about to record
+                           if (!lab.A) return (int)NMPC_OK;
+                           const int steps = cfg->replanning_steps;
+                           const int lrc = nmpc_plan_actions_batch(lab.torque, B, steps, N, X, U, lab.zoh, r.dt_nodes, r.sim_dt, lab.kp, lab.kd, nullptr,
+                                                                   r.term_mask ? failed : nullptr, r.term_mask, lab.A + (size_t)r.row0 * 12, r.n_rows, st);
+                           if (lrc) return fail(h, lrc, std::string("nmpc_plan_actions_batch: ") + nmpc_torque_last_error(lab.torque));
+                           if (r.term_mask)
+                               hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_hold_actions_kernel, dim3((unsigned)(((size_t)B * steps * 12 + 255) / 256)),
+                                                  dim3(256), 0, st, B, r.n_rows, r.row0, steps, r.term_mask, failed, lab.A);
+                           return (int)NMPC_OK;
+                       });
 }
 
 int nmpc_debug_set_buffer(void* handle, float* dev_buffer) {

@@ -15,91 +15,25 @@
 // Footsteps (cfg.footsteps): a foot in contact at the first node keeps its position up to its next swing node
 // (setup_initial_feet_pos, solver.py:194-210); every touch-down inside the window gets the Raibert target of
 // RaiberContactPlanner.get_locations (contact_planner.py:265-322) from the current base state and command.
-// Included by nmpc_api.hip.
+// What the two plants share -- the arguments of a rollout step, the fp64 base references, the contact window, the unsafe-state
+// predicates, the bookkeeping of failed[b], the push and the reference integration -- is in nmpc_rollout_common.hpp; here are the
+// Raibert footstep planner, the fp32 Hermite rows and the 19-slot row of the centroidal plant.  Included by nmpc_api.hip.
+
+#include "nmpc_rollout_common.hpp"
 
 #pragma clang fp contract(off)      // explicit: these kernels are compared bit for bit with their fp32 / fp64 restatements
 
 namespace nmpc {
 
-struct RolloutArgs {
-    int B, N, npc, node, first;          // nodes per gait cycle, current optimisation node, first replan
-    int nodes_per_replan, replanning_steps, replan_index, n_replans;
-    double sim_dt, t_horizon, nom_height, height_offset;
-    float mass, gz, push_dt;             // push_dt = 0: no push during this interval
-    float phase;                          // gait phase recorded with the state row
-    const signed char* gait;             // dev [4][npc] contact table
+struct RolloutArgs : RolloutCommon {
+    int nodes_per_replan;
+    float mass, gz;
+    float phase;                          // gait phase recorded with the state row (one row per replan)
     float* x;                             // dev [B][12] plant state
-    const double* v_des;                  // dev [B][3]
-    const double* w_des;                  // dev [B][3]
-    double* ref_state;                    // dev [B][12] integrated base reference (fp64, as the host keeps it)
     float* foot_pos;                      // dev [B][4][3] in/out: where each foot last stood / stands
-    const float* push_force;              // dev [B][3] or nullptr
-    float *yref, *yref_e, *params;        // dev problem tensors of the solve
-    float *X, *U;                         // dev trajectories
-    float* S;                             // dev [B][n_replans][19] recorded states
-    const int* status;                    // dev [B] status of the last solve
-    int* failed;                          // dev [B] sticky flag bits NMPC_ROLLOUT_FLAG_*
-    // footsteps and per-step recording (nmpc_rollout_cfg)
-    int footsteps, record_sim_steps;
-    float hip_offset[8], stance_ratio[4], nominal_period, foot_size;
-    double dt_nodes;
-    int row0;                             // first row of S this replan writes
-    int n_rows;                           // rows of S per rollout
-    int term_mask;                        // flag bits that terminate a rollout (nmpc_rollout_cfg.terminate_mask)
-    float collision_height;               // base height below which NMPC_ROLLOUT_FLAG_COLLISION is raised
+    int footsteps;                        // Raibert footsteps (nmpc_rollout_cfg)
+    float hip_offset[8], stance_ratio[4], foot_size;
 };
-
-__device__ inline void rpy_matrix(double roll, double pitch, double yaw, double (&R)[9]) {
-    const double cr = cos(roll), sr = sin(roll), cp = cos(pitch), sp = sin(pitch), cy = cos(yaw), sy = sin(yaw);
-    R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
-    R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;
-    R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
-}
-// numpy.round(x, d): rint(x * 10^d) / 10^d
-__device__ inline double np_round(double x, double p10) { return rint(x * p10) / p10; }
-// Python's builtin round(x, 1): the decimal nearest to the exact binary value (ties to even)
-__device__ inline double py_round1(double x) {
-    const double t = x * 10.0;
-    const double e = fma(x, 10.0, -t);          // exact residual of the product
-    double r = rint(t);
-    const double fl = floor(t);
-    if (t - fl == 0.5) r = (e > 0.0) ? fl + 1.0 : (e < 0.0) ? fl : r;
-    return r / 10.0;
-}
-__device__ inline double clipd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }   // np.clip
-
-// LocomotionMPC.compute_base_ref_vel_tracking (mpc.py:210-272) for one rollout, in fp64 with the reference's quantisation
-// (np.round to 2 / 1 decimals, the builtin round for the yaw) and crossed-bounds clips; (px, py, yaw) = q[0], q[1], q[3] of the
-// plant, rs = the controller's integrated reference.  Shared by the centroidal and the whole-body rollouts.
-__device__ inline void base_ref_vel_tracking_dev(double px, double py, double yaw, const double* rs, const double* v_des_p,
-                                                 const double* w_des_p, double t_horizon, double height, float (&ref)[12],
-                                                 float (&ref_e)[12]) {
-    const double v_des[3] = {v_des_p[0], v_des_p[1], v_des_p[2]};
-    const double w_des[3] = {w_des_p[0], w_des_p[1], w_des_p[2]};
-    double r[12] = {0}, re[12], R[9];
-    r[0] = np_round(px, 100.0);
-    r[1] = np_round(py, 100.0);
-    r[2] = height;
-    r[3] = py_round1(yaw);
-    rpy_matrix(rs[5], rs[4], rs[3], R);                   // rpyToMatrix(ref_state[3:6][::-1])
-    double vg[3];
-    for (int i = 0; i < 3; ++i) vg[i] = np_round(R[3 * i] * v_des[0] + R[3 * i + 1] * v_des[1] + R[3 * i + 2] * v_des[2], 10.0);
-    r[6] = vg[0]; r[7] = vg[1]; r[8] = vg[2];
-    r[9] = w_des[2]; r[10] = w_des[1]; r[11] = w_des[0];
-    for (int i = 0; i < 12; ++i) re[i] = r[i];
-    rpy_matrix(w_des[0] * t_horizon, w_des[1] * t_horizon, w_des[2] * t_horizon, R);
-    for (int i = 0; i < 3; ++i) re[6 + i] = R[3 * i] * r[6] + R[3 * i + 1] * r[7] + R[3 * i + 2] * r[8];
-    for (int i = 0; i < 2; ++i) {
-        const double reach = vg[i] * t_horizon;
-        re[i] = clipd(rs[i] + reach, -r[i] + 1.2 * reach, r[i] + 1.2 * reach);
-    }
-    const double yaw_reach = w_des[2] * t_horizon;
-    re[3] = clipd(rs[3] + yaw_reach, -rs[3] + 1.5 * yaw_reach, rs[3] + 1.5 * yaw_reach);
-    for (int i = 0; i < 2; ++i) r[i] += 0.75 * (re[i] - r[i]);
-    r[3] += 0.75 * (re[3] - r[3]);
-    re[8] = 0.0; re[4] = re[5] = 0.0; r[4] = r[5] = 0.0; re[10] = re[11] = 0.0;
-    for (int i = 0; i < 12; ++i) { ref[i] = (float)r[i]; ref_e[i] = (float)re[i]; }
-}
 
 // one block (64 threads) per problem
 __global__ __launch_bounds__(64) void nmpc_rollout_prepare_kernel(const RolloutArgs a) {
@@ -111,15 +45,7 @@ __global__ __launch_bounds__(64) void nmpc_rollout_prepare_kernel(const RolloutA
     if (tid == 0)
         base_ref_vel_tracking_dev((double)x[0], (double)x[1], (double)x[3], a.ref_state + (size_t)b * 12, a.v_des + (size_t)b * 3,
                                   a.w_des + (size_t)b * 3, a.t_horizon, a.nom_height + a.height_offset, ref, ref_e);
-    for (int k = tid; k <= N; k += 64) {
-        float n = 0.0f;
-        for (int f = 0; f < 4; ++f) {
-            const float c = (float)a.gait[f * a.npc + (a.node + k) % a.npc];
-            cflag[f * 129 + k] = c;
-            n += c;
-        }
-        fshare[k] = (-a.gz * a.mass) / fmaxf(n, 1.0f);
-    }
+    contact_window<129>(a, tid, nullptr, false, -a.gz * a.mass, cflag, nullptr, fshare);
     __syncthreads();
     const float* fp = a.foot_pos + (size_t)b * 12;
     if (a.footsteps && tid < 4) {
@@ -205,35 +131,24 @@ __global__ void nmpc_rollout_advance_kernel(const RolloutArgs a) {
     const float* pb = a.params + (size_t)b * (a.N + 1) * 16;
     int flags = a.failed[b];
     const int rows_per_replan = a.record_sim_steps ? a.replanning_steps : 1;
-    if (flags & a.term_mask) {
-        // Terminated in an earlier replan (the reference's simulator stops such a rollout, RolloutMPC.py:424-437): the
-        // plant, the feet and the controller are frozen; the remaining rows repeat the last recorded one so that S stays
-        // finite -- the rollout is invalid as a whole and is to be discarded or redone by the caller.
+    if (flags & a.term_mask) {                     // terminated in an earlier replan: frozen (hold_last_row)
         float* rows = a.S + ((size_t)b * a.n_rows + a.row0) * 19;
-        float last[19];
-        if (a.row0 > 0) {                          // the row that terminated it, or a copy of it
-            for (int i = 0; i < 19; ++i) last[i] = rows[i - 19];
+        if (a.row0 > 0) {
+            hold_last_row(rows, 19, rows_per_replan);
         } else {                                   // a call that continues an already terminated rollout: its frozen state
+            float last[19];
             last[0] = a.phase;
             for (int i = 0; i < 3; ++i) { last[1 + i] = x[6 + i]; last[4 + i] = x[9 + i]; }
             for (int i = 0; i < 4; ++i) last[7 + i] = x[2 + i];
             for (int f = 0; f < 4; ++f) { last[11 + 2 * f] = x[0] - fp[3 * f]; last[12 + 2 * f] = x[1] - fp[3 * f + 1]; }
+            for (int j = 0; j < rows_per_replan; ++j)
+                for (int i = 0; i < 19; ++i) rows[j * 19 + i] = last[i];
         }
-        for (int j = 0; j < rows_per_replan; ++j)
-            for (int i = 0; i < 19; ++i) rows[j * 19 + i] = last[i];
         return;
     }
-    const int st = a.status[b];
-    if (st == NMPC_STATUS_NAN || st == NMPC_STATUS_QP) flags |= NMPC_ROLLOUT_FLAG_SOLVER;
-    auto check_state = [&](const float* s12) {       // check_unsafe_state_v2 (Rollout_combined_controller.py:367-431)
-        const float lim = 25.0f * 0.017453292519943295f;
-        if (fabsf(s12[5]) > lim) flags |= NMPC_ROLLOUT_FLAG_ROLL;
-        if (fabsf(s12[4]) > lim) flags |= NMPC_ROLLOUT_FLAG_PITCH;
-        if (s12[2] < 0.18f || s12[2] > 0.45f) flags |= NMPC_ROLLOUT_FLAG_HEIGHT;
-        if (fabsf(s12[6] - (float)a.v_des[b * 3]) > 0.10f || fabsf(s12[7] - (float)a.v_des[b * 3 + 1]) > 0.10f)
-            flags |= NMPC_ROLLOUT_FLAG_VEL_TRACKING;
-        if (s12[2] < a.collision_height) flags |= NMPC_ROLLOUT_FLAG_COLLISION;
-        if (!(fabsf(s12[2]) <= 1e30f)) flags |= NMPC_ROLLOUT_FLAG_SOLVER;
+    flags |= solver_status_flag(a.status[b]);
+    auto check_state = [&](const float* s12) {
+        flags |= unsafe_state_flags(s12[5], s12[4], s12[2], s12[6], s12[7], a.v_des + b * 3, a.collision_height);
     };
     auto write_row = [&](float* row, float phase, const float* s12, int node) {
         row[0] = phase;
@@ -277,38 +192,21 @@ __global__ void nmpc_rollout_advance_kernel(const RolloutArgs a) {
                 s12[i] = hermite(x0[i], m0, x1[i], m1, dtn, s);
             }
             const double tw = (a.replan_index * a.replanning_steps + j + 1) * a.sim_dt;      // time of the recorded step
-            const double ph = rint(fmod(tw, period) / period * 1.0e4) / 1.0e4;                  // np.round(phase, 4)
-            write_row(a.S + ((size_t)b * a.n_rows + a.row0 + j) * 19, (float)ph, s12, k);
+            write_row(a.S + ((size_t)b * a.n_rows + a.row0 + j) * 19, (float)recorded_phase(tw, period), s12, k);
             check_state(s12);
         }
     }
-    if ((flags & a.term_mask) && !(flags >> NMPC_ROLLOUT_TERM_SHIFT))
-        flags |= (a.replan_index + 1) << NMPC_ROLLOUT_TERM_SHIFT;     // terminated by this replan's rows
-    a.failed[b] = flags;
-    if (flags & a.term_mask) return;             // frozen from here on
+    if (commit_flags(a, b, flags)) return;       // terminated by this replan's rows: frozen from here on
     // plant = plan
     const float* Xn = Xb + (size_t)a.nodes_per_replan * 12;
     for (int i = 0; i < 12; ++i) x[i] = Xn[i];
-    if (a.push_dt > 0.0f && a.push_force)
-        for (int i = 0; i < 3; ++i) x[6 + i] += a.push_force[b * 3 + i] * a.push_dt / a.mass;
+    apply_push(x + 6, a, b, a.mass);
     // feet that stand at the node the plant has reached are where the plan put them (touch-downs in between)
     if (a.footsteps)
         for (int f = 0; f < 4; ++f)
             if (pb[a.nodes_per_replan * 16 + f] > 0.5f)
                 for (int i = 0; i < 3; ++i) fp[3 * f + i] = pb[a.nodes_per_replan * 16 + 4 + 3 * f + i];
-    // integrate the base reference over the replanning interval (mpc.py:204-208, one sim step at a time)
-    double* rs = a.ref_state + (size_t)b * 12;
-    const double v_des[3] = {a.v_des[b * 3], a.v_des[b * 3 + 1], a.v_des[b * 3 + 2]};
-    const double wz = a.w_des[b * 3 + 2];
-    for (int s = 0; s < a.replanning_steps; ++s) {
-        double R[9];
-        rpy_matrix(rs[5], rs[4], rs[3], R);
-        const double vx = np_round(R[0] * v_des[0] + R[1] * v_des[1] + R[2] * v_des[2], 10.0);
-        const double vy = np_round(R[3] * v_des[0] + R[4] * v_des[1] + R[5] * v_des[2], 10.0);
-        rs[0] += vx * a.sim_dt;
-        rs[1] += vy * a.sim_dt;
-        rs[3] += wz * a.sim_dt;
-    }
+    integrate_base_reference(a, b);
 }
 
 }  // namespace nmpc

@@ -15,8 +15,11 @@
 //                                    (DAgger/utils/RolloutMPC.py:221; MuJoCo layout: dynamics.py:75-98), unsafe-state flags
 //                                    incl. joint limits (Rollout_combined_controller.py:367-431), early termination, base push,
 //                                    reference integration (mpc.py:204-208)
-// Included by nmpc_api.hip after nmpc_rollout.hip.inc (shares its fp64 helpers).
+// What the two plants share -- the arguments of a rollout step, the fp64 base references, the contact window, the unsafe-state
+// predicates, the bookkeeping of failed[b], the push and the reference integration -- is in nmpc_rollout_common.hpp; here are
+// forward kinematics, momentum, the 44-slot row, the joint limits and the label hold kernel.  Included by nmpc_api.hip.
 
+#include "nmpc_rollout_common.hpp"
 #include "nmpc_wb_plan.hpp"
 
 #pragma clang fp contract(off)
@@ -24,23 +27,14 @@
 namespace nmpc {
 namespace wb {
 
-struct WbRolloutArgs {
-    int B, N, npc, node, first, replanning_steps, replan_index, n_replans, record_sim_steps, force_gravity;
-    double sim_dt, t_horizon, nom_height, height_offset, dt_nodes;
-    float step_height, push_dt, nominal_period, collision_height;
-    int term_mask, row0, n_rows;
+struct WbRolloutArgs : RolloutCommon {
+    int force_gravity;
+    float step_height;
     ModelParams mp;
-    const signed char *gait, *peaks;      // dev [4][npc] contact and swing-peak tables
+    const signed char* peaks;             // dev [4][npc] swing-peak table
     float *q, *v;                         // dev [B][18] plant state, Euler layout (q = r, yaw, pitch, roll, joints; v = qdot)
-    const double *v_des, *w_des;          // dev [B][3]
-    double* ref_state;                    // dev [B][12]
     const float* joint_ref;               // dev [12]
-    const float* push_force;              // dev [B][3] or nullptr
-    float *x0, *yref, *yref_e, *params;   // dev problem tensors of the solve
-    float *X, *U;                         // dev trajectories
-    float* S;                             // dev [B][n_rows][44]
-    const int* status;
-    int* failed;
+    float* x0;                            // dev initial states of the solve (momentum slots included)
 };
 
 // foot positions in the world, [4][3], and the centroidal momentum of (q, v), in fp64 like the host helpers
@@ -95,17 +89,7 @@ __global__ __launch_bounds__(64) void nmpc_wb_rollout_prepare_kernel(const WbRol
         for (int i = 0; i < 18; ++i) { x0s[WQ + i] = qf[i]; x0s[WV + i] = vf[i]; }
         for (int i = 0; i < 6; ++i) x0s[WH + i] = (float)h[i];
     }
-    for (int k = tid; k <= N; k += 64) {
-        float n = 0.0f;
-        for (int f = 0; f < 4; ++f) {
-            float c = (float)a.gait[f * a.npc + (a.node + k) % a.npc];
-            if (a.node == 0 && k == 0) c = 1.0f;                  // setup_initial_feet_pos, solver.py:199-200: every foot stands at the very first node
-            cflag[f * 65 + k] = c;
-            pflag[f * 65 + k] = (float)a.peaks[f * a.npc + (a.node + k) % a.npc];
-            n += c;
-        }
-        fshare[k] = (-a.mp.gz * a.mp.mass) / fmaxf(n, 1.0f);
-    }
+    contact_window<65>(a, tid, a.peaks, true, -a.mp.gz * a.mp.mass, cflag, pflag, fshare);
     __syncthreads();
     if (tid < 4) {      // a foot in contact at node 0 keeps its position up to its next swing node; np.argmin: never swings -> 0 nodes
         int fs = 0;
@@ -188,14 +172,7 @@ __global__ void nmpc_wb_rollout_advance_kernel(const WbRolloutArgs a) {
         row[20] = (float)qw; row[21] = (float)qx; row[22] = (float)qy; row[23] = (float)qz;
         for (int i = 0; i < 12; ++i) row[24 + i] = (float)q[6 + i];
         for (int f = 0; f < 4; ++f) { row[36 + 2 * f] = (float)(q[0] - p[3 * f]); row[37 + 2 * f] = (float)(q[1] - p[3 * f + 1]); }
-        const float lim = 25.0f * 0.017453292519943295f, z = (float)q[2];
-        if (fabsf((float)q[5]) > lim) flags |= NMPC_ROLLOUT_FLAG_ROLL;
-        if (fabsf((float)q[4]) > lim) flags |= NMPC_ROLLOUT_FLAG_PITCH;
-        if (z < 0.18f || z > 0.45f) flags |= NMPC_ROLLOUT_FLAG_HEIGHT;
-        if (fabsf((float)v[0] - (float)a.v_des[b * 3]) > 0.10f || fabsf((float)v[1] - (float)a.v_des[b * 3 + 1]) > 0.10f)
-            flags |= NMPC_ROLLOUT_FLAG_VEL_TRACKING;
-        if (z < a.collision_height) flags |= NMPC_ROLLOUT_FLAG_COLLISION;
-        if (!(fabsf(z) <= 1e30f)) flags |= NMPC_ROLLOUT_FLAG_SOLVER;
+        flags |= unsafe_state_flags((float)q[5], (float)q[4], (float)q[2], (float)v[0], (float)v[1], a.v_des + b * 3, a.collision_height);
         for (int f = 0; f < 4; ++f) {       // joint limits in degrees: hip +-70, thigh [25, 115], knee [-155, -60]
             const float dg = 57.29577951308232f;
             const float hip = (float)q[6 + 3 * f] * dg, th = (float)q[7 + 3 * f] * dg, kn = (float)q[8 + 3 * f] * dg;
@@ -203,11 +180,10 @@ __global__ void nmpc_wb_rollout_advance_kernel(const WbRolloutArgs a) {
                 flags |= NMPC_ROLLOUT_FLAG_JOINT_LIMIT;
         }
     };
-    if (flags & a.term_mask) {             // terminated earlier: frozen, rows repeat the last recorded one
+    if (flags & a.term_mask) {             // terminated in an earlier replan: frozen (hold_last_row)
         if (a.row0 > 0) {
-            for (int j = 0; j < rows_per_replan; ++j)
-                for (int i = 0; i < 44; ++i) rows[j * 44 + i] = rows[i - 44];
-        } else {
+            hold_last_row(rows, 44, rows_per_replan);
+        } else {                           // a call that continues an already terminated rollout: its frozen state
             double q[18], v[18];
             for (int i = 0; i < 18; ++i) { q[i] = qf[i]; v[i] = vf[i]; }
             const int keep = flags;
@@ -216,42 +192,27 @@ __global__ void nmpc_wb_rollout_advance_kernel(const WbRolloutArgs a) {
         }
         return;
     }
-    const int st = a.status[b];
-    if (st == NMPC_STATUS_NAN || st == NMPC_STATUS_QP) flags |= NMPC_ROLLOUT_FLAG_SOLVER;
+    flags |= solver_status_flag(a.status[b]);
     // the plan at time t of the horizon (nmpc_wb_plan.hpp: the Hermite segments of mpc.py:388-414, shared with the label kernel)
     auto plan_at = [&](double t, double (&q)[18], double (&v)[18]) { wb_plan_at(Xb, Ub, N, a.dt_nodes, t, q, v); };
     double q[18], v[18];
     if (!a.record_sim_steps) {
         for (int i = 0; i < 18; ++i) { q[i] = qf[i]; v[i] = vf[i]; }
         const double tw = a.replan_index * a.replanning_steps * a.sim_dt;
-        record(rows, rint(fmod(tw, period) / period * 1.0e4) / 1.0e4, q, v);       // the state this replan started from
+        record(rows, recorded_phase(tw, period), q, v);       // the state this replan started from
     } else {
         for (int j = 0; j < a.replanning_steps; ++j) {                              // the states the plant runs through
             plan_at((j + 1) * a.sim_dt, q, v);
             const double tw = (a.replan_index * a.replanning_steps + j + 1) * a.sim_dt;
-            record(rows + j * 44, rint(fmod(tw, period) / period * 1.0e4) / 1.0e4, q, v);
+            record(rows + j * 44, recorded_phase(tw, period), q, v);
         }
     }
-    if ((flags & a.term_mask) && !(flags >> NMPC_ROLLOUT_TERM_SHIFT)) flags |= (a.replan_index + 1) << NMPC_ROLLOUT_TERM_SHIFT;
-    a.failed[b] = flags;
-    if (flags & a.term_mask) return;
+    if (commit_flags(a, b, flags)) return;       // terminated by this replan's rows: frozen from here on
     // plant = plan, `replanning_steps` simulation steps on
     plan_at(a.replanning_steps * a.sim_dt, q, v);
     for (int i = 0; i < 18; ++i) { qf[i] = (float)q[i]; vf[i] = (float)v[i]; }
-    if (a.push_dt > 0.0f && a.push_force)
-        for (int i = 0; i < 3; ++i) vf[i] += a.push_force[b * 3 + i] * a.push_dt / a.mp.mass;
-    double* rs = a.ref_state + (size_t)b * 12;
-    const double v_des[3] = {a.v_des[b * 3], a.v_des[b * 3 + 1], a.v_des[b * 3 + 2]};
-    const double wz = a.w_des[b * 3 + 2];
-    for (int s = 0; s < a.replanning_steps; ++s) {
-        double R[9];
-        rpy_matrix(rs[5], rs[4], rs[3], R);
-        const double vx = np_round(R[0] * v_des[0] + R[1] * v_des[1] + R[2] * v_des[2], 10.0);
-        const double vy = np_round(R[3] * v_des[0] + R[4] * v_des[1] + R[5] * v_des[2], 10.0);
-        rs[0] += vx * a.sim_dt;
-        rs[1] += vy * a.sim_dt;
-        rs[3] += wz * a.sim_dt;
-    }
+    apply_push(vf, a, b, a.mp.mass);
+    integrate_base_reference(a, b);
 }
 
 // Labels (nmpc_wb_rollout_set_actions) of the rollouts that terminated before this replan: their last written label row,

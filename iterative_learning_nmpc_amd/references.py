@@ -49,7 +49,7 @@ def euler_derivative_to_local_angular(ypr_euler, v_euler) -> np.ndarray:
 
 def _rotate_rpy(rpy, v) -> np.ndarray:
     """rpy_to_matrix(rpy[b]) @ v[b] for rows rpy, v [B, 3], each component summed left to right
-    R[i,0] v0 + R[i,1] v1 + R[i,2] v2 -- the order of the device's restatement (csrc/nmpc_rollout.hip.inc)."""
+    R[i,0] v0 + R[i,1] v1 + R[i,2] v2 -- the order of the device's restatement (csrc/nmpc_rollout_common.hpp)."""
     r, p, y = rpy[:, 0], rpy[:, 1], rpy[:, 2]
     cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
     v0, v1, v2 = v[:, 0], v[:, 1], v[:, 2]

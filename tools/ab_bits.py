@@ -2,15 +2,30 @@
 """Bit-identity check between two builds of libnmpc_hip.so (a kernel rewrite that claims to keep every rounding):
     NMPC_HIP_LIB=tools/_ab/lib_x.so python tools/ab_bits.py <tag>      -> gpurun_out/bits_<tag>.json (digests)
     python tools/ab_bits.py --compare tagA tagB
+One process per build, the second started only if the first exited 0.
 Solves fixed seeded batches of both model families (steady-state and multi-iteration policies, folded shift) and hashes
-X, U, status, stats."""
+X, U, status, stats; then device rollouts of both plants through the Python surface (`open_loop_device`), each case two calls
+in a row on one controller, and hashes every output of both calls.  A digest proves nothing about a path no rollout took:
+every rollout case starts a few rollouts above the height band (z0 = 0.5 > 0.45) with the height flag among the terminating
+bits, keeps rollout 0 nominal and unpushed at z0 = 0.30, counts from `failed >> 8` how many rollouts of the first call ended
+early and how many ran through, prints both and exits non-zero if either is zero.  The second call carries `failed` over
+(the Python surface hands every call fresh zeros), so rollouts that the first call ended enter it as already terminated
+(the row0 == 0 branch of the advance kernels), the others with a warm-started first replan."""
 import hashlib, json, os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def digests():
+def sha(*arrays):
+    import numpy as np
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)).tobytes())
+    return h.hexdigest()
+
+
+def solve_digests():
     import torch
     from iterative_learning_nmpc_amd import workloads as wl
     from iterative_learning_nmpc_amd.solver import BatchedNmpcSolver
@@ -25,18 +40,103 @@ def digests():
         X, U, st, stats = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], t["X"], t["U"])
         X, U, st, stats = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], X, U, shift=1)
         torch.cuda.synchronize()
-        h = hashlib.sha256()
-        for a in (X, U, st, stats):
-            h.update(a.cpu().numpy().tobytes())
-        out[name] = h.hexdigest()
+        out[name] = sha(X, U, st, stats)
     return out
+
+
+def carry_failed(solver):
+    """every rollout call of `solver` after the first starts from the flags the call before it left"""
+    make, last = solver._rollout_io, []
+
+    def io(*args):
+        S, failed = make(*args)
+        if last:
+            failed.copy_(last[0])
+        last[:] = [failed]
+        return S, failed
+    solver._rollout_io = io
+
+
+counts = {}      # per rollout case: how many rollouts of its first call ended early / ran through
+
+
+def both_groups(name, failed):
+    stamp = failed.cpu().numpy() >> 8
+    counts[name] = {"ended_early": int((stamp > 0).sum()), "ran_through": int((stamp == 0).sum())}
+    print(f"{name}: {counts[name]['ended_early']} rollouts ended early, {counts[name]['ran_through']} ran through", flush=True)
+
+
+def rollout_digests():
+    import numpy as np
+    import torch
+    from iterative_learning_nmpc_amd import _lib, wholebody as wbk
+    from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT
+    from iterative_learning_nmpc_amd.mpc import BatchedLocomotionMPC, sample_pushes
+    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
+    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
+    from iterative_learning_nmpc_amd.workloads import quadruped_tree
+    # the default mask ends a rollout on a solver failure or a trunk on the ground only; the posture predicates as well, as the
+    # reference's simulator does (check_unsafe_state_v2), so that a start above the height band ends a rollout for certain
+    mask = TERMINATE_DEFAULT | _lib.NMPC_ROLLOUT_FLAG_HEIGHT | _lib.NMPC_ROLLOUT_FLAG_ROLL | _lib.NMPC_ROLLOUT_FLAG_PITCH
+    out = {}
+    for name, opts in (("roll_c_steps", dict(footsteps=True, record_sim_steps=True)), ("roll_c_plain", dict())):
+        B, T = 64, 0.8                                   # 20 replans per call
+        x0 = np.zeros((B, 12)); x0[:, 2] = 0.3
+        x0[[5, 17, 40], 2] = 0.5
+        push = sample_pushes(B, (3, 1), start=0.2, duration=0.3)        # 50-70 N
+        push["force"][0] = 0.0
+        mpc = BatchedLocomotionMPC(B, n_nodes=50, device="cuda:0", terminate_mask=mask, **opts)
+        mpc.set_command(np.array([0.3, 0.0, 0.0]), 0.0)
+        carry_failed(mpc.solver)
+        parts = []
+        for call in range(2):
+            S, _ = mpc.open_loop_device(x0 if call == 0 else mpc.x_final.cpu().numpy().astype(np.float64), T, push if call == 0 else None)
+            torch.cuda.synchronize()
+            if call == 0:
+                both_groups(name, mpc.failed)
+            parts += [S, mpc.failed.clone(), mpc.x_final, mpc.base_ref_vel_tracking, mpc.foot_pos, mpc.X, mpc.U, mpc.status]
+        out[name] = sha(*parts)
+    layer = BatchedTorqueLayer(**quadruped_tree())
+    for name, steps, lab in (("roll_wb_steps_labels", True, layer), ("roll_wb_plain", False, None)):
+        B, T = 24, 0.8
+        rng = np.random.default_rng(2)                   # the batch of test_wholebody_device_rollouts_batch_and_termination
+        q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B, 12))
+        v0 = np.zeros((B, 18))
+        force = rng.uniform(-1, 1, (B, 3)); force /= np.linalg.norm(force, axis=1, keepdims=True); force *= rng.uniform(50, 70, (B, 1))
+        force[0] = 0.0
+        force[1] = [0.0, 0.0, -70.0]
+        q0[[4, 13], 2] = 0.5
+        mpc = LocomotionMPC(print_info=False, device="cuda:0", batch=B, n_nodes=30, force_reference="gravity_share")
+        mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
+        carry_failed(mpc.solver._device_solver())
+        parts = []
+        for call in range(2):
+            q, v = (q0, v0) if call == 0 else (mpc.q_final.cpu().numpy(), mpc.v_final.cpu().numpy())
+            S = mpc.open_loop_device(q, v, T, push=dict(start=0.2, duration=0.3, force=force) if call == 0 else None,
+                                     record_sim_steps=steps, terminate_mask=mask, torque_layer=lab)
+            torch.cuda.synchronize()
+            if call == 0:
+                both_groups(name, mpc.failed)
+            parts += [S, mpc.failed.clone(), mpc.q_final, mpc.v_final, mpc.base_ref_vel_tracking, mpc._X_dev, mpc._U_dev, mpc.status_dev]
+            if lab is not None:
+                parts.append(mpc.actions)
+        out[name] = sha(*parts)
+    return out
+
+
+def digests():
+    return {"digests": {**solve_digests(), **rollout_digests()}, "rollout_counts": counts}
 
 
 if __name__ == "__main__":
     if sys.argv[1] == "--compare":
         a, b = (json.load(open(os.path.join(ROOT, "gpurun_out", f"bits_{t}.json"))) for t in sys.argv[2:4])
-        same = {k: a[k] == b[k] for k in a}
+        same = {k: a["digests"][k] == b["digests"].get(k) for k in a["digests"]}
         print(same)
-        sys.exit(0 if all(same.values()) else 1)
+        print({t: d["rollout_counts"] for t, d in zip(sys.argv[2:4], (a, b))})
+        sys.exit(0 if all(same.values()) and set(a["digests"]) == set(b["digests"]) else 1)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     json.dump(digests(), open(os.path.join(ROOT, "gpurun_out", f"bits_{sys.argv[1]}.json"), "w"), indent=1)
+    vacuous = [k for k, c in counts.items() if not c["ended_early"] or not c["ran_through"]]
+    if vacuous:
+        sys.exit(f"rollout cases without both groups (ended early / ran through): {vacuous}")
