@@ -9,7 +9,7 @@
 #include <string>
 
 #include "../../include/nmpc_torque.h"
-#include "nmpc_device_guard.hpp"
+#include "nmpc_host.hpp"
 #include "nmpc_torque_plan.hpp"
 #include "nmpc_solve.hip"
 #include "nmpc_wb.hip"
@@ -19,7 +19,8 @@
 
 namespace {
 
-thread_local std::string g_create_error;
+using nmpc::fail;
+using nmpc::launched;
 
 struct Handle {
     nmpc_dims dims{};
@@ -54,17 +55,11 @@ struct Handle {
     std::string err;
 };
 
-int fail(Handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_error = msg;
-    return code;
-}
+Handle* const no_handle = nullptr;      // for nmpc_create: errors go to the family's slot
 
-#define HIP_TRY(h, expr)                                                                  \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(h, NMPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+// what several entry points ask of their handle: room for the batch, and a model and weights to solve with
+int check_batch(Handle* h, int B) { return (B < 0 || B > h->dims.B_max) ? fail(h, NMPC_E_ARG, "B exceeds B_max") : NMPC_OK; }
+int check_configured(Handle* h) { return (!h->mp_set || !h->w_set) ? fail(h, NMPC_E_STATE, "model parameters / weights not set") : NMPC_OK; }
 
 // the handle's configuration as kernel arguments (pointers and batch size left to the caller): what both families take ...
 template <class A>
@@ -106,10 +101,29 @@ nmpc::wb::WbArgs wb_args(const Handle* h) {
 // a dense-LQ call or a change of the weights left foreign values in the tile workspace: back to zeros before the next solve
 int clean_workspace(Handle* h, hipStream_t st) {
     if (h->ws_dirty) {
-        HIP_TRY(h, hipMemsetAsync(h->ws, 0, h->ws_bytes, st));
+        NMPC_TRY(h, hipMemsetAsync(h->ws, 0, h->ws_bytes, st));
         h->ws_dirty = false;
     }
     return NMPC_OK;
+}
+
+// The SQP loop of both families.  One iteration = linearise (thread per stage) + QP/step (wave per problem); linearize is
+// absent where the QP kernel linearises itself.  Problems that finish early (converged, NaN, QP failure) set their workspace
+// flag and later launches skip them.
+template <class A>
+int launch_sqp(Handle* h, A a, hipStream_t st, size_t lds_bytes, void (*qp)(const A), void (*linearize)(const A)) {
+    if (lds_bytes > 64 * 1024)
+        NMPC_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(qp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    const long long nthreads = (long long)a.B * (a.N + 1);
+    const unsigned lin_blocks = (unsigned)((nthreads + 63) / 64);
+    const int shift = a.shift;
+    for (int it = 0; it < a.max_sqp; ++it) {
+        a.it = it;
+        a.shift = (it == 0) ? shift : 0;     // later iterations read their own iterate
+        if (linearize) hipLaunchKernelGGL(linearize, dim3(lin_blocks), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(qp, dim3(a.B), dim3(64), lds_bytes, st, a);
+    }
+    return launched(h);
 }
 
 int launch_wb(Handle* h, nmpc::wb::WbArgs a, hipStream_t st) {
@@ -118,56 +132,28 @@ int launch_wb(Handle* h, nmpc::wb::WbArgs a, hipStream_t st) {
     auto misaligned = [](const void* p, unsigned m) { return (reinterpret_cast<uintptr_t>(p) & (m - 1u)) != 0; };
     if (misaligned(a.x0, 8) || misaligned(a.yref, 8) || misaligned(a.yref_e, 8) || misaligned(a.X, 8) || misaligned(a.U, 8) || misaligned(a.params, 16))
         return fail(h, NMPC_E_ARG, "whole-body arrays must be 8 B aligned (params: 16 B)");
-    const nmpc::wb::WbLds L(a.N);
-    const size_t bytes = (size_t)L.total * sizeof(float);
-    if (bytes > 64 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&nmpc::wb::nmpc_wb_qp_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    const long long nthreads = (long long)a.B * (a.N + 1);
-    const unsigned lin_blocks = (unsigned)((nthreads + 63) / 64);
-    const int shift = a.shift;
-    for (int it = 0; it < a.max_sqp; ++it) {
-        a.it = it;
-        a.shift = (it == 0) ? shift : 0;
-        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_linearize_kernel, dim3(lin_blocks), dim3(64), 0, st, a);
-        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_qp_kernel, dim3(a.B), dim3(64), bytes, st, a);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return NMPC_OK;
+    return launch_sqp(h, a, st, (size_t)nmpc::wb::WbLds(a.N).total * sizeof(float), nmpc::wb::nmpc_wb_qp_kernel,
+                      nmpc::wb::nmpc_wb_linearize_kernel);
 }
 
-// One SQP iteration = linearise (thread per stage) + QP/step (wave per problem).  Problems that
-// finish early (converged, NaN, QP failure) set their workspace flag and later launches skip them.
 // Two variants of the QP kernel (nmpc_solve.hip, Lds).  Resident: stage arrays in the LDS (39.6 KB at N = 50: four waves per CU),
 // pinned to one wave per SIMD -- the choice while the batch fits that many waves (B <= 4 x CUs: 2.2 M solves/s at B = 1024).
 // Lean: stage arrays in the workspace, 17.7 KB, two waves per SIMD -- the choice for larger batches, where the second wave fills
 // the first one's dependency stalls (2.7 M at B = 8192 against 2.3 M resident), for horizons whose resident layout does not
 // fit the LDS, and NMPC_QP_VARIANT=lean.  Both run the same arithmetic in the same order (bit-identical results, tested).
 template <class M, bool LEAN, bool BF16B, bool ALLV>
-int launch_qp(Handle* h, nmpc::SolveArgs a, hipStream_t st, unsigned lin_blocks) {
-    const nmpc::Lds<M, LEAN> L(a.N);
-    const size_t bytes = (size_t)L.total * sizeof(float);
+int launch_qp(Handle* h, nmpc::SolveArgs a, hipStream_t st) {
+    const size_t bytes = (size_t)nmpc::Lds<M, LEAN>(a.N).total * sizeof(float);
     if (bytes > 160 * 1024) return fail(h, NMPC_E_ARG, "horizon too long for the LDS-resident layout");
-    if (bytes > 64 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&nmpc::nmpc_qp_kernel<M, LEAN, BF16B, ALLV>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    const int shift = a.shift;
-    for (int it = 0; it < a.max_sqp; ++it) {
-        a.it = it;
-        a.shift = (it == 0) ? shift : 0;     // later iterations read their own iterate
-        if (!nmpc::qp_linearizes_itself(LEAN, a.N))
-            hipLaunchKernelGGL(nmpc::nmpc_linearize_kernel<M>, dim3(lin_blocks), dim3(64), 0, st, a);
-        hipLaunchKernelGGL((nmpc::nmpc_qp_kernel<M, LEAN, BF16B, ALLV>), dim3(a.B), dim3(64), bytes, st, a);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return NMPC_OK;
+    // (the code object keeps its kernels in the order they are named in: the QP kernel first)
+    void (*const qp)(const nmpc::SolveArgs) = nmpc::nmpc_qp_kernel<M, LEAN, BF16B, ALLV>;
+    void (*const linearize)(const nmpc::SolveArgs) = nmpc::nmpc_linearize_kernel<M>;
+    return launch_sqp(h, a, st, bytes, qp, nmpc::qp_linearizes_itself(LEAN, a.N) ? nullptr : linearize);
 }
 
 template <class M>
 int launch_solve(Handle* h, nmpc::SolveArgs a, hipStream_t st) {
     if (a.N > 64 * nmpc::N_LANE_STAGES) return fail(h, NMPC_E_ARG, "horizon too long for the lane = stage phases");
-    const long long nthreads = (long long)a.B * (a.N + 1);
-    const unsigned lin_blocks = (unsigned)((nthreads + 63) / 64);
     // problems in flight: a CU holds as many waves as its 160 KB of LDS take, at most one (resident) or two (lean) per SIMD
     auto in_flight = [&](size_t lds_bytes, long long per_simd) -> long long {
         if (lds_bytes > 160 * 1024) return 0;
@@ -182,13 +168,13 @@ int launch_solve(Handle* h, nmpc::SolveArgs a, hipStream_t st) {
     if constexpr (M::N_STATIC_MASKS > 4) {
         if (h->all_patterns) {
             if (h->dims.precision == 1)
-                return lean ? launch_qp<M, true, true, true>(h, a, st, lin_blocks) : launch_qp<M, false, true, true>(h, a, st, lin_blocks);
-            return lean ? launch_qp<M, true, false, true>(h, a, st, lin_blocks) : launch_qp<M, false, false, true>(h, a, st, lin_blocks);
+                return lean ? launch_qp<M, true, true, true>(h, a, st) : launch_qp<M, false, true, true>(h, a, st);
+            return lean ? launch_qp<M, true, false, true>(h, a, st) : launch_qp<M, false, false, true>(h, a, st);
         }
     }
     if (h->dims.precision == 1)
-        return lean ? launch_qp<M, true, true, false>(h, a, st, lin_blocks) : launch_qp<M, false, true, false>(h, a, st, lin_blocks);
-    return lean ? launch_qp<M, true, false, false>(h, a, st, lin_blocks) : launch_qp<M, false, false, false>(h, a, st, lin_blocks);
+        return lean ? launch_qp<M, true, true, false>(h, a, st) : launch_qp<M, false, true, false>(h, a, st);
+    return lean ? launch_qp<M, true, false, false>(h, a, st) : launch_qp<M, false, false, false>(h, a, st);
 }
 
 template <class M>
@@ -199,7 +185,7 @@ int read_tile(Handle* h, int b, int k, int which, float* out) {
                            wl.Kt + (size_t)k * G::K_FLOATS, wl.Ct + (size_t)k * G::C_FLOATS};
     const size_t len[4] = {G::A_FLOATS, G::B_FLOATS, G::K_FLOATS, G::C_FLOATS};
     float img[512];
-    HIP_TRY(h, hipMemcpy(img, h->ws + (size_t)b * wl.stride + off[which], len[which] * sizeof(float),
+    NMPC_TRY(h, hipMemcpy(img, h->ws + (size_t)b * wl.stride + off[which], len[which] * sizeof(float),
                          hipMemcpyDeviceToHost));
     std::memset(out, 0, 256 * sizeof(float));
     if (which == 0) {          // A~ : column-major, stride SA, columns 0..nx ; row nx = e_nx
@@ -226,8 +212,7 @@ int read_tile(Handle* h, int b, int k, int which, float* out) {
 template <class Cfg, class R, class A, class Plan, class AfterSolve>
 int run_rollout(Handle* h, int B, const Cfg* cfg, hipStream_t st, R& r, A& a, void (*prepare)(const R),
                 int (*solve)(Handle*, A, hipStream_t), void (*advance)(const R), Plan plan, AfterSolve after_solve) {
-    nmpc::DeviceGuard guard(h->device);
-    HIP_TRY(h, guard.err);
+    NMPC_ENTER(h, h->device);
     if (const int rc = clean_workspace(h, st)) return rc;
     const int N = h->dims.N;
     r.B = B; r.N = N; r.npc = cfg->nodes_per_cycle; r.replanning_steps = cfg->replanning_steps; r.n_replans = cfg->n_replans;
@@ -261,7 +246,17 @@ int run_rollout(Handle* h, int B, const Cfg* cfg, hipStream_t st, R& r, A& a, vo
         if (const int rc = after_solve(i)) return rc;
         hipLaunchKernelGGL(advance, dim3((B + 63) / 64), dim3(64), 0, st, r);
     }
-    HIP_TRY(h, hipGetLastError());
+    return launched(h);
+}
+
+// the device side of nmpc_create, on the handle's device; what was allocated before an error is nmpc_destroy's to free
+int allocate(Handle* h) {
+    NMPC_TRY(no_handle, hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
+    NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&h->ws), h->ws_bytes));
+    NMPC_TRY(no_handle, hipMemset(h->ws, 0, h->ws_bytes));
+    const int N = h->dims.N;
+    const size_t per = (size_t)N * h->ny + h->nye + (size_t)(N + 1) * (h->np > 0 ? h->np : 1) + h->nx;   // yref, yref_e, params, x0 of the rollouts
+    NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&h->roll), ((size_t)h->dims.B_max * per + 16) * sizeof(float)));   // (+ the 16 B roundings of the carve-up)
     return NMPC_OK;
 }
 }  // namespace
@@ -298,46 +293,30 @@ int nmpc_model_output_dims(int model_id, int* ny, int* ny_e) {
 }
 
 int nmpc_create(const nmpc_dims* dims, int device_id, void** handle) {
-    if (!dims || !handle) return fail(nullptr, NMPC_E_ARG, "null argument");
+    if (!dims || !handle) return fail(no_handle, NMPC_E_ARG, "null argument");
     *handle = nullptr;
     int nx, nu, np, ng;
-    if (nmpc_model_dims(dims->model_id, &nx, &nu, &np, &ng)) return fail(nullptr, NMPC_E_ARG, "unknown model_id");
-    if (dims->N < 1 || dims->B_max < 1) return fail(nullptr, NMPC_E_ARG, "N and B_max must be positive");
+    if (nmpc_model_dims(dims->model_id, &nx, &nu, &np, &ng)) return fail(no_handle, NMPC_E_ARG, "unknown model_id");
+    if (dims->N < 1 || dims->B_max < 1) return fail(no_handle, NMPC_E_ARG, "N and B_max must be positive");
     if (dims->precision < 0 || dims->precision > 3 || (dims->precision >= 2 && dims->model_id != NMPC_MODEL_WHOLEBODY))
-        return fail(nullptr, NMPC_E_ARG, "precision must be 0 (fp32), 1 (bf16 contraction) or, whole-body only, 2 (split bf16) / 3 (three-way split bf16)");
+        return fail(no_handle, NMPC_E_ARG, "precision must be 0 (fp32), 1 (bf16 contraction) or, whole-body only, 2 (split bf16) / 3 (three-way split bf16)");
+    if (dims->model_id == NMPC_MODEL_WHOLEBODY && dims->N > 64)
+        return fail(no_handle, NMPC_E_ARG, "the whole-body model needs N <= 64 (lane = stage phases)");
+    NMPC_ENTER(no_handle, device_id);
     Handle* h = new Handle();
     h->dims = *dims;
     h->device = device_id;
     h->nx = nx; h->nu = nu; h->np = np; h->ng = ng;
     nmpc_model_output_dims(dims->model_id, &h->ny, &h->nye);
-    if (dims->model_id == NMPC_MODEL_WHOLEBODY && dims->N > 64)
-        { delete h; return fail(nullptr, NMPC_E_ARG, "the whole-body model needs N <= 64 (lane = stage phases)"); }
-    nmpc::DeviceGuard guard(device_id);
-    hipError_t e = guard.err;
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device_id);
     if (const char* v = std::getenv("NMPC_QP_VARIANT")) {
         if (!std::strcmp(v, "resident")) h->force_variant = 1;
         else if (!std::strcmp(v, "lean")) h->force_variant = 2;
     }
-    if (e == hipSuccess) {
-        h->ws_stride = (dims->model_id == NMPC_MODEL_DOUBLE_INTEGRATOR) ? ws_floats_per_problem<nmpc::DoubleIntegrator>(dims->N)
-                     : (dims->model_id == NMPC_MODEL_CENTROIDAL)      ? ws_floats_per_problem<nmpc::Centroidal>(dims->N)
-                                                                      : nmpc::wb::WsLayout(dims->N).stride;
-        h->ws_bytes = (size_t)dims->B_max * h->ws_stride * sizeof(float);
-        e = hipMalloc(reinterpret_cast<void**>(&h->ws), h->ws_bytes);
-    }
-    if (e == hipSuccess) e = hipMemset(h->ws, 0, h->ws_bytes);
-    if (e == hipSuccess) {
-        const size_t per = (size_t)dims->N * h->ny + h->nye + (size_t)(dims->N + 1) * (np > 0 ? np : 1) + nx;   // yref, yref_e, params, x0 of the rollouts
-        e = hipMalloc(reinterpret_cast<void**>(&h->roll), ((size_t)dims->B_max * per + 16) * sizeof(float));   // (+ the 16 B roundings of the carve-up)
-    }
-    if (e != hipSuccess) {
-        g_create_error = std::string("nmpc_create: ") + hipGetErrorString(e);
-        if (h->ws) (void)hipFree(h->ws);
-        if (h->roll) (void)hipFree(h->roll);
-        delete h;
-        return NMPC_E_HIP;
-    }
+    h->ws_stride = (dims->model_id == NMPC_MODEL_DOUBLE_INTEGRATOR) ? ws_floats_per_problem<nmpc::DoubleIntegrator>(dims->N)
+                 : (dims->model_id == NMPC_MODEL_CENTROIDAL)      ? ws_floats_per_problem<nmpc::Centroidal>(dims->N)
+                                                                  : nmpc::wb::WsLayout(dims->N).stride;
+    h->ws_bytes = (size_t)dims->B_max * h->ws_stride * sizeof(float);
+    if (const int rc = allocate(h)) { nmpc_destroy(h); return rc; }
     *handle = h;
     return NMPC_OK;
 }
@@ -345,16 +324,14 @@ int nmpc_create(const nmpc_dims* dims, int device_id, void** handle) {
 void nmpc_destroy(void* handle) {
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return;
-    nmpc::DeviceGuard guard(h->device);
+    nmpc::DeviceGuard guard(h->device);      // nothing to return: a failed switch goes to the family's slot, the buffers are freed all the same
+    if (guard.err != hipSuccess) fail(no_handle, NMPC_E_HIP, std::string("nmpc_destroy: ") + hipGetErrorString(guard.err));
     if (h->ws) (void)hipFree(h->ws);
     if (h->roll) (void)hipFree(h->roll);
     delete h;
 }
 
-const char* nmpc_last_error(void* handle) {
-    Handle* h = static_cast<Handle*>(handle);
-    return h ? h->err.c_str() : g_create_error.c_str();
-}
+const char* nmpc_last_error(void* handle) { return nmpc::last_error(static_cast<Handle*>(handle)); }
 
 size_t nmpc_workspace_bytes(void* handle) {
     Handle* h = static_cast<Handle*>(handle);
@@ -450,19 +427,17 @@ int nmpc_shift_warm_start(void* handle, int B, int shift, float* X, float* U, vo
     if (!h) return NMPC_E_ARG;
     if (B == 0) return NMPC_OK;
     if (!X || !U) return fail(h, NMPC_E_ARG, "null argument");
-    if (B < 0 || B > h->dims.B_max) return fail(h, NMPC_E_ARG, "B exceeds B_max");
+    if (const int rc = check_batch(h, B)) return rc;
     if (shift < 0) return fail(h, NMPC_E_ARG, "negative shift");
     if (shift == 0) return NMPC_OK;
     const int N = h->dims.N;
     if (shift > N) shift = N;
     if ((size_t)N * h->nx > 256 * 16 || (size_t)N * h->nu > 256 * 16)
         return fail(h, NMPC_E_ARG, "trajectory too long for the shift kernel");
-    nmpc::DeviceGuard guard(h->device);
-    HIP_TRY(h, guard.err);
+    NMPC_ENTER(h, h->device);
     hipLaunchKernelGGL(nmpc::nmpc_shift_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
                        N, h->nx, h->nu, h->dims.model_id == NMPC_MODEL_WHOLEBODY ? nmpc::wb::WF : 0, shift, X, U);
-    HIP_TRY(h, hipGetLastError());
-    return NMPC_OK;
+    return launched(h);
 }
 
 int nmpc_shift_solve_batch(void* handle, int B, int shift, const float* x0, const float* yref,
@@ -472,12 +447,11 @@ int nmpc_shift_solve_batch(void* handle, int B, int shift, const float* x0, cons
     if (!h) return NMPC_E_ARG;
     if (B == 0) return NMPC_OK;     // an empty batch is a no-op (its tensors have no storage)
     if (!x0 || !yref || !yref_e || !X || !U || (h->np > 0 && !params)) return fail(h, NMPC_E_ARG, "null argument");
-    if (B < 0 || B > h->dims.B_max) return fail(h, NMPC_E_ARG, "B exceeds B_max");
+    if (const int rc = check_batch(h, B)) return rc;
     if (shift < 0) return fail(h, NMPC_E_ARG, "negative shift");
-    if (!h->mp_set || !h->w_set) return fail(h, NMPC_E_STATE, "model parameters / weights not set");
+    if (const int rc = check_configured(h)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    nmpc::DeviceGuard guard(h->device);
-    HIP_TRY(h, guard.err);
+    NMPC_ENTER(h, h->device);
     if (const int rc = clean_workspace(h, st)) return rc;
     if (h->dims.model_id == NMPC_MODEL_WHOLEBODY) {
         nmpc::wb::WbArgs w = wb_args(h);
@@ -510,18 +484,16 @@ int nmpc_riccati_batch(void* handle, int Bsz, int nx, int nu, const float* Q, co
                        void* stream) {
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return NMPC_E_ARG;
+    if (Bsz == 0) return NMPC_OK;
     if (!Q || !R || !q || !r || !A || !B_ || !d || !dx0 || !dX || !dU) return fail(h, NMPC_E_ARG, "null argument");
     if (nx < 1 || nx > 15 || nu < 1 || nu > 16) return fail(h, NMPC_E_ARG, "need 1 <= nx <= 15, 1 <= nu <= 16");
     if (h->dims.model_id == NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_riccati_batch needs a handle of the tile-family models");
-    if (Bsz < 0 || Bsz > h->dims.B_max) return fail(h, NMPC_E_ARG, "B exceeds B_max");
-    if (Bsz == 0) return NMPC_OK;
-    nmpc::DeviceGuard guard(h->device);
-    HIP_TRY(h, guard.err);
+    if (const int rc = check_batch(h, Bsz)) return rc;
+    NMPC_ENTER(h, h->device);
     nmpc::RiccatiArgs a{h->dims.N, Bsz, nx, nu, Q, R, q, r, A, B_, d, dx0, dX, dU, status, h->ws};
     h->ws_dirty = true;
     hipLaunchKernelGGL(nmpc::nmpc_riccati_kernel, dim3(Bsz), dim3(64), 0, static_cast<hipStream_t>(stream), a);
-    HIP_TRY(h, hipGetLastError());
-    return NMPC_OK;
+    return launched(h);
 }
 
 int nmpc_tracking_error(void* handle, int B, int T, int ns, const float* S, const float* S_nom,
@@ -532,15 +504,14 @@ int nmpc_tracking_error(void* handle, int B, int T, int ns, const float* S, cons
     if (B < 0 || T < 1 || ns < 2) return fail(h, NMPC_E_ARG, "need B >= 0, T >= 1, ns >= 2");
     const size_t lds = (size_t)nmpc::TRB * (ns | 1) * sizeof(float);
     if (lds > 64 * 1024) return fail(h, NMPC_E_ARG, "state dimension too large for the staging tile");
-    nmpc::DeviceGuard guard(nmpc::device_of(S));
     const long long rows = (long long)B * T;
     const long long blocks = (rows + nmpc::TRB - 1) / nmpc::TRB;
     if (blocks > 0x7fffffffLL) return fail(h, NMPC_E_ARG, "too many rows");
+    NMPC_ENTER(h, nmpc::device_of(S));
     hipLaunchKernelGGL(nmpc::nmpc_tracking_error_kernel, dim3((unsigned)blocks), dim3(nmpc::TRB), lds,
                        static_cast<hipStream_t>(stream), rows, T, ns, S, S_nom, err, weight, threshold,
                        ood_weight);
-    HIP_TRY(h, hipGetLastError());
-    return NMPC_OK;
+    return launched(h);
 }
 
 int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const signed char* gait, float* x,
@@ -553,12 +524,12 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
     if (!cfg || !gait || !x || !v_des || !w_des || !ref_state || !foot_pos || !phase || !X || !U || !S || !status || !failed)
         return fail(h, NMPC_E_ARG, "null argument");
     if (h->dims.model_id != NMPC_MODEL_CENTROIDAL) return fail(h, NMPC_E_ARG, "rollouts need the centroidal model");
-    if (B < 0 || B > h->dims.B_max) return fail(h, NMPC_E_ARG, "B exceeds B_max");
+    if (const int rc = check_batch(h, B)) return rc;
     if (h->dims.N > 128) return fail(h, NMPC_E_ARG, "rollouts need N <= 128");
     if (cfg->n_replans < 1 || cfg->nodes_per_replan < 1 || cfg->nodes_per_replan > h->dims.N ||
         cfg->replanning_steps < 1 || cfg->nodes_per_cycle < 1 || cfg->start_node < 0)
         return fail(h, NMPC_E_ARG, "rollout configuration out of range");
-    if (!h->mp_set || !h->w_set) return fail(h, NMPC_E_STATE, "model parameters / weights not set");
+    if (const int rc = check_configured(h)) return rc;
     if (cfg->footsteps && !(cfg->nominal_period > 0.0f)) return fail(h, NMPC_E_ARG, "footsteps need the gait period");
     if (cfg->record_sim_steps &&
         std::fabs(cfg->nodes_per_replan * (cfg->time_horizon / h->dims.N) - cfg->replanning_steps * cfg->sim_dt) > 1e-9)
@@ -597,10 +568,10 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
     if (!cfg || !gait || !peaks || !nodes || !q || !v || !v_des || !w_des || !ref_state || !joint_ref || !X || !U || !S || !status || !failed)
         return fail(h, NMPC_E_ARG, "null argument");
     if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_wb_rollout_batch needs the whole-body model");
-    if (B < 0 || B > h->dims.B_max) return fail(h, NMPC_E_ARG, "B exceeds B_max");
+    if (const int rc = check_batch(h, B)) return rc;
     if (cfg->n_replans < 1 || cfg->replanning_steps < 1 || cfg->nodes_per_cycle < 1 || !(cfg->sim_dt > 0) || !(cfg->time_horizon > 0))
         return fail(h, NMPC_E_ARG, "rollout configuration out of range");
-    if (!h->mp_set || !h->w_set) return fail(h, NMPC_E_STATE, "model parameters / weights not set");
+    if (const int rc = check_configured(h)) return rc;
     if (h->line_search) return fail(h, NMPC_E_ARG, "the whole-body model takes full steps (line_search = 0)");
     const int N = h->dims.N;
     if (cfg->replanning_steps * cfg->sim_dt > cfg->time_horizon) return fail(h, NMPC_E_ARG, "replanning interval longer than the horizon");
@@ -659,9 +630,8 @@ int nmpc_debug_read_tile(void* handle, int b, int k, int which, float* out_host)
     if (!h || !out_host) return fail(h, NMPC_E_ARG, "null argument");
     if (b < 0 || b >= h->dims.B_max || k < 0 || k >= h->dims.N || which < 0 || which > 3)
         return fail(h, NMPC_E_ARG, "index out of range");
-    nmpc::DeviceGuard guard(h->device);
-    HIP_TRY(h, guard.err);
-    HIP_TRY(h, hipDeviceSynchronize());
+    NMPC_ENTER(h, h->device);
+    NMPC_TRY(h, hipDeviceSynchronize());
     if (h->dims.model_id == NMPC_MODEL_DOUBLE_INTEGRATOR) return read_tile<nmpc::DoubleIntegrator>(h, b, k, which, out_host);
     if (h->dims.model_id == NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "use nmpc_debug_read_workspace for the whole-body model");
     return read_tile<nmpc::Centroidal>(h, b, k, which, out_host);
@@ -671,10 +641,9 @@ int nmpc_debug_read_workspace(void* handle, int b, size_t offset, size_t count, 
     Handle* h = static_cast<Handle*>(handle);
     if (!h || !out_host) return fail(h, NMPC_E_ARG, "null argument");
     if (b < 0 || b >= h->dims.B_max || offset + count > h->ws_stride) return fail(h, NMPC_E_ARG, "index out of range");
-    nmpc::DeviceGuard guard(h->device);
-    HIP_TRY(h, guard.err);
-    HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemcpy(out_host, h->ws + (size_t)b * h->ws_stride + offset, count * sizeof(float), hipMemcpyDeviceToHost));
+    NMPC_ENTER(h, h->device);
+    NMPC_TRY(h, hipDeviceSynchronize());
+    NMPC_TRY(h, hipMemcpy(out_host, h->ws + (size_t)b * h->ws_stride + offset, count * sizeof(float), hipMemcpyDeviceToHost));
     return NMPC_OK;
 }
 

@@ -7,7 +7,7 @@
 // the state table is 1.76 GB: it stays in HBM next to the rollouts that fill it.
 #include <hip/hip_runtime.h>
 
-#include "nmpc_device_guard.hpp"
+#include "nmpc_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -161,17 +161,11 @@ __global__ void assemble_batch_kernel(const float* __restrict__ states, int n_st
 namespace {
 
 using namespace nmpc_dataset;
+using nmpc::fail;
+using nmpc::launched;
 
-thread_local std::string g_dataset_error;
-
-int dfail(int code, const std::string& msg) {
-    g_dataset_error = msg;
-    return code;
-}
-int launched() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NMPC_OK : dfail(NMPC_E_HIP, hipGetErrorString(e));
-}
+struct Dataset { std::string err; };    // the family has no handles: the type names its error slot
+Dataset* const no_handle = nullptr;
 
 // One resident round: as many blocks as the device holds at once (a grid-stride kernel launched wider
 // than that runs a second, mostly idle round), at most STAT_BLOCKS_MAX (the scratch size).
@@ -207,30 +201,30 @@ void column_stats(hipStream_t st, const float* data, long long rows, int cols, d
 
 extern "C" {
 
-const char* nmpc_dataset_last_error(void) { return g_dataset_error.c_str(); }
+const char* nmpc_dataset_last_error(void) { return nmpc::last_error(no_handle); }
 
 int nmpc_ring_append(const float* src, int row_len, long long n, float* ring, long long limit, long long first_slot,
                      void* stream) {
     if (n == 0) return NMPC_OK;
-    if (!src || !ring) return dfail(NMPC_E_ARG, "null argument");
+    if (!src || !ring) return fail(no_handle, NMPC_E_ARG, "null argument");
     if (row_len < 1 || n < 0 || limit < 1 || first_slot < 0 || first_slot >= limit)
-        return dfail(NMPC_E_ARG, "need row_len >= 1, n >= 0, limit >= 1, 0 <= first_slot < limit");
-    nmpc::DeviceGuard guard(nmpc::device_of(ring));
+        return fail(no_handle, NMPC_E_ARG, "need row_len >= 1, n >= 0, limit >= 1, 0 <= first_slot < limit");
     const long long skip = n > limit ? n - limit : 0;
     const size_t elems = (size_t)(n - skip) * row_len;
-    if ((elems + 255) / 256 > 0x7fffffffULL) return dfail(NMPC_E_ARG, "append too large for one launch");
+    if ((elems + 255) / 256 > 0x7fffffffULL) return fail(no_handle, NMPC_E_ARG, "append too large for one launch");
+    NMPC_ENTER(no_handle, nmpc::device_of(ring));
     hipLaunchKernelGGL(ring_append_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        src, row_len, n, ring, limit, first_slot, skip);
-    return launched();
+    return launched(no_handle);
 }
 
 size_t nmpc_column_stats_scratch(int cols) { return cols < 1 ? 0 : (size_t)STAT_BLOCKS_MAX * cols; }
 
 int nmpc_column_stats(const float* data, long long rows, int cols, double* mean, double* std_out, double* scratch,
                       void* stream) {
-    if (!data || !mean || !std_out || !scratch) return dfail(NMPC_E_ARG, "null argument");
-    if (rows < 1 || cols < 1 || cols > 64) return dfail(NMPC_E_ARG, "need rows >= 1, 1 <= cols <= 64");
-    nmpc::DeviceGuard guard(nmpc::device_of(data));
+    if (!data || !mean || !std_out || !scratch) return fail(no_handle, NMPC_E_ARG, "null argument");
+    if (rows < 1 || cols < 1 || cols > 64) return fail(no_handle, NMPC_E_ARG, "need rows >= 1, 1 <= cols <= 64");
+    NMPC_ENTER(no_handle, nmpc::device_of(data));
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (cols) {   // the reference's row widths: state 44, action 12, contact goal 8, velocity goal 3
         case 44: column_stats<44>(st, data, rows, cols, mean, std_out, scratch); break;
@@ -239,26 +233,26 @@ int nmpc_column_stats(const float* data, long long rows, int cols, double* mean,
         case 3: column_stats<3>(st, data, rows, cols, mean, std_out, scratch); break;
         default: column_stats<0>(st, data, rows, cols, mean, std_out, scratch); break;
     }
-    return launched();
+    return launched(no_handle);
 }
 
 int nmpc_assemble_batch(const float* states, int n_state, const double* s_mean, const double* s_std, int s_first,
                         const float* goals, int n_goal, const double* g_mean, const double* g_std, const float* actions,
                         int n_action, long long n_rows, const int* idx, int n_idx, float* x, float* y, void* stream) {
     if (n_idx == 0) return NMPC_OK;
-    if (!states || !idx || !x) return dfail(NMPC_E_ARG, "null argument");
+    if (!states || !idx || !x) return fail(no_handle, NMPC_E_ARG, "null argument");
     if (n_state < 1 || n_goal < 0 || n_action < 0 || n_idx < 0 || s_first < 0 || n_rows < 1)
-        return dfail(NMPC_E_ARG, "need n_state, n_rows >= 1, n_goal, n_action, n_idx, s_first >= 0");
+        return fail(no_handle, NMPC_E_ARG, "need n_state, n_rows >= 1, n_goal, n_action, n_idx, s_first >= 0");
     if ((n_goal > 0 && !goals) || (n_action > 0 && (!actions || !y)))
-        return dfail(NMPC_E_ARG, "goals / actions / y missing for a non-zero width");
+        return fail(no_handle, NMPC_E_ARG, "goals / actions / y missing for a non-zero width");
     if ((s_mean == nullptr) != (s_std == nullptr) || (g_mean == nullptr) != (g_std == nullptr))
-        return dfail(NMPC_E_ARG, "mean and std come in pairs");
-    nmpc::DeviceGuard guard(nmpc::device_of(states));
+        return fail(no_handle, NMPC_E_ARG, "mean and std come in pairs");
+    NMPC_ENTER(no_handle, nmpc::device_of(states));
     const size_t elems = (size_t)n_idx * (n_state + n_goal + n_action);
     hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), states, n_state, s_mean, s_std, s_first, goals, n_goal, g_mean, g_std,
                        actions, n_action, n_rows, idx, n_idx, x, y);
-    return launched();
+    return launched(no_handle);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@
 // Adam are small HBM-bound kernels around it.
 #include <hip/hip_runtime.h>
 
-#include "nmpc_device_guard.hpp"
+#include "nmpc_host.hpp"
 
 #include <cmath>
 #include <cstdint>
@@ -490,8 +490,8 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, long long n_ro
 namespace {
 
 using namespace nmpc_policy;
-
-thread_local std::string g_policy_create_error;
+using nmpc::fail;
+using nmpc::launched;
 
 struct Policy {
     nmpc_policy_dims d{};
@@ -515,15 +515,7 @@ struct Policy {
     std::string err;
 };
 
-int pfail(Policy* p, int code, const std::string& msg) {
-    if (p) p->err = msg; else g_policy_create_error = msg;
-    return code;
-}
-#define PTRY(p, expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return pfail(p, NMPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+Policy* const no_handle = nullptr;      // for nmpc_policy_create and the calls on plain tensors: errors go to the family's slot
 
 // C[m][n] = sum over the splits, in split order (deterministic)
 __global__ __launch_bounds__(256) void split_reduce_kernel(int M, int N, int splits, const float* __restrict__ part,
@@ -596,16 +588,37 @@ int forward(Policy* p, int B, const float* X, float* out, bool train, hipStream_
     return NMPC_OK;
 }
 
+// the device side of nmpc_policy_create, on the handle's device: buffers of the sizes of p->d, zeroed; what was allocated
+// before an error is nmpc_policy_destroy's to free
+int allocate(Policy* p) {
+    const auto& d = p->d;
+    const size_t L = d.n_hidden, H = d.hidden, Bm = d.batch_max, no = d.n_out, off = p->n_theta;
+    const size_t wide = H > (size_t)d.n_in ? H : (size_t)d.n_in;
+    struct { float** ptr; size_t n; } bufs[] = {
+        {&p->theta, off}, {&p->grad, off}, {&p->m, off}, {&p->v, off},
+        {&p->run_mean, L * H}, {&p->run_var, L * H}, {&p->mu, L * H}, {&p->inv, L * H},
+        {&p->act, L * Bm * H}, {&p->z, L * Bm * H}, {&p->dbuf[0], Bm * wide}, {&p->dbuf[1], Bm * wide},
+        {&p->pred, Bm * no}, {&p->dpred, Bm * no}, {&p->part, 2 * RCHUNK * (H > no ? H : no)},
+        {&p->part_b, L * RCHUNK * H}, {&p->loss_part, (Bm * no + 255) / 256 + 1},
+        {&p->sign_count, no}, {&p->split_ws, SPLIT_WS_FLOATS}};
+    for (auto& b : bufs) {
+        NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(b.ptr), b.n * sizeof(float)));
+        NMPC_TRY(no_handle, hipMemset(*b.ptr, 0, b.n * sizeof(float)));
+    }
+    return NMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int nmpc_policy_create(const nmpc_policy_dims* dims, int device_id, void** handle) {
-    if (!dims || !handle) return pfail(nullptr, NMPC_E_ARG, "null argument");
+    if (!dims || !handle) return fail(no_handle, NMPC_E_ARG, "null argument");
     *handle = nullptr;
-    if (dims->n_out > 256) return pfail(nullptr, NMPC_E_ARG, "n_out <= 256");
+    if (dims->n_out > 256) return fail(no_handle, NMPC_E_ARG, "n_out <= 256");
     if (dims->n_in < 1 || dims->n_out < 1 || dims->hidden < 1 || dims->n_hidden < 1 || dims->n_hidden > 16 || dims->batch_max < 1)
-        return pfail(nullptr, NMPC_E_ARG, "need n_in, n_out, hidden, batch_max >= 1 and 1 <= n_hidden <= 16");
+        return fail(no_handle, NMPC_E_ARG, "need n_in, n_out, hidden, batch_max >= 1 and 1 <= n_hidden <= 16");
+    NMPC_ENTER(no_handle, device_id);
     Policy* p = new Policy();
     p->d = *dims;
     p->d.batch_norm = dims->batch_norm ? 1 : 0;
@@ -621,28 +634,7 @@ int nmpc_policy_create(const nmpc_policy_dims* dims, int device_id, void** handl
     p->oW[L] = off; off += (size_t)dims->n_out * H;
     p->ob[L] = off; off += dims->n_out;
     p->n_theta = off;
-    const size_t Bm = dims->batch_max;
-    const size_t wide = (size_t)(H > dims->n_in ? H : dims->n_in);
-    struct { float** ptr; size_t n; } bufs[] = {
-        {&p->theta, off}, {&p->grad, off}, {&p->m, off}, {&p->v, off},
-        {&p->run_mean, (size_t)L * H}, {&p->run_var, (size_t)L * H}, {&p->mu, (size_t)L * H}, {&p->inv, (size_t)L * H},
-        {&p->act, (size_t)L * Bm * H}, {&p->z, (size_t)L * Bm * H}, {&p->dbuf[0], Bm * wide}, {&p->dbuf[1], Bm * wide},
-        {&p->pred, Bm * dims->n_out}, {&p->dpred, Bm * dims->n_out},
-        {&p->part, (size_t)2 * RCHUNK * (size_t)(H > dims->n_out ? H : dims->n_out)},
-        {&p->part_b, (size_t)L * RCHUNK * H}, {&p->loss_part, (Bm * dims->n_out + 255) / 256 + 1},
-        {&p->sign_count, (size_t)dims->n_out}, {&p->split_ws, SPLIT_WS_FLOATS}};
-    nmpc::DeviceGuard guard(device_id);
-    hipError_t e = guard.err;
-    for (auto& b : bufs) {
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(b.ptr), b.n * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(*b.ptr, 0, b.n * sizeof(float));
-    }
-    if (e != hipSuccess) {
-        g_policy_create_error = std::string("nmpc_policy_create: ") + hipGetErrorString(e);
-        for (auto& b : bufs) if (*b.ptr) (void)hipFree(*b.ptr);
-        delete p;
-        return NMPC_E_HIP;
-    }
+    if (const int rc = allocate(p)) { nmpc_policy_destroy(p); return rc; }
     *handle = p;
     return NMPC_OK;
 }
@@ -650,17 +642,15 @@ int nmpc_policy_create(const nmpc_policy_dims* dims, int device_id, void** handl
 void nmpc_policy_destroy(void* handle) {
     Policy* p = static_cast<Policy*>(handle);
     if (!p) return;
-    nmpc::DeviceGuard guard(p->device);
+    nmpc::DeviceGuard guard(p->device);      // nothing to return: a failed switch goes to the family's slot, the buffers are freed all the same
+    if (guard.err != hipSuccess) fail(no_handle, NMPC_E_HIP, std::string("nmpc_policy_destroy: ") + hipGetErrorString(guard.err));
     float* all[] = {p->theta, p->grad, p->m, p->v, p->run_mean, p->run_var, p->mu, p->inv, p->act, p->z,
                     p->dbuf[0], p->dbuf[1], p->pred, p->dpred, p->part, p->part_b, p->loss_part, p->sign_count, p->split_ws};
     for (float* q : all) if (q) (void)hipFree(q);
     delete p;
 }
 
-const char* nmpc_policy_last_error(void* handle) {
-    Policy* p = static_cast<Policy*>(handle);
-    return p ? p->err.c_str() : g_policy_create_error.c_str();
-}
+const char* nmpc_policy_last_error(void* handle) { return nmpc::last_error(static_cast<Policy*>(handle)); }
 
 size_t nmpc_policy_param_count(void* handle) {
     Policy* p = static_cast<Policy*>(handle);
@@ -670,34 +660,32 @@ size_t nmpc_policy_param_count(void* handle) {
 int nmpc_policy_set_params(void* handle, const float* theta, const float* running_mean, const float* running_var,
                            void* stream) {
     Policy* p = static_cast<Policy*>(handle);
-    if (!p || !theta) return pfail(p, NMPC_E_ARG, "null argument");
-    if (p->d.batch_norm && (!running_mean || !running_var)) return pfail(p, NMPC_E_ARG, "running statistics missing");
+    if (!p || !theta) return fail(p, NMPC_E_ARG, "null argument");
+    if (p->d.batch_norm && (!running_mean || !running_var)) return fail(p, NMPC_E_ARG, "running statistics missing");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    nmpc::DeviceGuard guard(p->device);
-    PTRY(p, guard.err);
-    PTRY(p, hipMemcpyAsync(p->theta, theta, p->n_theta * sizeof(float), hipMemcpyDeviceToDevice, st));
+    NMPC_ENTER(p, p->device);
+    NMPC_TRY(p, hipMemcpyAsync(p->theta, theta, p->n_theta * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (p->d.batch_norm) {
         const size_t n = (size_t)p->d.n_hidden * p->d.hidden * sizeof(float);
-        PTRY(p, hipMemcpyAsync(p->run_mean, running_mean, n, hipMemcpyDeviceToDevice, st));
-        PTRY(p, hipMemcpyAsync(p->run_var, running_var, n, hipMemcpyDeviceToDevice, st));
+        NMPC_TRY(p, hipMemcpyAsync(p->run_mean, running_mean, n, hipMemcpyDeviceToDevice, st));
+        NMPC_TRY(p, hipMemcpyAsync(p->run_var, running_var, n, hipMemcpyDeviceToDevice, st));
     }
-    PTRY(p, hipMemsetAsync(p->m, 0, p->n_theta * sizeof(float), st));
-    PTRY(p, hipMemsetAsync(p->v, 0, p->n_theta * sizeof(float), st));
+    NMPC_TRY(p, hipMemsetAsync(p->m, 0, p->n_theta * sizeof(float), st));
+    NMPC_TRY(p, hipMemsetAsync(p->v, 0, p->n_theta * sizeof(float), st));
     p->step = 0;
     return NMPC_OK;
 }
 
 int nmpc_policy_get_params(void* handle, float* theta, float* running_mean, float* running_var, void* stream) {
     Policy* p = static_cast<Policy*>(handle);
-    if (!p || !theta) return pfail(p, NMPC_E_ARG, "null argument");
+    if (!p || !theta) return fail(p, NMPC_E_ARG, "null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    nmpc::DeviceGuard guard(p->device);
-    PTRY(p, guard.err);
-    PTRY(p, hipMemcpyAsync(theta, p->theta, p->n_theta * sizeof(float), hipMemcpyDeviceToDevice, st));
+    NMPC_ENTER(p, p->device);
+    NMPC_TRY(p, hipMemcpyAsync(theta, p->theta, p->n_theta * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (p->d.batch_norm && running_mean && running_var) {
         const size_t n = (size_t)p->d.n_hidden * p->d.hidden * sizeof(float);
-        PTRY(p, hipMemcpyAsync(running_mean, p->run_mean, n, hipMemcpyDeviceToDevice, st));
-        PTRY(p, hipMemcpyAsync(running_var, p->run_var, n, hipMemcpyDeviceToDevice, st));
+        NMPC_TRY(p, hipMemcpyAsync(running_mean, p->run_mean, n, hipMemcpyDeviceToDevice, st));
+        NMPC_TRY(p, hipMemcpyAsync(running_var, p->run_var, n, hipMemcpyDeviceToDevice, st));
     }
     return NMPC_OK;
 }
@@ -706,36 +694,33 @@ int nmpc_policy_forward(void* handle, int B, const float* X, float* Y, void* str
     Policy* p = static_cast<Policy*>(handle);
     if (!p) return NMPC_E_ARG;
     if (B == 0) return NMPC_OK;
-    if (!X || !Y) return pfail(p, NMPC_E_ARG, "null argument");
-    if (B < 0 || B > p->d.batch_max) return pfail(p, NMPC_E_ARG, "B exceeds batch_max");
+    if (!X || !Y) return fail(p, NMPC_E_ARG, "null argument");
+    if (B < 0 || B > p->d.batch_max) return fail(p, NMPC_E_ARG, "B exceeds batch_max");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    nmpc::DeviceGuard guard(p->device);
-    PTRY(p, guard.err);
+    NMPC_ENTER(p, p->device);
     forward(p, B, X, Y, false, st);
-    PTRY(p, hipGetLastError());
-    return NMPC_OK;
+    return launched(p);
 }
 
 int nmpc_policy_train_step(void* handle, int B, const float* X, const float* Y, float lr, float* loss, float* pred,
                            void* stream) {
     Policy* p = static_cast<Policy*>(handle);
     if (!p) return NMPC_E_ARG;
-    if (!X || !Y) return pfail(p, NMPC_E_ARG, "null argument");
-    if (B < 1 || B > p->d.batch_max) return pfail(p, NMPC_E_ARG, "B out of range");
-    if (p->d.batch_norm && B < 2) return pfail(p, NMPC_E_ARG, "BatchNorm in train mode needs B >= 2");
-    if (!(lr > 0.0f)) return pfail(p, NMPC_E_ARG, "learning rate must be positive");
+    if (!X || !Y) return fail(p, NMPC_E_ARG, "null argument");
+    if (B < 1 || B > p->d.batch_max) return fail(p, NMPC_E_ARG, "B out of range");
+    if (p->d.batch_norm && B < 2) return fail(p, NMPC_E_ARG, "BatchNorm in train mode needs B >= 2");
+    if (!(lr > 0.0f)) return fail(p, NMPC_E_ARG, "learning rate must be positive");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    nmpc::DeviceGuard guard(p->device);
-    PTRY(p, guard.err);
+    NMPC_ENTER(p, p->device);
     const int L = p->d.n_hidden, H = p->d.hidden, no = p->d.n_out;
     const bool bn = p->d.batch_norm != 0;
     if (p->grad_dirty) {                                    // normally both are left zero by adam_kernel
-        PTRY(p, hipMemsetAsync(p->grad, 0, p->n_theta * sizeof(float), st));
-        PTRY(p, hipMemsetAsync(p->sign_count, 0, (size_t)no * sizeof(int), st));
+        NMPC_TRY(p, hipMemsetAsync(p->grad, 0, p->n_theta * sizeof(float), st));
+        NMPC_TRY(p, hipMemsetAsync(p->sign_count, 0, (size_t)no * sizeof(int), st));
     }
     p->grad_dirty = true;
     forward(p, B, X, p->pred, true, st);
-    if (pred) PTRY(p, hipMemcpyAsync(pred, p->pred, (size_t)B * no * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (pred) NMPC_TRY(p, hipMemcpyAsync(pred, p->pred, (size_t)B * no * sizeof(float), hipMemcpyDeviceToDevice, st));
     const size_t np_ = (size_t)B * no;
     hipLaunchKernelGGL(l1_kernel, dim3(blocks_for(np_)), dim3(256), 0, st, np_, no, p->pred, Y, p->dpred, p->loss_part,
                        reinterpret_cast<int*>(p->sign_count));
@@ -777,41 +762,36 @@ int nmpc_policy_train_step(void* handle, int B, const float* X, const float* Y, 
     hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(p->n_theta)), dim3(256), 0, st, p->n_theta, p->theta, p->grad,
                        p->m, p->v, lr, c1, c2, tail);
     p->grad_dirty = false;
-    PTRY(p, hipGetLastError());
-    return NMPC_OK;
+    return launched(p);
 }
 
 int nmpc_weighted_sample(const float* weights, long long n, int num_samples, unsigned long long seed, double* scratch,
                          int* idx, void* stream) {
     if (num_samples == 0) return NMPC_OK;
-    if (!weights || !scratch || !idx) return pfail(nullptr, NMPC_E_ARG, "null argument");
-    if (n < 1 || n > 0x7fffffffLL || num_samples < 0) return pfail(nullptr, NMPC_E_ARG, "need 1 <= n < 2^31, num_samples >= 0");
+    if (!weights || !scratch || !idx) return fail(no_handle, NMPC_E_ARG, "null argument");
+    if (n < 1 || n > 0x7fffffffLL || num_samples < 0) return fail(no_handle, NMPC_E_ARG, "need 1 <= n < 2^31, num_samples >= 0");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     double* cdf = scratch;
     double* tot = scratch + n;                        // nb + 1 doubles
-    nmpc::DeviceGuard guard(nmpc::device_of(weights));
+    NMPC_ENTER(no_handle, nmpc::device_of(weights));
     hipLaunchKernelGGL(scan_block_totals_kernel, dim3((unsigned)nb), dim3(256), 0, st, weights, n, tot);
     hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(64), 0, st, tot, nb);
     hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)nb), dim3(256), 0, st, weights, n, tot, cdf);
     hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((num_samples + 255) / 256)), dim3(256), 0, st, cdf, n, tot + nb,
                        num_samples, seed, idx);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pfail(nullptr, NMPC_E_HIP, hipGetErrorString(e));
-    return NMPC_OK;
+    return launched(no_handle);
 }
 
 int nmpc_gather_rows(const float* src, long long n_rows, int row_len, const int* idx, int n_idx, float* dst, void* stream) {
     if (n_idx == 0) return NMPC_OK;
-    if (!src || !idx || !dst) return pfail(nullptr, NMPC_E_ARG, "null argument");
-    if (row_len < 1 || n_idx < 0 || n_rows < 1) return pfail(nullptr, NMPC_E_ARG, "need n_rows, row_len >= 1, n_idx >= 0");
+    if (!src || !idx || !dst) return fail(no_handle, NMPC_E_ARG, "null argument");
+    if (row_len < 1 || n_idx < 0 || n_rows < 1) return fail(no_handle, NMPC_E_ARG, "need n_rows, row_len >= 1, n_idx >= 0");
     const size_t n = (size_t)n_idx * row_len;
-    nmpc::DeviceGuard guard(nmpc::device_of(src));
+    NMPC_ENTER(no_handle, nmpc::device_of(src));
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        src, n_rows, row_len, idx, n_idx, dst);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pfail(nullptr, NMPC_E_HIP, hipGetErrorString(e));
-    return NMPC_OK;
+    return launched(no_handle);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 // are conflict-free LDS reads.  ~5 kFLOP per robot: the layer is latency-, not throughput-relevant.
 #include <hip/hip_runtime.h>
 
-#include "nmpc_device_guard.hpp"
+#include "nmpc_host.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -337,8 +337,8 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 namespace {
 
 using namespace nmpc_torque;
-
-thread_local std::string g_torque_create_error;
+using nmpc::fail;
+using nmpc::launched;
 
 struct Torque {
     Model host{};
@@ -347,9 +347,16 @@ struct Torque {
     std::string err;
 };
 
-int tfail(Torque* t, int code, const std::string& msg) {
-    if (t) t->err = msg; else g_torque_create_error = msg;
-    return code;
+Torque* const no_handle = nullptr;      // for nmpc_torque_create and calls without a handle: errors go to the family's slot
+
+// the device side of nmpc_torque_create, on the handle's device; what was allocated before an error is nmpc_torque_destroy's to free
+int allocate(Torque* t) {
+    NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&t->dev), sizeof(Model)));
+    NMPC_TRY(no_handle, hipMemcpy(t->dev, &t->host, sizeof(Model), hipMemcpyHostToDevice));
+    // more than the default 64 KB of LDS per block
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(id_torques_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            MAXJ * SLOTS * TPB * (int)sizeof(float)));
+    return NMPC_OK;
 }
 
 }  // namespace
@@ -370,48 +377,37 @@ extern "C" {
 
 int nmpc_torque_create(const nmpc_tree_model* mdl, int device_id, void** handle) {
     if (handle) *handle = nullptr;
-    if (!mdl || !handle) return tfail(nullptr, NMPC_E_ARG, "null argument");
+    if (!mdl || !handle) return fail(no_handle, NMPC_E_ARG, "null argument");
     if (mdl->n_joints < 1 || mdl->n_joints > MAXJ || mdl->n_actuated < 1 || mdl->n_actuated > mdl->n_joints ||
         mdl->n_feet < 0 || mdl->n_feet > MAXF)
-        return tfail(nullptr, NMPC_E_ARG, "need 1 <= n_actuated <= n_joints <= 32, 0 <= n_feet <= 8");
+        return fail(no_handle, NMPC_E_ARG, "need 1 <= n_actuated <= n_joints <= 32, 0 <= n_feet <= 8");
     if (!mdl->parent || !mdl->type || !mdl->axis || !mdl->placement || !mdl->mass || !mdl->com || !mdl->inertia ||
         (mdl->n_feet > 0 && (!mdl->foot_joint || !mdl->foot_offset)))
-        return tfail(nullptr, NMPC_E_ARG, "null model array");
+        return fail(no_handle, NMPC_E_ARG, "null model array");
     Model m{};
     m.n = mdl->n_joints; m.nu = mdl->n_actuated; m.nf = mdl->n_feet;
     for (int i = 0; i < m.n; ++i) {
-        if (mdl->parent[i] < -1 || mdl->parent[i] >= i) return tfail(nullptr, NMPC_E_ARG, "parents must come before their children");
-        if (mdl->type[i] != 0 && mdl->type[i] != 1) return tfail(nullptr, NMPC_E_ARG, "joint type is 0 (revolute) or 1 (prismatic)");
+        if (mdl->parent[i] < -1 || mdl->parent[i] >= i) return fail(no_handle, NMPC_E_ARG, "parents must come before their children");
+        if (mdl->type[i] != 0 && mdl->type[i] != 1) return fail(no_handle, NMPC_E_ARG, "joint type is 0 (revolute) or 1 (prismatic)");
         const float* ax = mdl->axis + 3 * i;
         const float len = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-        if (!(std::fabs(len - 1.0f) < 1e-4f)) return tfail(nullptr, NMPC_E_ARG, "joint axes must be unit vectors");
-        if (!(mdl->mass[i] >= 0.0f)) return tfail(nullptr, NMPC_E_ARG, "negative mass");
+        if (!(std::fabs(len - 1.0f) < 1e-4f)) return fail(no_handle, NMPC_E_ARG, "joint axes must be unit vectors");
+        if (!(mdl->mass[i] >= 0.0f)) return fail(no_handle, NMPC_E_ARG, "negative mass");
         m.parent[i] = mdl->parent[i]; m.type[i] = mdl->type[i]; m.mass[i] = mdl->mass[i];
         std::memcpy(m.axis[i], ax, 12); std::memcpy(m.R[i], mdl->placement + 12 * i, 36);
         std::memcpy(m.p[i], mdl->placement + 12 * i + 9, 12); std::memcpy(m.com[i], mdl->com + 3 * i, 12);
         std::memcpy(m.inertia[i], mdl->inertia + 6 * i, 24);
     }
     for (int k = 0; k < m.nf; ++k) {
-        if (mdl->foot_joint[k] < 0 || mdl->foot_joint[k] >= m.n) return tfail(nullptr, NMPC_E_ARG, "foot_joint out of range");
+        if (mdl->foot_joint[k] < 0 || mdl->foot_joint[k] >= m.n) return fail(no_handle, NMPC_E_ARG, "foot_joint out of range");
         m.foot_joint[k] = mdl->foot_joint[k];
         std::memcpy(m.foot_offset[k], mdl->foot_offset + 3 * k, 12);
     }
     std::memcpy(m.gravity, mdl->gravity, 12);
+    NMPC_ENTER(no_handle, device_id);
     Torque* t = new Torque();
     t->host = m; t->device = device_id;
-    nmpc::DeviceGuard guard(device_id);
-    hipError_t e = guard.err;
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->dev), sizeof(Model));
-    if (e == hipSuccess) e = hipMemcpy(t->dev, &m, sizeof(Model), hipMemcpyHostToDevice);
-    if (e == hipSuccess)                                   // more than the default 64 KB of LDS per block
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(id_torques_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                MAXJ * SLOTS * TPB * (int)sizeof(float));
-    if (e != hipSuccess) {
-        const std::string msg = hipGetErrorString(e);
-        if (t->dev) (void)hipFree(t->dev);
-        delete t;
-        return tfail(nullptr, NMPC_E_HIP, msg);
-    }
+    if (const int rc = allocate(t)) { nmpc_torque_destroy(t); return rc; }
     *handle = t;
     return NMPC_OK;
 }
@@ -419,71 +415,66 @@ int nmpc_torque_create(const nmpc_tree_model* mdl, int device_id, void** handle)
 void nmpc_torque_destroy(void* handle) {
     Torque* t = static_cast<Torque*>(handle);
     if (!t) return;
-    nmpc::DeviceGuard guard(t->device);
+    nmpc::DeviceGuard guard(t->device);      // nothing to return: a failed switch goes to the family's slot, the buffers are freed all the same
+    if (guard.err != hipSuccess) fail(no_handle, NMPC_E_HIP, std::string("nmpc_torque_destroy: ") + hipGetErrorString(guard.err));
     if (t->dev) (void)hipFree(t->dev);
     delete t;
 }
 
-const char* nmpc_torque_last_error(void* handle) {
-    Torque* t = static_cast<Torque*>(handle);
-    return t ? t->err.c_str() : g_torque_create_error.c_str();
-}
+const char* nmpc_torque_last_error(void* handle) { return nmpc::last_error(static_cast<Torque*>(handle)); }
 
 int nmpc_id_torques_batch(void* handle, int B, const float* q, const float* v, const float* a, const float* f, float* tau,
                           void* stream) {
     Torque* t = static_cast<Torque*>(handle);
-    if (!t) return tfail(nullptr, NMPC_E_ARG, "null handle");
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
     if (B == 0) return NMPC_OK;
-    nmpc::DeviceGuard guard(t->device);
-    if (B < 0 || !q || !v || !a || !tau) return tfail(t, NMPC_E_ARG, "need B >= 0 and q, v, a, tau");
+    if (B < 0 || !q || !v || !a || !tau) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, a, tau");
+    NMPC_ENTER(t, t->device);
     const size_t lds = (size_t)t->host.n * SLOTS * TPB * sizeof(float);
     hipLaunchKernelGGL(id_torques_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream),
                        t->dev, B, q, v, a, f, tau);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NMPC_OK : tfail(t, NMPC_E_HIP, hipGetErrorString(e));
+    return launched(t);
 }
 
 int nmpc_pd_torques_batch(void* handle, int B, const float* tau_ff, const float* q, const float* v, const float* q_plan,
                           const float* v_plan, float kp, float kd, float* tau, void* stream) {
     Torque* t = static_cast<Torque*>(handle);
-    if (!t) return tfail(nullptr, NMPC_E_ARG, "null handle");
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
     if (B == 0) return NMPC_OK;
-    nmpc::DeviceGuard guard(t->device);
-    if (B < 0 || !q || !v || !q_plan || !v_plan || !tau) return tfail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_plan, v_plan, tau");
+    if (B < 0 || !q || !v || !q_plan || !v_plan || !tau) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_plan, v_plan, tau");
+    NMPC_ENTER(t, t->device);
     const size_t n = (size_t)B * t->host.nu;
     hipLaunchKernelGGL(pd_torques_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B,
                        t->host.n, t->host.nu, tau_ff, q, v, q_plan, v_plan, kp, kd, tau);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NMPC_OK : tfail(t, NMPC_E_HIP, hipGetErrorString(e));
+    return launched(t);
 }
 
 int nmpc_pd_target_action_batch(void* handle, int B, const float* tau, const int* perm, const float* q, const float* v, float kp,
                                 float kd, float* action, void* stream) {
     Torque* t = static_cast<Torque*>(handle);
-    if (!t) return tfail(nullptr, NMPC_E_ARG, "null handle");
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
     if (B == 0) return NMPC_OK;
-    nmpc::DeviceGuard guard(t->device);
-    if (B < 0 || !tau || !q || !v || !action) return tfail(t, NMPC_E_ARG, "need B >= 0 and tau, q, v, action");
-    if (!(kp != 0.0f)) return tfail(t, NMPC_E_ARG, "kp must not be zero");
+    if (B < 0 || !tau || !q || !v || !action) return fail(t, NMPC_E_ARG, "need B >= 0 and tau, q, v, action");
+    if (!(kp != 0.0f)) return fail(t, NMPC_E_ARG, "kp must not be zero");
+    NMPC_ENTER(t, t->device);
     const size_t n = (size_t)B * t->host.nu;
     hipLaunchKernelGGL(pd_target_action_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        B, t->host.n, t->host.nu, tau, perm, q, v, kp, kd, action);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NMPC_OK : tfail(t, NMPC_E_HIP, hipGetErrorString(e));
+    return launched(t);
 }
 
 int nmpc_plan_actions_batch(void* handle, int B, int n_steps, int N, const float* X, const float* U, const int* zoh, double dt_nodes,
                             double sim_dt, float kp, float kd, const int* perm, const int* skip, int skip_mask, float* A, int a_rows,
                             void* stream) {
     Torque* t = static_cast<Torque*>(handle);
-    if (!t) return tfail(nullptr, NMPC_E_ARG, "null handle");
-    if (const char* why = plan_actions_refusal(handle, n_steps, zoh, kp, -1)) return tfail(t, NMPC_E_ARG, why);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (const char* why = plan_actions_refusal(handle, n_steps, zoh, kp, -1)) return fail(t, NMPC_E_ARG, why);   // a handle fit for plans (include/nmpc_torque.h)
     if (B == 0) return NMPC_OK;
-    if (B < 0 || N < 1 || !X || !U || !A) return tfail(t, NMPC_E_ARG, "need B >= 0, N >= 1 and X, U, A");
-    if (a_rows < n_steps) return tfail(t, NMPC_E_ARG, "a_rows must be at least n_steps");
+    if (B < 0 || N < 1 || !X || !U || !A) return fail(t, NMPC_E_ARG, "need B >= 0, N >= 1 and X, U, A");
+    if (a_rows < n_steps) return fail(t, NMPC_E_ARG, "a_rows must be at least n_steps");
     if (!(dt_nodes > 0.0) || !(sim_dt > 0.0) || n_steps * sim_dt > N * dt_nodes * (1.0 + 1e-9))
-        return tfail(t, NMPC_E_ARG, "need dt_nodes > 0, sim_dt > 0 and n_steps sim_dt within the horizon N dt_nodes");
-    nmpc::DeviceGuard guard(t->device);
+        return fail(t, NMPC_E_ARG, "need dt_nodes > 0, sim_dt > 0 and n_steps sim_dt within the horizon N dt_nodes");
+    NMPC_ENTER(t, t->device);
     PlanArgs p{};
     p.B = B; p.n_steps = n_steps; p.N = N; p.a_rows = a_rows; p.skip_mask = skip ? skip_mask : 0;
     p.dt_nodes = dt_nodes; p.sim_dt = sim_dt; p.kp = kp; p.kd = kd;
@@ -491,8 +482,7 @@ int nmpc_plan_actions_batch(void* handle, int B, int n_steps, int N, const float
     const size_t pairs = (size_t)B * n_steps, lds = (size_t)t->host.n * SLOTS * TPB * sizeof(float);
     hipLaunchKernelGGL(plan_actions_kernel, dim3((unsigned)((pairs + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream),
                        t->dev, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NMPC_OK : tfail(t, NMPC_E_HIP, hipGetErrorString(e));
+    return launched(t);
 }
 
 }  // extern "C"

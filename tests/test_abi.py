@@ -74,8 +74,9 @@ def test_dataset_calls_reject_bad_arguments_on_the_host(lib):
     assert lib.nmpc_assemble_batch(None, 44, None, None, 1, None, 0, None, None, None, 0, 10, None, 0, None, None, None) == 0
 
 
-def test_torque_model_is_validated_on_the_host(lib):
-    """include/nmpc_torque.h: a malformed tree is rejected before any device call."""
+def _torque_create(lib, n_act=2, **over):
+    """nmpc_torque_create on a three-joint chain with one foot, `over` replacing arrays of it: (return code, the family's
+    last error, the handle that came back)"""
     from iterative_learning_nmpc_amd import _lib
     import numpy as np
     n = 3
@@ -83,15 +84,22 @@ def test_torque_model_is_validated_on_the_host(lib):
                placement=np.tile(np.float32([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]), (n, 1)), mass=np.ones(n, np.float32),
                com=np.zeros((n, 3), np.float32), inertia=np.tile(np.float32([1, 0, 0, 1, 0, 1]), (n, 1)),
                foot_joint=np.array([2], np.int32), foot_offset=np.zeros((1, 3), np.float32))
+    a = {k: np.ascontiguousarray(over.get(k, v)) for k, v in arr.items()}
+    m = _lib.NmpcTreeModel()
+    m.n_joints, m.n_actuated, m.n_feet = n, n_act, 1
+    for k, v in a.items():
+        setattr(m, k, v.ctypes.data_as(ctypes.POINTER(ctypes.c_int if v.dtype == np.int32 else ctypes.c_float)))
+    h = ctypes.c_void_p(8)                       # not NULL going in: a failed create has to clear it
+    return lib.nmpc_torque_create(ctypes.byref(m), 0, ctypes.byref(h)), lib.nmpc_torque_last_error(None), h.value
 
-    def create(n_act=2, **over):
-        a = {k: np.ascontiguousarray(over.get(k, v)) for k, v in arr.items()}
-        m = _lib.NmpcTreeModel()
-        m.n_joints, m.n_actuated, m.n_feet = n, n_act, 1
-        for k, v in a.items():
-            setattr(m, k, v.ctypes.data_as(ctypes.POINTER(ctypes.c_int if v.dtype == np.int32 else ctypes.c_float)))
-        h = ctypes.c_void_p()
-        return lib.nmpc_torque_create(ctypes.byref(m), 0, ctypes.byref(h)), lib.nmpc_torque_last_error(None)
+
+def test_torque_model_is_validated_on_the_host(lib):
+    """include/nmpc_torque.h: a malformed tree is rejected before any device call."""
+    import numpy as np
+    n = 3
+
+    def create(**over):
+        return _torque_create(lib, **over)[:2]
 
     assert create(parent=np.array([-1, 2, 1], np.int32)) == (-1, b"parents must come before their children")
     assert create(type=np.array([0, 2, 0], np.int32))[0] == -1
@@ -100,6 +108,36 @@ def test_torque_model_is_validated_on_the_host(lib):
     assert create(n_act=4)[0] == -1
     assert lib.nmpc_torque_create(None, 0, None) == -1
     assert lib.nmpc_id_torques_batch(None, 1, None, None, None, None, None, None) == -1
+
+
+def test_error_slots_are_per_family(lib):
+    """What one family reports never overwrites what another reported last (the calls here fail on the host)."""
+    import numpy as np
+    from iterative_learning_nmpc_amd import _lib
+    one = ctypes.c_void_p(8)
+    assert lib.nmpc_column_stats(one, 10, 65, one, one, one, None) == -1
+    dataset = lib.nmpc_dataset_last_error()
+    rc, torque, _ = _torque_create(lib, parent=np.array([-1, 2, 1], np.int32))
+    assert rc == -1 and torque and dataset
+    dims = _lib.NmpcPolicyDims(4, 257, 1, 8, 0, 4)           # n_out = 257
+    h = ctypes.c_void_p()
+    assert lib.nmpc_policy_create(ctypes.byref(dims), 0, ctypes.byref(h)) == -1
+    assert lib.nmpc_policy_last_error(None)
+    assert lib.nmpc_torque_last_error(None) == torque
+    assert lib.nmpc_dataset_last_error() == dataset
+    assert lib.nmpc_policy_last_error(None) != torque
+
+
+def test_failed_create_leaves_a_null_handle(lib):
+    """policy and torque, as test_create_rejects_bad_dims_on_the_host has it for the solve family"""
+    import numpy as np
+    from iterative_learning_nmpc_amd import _lib
+    h = ctypes.c_void_p(8)
+    dims = _lib.NmpcPolicyDims(4, 257, 1, 8, 0, 4)
+    assert lib.nmpc_policy_create(ctypes.byref(dims), 0, ctypes.byref(h)) == -1
+    assert h.value is None
+    rc, _, handle = _torque_create(lib, parent=np.array([-1, 2, 1], np.int32))
+    assert rc == -1 and handle is None
 
 
 def test_python_layer_refuses_to_run_without_a_device():
