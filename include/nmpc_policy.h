@@ -68,6 +68,41 @@ int nmpc_weighted_sample(const float *weights, long long n, int num_samples, uns
 int nmpc_gather_rows(const float *src, long long n_rows, int row_len, const int *idx, int n_idx, float *dst,
                      void *stream);
 
+/* The tables a batch is assembled from: the arguments of nmpc_assemble_batch (nmpc_dataset.h), with the same
+ * meaning -- s_mean/s_std NULL: states raw; states normalised from column s_first on; g_mean/g_std NULL: goals raw;
+ * n_rows: rows of the three tables. */
+typedef struct {
+    const float *states;  int n_state;  const double *s_mean, *s_std;  int s_first;
+    const float *goals;   int n_goal;   const double *g_mean, *g_std;
+    const float *actions; int n_action;
+    long long n_rows;
+} nmpc_batch_source;
+
+/* One epoch of BehavioralCloning.train_network (DAgger/utils/train_locosafedagger.py:93-102) in one call: n_batches
+ * Adam steps on batches of `batch` rows drawn from src with replacement, row r with probability
+ * weights[r] / sum(weights) (weights: n_rows floats).  Step t trains on rows idx[t*batch + j], j < batch, where idx
+ * is the sequence nmpc_weighted_sample gives for (weights, n_rows, n_batches*batch, seed), assembled as
+ * nmpc_assemble_batch assembles them and stepped as nmpc_policy_train_step steps: parameters, running statistics,
+ * optimiser state and losses are bit for bit those of that chain of calls.  The prefix sums of the weights are made
+ * once per call; a row of weight zero is never drawn.  All-zero or non-finite weights have the behaviour they have
+ * in nmpc_weighted_sample: no guarantee.
+ *   scratch: nmpc_policy_train_epoch_scratch of n_rows doubles (the prefix sums and their block totals: the size
+ *            rule of nmpc_weighted_sample)
+ *   losses:  n_batches floats, the loss BEFORE each step
+ *   idx_out: n_batches*batch ints, the rows drawn, or NULL
+ * Needs src->n_state + src->n_goal == n_in, src->n_action == n_out, 1 <= batch <= batch_max (2 <= batch with
+ * batch_norm), n_batches >= 0 (0: nothing happens), n_batches*batch < 2^31, 1 <= n_rows < 2^31, lr > 0. */
+size_t nmpc_policy_train_epoch_scratch(long long n_rows);
+int nmpc_policy_train_epoch(void *handle, const nmpc_batch_source *src, const float *weights, int batch,
+                            int n_batches, unsigned long long seed, float lr, double *scratch, float *losses,
+                            int *idx_out, void *stream);
+
+/* network.eval(); mean |network(X) - Y| over n rows, n of any size >= 1 (the validation loss of
+ * train_locosafedagger.py:129-132).  X[n][n_in], Y[n][n_out], loss: device scalar.  Parameters, running statistics
+ * and optimiser state are not touched.  The sum runs in a fixed order, in float64 across blocks: the same bits on
+ * every run. */
+int nmpc_policy_loss(void *handle, long long n, const float *X, const float *Y, float *loss, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

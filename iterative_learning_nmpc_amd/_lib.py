@@ -65,6 +65,10 @@ SIGNATURES = {
     "nmpc_policy_train_step": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "nmpc_weighted_sample": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p]),
     "nmpc_gather_rows": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "nmpc_policy_train_epoch_scratch": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "nmpc_policy_train_epoch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_ulonglong, c_float, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    "nmpc_policy_loss": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/nmpc_dataset.h
     "nmpc_dataset_last_error": (ctypes.c_char_p, []),
     "nmpc_ring_append": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
@@ -93,6 +97,12 @@ SIGNATURES = {
 class NmpcPolicyDims(ctypes.Structure):
     _fields_ = [("n_in", c_int), ("n_out", c_int), ("n_hidden", c_int), ("hidden", c_int),
                 ("batch_norm", c_int), ("batch_max", c_int)]
+
+
+class NmpcBatchSource(ctypes.Structure):
+    _fields_ = [("states", c_void_p), ("n_state", c_int), ("s_mean", c_void_p), ("s_std", c_void_p), ("s_first", c_int),
+                ("goals", c_void_p), ("n_goal", c_int), ("g_mean", c_void_p), ("g_std", c_void_p),
+                ("actions", c_void_p), ("n_action", c_int), ("n_rows", ctypes.c_longlong)]
 
 
 class NmpcTreeModel(ctypes.Structure):

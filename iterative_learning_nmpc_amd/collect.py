@@ -28,7 +28,8 @@ def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = No
     Rows of the valid rollouts -- those that no bit of `terminate_mask` ended -- are appended in rollout order with the goal
     the recorder stores (the commanded v_des, one copy per row).  Returns (err [B, K] tracking errors against the nominal
     rollout on the reference's own 44-slot row and its own threshold 4.0, weights [B, K] of
-    `parallel.learning_update`: 0 on invalid rollouts, `ood_weight` where err > 4.0, else 1; rows appended).
+    `parallel.learning_update`: 0 on invalid rollouts, `ood_weight` where err > 4.0, else 1; rows appended).  The weights of
+    the appended rows go into the database with them (`db.weights`).
     After the call `mpc.actions`, `mpc.failed` and the returned S of the rollout are as `open_loop_device` leaves them
     (`mpc.states` keeps S)."""
     S = mpc.open_loop_device(q0, v0, T, push=push, record_sim_steps=True, terminate_mask=terminate_mask, torque_layer=layer,
@@ -46,5 +47,5 @@ def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = No
         # the goal the recorder stores with every row (trajectory_io.TrajectoryRecorder.vc_goals): the rollout's commanded v_des
         goals = torch.as_tensor(np.broadcast_to(np.asarray(mpc.v_des, float), (B, 3)).copy(), dtype=torch.float32).to(S.device)
         db.append(S[keep].reshape(n_rows, S.shape[2]), A[keep].reshape(n_rows, A.shape[2]),
-                  goals[keep].repeat_interleave(K, dim=0))
+                  goals[keep].repeat_interleave(K, dim=0), weights=weights[keep].reshape(n_rows))
     return err, weights, n_rows

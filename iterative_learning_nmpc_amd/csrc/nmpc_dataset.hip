@@ -7,6 +7,7 @@
 // the state table is 1.76 GB: it stays in HBM next to the rollouts that fill it.
 #include <hip/hip_runtime.h>
 
+#include "nmpc_batch_row.hpp"
 #include "nmpc_host.hpp"
 
 #include <algorithm>
@@ -127,32 +128,20 @@ __global__ __launch_bounds__(64 * STAT_SEGS) void colstat_final_kernel(const dou
     }
 }
 
-__global__ void assemble_batch_kernel(const float* __restrict__ states, int n_state, const double* __restrict__ s_mean,
-                                      const double* __restrict__ s_std, int s_first, const float* __restrict__ goals, int n_goal,
-                                      const double* __restrict__ g_mean, const double* __restrict__ g_std,
-                                      const float* __restrict__ actions, int n_action, long long n_rows,
-                                      const int* __restrict__ idx, int n_idx, float* __restrict__ x, float* __restrict__ y) {
-    const int n_x = n_state + n_goal, width = n_x + n_action;
+// one thread per element of [x | y]; the row arithmetic is nmpc_batch::write_element (nmpc_batch_row.hpp), shared with the
+// epoch call of nmpc_policy.hip
+__global__ void assemble_batch_kernel(const nmpc_batch_source t, const int* __restrict__ idx, int n_idx, float* __restrict__ x,
+                                      float* __restrict__ y) {
+    const int n_x = t.n_state + t.n_goal, width = n_x + t.n_action;
     const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (size_t)n_idx * width) return;
     const int i = (int)(e / width), j = (int)(e % width);
     const long long r = idx[i];
-    if (r < 0 || r >= n_rows) {   // never read outside the tables: an index out of range shows up as NaN
-        if (j < n_x) x[(size_t)i * n_x + j] = NAN; else y[(size_t)i * n_action + j - n_x] = NAN;
+    if (r < 0 || r >= t.n_rows) {   // never read outside the tables: an index out of range shows up as NaN
+        if (j < n_x) x[(size_t)i * n_x + j] = NAN; else y[(size_t)i * t.n_action + j - n_x] = NAN;
         return;
     }
-    const size_t row = (size_t)r;
-    if (j < n_state) {
-        const float s = states[row * n_state + j];
-        x[(size_t)i * n_x + j] = (s_mean && j >= s_first) ? (float)(((double)s - s_mean[j]) / s_std[j]) : s;
-    } else if (j < n_x) {
-        const int k = j - n_state;
-        const float g = goals[row * n_goal + k];
-        x[(size_t)i * n_x + j] = g_mean ? (float)(((double)g - g_mean[k]) / g_std[k]) : g;
-    } else {
-        const int k = j - n_x;
-        y[(size_t)i * n_action + k] = actions[row * n_action + k];
-    }
+    nmpc_batch::write_element(t, (size_t)r, i, j, x, y);
 }
 
 }  // namespace nmpc_dataset
@@ -248,10 +237,10 @@ int nmpc_assemble_batch(const float* states, int n_state, const double* s_mean, 
     if ((s_mean == nullptr) != (s_std == nullptr) || (g_mean == nullptr) != (g_std == nullptr))
         return fail(no_handle, NMPC_E_ARG, "mean and std come in pairs");
     NMPC_ENTER(no_handle, nmpc::device_of(states));
+    const nmpc_batch_source src{states, n_state, s_mean, s_std, s_first, goals, n_goal, g_mean, g_std, actions, n_action, n_rows};
     const size_t elems = (size_t)n_idx * (n_state + n_goal + n_action);
     hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), states, n_state, s_mean, s_std, s_first, goals, n_goal, g_mean, g_std,
-                       actions, n_action, n_rows, idx, n_idx, x, y);
+                       static_cast<hipStream_t>(stream), src, idx, n_idx, x, y);
     return launched(no_handle);
 }
 

@@ -8,6 +8,7 @@
 // Adam are small HBM-bound kernels around it.
 #include <hip/hip_runtime.h>
 
+#include "nmpc_batch_row.hpp"
 #include "nmpc_host.hpp"
 
 #include <cmath>
@@ -446,33 +447,54 @@ __global__ __launch_bounds__(256) void scan_write_kernel(const float* __restrict
     for (int e = 0; e < 8; ++e) { run += v[e]; if (base + e < n) cdf[base + e] = run; }
 }
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned& o0, unsigned& o1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o0 = c0; o1 = c1;
-}
-
-// (the total weight is read from the device: no host round trip)
+// one inverse-CDF lookup per sample (nmpc_batch::sample_row, nmpc_batch_row.hpp); the total weight is read from the
+// device: no host round trip
 __global__ void sample_kernel(const double* __restrict__ cdf, long long n, const double* __restrict__ total_ptr,
                                           int num_samples, unsigned long long seed, int* __restrict__ idx) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= num_samples) return;
-    unsigned a, b;
-    philox4x32_10((unsigned)i, 0u, 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32), a, b);
-    const double u = ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);   // 53 bits in [0, 1)
-    const double target = u * total_ptr[0];
-    long long lo = 0, hi = n - 1;                      // first index with cdf > target
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (cdf[mid] > target) hi = mid; else lo = mid + 1;
+    idx[i] = (int)nmpc_batch::sample_row(cdf, n, total_ptr[0], seed, i);
+}
+
+// Sample + assemble of one training batch in one launch: a wave per output row.  Every lane of the wave makes the
+// row's Philox number and runs the lookup (the same addresses in all lanes: one cache line per probe), then the lanes
+// share out the elements of the row and write them, normalised, into the staging x[batch][n_state + n_goal],
+// y[batch][n_action].  Row j of the batch is sample first + j of the seed.
+__global__ __launch_bounds__(256) void sample_assemble_kernel(const nmpc_batch_source t, const double* __restrict__ cdf,
+                                                              const double* __restrict__ total_ptr, unsigned long long seed,
+                                                              int first, int batch, float* __restrict__ x, float* __restrict__ y,
+                                                              int* __restrict__ idx_out) {
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= batch) return;
+    const long long r = nmpc_batch::sample_row(cdf, t.n_rows, total_ptr[0], seed, first + j);
+    if (idx_out && lane == 0) idx_out[first + j] = (int)r;
+    const int width = t.n_state + t.n_goal + t.n_action;
+    for (int e = lane; e < width; e += 64) nmpc_batch::write_element(t, (size_t)r, j, e, x, y);
+}
+
+// Validation loss, one chunk of rows: slot[block] (+)= sum |P - Y| over the block's 256 elements, in float64.  A slot
+// belongs to one block of every chunk and the chunks follow each other on the stream, so a slot adds its chunks up in
+// chunk order without an atomic; the first chunk overwrites what an earlier call left.
+__global__ __launch_bounds__(256) void abs_err_partial_kernel(size_t n, const float* __restrict__ P, const float* __restrict__ Y,
+                                                              double* __restrict__ slot, bool first_chunk) {
+    __shared__ double wsum[4];
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double a = i < n ? (double)fabsf(P[i] - Y[i]) : 0.0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        slot[blockIdx.x] = first_chunk ? s : slot[blockIdx.x] + s;
     }
-    idx[i] = (int)lo;
+}
+// loss = (slot[0] + slot[1] + ...) / count, in slot order
+__global__ void abs_err_final_kernel(const double* __restrict__ slot, int n_slots, double count, float* __restrict__ loss) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int b = 0; b < n_slots; ++b) s += slot[b];
+    loss[0] = (float)(s / count);
 }
 
 __global__ void gather_rows_kernel(const float* __restrict__ src, long long n_rows, int row_len, const int* __restrict__ idx,
@@ -510,6 +532,8 @@ struct Policy {
     float *loss_part = nullptr;   // per-block partial losses of l1_kernel
     float *split_ws = nullptr;    // partial products of the split-K weight-gradient GEMMs [splits][M][N]
     float *sign_count = nullptr;  // int[n_out]: l1_kernel's sign counts (allocated and zeroed with the float buffers)
+    float *stage_x = nullptr, *stage_y = nullptr;   // the epoch call's batch [batch_max][n_in], [batch_max][n_out]
+    float *eval_slot = nullptr;   // double[blocks of a batch_max chunk]: nmpc_policy_loss's partial sums (allocated with the float buffers)
     bool grad_dirty = false;   // a step that did not reach adam_kernel left grad non-zero
     long long step = 0;
     std::string err;
@@ -600,12 +624,79 @@ int allocate(Policy* p) {
         {&p->act, L * Bm * H}, {&p->z, L * Bm * H}, {&p->dbuf[0], Bm * wide}, {&p->dbuf[1], Bm * wide},
         {&p->pred, Bm * no}, {&p->dpred, Bm * no}, {&p->part, 2 * RCHUNK * (H > no ? H : no)},
         {&p->part_b, L * RCHUNK * H}, {&p->loss_part, (Bm * no + 255) / 256 + 1},
-        {&p->sign_count, no}, {&p->split_ws, SPLIT_WS_FLOATS}};
+        {&p->sign_count, no}, {&p->split_ws, SPLIT_WS_FLOATS},
+        {&p->stage_x, Bm * d.n_in}, {&p->stage_y, Bm * no}, {&p->eval_slot, 2 * ((Bm * no + 255) / 256)}};
     for (auto& b : bufs) {
         NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(b.ptr), b.n * sizeof(float)));
         NMPC_TRY(no_handle, hipMemset(*b.ptr, 0, b.n * sizeof(float)));
     }
     return NMPC_OK;
+}
+
+// One Adam step on the L1 loss of the batch X, Y (checked by the entry point, on the handle's device): what
+// nmpc_policy_train_step does, and what nmpc_policy_train_epoch does per batch on the staging buffers.
+int train_step(Policy* p, int B, const float* X, const float* Y, float lr, float* loss, float* pred, hipStream_t st) {
+    const int L = p->d.n_hidden, H = p->d.hidden, no = p->d.n_out;
+    const bool bn = p->d.batch_norm != 0;
+    if (p->grad_dirty) {                                    // normally both are left zero by adam_kernel
+        NMPC_TRY(p, hipMemsetAsync(p->grad, 0, p->n_theta * sizeof(float), st));
+        NMPC_TRY(p, hipMemsetAsync(p->sign_count, 0, (size_t)no * sizeof(int), st));
+    }
+    p->grad_dirty = true;
+    forward(p, B, X, p->pred, true, st);
+    if (pred) NMPC_TRY(p, hipMemcpyAsync(pred, p->pred, (size_t)B * no * sizeof(float), hipMemcpyDeviceToDevice, st));
+    const size_t np_ = (size_t)B * no;
+    hipLaunchKernelGGL(l1_kernel, dim3(blocks_for(np_)), dim3(256), 0, st, np_, no, p->pred, Y, p->dpred, p->loss_part,
+                       reinterpret_cast<int*>(p->sign_count));
+    // output layer: dW = dP' a_L, db = colsum dP, d = dP W
+    const float* aL = p->act + (size_t)(L - 1) * p->d.batch_max * H;
+    gemm<true, true>(st, no, H, B, p->dpred, no, aL, H, p->grad + p->oW[L], H, nullptr, SPLIT_K, p->split_ws);
+    float* d = p->dbuf[0];
+    float* dn = p->dbuf[1];
+    gemm<false, true>(st, B, H, no, p->dpred, no, p->theta + p->oW[L], H, d, H, nullptr);
+    for (int l = L - 1; l >= 0; --l) {
+        const int fan_in = l == 0 ? p->d.n_in : H;
+        const float* z = p->z + (size_t)l * p->d.batch_max * H;
+        const float* a = l == 0 ? X : p->act + (size_t)(l - 1) * p->d.batch_max * H;
+        const float *mu = bn ? p->mu + (size_t)l * H : nullptr, *inv = bn ? p->inv + (size_t)l * H : nullptr;
+        float* dgamma = bn ? p->grad + p->og[l] : nullptr;
+        float* dbeta = bn ? p->grad + p->obe[l] : p->grad + p->ob[l];
+        hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3((H + 63) / 64, RCHUNK), dim3(256), 0, st, B, H, d, z, mu, inv,
+                           bn ? p->theta + p->og[l] : nullptr, bn ? p->theta + p->obe[l] : nullptr, p->part);
+        if (bn) {
+            hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((H + 63) / 64, RCHUNK), dim3(256), 0, st, B, H, d, z, mu, inv,
+                               p->theta + p->og[l], p->part, dgamma, dbeta, p->part_b + (size_t)l * RCHUNK * H);
+        } else {
+            hipLaunchKernelGGL(reduce_final_kernel, dim3((H + 255) / 256), dim3(256), 0, st, H, p->part, dbeta, (float*)nullptr);
+        }
+        gemm<true, true>(st, H, fan_in, B, d, H, a, fan_in, p->grad + p->oW[l], fan_in, nullptr, SPLIT_K, p->split_ws);
+        if (l > 0) {
+            gemm<false, true>(st, B, H, H, d, H, p->theta + p->oW[l], H, dn, H, nullptr);
+            float* t = d; d = dn; dn = t;
+        }
+    }
+    p->step += 1;
+    const float c1 = 1.0f - std::pow(ADAM_B1, (float)p->step), c2 = 1.0f - std::pow(ADAM_B2, (float)p->step);
+    AdamTail tail{};
+    tail.part_b = bn ? p->part_b : nullptr;
+    for (int l = 0; l < L; ++l) tail.ob[l] = p->ob[l];
+    tail.L = L; tail.H = H;
+    tail.loss_part = p->loss_part; tail.n_loss_part = (int)blocks_for(np_); tail.loss = loss;
+    tail.sign_count = reinterpret_cast<int*>(p->sign_count); tail.ob_out = p->ob[L]; tail.n_out = no; tail.n_pred = (float)np_;
+    hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(p->n_theta)), dim3(256), 0, st, p->n_theta, p->theta, p->grad,
+                       p->m, p->v, lr, c1, c2, tail);
+    p->grad_dirty = false;
+    return launched(p);
+}
+
+// fp64 inclusive prefix sums of w[0..n) to scratch[0..n); returns where their total is (scratch[n + blocks])
+const double* build_cdf(hipStream_t st, const float* w, long long n, double* scratch) {
+    const long long nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    double* tot = scratch + n;                        // nb + 1 doubles
+    hipLaunchKernelGGL(scan_block_totals_kernel, dim3((unsigned)nb), dim3(256), 0, st, w, n, tot);
+    hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(64), 0, st, tot, nb);
+    hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)nb), dim3(256), 0, st, w, n, tot, scratch);
+    return tot + nb;
 }
 
 }  // namespace
@@ -645,7 +736,8 @@ void nmpc_policy_destroy(void* handle) {
     nmpc::DeviceGuard guard(p->device);      // nothing to return: a failed switch goes to the family's slot, the buffers are freed all the same
     if (guard.err != hipSuccess) fail(no_handle, NMPC_E_HIP, std::string("nmpc_policy_destroy: ") + hipGetErrorString(guard.err));
     float* all[] = {p->theta, p->grad, p->m, p->v, p->run_mean, p->run_var, p->mu, p->inv, p->act, p->z,
-                    p->dbuf[0], p->dbuf[1], p->pred, p->dpred, p->part, p->part_b, p->loss_part, p->sign_count, p->split_ws};
+                    p->dbuf[0], p->dbuf[1], p->pred, p->dpred, p->part, p->part_b, p->loss_part, p->sign_count, p->split_ws,
+                    p->stage_x, p->stage_y, p->eval_slot};
     for (float* q : all) if (q) (void)hipFree(q);
     delete p;
 }
@@ -710,59 +802,8 @@ int nmpc_policy_train_step(void* handle, int B, const float* X, const float* Y, 
     if (B < 1 || B > p->d.batch_max) return fail(p, NMPC_E_ARG, "B out of range");
     if (p->d.batch_norm && B < 2) return fail(p, NMPC_E_ARG, "BatchNorm in train mode needs B >= 2");
     if (!(lr > 0.0f)) return fail(p, NMPC_E_ARG, "learning rate must be positive");
-    hipStream_t st = static_cast<hipStream_t>(stream);
     NMPC_ENTER(p, p->device);
-    const int L = p->d.n_hidden, H = p->d.hidden, no = p->d.n_out;
-    const bool bn = p->d.batch_norm != 0;
-    if (p->grad_dirty) {                                    // normally both are left zero by adam_kernel
-        NMPC_TRY(p, hipMemsetAsync(p->grad, 0, p->n_theta * sizeof(float), st));
-        NMPC_TRY(p, hipMemsetAsync(p->sign_count, 0, (size_t)no * sizeof(int), st));
-    }
-    p->grad_dirty = true;
-    forward(p, B, X, p->pred, true, st);
-    if (pred) NMPC_TRY(p, hipMemcpyAsync(pred, p->pred, (size_t)B * no * sizeof(float), hipMemcpyDeviceToDevice, st));
-    const size_t np_ = (size_t)B * no;
-    hipLaunchKernelGGL(l1_kernel, dim3(blocks_for(np_)), dim3(256), 0, st, np_, no, p->pred, Y, p->dpred, p->loss_part,
-                       reinterpret_cast<int*>(p->sign_count));
-    // output layer: dW = dP' a_L, db = colsum dP, d = dP W
-    const float* aL = p->act + (size_t)(L - 1) * p->d.batch_max * H;
-    gemm<true, true>(st, no, H, B, p->dpred, no, aL, H, p->grad + p->oW[L], H, nullptr, SPLIT_K, p->split_ws);
-    float* d = p->dbuf[0];
-    float* dn = p->dbuf[1];
-    gemm<false, true>(st, B, H, no, p->dpred, no, p->theta + p->oW[L], H, d, H, nullptr);
-    for (int l = L - 1; l >= 0; --l) {
-        const int fan_in = l == 0 ? p->d.n_in : H;
-        const float* z = p->z + (size_t)l * p->d.batch_max * H;
-        const float* a = l == 0 ? X : p->act + (size_t)(l - 1) * p->d.batch_max * H;
-        const float *mu = bn ? p->mu + (size_t)l * H : nullptr, *inv = bn ? p->inv + (size_t)l * H : nullptr;
-        float* dgamma = bn ? p->grad + p->og[l] : nullptr;
-        float* dbeta = bn ? p->grad + p->obe[l] : p->grad + p->ob[l];
-        hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3((H + 63) / 64, RCHUNK), dim3(256), 0, st, B, H, d, z, mu, inv,
-                           bn ? p->theta + p->og[l] : nullptr, bn ? p->theta + p->obe[l] : nullptr, p->part);
-        if (bn) {
-            hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((H + 63) / 64, RCHUNK), dim3(256), 0, st, B, H, d, z, mu, inv,
-                               p->theta + p->og[l], p->part, dgamma, dbeta, p->part_b + (size_t)l * RCHUNK * H);
-        } else {
-            hipLaunchKernelGGL(reduce_final_kernel, dim3((H + 255) / 256), dim3(256), 0, st, H, p->part, dbeta, (float*)nullptr);
-        }
-        gemm<true, true>(st, H, fan_in, B, d, H, a, fan_in, p->grad + p->oW[l], fan_in, nullptr, SPLIT_K, p->split_ws);
-        if (l > 0) {
-            gemm<false, true>(st, B, H, H, d, H, p->theta + p->oW[l], H, dn, H, nullptr);
-            float* t = d; d = dn; dn = t;
-        }
-    }
-    p->step += 1;
-    const float c1 = 1.0f - std::pow(ADAM_B1, (float)p->step), c2 = 1.0f - std::pow(ADAM_B2, (float)p->step);
-    AdamTail tail{};
-    tail.part_b = bn ? p->part_b : nullptr;
-    for (int l = 0; l < L; ++l) tail.ob[l] = p->ob[l];
-    tail.L = L; tail.H = H;
-    tail.loss_part = p->loss_part; tail.n_loss_part = (int)blocks_for(np_); tail.loss = loss;
-    tail.sign_count = reinterpret_cast<int*>(p->sign_count); tail.ob_out = p->ob[L]; tail.n_out = no; tail.n_pred = (float)np_;
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(p->n_theta)), dim3(256), 0, st, p->n_theta, p->theta, p->grad,
-                       p->m, p->v, lr, c1, c2, tail);
-    p->grad_dirty = false;
-    return launched(p);
+    return train_step(p, B, X, Y, lr, loss, pred, static_cast<hipStream_t>(stream));
 }
 
 int nmpc_weighted_sample(const float* weights, long long n, int num_samples, unsigned long long seed, double* scratch,
@@ -771,16 +812,66 @@ int nmpc_weighted_sample(const float* weights, long long n, int num_samples, uns
     if (!weights || !scratch || !idx) return fail(no_handle, NMPC_E_ARG, "null argument");
     if (n < 1 || n > 0x7fffffffLL || num_samples < 0) return fail(no_handle, NMPC_E_ARG, "need 1 <= n < 2^31, num_samples >= 0");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const long long nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    double* cdf = scratch;
-    double* tot = scratch + n;                        // nb + 1 doubles
     NMPC_ENTER(no_handle, nmpc::device_of(weights));
-    hipLaunchKernelGGL(scan_block_totals_kernel, dim3((unsigned)nb), dim3(256), 0, st, weights, n, tot);
-    hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(64), 0, st, tot, nb);
-    hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)nb), dim3(256), 0, st, weights, n, tot, cdf);
-    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((num_samples + 255) / 256)), dim3(256), 0, st, cdf, n, tot + nb,
+    const double* total = build_cdf(st, weights, n, scratch);
+    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((num_samples + 255) / 256)), dim3(256), 0, st, scratch, n, total,
                        num_samples, seed, idx);
     return launched(no_handle);
+}
+
+size_t nmpc_policy_train_epoch_scratch(long long n_rows) {
+    return n_rows < 1 ? 0 : (size_t)n_rows + (size_t)(n_rows / SCAN_CHUNK) + 2;
+}
+
+int nmpc_policy_train_epoch(void* handle, const nmpc_batch_source* src, const float* weights, int batch, int n_batches,
+                            unsigned long long seed, float lr, double* scratch, float* losses, int* idx_out, void* stream) {
+    Policy* p = static_cast<Policy*>(handle);
+    if (!p) return fail(p, NMPC_E_ARG, "null handle");
+    if (n_batches == 0) return NMPC_OK;
+    if (!src || !weights || !scratch || !losses) return fail(p, NMPC_E_ARG, "null argument");
+    if (!src->states || !src->actions || (src->n_goal > 0 && !src->goals)) return fail(p, NMPC_E_ARG, "null table");
+    if (src->n_state < 1 || src->n_goal < 0 || src->s_first < 0) return fail(p, NMPC_E_ARG, "need n_state >= 1, n_goal, s_first >= 0");
+    if (src->n_state + src->n_goal != p->d.n_in || src->n_action != p->d.n_out)
+        return fail(p, NMPC_E_ARG, "row widths: need n_state + n_goal == n_in and n_action == n_out");
+    if ((src->s_mean == nullptr) != (src->s_std == nullptr) || (src->g_mean == nullptr) != (src->g_std == nullptr))
+        return fail(p, NMPC_E_ARG, "mean and std come in pairs");
+    if (batch < 1 || batch > p->d.batch_max) return fail(p, NMPC_E_ARG, "batch out of range: need 1 <= batch <= batch_max");
+    if (p->d.batch_norm && batch < 2) return fail(p, NMPC_E_ARG, "BatchNorm in train mode needs batch >= 2");
+    if (n_batches < 0 || (long long)n_batches * batch > 0x7fffffffLL) return fail(p, NMPC_E_ARG, "need 0 <= n_batches * batch < 2^31");
+    if (src->n_rows < 1 || src->n_rows > 0x7fffffffLL) return fail(p, NMPC_E_ARG, "need 1 <= n_rows < 2^31");
+    if (!(lr > 0.0f)) return fail(p, NMPC_E_ARG, "learning rate must be positive");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    NMPC_ENTER(p, p->device);
+    const double* total = build_cdf(st, weights, src->n_rows, scratch);
+    for (int t = 0; t < n_batches; ++t) {
+        hipLaunchKernelGGL(sample_assemble_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, *src, scratch, total, seed,
+                           t * batch, batch, p->stage_x, p->stage_y, idx_out);
+        if (const int rc = train_step(p, batch, p->stage_x, p->stage_y, lr, losses + t, nullptr, st)) return rc;
+    }
+    return launched(p);
+}
+
+int nmpc_policy_loss(void* handle, long long n, const float* X, const float* Y, float* loss, void* stream) {
+    Policy* p = static_cast<Policy*>(handle);
+    if (!p) return fail(p, NMPC_E_ARG, "null handle");
+    if (n < 1) return fail(p, NMPC_E_ARG, "need n >= 1");      // (in front of the pointers: tensors without rows have no storage)
+    if (!X || !Y || !loss) return fail(p, NMPC_E_ARG, "null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    NMPC_ENTER(p, p->device);
+    const long long Bm = p->d.batch_max;
+    const int ni = p->d.n_in, no = p->d.n_out;
+    double* slot = reinterpret_cast<double*>(p->eval_slot);
+    for (long long r0 = 0; r0 < n; r0 += Bm) {
+        const int B = (int)(n - r0 < Bm ? n - r0 : Bm);
+        forward(p, B, X + (size_t)r0 * ni, p->pred, false, st);
+        const size_t np_ = (size_t)B * no;
+        hipLaunchKernelGGL(abs_err_partial_kernel, dim3(blocks_for(np_)), dim3(256), 0, st, np_, p->pred, Y + (size_t)r0 * no, slot,
+                           r0 == 0);
+    }
+    // the first chunk is the longest: it wrote every slot a later one adds to
+    const int n_slots = (int)blocks_for((size_t)(n < Bm ? n : Bm) * no);
+    hipLaunchKernelGGL(abs_err_final_kernel, dim3(1), dim3(64), 0, st, slot, n_slots, (double)n * (double)no, loss);
+    return launched(p);
 }
 
 int nmpc_gather_rows(const float* src, long long n_rows, int row_len, const int* idx, int n_idx, float* dst, void* stream) {

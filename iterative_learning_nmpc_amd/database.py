@@ -9,7 +9,12 @@ one `(x, y)` item per `__getitem__` call, `batch(idx)` assembles a whole normali
 idx typically comes from `policy.weighted_sample` -- ready for `DevicePolicy.train_step`.
 
 Rows are stored in fp32 (what the rollout kernels produce and the network consumes); the statistics are
-float64 like numpy's.  Indices are PHYSICAL ring positions, as in the reference (`self.states[index]`)."""
+float64 like numpy's.  Indices are PHYSICAL ring positions, as in the reference (`self.states[index]`).
+
+Beside the reference's four fields every row carries a sampling weight (`weights`, fp32 [limit]: the out-of-distribution
+weight `collect.collect_rollouts` computed for it, 1 where none was given).  It rides the ring with the row, so after any
+number of appends and wraps `weights[i]` is the weight of physical row i -- what the weighted sampler of
+`DevicePolicy.train_epoch` needs.  It is no field of the file schema: npz files are the reference's."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -47,6 +52,7 @@ class DeviceDatabase:
         self.limit, self.length, self.start = int(limit), 0, 0
         self.widths = {"states": n_state, "vc_goals": n_vc_goal, "cc_goals": n_cc_goal, "actions": n_action}
         self.tables = {f: torch.zeros(self.limit, w, dtype=torch.float32, device=self.device) for f, w in self.widths.items()}
+        self.weights = torch.zeros(self.limit, dtype=torch.float32, device=self.device)
         self.has = {"vc_goals": False, "cc_goals": False}
         self.norm_input, self.goal_type = bool(norm_input), goal_type
         self.states_mean = self.states_std = None          # float64 device vectors
@@ -64,8 +70,9 @@ class DeviceDatabase:
         self.goal_type = value
 
     # ------------------------------------------------------------------ aggregation
-    def append(self, states, actions, vc_goals=None, cc_goals=None):
-        """database.py:105-154.  Arguments: device (or host) arrays [n, width]."""
+    def append(self, states, actions, vc_goals=None, cc_goals=None, weights=None):
+        """database.py:105-154.  Arguments: device (or host) arrays [n, width]; weights: [n] sampling weights of the rows
+        (None: ones)."""
         if vc_goals is None and cc_goals is None:
             raise ValueError("both vc_goals and cc_goals cant be empty!")
         lib = _lib.load()
@@ -79,7 +86,14 @@ class DeviceDatabase:
                 raise ValueError(f"{f}: expected [{n if n is not None else 'n'}, {self.widths[f]}], got {tuple(a.shape)}")
             n = a.shape[0]
             given[f] = a
+        if weights is None:
+            weights = torch.ones(n, dtype=torch.float32, device=self.device)
+        weights = torch.as_tensor(weights, dtype=torch.float32, device=self.device).contiguous()
+        if weights.shape != (n,):
+            raise ValueError(f"weights: expected [{n}], got {tuple(weights.shape)}")
         first_slot = (self.start + self.length) % self.limit
+        _lib.check(lib.nmpc_ring_append(ptr(weights), 1, n, ptr(self.weights), self.limit, first_slot, stream(self.device)),
+                   None, "nmpc_ring_append", "dataset")
         for f, a in given.items():
             if a is None:
                 continue
@@ -110,27 +124,34 @@ class DeviceDatabase:
         return out + [self.cc_goals_mean.cpu().numpy(), self.cc_goals_std.cpu().numpy()]
 
     # ------------------------------------------------------------------ batches
-    def batch(self, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """x[i] = hstack(state_norm, goal)[idx[i]], y[i] = actions[idx[i]] as fp32 (database.py:54-84 and
-        the `.float()` of train_locosafedagger.py:95) for int32 device indices."""
-        lib = _lib.load()
-        assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 1
+    def batch_source(self) -> _lib.NmpcBatchSource:
+        """What a batch is assembled from under the current goal type and normalisation switch (nmpc_batch_source of
+        include/nmpc_policy.h): the tables and statistics `batch` reads, and `DevicePolicy.train_epoch` with it.  The
+        pointers are the database's own tensors: use it before the next append."""
         if self.length == 0:
             raise IndexError("the database is empty")
         goal_field = "vc_goals" if self.goal_type == "vc" else "cc_goals"
         if not self.has[goal_field]:
             raise ValueError(f"no {goal_field} were appended")
-        n_state, n_goal, n_action = self.widths["states"], self.widths[goal_field], self.widths["actions"]
-        x = torch.empty(idx.numel(), n_state + n_goal, dtype=torch.float32, device=self.device)
-        y = torch.empty(idx.numel(), n_action, dtype=torch.float32, device=self.device)
         s_mean = s_std = g_mean = g_std = None
         if self.norm_input:
             s_mean, s_std = self.states_mean, self.states_std
             if self.goal_type == "cc":
                 g_mean, g_std = self.cc_goals_mean, self.cc_goals_std
-        _lib.check(lib.nmpc_assemble_batch(ptr(self.tables["states"]), n_state, ptr(s_mean), ptr(s_std), 1,
-                                           ptr(self.tables[goal_field]), n_goal, ptr(g_mean), ptr(g_std),
-                                           ptr(self.tables["actions"]), n_action, self.length, ptr(idx), idx.numel(),
+        return _lib.NmpcBatchSource(ptr(self.tables["states"]), self.widths["states"], ptr(s_mean), ptr(s_std), 1,
+                                    ptr(self.tables[goal_field]), self.widths[goal_field], ptr(g_mean), ptr(g_std),
+                                    ptr(self.tables["actions"]), self.widths["actions"], self.length)
+
+    def batch(self, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """x[i] = hstack(state_norm, goal)[idx[i]], y[i] = actions[idx[i]] as fp32 (database.py:54-84 and
+        the `.float()` of train_locosafedagger.py:95) for int32 device indices."""
+        lib = _lib.load()
+        assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 1
+        s = self.batch_source()
+        x = torch.empty(idx.numel(), s.n_state + s.n_goal, dtype=torch.float32, device=self.device)
+        y = torch.empty(idx.numel(), s.n_action, dtype=torch.float32, device=self.device)
+        _lib.check(lib.nmpc_assemble_batch(s.states, s.n_state, s.s_mean, s.s_std, s.s_first, s.goals, s.n_goal, s.g_mean,
+                                           s.g_std, s.actions, s.n_action, s.n_rows, ptr(idx), idx.numel(),
                                            ptr(x), ptr(y), stream(self.device)), None, "nmpc_assemble_batch", "dataset")
         return x, y
 
@@ -153,6 +174,7 @@ class DeviceDatabase:
             if a.shape != (n, self.widths[f]):
                 raise ValueError(f"{f}: expected {(n, self.widths[f])}, got {a.shape}")
             self.tables[f][:n] = torch.from_numpy(a).to(self.device)
+        self.weights[:n] = 1.0
         self.has = {"vc_goals": True, "cc_goals": True}
         self.length, self.start = n, 0
         self.calc_input_mean_std()

@@ -1,0 +1,79 @@
+"""Policy training from the device-resident database, and one whole learning iteration.
+
+    BehavioralCloning.train_network     DAgger/utils/train_locosafedagger.py:66-138   -> train_network
+    one DAgger iteration: roll the expert out, aggregate, train
+        DAgger/utils/data_collection_locosafedagger.py:92-131                         -> learning_iteration
+
+The pieces are `collect.collect_rollouts` (rollouts -> `DeviceDatabase`, with the out-of-distribution weight of every
+row), `DevicePolicy.train_epoch` (an epoch of weighted batches in one library call) and `DevicePolicy.loss` (the
+validation loss).  No table, batch, index or loss passes through the host, and nothing here waits for the device: what
+comes back are device tensors.
+
+Declared choices:
+  * Sampling is WITH replacement, as the reference's WeightedRandomSampler loader draws
+    (Behavior_Cloning/examples/test_train_policy.py:128-134) -- also when every weight is 1, where the reference's plain
+    loader would shuffle without replacement.  An epoch is ceil(n_train / batch_size) full batches.
+  * The validation rows stay in the tables and get weight ZERO in a copy of the weight vector: the inverse-CDF lookup
+    returns the first row whose prefix sum exceeds the target, which a row that adds nothing to the sum never is.  So
+    the split needs no compaction of the tables, and the database's own weights are left as they are.
+  * `learning_iteration` validates on the LAST floor(val_fraction * len(db)) physical rows of the database after the
+    append (on a ring that has not wrapped: the newest rows)."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from .collect import collect_rollouts
+from .config import TERMINATE_DEFAULT
+from .trajectory_io import KD, KP
+
+
+def train_network(policy, db, n_epoch: int, batch_size: int, lr: float = 1e-3, seed: int = 0,
+                  val_idx: Optional[torch.Tensor] = None):
+    """`n_epoch` epochs of `policy` (a `DevicePolicy`) on `db` (a `DeviceDatabase`), rows drawn by `db.weights`.
+
+    Epoch e is `policy.train_epoch` with seed `seed + e` over ceil(n_train / batch_size) batches, followed by the
+    validation loss on the rows `val_idx` (distinct physical ring positions, int32 or int64, host or device), which are
+    assembled once with `db.batch` and never trained on.  Returns (train_loss [n_epoch, n_batches], val_loss [n_epoch])
+    on the device; without validation rows val_loss is NaN."""
+    n = len(db)
+    weights = db.weights[:n].clone()
+    n_val = 0
+    if val_idx is not None:
+        val_idx = torch.as_tensor(val_idx, device=db.device).to(torch.int32).contiguous()
+        n_val = int(val_idx.numel())
+    if n_val:
+        weights[val_idx.long()] = 0.0
+        x_val, y_val = db.batch(val_idx)
+    n_train = n - n_val
+    if n_train < 1:
+        raise ValueError(f"no training rows: {n} rows in the database, {n_val} of them for validation")
+    n_batches = -(-n_train // int(batch_size))
+    train_loss = torch.empty(n_epoch, n_batches, dtype=torch.float32, device=db.device)
+    val_loss = torch.full((n_epoch,), float("nan"), dtype=torch.float32, device=db.device)
+    for e in range(n_epoch):
+        train_loss[e] = policy.train_epoch(db, batch_size, n_batches, lr, seed + e, weights=weights)
+        if n_val:
+            val_loss[e:e + 1] = policy.loss(x_val, y_val)
+    return train_loss, val_loss
+
+
+def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[dict] = None, nominal: int = 0,
+                       ood_weight: float = 5.0, terminate_mask: int = TERMINATE_DEFAULT, kp: float = KP, kd: float = KD,
+                       n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0):
+    """One DAgger iteration, from rollouts to updated parameters: `collect.collect_rollouts` (its arguments up to `kd`)
+    appends the valid rollouts and their weights to `db`, then `train_network` trains `policy` on all of `db`, validating
+    on its last floor(val_fraction * len(db)) physical rows.  Returns (err, weights, n_rows, train_loss, val_loss): what
+    the two parts return."""
+    if not 0.0 <= val_fraction < 1.0:
+        raise ValueError("val_fraction must be in [0, 1)")
+    err, weights, n_rows = collect_rollouts(mpc, layer, db, q0, v0, T, push=push, nominal=nominal, ood_weight=ood_weight,
+                                            terminate_mask=terminate_mask, kp=kp, kd=kd)
+    n = len(db)
+    if n == 0:
+        raise ValueError("the database is empty: no rollout of the batch was valid")
+    n_val = int(val_fraction * n)
+    val_idx = torch.arange(n - n_val, n, dtype=torch.int32, device=db.device) if n_val else None
+    train_loss, val_loss = train_network(policy, db, n_epoch, batch_size, lr=lr, seed=seed, val_idx=val_idx)
+    return err, weights, n_rows, train_loss, val_loss

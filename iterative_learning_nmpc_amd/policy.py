@@ -4,6 +4,10 @@
         DAgger/utils/network.py:7-81          -> DevicePolicy (forward = eval mode)
     BehavioralCloning.train_network, inner loop   DAgger/utils/train_locosafedagger.py:93-102
         -> DevicePolicy.train_step(x, y, lr)   (L1 loss, Adam)
+    one epoch of that loop over a weighted loader   train_locosafedagger.py:93-102
+        -> DevicePolicy.train_epoch(db, batch_size, n_batches, lr, seed)
+    the validation loss of an epoch                 train_locosafedagger.py:129-132
+        -> DevicePolicy.loss(x, y)
 
 The kernels are in csrc/nmpc_policy.hip behind include/nmpc_policy.h; tensors stay on the device
 (torch is the container only).  There is no CPU path."""
@@ -136,6 +140,38 @@ class DevicePolicy:
         _lib.check(self.lib.nmpc_policy_train_step(self._h, B, ptr(x), ptr(y), float(lr), ptr(loss), ptr(pred),
                                                    stream(self.device)), self._h, "nmpc_policy_train_step", "policy")
         return (loss, pred) if return_pred else loss
+
+    def train_epoch(self, db, batch_size: int, n_batches: int, lr: float, seed: int, weights: Optional[torch.Tensor] = None,
+                    return_idx: bool = False):
+        """`n_batches` training steps in one library call (train_locosafedagger.py:93-102 over a WeightedRandomSampler
+        loader): step t trains on `db.batch(idx[t])` with idx = weighted_sample(weights, n_batches * batch_size,
+        seed).reshape(n_batches, batch_size), bit for bit, but the prefix sums of the weights are made once, and index,
+        batch and staging tensors never surface.  db: a `DeviceDatabase` (its goal type and normalisation switch as in
+        `db.batch`); weights: fp32 [len(db)] on the device, default `db.weights[:len(db)]`; a row of weight zero is never
+        drawn.  Returns the losses before each step as a device vector [n_batches] (and idx [n_batches, batch_size],
+        int32)."""
+        src = db.batch_source()
+        n = len(db)
+        w = db.weights[:n] if weights is None else weights
+        assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.shape == (n,)
+        scratch = torch.empty(self.lib.nmpc_policy_train_epoch_scratch(n), dtype=torch.float64, device=self.device)
+        losses = torch.empty(n_batches, dtype=torch.float32, device=self.device)
+        idx = torch.empty(n_batches, batch_size, dtype=torch.int32, device=self.device) if return_idx else None
+        _lib.check(self.lib.nmpc_policy_train_epoch(self._h, ctypes.byref(src), ptr(w), int(batch_size), int(n_batches),
+                                                    int(seed) & (2 ** 64 - 1), float(lr), ptr(scratch), ptr(losses), ptr(idx),
+                                                    stream(self.device)), self._h, "nmpc_policy_train_epoch", "policy")
+        return (losses, idx) if return_idx else losses
+
+    def loss(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """network.eval(); L1Loss(network(x), y) as a device scalar, for any number of rows (the validation loss of
+        train_locosafedagger.py:129-132); nothing of the policy changes."""
+        n = x.shape[0]
+        assert x.is_cuda and y.is_cuda and x.dtype == y.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous()
+        assert x.shape == (n, self.dims[0]) and y.shape == (n, self.dims[1])
+        out = torch.empty(1, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nmpc_policy_loss(self._h, n, ptr(x), ptr(y), ptr(out), stream(self.device)), self._h,
+                   "nmpc_policy_loss", "policy")
+        return out
 
 
 def weighted_sample(weights: torch.Tensor, num_samples: int, seed: int) -> torch.Tensor:
