@@ -15,7 +15,7 @@
 // Jacobian code wants hundreds of VGPRs; fused, it forced the MFMA accumulators of the sweeps
 // through AGPR<->VGPR copies and pinned the kernel at one wave per SIMD).
 // Stage matrices A~, B~, K~, Acl~ live in an HBM/L2 workspace as compact images (640-768 B);
-// trajectories, gradients and IPM state of a problem live in LDS (39.6 KB at N = 50) inside
+// trajectories, gradients and IPM state of a problem live in LDS (39.9 KB at N = 50) inside
 // nmpc_qp_kernel -- or, in its lean variant for batches beyond one wave per SIMD, partly in the workspace (Lds).
 // Kernel variants (template flags): LDS layout, precision of the barrier product, set of contact
 // patterns with a static stage body.  DESIGN.md 5 has the measurements behind each choice.
@@ -247,7 +247,7 @@ __host__ __device__ constexpr bool qp_linearizes_itself(bool lean, int N) { retu
 #endif
 
 // LDS layout of one problem.  Two variants of the QP kernel:
-//   resident (LEAN = false): stage arrays + sweep operands + conversion tiles, 39.6 KB at N = 50 ->
+//   resident (LEAN = false): stage arrays + sweep operands + run schedule + conversion tiles, 39.9 KB at N = 50 ->
 //       4 waves per CU, one per SIMD: the choice while the batch fits that many waves (B <= 1024 on an MI355X);
 //   lean (LEAN = true): the stage arrays live in the workspace (stage-major rows), 17.8 KB -> 8 waves per CU, two per
 //       SIMD: the choice for larger batches (the second wave fills the first one's dependency stalls: 2.7 M solves/s
@@ -255,7 +255,7 @@ __host__ __device__ constexpr bool qp_linearizes_itself(bool lean, int N) { retu
 // Same arithmetic in the same order: results are bit-identical (tests/test_gpu_parity.py).  DESIGN.md 7.
 template <class M, bool LEAN>
 struct Lds {
-    int arr, qv, rv, gsq, gvt, act, umk, conv, dx0, total;   // float offsets
+    int arr, qv, rv, gsq, gvt, act, umk, runs, conv, dx0, total;   // float offsets
     __host__ __device__ explicit Lds(int N) {
         const int NS = (N + 1) | 1;
         int o = 0;
@@ -268,6 +268,7 @@ struct Lds {
         gvt = o; o += N * TS;
         act = o; o += round4(NS);
         umk = o; o += round4(NS);
+        runs = o; o += LEAN ? 0 : round4(N + 1);  // run-length schedule of the backward sweep (resident): at most N runs and the end word
         conv = o; o += CONV_FLOATS;
         dx0 = o; o += LEAN ? TS : 0;              // lean: x0 - X[0], read at the start of every forward sweep
         total = o;
@@ -677,6 +678,48 @@ void nmpc_qp_kernel(const SolveArgs a) {
     }
     const bool is_hx_col = (c == HS);
     phase_sync();
+    // Run-length schedule of the backward sweeps: the stages N-1 .. 0 as runs of ONE stage body, so that the sweep picks a
+    // body once per run and the loop over a run's stages holds nothing but that body.  A run word is
+    //   top (bits 0..8: first stage of the run + 1) | length (bits 9..17) | key (bits 18..22: run_key);  the end word is 0.
+    // The stage in front of a touch-down (bit 24 of its mask word: the body of the widest pattern) is a run of its own;
+    // masks without a static body form runs of the run-time fallback, which takes the mask of each stage.
+    // Built once per launch: the masks do not change over the interior-point sweeps.
+    constexpr int WIDEST = M::static_index((NU < 32) ? ((1u << NU) - 1u) : 0xFFFFFFFFu);
+    constexpr unsigned KEY_DYNAMIC = ALLV ? 16u : 4u;
+    auto run_key = [&](unsigned w) -> unsigned {
+        const int vi = ((w >> 24) & 1u) ? WIDEST : (int)((w >> 16) & 0x1Fu) - 1;
+        if constexpr (ALLV) {
+            return (vi >= 0 && vi < 16 && vi < M::N_STATIC_MASKS) ? (unsigned)vi : KEY_DYNAMIC;
+        } else {
+            unsigned key = KEY_DYNAMIC;
+#pragma unroll
+            for (int j = 3; j >= 0; --j)
+                if (M::common_variant(j) >= 0 && vi == M::common_variant(j)) key = (unsigned)j;
+            return key;
+        }
+    };
+    unsigned* runs = reinterpret_cast<unsigned*>(smem + L.runs);
+    if constexpr (!LEAN) {       // (the lean variant dispatches per stage, see the sweep)
+        int n_runs = 0;
+        for (int base = ((N - 1) >> 6) << 6; base >= 0; base -= 64) {      // lane = stage, the top 64 stages first
+            const int k = base + lane;
+            const bool valid = k < N;
+            const unsigned w = umask[valid ? k : N - 1], w_above = umask[k + 1 < N ? k + 1 : N - 1];
+            const unsigned key = run_key(w);
+            const bool first = valid && (k == N - 1 || key != run_key(w_above) || (((w | w_above) >> 24) & 1u) != 0u);
+            const unsigned long long m = __ballot(first);
+            const unsigned long long above = (lane < 63) ? (m >> (lane + 1)) : 0ull;
+            if (first) runs[n_runs + __popcll(above)] = (key << 18) | (unsigned)(k + 1);
+            n_runs += __popcll(m);
+        }
+        if (lane == 0) runs[n_runs] = 0u;
+        wave_sync();
+        for (int i = lane; i < n_runs; i += 64) {      // length of a run: down to the top of the next one
+            const unsigned w = runs[i], w_next = runs[i + 1];
+            runs[i] = w | (((w & 0x1FFu) - (w_next & 0x1FFu)) << 9);
+        }
+        wave_sync();
+    }
 
     int status = NMPC_STATUS_MAXITER;
     bool finished = false;
@@ -832,85 +875,176 @@ void nmpc_qp_kernel(const SolveArgs a) {
                     nc.finish();
                     Qt = nc.Qn; St = nc.Sn; Rt = nc.Rn;
                 }
-                unsigned cm = umask[N - 1];
                 int lane_zero = 0;
                 asm volatile("" : "+v"(lane_zero));
-                for (int k = N - 1; k >= 0; --k) {
-#ifdef NMPC_STAMPS
-                    sst.t0 = __builtin_readcyclecounter();
-#endif
-                    // next stage's images and coupling mask: issued first, consumed by the register
-                    // rotation at the end of this stage -- by then only this stage's K~/Acl~ stores are
-                    // younger (vmcnt retires in order), so neither the loads nor the stores stall the sweep
-                    const int kn = (k > 0) ? k - 1 : 0;
-#ifdef QP_T_ONEIMG      // timing build (tools/qp_traffic_timing.sh): every stage reads the images of stage 0 (cache-resident) -- results are wrong
-                    const int ki = (a.B < 0) ? kn : 0;
-#else
-                    const int ki = kn;
-#endif
-                    const f32x4 A1 = il.load_A(At + (size_t)ki * G::A_FLOATS);
-                    const f32x4 B1 = il.load_B(Bt + (size_t)ki * G::B_FLOATS);
-                    const f32x4 T1 = il.load_Bt(Bt + (size_t)ki * G::B_FLOATS);
-                    // (read through an offset the compiler cannot see is uniform: the value stays in a
-                    // VGPR until the end of the stage instead of being scalarised, and waited for, here)
-                    const unsigned cm_next = umask[kn + lane_zero];
-                    f32x4 Kk, Acl;
-                    NextCost sh = next_cost(kn);
-                    // a static body holds the barrier-product steps of its own stance feet only: exact zeros elsewhere
-                    // while the next stage's pattern is the same or narrower.  The rare stage before a touch-down
-                    // (bit 24 of the mask word) runs the body of the widest pattern instead -- valid for any pattern
-                    // (it eliminates every pivot for real), all four steps, and no extra code on the common path
-                    auto run = [&](auto mask_tag) {
-                        constexpr unsigned MK = decltype(mask_tag)::value;
-                        constexpr unsigned STEPS = (IPM && !BF16B && MK != DYNAMIC_MASK) ? M::barrier_steps(MK) : 0xFu;
-                        return backward_stage<NU, MK, true, ALLV, STEPS, LEAN ? 0 : 2>(P, A0, B0, T0, Qt, St, Rt, conv, sl, lane,
-                                                                        cm & 0xFFFFu, Kk, Acl, sh SST_PASS);
-                    };
-                    bool ok = true;
-                    // one static variant per mask: the model's short list as a chain (ALLV = false), or
-                    // every listed variant through a decision tree; any other mask takes the run-time fallback
-#define NMPC_VARIANT(I)                                                                                   \
-    case I:                                                                                               \
-        if constexpr (I < M::N_STATIC_MASKS)                                                              \
-            ok = run(std::integral_constant<unsigned, M::static_mask(I < M::N_STATIC_MASKS ? I : 0)>{}); \
-        else ok = run(std::integral_constant<unsigned, DYNAMIC_MASK>{});                                  \
-        break;
-#define NMPC_COMMON(J) (M::common_variant(J) >= 0 && vi == M::common_variant(J))
-#define NMPC_RUN_COMMON(J) run(std::integral_constant<unsigned, M::static_mask(M::common_variant(J) >= 0 ? M::common_variant(J) : 0)>{})
-                    constexpr int WIDEST = M::static_index((NU < 32) ? ((1u << NU) - 1u) : 0xFFFFFFFFu);
-                    const int vi = ((cm >> 24) & 1u) ? WIDEST : (int)((cm >> 16) & 0x1Fu) - 1;
-                    if constexpr (!ALLV) {
-                        if (NMPC_COMMON(0)) ok = NMPC_RUN_COMMON(0);
-                        else if (NMPC_COMMON(1)) ok = NMPC_RUN_COMMON(1);
-                        else if (NMPC_COMMON(2)) ok = NMPC_RUN_COMMON(2);
-                        else if (NMPC_COMMON(3)) ok = NMPC_RUN_COMMON(3);
-                        else ok = run(std::integral_constant<unsigned, DYNAMIC_MASK>{});
-                    } else {
-                        switch (vi) {
-                            NMPC_VARIANT(0) NMPC_VARIANT(1) NMPC_VARIANT(2) NMPC_VARIANT(3)
-                            NMPC_VARIANT(4) NMPC_VARIANT(5) NMPC_VARIANT(6) NMPC_VARIANT(7)
-                            NMPC_VARIANT(8) NMPC_VARIANT(9) NMPC_VARIANT(10) NMPC_VARIANT(11)
-                            NMPC_VARIANT(12) NMPC_VARIANT(13) NMPC_VARIANT(14) NMPC_VARIANT(15)
-                            default: ok = run(std::integral_constant<unsigned, DYNAMIC_MASK>{});
+                // Two stage loops, chosen by measurement: one wave per SIMD (resident) walks the horizon in runs of one
+                // contact pattern; two waves per SIMD (lean) keep the dispatch per stage -- there the other wave hides it, and the
+                // run loops measured 3.0 % slower at B = 8192.
+                if constexpr (LEAN) {
+                    unsigned cm = umask[N - 1];
+                    for (int k = N - 1; k >= 0; --k) {
+    #ifdef NMPC_STAMPS
+                        sst.t0 = __builtin_readcyclecounter();
+    #endif
+                        // next stage's images and coupling mask: issued first, consumed by the register
+                        // rotation at the end of this stage -- by then only this stage's K~/Acl~ stores are
+                        // younger (vmcnt retires in order), so neither the loads nor the stores stall the sweep
+                        const int kn = (k > 0) ? k - 1 : 0;
+    #ifdef QP_T_ONEIMG      // timing build (tools/qp_traffic_timing.sh): every stage reads the images of stage 0 (cache-resident) -- results are wrong
+                        const int ki = (a.B < 0) ? kn : 0;
+    #else
+                        const int ki = kn;
+    #endif
+                        const f32x4 A1 = il.load_A(At + (size_t)ki * G::A_FLOATS);
+                        const f32x4 B1 = il.load_B(Bt + (size_t)ki * G::B_FLOATS);
+                        const f32x4 T1 = il.load_Bt(Bt + (size_t)ki * G::B_FLOATS);
+                        // (read through an offset the compiler cannot see is uniform: the value stays in a
+                        // VGPR until the end of the stage instead of being scalarised, and waited for, here)
+                        const unsigned cm_next = umask[kn + lane_zero];
+                        f32x4 Kk, Acl;
+                        NextCost sh = next_cost(kn);
+                        // a static body holds the barrier-product steps of its own stance feet only: exact zeros elsewhere
+                        // while the next stage's pattern is the same or narrower.  The rare stage before a touch-down
+                        // (bit 24 of the mask word) runs the body of the widest pattern instead -- valid for any pattern
+                        // (it eliminates every pivot for real), all four steps, and no extra code on the common path
+                        auto run = [&](auto mask_tag) {
+                            constexpr unsigned MK = decltype(mask_tag)::value;
+                            constexpr unsigned STEPS = (IPM && !BF16B && MK != DYNAMIC_MASK) ? M::barrier_steps(MK) : 0xFu;
+                            return backward_stage<NU, MK, true, ALLV, STEPS, LEAN ? 0 : 2>(P, A0, B0, T0, Qt, St, Rt, conv, sl, lane,
+                                                                            cm & 0xFFFFu, Kk, Acl, sh SST_PASS);
+                        };
+                        bool ok = true;
+                        // one static variant per mask: the model's short list as a chain (ALLV = false), or
+                        // every listed variant through a decision tree; any other mask takes the run-time fallback
+    #define NMPC_VARIANT(I)                                                                                   \
+        case I:                                                                                               \
+            if constexpr (I < M::N_STATIC_MASKS)                                                              \
+                ok = run(std::integral_constant<unsigned, M::static_mask(I < M::N_STATIC_MASKS ? I : 0)>{}); \
+            else ok = run(std::integral_constant<unsigned, DYNAMIC_MASK>{});                                  \
+            break;
+    #define NMPC_COMMON(J) (M::common_variant(J) >= 0 && vi == M::common_variant(J))
+    #define NMPC_RUN_COMMON(J) run(std::integral_constant<unsigned, M::static_mask(M::common_variant(J) >= 0 ? M::common_variant(J) : 0)>{})
+                        const int vi = ((cm >> 24) & 1u) ? WIDEST : (int)((cm >> 16) & 0x1Fu) - 1;
+                        if constexpr (!ALLV) {
+                            if (NMPC_COMMON(0)) ok = NMPC_RUN_COMMON(0);
+                            else if (NMPC_COMMON(1)) ok = NMPC_RUN_COMMON(1);
+                            else if (NMPC_COMMON(2)) ok = NMPC_RUN_COMMON(2);
+                            else if (NMPC_COMMON(3)) ok = NMPC_RUN_COMMON(3);
+                            else ok = run(std::integral_constant<unsigned, DYNAMIC_MASK>{});
+                        } else {
+                            switch (vi) {
+                                NMPC_VARIANT(0) NMPC_VARIANT(1) NMPC_VARIANT(2) NMPC_VARIANT(3)
+                                NMPC_VARIANT(4) NMPC_VARIANT(5) NMPC_VARIANT(6) NMPC_VARIANT(7)
+                                NMPC_VARIANT(8) NMPC_VARIANT(9) NMPC_VARIANT(10) NMPC_VARIANT(11)
+                                NMPC_VARIANT(12) NMPC_VARIANT(13) NMPC_VARIANT(14) NMPC_VARIANT(15)
+                                default: ok = run(std::integral_constant<unsigned, DYNAMIC_MASK>{});
+                            }
                         }
+    #undef NMPC_VARIANT
+    #undef NMPC_COMMON
+    #undef NMPC_RUN_COMMON
+                        qp_ok = ok && qp_ok;
+    #ifdef QP_T_NOSTORE     // timing build: no gain stores -- results are wrong, the time tells what the stores cost
+                        if (a.B < 0)
+    #endif
+                        {
+                        ks.store(Kt, Kk);      // gain tiles of this stage, read by the forward sweep
+                        cs.store(Ct, Acl);
+                        }
+                        A0 = il.fix_A(A1, lane);
+                        B0 = il.fix_B(B1, lane);
+                        T0 = il.fix_Bt(T1, lane);
+                        Qt = sh.Qn; St = sh.Sn; Rt = sh.Rn;
+                        cm = __builtin_amdgcn_readfirstlane(cm_next);
+                        SST_TILES(5);
+                    }
+                } else {
+                    // The stages of one run (run-length schedule of the prologue): top-1 down to top-len, all with the body of
+                    // MK.  A static body holds the barrier-product steps of its own stance feet only: exact zeros elsewhere
+                    // while the next stage's pattern is the same or narrower -- inside a run it is the same, behind its last
+                    // stage it is narrower, since the stage before a touch-down is a run of the widest pattern's body (valid
+                    // for any pattern: it eliminates every pivot for real, all four steps).
+                    auto run_stages = [&](auto mask_tag, int top, int len) {
+                        constexpr unsigned MK = decltype(mask_tag)::value;
+                        constexpr bool DYN = (MK == DYNAMIC_MASK);
+                        constexpr unsigned STEPS = (IPM && !BF16B && !DYN) ? M::barrier_steps(MK) : 0xFu;
+                        unsigned cm = 0u;       // coupling mask of the stage: the fallback body alone reads it
+                        if constexpr (DYN) cm = __builtin_amdgcn_readfirstlane(umask[top - 1]);
+                        for (int k = top - 1; k >= top - len; --k) {
+#ifdef NMPC_STAMPS
+                            sst.t0 = __builtin_readcyclecounter();
+#endif
+                            // next stage's images: issued first, consumed by the register rotation at the end of this
+                            // stage -- by then only this stage's K~/Acl~ stores are younger (vmcnt retires in order), so
+                            // neither the loads nor the stores stall the sweep
+                            const int kn = (k > 0) ? k - 1 : 0;
+#ifdef QP_T_ONEIMG      // timing build (tools/qp_traffic_timing.sh): every stage reads the images of stage 0 (cache-resident) -- results are wrong
+                            const int ki = (a.B < 0) ? kn : 0;
+#else
+                            const int ki = kn;
+#endif
+                            const f32x4 A1 = il.load_A(At + (size_t)ki * G::A_FLOATS);
+                            const f32x4 B1 = il.load_B(Bt + (size_t)ki * G::B_FLOATS);
+                            const f32x4 T1 = il.load_Bt(Bt + (size_t)ki * G::B_FLOATS);
+                            // (the fallback's next mask: read through an offset the compiler cannot see is uniform, so the
+                            // value stays in a VGPR until the end of the stage instead of being scalarised, and waited for, here)
+                            unsigned cm_next = 0u;
+                            if constexpr (DYN) cm_next = umask[kn + lane_zero];
+                            f32x4 Kk, Acl;
+                            NextCost sh = next_cost(kn);
+                            const bool ok = backward_stage<NU, MK, true, ALLV, STEPS, LEAN ? 0 : 2>(P, A0, B0, T0, Qt, St, Rt, conv, sl, lane,
+                                                                                                 cm & 0xFFFFu, Kk, Acl, sh SST_PASS);
+                            qp_ok = ok && qp_ok;
+#ifdef QP_T_NOSTORE     // timing build: no gain stores -- results are wrong, the time tells what the stores cost
+                            if (a.B < 0)
+#endif
+                            {
+                            ks.store(Kt, Kk);      // gain tiles of this stage, read by the forward sweep
+                            cs.store(Ct, Acl);
+                            }
+                            A0 = il.fix_A(A1, lane);
+                            B0 = il.fix_B(B1, lane);
+                            T0 = il.fix_Bt(T1, lane);
+                            Qt = sh.Qn; St = sh.Sn; Rt = sh.Rn;
+                            if constexpr (DYN) cm = __builtin_amdgcn_readfirstlane(cm_next);
+                            SST_TILES(5);
+                        }
+                    };
+                    // one static body per key: the model's short list (ALLV = false) or every listed variant; the run word
+                    // of the next run is requested when a run starts and waited for when it ends
+#define NMPC_VARIANT(I)                                                                                                 \
+        case I:                                                                                                             \
+            if constexpr (I < M::N_STATIC_MASKS)                                                                            \
+                run_stages(std::integral_constant<unsigned, M::static_mask(I < M::N_STATIC_MASKS ? I : 0)>{}, top, len);    \
+            else run_stages(std::integral_constant<unsigned, DYNAMIC_MASK>{}, top, len);                                    \
+            break;
+#define NMPC_COMMON(J) (M::common_variant(J) >= 0 && key == J##u)
+#define NMPC_RUN_COMMON(J) run_stages(std::integral_constant<unsigned, M::static_mask(M::common_variant(J) >= 0 ? M::common_variant(J) : 0)>{}, top, len)
+                    unsigned rw = __builtin_amdgcn_readfirstlane(runs[0]);
+                    for (int r = 1; (rw & 0x1FFu) != 0u; ++r) {
+                        const unsigned rw_next = runs[r + lane_zero];
+                        const int top = (int)(rw & 0x1FFu), len = (int)((rw >> 9) & 0x1FFu);
+                        const unsigned key = rw >> 18;
+                        if constexpr (!ALLV) {
+                            if (NMPC_COMMON(0)) NMPC_RUN_COMMON(0);
+                            else if (NMPC_COMMON(1)) NMPC_RUN_COMMON(1);
+                            else if (NMPC_COMMON(2)) NMPC_RUN_COMMON(2);
+                            else if (NMPC_COMMON(3)) NMPC_RUN_COMMON(3);
+                            else run_stages(std::integral_constant<unsigned, DYNAMIC_MASK>{}, top, len);
+                        } else {
+                            switch (key) {
+                                NMPC_VARIANT(0) NMPC_VARIANT(1) NMPC_VARIANT(2) NMPC_VARIANT(3)
+                                NMPC_VARIANT(4) NMPC_VARIANT(5) NMPC_VARIANT(6) NMPC_VARIANT(7)
+                                NMPC_VARIANT(8) NMPC_VARIANT(9) NMPC_VARIANT(10) NMPC_VARIANT(11)
+                                NMPC_VARIANT(12) NMPC_VARIANT(13) NMPC_VARIANT(14) NMPC_VARIANT(15)
+                                default: run_stages(std::integral_constant<unsigned, DYNAMIC_MASK>{}, top, len);
+                            }
+                        }
+                        rw = __builtin_amdgcn_readfirstlane(rw_next);
                     }
 #undef NMPC_VARIANT
 #undef NMPC_COMMON
 #undef NMPC_RUN_COMMON
-                    qp_ok = ok && qp_ok;
-#ifdef QP_T_NOSTORE     // timing build: no gain stores -- results are wrong, the time tells what the stores cost
-                    if (a.B < 0)
-#endif
-                    {
-                    ks.store(Kt, Kk);      // gain tiles of this stage, read by the forward sweep
-                    cs.store(Ct, Acl);
-                    }
-                    A0 = il.fix_A(A1, lane);
-                    B0 = il.fix_B(B1, lane);
-                    T0 = il.fix_Bt(T1, lane);
-                    Qt = sh.Qn; St = sh.Sn; Rt = sh.Rn;
-                    cm = __builtin_amdgcn_readfirstlane(cm_next);
-                    SST_TILES(5);
                 }
             };
             if (use_ipm) sweep(std::true_type{}); else sweep(std::false_type{});
