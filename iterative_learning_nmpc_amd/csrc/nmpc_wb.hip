@@ -23,747 +23,25 @@
 // Stage data that does not fit the LDS (Q~, K~' images, 6 + 6 KB per stage and sweep) streams through an HBM workspace;
 // the per-stage record, the elimination columns, the transposition buffer and the gains of the last two stages live in the LDS
 // (37.8 KB at N = 30: four waves per CU).  DESIGN.md 5b has the measurements behind every choice.
+// The family by file: nmpc_wb_model.hpp (the model), nmpc_wb_layout.hpp (sizes, offsets, index maps, argument block: no kernel),
+// nmpc_wb_linearize.hip.inc (the linearisation kernel), nmpc_wb_ldl.hpp (the LDL' elimination), and this file: the QP kernel and the
+// wave helpers only it uses.  This file includes the others and is what nmpc_api.hip includes.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
 #include "../../include/nmpc.h"
 #include "nmpc_wb_model.hpp"
 
-// Contraction off from here on (as in the QP kernel of nmpc_solve.hip): every intended a*b + c of this file is an fmaf or an MFMA;
-// what the backend would fuse on its own depends on the instantiation.
+// Contraction off from here on (as in the QP kernel of nmpc_solve.hip), for every file of the family: every intended a*b + c is an
+// fmaf or an MFMA; what the backend would fuse on its own depends on the instantiation.
 #pragma clang fp contract(off)
+
+#include "nmpc_wb_layout.hpp"
+#include "nmpc_wb_linearize.hip.inc"
+#include "nmpc_wb_ldl.hpp"
 
 namespace nmpc {
 namespace wb {
-
-// Positions of the states in the 48-wide homogeneous vector x~ (three tiles of 16).  States 0..35 (q, v_0..v_17) sit at their own
-// index: tiles 0, 1 and slots 0..3 of tile 2.  The six momentum states sit at slots 4, 5, 8, 9, 12, 13 of tile 2 and the
-// homogeneous coordinate at slot 6: registers 0 and 1 of lane rows 1..3 in the accumulator layout.  A product that contracts over
-// tile row 2 against an operand whose only non-zero rows are momentum rows (the dense part of N~ = A~ - I and of B~) then needs
-// contraction steps 0 and 1 only: 34 of 196 MFMAs of a backward stage less than with the states in their own order.
-constexpr int HX = 38;                 // position of the homogeneous coordinate of x~ = [dx; 1]
-constexpr int XW = 46;                 // positions in use: 0..45
-__host__ __device__ constexpr int pos_of(int s) { return s < 36 ? s : 32 + 4 * (1 + (s - 36) / 2) + ((s - 36) & 1); }      // s < 42
-__host__ __device__ constexpr int state_at(int p) {      // -1: padding or the homogeneous coordinate
-    return p < 36 ? p : (p < XW && (p & 3) < 2) ? 36 + 2 * ((p - 36) >> 2) + (p & 1) : -1;
-}
-static_assert(pos_of(36) == 36 && pos_of(37) == 37 && pos_of(38) == 40 && pos_of(39) == 41 && pos_of(40) == 44 && pos_of(41) == 45, "momentum slots");
-static_assert(state_at(40) == 38 && state_at(45) == 41 && state_at(HX) == -1 && state_at(39) == -1 && state_at(46) == -1, "momentum slots");
-constexpr int HXQ = (HX - 32) >> 2, HXR = (HX - 32) & 3;      // lane row and register of row HX in tile row 2
-static_assert(HXR == 2, "the homogeneous row is register 2 of its lane row");
-
-// ---- the scaled residual Jacobian Js = sqrt(W) [J | res] of a node, COMPACT -------------------------------------------------------
-// Js is 30 x 46 with 381 structural non-zeros.  As a dense tile image (6 KB per node, each thread of the linearisation scattering
-// its ~440 dword stores over its own image) it cost 0.6 of the linearisation's 0.78 ms per launch; it is now a 388-float record
-// in the order the linearisation produces it, written in 16 B pieces, and the QP kernel's prologue gathers its operand tiles
-// from the record through a per-lane index map (cj_index) -- the way the stage sweeps synthesise N~ and B~.
-//   foot f, floats 88 f ..:  contact rows 3f+i (i < 3):  [6 c + i]      column q(xi_c)       c < 9  (xi = [r, theta, ql_f])
-//                                                        [6 c + 3 + i]  column v(xi_c)
-//                                                        [54 + i]       column HX (the scaled residual)
-//                            swing row 12+f:             [57 + c], [66] column HX            ([67] padding)
-//                            placement rows 22+2f+i:     [68 + 10 i + c], [68 + 10 i + 9] column HX
-//   consistency, floats 352 ..:  rows 16+i: [3 i] h_lin_i, [3 i + 1] v_i, [3 i + 2] HX;  rows 19+i: [9 + 2 i] h_ang_i, [10 + 2 i] HX,
-//                                [15 + 3 a + i] theta_a, [24 + 3 a + i] thetadot_a            ([33..35] padding)
-constexpr int CJ_FOOT = 88, CJ_CONS = 4 * CJ_FOOT, CJ_FLOATS = CJ_CONS + 36;
-constexpr int JS_FLOATS = CJ_FLOATS;
-static_assert(CJ_FLOATS % 4 == 0, "records are whole 16 B pieces");
-__host__ __device__ constexpr int xi_slot(int f, int qi) {      // inverse of xi_col: slot of coordinate qi in xi_f, or -1
-    return qi < 6 ? qi : (qi >= 6 + 3 * f && qi < 9 + 3 * f) ? 6 + (qi - 6 - 3 * f) : -1;
-}
-// record index of element (row, column POSITION) of Js, or -1 for a structural zero
-__host__ __device__ constexpr int cj_index(int row, int col) {
-    if (row < 12) {
-        const int f = row / 3, i = row % 3;
-        if (col == HX) return CJ_FOOT * f + 54 + i;
-        if (col < 18) { const int c = xi_slot(f, col); return c < 0 ? -1 : CJ_FOOT * f + 6 * c + i; }
-        if (col < 36) { const int c = xi_slot(f, col - 18); return c < 0 ? -1 : CJ_FOOT * f + 6 * c + 3 + i; }
-        return -1;
-    }
-    if (row < 16) {
-        const int f = row - 12;
-        if (col == HX) return CJ_FOOT * f + 66;
-        if (col < 18) { const int c = xi_slot(f, col); return c < 0 ? -1 : CJ_FOOT * f + 57 + c; }
-        return -1;
-    }
-    if (row < 19) {
-        const int i = row - 16;
-        return col == pos_of(WH + i) ? CJ_CONS + 3 * i : col == WV + i ? CJ_CONS + 3 * i + 1 : col == HX ? CJ_CONS + 3 * i + 2 : -1;
-    }
-    if (row < 22) {
-        const int i = row - 19;
-        if (col == pos_of(WH + 3 + i)) return CJ_CONS + 9 + 2 * i;
-        if (col == HX) return CJ_CONS + 10 + 2 * i;
-        if (col >= WQ + 3 && col < WQ + 6) return CJ_CONS + 15 + 3 * (col - WQ - 3) + i;
-        if (col >= WV + 3 && col < WV + 6) return CJ_CONS + 24 + 3 * (col - WV - 3) + i;
-        return -1;
-    }
-    if (row < 30) {
-        const int f = (row - 22) / 2, i = (row - 22) % 2;
-        if (col == HX) return CJ_FOOT * f + 68 + 10 * i + 9;
-        if (col < 18) { const int c = xi_slot(f, col); return c < 0 ? -1 : CJ_FOOT * f + 68 + 10 * i + c; }
-        return -1;
-    }
-    return -1;
-}
-static_assert(cj_index(0, 0) == 0 && cj_index(5, 18 + 9) == CJ_FOOT + 6 * 6 + 3 + 2 && cj_index(4, 6) == -1 && cj_index(13, HX) == CJ_FOOT + 66, "cj_index");
-static_assert(cj_index(17, pos_of(WH + 1)) == CJ_CONS + 3 && cj_index(20, WV + 4) == CJ_CONS + 24 + 3 + 1 && cj_index(29, 2) == CJ_FOOT * 3 + 68 + 10 + 2, "cj_index");
-constexpr int XT = 3, UT = 2;          // 16-wide tiles of the state (48) and input (32) dimensions
-constexpr int JT = 2;                  // K tiles of the dense residual Jacobian (22 rows)
-constexpr int IMG = TILE;              // floats of one tile image (column-major 16x16)
-constexpr int QT_FLOATS = XT * XT * IMG, KT_FLOATS = UT * XT * IMG;
-
-// per-node record written by the linearisation (float offsets)
-constexpr int R_D = 0;                 // defect d, by POSITION: [48], zero where no state sits
-constexpr int R_HQ = 48;               // d h_ang+ / d q[3..17]: [3][16]
-constexpr int R_HF = 96;               // d h_ang+ / d f: [3][12]
-constexpr int R_CDT = 132;             // dt c_i: d h_lin+ / d f_i = cdt_i I
-constexpr int R_R = 136;               // input gradient r[30] (+2)
-constexpr int R_C = 168;               // friction pyramid values c = G u - h [16]
-constexpr int R_ACT = 184, R_COST = 185;
-constexpr int R_ZERO = 186, R_DT = 187, R_DT2 = 224;   // constants the tile synthesis reads like any other entry
-constexpr int R_GQ = 188;              // gradient of the diagonal residuals on x[0..35]
-constexpr int REC = 228;
-
-struct WbArgs {
-    ModelParams mp;
-    float W[NY], We[NYE];
-    float reg, reg_e;
-    int N, B;
-    int max_sqp, n_ipm, yref_per_stage, it, shift;
-    int precision;      // 0: fp32; 1: bf16 residual Jacobian, J'WJ on the bf16 matrix pipe; 2: split bf16 (hi + lo); 3: hi + mid + lo
-    int pos_rows;       // 1: some foot-placement weight (W / W_e rows RY_POS.., RE_POS..) is non-zero
-    float nlp_tol, mu0, sigma, s_min, gamma, tau_min;
-    const float* x0;
-    const float* yref;
-    const float* yref_e;
-    const float* params;
-    float* X;
-    float* U;
-    int* status;
-    float* stats;
-    float* ws;
-    const int* skip;    // nullptr, or dev [B] flag words: a problem with skip[b] & skip_mask != 0 is left untouched (nmpc_set_skip)
-    int skip_mask;
-};
-
-__host__ __device__ inline int r4(int n) { return (n + 3) & ~3; }
-__device__ __forceinline__ int shifted_node(int k, int shift, int N) { return (k >= 1 && k <= N - shift) ? k + shift : k; }
-__device__ __forceinline__ bool shifted_stage_valid(int k, int shift, int N) { return k < N - shift; }
-
-// arrays of the lane = stage phases, feature-major [feature][stage], odd stage stride
-struct StageArr {
-    int NS, dX, dU, dXp, dUp, sv, lv, total;
-    __host__ __device__ explicit StageArr(int N) {
-        NS = (N + 1) | 1;
-        int o = 0;
-        dX = o;  o += r4(NX * NS);
-        dU = o;  o += r4(NU * NS);
-        dXp = o; o += r4(NX * NS);
-        dUp = o; o += r4(NU * NS);
-        sv = o;  o += r4(NG * NS);
-        lv = o;  o += r4(NG * NS);
-        total = o;
-    }
-};
-// workspace of one problem (float offsets)
-struct WsLayout {
-    size_t rec, js, qt, kt, arr, flag, stride;
-    __host__ __device__ explicit WsLayout(int N) {
-        size_t o = 0;
-        rec = o; o += (size_t)(N + 1) * REC;
-        js = o;  o += (size_t)(N + 1) * JS_FLOATS;
-        qt = o;  o += (size_t)(N + 1) * QT_FLOATS;
-        kt = o;  o += (size_t)N * KT_FLOATS;
-        arr = o; o += StageArr(N).total;
-        flag = o; o += 4;
-        stride = (o + 63) & ~(size_t)63;
-#ifdef WB_T_ODD_STRIDE       // timing build: an odd number of 256 B units per problem (do the problems' images camp on memory channels?)
-        if (((stride / 64) & 1) == 0) stride += 64;
-#endif
-    }
-};
-
-// weight of the diagonal residual that sits on state index s < 36 (base / joint rows), stage and terminal
-__device__ __forceinline__ float wdiag(const WbArgs& a, int s, bool term) {
-    const int i = (s < 6) ? RY_BASE + s : (s < 18) ? RY_JOINT + (s - 6) : (s < 24) ? RY_BASE + 6 + (s - 18) : RY_JOINT + 12 + (s - 24);
-    return term ? a.We[i] : a.W[i];        // base and joint rows have the same offsets in W and W_e
-}
-__device__ __forceinline__ int yref_of_state(int s) {
-    return (s < 6) ? RY_BASE + s : (s < 18) ? RY_JOINT + (s - 6) : (s < 24) ? RY_BASE + 6 + (s - 18) : RY_JOINT + 12 + (s - 24);
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Linearisation: thread t <-> (problem b, node k), k = N is the terminal node.
-#ifndef WB_LIN_WAVES
-#define WB_LIN_WAVES 1
-#endif
-__global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_kernel(const WbArgs a) {
-    const int N = a.N;
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long long)a.B * (N + 1)) return;
-    const int b = (int)(t / (N + 1)), k = (int)(t - (long long)b * (N + 1));
-    const WsLayout wl(N);
-    float* ws = a.ws + (size_t)b * wl.stride;
-    if (a.it > 0 && reinterpret_cast<const int*>(ws + wl.flag)[0]) return;
-    if (a.skip && (a.skip[b] & a.skip_mask) != 0) return;
-    const bool term = (k == N);
-    const ModelParams& mp = a.mp;
-    const float dt = mp.dt;
-    const float* Xg = a.X + (size_t)b * (N + 1) * NX;
-    const float* Ug = a.U + (size_t)b * N * NU;
-    // alignments the vectoriser may rely on (a lane is a node: every access of this kernel is strided across the wave, so its
-    // cost is the number of memory instructions -- 16 B pieces of the record instead of 210 dword stores, 8 B pieces of x, u, yref).
-    // Workspace: 256 B; caller's arrays: 8 B (x, u, references: rows of 42, 30, 90 / 66 floats) and 16 B (parameters), checked by
-    // the C-ABI (nmpc_api.hip, launch_wb).
-    float* rec = static_cast<float*>(__builtin_assume_aligned(ws + wl.rec + (size_t)k * REC, 16));
-    float* js = ws + wl.js + (size_t)k * JS_FLOATS;
-
-    float x[NX], u[NU], p[NP];
-    const float* xk = static_cast<const float*>(__builtin_assume_aligned(Xg + (size_t)shifted_node(k, a.shift, N) * NX, 8));
-#pragma unroll
-    for (int i = 0; i < NX; i += 2) { const f32x2 v = *reinterpret_cast<const f32x2*>(xk + i); x[i] = v[0]; x[i + 1] = v[1]; }
-    const int ks = term ? 0 : k;
-    {
-        // warm-start shift as an index map; in the exposed tail the contact forces are zero and the accelerations keep the
-        // previous solution's values at that stage (solver.py:316-322 moves a[:, :n_warm_start] and zeroes f[:, n_warm_start:])
-        const bool ok = (a.shift == 0) || shifted_stage_valid(ks, a.shift, N);
-        const float* uk = static_cast<const float*>(__builtin_assume_aligned(Ug + (size_t)(ok ? ks + a.shift : ks) * NU, 8));
-#pragma unroll
-        for (int i = 0; i < NU; i += 2) {
-            const f32x2 v = *reinterpret_cast<const f32x2*>(uk + i);
-            u[i] = (ok || i < WF) ? v[0] : 0.0f; u[i + 1] = (ok || i + 1 < WF) ? v[1] : 0.0f;
-        }
-    }
-    const float* pg = static_cast<const float*>(__builtin_assume_aligned(a.params + ((size_t)b * (N + 1) + k) * NP, 16));
-    static_assert(NX % 2 == 0 && NU % 2 == 0 && NY % 2 == 0 && NYE % 2 == 0 && NP % 4 == 0 && REC % 4 == 0, "row alignments");
-#pragma unroll
-    for (int i = 0; i < NP; i += 4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(pg + i);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) p[i + r] = v[r];
-    }
-    const int ny = term ? NYE : NY;
-    const float* yr = static_cast<const float*>(__builtin_assume_aligned(
-        term ? a.yref_e + (size_t)b * NYE
-             : a.yref + (size_t)b * (a.yref_per_stage ? (size_t)N * NY : (size_t)NY) + (a.yref_per_stage ? (size_t)k * NY : 0), 8));
-    const float* Wv = term ? a.We : a.W;
-    const int r_sw = term ? RE_SWING : RY_SWING, r_ct = term ? RE_CNT : RY_CNT, r_cs = term ? RE_CONS : RY_CONS;
-    const int r_ps = term ? RE_POS : RY_POS;
-    (void)ny;
-
-    // ---- kinematics
-    BaseRot br;
-    {
-        const float th[3] = {x[WQ + 3], x[WQ + 4], x[WQ + 5]}, thd[3] = {x[WV + 3], x[WV + 4], x[WV + 5]};
-        base_rotation<true>(th, thd, br);
-    }
-    float cost = 0.0f;
-    // a run of the node's compact Jacobian record (layout: cj_index), from registers, in 16 B pieces
-    float* cj = static_cast<float*>(__builtin_assume_aligned(js, 16));
-    auto put_cj = [&](int off, int n, const float* v) {
-#pragma unroll
-        for (int i = 0; i < n; i += 4) *reinterpret_cast<f32x4*>(cj + off + i) = f32x4{v[i], v[i + 1], v[i + 2], v[i + 3]};
-    };
-
-    // a run of the record, from registers, in 16 B pieces (`off` a multiple of four)
-    auto put_rec = [&](int off, const auto& v) {
-        constexpr int n = (int)(sizeof(v) / sizeof(float));
-        static_assert(n % 4 == 0, "record runs are whole 16 B pieces");
-#pragma unroll
-        for (int i = 0; i < n; i += 4) *reinterpret_cast<f32x4*>(rec + off + i) = f32x4{v[i], v[i + 1], v[i + 2], v[i + 3]};
-    };
-    float tau_acc[3] = {0.f, 0.f, 0.f}, F[3] = {0.f, 0.f, 0.f};
-    float hfr[36], cdt[4] = {0.f, 0.f, 0.f, 0.f};      // d h_ang+ / d f [3][12] and dt c_f of the record
-#pragma unroll
-    for (int i = 0; i < 36; ++i) hfr[i] = 0.0f;
-    float hq[3][15];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 15; ++j) hq[i][j] = 0.0f;
-
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        const float ql[3] = {x[WQ + 6 + 3 * f], x[WQ + 7 + 3 * f], x[WQ + 8 + 3 * f]};
-        const float wl3[3] = {x[WV + 6 + 3 * f], x[WV + 7 + 3 * f], x[WV + 8 + 3 * f]};
-        Leg lg;
-        leg_kin<true>(mp, f, ql, wl3, lg);
-        // world position, Jacobian J (3x9 wrt xi = [r, theta, ql]) and its time derivative Jd
-        float Rb[3];
-        mv(br.R, lg.b, Rb);
-        const float pz = x[WQ + 2] + Rb[2];
-        float J[3][9], Jd[3][9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { J[i][c] = (i == c) ? 1.0f : 0.0f; Jd[i][c] = 0.0f; }
-#pragma unroll
-        for (int aa = 0; aa < 3; ++aa) {
-            float t0[3], t1[3], t2[3];
-            mv(br.Ra[aa], lg.b, t0);
-            mv(br.Rad[aa], lg.b, t1);
-            mv(br.Ra[aa], lg.bd, t2);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { J[i][3 + aa] = t0[i]; Jd[i][3 + aa] = t1[i] + t2[i]; }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float jc[3] = {lg.Jb.m[c], lg.Jb.m[3 + c], lg.Jb.m[6 + c]};
-            const float jdc[3] = {lg.Jbd.m[c], lg.Jbd.m[3 + c], lg.Jbd.m[6 + c]};
-            float t0[3], t1[3], t2[3];
-            mv(br.R, jc, t0);
-            mv(br.Rd, jc, t1);
-            mv(br.R, jdc, t2);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { J[i][6 + c] = t0[i]; Jd[i][6 + c] = t1[i] + t2[i]; }
-        }
-        const float cf = p[f], peak = p[4 + f], ppz = p[8 + 3 * f + 2];
-        // foot-placement rows (pos_cost, solver.py:128-137,272-273): world x, y of the foot - planned location.  Weight 0
-        // outside the contact-restricted mode: the rows are then exact zeros in the image and are not rewritten
-        // (a.pos_rows, wave-uniform; nmpc_set_weights has the image cleared when the rows go from weighted to unweighted)
-        float fb[CJ_FOOT];      // this foot's part of the compact Jacobian record
-        fb[67] = 0.0f;
-        if (a.pos_rows) {
-            const float px[2] = {x[WQ] + Rb[0], x[WQ + 1] + Rb[1]};
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float w = Wv[r_ps + 2 * f + i], sw = sqrtf(w);
-                const float res = px[i] - yr[r_ps + 2 * f + i];
-                cost += 0.5f * w * res * res;
-#pragma unroll
-                for (int c = 0; c < 9; ++c) fb[68 + 10 * i + c] = sw * J[i][c];
-                fb[68 + 10 * i + 9] = sw * res;
-            }
-            put_cj(CJ_FOOT * f + 68, 20, fb + 68);
-        }
-        // swing row: peak z_foot - ref
-        {
-            const float w = Wv[r_sw + f], sw = sqrtf(w);
-            const float res = peak * pz - yr[r_sw + f];
-            cost += 0.5f * w * res * res;
-#pragma unroll
-            for (int c = 0; c < 9; ++c) fb[57 + c] = sw * peak * J[2][c];
-            fb[66] = sw * res;
-        }
-        // contact rows: c (J v + p_gain e_z (z - plane_z)) - ref
-        {
-            float sres[3], swc[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                float vel = 0.0f;
-#pragma unroll
-                for (int c = 0; c < 9; ++c) vel += J[i][c] * x[WV + xi_col(f, c)];
-                const float w = Wv[r_ct + 3 * f + i], sw = sqrtf(w);
-                const float res = cf * (vel + (i == 2 ? mp.p_gain * (pz - ppz) : 0.0f)) - yr[r_ct + 3 * f + i];
-                cost += 0.5f * w * res * res;
-                sres[i] = sw * res; swc[i] = sw * cf;
-            }
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                fb[6 * c + 0] = swc[0] * Jd[0][c]; fb[6 * c + 1] = swc[1] * Jd[1][c]; fb[6 * c + 2] = swc[2] * (Jd[2][c] + mp.p_gain * J[2][c]);
-                fb[6 * c + 3] = swc[0] * J[0][c];  fb[6 * c + 4] = swc[1] * J[1][c];  fb[6 * c + 5] = swc[2] * J[2][c];
-            }
-            fb[54] = sres[0]; fb[55] = sres[1]; fb[56] = sres[2];
-        }
-        put_cj(CJ_FOOT * f, 68, fb);
-        if (!term) {   // momentum rows of the dynamics
-            const float ff[3] = {u[WF + 3 * f], u[WF + 3 * f + 1], u[WF + 3 * f + 2]};
-            float tq[3];
-            cross(Rb, ff, tq);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { F[i] += cf * ff[i]; tau_acc[i] += cf * tq[i]; }
-            // d(arm x f)/d xi_c, c = 3..8 (arm = R b does not depend on r)
-#pragma unroll
-            for (int c = 3; c < 9; ++c) {
-                const float da[3] = {J[0][c], J[1][c], J[2][c]};
-                float tc[3];
-                cross(da, ff, tc);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) hq[i][xi_col(f, c) - 3] += dt * cf * tc[i];
-            }
-            const float ax[9] = {0.f, -Rb[2], Rb[1], Rb[2], 0.f, -Rb[0], -Rb[1], Rb[0], 0.f};
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) hfr[i * 12 + 3 * f + j] = dt * cf * ax[3 * i + j];
-            cdt[f] = dt * cf;
-        }
-    }
-    // ---- consistency rows  h - A_g(q) v,  A_g v = [m rdot ; R I_b E(theta) thetadot]
-    {
-        float cb[36];      // the consistency part of the compact Jacobian record
-        cb[33] = cb[34] = cb[35] = 0.0f;
-        const float thd[3] = {x[WV + 3], x[WV + 4], x[WV + 5]};
-        const float Ib[3] = {mp.ixx, mp.iyy, mp.izz};
-        float sy, cy, sx, cx;
-        sincosf(x[WQ + 4], &sy, &cy);
-        sincosf(x[WQ + 5], &sx, &cx);
-        const M3 E = {{-sy, 0.f, 1.f, cy * sx, cx, 0.f, cx * cy, -sx, 0.f}};
-        const M3 Ea[3] = {{{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}},
-                          {{-cy, 0.f, 0.f, -sy * sx, 0.f, 0.f, -cx * sy, 0.f, 0.f}},
-                          {{0.f, 0.f, 0.f, cy * cx, -sx, 0.f, -sx * cy, -cx, 0.f}}};
-        float wbv[3], Iw[3], L[3];
-        mv(E, thd, wbv);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) Iw[i] = Ib[i] * wbv[i];
-        mv(br.R, Iw, L);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            {   // linear momentum
-                const float w = Wv[r_cs + i], sw = sqrtf(w);
-                const float res = x[WH + i] - mp.mass * x[WV + i] - yr[r_cs + i];
-                cost += 0.5f * w * res * res;
-                cb[3 * i] = sw; cb[3 * i + 1] = -sw * mp.mass; cb[3 * i + 2] = sw * res;
-            }
-            {   // angular momentum
-                const float w = Wv[r_cs + 3 + i], sw = sqrtf(w);
-                const float res = x[WH + 3 + i] - L[i] - yr[r_cs + 3 + i];
-                cost += 0.5f * w * res * res;
-                cb[9 + 2 * i] = sw; cb[10 + 2 * i] = sw * res;
-            }
-        }
-#pragma unroll
-        for (int aa = 0; aa < 3; ++aa) {
-            float t0[3], t1[3], t2[3], ew[3], iew[3], iec[3];
-            mv(br.Ra[aa], Iw, t0);
-            mv(Ea[aa], thd, ew);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { iew[i] = Ib[i] * ew[i]; iec[i] = Ib[i] * E.m[3 * i + aa]; }
-            mv(br.R, iew, t1);
-            mv(br.R, iec, t2);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const float sw = sqrtf(Wv[r_cs + 3 + i]);
-                cb[15 + 3 * aa + i] = -sw * (t0[i] + t1[i]);
-                cb[24 + 3 * aa + i] = -sw * t2[i];
-            }
-        }
-        put_cj(CJ_CONS, 36, cb);
-    }
-    // ---- diagonal residuals (base, joint) on x[0..35]: gradient and cost
-    {
-        float gq[36];
-#pragma unroll
-        for (int s = 0; s < 36; ++s) {
-            const float w = wdiag(a, s, term);
-            const float e = x[s] - yr[yref_of_state(s)];
-            gq[s] = w * e;
-            cost += 0.5f * w * e * e;
-        }
-        put_rec(R_GQ, gq);
-    }
-    if (!term) {
-        // input residuals: acc on a[6..17], f_reg on f
-        float rr[32];
-        rr[30] = rr[31] = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NU; ++i) {
-            float g = 0.0f;
-            if (i >= 6 && i < 18) {
-                const float w = a.W[RY_ACC + i - 6], e = u[i] - yr[RY_ACC + i - 6];
-                g = w * e; cost += 0.5f * w * e * e;
-            } else if (i >= WF) {
-                const float w = a.W[RY_FREG + i - WF], e = u[i] - yr[RY_FREG + i - WF];
-                g = w * e; cost += 0.5f * w * e * e;
-            }
-            rr[i] = g;
-        }
-        put_rec(R_R, rr);
-        // dynamics defect
-        const float* xn_g = static_cast<const float*>(__builtin_assume_aligned(Xg + (size_t)shifted_node(k + 1, a.shift, N) * NX, 8));
-        float xn[NX], dd[48];
-#pragma unroll
-        for (int i = 36; i < 48; ++i) dd[i] = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NX; i += 2) { const f32x2 v = *reinterpret_cast<const f32x2*>(xn_g + i); xn[i] = v[0]; xn[i + 1] = v[1]; }
-#pragma unroll
-        for (int i = 0; i < 18; ++i) {
-            const float vn = x[WV + i] + dt * u[WA + i];
-            dd[WV + i] = vn - xn[WV + i];
-            dd[WQ + i] = x[WQ + i] + dt * vn - xn[WQ + i];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            dd[pos_of(WH + i)] = x[WH + i] + dt * (F[i] + (i == 2 ? mp.mass * mp.gz : 0.0f)) - xn[WH + i];
-            dd[pos_of(WH + 3 + i)] = x[WH + 3 + i] + dt * tau_acc[i] - xn[WH + 3 + i];
-        }
-        put_rec(R_D, dd);
-        {
-            float hq16[48];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) hq16[i * 16 + j] = j < 15 ? hq[i][j < 15 ? j : 0] : 0.0f;
-            put_rec(R_HQ, hq16);
-        }
-        put_rec(R_HF, hfr);
-        put_rec(R_CDT, cdt);
-        // friction pyramid
-        float fv[12], g[NG];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) fv[i] = u[WF + i];
-        gdot(mp, fv, g);
-        put_rec(R_C, g);       // h = 0
-        static_assert(R_ACT % 4 == 0 && R_COST == R_ACT + 1 && R_ZERO == R_ACT + 2 && R_DT == R_ACT + 3 && R_DT2 % 4 == 0, "tail of the record");
-        const unsigned act = (a.n_ipm > 0) ? active_mask(p) : 0u;
-        *reinterpret_cast<f32x4*>(rec + R_ACT) = f32x4{__uint_as_float(act), cost, 0.0f, dt};
-        rec[R_DT2] = dt * dt;
-    } else {
-        rec[R_COST] = cost;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// tile helpers of the blocked sweeps
-constexpr int LDU = 36;      // LDS column stride of the 32-row elimination columns (Huu | H~ux -> W | Y)
-constexpr int LDH = 52;      // LDS column stride of the 48-row transposition buffer of H~xx
-constexpr int IPMW = 57;     // LDS row of a stage's barrier-modified input terms: rt[30] at 0, Rf[4][5] at 32
-constexpr int IPM_RF = 32;
-
-constexpr int KLD = 20;                      // LDS column stride of a gain tile K~' (conflict-free 16 B row reads)
-constexpr int KBUF = UT * XT * 16 * KLD;     // the six tiles of one stage
-struct WbLds {
-    int colU, hbuf, recb, ipm, klds, n_klds, total;
-    __host__ __device__ explicit WbLds(int N) {
-        int o = 0;
-        colU = o; o += NG * 0 + 32 * LDU;
-        hbuf = o; o += 48 * LDH;
-        recb = o; o += 256;
-        ipm = o;  o += r4(N * IPMW);
-        // the gains of the LAST stages of a backward sweep (the first of the forward sweep) stay in the LDS -- as many as fit next to
-        // three other waves of the CU (160 KB / 4): the forward sweep starts without a trip to memory and those images never leave the CU
-        klds = o;
-        n_klds = (o + 2 * KBUF) * 4 <= 40 * 1024 ? 2 : (o + KBUF) * 4 <= 40 * 1024 ? 1 : 0;
-        if (n_klds > N) n_klds = N;
-        o += n_klds * KBUF;
-        total = o;
-    }
-};
-
-// Eight multipliers of pivot J at once: eight v_readlane into eight different SGPRs, then the wait states a VALU read of
-// a freshly written SGPR needs on gfx950 -- once per group.  Left to the compiler the elimination came out as
-// readlane -> s_nop 1 -> fma on ONE reused SGPR, 435 times per stage (tools/wb_stamps.py: 7.8 k cycles per stage).
-template <int J>
-__device__ __forceinline__ void bcast_group(const float (&v)[8], float (&o)[8]) {
-    int r0, r1, r2, r3, r4, r5, r6, r7;
-    // The leading s_nop is the wait state gfx950 needs between a VALU write of a VGPR and a v_readlane of it: the
-    // hazard recognizer does not look into inline assembly, and the scheduler is free to sink the last FMA of the
-    // previous group to just in front of this one (found as a run-to-run varying 5e-5 error after an unrelated edit
-    // had changed the schedule).
-    asm volatile("s_nop 0\n\tv_readlane_b32 %0, %8, %16\n\tv_readlane_b32 %1, %9, %16\n\tv_readlane_b32 %2, %10, %16\n\t"
-                 "v_readlane_b32 %3, %11, %16\n\tv_readlane_b32 %4, %12, %16\n\tv_readlane_b32 %5, %13, %16\n\t"
-                 "v_readlane_b32 %6, %14, %16\n\tv_readlane_b32 %7, %15, %16\n\ts_nop 1"
-                 : "=s"(r0), "=s"(r1), "=s"(r2), "=s"(r3), "=s"(r4), "=s"(r5), "=s"(r6), "=s"(r7)
-                 : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "n"(J));
-    o[0] = __int_as_float(r0); o[1] = __int_as_float(r1); o[2] = __int_as_float(r2); o[3] = __int_as_float(r3);
-    o[4] = __int_as_float(r4); o[5] = __int_as_float(r5); o[6] = __int_as_float(r6); o[7] = __int_as_float(r7);
-}
-// Coupling mask of the inputs at a stage: the accelerations always couple (bits 0..17); the three force components of a
-// foot couple only while the foot stands -- a swing foot has a zero column in B~, no active pyramid row and a diagonal
-// cost, so its row and column of Huu are exactly diagonal: its multipliers are exact zeros and nothing below it changes.
-// The elimination is instantiated for the contact patterns of a trot (the two diagonal pairs, four-foot stance, flight)
-// with those rows and pivots left out at compile time (160 of the 435 multipliers of a two-foot stage), and for the full
-// mask, which is valid for every pattern.
-__host__ __device__ constexpr unsigned coupling_mask(unsigned stance) {
-    unsigned m = 0x3FFFFu;
-    for (int f = 0; f < 4; ++f) m |= ((stance >> f) & 1u) ? (0x7u << (WF + 3 * f)) : 0u;
-    return m;
-}
-// idx-th coupled row above `after`, or -1
-__host__ __device__ constexpr int coupled_row(unsigned mask, int after, int idx) {
-    for (int i = after + 1; i < NU; ++i)
-        if ((mask >> i) & 1u) { if (idx == 0) return i; --idx; }
-    return -1;
-}
-__host__ __device__ constexpr int coupled_rows_above(unsigned mask, int after) {
-    int n = 0;
-    for (int i = after + 1; i < NU; ++i) n += (mask >> i) & 1u;
-    return n;
-}
-// the coupled rows below pivot J, eight per group (the last group padded with its own last row)
-template <int J, unsigned MASK>
-__device__ __forceinline__ void ldl_update(float (&X)[NU], float wx) {
-    constexpr int n = coupled_rows_above(MASK, J);
-#pragma unroll
-    for (int g = 0; g < (n + 7) / 8; ++g) {
-        float v[8], l[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            constexpr int dummy = 0; (void)dummy;
-            const int idx = 8 * g + u < n ? 8 * g + u : n - 1;
-            v[u] = X[coupled_row(MASK, J, idx)];
-        }
-        bcast_group<J>(v, l);
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (8 * g + u < n) X[coupled_row(MASK, J, 8 * g + u)] = fmaf(-l[u], wx, X[coupled_row(MASK, J, 8 * g + u)]);
-    }
-}
-template <int J, unsigned MASK>
-__device__ __forceinline__ void ldl_pivots(float (&X)[NU], bool& ok, const float (&rs_free)[12]) {
-    if constexpr (J < NU) {
-        if constexpr ((MASK >> J) & 1u) {
-            const float d = bcast(X[J], J);
-            ok = ok && (d > 0.0f);
-            const float rs = __builtin_amdgcn_rsqf(d);
-            X[J] *= rs;
-            if constexpr (coupled_rows_above(MASK, J) > 0) ldl_update<J, MASK>(X, X[J] * rs);
-        } else {
-            // a decoupled input (a force component of a swing foot): nothing of B~'P~B~ or of the barrier reaches its pivot, which
-            // is the constant W_f_reg + reg -- its 1 / sqrt comes from the kernel's prologue (the same v_rsq of the same bits)
-            // instead of a v_readlane -> v_rsq on the elimination's dependent chain
-            X[J] *= rs_free[J >= WF ? J - WF : 0];
-        }
-        ldl_pivots<J + 1, MASK>(X, ok, rs_free);
-    }
-}
-
-// ---- the same elimination with its rank-1 updates on the matrix pipe ------------------------------------------------------
-// Register file: row i of [Huu | I] in register i & 3 of Xq[i >> 2] (lane = column).  v_mfma_f32_4x4x1_16b_f32 is sixteen 4 x 4
-// outer products, D[v][lane] = C[v][lane] + A[lane 4 (lane / 4) + v] B[lane], and with its A-broadcast control (cbsz = 4,
-// abid = g) all sixteen blocks take the A operand of block g: D[v][lane] = C[v][lane] + A[lane 4g + v] B[lane].  Huu is symmetric
-// and stays so under the elimination, so the multiplier of row i under pivot J, M[i][J], is what the scaled pivot row y_J holds
-// in LANE i: with A = y_J and B = -y_J ONE two-pass instruction updates the four rows of group g in all 64 columns -- no
-// broadcast, no data movement -- where the scalar form spends four v_readlane and four v_fma.
-// The pivots themselves are a dependent chain (v_readlane -> v_rsq -> scale -> update of the next row -> v_readlane ...): a pivot
-// updates the rows up to the end of panel P + LDL_AHEAD with scalar multipliers (v_readlane of y_J), the row groups further down
-// take the four pivots of a panel as four MFMAs each (tools/probes/mfma4x4x1.hip checks the operand layout on the device).
-constexpr int LDL_ROWS = 32, LDL_GROUPS = LDL_ROWS / 4;
-#ifndef WB_LDL_AHEAD
-#define WB_LDL_AHEAD 0
-#endif
-constexpr int LDL_AHEAD = WB_LDL_AHEAD;
-template <int J>
-__device__ __forceinline__ void bcast_lanes7(float y, float (&o)[7]) {
-    int r0, r1, r2, r3, r4, r5, r6;
-    // leading s_nop: see bcast_group
-    asm volatile("s_nop 0\n\tv_readlane_b32 %0, %7, %8\n\tv_readlane_b32 %1, %7, %9\n\tv_readlane_b32 %2, %7, %10\n\t"
-                 "v_readlane_b32 %3, %7, %11\n\tv_readlane_b32 %4, %7, %12\n\tv_readlane_b32 %5, %7, %13\n\t"
-                 "v_readlane_b32 %6, %7, %14\n\ts_nop 1"
-                 : "=s"(r0), "=s"(r1), "=s"(r2), "=s"(r3), "=s"(r4), "=s"(r5), "=s"(r6)
-                 : "v"(y), "n"(J + 1), "n"(J + 2), "n"(J + 3), "n"(J + 4), "n"(J + 5), "n"(J + 6), "n"(J + 7));
-    o[0] = __int_as_float(r0); o[1] = __int_as_float(r1); o[2] = __int_as_float(r2); o[3] = __int_as_float(r3);
-    o[4] = __int_as_float(r4); o[5] = __int_as_float(r5); o[6] = __int_as_float(r6);
-}
-template <int J>
-__device__ __forceinline__ void bcast_lanes3(float y, float (&o)[7]) {
-    int r0, r1, r2;
-    asm volatile("s_nop 0\n\tv_readlane_b32 %0, %3, %4\n\tv_readlane_b32 %1, %3, %5\n\tv_readlane_b32 %2, %3, %6\n\ts_nop 1"
-                 : "=s"(r0), "=s"(r1), "=s"(r2)
-                 : "v"(y), "n"(J + 1), "n"(J + 2), "n"(J + 3));
-    o[0] = __int_as_float(r0); o[1] = __int_as_float(r1); o[2] = __int_as_float(r2);
-    o[3] = o[4] = o[5] = o[6] = 0.0f;
-}
-// the pivots `panel` (bit jj: pivot 4P + jj is coupled) applied to the row groups G .. LDL_GROUPS-1
-template <int P, int G, unsigned MASK>
-__device__ __forceinline__ void ldl_trailing(f32x4 (&Xq)[LDL_GROUPS], const float (&ny)[4]) {
-    if constexpr (G < LDL_GROUPS) {
-        if constexpr (((MASK >> (4 * G)) & 0xFu) != 0u) {      // not a group of decoupled inputs only (or past the last row)
-            constexpr unsigned panel = (MASK >> (4 * P)) & 0xFu;
-            if constexpr (panel & 1u) Xq[G] = __builtin_amdgcn_mfma_f32_4x4x1f32(Xq[P][0], ny[0], Xq[G], 4, G, 0);
-            if constexpr (panel & 2u) Xq[G] = __builtin_amdgcn_mfma_f32_4x4x1f32(Xq[P][1], ny[1], Xq[G], 4, G, 0);
-            if constexpr (panel & 4u) Xq[G] = __builtin_amdgcn_mfma_f32_4x4x1f32(Xq[P][2], ny[2], Xq[G], 4, G, 0);
-            if constexpr (panel & 8u) Xq[G] = __builtin_amdgcn_mfma_f32_4x4x1f32(Xq[P][3], ny[3], Xq[G], 4, G, 0);
-        }
-        ldl_trailing<P, G + 1, MASK>(Xq, ny);
-    }
-}
-#ifdef WB_T_LDL_ROWCHAIN   // timing build (tools/ab_wb.sh): the panel's pivots as a chain of row operations
-template <int P, unsigned MASK>
-__device__ __forceinline__ void ldl_panel(f32x4 (&Xq)[LDL_GROUPS], bool& ok, const float (&rs_free)[12]) {
-    if constexpr (P < LDL_GROUPS) {
-        float ny[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        auto pivot = [&](auto jc) {
-            constexpr int J = 4 * P + decltype(jc)::value;
-            if constexpr (J < NU) {
-                if constexpr ((MASK >> J) & 1u) {
-                    const float d = bcast(Xq[P][J & 3], J);
-                    ok = ok && (d > 0.0f);
-                    const float y = Xq[P][J & 3] * __builtin_amdgcn_rsqf(d);
-                    Xq[P][J & 3] = y;
-                    ny[J & 3] = -y;
-                    constexpr int end = 4 * (P + LDL_AHEAD) + 3;
-                    constexpr int last = end < NU - 1 ? end : NU - 1;                    // last row that takes scalar multipliers
-                    constexpr unsigned below = (last > J) ? (MASK >> (J + 1)) & ((1u << (last - J)) - 1u) : 0u;
-                    if constexpr (below != 0u) {
-                        float l[7];
-                        if constexpr (last - J > 3) bcast_lanes7<J>(y, l); else bcast_lanes3<J>(y, l);
-#pragma unroll
-                        for (int u = 0; u < 7; ++u)
-                            if (u < last - J && ((below >> u) & 1u)) {
-                                const int i = J + 1 + u;
-                                Xq[i >> 2][i & 3] = fmaf(-l[u], y, Xq[i >> 2][i & 3]);
-                            }
-                    }
-                } else {
-                    Xq[P][J & 3] *= rs_free[J >= WF ? J - WF : 0];
-                }
-            }
-        };
-        pivot(std::integral_constant<int, 0>{});
-        pivot(std::integral_constant<int, 1>{});
-        pivot(std::integral_constant<int, 2>{});
-        pivot(std::integral_constant<int, 3>{});
-        ldl_trailing<P, P + 1 + LDL_AHEAD, MASK>(Xq, ny);
-        ldl_panel<P + 1, MASK>(Xq, ok, rs_free);
-    }
-}
-#else
-// One panel: the 4 x 4 diagonal block of the panel's rows (ten numbers, lanes 4P .. 4P+3 of the four registers) is factorised on
-// wave-uniform values -- pivot -> v_rsq -> multiplier -> next pivot, three operations per pivot and no cross-lane move on the
-// chain -- and the four rows follow it as y_c = (x_c - sum_{k<c} l_ck y_k) / sqrt(d_c); then the row groups below, on the matrix pipe.
-template <int P, unsigned MASK>
-__device__ __forceinline__ void ldl_panel(f32x4 (&Xq)[LDL_GROUPS], bool& ok, const float (&rs_free)[12]) {
-    if constexpr (P < LDL_GROUPS) {
-        constexpr int J0 = 4 * P;
-        constexpr unsigned pm = (MASK >> J0) & 0xFu;          // coupled rows of the panel (rows past NU - 1 have no bit)
-        float blk[4][4], l[4][4], rs[4] = {1.0f, 1.0f, 1.0f, 1.0f}, ny[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c <= r; ++c)
-                blk[r][c] = (((pm >> r) & 1u) && ((pm >> c) & 1u)) ? bcast(Xq[P][r], J0 + c) : 0.0f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if ((pm >> c) & 1u) {
-                float d = blk[c][c];
-#pragma unroll
-                for (int k = 0; k < c; ++k)
-                    if ((pm >> k) & 1u) d = fmaf(-l[c][k], l[c][k], d);
-                ok = ok && (d > 0.0f);
-                rs[c] = __builtin_amdgcn_rsqf(d);
-#pragma unroll
-                for (int r = c + 1; r < 4; ++r)
-                    if ((pm >> r) & 1u) {
-                        float t = blk[r][c];
-#pragma unroll
-                        for (int k = 0; k < c; ++k)
-                            if ((pm >> k) & 1u) t = fmaf(-l[r][k], l[c][k], t);
-                        l[r][c] = t * rs[c];
-                    }
-            } else if (J0 + c < NU) {
-                // a decoupled input (a force component of a swing foot): see ldl_pivots
-                rs[c] = rs_free[J0 + c >= WF ? J0 + c - WF : 0];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (J0 + c < NU) {
-                float v = Xq[P][c];
-                if ((pm >> c) & 1u) {
-#pragma unroll
-                    for (int k = 0; k < c; ++k)
-                        if ((pm >> k) & 1u) v = fmaf(-l[c][k], Xq[P][k], v);
-                }
-                v *= rs[c];
-                Xq[P][c] = v;
-                ny[c] = -v;
-            }
-        ldl_trailing<P, P + 1, MASK>(Xq, ny);
-        ldl_panel<P + 1, MASK>(Xq, ok, rs_free);
-    }
-}
-#endif
 
 // a lane shift inside the 16-lane rows (DPP row_shr:n = 0x110 + n: lane i reads lane i - n; row_shl:n = 0x100 + n: lane i + n);
 // lanes whose source falls outside their row read 0
@@ -870,7 +148,7 @@ __global__ __launch_bounds__(64, 1) void nmpc_wb_qp_kernel(const WbArgs a) {
     f32x4 cjA, cjB, gcol_n[XT];
     float grow_n[XT];
     auto request_node = [&](int k) {
-        const float* js = ws + wl.js + (size_t)k * JS_FLOATS;
+        const float* js = ws + wl.js + (size_t)k * CJ_FLOATS;
         const float* rec = recs + (size_t)k * REC;
         cjA = *reinterpret_cast<const f32x4*>(js + 4 * lane);
         cjB = *reinterpret_cast<const f32x4*>(js + (cj_second ? 4 * (lane + 64) : 0));
@@ -1166,7 +444,7 @@ __global__ __launch_bounds__(64, 1) void nmpc_wb_qp_kernel(const WbArgs a) {
             }
         }
         // constants of the identity blocks of B~ (see the backward stage): dt^2, on columns 0, 1 of a tile, on rows 0, 1 of a tile
-        // 1 / sqrt of the pivot of a decoupled force input, by component: Huu[j][j] = (W_f_reg + reg) + 0 there (see ldl_pivots)
+        // 1 / sqrt of the pivot of a decoupled force input, by component: Huu[j][j] = (W_f_reg + reg) + 0 there (see ldl_panel)
         float rs_free[12];
     #pragma unroll
         for (int i = 0; i < 12; ++i) rs_free[i] = rs_free_w[i];
