@@ -1,5 +1,6 @@
 /* nmpc_torque.h -- C-ABI of the torque layer: batched inverse dynamics + PD for the
- * plans the NMPC solve produces (libnmpc_hip.so).
+ * plans the NMPC solve produces, and the forward dynamics that turn a torque or a PD target back into
+ * motion under given contact forces (libnmpc_hip.so).
  *
  * Replaces, for B robots at once:
  *   QuadrupedDynamics.id_torques            mpc_controller/utils/dynamics.py:136-163
@@ -53,6 +54,25 @@ const char *nmpc_torque_last_error(void *handle);
  * tau [B][n_actuated]. */
 int nmpc_id_torques_batch(void *handle, int B, const float *q, const float *v, const float *a,
                           const float *f, float *tau, void *stream);
+
+/* Forward dynamics: a = M(q)^-1 ( S^T tau - h(q, v) + sum_feet J_foot^T f ), the inverse of nmpc_id_torques_batch
+ * (articulated-body algorithm, one thread per robot; contact forces are inputs, there is no contact model).
+ * q, v [B][n_joints]; tau [B][n_actuated], the generalised forces of the LAST n_actuated joints, all other joints
+ * carry none (NULL = all zero); f [B][n_feet][3] world frame (NULL = none); a [B][n_joints].
+ * A robot whose elimination meets a joint pivot that is not a positive finite number (a massless leaf body) gets a
+ * row of NaN, as nmpc_gather_rows marks its rows; the call returns NMPC_OK. */
+int nmpc_fd_accel_batch(void *handle, int B, const float *q, const float *v, const float *tau,
+                        const float *f, float *a, void *stream);
+
+/* n_sub semi-implicit Euler substeps of length dt under constant f, the PD law re-evaluated every substep:
+ *   tau = tau_ff + kp (q_des - q[-nu:]) - kd v[-nu:]     (q_des NULL: tau = tau_ff; tau_ff NULL = 0)
+ *   a = fd(q, v, tau, f);  v += dt a;  q += dt v          (q_dot = v holds for this state)
+ * q_des [B][n_actuated] is a recorded action in joint order (RolloutMPC.py:250).  q_out, v_out [B][n_joints] may
+ * alias q, v; a_out [B][n_joints] (NULL allowed) is the acceleration of the last substep.  One launch per call.
+ * NMPC_E_ARG (text in nmpc_torque_last_error): n_sub < 1, dt <= 0, a NULL q, v, q_out or v_out.  NaN rows as above. */
+int nmpc_fd_step_batch(void *handle, int B, int n_sub, float dt, const float *q, const float *v,
+                       const float *tau_ff, const float *q_des, float kp, float kd, const float *f,
+                       float *q_out, float *v_out, float *a_out, void *stream);
 
 /* _compute_pd_torques: tau_ff [B][nu] (NULL = 0); q, v, q_plan, v_plan [B][n_joints] (their last nu
  * entries are used); tau [B][nu] (may alias tau_ff). */

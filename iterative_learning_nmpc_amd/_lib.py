@@ -81,6 +81,9 @@ SIGNATURES = {
     "nmpc_torque_destroy": (None, [c_void_p]),
     "nmpc_torque_last_error": (ctypes.c_char_p, [c_void_p]),
     "nmpc_id_torques_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_fd_accel_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_fd_step_batch": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_pd_torques_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                       c_void_p, c_void_p]),
     "nmpc_pd_target_action_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,

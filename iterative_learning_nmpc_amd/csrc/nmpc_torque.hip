@@ -9,11 +9,14 @@
 // out; force and moment on the way back) live in a 3.5 KB LDS slice per thread laid out [slot][thread], so
 // that the parent look-ups -- a run-time index, which would push register arrays into scratch memory --
 // are conflict-free LDS reads.  ~5 kFLOP per robot: the layer is latency-, not throughput-relevant.
+// The other direction -- accelerations from torques and given contact forces, and a PD-driven integration step around them --
+// is nmpc_torque_fd.hip.inc, included below.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -331,6 +334,8 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
     action[e] = (tau[b * nu + src] + kd * v[j]) / kp + q[j];
 }
 
+#include "nmpc_torque_fd.hip.inc"
+
 }  // namespace nmpc_torque
 
 // ================================================================================================
@@ -344,6 +349,7 @@ struct Torque {
     Model host{};
     Model* dev = nullptr;
     int device = 0;
+    int fd_width = 32;                  // robots per block of fd_kernel: fd_block_width(n), or 16 if NMPC_FD_WIDTH=16 asks for it (tools/fd_cost.py)
     std::string err;
 };
 
@@ -356,7 +362,24 @@ int allocate(Torque* t) {
     // more than the default 64 KB of LDS per block
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(id_torques_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             MAXJ * SLOTS * TPB * (int)sizeof(float)));
+    // the forward dynamics' slice: the most its instantiation can be asked for (25 joints x 32 robots, 32 joints x 16)
+    if (t->fd_width == 32)
+        NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(fd_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)fd_lds_bytes(25, 32)));
+    else
+        NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(fd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)fd_lds_bytes(MAXJ, 16)));
     return NMPC_OK;
+}
+
+// both forward-dynamics entry points: one launch of fd_kernel at the handle's block width
+int launch_fd(Torque* t, const FdArgs& p, void* stream) {
+    const int w = t->fd_width;
+    const dim3 grid((unsigned)((p.B + w - 1) / w));
+    const size_t lds = fd_lds_bytes(t->host.n, w);
+    if (w == 32) hipLaunchKernelGGL(fd_kernel<32>, grid, dim3(32), lds, static_cast<hipStream_t>(stream), t->dev, p);
+    else hipLaunchKernelGGL(fd_kernel<16>, grid, dim3(16), lds, static_cast<hipStream_t>(stream), t->dev, p);
+    return launched(t);
 }
 
 }  // namespace
@@ -407,6 +430,9 @@ int nmpc_torque_create(const nmpc_tree_model* mdl, int device_id, void** handle)
     NMPC_ENTER(no_handle, device_id);
     Torque* t = new Torque();
     t->host = m; t->device = device_id;
+    t->fd_width = fd_block_width(m.n);
+    if (const char* w = std::getenv("NMPC_FD_WIDTH"))
+        if (!std::strcmp(w, "16")) t->fd_width = 16;
     if (const int rc = allocate(t)) { nmpc_torque_destroy(t); return rc; }
     *handle = t;
     return NMPC_OK;
@@ -434,6 +460,32 @@ int nmpc_id_torques_batch(void* handle, int B, const float* q, const float* v, c
     hipLaunchKernelGGL(id_torques_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream),
                        t->dev, B, q, v, a, f, tau);
     return launched(t);
+}
+
+int nmpc_fd_accel_batch(void* handle, int B, const float* q, const float* v, const float* tau, const float* f, float* a, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !v || !a) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, a");
+    NMPC_ENTER(t, t->device);
+    FdArgs p{};
+    p.B = B; p.q = q; p.v = v; p.tau = tau; p.f = f; p.a_out = a;
+    return launch_fd(t, p, stream);
+}
+
+int nmpc_fd_step_batch(void* handle, int B, int n_sub, float dt, const float* q, const float* v, const float* tau_ff, const float* q_des,
+                       float kp, float kd, const float* f, float* q_out, float* v_out, float* a_out, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
+    if (n_sub < 1) return fail(t, NMPC_E_ARG, "n_sub must be at least 1");
+    if (!(dt > 0.0f)) return fail(t, NMPC_E_ARG, "dt must be positive");
+    NMPC_ENTER(t, t->device);
+    FdArgs p{};
+    p.B = B; p.n_sub = n_sub; p.dt = dt; p.kp = kp; p.kd = kd;
+    p.q = q; p.v = v; p.tau = tau_ff; p.q_des = q_des; p.f = f; p.q_out = q_out; p.v_out = v_out; p.a_out = a_out;
+    return launch_fd(t, p, stream);
 }
 
 int nmpc_pd_torques_batch(void* handle, int B, const float* tau_ff, const float* q, const float* v, const float* q_plan,

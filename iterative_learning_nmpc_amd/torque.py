@@ -65,6 +65,37 @@ class BatchedTorqueLayer:
                    self._h, "nmpc_id_torques_batch", "torque")
         return tau
 
+    def forward_dynamics(self, q, v, tau=None, f=None) -> torch.Tensor:
+        """nmpc_fd_accel_batch, the inverse of `id_torques`: q, v [B, n]; tau [B, nu] on the last nu joints (None = zero);
+        f [B, n_feet, 3] world-frame contact forces (None = none) -> the accelerations [B, n]."""
+        q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
+        tau = None if tau is None else self._in(tau, (self.nu,), "tau")
+        f = None if f is None else self._in(f, (self.n_feet, 3), "f")
+        B = q.shape[0]
+        if any(x is not None and x.shape[0] != B for x in (v, tau, f)):
+            raise ValueError("batch sizes differ")
+        a = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nmpc_fd_accel_batch(self._h, B, ptr(q), ptr(v), ptr(tau), ptr(f), ptr(a), stream(self.device)),
+                   self._h, "nmpc_fd_accel_batch", "torque")
+        return a
+
+    def step(self, q, v, dt: float, n_sub: int = 1, tau_ff=None, q_des=None, kp: float = KP, kd: float = KD, f=None):
+        """nmpc_fd_step_batch: n_sub semi-implicit Euler substeps of length dt under constant f with
+        tau = tau_ff + kp (q_des - q_j) - kd v_j re-evaluated every substep (q_des [B, nu]: a recorded action in joint
+        order; None: tau = tau_ff; tau_ff None = zero) -> (q, v, a of the last substep), new tensors [B, n]."""
+        q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
+        tau_ff = None if tau_ff is None else self._in(tau_ff, (self.nu,), "tau_ff")
+        q_des = None if q_des is None else self._in(q_des, (self.nu,), "q_des")
+        f = None if f is None else self._in(f, (self.n_feet, 3), "f")
+        B = q.shape[0]
+        if any(x is not None and x.shape[0] != B for x in (v, tau_ff, q_des, f)):
+            raise ValueError("batch sizes differ")
+        q_out, v_out, a_out = (torch.empty(B, self.n, dtype=torch.float32, device=self.device) for _ in range(3))
+        _lib.check(self.lib.nmpc_fd_step_batch(self._h, B, int(n_sub), float(dt), ptr(q), ptr(v), ptr(tau_ff), ptr(q_des), float(kp),
+                                               float(kd), ptr(f), ptr(q_out), ptr(v_out), ptr(a_out), stream(self.device)),
+                   self._h, "nmpc_fd_step_batch", "torque")
+        return q_out, v_out, a_out
+
     def compute_pd_torques(self, q, v, torques_ff, q_plan, v_plan, Kp: float, Kd: float) -> torch.Tensor:
         """mpc.py:592-599: torques_ff + Kp (q_plan[-nu:] - q[-nu:]) + Kd (v_plan[-nu:] - v[-nu:])."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")

@@ -1,0 +1,56 @@
+"""The forward-dynamics entry points of include/nmpc_torque.h exist in every layer: exported by libnmpc_hip.so, bound with
+the header's argument lists, and behind methods of BatchedTorqueLayer.  No GPU: what is decided on the host is checked."""
+import ctypes
+import inspect
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+C_TYPES = {"void *": ctypes.c_void_p, "const float *": ctypes.c_void_p, "float *": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float}
+NAMES = ("nmpc_fd_accel_batch", "nmpc_fd_step_batch")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    from iterative_learning_nmpc_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    return _lib.load()
+
+
+def header_arguments(name):
+    """The ctypes argument list the header's declaration of `name` asks for."""
+    header = open(os.path.join(ROOT, "include", "nmpc_torque.h")).read()
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header)
+    assert m, f"{name} is not declared in include/nmpc_torque.h"
+    return [C_TYPES[re.sub(r"\s*\w+$", "", " ".join(a.split())).strip()] for a in m.group(1).split(",")]
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_symbol_is_exported_and_bound_as_the_header_declares_it(lib, name):
+    from iterative_learning_nmpc_amd import _lib
+    assert getattr(lib, name) is not None
+    res, args = _lib.SIGNATURES[name]
+    assert res is ctypes.c_int and args == header_arguments(name)
+
+
+def test_argument_lists():
+    assert len(header_arguments("nmpc_fd_accel_batch")) == 8 and len(header_arguments("nmpc_fd_step_batch")) == 15
+
+
+def test_layer_has_both_methods():
+    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
+    from iterative_learning_nmpc_amd.trajectory_io import KD, KP
+    assert list(inspect.signature(BatchedTorqueLayer.forward_dynamics).parameters) == ["self", "q", "v", "tau", "f"]
+    step = inspect.signature(BatchedTorqueLayer.step).parameters
+    assert list(step) == ["self", "q", "v", "dt", "n_sub", "tau_ff", "q_des", "kp", "kd", "f"]
+    assert (step["n_sub"].default, step["kp"].default, step["kd"].default) == (1, KP, KD)
+
+
+def test_a_null_handle_is_refused_on_the_host(lib):
+    assert lib.nmpc_fd_accel_batch(None, 1, None, None, None, None, None, None) == -1
+    assert lib.nmpc_fd_step_batch(None, 1, 1, 1e-3, None, None, None, None, 0.0, 0.0, None, None, None, None, None) == -1
+    assert b"handle" in lib.nmpc_torque_last_error(None)
