@@ -1,6 +1,6 @@
 /* nmpc_torque.h -- C-ABI of the torque layer: batched inverse dynamics + PD for the
  * plans the NMPC solve produces, and the forward dynamics that turn a torque or a PD target back into
- * motion under given contact forces (libnmpc_hip.so).
+ * motion under given contact forces or on a declared ground-contact law (libnmpc_hip.so).
  *
  * Replaces, for B robots at once:
  *   QuadrupedDynamics.id_torques            mpc_controller/utils/dynamics.py:136-163
@@ -73,6 +73,33 @@ int nmpc_fd_accel_batch(void *handle, int B, const float *q, const float *v, con
 int nmpc_fd_step_batch(void *handle, int B, int n_sub, float dt, const float *q, const float *v,
                        const float *tau_ff, const float *q_des, float kp, float kd, const float *f,
                        float *q_out, float *v_out, float *a_out, void *stream);
+
+/* The ground-contact plant [decl] (the reference's is MuJoCo).  The ground is the plane z = ground_z with normal e_z.  A foot
+ * point at world position p with world velocity pd and penetration delta = ground_z - p_z is pushed with
+ *   f_z  = stiffness delta max(0, 1 - damping pd_z)  for delta > 0, else 0    (Hunt-Crossley: continuous at touch-down, never pulls)
+ *   f_xy = -mu f_z pd_xy / sqrt(|pd_xy|^2 + slip_velocity^2)                  (regularised Coulomb, |f_xy| < mu f_z)
+ * and the PD torque of the step is clamped to [-tau_max, tau_max] (tau_max <= 0: no limit).  The step integrates explicitly,
+ * and both terms are dampers on the foot, so it is stable only while
+ *   mu f_z dt / (slip_velocity m_foot) < 2   and   stiffness delta damping dt / m_foot < 2
+ * (m_foot: the mass the foot point moves, a few hundred grams on the quadruped).  k = 1e4 N/m, c = 3 s/m, mu = 0.8,
+ * slip_velocity = 0.05 m/s at dt = 0.5 ms let the 15 kg quadruped stand; dt = 1 ms with slip_velocity = 0.01 m/s chatters.
+ * NMPC_E_ARG wherever a cfg is taken: cfg NULL, a field that is not finite, stiffness, damping or mu < 0, slip_velocity <= 0. */
+typedef struct { float ground_z, stiffness, damping, mu, slip_velocity, tau_max; } nmpc_contact_cfg;   /* host struct, read at the call */
+
+/* world position and velocity of every foot point: pos, vel [B][n_feet][3] (either may be NULL, not both); v NULL = zero */
+int nmpc_foot_kinematics_batch(void *handle, int B, const float *q, const float *v, float *pos, float *vel, void *stream);
+
+/* the law alone: f [B][n_feet][3], the forces nmpc_fd_accel_batch would have to be handed (v NULL = zero) */
+int nmpc_contact_forces_batch(void *handle, int B, const nmpc_contact_cfg *cfg, const float *q, const float *v, float *f, void *stream);
+
+/* nmpc_fd_step_batch with the contact forces re-evaluated from (q, v) in every substep and the torque limit applied:
+ *   tau = clamp(tau_ff + kp (q_des - q_j) - kd v_j);  f = contact(q, v);  a = fd(q, v, tau, f);  v += dt a;  q += dt v
+ * f_out [B][n_feet][3], tau_out [B][n_actuated]: force and clamped torque of the LAST substep (NULL allowed); q_out, v_out may
+ * alias q, v.  One launch per call; f never goes through memory between substeps.  NMPC_E_ARG as nmpc_fd_step_batch and for
+ * the cfg as above.  NaN rows in all outputs as nmpc_fd_accel_batch. */
+int nmpc_contact_step_batch(void *handle, int B, int n_sub, float dt, const nmpc_contact_cfg *cfg, const float *q, const float *v,
+                            const float *tau_ff, const float *q_des, float kp, float kd,
+                            float *q_out, float *v_out, float *a_out, float *f_out, float *tau_out, void *stream);
 
 /* _compute_pd_torques: tau_ff [B][nu] (NULL = 0); q, v, q_plan, v_plan [B][n_joints] (their last nu
  * entries are used); tau [B][nu] (may alias tau_ff). */

@@ -84,6 +84,10 @@ SIGNATURES = {
     "nmpc_fd_accel_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_fd_step_batch": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_foot_kinematics_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_contact_forces_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_contact_step_batch": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                        c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_pd_torques_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                       c_void_p, c_void_p]),
     "nmpc_pd_target_action_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
@@ -114,6 +118,11 @@ class NmpcTreeModel(ctypes.Structure):
                 ("placement", POINTER(c_float)), ("mass", POINTER(c_float)), ("com", POINTER(c_float)),
                 ("inertia", POINTER(c_float)), ("foot_joint", POINTER(c_int)), ("foot_offset", POINTER(c_float)),
                 ("gravity", c_float * 3)]
+
+
+class NmpcContactCfg(ctypes.Structure):
+    _fields_ = [("ground_z", c_float), ("stiffness", c_float), ("damping", c_float), ("mu", c_float),
+                ("slip_velocity", c_float), ("tau_max", c_float)]
 
 
 class NmpcRolloutCfg(ctypes.Structure):

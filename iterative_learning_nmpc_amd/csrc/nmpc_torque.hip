@@ -10,7 +10,8 @@
 // that the parent look-ups -- a run-time index, which would push register arrays into scratch memory --
 // are conflict-free LDS reads.  ~5 kFLOP per robot: the layer is latency-, not throughput-relevant.
 // The other direction -- accelerations from torques and given contact forces, and a PD-driven integration step around them --
-// is nmpc_torque_fd.hip.inc, included below.
+// is nmpc_torque_fd.hip.inc, included below; the declared ground-contact law, the foot kinematics it needs and the plant step
+// that evaluates it inside that recursion are nmpc_torque_contact.hip.inc.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -335,6 +336,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 }
 
 #include "nmpc_torque_fd.hip.inc"
+#include "nmpc_torque_contact.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -350,6 +352,7 @@ struct Torque {
     Model* dev = nullptr;
     int device = 0;
     int fd_width = 32;                  // robots per block of fd_kernel: fd_block_width(n), or 16 if NMPC_FD_WIDTH=16 asks for it (tools/fd_cost.py)
+    int ct_width = 32;                  // robots per block of contact_step_kernel: ct_block_width(n)
     std::string err;
 };
 
@@ -369,6 +372,16 @@ int allocate(Torque* t) {
     else
         NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(fd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                 (int)fd_lds_bytes(MAXJ, 16)));
+    // the contact plant: the kinematics slice of the largest tree, and the most the step's instantiation can be asked for by its
+    // own width rule (ct_block_width: ct_wide_joints() joints x 32 robots, the largest tree x 16)
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(foot_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)fk_lds_bytes(MAXJ)));
+    if (t->ct_width == 32)
+        NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(contact_step_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)ct_lds_bytes(ct_wide_joints(), 32)));
+    else
+        NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(contact_step_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)ct_lds_bytes(MAXJ, 16)));
     return NMPC_OK;
 }
 
@@ -379,6 +392,27 @@ int launch_fd(Torque* t, const FdArgs& p, void* stream) {
     const size_t lds = fd_lds_bytes(t->host.n, w);
     if (w == 32) hipLaunchKernelGGL(fd_kernel<32>, grid, dim3(32), lds, static_cast<hipStream_t>(stream), t->dev, p);
     else hipLaunchKernelGGL(fd_kernel<16>, grid, dim3(16), lds, static_cast<hipStream_t>(stream), t->dev, p);
+    return launched(t);
+}
+
+// why a contact configuration cannot be used (nullptr: it can), and the form the kernels read
+const char* contact_cfg_refusal(const nmpc_contact_cfg* c) {
+    if (!c) return "cfg is NULL";
+    for (const float x : {c->ground_z, c->stiffness, c->damping, c->mu, c->slip_velocity, c->tau_max})
+        if (!std::isfinite(x)) return "the contact parameters must be finite";
+    if (c->stiffness < 0.0f || c->damping < 0.0f || c->mu < 0.0f) return "stiffness, damping and mu must not be negative";
+    if (!(c->slip_velocity > 0.0f)) return "slip_velocity must be positive";
+    return nullptr;
+}
+
+ContactCfg device_cfg(const nmpc_contact_cfg& c) {
+    return {c.ground_z, c.stiffness, c.damping, c.mu, c.slip_velocity * c.slip_velocity, c.tau_max};
+}
+
+// the kinematics pass, with or without the law
+int launch_feet(Torque* t, const FootArgs& a, void* stream) {
+    hipLaunchKernelGGL(foot_kernel, dim3((unsigned)((a.B + TPB - 1) / TPB)), dim3(TPB), fk_lds_bytes(t->host.n),
+                       static_cast<hipStream_t>(stream), t->dev, a);
     return launched(t);
 }
 
@@ -431,6 +465,7 @@ int nmpc_torque_create(const nmpc_tree_model* mdl, int device_id, void** handle)
     Torque* t = new Torque();
     t->host = m; t->device = device_id;
     t->fd_width = fd_block_width(m.n);
+    t->ct_width = ct_block_width(m.n);
     if (const char* w = std::getenv("NMPC_FD_WIDTH"))
         if (!std::strcmp(w, "16")) t->fd_width = 16;
     if (const int rc = allocate(t)) { nmpc_torque_destroy(t); return rc; }
@@ -486,6 +521,52 @@ int nmpc_fd_step_batch(void* handle, int B, int n_sub, float dt, const float* q,
     p.B = B; p.n_sub = n_sub; p.dt = dt; p.kp = kp; p.kd = kd;
     p.q = q; p.v = v; p.tau = tau_ff; p.q_des = q_des; p.f = f; p.q_out = q_out; p.v_out = v_out; p.a_out = a_out;
     return launch_fd(t, p, stream);
+}
+
+int nmpc_foot_kinematics_batch(void* handle, int B, const float* q, const float* v, float* pos, float* vel, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || (!pos && !vel)) return fail(t, NMPC_E_ARG, "need B >= 0, q and pos or vel");
+    NMPC_ENTER(t, t->device);
+    FootArgs a{};
+    a.B = B; a.q = q; a.v = v; a.pos = pos; a.vel = vel;
+    return launch_feet(t, a, stream);
+}
+
+int nmpc_contact_forces_batch(void* handle, int B, const nmpc_contact_cfg* cfg, const float* q, const float* v, float* f, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !f) return fail(t, NMPC_E_ARG, "need B >= 0 and q, f");
+    if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
+    NMPC_ENTER(t, t->device);
+    FootArgs a{};
+    a.B = B; a.q = q; a.v = v; a.f = f; a.c = device_cfg(*cfg);
+    return launch_feet(t, a, stream);
+}
+
+int nmpc_contact_step_batch(void* handle, int B, int n_sub, float dt, const nmpc_contact_cfg* cfg, const float* q, const float* v,
+                            const float* tau_ff, const float* q_des, float kp, float kd, float* q_out, float* v_out, float* a_out,
+                            float* f_out, float* tau_out, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
+    if (n_sub < 1) return fail(t, NMPC_E_ARG, "n_sub must be at least 1");
+    if (!(dt > 0.0f)) return fail(t, NMPC_E_ARG, "dt must be positive");
+    if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
+    NMPC_ENTER(t, t->device);
+    ContactArgs p{};
+    p.B = B; p.n_sub = n_sub; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+    p.q = q; p.v = v; p.tau = tau_ff; p.q_des = q_des;
+    p.q_out = q_out; p.v_out = v_out; p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out;
+    const int w = t->ct_width;
+    const dim3 grid((unsigned)((B + w - 1) / w));
+    const size_t lds = ct_lds_bytes(t->host.n, w);
+    if (w == 32) hipLaunchKernelGGL(contact_step_kernel<32>, grid, dim3(32), lds, static_cast<hipStream_t>(stream), t->dev, p);
+    else hipLaunchKernelGGL(contact_step_kernel<16>, grid, dim3(16), lds, static_cast<hipStream_t>(stream), t->dev, p);
+    return launched(t);
 }
 
 int nmpc_pd_torques_batch(void* handle, int B, const float* tau_ff, const float* q, const float* v, const float* q_plan,

@@ -1,0 +1,186 @@
+// nmpc_torque_contact.hip.inc -- the ground-contact plant of the torque layer (nmpc_foot_kinematics_batch,
+// nmpc_contact_forces_batch, nmpc_contact_step_batch of include/nmpc_torque.h); included by nmpc_torque.hip inside namespace
+// nmpc_torque, after nmpc_torque_fd.hip.inc.
+//
+// The declared law (DESIGN.md 8d): the ground is the plane z = ground_z with normal e_z; a foot point at p moving with pd,
+// penetration delta = ground_z - p_z, gets
+//     f_z  = k delta max(0, 1 - c pd_z)                   for delta > 0, else no force      (Hunt-Crossley: continuous, never pulls)
+//     f_xy = -mu f_z pd_xy / sqrt(|pd_xy|^2 + v_eps^2)                                       (regularised Coulomb)
+// One device function states it; the forces kernel evaluates it on the foot kinematics, the step evaluates it inside the
+// articulated-body recursion (fd_accel_body with GroundForces as its force source) where the first outward pass visits the
+// body that carries the foot, so the forces never go through memory between substeps.
+#pragma once
+
+struct ContactCfg {                                       // nmpc_contact_cfg as the kernels read it
+    float ground_z, stiffness, damping, mu, slip2, tau_max;   // slip2 = slip_velocity^2
+};
+
+__device__ __forceinline__ V3 contact_law(const ContactCfg& c, V3 p, V3 pd) {
+    const float delta = c.ground_z - p.z;
+    if (!(delta > 0.0f)) return {0.0f, 0.0f, 0.0f};
+    const float fz = c.stiffness * delta * fmaxf(0.0f, 1.0f - c.damping * pd.z);
+    const float s = -c.mu * fz / sqrtf(pd.x * pd.x + pd.y * pd.y + c.slip2);
+    return {s * pd.x, s * pd.y, fz};
+}
+
+// ---- foot kinematics, and the law on them ---------------------------------------------------------------------------------
+constexpr int FK_RW = 0;     // Rw 9
+constexpr int FK_PW = 9;     // world position of the body origin 3
+constexpr int FK_V = 12;     // w 3, vo 3 (body coordinates)
+constexpr int FK_SLOTS = 18;
+constexpr size_t fk_lds_bytes(int n) { return (size_t)n * FK_SLOTS * TPB * sizeof(float); }
+
+struct FootArgs {
+    int B;
+    const float *q, *v;                                   // v nullptr: at rest
+    float *pos, *vel, *f;                                 // each may be nullptr; f: the law of c on (pos, vel)
+    ContactCfg c;
+};
+
+// One outward pass: Rw, the world position of the body origin and the body-coordinate velocity (w, vo); the foot point of a
+// body is then p = p_w + Rw r, pd = Rw (vo + w x r).  One thread per robot, LDS slice [joint][FK_SLOTS][TPB].
+__global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp, const FootArgs a) {
+    extern __shared__ float body[];                       // [joint][FK_SLOTS][TPB]
+    const Model& m = *mp;
+    const int b = blockIdx.x * TPB + threadIdx.x;
+    if (b >= a.B) return;
+    const int n = m.n;
+    auto at = [&](int joint, int slot) -> float& { return body[(joint * FK_SLOTS + slot) * TPB + threadIdx.x]; };
+    auto get3 = [&](int joint, int slot) { return V3{at(joint, slot), at(joint, slot + 1), at(joint, slot + 2)}; };
+    auto put3 = [&](int joint, int slot, V3 x) { at(joint, slot) = x.x; at(joint, slot + 1) = x.y; at(joint, slot + 2) = x.z; };
+    const float* qb = a.q + (size_t)b * n;
+    const float* vb = a.v ? a.v + (size_t)b * n : nullptr;
+    for (int i = 0; i < n; ++i) {
+        M3 R; V3 p;
+        joint_transform(m, i, qb[i], R, p);
+        const int par = m.parent[i];
+        V3 w_p{0, 0, 0}, vo_p{0, 0, 0}, pw = p;
+        M3 Rw = R;
+        if (par >= 0) {
+            w_p = get3(par, FK_V); vo_p = get3(par, FK_V + 3);
+            M3 Rp;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, FK_RW + k);
+            Rw = mul(Rp, R);
+            pw = get3(par, FK_PW) + mul(Rp, p);
+        }
+        V3 w = mul_t(R, w_p), vo = mul_t(R, vo_p + cross(w_p, p));
+        const float qd = vb ? vb[i] : 0.0f;
+        const V3 ax = v3(m.axis[i]);
+        if (m.type[i] == 0) w = w + qd * ax;
+        else vo = vo + qd * ax;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) at(i, FK_RW + k) = Rw.m[k];
+        put3(i, FK_PW, pw); put3(i, FK_V, w); put3(i, FK_V + 3, vo);
+    }
+    for (int k = 0; k < m.nf; ++k) {
+        const int j = m.foot_joint[k];
+        M3 Rw;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Rw.m[e] = at(j, FK_RW + e);
+        const V3 r = v3(m.foot_offset[k]);
+        const V3 p = get3(j, FK_PW) + mul(Rw, r), pd = mul(Rw, get3(j, FK_V + 3) + cross(get3(j, FK_V), r));
+        const size_t e = ((size_t)b * m.nf + k) * 3;
+        if (a.pos) { a.pos[e] = p.x; a.pos[e + 1] = p.y; a.pos[e + 2] = p.z; }
+        if (a.vel) { a.vel[e] = pd.x; a.vel[e + 1] = pd.y; a.vel[e + 2] = pd.z; }
+        if (a.f) {
+            const V3 f = contact_law(a.c, p, pd);
+            a.f[e] = f.x; a.f[e + 1] = f.y; a.f[e + 2] = f.z;
+        }
+    }
+}
+
+// ---- the contact step -----------------------------------------------------------------------------------------------------
+constexpr int CT_SLOTS = FD_SLOTS + 3;                    // the slice of fd_accel_body and FD_PW, the world position of the body origin
+// the slice, and behind it the parameters of the law: six uniform values that would otherwise live in scalar registers across
+// the whole recursion, which fills the scalar file on its own (they cost 13 SGPR spills there)
+constexpr size_t ct_lds_bytes(int n, int width) { return (size_t)n * CT_SLOTS * width * sizeof(float) + sizeof(ContactCfg); }
+// robots per block: 32 where the slice of n joints fits the CU (n <= 23), 16 otherwise (32 joints: 110 616 B)
+constexpr int ct_block_width(int n) { return ct_lds_bytes(n, 32) <= FD_LDS_MAX ? 32 : 16; }
+// the largest tree that runs at 32 robots per block: its slice is the most contact_step_kernel<32> can be asked for
+constexpr int ct_wide_joints() {
+    int n = MAXJ;
+    while (n > 1 && ct_block_width(n) != 32) --n;
+    return n;
+}
+
+// the law as the force source of fd_accel_body; `out` (this robot's row of f_out, or nullptr) takes the forces as they are used
+struct GroundForces {
+    const ContactCfg* c;                                  // in LDS, behind the block's slice
+    float* out;
+    static constexpr bool kinematic = true;
+    __device__ __forceinline__ bool any() const { return true; }
+    __device__ __forceinline__ V3 operator()(int k, V3 p, V3 pd) const {
+        const V3 f = contact_law(*c, p, pd);
+        if (out) { out[3 * k] = f.x; out[3 * k + 1] = f.y; out[3 * k + 2] = f.z; }
+        return f;
+    }
+};
+
+struct ContactArgs {
+    int B, n_sub;
+    float dt, kp, kd;
+    ContactCfg c;
+    const float *q, *v, *tau, *q_des;                     // tau: tau_ff
+    float *q_out, *v_out, *a_out, *f_out, *tau_out;
+};
+
+// fd_kernel's step with the law in place of given forces and the torque limit after the PD law.  f_out and tau_out are
+// written by the last substep as its force and torque are formed (nothing reads them), a_out, q_out, v_out after the last read
+// of the inputs, so q_out, v_out may alias q, v.  The copy loops are kept as written, as fd_kernel's.
+template <int W>
+__global__ __launch_bounds__(W) void contact_step_kernel(const Model* __restrict__ mp, const ContactArgs p) {
+    extern __shared__ float body[];                       // [joint][CT_SLOTS][W]
+    const Model& m = *mp;
+    const int n = m.n, nu = m.nu, base = n - nu, nf3 = 3 * m.nf;
+    ContactCfg* cfg = reinterpret_cast<ContactCfg*>(body + n * CT_SLOTS * W);
+    if (threadIdx.x == 0) *cfg = p.c;
+    __syncthreads();
+    const int b = blockIdx.x * W + threadIdx.x;
+    if (b >= p.B) return;
+    auto at = [&](int joint, int slot) -> float& { return body[(joint * CT_SLOTS + slot) * W + threadIdx.x]; };
+    const float* qb = p.q + (size_t)b * n;
+    const float* vb = p.v + (size_t)b * n;
+    const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;
+    const float* db = p.q_des ? p.q_des + (size_t)b * nu : nullptr;
+    float* fo = p.f_out ? p.f_out + (size_t)b * nf3 : nullptr;
+    float* to = p.tau_out ? p.tau_out + (size_t)b * nu : nullptr;
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = 0; i < n; ++i) { at(i, FD_Q) = qb[i]; at(i, FD_Q + 1) = vb[i]; }
+    bool sound = true;
+    for (int s = 0; s < p.n_sub; ++s) {
+        const bool last = s == p.n_sub - 1;
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int i = 0; i < n; ++i) {
+            float t = 0.0f;
+            if (i >= base) {
+                t = tb ? tb[i - base] : 0.0f;
+                if (db) t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
+                { const float lim = cfg->tau_max; if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t); }   // a NaN stays NaN
+                if (last && to) to[i - base] = t;
+            }
+            at(i, FD_Q + 2) = t;
+        }
+        sound = fd_accel_body<W, CT_SLOTS>(m, GroundForces{cfg, last ? fo : nullptr}) && sound;
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int i = 0; i < n; ++i) {
+            const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);
+            at(i, FD_Q + 1) = v;
+            at(i, FD_Q) = at(i, FD_Q) + p.dt * v;
+        }
+    }
+    const float nan = __builtin_nanf("");
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = 0; i < n; ++i) {
+        const size_t e = (size_t)b * n + i;
+        if (p.a_out) p.a_out[e] = sound ? at(i, FD_Q + 2) : nan;
+        p.q_out[e] = sound ? at(i, FD_Q) : nan;
+        p.v_out[e] = sound ? at(i, FD_Q + 1) : nan;
+    }
+    if (!sound) {
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int i = 0; fo && i < nf3; ++i) fo[i] = nan;
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int i = 0; to && i < nu; ++i) to[i] = nan;
+    }
+}

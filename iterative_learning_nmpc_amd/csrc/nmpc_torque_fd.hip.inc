@@ -51,14 +51,28 @@ __device__ __forceinline__ void sub_outer(S6& A, V3 x, float s) {
 // R A R^T
 __device__ __forceinline__ M3 rotated(const M3& R, const M3& A) { return mul(mul(R, A), transposed(R)); }
 
-// The accelerations of the robot whose q_i, qd_i and joint forces lie in slots FD_Q .. FD_Q + 2 of its LDS slice; f (world-frame
-// foot forces of this robot, or nullptr) is read from memory.  qdd_i is left in slot FD_Q + 2 of joint i.  Returns false if a
-// pivot is not a positive finite number (a massless leaf body): the caller writes NaN.  W: robots per block (the slice's stride).
-template <int W>
-__device__ __forceinline__ bool fd_accel_body(const Model& m, const float* __restrict__ f) {
-    extern __shared__ float body[];                       // [joint][FD_SLOTS][W]
+// Where the foot forces of the recursion come from.  `force.any()`: are there any; `force(k, p, pd)`: the world-frame force on
+// foot k, whose point is at p and moves with pd in the world.  A source that reads p, pd says so with `kinematic`: the outward
+// pass then also carries the world position of every body origin, in three slots past FD_SLOTS (FD_PW) that its slice must have.
+constexpr int FD_PW = FD_SLOTS;
+
+// given forces: f (world-frame foot forces of this robot, or nullptr) is read from memory
+struct GivenForces {
+    const float* __restrict__ f;
+    static constexpr bool kinematic = false;
+    __device__ __forceinline__ bool any() const { return f; }
+    __device__ __forceinline__ V3 operator()(int k, V3, V3) const { return v3(f + 3 * k); }
+};
+
+// The accelerations of the robot whose q_i, qd_i and joint forces lie in slots FD_Q .. FD_Q + 2 of its LDS slice, under the foot
+// forces of `force`.  qdd_i is left in slot FD_Q + 2 of joint i.  Returns false if a pivot is not a positive finite number (a
+// massless leaf body): the caller writes NaN.  W: robots per block (the slice's stride), NS: slots per joint of the slice.
+template <int W, int NS, class Force>
+__device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force) {
+    extern __shared__ float body[];                       // [joint][NS][W]
+    static_assert(NS >= FD_SLOTS + (Force::kinematic ? 3 : 0), "the slice is too narrow for this force source");
     const int n = m.n;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * FD_SLOTS + slot) * W + threadIdx.x]; };
+    auto at = [&](int joint, int slot) -> float& { return body[(joint * NS + slot) * W + threadIdx.x]; };
     auto get3 = [&](int joint, int slot) { return V3{at(joint, slot), at(joint, slot + 1), at(joint, slot + 2)}; };
     auto put3 = [&](int joint, int slot, V3 x) { at(joint, slot) = x.x; at(joint, slot + 1) = x.y; at(joint, slot + 2) = x.z; };
 
@@ -69,13 +83,16 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const float* __res
         const int par = m.parent[i];
         V3 w_p{0, 0, 0}, vo_p{0, 0, 0};
         M3 Rw = R;
+        V3 pw = p;                     // world position of the body origin (kinematic force sources only)
         if (par >= 0) {
             w_p = get3(par, FD_V); vo_p = get3(par, FD_V + 3);
             M3 Rp;
 #pragma unroll
             for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, FD_RW + k);
             Rw = mul(Rp, R);
+            if constexpr (Force::kinematic) pw = get3(par, FD_PW) + mul(Rp, p);
         }
+        if constexpr (Force::kinematic) put3(i, FD_PW, pw);
         V3 w = mul_t(R, w_p), vo = mul_t(R, vo_p + cross(w_p, p));
         const V3 ax = v3(m.axis[i]);
         const float qd = at(i, FD_Q + 1);
@@ -106,10 +123,15 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const float* __res
         const V3 h_l = mass * (vo + cross(w, c)), h_n = inertia(w) + cross(c, h_l);
         V3 p_n = cross(w, h_n) + cross(vo, h_l), p_l = cross(w, h_l);
         // contact forces: world-frame force at the foot point of this body
-        if (f) {
+        if (force.any()) {
             for (int k = 0; k < m.nf; ++k) {
                 if (m.foot_joint[k] != i) continue;
-                const V3 l = mul_t(Rw, v3(f + 3 * k));
+                V3 fp{0, 0, 0}, fv{0, 0, 0};       // the foot point's world position and velocity, for a source that reads them
+                if constexpr (Force::kinematic) {
+                    const V3 r = v3(m.foot_offset[k]);
+                    fp = pw + mul(Rw, r); fv = mul(Rw, vo + cross(w, r));
+                }
+                const V3 l = mul_t(Rw, force(k, fp, fv));
                 p_l = p_l - l;
                 p_n = p_n - cross(v3(m.foot_offset[k]), l);
             }
@@ -223,7 +245,7 @@ __global__ __launch_bounds__(W) void fd_kernel(const Model* __restrict__ mp, con
             }
             at(i, FD_Q + 2) = t;
         }
-        sound = fd_accel_body<W>(m, fb) && sound;
+        sound = fd_accel_body<W, FD_SLOTS>(m, GivenForces{fb}) && sound;
         if (p.n_sub > 0)
 #pragma clang loop unroll(disable) vectorize(disable)
             for (int i = 0; i < n; ++i) {

@@ -8,6 +8,7 @@ of 1-DoF joints whose first six are the virtual base joints of the reference's s
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
@@ -16,6 +17,24 @@ import torch
 from . import _lib
 from ._lib import ptr, stream
 from .trajectory_io import KD, KP
+
+
+@dataclass(frozen=True)
+class GroundContact:
+    """The declared ground-contact law of include/nmpc_torque.h: the plane z = ground_z, Hunt-Crossley normal force
+    f_z = stiffness delta max(0, 1 - damping pd_z), regularised Coulomb friction of coefficient mu that is linear below
+    slip_velocity, and the torque limit of the step (None: no limit).  The defaults let the 15 kg quadruped stand at
+    dt = 0.5 ms; the explicit step needs mu f_z dt / (slip_velocity m_foot) < 2 and stiffness delta damping dt / m_foot < 2."""
+    ground_z: float = 0.0
+    stiffness: float = 1e4
+    damping: float = 3.0
+    mu: float = 0.8
+    slip_velocity: float = 0.05
+    tau_max: Optional[float] = None
+
+    def cfg(self) -> _lib.NmpcContactCfg:
+        return _lib.NmpcContactCfg(float(self.ground_z), float(self.stiffness), float(self.damping), float(self.mu),
+                                   float(self.slip_velocity), 0.0 if self.tau_max is None else float(self.tau_max))
 
 
 class BatchedTorqueLayer:
@@ -95,6 +114,53 @@ class BatchedTorqueLayer:
                                                float(kd), ptr(f), ptr(q_out), ptr(v_out), ptr(a_out), stream(self.device)),
                    self._h, "nmpc_fd_step_batch", "torque")
         return q_out, v_out, a_out
+
+    def foot_kinematics(self, q, v=None):
+        """nmpc_foot_kinematics_batch: q, v [B, n] (v None = at rest) -> world position and velocity of every foot point,
+        (pos, vel), each [B, n_feet, 3]."""
+        q = self._in(q, (self.n,), "q")
+        v = None if v is None else self._in(v, (self.n,), "v")
+        B = q.shape[0]
+        if v is not None and v.shape[0] != B:
+            raise ValueError("batch sizes differ")
+        pos, vel = (torch.empty(B, self.n_feet, 3, dtype=torch.float32, device=self.device) for _ in range(2))
+        _lib.check(self.lib.nmpc_foot_kinematics_batch(self._h, B, ptr(q), ptr(v), ptr(pos), ptr(vel), stream(self.device)),
+                   self._h, "nmpc_foot_kinematics_batch", "torque")
+        return pos, vel
+
+    def contact_forces(self, q, v, ground: GroundContact) -> torch.Tensor:
+        """nmpc_contact_forces_batch: the ground-contact law on the foot kinematics of q, v [B, n] (v None = at rest) ->
+        f [B, n_feet, 3], the world-frame forces `forward_dynamics` would have to be handed."""
+        q = self._in(q, (self.n,), "q")
+        v = None if v is None else self._in(v, (self.n,), "v")
+        B = q.shape[0]
+        if v is not None and v.shape[0] != B:
+            raise ValueError("batch sizes differ")
+        f = torch.empty(B, self.n_feet, 3, dtype=torch.float32, device=self.device)
+        cfg = ground.cfg()
+        _lib.check(self.lib.nmpc_contact_forces_batch(self._h, B, ctypes.byref(cfg), ptr(q), ptr(v), ptr(f), stream(self.device)),
+                   self._h, "nmpc_contact_forces_batch", "torque")
+        return f
+
+    def contact_step(self, q, v, dt: float, n_sub: int = 1, tau_ff=None, q_des=None, kp: float = KP, kd: float = KD,
+                     ground: GroundContact = GroundContact()):
+        """nmpc_contact_step_batch: `step` on the ground -- the contact forces of `ground` re-evaluated from (q, v) in every
+        substep, the PD torque clamped to ground.tau_max -> (q, v, a, f, tau): the new state [B, n], and the acceleration
+        [B, n], foot forces [B, n_feet, 3] and clamped torques [B, nu] of the last substep."""
+        q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
+        tau_ff = None if tau_ff is None else self._in(tau_ff, (self.nu,), "tau_ff")
+        q_des = None if q_des is None else self._in(q_des, (self.nu,), "q_des")
+        B = q.shape[0]
+        if any(x is not None and x.shape[0] != B for x in (v, tau_ff, q_des)):
+            raise ValueError("batch sizes differ")
+        q_out, v_out, a_out = (torch.empty(B, self.n, dtype=torch.float32, device=self.device) for _ in range(3))
+        f_out = torch.empty(B, self.n_feet, 3, dtype=torch.float32, device=self.device)
+        tau_out = torch.empty(B, self.nu, dtype=torch.float32, device=self.device)
+        cfg = ground.cfg()
+        _lib.check(self.lib.nmpc_contact_step_batch(self._h, B, int(n_sub), float(dt), ctypes.byref(cfg), ptr(q), ptr(v), ptr(tau_ff),
+                                                    ptr(q_des), float(kp), float(kd), ptr(q_out), ptr(v_out), ptr(a_out), ptr(f_out),
+                                                    ptr(tau_out), stream(self.device)), self._h, "nmpc_contact_step_batch", "torque")
+        return q_out, v_out, a_out, f_out, tau_out
 
     def compute_pd_torques(self, q, v, torques_ff, q_plan, v_plan, Kp: float, Kd: float) -> torch.Tensor:
         """mpc.py:592-599: torques_ff + Kp (q_plan[-nu:] - q[-nu:]) + Kd (v_plan[-nu:] - v[-nu:])."""
