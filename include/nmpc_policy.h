@@ -38,6 +38,9 @@ const char *nmpc_policy_last_error(void *handle);
 /* length of theta */
 size_t nmpc_policy_param_count(void *handle);
 
+/* the dims the handle was created with and the device it lives on (either pointer may be NULL) */
+int nmpc_policy_get_dims(void *handle, nmpc_policy_dims *dims, int *device_id);
+
 /* Copy parameters and BatchNorm buffers in / out (device pointers; running_* may be NULL without
  * batch_norm).  set_params also resets the optimiser state (Adam moments, step count). */
 int nmpc_policy_set_params(void *handle, const float *theta, const float *running_mean,

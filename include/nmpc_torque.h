@@ -15,7 +15,8 @@
  * virtual joints in front of the legs.  The reference builds its model from a URDF through pinocchio
  * (both absent here); this boundary takes the same information as arrays.
  * All batch tensors are fp32 device pointers, row-major [batch][...]; calls are stream-ordered, never
- * allocate and never synchronise.  Return values: NMPC_OK / NMPC_E_* of nmpc.h. */
+ * allocate and never synchronise (the one exception is stated at nmpc_policy_rollout_batch).  Return values: NMPC_OK /
+ * NMPC_E_* of nmpc.h. */
 #ifndef NMPC_TORQUE_H
 #define NMPC_TORQUE_H
 
@@ -100,6 +101,60 @@ int nmpc_contact_forces_batch(void *handle, int B, const nmpc_contact_cfg *cfg, 
 int nmpc_contact_step_batch(void *handle, int B, int n_sub, float dt, const nmpc_contact_cfg *cfg, const float *q, const float *v,
                             const float *tau_ff, const float *q_des, float kp, float kd,
                             float *q_out, float *v_out, float *a_out, float *f_out, float *tau_out, void *stream);
+
+/* A policy in the loop on the contact plant [decl] (the reference: DAgger/utils/RolloutPolicy.py, PolicyController: MLP -> PD
+ * target -> torque, in MuJoCo).
+ *
+ * The observation of a plant state: q, v [B][18] in the solver's Euler layout [x y z yaw pitch roll joints].  Every output may
+ * be NULL.
+ *   S       robot b's 44-slot state row (RolloutMPC.py:221) at S + b * s_stride (s_stride >= 44 floats):
+ *           [phase, v_lin(3), body rates(3), joint rates(12), z, quaternion wxyz with w >= 0 (4), joints(12), base_wrt_feet(8)];
+ *           phase = round(fmod(t, period) / period, 4) of the host doubles t, period; body rates and quaternion in fp64 from
+ *           the fp32 state; base_wrt_feet[2f..2f+1] = q[0..1] - p_foot_f,xy with the foot points of the tree's own kinematics,
+ *           the ones the contact law pushes.
+ *   X       [B][44 + n_goal], the policy input: what nmpc_assemble_batch (nmpc_dataset.h) makes of that row and goal[b]
+ *           ([B][n_goal], raw), bit for bit -- columns [s_first, 44) are (float)(((double)s - s_mean) / s_std), the others raw;
+ *           s_mean, s_std: dev double [44], both NULL = raw.
+ *   failed  dev int [B], sticky: failed[b] |= the NMPC_ROLLOUT_FLAG_* bits of nmpc.h the state raises -- roll, pitch, height,
+ *           collision (z < collision_height), joint limits, and the solver bit for a height that is not finite; the velocity-
+ *           tracking bit is never raised (there is no command).  If a bit of term_mask is set and failed[b] carries no stamp yet,
+ *           (step_index + 1) << NMPC_ROLLOUT_TERM_SHIFT is added.
+ * One launch; with S and X NULL the kinematics are not run.  NMPC_E_ARG (text in nmpc_torque_last_error): a tree that is not
+ * 18 joints / 12 actuated / 4 feet, a NULL q or v, period <= 0, n_goal < 0, X without goal (n_goal > 0), only one of s_mean /
+ * s_std, s_first outside [0, 44], S with s_stride < 44. */
+int nmpc_observe_batch(void *handle, int B, const float *q, const float *v, double t, double period, const float *goal, int n_goal,
+                       const double *s_mean, const double *s_std, int s_first, float collision_height, float *S, int s_stride,
+                       float *X, int *failed, int step_index, int term_mask, void *stream);
+
+/* n_steps control steps of observe -> policy -> contact step in one call, nothing passing through the host.  For control step
+ * k = 0 .. n_steps - 1:
+ *   1. nmpc_observe_batch at t = t0 + (double)(k n_sub) (double)dt: row k of S, X, flags with step index k;
+ *   2. nmpc_policy_forward(policy, B, X, A_k), A_k a dense [B][12] buffer of the torque handle (the policy writes dense rows,
+ *      and row k of A is strided), copied into row k of A when A is given; the handle allocates the buffer the first time a
+ *      batch larger than any before needs it -- the one allocation of this header, and none in any later call.  That call
+ *      frees and allocates, which synchronises the device and cannot be captured into a graph; every other call synchronises
+ *      nothing.  The buffer belongs to the handle: one rollout per torque handle at a time, whatever the streams;
+ *   3. nmpc_contact_step_batch with q_des = A_k (actions are PD targets in joint order, as the labels are), n_sub substeps in
+ *      place on q, v;
+ * then one more observation with S and X NULL and step index n_steps, so that a robot that falls in the last interval is seen.
+ * S, A, q, v and failed are bit for bit those of that chain of the three public calls.
+ * No freeze: robots are independent, a NaN row stays in its row, a terminated robot keeps being stepped and its later rows
+ * are written as the plant produces them; the stamp in failed[b] (1 + the control step whose observation terminated it) tells
+ * the consumer where to cut.  Stream-ordered; no synchronisation but for the growth of the action buffer above.
+ * NMPC_E_ARG (text in nmpc_torque_last_error): a NULL torque, policy, cfg, ground, q, v, goal or X; n_steps < 1, n_sub < 1,
+ * dt <= 0, period <= 0; kp not finite; only one of s_mean / s_std; s_first outside [0, 44]; n_goal < 0; a policy whose
+ * n_in != 44 + n_goal or n_out != 12; B > its batch_max; a policy on another device; a tree that is not 18 / 12 / 4; a ground
+ * cfg nmpc_contact_step_batch refuses.  A failing nmpc_policy_forward returns its code, its text copied over. */
+typedef struct { int n_steps, n_sub; float dt, kp, kd; double t0, period; float collision_height; int term_mask, n_goal, s_first; } nmpc_policy_rollout_cfg;
+int nmpc_policy_rollout_batch(void *torque, void *policy, int B, const nmpc_policy_rollout_cfg *cfg, const nmpc_contact_cfg *ground,
+                              float *q, float *v,                 /* [B][18] in: start state, out: final state */
+                              const float *tau_ff,                /* [B][12] constant feed-forward or NULL */
+                              const float *goal,                  /* [B][n_goal] */
+                              const double *s_mean, const double *s_std,   /* dev [44] or both NULL */
+                              float *S, float *A,                 /* [B][n_steps][44], [B][n_steps][12]; either may be NULL */
+                              float *X,                           /* workspace [B][44 + n_goal] */
+                              int *failed,                        /* dev [B], sticky, caller zeroes; NULL allowed */
+                              void *stream);
 
 /* _compute_pd_torques: tau_ff [B][nu] (NULL = 0); q, v, q_plan, v_plan [B][n_joints] (their last nu
  * entries are used); tau [B][nu] (may alias tau_ff). */

@@ -59,6 +59,7 @@ SIGNATURES = {
     "nmpc_policy_destroy": (None, [c_void_p]),
     "nmpc_policy_last_error": (ctypes.c_char_p, [c_void_p]),
     "nmpc_policy_param_count": (ctypes.c_size_t, [c_void_p]),
+    "nmpc_policy_get_dims": (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
     "nmpc_policy_set_params": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_policy_get_params": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_policy_forward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
@@ -88,6 +89,10 @@ SIGNATURES = {
     "nmpc_contact_forces_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_contact_step_batch": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_observe_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "nmpc_policy_rollout_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_pd_torques_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                       c_void_p, c_void_p]),
     "nmpc_pd_target_action_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
@@ -123,6 +128,12 @@ class NmpcTreeModel(ctypes.Structure):
 class NmpcContactCfg(ctypes.Structure):
     _fields_ = [("ground_z", c_float), ("stiffness", c_float), ("damping", c_float), ("mu", c_float),
                 ("slip_velocity", c_float), ("tau_max", c_float)]
+
+
+class NmpcPolicyRolloutCfg(ctypes.Structure):
+    _fields_ = [("n_steps", c_int), ("n_sub", c_int), ("dt", c_float), ("kp", c_float), ("kd", c_float),
+                ("t0", ctypes.c_double), ("period", ctypes.c_double), ("collision_height", c_float),
+                ("term_mask", c_int), ("n_goal", c_int), ("s_first", c_int)]
 
 
 class NmpcRolloutCfg(ctypes.Structure):

@@ -749,6 +749,14 @@ size_t nmpc_policy_param_count(void* handle) {
     return p ? p->n_theta : 0;
 }
 
+int nmpc_policy_get_dims(void* handle, nmpc_policy_dims* dims, int* device_id) {
+    Policy* p = static_cast<Policy*>(handle);
+    if (!p) return fail(no_handle, NMPC_E_ARG, "nmpc_policy_get_dims: null handle");
+    if (dims) *dims = p->d;
+    if (device_id) *device_id = p->device;
+    return NMPC_OK;
+}
+
 int nmpc_policy_set_params(void* handle, const float* theta, const float* running_mean, const float* running_var,
                            void* stream) {
     Policy* p = static_cast<Policy*>(handle);

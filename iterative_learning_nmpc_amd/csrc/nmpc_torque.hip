@@ -11,7 +11,8 @@
 // are conflict-free LDS reads.  ~5 kFLOP per robot: the layer is latency-, not throughput-relevant.
 // The other direction -- accelerations from torques and given contact forces, and a PD-driven integration step around them --
 // is nmpc_torque_fd.hip.inc, included below; the declared ground-contact law, the foot kinematics it needs and the plant step
-// that evaluates it inside that recursion are nmpc_torque_contact.hip.inc.
+// that evaluates it inside that recursion are nmpc_torque_contact.hip.inc; the observation of a plant state for a policy in the
+// loop is nmpc_torque_policy.hip.inc, and the loop itself (nmpc_policy_rollout_batch) is host code at the end of this file.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -23,7 +24,9 @@
 #include <vector>
 
 #include "../../include/nmpc.h"
+#include "../../include/nmpc_policy.h"
 #include "../../include/nmpc_torque.h"
+#include "nmpc_rollout_common.hpp"
 #include "nmpc_torque_plan.hpp"
 #include "nmpc_wb_plan.hpp"
 
@@ -337,6 +340,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 
 #include "nmpc_torque_fd.hip.inc"
 #include "nmpc_torque_contact.hip.inc"
+#include "nmpc_torque_policy.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -353,6 +357,8 @@ struct Torque {
     int device = 0;
     int fd_width = 32;                  // robots per block of fd_kernel: fd_block_width(n), or 16 if NMPC_FD_WIDTH=16 asks for it (tools/fd_cost.py)
     int ct_width = 32;                  // robots per block of contact_step_kernel: ct_block_width(n)
+    float* act = nullptr;               // [act_rows][nu]: the actions of nmpc_policy_rollout_batch when its caller keeps none
+    int act_rows = 0;
     std::string err;
 };
 
@@ -407,6 +413,21 @@ const char* contact_cfg_refusal(const nmpc_contact_cfg* c) {
 
 ContactCfg device_cfg(const nmpc_contact_cfg& c) {
     return {c.ground_z, c.stiffness, c.damping, c.mu, c.slip_velocity * c.slip_velocity, c.tau_max};
+}
+
+// why a state cannot be observed (nullptr: it can): the arguments nmpc_observe_batch and nmpc_policy_rollout_batch share
+const char* observe_refusal(const Torque* t, int B, const float* q, const float* v, double period, const float* goal, int n_goal,
+                            const double* s_mean, const double* s_std, int s_first, const float* S, int s_stride, const float* X) {
+    if (t->host.n != 18 || t->host.nu != 12 || t->host.nf != 4)
+        return "the observation needs the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4";
+    if (B < 0 || !q || !v) return "need B >= 0 and q, v";
+    if (!(period > 0.0)) return "period must be positive";
+    if (n_goal < 0) return "n_goal must not be negative";
+    if (X && n_goal > 0 && !goal) return "X needs goal";
+    if (!s_mean != !s_std) return "s_mean and s_std come together or not at all";
+    if (s_first < 0 || s_first > OB_STATE) return "s_first must be in [0, 44]";
+    if (S && s_stride < OB_STATE) return "s_stride must be at least 44";
+    return nullptr;
 }
 
 // the kinematics pass, with or without the law
@@ -479,6 +500,7 @@ void nmpc_torque_destroy(void* handle) {
     nmpc::DeviceGuard guard(t->device);      // nothing to return: a failed switch goes to the family's slot, the buffers are freed all the same
     if (guard.err != hipSuccess) fail(no_handle, NMPC_E_HIP, std::string("nmpc_torque_destroy: ") + hipGetErrorString(guard.err));
     if (t->dev) (void)hipFree(t->dev);
+    if (t->act) (void)hipFree(t->act);
     delete t;
 }
 
@@ -567,6 +589,81 @@ int nmpc_contact_step_batch(void* handle, int B, int n_sub, float dt, const nmpc
     if (w == 32) hipLaunchKernelGGL(contact_step_kernel<32>, grid, dim3(32), lds, static_cast<hipStream_t>(stream), t->dev, p);
     else hipLaunchKernelGGL(contact_step_kernel<16>, grid, dim3(16), lds, static_cast<hipStream_t>(stream), t->dev, p);
     return launched(t);
+}
+
+int nmpc_observe_batch(void* handle, int B, const float* q, const float* v, double t, double period, const float* goal, int n_goal,
+                       const double* s_mean, const double* s_std, int s_first, float collision_height, float* S, int s_stride, float* X,
+                       int* failed, int step_index, int term_mask, void* stream) {
+    Torque* h = static_cast<Torque*>(handle);
+    if (!h) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (const char* why = observe_refusal(h, B, q, v, period, goal, n_goal, s_mean, s_std, s_first, S, s_stride, X)) return fail(h, NMPC_E_ARG, why);
+    NMPC_ENTER(h, h->device);
+    ObserveArgs a{};
+    a.B = B; a.n_goal = n_goal; a.s_first = s_first; a.s_stride = s_stride; a.step_index = step_index; a.term_mask = term_mask;
+    a.t = t; a.period = period; a.collision_height = collision_height;
+    a.q = q; a.v = v; a.goal = goal; a.s_mean = s_mean; a.s_std = s_std; a.S = S; a.X = X; a.failed = failed;
+    const size_t lds = (S || X) ? ob_lds_bytes(h->host.n) : 0;      // the flags alone run no kinematics and ask for no slice
+    hipLaunchKernelGGL(observe_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream), h->dev, a);
+    return launched(h);
+}
+
+int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_policy_rollout_cfg* cfg, const nmpc_contact_cfg* ground,
+                              float* q, float* v, const float* tau_ff, const float* goal, const double* s_mean, const double* s_std,
+                              float* S, float* A, float* X, int* failed, void* stream) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (B == 0) return NMPC_OK;
+    if (!policy) return fail(t, NMPC_E_ARG, "policy is NULL");
+    if (!cfg) return fail(t, NMPC_E_ARG, "the rollout cfg is NULL");
+    if (B < 0 || !q || !v || !goal || !X) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, goal, X");
+    if (cfg->n_steps < 1) return fail(t, NMPC_E_ARG, "n_steps must be at least 1");
+    if (cfg->n_sub < 1) return fail(t, NMPC_E_ARG, "n_sub must be at least 1");
+    if (!(cfg->dt > 0.0f)) return fail(t, NMPC_E_ARG, "dt must be positive");
+    if (!std::isfinite(cfg->kp)) return fail(t, NMPC_E_ARG, "kp must be finite");
+    if (const char* why = observe_refusal(t, B, q, v, cfg->period, goal, cfg->n_goal, s_mean, s_std, cfg->s_first, nullptr, 0, X))
+        return fail(t, NMPC_E_ARG, why);
+    if (const char* why = contact_cfg_refusal(ground)) return fail(t, NMPC_E_ARG, std::string("ground: ") + why);
+    nmpc_policy_dims d{};
+    int policy_device = -1;
+    if (nmpc_policy_get_dims(policy, &d, &policy_device) != NMPC_OK) return fail(t, NMPC_E_ARG, "policy is not a policy handle");
+    if (d.n_in != OB_STATE + cfg->n_goal || d.n_out != t->host.nu)
+        return fail(t, NMPC_E_ARG, "the policy must map 44 + n_goal inputs to 12 actions");
+    if (B > d.batch_max) return fail(t, NMPC_E_ARG, "B exceeds the policy's batch_max");
+    if (policy_device != t->device) return fail(t, NMPC_E_ARG, "the policy lives on another device");
+    const int nu = t->host.nu, K = cfg->n_steps;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
+        NMPC_ENTER(t, t->device);
+        if (t->act) NMPC_TRY(t, hipFree(t->act));
+        t->act = nullptr; t->act_rows = 0;
+        NMPC_TRY(t, hipMalloc(reinterpret_cast<void**>(&t->act), (size_t)B * nu * sizeof(float)));
+        t->act_rows = B;
+    }
+    // the chain of the public calls; row k of S is written in place through its stride, row k of A is copied from the dense actions
+    for (int k = 0; k <= K; ++k) {
+        const double at = cfg->t0 + (double)(k * cfg->n_sub) * (double)cfg->dt;
+        const bool rows = k < K;
+        if (const int rc = nmpc_observe_batch(t, B, q, v, at, cfg->period, goal, cfg->n_goal, s_mean, s_std, cfg->s_first, cfg->collision_height,
+                                              rows && S ? S + (size_t)k * OB_STATE : nullptr, K * OB_STATE, rows ? X : nullptr, failed, k,
+                                              cfg->term_mask, stream))
+            return rc;
+        if (!rows) break;
+        if (const int rc = nmpc_policy_forward(policy, B, X, t->act, stream)) {
+            const char* why = nmpc_policy_last_error(policy);
+            return fail(t, rc, std::string("nmpc_policy_forward: ") + (why ? why : ""));
+        }
+        if (A) {
+            NMPC_ENTER(t, t->device);
+            const size_t n = (size_t)B * nu;
+            hipLaunchKernelGGL(action_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, nu, t->act, A + (size_t)k * nu, K * nu);
+            if (const int rc = launched(t)) return rc;
+        }
+        if (const int rc = nmpc_contact_step_batch(t, B, cfg->n_sub, cfg->dt, ground, q, v, tau_ff, t->act, cfg->kp, cfg->kd, q, v, nullptr, nullptr,
+                                                   nullptr, stream))
+            return rc;
+    }
+    return NMPC_OK;
 }
 
 int nmpc_pd_torques_batch(void* handle, int B, const float* tau_ff, const float* q, const float* v, const float* q_plan,

@@ -7,7 +7,8 @@
 The pieces are `collect.collect_rollouts` (rollouts -> `DeviceDatabase`, with the out-of-distribution weight of every
 row), `DevicePolicy.train_epoch` (an epoch of weighted batches in one library call) and `DevicePolicy.loss` (the
 validation loss).  No table, batch, index or loss passes through the host, and nothing here waits for the device: what
-comes back are device tensors.
+comes back are device tensors.  `evaluate_policy` closes the loop on the declared contact plant: the trained policy drives
+the robots, and what comes back is who stayed up and which states the learner visited.
 
 Declared choices:
   * Sampling is WITH replacement, as the reference's WeightedRandomSampler loader draws
@@ -24,8 +25,10 @@ from typing import Optional
 
 import torch
 
+from ._lib import NMPC_ROLLOUT_TERM_SHIFT
 from .collect import collect_rollouts
 from .config import TERMINATE_DEFAULT
+from .torque import NOMINAL_PERIOD, GroundContact
 from .trajectory_io import KD, KP
 
 
@@ -77,3 +80,28 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
     val_idx = torch.arange(n - n_val, n, dtype=torch.int32, device=db.device) if n_val else None
     train_loss, val_loss = train_network(policy, db, n_epoch, batch_size, lr=lr, seed=seed, val_idx=val_idx)
     return err, weights, n_rows, train_loss, val_loss
+
+
+def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, tau_ff=None, kp: float = KP,
+                    kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
+                    terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08):
+    """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
+    from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
+    (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
+    declared plant).  Returns a dict of device tensors, nothing here waits for the device:
+        failed          int32 [B]: the flag bits every robot raised, above them the stamp of its termination
+        survived        bool [B]: no stamp, failed >> 8 == 0
+        steps_survived  int32 [B]: control steps before the observation that terminated the robot (all of them if none did)
+        S, A            [B, n_steps, 44], [B, n_steps, 12]: the states visited and the actions taken -- the rows of a
+                        terminated robot from its stamp on are those of a fallen robot; cut there
+        q, v            [B, 18]: the state after the last control step."""
+    n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
+    if n_steps < 1:
+        raise ValueError(f"T = {T} s is shorter than one control step of {n_sub} x {dt} s")
+    q, v, S, A, failed = layer.policy_rollout(policy, q0, v0, n_steps, dt, n_sub, goal, tau_ff=tau_ff, kp=kp, kd=kd,
+                                              ground=GroundContact() if ground is None else ground, t0=t0,
+                                              period=NOMINAL_PERIOD if period is None else period, db=db,
+                                              terminate_mask=terminate_mask, collision_height=collision_height)
+    stamp = failed >> NMPC_ROLLOUT_TERM_SHIFT
+    return dict(failed=failed, survived=stamp == 0, steps_survived=torch.where(stamp == 0, torch.full_like(stamp, n_steps), stamp - 1),
+                S=S, A=A, q=q, v=v)

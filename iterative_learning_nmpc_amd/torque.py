@@ -16,7 +16,10 @@ import torch
 
 from . import _lib
 from ._lib import ptr, stream
-from .trajectory_io import KD, KP
+from .config import TERMINATE_DEFAULT, GaitConfigFactory
+from .trajectory_io import KD, KP, N_STATE
+
+NOMINAL_PERIOD = GaitConfigFactory.get("trot").nominal_period      # the recorded phase of a row runs over the gait's nominal period
 
 
 @dataclass(frozen=True)
@@ -161,6 +164,97 @@ class BatchedTorqueLayer:
                                                     ptr(q_des), float(kp), float(kd), ptr(q_out), ptr(v_out), ptr(a_out), ptr(f_out),
                                                     ptr(tau_out), stream(self.device)), self._h, "nmpc_contact_step_batch", "torque")
         return q_out, v_out, a_out, f_out, tau_out
+
+    def _stats(self, s_mean, s_std):
+        """the column statistics of the state rows as float64 device vectors [44], or (None, None)"""
+        if (s_mean is None) != (s_std is None):
+            raise ValueError("s_mean and s_std come together or not at all")
+        if s_mean is None:
+            return None, None
+        out = [torch.as_tensor(x, dtype=torch.float64, device=self.device).contiguous() for x in (s_mean, s_std)]
+        if any(tuple(x.shape) != (N_STATE,) for x in out):
+            raise ValueError(f"s_mean, s_std: expected [{N_STATE}]")
+        return out
+
+    def _goal(self, goal, B):
+        goal = torch.as_tensor(goal, dtype=torch.float32, device=self.device).contiguous()
+        if goal.dim() != 2 or goal.shape[0] != B:
+            raise ValueError(f"goal: expected [{B}, n_goal], got {tuple(goal.shape)}")
+        return goal
+
+    def _failed(self, failed, B):
+        if failed is not None and (failed.dtype != torch.int32 or tuple(failed.shape) != (B,) or not failed.is_contiguous()
+                                   or failed.device != self.device):
+            raise ValueError(f"failed: need contiguous int32 ({B},) on {self.device}")
+        return failed
+
+    def observe(self, q, v, t: float, period: float, goal, s_mean=None, s_std=None, s_first: int = 1,
+                collision_height: float = 0.08, failed: Optional[torch.Tensor] = None, step_index: int = 0, term_mask: int = 0):
+        """nmpc_observe_batch: the plant state q, v [B, 18] (Euler layout) at time t as the reference's 44-slot state row
+        (phase over `period`, base_wrt_feet from the tree's own feet) and the policy input [row, goal] with columns
+        [s_first, 44) normalised by s_mean, s_std (float64 [44]; None: raw), as `DeviceDatabase.batch` assembles it.  failed:
+        int32 [B] on the device, updated in place with the flags the state raises and, where a bit of term_mask is set and
+        no stamp is present, the stamp step_index + 1 (None: nothing is written).  -> (S_row [B, 44], X [B, 44 + n_goal])."""
+        q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
+        B = q.shape[0]
+        if v.shape[0] != B:
+            raise ValueError("batch sizes differ")
+        goal = self._goal(goal, B)
+        s_mean, s_std = self._stats(s_mean, s_std)
+        failed = self._failed(failed, B)
+        S = torch.empty(B, N_STATE, dtype=torch.float32, device=self.device)
+        X = torch.empty(B, N_STATE + goal.shape[1], dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nmpc_observe_batch(self._h, B, ptr(q), ptr(v), float(t), float(period), ptr(goal), goal.shape[1], ptr(s_mean),
+                                               ptr(s_std), int(s_first), float(collision_height), ptr(S), N_STATE, ptr(X), ptr(failed),
+                                               int(step_index), int(term_mask), stream(self.device)),
+                   self._h, "nmpc_observe_batch", "torque")
+        return S, X
+
+    def policy_rollout(self, policy, q, v, n_steps: int, dt: float, n_sub: int, goal, tau_ff=None, kp: float = KP, kd: float = KD,
+                       ground: GroundContact = GroundContact(), t0: float = 0.0, period: float = NOMINAL_PERIOD, db=None,
+                       s_mean=None, s_std=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
+                       record: bool = True):
+        """nmpc_policy_rollout_batch: n_steps control steps of `observe` -> `policy.forward` -> `contact_step` (n_sub substeps
+        of dt, q_des = the action) in one library call, and a last flags-only observation; bit for bit that chain of calls
+        with observation k at t0 + (k n_sub) float32(dt) and step index k.  policy: a `DevicePolicy` of 44 + n_goal inputs
+        and 12 outputs with batch_max >= B; goal [B, n_goal]; tau_ff [B, 12] a constant feed-forward torque.  The policy
+        input is normalised with the statistics of db (a `DeviceDatabase` whose norm_input is set: its states_mean /
+        states_std from column 1 on, what its `batch_source()` hands the trainer for velocity goals; the goal is always fed
+        raw, so a database that normalises its goals -- goal_type 'cc' with norm_input -- and an empty one are refused) or
+        with s_mean, s_std given directly (from column 1 on).  One rollout per layer at a time: the dense actions of a step
+        live in a buffer of the layer's handle, which grows (and then synchronises the device) for a larger batch.  Nothing is frozen: a robot whose flags hit terminate_mask is stamped in failed
+        (failed >> 8 = 1 + the control step whose observation saw it) and keeps being stepped.
+        -> (q, v, S [B, n_steps, 44], A [B, n_steps, 12], failed int32 [B]); S and A are None with record=False."""
+        q = self._in(q, (self.n,), "q").clone(); v = self._in(v, (self.n,), "v").clone()
+        B = q.shape[0]
+        tau_ff = None if tau_ff is None else self._in(tau_ff, (self.nu,), "tau_ff")
+        if v.shape[0] != B or (tau_ff is not None and tau_ff.shape[0] != B):
+            raise ValueError("batch sizes differ")
+        goal = self._goal(goal, B)
+        if db is not None:
+            if s_mean is not None or s_std is not None:
+                raise ValueError("give db or s_mean / s_std, not both")
+            if db.norm_input:
+                if db.goal_type != "vc":
+                    raise ValueError("a database that normalises its goals (goal_type 'cc' with norm_input) is not supported: the goal is fed raw")
+                if db.states_mean is None:
+                    raise ValueError("the database is empty: it has no statistics to normalise with")
+                s_mean, s_std = db.states_mean, db.states_std
+        s_mean, s_std = self._stats(s_mean, s_std)
+        n_steps, n_goal = int(n_steps), goal.shape[1]
+        rows = max(n_steps, 0)
+        S = torch.empty(B, rows, N_STATE, dtype=torch.float32, device=self.device) if record else None
+        A = torch.empty(B, rows, self.nu, dtype=torch.float32, device=self.device) if record else None
+        X = torch.empty(B, N_STATE + n_goal, dtype=torch.float32, device=self.device)
+        failed = torch.zeros(B, dtype=torch.int32, device=self.device)
+        cfg = _lib.NmpcPolicyRolloutCfg(n_steps, int(n_sub), float(dt), float(kp), float(kd), float(t0), float(period),
+                                        float(collision_height), int(terminate_mask), n_goal, 1)
+        g = ground.cfg()
+        _lib.check(self.lib.nmpc_policy_rollout_batch(self._h, getattr(policy, "_h", None), B, ctypes.byref(cfg), ctypes.byref(g), ptr(q),
+                                                      ptr(v), ptr(tau_ff), ptr(goal), ptr(s_mean), ptr(s_std), ptr(S), ptr(A), ptr(X),
+                                                      ptr(failed), stream(self.device)),
+                   self._h, "nmpc_policy_rollout_batch", "torque")
+        return q, v, S, A, failed
 
     def compute_pd_torques(self, q, v, torques_ff, q_plan, v_plan, Kp: float, Kd: float) -> torch.Tensor:
         """mpc.py:592-599: torques_ff + Kp (q_plan[-nu:] - q[-nu:]) + Kd (v_plan[-nu:] - v[-nu:])."""

@@ -1,0 +1,414 @@
+"""GPU checks of the policy-driven rollout on the contact plant (nmpc_observe_batch, nmpc_policy_rollout_batch,
+learning.evaluate_policy) against tests/policy_rollout_reference.py (itself checked in tests/test_policy_rollout_reference.py).
+
+The accuracy bar is the one of tests/test_gpu_contact.py: a device result is compared with the fp64 reference under
+    max(1e-5 * scale, 4 x the deviation of the numpy-float32 run of the same reference loop from the fp64 run),
+both computed here, never from the code under test; scale is the largest |reference| of the compared array.  Bit-for-bit
+claims are array equality.  Every figure is printed before it is asserted."""
+import copy
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+from oracle.policy_oracle import PolicyOracle
+from tests import contact_reference as cr
+from tests import fd_reference as fr
+from tests import policy_rollout_reference as pr
+from tests.test_gpu_contact import Case, branches, ground, held, host, layer
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+KP, KD, DT = 20.0, 1.5, 5e-4
+DT32 = float(np.float32(DT))
+PERIOD, T0, HEIGHT = 0.5, 0.37, 0.08
+N_GOAL, HIDDEN, LAYERS = 3, 64, 2
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contact_settle.npz")
+
+
+def device_policy(oracle, batch_max):
+    from iterative_learning_nmpc_amd.policy import DevicePolicy
+    n_in, n_out, L, hidden, bn = oracle.dims
+    p = DevicePolicy(n_in, n_out, L, hidden, bn, batch_max=batch_max, seed=None)
+    p.set_parameters(oracle.theta.astype(np.float32), oracle.running_mean.astype(np.float32), oracle.running_var.astype(np.float32))
+    return p
+
+
+def as32(oracle):
+    o = PolicyOracle(*oracle.dims, dtype=np.float32)
+    o.theta, o.running_mean, o.running_var = (x.astype(np.float32) for x in (oracle.theta, oracle.running_mean, oracle.running_var))
+    return o
+
+
+def standing_oracle():
+    """all weights zero, last bias = STAND"""
+    o = PolicyOracle(44 + N_GOAL, 12, LAYERS, HIDDEN, True)
+    o.view()[f"b{LAYERS}"][:] = fr.STAND.astype(np.float32)
+    return o
+
+
+class World:
+    """The tilted quadruped with 257 states whose lowest foot is at -3 mm / 0 / +2 cm in turn (the Case of
+    tests/test_gpu_contact.py), goals, feed-forward torques, column statistics, and a small random policy (47 -> 2 x 64 with
+    BatchNorm and random running statistics -> 12) whose last bias is STAND and whose last weights are scaled so that its
+    actions on the first observation stay within 0.1 rad of STAND; all parameters are float32 values.  Computed once."""
+    B = 257
+
+    def __init__(self):
+        self.c = c = Case(fr.quadruped(perturb=0.3), self.B, seed=258)
+        self.m, self.L, self.g = c.m, c.L, c.g
+        rng = np.random.default_rng(11)
+        self.goal = rng.uniform(-0.5, 0.5, (self.B, N_GOAL)).astype(np.float32)
+        self.tau = (0.1 * c.tau).astype(np.float32)
+        self.s_mean, self.s_std = rng.uniform(-0.5, 0.5, 44), rng.uniform(0.5, 2.0, 44)
+        o = PolicyOracle(44 + N_GOAL, 12, LAYERS, HIDDEN, True)
+        o.theta = rng.standard_normal(o.n_theta).astype(np.float32).astype(np.float64) * 0.2
+        o.theta = o.theta.astype(np.float32).astype(np.float64)
+        o.running_mean = rng.uniform(-0.5, 0.5, o.running_mean.shape).astype(np.float32).astype(np.float64)
+        o.running_var = rng.uniform(0.5, 2.0, o.running_var.shape).astype(np.float32).astype(np.float64)
+        p = o.view()
+        p[f"b{LAYERS}"][:] = fr.STAND.astype(np.float32)
+        x0 = np.stack([pr.normalise(pr.row(self.m, c.q[b], c.v[b], pr.phase(T0, PERIOD)), self.goal[b], self.s_mean, self.s_std) for b in range(self.B)])
+        away = np.abs(o.forward(x0, train=False) - fr.STAND).max()
+        p[f"W{LAYERS}"][:] = (p[f"W{LAYERS}"] * (0.05 / away)).astype(np.float32)
+        assert np.abs(o.forward(x0, train=False) - fr.STAND).max() < 0.06
+        self.oracle, self.oracle32 = o, as32(o)
+        self.policy = device_policy(o, self.B)
+        self.standing = device_policy(standing_oracle(), 64)
+
+    def dev(self, x, dtype=torch.float32):
+        return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype, device=self.L.device)
+
+    def chain(self, B, K, n_sub, mask, stats=True, tau=True, rows=slice(None)):
+        """the Python loop of the three public calls -> (q, v, S, A, failed)"""
+        L, c = self.L, self.c
+        r = rows if rows != slice(None) else slice(0, B)
+        q, v, goal = self.dev(c.q[r]), self.dev(c.v[r]), self.dev(self.goal[r])
+        tau_ff = self.dev(self.tau[r]) if tau else None
+        kw = dict(s_mean=self.s_mean, s_std=self.s_std) if stats else {}
+        failed = torch.zeros(q.shape[0], dtype=torch.int32, device=L.device)
+        S, A = [], []
+        for k in range(K):
+            s, x = L.observe(q, v, T0 + (k * n_sub) * DT32, PERIOD, goal, collision_height=HEIGHT, failed=failed, step_index=k, term_mask=mask, **kw)
+            a = self.policy.forward(x)
+            q, v = L.contact_step(q, v, DT, n_sub, tau_ff=tau_ff, q_des=a, kp=KP, kd=KD, ground=ground(self.g))[:2]
+            S.append(s); A.append(a)
+        L.observe(q, v, T0 + (K * n_sub) * DT32, PERIOD, goal, collision_height=HEIGHT, failed=failed, step_index=K, term_mask=mask, **kw)
+        return q, v, torch.stack(S, 1), torch.stack(A, 1), failed
+
+    def rollout(self, B, K, n_sub, mask, stats=True, tau=True, rows=slice(None), **kw):
+        c = self.c
+        r = rows if rows != slice(None) else slice(0, B)
+        st = dict(s_mean=self.s_mean, s_std=self.s_std) if stats else {}
+        return self.L.policy_rollout(self.policy, c.q[r], c.v[r], K, DT, n_sub, self.goal[r], tau_ff=self.tau[r] if tau else None, kp=KP, kd=KD,
+                                     ground=ground(self.g), t0=T0, period=PERIOD, terminate_mask=mask, collision_height=HEIGHT, **st, **kw)
+
+
+@pytest.fixture(scope="module")
+def world():
+    return World()
+
+
+@pytest.fixture(scope="module")
+def rows(world):
+    """fp64 and float32 reference rows of all 257 states at t = T0"""
+    w, ph = world, pr.phase(T0, PERIOD)
+    ref = np.stack([pr.row(w.m, w.c.q[b], w.c.v[b], ph) for b in range(w.B)])
+    f32 = np.stack([pr.row(w.m, w.c.q[b], w.c.v[b], ph, np.float32) for b in range(w.B)])
+    ref.setflags(write=False); f32.setflags(write=False)
+    return ref, f32
+
+
+def assemble(w, S, goal, stats, s_first):
+    """nmpc_assemble_batch of a one-row-per-robot table"""
+    from iterative_learning_nmpc_amd import _lib
+    B = S.shape[0]
+    idx = torch.arange(B, dtype=torch.int32, device=S.device)
+    act, y = torch.zeros(B, 12, device=S.device), torch.empty(B, 12, device=S.device)
+    x = torch.empty(B, 44 + goal.shape[1], device=S.device)
+    mean, std = (w.dev(w.s_mean, torch.float64), w.dev(w.s_std, torch.float64)) if stats else (None, None)
+    ptr = _lib.ptr
+    _lib.check(w.L.lib.nmpc_assemble_batch(ptr(S), 44, ptr(mean), ptr(std), s_first, ptr(goal), goal.shape[1], None, None, ptr(act), 12, B,
+                                           ptr(idx), B, ptr(x), ptr(y), _lib.stream(S.device)), None, "nmpc_assemble_batch", "dataset")
+    return x
+
+
+# ---- 1. the observation ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B", [1, 33, 257])
+def test_observation_matches_the_reference(world, rows, B):
+    w, (ref, f32) = world, rows
+    q, v, goal = w.c.q[:B], w.c.v[:B], w.dev(w.goal[:B])
+    S, X = w.L.observe(q, v, T0, PERIOD, goal, s_mean=w.s_mean, s_std=w.s_std)
+    assert S.shape == (B, 44) and X.shape == (B, 47)
+    s = S.cpu().numpy()
+    print(f"observation, B {B}")
+    ok = [held(name, s[:, pr.GROUPS[name]], ref[:B, pr.GROUPS[name]], f32[:B, pr.GROUPS[name]]) for name in ("rates", "quaternion", "joints", "base_wrt_feet")]
+    assert all(ok)
+    # what is copied is copied, and the phase is exact -- beyond one period too
+    assert np.array_equal(s[:, 1:4], v[:, :3]) and np.array_equal(s[:, 7:19], v[:, 6:]) and np.array_equal(s[:, 19], q[:, 2]) and np.array_equal(s[:, 24:36], q[:, 6:])
+    for t in (0.0, T0, 0.8125, 1.23456, 7.0 + 1e-5):
+        got = w.L.observe(q, v, t, PERIOD, goal)[0][:, 0].cpu().numpy()
+        assert np.array_equal(got, np.full(B, np.float32(pr.phase(t, PERIOD)))), t
+    assert np.float32(pr.phase(0.8125, PERIOD)) == np.float32(0.625)
+    # the policy input is the database's batch assembly of the device's own row
+    for stats, s_first in ((True, 1), (True, 0), (False, 1)):
+        kw = dict(s_mean=w.s_mean, s_std=w.s_std) if stats else {}
+        S2, X2 = w.L.observe(q, v, T0, PERIOD, goal, s_first=s_first, **kw)
+        assert torch.equal(S2, S) and torch.equal(X2, assemble(w, S, goal, stats, s_first)), (stats, s_first)
+        if not stats:
+            assert torch.equal(X2[:, :44], S) and torch.equal(X2[:, 44:], goal)
+    # at rest the rate slots are zeros
+    rest = w.L.observe(q, np.zeros_like(v), T0, PERIOD, goal)[0].cpu().numpy()
+    assert not np.any(rest[:, 1:19]) and np.array_equal(rest[:, 19:], s[:, 19:])
+
+
+# ---- 2. the flags ---------------------------------------------------------------------------------------------------------------
+def test_flags_and_stamps(world):
+    from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT
+    w, L = world, world.L
+    up = np.zeros(18, np.float32); up[2] = 0.3; up[6:] = fr.STAND
+    crafted = [(), ((5, 0.5),), ((4, -0.5),), ((2, 0.5),), ((2, 0.15),), ((2, 0.05),), ((8, -0.9),), ((2, np.nan),)]
+    q = np.tile(up, (len(crafted), 1))
+    for b, changes in enumerate(crafted):
+        for i, x in changes:
+            q[b, i] = x
+    B = len(q)
+    v = np.random.default_rng(2).uniform(-2, 2, (B, 18)).astype(np.float32); v[:, 0] = 5.0     # far from any command
+    goal = w.dev(w.goal[:B])
+    with np.errstate(invalid="ignore"):
+        want = np.array([pr.flags_ref(pr.row(w.m, q[b], v[b], 0.0, np.float32), q[b, 6:], HEIGHT) for b in range(B)])
+    assert list(want) == [0, pr.FLAG_ROLL, pr.FLAG_PITCH, pr.FLAG_HEIGHT, pr.FLAG_HEIGHT, pr.FLAG_HEIGHT | pr.FLAG_COLLISION, pr.FLAG_JOINT_LIMIT, pr.FLAG_SOLVER]
+    failed = torch.zeros(B, dtype=torch.int32, device=L.device)
+    S, X = L.observe(q, v, T0, PERIOD, goal, s_mean=w.s_mean, s_std=w.s_std, collision_height=HEIGHT, failed=failed, step_index=4, term_mask=TERMINATE_DEFAULT)
+    got = failed.cpu().numpy()
+    print("flags", got & 0xFF, "stamps", got >> 8)
+    assert np.array_equal(got & 0xFF, want) and not np.any(got & pr.FLAG_VEL_TRACKING)
+    hit = (want & TERMINATE_DEFAULT) != 0
+    assert hit.sum() == 2 and np.array_equal(got >> 8, np.where(hit, 5, 0))
+    # sticky: bits stay, an existing stamp is kept, a new one comes only where there was none
+    before = torch.tensor([pr.FLAG_PITCH, 0, 0, 0, 0, (2 << 8) | pr.FLAG_COLLISION, 0, 0], dtype=torch.int32, device=L.device)
+    again = before.clone()
+    L.observe(q, v, T0, PERIOD, goal, collision_height=HEIGHT, failed=again, step_index=9, term_mask=TERMINATE_DEFAULT)
+    again = again.cpu().numpy()
+    assert np.array_equal(again & 0xFF, want | (before.cpu().numpy() & 0xFF)) and list(again >> 8) == [0, 0, 0, 0, 0, 2, 0, 10]
+    # no mask, no stamp; no tensor, nothing written and the same rows
+    free = torch.zeros(B, dtype=torch.int32, device=L.device)
+    L.observe(q, v, T0, PERIOD, goal, collision_height=HEIGHT, failed=free)
+    assert np.array_equal(free.cpu().numpy(), want)
+    S0, X0 = L.observe(q, v, T0, PERIOD, goal, s_mean=w.s_mean, s_std=w.s_std)
+    assert torch.equal(S0[:7], S[:7]) and torch.equal(X0[:7], X[:7])
+    # the flags-only launch (S and X NULL) raises the same flags
+    from iterative_learning_nmpc_amd import _lib
+    only = torch.zeros(B, dtype=torch.int32, device=L.device)
+    qd, vd = w.dev(q), w.dev(v)
+    _lib.check(L.lib.nmpc_observe_batch(L._h, B, _lib.ptr(qd), _lib.ptr(vd), T0, PERIOD, None, 3, None, None, 1, HEIGHT, None, 0, None, _lib.ptr(only), 4,
+                                        TERMINATE_DEFAULT, _lib.stream(L.device)), L._h, "nmpc_observe_batch", "torque")
+    assert torch.equal(only, failed)
+    # the upright robot beside a NaN robot: its rows are those of a batch of its own
+    S1, X1 = L.observe(q[:1], v[:1], T0, PERIOD, goal[:1], s_mean=w.s_mean, s_std=w.s_std)
+    assert torch.equal(S1[0], S[0]) and torch.equal(X1[0], X[0]) and bool(torch.isfinite(S[0]).all())
+    assert bool(torch.isnan(S[7, 19])) and bool(torch.isfinite(S[:7]).all())
+
+
+# ---- 3. the rollout is the chain ------------------------------------------------------------------------------------------------
+MASK = pr.FLAG_SOLVER | pr.FLAG_COLLISION | pr.FLAG_HEIGHT
+
+
+@pytest.mark.parametrize("B", [33, 257])
+def test_the_rollout_is_the_chain_of_the_public_calls(world, B):
+    w = world
+    chain = w.chain(B, 3, 2, MASK)
+    got = w.rollout(B, 3, 2, MASK)
+    assert [tuple(x.shape) for x in got] == [(B, 18), (B, 18), (B, 3, 44), (B, 3, 12), (B,)] and got[4].dtype == torch.int32
+    names = ("q", "v", "S", "A", "failed")
+    assert all(torch.equal(x, y) for x, y in zip(got, chain)), [n for n, x, y in zip(names, got, chain) if not torch.equal(x, y)]
+    stamps = (got[4] >> 8).cpu().numpy()
+    print(f"B {B}: stamps 0..4 -> {np.bincount(stamps, minlength=5)}")
+    assert stamps.max() <= 4
+    # without records the state and the flags are the same
+    bare = w.rollout(B, 3, 2, MASK, record=False)
+    assert bare[2] is None and bare[3] is None
+    assert torch.equal(bare[0], got[0]) and torch.equal(bare[1], got[1]) and torch.equal(bare[4], got[4])
+    # raw input, no feed-forward
+    assert all(torch.equal(x, y) for x, y in zip(w.rollout(B, 2, 1, 0, stats=False, tau=False), w.chain(B, 2, 1, 0, stats=False, tau=False)))
+
+
+def test_the_last_interval_is_observed(world):
+    """A robot in free fall (the plane far below) under the standing policy, 2 m/s downwards from z = 0.185: it is above the
+    height limit of 0.18 at the observations of steps 0, 1, 2 (0.1850, 0.1830, 0.1810 in the fp64 reference loop) and below it
+    after the last interval (0.1789).  Only the flags-only observation with step index K can stamp it, with K + 1."""
+    w, K = world, 3
+    q = np.zeros((2, 18), np.float32); q[:, 2] = (0.185, 0.3); q[:, 6:] = fr.STAND
+    v = np.zeros((2, 18), np.float32); v[0, 2] = -2.0
+    goal, far = np.zeros((2, N_GOAL), np.float32), cr.Ground(ground_z=-10.0)
+    ref = [pr.rollout_ref(w.m, far, standing_oracle(), q[0], v[0], k, DT, 2, goal[0])[2][2] for k in (2, 3)]
+    print(f"reference z after 2 and 3 control steps: {ref[0]:.5f}, {ref[1]:.5f}")
+    assert ref[0] > 0.1805 and ref[1] < 0.1795
+    qf, vf, S, A, failed = w.L.policy_rollout(w.standing, q, v, K, DT, 2, goal, ground=ground(far), terminate_mask=pr.FLAG_HEIGHT)
+    z = S[0, :, 19].cpu().numpy()
+    print(f"device z at the observations: {z}, after the last interval {float(qf[0, 2]):.5f}; failed {failed.tolist()}")
+    assert np.all(z > 0.18) and float(qf[0, 2]) < 0.18
+    assert failed.tolist() == [pr.FLAG_HEIGHT | ((K + 1) << pr.TERM_SHIFT), 0]
+    # one step fewer: nothing to see yet
+    assert w.L.policy_rollout(w.standing, q, v, K - 1, DT, 2, goal, ground=ground(far), terminate_mask=pr.FLAG_HEIGHT)[4].tolist() == [0, 0]
+
+
+def test_a_rollout_row_does_not_depend_on_its_batch(world):
+    w = world
+    whole = w.rollout(257, 3, 2, MASK)
+    for b in (0, 31, 32, 256):
+        one = w.rollout(1, 3, 2, MASK, rows=slice(b, b + 1))
+        assert all(torch.equal(x[0], y[b]) for x, y in zip(one, whole)), b
+
+
+# ---- 4. accuracy ----------------------------------------------------------------------------------------------------------------
+def test_the_rollout_matches_the_fp64_loop(world):
+    w, B, K, n_sub = world, 33, 3, 2
+    c = w.c
+    kw = dict(tau_ff=None, kp=KP, kd=KD, t0=T0, period=PERIOD, s_mean=w.s_mean, s_std=w.s_std)
+    run = lambda o, **x: [np.stack(r) for r in zip(*[pr.rollout_ref(w.m, w.g, o, c.q[b], c.v[b], K, DT, n_sub, w.goal[b], **{**kw, "tau_ff": w.tau[b]}, **x)   # noqa: E731
+                                                       for b in range(B)])]
+    ref, f32 = run(w.oracle), run(w.oracle32, fd=fr.aba, dtype=np.float32)
+    off, pushed, leaving = branches(w.g, c.pos[:B], c.vel[:B], c.f[:B])
+    print(f"feet off the ground {off}, pushed {pushed}, leaving too fast to be pushed {leaving}")
+    assert off and pushed and leaving
+    assert np.abs(ref[1] - fr.STAND).max() < 0.1
+    q, v, S, A, _ = host(*w.rollout(B, K, n_sub, MASK))
+    print("A_0 alone")
+    first = held("A_0", A[:, 0], ref[1][:, 0], f32[1][:, 0])
+    print(f"rollout, B {B}, K {K}, n_sub {n_sub}")
+    ok = [held(name, x, r, f) for name, x, r, f in (("S", S, ref[0], f32[0]), ("A", A, ref[1], f32[1]), ("q", q, ref[2], f32[2]), ("v", v, ref[3], f32[3]))]
+    assert first and all(ok)
+
+
+# ---- 5. the standing policy -----------------------------------------------------------------------------------------------------
+def test_the_standing_policy_settles(world):
+    from iterative_learning_nmpc_amd import learning
+    from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT
+    s, L = np.load(GOLDEN), layer(fr.quadruped())
+    two = lambda x: np.tile(x, (2, 1))                                             # noqa: E731
+    K, n_sub = 100, 20
+    assert K * n_sub == int(s["n_sub"]) and np.array_equal(s["q_des"], fr.STAND.astype(np.float32))
+    goal = np.zeros((2, N_GOAL), np.float32)
+    q, v, S, A, failed = L.policy_rollout(world.standing, two(s["q0"]), two(s["v0"]), K, float(s["dt"]), n_sub, goal, tau_ff=two(s["tau_ff"]),
+                                          kp=float(s["kp"]), kd=float(s["kd"]))
+    assert torch.equal(A, world.dev(fr.STAND).expand(2, K, 12))
+    once = L.contact_step(two(s["q0"]), two(s["v0"]), float(s["dt"]), int(s["n_sub"]), tau_ff=two(s["tau_ff"]), q_des=two(s["q_des"]),
+                          kp=float(s["kp"]), kd=float(s["kd"]))
+    assert torch.equal(q, once[0]) and torch.equal(v, once[1])
+    print("settling under the standing policy, 100 x 20 substeps")
+    qh, vh = host(q, v)
+    assert held("q", qh[0], s["q"], s["q32"]) and held("v", vh[0], s["v"], s["v32"])
+    assert failed.dtype == torch.int32 and not bool(failed.any())
+    assert bool(torch.isfinite(S).all()) and torch.equal(S[:, 0, 24:36], world.dev(two(s["q0"]))[:, 6:])
+    ev = learning.evaluate_policy(L, world.standing, None, two(s["q0"]), two(s["v0"]), goal, K * n_sub * float(s["dt"]), dt=float(s["dt"]),
+                                  n_sub=n_sub, tau_ff=two(s["tau_ff"]), kp=float(s["kp"]), kd=float(s["kd"]), terminate_mask=TERMINATE_DEFAULT)
+    assert all(isinstance(ev[k], torch.Tensor) and ev[k].is_cuda for k in ("failed", "survived", "steps_survived", "S", "A"))
+    assert bool(ev["survived"].all()) and ev["steps_survived"].tolist() == [K, K] and not bool(ev["failed"].any())
+    assert torch.equal(ev["S"], S) and torch.equal(ev["A"], A)
+    # a robot that starts below the collision height is stamped at the first observation and survives no step
+    low = two(s["q0"]); low[1, 2] = 0.05
+    ev = learning.evaluate_policy(L, world.standing, None, low, two(s["v0"]), goal, 3 * n_sub * float(s["dt"]), dt=float(s["dt"]), n_sub=n_sub)
+    assert ev["survived"].tolist() == [True, False] and ev["steps_survived"].tolist() == [3, 0] and tuple(ev["S"].shape) == (2, 3, 44)
+
+
+# ---- 6. errors ------------------------------------------------------------------------------------------------------------------
+def test_errors_and_the_empty_batch(world):
+    from iterative_learning_nmpc_amd import _lib
+    from iterative_learning_nmpc_amd._lib import NmpcError
+    from iterative_learning_nmpc_amd.policy import DevicePolicy
+    from iterative_learning_nmpc_amd.torque import GroundContact
+    w, L, B = world, world.L, 4
+    q, v, goal, X = w.dev(w.c.q[:B]), w.dev(w.c.v[:B]), w.dev(w.goal[:B]), torch.empty(B, 47, device=world.L.device)
+    mean, std = w.dev(w.s_mean, torch.float64), w.dev(w.s_std, torch.float64)
+    ptr = _lib.ptr
+
+    def call(cfg=(), ground=GroundContact().cfg(), **over):
+        """nmpc_policy_rollout_batch at the C boundary, arguments replaced by name -> (return code, text)"""
+        c = dict(n_steps=2, n_sub=1, dt=DT, kp=KP, kd=KD, t0=0.0, period=PERIOD, collision_height=HEIGHT, term_mask=0, n_goal=3, s_first=1)
+        if cfg is not None:
+            c.update(dict(cfg))
+            cfg = ctypes.byref(_lib.NmpcPolicyRolloutCfg(*c.values()))
+        qc, vc = q.clone(), v.clone()                       # the call steps them in place
+        a = dict(torque=L._h, policy=w.policy._h, B=B, cfg=cfg, ground=None if ground is None else ctypes.byref(ground),
+                 q=ptr(qc), v=ptr(vc), tau_ff=None, goal=ptr(goal), s_mean=None, s_std=None, S=None, A=None, X=ptr(X), failed=None)
+        a.update(over)
+        rc = L.lib.nmpc_policy_rollout_batch(*a.values(), _lib.stream(L.device))
+        torch.cuda.synchronize()
+        return rc, L.lib.nmpc_torque_last_error(a["torque"]).decode()
+
+    assert call()[0] == 0
+    small, wrong_in = DevicePolicy(47, 12, 1, 8, False, batch_max=2), DevicePolicy(46, 12, 1, 8, False, batch_max=8)
+    wrong_out = DevicePolicy(47, 11, 1, 8, False, batch_max=8)
+    bad_ground = GroundContact(slip_velocity=0.0).cfg()
+    refused = [(dict(policy=None), "policy is NULL"), (dict(cfg=None), "cfg is NULL"), (dict(ground=None), "cfg is NULL"),
+               (dict(q=None), "q, v, goal, X"), (dict(v=None), "q, v, goal, X"), (dict(goal=None), "q, v, goal, X"), (dict(X=None), "q, v, goal, X"),
+               (dict(cfg=dict(n_steps=0)), "n_steps must be at least 1"), (dict(cfg=dict(n_sub=0)), "n_sub must be at least 1"),
+               (dict(cfg=dict(dt=0.0)), "dt must be positive"), (dict(cfg=dict(period=0.0)), "period must be positive"),
+               (dict(cfg=dict(kp=float("nan"))), "kp must be finite"), (dict(cfg=dict(kp=float("inf"))), "kp must be finite"),
+               (dict(s_mean=ptr(mean)), "come together"), (dict(s_std=ptr(std)), "come together"),
+               (dict(cfg=dict(s_first=45)), r"s_first must be in [0, 44]"), (dict(cfg=dict(s_first=-1)), r"s_first must be in [0, 44]"),
+               (dict(policy=wrong_in._h), "44 + n_goal inputs"), (dict(cfg=dict(n_goal=2)), "44 + n_goal inputs"), (dict(policy=wrong_out._h), "12 actions"),
+               (dict(policy=small._h), "batch_max"), (dict(ground=bad_ground), "slip_velocity must be positive")]
+    for over, text in refused:
+        rc, why = call(**over)
+        assert rc == -1 and text in why, (over, rc, why)
+    assert call(s_mean=ptr(mean), s_std=ptr(std), cfg=dict(s_first=44))[0] == 0 and call(cfg=dict(s_first=0), s_mean=ptr(mean), s_std=ptr(std))[0] == 0
+    rc, why = L.lib.nmpc_policy_rollout_batch(None, w.policy._h, B, None, None, None, None, None, None, None, None, None, None, None, None, None), \
+        L.lib.nmpc_torque_last_error(None).decode()
+    assert rc == -1 and "null torque handle" in why
+    # a tree that is not the whole-body tree
+    other = layer(fr.random_tree())
+    assert call(torque=other._h) == (-1, "the observation needs the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4")
+    with pytest.raises(NmpcError, match="whole-body tree"):
+        other.observe(np.zeros((2, 23), np.float32), np.zeros((2, 23), np.float32), 0.0, PERIOD, np.zeros((2, 3), np.float32))
+    # the layer's own texts and checks
+    with pytest.raises(NmpcError, match="batch_max"):
+        L.policy_rollout(small, q, v, 2, DT, 1, goal)
+    with pytest.raises(NmpcError, match="44 \\+ n_goal inputs"):
+        L.policy_rollout(wrong_in, q, v, 2, DT, 1, goal)
+    with pytest.raises(NmpcError, match="policy is NULL"):
+        L.policy_rollout(None, q, v, 2, DT, 1, goal)
+    with pytest.raises(NmpcError, match="period must be positive"):
+        L.observe(q, v, 0.0, 0.0, goal)
+    with pytest.raises(NmpcError, match="s_first"):
+        L.observe(q, v, 0.0, PERIOD, goal, s_first=45)
+    with pytest.raises(ValueError, match="come together"):
+        L.observe(q, v, 0.0, PERIOD, goal, s_mean=w.s_mean)
+    with pytest.raises(ValueError, match="goal"):
+        L.policy_rollout(w.policy, q, v, 2, DT, 1, goal[:3])
+    with pytest.raises(ValueError, match="failed"):
+        L.observe(q, v, 0.0, PERIOD, goal, failed=torch.zeros(B, dtype=torch.int64, device=L.device))
+    st = _lib.stream(L.device)
+    assert L.lib.nmpc_observe_batch(L._h, B, ptr(q), ptr(v), 0.0, PERIOD, None, 3, None, None, 1, HEIGHT, None, 44, ptr(X), None, 0, 0, st) == -1
+    assert "X needs goal" in L.lib.nmpc_torque_last_error(L._h).decode()
+    assert L.lib.nmpc_observe_batch(L._h, B, ptr(q), ptr(v), 0.0, PERIOD, ptr(goal), 3, None, None, 1, HEIGHT, ptr(X), 43, None, None, 0, 0, st) == -1
+    assert "s_stride" in L.lib.nmpc_torque_last_error(L._h).decode()
+    assert L.lib.nmpc_observe_batch(L._h, B, None, ptr(v), 0.0, PERIOD, ptr(goal), 3, None, None, 1, HEIGHT, None, 44, None, None, 0, 0, st) == -1
+    # a database whose batches the rollout cannot reproduce: goals that are normalised, or no statistics yet
+    from iterative_learning_nmpc_amd.database import DeviceDatabase
+    with pytest.raises(ValueError, match="normalises its goals"):
+        L.policy_rollout(w.policy, q, v, 2, DT, 1, goal, db=DeviceDatabase(16, goal_type="cc"))
+    with pytest.raises(ValueError, match="database is empty"):
+        L.policy_rollout(w.policy, q, v, 2, DT, 1, goal, db=DeviceDatabase(16))
+    assert L.policy_rollout(w.policy, q, v, 2, DT, 1, goal, db=DeviceDatabase(16, norm_input=False))[2].shape == (B, 2, 44)
+    # B = 0
+    out = L.policy_rollout(w.policy, q[:0], v[:0], 3, DT, 2, goal[:0])
+    assert [tuple(x.shape) for x in out] == [(0, 18), (0, 18), (0, 3, 44), (0, 3, 12), (0,)]
+    assert [tuple(x.shape) for x in L.observe(q[:0], v[:0], 0.0, PERIOD, goal[:0])] == [(0, 44), (0, 47)]
+
+
+def test_massless_leaf_gives_nan_rows_and_the_next_call_is_sound(world):
+    w, B = world, 33
+    bad = copy.deepcopy(w.m)
+    bad.mass[17] = 0.0; bad.inertia[17] = 0.0
+    c = w.c
+    q, v, S, A, failed = layer(bad).policy_rollout(w.policy, c.q[:B], c.v[:B], 3, DT, 2, w.goal[:B], s_mean=w.s_mean, s_std=w.s_std,
+                                                   ground=ground(w.g), t0=T0, terminate_mask=pr.FLAG_SOLVER)
+    assert bool(torch.isnan(q).all()) and bool(torch.isnan(v).all())
+    # (the actions stay finite: the policy's ReLU turns a NaN into 0; the plant state is what carries the NaN on)
+    assert bool(torch.isfinite(S[:, 0]).all()) and bool(torch.isnan(S[:, 1:, 19]).all()) and bool(torch.isnan(S[:, 1:, 24:36]).all())
+    assert bool(((failed & pr.FLAG_SOLVER) != 0).all()) and (failed >> 8).tolist() == [2] * B      # seen by the observation of step 1
+    assert all(torch.equal(x, y) for x, y in zip(w.rollout(B, 3, 2, MASK), w.chain(B, 3, 2, MASK)))

@@ -1,0 +1,101 @@
+"""The policy-rollout entry points of include/nmpc_torque.h exist in every layer: exported by libnmpc_hip.so, bound with the
+header's argument lists, and behind methods of BatchedTorqueLayer and `learning.evaluate_policy`.  No GPU: what is decided on
+the host is checked."""
+import ctypes
+import inspect
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+C_TYPES = {"void *": ctypes.c_void_p, "const float *": ctypes.c_void_p, "float *": ctypes.c_void_p, "const double *": ctypes.c_void_p,
+           "int *": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
+           "const nmpc_contact_cfg *": ctypes.c_void_p, "const nmpc_policy_rollout_cfg *": ctypes.c_void_p}
+NAMES = ("nmpc_observe_batch", "nmpc_policy_rollout_batch")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    from iterative_learning_nmpc_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    return _lib.load()
+
+
+def header():
+    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "nmpc_torque.h")).read(), flags=re.S)      # comments aside
+
+
+def header_arguments(name):
+    """The ctypes argument list the header's declaration of `name` asks for."""
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header())
+    assert m, f"{name} is not declared in include/nmpc_torque.h"
+    out = []
+    for a in m.group(1).split(","):
+        a = " ".join(a.split())
+        if not re.match(r"^(const )?\w+ \*?\w+$", a):          # "const double *s_mean, const double *s_std" style lists are split already;
+            raise AssertionError(a)                             # anything else is a declaration this parser does not read
+        out.append(C_TYPES[re.sub(r"\s*\w+$", "", a).strip()])
+    return out
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_symbol_is_exported_and_bound_as_the_header_declares_it(lib, name):
+    from iterative_learning_nmpc_amd import _lib
+    assert getattr(lib, name) is not None
+    res, args = _lib.SIGNATURES[name]
+    assert res is ctypes.c_int and args == header_arguments(name)
+
+
+def test_argument_lists():
+    assert [len(header_arguments(n)) for n in NAMES] == [19, 16]
+
+
+def test_the_cfg_structure_has_the_headers_fields():
+    from iterative_learning_nmpc_amd import _lib
+    body = re.search(r"typedef struct \{([^}]*)\} nmpc_policy_rollout_cfg;", header()).group(1)
+    fields = []
+    for decl in body.strip().rstrip(";").split(";"):
+        typ, names = decl.split(None, 1)
+        fields += [(n.strip(), {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double}[typ]) for n in names.split(",")]
+    assert [n for n, _ in fields] == ["n_steps", "n_sub", "dt", "kp", "kd", "t0", "period", "collision_height", "term_mask", "n_goal", "s_first"]
+    assert list(_lib.NmpcPolicyRolloutCfg._fields_) == fields
+
+
+def test_the_policy_getter_is_declared_and_bound(lib):
+    from iterative_learning_nmpc_amd import _lib
+    text = open(os.path.join(ROOT, "include", "nmpc_policy.h")).read()
+    assert re.search(r"\bint\s+nmpc_policy_get_dims\s*\(void \*handle, nmpc_policy_dims \*dims, int \*device_id\)\s*;", text)
+    assert _lib.SIGNATURES["nmpc_policy_get_dims"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)])
+    assert lib.nmpc_policy_get_dims(None, None, None) == -1
+
+
+def test_layer_has_the_methods_and_the_defaults():
+    from iterative_learning_nmpc_amd import learning
+    from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT, GaitConfigFactory
+    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer, GroundContact
+    from iterative_learning_nmpc_amd.trajectory_io import KD, KP
+    ob = inspect.signature(BatchedTorqueLayer.observe).parameters
+    assert list(ob) == ["self", "q", "v", "t", "period", "goal", "s_mean", "s_std", "s_first", "collision_height", "failed", "step_index", "term_mask"]
+    assert [ob[k].default for k in list(ob)[6:]] == [None, None, 1, 0.08, None, 0, 0]
+    ro = inspect.signature(BatchedTorqueLayer.policy_rollout).parameters
+    assert list(ro) == ["self", "policy", "q", "v", "n_steps", "dt", "n_sub", "goal", "tau_ff", "kp", "kd", "ground", "t0", "period", "db",
+                        "s_mean", "s_std", "terminate_mask", "collision_height", "record"]
+    assert [ro[k].default for k in list(ro)[8:]] == [None, KP, KD, GroundContact(), 0.0, GaitConfigFactory.get("trot").nominal_period, None,
+                                                     None, None, TERMINATE_DEFAULT, 0.08, True]
+    ev = inspect.signature(learning.evaluate_policy).parameters
+    assert list(ev)[:7] == ["layer", "policy", "db", "q0", "v0", "goal", "T"]
+    assert ev["terminate_mask"].default == TERMINATE_DEFAULT
+
+
+def test_a_null_handle_is_refused_on_the_host(lib):
+    from iterative_learning_nmpc_amd import _lib
+    cfg = _lib.NmpcPolicyRolloutCfg(3, 2, 5e-4, 20.0, 1.5, 0.0, 0.5, 0.08, 0, 3, 1)
+    ground = _lib.NmpcContactCfg(0.0, 1e4, 3.0, 0.8, 0.05, 0.0)
+    assert lib.nmpc_observe_batch(None, 1, None, None, 0.0, 0.5, None, 3, None, None, 1, 0.08, None, 44, None, None, 0, 0, None) == -1
+    assert b"handle" in lib.nmpc_torque_last_error(None)
+    assert lib.nmpc_policy_rollout_batch(None, None, 1, ctypes.byref(cfg), ctypes.byref(ground), None, None, None, None, None, None, None, None,
+                                         None, None, None) == -1
+    assert b"handle" in lib.nmpc_torque_last_error(None)
