@@ -48,6 +48,17 @@ int nmpc_policy_set_params(void *handle, const float *theta, const float *runnin
 int nmpc_policy_get_params(void *handle, float *theta, float *running_mean, float *running_var,
                            void *stream);
 
+/* The optimiser state, for checkpoint / resume and for tests that need the gradient: Adam's first and second moments
+ * m, v (device pointers, param_count floats each, in the layout of theta) and the count of steps taken (it sets the
+ * bias corrections 1 - beta^step of the next step).  The copies are device to device and asynchronous on the stream.
+ *   get: any of m, v, step may be NULL; step is host state and is written at once -- it counts the steps launched so
+ *        far, whose moments the copies deliver in stream order.
+ *   set: needs m, v and step >= 0 (NMPC_E_ARG otherwise, nothing changed); step 0 with zero moments is the state
+ *        set_params leaves.  To resume a run, call set_params first (it resets the state), then this.
+ * After one step from the reset state m = (1 - 0.9f) g, so the gradient g of that step can be read off m. */
+int nmpc_policy_get_opt_state(void *handle, float *m, float *v, long long *step, void *stream);
+int nmpc_policy_set_opt_state(void *handle, const float *m, const float *v, long long step, void *stream);
+
 /* network.eval(); Y = network(X)      X[B][n_in] -> Y[B][n_out] */
 int nmpc_policy_forward(void *handle, int B, const float *X, float *Y, void *stream);
 

@@ -62,6 +62,8 @@ SIGNATURES = {
     "nmpc_policy_get_dims": (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
     "nmpc_policy_set_params": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_policy_get_params": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_policy_get_opt_state": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_longlong), c_void_p]),
+    "nmpc_policy_set_opt_state": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
     "nmpc_policy_forward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "nmpc_policy_train_step": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "nmpc_weighted_sample": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p]),

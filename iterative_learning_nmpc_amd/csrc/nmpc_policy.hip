@@ -790,6 +790,31 @@ int nmpc_policy_get_params(void* handle, float* theta, float* running_mean, floa
     return NMPC_OK;
 }
 
+int nmpc_policy_get_opt_state(void* handle, float* m, float* v, long long* step, void* stream) {
+    Policy* p = static_cast<Policy*>(handle);
+    if (!p) return fail(p, NMPC_E_ARG, "nmpc_policy_get_opt_state: null handle");
+    if (step) *step = p->step;                              // host state: the steps launched so far
+    if (!m && !v) return NMPC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    NMPC_ENTER(p, p->device);
+    if (m) NMPC_TRY(p, hipMemcpyAsync(m, p->m, p->n_theta * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (v) NMPC_TRY(p, hipMemcpyAsync(v, p->v, p->n_theta * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return NMPC_OK;
+}
+
+int nmpc_policy_set_opt_state(void* handle, const float* m, const float* v, long long step, void* stream) {
+    Policy* p = static_cast<Policy*>(handle);
+    if (!p) return fail(p, NMPC_E_ARG, "nmpc_policy_set_opt_state: null handle");
+    if (!m || !v) return fail(p, NMPC_E_ARG, "nmpc_policy_set_opt_state: null moments");
+    if (step < 0) return fail(p, NMPC_E_ARG, "nmpc_policy_set_opt_state: need step >= 0");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    NMPC_ENTER(p, p->device);
+    NMPC_TRY(p, hipMemcpyAsync(p->m, m, p->n_theta * sizeof(float), hipMemcpyDeviceToDevice, st));
+    NMPC_TRY(p, hipMemcpyAsync(p->v, v, p->n_theta * sizeof(float), hipMemcpyDeviceToDevice, st));
+    p->step = step;
+    return NMPC_OK;
+}
+
 int nmpc_policy_forward(void* handle, int B, const float* X, float* Y, void* stream) {
     Policy* p = static_cast<Policy*>(handle);
     if (!p) return NMPC_E_ARG;

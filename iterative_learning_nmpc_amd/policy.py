@@ -77,16 +77,24 @@ class DevicePolicy:
                 theta[off:off + n] = 1.0
         self.set_parameters(theta, torch.zeros(L, hidden), torch.ones(L, hidden))
 
+    def _staged(self, t, numel: int, what: str) -> torch.Tensor:
+        """`t` as contiguous fp32 on the policy's device, its length checked before anything is copied there"""
+        t = torch.as_tensor(t, dtype=torch.float32)
+        if t.numel() != numel:
+            raise ValueError(f"{what} needs {numel} elements, got {t.numel()}")
+        return t.contiguous().to(self.device)
+
+    def _set(self, name: str, *args):
+        """a set call of the library on staged tensors, which go out of scope afterwards: the stream is waited for"""
+        _lib.check(getattr(self.lib, name)(self._h, *args, stream(self.device)), self._h, name, "policy")
+        torch.cuda.current_stream(self.device).synchronize()
+
     def set_parameters(self, theta, running_mean=None, running_var=None):
         n_in, n_out, L, hidden, bn = self.dims
-        dev = lambda t: torch.as_tensor(t, dtype=torch.float32).contiguous().to(self.device)
-        theta = dev(theta)
-        assert theta.numel() == self.n_theta
-        rm = dev(running_mean) if bn else None
-        rv = dev(running_var) if bn else None
-        _lib.check(self.lib.nmpc_policy_set_params(self._h, ptr(theta), ptr(rm), ptr(rv), stream(self.device)),
-                   self._h, "nmpc_policy_set_params", "policy")
-        torch.cuda.current_stream(self.device).synchronize()      # the staging tensors go out of scope
+        theta = self._staged(theta, self.n_theta, "theta")
+        rm = self._staged(running_mean, L * hidden, "running_mean") if bn else None
+        rv = self._staged(running_var, L * hidden, "running_var") if bn else None
+        self._set("nmpc_policy_set_params", ptr(theta), ptr(rm), ptr(rv))
 
     def get_parameters(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         n_in, n_out, L, hidden, bn = self.dims
@@ -98,6 +106,21 @@ class DevicePolicy:
         _lib.check(self.lib.nmpc_policy_get_params(self._h, ptr(theta), ptr(rm), ptr(rv), stream(self.device)),
                    self._h, "nmpc_policy_get_params", "policy")
         return theta, rm, rv
+
+    def get_optimizer_state(self) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """Adam's moments (m, v: fp32 [n_theta] on the device, in the layout of theta) and the count of steps taken."""
+        m = torch.empty(self.n_theta, dtype=torch.float32, device=self.device)
+        v = torch.empty(self.n_theta, dtype=torch.float32, device=self.device)
+        step = ctypes.c_longlong()
+        _lib.check(self.lib.nmpc_policy_get_opt_state(self._h, ptr(m), ptr(v), ctypes.byref(step), stream(self.device)),
+                   self._h, "nmpc_policy_get_opt_state", "policy")
+        return m, v, int(step.value)
+
+    def set_optimizer_state(self, m, v, step: int):
+        """Resume from a checkpoint: after `set_parameters` (which resets the optimiser), put back what
+        `get_optimizer_state` gave."""
+        m, v = self._staged(m, self.n_theta, "m"), self._staged(v, self.n_theta, "v")
+        self._set("nmpc_policy_set_opt_state", ptr(m), ptr(v), int(step))
 
     def load_state_dict(self, state: Dict[str, "np.ndarray"]):
         """Parameters from the reference's state_dict ('net.<i>.weight', BatchNorm buffers ...)."""

@@ -71,6 +71,15 @@ def assert_same_state(pol_a, pol_b, what):
         assert np.array_equal(a, b), (what, name, int((a != b).sum()), float(np.abs(a - b).max()))
 
 
+def assert_same_optimizer_state(pol_a, pol_b, what, steps):
+    """Adam's moments and step count (nmpc_policy_get_opt_state), bit for bit; `steps`: the count both must have reached"""
+    (ma, va, sa), (mb, vb, sb) = pol_a.get_optimizer_state(), pol_b.get_optimizer_state()
+    assert sa == sb == steps, (what, sa, sb, steps)
+    for name, a, b in (("m", ma, mb), ("v", va, vb)):
+        assert same_bits(a, b), (what, name, int((a != b).sum()))
+    assert bool((va > 0).any()) or steps == 0
+
+
 # ---------------------------------------------------------------------------------------------- 1
 @pytest.mark.parametrize("name", ["A", "B", "C"])
 def test_epoch_equals_the_chain_of_entry_points_bit_for_bit(name):
@@ -82,12 +91,14 @@ def test_epoch_equals_the_chain_of_entry_points_bit_for_bit(name):
     assert idx.shape == (n_batches, batch) and idx.dtype == torch.int32 and same_bits(idx, idx_ref)
     assert same_bits(losses, losses_ref), (losses, losses_ref)
     assert_same_state(fused, ref, "one epoch")
+    assert_same_optimizer_state(fused, ref, "one epoch", n_batches)
     # two more calls on the same handle: the optimiser's step count (the Adam bias corrections) carries over
     for nb, s in ((2, 77), (1, 2 ** 40 + 5)):
         losses, idx = fused.train_epoch(db, batch, nb, LR, s, weights=w, return_idx=True)
         losses_ref, idx_ref = chain(ref, db, w, batch, nb, s)
         assert same_bits(idx, idx_ref) and same_bits(losses, losses_ref)
     assert_same_state(fused, ref, "three epochs in a row")
+    assert_same_optimizer_state(fused, ref, "three epochs in a row", n_batches + 3)
     assert bool(torch.isfinite(losses).all())
     # without idx_out, and with the database's own weight column as the default
     a, b = policy(net, batch), policy(net, batch)
@@ -95,8 +106,10 @@ def test_epoch_equals_the_chain_of_entry_points_bit_for_bit(name):
     lb, _ = chain(b, db, db.weights[:len(db)], batch, 2, 5)
     assert same_bits(la, lb)
     assert_same_state(a, b, "default weights")
+    assert_same_optimizer_state(a, b, "default weights", 2)
     assert a.train_epoch(db, batch, 0, LR, 5).shape == (0,)                    # no batches: nothing happens
     assert_same_state(a, b, "empty epoch")
+    assert_same_optimizer_state(a, b, "empty epoch", 2)
 
 
 # ---------------------------------------------------------------------------------------------- 2
