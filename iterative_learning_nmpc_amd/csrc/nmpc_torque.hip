@@ -35,6 +35,7 @@ namespace nmpc_torque {
 constexpr int MAXJ = NMPC_TREE_MAX_JOINTS, MAXF = NMPC_TREE_MAX_FEET;
 constexpr int TPB = 32;                    // robots per block: 27 floats x 32 joints x 32 threads = 108 KB of LDS at most
 constexpr int SLOTS = 27;                  // w 3, vo 3, dw 3, dvo 3 (reused as moment 3, force 3 ...), Rw 9, n 3, l 3
+constexpr size_t id_lds_bytes(int n) { return (size_t)n * SLOTS * TPB * sizeof(float); }
 
 struct Model {                             // device copy, fixed-size arrays
     int n, nu, nf;
@@ -73,6 +74,17 @@ __device__ __forceinline__ M3 mul(const M3& A, const M3& B) {
     return C;
 }
 
+// This thread's robot in the block's LDS slice [joint][NS slots][W threads]: the per-body state of every recursion of the family.
+template <int NS, int W>
+struct Slice {
+    __device__ __forceinline__ float& operator()(int joint, int slot) const {
+        extern __shared__ float body[];
+        return body[(joint * NS + slot) * W + threadIdx.x];
+    }
+    __device__ __forceinline__ V3 get3(int joint, int slot) const { return {(*this)(joint, slot), (*this)(joint, slot + 1), (*this)(joint, slot + 2)}; }
+    __device__ __forceinline__ void put3(int joint, int slot, V3 x) const { (*this)(joint, slot) = x.x; (*this)(joint, slot + 1) = x.y; (*this)(joint, slot + 2) = x.z; }
+};
+
 // x_parent = R x_child + p for joint i at coordinate qi: R = R_fix Rot(axis, qi) (revolute) or R_fix, p moved
 // along the axis (prismatic).  Rodrigues: Rot = I + sin K + (1 - cos) K^2.
 __device__ __forceinline__ void joint_transform(const Model& m, int i, float qi, M3& R, V3& p) {
@@ -99,14 +111,11 @@ __device__ __forceinline__ void joint_transform(const Model& m, int i, float qi,
 __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict__ mp, int B, const float* __restrict__ q,
                                                          const float* __restrict__ v, const float* __restrict__ a,
                                                          const float* __restrict__ f, float* __restrict__ tau) {
-    extern __shared__ float body[];                       // [joint][SLOTS][TPB]
     const Model& m = *mp;
     const int b = blockIdx.x * TPB + threadIdx.x;
     if (b >= B) return;
     const int n = m.n;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * SLOTS + slot) * TPB + threadIdx.x]; };
-    auto get3 = [&](int joint, int slot) { return V3{at(joint, slot), at(joint, slot + 1), at(joint, slot + 2)}; };
-    auto put3 = [&](int joint, int slot, V3 x) { at(joint, slot) = x.x; at(joint, slot + 1) = x.y; at(joint, slot + 2) = x.z; };
+    const Slice<SLOTS, TPB> at;
     const float* qb = q + (size_t)b * n;
     const float* vb = v + (size_t)b * n;
     const float* ab = a + (size_t)b * n;
@@ -119,7 +128,7 @@ __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict
         V3 w_p{0, 0, 0}, vo_p{0, 0, 0}, dw_p{0, 0, 0}, dvo_p{-m.gravity[0], -m.gravity[1], -m.gravity[2]};
         M3 Rw = R;
         if (par >= 0) {
-            w_p = get3(par, 0); vo_p = get3(par, 3); dw_p = get3(par, 6); dvo_p = get3(par, 9);
+            w_p = at.get3(par, 0); vo_p = at.get3(par, 3); dw_p = at.get3(par, 6); dvo_p = at.get3(par, 9);
             M3 Rp;
 #pragma unroll
             for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, 12 + k);
@@ -137,7 +146,7 @@ __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict
             dvo = dvo + qdd * ax + cross(w, qd * ax);
             vo = vo + qd * ax;
         }
-        put3(i, 0, w); put3(i, 3, vo); put3(i, 6, dw); put3(i, 9, dvo);
+        at.put3(i, 0, w); at.put3(i, 3, vo); at.put3(i, 6, dw); at.put3(i, 9, dvo);
 #pragma unroll
         for (int k = 0; k < 9; ++k) at(i, 12 + k) = Rw.m[k];
         // f = I a + v x* (I v) with the spatial inertia about the body origin
@@ -147,8 +156,8 @@ __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict
         auto inertia = [&](V3 x) { return V3{I[0] * x.x + I[1] * x.y + I[2] * x.z, I[1] * x.x + I[3] * x.y + I[4] * x.z, I[2] * x.x + I[4] * x.y + I[5] * x.z}; };
         const V3 h_l = mass * (vo + cross(w, c)), h_n = inertia(w) + cross(c, h_l);
         const V3 g_l = mass * (dvo + cross(dw, c)), g_n = inertia(dw) + cross(c, g_l);
-        put3(i, 21, g_n + cross(w, h_n) + cross(vo, h_l));      // moment about the body origin
-        put3(i, 24, g_l + cross(w, h_l));                       // force
+        at.put3(i, 21, g_n + cross(w, h_n) + cross(vo, h_l));      // moment about the body origin
+        at.put3(i, 24, g_l + cross(w, h_l));                       // force
     }
     // contact forces: world-frame force at the foot point of its body (= - J^T f, dynamics.py:158-161)
     if (f) {
@@ -158,13 +167,13 @@ __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict
 #pragma unroll
             for (int e = 0; e < 9; ++e) Rw.m[e] = at(j, 12 + e);
             const V3 l = mul_t(Rw, v3(f + ((size_t)b * m.nf + k) * 3));
-            put3(j, 24, get3(j, 24) - l);
-            put3(j, 21, get3(j, 21) - cross(v3(m.foot_offset[k]), l));
+            at.put3(j, 24, at.get3(j, 24) - l);
+            at.put3(j, 21, at.get3(j, 21) - cross(v3(m.foot_offset[k]), l));
         }
     }
     // inward: joint torques, forces handed to the parents
     for (int i = n - 1; i >= 0; --i) {
-        const V3 fn = get3(i, 21), fl = get3(i, 24);
+        const V3 fn = at.get3(i, 21), fl = at.get3(i, 24);
         const int act = i - (n - m.nu);
         if (act >= 0) tau[(size_t)b * m.nu + act] = dot(v3(m.axis[i]), m.type[i] == 0 ? fn : fl);
         const int par = m.parent[i];
@@ -172,8 +181,8 @@ __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict
             M3 R; V3 p;
             joint_transform(m, i, qb[i], R, p);
             const V3 l_p = mul(R, fl);
-            put3(par, 24, get3(par, 24) + l_p);
-            put3(par, 21, get3(par, 21) + mul(R, fn) + cross(p, l_p));
+            at.put3(par, 24, at.get3(par, 24) + l_p);
+            at.put3(par, 21, at.get3(par, 21) + mul(R, fn) + cross(p, l_p));
         }
     }
 }
@@ -185,11 +194,8 @@ __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict
 // rounds differently on tilted trees, and its outputs are held bit for bit.  A change to the recursion goes into both.
 template <class In, class Out>
 __device__ __forceinline__ void id_torques_body(const Model& m, const In& in, const Out& out) {
-    extern __shared__ float body[];                       // [joint][SLOTS][TPB]
     const int n = m.n;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * SLOTS + slot) * TPB + threadIdx.x]; };
-    auto get3 = [&](int joint, int slot) { return V3{at(joint, slot), at(joint, slot + 1), at(joint, slot + 2)}; };
-    auto put3 = [&](int joint, int slot, V3 x) { at(joint, slot) = x.x; at(joint, slot + 1) = x.y; at(joint, slot + 2) = x.z; };
+    const Slice<SLOTS, TPB> at;
 
     // outward: velocities, accelerations (gravity enters as an acceleration of the world), net force and moment
     for (int i = 0; i < n; ++i) {
@@ -199,7 +205,7 @@ __device__ __forceinline__ void id_torques_body(const Model& m, const In& in, co
         V3 w_p{0, 0, 0}, vo_p{0, 0, 0}, dw_p{0, 0, 0}, dvo_p{-m.gravity[0], -m.gravity[1], -m.gravity[2]};
         M3 Rw = R;
         if (par >= 0) {
-            w_p = get3(par, 0); vo_p = get3(par, 3); dw_p = get3(par, 6); dvo_p = get3(par, 9);
+            w_p = at.get3(par, 0); vo_p = at.get3(par, 3); dw_p = at.get3(par, 6); dvo_p = at.get3(par, 9);
             M3 Rp;
 #pragma unroll
             for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, 12 + k);
@@ -217,7 +223,7 @@ __device__ __forceinline__ void id_torques_body(const Model& m, const In& in, co
             dvo = dvo + qdd * ax + cross(w, qd * ax);
             vo = vo + qd * ax;
         }
-        put3(i, 0, w); put3(i, 3, vo); put3(i, 6, dw); put3(i, 9, dvo);
+        at.put3(i, 0, w); at.put3(i, 3, vo); at.put3(i, 6, dw); at.put3(i, 9, dvo);
 #pragma unroll
         for (int k = 0; k < 9; ++k) at(i, 12 + k) = Rw.m[k];
         // f = I a + v x* (I v) with the spatial inertia about the body origin
@@ -227,8 +233,8 @@ __device__ __forceinline__ void id_torques_body(const Model& m, const In& in, co
         auto inertia = [&](V3 x) { return V3{I[0] * x.x + I[1] * x.y + I[2] * x.z, I[1] * x.x + I[3] * x.y + I[4] * x.z, I[2] * x.x + I[4] * x.y + I[5] * x.z}; };
         const V3 h_l = mass * (vo + cross(w, c)), h_n = inertia(w) + cross(c, h_l);
         const V3 g_l = mass * (dvo + cross(dw, c)), g_n = inertia(dw) + cross(c, g_l);
-        put3(i, 21, g_n + cross(w, h_n) + cross(vo, h_l));      // moment about the body origin
-        put3(i, 24, g_l + cross(w, h_l));                       // force
+        at.put3(i, 21, g_n + cross(w, h_n) + cross(vo, h_l));      // moment about the body origin
+        at.put3(i, 24, g_l + cross(w, h_l));                       // force
     }
     // contact forces: world-frame force at the foot point of its body (= - J^T f, dynamics.py:158-161)
     if (in.has_f()) {
@@ -238,13 +244,13 @@ __device__ __forceinline__ void id_torques_body(const Model& m, const In& in, co
 #pragma unroll
             for (int e = 0; e < 9; ++e) Rw.m[e] = at(j, 12 + e);
             const V3 l = mul_t(Rw, in.f_at(k));
-            put3(j, 24, get3(j, 24) - l);
-            put3(j, 21, get3(j, 21) - cross(v3(m.foot_offset[k]), l));
+            at.put3(j, 24, at.get3(j, 24) - l);
+            at.put3(j, 21, at.get3(j, 21) - cross(v3(m.foot_offset[k]), l));
         }
     }
     // inward: joint torques, forces handed to the parents
     for (int i = n - 1; i >= 0; --i) {
-        const V3 fn = get3(i, 21), fl = get3(i, 24);
+        const V3 fn = at.get3(i, 21), fl = at.get3(i, 24);
         const int act = i - (n - m.nu);
         if (act >= 0) out(i, act, dot(v3(m.axis[i]), m.type[i] == 0 ? fn : fl));
         const int par = m.parent[i];
@@ -252,8 +258,8 @@ __device__ __forceinline__ void id_torques_body(const Model& m, const In& in, co
             M3 R; V3 p;
             joint_transform(m, i, in.q(i), R, p);
             const V3 l_p = mul(R, fl);
-            put3(par, 24, get3(par, 24) + l_p);
-            put3(par, 21, get3(par, 21) + mul(R, fn) + cross(p, l_p));
+            at.put3(par, 24, at.get3(par, 24) + l_p);
+            at.put3(par, 21, at.get3(par, 21) + mul(R, fn) + cross(p, l_p));
         }
     }
 }
@@ -288,7 +294,6 @@ struct PlanIn {
 };
 
 __global__ __launch_bounds__(TPB) void plan_actions_kernel(const Model* __restrict__ mp, const PlanArgs p) {
-    extern __shared__ float body[];                       // [joint][SLOTS][TPB]
     const Model& m = *mp;
     const size_t e = (size_t)blockIdx.x * TPB + threadIdx.x;
     if (e >= (size_t)p.B * p.n_steps) return;
@@ -302,7 +307,7 @@ __global__ __launch_bounds__(TPB) void plan_actions_kernel(const Model* __restri
     in.Xb = p.X + b * (p.N + 1) * nmpc::wb::NX;
     in.Ub = p.U + b * p.N * nmpc::wb::NU;
     in.ub = in.Ub + (size_t)hold * nmpc::wb::NU;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * SLOTS + slot) * TPB + threadIdx.x]; };
+    const Slice<SLOTS, TPB> at;
     id_torques_body(m, in, [&](int i, int, float t) {
         at(i, 0) = t;
         in.qv(i, at(i, 1), at(i, 2));
@@ -364,41 +369,59 @@ struct Torque {
 
 Torque* const no_handle = nullptr;      // for nmpc_torque_create and calls without a handle: errors go to the family's slot
 
+// the instantiation of a `template <int W>` kernel at a run-time block width of 32 or 16, for its attributes and its launches
+#define KERNEL_AT_WIDTH(kernel, w) ((w) == 32 ? kernel<32> : kernel<16>)
+
+// one of the plant steps, `width` robots per block
+template <class Args>
+int launch_step(Torque* t, void (*kernel)(const Model*, Args), int width, size_t lds, const Args& p, void* stream) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((p.B + width - 1) / width)), dim3(width), lds, static_cast<hipStream_t>(stream), t->dev, p);
+    return launched(t);
+}
+
+// one of the element-wise kernels: a thread per entry of a [B][nu] table
+template <class... KArgs, class... Args>
+int launch_elementwise(Torque* t, void (*kernel)(int, KArgs...), int B, void* stream, Args... args) {
+    const size_t n = (size_t)B * t->host.nu;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, args...);
+    return launched(t);
+}
+
+// why a step cannot be taken (nullptr: it can)
+const char* step_refusal(int n_sub, float dt) {
+    if (n_sub < 1) return "n_sub must be at least 1";
+    if (!(dt > 0.0f)) return "dt must be positive";
+    return nullptr;
+}
+
+// the tree of the whole-body model, whose state layout the observation and the plan labels read
+bool whole_body_tree(const Model& m) { return m.n == 18 && m.nu == 12 && m.nf == 4; }
+
 // the device side of nmpc_torque_create, on the handle's device; what was allocated before an error is nmpc_torque_destroy's to free
 int allocate(Torque* t) {
     NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&t->dev), sizeof(Model)));
     NMPC_TRY(no_handle, hipMemcpy(t->dev, &t->host, sizeof(Model), hipMemcpyHostToDevice));
     // more than the default 64 KB of LDS per block
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(id_torques_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            MAXJ * SLOTS * TPB * (int)sizeof(float)));
+                                            (int)id_lds_bytes(MAXJ)));
     // the forward dynamics' slice: the most its instantiation can be asked for (25 joints x 32 robots, 32 joints x 16)
-    if (t->fd_width == 32)
-        NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(fd_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)fd_lds_bytes(25, 32)));
-    else
-        NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(fd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)fd_lds_bytes(MAXJ, 16)));
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(fd_kernel, t->fd_width)),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)(t->fd_width == 32 ? fd_lds_bytes(25, 32) : fd_lds_bytes(MAXJ, 16))));
     // the contact plant: the kinematics slice of the largest tree, and the most the step's instantiation can be asked for by its
     // own width rule (ct_block_width: ct_wide_joints() joints x 32 robots, the largest tree x 16)
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(foot_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)fk_lds_bytes(MAXJ)));
-    if (t->ct_width == 32)
-        NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(contact_step_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)ct_lds_bytes(ct_wide_joints(), 32)));
-    else
-        NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(contact_step_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)ct_lds_bytes(MAXJ, 16)));
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width)),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
     return NMPC_OK;
 }
 
 // both forward-dynamics entry points: one launch of fd_kernel at the handle's block width
 int launch_fd(Torque* t, const FdArgs& p, void* stream) {
     const int w = t->fd_width;
-    const dim3 grid((unsigned)((p.B + w - 1) / w));
-    const size_t lds = fd_lds_bytes(t->host.n, w);
-    if (w == 32) hipLaunchKernelGGL(fd_kernel<32>, grid, dim3(32), lds, static_cast<hipStream_t>(stream), t->dev, p);
-    else hipLaunchKernelGGL(fd_kernel<16>, grid, dim3(16), lds, static_cast<hipStream_t>(stream), t->dev, p);
-    return launched(t);
+    return launch_step(t, KERNEL_AT_WIDTH(fd_kernel, w), w, fd_lds_bytes(t->host.n, w), p, stream);
 }
 
 // why a contact configuration cannot be used (nullptr: it can), and the form the kernels read
@@ -418,7 +441,7 @@ ContactCfg device_cfg(const nmpc_contact_cfg& c) {
 // why a state cannot be observed (nullptr: it can): the arguments nmpc_observe_batch and nmpc_policy_rollout_batch share
 const char* observe_refusal(const Torque* t, int B, const float* q, const float* v, double period, const float* goal, int n_goal,
                             const double* s_mean, const double* s_std, int s_first, const float* S, int s_stride, const float* X) {
-    if (t->host.n != 18 || t->host.nu != 12 || t->host.nf != 4)
+    if (!whole_body_tree(t->host))
         return "the observation needs the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4";
     if (B < 0 || !q || !v) return "need B >= 0 and q, v";
     if (!(period > 0.0)) return "period must be positive";
@@ -442,7 +465,7 @@ int launch_feet(Torque* t, const FootArgs& a, void* stream) {
 const char* nmpc_torque::plan_actions_refusal(void* handle, int n_steps, const int* zoh, float kp, int device) {
     const Torque* t = static_cast<const Torque*>(handle);
     if (!t) return "null torque handle";
-    if (t->host.n != 18 || t->host.nu != 12 || t->host.nf != 4)
+    if (!whole_body_tree(t->host))
         return "plan labels need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4";
     if (n_steps < 1) return "n_steps must be at least 1";
     if (!zoh) return "zoh is NULL";
@@ -513,9 +536,8 @@ int nmpc_id_torques_batch(void* handle, int B, const float* q, const float* v, c
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || !v || !a || !tau) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, a, tau");
     NMPC_ENTER(t, t->device);
-    const size_t lds = (size_t)t->host.n * SLOTS * TPB * sizeof(float);
-    hipLaunchKernelGGL(id_torques_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream),
-                       t->dev, B, q, v, a, f, tau);
+    hipLaunchKernelGGL(id_torques_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), id_lds_bytes(t->host.n),
+                       static_cast<hipStream_t>(stream), t->dev, B, q, v, a, f, tau);
     return launched(t);
 }
 
@@ -536,8 +558,7 @@ int nmpc_fd_step_batch(void* handle, int B, int n_sub, float dt, const float* q,
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
-    if (n_sub < 1) return fail(t, NMPC_E_ARG, "n_sub must be at least 1");
-    if (!(dt > 0.0f)) return fail(t, NMPC_E_ARG, "dt must be positive");
+    if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     FdArgs p{};
     p.B = B; p.n_sub = n_sub; p.dt = dt; p.kp = kp; p.kd = kd;
@@ -575,8 +596,7 @@ int nmpc_contact_step_batch(void* handle, int B, int n_sub, float dt, const nmpc
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
-    if (n_sub < 1) return fail(t, NMPC_E_ARG, "n_sub must be at least 1");
-    if (!(dt > 0.0f)) return fail(t, NMPC_E_ARG, "dt must be positive");
+    if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     ContactArgs p{};
@@ -584,11 +604,7 @@ int nmpc_contact_step_batch(void* handle, int B, int n_sub, float dt, const nmpc
     p.q = q; p.v = v; p.tau = tau_ff; p.q_des = q_des;
     p.q_out = q_out; p.v_out = v_out; p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out;
     const int w = t->ct_width;
-    const dim3 grid((unsigned)((B + w - 1) / w));
-    const size_t lds = ct_lds_bytes(t->host.n, w);
-    if (w == 32) hipLaunchKernelGGL(contact_step_kernel<32>, grid, dim3(32), lds, static_cast<hipStream_t>(stream), t->dev, p);
-    else hipLaunchKernelGGL(contact_step_kernel<16>, grid, dim3(16), lds, static_cast<hipStream_t>(stream), t->dev, p);
-    return launched(t);
+    return launch_step(t, KERNEL_AT_WIDTH(contact_step_kernel, w), w, ct_lds_bytes(t->host.n, w), p, stream);
 }
 
 int nmpc_observe_batch(void* handle, int B, const float* q, const float* v, double t, double period, const float* goal, int n_goal,
@@ -618,8 +634,7 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     if (!cfg) return fail(t, NMPC_E_ARG, "the rollout cfg is NULL");
     if (B < 0 || !q || !v || !goal || !X) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, goal, X");
     if (cfg->n_steps < 1) return fail(t, NMPC_E_ARG, "n_steps must be at least 1");
-    if (cfg->n_sub < 1) return fail(t, NMPC_E_ARG, "n_sub must be at least 1");
-    if (!(cfg->dt > 0.0f)) return fail(t, NMPC_E_ARG, "dt must be positive");
+    if (const char* why = step_refusal(cfg->n_sub, cfg->dt)) return fail(t, NMPC_E_ARG, why);
     if (!std::isfinite(cfg->kp)) return fail(t, NMPC_E_ARG, "kp must be finite");
     if (const char* why = observe_refusal(t, B, q, v, cfg->period, goal, cfg->n_goal, s_mean, s_std, cfg->s_first, nullptr, 0, X))
         return fail(t, NMPC_E_ARG, why);
@@ -632,7 +647,6 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     if (B > d.batch_max) return fail(t, NMPC_E_ARG, "B exceeds the policy's batch_max");
     if (policy_device != t->device) return fail(t, NMPC_E_ARG, "the policy lives on another device");
     const int nu = t->host.nu, K = cfg->n_steps;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
         NMPC_ENTER(t, t->device);
         if (t->act) NMPC_TRY(t, hipFree(t->act));
@@ -655,9 +669,7 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
         }
         if (A) {
             NMPC_ENTER(t, t->device);
-            const size_t n = (size_t)B * nu;
-            hipLaunchKernelGGL(action_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, nu, t->act, A + (size_t)k * nu, K * nu);
-            if (const int rc = launched(t)) return rc;
+            if (const int rc = launch_elementwise(t, action_rows_kernel, B, stream, nu, t->act, A + (size_t)k * nu, K * nu)) return rc;
         }
         if (const int rc = nmpc_contact_step_batch(t, B, cfg->n_sub, cfg->dt, ground, q, v, tau_ff, t->act, cfg->kp, cfg->kd, q, v, nullptr, nullptr,
                                                    nullptr, stream))
@@ -673,10 +685,7 @@ int nmpc_pd_torques_batch(void* handle, int B, const float* tau_ff, const float*
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || !v || !q_plan || !v_plan || !tau) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_plan, v_plan, tau");
     NMPC_ENTER(t, t->device);
-    const size_t n = (size_t)B * t->host.nu;
-    hipLaunchKernelGGL(pd_torques_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B,
-                       t->host.n, t->host.nu, tau_ff, q, v, q_plan, v_plan, kp, kd, tau);
-    return launched(t);
+    return launch_elementwise(t, pd_torques_kernel, B, stream, t->host.n, t->host.nu, tau_ff, q, v, q_plan, v_plan, kp, kd, tau);
 }
 
 int nmpc_pd_target_action_batch(void* handle, int B, const float* tau, const int* perm, const float* q, const float* v, float kp,
@@ -687,10 +696,7 @@ int nmpc_pd_target_action_batch(void* handle, int B, const float* tau, const int
     if (B < 0 || !tau || !q || !v || !action) return fail(t, NMPC_E_ARG, "need B >= 0 and tau, q, v, action");
     if (!(kp != 0.0f)) return fail(t, NMPC_E_ARG, "kp must not be zero");
     NMPC_ENTER(t, t->device);
-    const size_t n = (size_t)B * t->host.nu;
-    hipLaunchKernelGGL(pd_target_action_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       B, t->host.n, t->host.nu, tau, perm, q, v, kp, kd, action);
-    return launched(t);
+    return launch_elementwise(t, pd_target_action_kernel, B, stream, t->host.n, t->host.nu, tau, perm, q, v, kp, kd, action);
 }
 
 int nmpc_plan_actions_batch(void* handle, int B, int n_steps, int N, const float* X, const float* U, const int* zoh, double dt_nodes,
@@ -709,9 +715,9 @@ int nmpc_plan_actions_batch(void* handle, int B, int n_steps, int N, const float
     p.B = B; p.n_steps = n_steps; p.N = N; p.a_rows = a_rows; p.skip_mask = skip ? skip_mask : 0;
     p.dt_nodes = dt_nodes; p.sim_dt = sim_dt; p.kp = kp; p.kd = kd;
     p.X = X; p.U = U; p.zoh = zoh; p.perm = perm; p.skip = p.skip_mask ? skip : nullptr; p.A = A;
-    const size_t pairs = (size_t)B * n_steps, lds = (size_t)t->host.n * SLOTS * TPB * sizeof(float);
-    hipLaunchKernelGGL(plan_actions_kernel, dim3((unsigned)((pairs + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream),
-                       t->dev, p);
+    const size_t pairs = (size_t)B * n_steps;
+    hipLaunchKernelGGL(plan_actions_kernel, dim3((unsigned)((pairs + TPB - 1) / TPB)), dim3(TPB), id_lds_bytes(t->host.n),
+                       static_cast<hipStream_t>(stream), t->dev, p);
     return launched(t);
 }
 

@@ -39,15 +39,13 @@ struct FootArgs {
 
 // One outward pass: Rw, the world position of the body origin and the body-coordinate velocity (w, vo); the foot point of a
 // body is then p = p_w + Rw r, pd = Rw (vo + w x r).  One thread per robot, LDS slice [joint][FK_SLOTS][TPB].
+// The pass keeps its text here and in observe_kernel: as one function template called from both, this kernel rounded differently.
 __global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp, const FootArgs a) {
-    extern __shared__ float body[];                       // [joint][FK_SLOTS][TPB]
     const Model& m = *mp;
     const int b = blockIdx.x * TPB + threadIdx.x;
     if (b >= a.B) return;
     const int n = m.n;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * FK_SLOTS + slot) * TPB + threadIdx.x]; };
-    auto get3 = [&](int joint, int slot) { return V3{at(joint, slot), at(joint, slot + 1), at(joint, slot + 2)}; };
-    auto put3 = [&](int joint, int slot, V3 x) { at(joint, slot) = x.x; at(joint, slot + 1) = x.y; at(joint, slot + 2) = x.z; };
+    const Slice<FK_SLOTS, TPB> at;
     const float* qb = a.q + (size_t)b * n;
     const float* vb = a.v ? a.v + (size_t)b * n : nullptr;
     for (int i = 0; i < n; ++i) {
@@ -57,12 +55,12 @@ __global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp,
         V3 w_p{0, 0, 0}, vo_p{0, 0, 0}, pw = p;
         M3 Rw = R;
         if (par >= 0) {
-            w_p = get3(par, FK_V); vo_p = get3(par, FK_V + 3);
+            w_p = at.get3(par, FK_V); vo_p = at.get3(par, FK_V + 3);
             M3 Rp;
 #pragma unroll
             for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, FK_RW + k);
             Rw = mul(Rp, R);
-            pw = get3(par, FK_PW) + mul(Rp, p);
+            pw = at.get3(par, FK_PW) + mul(Rp, p);
         }
         V3 w = mul_t(R, w_p), vo = mul_t(R, vo_p + cross(w_p, p));
         const float qd = vb ? vb[i] : 0.0f;
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp,
         else vo = vo + qd * ax;
 #pragma unroll
         for (int k = 0; k < 9; ++k) at(i, FK_RW + k) = Rw.m[k];
-        put3(i, FK_PW, pw); put3(i, FK_V, w); put3(i, FK_V + 3, vo);
+        at.put3(i, FK_PW, pw); at.put3(i, FK_V, w); at.put3(i, FK_V + 3, vo);
     }
     for (int k = 0; k < m.nf; ++k) {
         const int j = m.foot_joint[k];
@@ -79,7 +77,7 @@ __global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp,
 #pragma unroll
         for (int e = 0; e < 9; ++e) Rw.m[e] = at(j, FK_RW + e);
         const V3 r = v3(m.foot_offset[k]);
-        const V3 p = get3(j, FK_PW) + mul(Rw, r), pd = mul(Rw, get3(j, FK_V + 3) + cross(get3(j, FK_V), r));
+        const V3 p = at.get3(j, FK_PW) + mul(Rw, r), pd = mul(Rw, at.get3(j, FK_V + 3) + cross(at.get3(j, FK_V), r));
         const size_t e = ((size_t)b * m.nf + k) * 3;
         if (a.pos) { a.pos[e] = p.x; a.pos[e + 1] = p.y; a.pos[e + 2] = p.z; }
         if (a.vel) { a.vel[e] = pd.x; a.vel[e + 1] = pd.y; a.vel[e + 2] = pd.z; }
@@ -128,6 +126,7 @@ struct ContactArgs {
 // fd_kernel's step with the law in place of given forces and the torque limit after the PD law.  f_out and tau_out are
 // written by the last substep as its force and torque are formed (nothing reads them), a_out, q_out, v_out after the last read
 // of the inputs, so q_out, v_out may alias q, v.  The copy loops are kept as written, as fd_kernel's.
+// Both keep their text: as wrappers of one step driver with two plants the bits held, but fd_kernel<32> was 0.7-1.2 % slower.
 template <int W>
 __global__ __launch_bounds__(W) void contact_step_kernel(const Model* __restrict__ mp, const ContactArgs p) {
     extern __shared__ float body[];                       // [joint][CT_SLOTS][W]
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(W) void contact_step_kernel(const Model* __restrict
     __syncthreads();
     const int b = blockIdx.x * W + threadIdx.x;
     if (b >= p.B) return;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * CT_SLOTS + slot) * W + threadIdx.x]; };
+    const Slice<CT_SLOTS, W> at;
     const float* qb = p.q + (size_t)b * n;
     const float* vb = p.v + (size_t)b * n;
     const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;

@@ -69,12 +69,9 @@ struct GivenForces {
 // massless leaf body): the caller writes NaN.  W: robots per block (the slice's stride), NS: slots per joint of the slice.
 template <int W, int NS, class Force>
 __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force) {
-    extern __shared__ float body[];                       // [joint][NS][W]
     static_assert(NS >= FD_SLOTS + (Force::kinematic ? 3 : 0), "the slice is too narrow for this force source");
     const int n = m.n;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * NS + slot) * W + threadIdx.x]; };
-    auto get3 = [&](int joint, int slot) { return V3{at(joint, slot), at(joint, slot + 1), at(joint, slot + 2)}; };
-    auto put3 = [&](int joint, int slot, V3 x) { at(joint, slot) = x.x; at(joint, slot + 1) = x.y; at(joint, slot + 2) = x.z; };
+    const Slice<NS, W> at;
 
     // outward: velocities, c = v x (S qd), world rotation, I^A = I, p^A = v x* (I v) - foot forces
     for (int i = 0; i < n; ++i) {
@@ -85,14 +82,14 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
         M3 Rw = R;
         V3 pw = p;                     // world position of the body origin (kinematic force sources only)
         if (par >= 0) {
-            w_p = get3(par, FD_V); vo_p = get3(par, FD_V + 3);
+            w_p = at.get3(par, FD_V); vo_p = at.get3(par, FD_V + 3);
             M3 Rp;
 #pragma unroll
             for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, FD_RW + k);
             Rw = mul(Rp, R);
-            if constexpr (Force::kinematic) pw = get3(par, FD_PW) + mul(Rp, p);
+            if constexpr (Force::kinematic) pw = at.get3(par, FD_PW) + mul(Rp, p);
         }
-        if constexpr (Force::kinematic) put3(i, FD_PW, pw);
+        if constexpr (Force::kinematic) at.put3(i, FD_PW, pw);
         V3 w = mul_t(R, w_p), vo = mul_t(R, vo_p + cross(w_p, p));
         const V3 ax = v3(m.axis[i]);
         const float qd = at(i, FD_Q + 1);
@@ -104,7 +101,7 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
             c_v = cross(w, qd * ax);
             vo = vo + qd * ax;
         }
-        put3(i, FD_V, w); put3(i, FD_V + 3, vo); put3(i, FD_C, c_w); put3(i, FD_C + 3, c_v);
+        at.put3(i, FD_V, w); at.put3(i, FD_V + 3, vo); at.put3(i, FD_C, c_w); at.put3(i, FD_C + 3, c_v);
 #pragma unroll
         for (int k = 0; k < 9; ++k) at(i, FD_RW + k) = Rw.m[k];
         // spatial inertia about the body origin: A = Ic - m [c]x [c]x, B = m [c]x, C = m 1
@@ -136,7 +133,7 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
                 p_n = p_n - cross(v3(m.foot_offset[k]), l);
             }
         }
-        put3(i, FD_P, p_n); put3(i, FD_P + 3, p_l);
+        at.put3(i, FD_P, p_n); at.put3(i, FD_P + 3, p_l);
     }
 
     // inward: U = I^A S, d = S^T U, u = tau - S^T p^A; I^a = I^A - U U^T / d and p^a = p^A + I^a c + U u / d go to the parent
@@ -152,17 +149,17 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
         const V3 ax = v3(m.axis[i]);
         const bool rev = m.type[i] == 0;
         const V3 U_n = rev ? mul(A, ax) : mul(Bm, ax), U_l = rev ? mul_t(Bm, ax) : mul(C, ax);
-        const V3 p_n = get3(i, FD_P), p_l = get3(i, FD_P + 3);
+        const V3 p_n = at.get3(i, FD_P), p_l = at.get3(i, FD_P + 3);
         const float d = dot(ax, rev ? U_n : U_l);
         const float u = at(i, FD_Q + 2) - dot(ax, rev ? p_n : p_l);
         sound = sound && d > 0.0f && d < INFINITY;
-        put3(i, FD_RW, U_n); put3(i, FD_RW + 3, U_l);
+        at.put3(i, FD_RW, U_n); at.put3(i, FD_RW + 3, U_l);
         at(i, FD_RW + 6) = d; at(i, FD_RW + 7) = u;
         const int par = m.parent[i];
         if (par < 0) continue;
         const float inv_d = 1.0f / d;
         sub_outer(A, U_n, inv_d); sub_outer(Bm, U_n, U_l, inv_d); sub_outer(C, U_l, inv_d);
-        const V3 c_w = get3(i, FD_C), c_v = get3(i, FD_C + 3);
+        const V3 c_w = at.get3(i, FD_C), c_v = at.get3(i, FD_C + 3);
         const float s = u * inv_d;
         const V3 a_n = p_n + mul(A, c_w) + mul(Bm, c_v) + s * U_n, a_l = p_l + mul_t(Bm, c_w) + mul(C, c_v) + s * U_l;
         // to the parent's frame: forces l' = R l, n' = R n + p x l'; the inertia R (.) R^T, then shifted by p:
@@ -170,8 +167,8 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
         M3 R; V3 p;
         joint_transform(m, i, at(i, FD_Q), R, p);
         const V3 l_p = mul(R, a_l);
-        put3(par, FD_P + 3, get3(par, FD_P + 3) + l_p);
-        put3(par, FD_P, get3(par, FD_P) + mul(R, a_n) + cross(p, l_p));
+        at.put3(par, FD_P + 3, at.get3(par, FD_P + 3) + l_p);
+        at.put3(par, FD_P, at.get3(par, FD_P) + mul(R, a_n) + cross(p, l_p));
         const M3 Ar = rotated(R, full(A)), Br = rotated(R, Bm), Cr = rotated(R, full(C)), P = skew(p);
         M3 Bp = mul(P, Cr);
 #pragma unroll
@@ -195,13 +192,13 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
         joint_transform(m, i, at(i, FD_Q), R, p);
         const int par = m.parent[i];
         V3 dw_p{0, 0, 0}, dvo_p{-m.gravity[0], -m.gravity[1], -m.gravity[2]};
-        if (par >= 0) { dw_p = get3(par, FD_V); dvo_p = get3(par, FD_V + 3); }
-        V3 dw = mul_t(R, dw_p) + get3(i, FD_C), dvo = mul_t(R, dvo_p + cross(dw_p, p)) + get3(i, FD_C + 3);
-        const float qdd = (at(i, FD_RW + 7) - dot(get3(i, FD_RW), dw) - dot(get3(i, FD_RW + 3), dvo)) / at(i, FD_RW + 6);
+        if (par >= 0) { dw_p = at.get3(par, FD_V); dvo_p = at.get3(par, FD_V + 3); }
+        V3 dw = mul_t(R, dw_p) + at.get3(i, FD_C), dvo = mul_t(R, dvo_p + cross(dw_p, p)) + at.get3(i, FD_C + 3);
+        const float qdd = (at(i, FD_RW + 7) - dot(at.get3(i, FD_RW), dw) - dot(at.get3(i, FD_RW + 3), dvo)) / at(i, FD_RW + 6);
         const V3 ax = v3(m.axis[i]);
         if (m.type[i] == 0) dw = dw + qdd * ax;
         else dvo = dvo + qdd * ax;
-        put3(i, FD_V, dw); put3(i, FD_V + 3, dvo);
+        at.put3(i, FD_V, dw); at.put3(i, FD_V + 3, dvo);
         at(i, FD_Q + 2) = qdd;
     }
     return sound;
@@ -220,12 +217,11 @@ struct FdArgs {
 // with their run-time overlap checks they cost 26 SGPR spills around the recursion and save nothing.
 template <int W>
 __global__ __launch_bounds__(W) void fd_kernel(const Model* __restrict__ mp, const FdArgs p) {
-    extern __shared__ float body[];                       // [joint][FD_SLOTS][W]
     const Model& m = *mp;
     const int b = blockIdx.x * W + threadIdx.x;
     if (b >= p.B) return;
     const int n = m.n, nu = m.nu, base = n - nu;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * FD_SLOTS + slot) * W + threadIdx.x]; };
+    const Slice<FD_SLOTS, W> at;
     const float* qb = p.q + (size_t)b * n;
     const float* vb = p.v + (size_t)b * n;
     const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;

@@ -5,7 +5,7 @@
 // The plant state (q, v [18] in the solver's Euler layout [x y z yaw pitch roll joints]) becomes the reference's 44-slot state
 // row (RolloutMPC.py:221; the layout of `record` in nmpc_wb_rollout.hip.inc), the policy input made of it, and the fall
 // predicates.  The feet of base_wrt_feet are the tree's own -- the points the contact law pushes --, so the kernel runs the
-// outward pass of foot_kernel (its text, without the velocities: Rw and the world position of the body origins, 12 slots), not
+// outward pass of foot_kernel (a copy without the velocities, DESIGN.md 8d: Rw and the world position of the body origins, 12 slots), not
 // the closed-form geometry of the whole-body model.  One thread per robot, LDS slice [joint][OB_SLOTS][TPB].
 #pragma once
 
@@ -26,14 +26,11 @@ struct ObserveArgs {
 };
 
 __global__ __launch_bounds__(TPB) void observe_kernel(const Model* __restrict__ mp, const ObserveArgs a) {
-    extern __shared__ float body[];                       // [joint][OB_SLOTS][TPB]
     const Model& m = *mp;
     const int b = blockIdx.x * TPB + threadIdx.x;
     if (b >= a.B) return;
     const int n = m.n;
-    auto at = [&](int joint, int slot) -> float& { return body[(joint * OB_SLOTS + slot) * TPB + threadIdx.x]; };
-    auto get3 = [&](int joint, int slot) { return V3{at(joint, slot), at(joint, slot + 1), at(joint, slot + 2)}; };
-    auto put3 = [&](int joint, int slot, V3 x) { at(joint, slot) = x.x; at(joint, slot + 1) = x.y; at(joint, slot + 2) = x.z; };
+    const Slice<OB_SLOTS, TPB> at;
     const float* qb = a.q + (size_t)b * n;
     const float* vb = a.v + (size_t)b * n;
     if (a.S || a.X) {
@@ -56,11 +53,11 @@ __global__ __launch_bounds__(TPB) void observe_kernel(const Model* __restrict__ 
 #pragma unroll
                 for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, OB_RW + k);
                 Rw = mul(Rp, R);
-                pw = get3(par, OB_PW) + mul(Rp, p);
+                pw = at.get3(par, OB_PW) + mul(Rp, p);
             }
 #pragma unroll
             for (int k = 0; k < 9; ++k) at(i, OB_RW + k) = Rw.m[k];
-            put3(i, OB_PW, pw);
+            at.put3(i, OB_PW, pw);
         }
         // the row: [phase, v_lin 3, body rates 3, joint rates 12, z, quaternion wxyz (w >= 0) 4, joints 12, base_wrt_feet 8]
         put(0, (float)nmpc::recorded_phase(a.t, a.period));
@@ -86,7 +83,7 @@ __global__ __launch_bounds__(TPB) void observe_kernel(const Model* __restrict__ 
             M3 Rw;
 #pragma unroll
             for (int e = 0; e < 9; ++e) Rw.m[e] = at(j, OB_RW + e);
-            const V3 p = get3(j, OB_PW) + mul(Rw, v3(m.foot_offset[k]));
+            const V3 p = at.get3(j, OB_PW) + mul(Rw, v3(m.foot_offset[k]));
             put(36 + 2 * k, qb[0] - p.x); put(37 + 2 * k, qb[1] - p.y);
         }
 #pragma clang loop unroll(disable) vectorize(disable)

@@ -75,13 +75,37 @@ class BatchedTorqueLayer:
             raise ValueError(f"{name}: expected [B, {', '.join(map(str, width))}], got {tuple(t.shape)}")
         return t
 
+    def _opt(self, t, width, name):
+        return None if t is None else self._in(t, width, name)
+
+    @staticmethod
+    def _batch(*tensors):
+        """the B that all given tensors share"""
+        B = tensors[0].shape[0]
+        if any(x is not None and x.shape[0] != B for x in tensors):
+            raise ValueError("batch sizes differ")
+        return B
+
+    def _perm(self, actuator_to_joint):
+        if actuator_to_joint is None:
+            return None
+        perm = torch.as_tensor(list(actuator_to_joint), dtype=torch.int32, device=self.device)
+        if perm.numel() != self.nu or sorted(perm.tolist()) != list(range(self.nu)):
+            raise ValueError("actuator_to_joint must be a permutation of range(nu)")
+        return perm
+
+    def _flags(self, x, like, name):
+        """x, an int32 vector with one entry per row of `like` and on its device, or None"""
+        B = like.shape[0]
+        if x is not None and (x.dtype != torch.int32 or tuple(x.shape) != (B,) or not x.is_contiguous() or x.device != like.device):
+            raise ValueError(f"{name}: need contiguous int32 ({B},) on {self.device}")
+        return x
+
     def id_torques(self, q_plan, v_plan, a_plan, f_plan=None) -> torch.Tensor:
         """dynamics.py:136-163 per robot: q, v, a [B, n]; f [B, n_feet, 3] world-frame contact forces -> [B, nu]."""
         q = self._in(q_plan, (self.n,), "q_plan"); v = self._in(v_plan, (self.n,), "v_plan"); a = self._in(a_plan, (self.n,), "a_plan")
-        f = None if f_plan is None else self._in(f_plan, (self.n_feet, 3), "f_plan")
-        B = q.shape[0]
-        if v.shape[0] != B or a.shape[0] != B or (f is not None and f.shape[0] != B):
-            raise ValueError("batch sizes differ")
+        f = self._opt(f_plan, (self.n_feet, 3), "f_plan")
+        B = self._batch(q, v, a, f)
         tau = torch.empty(B, self.nu, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.nmpc_id_torques_batch(self._h, B, ptr(q), ptr(v), ptr(a), ptr(f), ptr(tau), stream(self.device)),
                    self._h, "nmpc_id_torques_batch", "torque")
@@ -91,11 +115,8 @@ class BatchedTorqueLayer:
         """nmpc_fd_accel_batch, the inverse of `id_torques`: q, v [B, n]; tau [B, nu] on the last nu joints (None = zero);
         f [B, n_feet, 3] world-frame contact forces (None = none) -> the accelerations [B, n]."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
-        tau = None if tau is None else self._in(tau, (self.nu,), "tau")
-        f = None if f is None else self._in(f, (self.n_feet, 3), "f")
-        B = q.shape[0]
-        if any(x is not None and x.shape[0] != B for x in (v, tau, f)):
-            raise ValueError("batch sizes differ")
+        tau = self._opt(tau, (self.nu,), "tau"); f = self._opt(f, (self.n_feet, 3), "f")
+        B = self._batch(q, v, tau, f)
         a = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.nmpc_fd_accel_batch(self._h, B, ptr(q), ptr(v), ptr(tau), ptr(f), ptr(a), stream(self.device)),
                    self._h, "nmpc_fd_accel_batch", "torque")
@@ -106,12 +127,9 @@ class BatchedTorqueLayer:
         tau = tau_ff + kp (q_des - q_j) - kd v_j re-evaluated every substep (q_des [B, nu]: a recorded action in joint
         order; None: tau = tau_ff; tau_ff None = zero) -> (q, v, a of the last substep), new tensors [B, n]."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
-        tau_ff = None if tau_ff is None else self._in(tau_ff, (self.nu,), "tau_ff")
-        q_des = None if q_des is None else self._in(q_des, (self.nu,), "q_des")
-        f = None if f is None else self._in(f, (self.n_feet, 3), "f")
-        B = q.shape[0]
-        if any(x is not None and x.shape[0] != B for x in (v, tau_ff, q_des, f)):
-            raise ValueError("batch sizes differ")
+        tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff"); q_des = self._opt(q_des, (self.nu,), "q_des")
+        f = self._opt(f, (self.n_feet, 3), "f")
+        B = self._batch(q, v, tau_ff, q_des, f)
         q_out, v_out, a_out = (torch.empty(B, self.n, dtype=torch.float32, device=self.device) for _ in range(3))
         _lib.check(self.lib.nmpc_fd_step_batch(self._h, B, int(n_sub), float(dt), ptr(q), ptr(v), ptr(tau_ff), ptr(q_des), float(kp),
                                                float(kd), ptr(f), ptr(q_out), ptr(v_out), ptr(a_out), stream(self.device)),
@@ -122,10 +140,8 @@ class BatchedTorqueLayer:
         """nmpc_foot_kinematics_batch: q, v [B, n] (v None = at rest) -> world position and velocity of every foot point,
         (pos, vel), each [B, n_feet, 3]."""
         q = self._in(q, (self.n,), "q")
-        v = None if v is None else self._in(v, (self.n,), "v")
-        B = q.shape[0]
-        if v is not None and v.shape[0] != B:
-            raise ValueError("batch sizes differ")
+        v = self._opt(v, (self.n,), "v")
+        B = self._batch(q, v)
         pos, vel = (torch.empty(B, self.n_feet, 3, dtype=torch.float32, device=self.device) for _ in range(2))
         _lib.check(self.lib.nmpc_foot_kinematics_batch(self._h, B, ptr(q), ptr(v), ptr(pos), ptr(vel), stream(self.device)),
                    self._h, "nmpc_foot_kinematics_batch", "torque")
@@ -135,10 +151,8 @@ class BatchedTorqueLayer:
         """nmpc_contact_forces_batch: the ground-contact law on the foot kinematics of q, v [B, n] (v None = at rest) ->
         f [B, n_feet, 3], the world-frame forces `forward_dynamics` would have to be handed."""
         q = self._in(q, (self.n,), "q")
-        v = None if v is None else self._in(v, (self.n,), "v")
-        B = q.shape[0]
-        if v is not None and v.shape[0] != B:
-            raise ValueError("batch sizes differ")
+        v = self._opt(v, (self.n,), "v")
+        B = self._batch(q, v)
         f = torch.empty(B, self.n_feet, 3, dtype=torch.float32, device=self.device)
         cfg = ground.cfg()
         _lib.check(self.lib.nmpc_contact_forces_batch(self._h, B, ctypes.byref(cfg), ptr(q), ptr(v), ptr(f), stream(self.device)),
@@ -151,11 +165,8 @@ class BatchedTorqueLayer:
         substep, the PD torque clamped to ground.tau_max -> (q, v, a, f, tau): the new state [B, n], and the acceleration
         [B, n], foot forces [B, n_feet, 3] and clamped torques [B, nu] of the last substep."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
-        tau_ff = None if tau_ff is None else self._in(tau_ff, (self.nu,), "tau_ff")
-        q_des = None if q_des is None else self._in(q_des, (self.nu,), "q_des")
-        B = q.shape[0]
-        if any(x is not None and x.shape[0] != B for x in (v, tau_ff, q_des)):
-            raise ValueError("batch sizes differ")
+        tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff"); q_des = self._opt(q_des, (self.nu,), "q_des")
+        B = self._batch(q, v, tau_ff, q_des)
         q_out, v_out, a_out = (torch.empty(B, self.n, dtype=torch.float32, device=self.device) for _ in range(3))
         f_out = torch.empty(B, self.n_feet, 3, dtype=torch.float32, device=self.device)
         tau_out = torch.empty(B, self.nu, dtype=torch.float32, device=self.device)
@@ -182,12 +193,6 @@ class BatchedTorqueLayer:
             raise ValueError(f"goal: expected [{B}, n_goal], got {tuple(goal.shape)}")
         return goal
 
-    def _failed(self, failed, B):
-        if failed is not None and (failed.dtype != torch.int32 or tuple(failed.shape) != (B,) or not failed.is_contiguous()
-                                   or failed.device != self.device):
-            raise ValueError(f"failed: need contiguous int32 ({B},) on {self.device}")
-        return failed
-
     def observe(self, q, v, t: float, period: float, goal, s_mean=None, s_std=None, s_first: int = 1,
                 collision_height: float = 0.08, failed: Optional[torch.Tensor] = None, step_index: int = 0, term_mask: int = 0):
         """nmpc_observe_batch: the plant state q, v [B, 18] (Euler layout) at time t as the reference's 44-slot state row
@@ -196,12 +201,10 @@ class BatchedTorqueLayer:
         int32 [B] on the device, updated in place with the flags the state raises and, where a bit of term_mask is set and
         no stamp is present, the stamp step_index + 1 (None: nothing is written).  -> (S_row [B, 44], X [B, 44 + n_goal])."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
-        B = q.shape[0]
-        if v.shape[0] != B:
-            raise ValueError("batch sizes differ")
+        B = self._batch(q, v)
         goal = self._goal(goal, B)
         s_mean, s_std = self._stats(s_mean, s_std)
-        failed = self._failed(failed, B)
+        failed = self._flags(failed, q, "failed")
         S = torch.empty(B, N_STATE, dtype=torch.float32, device=self.device)
         X = torch.empty(B, N_STATE + goal.shape[1], dtype=torch.float32, device=self.device)
         _lib.check(self.lib.nmpc_observe_batch(self._h, B, ptr(q), ptr(v), float(t), float(period), ptr(goal), goal.shape[1], ptr(s_mean),
@@ -226,10 +229,8 @@ class BatchedTorqueLayer:
         (failed >> 8 = 1 + the control step whose observation saw it) and keeps being stepped.
         -> (q, v, S [B, n_steps, 44], A [B, n_steps, 12], failed int32 [B]); S and A are None with record=False."""
         q = self._in(q, (self.n,), "q").clone(); v = self._in(v, (self.n,), "v").clone()
-        B = q.shape[0]
-        tau_ff = None if tau_ff is None else self._in(tau_ff, (self.nu,), "tau_ff")
-        if v.shape[0] != B or (tau_ff is not None and tau_ff.shape[0] != B):
-            raise ValueError("batch sizes differ")
+        tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff")
+        B = self._batch(q, v, tau_ff)
         goal = self._goal(goal, B)
         if db is not None:
             if s_mean is not None or s_std is not None:
@@ -260,7 +261,7 @@ class BatchedTorqueLayer:
         """mpc.py:592-599: torques_ff + Kp (q_plan[-nu:] - q[-nu:]) + Kd (v_plan[-nu:] - v[-nu:])."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
         qp = self._in(q_plan, (self.n,), "q_plan"); vp = self._in(v_plan, (self.n,), "v_plan")
-        ff = None if torques_ff is None else self._in(torques_ff, (self.nu,), "torques_ff")
+        ff = self._opt(torques_ff, (self.nu,), "torques_ff")
         tau = torch.empty(q.shape[0], self.nu, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.nmpc_pd_torques_batch(self._h, q.shape[0], ptr(ff), ptr(q), ptr(v), ptr(qp), ptr(vp), float(Kp),
                                                   float(Kd), ptr(tau), stream(self.device)), self._h, "nmpc_pd_torques_batch", "torque")
@@ -269,9 +270,7 @@ class BatchedTorqueLayer:
     def pd_target_action(self, tau, q, v, kp: float = 20.0, kd: float = 1.5, actuator_to_joint: Optional[Sequence[int]] = None):
         """RolloutMPC.py:228-250: action = (tau[perm] + kd v_j) / kp + q_j (kp = 20, kd = 1.5 in the reference)."""
         tau = self._in(tau, (self.nu,), "tau"); q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
-        perm = None if actuator_to_joint is None else torch.as_tensor(list(actuator_to_joint), dtype=torch.int32, device=self.device)
-        if perm is not None and (perm.numel() != self.nu or sorted(perm.tolist()) != list(range(self.nu))):
-            raise ValueError("actuator_to_joint must be a permutation of range(nu)")
+        perm = self._perm(actuator_to_joint)
         out = torch.empty_like(tau)
         _lib.check(self.lib.nmpc_pd_target_action_batch(self._h, tau.shape[0], ptr(tau), ptr(perm), ptr(q), ptr(v), float(kp),
                                                         float(kd), ptr(out), stream(self.device)),
@@ -291,17 +290,13 @@ class BatchedTorqueLayer:
             raise ValueError(f"X: expected [B, N + 1, 42], got {tuple(X.shape)}")
         B, N = X.shape[0], X.shape[1] - 1
         U = self._in(U, (N, 30), "U")
-        if U.shape[0] != B:
-            raise ValueError("batch sizes differ")
+        self._batch(X, U)
         zoh = torch.as_tensor(zoh, dtype=torch.int32, device=self.device).contiguous()
         n_steps = zoh.numel()
         if zoh.dim() != 1 or (n_steps and not bool(((zoh >= 0) & (zoh < N)).all())):
             raise ValueError(f"zoh: expected node indices [n_steps] in [0, {N})")
-        perm = None if actuator_to_joint is None else torch.as_tensor(list(actuator_to_joint), dtype=torch.int32, device=self.device)
-        if perm is not None and (perm.numel() != self.nu or sorted(perm.tolist()) != list(range(self.nu))):
-            raise ValueError("actuator_to_joint must be a permutation of range(nu)")
-        if skip is not None and (skip.dtype != torch.int32 or tuple(skip.shape) != (B,) or not skip.is_contiguous() or skip.device != X.device):
-            raise ValueError(f"skip: need contiguous int32 ({B},) on {self.device}")
+        perm = self._perm(actuator_to_joint)
+        self._flags(skip, X, "skip")
         if out is None:
             out = torch.empty(B, n_steps, 12, dtype=torch.float32, device=self.device)
         elif out.dtype != torch.float32 or tuple(out.shape) != (B, n_steps, 12) or not out.is_contiguous() or out.device != X.device:

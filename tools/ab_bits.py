@@ -8,7 +8,8 @@ X, U, status, stats; then device rollouts of both plants through the Python surf
 in a row on one controller, and hashes every output of both calls.  A digest proves nothing about a path no rollout took:
 every rollout case starts a few rollouts above the height band (z0 = 0.5 > 0.45) with the height flag among the terminating
 bits, keeps rollout 0 nominal and unpushed at z0 = 0.30, counts from `failed >> 8` how many rollouts of the first call ended
-early and how many ran through, prints both and exits non-zero if either is zero.  The second call carries `failed` over
+early and how many ran through, prints both and exits non-zero if either is zero.  Last, every entry point of the torque layer
+(`torque_digests`).  The second call carries `failed` over
 (the Python surface hands every call fresh zeros), so rollouts that the first call ended enter it as already terminated
 (the row0 == 0 branch of the advance kernels), the others with a warm-started first replan."""
 import hashlib, json, os, sys
@@ -124,8 +125,56 @@ def rollout_digests():
     return out
 
 
+def torque_digests():
+    """One digest per entry point of include/nmpc_torque.h (`nmpc_plan_actions_batch` is under roll_wb_steps_labels) on the states
+    of the layer's own GPU tests, B = 257 (eight blocks and one lane), 33 and 40 (a full and a ragged block at either width);
+    `_w16`: the 16-robot instantiations, on the 30-joint tree.  Prints what is not finite: NaN bytes compare equal and say less."""
+    import numpy as np
+    import torch
+    from tests import fd_reference as fr
+    from tests.test_gpu_contact import DT, KD, KP, SOFT, Case, ground, layer
+    from tests.test_gpu_policy_rollout import HEIGHT, PERIOD, T0, World
+    from iterative_learning_nmpc_amd.torque import GroundContact
+    parts = {}
+
+    def add(name, *tensors):
+        torch.cuda.synchronize()
+        if not all(bool(torch.isfinite(t).all()) for t in tensors if t.is_floating_point()):
+            print(f"torque_{name}: an output is not finite", flush=True)
+        parts.setdefault("torque_" + name, []).extend(tensors)
+
+    def dynamics(L, m, B, seeds, tag=""):
+        for seed in seeds:
+            q, v, tau, f = fr.inputs(m, B, seed)
+            a = L.forward_dynamics(q, v, tau, f)
+            add("fd_accel" + tag, a)
+            add("fd_step" + tag, *L.step(q, v, 1e-3, 20, tau_ff=tau, q_des=q[:, m.n - m.nu:], f=f))
+            if not tag:
+                ff = L.id_torques(q, v, a, f)
+                add("id_torques", ff)
+                add("pd_torques", L.compute_pd_torques(q, v, ff, 0.5 * q, 0.5 * v, KP, KD))
+                add("pd_target_action", L.pd_target_action(ff, q, v, KP, KD, list(range(m.nu))[::-1]))
+
+    w = World()                                           # its Case is the tilted quadruped of tests/test_gpu_contact.py
+    for c in (Case(fr.quadruped(), 257, seed=257), w.c):
+        dynamics(c.L, c.m, 257, (257, 7))
+        add("foot_kinematics", *c.L.foot_kinematics(c.q, c.v))
+        add("contact_forces", c.L.contact_forces(c.q, c.v, ground(c.g)))
+        add("contact_step", *c.L.contact_step(c.q, c.v, DT, 20, tau_ff=c.tau, q_des=c.q[:, 6:], kp=KP, kd=KD, ground=ground(c.g)))
+    failed = torch.zeros(33, dtype=torch.int32, device=w.L.device)
+    add("observe", *w.L.observe(w.c.q[:33], w.c.v[:33], T0, PERIOD, w.goal[:33], s_mean=w.s_mean, s_std=w.s_std, collision_height=HEIGHT,
+                                failed=failed, step_index=2, term_mask=0xFF), failed)
+    add("policy_rollout", *w.rollout(33, 4, 5, 0xFF))
+    m = fr.random_tree(n=30, seed=13, feet=(4, 29, 29, 17))
+    L = layer(m)
+    dynamics(L, m, 40, (6,), "_w16")
+    q, v, tau, _ = fr.inputs(m, 40, 6)
+    add("contact_step_w16", *L.contact_step(q, v, DT, 20, tau_ff=tau, q_des=q, kp=KP, kd=KD, ground=GroundContact(**SOFT)))
+    return {k: sha(*v) for k, v in parts.items()}
+
+
 def digests():
-    return {"digests": {**solve_digests(), **rollout_digests()}, "rollout_counts": counts}
+    return {"digests": {**solve_digests(), **rollout_digests(), **torque_digests()}, "rollout_counts": counts}
 
 
 if __name__ == "__main__":
