@@ -28,6 +28,8 @@
 #define NMPC_H
 #include <stddef.h>
 
+#include "nmpc_torque.h"   /* nmpc_contact_cfg of nmpc_wb_rollout_set_plant */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -295,6 +297,35 @@ int nmpc_wb_rollout_batch(void *handle, int B, const nmpc_wb_rollout_cfg *cfg, c
  * this call.  A rollout with labels attached needs cfg.record_sim_steps = 1 and arguments nmpc_plan_actions_batch
  * accepts, otherwise it returns NMPC_E_ARG and launches nothing. */
 int nmpc_wb_rollout_set_actions(void *handle, void *torque_handle, const int *zoh, float kp, float kd, float *A);
+
+/* A plant for nmpc_wb_rollout_batch [decl]: the whole-body expert in closed loop on the ground-contact plant of
+ * include/nmpc_torque.h instead of "plant = plan".  While a torque handle is attached, every replan of a following rollout of
+ * this handle runs, after the solve:
+ *   1. labels  nmpc_plan_actions_batch on this replan's X, U with kp, kd (terminated rollouts skipped) -- into rows row0 .. of
+ *              the A of nmpc_wb_rollout_set_actions if one is attached (its kp, kd must equal these, its zoh is used), else
+ *              into Aw with this call's zoh (dev int [replanning_steps], as there);
+ *   2. track   nmpc_contact_track_batch: replanning_steps control steps of n_sub substeps of sim_dt / n_sub from the plant
+ *              state q, v with those rows as PD targets -- tau = tau_id + kp (q_plan - q) + kd (v_plan - v), the reference's
+ *              _compute_pd_torques (mpc.py:583-599) --, the states before each step into Qw, Vw;
+ *   3. observe nmpc_observe_rows_batch on Qw, Vw into rows row0 .. of S, at t = (replan_index replanning_steps + j) sim_dt over
+ *              nominal_period, flags into failed[b] without a stamp;
+ *   4. the advance kernel in plant mode: solver status flag, the one stamping rule of the harness, held rows for rollouts
+ *      terminated earlier, the push on the plant's v, the reference integration -- no plan rows, no plant = plan.
+ * After the last replan one flags-only nmpc_observe_batch on the final q, v with step index n_replans - 1 and the cfg's
+ * terminate_mask sees a robot that fell in the last interval (stamp n_replans).
+ * Row j of S is then the plant state BEFORE simulation step j and row j of A the PD target applied from it: the pair the
+ * reference records (RolloutMPC.py:168-258), and what nmpc_policy_rollout_batch records.  Rows come from the tree's own foot
+ * points; the velocity-tracking bit is never raised; a rollout that terminates in a replan keeps the plant state that interval
+ * left it in; a rollout that enters a call already terminated must carry its stamp, as every rollout this harness terminated
+ * does (its rows of that call are its frozen state).
+ * ground is copied at the call; zoh and the workspaces Aw [B_max][replanning_steps][12], Qw, Vw [B_max][replanning_steps][18]
+ * (dev, caller-owned) are kept as nmpc_wb_rollout_set_actions keeps its pointers.  torque_handle = NULL detaches; detached, the
+ * launches of a rollout are exactly what they are without this call.  A rollout with a plant attached needs
+ * cfg.record_sim_steps = 1, a torque handle on the same device with the 18 / 12 / 4 tree, n_sub >= 1, kp != 0, a ground
+ * nmpc_contact_step_batch accepts, zoh from one of the two calls, Qw, Vw, and Aw unless labels are attached; otherwise it returns
+ * NMPC_E_ARG and launches nothing.  nmpc_wb_rollout_cfg is unchanged. */
+int nmpc_wb_rollout_set_plant(void *handle, void *torque_handle, const nmpc_contact_cfg *ground, int n_sub, float kp, float kd,
+                              const int *zoh, float *Aw, float *Qw, float *Vw);
 
 /* Problems to leave out of the following *_batch solves of this handle: flags dev int[B_max] (or NULL: none); a problem
  * with flags[b] & mask != 0 is skipped by every kernel -- its X, U, status, stats stay as they are and it costs no

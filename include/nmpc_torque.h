@@ -156,6 +156,37 @@ int nmpc_policy_rollout_batch(void *torque, void *policy, int B, const nmpc_poli
                               int *failed,                        /* dev [B], sticky, caller zeroes; NULL allowed */
                               void *stream);
 
+/* A table of PD targets tracked on the contact plant [decl]: n_steps control steps in one launch, control step k being n_sub
+ * substeps of nmpc_contact_step_batch's law with q_des = row k of robot b's table, at A + (b * a_rows + k) * 12 (a_rows >=
+ * n_steps; 12 = n_actuated).  With the label rows of nmpc_plan_actions_batch as the table, A = (tau_id + kd v_plan) / kp + q_plan,
+ * the PD law is tau = kp (A - q) - kd v = tau_id + kp (q_plan - q) + kd (v_plan - v): the reference's _compute_pd_torques
+ * (mpc.py:592-599) on the plan's inverse-dynamics torque -- the whole-body expert driving the plant for a replanning interval.
+ * q, v [B][n_joints] are in/out; tau_ff [B][12] is a constant feed-forward torque or NULL; Q, V (both or neither) take the state
+ * BEFORE control step k at + (b * qv_rows + k) * 18 (qv_rows >= n_steps), so row 0 is the start state and row k goes with
+ * row k of A.  skip: dev int [B] or NULL; a robot with skip[b] & skip_mask != 0 is left out entirely (its q, v and its rows of
+ * Q, V stay as they are; read in stream order).  The state stays in the LDS over all n_steps * n_sub substeps; per control step
+ * the 12 targets come in and, if asked for, 36 floats of state go out.
+ * q, v, Q, V are bit for bit those of the chain of n_steps calls nmpc_contact_step_batch(.., q, v, tau_ff, A[:, k], kp, kd,
+ * q, v, NULL, NULL, NULL), NaN rows of a massless leaf included: the NaN is first written where the chain first writes it.
+ * NMPC_E_ARG (text in nmpc_torque_last_error) as nmpc_contact_step_batch, and: n_steps < 1, A NULL, a_rows < n_steps, only one
+ * of Q / V, qv_rows < n_steps, a tree that is not 18 / 12 / 4 when Q is given. */
+int nmpc_contact_track_batch(void *handle, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg *cfg, float *q, float *v,
+                             const float *tau_ff, const float *A, int a_rows, float kp, float kd, float *Q, float *V, int qv_rows,
+                             const int *skip, int skip_mask, void *stream);
+
+/* nmpc_observe_batch for the rows k = 0 .. n_rows - 1 of every robot's table of states, in one launch: row k of Q, V (at
+ * + (b * qv_rows + k) * 18) observed at t = t0 + (double)k * dt_row (the product and the sum each rounded once, as a host
+ * computes them) goes to S + (b * s_rows + k) * 44 (S may be NULL: flags only); failed[b] |= the bits of all rows, and after the
+ * rows the stamp (step_index + 1) << NMPC_ROLLOUT_TERM_SHIFT under nmpc_observe_batch's rule (a bit of term_mask is set and no
+ * stamp is present).  One thread per robot runs over its rows, so the result does not depend on scheduling.  skip as
+ * nmpc_contact_track_batch: a skipped robot's rows and flags are untouched.
+ * S and failed are bit for bit those of n_rows calls nmpc_observe_batch(.., Q[:, k], V[:, k], t0 + k dt_row, period, NULL, 0,
+ * NULL, NULL, 0, collision_height, S + 44 k, 44 s_rows, NULL, failed, step_index, term_mask, ..).
+ * NMPC_E_ARG: a tree that is not 18 / 12 / 4, a NULL Q or V, period <= 0, n_rows < 1, qv_rows < n_rows, S with s_rows < n_rows. */
+int nmpc_observe_rows_batch(void *handle, int B, int n_rows, const float *Q, const float *V, int qv_rows, double t0, double dt_row,
+                            double period, float collision_height, float *S, int s_rows, int *failed, int step_index, int term_mask,
+                            const int *skip, int skip_mask, void *stream);
+
 /* _compute_pd_torques: tau_ff [B][nu] (NULL = 0); q, v, q_plan, v_plan [B][n_joints] (their last nu
  * entries are used); tau [B][nu] (may alias tau_ff). */
 int nmpc_pd_torques_batch(void *handle, int B, const float *tau_ff, const float *q, const float *v,

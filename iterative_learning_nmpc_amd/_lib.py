@@ -43,6 +43,7 @@ SIGNATURES = {
     "nmpc_set_contact_patterns": (c_int, [c_void_p, c_int]),
     "nmpc_set_skip": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_wb_rollout_set_actions": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p]),
+    "nmpc_wb_rollout_set_plant": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_set_ipm": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float]),
     "nmpc_shift_warm_start": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "nmpc_solve_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -95,6 +96,10 @@ SIGNATURES = {
                                    c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "nmpc_policy_rollout_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_contact_track_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "nmpc_observe_rows_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "nmpc_pd_torques_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                       c_void_p, c_void_p]),
     "nmpc_pd_target_action_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,

@@ -16,11 +16,11 @@ import torch
 from .config import TERMINATE_DEFAULT
 from .parallel import learning_update, ood_threshold
 from .solver import tracking_error
-from .trajectory_io import KD, KP
 
 
 def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = None, nominal: int = 0, ood_weight: float = 5.0,
-                     terminate_mask: int = TERMINATE_DEFAULT, kp: float = KP, kd: float = KD):
+                     terminate_mask: int = TERMINATE_DEFAULT, kp: Optional[float] = None, kd: Optional[float] = None, plant=None,
+                     plant_substeps: int = 2):
     """One batch of whole-body expert rollouts of `T` seconds into `db`.
 
     mpc: a `LocomotionMPC` (batch B, command set); layer: the robot's `BatchedTorqueLayer`; db: a `DeviceDatabase` with
@@ -30,10 +30,13 @@ def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = No
     rollout on the reference's own 44-slot row and its own threshold 4.0, weights [B, K] of
     `parallel.learning_update`: 0 on invalid rollouts, `ood_weight` where err > 4.0, else 1; rows appended).  The weights of
     the appended rows go into the database with them (`db.weights`).
+    plant (a `torque.GroundContact`, None: the plant follows the plan): the expert runs in closed loop on the ground-contact
+    plant with `plant_substeps` substeps per simulation step (`open_loop_device`): the rows are then states of the plant, each
+    with the PD target the expert applied from it.  kp, kd: as `open_loop_device` (None: its defaults).
     After the call `mpc.actions`, `mpc.failed` and the returned S of the rollout are as `open_loop_device` leaves them
     (`mpc.states` keeps S)."""
     S = mpc.open_loop_device(q0, v0, T, push=push, record_sim_steps=True, terminate_mask=terminate_mask, torque_layer=layer,
-                             kp=kp, kd=kd).contiguous()
+                             kp=kp, kd=kd, plant=plant, plant_substeps=plant_substeps).contiguous()
     A = mpc.actions
     mpc.states = S
     B, K = S.shape[:2]

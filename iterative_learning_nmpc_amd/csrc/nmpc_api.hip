@@ -43,6 +43,15 @@ struct Handle {
         float kp = 0.0f, kd = 0.0f;
         float* A = nullptr;
     } labels;
+    struct {                     // nmpc_wb_rollout_set_plant: the contact plant of the whole-body rollouts (torque == nullptr: plant = plan)
+        void* torque = nullptr;
+        nmpc_contact_cfg ground{};
+        bool ground_set = false; // the caller gave a cfg (a NULL one is refused when the rollout runs)
+        int n_sub = 0;
+        float kp = 0.0f, kd = 0.0f;
+        const int* zoh = nullptr;
+        float *Aw = nullptr, *Qw = nullptr, *Vw = nullptr;
+    } plant;
     bool ws_dirty = false;   // a dense-LQ call left foreign padding in the tile workspace
     bool mp_set = false, w_set = false;
     nmpc::ModelParams mp{};
@@ -412,6 +421,19 @@ int nmpc_wb_rollout_set_actions(void* handle, void* torque_handle, const int* zo
     return NMPC_OK;
 }
 
+int nmpc_wb_rollout_set_plant(void* handle, void* torque_handle, const nmpc_contact_cfg* ground, int n_sub, float kp, float kd,
+                              const int* zoh, float* Aw, float* Qw, float* Vw) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    h->plant = {};
+    if (torque_handle) {
+        auto& p = h->plant;
+        p.torque = torque_handle; p.n_sub = n_sub; p.kp = kp; p.kd = kd; p.zoh = zoh; p.Aw = Aw; p.Qw = Qw; p.Vw = Vw;
+        if (ground) { p.ground = *ground; p.ground_set = true; }
+    }
+    return NMPC_OK;
+}
+
 int nmpc_set_ipm(void* handle, float mu0, float sigma, float s_min, float gamma, float tau_min,
                  float merit_rho) {
     Handle* h = static_cast<Handle*>(handle);
@@ -583,9 +605,24 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
         if (const char* why = nmpc_torque::plan_actions_refusal(lab.torque, cfg->replanning_steps, lab.zoh, lab.kp, h->device))
             return fail(h, NMPC_E_ARG, std::string("action labels: ") + why);
     }
+    const auto& pl = h->plant;
+    const int* const plant_zoh = lab.A ? lab.zoh : pl.zoh;         // the labels' hold table serves both
+    float* const targets = lab.A ? lab.A : pl.Aw;                  // where the PD targets of a replan are written and read
+    if (pl.torque) {
+        if (!cfg->record_sim_steps) return fail(h, NMPC_E_ARG, "a plant records rows per simulation step: record_sim_steps must be 1");
+        if (const char* why = nmpc_torque::plan_actions_refusal(pl.torque, cfg->replanning_steps, plant_zoh, pl.kp, h->device))
+            return fail(h, NMPC_E_ARG, std::string("plant: ") + why);
+        if (const char* why = nmpc_torque::contact_track_refusal(pl.torque, pl.ground_set ? &pl.ground : nullptr, pl.n_sub,
+                                                                 (float)(cfg->sim_dt / (pl.n_sub > 0 ? pl.n_sub : 1)), h->device))
+            return fail(h, NMPC_E_ARG, std::string("plant: ") + why);
+        if (lab.A && (lab.kp != pl.kp || lab.kd != pl.kd))
+            return fail(h, NMPC_E_ARG, "plant: the attached action labels must be recorded with the plant's gains kp, kd");
+        if (!targets || !pl.Qw || !pl.Vw) return fail(h, NMPC_E_ARG, "plant: the workspaces Qw, Vw and (without attached labels) Aw are needed");
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };       // every array starts on a 16 B boundary (launch_wb checks)
     nmpc::wb::WbRolloutArgs r{};
+    r.plant = pl.torque ? 1 : 0;
     r.yref = h->roll;
     r.yref_e = r.yref + up4((size_t)h->dims.B_max * N * h->ny);
     r.params = r.yref_e + up4((size_t)h->dims.B_max * h->nye);
@@ -599,23 +636,46 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
     nmpc::wb::WbArgs w = wb_args(h);
     w.x0 = r.x0; w.status = status;
     int last_node = cfg->last_node;
-    return run_rollout(h, B, cfg, st, r, w, nmpc::wb::nmpc_wb_rollout_prepare_kernel, launch_wb, nmpc::wb::nmpc_wb_rollout_advance_kernel,
-                       [&](int i) {          // warm_start_solver(i_node): start_node = i_node - last_node (solver.py:304-309)
-                           const int shift = nodes[i] - last_node;
-                           r.node = last_node = nodes[i];
-                           return shift;
-                       },
-                       [&](int) {            // the labels of this replan's plan, beside the rows the advance kernel is about to record
-                           if (!lab.A) return (int)NMPC_OK;
-                           const int steps = cfg->replanning_steps;
-                           const int lrc = nmpc_plan_actions_batch(lab.torque, B, steps, N, X, U, lab.zoh, r.dt_nodes, r.sim_dt, lab.kp, lab.kd, nullptr,
-                                                                   r.term_mask ? failed : nullptr, r.term_mask, lab.A + (size_t)r.row0 * 12, r.n_rows, st);
-                           if (lrc) return fail(h, lrc, std::string("nmpc_plan_actions_batch: ") + nmpc_torque_last_error(lab.torque));
-                           if (r.term_mask)
-                               hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_hold_actions_kernel, dim3((unsigned)(((size_t)B * steps * 12 + 255) / 256)),
-                                                  dim3(256), 0, st, B, r.n_rows, r.row0, steps, r.term_mask, failed, lab.A);
-                           return (int)NMPC_OK;
-                       });
+    const int rc = run_rollout(
+        h, B, cfg, st, r, w, nmpc::wb::nmpc_wb_rollout_prepare_kernel, launch_wb, nmpc::wb::nmpc_wb_rollout_advance_kernel,
+        [&](int i) {          // warm_start_solver(i_node): start_node = i_node - last_node (solver.py:304-309)
+            const int shift = nodes[i] - last_node;
+            r.node = last_node = nodes[i];
+            return shift;
+        },
+        [&](int i) {          // the labels of this replan's plan, beside the rows the advance kernel is about to record
+            if (!lab.A && !pl.torque) return (int)NMPC_OK;
+            const int steps = cfg->replanning_steps;
+            const int* skip = r.term_mask ? failed : nullptr;
+            void* torque = lab.A ? lab.torque : pl.torque;
+            // labels attached: rows row0 .. of the caller's table of n_rows rows per rollout; the plant alone: its workspace of one replan
+            float* rows = lab.A ? lab.A + (size_t)r.row0 * 12 : pl.Aw;
+            const int a_rows = lab.A ? r.n_rows : steps;
+            const int lrc = nmpc_plan_actions_batch(torque, B, steps, N, X, U, plant_zoh, r.dt_nodes, r.sim_dt, lab.A ? lab.kp : pl.kp,
+                                                    lab.A ? lab.kd : pl.kd, nullptr, skip, r.term_mask, rows, a_rows, st);
+            if (lrc) return fail(h, lrc, std::string("nmpc_plan_actions_batch: ") + nmpc_torque_last_error(torque));
+            if (lab.A && r.term_mask)
+                hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_hold_actions_kernel, dim3((unsigned)(((size_t)B * steps * 12 + 255) / 256)),
+                                   dim3(256), 0, st, B, r.n_rows, r.row0, steps, r.term_mask, failed, lab.A);
+            if (!pl.torque) return (int)NMPC_OK;
+            // the expert drives the plant: the label rows as PD targets of `steps` simulation steps, the states before each step
+            // into the workspace, and those states as rows row0 .. of S with their flags (no stamp: the advance kernel stamps)
+            const int trc = nmpc_contact_track_batch(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
+                                                     rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, st);
+            if (trc) return fail(h, trc, std::string("nmpc_contact_track_batch: ") + nmpc_torque_last_error(pl.torque));
+            const int orc = nmpc_observe_rows_batch(pl.torque, B, steps, pl.Qw, pl.Vw, steps, (double)(i * steps) * cfg->sim_dt, cfg->sim_dt,
+                                                    (double)cfg->nominal_period, cfg->collision_height, S + (size_t)r.row0 * 44, r.n_rows,
+                                                    failed, i, 0, skip, r.term_mask, st);
+            if (orc) return fail(h, orc, std::string("nmpc_observe_rows_batch: ") + nmpc_torque_last_error(pl.torque));
+            return (int)NMPC_OK;
+        });
+    if (rc || !pl.torque) return rc;
+    // the state the last interval left: a robot that fell in it is flagged and stamped with the last replan
+    const int frc = nmpc_observe_batch(pl.torque, B, q, v, (double)(cfg->n_replans * cfg->replanning_steps) * cfg->sim_dt,
+                                       (double)cfg->nominal_period, nullptr, 0, nullptr, nullptr, 0, cfg->collision_height, nullptr, 0,
+                                       nullptr, failed, cfg->n_replans - 1, cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK, st);
+    if (frc) return fail(h, frc, std::string("nmpc_observe_batch: ") + nmpc_torque_last_error(pl.torque));
+    return NMPC_OK;
 }
 
 int nmpc_debug_set_buffer(void* handle, float* dev_buffer) {

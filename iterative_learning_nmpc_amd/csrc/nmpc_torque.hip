@@ -12,7 +12,9 @@
 // The other direction -- accelerations from torques and given contact forces, and a PD-driven integration step around them --
 // is nmpc_torque_fd.hip.inc, included below; the declared ground-contact law, the foot kinematics it needs and the plant step
 // that evaluates it inside that recursion are nmpc_torque_contact.hip.inc; the observation of a plant state for a policy in the
-// loop is nmpc_torque_policy.hip.inc, and the loop itself (nmpc_policy_rollout_batch) is host code at the end of this file.
+// loop is nmpc_torque_policy.hip.inc, and the loop itself (nmpc_policy_rollout_batch) is host code at the end of this file;
+// a table of PD targets tracked on the plant in one launch, and the rows of the states it ran through, are
+// nmpc_torque_track.hip.inc.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -346,6 +348,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_fd.hip.inc"
 #include "nmpc_torque_contact.hip.inc"
 #include "nmpc_torque_policy.hip.inc"
+#include "nmpc_torque_track.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -415,6 +418,10 @@ int allocate(Torque* t) {
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width)),
                                             hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
+    // the tracked chain of contact steps: the step's slice and width
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_track_kernel, t->ct_width)),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
     return NMPC_OK;
 }
 
@@ -470,6 +477,17 @@ const char* nmpc_torque::plan_actions_refusal(void* handle, int n_steps, const i
     if (n_steps < 1) return "n_steps must be at least 1";
     if (!zoh) return "zoh is NULL";
     if (!(kp != 0.0f)) return "kp must not be zero";
+    if (device >= 0 && t->device != device) return "the torque handle lives on another device";
+    return nullptr;
+}
+
+const char* nmpc_torque::contact_track_refusal(void* handle, const nmpc_contact_cfg* ground, int n_sub, float dt, int device) {
+    const Torque* t = static_cast<const Torque*>(handle);
+    if (!t) return "null torque handle";
+    if (!whole_body_tree(t->host))
+        return "the rows of a tracked plan need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4";
+    if (const char* why = step_refusal(n_sub, dt)) return why;
+    if (const char* why = contact_cfg_refusal(ground)) return why;
     if (device >= 0 && t->device != device) return "the torque handle lives on another device";
     return nullptr;
 }
@@ -621,6 +639,52 @@ int nmpc_observe_batch(void* handle, int B, const float* q, const float* v, doub
     a.q = q; a.v = v; a.goal = goal; a.s_mean = s_mean; a.s_std = s_std; a.S = S; a.X = X; a.failed = failed;
     const size_t lds = (S || X) ? ob_lds_bytes(h->host.n) : 0;      // the flags alone run no kinematics and ask for no slice
     hipLaunchKernelGGL(observe_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream), h->dev, a);
+    return launched(h);
+}
+
+int nmpc_contact_track_batch(void* handle, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v,
+                             const float* tau_ff, const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows,
+                             const int* skip, int skip_mask, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !v) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v");
+    if (n_steps < 1) return fail(t, NMPC_E_ARG, "n_steps must be at least 1");
+    if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
+    if (!A) return fail(t, NMPC_E_ARG, "A is NULL");
+    if (a_rows < n_steps) return fail(t, NMPC_E_ARG, "a_rows must be at least n_steps");
+    if (!Q != !V) return fail(t, NMPC_E_ARG, "Q and V come together or not at all");
+    if (Q && qv_rows < n_steps) return fail(t, NMPC_E_ARG, "qv_rows must be at least n_steps");
+    if (Q && !whole_body_tree(t->host))
+        return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
+    NMPC_ENTER(t, t->device);
+    TrackArgs p{};
+    p.B = B; p.n_steps = n_steps; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
+    p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+    p.tau = tau_ff; p.A = A; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v; p.Q = Q; p.V = V;
+    const int w = t->ct_width;
+    return launch_step(t, KERNEL_AT_WIDTH(contact_track_kernel, w), w, ct_lds_bytes(t->host.n, w), p, stream);
+}
+
+int nmpc_observe_rows_batch(void* handle, int B, int n_rows, const float* Q, const float* V, int qv_rows, double t0, double dt_row,
+                            double period, float collision_height, float* S, int s_rows, int* failed, int step_index, int term_mask,
+                            const int* skip, int skip_mask, void* stream) {
+    Torque* h = static_cast<Torque*>(handle);
+    if (!h) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (const char* why = observe_refusal(h, B, Q, V, period, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr)) return fail(h, NMPC_E_ARG, why);
+    if (n_rows < 1) return fail(h, NMPC_E_ARG, "n_rows must be at least 1");
+    if (qv_rows < n_rows) return fail(h, NMPC_E_ARG, "qv_rows must be at least n_rows");
+    if (S && s_rows < n_rows) return fail(h, NMPC_E_ARG, "s_rows must be at least n_rows");
+    NMPC_ENTER(h, h->device);
+    ObserveRowsArgs a{};
+    a.B = B; a.n_rows = n_rows; a.qv_rows = qv_rows; a.s_rows = s_rows; a.step_index = step_index; a.term_mask = term_mask;
+    a.skip_mask = skip ? skip_mask : 0;
+    a.t0 = t0; a.dt_row = dt_row; a.period = period; a.collision_height = collision_height;
+    a.Q = Q; a.V = V; a.S = S; a.failed = failed; a.skip = a.skip_mask ? skip : nullptr;
+    const size_t lds = S ? ob_lds_bytes(h->host.n) : 0;      // the flags alone run no kinematics and ask for no slice
+    hipLaunchKernelGGL(observe_rows_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream), h->dev, a);
     return launched(h);
 }
 

@@ -1,11 +1,18 @@
-// nmpc_torque_plan.hpp -- the one thing the rollout host code (nmpc_api.hip) asks of the torque layer (nmpc_torque.hip) beyond
-// its C-ABI: whether a label launch with these arguments would be refused, so that a rollout refuses before it launches anything.
+// nmpc_torque_plan.hpp -- what the rollout host code (nmpc_api.hip) asks of the torque layer (nmpc_torque.hip) beyond its
+// C-ABI: whether a label launch, or the launches of an attached plant, would be refused with these arguments, so that a rollout
+// refuses before it launches anything.
 #pragma once
+
+#include "../../include/nmpc_torque.h"
 
 namespace nmpc_torque {
 
 // nullptr if nmpc_plan_actions_batch accepts (handle, n_steps, zoh, kp) and the handle lives on `device` (-1: any device);
 // otherwise the text nmpc_torque_last_error would give
 const char* plan_actions_refusal(void* handle, int n_steps, const int* zoh, float kp, int device);
+
+// nullptr if nmpc_contact_track_batch with rows Q, V and nmpc_observe_rows_batch accept (handle, ground, n_sub, dt) and the handle
+// lives on `device` (-1: any device); otherwise the text nmpc_torque_last_error would give
+const char* contact_track_refusal(void* handle, const nmpc_contact_cfg* ground, int n_sub, float dt, int device);
 
 }  // namespace nmpc_torque

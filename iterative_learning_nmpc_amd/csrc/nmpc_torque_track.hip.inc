@@ -1,0 +1,183 @@
+// nmpc_torque_track.hip.inc -- a table of PD targets tracked on the ground-contact plant, and the observation of the states it
+// ran through (nmpc_contact_track_batch, nmpc_observe_rows_batch of include/nmpc_torque.h); included by nmpc_torque.hip inside
+// namespace nmpc_torque, after nmpc_torque_policy.hip.inc.
+//
+// The whole-body expert on the declared plant (DESIGN.md 8h): the label row of a plan, A = (tau_id + kd v_plan) / kp + q_plan,
+// handed to the contact step as q_des gives tau = tau_id + kp (q_plan - q) + kd (v_plan - v), the reference's
+// _compute_pd_torques on the plan's inverse-dynamics torque (mpc.py:583-599).  So a replanning interval is a chain of contact
+// steps, one per row of the label table; contact_track_kernel runs that chain in one launch with the robot's state resident in
+// the LDS, observe_rows_kernel turns the states it went through into the 44-slot rows and the fall predicates.
+// Both are held bit for bit to the chain of public calls they replace (tests/test_gpu_contact_track.py).
+#pragma once
+
+struct TrackArgs {
+    int B, n_steps, n_sub, a_rows, qv_rows, skip_mask;
+    float dt, kp, kd;
+    ContactCfg c;
+    const float *tau, *A;                                 // tau: tau_ff [B][nu] or nullptr; A: robot b's targets from A + b * a_rows * nu
+    const int* skip;                                      // nullptr: nobody is left out
+    float *q, *v;                                         // in/out
+    float *Q, *V;                                         // both or neither: the state before control step k at + (b * qv_rows + k) * n
+};
+
+// contact_step_kernel's substep, n_steps * n_sub times on the state in the slice: per control step the state goes out to row k
+// of Q, V (if given), the PD target becomes row k of the robot's table, and n_sub substeps follow.  A control step whose
+// recursion met an unsound pivot leaves NaN in the whole state, as the contact step writes it and the next call of a chain
+// reads it back, so the NaN appears in the row of Q, V the chain would first have it in.
+// The substep is a copy of contact_step_kernel's text without f_out / tau_out (DESIGN.md 8h): that kernel and fd_kernel keep
+// theirs, as their comments say, and a driver shared with them would have to be proven bit-neutral for both.
+template <int W>
+__global__ __launch_bounds__(W) void contact_track_kernel(const Model* __restrict__ mp, const TrackArgs p) {
+    extern __shared__ float body[];                       // [joint][CT_SLOTS][W]
+    const Model& m = *mp;
+    const int n = m.n, nu = m.nu, base = n - nu;
+    ContactCfg* cfg = reinterpret_cast<ContactCfg*>(body + n * CT_SLOTS * W);
+    if (threadIdx.x == 0) *cfg = p.c;
+    __syncthreads();
+    const int b = blockIdx.x * W + threadIdx.x;
+    if (b >= p.B) return;
+    if (p.skip && (p.skip[b] & p.skip_mask)) return;
+    const Slice<CT_SLOTS, W> at;
+    float* qb = p.q + (size_t)b * n;
+    float* vb = p.v + (size_t)b * n;
+    const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;
+    const float nan = __builtin_nanf("");
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = 0; i < n; ++i) { at(i, FD_Q) = qb[i]; at(i, FD_Q + 1) = vb[i]; }
+    for (int k = 0; k < p.n_steps; ++k) {
+        if (p.Q) {
+            float* Qk = p.Q + ((size_t)b * p.qv_rows + k) * n;
+            float* Vk = p.V + ((size_t)b * p.qv_rows + k) * n;
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < n; ++i) { Qk[i] = at(i, FD_Q); Vk[i] = at(i, FD_Q + 1); }
+        }
+        const float* db = p.A + ((size_t)b * p.a_rows + k) * nu;
+        bool sound = true;
+        for (int s = 0; s < p.n_sub; ++s) {
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < n; ++i) {
+                float t = 0.0f;
+                if (i >= base) {
+                    t = tb ? tb[i - base] : 0.0f;
+                    t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
+                    { const float lim = cfg->tau_max; if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t); }   // a NaN stays NaN
+                }
+                at(i, FD_Q + 2) = t;
+            }
+            sound = fd_accel_body<W, CT_SLOTS>(m, GroundForces{cfg, nullptr}) && sound;
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < n; ++i) {
+                const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);
+                at(i, FD_Q + 1) = v;
+                at(i, FD_Q) = at(i, FD_Q) + p.dt * v;
+            }
+        }
+        if (!sound) {
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < n; ++i) { at(i, FD_Q) = nan; at(i, FD_Q + 1) = nan; }
+        }
+    }
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = 0; i < n; ++i) { qb[i] = at(i, FD_Q); vb[i] = at(i, FD_Q + 1); }
+}
+
+// ---- the rows of a table of states --------------------------------------------------------------------------------------------
+struct ObserveRowsArgs {
+    int B, n_rows, qv_rows, s_rows, step_index, term_mask, skip_mask;
+    double t0, dt_row, period;
+    float collision_height;
+    const float *Q, *V;                                   // row k of robot b at + (b * qv_rows + k) * 18
+    float* S;                                             // row k of robot b at + (b * s_rows + k) * 44; may be nullptr
+    int* failed;                                          // may be nullptr
+    const int* skip;
+};
+
+// the time of row k, in the two roundings of the host expression t0 + k * dt_row
+__device__ inline double row_time(double t0, int k, double dt_row) {
+#pragma clang fp contract(off)
+    const double d = (double)k * dt_row;
+    return t0 + d;
+}
+
+// observe_kernel's row and flags for every row of the robot's table, one thread per robot: the flags of all rows are gathered
+// in a register and the stamp is set once after them, which is what n_rows calls with one step index leave (the first call
+// that sees a terminating bit stamps, the later ones find the stamp).  The body is observe_kernel's text without the policy
+// input; that kernel keeps its own (nmpc_torque_policy.hip.inc).
+__global__ __launch_bounds__(TPB) void observe_rows_kernel(const Model* __restrict__ mp, const ObserveRowsArgs a) {
+    const Model& m = *mp;
+    const int b = blockIdx.x * TPB + threadIdx.x;
+    if (b >= a.B) return;
+    if (a.skip && (a.skip[b] & a.skip_mask)) return;
+    const int n = m.n;
+    const Slice<OB_SLOTS, TPB> at;
+    int flags = a.failed ? a.failed[b] : 0;
+    for (int r = 0; r < a.n_rows; ++r) {
+        const float* qb = a.Q + ((size_t)b * a.qv_rows + r) * n;
+        const float* vb = a.V + ((size_t)b * a.qv_rows + r) * n;
+        if (a.S) {
+            float* Sb = a.S + ((size_t)b * a.s_rows + r) * OB_STATE;
+            auto put = [&](int j, float s) { Sb[j] = s; };
+            // the outward pass of foot_kernel, positions only
+            for (int i = 0; i < n; ++i) {
+                M3 R; V3 p;
+                joint_transform(m, i, qb[i], R, p);
+                const int par = m.parent[i];
+                V3 pw = p;
+                M3 Rw = R;
+                if (par >= 0) {
+                    M3 Rp;
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, OB_RW + k);
+                    Rw = mul(Rp, R);
+                    pw = at.get3(par, OB_PW) + mul(Rp, p);
+                }
+#pragma unroll
+                for (int k = 0; k < 9; ++k) at(i, OB_RW + k) = Rw.m[k];
+                at.put3(i, OB_PW, pw);
+            }
+            // the row: [phase, v_lin 3, body rates 3, joint rates 12, z, quaternion wxyz (w >= 0) 4, joints 12, base_wrt_feet 8]
+            put(0, (float)nmpc::recorded_phase(row_time(a.t0, r, a.dt_row), a.period));
+            {   // E(theta) thetadot (wb_body_rates) and the quaternion of `record`, in fp64 from the fp32 state
+                const double yaw = qb[3], pitch = qb[4], roll = qb[5], dyaw = vb[3], dpitch = vb[4], droll = vb[5];
+                const double sy = sin(pitch), cy = cos(pitch), sx = sin(roll), cx = cos(roll);
+                put(4, (float)(-sy * dyaw + droll));
+                put(5, (float)(cy * sx * dyaw + cx * dpitch));
+                put(6, (float)(cx * cy * dyaw - sx * dpitch));
+                const double hy = cos(0.5 * yaw), ky = sin(0.5 * yaw), hp = cos(0.5 * pitch), kp = sin(0.5 * pitch), hr = cos(0.5 * roll), kr = sin(0.5 * roll);
+                double qw = hy * hp * hr + ky * kp * kr, qx = hy * hp * kr - ky * kp * hr, qy = hy * kp * hr + ky * hp * kr, qz = ky * hp * hr - hy * kp * kr;
+                if (qw < 0.0) { qw = -qw; qx = -qx; qy = -qy; qz = -qz; }
+                put(20, (float)qw); put(21, (float)qx); put(22, (float)qy); put(23, (float)qz);
+            }
+            put(19, qb[2]);
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < 3; ++i) put(1 + i, vb[i]);
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < 12; ++i) { put(7 + i, vb[6 + i]); put(24 + i, qb[6 + i]); }
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int k = 0; k < 4; ++k) {
+                const int j = m.foot_joint[k];
+                M3 Rw;
+#pragma unroll
+                for (int e = 0; e < 9; ++e) Rw.m[e] = at(j, OB_RW + e);
+                const V3 p = at.get3(j, OB_PW) + mul(Rw, v3(m.foot_offset[k]));
+                put(36 + 2 * k, qb[0] - p.x); put(37 + 2 * k, qb[1] - p.y);
+            }
+        }
+        if (a.failed) {
+            // the command handed to the predicates is the state's own velocity: the velocity-tracking bit is never raised here
+            const double own[2] = {(double)vb[0], (double)vb[1]};
+            flags |= nmpc::unsafe_state_flags(qb[5], qb[4], qb[2], vb[0], vb[1], own, a.collision_height);
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int f = 0; f < 4; ++f) {       // joint limits in degrees, as observe_kernel
+                const float dg = 57.29577951308232f;
+                const float hip = qb[6 + 3 * f] * dg, th = qb[7 + 3 * f] * dg, kn = qb[8 + 3 * f] * dg;
+                if (!(hip >= -70.0f && hip <= 70.0f) || !(th >= 25.0f && th <= 115.0f) || !(kn >= -155.0f && kn <= -60.0f))
+                    flags |= NMPC_ROLLOUT_FLAG_JOINT_LIMIT;
+            }
+        }
+    }
+    if (a.failed) {
+        if ((flags & a.term_mask) && !(flags >> NMPC_ROLLOUT_TERM_SHIFT)) flags |= (a.step_index + 1) << NMPC_ROLLOUT_TERM_SHIFT;   // commit_flags' stamp
+        a.failed[b] = flags;
+    }
+}

@@ -14,7 +14,9 @@
 //                                    reference's 44-slot layout [phase, v_mj(18), q_mj[2:](17), base_wrt_feet(8)]
 //                                    (DAgger/utils/RolloutMPC.py:221; MuJoCo layout: dynamics.py:75-98), unsafe-state flags
 //                                    incl. joint limits (Rollout_combined_controller.py:367-431), early termination, base push,
-//                                    reference integration (mpc.py:204-208)
+//                                    reference integration (mpc.py:204-208); with a contact plant attached
+//                                    (nmpc_wb_rollout_set_plant) the torque layer has moved the plant and written the rows, and
+//                                    the kernel only keeps the flags, applies the push and integrates the reference
 // What the two plants share -- the arguments of a rollout step, the fp64 base references, the contact window, the unsafe-state
 // predicates, the bookkeeping of failed[b], the push and the reference integration -- is in nmpc_rollout_common.hpp; here are
 // forward kinematics, momentum, the 44-slot row, the joint limits and the label hold kernel.  Included by nmpc_api.hip.
@@ -35,6 +37,8 @@ struct WbRolloutArgs : RolloutCommon {
     float *q, *v;                         // dev [B][18] plant state, Euler layout (q = r, yaw, pitch, roll, joints; v = qdot)
     const float* joint_ref;               // dev [12]
     float* x0;                            // dev initial states of the solve (momentum slots included)
+    int plant;                            // 0: plant = plan; 1: the contact plant has moved q, v and written this replan's rows and
+                                          // flags (nmpc_wb_rollout_set_plant), the kernel keeps the books only
 };
 
 // foot positions in the world, [4][3], and the centroidal momentum of (q, v), in fp64 like the host helpers
@@ -180,7 +184,10 @@ __global__ void nmpc_wb_rollout_advance_kernel(const WbRolloutArgs a) {
                 flags |= NMPC_ROLLOUT_FLAG_JOINT_LIMIT;
         }
     };
-    if (flags & a.term_mask) {             // terminated in an earlier replan: frozen (hold_last_row)
+    // terminated in an earlier replan; in plant mode this replan's observation has already raised its flags, so there only a
+    // stamp tells an earlier termination from one of this replan
+    const bool earlier = a.plant ? (flags & a.term_mask) && (flags >> NMPC_ROLLOUT_TERM_SHIFT) : (flags & a.term_mask) != 0;
+    if (earlier) {                         // frozen (hold_last_row)
         if (a.row0 > 0) {
             hold_last_row(rows, 44, rows_per_replan);
         } else {                           // a call that continues an already terminated rollout: its frozen state
@@ -193,6 +200,12 @@ __global__ void nmpc_wb_rollout_advance_kernel(const WbRolloutArgs a) {
         return;
     }
     flags |= solver_status_flag(a.status[b]);
+    if (a.plant) {                         // the rows are written and the plant has moved: the books, the push and the reference
+        if (commit_flags(a, b, flags)) return;
+        apply_push(vf, a, b, a.mp.mass);
+        integrate_base_reference(a, b);
+        return;
+    }
     // the plan at time t of the horizon (nmpc_wb_plan.hpp: the Hermite segments of mpc.py:388-414, shared with the label kernel)
     auto plan_at = [&](double t, double (&q)[18], double (&v)[18]) { wb_plan_at(Xb, Ub, N, a.dt_nodes, t, q, v); };
     double q[18], v[18];

@@ -214,7 +214,8 @@ class LocomotionMPC:
 
     def open_loop_device(self, q0: np.ndarray, v0: np.ndarray, trajectory_time: float, push: Optional[dict] = None,
                          record_sim_steps: bool = True, terminate_mask: int = TERMINATE_DEFAULT,
-                         collision_height: float = COLLISION_HEIGHT, torque_layer=None, kp: float = KP, kd: float = KD):
+                         collision_height: float = COLLISION_HEIGHT, torque_layer=None, kp: Optional[float] = None,
+                         kd: Optional[float] = None, plant=None, plant_substeps: int = 2):
         """`open_loop` with the whole rollout on the device (nmpc_wb_rollout_batch): per replan the problem is assembled from
         the plant state by a kernel, solved with the warm-start shift folded in, and the up-sampled plan is followed for
         `replanning_steps` simulation steps -- one host call, no round trip per replan, the whole batch at once.
@@ -225,7 +226,14 @@ class LocomotionMPC:
         `self.q_final` / `self.v_final` the plant state.
         torque_layer (a `BatchedTorqueLayer` of the robot; needs rows per simulation step): the expert's action labels are
         recorded beside the rows -- `self.actions` [B, K, 12] (device), row j = (tau + kd v_j) / kp + q_j of the state in S's
-        row j, tau the inverse-dynamics torque of the plan that row was taken from (`references.plan_rows`)."""
+        row j, tau the inverse-dynamics torque of the plan that row was taken from (`references.plan_rows`); kp, kd default to
+        the recorder's KP, KD.
+        plant (a `torque.GroundContact`; needs torque_layer and rows per simulation step): the expert runs in closed loop on
+        the declared ground-contact plant instead of following its plan (nmpc_wb_rollout_set_plant) -- between replans the
+        robot is driven by tau_id + Kp (q_plan - q) + Kd (v_plan - v) (mpc.py:583-599) through `plant_substeps` substeps of
+        sim_dt / plant_substeps per simulation step, and every replan starts from the state the plant is in.  kp, kd then
+        default to the controller's Kp, Kd.  Row j of S is the plant state BEFORE simulation step j and `self.actions` row j
+        the PD target applied from it (RolloutMPC.py:168-258); a robot that falls in the last interval is flagged too."""
         import torch
         fs = self.solver
         s = fs._device_solver()
@@ -242,12 +250,18 @@ class LocomotionMPC:
             self._X_dev = torch.zeros(B, N + 1, 42, dtype=torch.float32, device=dev)
             self._U_dev = torch.zeros(B, N, 30, dtype=torch.float32, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
+        if plant is not None and torque_layer is None:
+            raise ValueError("plant: the contact plant lives in the torque layer, give torque_layer")
+        kp = (self.Kp if plant is not None else KP) if kp is None else kp
+        kd = (self.Kd if plant is not None else KD) if kd is None else kd
         A = None
         if torque_layer is not None:
             rows = n_replans * (self.replanning_steps if record_sim_steps else 1)
             A = torch.zeros(B, rows, 12, dtype=torch.float32, device=dev)
             s.set_rollout_actions(torque_layer, s.to_device(self.id_repeat[:self.replanning_steps], torch.int32), A, kp, kd)
         try:
+            if plant is not None:
+                s.set_rollout_plant(torque_layer, plant, plant_substeps, kp, kd)
             S, failed = s.wb_rollout(
                 s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
                 nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref), by_rollout(push["force"]) if push else None,
@@ -262,6 +276,8 @@ class LocomotionMPC:
                 nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
                 collision_height=float(collision_height))
         finally:
+            if plant is not None:
+                s.set_rollout_plant(None)
             if torque_layer is not None:
                 s.set_rollout_actions(None)
         # bookkeeping as open_loop leaves it

@@ -127,6 +127,38 @@ class BatchedNmpcSolver:
         _lib.check(self.lib.nmpc_wb_rollout_set_actions(self._h, layer._h, ptr(zoh), float(kp), float(kd), ptr(A)),
                    self._h, "nmpc_wb_rollout_set_actions")
 
+    def set_rollout_plant(self, layer, ground=None, n_sub: int = 2, kp: float = KP, kd: float = KD,
+                          zoh: Optional[torch.Tensor] = None):
+        """nmpc_wb_rollout_set_plant: while a plant is attached, `wb_rollout` runs the expert in closed loop on the ground-contact
+        plant of `layer` (a `BatchedTorqueLayer` of the robot) instead of following its plan: per replan the labels of the plan
+        (`plan_actions`), `contact_track` over the interval with those rows as PD targets (n_sub substeps of sim_dt / n_sub per
+        simulation step), `observe_rows` into S.  Row j of S is then the plant state before simulation step j, row j of the
+        actions of `set_rollout_actions` (same kp, kd) the PD target applied from it.  ground: a `torque.GroundContact`; zoh
+        int32 [replanning_steps] on the device, the held node of each step (not needed while `set_rollout_actions` is attached,
+        whose zoh is used).  `set_rollout_plant(None)` detaches.  The workspaces of the call ([batch_max, replanning_steps, 12 /
+        18 / 18]) are allocated here and kept alive, with layer and zoh, while the plant is attached."""
+        if layer is None:
+            self._plant = None
+            _lib.check(self.lib.nmpc_wb_rollout_set_plant(self._h, None, None, 0, 0.0, 0.0, None, None, None, None), self._h,
+                       "nmpc_wb_rollout_set_plant")
+            return
+        if zoh is not None:
+            if not isinstance(zoh, torch.Tensor) or zoh.dim() != 1:
+                raise ValueError("zoh: need an int32 tensor [replanning_steps] on the GPU")
+            self._chk(zoh, (zoh.shape[0],), "zoh", torch.int32)
+            if not bool(((zoh >= 0) & (zoh < self.n_nodes)).all()):
+                raise ValueError(f"zoh: node indices must lie in [0, {self.n_nodes})")
+        labels = getattr(self, "_labels", None)
+        steps = zoh.shape[0] if zoh is not None else (labels[1].shape[0] if labels is not None else 0)
+        if steps < 1:
+            raise ValueError("zoh: the plant needs the held node of each step, here or from set_rollout_actions")
+        Aw = torch.zeros(self.batch_max, steps, 12, dtype=torch.float32, device=self.device)
+        Qw, Vw = (torch.zeros(self.batch_max, steps, 18, dtype=torch.float32, device=self.device) for _ in range(2))
+        cfg = ground.cfg() if ground is not None else None
+        self._plant = (layer, zoh, Aw, Qw, Vw)
+        _lib.check(self.lib.nmpc_wb_rollout_set_plant(self._h, layer._h, ctypes.byref(cfg) if cfg is not None else None, int(n_sub), float(kp),
+                                                      float(kd), ptr(zoh), ptr(Aw), ptr(Qw), ptr(Vw)), self._h, "nmpc_wb_rollout_set_plant")
+
     def set_ipm(self, mu0=10.0, sigma=0.2, s_min=1.0, gamma=0.995, tau_min=0.1, merit_rho=1e3):
         _lib.check(self.lib.nmpc_set_ipm(self._h, mu0, sigma, s_min, gamma, tau_min, merit_rho),
                    self._h, "nmpc_set_ipm")
@@ -249,6 +281,8 @@ class BatchedNmpcSolver:
             self._chk(A, (B, S.shape[1], 12), "A (set_rollout_actions)")
             if c.record_sim_steps:
                 self._chk(zoh, (c.replanning_steps,), "zoh (set_rollout_actions)", torch.int32)
+        if getattr(self, "_plant", None) is not None and c.record_sim_steps:      # the plant's workspaces hold one replanning interval
+            self._chk(self._plant[2], (self.batch_max, c.replanning_steps, 12), "workspace (set_rollout_plant: zoh has another length)")
         nodes = (ctypes.c_int * c.n_replans)(*nodes)
         _lib.check(self.lib.nmpc_wb_rollout_batch(
             self._h, B, ctypes.byref(c), ptr(gait), ptr(peaks), ctypes.cast(nodes, ctypes.c_void_p), ptr(q), ptr(v),

@@ -257,6 +257,85 @@ class BatchedTorqueLayer:
                    self._h, "nmpc_policy_rollout_batch", "torque")
         return q, v, S, A, failed
 
+    def _state_io(self, t, name):
+        """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != self.n or not t.is_contiguous() \
+                or t.device != self.device:
+            raise ValueError(f"{name}: need a contiguous float32 [B, {self.n}] tensor on {self.device} (it is updated in place)")
+        return t
+
+    def _rows(self, t, width, name, B):
+        """t [B, rows, width] float32 on the device whose rows of a robot are contiguous; -> (t, rows per robot in memory)"""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != B or t.shape[2] != width \
+                or t.device != self.device:
+            raise ValueError(f"{name}: need a float32 [{B}, rows, {width}] tensor on {self.device}")
+        if B == 0 or t.shape[1] == 0:
+            return t, t.shape[1]
+        table = t.stride(0) >= t.shape[1] * width and t.stride(0) % width == 0      # robot b's rows start at b * stride(0)
+        if t.stride(2) != 1 or t.stride(1) != width or not (table or B == 1):
+            raise ValueError(f"{name}: rows must be dense and a robot's rows contiguous (a slice [:, :k] of a contiguous table is fine)")
+        return t, (t.stride(0) // width if table else t.shape[1])
+
+    def contact_track(self, q, v, A, dt: float, n_sub: int = 1, tau_ff=None, kp: float = KP, kd: float = KD,
+                      ground: GroundContact = GroundContact(), Q: Optional[torch.Tensor] = None, V: Optional[torch.Tensor] = None,
+                      record: bool = True, skip: Optional[torch.Tensor] = None, skip_mask: int = 0):
+        """nmpc_contact_track_batch: A.shape[1] control steps of `contact_step` in one launch, step k with q_des = A[:, k]
+        (n_sub substeps of dt each) -- with A the rows of `plan_actions`, the whole-body expert's PD law driving the plant over
+        a replanning interval.  q, v [B, n]: contiguous float32 device tensors, updated IN PLACE.  A [B, n_steps, 12] (a slice
+        [:, :n_steps] of a longer table is taken with its stride).  Q, V [B, n_steps, 18]: the state before every control step
+        (row 0 is the start state), written into the given tensors (again slices are fine) or into new ones with record=True;
+        None with record=False.  skip int32 [B]: robots with skip[b] & skip_mask != 0 are left out, their q, v and rows
+        untouched.  Bit for bit the chain of `contact_step` calls.  -> (q, v, Q, V)."""
+        q = self._state_io(q, "q"); v = self._state_io(v, "v")
+        tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff")
+        B = self._batch(q, v, tau_ff)
+        A, a_rows = self._rows(A, self.nu, "A", B)
+        n_steps = A.shape[1]
+        if (Q is None) != (V is None):
+            raise ValueError("Q and V come together or not at all")
+        if Q is None and record:
+            Q, V = (torch.empty(B, n_steps, self.n, dtype=torch.float32, device=self.device) for _ in range(2))
+        qv_rows = 0
+        if Q is not None:
+            Q, qv_rows = self._rows(Q, self.n, "Q", B)
+            V, v_rows = self._rows(V, self.n, "V", B)
+            if Q.shape[1] != n_steps or V.shape[1] != n_steps or v_rows != qv_rows:
+                raise ValueError("Q, V: need n_steps rows each and one layout")
+        self._flags(skip, q, "skip")
+        cfg = ground.cfg()
+        _lib.check(self.lib.nmpc_contact_track_batch(self._h, B, n_steps, int(n_sub), float(dt), ctypes.byref(cfg), ptr(q), ptr(v), ptr(tau_ff),
+                                                     ptr(A), a_rows, float(kp), float(kd), ptr(Q), ptr(V), qv_rows, ptr(skip), int(skip_mask),
+                                                     stream(self.device)), self._h, "nmpc_contact_track_batch", "torque")
+        return q, v, Q, V
+
+    def observe_rows(self, Q, V, t0: float, dt_row: float, period: float = NOMINAL_PERIOD, collision_height: float = 0.08,
+                     S: Optional[torch.Tensor] = None, failed: Optional[torch.Tensor] = None, step_index: int = 0, term_mask: int = 0,
+                     skip: Optional[torch.Tensor] = None, skip_mask: int = 0) -> torch.Tensor:
+        """nmpc_observe_rows_batch: `observe` for every row of a table of plant states in one launch.  Q, V [B, n_rows, 18] (as
+        `contact_track` writes them; slices of longer tables are taken with their stride); row k is observed at
+        t0 + k dt_row.  -> S [B, n_rows, 44] (written into `S` if given, which may be a slice of the rows of a longer table).
+        failed int32 [B]: updated in place with the flags of all rows and then, under `observe`'s rule, the stamp
+        step_index + 1.  Robots with skip[b] & skip_mask != 0 are untouched.  Bit for bit the n_rows `observe` calls."""
+        if not isinstance(Q, torch.Tensor) or Q.dim() != 3:
+            raise ValueError("Q: need a float32 [B, n_rows, 18] tensor")
+        B = Q.shape[0]
+        Q, qv_rows = self._rows(Q, self.n, "Q", B)
+        V, v_rows = self._rows(V, self.n, "V", B)
+        n_rows = Q.shape[1]
+        if V.shape[1] != n_rows or v_rows != qv_rows:
+            raise ValueError("Q, V: need the same rows and one layout")
+        if S is None:
+            S = torch.empty(B, n_rows, N_STATE, dtype=torch.float32, device=self.device)
+        S, s_rows = self._rows(S, N_STATE, "S", B)
+        if S.shape[1] != n_rows:
+            raise ValueError(f"S: need {n_rows} rows")
+        self._flags(failed, Q, "failed"); self._flags(skip, Q, "skip")
+        _lib.check(self.lib.nmpc_observe_rows_batch(self._h, B, n_rows, ptr(Q), ptr(V), qv_rows, float(t0), float(dt_row), float(period),
+                                                    float(collision_height), ptr(S), s_rows, ptr(failed), int(step_index), int(term_mask),
+                                                    ptr(skip), int(skip_mask), stream(self.device)),
+                   self._h, "nmpc_observe_rows_batch", "torque")
+        return S
+
     def compute_pd_torques(self, q, v, torques_ff, q_plan, v_plan, Kp: float, Kd: float) -> torch.Tensor:
         """mpc.py:592-599: torques_ff + Kp (q_plan[-nu:] - q[-nu:]) + Kd (v_plan[-nu:] - v[-nu:])."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")

@@ -1,0 +1,95 @@
+"""The entry points of the whole-body expert on the contact plant exist in every layer: nmpc_contact_track_batch and
+nmpc_observe_rows_batch (include/nmpc_torque.h) and nmpc_wb_rollout_set_plant (include/nmpc.h) are declared, exported by
+libnmpc_hip.so and bound with the headers' argument lists; BatchedTorqueLayer, BatchedNmpcSolver, LocomotionMPC, collect and
+learning take the plant.  No GPU: what is decided on the host is checked."""
+import ctypes
+import inspect
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+C_TYPES = {"void *": ctypes.c_void_p, "const float *": ctypes.c_void_p, "float *": ctypes.c_void_p, "const int *": ctypes.c_void_p,
+           "int *": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
+           "const nmpc_contact_cfg *": ctypes.c_void_p}
+# the argument names the issue gives, in order
+ARGUMENTS = {
+    "nmpc_contact_track_batch": ("nmpc_torque.h", ["handle", "B", "n_steps", "n_sub", "dt", "cfg", "q", "v", "tau_ff", "A", "a_rows", "kp", "kd",
+                                                   "Q", "V", "qv_rows", "skip", "skip_mask", "stream"]),
+    "nmpc_observe_rows_batch": ("nmpc_torque.h", ["handle", "B", "n_rows", "Q", "V", "qv_rows", "t0", "dt_row", "period", "collision_height", "S",
+                                                  "s_rows", "failed", "step_index", "term_mask", "skip", "skip_mask", "stream"]),
+    "nmpc_wb_rollout_set_plant": ("nmpc.h", ["handle", "torque_handle", "ground", "n_sub", "kp", "kd", "zoh", "Aw", "Qw", "Vw"]),
+}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    from iterative_learning_nmpc_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    return _lib.load()
+
+
+def declaration(name):
+    """(argument names, ctypes argument list) of the header's declaration of `name`"""
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", ARGUMENTS[name][0])).read(), flags=re.S)      # comments aside
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
+    assert m, f"{name} is not declared in include/{ARGUMENTS[name][0]}"
+    names, types = [], []
+    for a in m.group(1).split(","):
+        a = " ".join(a.split())
+        assert re.match(r"^(const )?\w+ \*?\w+$", a), a
+        names.append(re.search(r"\w+$", a).group(0))
+        types.append(C_TYPES[re.sub(r"\s*\w+$", "", a).strip()])
+    return names, types
+
+
+@pytest.mark.parametrize("name", sorted(ARGUMENTS))
+def test_symbol_is_declared_exported_and_bound_as_the_header_declares_it(lib, name):
+    from iterative_learning_nmpc_amd import _lib
+    names, types = declaration(name)
+    assert names == ARGUMENTS[name][1]
+    assert getattr(lib, name) is not None
+    assert _lib.SIGNATURES[name] == (ctypes.c_int, types)
+
+
+def test_the_rollout_cfg_keeps_its_fields():
+    """the plant is attached by a call: nmpc_wb_rollout_cfg is the structure it was"""
+    from iterative_learning_nmpc_amd import _lib
+    assert [n for n, _ in _lib.NmpcWbRolloutCfg._fields_] == [
+        "n_replans", "replanning_steps", "nodes_per_cycle", "first_solve", "last_node", "max_sqp_first", "nlp_tol_first", "nlp_tol", "sim_dt",
+        "time_horizon", "nom_height", "height_offset", "step_height", "push_start", "push_duration", "record_sim_steps",
+        "force_reference_gravity", "nominal_period", "terminate_mask", "collision_height"]
+    assert ctypes.sizeof(_lib.NmpcWbRolloutCfg) == 96
+
+
+def test_python_layers_take_the_plant():
+    from iterative_learning_nmpc_amd import collect, learning
+    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
+    from iterative_learning_nmpc_amd.solver import BatchedNmpcSolver
+    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer, GroundContact
+    from iterative_learning_nmpc_amd.trajectory_io import KD, KP
+    tr = inspect.signature(BatchedTorqueLayer.contact_track).parameters
+    assert list(tr) == ["self", "q", "v", "A", "dt", "n_sub", "tau_ff", "kp", "kd", "ground", "Q", "V", "record", "skip", "skip_mask"]
+    assert [tr[k].default for k in list(tr)[5:]] == [1, None, KP, KD, GroundContact(), None, None, True, None, 0]
+    ob = inspect.signature(BatchedTorqueLayer.observe_rows).parameters
+    assert list(ob) == ["self", "Q", "V", "t0", "dt_row", "period", "collision_height", "S", "failed", "step_index", "term_mask", "skip", "skip_mask"]
+    assert [ob[k].default for k in list(ob)[6:]] == [0.08, None, None, 0, 0, None, 0]
+    sp = inspect.signature(BatchedNmpcSolver.set_rollout_plant).parameters
+    assert list(sp) == ["self", "layer", "ground", "n_sub", "kp", "kd", "zoh"]
+    for fn in (LocomotionMPC.open_loop_device, collect.collect_rollouts, learning.learning_iteration):
+        p = inspect.signature(fn).parameters
+        assert p["plant"].default is None and p["plant_substeps"].default == 2, fn.__name__
+
+
+def test_a_null_handle_is_refused_on_the_host(lib):
+    from iterative_learning_nmpc_amd import _lib
+    ground = _lib.NmpcContactCfg(0.0, 1e4, 3.0, 0.8, 0.05, 0.0)
+    assert lib.nmpc_contact_track_batch(None, 1, 3, 2, 5e-4, ctypes.byref(ground), None, None, None, None, 3, 20.0, 1.5, None, None, 3, None, 0,
+                                        None) == -1
+    assert b"handle" in lib.nmpc_torque_last_error(None)
+    assert lib.nmpc_observe_rows_batch(None, 1, 3, None, None, 3, 0.0, 1e-3, 0.5, 0.08, None, 3, None, 0, 0, None, 0, None) == -1
+    assert b"handle" in lib.nmpc_torque_last_error(None)
+    assert lib.nmpc_wb_rollout_set_plant(None, None, None, 2, 20.0, 1.5, None, None, None, None) == -1
