@@ -19,10 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from iterative_learning_nmpc_amd import workloads as wl  # noqa: E402
 from oracle.oracle import Oracle  # noqa: E402
-
-
-def rel(a, b):
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+from tests.solve_helpers import rel  # noqa: E402
 
 
 def run(mu, floors, K=8, B=128, shift=2):

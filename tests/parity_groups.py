@@ -25,6 +25,9 @@ from typing import Tuple
 
 import numpy as np
 
+from tests import solve_helpers
+from tests.solve_helpers import rel as batch_rel  # noqa: F401  the figure of the batch-level solve tests: relative L2 over the whole tensor
+
 NORTH_STAR = 1e-5          # BASELINE.json north_star: relative L2 on trajectories
 F32_FACTOR = 4.0           # the standing factor on the float32 restatement's own error
 DEN_FLOOR = 1e-3           # every per-problem group norm of the reference >= this share of the group's batch median
@@ -63,12 +66,6 @@ def denominators_ok(den):
 def over_bar(e, bar):
     """[(problem, group index)] of every entry over its bar (NaN counts as over)"""
     return [(int(b), int(g)) for b, g in zip(*np.nonzero(~(e <= bar[None, :])))]
-
-
-def batch_rel(a, b):
-    """the figure of the batch-level solve tests: relative L2 over the whole tensor"""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def report(case, tensor, groups, e_gpu, e32, bar):
@@ -197,9 +194,7 @@ def oracle_solve(o, case, w, sqp=None):
     X, U = w.X, w.U
     if case.shift:
         X, U = o.shift_warm_start(X, U, case.shift)
-    opt = o.opt(max_sqp_iter=case.sqp if sqp is None else sqp, n_ipm=case.n_ipm, yref_per_stage=1,
-                reg=w.meta.get("reg", 1e-6), reg_e=w.meta.get("reg_e", 1e-5))
-    return o.solve_batch(w.model_id, w.N, w.mp, opt, w.W, w.W_e, w.x0, w.yref, w.yref_e, w.params, X, U)
+    return solve_helpers.oracle_solve(o, w, X, U, max_sqp_iter=case.sqp if sqp is None else sqp, n_ipm=case.n_ipm)
 
 
 def ulp_copy(w, k):

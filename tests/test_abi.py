@@ -6,16 +6,9 @@ import re
 
 import pytest
 
+from tests.abi_header import lib  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from iterative_learning_nmpc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
 
 
 def test_header_symbols_are_exported_and_bound(lib):

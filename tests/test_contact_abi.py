@@ -3,35 +3,17 @@ header's argument lists, and behind methods of BatchedTorqueLayer.  No GPU: what
 import ctypes
 import dataclasses
 import inspect
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-C_TYPES = {"void *": ctypes.c_void_p, "const float *": ctypes.c_void_p, "float *": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float,
-           "const nmpc_contact_cfg *": ctypes.c_void_p}
+from tests.abi_header import declaration, lib, struct_fields  # noqa: F401
+
 NAMES = ("nmpc_foot_kinematics_batch", "nmpc_contact_forces_batch", "nmpc_contact_step_batch")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from iterative_learning_nmpc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "nmpc_torque.h")).read()
 
 
 def header_arguments(name):
     """The ctypes argument list the header's declaration of `name` asks for."""
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header())
-    assert m, f"{name} is not declared in include/nmpc_torque.h"
-    return [C_TYPES[re.sub(r"\s*\w+$", "", " ".join(a.split())).strip()] for a in m.group(1).split(",")]
+    return declaration("nmpc_torque.h", name)[1]
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -48,11 +30,11 @@ def test_argument_lists():
 
 def test_the_cfg_structure_has_the_headers_fields():
     from iterative_learning_nmpc_amd import _lib
-    body = re.search(r"typedef struct \{([^}]*)\} nmpc_contact_cfg;", header()).group(1)
-    assert body.split()[0] == "float"
-    names = [x.strip() for x in body.replace("float", "").rstrip("; ").split(",")]
+    fields = struct_fields("nmpc_torque.h", "nmpc_contact_cfg")
+    names = [n for n, _ in fields]
     assert names == ["ground_z", "stiffness", "damping", "mu", "slip_velocity", "tau_max"]
-    assert [(n, t) for n, t in _lib.NmpcContactCfg._fields_] == [(n, ctypes.c_float) for n in names]
+    assert fields == [(n, ctypes.c_float) for n in names]
+    assert [(n, t) for n, t in _lib.NmpcContactCfg._fields_] == fields
 
 
 def test_layer_has_the_methods_and_the_defaults():

@@ -4,15 +4,11 @@ libnmpc_hip.so and bound with the headers' argument lists; BatchedTorqueLayer, B
 learning take the plant.  No GPU: what is decided on the host is checked."""
 import ctypes
 import inspect
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-C_TYPES = {"void *": ctypes.c_void_p, "const float *": ctypes.c_void_p, "float *": ctypes.c_void_p, "const int *": ctypes.c_void_p,
-           "int *": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
-           "const nmpc_contact_cfg *": ctypes.c_void_p}
+from tests.abi_header import declaration, lib  # noqa: F401
+
 # the argument names the issue gives, in order
 ARGUMENTS = {
     "nmpc_contact_track_batch": ("nmpc_torque.h", ["handle", "B", "n_steps", "n_sub", "dt", "cfg", "q", "v", "tau_ff", "A", "a_rows", "kp", "kd",
@@ -23,33 +19,10 @@ ARGUMENTS = {
 }
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from iterative_learning_nmpc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def declaration(name):
-    """(argument names, ctypes argument list) of the header's declaration of `name`"""
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", ARGUMENTS[name][0])).read(), flags=re.S)      # comments aside
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in include/{ARGUMENTS[name][0]}"
-    names, types = [], []
-    for a in m.group(1).split(","):
-        a = " ".join(a.split())
-        assert re.match(r"^(const )?\w+ \*?\w+$", a), a
-        names.append(re.search(r"\w+$", a).group(0))
-        types.append(C_TYPES[re.sub(r"\s*\w+$", "", a).strip()])
-    return names, types
-
-
 @pytest.mark.parametrize("name", sorted(ARGUMENTS))
 def test_symbol_is_declared_exported_and_bound_as_the_header_declares_it(lib, name):
     from iterative_learning_nmpc_amd import _lib
-    names, types = declaration(name)
+    names, types = declaration(ARGUMENTS[name][0], name)
     assert names == ARGUMENTS[name][1]
     assert getattr(lib, name) is not None
     assert _lib.SIGNATURES[name] == (ctypes.c_int, types)

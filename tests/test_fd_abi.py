@@ -2,31 +2,17 @@
 the header's argument lists, and behind methods of BatchedTorqueLayer.  No GPU: what is decided on the host is checked."""
 import ctypes
 import inspect
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-C_TYPES = {"void *": ctypes.c_void_p, "const float *": ctypes.c_void_p, "float *": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float}
+from tests.abi_header import declaration, lib  # noqa: F401
+
 NAMES = ("nmpc_fd_accel_batch", "nmpc_fd_step_batch")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from iterative_learning_nmpc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
 
 
 def header_arguments(name):
     """The ctypes argument list the header's declaration of `name` asks for."""
-    header = open(os.path.join(ROOT, "include", "nmpc_torque.h")).read()
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header)
-    assert m, f"{name} is not declared in include/nmpc_torque.h"
-    return [C_TYPES[re.sub(r"\s*\w+$", "", " ".join(a.split())).strip()] for a in m.group(1).split(",")]
+    return declaration("nmpc_torque.h", name)[1]
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -14,70 +14,13 @@ import pytest
 
 from tests import contact_reference as cr
 from tests import fd_reference as fr
+from tests.torque_helpers import Case, bar, branches, ground, held, host, layer
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-BAR = 1e-5
 KP, KD, DT = 20.0, 1.5, 5e-4
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contact_settle.npz")
-
-
-def layer(m):
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    return BatchedTorqueLayer(m.parent, m.jtype, m.axis, m.R_fix, m.p_fix, m.mass, m.com, m.inertia, m.foot_joint, m.foot_offset,
-                              m.nu, gravity=m.gravity)
-
-
-def ground(g):
-    from iterative_learning_nmpc_amd.torque import GroundContact
-    return GroundContact(g.ground_z, g.stiffness, g.damping, g.mu, g.slip_velocity, g.tau_max)
-
-
-def host(*tensors):
-    return [t.cpu().numpy() for t in tensors]
-
-
-def bar(ref, f32):
-    """the accuracy bar of an array: max(1e-5 of its largest |reference|, 4 x the float32 run's deviation)"""
-    return max(BAR * np.abs(ref).max(), 4 * np.abs(f32.astype(np.float64) - ref).max())
-
-
-def held(name, got, ref, f32):
-    err, b = np.abs(got - ref).max(), bar(ref, f32)
-    print(f"  {name}: {err:.2e} (bar {b:.2e}, float32 loop {np.abs(f32.astype(np.float64) - ref).max():.2e}, scale {np.abs(ref).max():.2e})")
-    return err <= b                     # <=: an array whose reference is all zeros has to come out as zeros
-
-
-def branches(g, pos, vel, f):
-    """(feet off the ground, feet pushed, feet in the ground that leave too fast to be pushed) of reference kinematics and forces"""
-    inside = g.ground_z - pos[..., 2] > 0
-    return int((~inside).sum()), int((inside & (f[..., 2] > 0)).sum()), int((inside & (f[..., 2] == 0)).sum())
-
-
-class Case:
-    """A tree, its device layer, B float32 states with feet above, at and a few millimetres below the ground, and their fp64
-    and numpy-float32 foot kinematics and forces: computed once, never written to."""
-    def __init__(self, m, B, seed, g=None):
-        self.m, self.L = m, layer(m)
-        q, v, tau, _ = fr.inputs(m, B, seed)
-        if g is None:                   # the quadruped: joint 2 slides the base, the lowest foot goes to -3 mm, 0, +2 cm in turn
-            g = cr.Ground()
-            lowest = lambda: np.array([cr.feet(m, q[b])[0][:, 2].min() for b in range(B)])      # noqa: E731
-            want = np.array([-0.003, 0.0, 0.02])[np.arange(B) % 3]
-            lift = (m.forward_kinematics(q[0])[0][2] @ m.axis[2])[2]                              # world z per unit of q[2]
-            assert m.jtype[2] == 1 and lift > 0.5
-            q[:, 2] += ((want - lowest()) / lift).astype(np.float32)
-            assert np.abs(lowest() - want).max() < 1e-6
-        self.g, self.q, self.v, self.tau = g, q, v, tau
-        k64 = [cr.feet(m, q[b], v[b]) for b in range(B)]
-        k32 = [cr.feet(m, q[b], v[b], np.float32) for b in range(B)]
-        self.pos, self.vel = np.stack([k[0] for k in k64]), np.stack([k[1] for k in k64])
-        self.pos32, self.vel32 = np.stack([k[0] for k in k32]), np.stack([k[1] for k in k32])
-        self.f, self.f32 = cr.contact_law(g, self.pos, self.vel), cr.contact_law(g, self.pos32, self.vel32)
-        assert self.f32.dtype == np.float32
-        for x in (self.q, self.v, self.tau, self.pos, self.vel, self.f, self.pos32, self.vel32, self.f32):
-            x.setflags(write=False)
 
 
 def general_tree_case(m, B, seed):

@@ -12,6 +12,7 @@ import pytest
 
 from tests import contact_reference as cr
 from tests import fd_reference as fr
+from tests.torque_helpers import ground, layer, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -24,33 +25,12 @@ KEPT = 16                                              # the velocity-tracking b
 SENTINEL = -77.0
 
 
-def make_layer(m):
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    return BatchedTorqueLayer(m.parent, m.jtype, m.axis, m.R_fix, m.p_fix, m.mass, m.com, m.inertia, m.foot_joint, m.foot_offset,
-                              m.nu, gravity=m.gravity)
-
-
-def ground(tau_max=None):
-    from iterative_learning_nmpc_amd.torque import GroundContact
-    g = cr.Ground()
-    return GroundContact(g.ground_z, g.stiffness, g.damping, g.mu, g.slip_velocity, tau_max)
-
-
-def bits(t):
-    """the bit patterns of a float32 tensor: equality of these is equality of every bit, NaN payloads included"""
-    return t.contiguous().view(torch.int32)
-
-
-def same(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
 class World:
     B = 257
 
     def __init__(self):
         self.m = m = fr.quadruped(perturb=0.3)
-        self.L = make_layer(m)
+        self.L = layer(m)
         B = self.B
         q, v, tau, _ = fr.inputs(m, B, 258)
         lowest = lambda: np.array([cr.feet(m, q[b])[0][:, 2].min() for b in range(B)])      # noqa: E731
@@ -77,7 +57,7 @@ class World:
         Q, V, T = [], [], []
         for k in range(N_STEPS):
             Q.append(q); V.append(v)
-            q, v, _, _, t = L.contact_step(q, v, DT, N_SUB, tau_ff=tau_ff, q_des=A[:, k].contiguous(), kp=KP, kd=KD, ground=ground(tau_max))
+            q, v, _, _, t = L.contact_step(q, v, DT, N_SUB, tau_ff=tau_ff, q_des=A[:, k].contiguous(), kp=KP, kd=KD, ground=ground(tau_max=tau_max))
             T.append(t)
         return q, v, torch.stack(Q, 1), torch.stack(V, 1), torch.stack(T, 1)
 
@@ -88,7 +68,7 @@ class World:
         B = q.shape[0]
         Qt, Vt = (torch.full((B, QV_ROWS, 18), SENTINEL if fill is None else fill, dtype=torch.float32, device=L.device) for _ in range(2))
         tau_ff = self.dev(self.tau[rows]) if tau else None
-        q2, v2, Q, V = L.contact_track(q, v, A[:, :N_STEPS], DT, N_SUB, tau_ff=tau_ff, kp=KP, kd=KD, ground=ground(tau_max),
+        q2, v2, Q, V = L.contact_track(q, v, A[:, :N_STEPS], DT, N_SUB, tau_ff=tau_ff, kp=KP, kd=KD, ground=ground(tau_max=tau_max),
                                        Q=Qt[:, :N_STEPS], V=Vt[:, :N_STEPS], skip=skip, skip_mask=skip_mask)
         assert q2.data_ptr() == q.data_ptr() and v2.data_ptr() == v.data_ptr()        # in place on q, v
         return q, v, Q, V, Qt, Vt
@@ -213,7 +193,7 @@ def test_massless_leaf_gives_nan_rows_where_the_chain_has_them_and_the_next_call
     r = slice(0, 33)
     bad = copy.deepcopy(world.m)
     bad.mass[17] = 0.0; bad.inertia[17] = 0.0
-    Lb = make_layer(bad)
+    Lb = layer(bad)
     ref = world.chain(r, L=Lb)
     got = world.track(r, L=Lb)
     assert same(ref[2][:, 0], world.dev(world.q[r])) and bool(torch.isnan(ref[2][:, 1:]).all()) and bool(torch.isnan(ref[0]).all())
@@ -260,7 +240,7 @@ def test_errors_and_the_empty_batch(world):
     assert refused(track(Q=None), "Q and V come together") and refused(track(V=None), "Q and V come together")
     assert refused(track(qv_rows=N_STEPS - 1), "qv_rows must be at least n_steps")
     small = fr.random_tree()                                                           # 23 joints: no rows of 18
-    Ls = make_layer(small)
+    Ls = layer(small)
     assert refused(track(h=Ls), "whole-body tree", Ls)
     assert refused(rows(h=Ls), "whole-body tree", Ls)
     assert refused(rows(n_rows=0), "n_rows must be at least 1")

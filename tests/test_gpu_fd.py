@@ -6,23 +6,13 @@ import numpy as np
 import pytest
 
 from tests import fd_reference as fr
+from tests.torque_helpers import host, layer
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 BAR = 1e-5
 ZERO3 = (0.0, 0.0, 0.0)
-
-
-def layer(m, gravity=None):
-    """The device layer for the arrays an oracle model holds."""
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    return BatchedTorqueLayer(m.parent, m.jtype, m.axis, m.R_fix, m.p_fix, m.mass, m.com, m.inertia, m.foot_joint, m.foot_offset,
-                              m.nu, gravity=m.gravity if gravity is None else gravity)
-
-
-def host(*tensors):
-    return [t.cpu().numpy() for t in tensors]
 
 
 class Case:

@@ -7,47 +7,11 @@ measured fp32-vs-fp64 floor quoted next to each bound.
 import numpy as np
 import pytest
 
+from tests.solve_helpers import dev, gpu_solve, make_solver, oracle_solve, rel, within_tolerance  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _solver(w, B, dev, **opts):
-    from iterative_learning_nmpc_amd.solver import BatchedNmpcSolver
-    s = BatchedNmpcSolver(w.model_id, w.N, B, dev)
-    s.set_model_params(w.mp)
-    s.set_cost_weights(w.W, w.W_e, w.meta.get("reg", 1e-6), w.meta.get("reg_e", 1e-5))
-    s.set_max_iter(opts.get("max_sqp_iter", 1))
-    s.set_max_qp_iter(opts.get("n_ipm", 6))
-    s.set_nlp_tol(opts.get("nlp_tol", 0.0))
-    s.set_line_search(opts.get("line_search", 0))
-    return s
-
-
-def _gpu_solve(s, w):
-    t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params", "X", "U")}
-    X, U, st, stats = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], t["X"], t["U"])
-    torch.cuda.synchronize()
-    return X.cpu().numpy(), U.cpu().numpy(), st.cpu().numpy(), stats.cpu().numpy()
-
-
-def _oracle_solve(o, w, **opts):
-    kw = dict(max_sqp_iter=1, n_ipm=6, yref_per_stage=1, reg=w.meta.get("reg", 1e-6),
-              reg_e=w.meta.get("reg_e", 1e-5))
-    kw.update(opts)
-    return o.solve_batch(w.model_id, w.N, w.mp, o.opt(**kw), w.W, w.W_e, w.x0, w.yref, w.yref_e,
-                         w.params, w.X, w.U)
 
 
 # ------------------------------------------------------------------------------- LQ core
@@ -98,8 +62,8 @@ def test_centroidal_stage_tiles_match_oracle(dev, oracle64):
     from iterative_learning_nmpc_amd import workloads as wl
     w = wl.centroidal_trot(B=4, N=50, seed=3)
     w.X += np.random.default_rng(0).normal(0, 0.02, w.X.shape)     # non-trivial defects
-    s = _solver(w, 4, dev, n_ipm=0)
-    _gpu_solve(s, w)
+    s = make_solver(w, 4, dev, n_ipm=0)
+    gpu_solve(s, w)
     for b in (0, 3):
         for k in (0, 17, 49):
             xn, A, Bj = oracle64.dynamics(1, w.mp, w.X[b, k], w.U[b, k], w.params[b, k])
@@ -116,14 +80,14 @@ def test_double_integrator_lq_exact(dev, oracle64):
     """Config 1: an LQ problem, one SQP iteration is the exact optimum."""
     from iterative_learning_nmpc_amd import workloads as wl
     w = wl.double_integrator(B=16, N=20, seed=0)
-    s = _solver(w, 16, dev, n_ipm=0)
-    X, U, st, stats = _gpu_solve(s, w)
-    Xo, Uo, sto, _ = _oracle_solve(oracle64, w, n_ipm=0)
+    s = make_solver(w, 16, dev, n_ipm=0)
+    X, U, st, stats = gpu_solve(s, w)
+    Xo, Uo, sto, _ = oracle_solve(oracle64, w, n_ipm=0)
     assert rel(X, Xo) < 1e-5 and rel(U, Uo) < 1e-5
     assert (st == 2).all() and (sto == 2).all()
     # a second iteration does not move the solution: converged -> status 0 with a tolerance
     s.set_max_iter(3); s.set_nlp_tol(1e-3)
-    X2, U2, st2, stats2 = _gpu_solve(s, w)
+    X2, U2, st2, stats2 = gpu_solve(s, w)
     assert (st2 == 0).all() and (stats2[:, 3] == 2).all()
     assert rel(X2, Xo) < 1e-5
 
@@ -131,20 +95,12 @@ def test_double_integrator_lq_exact(dev, oracle64):
 def test_double_integrator_box_constraints(dev, oracle64, oracle32):
     from iterative_learning_nmpc_amd import workloads as wl
     w = wl.double_integrator(B=16, N=20, seed=1, umax=1.0)
-    s = _solver(w, 16, dev, n_ipm=8)
-    X, U, st, _ = _gpu_solve(s, w)
-    Xo, Uo, _, _ = _oracle_solve(oracle64, w, n_ipm=8)
+    s = make_solver(w, 16, dev, n_ipm=8)
+    X, U, st, _ = gpu_solve(s, w)
+    Xo, Uo, _, _ = oracle_solve(oracle64, w, n_ipm=8)
     assert np.abs(U).max() <= 1.0 + 1e-4          # box respected
     assert np.abs(Uo).max() > 0.9                   # and it is active
     assert rel(X, Xo) < 1e-5 and rel(U, Uo) < 1e-5, (rel(X, Xo), rel(U, Uo))      # measured 2.9e-7 / 4.4e-7 (tools/parity_floor.py)
-
-
-def _within_tolerance(e, floor):
-    """The stated bar, 1e-5 relative L2 against the fp64 oracle.  The fp32 oracle is the same algorithm in float with
-    the CPU's summation order -- the kernels contract in the order of the matrix instruction, so neither is bit-equal
-    to the other; where the CPU's own fp32 error approaches the bar (measured: 7.8e-6 after three SQP iterations,
-    1.65e-5 with a binding friction pyramid, tools/parity_floor.py) the device may sit at 1.5 x that floor."""
-    return e < 1e-5 or e < 1.5 * floor
 
 
 # (6, 15) is the reference's first-solve policy (6 IPM x 15 SQP, mpc.py:464-473)
@@ -154,10 +110,10 @@ def test_centroidal_solve_parity(dev, oracle64, oracle32, n_ipm, sqp):
     from iterative_learning_nmpc_amd import workloads as wl
     B = 64
     w = wl.centroidal_trot(B=B, N=50, seed=0)
-    s = _solver(w, B, dev, n_ipm=n_ipm, max_sqp_iter=sqp)
-    X, U, st, stats = _gpu_solve(s, w)
-    X64, U64, st64, stats64 = _oracle_solve(oracle64, w, n_ipm=n_ipm, max_sqp_iter=sqp)
-    X32, U32, _, _ = _oracle_solve(oracle32, w, n_ipm=n_ipm, max_sqp_iter=sqp)
+    s = make_solver(w, B, dev, n_ipm=n_ipm, max_sqp_iter=sqp)
+    X, U, st, stats = gpu_solve(s, w)
+    X64, U64, st64, stats64 = oracle_solve(oracle64, w, n_ipm=n_ipm, max_sqp_iter=sqp)
+    X32, U32, _, _ = oracle_solve(oracle32, w, n_ipm=n_ipm, max_sqp_iter=sqp)
     floor = max(rel(X32, X64), rel(U32, U64))         # what fp32 itself costs on the CPU
     eX, eU = rel(X, X64), rel(U, U64)
     print(f"n_ipm={n_ipm} sqp={sqp}: gpu-vs-f64 X {eX:.2e} U {eU:.2e}; gpu-vs-f32 X {rel(X, X32):.2e} "
@@ -165,7 +121,7 @@ def test_centroidal_solve_parity(dev, oracle64, oracle32, n_ipm, sqp):
     assert np.array_equal(st, st64)
     # measured gpu-vs-fp64 (X / U): 4.2e-6 / 9e-7, 4.1e-6 / 1.0e-6, 9.6e-6 / 1.2e-6 (fp32 oracle itself 7.8e-6), 9.7e-7 / 2.2e-7,
     # 1.0e-6 / 2.3e-7: fifteen iterations contract the rounding differences, they do not amplify them
-    assert _within_tolerance(eX, rel(X32, X64)) and eU < 1e-5, (eX, eU, floor)
+    assert within_tolerance(eX, rel(X32, X64)) and eU < 1e-5, (eX, eU, floor)
     assert rel(X, X32) < 1e-5 and rel(U, U32) < 1e-5                 # and against the fp32 oracle (measured <= 6.2e-6)
     assert np.allclose(stats[:, 0], stats64[:, 0], rtol=1e-4)       # cost at linearisation
     assert np.array_equal(stats[:, 3], stats64[:, 3])               # iteration count
@@ -178,25 +134,25 @@ def test_centroidal_active_friction(dev, oracle64, oracle32):
     B = 32
     w = wl.centroidal_trot(B=B, N=50, seed=1)
     w.mp[6] = 0.3
-    s = _solver(w, B, dev, n_ipm=6)
-    X, U, st, _ = _gpu_solve(s, w)
-    X64, U64, _, _ = _oracle_solve(oracle64, w, n_ipm=6)
+    s = make_solver(w, B, dev, n_ipm=6)
+    X, U, st, _ = gpu_solve(s, w)
+    X64, U64, _, _ = oracle_solve(oracle64, w, n_ipm=6)
     f = U.reshape(B, 50, 4, 3)
     c = np.moveaxis(w.params[:, :50, :4], 2, 2)
     viol = np.maximum(np.abs(f[..., :2]).max(-1) - 0.3 * f[..., 2], 0) * c
     assert viol.max() < 1e-3
-    X32, U32, _, _ = _oracle_solve(oracle32, w, n_ipm=6)
+    X32, U32, _, _ = oracle_solve(oracle32, w, n_ipm=6)
     # measured 1.84e-5 / 4.6e-6 with the fp32 oracle itself at 1.65e-5 / 4.6e-6: the stiff barrier system, not the kernel
-    assert _within_tolerance(rel(X, X64), rel(X32, X64)) and rel(U, U64) < 1e-5, (rel(X, X64), rel(U, U64), rel(X32, X64))
+    assert within_tolerance(rel(X, X64), rel(X32, X64)) and rel(U, U64) < 1e-5, (rel(X, X64), rel(U, U64), rel(X32, X64))
 
 
 def test_centroidal_line_search_and_status(dev, oracle64):
     from iterative_learning_nmpc_amd import workloads as wl
     B = 16
     w = wl.centroidal_trot(B=B, N=50, seed=2, warm="zero")
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=2, line_search=1)
-    X, U, st, stats = _gpu_solve(s, w)
-    X64, U64, st64, stats64 = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2, line_search=1)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=2, line_search=1)
+    X, U, st, stats = gpu_solve(s, w)
+    X64, U64, st64, stats64 = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2, line_search=1)
     # every problem of the batch backtracks to the same step length as the oracle (a merit value within rounding of the
     # acceptance threshold could flip one; none does on this seed, and the assertion is on the whole batch)
     assert np.array_equal(stats[:, 2], stats64[:, 2])
@@ -204,8 +160,8 @@ def test_centroidal_line_search_and_status(dev, oracle64):
     # NaN input -> status 1 for that problem only
     w2 = wl.centroidal_trot(B=4, N=50, seed=5)
     w2.x0[2, 0] = np.nan
-    s2 = _solver(w2, 4, dev)
-    _, _, st2, _ = _gpu_solve(s2, w2)
+    s2 = make_solver(w2, 4, dev)
+    _, _, st2, _ = gpu_solve(s2, w2)
     assert st2.tolist() == [2, 2, 1, 2]
 
 
@@ -308,9 +264,9 @@ def test_odd_batches_and_horizons(dev, oracle64, model, B, N):
     """Ragged sizes: B = 1, odd B, N below / above the 64-lane stage loop, N = 1."""
     from iterative_learning_nmpc_amd import workloads as wl
     w = wl.centroidal_trot(B=B, N=N, seed=11) if model == 1 else wl.double_integrator(B=B, N=N, seed=11, umax=1.5)
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
-    X, U, st, stats = _gpu_solve(s, w)
-    Xo, Uo, sto, statso = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
+    X, U, st, stats = gpu_solve(s, w)
+    Xo, Uo, sto, statso = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2)
     assert np.array_equal(st, sto)
     assert rel(X, Xo) < 1e-5 and rel(U, Uo) < 1e-5, (rel(X, Xo), rel(U, Uo))           # measured <= 2.3e-6
 
@@ -322,9 +278,9 @@ def test_per_problem_early_exit(dev, oracle64):
     B = 24
     w = wl.centroidal_trot(B=B, N=50, seed=8)
     w.X[B // 2:] += np.random.default_rng(1).normal(0, 0.05, w.X[B // 2:].shape)   # harder half
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=10, nlp_tol=0.5)
-    X, U, st, stats = _gpu_solve(s, w)
-    Xo, Uo, sto, statso = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=10, nlp_tol=0.5)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=10, nlp_tol=0.5)
+    X, U, st, stats = gpu_solve(s, w)
+    Xo, Uo, sto, statso = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=10, nlp_tol=0.5)
     assert len(set(statso[:, 3].tolist())) > 1, "test needs problems stopping at different iterations"
     # every problem stops at the oracle's iteration (a step norm within rounding of the tolerance could flip one: the
     # closest on this seed is 3 % away from it)
@@ -338,26 +294,26 @@ def test_handle_reuse_after_riccati_and_argument_errors(dev, oracle64):
     from iterative_learning_nmpc_amd.solver import BatchedNmpcSolver
     B = 4
     w = wl.centroidal_trot(B=B, N=50, seed=4)
-    s = _solver(w, B, dev)
-    X1, U1, _, _ = _gpu_solve(s, w)
+    s = make_solver(w, B, dev)
+    X1, U1, _, _ = gpu_solve(s, w)
     # a dense-LQ call on the same handle dirties the tile workspace; the next solve must not care
     rng = np.random.default_rng(0)
     lq = [np.tile(np.eye(9), (B, 51, 1, 1)), np.tile(np.eye(5), (B, 50, 1, 1)), rng.normal(size=(B, 51, 9)),
           rng.normal(size=(B, 50, 5)), np.tile(np.eye(9), (B, 50, 1, 1)), rng.normal(size=(B, 50, 9, 5)),
           rng.normal(size=(B, 50, 9)), rng.normal(size=(B, 9))]
     s.riccati(*[s.to_device(a) for a in lq])
-    X2, U2, _, _ = _gpu_solve(s, w)
+    X2, U2, _, _ = gpu_solve(s, w)
     assert np.array_equal(X1, X2) and np.array_equal(U1, U2)          # and the solve is deterministic
     # argument errors surface as exceptions with the library's message
     big = wl.centroidal_trot(B=B + 1, N=50, seed=4)
     with pytest.raises(_lib.NmpcError, match="B_max"):
-        _gpu_solve(s, big)
+        gpu_solve(s, big)
     with pytest.raises(ValueError):
         s.solve(s.to_device(w.x0[:, :5]), s.to_device(w.yref), s.to_device(w.yref_e), s.to_device(w.params),
                 s.to_device(w.X), s.to_device(w.U))
     fresh = BatchedNmpcSolver(1, 50, B, dev)
     with pytest.raises(_lib.NmpcError, match="not set"):
-        _gpu_solve(fresh, w)
+        gpu_solve(fresh, w)
     with pytest.raises(_lib.NmpcError):
         fresh.set_model_params(wl.model_params(dt=0.0))    # dt = 0
     # an empty batch is a no-op
@@ -372,8 +328,8 @@ def test_full_size_properties(dev):
     from iterative_learning_nmpc_amd import workloads as wl
     B = 1024
     w = wl.centroidal_trot(B=B, N=50, seed=21)
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=8)
-    X, U, st, stats = _gpu_solve(s, w)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=8)
+    X, U, st, stats = gpu_solve(s, w)
     assert (st != 1).all() and (st != 4).all() and np.isfinite(X).all()
     assert np.abs(X[:, 0] - w.x0).max() < 1e-5
     c = w.params[:, :50, :4]
@@ -390,7 +346,7 @@ def test_full_size_properties(dev):
     w2 = wl.centroidal_trot(B=B, N=50, seed=21)
     for k in ("x0", "yref", "yref_e", "params", "X", "U"):
         setattr(w2, k, getattr(w2, k)[perm])
-    X2, U2, _, _ = _gpu_solve(s, w2)
+    X2, U2, _, _ = gpu_solve(s, w2)
     assert np.array_equal(X2, X[perm]) and np.array_equal(U2, U[perm])
 
 
@@ -440,7 +396,7 @@ def test_lean_variant_is_bit_identical_to_resident(dev, monkeypatch, model, N, o
     out = {}
     for variant in ("resident", "lean"):
         monkeypatch.setenv("NMPC_QP_VARIANT", variant)       # read by nmpc_create
-        out[variant] = _gpu_solve(_solver(w, B, dev, **opts), w)
+        out[variant] = gpu_solve(make_solver(w, B, dev, **opts), w)
     for a, b in zip(out["resident"], out["lean"]):
         assert np.array_equal(a, b)
 
@@ -460,7 +416,7 @@ def test_lean_variant_equals_resident_on_the_step_and_write_back_paths(dev, monk
     out = {}
     for variant in ("resident", "lean"):
         monkeypatch.setenv("NMPC_QP_VARIANT", variant)
-        s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=4 if case == "early_exit" else 1, nlp_tol=0.2 if case == "early_exit" else 0.0)
+        s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=4 if case == "early_exit" else 1, nlp_tol=0.2 if case == "early_exit" else 0.0)
         t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params", "X", "U")}
         X, U, st, stats = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], t["X"], t["U"], shift=shift)
         torch.cuda.synchronize()
@@ -488,9 +444,9 @@ def test_batch_beyond_one_wave_per_simd_runs_in_rounds(dev, oracle32, monkeypatc
     monkeypatch.delenv("NMPC_QP_VARIANT", raising=False)
     B = 1100
     w = wl.centroidal_trot(B=B, N=50, seed=17)
-    X, U, st, _ = _gpu_solve(_solver(w, B, dev), w)
+    X, U, st, _ = gpu_solve(make_solver(w, B, dev), w)
     monkeypatch.setenv("NMPC_QP_VARIANT", "resident")
-    Xr, Ur, str_, _ = _gpu_solve(_solver(w, B, dev), w)
+    Xr, Ur, str_, _ = gpu_solve(make_solver(w, B, dev), w)
     assert np.array_equal(X, Xr) and np.array_equal(U, Ur) and np.array_equal(st, str_)
     sel = slice(B - 24, B)                                    # the tail of the batch: the second round
     ws = wl.centroidal_trot(B=B, N=50, seed=17)
@@ -516,8 +472,8 @@ def test_mixed_precision_barrier_product(dev, oracle64):
     s = BatchedNmpcSolver(w.model_id, w.N, B, dev, precision=1)
     s.set_model_params(w.mp)
     s.set_cost_weights(w.W, w.W_e, w.meta["reg"], w.meta["reg_e"])
-    X, U, st, _ = _gpu_solve(s, w)
-    Xo, Uo, sto, _ = _oracle_solve(oracle64, w)
+    X, U, st, _ = gpu_solve(s, w)
+    Xo, Uo, sto, _ = oracle_solve(oracle64, w)
     eX, eU = rel(X, Xo), rel(U, Uo)
     print(f"mixed precision: rel-L2 X {eX:.2e} U {eU:.2e}")
     assert np.array_equal(st, sto)
@@ -536,7 +492,7 @@ def test_fused_shift_solve_equals_shift_then_solve(dev, shift, sqp):
     rng = np.random.default_rng(5)
     w.X = (w.X + 0.01 * rng.standard_normal(w.X.shape)).astype(np.float32)      # a previous solution with structure
     w.U = (w.U + 0.5 * rng.standard_normal(w.U.shape)).astype(np.float32)
-    s = _solver(w, B, dev, max_sqp_iter=sqp)
+    s = make_solver(w, B, dev, max_sqp_iter=sqp)
     t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params")}
     Xa, Ua = s.to_device(w.X), s.to_device(w.U)
     s.warm_start_solver(Xa, Ua, shift)
@@ -569,10 +525,10 @@ def test_all_contact_patterns_kernel_matches_default_and_oracle(dev, oracle64):
     assert len(np.unique((flags[:, :N] * np.array([1, 2, 4, 8])).sum(-1))) == 16
     out = {}
     for allp in (False, True):
-        s = _solver(w, B, dev)
+        s = make_solver(w, B, dev)
         assert s.set_contact_patterns(all_patterns=allp) == allp
-        out[allp] = _gpu_solve(s, w)
-    Xo, Uo, sto, _ = _oracle_solve(oracle64, w)
+        out[allp] = gpu_solve(s, w)
+    Xo, Uo, sto, _ = oracle_solve(oracle64, w)
     for allp in (False, True):
         X, U, st, _ = out[allp]
         assert np.array_equal(st, sto)
@@ -625,7 +581,7 @@ def test_device_rollout_is_the_same_under_every_kernel_variant(dev, monkeypatch)
 def test_option_argument_errors(dev):
     from iterative_learning_nmpc_amd import workloads as wl, _lib
     w = wl.centroidal_trot(B=2, N=50, seed=0)
-    s = _solver(w, 2, dev)
+    s = make_solver(w, 2, dev)
     t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params", "X", "U")}
     with pytest.raises(_lib.NmpcError, match="negative shift"):
         s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], t["X"], t["U"], shift=-1)

@@ -6,35 +6,12 @@ import os
 import numpy as np
 import pytest
 
+from tests.solve_helpers import policy_pair, rel
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-def _pair(n_in, n_out, L, hidden, bn, batch_max, seed=0):
-    """A DevicePolicy and an fp64 oracle with the same (random, non-trivial) parameters."""
-    from iterative_learning_nmpc_amd.policy import DevicePolicy
-    from oracle.policy_oracle import PolicyOracle
-    pol = DevicePolicy(n_in, n_out, L, hidden, bn, batch_max=batch_max, device="cuda:0", seed=seed)
-    o = PolicyOracle(n_in, n_out, L, hidden, bn, np.float64)
-    rng = np.random.default_rng(seed + 1)
-    theta, rm, rv = (t.cpu().numpy().astype(np.float64) for t in pol.get_parameters())
-    for name, shape, off in pol.items:                   # biases, gamma, beta away from their trivial start values
-        n = int(np.prod(shape))
-        if name.endswith(".b") or name.endswith(".beta"):
-            theta[off:off + n] = 0.1 * rng.standard_normal(n)
-        if name.endswith(".gamma"):
-            theta[off:off + n] = 1.0 + 0.1 * rng.standard_normal(n)
-    rm = 0.1 * rng.standard_normal(rm.shape); rv = 1.0 + 0.2 * rng.random(rv.shape)
-    pol.set_parameters(theta, rm, rv)
-    o.theta[:] = theta; o.running_mean[:] = rm; o.running_var[:] = rv
-    return pol, o
 
 
 @pytest.mark.parametrize("name", ["bn", "plain"])
@@ -74,7 +51,7 @@ def test_policy_matches_reference_vectors(name):
 def test_policy_forward_and_train_step_match_oracle(n_in, n_out, L, hidden, bn, B):
     """Full-size network of the reference's configuration (47 -> 3 x 512 -> 12, BatchNorm, batch 256 / 1000)
     and ragged shapes (tile remainders in every GEMM dimension)."""
-    pol, o = _pair(n_in, n_out, L, hidden, bn, batch_max=B + 3)
+    pol, o = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B + 3)
     rng = np.random.default_rng(5)
     dev = pol.device
     X = rng.standard_normal((B, n_in)); Y = rng.standard_normal((B, n_out))
@@ -109,7 +86,7 @@ def test_training_is_reproducible_run_to_run(n_in, n_out, L, hidden, bn, B):
     Y = torch.tensor(rng.standard_normal((5, B, n_out)), dtype=torch.float32, device="cuda:0")
     runs = []
     for _ in range(2):
-        pol, _o = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+        pol, _o = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
         losses = [pol.train_step(X[s], Y[s], 1e-3).item() for s in range(5)]
         runs.append((losses, [t.cpu().numpy() for t in pol.get_parameters()]))
     assert runs[0][0] == runs[1][0], (runs[0][0], runs[1][0])

@@ -13,7 +13,7 @@ roundings of fp32 and written down where it is asserted.  Every figure is printe
 import numpy as np
 import pytest
 
-from tests.test_gpu_policy import _pair
+from tests.solve_helpers import policy_pair
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -98,13 +98,13 @@ _cases = {}
 
 
 def case(shape):
-    """The device's gradient and both oracles' at two points -- the parameters of _pair and the parameters one Adam step later,
+    """The device's gradient and both oracles' at two points -- the parameters of policy_pair and the parameters one Adam step later,
     the oracles loaded with the device's fp32 theta and running statistics at each -- made once per shape and left unchanged:
     (blocks, [{g, v: device; g64, g32: oracles; margin: the smallest |ReLU input| of the float64 oracle}, ...])"""
     if shape not in _cases:
         from oracle.policy_oracle import PolicyOracle
         n_in, n_out, L, hidden, bn, B = shape
-        pol, o64 = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+        pol, o64 = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
         o32 = PolicyOracle(n_in, n_out, L, hidden, bn, F32)
         X, Y = batch(shape)
         x, y = on(pol, X), on(pol, Y)
@@ -197,7 +197,7 @@ def test_output_bias_gradient_counts_signs_exactly(shape):
     float32(0.1f * count / (B * n_out)) within 1 ulp (the device rounds the quotient, then the product)."""
     n_in, n_out, L, hidden, bn, B = shape
     X, Y = batch(shape)
-    twin, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+    twin, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
     _, pred = twin.train_step(on(twin, X), on(twin, Y), LR, return_pred=True)
     pred = pred.cpu().numpy()
     assert B % 2 == 0
@@ -205,7 +205,7 @@ def test_output_bias_gradient_counts_signs_exactly(shape):
     balanced = np.tile(np.where(np.arange(B) % 2 == 0, 1.0, -1.0).astype(F32)[:, None], (1, n_out))
     ragged = rng.choice(np.array([1.0, -1.0, 0.0], F32), size=(B, n_out), p=[0.45, 0.3, 0.25])
     for what, s in (("balanced", balanced), ("ties", ragged)):
-        pol, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+        pol, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
         target = pred + s                                            # s = 0: the prediction itself, bit for bit
         assert np.array_equal(np.sign(pred - target), -np.sign(s))
         loss, again = pol.train_step(on(pol, X), on(pol, target), LR, return_pred=True)
@@ -235,8 +235,8 @@ def adam_case():
         shape = (130, 70, 2, 100, True, 129)
         n_in, n_out, L, hidden, bn, B = shape
         X, Y = batch(shape, seed=8)
-        pol, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
-        twin, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+        pol, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
+        twin, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
         params = host(pol)
         _, gm, gv = device_gradient(twin, on(twin, X), on(twin, Y))
         _adam.update(pol=pol, params=params, x=on(pol, X), y=on(pol, Y), gm=gm, gv=gv)
@@ -307,7 +307,7 @@ def assert_identical(a, b, what):
 def test_set_parameters_resets_and_forward_and_loss_leave_the_state_alone():
     shape = (9, 4, 2, 65, True, 33)
     n_in, n_out, L, hidden, bn, B = shape
-    pol, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+    pol, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
     m, v, step = opt_state(pol)
     assert step == 0 and not m.any() and not v.any()                 # a fresh policy
     X, Y = batch(shape)
@@ -322,7 +322,7 @@ def test_set_parameters_resets_and_forward_and_loss_leave_the_state_alone():
     m, v, step = opt_state(pol)
     assert step == 0 and not m.any() and not v.any()
     # step 0 with zero moments is the state set_parameters leaves: the next step is the same either way
-    other, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+    other, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
     other.set_parameters(*pol.get_parameters())
     other.set_optimizer_state(before[3], before[4], 7)
     other.set_optimizer_state(np.zeros(pol.n_theta, F32), np.zeros(pol.n_theta, F32), 0)
@@ -338,8 +338,8 @@ def test_resume_from_saved_state_is_bit_identical(shape):
     from iterative_learning_nmpc_amd.policy import DevicePolicy
     n_in, n_out, L, hidden, bn, B = shape
     rng = np.random.default_rng(11)
-    whole, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
-    first, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+    whole, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
+    first, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
     X = on(whole, rng.standard_normal((5, B, n_in))); Y = on(whole, rng.standard_normal((5, B, n_out)))
     losses = [whole.train_step(X[s], Y[s], LR).item() for s in range(5)]
     resumed = [first.train_step(X[s], Y[s], LR).item() for s in range(3)]
@@ -359,8 +359,8 @@ def test_refused_optimizer_state_leaves_the_handle_usable():
     from iterative_learning_nmpc_amd._lib import NmpcError, ptr, stream
     shape = (9, 4, 2, 65, False, 33)
     n_in, n_out, L, hidden, bn, B = shape
-    pol, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
-    twin, _ = _pair(n_in, n_out, L, hidden, bn, batch_max=B)
+    pol, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
+    twin, _ = policy_pair(n_in, n_out, L, hidden, bn, batch_max=B)
     X, Y = batch(shape)
     x, y = on(pol, X), on(pol, Y)
     pol.train_step(x, y, LR); twin.train_step(x, y, LR)

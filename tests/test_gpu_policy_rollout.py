@@ -16,7 +16,7 @@ from oracle.policy_oracle import PolicyOracle
 from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import policy_rollout_reference as pr
-from tests.test_gpu_contact import Case, branches, ground, held, host, layer
+from tests.torque_helpers import Case, branches, ground, held, host, layer
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")

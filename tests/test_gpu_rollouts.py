@@ -4,20 +4,11 @@ for the solve itself, the CPU oracle.  BASELINE configs[3] per-GPU size at the e
 import numpy as np
 import pytest
 
+from tests.solve_helpers import dev, rel  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch.device("cuda:0")
 
 
 def _inputs(B, seed, push_scale=50.0):

@@ -4,52 +4,18 @@ fallback).  Contact schedules that hit every edge of that run logic, each solved
 default kernel and by the all-patterns kernel, against the fp64 oracle.
 
 Tolerances are those of tests/test_gpu_parity.py: status equal and 1e-5 relative L2 on X (or 1.5 x the fp32 oracle's own error,
-`_within_tolerance`) and on U against the fp64 oracle, as test_centroidal_solve_parity; 3e-5 between the default and the
+`within_tolerance`) and on U against the fp64 oracle, as test_centroidal_solve_parity; 3e-5 between the default and the
 all-patterns kernel, as test_all_contact_patterns_kernel_matches_default_and_oracle.  Every schedule was first solved by the
 fp64 oracle alone: no failed problem, finite trajectories (asserted again here, so the reference stays inside the comparison).
 """
 import numpy as np
 import pytest
 
+from tests.solve_helpers import dev, gpu_solve, make_solver, oracle_solve, rel, within_tolerance  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-# ---- restated from tests/test_gpu_parity.py (helpers and the tolerance of the centroidal solves) ----
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-def _within_tolerance(e, floor):
-    """1e-5 relative L2 against the fp64 oracle, or 1.5 x the fp32 oracle's own error where that approaches the bar"""
-    return e < 1e-5 or e < 1.5 * floor
-
-
-def _solver(w, dev):
-    from iterative_learning_nmpc_amd.solver import BatchedNmpcSolver
-    s = BatchedNmpcSolver(w.model_id, w.N, B, dev)
-    s.set_model_params(w.mp)
-    s.set_cost_weights(w.W, w.W_e, w.meta.get("reg", 1e-6), w.meta.get("reg_e", 1e-5))
-    s.set_max_iter(1)
-    s.set_max_qp_iter(6)
-    s.set_nlp_tol(0.0)
-    s.set_line_search(0)
-    return s
-
-
-def _gpu_solve(s, w):
-    t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params", "X", "U")}
-    X, U, st, stats = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], t["X"], t["U"])
-    torch.cuda.synchronize()
-    return X.cpu().numpy(), U.cpu().numpy(), st.cpu().numpy(), stats.cpu().numpy()
-
-
-def _oracle_solve(o, w):
-    return o.solve_batch(w.model_id, w.N, w.mp, o.opt(max_sqp_iter=1, n_ipm=6, yref_per_stage=1, reg=w.meta.get("reg", 1e-6),
-                                                      reg_e=w.meta.get("reg_e", 1e-5)),
-                         w.W, w.W_e, w.x0, w.yref, w.yref_e, w.params, w.X, w.U)
 
 
 B = 8
@@ -97,17 +63,11 @@ def _workload(schedule):
     return w
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch.device("cuda:0")
-
-
 @pytest.mark.parametrize("name", list(SCHEDULES))
 def test_run_sweep_schedule(dev, oracle64, oracle32, monkeypatch, name):
     w = _workload(SCHEDULES[name])
-    X64, U64, st64, _ = _oracle_solve(oracle64, w)
-    X32, U32, _, _ = _oracle_solve(oracle32, w)
+    X64, U64, st64, _ = oracle_solve(oracle64, w)
+    X32, U32, _, _ = oracle_solve(oracle32, w)
     # the reference itself solved the schedule: one SQP iteration without a tolerance ends as "iteration limit" (2), a
     # failed QP (4) or a NaN step (1) would not
     assert (st64 == 2).all() and np.isfinite(X64).all() and np.isfinite(U64).all()
@@ -115,16 +75,16 @@ def test_run_sweep_schedule(dev, oracle64, oracle32, monkeypatch, name):
     for variant in ("resident", "lean"):
         monkeypatch.setenv("NMPC_QP_VARIANT", variant)       # read by nmpc_create
         for allp in (False, True):
-            s = _solver(w, dev)
+            s = make_solver(w, B, dev)
             assert s.set_contact_patterns(all_patterns=allp) == allp
-            out[variant, allp] = _gpu_solve(s, w)
+            out[variant, allp] = gpu_solve(s, w)
     floor = rel(X32, X64)
     for key, (X, U, st, _) in out.items():
         eX, eU = rel(X, X64), rel(U, U64)
         print(f"{name} {key}: gpu-vs-f64 X {eX:.2e} U {eU:.2e}; f32-vs-f64 X {floor:.2e} U {rel(U32, U64):.2e}")
     for key, (X, U, st, _) in out.items():
         assert np.array_equal(st, st64), key
-        assert _within_tolerance(rel(X, X64), floor) and rel(U, U64) < 1e-5, (key, rel(X, X64), rel(U, U64), floor)
+        assert within_tolerance(rel(X, X64), floor) and rel(U, U64) < 1e-5, (key, rel(X, X64), rel(U, U64), floor)
     for allp in (False, True):                                # resident against lean: bit for bit
         for a, b in zip(out["resident", allp], out["lean", allp]):
             assert np.array_equal(a, b), allp

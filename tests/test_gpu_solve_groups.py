@@ -17,37 +17,11 @@ import numpy as np
 import pytest
 
 from tests import parity_groups as pg
+from tests.solve_helpers import dev, gpu_solve, make_solver  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-# ---- restated from tests/test_gpu_parity.py / tests/test_gpu_wholebody.py ----
-def _solver(w, B, dev, case):
-    from iterative_learning_nmpc_amd.solver import BatchedNmpcSolver
-    s = BatchedNmpcSolver(w.model_id, w.N, B, dev, precision=case.precision)
-    s.set_model_params(w.mp)
-    s.set_cost_weights(w.W, w.W_e, w.meta.get("reg", 1e-6), w.meta.get("reg_e", 1e-5))
-    s.set_max_iter(case.sqp)
-    s.set_max_qp_iter(case.n_ipm)
-    s.set_nlp_tol(0.0)
-    if w.model_id != 2:                       # the whole-body model takes full steps only
-        s.set_line_search(0)
-    return s
-
-
-def _gpu_solve(s, w, shift=0):
-    t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params", "X", "U")}
-    X, U, st, stats = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], t["X"], t["U"], shift=shift)
-    torch.cuda.synchronize()
-    return X.cpu().numpy(), U.cpu().numpy(), st.cpu().numpy(), stats.cpu().numpy()
 
 
 @pytest.mark.parametrize("case", pg.CASES, ids=lambda c: c.name)
@@ -68,10 +42,10 @@ def test_solve_parity_per_problem_and_group(dev, oracle64, oracle32, monkeypatch
         else:
             monkeypatch.setenv("NMPC_QP_VARIANT", variant)       # read by nmpc_create
         for allp in case.all_patterns:
-            s = _solver(w, case.B, dev, case)
+            s = make_solver(w, case.B, dev, precision=case.precision, max_sqp_iter=case.sqp, n_ipm=case.n_ipm)
             if allp is not None:
                 assert s.set_contact_patterns(all_patterns=allp) == allp
-            out[variant, allp] = _gpu_solve(s, w, shift=case.shift)
+            out[variant, allp] = gpu_solve(s, w, shift=case.shift)
 
     failures = []
     for allp in case.all_patterns:                                # the tables first: a failing case prints all of them

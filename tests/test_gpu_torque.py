@@ -5,18 +5,12 @@ import numpy as np
 import pytest
 
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.torque_helpers import layer
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 CTRL_TO_JOINT = [3, 4, 5, 0, 1, 2, 9, 10, 11, 6, 7, 8]          # ctrl [FR, FL, RR, RL] -> joints [FL, FR, RL, RR]
-
-
-def layer(m):
-    """The device layer for the arrays an oracle model holds."""
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    return BatchedTorqueLayer(m.parent, m.jtype, m.axis, m.R_fix, m.p_fix, m.mass, m.com, m.inertia, m.foot_joint, m.foot_offset,
-                              m.nu, gravity=m.gravity)
 
 
 def batch(m, B, seed):

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.solve_helpers import dev  # noqa: F401
+from tests.torque_helpers import bits, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -21,11 +23,6 @@ STEPS, N_SUB = 40, 2
 ONE, TWO, THREE, FIVE = 0.0395, 0.0795, 0.1195, 0.1995
 SOLVER, HEIGHT, COLLISION, SHIFT = 1, 8, 32, 8
 SENTINEL = -77.0
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return "cuda:0"
 
 
 @pytest.fixture(scope="module")
@@ -48,14 +45,6 @@ def start(B=3):
 def plant():
     from iterative_learning_nmpc_amd.torque import GroundContact
     return GroundContact()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def same(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 def rollout(mpc, L, q0, v0, T, **kw):

@@ -9,43 +9,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from iterative_learning_nmpc_amd import workloads as wl  # noqa: E402
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _solver(w, B, dev, **opts):
-    from iterative_learning_nmpc_amd.solver import BatchedNmpcSolver
-    s = BatchedNmpcSolver(w.model_id, w.N, B, dev)
-    s.set_model_params(w.mp)
-    s.set_cost_weights(w.W, w.W_e, w.meta["reg"], w.meta["reg_e"])
-    s.set_max_iter(opts.get("max_sqp_iter", 1))
-    s.set_max_qp_iter(opts.get("n_ipm", 6))
-    s.set_nlp_tol(opts.get("nlp_tol", 0.0))
-    return s
-
-
-def _gpu_solve(s, w, shift=0, X=None, U=None):
-    t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params")}
-    Xd, Ud = s.to_device(w.X if X is None else X), s.to_device(w.U if U is None else U)
-    Xd, Ud, st, stats = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], Xd, Ud, shift=shift)
-    torch.cuda.synchronize()
-    return Xd.cpu().numpy(), Ud.cpu().numpy(), st.cpu().numpy(), stats.cpu().numpy()
-
-
-def _oracle_solve(o, w, X=None, U=None, **opts):
-    kw = dict(max_sqp_iter=1, n_ipm=6, yref_per_stage=int(w.yref.ndim == 3), reg=w.meta["reg"], reg_e=w.meta["reg_e"])
-    kw.update(opts)
-    return o.solve_batch(w.model_id, w.N, w.mp, o.opt(**kw), w.W, w.W_e, w.x0, w.yref, w.yref_e, w.params,
-                         w.X if X is None else X, w.U if U is None else U)
+from tests.solve_helpers import dev, gpu_solve, make_solver, oracle_solve, rel  # noqa: E402,F401
 
 
 # (n_ipm, sqp): no inequalities / the reference's steady-state policy (mpc_opt.py:25-27) / a few SQP iterations /
@@ -54,15 +18,15 @@ def _oracle_solve(o, w, X=None, U=None, **opts):
 def test_wholebody_solve_parity(dev, oracle64, oracle32, n_ipm, sqp):
     B = 64
     w = wl.wholebody_trot(B=B, N=30, seed=0)
-    s = _solver(w, B, dev, n_ipm=n_ipm, max_sqp_iter=sqp)
-    X, U, st, stats = _gpu_solve(s, w)
-    Xo, Uo, sto, statso = _oracle_solve(oracle64, w, n_ipm=n_ipm, max_sqp_iter=sqp)
+    s = make_solver(w, B, dev, n_ipm=n_ipm, max_sqp_iter=sqp)
+    X, U, st, stats = gpu_solve(s, w)
+    Xo, Uo, sto, statso = oracle_solve(oracle64, w, n_ipm=n_ipm, max_sqp_iter=sqp)
     assert np.array_equal(st, sto)
     assert np.isfinite(X).all() and np.isfinite(U).all()
     # measured: 7.3e-6 / 3.5e-6 at (6, 1); 6e-7 / 1e-6 at (6, 3): the iteration contracts rounding differences
     assert rel(X, Xo) < 1e-5 and rel(U, Uo) < 1e-5, (rel(X, Xo), rel(U, Uo))
     assert np.allclose(stats[:, 0], statso[:, 0], rtol=2e-5)                   # cost at the last linearisation
-    X32, U32, st32, _ = _oracle_solve(oracle32, w, n_ipm=n_ipm, max_sqp_iter=sqp)
+    X32, U32, st32, _ = oracle_solve(oracle32, w, n_ipm=n_ipm, max_sqp_iter=sqp)
     # fp32 oracle: same algorithm in float with its own summation order -- both sit at the fp32 floor around fp64
     assert rel(X, X32) < 2e-5 and rel(U, U32) < 2e-5, (rel(X, X32), rel(U, U32))
     assert rel(X32, Xo) < 1e-5, rel(X32, Xo)
@@ -74,9 +38,9 @@ def test_wholebody_active_friction_pyramid(dev, oracle64):
     w = wl.wholebody_trot(B=B, N=30, seed=3)
     w.mp = w.mp.copy(); w.mp[6] = 0.15
     w.yref = w.yref.copy(); w.yref[:, :, 6] = 1.0
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=4)
-    X, U, st, _ = _gpu_solve(s, w)
-    Xo, Uo, sto, _ = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=4)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=4)
+    X, U, st, _ = gpu_solve(s, w)
+    Xo, Uo, sto, _ = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=4)
     assert np.array_equal(st, sto)
     f = Uo[:, :, 18:].reshape(B, 30, 4, 3)
     stance = w.params[:, :30, :4] > 0.5
@@ -103,9 +67,9 @@ def test_wholebody_any_contact_pattern(dev, oracle64):
     w.U[:, :, 18:] = 0.0
     w.U[:, :, 20::3] = c[:, :30] * (-w.mp[5] * w.mp[1]) / n_st
     w.yref[:, :, 52:64] = w.U[:, :, 18:]
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
-    X, U, st, _ = _gpu_solve(s, w)
-    Xo, Uo, sto, _ = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
+    X, U, st, _ = gpu_solve(s, w)
+    Xo, Uo, sto, _ = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2)
     assert np.array_equal(st, sto)
     assert rel(X, Xo) < 1e-5 and rel(U, Uo) < 1e-5, (rel(X, Xo), rel(U, Uo))
 
@@ -116,9 +80,9 @@ def test_wholebody_odd_batches_and_horizons(dev, oracle64, B, N):
     either side of the LDS budget that keeps the gains of two (N <= 43) or one (N >= 44) backward stages on the CU, and horizons
     no longer than that"""
     w = wl.wholebody_trot(B=B, N=N, seed=7)
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
-    X, U, st, stats = _gpu_solve(s, w)
-    Xo, Uo, sto, statso = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
+    X, U, st, stats = gpu_solve(s, w)
+    Xo, Uo, sto, statso = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2)
     assert np.array_equal(st, sto)
     assert rel(X, Xo) < 1e-5 and rel(U, Uo) < 1e-5, (rel(X, Xo), rel(U, Uo))
     # cost at the last linearisation, every node counted (N = 64: node 64 has no lane of its own), and the iteration count
@@ -132,18 +96,18 @@ def test_wholebody_foot_placement_cost(dev, oracle64):
     of the Jacobian image are exact zeros again)."""
     B = 32
     w = wl.wholebody_trot(B=B, N=30, seed=8, foot_placement=1.0e3)
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=3)
-    X, U, st, stats = _gpu_solve(s, w)
-    Xo, Uo, sto, statso = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=3)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=3)
+    X, U, st, stats = gpu_solve(s, w)
+    Xo, Uo, sto, statso = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=3)
     assert np.array_equal(st, sto)
     assert rel(X, Xo) < 1e-5 and rel(U, Uo) < 1e-5, (rel(X, Xo), rel(U, Uo))
     assert np.allclose(stats[:, 0], statso[:, 0], rtol=2e-5)
     w0 = wl.wholebody_trot(B=B, N=30, seed=8)
-    assert rel(X, _oracle_solve(oracle64, w0, n_ipm=6, max_sqp_iter=3)[0]) > 1e-3          # the cost term does something
+    assert rel(X, oracle_solve(oracle64, w0, n_ipm=6, max_sqp_iter=3)[0]) > 1e-3          # the cost term does something
     s.set_cost_weights(w0.W, w0.W_e, w0.meta["reg"], w0.meta["reg_e"])
-    X0, U0, _, _ = _gpu_solve(s, w0)
-    fresh = _solver(w0, B, dev, n_ipm=6, max_sqp_iter=3)
-    Xf, Uf, _, _ = _gpu_solve(fresh, w0)
+    X0, U0, _, _ = gpu_solve(s, w0)
+    fresh = make_solver(w0, B, dev, n_ipm=6, max_sqp_iter=3)
+    Xf, Uf, _, _ = gpu_solve(fresh, w0)
     assert np.array_equal(X0, Xf) and np.array_equal(U0, Uf)
 
 
@@ -152,9 +116,9 @@ def test_wholebody_stage_constant_reference(dev, oracle64):
     B = 8
     w = wl.wholebody_trot(B=B, N=30, seed=2)
     w.yref = np.ascontiguousarray(w.yref[:, 0, :])
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
-    X, U, st, _ = _gpu_solve(s, w)
-    Xo, Uo, sto, _ = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
+    X, U, st, _ = gpu_solve(s, w)
+    Xo, Uo, sto, _ = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=2)
     assert np.array_equal(st, sto)
     assert rel(X, Xo) < 1e-5 and rel(U, Uo) < 1e-5
 
@@ -164,18 +128,18 @@ def test_wholebody_warm_start_shift_folded(dev, oracle64):
     shift equals shifting the oracle's own previous solution first"""
     B = 16
     w = wl.wholebody_trot(B=B, N=30, seed=5)
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=1)
-    X1, U1, _, _ = _gpu_solve(s, w)
-    X2, U2, st2, _ = _gpu_solve(s, w, shift=1, X=X1, U=U1)
-    Xo1, Uo1, _, _ = _oracle_solve(oracle64, w)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=1)
+    X1, U1, _, _ = gpu_solve(s, w)
+    X2, U2, st2, _ = gpu_solve(s, w, shift=1, X=X1, U=U1)
+    Xo1, Uo1, _, _ = oracle_solve(oracle64, w)
     Xs, Us = oracle64.shift_warm_start(Xo1, Uo1, 1)
-    Xo2, Uo2, sto2, _ = _oracle_solve(oracle64, w, X=Xs, U=Us)
+    Xo2, Uo2, sto2, _ = oracle_solve(oracle64, w, X=Xs, U=Us)
     assert np.array_equal(st2, sto2)
     assert rel(X2, Xo2) < 1e-5 and rel(U2, Uo2) < 1e-5, (rel(X2, Xo2), rel(U2, Uo2))
     # shift of the whole horizon: nothing of the old inputs survives
-    X3, U3, _, _ = _gpu_solve(s, w, shift=30, X=X1, U=U1)
+    X3, U3, _, _ = gpu_solve(s, w, shift=30, X=X1, U=U1)
     Xs, Us = oracle64.shift_warm_start(Xo1, Uo1, 30)
-    Xo3, Uo3, _, _ = _oracle_solve(oracle64, w, X=Xs, U=Us)
+    Xo3, Uo3, _, _ = oracle_solve(oracle64, w, X=Xs, U=Us)
     assert rel(X3, Xo3) < 1e-5 and rel(U3, Uo3) < 1e-5
 
 
@@ -188,7 +152,7 @@ def test_wholebody_shift_zeroes_forces_and_keeps_accelerations(dev, oracle64):
     X = rng.standard_normal((B, N + 1, 42)).astype(np.float32)
     U = rng.standard_normal((B, N, 30)).astype(np.float32)
     w = wl.wholebody_trot(B=B, N=N, seed=0)
-    s = _solver(w, B, dev)
+    s = make_solver(w, B, dev)
     Xd, Ud = s.to_device(X), s.to_device(U)
     s.warm_start_solver(Xd, Ud, shift)
     torch.cuda.synchronize()
@@ -204,15 +168,15 @@ def test_wholebody_solves_are_bit_reproducible(dev):
     behind a uniform branch), which showed up as a run-to-run varying 5e-5 error."""
     B = 256
     w = wl.wholebody_trot(B=B, N=30, seed=4)
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=2)
     ref = None
     for _ in range(3):
-        X, U, st, stats = _gpu_solve(s, w)
+        X, U, st, stats = gpu_solve(s, w)
         if ref is None:
             ref = (X, U, st, stats)
         assert np.array_equal(X, ref[0]) and np.array_equal(U, ref[1]) and np.array_equal(st, ref[2]) and np.array_equal(stats, ref[3])
-    X, U, _, _ = _gpu_solve(s, w, shift=1, X=ref[0], U=ref[1])
-    X2, U2, _, _ = _gpu_solve(s, w, shift=1, X=ref[0], U=ref[1])
+    X, U, _, _ = gpu_solve(s, w, shift=1, X=ref[0], U=ref[1])
+    X2, U2, _, _ = gpu_solve(s, w, shift=1, X=ref[0], U=ref[1])
     assert np.array_equal(X, X2) and np.array_equal(U, U2)
 
 
@@ -220,9 +184,9 @@ def test_wholebody_early_exit_and_status(dev, oracle64):
     """status 0 once max|step| < nlp_tol, else 2; the same problems stop at the same iteration as the oracle"""
     B = 24
     w = wl.wholebody_trot(B=B, N=30, seed=9, sigma_joint=0.05)
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=12, nlp_tol=2e-2)
-    X, U, st, stats = _gpu_solve(s, w)
-    Xo, Uo, sto, statso = _oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=12, nlp_tol=2e-2)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=12, nlp_tol=2e-2)
+    X, U, st, stats = gpu_solve(s, w)
+    Xo, Uo, sto, statso = oracle_solve(oracle64, w, n_ipm=6, max_sqp_iter=12, nlp_tol=2e-2)
     assert set(np.unique(sto)) <= {0, 2}
     same = stats[:, 3] == statso[:, 3]
     # a problem whose step norm crosses the tolerance within rounding may stop one iteration apart: enumerate them
@@ -237,8 +201,8 @@ def test_wholebody_nan_input_is_reported_not_propagated(dev):
     w = wl.wholebody_trot(B=B, N=30, seed=1)
     w.x0 = w.x0.copy(); w.x0[2, 7] = np.nan
     w.X = w.X.copy(); w.X[2, :, 7] = np.nan
-    s = _solver(w, B, dev)
-    X, U, st, _ = _gpu_solve(s, w)
+    s = make_solver(w, B, dev)
+    X, U, st, _ = gpu_solve(s, w)
     assert st[2] == 1 and (st[[0, 1, 3]] == 2).all()
     assert np.isfinite(X[[0, 1, 3]]).all()
 
@@ -248,8 +212,8 @@ def test_wholebody_full_size_properties(dev, oracle64):
     and the first problems against the oracle."""
     B = 8192
     w = wl.wholebody_trot(B=B, N=30, seed=11)
-    s = _solver(w, B, dev, n_ipm=6, max_sqp_iter=1)
-    X, U, st, stats = _gpu_solve(s, w)
+    s = make_solver(w, B, dev, n_ipm=6, max_sqp_iter=1)
+    X, U, st, stats = gpu_solve(s, w)
     assert (st == 2).all() and np.isfinite(X).all() and np.isfinite(U).all()
     # a full step lands on the measured state: X[:, 0] = x0
     assert np.abs(X[:, 0] - w.x0).max() < 1e-5
@@ -269,7 +233,7 @@ def test_wholebody_full_size_properties(dev, oracle64):
     w8 = copy.copy(w)
     for k in ("x0", "yref", "yref_e", "params", "X", "U"):
         setattr(w8, k, getattr(w, k)[:n])
-    Xo, Uo, sto, _ = _oracle_solve(oracle64, w8)
+    Xo, Uo, sto, _ = oracle_solve(oracle64, w8)
     assert rel(X[:n], Xo) < 1e-5 and rel(U[:n], Uo) < 1e-5
 
 
@@ -290,8 +254,8 @@ def test_wholebody_mixed_precision(dev, oracle64, precision, sqp, lo, hi):
     s.set_model_params(w.mp)
     s.set_cost_weights(w.W, w.W_e, w.meta["reg"], w.meta["reg_e"])
     s.set_max_iter(sqp)
-    X, U, st, _ = _gpu_solve(s, w)
-    Xo, Uo, sto, _ = _oracle_solve(oracle64, w, max_sqp_iter=sqp)
+    X, U, st, _ = gpu_solve(s, w)
+    Xo, Uo, sto, _ = oracle_solve(oracle64, w, max_sqp_iter=sqp)
     eX, eU = rel(X, Xo), rel(U, Uo)
     print(f"precision {precision}, {sqp} SQP: rel-L2 X {eX:.2e} U {eU:.2e}")
     assert np.array_equal(st, sto)
@@ -310,10 +274,10 @@ def test_wholebody_api_limits(dev):
     with pytest.raises(NmpcError):
         BatchedNmpcSolver(wl.MODEL_CENTROIDAL, 50, 4, dev, precision=3)
     w = wl.wholebody_trot(B=2, N=30, seed=0)
-    s = _solver(w, 2, dev)
+    s = make_solver(w, 2, dev)
     s.set_line_search(True)
     with pytest.raises(NmpcError):
-        _gpu_solve(s, w)                                               # the whole-body model takes full steps
+        gpu_solve(s, w)                                               # the whole-body model takes full steps
 
 
 def _robot_state(seed=0):
@@ -357,7 +321,7 @@ def test_facade_optimize_is_the_oracle_solution_of_its_packed_problem(dev, oracl
     assert s.last_node == 1 and s.status[0] == sto2[0]
     assert rel(q2, Xo2[0, :, :18]) < 1e-5 and rel(f2.reshape(30, 12), Uo2[0, :, 18:]) < 1e-5
     # the same packed problem through the batched solver: the facade adds nothing of its own
-    X, U, st, _ = _gpu_solve(s._device_solver(), type("W", (), dict(
+    X, U, st, _ = gpu_solve(s._device_solver(), type("W", (), dict(
         x0=s._problem["x0"], yref=s._problem["yref"], yref_e=s._problem["yref_e"], params=s._problem["params"],
         X=s._problem["X"], U=s._problem["U"])))
     assert np.array_equal(X[0, :, :18].astype(np.float64), q2)

@@ -7,10 +7,7 @@ import numpy as np
 import pytest
 
 from iterative_learning_nmpc_amd import workloads as wl
-
-
-def rel(a, b):
-    return float(np.linalg.norm(np.asarray(a, float) - b) / np.linalg.norm(b))
+from tests.solve_helpers import rel
 
 
 def test_dims(oracle64):

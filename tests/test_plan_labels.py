@@ -1,6 +1,6 @@
 """Action labels of a whole-body plan, the parts that need no device: the C-ABI declarations, `references.plan_rows` (the
 declared meaning of "row j of a plan") against the host loop's own up-sampling, and the label formula on a case with a
-known answer.  "Oracle labels" (`oracle_labels`, used by the GPU tests too): plan_rows in fp64 -> oracle/torque_oracle.py
+known answer.  "Oracle labels" (`torque_helpers.oracle_labels`, used by the GPU tests too): plan_rows in fp64 -> oracle/torque_oracle.py
 on the declared tree -> (tau + kd v_j) / kp + q_j in fp64."""
 import os
 import re
@@ -9,37 +9,9 @@ import numpy as np
 
 from iterative_learning_nmpc_amd import references as refs
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.torque_helpers import oracle_labels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-_POOL = None
-
-
-def _oracle_chunk(args):
-    from oracle import torque_oracle as to
-    return to.id_torques_batch(*args)
-
-
-def _oracle_torques(m, q, v, a, f):
-    """oracle.torque_oracle.id_torques_batch, large batches cut into chunks for worker processes (the oracle is a Python loop
-    over samples, 5 ms each; the workers are spawned, not forked: they never see the parent's device)"""
-    global _POOL
-    n = len(q)
-    if n < 2000:
-        return _oracle_chunk((m, q, v, a, f))
-    if _POOL is None:
-        import multiprocessing as mp
-        _POOL = mp.get_context("spawn").Pool(min(16, os.cpu_count() or 1))
-    cuts = np.linspace(0, n, 65).astype(int)
-    return np.concatenate(_POOL.map(_oracle_chunk, [(m, q[i:j], v[i:j], a[i:j], f[i:j]) for i, j in zip(cuts[:-1], cuts[1:])]))
-
-
-def oracle_labels(m, X, U, zoh, dt_nodes, sim_dt, kp, kd):
-    """fp64 labels [.., n_steps, 12] of plans X, U on the oracle tree m, with the torques and the rows they were made from"""
-    q, v, a, f = refs.plan_rows(X, U, zoh, dt_nodes, sim_dt)
-    tau = _oracle_torques(m, q.reshape(-1, 18), v.reshape(-1, 18), a.reshape(-1, 18), f.reshape(-1, 4, 3)).reshape(q.shape[:-1] + (12,))
-    return (tau + kd * v[..., 6:]) / kp + q[..., 6:], tau, q, v
 
 
 def test_label_calls_are_declared_and_bound():

@@ -3,22 +3,10 @@ as a machine without a GPU decides: they are exported and bound with the declare
 as NMPC_E_ARG with a message in the policy family's error slot.  (A policy handle cannot be made without a device: the
 checks behind the handle -- null moments, a negative step -- and the copies are exercised in tests/test_gpu_policy_grad.py.)"""
 import ctypes
-import os
-import re
 
-import pytest
+from tests.abi_header import declaration, lib  # noqa: F401
 
 NEW = ("nmpc_policy_get_opt_state", "nmpc_policy_set_opt_state")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from iterative_learning_nmpc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
 
 
 def test_new_symbols_are_exported_and_bound(lib):
@@ -35,20 +23,10 @@ def test_signatures_mirror_the_header():
     """argument by argument, read from the header: pointers to device memory and the stream are void pointers in the
     binding, `long long *step` is a pointer to a long long, `long long step` a long long"""
     from iterative_learning_nmpc_amd import _lib
-    header = open(os.path.join(ROOT, "include", "nmpc_policy.h")).read()
     for name in NEW:
-        ret, params = re.search(r"^(\w+)\s+%s\(([^)]*)\);" % name, header, re.M).groups()
-        want = []
-        for decl in params.split(","):
-            decl = " ".join(decl.split())
-            if decl.startswith("long long *"):
-                want.append(ctypes.POINTER(ctypes.c_longlong))
-            elif "*" in decl:
-                want.append(ctypes.c_void_p)
-            else:
-                assert decl.startswith("long long "), decl
-                want.append(ctypes.c_longlong)
-        assert ret == "int" and _lib.SIGNATURES[name] == (ctypes.c_int, want), (name, want)
+        want = declaration("nmpc_policy.h", name)[1]                 # an `int name(...)`, or it is not found
+        assert ctypes.POINTER(ctypes.c_longlong) in want or ctypes.c_longlong in want
+        assert _lib.SIGNATURES[name] == (ctypes.c_int, want), (name, want)
 
 
 def test_a_null_handle_is_refused_with_a_message_in_the_family_slot(lib):

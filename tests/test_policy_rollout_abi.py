@@ -8,37 +8,14 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-C_TYPES = {"void *": ctypes.c_void_p, "const float *": ctypes.c_void_p, "float *": ctypes.c_void_p, "const double *": ctypes.c_void_p,
-           "int *": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
-           "const nmpc_contact_cfg *": ctypes.c_void_p, "const nmpc_policy_rollout_cfg *": ctypes.c_void_p}
+from tests.abi_header import ROOT, declaration, lib, struct_fields  # noqa: F401
+
 NAMES = ("nmpc_observe_batch", "nmpc_policy_rollout_batch")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from iterative_learning_nmpc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def header():
-    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "nmpc_torque.h")).read(), flags=re.S)      # comments aside
 
 
 def header_arguments(name):
     """The ctypes argument list the header's declaration of `name` asks for."""
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header())
-    assert m, f"{name} is not declared in include/nmpc_torque.h"
-    out = []
-    for a in m.group(1).split(","):
-        a = " ".join(a.split())
-        if not re.match(r"^(const )?\w+ \*?\w+$", a):          # "const double *s_mean, const double *s_std" style lists are split already;
-            raise AssertionError(a)                             # anything else is a declaration this parser does not read
-        out.append(C_TYPES[re.sub(r"\s*\w+$", "", a).strip()])
-    return out
+    return declaration("nmpc_torque.h", name)[1]
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -55,11 +32,7 @@ def test_argument_lists():
 
 def test_the_cfg_structure_has_the_headers_fields():
     from iterative_learning_nmpc_amd import _lib
-    body = re.search(r"typedef struct \{([^}]*)\} nmpc_policy_rollout_cfg;", header()).group(1)
-    fields = []
-    for decl in body.strip().rstrip(";").split(";"):
-        typ, names = decl.split(None, 1)
-        fields += [(n.strip(), {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double}[typ]) for n in names.split(",")]
+    fields = struct_fields("nmpc_torque.h", "nmpc_policy_rollout_cfg")
     assert [n for n, _ in fields] == ["n_steps", "n_sub", "dt", "kp", "kd", "t0", "period", "collision_height", "term_mask", "n_goal", "s_first"]
     assert list(_lib.NmpcPolicyRolloutCfg._fields_) == fields
 

@@ -3,20 +3,12 @@ they are exported and bound, and what their argument checks refuse on the host c
 in the policy family's error slot.  (A policy handle cannot be made without a device, so the checks behind the handle --
 widths, batch range, learning rate -- are exercised in tests/test_gpu_train_epoch.py.)"""
 import ctypes
-import os
 
 import pytest
 
+from tests.abi_header import lib, struct_fields  # noqa: F401
+
 NEW = ("nmpc_policy_train_epoch_scratch", "nmpc_policy_train_epoch", "nmpc_policy_loss")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from iterative_learning_nmpc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
 
 
 def test_new_symbols_are_exported_and_bound(lib):
@@ -31,21 +23,8 @@ def test_new_symbols_are_exported_and_bound(lib):
 
 def test_batch_source_mirrors_the_header():
     """field order and types of nmpc_batch_source, read from the header"""
-    import re
     from iterative_learning_nmpc_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "nmpc_policy.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} nmpc_batch_source;", header).group(1)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        pointer = "*" in decl
-        ctype = ctypes.c_void_p if pointer else ctypes.c_longlong if decl.startswith("long long") else ctypes.c_int
-        names = re.sub(r"^(const\s+)?(float|double|int|long long)\s*", "", decl)
-        fields += [(n.strip(" *"), ctype) for n in names.split(",")]
-    assert fields == list(_lib.NmpcBatchSource._fields_)
+    assert struct_fields("nmpc_policy.h", "nmpc_batch_source") == list(_lib.NmpcBatchSource._fields_)
 
 
 def test_epoch_and_loss_reject_bad_arguments_on_the_host(lib):
