@@ -10,6 +10,7 @@
 //   step()       x+ = phi(x,u,p)
 //   linearize()  x+ and the columns of A = dphi/dx, B = dphi/du through emit callbacks
 //   G(j,c), h(j), active_mask(), gdot()   the stage inequality  G u <= h  (linear in u)
+//   foot_terms()                           the barrier terms G'DG, G'v in closed form per foot (Centroidal)
 #pragma once
 #include "nmpc_tile.hpp"
 
@@ -71,6 +72,8 @@ struct DoubleIntegrator {
     __host__ __device__ static constexpr int common_variant(int i) { return i == 0 ? 0 : -1; }
     // MFMA steps of the barrier product that can hold active rows under an input mask (all: the box rows)
     __host__ __device__ static constexpr unsigned barrier_steps(unsigned) { return 0xFu; }
+    // no closed form of the barrier terms: the QP kernel keeps the matrix product Gs'[Gs | vt] for this model (Centroidal::foot_terms)
+    static constexpr bool FOOT_TERMS = false;
     __device__ static unsigned input_mask(const ModelParams&, const float*) { return 0x3u; }
 };
 
@@ -274,7 +277,7 @@ struct Centroidal {
     // of every quad -- with this order step i is "foot i, all four faces", so the steps of swing feet (all
     // rows inactive: exact zeros) can be left out where the contact pattern is a compile-time constant
     __host__ __device__ static constexpr int row_of(int f, int jj) { return 4 * jj + f; }
-    __device__ static float G(const ModelParams& mp, int j, int c) {
+    __host__ __device__ static float G(const ModelParams& mp, int j, int c) {
         const int f = j & 3, jj = j >> 2;
         const int d = c - 3 * f;
         return (d == (jj >> 1)) ? ((jj & 1) ? -1.f : 1.f) : (d == 2 ? -mp.mu : 0.f);
@@ -330,6 +333,37 @@ struct Centroidal {
             o[row_of(f, 2)] = __builtin_fmaf(-mp.mu, v[3 * f + 2], v[3 * f + 1]);
             o[row_of(f, 3)] = __builtin_fmaf(-mp.mu, v[3 * f + 2], -v[3 * f + 1]);
         }
+    }
+    // The barrier terms of foot f in closed form, from sq = sqrt(D) and vt = v/sqrt(D) by constraint row (exact zeros in
+    // inactive rows).  With the four faces [+-1, 0, -mu], [0, +-1, -mu] the foot's block of G'DG is symmetric 3 x 3 with a
+    // structurally zero xy entry, and G'v has three entries: eight numbers,
+    //   o = { xx, yy, zz, xz,   G'v x, G'v y, G'v z, yz }.
+    // Each is the chain that the fp32 matrix instruction runs for it in the product Gs'[Gs | vt], Gs = G.sqrt(D): from
+    // zero, one fmaf per face in row order row_of(f, 0..3), on the same operands; products with a structural zero of G
+    // add an exact zero there and are left out.  So the numbers carry the bits of the product (tests/test_barrier_terms.py);
+    // the QP kernel builds them lane = stage, off the serial stage sweep.  Its bf16 variant and the double integrator
+    // (FOOT_TERMS = false) keep the product.
+    static constexpr bool FOOT_TERMS = true;
+    __host__ __device__ static void foot_terms(const ModelParams& mp, int f, const float (&sq)[NG], const float (&vt)[NG],
+                                               float (&o)[8]) {
+#pragma clang fp contract(off)
+        float gx[2], gy[2], gz[4], v[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const float s = sq[row_of(f, jj)];
+            if (jj < 2) gx[jj] = G(mp, row_of(f, jj), 3 * f) * s;
+            else gy[jj - 2] = G(mp, row_of(f, jj), 3 * f + 1) * s;
+            gz[jj] = G(mp, row_of(f, jj), 3 * f + 2) * s;
+            v[jj] = vt[row_of(f, jj)];
+        }
+        o[0] = __builtin_fmaf(gx[1], gx[1], __builtin_fmaf(gx[0], gx[0], 0.0f));
+        o[1] = __builtin_fmaf(gy[1], gy[1], __builtin_fmaf(gy[0], gy[0], 0.0f));
+        o[2] = __builtin_fmaf(gz[3], gz[3], __builtin_fmaf(gz[2], gz[2], __builtin_fmaf(gz[1], gz[1], __builtin_fmaf(gz[0], gz[0], 0.0f))));
+        o[3] = __builtin_fmaf(gx[1], gz[1], __builtin_fmaf(gx[0], gz[0], 0.0f));
+        o[4] = __builtin_fmaf(gx[1], v[1], __builtin_fmaf(gx[0], v[0], 0.0f));
+        o[5] = __builtin_fmaf(gy[1], v[3], __builtin_fmaf(gy[0], v[2], 0.0f));
+        o[6] = __builtin_fmaf(gz[3], v[3], __builtin_fmaf(gz[2], v[2], __builtin_fmaf(gz[1], v[1], __builtin_fmaf(gz[0], v[0], 0.0f))));
+        o[7] = __builtin_fmaf(gy[1], gz[3], __builtin_fmaf(gy[0], gz[2], 0.0f));
     }
 };
 

@@ -264,8 +264,8 @@ struct Lds {
         // are one 16 B read (only the stage sweeps touch them after they are written)
         qv = o;  o += (N + 1) * TS;
         rv = o;  o += N * TS;
-        gsq = o; o += N * TS;
-        gvt = o; o += N * TS;
+        gsq = o; o += N * TS;                     // barrier terms of the interior-point iterate, 2 x 16 floats per stage:
+        gvt = o; o += N * TS;                     // eight numbers per foot (M::foot_terms), or sqrt(D) | v/sqrt(D) by row
         act = o; o += round4(NS);
         umk = o; o += round4(NS);
         runs = o; o += LEAN ? 0 : round4(N + 1);  // run-length schedule of the backward sweep (resident): at most N runs and the end word
@@ -448,6 +448,59 @@ __device__ __forceinline__ void batched(int n, int lane, Load&& ld, Store&& st) 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The barrier part of a stage's cost tiles (NextCost in nmpc_qp_kernel), one form per instantiation of the kernel.  b0, b1: the
+// lane's two 16 B reads of the stage's barrier rows; Rn, Sn: the tiles R and S~ = [0 r] they are added to.
+//   FOOT: the rows hold the terms ready, b0 = {xx, yy, zz, xz}, b1 = {G'v x, G'v y, G'v z, yz} of the foot of this lane's row
+//   quad (Centroidal::foot_terms).  mx / my / mz are 1 where the lane's column is the x / y / z force of that foot (it then
+//   takes entries of the foot's block of G'DG), mh where it is the homogeneous column (which takes G'v), else 0; at most one
+//   of a lane is 1, so each register takes ONE add: R + block entry, r + G'v.  Multipliers rather than select masks: a mask
+//   is an SGPR pair, and the stage bodies already spill scalars (measured: the same terms picked with selects cost the
+//   headline 5.6 %).  x.1 + y is x + y and x.0 + y is y bit for bit, the sign of a zero aside, which no sum here keeps.
+//   Otherwise: the rows hold sqrt(D) and vt = v/sqrt(D); with Gs = sqrt(D).G the tile T = Gs'[Gs | vt] holds G'DG in its
+//   columns < nu and G'v in column nx (the Gauss-Newton contraction of the barrier): ONE product on the matrix pipe, step(i)
+//   its K step i in fp32, or one bf16 instruction (BF16B); finish() splits it onto R and S~.
+// Same sums on the same bits in the two fp32 forms.
+template <bool FOOT, bool BF16B>
+struct BarrierTiles;
+template <bool BF16B>
+struct BarrierTiles<true, BF16B> {
+    float mx, my, mz, mh;
+    __device__ __forceinline__ void build(f32x4 b0, f32x4 b1, bool, f32x4& Rn, f32x4& Sn) {
+        Rn[0] = __builtin_fmaf(b0[3], mz, __builtin_fmaf(b0[0], mx, Rn[0]));
+        Rn[1] = __builtin_fmaf(b1[3], mz, __builtin_fmaf(b0[1], my, Rn[1]));
+        Rn[2] = __builtin_fmaf(b0[2], mz, __builtin_fmaf(b1[3], my, __builtin_fmaf(b0[3], mx, Rn[2])));
+#pragma unroll
+        for (int r = 0; r < 3; ++r) Sn[r] = __builtin_fmaf(b1[r], mh, Sn[r]);
+    }
+    __device__ __forceinline__ void step(int) {}
+    __device__ __forceinline__ void finish(bool, f32x4&, f32x4&) {}
+};
+template <bool BF16B>
+struct BarrierTiles<false, BF16B> {
+    f32x4 Gc;            // this lane's registers of the constraint matrix G (rows: constraints)
+    f32x4 Gs, Vt, Tb;
+    __device__ __forceinline__ void build(f32x4 b0, f32x4 b1, bool hx_col, f32x4&, f32x4&) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            Gs[r] = Gc[r] * b0[r];                  // rows >= ng: Gc = 0
+            Vt[r] = hx_col ? b1[r] : Gs[r];         // [Gs | vt]
+        }
+        Tb = zero4();
+    }
+    __device__ __forceinline__ void step(int i) {
+        if constexpr (!BF16B) Tb = __builtin_amdgcn_mfma_f32_16x16x4f32(Gs[i], Vt[i], Tb, 0, 0, 0);
+        else if (i == 0) Tb = xty_bf16(Gs, Vt);
+    }
+    __device__ __forceinline__ void finish(bool hx_col, f32x4& Rn, f32x4& Sn) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            Rn[r] += hx_col ? 0.0f : Tb[r];     // columns >= nu of Tb are zero
+            Sn[r] += hx_col ? Tb[r] : 0.0f;
+        }
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // QP + step of one SQP iteration: one problem per wavefront.
 // LEAN: LDS layout variant (Lds).  BF16B: the barrier product Gs'[Gs | vt] on the bf16 matrix pipe
 // (nmpc_dims.precision = 1, BASELINE configs[4]); everything else stays fp32.
@@ -498,6 +551,39 @@ void nmpc_qp_kernel(const SolveArgs a) {
     float* idle_sink = arr + SA_.total - 4;
     float* qv = smem + L.qv;   float* rv = smem + L.rv;
     float* gsq = smem + L.gsq; float* gvt = smem + L.gvt;
+    // Barrier terms of a stage as the stage sweep reads them.  FOOT (fp32 barrier of a model with the closed form per foot, one
+    // wave per SIMD): quad f of gsq / gvt holds the first / second four numbers of foot f (M::foot_terms) -- G'DG and G'v ready
+    // to add, built where every stage has a lane of its own (put_foot_terms).  Otherwise (bf16 barrier product, double
+    // integrator, lean variant): sqrt(D) and v/sqrt(D) by constraint row, and the sweep forms the product Gs'[Gs | vt] on the
+    // matrix pipe.  Lean keeps the product: with a second wave to fill the stage body's stalls it was never exposed, and the
+    // terms built lane = stage cost that variant 4.7 % at B = 8192 (its update phase spills: 16 -> 56 registers in scratch).
+    // The two are bit-identical (same chain, see foot_terms), as the variants have to be.
+    constexpr bool FOOT = M::FOOT_TERMS && !BF16B && !LEAN;
+    // Input: the stage's active rows, slacks s, multipliers lam, constraint values c and the barrier parameter tau:
+    //   D = lam/s, sq = sqrt(D), vt = (tau/s + lam + D c)/sqrt(D), exact zeros in inactive rows -- the same arithmetic as
+    // the by-row loops of the product path.  Foot by foot: four rows, eight numbers, two stores.
+    auto put_foot_terms = [&](int k, unsigned am, const float (&s)[NG], const float (&l)[NG], const float (&cc)[NG], float tau_k) {
+        if constexpr (FOOT) {
+            static_assert(!FOOT || (NG == 16 && NU == 12), "foot terms: four feet, quad f of the tiles = foot f");
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                float sq[NG] = {}, vt[NG] = {}, t[8];
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    const int j = M::row_of(f, jj);
+                    const bool on = (am >> j) & 1u;
+                    const float is = fast_rcp(s[j]);
+                    const float D = l[j] * is;
+                    const float rs = __builtin_amdgcn_rsqf(D);
+                    sq[j] = on ? D * rs : 0.0f;
+                    vt[j] = on ? __builtin_fmaf(D, cc[j], __builtin_fmaf(tau_k, is, l[j])) * rs : 0.0f;
+                }
+                M::foot_terms(a.mp, f, sq, vt, t);
+                *reinterpret_cast<f32x4*>(gsq + k * TS + 4 * f) = f32x4{t[0], t[1], t[2], t[3]};
+                *reinterpret_cast<f32x4*>(gvt + k * TS + 4 * f) = f32x4{t[4], t[5], t[6], t[7]};
+            }
+        }
+    };
     // ordering point between phases that exchange data between lanes: LDS traffic of a single wave
     // is ordered by issue; the workspace needs the stores drained first
     auto phase_sync = [&]() {
@@ -664,8 +750,13 @@ void nmpc_qp_kernel(const SolveArgs a) {
     // cost tiles of a stage are built with unconditional loads and selects (no branches)
     SweepLane sl;
     sl.init(conv, lane, HS, a.rs_free);
-    f32x4 Qc, Rc, Gc;            // constant parts: diag(Wx)+reg, diag(Wu)+reg, constraint matrix G
+    f32x4 Qc, Rc;                // constant parts: diag(Wx)+reg, diag(Wu)+reg
     bool qm[4], rm[4];           // masks: the register takes an element of q / r
+    BarrierTiles<FOOT, BF16B> bt;    // per-lane constants of the barrier, one form per instantiation
+    if constexpr (FOOT) {
+        bt.mx = (c == 4 * q4) ? 1.0f : 0.0f; bt.my = (c == 4 * q4 + 1) ? 1.0f : 0.0f;
+        bt.mz = (c == 4 * q4 + 2) ? 1.0f : 0.0f; bt.mh = (c == HS) ? 1.0f : 0.0f;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int row = 4 * q4 + r, ir = index_of(row);      // row slot and its logical index
@@ -674,7 +765,7 @@ void nmpc_qp_kernel(const SolveArgs a) {
         Rc[r] = (row == c && r_is_u) ? wr_c : 0.0f;
         qm[r] = (c == HS && r_is_x) || (row == HS && c_is_x);
         rm[r] = (c == HS && r_is_u);
-        Gc[r] = (row < NG && c_is_u) ? M::G(a.mp, row < NG ? row : 0, c_is_u ? ic : 0) : 0.0f;   // rows: constraints
+        if constexpr (!FOOT) bt.Gc[r] = (row < NG && c_is_u) ? M::G(a.mp, row < NG ? row : 0, c_is_u ? ic : 0) : 0.0f;
     }
     const bool is_hx_col = (c == HS);
     phase_sync();
@@ -751,7 +842,8 @@ void nmpc_qp_kernel(const SolveArgs a) {
             if (use_ipm) {
                 // barrier coefficients of this iteration, lane = stage:
                 //   D = lam/s, gsq = sqrt(D), gvt = (tau/s + lam + D c)/sqrt(D)
-                // so that the stage sweep only builds Gs = gsq.G and Vt = gvt.e_nx (no divides there)
+                // so that the stage sweep only builds Gs = gsq.G and Vt = gvt.e_nx (no divides there) -- or, FOOT, the
+                // barrier terms themselves (put_foot_terms)
                 tau = fmaxf(a.sigma * mu_sum / (float)n_act, a.tau_min);
                 // (with N <= 64 the update phase of the previous iteration has already written them)
                 if (ii == 0 || !one_stage_per_lane)
@@ -762,15 +854,21 @@ void nmpc_qp_kernel(const SolveArgs a) {
                     ld_row(sv, k, sk);
                     ld_row(lv, k, lk);
                     M::gdot(a.mp, uk, gk);
+                    if constexpr (FOOT) {
 #pragma unroll
-                    for (int j = 0; j < NG; ++j) {
-                        const bool on = (am >> j) & 1u;
-                        const float s = sk[j], l = lk[j], cj = gk[j] - M::h(a.mp, j);
-                        const float is = fast_rcp(s);
-                        const float D = l * is;
-                        const float rs = __builtin_amdgcn_rsqf(D);
-                        gsq[k * TS + j] = on ? D * rs : 0.0f;
-                        gvt[k * TS + j] = on ? __builtin_fmaf(D, cj, __builtin_fmaf(tau, is, l)) * rs : 0.0f;
+                        for (int j = 0; j < NG; ++j) gk[j] -= M::h(a.mp, j);      // c = G u - h
+                        put_foot_terms(k, am, sk, lk, gk, tau);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < NG; ++j) {
+                            const bool on = (am >> j) & 1u;
+                            const float s = sk[j], l = lk[j], cj = gk[j] - M::h(a.mp, j);
+                            const float is = fast_rcp(s);
+                            const float D = l * is;
+                            const float rs = __builtin_amdgcn_rsqf(D);
+                            gsq[k * TS + j] = on ? D * rs : 0.0f;
+                            gvt[k * TS + j] = on ? __builtin_fmaf(D, cj, __builtin_fmaf(tau, is, l)) * rs : 0.0f;
+                        }
                     }
                 }
                 phase_sync();
@@ -796,17 +894,18 @@ void nmpc_qp_kernel(const SolveArgs a) {
             // stage are built inside the current one.
             auto sweep = [&](auto ipm_tag) {
                 constexpr bool IPM = decltype(ipm_tag)::value;
-                // The additive cost tiles of a stage (NextCost of backward_stage): Q~ = [Q q; q' 0],
-                // S~ = [0 r], R, and with the barrier Gs = sqrt(D).G, vt = v/sqrt(D):
-                // T = Gs'[Gs | vt] holds G'DG in its columns < nu and G'v in column nx (ONE product, the
-                // Gauss-Newton contraction of the barrier); finish() splits it onto R and S~.
+                // The additive cost tiles of a stage (NextCost of backward_stage): Q~ = [Q q; q' 0], S~ = [0 r], R, and on R and
+                // S~ the barrier terms G'DG and G'v in the form of this instantiation (BarrierTiles): ready from the lane = stage
+                // phase (put_foot_terms) and added in build() -- no matrix instruction, nothing to wait for -- or as one product,
+                // mfma(i), that finish() folds in.
                 struct NextCost {
-                    f32x4 Gs, Vt, Tb, Qn, Sn, Rn;
-                    const float *qrow, *rrow, *sqrow, *vtrow;   // 16 B of this lane's row quad of q, r, sqrt(D), vt
+                    f32x4 Qn, Sn, Rn;
+                    const float *qrow, *rrow, *sqrow, *vtrow;   // 16 B of this lane's row quad of q, r and the two barrier rows
                     const float* qcol;                          // q at this lane's column slot
                     const bool *qm, *rm;
-                    f32x4 Qc, Rc, Gc;
+                    f32x4 Qc, Rc;
                     bool hx_col;
+                    BarrierTiles<FOOT, BF16B> bt;
                     f32x4 q4v, r4v, sq4, vt4;
                     float qcv;
                     __device__ __forceinline__ void fetch() {
@@ -825,27 +924,13 @@ void nmpc_qp_kernel(const SolveArgs a) {
                             Qn[r] = Qc[r] + (qm[r] ? (hx_col ? q4v[r] : qcv) : 0.0f);
                             Sn[r] = rm[r] ? r4v[r] : 0.0f;
                         }
-                        if constexpr (IPM) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                Gs[r] = Gc[r] * sq4[r];                  // rows >= ng: Gc = 0
-                                Vt[r] = hx_col ? vt4[r] : Gs[r];         // [Gs | vt]
-                            }
-                            Tb = zero4();
-                        }
+                        if constexpr (IPM) bt.build(sq4, vt4, hx_col, Rn, Sn);
                     }
                     __device__ __forceinline__ void mfma(int i) {
-                        if constexpr (IPM && !BF16B) Tb = __builtin_amdgcn_mfma_f32_16x16x4f32(Gs[i], Vt[i], Tb, 0, 0, 0);
-                        if constexpr (IPM && BF16B) { if (i == 0) Tb = xty_bf16(Gs, Vt); }
+                        if constexpr (IPM) bt.step(i);
                     }
                     __device__ __forceinline__ void finish() {
-                        if constexpr (IPM) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                Rn[r] += hx_col ? 0.0f : Tb[r];     // columns >= nu of Tb are zero
-                                Sn[r] += hx_col ? Tb[r] : 0.0f;
-                            }
-                        }
+                        if constexpr (IPM) bt.finish(hx_col, Rn, Sn);
                     }
                 };
                 auto next_cost = [&](int kk) {
@@ -854,7 +939,7 @@ void nmpc_qp_kernel(const SolveArgs a) {
                     nc.sqrow = gsq + kk * TS + 4 * q4; nc.vtrow = gvt + kk * TS + 4 * q4;
                     nc.qcol = qv + kk * TS + c;
                     nc.qm = qm; nc.rm = rm;
-                    nc.Qc = Qc; nc.Rc = Rc; nc.Gc = Gc; nc.hx_col = is_hx_col;
+                    nc.Qc = Qc; nc.Rc = Rc; nc.bt = bt; nc.hx_col = is_hx_col;
                     return nc;
                 };
                 ImageLane<M> il;
@@ -909,7 +994,7 @@ void nmpc_qp_kernel(const SolveArgs a) {
                         // (it eliminates every pivot for real), all four steps, and no extra code on the common path
                         auto run = [&](auto mask_tag) {
                             constexpr unsigned MK = decltype(mask_tag)::value;
-                            constexpr unsigned STEPS = (IPM && !BF16B && MK != DYNAMIC_MASK) ? M::barrier_steps(MK) : 0xFu;
+                            constexpr unsigned STEPS = (IPM && !FOOT && !BF16B && MK != DYNAMIC_MASK) ? M::barrier_steps(MK) : 0xFu;
                             return backward_stage<NU, MK, true, ALLV, STEPS, LEAN ? 0 : 2>(P, A0, B0, T0, Qt, St, Rt, conv, sl, lane,
                                                                             cm & 0xFFFFu, Kk, Acl, sh SST_PASS);
                         };
@@ -967,7 +1052,7 @@ void nmpc_qp_kernel(const SolveArgs a) {
                     auto run_stages = [&](auto mask_tag, int top, int len) {
                         constexpr unsigned MK = decltype(mask_tag)::value;
                         constexpr bool DYN = (MK == DYNAMIC_MASK);
-                        constexpr unsigned STEPS = (IPM && !BF16B && !DYN) ? M::barrier_steps(MK) : 0xFu;
+                        constexpr unsigned STEPS = (IPM && !FOOT && !BF16B && !DYN) ? M::barrier_steps(MK) : 0xFu;
                         unsigned cm = 0u;       // coupling mask of the stage: the fallback body alone reads it
                         if constexpr (DYN) cm = __builtin_amdgcn_readfirstlane(umask[top - 1]);
                         for (int k = top - 1; k >= top - len; --k) {
@@ -1189,18 +1274,22 @@ void nmpc_qp_kernel(const SolveArgs a) {
                 }
                 if (ii + 1 < n_sweeps && live) {
                     const float tau_n = fmaxf(a.sigma * mu_sum / (float)n_act, a.tau_min);
-                    float sq[NG], vt[NG];
+                    if constexpr (FOOT) {
+                        put_foot_terms(k, am, s, l, cc, tau_n);
+                    } else {
+                        float sq[NG], vt[NG];
 #pragma unroll
-                    for (int j = 0; j < NG; ++j) {
-                        const bool on = (am >> j) & 1u;
-                        const float is = fast_rcp(s[j]);
-                        const float D = l[j] * is;
-                        const float rs = __builtin_amdgcn_rsqf(D);
-                        sq[j] = on ? D * rs : 0.0f;
-                        vt[j] = on ? __builtin_fmaf(D, cc[j], __builtin_fmaf(tau_n, is, l[j])) * rs : 0.0f;
+                        for (int j = 0; j < NG; ++j) {
+                            const bool on = (am >> j) & 1u;
+                            const float is = fast_rcp(s[j]);
+                            const float D = l[j] * is;
+                            const float rs = __builtin_amdgcn_rsqf(D);
+                            sq[j] = on ? D * rs : 0.0f;
+                            vt[j] = on ? __builtin_fmaf(D, cc[j], __builtin_fmaf(tau_n, is, l[j])) * rs : 0.0f;
+                        }
+#pragma unroll
+                        for (int j = 0; j < NG; ++j) { gsq[k * TS + j] = sq[j]; gvt[k * TS + j] = vt[j]; }
                     }
-#pragma unroll
-                    for (int j = 0; j < NG; ++j) { gsq[k * TS + j] = sq[j]; gvt[k * TS + j] = vt[j]; }
                 }
                 phase_sync();
             } else if (use_ipm) {
