@@ -327,6 +327,46 @@ int nmpc_wb_rollout_set_actions(void *handle, void *torque_handle, const int *zo
 int nmpc_wb_rollout_set_plant(void *handle, void *torque_handle, const nmpc_contact_cfg *ground, int n_sub, float kp, float kd,
                               const int *zoh, float *Aw, float *Qw, float *Vw);
 
+/* DAgger relabelling: the expert's labels for states somebody else's rollout visited (nmpc_policy_rollout_batch with
+ * nmpc_policy_rollout_set_states, include/nmpc_torque.h).  For every state (b, k) -- robot b < B, row k < n_rows -- the
+ * expert's FIRST solve from that state (cold start, max_sqp iterations at nlp_tol) and the PD target it would apply from it:
+ *   prepare  nmpc_wb_label_prepare_kernel, one block per problem m = b n_rows + k: the problem nmpc_wb_rollout_batch prepares
+ *            for a rollout in plant state Q, V[b][k] whose replan stands at node[k] (the node-0 rule of setup_initial_feet_pos
+ *            where node[k] = 0) and whose integrated base reference is ref_state[b] advanced by ref_steps[k] simulation steps
+ *            (a private copy: ref_state is read only) -- the same device functions, so bit for bit that problem;
+ *   solve    on this handle's kernels, in chunks of at most B_max problems in the order of m (the last one may be ragged);
+ *            X, U hold one chunk, so after the call the plans of the LAST chunk; status[b][k] of every state;
+ *   label    per chunk nmpc_plan_actions_batch(torque_handle, chunk, n_steps = 1, .., a_rows = 1) on the chunk's X, U: label
+ *            row 0 of a plan, the target applied from the state its solve started from (the plant-mode pairing of
+ *            nmpc_wb_rollout_set_plant), lands in A[b][k] = A + (b * a_rows + k) * 12.
+ * Skipped: with failed given, a robot whose stamp s = failed[b] >> NMPC_ROLLOUT_TERM_SHIFT is not zero has fallen at the
+ * observation of control step s - 1, and its states k >= s - 1 are left out -- their A, status, X and U stay as they are and
+ * they cost no solve.  The chunk's flags live in a buffer of the handle (sized by nmpc_create: the call allocates nothing) and
+ * are used for the solves of this call only: what nmpc_set_skip holds for the caller's own solves is as it was afterwards.
+ * Stream-ordered, never synchronises, leaves the caller's device as it was.  B is not bounded by B_max.
+ * NMPC_E_ARG before any launch (text in nmpc_last_error): a handle that is not NMPC_MODEL_WHOLEBODY with line_search = 0; a
+ * torque handle on another device or with another tree than 18 joints / 12 actuated / 4 feet; n_rows < 1; qv_rows < n_rows or
+ * a_rows < n_rows; kp = 0; a NULL among the pointers but failed; sim_dt beyond the horizon; X or U not 8 B aligned. */
+typedef struct {
+    int n_rows, nodes_per_cycle, max_sqp;      /* K states per robot; max_sqp = 15: every label is a first solve */
+    float nlp_tol;                             /* nlp_tol / 10, as the first solve */
+    double sim_dt, time_horizon, nom_height, height_offset;
+    float step_height;
+    int force_reference_gravity;
+    float kp, kd;                              /* gains of the PD target, as nmpc_wb_rollout_set_plant */
+    int terminate_mask;                        /* the mask the stamps of failed were made under; the cut reads the stamp alone */
+} nmpc_wb_label_cfg;
+int nmpc_wb_label_states_batch(void *handle, void *torque_handle, int B, const nmpc_wb_label_cfg *cfg,
+        const signed char *gait, const signed char *peaks,      /* dev int8 [4][nodes_per_cycle] */
+        const int *node, const int *ref_steps,                  /* dev int [K]: per row index, shared by the robots */
+        const float *Q, const float *V, int qv_rows,            /* dev, row k of robot b at (b*qv_rows + k)*18 */
+        const double *v_des, const double *w_des, const double *ref_state,   /* dev [B][3], [B][3], [B][12] at simulation step 0; read only */
+        const float *joint_ref, const int *failed,              /* dev [12]; dev int [B] or NULL */
+        const int *zoh,                                         /* dev int [1]: hold index of simulation step 0 */
+        float *A, int a_rows, int *status,                      /* dev [B][a_rows][12], dev int [B][K] */
+        float *X, float *U,                                     /* dev workspace / out: [min(B*K, B_max)][N+1][42], [..][N][30] */
+        void *stream);
+
 /* Problems to leave out of the following *_batch solves of this handle: flags dev int[B_max] (or NULL: none); a problem
  * with flags[b] & mask != 0 is skipped by every kernel -- its X, U, status, stats stay as they are and it costs no
  * time.  The flags are read when the kernels run (stream order), so the caller may update them between calls without

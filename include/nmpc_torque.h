@@ -156,6 +156,15 @@ int nmpc_policy_rollout_batch(void *torque, void *policy, int B, const nmpc_poli
                               int *failed,                        /* dev [B], sticky, caller zeroes; NULL allowed */
                               void *stream);
 
+/* The plant states beside a policy rollout: the attach idiom of nmpc_wb_rollout_set_actions (nmpc.h).  While Q, V (dev, caller-
+ * owned, kept as pointers) are attached, every nmpc_policy_rollout_batch of this handle writes the plant state BEFORE control
+ * step k to Q + (b * qv_rows + k) * 18, and V alike -- nmpc_contact_track_batch's row convention, so row k goes with row k of S
+ * and A; these are the states a solver can start from (the 44-slot rows drop x, y and the Euler layout).  One strided-copy launch
+ * per control step; every other output of the rollout is bit for bit what it is without.  Q = V = NULL detaches; detached, the
+ * launches of a rollout are exactly what they are without this call, and nmpc_policy_rollout_cfg is unchanged.  A rollout with
+ * only one of Q / V attached, or with qv_rows < n_steps, returns NMPC_E_ARG before any launch. */
+int nmpc_policy_rollout_set_states(void *torque, float *Q, float *V, int qv_rows);
+
 /* A table of PD targets tracked on the contact plant [decl]: n_steps control steps in one launch, control step k being n_sub
  * substeps of nmpc_contact_step_batch's law with q_des = row k of robot b's table, at A + (b * a_rows + k) * 12 (a_rows >=
  * n_steps; 12 = n_actuated).  With the label rows of nmpc_plan_actions_batch as the table, A = (tau_id + kd v_plan) / kp + q_plan,

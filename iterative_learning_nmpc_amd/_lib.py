@@ -55,6 +55,8 @@ SIGNATURES = {
                                     c_void_p, c_float, c_float, c_void_p]),
     "nmpc_rollout_batch": (c_int, [c_void_p, c_int, c_void_p] + [c_void_p] * 14),
     "nmpc_wb_rollout_batch": (c_int, [c_void_p, c_int, c_void_p] + [c_void_p] * 16),
+    "nmpc_wb_label_states_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_void_p] * 6 + [c_int] + [c_void_p] * 7
+                                   + [c_int] + [c_void_p] * 4),
     # include/nmpc_policy.h
     "nmpc_policy_create": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "nmpc_policy_destroy": (None, [c_void_p]),
@@ -96,6 +98,7 @@ SIGNATURES = {
                                    c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "nmpc_policy_rollout_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_policy_rollout_set_states": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "nmpc_contact_track_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "nmpc_observe_rows_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double,
@@ -161,6 +164,13 @@ class NmpcWbRolloutCfg(ctypes.Structure):
                 ("height_offset", ctypes.c_double), ("step_height", c_float), ("push_start", c_float), ("push_duration", c_float),
                 ("record_sim_steps", c_int), ("force_reference_gravity", c_int), ("nominal_period", c_float),
                 ("terminate_mask", c_int), ("collision_height", c_float)]
+
+
+class NmpcWbLabelCfg(ctypes.Structure):
+    _fields_ = [("n_rows", c_int), ("nodes_per_cycle", c_int), ("max_sqp", c_int), ("nlp_tol", c_float),
+                ("sim_dt", ctypes.c_double), ("time_horizon", ctypes.c_double), ("nom_height", ctypes.c_double),
+                ("height_offset", ctypes.c_double), ("step_height", c_float), ("force_reference_gravity", c_int),
+                ("kp", c_float), ("kd", c_float), ("terminate_mask", c_int)]
 
 
 class NmpcDims(ctypes.Structure):

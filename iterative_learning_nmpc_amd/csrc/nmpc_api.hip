@@ -16,6 +16,7 @@
 #include "nmpc_aux.hip.inc"
 #include "nmpc_rollout.hip.inc"
 #include "nmpc_wb_rollout.hip.inc"
+#include "nmpc_wb_label.hip.inc"
 
 namespace {
 
@@ -32,6 +33,7 @@ struct Handle {
     size_t ws_stride = 0;    // floats per problem
     float* dbg = nullptr;    // diagnostic builds only (nmpc_debug_set_buffer)
     float* roll = nullptr;   // rollout problem tensors: x0 alias, yref, yref_e, params (B_max sized)
+    int* label_skip = nullptr;   // nmpc_wb_label_states_batch: per-problem skip flags of a chunk (B_max sized)
     int n_cu = 256;          // compute units of the device
     int force_variant = 0;   // NMPC_QP_VARIANT: 0 chosen per call by batch size and horizon (launch_solve), 1 resident, 2 lean (tests, tuning)
     int all_patterns = 0;    // nmpc_set_contact_patterns: 1 = kernel with a static stage body per contact pattern
@@ -266,6 +268,8 @@ int allocate(Handle* h) {
     const int N = h->dims.N;
     const size_t per = (size_t)N * h->ny + h->nye + (size_t)(N + 1) * (h->np > 0 ? h->np : 1) + h->nx;   // yref, yref_e, params, x0 of the rollouts
     NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&h->roll), ((size_t)h->dims.B_max * per + 16) * sizeof(float)));   // (+ the 16 B roundings of the carve-up)
+    NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&h->label_skip), (size_t)h->dims.B_max * sizeof(int)));
+    NMPC_TRY(no_handle, hipMemset(h->label_skip, 0, (size_t)h->dims.B_max * sizeof(int)));
     return NMPC_OK;
 }
 }  // namespace
@@ -337,6 +341,7 @@ void nmpc_destroy(void* handle) {
     if (guard.err != hipSuccess) fail(no_handle, NMPC_E_HIP, std::string("nmpc_destroy: ") + hipGetErrorString(guard.err));
     if (h->ws) (void)hipFree(h->ws);
     if (h->roll) (void)hipFree(h->roll);
+    if (h->label_skip) (void)hipFree(h->label_skip);
     delete h;
 }
 
@@ -676,6 +681,77 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
                                        nullptr, failed, cfg->n_replans - 1, cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK, st);
     if (frc) return fail(h, frc, std::string("nmpc_observe_batch: ") + nmpc_torque_last_error(pl.torque));
     return NMPC_OK;
+}
+
+int nmpc_wb_label_states_batch(void* handle, void* torque_handle, int B, const nmpc_wb_label_cfg* cfg, const signed char* gait,
+                               const signed char* peaks, const int* node, const int* ref_steps, const float* Q, const float* V,
+                               int qv_rows, const double* v_des, const double* w_des, const double* ref_state,
+                               const float* joint_ref, const int* failed, const int* zoh, float* A, int a_rows, int* status, float* X,
+                               float* U, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    if (B == 0) return NMPC_OK;
+    if (!cfg || !gait || !peaks || !node || !ref_steps || !Q || !V || !v_des || !w_des || !ref_state || !joint_ref || !zoh || !A || !status ||
+        !X || !U)
+        return fail(h, NMPC_E_ARG, "null argument");
+    if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_wb_label_states_batch needs the whole-body model");
+    if (h->line_search) return fail(h, NMPC_E_ARG, "the whole-body model takes full steps (line_search = 0)");
+    if (const int rc = check_configured(h)) return rc;
+    if (const char* why = nmpc_torque::label_states_refusal(torque_handle, cfg->n_rows, qv_rows, a_rows, zoh, cfg->kp, h->device))
+        return fail(h, NMPC_E_ARG, std::string("labels: ") + why);
+    const int N = h->dims.N, K = cfg->n_rows, B_max = h->dims.B_max;
+    if (B < 0 || (long long)B * K > 0x7fffffffLL) return fail(h, NMPC_E_ARG, "B out of range");
+    if (cfg->nodes_per_cycle < 1 || cfg->max_sqp < 1 || !(cfg->sim_dt > 0) || !(cfg->time_horizon > 0))
+        return fail(h, NMPC_E_ARG, "label configuration out of range");
+    const double dt_nodes = cfg->time_horizon / N;
+    if (cfg->sim_dt > N * dt_nodes * (1.0 + 1e-9)) return fail(h, NMPC_E_ARG, "sim_dt beyond the horizon");
+    if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(U)) & 7u) != 0)      // launch_wb's rule, in front of the first launch
+        return fail(h, NMPC_E_ARG, "whole-body arrays must be 8 B aligned (params: 16 B)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    NMPC_ENTER(h, h->device);
+    if (const int rc = clean_workspace(h, st)) return rc;
+    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };       // the carve-up of nmpc_wb_rollout_batch
+    nmpc::wb::WbLabelArgs r{};
+    r.K = K; r.N = N; r.npc = cfg->nodes_per_cycle; r.qv_rows = qv_rows;
+    r.force_gravity = cfg->force_reference_gravity ? 1 : 0;
+    r.step_height = cfg->step_height;
+    r.sim_dt = cfg->sim_dt; r.t_horizon = cfg->time_horizon; r.nom_height = cfg->nom_height; r.height_offset = cfg->height_offset;
+    r.mp = h->mp;
+    r.gait = gait; r.peaks = peaks; r.node = node; r.ref_steps = ref_steps; r.failed = failed; r.Q = Q; r.V = V; r.joint_ref = joint_ref;
+    r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state;
+    r.yref = h->roll;
+    r.yref_e = r.yref + up4((size_t)B_max * N * h->ny);
+    r.params = r.yref_e + up4((size_t)B_max * h->nye);
+    r.x0 = r.params + up4((size_t)B_max * (N + 1) * h->np);
+    r.X = X; r.U = U; r.skip = h->label_skip;
+    nmpc::wb::WbArgs w = wb_args(h);
+    w.yref_per_stage = 1; w.shift = 0;
+    w.x0 = r.x0; w.yref = r.yref; w.yref_e = r.yref_e; w.params = r.params; w.X = X; w.U = U; w.stats = nullptr;
+    w.max_sqp = cfg->max_sqp; w.nlp_tol = cfg->nlp_tol;
+    // the states behind a termination cost no solve: the chunk's own flags for the duration of its solve, whatever nmpc_set_skip
+    // holds for the caller's solves (the handle's setting is not written, so there is nothing to put back)
+    w.skip = h->label_skip; w.skip_mask = 1;
+    const long long total = (long long)B * K;
+    for (long long m0 = 0; m0 < total; m0 += B_max) {
+        const int count = (int)(total - m0 < B_max ? total - m0 : B_max);
+        r.m0 = (int)m0;
+        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_label_prepare_kernel, dim3(count), dim3(64), 0, st, r);
+        w.B = count; w.status = status + m0;
+        if (const int rc = launch_wb(h, w, st)) return rc;
+        // label row 0 of every plan of the chunk: the target applied from the state its solve started from.  Problem m = b K + k
+        // goes to A[b][k]; where the table has exactly K rows per robot that is row m of a dense table, otherwise robot by robot
+        for (long long m = m0; m < m0 + count;) {
+            const long long b = m / K, k = m - b * K;
+            const int run = a_rows == K ? count : (int)((K - k < m0 + count - m) ? K - k : m0 + count - m);
+            const size_t i = (size_t)(m - m0);
+            const int lrc = nmpc_plan_actions_batch(torque_handle, run, 1, N, X + i * (N + 1) * nmpc::wb::NX, U + i * N * nmpc::wb::NU, zoh, dt_nodes,
+                                                    cfg->sim_dt, cfg->kp, cfg->kd, nullptr, h->label_skip + i, 1,
+                                                    A + ((size_t)b * a_rows + k) * 12, 1, st);
+            if (lrc) return fail(h, lrc, std::string("nmpc_plan_actions_batch: ") + nmpc_torque_last_error(torque_handle));
+            m += run;
+        }
+    }
+    return launched(h);
 }
 
 int nmpc_debug_set_buffer(void* handle, float* dev_buffer) {

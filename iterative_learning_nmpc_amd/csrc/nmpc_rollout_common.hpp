@@ -100,22 +100,28 @@ __device__ inline void base_ref_vel_tracking_dev(double px, double py, double ya
 // The window of the gait table that starts at the current node (contact_planner.py:121-149), by the 64 threads of a block: per
 // node k <= N the contact flags of the four feet at cflag[f * STRIDE + k] (and the swing-peak flags at pflag, where peaks is
 // given), and the share of `weight` that each standing foot carries.  stand_first: every foot stands at the very first node of
-// a rollout (setup_initial_feet_pos, solver.py:199-200).  The caller synchronises.
+// a rollout (setup_initial_feet_pos, solver.py:199-200).  The caller synchronises.  The node is an argument: a rollout step has
+// one per launch (below), the labeller one per problem (nmpc_wb_label.hip.inc).
 template <int STRIDE>
-__device__ inline void contact_window(const RolloutCommon& a, int tid, const signed char* peaks, bool stand_first, float weight,
-                                      float* cflag, float* pflag, float* fshare) {
+__device__ inline void contact_window(const signed char* gait, int npc, int N, int node, int tid, const signed char* peaks,
+                                      bool stand_first, float weight, float* cflag, float* pflag, float* fshare) {
 #pragma clang fp contract(off)
-    for (int k = tid; k <= a.N; k += 64) {
+    for (int k = tid; k <= N; k += 64) {
         float n = 0.0f;
         for (int f = 0; f < 4; ++f) {
-            float c = (float)a.gait[f * a.npc + (a.node + k) % a.npc];
-            if (stand_first && a.node == 0 && k == 0) c = 1.0f;
+            float c = (float)gait[f * npc + (node + k) % npc];
+            if (stand_first && node == 0 && k == 0) c = 1.0f;
             cflag[f * STRIDE + k] = c;
-            if (peaks) pflag[f * STRIDE + k] = (float)peaks[f * a.npc + (a.node + k) % a.npc];
+            if (peaks) pflag[f * STRIDE + k] = (float)peaks[f * npc + (node + k) % npc];
             n += c;
         }
         fshare[k] = weight / fmaxf(n, 1.0f);
     }
+}
+template <int STRIDE>
+__device__ inline void contact_window(const RolloutCommon& a, int tid, const signed char* peaks, bool stand_first, float weight,
+                                      float* cflag, float* pflag, float* fshare) {
+    contact_window<STRIDE>(a.gait, a.npc, a.N, a.node, tid, peaks, stand_first, weight, cflag, pflag, fshare);
 }
 
 // check_unsafe_state_v2 (Rollout_combined_controller.py:367-431) on a recorded state, in fp32: the flag bits it raises.
@@ -170,21 +176,25 @@ __device__ inline void apply_push(float* v3, const RolloutCommon& a, int b, floa
         for (int i = 0; i < 3; ++i) v3[i] += a.push_force[b * 3 + i] * a.push_dt / mass;
 }
 
-// integrate the base reference of rollout b over the replanning interval (mpc.py:204-208, one simulation step at a time)
+// one simulation step of the integrated base reference rs[12] (increment_base_ref_position, mpc.py:204-208)
+__device__ inline void base_reference_step(double* rs, const double (&v_des)[3], double wz, double sim_dt) {
+#pragma clang fp contract(off)
+    double R[9];
+    rpy_matrix(rs[5], rs[4], rs[3], R);
+    const double vx = np_round(R[0] * v_des[0] + R[1] * v_des[1] + R[2] * v_des[2], 10.0);
+    const double vy = np_round(R[3] * v_des[0] + R[4] * v_des[1] + R[5] * v_des[2], 10.0);
+    rs[0] += vx * sim_dt;
+    rs[1] += vy * sim_dt;
+    rs[3] += wz * sim_dt;
+}
+
+// integrate the base reference of rollout b over the replanning interval, one simulation step at a time
 __device__ inline void integrate_base_reference(const RolloutCommon& a, int b) {
 #pragma clang fp contract(off)
     double* rs = a.ref_state + (size_t)b * 12;
     const double v_des[3] = {a.v_des[b * 3], a.v_des[b * 3 + 1], a.v_des[b * 3 + 2]};
     const double wz = a.w_des[b * 3 + 2];
-    for (int s = 0; s < a.replanning_steps; ++s) {
-        double R[9];
-        rpy_matrix(rs[5], rs[4], rs[3], R);
-        const double vx = np_round(R[0] * v_des[0] + R[1] * v_des[1] + R[2] * v_des[2], 10.0);
-        const double vy = np_round(R[3] * v_des[0] + R[4] * v_des[1] + R[5] * v_des[2], 10.0);
-        rs[0] += vx * a.sim_dt;
-        rs[1] += vy * a.sim_dt;
-        rs[3] += wz * a.sim_dt;
-    }
+    for (int s = 0; s < a.replanning_steps; ++s) base_reference_step(rs, v_des, wz, a.sim_dt);
 }
 
 }  // namespace nmpc

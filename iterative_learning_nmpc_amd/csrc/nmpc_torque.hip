@@ -367,6 +367,10 @@ struct Torque {
     int ct_width = 32;                  // robots per block of contact_step_kernel: ct_block_width(n)
     float* act = nullptr;               // [act_rows][nu]: the actions of nmpc_policy_rollout_batch when its caller keeps none
     int act_rows = 0;
+    struct {                            // nmpc_policy_rollout_set_states: the plant states beside a policy rollout (Q == nullptr: none)
+        float *Q = nullptr, *V = nullptr;
+        int rows = 0;
+    } states;
     std::string err;
 };
 
@@ -479,6 +483,13 @@ const char* nmpc_torque::plan_actions_refusal(void* handle, int n_steps, const i
     if (!(kp != 0.0f)) return "kp must not be zero";
     if (device >= 0 && t->device != device) return "the torque handle lives on another device";
     return nullptr;
+}
+
+const char* nmpc_torque::label_states_refusal(void* handle, int n_rows, int qv_rows, int a_rows, const int* zoh, float kp, int device) {
+    if (n_rows < 1) return "n_rows must be at least 1";
+    if (qv_rows < n_rows) return "qv_rows must be at least n_rows";
+    if (a_rows < n_rows) return "a_rows must be at least n_rows";
+    return plan_actions_refusal(handle, 1, zoh, kp, device);
 }
 
 const char* nmpc_torque::contact_track_refusal(void* handle, const nmpc_contact_cfg* ground, int n_sub, float dt, int device) {
@@ -688,6 +699,14 @@ int nmpc_observe_rows_batch(void* handle, int B, int n_rows, const float* Q, con
     return launched(h);
 }
 
+int nmpc_policy_rollout_set_states(void* torque, float* Q, float* V, int qv_rows) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    t->states = {};
+    if (Q || V) { t->states.Q = Q; t->states.V = V; t->states.rows = qv_rows; }
+    return NMPC_OK;
+}
+
 int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_policy_rollout_cfg* cfg, const nmpc_contact_cfg* ground,
                               float* q, float* v, const float* tau_ff, const float* goal, const double* s_mean, const double* s_std,
                               float* S, float* A, float* X, int* failed, void* stream) {
@@ -710,6 +729,9 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
         return fail(t, NMPC_E_ARG, "the policy must map 44 + n_goal inputs to 12 actions");
     if (B > d.batch_max) return fail(t, NMPC_E_ARG, "B exceeds the policy's batch_max");
     if (policy_device != t->device) return fail(t, NMPC_E_ARG, "the policy lives on another device");
+    const auto& rec = t->states;
+    if (!rec.Q != !rec.V) return fail(t, NMPC_E_ARG, "states: Q and V come together or not at all");
+    if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
         NMPC_ENTER(t, t->device);
@@ -727,6 +749,13 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
                                               cfg->term_mask, stream))
             return rc;
         if (!rows) break;
+        if (rec.Q) {                    // the state before control step k, beside row k of S and A
+            NMPC_ENTER(t, t->device);
+            const size_t n = (size_t)B * t->host.n;
+            hipLaunchKernelGGL(state_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, t->host.n,
+                               q, v, rec.Q + (size_t)k * t->host.n, rec.V + (size_t)k * t->host.n, (size_t)rec.rows * t->host.n);
+            if (const int rc = launched(t)) return rc;
+        }
         if (const int rc = nmpc_policy_forward(policy, B, X, t->act, stream)) {
             const char* why = nmpc_policy_last_error(policy);
             return fail(t, rc, std::string("nmpc_policy_forward: ") + (why ? why : ""));

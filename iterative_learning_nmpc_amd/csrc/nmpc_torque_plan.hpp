@@ -11,6 +11,11 @@ namespace nmpc_torque {
 // otherwise the text nmpc_torque_last_error would give
 const char* plan_actions_refusal(void* handle, int n_steps, const int* zoh, float kp, int device);
 
+// nullptr if nmpc_wb_label_states_batch (include/nmpc.h) can label n_rows states per robot with this handle: the one-step
+// nmpc_plan_actions_batch of every plan is accepted (handle, zoh, kp, device as above) and the tables have their rows
+// (qv_rows >= n_rows, a_rows >= n_rows, n_rows >= 1); otherwise the text nmpc_last_error gives
+const char* label_states_refusal(void* handle, int n_rows, int qv_rows, int a_rows, const int* zoh, float kp, int device);
+
 // nullptr if nmpc_contact_track_batch with rows Q, V and nmpc_observe_rows_batch accept (handle, ground, n_sub, dt) and the handle
 // lives on `device` (-1: any device); otherwise the text nmpc_torque_last_error would give
 const char* contact_track_refusal(void* handle, const nmpc_contact_cfg* ground, int n_sub, float dt, int device);

@@ -105,6 +105,17 @@ __global__ __launch_bounds__(TPB) void observe_kernel(const Model* __restrict__ 
     }
 }
 
+// row k of the [B][rows][n] tables Q, V from the dense [B][n] plant state (nmpc_policy_rollout_set_states): Q, V point at row k
+// of robot 0
+__global__ __launch_bounds__(256) void state_rows_kernel(int B, int n, const float* __restrict__ q, const float* __restrict__ v,
+                                                         float* __restrict__ Q, float* __restrict__ V, size_t stride) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)B * n) return;
+    const size_t b = e / n, j = b * stride + (e - b * n);
+    Q[j] = q[e];
+    V[j] = v[e];
+}
+
 // row k of a [B][rows][nu] table from the dense [B][nu] actions of one control step: dst points at row k of robot 0
 __global__ __launch_bounds__(256) void action_rows_kernel(int B, int nu, const float* __restrict__ src, float* __restrict__ dst, int stride) {
     const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -19,7 +19,8 @@
 //                                    the kernel only keeps the flags, applies the push and integrates the reference
 // What the two plants share -- the arguments of a rollout step, the fp64 base references, the contact window, the unsafe-state
 // predicates, the bookkeeping of failed[b], the push and the reference integration -- is in nmpc_rollout_common.hpp; here are
-// forward kinematics, momentum, the 44-slot row, the joint limits and the label hold kernel.  Included by nmpc_api.hip.
+// forward kinematics, momentum, the 44-slot row, the joint limits and the label hold kernel, and what the prepare kernel shares
+// with the labeller's (nmpc_wb_label.hip.inc): the measured state and the write-out of a gathered problem.  Included by nmpc_api.hip.
 
 #include "nmpc_rollout_common.hpp"
 #include "nmpc_wb_plan.hpp"
@@ -73,78 +74,97 @@ __device__ inline void wb_momentum(const ModelParams& mp, const double* q, const
     }
 }
 
+// What a block gathers of one problem before it writes it out -- the rollout's prepare kernel below and the labeller's
+// (nmpc_wb_label.hip.inc) fill it from different places and write it with one text.
+struct WbProblem {
+    float ref[12], ref_e[12], cflag[4 * 65], pflag[4 * 65], fshare[65], x0s[NX], feet[12];
+    int first_swing[4];
+};
+struct WbProblemOut {                     // the problem's own slices of the tensors of the solve
+    float *yref, *yref_e, *params, *x0, *X, *U;
+};
+
+// x0 = [q, v, h_g(q, v)] and the feet of the plant state (qf, vf), by one thread
+__device__ inline void wb_measured_state(const ModelParams& mp, const float* qf, const float* vf, WbProblem& P) {
+    double q[18], v[18], p[12], h[6];
+    for (int i = 0; i < 18; ++i) { q[i] = qf[i]; v[i] = vf[i]; }
+    wb_feet_world(mp, q, p);
+    wb_momentum(mp, q, v, h);
+    for (int i = 0; i < 12; ++i) P.feet[i] = (float)p[i];
+    for (int i = 0; i < 18; ++i) { P.x0s[WQ + i] = qf[i]; P.x0s[WV + i] = vf[i]; }
+    for (int i = 0; i < 6; ++i) P.x0s[WH + i] = (float)h[i];
+}
+
+// references, parameters, x0 and node 0 of the guess from a gathered problem, by the 64 threads of its block; cold: the rest of the
+// guess is zero.  Synchronises first: the caller has filled ref, ref_e, the windows, x0s and feet.
+__device__ inline void wb_write_problem(WbProblem& P, int tid, int N, const float* joint_ref, float step_height, int force_gravity,
+                                        float height_offset, bool cold, const WbProblemOut& o) {
+    __syncthreads();
+    if (tid < 4) {      // a foot in contact at node 0 keeps its position up to its next swing node; np.argmin: never swings -> 0 nodes
+        int fs = 0;
+        if (P.cflag[tid * 65] > 0.5f) {
+            for (int k = 0; k <= N; ++k)
+                if (P.cflag[tid * 65 + k] < 0.5f) { fs = k; break; }
+        }
+        P.first_swing[tid] = fs;
+    }
+    __syncthreads();
+    for (int e = tid; e < N * NY; e += 64) {
+        const int k = e / NY, i = e - k * NY;
+        float val = 0.0f;
+        if (i < RY_JOINT) val = P.ref[i];                                                   // base (12)
+        else if (i < RY_JOINT + 12) val = joint_ref[i - RY_JOINT];                          // joint positions; rates 0 (solver.py:175-177)
+        else if (i >= RY_SWING && i < RY_FREG) val = step_height;                           // swing height (solver.py:170)
+        else if (i >= RY_FREG && i < RY_CNT && force_gravity && (i - RY_FREG) % 3 == 2)     // [decl] option: weight share instead of the reference's zero
+            val = P.cflag[((i - RY_FREG) / 3) * 65 + k] * P.fshare[k];
+        o.yref[e] = val;
+    }
+    for (int i = tid; i < NYE; i += 64) {
+        float val = 0.0f;
+        if (i < RE_JOINT) val = P.ref_e[i];
+        else if (i < RE_JOINT + 12) val = joint_ref[i - RE_JOINT];
+        else if (i >= RE_SWING && i < RE_CNT) val = step_height;
+        o.yref_e[i] = val;
+    }
+    for (int e = tid; e < (N + 1) * NP; e += 64) {
+        const int k = e / NP, i = e - k * NP;
+        float val;
+        if (i < 4) val = P.cflag[i * 65 + k];
+        else if (i < 8) val = P.pflag[(i - 4) * 65 + k];
+        else {
+            const int f = (i - 8) / 3, c = (i - 8) % 3;
+            val = (k < P.first_swing[f]) ? P.feet[3 * f + c] : (c == 2 ? height_offset : 0.0f);     // solver.py:212-225,194-210
+        }
+        o.params[e] = val;
+    }
+    if (tid < NX) {
+        o.x0[tid] = P.x0s[tid];
+        // set_initial_state: node 0 of the guess is the measured state (a fixed point of the warm-start shift map)
+        o.X[tid] = P.x0s[tid];
+    }
+    if (cold) {         // first solve: the views are zero but for node 0 (solver.py:386-388: no warm start)
+        for (int e = NX + tid; e < (N + 1) * NX; e += 64) o.X[e] = 0.0f;
+        for (int e = tid; e < N * NU; e += 64) o.U[e] = 0.0f;
+    }
+}
+
 // one block (64 threads) per rollout
 __global__ __launch_bounds__(64) void nmpc_wb_rollout_prepare_kernel(const WbRolloutArgs a) {
-    __shared__ float ref[12], ref_e[12], cflag[4 * 65], pflag[4 * 65], fshare[65], x0s[NX], feet[12];
-    __shared__ int first_swing[4];
+    __shared__ WbProblem P;
     const int b = blockIdx.x, tid = threadIdx.x, N = a.N;
     if (a.failed[b] & a.term_mask) return;
     const float* qf = a.q + (size_t)b * 18;
     const float* vf = a.v + (size_t)b * 18;
     if (tid == 0) {
         base_ref_vel_tracking_dev((double)qf[0], (double)qf[1], (double)qf[3], a.ref_state + (size_t)b * 12, a.v_des + (size_t)b * 3,
-                                  a.w_des + (size_t)b * 3, a.t_horizon, a.nom_height + a.height_offset, ref, ref_e);
+                                  a.w_des + (size_t)b * 3, a.t_horizon, a.nom_height + a.height_offset, P.ref, P.ref_e);
     } else if (tid == 1) {
-        double q[18], v[18], p[12], h[6];
-        for (int i = 0; i < 18; ++i) { q[i] = qf[i]; v[i] = vf[i]; }
-        wb_feet_world(a.mp, q, p);
-        wb_momentum(a.mp, q, v, h);
-        for (int i = 0; i < 12; ++i) feet[i] = (float)p[i];
-        for (int i = 0; i < 18; ++i) { x0s[WQ + i] = qf[i]; x0s[WV + i] = vf[i]; }
-        for (int i = 0; i < 6; ++i) x0s[WH + i] = (float)h[i];
+        wb_measured_state(a.mp, qf, vf, P);
     }
-    contact_window<65>(a, tid, a.peaks, true, -a.mp.gz * a.mp.mass, cflag, pflag, fshare);
-    __syncthreads();
-    if (tid < 4) {      // a foot in contact at node 0 keeps its position up to its next swing node; np.argmin: never swings -> 0 nodes
-        int fs = 0;
-        if (cflag[tid * 65] > 0.5f) {
-            for (int k = 0; k <= N; ++k)
-                if (cflag[tid * 65 + k] < 0.5f) { fs = k; break; }
-        }
-        first_swing[tid] = fs;
-    }
-    __syncthreads();
-    float* yr = a.yref + (size_t)b * N * NY;
-    float* pr = a.params + (size_t)b * (N + 1) * NP;
-    for (int e = tid; e < N * NY; e += 64) {
-        const int k = e / NY, i = e - k * NY;
-        float val = 0.0f;
-        if (i < RY_JOINT) val = ref[i];                                                     // base (12)
-        else if (i < RY_JOINT + 12) val = a.joint_ref[i - RY_JOINT];                        // joint positions; rates 0 (solver.py:175-177)
-        else if (i >= RY_SWING && i < RY_FREG) val = a.step_height;                         // swing height (solver.py:170)
-        else if (i >= RY_FREG && i < RY_CNT && a.force_gravity && (i - RY_FREG) % 3 == 2)   // [decl] option: weight share instead of the reference's zero
-            val = cflag[((i - RY_FREG) / 3) * 65 + k] * fshare[k];
-        yr[e] = val;
-    }
-    for (int i = tid; i < NYE; i += 64) {
-        float val = 0.0f;
-        if (i < RE_JOINT) val = ref_e[i];
-        else if (i < RE_JOINT + 12) val = a.joint_ref[i - RE_JOINT];
-        else if (i >= RE_SWING && i < RE_CNT) val = a.step_height;
-        a.yref_e[(size_t)b * NYE + i] = val;
-    }
-    for (int e = tid; e < (N + 1) * NP; e += 64) {
-        const int k = e / NP, i = e - k * NP;
-        float val;
-        if (i < 4) val = cflag[i * 65 + k];
-        else if (i < 8) val = pflag[(i - 4) * 65 + k];
-        else {
-            const int f = (i - 8) / 3, c = (i - 8) % 3;
-            val = (k < first_swing[f]) ? feet[3 * f + c] : (c == 2 ? (float)a.height_offset : 0.0f);     // solver.py:212-225,194-210
-        }
-        pr[e] = val;
-    }
-    if (tid < NX) {
-        a.x0[(size_t)b * NX + tid] = x0s[tid];
-        // set_initial_state: node 0 of the guess is the measured state (a fixed point of the warm-start shift map)
-        a.X[(size_t)b * (N + 1) * NX + tid] = x0s[tid];
-    }
-    if (a.first) {      // first solve: the views are zero but for node 0 (solver.py:386-388: no warm start)
-        float* Xb = a.X + (size_t)b * (N + 1) * NX;
-        float* Ub = a.U + (size_t)b * N * NU;
-        for (int e = NX + tid; e < (N + 1) * NX; e += 64) Xb[e] = 0.0f;
-        for (int e = tid; e < N * NU; e += 64) Ub[e] = 0.0f;
-    }
+    contact_window<65>(a, tid, a.peaks, true, -a.mp.gz * a.mp.mass, P.cflag, P.pflag, P.fshare);
+    wb_write_problem(P, tid, N, a.joint_ref, a.step_height, a.force_gravity, (float)a.height_offset, a.first != 0,
+                     {a.yref + (size_t)b * N * NY, a.yref_e + (size_t)b * NYE, a.params + (size_t)b * (N + 1) * NP,
+                      a.x0 + (size_t)b * NX, a.X + (size_t)b * (N + 1) * NX, a.U + (size_t)b * N * NU});
 }
 
 // one thread per rollout

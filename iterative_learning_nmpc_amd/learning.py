@@ -8,7 +8,9 @@ The pieces are `collect.collect_rollouts` (rollouts -> `DeviceDatabase`, with th
 row), `DevicePolicy.train_epoch` (an epoch of weighted batches in one library call) and `DevicePolicy.loss` (the
 validation loss).  No table, batch, index or loss passes through the host, and nothing here waits for the device: what
 comes back are device tensors.  `evaluate_policy` closes the loop on the declared contact plant: the trained policy drives
-the robots, and what comes back is who stayed up and which states the learner visited.
+the robots, and what comes back is who stayed up and which states the learner visited.  `dagger_iteration` joins the two
+halves: the learner's rollout, the expert's labels for the states it visited (`LocomotionMPC.label_states`), aggregate, train --
+where `learning_iteration` aggregates the expert's own rollouts (behaviour cloning with pushes).
 
 Declared choices:
   * Sampling is WITH replacement, as the reference's WeightedRandomSampler loader draws
@@ -25,7 +27,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import NMPC_ROLLOUT_TERM_SHIFT
+from ._lib import NMPC_ROLLOUT_TERM_SHIFT, NMPC_STATUS_NAN, NMPC_STATUS_QP
 from .collect import collect_rollouts
 from .config import TERMINATE_DEFAULT
 from .torque import NOMINAL_PERIOD, GroundContact
@@ -85,7 +87,7 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
 
 def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, tau_ff=None, kp: float = KP,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
-                    terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08):
+                    terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -95,14 +97,65 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
         steps_survived  int32 [B]: control steps before the observation that terminated the robot (all of them if none did)
         S, A            [B, n_steps, 44], [B, n_steps, 12]: the states visited and the actions taken -- the rows of a
                         terminated robot from its stamp on are those of a fallen robot; cut there
-        q, v            [B, 18]: the state after the last control step."""
+        q, v            [B, 18]: the state after the last control step
+        Q, V            with record_states=True, [B, n_steps, 18]: the plant state before every control step, row k the state
+                        row k of S was made of (`BatchedTorqueLayer.set_rollout_states`, attached for this call) -- what
+                        `LocomotionMPC.label_states` starts the expert's solves from."""
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
     if n_steps < 1:
         raise ValueError(f"T = {T} s is shorter than one control step of {n_sub} x {dt} s")
-    q, v, S, A, failed = layer.policy_rollout(policy, q0, v0, n_steps, dt, n_sub, goal, tau_ff=tau_ff, kp=kp, kd=kd,
-                                              ground=GroundContact() if ground is None else ground, t0=t0,
-                                              period=NOMINAL_PERIOD if period is None else period, db=db,
-                                              terminate_mask=terminate_mask, collision_height=collision_height)
+    states = {}
+    if record_states:
+        B = torch.as_tensor(q0).reshape(-1, layer.n).shape[0]
+        states = {k: torch.empty(B, n_steps, layer.n, dtype=torch.float32, device=layer.device) for k in ("Q", "V")}
+        layer.set_rollout_states(states["Q"], states["V"])
+    try:
+        q, v, S, A, failed = layer.policy_rollout(policy, q0, v0, n_steps, dt, n_sub, goal, tau_ff=tau_ff, kp=kp, kd=kd,
+                                                  ground=GroundContact() if ground is None else ground, t0=t0,
+                                                  period=NOMINAL_PERIOD if period is None else period, db=db,
+                                                  terminate_mask=terminate_mask, collision_height=collision_height)
+    finally:
+        if record_states:
+            layer.set_rollout_states(None)
     stamp = failed >> NMPC_ROLLOUT_TERM_SHIFT
     return dict(failed=failed, survived=stamp == 0, steps_survived=torch.where(stamp == 0, torch.full_like(stamp, n_steps), stamp - 1),
-                S=S, A=A, q=q, v=v)
+                S=S, A=A, q=q, v=v, **states)
+
+
+def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, kp: Optional[float] = None,
+                     kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
+                     n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0):
+    """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
+        1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
+           [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
+           given with `set_command`);
+        2. `mpc.label_states` on the visited Q, V with dt_row = n_sub dt and the rollout's `failed`: the expert's first solve
+           from every state up to each robot's termination and the PD target it would apply from it;
+        3. the rows (S[b, k], A*[b, k], goal[b]) with k < steps_survived[b] whose solve neither ended in NaN nor in a QP failure
+           are appended to `db` with weight 1 -- chosen by a mask and `nonzero` on the device, in (b, k) order;
+        4. `train_network` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows, as
+           `learning_iteration` does.
+    kp, kd: the gains of the policy's PD law and of the labels alike (None: the controller's Kp, Kd), so that an action and
+    its label mean the same torque.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
+    train_loss and val_loss added."""
+    if not 0.0 <= val_fraction < 1.0:
+        raise ValueError("val_fraction must be in [0, 1)")
+    kp, kd = float(mpc.Kp if kp is None else kp), float(mpc.Kd if kd is None else kd)
+    out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
+                          terminate_mask=terminate_mask, collision_height=collision_height, record_states=True)
+    A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
+    S = out["S"]
+    B, K = S.shape[:2]
+    alive = torch.arange(K, device=S.device)[None, :] < out["steps_survived"][:, None]
+    keep = torch.nonzero((alive & (status != NMPC_STATUS_NAN) & (status != NMPC_STATUS_QP)).reshape(-1)).squeeze(1)      # device index, (b, k) order
+    n_rows = int(keep.numel())
+    if n_rows:
+        goals = torch.as_tensor(goal, dtype=torch.float32, device=S.device).reshape(B, -1)
+        db.append(S.reshape(B * K, -1)[keep], A_star.reshape(B * K, -1)[keep], goals.repeat_interleave(K, dim=0)[keep])
+    n = len(db)
+    if n == 0:
+        raise ValueError("the database is empty: no visited state of the batch got a label")
+    n_val = int(val_fraction * n)
+    val_idx = torch.arange(n - n_val, n, dtype=torch.int32, device=db.device) if n_val else None
+    train_loss, val_loss = train_network(policy, db, n_epoch, batch_size, lr=lr, seed=seed, val_idx=val_idx)
+    return dict(out, A_star=A_star, status=status, n_rows=n_rows, train_loss=train_loss, val_loss=val_loss)

@@ -295,6 +295,53 @@ class LocomotionMPC:
         fs.parse_sol(self._X_dev.cpu().numpy().astype(np.float64), self._U_dev.cpu().numpy().astype(np.float64))
         return S[:, :steps] if record_sim_steps else S
 
+    def label_clock(self, n_rows: int, t0: float, dt_row: float):
+        """The float clock of `replan_clock` for rows that are not replans: row k of a table of visited states was reached at
+        time t0 + k dt_row, that is at simulation step round((t0 + k dt_row) / sim_dt) of a rollout that starts from the
+        controller's current counters.  -> (nodes [n_rows]: the optimisation node the clock shows at that step, ref_steps
+        [n_rows]: the simulation steps run by then, over which the base reference has been integrated).  Host code only."""
+        if n_rows < 1 or t0 < 0.0 or not dt_row > 0.0:
+            raise ValueError("label_clock: need n_rows >= 1, t0 >= 0 and dt_row > 0")
+        ref_steps = [int(round((t0 + k * dt_row) / self.sim_dt)) for k in range(n_rows)]
+        sim_time, node, node_at = 0.0, self.current_opt_node, []
+        for _ in range(ref_steps[-1] + 1):
+            if sim_time >= (node + 1) * self.dt_nodes:
+                node += 1
+            node_at.append(node)
+            sim_time = sim_time + self.sim_dt
+        return [node_at[s] for s in ref_steps], ref_steps
+
+    def label_states(self, Q, V, torque_layer, t0: float = 0.0, dt_row: Optional[float] = None, failed=None,
+                     kp: Optional[float] = None, kd: Optional[float] = None):
+        """DAgger relabelling (nmpc_wb_label_states_batch): what this expert would have done in states somebody else reached.
+        Q, V [B, K, 18] (device, B = the controller's batch): row k of robot b is a plant state at time t0 + k dt_row of a rollout
+        under the controller's command, dt_row defaulting to the replanning interval (`BatchedTorqueLayer.set_rollout_states`
+        records them beside a policy rollout; there dt_row = n_sub dt).  Every state gets the expert's FIRST solve -- cold start,
+        N_SQP_FIRST iterations at a tenth of the tolerance -- at the node and with the base reference `label_clock` gives its
+        row, and the label is the PD target of simulation step 0 of that plan: the target applied from the state, the pairing of
+        plant mode (`open_loop_device(plant=...)`), whose gains kp, kd default to the controller's Kp, Kd as well.  failed
+        (int32 [B], a policy rollout's): the states from a robot's termination on are left out, their rows stay zero.
+        -> (A [B, K, 12], status int32 [B, K]) on the device.  Not a replan of the controller: its counters, reference, views
+        and `_X_dev` / `_U_dev` are as they were."""
+        import torch
+        fs = self.solver
+        s = fs._device_solver()
+        if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] != self.batch:
+            raise ValueError(f"Q: need a float32 tensor [{self.batch}, K, 18] on the GPU")
+        B, K = Q.shape[0], Q.shape[1]
+        nodes, ref_steps = self.label_clock(K, t0, self.replanning_steps * self.sim_dt if dt_row is None else dt_row)
+        cfg_o = self.config_opt
+        by_robot = lambda a: s.to_device(np.asarray(a, np.float64).reshape(B, -1), torch.float64)   # noqa: E731
+        A, status, _, _ = s.label_states(
+            torque_layer, s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
+            s.to_device(nodes, torch.int32), s.to_device(ref_steps, torch.int32), Q, V, by_robot(self.v_des), by_robot(self.w_des),
+            by_robot(self.base_ref_vel_tracking), s.to_device(self.joint_ref), s.to_device(self.id_repeat[:1], torch.int32), failed=failed,
+            nodes_per_cycle=self.contact_planner.nodes_per_cycle, max_sqp=N_SQP_FIRST, nlp_tol=cfg_o.nlp_tol / 10.0, sim_dt=self.sim_dt,
+            time_horizon=cfg_o.time_horizon, nom_height=self.config_gait.nom_height, height_offset=self.height_offset,
+            step_height=float(self.config_gait.step_height), force_reference_gravity=int(fs.force_reference == "gravity_share"),
+            kp=float(self.Kp if kp is None else kp), kd=float(self.Kd if kd is None else kd), terminate_mask=int(TERMINATE_DEFAULT))
+        return A, status
+
     def _step(self) -> None:                                                                # mpc.py:183-186
         self.increment_base_ref_position()
         self.sim_step += 1

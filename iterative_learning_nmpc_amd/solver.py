@@ -290,6 +290,57 @@ class BatchedNmpcSolver:
             ptr(failed), stream(self.device)), self._h, "nmpc_wb_rollout_batch")
         return S, failed
 
+    def label_states(self, layer, gait, peaks, node, ref_steps, Q, V, v_des, w_des, ref_state, joint_ref, zoh, failed=None,
+                     A=None, status=None, X=None, U=None, **cfg):
+        """nmpc_wb_label_states_batch: the expert's first solve from every visited state Q, V [B, K, 18] (a policy rollout's, with
+        `BatchedTorqueLayer.set_rollout_states`; slices of longer tables are taken with their stride) and the PD target it would
+        apply from it.  cfg: every field of nmpc_wb_label_cfg by name but n_rows (= K); node, ref_steps: int32 [K] on the
+        device, the optimisation node of row k and the simulation steps the base reference has been integrated over by then;
+        v_des, w_des, ref_state: float64 [B, 3 / 3 / 12], read only; zoh int32 [1]: the held node of simulation step 0; failed
+        int32 [B] or None: the rollout's flags, states from a robot's termination on are left out (their A and status keep what
+        the given tensors hold, zeros in new ones).  B K problems are solved in chunks of batch_max; X, U (the workspace of one
+        chunk, [min(B K, batch_max), N + 1, 42] and [.., N, 30]) hold the plans of the last chunk afterwards.
+        -> (A [B, K, 12], status int32 [B, K], X, U)."""
+        if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[1] < 1:
+            raise ValueError("Q: need a float32 tensor [B, K, 18] on the GPU with K >= 1")
+        B, K, N = Q.shape[0], Q.shape[1], self.n_nodes
+        Q, qv_rows = layer._rows(Q, 18, "Q", B)
+        V, v_rows = layer._rows(V, 18, "V", B)
+        if V.shape[1] != K or v_rows != qv_rows:
+            raise ValueError("Q, V: need the same rows and one layout")
+        c = _cfg(_lib.NmpcWbLabelCfg, dict(cfg, n_rows=K))
+        for t, name in ((gait, "gait"), (peaks, "peaks")):
+            self._chk(t, (4, c.nodes_per_cycle), name, torch.int8)
+        self._chk(node, (K,), "node", torch.int32)
+        self._chk(ref_steps, (K,), "ref_steps", torch.int32)
+        if not bool((node >= 0).all()) or not bool((ref_steps >= 0).all()):
+            raise ValueError("node, ref_steps: must not be negative")
+        self._chk(v_des, (B, 3), "v_des", torch.float64)
+        self._chk(w_des, (B, 3), "w_des", torch.float64)
+        self._chk(ref_state, (B, 12), "ref_state", torch.float64)
+        self._chk(joint_ref, (12,), "joint_ref")
+        self._chk(zoh, (1,), "zoh", torch.int32)
+        if not bool(((zoh >= 0) & (zoh < N)).all()):
+            raise ValueError(f"zoh: node indices must lie in [0, {N})")
+        if failed is not None:
+            self._chk(failed, (B,), "failed", torch.int32)
+        chunk = min(B * K, self.batch_max)
+        A = torch.zeros(B, K, 12, dtype=torch.float32, device=self.device) if A is None else A
+        A, a_rows = layer._rows(A, 12, "A", B)
+        if A.shape[1] != K:
+            raise ValueError(f"A: need {K} rows")
+        status = torch.zeros(B, K, dtype=torch.int32, device=self.device) if status is None else status
+        X = torch.zeros(chunk, N + 1, self.nx, dtype=torch.float32, device=self.device) if X is None else X
+        U = torch.zeros(chunk, N, self.nu, dtype=torch.float32, device=self.device) if U is None else U
+        self._chk(status, (B, K), "status", torch.int32)
+        self._chk(X, (chunk, N + 1, self.nx), "X")
+        self._chk(U, (chunk, N, self.nu), "U")
+        _lib.check(self.lib.nmpc_wb_label_states_batch(
+            self._h, layer._h, B, ctypes.byref(c), ptr(gait), ptr(peaks), ptr(node), ptr(ref_steps), ptr(Q), ptr(V), qv_rows,
+            ptr(v_des), ptr(w_des), ptr(ref_state), ptr(joint_ref), ptr(failed), ptr(zoh), ptr(A), a_rows, ptr(status), ptr(X), ptr(U),
+            stream(self.device)), self._h, "nmpc_wb_label_states_batch")
+        return A, status, X, U
+
     def _rollout_io(self, c, B, v_des, w_des, ref_state, push_force, X, U, status, row_width):
         """checks of the arguments both rollout calls share; the outputs S and failed"""
         N = self.n_nodes

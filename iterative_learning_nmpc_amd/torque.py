@@ -243,6 +243,9 @@ class BatchedTorqueLayer:
                 s_mean, s_std = db.states_mean, db.states_std
         s_mean, s_std = self._stats(s_mean, s_std)
         n_steps, n_goal = int(n_steps), goal.shape[1]
+        states = getattr(self, "_states", None)
+        if states is not None and (states[0].shape[0] != B or states[0].shape[1] < n_steps):      # the attached tables must be this rollout's size
+            raise ValueError(f"Q, V (set_rollout_states): need [{B}, >= {n_steps}, {self.n}], got {tuple(states[0].shape)}")
         rows = max(n_steps, 0)
         S = torch.empty(B, rows, N_STATE, dtype=torch.float32, device=self.device) if record else None
         A = torch.empty(B, rows, self.nu, dtype=torch.float32, device=self.device) if record else None
@@ -256,6 +259,27 @@ class BatchedTorqueLayer:
                                                       ptr(failed), stream(self.device)),
                    self._h, "nmpc_policy_rollout_batch", "torque")
         return q, v, S, A, failed
+
+    def set_rollout_states(self, Q: Optional[torch.Tensor] = None, V: Optional[torch.Tensor] = None):
+        """nmpc_policy_rollout_set_states: while Q, V [B, rows, 18] (rows >= n_steps; slices [:, :k] of longer tables are taken
+        with their stride) are attached, every `policy_rollout` of this layer writes the plant state before control step k into
+        row k of both -- the states its rows of S were made of, which `LocomotionMPC.label_states` starts the expert's solves
+        from.  Every other output of the rollout is the same bits.  `set_rollout_states(None)` detaches.  The layer keeps the two
+        alive while they are attached; a rollout of another batch size than theirs is refused."""
+        if Q is None and V is None:
+            self._states = None
+            _lib.check(self.lib.nmpc_policy_rollout_set_states(self._h, None, None, 0), self._h, "nmpc_policy_rollout_set_states", "torque")
+            return
+        if Q is None or V is None:
+            raise ValueError("Q and V come together or not at all")
+        if not isinstance(Q, torch.Tensor) or Q.dim() != 3:
+            raise ValueError("Q: need a float32 [B, rows, 18] tensor")
+        Q, qv_rows = self._rows(Q, self.n, "Q", Q.shape[0])
+        V, v_rows = self._rows(V, self.n, "V", Q.shape[0])
+        if V.shape[1] != Q.shape[1] or v_rows != qv_rows:
+            raise ValueError("Q, V: need the same rows and one layout")
+        self._states = (Q, V)
+        _lib.check(self.lib.nmpc_policy_rollout_set_states(self._h, ptr(Q), ptr(V), qv_rows), self._h, "nmpc_policy_rollout_set_states", "torque")
 
     def _state_io(self, t, name):
         """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""

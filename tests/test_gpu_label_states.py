@@ -1,0 +1,291 @@
+"""DAgger relabelling on the device (nmpc_wb_label_states_batch, `BatchedNmpcSolver.label_states`, `LocomotionMPC.label_states`).
+
+The yardstick of the problem and its solve is code the parent has and the existing suites pin to the oracle: one replan of
+nmpc_wb_rollout_batch with first_solve = 1 and labels attached -- the same solves behind the existing prepare kernel --, started
+at the node and with the integrated base reference the labeller is told; the comparison is bit for bit.  The labels themselves
+are held to the fp64 oracle labels of the call's own plans under the bar of tests/test_gpu_plan_labels.py, restated here:
+    kp |A - A_ref| <= 1e-5 max|tau_ref| + 4 eps32 (kp |q| + kd |v|).
+B = 3 robots x K = 5 rows, standing starts (Q_HOME + N(0, 0.03), seed 2: all 15 first solves end with status 0 on the CPU oracle,
+fp32 and fp64, at every node used here), command 0.2 m/s, gravity_share."""
+import numpy as np
+import pytest
+
+from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.solve_helpers import dev  # noqa: F401
+from tests.torque_helpers import oracle_labels, same
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+KP, KD = 20.0, 1.5
+EPS32 = float(np.finfo(np.float32).eps)
+B, K, STEPS = 3, 5, 40
+SENTINEL = -7.0
+
+
+class Rig:
+    """a configured whole-body device solver of `batch_max` problems with the controller's tables, and the 15 states"""
+    def __init__(self, dev, batch_max):
+        from iterative_learning_nmpc_amd import wholebody as wbk
+        from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
+        from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
+        self.mpc = mpc = LocomotionMPC(print_info=False, device=dev, batch=batch_max, n_nodes=30, force_reference="gravity_share")
+        assert mpc.replanning_steps == STEPS
+        self.s = s = mpc.solver._device_solver()
+        self.L = BatchedTorqueLayer(**quadruped_tree(), device=dev)
+        self.npc = mpc.contact_planner.nodes_per_cycle
+        self.gait, self.peaks = (s.to_device(t, torch.int8) for t in (mpc.contact_planner.gait_sequence, mpc.contact_planner.peak_swing))
+        self.joint_ref = s.to_device(mpc.joint_ref)
+        rng = np.random.default_rng(2)
+        q = np.zeros((B * K, 18)); q[:, 2] = 0.30; q[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B * K, 12))
+        self.Q = s.to_device(q.reshape(B, K, 18))
+        self.V = torch.zeros_like(self.Q)
+        # per robot: the command, a yaw rate and a reference that has already turned, so that its integration shows
+        self.v_des = s.to_device(np.tile([0.2, 0.0, 0.0], (B, 1)), torch.float64)
+        self.w_des = s.to_device(np.array([[0.0, 0.0, 0.1 * b] for b in range(B)]), torch.float64)
+        ref = np.zeros((B, 12)); ref[:, 3] = [0.0, 0.3, -0.2]; ref[:, 0] = [0.0, 0.01, 0.02]
+        self.ref_state = s.to_device(ref, torch.float64)
+        c, g = mpc.config_opt, mpc.config_gait
+        self.common = dict(nodes_per_cycle=self.npc, sim_dt=mpc.sim_dt, time_horizon=c.time_horizon, nom_height=g.nom_height,
+                           height_offset=mpc.height_offset, step_height=float(g.step_height), force_reference_gravity=1)
+        self.nlp_tol = c.nlp_tol
+        self.dt_nodes = c.time_horizon / c.n_nodes
+
+    def label(self, node, ref_steps, failed=None, A=None, status=None, X=None, U=None, Q=None, V=None, layer=None, **over):
+        from iterative_learning_nmpc_amd.config import N_SQP_FIRST, TERMINATE_DEFAULT
+        s = self.s
+        cfg = dict(self.common, max_sqp=N_SQP_FIRST, nlp_tol=self.nlp_tol / 10.0, kp=KP, kd=KD, terminate_mask=TERMINATE_DEFAULT)
+        cfg.update(over)
+        out = s.label_states(self.L if layer is None else layer, self.gait, self.peaks, s.to_device(node, torch.int32),
+                             s.to_device(ref_steps, torch.int32), self.Q if Q is None else Q, self.V if V is None else V, self.v_des, self.w_des,
+                             self.ref_state, self.joint_ref, s.to_device([0], torch.int32), failed=failed, A=A, status=status, X=X, U=U, **cfg)
+        torch.cuda.synchronize()
+        return out
+
+    def harness(self, rows, node, ref_state):
+        """one replan of nmpc_wb_rollout_batch (first solve, labels attached) from the states (b, k), k in rows, of every robot,
+        at `node`, from the integrated reference ref_state [B, 12] (one per robot; left as it was)
+        -> (row 0 of its labels [B, len(rows), 12], X, U, status, the reference the call leaves per robot)"""
+        from iterative_learning_nmpc_amd.config import COLLISION_HEIGHT, N_SQP_FIRST
+        s, mpc, n = self.s, self.mpc, len(rows)
+        M = B * n
+        per_robot = lambda t: t.repeat_interleave(n, dim=0).contiguous()      # noqa: E731
+        q, v = self.Q[:, rows].reshape(M, 18).contiguous(), self.V[:, rows].reshape(M, 18).contiguous()
+        ref = per_robot(ref_state)
+        X = torch.zeros(M, 31, 42, dtype=torch.float32, device=s.device); U = torch.zeros(M, 30, 30, dtype=torch.float32, device=s.device)
+        status = torch.zeros(M, dtype=torch.int32, device=s.device)
+        A = torch.zeros(M, STEPS, 12, dtype=torch.float32, device=s.device)
+        s.set_rollout_actions(self.L, s.to_device(mpc.id_repeat[:STEPS], torch.int32), A, KP, KD)
+        try:
+            s.wb_rollout(self.gait, self.peaks, [node], q, v, per_robot(self.v_des), per_robot(self.w_des), ref, self.joint_ref, None, X, U, status,
+                         n_replans=1, replanning_steps=STEPS, first_solve=1, last_node=0, max_sqp_first=N_SQP_FIRST,
+                         nlp_tol_first=self.nlp_tol / 10.0, nlp_tol=self.nlp_tol, push_start=0.0, push_duration=0.0, record_sim_steps=1,
+                         nominal_period=float(mpc.config_gait.nominal_period), terminate_mask=0, collision_height=float(COLLISION_HEIGHT),
+                         **self.common)
+        finally:
+            s.set_rollout_actions(None)
+        torch.cuda.synchronize()
+        return A[:, 0].reshape(B, n, 12), X, U, status.reshape(B, n), ref.reshape(B, n, 12)[:, 0].contiguous()
+
+    def advanced(self, intervals):
+        """ref_state after `intervals` one-replan calls of the harness"""
+        ref = self.ref_state
+        for _ in range(intervals):
+            ref = self.harness([0], 0, ref)[4]
+        return ref
+
+
+@pytest.fixture(scope="module")
+def rig(dev):
+    return Rig(dev, 16)
+
+
+@pytest.fixture(scope="module")
+def mixed(rig):
+    """the labels of the mixed-node call, shared by the tests that compare against it: (node, A, status, X, U), never written to"""
+    node = [0, 0, 1, 1, rig.npc - 1]
+    return (node,) + rig.label(node, [0] * K)
+
+
+def assert_groups(rig, node, ref_steps, A, status, X, U):
+    """per group of rows with one (node, ref_steps): bit for bit the one-replan rollout at that node from that reference"""
+    Xr, Ur = X.reshape(B, K, 31, 42), U.reshape(B, K, 30, 30)
+    for key in sorted(set(zip(node, ref_steps))):
+        rows = [k for k in range(K) if (node[k], ref_steps[k]) == key]
+        assert key[1] % STEPS == 0
+        A0, Xh, Uh, sh, _ = rig.harness(rows, key[0], rig.advanced(key[1] // STEPS))
+        n = len(rows)
+        assert same(A[:, rows], A0), key
+        assert same(Xr[:, rows], Xh.reshape(B, n, 31, 42)) and same(Ur[:, rows], Uh.reshape(B, n, 30, 30)), key
+        assert torch.equal(status[:, rows], sh), key
+
+
+@pytest.mark.parametrize("which", ["node 0: every foot stands at the first node", "the window wraps"])
+def test_uniform_node_equals_the_rollout_harness(rig, which):
+    n = 0 if which.startswith("node 0") else rig.npc - 3
+    A, status, X, U = rig.label([n] * K, [0] * K)
+    assert_groups(rig, [n] * K, [0] * K, A, status, X, U)
+    assert bool(torch.isfinite(A).all())
+
+
+def test_mixed_nodes(rig, mixed):
+    node, A, status, X, U = mixed
+    assert_groups(rig, node, [0] * K, A, status, X, U)
+    # the node is the problem's: rows of one robot at different nodes got different problems
+    assert not same(X[0 * K + 1, 1:], X[0 * K + 2, 1:])
+
+
+def test_reference_integration(rig):
+    node, ref_steps = [0, 1, 1, 2, 2], [0, STEPS, STEPS, 2 * STEPS, 2 * STEPS]
+    before = rig.ref_state.clone()
+    A, status, X, U = rig.label(node, ref_steps)
+    assert torch.equal(rig.ref_state, before)                       # read only
+    assert not torch.equal(rig.advanced(2), before)                 # and the integration moves it
+    assert_groups(rig, node, ref_steps, A, status, X, U)
+
+
+def test_chunks(dev, rig, mixed):
+    """B_max = 4: 15 problems as 4 + 4 + 4 + 3, the same labels and statuses; X, U hold the last chunk's three plans"""
+    node, A, status, X, U = mixed
+    small = Rig(dev, 4)
+    A4, status4, X4, U4 = small.label(node, [0] * K)
+    assert X4.shape[0] == 4
+    assert same(A4, A) and torch.equal(status4, status)
+    assert same(X4[:3], X[12:]) and same(U4[:3], U[12:])
+    # a table with more rows than states per robot: the labels land in its first K rows, robot by robot
+    wide = torch.full((B, K + 2, 12), SENTINEL, dtype=torch.float32, device=dev)
+    small.label(node, [0] * K, A=wide[:, :K])
+    assert same(wide[:, :K], A) and bool((wide[:, K:] == SENTINEL).all())
+
+
+def test_labels_against_the_oracle(rig, mixed):
+    from iterative_learning_nmpc_amd import _lib
+    from oracle import torque_oracle as to
+    node, A, status, X, U = mixed
+    st = status.cpu().numpy()
+    print("statuses", st.tolist())
+    assert not np.isin(st, (_lib.NMPC_STATUS_NAN, _lib.NMPC_STATUS_QP)).any()          # a failed solve cannot hide as a label
+    m = to.TreeModel.from_arrays(quadruped_tree())
+    ref, tau, q, v = oracle_labels(m, X.cpu().numpy().astype(np.float64), U.cpu().numpy().astype(np.float64), np.array([0]), rig.dt_nodes,
+                                   rig.mpc.sim_dt, KP, KD)
+    bar = 1e-5 * np.abs(tau).max(axis=-1, keepdims=True) + 4 * EPS32 * (KP * np.abs(q[..., 6:]) + KD * np.abs(v[..., 6:]))
+    err = KP * np.abs(A.reshape(B * K, 1, 12).cpu().numpy().astype(np.float64) - ref)
+    ratio = float((err / bar).max())
+    print(f"labels of visited states: worst kp |A - A_ref| / bar = {ratio:.3f} (max |tau_ref| {np.abs(tau).max():.1f})")
+    assert np.isfinite(err).all() and ratio <= 1.0
+
+
+def test_skip(rig, mixed):
+    """stamps 0, 3, 1: robot 1 fell at the observation of control step 2, robot 2 at the first one"""
+    from iterative_learning_nmpc_amd import _lib
+    node, A, status, X, U = mixed
+    s = rig.s
+    failed = s.to_device([0, (3 << _lib.NMPC_ROLLOUT_TERM_SHIFT) | _lib.NMPC_ROLLOUT_FLAG_COLLISION,
+                          (1 << _lib.NMPC_ROLLOUT_TERM_SHIFT) | _lib.NMPC_ROLLOUT_FLAG_COLLISION], torch.int32)
+    As = torch.full((B, K, 12), SENTINEL, dtype=torch.float32, device=s.device)
+    sts = torch.full((B, K), 99, dtype=torch.int32, device=s.device)
+    Xs = torch.full((B * K, 31, 42), SENTINEL, dtype=torch.float32, device=s.device)
+    Us = torch.full((B * K, 30, 30), SENTINEL, dtype=torch.float32, device=s.device)
+    # the caller's own skip setting: problem 1 of its plain solves is left out
+    own = torch.zeros(s.batch_max, dtype=torch.int32, device=s.device); own[1] = 4
+    s.set_skip(own, 4)
+    try:
+        rig.label(node, [0] * K, failed=failed, A=As, status=sts, X=Xs, U=Us)
+        skipped = torch.zeros(B, K, dtype=torch.bool, device=s.device)
+        skipped[1, 2:] = True; skipped[2, :] = True
+        assert bool((As[skipped] == SENTINEL).all()) and bool((sts[skipped] == 99).all())
+        flat = skipped.reshape(-1)
+        assert bool((Xs[flat] == SENTINEL).all()) and bool((Us[flat] == SENTINEL).all())
+        assert same(As[~skipped], A[~skipped]) and torch.equal(sts[~skipped], status[~skipped])
+        assert same(Xs[~flat], X[~flat]) and same(Us[~flat], U[~flat])
+        # a plain solve on the handle sees the caller's flags again: problem 1 untouched, problem 0 solved
+        from iterative_learning_nmpc_amd import workloads as wl
+        w = wl.wholebody_trot(B=2, N=30, seed=3)
+        t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params", "X", "U")}
+        X0, U0 = t["X"].clone(), t["U"].clone()
+        Xp, Up, _, _ = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], t["X"], t["U"])
+        torch.cuda.synchronize()
+        assert same(Xp[1], X0[1]) and same(Up[1], U0[1]) and not same(Up[0], U0[0])
+    finally:
+        s.set_skip(None)
+
+
+def test_refusals_launch_nothing(dev, rig, mixed):
+    from iterative_learning_nmpc_amd._lib import NmpcError, ptr, stream
+    from iterative_learning_nmpc_amd import _lib
+    from iterative_learning_nmpc_amd.config import N_SQP_FIRST
+    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
+    node, A, status, X, U = mixed
+    s, mpc = rig.s, rig.mpc
+    out = dict(A=torch.full((B, K, 12), SENTINEL, dtype=torch.float32, device=dev), status=torch.full((B, K), 99, dtype=torch.int32, device=dev),
+               X=torch.full((B * K, 31, 42), SENTINEL, dtype=torch.float32, device=dev), U=torch.full((B * K, 30, 30), SENTINEL, dtype=torch.float32, device=dev))
+
+    def untouched():
+        torch.cuda.synchronize()
+        return all(bool((t == (99 if t.dtype == torch.int32 else SENTINEL)).all()) for t in out.values())
+
+    n = 23                                                            # a chain of 23 revolute joints: not the whole-body tree
+    eye = np.tile(np.eye(3).reshape(9), (n, 1))
+    chain = BatchedTorqueLayer(list(range(-1, n - 1)), [0] * n, np.tile([0.0, 0.0, 1.0], (n, 1)), eye, np.tile([0.1, 0.0, 0.0], (n, 1)),
+                               np.ones(n), np.zeros((n, 3)), np.tile([1.0, 0, 0, 1.0, 0, 1.0], (n, 1)), [n - 1], np.zeros((1, 3)), 12, device=dev)
+    for text, kw in (("kp must not be zero", dict(kp=0.0)), ("n_joints", dict(layer=chain)), ("beyond the horizon", dict(sim_dt=2.0 * mpc.config_opt.time_horizon))):
+        with pytest.raises(NmpcError, match=text):
+            rig.label(node, [0] * K, **out, **kw)
+        assert untouched(), text
+    s.set_line_search(True)
+    try:
+        with pytest.raises(NmpcError, match="line_search"):
+            rig.label(node, [0] * K, **out)
+    finally:
+        s.set_line_search(False)
+    assert untouched()
+    # what the Python layer checks before the library sees it, handed to the library directly: another model, rows, a NULL pointer
+    import copy
+    import ctypes
+    from tests.solve_helpers import make_solver
+    from iterative_learning_nmpc_amd import workloads as wl
+    cent = make_solver(wl.centroidal_trot(B=4, N=30, seed=0), 16, dev)
+    cfg = _lib.NmpcWbLabelCfg(n_rows=K, max_sqp=N_SQP_FIRST, nlp_tol=rig.nlp_tol / 10.0, kp=KP, kd=KD, terminate_mask=0, **rig.common)
+    dnode, dsteps, zoh = s.to_device(node, torch.int32), s.to_device([0] * K, torch.int32), s.to_device([0], torch.int32)
+
+    def raw(cfg, qv_rows=K, a_rows=K, Q=rig.Q, handle=s._h, torque=rig.L._h):
+        rc = s.lib.nmpc_wb_label_states_batch(handle, torque, B, ctypes.byref(cfg), ptr(rig.gait), ptr(rig.peaks), ptr(dnode), ptr(dsteps), ptr(Q),
+                                              ptr(rig.V), qv_rows, ptr(rig.v_des), ptr(rig.w_des), ptr(rig.ref_state), ptr(rig.joint_ref), None,
+                                              ptr(zoh), ptr(out["A"]), a_rows, ptr(out["status"]), ptr(out["X"]), ptr(out["U"]), stream(dev))
+        return rc, s.lib.nmpc_last_error(handle)
+    none = copy.copy(cfg); none.n_rows = 0
+    for (rc, why), text in ((raw(none), b"n_rows"), (raw(cfg, qv_rows=K - 1), b"qv_rows"), (raw(cfg, a_rows=K - 1), b"a_rows"),
+                            (raw(cfg, Q=None), b"null"), (raw(cfg, torque=None), b"null torque handle"),
+                            (raw(cfg, handle=cent._h), b"whole-body model")):
+        assert rc == -1 and text in why, (text, why)
+        assert untouched(), text
+    # the handle then labels correctly
+    A2, status2, X2, U2 = rig.label(node, [0] * K)
+    assert same(A2, A) and torch.equal(status2, status) and same(X2, X) and same(U2, U)
+
+
+def test_controller_label_states_leaves_the_controller_alone(dev, rig, mixed):
+    """`LocomotionMPC.label_states`: the clock's nodes and steps, the controller's command and reference, Kp / Kd by default; no
+    counter, view or device plan of the controller moves"""
+    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
+    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
+    mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
+    before = (mpc.sim_step, mpc.current_opt_node, mpc.first_solve, mpc.base_ref_vel_tracking.copy(), mpc.solver.last_node)
+    A, status = mpc.label_states(rig.Q, rig.V, rig.L, kp=KP, kd=KD)
+    torch.cuda.synchronize()
+    assert A.shape == (B, K, 12) and status.shape == (B, K) and getattr(mpc, "_X_dev", None) is None
+    assert (mpc.sim_step, mpc.current_opt_node, mpc.first_solve, mpc.solver.last_node) == (before[0], before[1], before[2], before[4])
+    assert np.array_equal(mpc.base_ref_vel_tracking, before[3])
+    # the same call through the solver with the clock's rows, zero yaw rate and a zero reference
+    nodes, ref_steps = mpc.label_clock(K, 0.0, STEPS * mpc.sim_dt)
+    assert ref_steps == [k * STEPS for k in range(K)]
+    keep = rig.w_des, rig.ref_state
+    rig.w_des, rig.ref_state = torch.zeros_like(rig.w_des), torch.zeros_like(rig.ref_state)
+    try:
+        Ar, sr, _, _ = rig.label(nodes, ref_steps)
+        A_gains = rig.label(nodes, ref_steps, kp=mpc.Kp, kd=mpc.Kd)[0]
+    finally:
+        rig.w_des, rig.ref_state = keep
+    assert same(A, Ar) and torch.equal(status, sr)
+    # the controller's own gains by default, as plant mode
+    assert same(mpc.label_states(rig.Q, rig.V, rig.L)[0], A_gains)
