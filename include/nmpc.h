@@ -327,6 +327,18 @@ int nmpc_wb_rollout_set_actions(void *handle, void *torque_handle, const int *zo
 int nmpc_wb_rollout_set_plant(void *handle, void *torque_handle, const nmpc_contact_cfg *ground, int n_sub, float kp, float kd,
                               const int *zoh, float *Aw, float *Qw, float *Vw);
 
+/* How a plant-mode rollout applies its push_force [decl].  as_force = 0 (the default, and what every rollout did before this
+ * call existed): the advance kernel adds the velocity jump F replanning_steps sim_dt / m to the base once per replanning
+ * interval inside the window, the push of the "plant = plan" rollouts.  as_force = 1: the push is a force on the plant
+ * (nmpc_push_cfg, include/nmpc_torque.h) -- replan r hands the rollout's own push_force ([B][3], on joint 5, the trunk) to its
+ * track launch with the window, in substeps of sim_dt / n_sub,
+ *   first_substep = lround(push_start n_sub / sim_dt) - r replanning_steps n_sub,   n_substeps = lround(push_duration n_sub / sim_dt)
+ * and the advance kernel gets no push.  The rollout passes the push to the launch itself: whatever is attached to the torque
+ * handle is not rewritten.  A rollout returns NMPC_E_ARG and launches nothing if as_force = 1 and no plant is attached, or if
+ * as_force = 1, it has a push_force and the caller has attached a push of its own to the plant's torque handle
+ * (nmpc_contact_set_push). */
+int nmpc_wb_rollout_set_plant_push(void *handle, int as_force);
+
 /* DAgger relabelling: the expert's labels for states somebody else's rollout visited (nmpc_policy_rollout_batch with
  * nmpc_policy_rollout_set_states, include/nmpc_torque.h).  For every state (b, k) -- robot b < B, row k < n_rows -- the
  * expert's FIRST solve from that state (cold start, max_sqp iterations at nlp_tol) and the PD target it would apply from it:

@@ -102,6 +102,26 @@ int nmpc_contact_step_batch(void *handle, int B, int n_sub, float dt, const nmpc
                             const float *tau_ff, const float *q_des, float kp, float kd,
                             float *q_out, float *v_out, float *a_out, float *f_out, float *tau_out, void *stream);
 
+/* A push on the contact plant [decl] (the reference pushes the MuJoCo base: data_collection_force_perturbation.py): robot b is
+ * pushed with the world-frame force force[b] (N, no moment) at the origin of the body frame of joint `joint` (5: the trunk of the
+ * 18-joint tree) -- in the recursion one more foot force with zero offset, so it acts inside every pushed substep, where the
+ * feet and the torque limit answer it.  The attach idiom of nmpc_policy_rollout_set_states: the struct is copied at the call,
+ * force (dev [force_rows][3], caller-owned, kept as a pointer) is read in stream order.  While a push is attached it acts in
+ * three calls, in the substeps s with first_substep <= s < first_substep + n_substeps, s counted from 0 at the start of each call:
+ *   nmpc_contact_step_batch     s = i                (substep i of the call)
+ *   nmpc_contact_track_batch    s = k n_sub + i      (substep i of control step k)
+ *   nmpc_policy_rollout_batch   s = k n_sub + i      (its step launches see the window moved by k n_sub; the attachment stays)
+ * first_substep may be negative: the window is cut to the call's substeps, so a chain of single calls with the window moved
+ * along is bit for bit the long call.  A call is cut into runs of un-pushed substeps, which are launches of the un-pushed kernels
+ * (no zero force is added: their arithmetic is the one it was), and runs of pushed substeps, which are launches of one pushed
+ * kernel for the step and the track alike -- up to three launches for a step, and for a track one more per control step the
+ * window starts or ends in.  With nothing attached, or a window that misses the call, the launches are the ones made without.
+ * nmpc_fd_step_batch, nmpc_fd_accel_batch and nmpc_contact_forces_batch are not affected.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), what was attached staying: force NULL, force_rows < 1, joint outside
+ * [0, n_joints), n_substeps < 0.  At a plant call, before any launch: B > force_rows.  push = NULL detaches. */
+typedef struct { const float *force; int force_rows, joint, first_substep, n_substeps; } nmpc_push_cfg;   /* host struct, copied at the call */
+int nmpc_contact_set_push(void *torque, const nmpc_push_cfg *push);
+
 /* A policy in the loop on the contact plant [decl] (the reference: DAgger/utils/RolloutPolicy.py, PolicyController: MLP -> PD
  * target -> torque, in MuJoCo).
  *

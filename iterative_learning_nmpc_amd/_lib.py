@@ -44,6 +44,7 @@ SIGNATURES = {
     "nmpc_set_skip": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_wb_rollout_set_actions": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p]),
     "nmpc_wb_rollout_set_plant": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_wb_rollout_set_plant_push": (c_int, [c_void_p, c_int]),
     "nmpc_set_ipm": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float]),
     "nmpc_shift_warm_start": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "nmpc_solve_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -94,6 +95,7 @@ SIGNATURES = {
     "nmpc_contact_forces_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_contact_step_batch": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_contact_set_push": (c_int, [c_void_p, c_void_p]),
     "nmpc_observe_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "nmpc_policy_rollout_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -138,6 +140,10 @@ class NmpcTreeModel(ctypes.Structure):
 class NmpcContactCfg(ctypes.Structure):
     _fields_ = [("ground_z", c_float), ("stiffness", c_float), ("damping", c_float), ("mu", c_float),
                 ("slip_velocity", c_float), ("tau_max", c_float)]
+
+
+class NmpcPushCfg(ctypes.Structure):
+    _fields_ = [("force", c_void_p), ("force_rows", c_int), ("joint", c_int), ("first_substep", c_int), ("n_substeps", c_int)]
 
 
 class NmpcPolicyRolloutCfg(ctypes.Structure):

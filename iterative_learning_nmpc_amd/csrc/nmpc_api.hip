@@ -54,6 +54,7 @@ struct Handle {
         const int* zoh = nullptr;
         float *Aw = nullptr, *Qw = nullptr, *Vw = nullptr;
     } plant;
+    bool plant_push_as_force = false;   // nmpc_wb_rollout_set_plant_push: a plant-mode rollout pushes with a force on the plant, not a velocity jump
     bool ws_dirty = false;   // a dense-LQ call left foreign padding in the tile workspace
     bool mp_set = false, w_set = false;
     nmpc::ModelParams mp{};
@@ -439,6 +440,13 @@ int nmpc_wb_rollout_set_plant(void* handle, void* torque_handle, const nmpc_cont
     return NMPC_OK;
 }
 
+int nmpc_wb_rollout_set_plant_push(void* handle, int as_force) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    h->plant_push_as_force = as_force != 0;
+    return NMPC_OK;
+}
+
 int nmpc_set_ipm(void* handle, float mu0, float sigma, float s_min, float gamma, float tau_min,
                  float merit_rho) {
     Handle* h = static_cast<Handle*>(handle);
@@ -624,6 +632,18 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
             return fail(h, NMPC_E_ARG, "plant: the attached action labels must be recorded with the plant's gains kp, kd");
         if (!targets || !pl.Qw || !pl.Vw) return fail(h, NMPC_E_ARG, "plant: the workspaces Qw, Vw and (without attached labels) Aw are needed");
     }
+    // the push as a force on the plant (nmpc_wb_rollout_set_plant_push): the rollout's own push_force, in substeps of sim_dt / n_sub
+    if (h->plant_push_as_force && !pl.torque) return fail(h, NMPC_E_ARG, "plant push: a push as a force needs a plant (nmpc_wb_rollout_set_plant)");
+    const bool force_push = h->plant_push_as_force && push_force;
+    if (force_push && nmpc_torque::push_attached(pl.torque))
+        return fail(h, NMPC_E_ARG, "plant push: the torque handle has a push of the caller's attached (nmpc_contact_set_push)");
+    nmpc_push_cfg plant_push{};
+    if (force_push) {
+        plant_push.force = push_force; plant_push.force_rows = B; plant_push.joint = 5;
+        plant_push.first_substep = (int)std::lround((double)cfg->push_start * pl.n_sub / cfg->sim_dt);
+        plant_push.n_substeps = (int)std::lround((double)cfg->push_duration * pl.n_sub / cfg->sim_dt);
+        if (plant_push.n_substeps < 0) plant_push.n_substeps = 0;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };       // every array starts on a 16 B boundary (launch_wb checks)
     nmpc::wb::WbRolloutArgs r{};
@@ -646,6 +666,7 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
         [&](int i) {          // warm_start_solver(i_node): start_node = i_node - last_node (solver.py:304-309)
             const int shift = nodes[i] - last_node;
             r.node = last_node = nodes[i];
+            if (force_push) r.push_dt = 0.0f;      // the track launch pushes: no velocity jump in the advance kernel
             return shift;
         },
         [&](int i) {          // the labels of this replan's plan, beside the rows the advance kernel is about to record
@@ -665,8 +686,16 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
             if (!pl.torque) return (int)NMPC_OK;
             // the expert drives the plant: the label rows as PD targets of `steps` simulation steps, the states before each step
             // into the workspace, and those states as rows row0 .. of S with their flags (no stamp: the advance kernel stamps)
-            const int trc = nmpc_contact_track_batch(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
-                                                     rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, st);
+            int trc;
+            if (force_push) {                      // this replan's substeps start at substep i steps n_sub of the rollout
+                nmpc_push_cfg push = plant_push;
+                push.first_substep -= i * steps * pl.n_sub;
+                trc = nmpc_torque::contact_track_pushed(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
+                                                        rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, push, st);
+            } else {
+                trc = nmpc_contact_track_batch(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
+                                               rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, st);
+            }
             if (trc) return fail(h, trc, std::string("nmpc_contact_track_batch: ") + nmpc_torque_last_error(pl.torque));
             const int orc = nmpc_observe_rows_batch(pl.torque, B, steps, pl.Qw, pl.Vw, steps, (double)(i * steps) * cfg->sim_dt, cfg->sim_dt,
                                                     (double)cfg->nominal_period, cfg->collision_height, S + (size_t)r.row0 * 44, r.n_rows,

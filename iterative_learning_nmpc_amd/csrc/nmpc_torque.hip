@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nmpc.h"
@@ -371,6 +372,7 @@ struct Torque {
         float *Q = nullptr, *V = nullptr;
         int rows = 0;
     } states;
+    nmpc_push_cfg push{};               // nmpc_contact_set_push: the push of the plant calls (force == nullptr: none)
     std::string err;
 };
 
@@ -426,6 +428,10 @@ int allocate(Torque* t) {
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_track_kernel, t->ct_width)),
                                             hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
+    // the pushed substeps of either: the same slice
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_push_kernel, t->ct_width)),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
     return NMPC_OK;
 }
 
@@ -471,7 +477,135 @@ int launch_feet(Torque* t, const FootArgs& a, void* stream) {
     return launched(t);
 }
 
+// why a push cannot be attached to a tree of n_joints joints (nullptr: it can)
+const char* push_refusal(const nmpc_push_cfg& p, int n_joints) {
+    if (!p.force) return "push: force is NULL";
+    if (p.force_rows < 1) return "push: force_rows must be at least 1";
+    if (p.joint < 0 || p.joint >= n_joints) return "push: joint must be in [0, n_joints)";
+    if (p.n_substeps < 0) return "push: n_substeps must not be negative";
+    return nullptr;
+}
+
+// The window of `push` (force == nullptr: none) in a call of `total` substeps whose substep 0 is substep s0 of the count the
+// window is stated in: the intersection [lo, hi) in the call's own count; lo == hi: nothing of the call is pushed.
+struct Window { long long lo = 0, hi = 0; };
+Window push_window(const nmpc_push_cfg& push, long long s0, long long total) {
+    Window w;
+    if (!push.force) return w;
+    const long long first = (long long)push.first_substep - s0, end = first + push.n_substeps;
+    w.lo = first > 0 ? first : 0; w.hi = end < total ? end : total;
+    if (w.hi <= w.lo) w = Window{};
+    return w;
+}
+
+// A plant call under a push is cut into runs of substeps that are all un-pushed -- launches of the un-pushed kernels, as a call
+// without a push makes them -- and runs that are all pushed, launches of contact_push_kernel (nmpc_torque_track.hip.inc says why).
+
+// nmpc_contact_step_batch under an explicit push: the call's substep i is substep s0 + i of the count `push` is stated in.
+// At most three launches: before, inside and after the window; the first reads q, v, the later ones go on in place on q_out,
+// v_out, and the last one writes a_out, f_out, tau_out.
+int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* cfg, const float* q, const float* v, const float* tau_ff,
+                 const float* q_des, float kp, float kd, float* q_out, float* v_out, float* a_out, float* f_out, float* tau_out,
+                 const nmpc_push_cfg& push, long long s0, void* stream) {
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
+    if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
+    if (push.force && B > push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
+    NMPC_ENTER(t, t->device);
+    const int w = t->ct_width;
+    const size_t lds = ct_lds_bytes(t->host.n, w);
+    const Window win = push_window(push, s0, n_sub);
+    const int cuts[4] = {0, (int)win.lo, (int)win.hi, n_sub};
+    bool first = true;
+    for (int r = 0; r < 3; ++r) {
+        const int count = cuts[r + 1] - cuts[r];
+        if (count <= 0) continue;
+        const bool last = cuts[r + 1] == n_sub;
+        const float *qi = first ? q : q_out, *vi = first ? v : v_out;
+        if (r == 1) {
+            PushArgs p{};
+            p.B = B; p.n_steps = 1; p.n_sub = count; p.a_rows = 1; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+            p.tau = tau_ff; p.A = q_des; p.q = q_out; p.v = v_out; p.q_in = qi; p.v_in = vi;
+            p.force = push.force; p.joint = push.joint;
+            if (last) { p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out; }
+            if (const int rc = launch_step(t, KERNEL_AT_WIDTH(contact_push_kernel, w), w, lds, p, stream)) return rc;
+        } else {
+            ContactArgs p{};
+            p.B = B; p.n_sub = count; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+            p.q = qi; p.v = vi; p.tau = tau_ff; p.q_des = q_des; p.q_out = q_out; p.v_out = v_out;
+            if (last) { p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out; }
+            if (const int rc = launch_step(t, KERNEL_AT_WIDTH(contact_step_kernel, w), w, lds, p, stream)) return rc;
+        }
+        first = false;
+    }
+    return NMPC_OK;
+}
+
+// nmpc_contact_track_batch under an explicit push, in substeps s = k * n_sub + i of the call.  Whole control steps of one kind
+// go into one launch; a control step the window starts or ends in is cut at that substep, and only its first piece writes its row
+// of Q, V.
+int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v, const float* tau_ff,
+                  const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows, const int* skip, int skip_mask,
+                  const nmpc_push_cfg& push, void* stream) {
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !v) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v");
+    if (n_steps < 1) return fail(t, NMPC_E_ARG, "n_steps must be at least 1");
+    if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
+    if (!A) return fail(t, NMPC_E_ARG, "A is NULL");
+    if (a_rows < n_steps) return fail(t, NMPC_E_ARG, "a_rows must be at least n_steps");
+    if (!Q != !V) return fail(t, NMPC_E_ARG, "Q and V come together or not at all");
+    if (Q && qv_rows < n_steps) return fail(t, NMPC_E_ARG, "qv_rows must be at least n_steps");
+    if (Q && !whole_body_tree(t->host))
+        return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
+    if (push.force && B > push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
+    NMPC_ENTER(t, t->device);
+    const int w = t->ct_width, n = t->host.n, nu = t->host.nu;
+    const size_t lds = ct_lds_bytes(n, w);
+    const long long total = (long long)n_steps * n_sub;
+    const Window win = push_window(push, 0, total);
+    for (long long s = 0; s < total;) {
+        const bool pushed = s >= win.lo && s < win.hi;
+        const long long change = s < win.lo ? win.lo : (s < win.hi ? win.hi : total);      // where the kind of substep changes next
+        const long long k = s / n_sub, i0 = s % n_sub, step_end = (k + 1) * n_sub;
+        PushArgs p{};
+        p.B = B; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
+        p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+        p.tau = tau_ff; p.A = A + (size_t)k * nu; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v;
+        if (Q && i0 == 0) { p.Q = Q + (size_t)k * n; p.V = V + (size_t)k * n; }
+        if (i0 != 0 || change < step_end) {      // a piece of control step k
+            const long long end = change < step_end ? change : step_end;
+            p.n_steps = 1; p.n_sub = (int)(end - s);
+            s = end;
+        } else {                                 // whole control steps up to the next change
+            p.n_steps = (int)(change / n_sub - k);
+            s = (k + p.n_steps) * n_sub;
+        }
+        int rc;
+        if (pushed) {
+            p.force = push.force; p.joint = push.joint;
+            rc = launch_step(t, KERNEL_AT_WIDTH(contact_push_kernel, w), w, lds, p, stream);
+        } else {
+            rc = launch_step(t, KERNEL_AT_WIDTH(contact_track_kernel, w), w, lds, static_cast<const TrackArgs&>(p), stream);
+        }
+        if (rc) return rc;
+    }
+    return NMPC_OK;
+}
+
 }  // namespace
+
+bool nmpc_torque::push_attached(void* handle) { return handle && static_cast<const Torque*>(handle)->push.force; }
+
+int nmpc_torque::contact_track_pushed(void* handle, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v,
+                                      const float* tau_ff, const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows,
+                                      const int* skip, int skip_mask, const nmpc_push_cfg& push, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (const char* why = push_refusal(push, t->host.n)) return fail(t, NMPC_E_ARG, why);
+    return contact_track(t, B, n_steps, n_sub, dt, cfg, q, v, tau_ff, A, a_rows, kp, kd, Q, V, qv_rows, skip, skip_mask, push, stream);
+}
 
 const char* nmpc_torque::plan_actions_refusal(void* handle, int n_steps, const int* zoh, float kp, int device) {
     const Torque* t = static_cast<const Torque*>(handle);
@@ -623,17 +757,16 @@ int nmpc_contact_step_batch(void* handle, int B, int n_sub, float dt, const nmpc
                             float* f_out, float* tau_out, void* stream) {
     Torque* t = static_cast<Torque*>(handle);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
-    if (B == 0) return NMPC_OK;
-    if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
-    if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
-    NMPC_ENTER(t, t->device);
-    ContactArgs p{};
-    p.B = B; p.n_sub = n_sub; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
-    p.q = q; p.v = v; p.tau = tau_ff; p.q_des = q_des;
-    p.q_out = q_out; p.v_out = v_out; p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out;
-    const int w = t->ct_width;
-    return launch_step(t, KERNEL_AT_WIDTH(contact_step_kernel, w), w, ct_lds_bytes(t->host.n, w), p, stream);
+    return contact_step(t, B, n_sub, dt, cfg, q, v, tau_ff, q_des, kp, kd, q_out, v_out, a_out, f_out, tau_out, t->push, 0, stream);
+}
+
+int nmpc_contact_set_push(void* torque, const nmpc_push_cfg* push) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (push)
+        if (const char* why = push_refusal(*push, t->host.n)) return fail(t, NMPC_E_ARG, why);      // what was attached stays
+    t->push = push ? *push : nmpc_push_cfg{};
+    return NMPC_OK;
 }
 
 int nmpc_observe_batch(void* handle, int B, const float* q, const float* v, double t, double period, const float* goal, int n_goal,
@@ -658,24 +791,7 @@ int nmpc_contact_track_batch(void* handle, int B, int n_steps, int n_sub, float 
                              const int* skip, int skip_mask, void* stream) {
     Torque* t = static_cast<Torque*>(handle);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
-    if (B == 0) return NMPC_OK;
-    if (B < 0 || !q || !v) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v");
-    if (n_steps < 1) return fail(t, NMPC_E_ARG, "n_steps must be at least 1");
-    if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
-    if (!A) return fail(t, NMPC_E_ARG, "A is NULL");
-    if (a_rows < n_steps) return fail(t, NMPC_E_ARG, "a_rows must be at least n_steps");
-    if (!Q != !V) return fail(t, NMPC_E_ARG, "Q and V come together or not at all");
-    if (Q && qv_rows < n_steps) return fail(t, NMPC_E_ARG, "qv_rows must be at least n_steps");
-    if (Q && !whole_body_tree(t->host))
-        return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
-    NMPC_ENTER(t, t->device);
-    TrackArgs p{};
-    p.B = B; p.n_steps = n_steps; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
-    p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
-    p.tau = tau_ff; p.A = A; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v; p.Q = Q; p.V = V;
-    const int w = t->ct_width;
-    return launch_step(t, KERNEL_AT_WIDTH(contact_track_kernel, w), w, ct_lds_bytes(t->host.n, w), p, stream);
+    return contact_track(t, B, n_steps, n_sub, dt, cfg, q, v, tau_ff, A, a_rows, kp, kd, Q, V, qv_rows, skip, skip_mask, t->push, stream);
 }
 
 int nmpc_observe_rows_batch(void* handle, int B, int n_rows, const float* Q, const float* V, int qv_rows, double t0, double dt_row,
@@ -732,6 +848,7 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     const auto& rec = t->states;
     if (!rec.Q != !rec.V) return fail(t, NMPC_E_ARG, "states: Q and V come together or not at all");
     if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
+    if (t->push.force && B > t->push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
         NMPC_ENTER(t, t->device);
@@ -764,8 +881,9 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
             NMPC_ENTER(t, t->device);
             if (const int rc = launch_elementwise(t, action_rows_kernel, B, stream, nu, t->act, A + (size_t)k * nu, K * nu)) return rc;
         }
-        if (const int rc = nmpc_contact_step_batch(t, B, cfg->n_sub, cfg->dt, ground, q, v, tau_ff, t->act, cfg->kp, cfg->kd, q, v, nullptr, nullptr,
-                                                   nullptr, stream))
+        // the attached push (if any) with its window moved to this step's substeps: s = k n_sub + i
+        if (const int rc = contact_step(t, B, cfg->n_sub, cfg->dt, ground, q, v, tau_ff, t->act, cfg->kp, cfg->kd, q, v, nullptr, nullptr, nullptr,
+                                        t->push, (long long)k * cfg->n_sub, stream))
             return rc;
     }
     return NMPC_OK;

@@ -115,6 +115,16 @@ struct GroundForces {
     }
 };
 
+// the law and a push (DESIGN.md 8d): the world-frame force F at the origin of the body frame of `joint`, in every evaluation --
+// a substep that is not pushed is not run with this source at all (nmpc_torque.hip cuts a call into pushed and un-pushed launches)
+struct PushedGroundForces : GroundForces {
+    V3 F;
+    int joint;
+    static constexpr bool pushes = true;
+    __device__ __forceinline__ bool pushed(int i) const { return i == joint; }
+    __device__ __forceinline__ V3 body() const { return F; }
+};
+
 struct ContactArgs {
     int B, n_sub;
     float dt, kp, kd;

@@ -55,6 +55,13 @@ __device__ __forceinline__ M3 rotated(const M3& R, const M3& A) { return mul(mul
 // foot k, whose point is at p and moves with pd in the world.  A source that reads p, pd says so with `kinematic`: the outward
 // pass then also carries the world position of every body origin, in three slots past FD_SLOTS (FD_PW) that its slice must have.
 constexpr int FD_PW = FD_SLOTS;
+// A source may also push a body: with a member `static constexpr bool pushes = true` it has `pushed(i)`, is body i pushed in this
+// evaluation, and `body()`, the world-frame force at the origin of that body's frame (no moment: a foot force with zero offset).
+// The hook is read under `if constexpr`, so a source without the member compiles to what it compiled to before there was one.
+template <class Force, class = void>
+struct force_pushes : std::false_type {};
+template <class Force>
+struct force_pushes<Force, std::void_t<decltype(Force::pushes)>> : std::bool_constant<Force::pushes> {};
 
 // given forces: f (world-frame foot forces of this robot, or nullptr) is read from memory
 struct GivenForces {
@@ -134,6 +141,19 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
             }
         }
         at.put3(i, FD_P, p_n); at.put3(i, FD_P + 3, p_l);
+        // the push: p^A -= (0; Rw^T F) on the pushed body, and no term at all (not a zero force) on any other evaluation.
+        // It is applied to the slice, from the slice, behind a compiler barrier: the branch then uses no value of the pass
+        // above, whose arithmetic stays the one of a source without the hook (as a term on p_l in registers the pass is
+        // vectorised and fused differently).
+        if constexpr (force_pushes<Force>::value) {
+            if (force.pushed(i)) {
+                __asm__ volatile("" ::: "memory");
+                M3 Rs;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) Rs.m[k] = at(i, FD_RW + k);
+                at.put3(i, FD_P + 3, at.get3(i, FD_P + 3) - mul_t(Rs, force.body()));
+            }
+        }
     }
 
     // inward: U = I^A S, d = S^T U, u = tau - S^T p^A; I^a = I^A - U U^T / d and p^a = p^A + I^a c + U u / d go to the parent

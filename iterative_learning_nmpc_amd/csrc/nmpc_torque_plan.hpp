@@ -20,4 +20,13 @@ const char* label_states_refusal(void* handle, int n_rows, int qv_rows, int a_ro
 // lives on `device` (-1: any device); otherwise the text nmpc_torque_last_error would give
 const char* contact_track_refusal(void* handle, const nmpc_contact_cfg* ground, int n_sub, float dt, int device);
 
+// has the caller attached a push to the handle (nmpc_contact_set_push)
+bool push_attached(void* handle);
+
+// nmpc_contact_track_batch under the explicit `push` (refused as nmpc_contact_set_push refuses it) in place of whatever is
+// attached to the handle, which is neither read nor rewritten: the track launch of a plant-mode rollout that pushes as a force
+int contact_track_pushed(void* handle, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v,
+                         const float* tau_ff, const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows,
+                         const int* skip, int skip_mask, const nmpc_push_cfg& push, void* stream);
+
 }  // namespace nmpc_torque

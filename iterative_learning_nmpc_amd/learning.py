@@ -67,15 +67,16 @@ def train_network(policy, db, n_epoch: int, batch_size: int, lr: float = 1e-3, s
 def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[dict] = None, nominal: int = 0,
                        ood_weight: float = 5.0, terminate_mask: int = TERMINATE_DEFAULT, kp: Optional[float] = None,
                        kd: Optional[float] = None, n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0,
-                       val_fraction: float = 0.0, plant=None, plant_substeps: int = 2):
+                       val_fraction: float = 0.0, plant=None, plant_substeps: int = 2, push_as_force: bool = False):
     """One DAgger iteration, from rollouts to updated parameters: `collect.collect_rollouts` (its arguments up to `kd`, and
-    `plant` / `plant_substeps`: the expert on the ground-contact plant) appends the valid rollouts and their weights to `db`, then
+    `plant` / `plant_substeps` / `push_as_force`: the expert on the ground-contact plant, pushed by a force) appends the valid rollouts and their weights to `db`, then
     `train_network` trains `policy` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows.  Returns (err, weights, n_rows, train_loss, val_loss): what
     the two parts return."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
     err, weights, n_rows = collect_rollouts(mpc, layer, db, q0, v0, T, push=push, nominal=nominal, ood_weight=ood_weight,
-                                            terminate_mask=terminate_mask, kp=kp, kd=kd, plant=plant, plant_substeps=plant_substeps)
+                                            terminate_mask=terminate_mask, kp=kp, kd=kd, plant=plant, plant_substeps=plant_substeps,
+                                            push_as_force=push_as_force)
     n = len(db)
     if n == 0:
         raise ValueError("the database is empty: no rollout of the batch was valid")
@@ -87,7 +88,8 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
 
 def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, tau_ff=None, kp: float = KP,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
-                    terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False):
+                    terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False,
+                    push: Optional[dict] = None):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -100,21 +102,33 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
         q, v            [B, 18]: the state after the last control step
         Q, V            with record_states=True, [B, n_steps, 18]: the plant state before every control step, row k the state
                         row k of S was made of (`BatchedTorqueLayer.set_rollout_states`, attached for this call) -- what
-                        `LocomotionMPC.label_states` starts the expert's solves from."""
+                        `LocomotionMPC.label_states` starts the expert's solves from.
+    push: the dict of `mpc.sample_pushes` -- {"start": s, "duration": s, "force": [B, 3] N} -- as a force on the trunk
+    (`BatchedTorqueLayer.set_push`, attached for this call): the substeps round(start / dt) <= s < round(start / dt) +
+    round(duration / dt) of the rollout are pushed.  None, or a duration that rounds to no substep: the rollout is the bits it
+    is without.  A layer that has a push of the caller's attached already is refused with ValueError: the call would replace
+    it and leave nothing attached."""
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
     if n_steps < 1:
         raise ValueError(f"T = {T} s is shorter than one control step of {n_sub} x {dt} s")
+    if push is not None and layer._push is not None:
+        raise ValueError("push: the layer has a push attached already (set_push)")
     states = {}
     if record_states:
         B = torch.as_tensor(q0).reshape(-1, layer.n).shape[0]
         states = {k: torch.empty(B, n_steps, layer.n, dtype=torch.float32, device=layer.device) for k in ("Q", "V")}
         layer.set_rollout_states(states["Q"], states["V"])
     try:
+        if push is not None:
+            layer.set_push(torch.as_tensor(push["force"], dtype=torch.float32, device=layer.device).reshape(-1, 3),
+                           start_substep=int(round(float(push["start"]) / float(dt))), n_substeps=int(round(float(push["duration"]) / float(dt))))
         q, v, S, A, failed = layer.policy_rollout(policy, q0, v0, n_steps, dt, n_sub, goal, tau_ff=tau_ff, kp=kp, kd=kd,
                                                   ground=GroundContact() if ground is None else ground, t0=t0,
                                                   period=NOMINAL_PERIOD if period is None else period, db=db,
                                                   terminate_mask=terminate_mask, collision_height=collision_height)
     finally:
+        if push is not None:
+            layer.set_push(None)
         if record_states:
             layer.set_rollout_states(None)
     stamp = failed >> NMPC_ROLLOUT_TERM_SHIFT
@@ -124,11 +138,13 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
 
 def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, kp: Optional[float] = None,
                      kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
-                     n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0):
+                     n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0,
+                     push: Optional[dict] = None):
     """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
         1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
            [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
-           given with `set_command`);
+           given with `set_command`), pushed by `push` (the dict of `mpc.sample_pushes`, as `evaluate_policy` takes it:
+           a force on the trunk; None: no push) -- the perturbation the learner is to survive;
         2. `mpc.label_states` on the visited Q, V with dt_row = n_sub dt and the rollout's `failed`: the expert's first solve
            from every state up to each robot's termination and the PD target it would apply from it;
         3. the rows (S[b, k], A*[b, k], goal[b]) with k < steps_survived[b] whose solve neither ended in NaN nor in a QP failure
@@ -142,7 +158,7 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
         raise ValueError("val_fraction must be in [0, 1)")
     kp, kd = float(mpc.Kp if kp is None else kp), float(mpc.Kd if kd is None else kd)
     out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
-                          terminate_mask=terminate_mask, collision_height=collision_height, record_states=True)
+                          terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push)
     A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
     S = out["S"]
     B, K = S.shape[:2]

@@ -215,7 +215,7 @@ class LocomotionMPC:
     def open_loop_device(self, q0: np.ndarray, v0: np.ndarray, trajectory_time: float, push: Optional[dict] = None,
                          record_sim_steps: bool = True, terminate_mask: int = TERMINATE_DEFAULT,
                          collision_height: float = COLLISION_HEIGHT, torque_layer=None, kp: Optional[float] = None,
-                         kd: Optional[float] = None, plant=None, plant_substeps: int = 2):
+                         kd: Optional[float] = None, plant=None, plant_substeps: int = 2, push_as_force: bool = False):
         """`open_loop` with the whole rollout on the device (nmpc_wb_rollout_batch): per replan the problem is assembled from
         the plant state by a kernel, solved with the warm-start shift folded in, and the up-sampled plan is followed for
         `replanning_steps` simulation steps -- one host call, no round trip per replan, the whole batch at once.
@@ -233,7 +233,10 @@ class LocomotionMPC:
         robot is driven by tau_id + Kp (q_plan - q) + Kd (v_plan - v) (mpc.py:583-599) through `plant_substeps` substeps of
         sim_dt / plant_substeps per simulation step, and every replan starts from the state the plant is in.  kp, kd then
         default to the controller's Kp, Kd.  Row j of S is the plant state BEFORE simulation step j and `self.actions` row j
-        the PD target applied from it (RolloutMPC.py:168-258); a robot that falls in the last interval is flagged too."""
+        the PD target applied from it (RolloutMPC.py:168-258); a robot that falls in the last interval is flagged too.
+        push_as_force (needs plant): the push is a force on the trunk of the plant over the substeps its window covers
+        (nmpc_wb_rollout_set_plant_push), where the feet and the torque limit answer it, instead of the velocity jump per
+        replanning interval."""
         import torch
         fs = self.solver
         s = fs._device_solver()
@@ -252,6 +255,8 @@ class LocomotionMPC:
         status = torch.zeros(B, dtype=torch.int32, device=dev)
         if plant is not None and torque_layer is None:
             raise ValueError("plant: the contact plant lives in the torque layer, give torque_layer")
+        if push_as_force and plant is None:
+            raise ValueError("push_as_force: a push as a force needs the contact plant, give plant")
         kp = (self.Kp if plant is not None else KP) if kp is None else kp
         kd = (self.Kd if plant is not None else KD) if kd is None else kd
         A = None
@@ -262,6 +267,8 @@ class LocomotionMPC:
         try:
             if plant is not None:
                 s.set_rollout_plant(torque_layer, plant, plant_substeps, kp, kd)
+            if push_as_force:
+                s.set_rollout_plant_push(True)
             S, failed = s.wb_rollout(
                 s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
                 nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref), by_rollout(push["force"]) if push else None,
@@ -276,6 +283,8 @@ class LocomotionMPC:
                 nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
                 collision_height=float(collision_height))
         finally:
+            if push_as_force:
+                s.set_rollout_plant_push(False)
             if plant is not None:
                 s.set_rollout_plant(None)
             if torque_layer is not None:

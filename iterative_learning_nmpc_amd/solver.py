@@ -159,6 +159,14 @@ class BatchedNmpcSolver:
         _lib.check(self.lib.nmpc_wb_rollout_set_plant(self._h, layer._h, ctypes.byref(cfg) if cfg is not None else None, int(n_sub), float(kp),
                                                       float(kd), ptr(zoh), ptr(Aw), ptr(Qw), ptr(Vw)), self._h, "nmpc_wb_rollout_set_plant")
 
+    def set_rollout_plant_push(self, as_force: bool = False):
+        """nmpc_wb_rollout_set_plant_push: how a `wb_rollout` with a plant attached applies its push_force.  False (the
+        default): the velocity jump F dt_replan / m per replanning interval of the plan-following rollouts.  True: a force on
+        the trunk of the plant (`BatchedTorqueLayer.set_push`'s push, handed to every replan's track launch by the rollout
+        itself) over the substeps of sim_dt / n_sub the window covers; a rollout without a plant is then refused, as is one
+        whose torque layer has a push of the caller's attached."""
+        _lib.check(self.lib.nmpc_wb_rollout_set_plant_push(self._h, int(bool(as_force))), self._h, "nmpc_wb_rollout_set_plant_push")
+
     def set_ipm(self, mu0=10.0, sigma=0.2, s_min=1.0, gamma=0.995, tau_min=0.1, merit_rho=1e3):
         _lib.check(self.lib.nmpc_set_ipm(self._h, mu0, sigma, s_min, gamma, tau_min, merit_rho),
                    self._h, "nmpc_set_ipm")

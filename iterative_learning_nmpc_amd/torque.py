@@ -63,6 +63,8 @@ class BatchedTorqueLayer:
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _lib.check(self.lib.nmpc_torque_create(ctypes.byref(m), idx, ctypes.byref(self._h)), None, "nmpc_torque_create", "torque")
         self.n, self.nu, self.n_feet = n, int(n_actuated), nf
+        self._states = None             # set_rollout_states: the attached (Q, V)
+        self._push = None               # set_push: the attached force
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -243,7 +245,7 @@ class BatchedTorqueLayer:
                 s_mean, s_std = db.states_mean, db.states_std
         s_mean, s_std = self._stats(s_mean, s_std)
         n_steps, n_goal = int(n_steps), goal.shape[1]
-        states = getattr(self, "_states", None)
+        states = self._states
         if states is not None and (states[0].shape[0] != B or states[0].shape[1] < n_steps):      # the attached tables must be this rollout's size
             raise ValueError(f"Q, V (set_rollout_states): need [{B}, >= {n_steps}, {self.n}], got {tuple(states[0].shape)}")
         rows = max(n_steps, 0)
@@ -280,6 +282,23 @@ class BatchedTorqueLayer:
             raise ValueError("Q, V: need the same rows and one layout")
         self._states = (Q, V)
         _lib.check(self.lib.nmpc_policy_rollout_set_states(self._h, ptr(Q), ptr(V), qv_rows), self._h, "nmpc_policy_rollout_set_states", "torque")
+
+    def set_push(self, force: Optional[torch.Tensor] = None, start_substep: int = 0, n_substeps: int = 0, joint: int = 5):
+        """nmpc_contact_set_push: while force [B, 3] (N, world frame, no moment) is attached, robot b of every `contact_step`,
+        `contact_track` and `policy_rollout` of this layer is pushed with force[b] at the origin of the body frame of `joint`
+        (5: the trunk) in the substeps start_substep <= s < start_substep + n_substeps, s counted from 0 at the start of each
+        call (s = k n_sub + i for substep i of control step k).  start_substep may be negative: the window is cut to the call,
+        so a chain of calls with the window moved along is the long call.  Calls with more robots than force has rows are
+        refused.  `set_push(None)` detaches; detached, or with a window that misses the call, every call is the bits it is
+        without.  The layer keeps the tensor alive while it is attached."""
+        if force is None:
+            self._push = None
+            _lib.check(self.lib.nmpc_contact_set_push(self._h, None), self._h, "nmpc_contact_set_push", "torque")
+            return
+        force = self._in(force, (3,), "force")
+        cfg = _lib.NmpcPushCfg(force.data_ptr(), force.shape[0], int(joint), int(start_substep), int(n_substeps))
+        _lib.check(self.lib.nmpc_contact_set_push(self._h, ctypes.byref(cfg)), self._h, "nmpc_contact_set_push", "torque")
+        self._push = force
 
     def _state_io(self, t, name):
         """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""

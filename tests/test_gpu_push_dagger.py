@@ -1,0 +1,84 @@
+"""`learning.dagger_iteration(push=...)`: the learner is pushed while it drives, the expert labels the states it visited under
+the push, and the rows that go into the database are those of the stated selection rule.  B = 4 robots, T = 0.1 s = 10 control
+steps of 20 substeps, an untrained policy, one epoch of batches of 8 (the set-up of tests/test_gpu_dagger_iteration.py)."""
+import numpy as np
+import pytest
+
+from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.solve_helpers import dev, policy_pair  # noqa: F401
+from tests.torque_helpers import same
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+B, K, DT, N_SUB = 4, 10, 5e-4, 20
+T = 0.1
+SEED, BATCH = 7, 8
+START, DURATION = 0.0125, 0.03                 # substeps [25, 85): from inside control step 1 to inside control step 4
+
+
+def setup(dev):
+    from iterative_learning_nmpc_amd import wholebody as wbk
+    from iterative_learning_nmpc_amd.database import DeviceDatabase
+    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
+    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
+    rng = np.random.default_rng(2)
+    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B, 12))
+    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
+    mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
+    goal = np.tile(np.float32([0.2, 0.0, 0.0]), (B, 1))
+    return dict(mpc=mpc, layer=BatchedTorqueLayer(**quadruped_tree(), device=dev), db=DeviceDatabase(limit=256, norm_input=False, device=dev),
+                policy=policy_pair(47, 12, 2, 64, False, 64, seed=3)[0], q0=q0, v0=np.zeros((B, 18)), goal=goal)
+
+
+def run(w, **kw):
+    from iterative_learning_nmpc_amd import learning
+    out = learning.dagger_iteration(w["mpc"], w["layer"], w["db"], w["policy"], w["q0"], w["v0"], w["goal"], T, dt=DT, n_sub=N_SUB,
+                                    n_epoch=1, batch_size=BATCH, lr=1e-3, seed=SEED, val_fraction=0.0, **kw)
+    torch.cuda.synchronize()
+    return out
+
+
+def kept(out):
+    """host copy of the selection rule: k < steps_survived[b] and a status that is neither NaN nor a QP failure"""
+    from iterative_learning_nmpc_amd import _lib
+    st, alive = out["status"].cpu().numpy(), out["steps_survived"].cpu().numpy()
+    return [(b, k) for b in range(B) for k in range(K)
+            if k < alive[b] and st[b, k] not in (_lib.NMPC_STATUS_NAN, _lib.NMPC_STATUS_QP)]
+
+
+def test_the_pushed_iteration_appends_the_rows_of_the_selection_rule(dev):
+    w = setup(dev)
+    force = np.random.default_rng(71).uniform(-80, 80, (B, 3)).astype(np.float32)
+    out = run(w, push=dict(start=START, duration=DURATION, force=force))
+    idx = kept(out)
+    print("steps survived", out["steps_survived"].tolist(), "statuses", out["status"].tolist(), "rows", out["n_rows"])
+    assert out["Q"].shape == (B, K, 18) and out["A_star"].shape == (B, K, 12) and out["status"].shape == (B, K)
+    assert out["n_rows"] == len(idx) == len(w["db"]) and len(idx) > 0
+    bs, ks = (torch.as_tensor(x, device=dev) for x in zip(*idx))
+    db = w["db"]
+    assert same(db.tables["states"][:len(db)], out["S"][bs, ks]) and same(db.tables["actions"][:len(db)], out["A_star"][bs, ks])
+    assert same(db.tables["vc_goals"][:len(db)], torch.as_tensor(w["goal"], device=dev)[bs])
+    assert w["layer"]._push is None
+    # the push was there: the states visited after its first substep are not those of the un-pushed learner
+    plain = run(setup(dev))
+    assert same(out["Q"][:, :2], plain["Q"][:, :2]) and not same(out["V"][:, 2:], plain["V"][:, 2:])
+
+
+def test_without_a_push_the_iteration_trains_as_it_did(dev):
+    """push=None attaches nothing: the loss of every batch is the one of the iteration through `evaluate_policy` and
+    `train_network` without the keyword, on the same seeds"""
+    from iterative_learning_nmpc_amd import learning
+    from iterative_learning_nmpc_amd.database import DeviceDatabase
+    w = setup(dev)
+    out = run(w, push=None)
+    ref = setup(dev)
+    ev = learning.evaluate_policy(ref["layer"], ref["policy"], ref["db"], ref["q0"], ref["v0"], ref["goal"], T, dt=DT, n_sub=N_SUB,
+                                  kp=float(ref["mpc"].Kp), kd=float(ref["mpc"].Kd), record_states=True)
+    assert all(same(out[k], ev[k]) for k in ("S", "A", "Q", "V", "q", "v")) and torch.equal(out["failed"], ev["failed"])
+    idx = kept(out)
+    bs, ks = (torch.as_tensor(x, device=dev) for x in zip(*idx))
+    hand = DeviceDatabase(limit=256, norm_input=False, device=dev)
+    hand.append(out["S"][bs, ks], out["A_star"][bs, ks], torch.as_tensor(w["goal"], device=dev)[bs])
+    loss, _ = learning.train_network(ref["policy"], hand, 1, BATCH, lr=1e-3, seed=SEED)
+    assert out["train_loss"].shape == loss.shape and same(out["train_loss"], loss)
