@@ -75,6 +75,23 @@ int nmpc_fd_step_batch(void *handle, int B, int n_sub, float dt, const float *q,
                        const float *tau_ff, const float *q_des, float kp, float kd, const float *f,
                        float *q_out, float *v_out, float *a_out, void *stream);
 
+/* The tree's inertia at q, from one composite-rigid-body pass (one thread per robot): the joint-space mass matrix M(q) of
+ *   tau = M(q) a + h(q, v) - sum_feet J_foot^T f, so that column j of M is nmpc_id_torques_batch(q, 0, e_j) - (q, 0, 0) on a
+ * tree with every joint actuated.  Any tree the handle accepts.  Massless bodies add nothing (a tree of them has M = 0); nothing
+ * is inverted, so there are no NaN rows of the nmpc_fd_accel_batch kind: a q that is not finite gives outputs that are not
+ * finite in its own row only.  M[i][j] of two joints that are not on one path to the root is written as 0.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), before any launch: B < 0, a NULL q or M. */
+/* M [B][n_joints][n_joints], symmetric, every entry written. */
+int nmpc_mass_matrix_batch(void *handle, int B, const float *q, float *M, void *stream);
+
+/* The centre of mass of the whole tree and its centroidal momentum (pin.computeCentroidalMomentum of the articulated model:
+ * the momentum of all bodies, linear and angular about the centre of mass, in world axes) with its map A_g(q).
+ * NMPC_E_ARG, before any launch: B < 0, a NULL q, all outputs NULL, h without v, a tree whose total mass is zero (its centre
+ * of mass is undefined; decided from the model of nmpc_torque_create). */
+/* com [B][3] world; h [B][6] = [linear (world axes); angular about the centre of mass (world axes)] -- the slot order of
+ * model 2's h; Ag [B][6][n_joints] with h = Ag v.  Every output may be NULL, not all; v may be NULL only if h is. */
+int nmpc_centroidal_batch(void *handle, int B, const float *q, const float *v, float *com, float *h, float *Ag, void *stream);
+
 /* The ground-contact plant [decl] (the reference's is MuJoCo).  The ground is the plane z = ground_z with normal e_z.  A foot
  * point at world position p with world velocity pd and penetration delta = ground_z - p_z is pushed with
  *   f_z  = stiffness delta max(0, 1 - damping pd_z)  for delta > 0, else 0    (Hunt-Crossley: continuous at touch-down, never pulls)

@@ -14,7 +14,8 @@
 // that evaluates it inside that recursion are nmpc_torque_contact.hip.inc; the observation of a plant state for a policy in the
 // loop is nmpc_torque_policy.hip.inc, and the loop itself (nmpc_policy_rollout_batch) is host code at the end of this file;
 // a table of PD targets tracked on the plant in one launch, and the rows of the states it ran through, are
-// nmpc_torque_track.hip.inc.
+// nmpc_torque_track.hip.inc; what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of
+// one composite-rigid-body pass -- is nmpc_torque_crba.hip.inc.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -350,6 +351,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_contact.hip.inc"
 #include "nmpc_torque_policy.hip.inc"
 #include "nmpc_torque_track.hip.inc"
+#include "nmpc_torque_crba.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -432,7 +434,15 @@ int allocate(Torque* t) {
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_push_kernel, t->ct_width)),
                                             hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
+    // the composite-inertia pass: the slice of the largest tree at its one width
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(crba_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)crba_lds_bytes(MAXJ, CR_W)));
     return NMPC_OK;
+}
+
+// both composite-inertia entry points: one launch of crba_kernel
+int launch_crba(Torque* t, const CrbaArgs& p, void* stream) {
+    return launch_step(t, crba_kernel, CR_W, crba_lds_bytes(t->host.n, CR_W), p, stream);
 }
 
 // both forward-dynamics entry points: one launch of fd_kernel at the handle's block width
@@ -727,6 +737,32 @@ int nmpc_fd_step_batch(void* handle, int B, int n_sub, float dt, const float* q,
     p.B = B; p.n_sub = n_sub; p.dt = dt; p.kp = kp; p.kd = kd;
     p.q = q; p.v = v; p.tau = tau_ff; p.q_des = q_des; p.f = f; p.q_out = q_out; p.v_out = v_out; p.a_out = a_out;
     return launch_fd(t, p, stream);
+}
+
+int nmpc_mass_matrix_batch(void* handle, int B, const float* q, float* M, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !M) return fail(t, NMPC_E_ARG, "need B >= 0 and q, M");
+    NMPC_ENTER(t, t->device);
+    CrbaArgs p{};
+    p.B = B; p.q = q; p.M = M;
+    return launch_crba(t, p, stream);
+}
+
+int nmpc_centroidal_batch(void* handle, int B, const float* q, const float* v, float* com, float* h, float* Ag, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || (!com && !h && !Ag)) return fail(t, NMPC_E_ARG, "need B >= 0, q and com, h or Ag");
+    if (h && !v) return fail(t, NMPC_E_ARG, "h needs v");
+    float total = 0.0f;
+    for (int i = 0; i < t->host.n; ++i) total += t->host.mass[i];
+    if (!(total > 0.0f)) return fail(t, NMPC_E_ARG, "the tree has no mass: its centre of mass is undefined");
+    NMPC_ENTER(t, t->device);
+    CrbaArgs p{};
+    p.B = B; p.q = q; p.v = h ? v : nullptr; p.com = com; p.h = h; p.Ag = Ag;
+    return launch_crba(t, p, stream);
 }
 
 int nmpc_foot_kinematics_batch(void* handle, int B, const float* q, const float* v, float* pos, float* vel, void* stream) {

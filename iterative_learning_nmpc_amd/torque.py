@@ -138,6 +138,29 @@ class BatchedTorqueLayer:
                    self._h, "nmpc_fd_step_batch", "torque")
         return q_out, v_out, a_out
 
+    def mass_matrix(self, q) -> torch.Tensor:
+        """nmpc_mass_matrix_batch: q [B, n] -> the joint-space mass matrix M(q) [B, n, n] of the tree, symmetric bit for bit, with
+        exact zeros between joints that are not on one path to the root."""
+        q = self._in(q, (self.n,), "q")
+        B = self._batch(q)
+        M = torch.empty(B, self.n, self.n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nmpc_mass_matrix_batch(self._h, B, ptr(q), ptr(M), stream(self.device)), self._h, "nmpc_mass_matrix_batch", "torque")
+        return M
+
+    def centroidal(self, q, v=None, jacobian: bool = False):
+        """nmpc_centroidal_batch: q [B, n], v [B, n] or None -> (com [B, 3], the world position of the tree's centre of mass;
+        h [B, 6] = [linear; angular about com] in world axes, the centroidal momentum of the articulated tree, None without v)
+        and, with jacobian=True, a third entry Ag [B, 6, n], the centroidal momentum map: h = Ag v."""
+        q = self._in(q, (self.n,), "q")
+        v = self._opt(v, (self.n,), "v")
+        B = self._batch(q, v)
+        com = torch.empty(B, 3, dtype=torch.float32, device=self.device)
+        h = None if v is None else torch.empty(B, 6, dtype=torch.float32, device=self.device)
+        Ag = torch.empty(B, 6, self.n, dtype=torch.float32, device=self.device) if jacobian else None
+        _lib.check(self.lib.nmpc_centroidal_batch(self._h, B, ptr(q), ptr(v), ptr(com), ptr(h), ptr(Ag), stream(self.device)),
+                   self._h, "nmpc_centroidal_batch", "torque")
+        return (com, h, Ag) if jacobian else (com, h)
+
     def foot_kinematics(self, q, v=None):
         """nmpc_foot_kinematics_batch: q, v [B, n] (v None = at rest) -> world position and velocity of every foot point,
         (pos, vel), each [B, n_feet, 3]."""
