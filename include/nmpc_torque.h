@@ -139,6 +139,41 @@ int nmpc_contact_step_batch(void *handle, int B, int n_sub, float dt, const nmpc
 typedef struct { const float *force; int force_rows, joint, first_substep, n_substeps; } nmpc_push_cfg;   /* host struct, copied at the call */
 int nmpc_contact_set_push(void *torque, const nmpc_push_cfg *push);
 
+/* The integrator of the contact plant [decl].  NMPC_INTEGRATOR_EXPLICIT (the default) is the step stated above, launch for launch.
+ * NMPC_INTEGRATOR_LINEARLY_IMPLICIT takes the stiff terms -- ground stiffness and damping, the friction regulariser, the PD law --
+ * at the end of the substep, linearised at its start.  One substep from (q, v):
+ *   1. tau = clamp(tau_ff + kp (q_des - q_j) - kd v_j)                                       (the explicit step's)
+ *   2. f_k = contact(p_k, pd_k) per foot, plus the attached push in the substeps of its window;  a_exp = fd(q, v, tau, f)
+ *   3. for every foot with delta_k > 0, J_k the 3 x n world Jacobian of the foot point, pd_k = J_k v:
+ *        g_k = max(0, 1 - damping pd_k,z),  r_k = sqrt(|pd_k,xy|^2 + slip_velocity^2),  kz_k = stiffness g_k,
+ *        C_k = blockdiag( mu f_k,z (I_2 / r_k - pd_xy pd_xy^T / r_k^3),  g_k > 0 ? stiffness delta_k damping : 0 )
+ *      -- the symmetric positive semidefinite parts of -df/dpd and -df/dp; the coupling of f_xy to pd_z and p_z is dropped, so
+ *      the system below is symmetric positive definite (the scheme is first-order consistent for any such choice);
+ *   4. A = M(q) + sum_k (dt J_k^T C_k J_k + dt^2 kz_k J_k,z^T J_k,z),   rhs = M a_exp - dt sum_k kz_k pd_k,z J_k,z^T, and with
+ *      q_des given, on every actuated joint whose torque the clamp did not cut (tau_max <= 0 or |tau_i| < tau_max):
+ *      A_ii += dt kd + dt^2 kp,  rhs_i -= dt kp v_i;
+ *   5. a = A^-1 rhs (L^T D L on the tree's sparsity: A couples only joints on one path to the root, as M does);
+ *      v += dt a;  q += dt v.
+ * a_out = a; f_out, tau_out are those of steps 1 and 2 of the last substep.  A pivot that is not a positive finite number, or an
+ * unsound fd, gives the robot the NaN rows of nmpc_contact_step_batch in all outputs; other rows are untouched.
+ * What it buys, on the default ground (k = 1e4, c = 3, mu = 0.8, slip_velocity = 0.05), the quadruped dropped from 2 cm, largest
+ * |v| over the last 20 % of 1 s: explicit 6.7e-3 at dt = 0.5 ms, 0.46 at 1 ms (chatters), 7.0 at 2 ms; implicit below 1e-2 at
+ * 0.5, 1 and 2 ms.  What it does not buy: at dt = 4 ms the implicit step no longer settles (0.78), and at slip_velocity = 0.01
+ * its gain is small (0.41 at 2 ms): a factor of 4 in dt on the default ground, not more.
+ * While NMPC_INTEGRATOR_LINEARLY_IMPLICIT is set, nmpc_contact_step_batch, nmpc_contact_track_batch, nmpc_policy_rollout_batch
+ * (through its step launches) and nmpc_wb_rollout_* with a plant (through its track launches) run this substep, with the row
+ * conventions, skip masks, in-place rules and stamps they have; each plant call is one launch of one kernel, 16 robots per
+ * block, and the window of an attached push is tested per substep inside it.  A track is bit for bit the chain of its steps.
+ * nmpc_fd_step_batch, nmpc_fd_accel_batch and nmpc_contact_forces_batch are never affected.
+ * The slice of a robot is 54 n + n (n + 1) / 2 floats of LDS (the forward dynamics' slice and the packed triangle of A); at 16
+ * robots per block a tree fits while 64 (54 n + n (n + 1) / 2) + 24 <= 163 840 bytes: n <= 35, so every tree
+ * nmpc_torque_create accepts (n <= NMPC_TREE_MAX_JOINTS = 32: 144 408 bytes) fits.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), the previous mode staying: a mode other than the two, the implicit mode on a tree
+ * beyond that bound. */
+#define NMPC_INTEGRATOR_EXPLICIT 0
+#define NMPC_INTEGRATOR_LINEARLY_IMPLICIT 1
+int nmpc_contact_set_integrator(void *torque, int mode);
+
 /* A policy in the loop on the contact plant [decl] (the reference: DAgger/utils/RolloutPolicy.py, PolicyController: MLP -> PD
  * target -> torque, in MuJoCo).
  *

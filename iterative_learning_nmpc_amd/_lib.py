@@ -28,6 +28,9 @@ NMPC_ROLLOUT_FLAG_COLLISION = 32
 NMPC_ROLLOUT_FLAG_JOINT_LIMIT = 64      # whole-body rollouts only
 NMPC_ROLLOUT_FLAG_MASK = 0xFF
 NMPC_ROLLOUT_TERM_SHIFT = 8
+# the integrators of the contact plant (include/nmpc_torque.h, nmpc_contact_set_integrator)
+NMPC_INTEGRATOR_EXPLICIT = 0
+NMPC_INTEGRATOR_LINEARLY_IMPLICIT = 1
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -98,6 +101,7 @@ SIGNATURES = {
     "nmpc_contact_step_batch": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_contact_set_push": (c_int, [c_void_p, c_void_p]),
+    "nmpc_contact_set_integrator": (c_int, [c_void_p, c_int]),
     "nmpc_observe_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "nmpc_policy_rollout_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

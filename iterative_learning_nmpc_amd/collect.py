@@ -20,7 +20,7 @@ from .solver import tracking_error
 
 def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = None, nominal: int = 0, ood_weight: float = 5.0,
                      terminate_mask: int = TERMINATE_DEFAULT, kp: Optional[float] = None, kd: Optional[float] = None, plant=None,
-                     plant_substeps: int = 2, push_as_force: bool = False):
+                     plant_substeps: int = 2, push_as_force: bool = False, integrator: Optional[str] = None):
     """One batch of whole-body expert rollouts of `T` seconds into `db`.
 
     mpc: a `LocomotionMPC` (batch B, command set); layer: the robot's `BatchedTorqueLayer`; db: a `DeviceDatabase` with
@@ -33,11 +33,13 @@ def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = No
     plant (a `torque.GroundContact`, None: the plant follows the plan): the expert runs in closed loop on the ground-contact
     plant with `plant_substeps` substeps per simulation step (`open_loop_device`): the rows are then states of the plant, each
     with the PD target the expert applied from it.  kp, kd: as `open_loop_device` (None: its defaults).  push_as_force (with
-    plant): the push is a force on the plant's trunk instead of a velocity jump per replanning interval.
+    plant): the push is a force on the plant's trunk instead of a velocity jump per replanning interval.  integrator (with
+    plant): the plant's integrator, as `open_loop_device` takes it (None: as the layer is set).
     After the call `mpc.actions`, `mpc.failed` and the returned S of the rollout are as `open_loop_device` leaves them
     (`mpc.states` keeps S)."""
     S = mpc.open_loop_device(q0, v0, T, push=push, record_sim_steps=True, terminate_mask=terminate_mask, torque_layer=layer,
-                             kp=kp, kd=kd, plant=plant, plant_substeps=plant_substeps, push_as_force=push_as_force).contiguous()
+                             kp=kp, kd=kd, plant=plant, plant_substeps=plant_substeps, push_as_force=push_as_force,
+                             integrator=integrator).contiguous()
     A = mpc.actions
     mpc.states = S
     B, K = S.shape[:2]

@@ -15,7 +15,8 @@
 // loop is nmpc_torque_policy.hip.inc, and the loop itself (nmpc_policy_rollout_batch) is host code at the end of this file;
 // a table of PD targets tracked on the plant in one launch, and the rows of the states it ran through, are
 // nmpc_torque_track.hip.inc; what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of
-// one composite-rigid-body pass -- is nmpc_torque_crba.hip.inc.
+// one composite-rigid-body pass -- is nmpc_torque_crba.hip.inc; the plant's second integrator, which takes the stiff contact and PD
+// terms implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -352,6 +353,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_policy.hip.inc"
 #include "nmpc_torque_track.hip.inc"
 #include "nmpc_torque_crba.hip.inc"
+#include "nmpc_torque_implicit.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -375,6 +377,7 @@ struct Torque {
         int rows = 0;
     } states;
     nmpc_push_cfg push{};               // nmpc_contact_set_push: the push of the plant calls (force == nullptr: none)
+    int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
 
@@ -437,6 +440,9 @@ int allocate(Torque* t) {
     // the composite-inertia pass: the slice of the largest tree at its one width
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(crba_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)crba_lds_bytes(MAXJ, CR_W)));
+    // the implicit plant step: the slice and the triangle of the largest tree at its one width
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(contact_implicit_kernel<IM_W>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)im_lds_bytes(MAXJ)));
     return NMPC_OK;
 }
 
@@ -511,6 +517,18 @@ Window push_window(const nmpc_push_cfg& push, long long s0, long long total) {
 // A plant call under a push is cut into runs of substeps that are all un-pushed -- launches of the un-pushed kernels, as a call
 // without a push makes them -- and runs that are all pushed, launches of contact_push_kernel (nmpc_torque_track.hip.inc says why).
 
+// why the implicit integrator cannot run a tree of n joints (nullptr: it can)
+const char* implicit_refusal(int n) {
+    if (im_lds_bytes(n) > FD_LDS_MAX) return "integrator: the implicit slice of this tree does not fit the LDS";
+    return nullptr;
+}
+
+// both plant calls under the implicit integrator: one launch of contact_implicit_kernel, the push window tested inside it
+int launch_implicit(Torque* t, ImplicitArgs& p, const nmpc_push_cfg& push, const Window& win, void* stream) {
+    if (win.hi > win.lo) { p.force = push.force; p.joint = push.joint; p.push_lo = win.lo; p.push_hi = win.hi; }
+    return launch_step(t, contact_implicit_kernel<IM_W>, IM_W, im_lds_bytes(t->host.n), p, stream);
+}
+
 // nmpc_contact_step_batch under an explicit push: the call's substep i is substep s0 + i of the count `push` is stated in.
 // At most three launches: before, inside and after the window; the first reads q, v, the later ones go on in place on q_out,
 // v_out, and the last one writes a_out, f_out, tau_out.
@@ -526,6 +544,13 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
     const int w = t->ct_width;
     const size_t lds = ct_lds_bytes(t->host.n, w);
     const Window win = push_window(push, s0, n_sub);
+    if (t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT) {
+        ImplicitArgs p{};
+        p.B = B; p.n_steps = 1; p.n_sub = n_sub; p.a_rows = 1; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+        p.tau = tau_ff; p.A = q_des; p.q = q_out; p.v = v_out; p.q_in = q; p.v_in = v;
+        p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out;
+        return launch_implicit(t, p, push, win, stream);
+    }
     const int cuts[4] = {0, (int)win.lo, (int)win.hi, n_sub};
     bool first = true;
     for (int r = 0; r < 3; ++r) {
@@ -575,6 +600,13 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
     const size_t lds = ct_lds_bytes(n, w);
     const long long total = (long long)n_steps * n_sub;
     const Window win = push_window(push, 0, total);
+    if (t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT) {
+        ImplicitArgs p{};
+        p.B = B; p.n_steps = n_steps; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
+        p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+        p.tau = tau_ff; p.A = A; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v; p.Q = Q; p.V = V;
+        return launch_implicit(t, p, push, win, stream);
+    }
     for (long long s = 0; s < total;) {
         const bool pushed = s >= win.lo && s < win.hi;
         const long long change = s < win.lo ? win.lo : (s < win.hi ? win.hi : total);      // where the kind of substep changes next
@@ -802,6 +834,17 @@ int nmpc_contact_set_push(void* torque, const nmpc_push_cfg* push) {
     if (push)
         if (const char* why = push_refusal(*push, t->host.n)) return fail(t, NMPC_E_ARG, why);      // what was attached stays
     t->push = push ? *push : nmpc_push_cfg{};
+    return NMPC_OK;
+}
+
+int nmpc_contact_set_integrator(void* torque, int mode) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (mode != NMPC_INTEGRATOR_EXPLICIT && mode != NMPC_INTEGRATOR_LINEARLY_IMPLICIT)      // the mode that was set stays
+        return fail(t, NMPC_E_ARG, "integrator: mode must be NMPC_INTEGRATOR_EXPLICIT (0) or NMPC_INTEGRATOR_LINEARLY_IMPLICIT (1)");
+    if (mode == NMPC_INTEGRATOR_LINEARLY_IMPLICIT)
+        if (const char* why = implicit_refusal(t->host.n)) return fail(t, NMPC_E_ARG, why);
+    t->integrator = mode;
     return NMPC_OK;
 }
 

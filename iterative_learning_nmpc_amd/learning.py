@@ -30,7 +30,7 @@ import torch
 from ._lib import NMPC_ROLLOUT_TERM_SHIFT, NMPC_STATUS_NAN, NMPC_STATUS_QP
 from .collect import collect_rollouts
 from .config import TERMINATE_DEFAULT
-from .torque import NOMINAL_PERIOD, GroundContact
+from .torque import NOMINAL_PERIOD, GroundContact, integrator_mode
 from .trajectory_io import KD, KP
 
 
@@ -67,16 +67,17 @@ def train_network(policy, db, n_epoch: int, batch_size: int, lr: float = 1e-3, s
 def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[dict] = None, nominal: int = 0,
                        ood_weight: float = 5.0, terminate_mask: int = TERMINATE_DEFAULT, kp: Optional[float] = None,
                        kd: Optional[float] = None, n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0,
-                       val_fraction: float = 0.0, plant=None, plant_substeps: int = 2, push_as_force: bool = False):
+                       val_fraction: float = 0.0, plant=None, plant_substeps: int = 2, push_as_force: bool = False,
+                       integrator: Optional[str] = None):
     """One DAgger iteration, from rollouts to updated parameters: `collect.collect_rollouts` (its arguments up to `kd`, and
-    `plant` / `plant_substeps` / `push_as_force`: the expert on the ground-contact plant, pushed by a force) appends the valid rollouts and their weights to `db`, then
+    `plant` / `plant_substeps` / `push_as_force` / `integrator`: the expert on the ground-contact plant, pushed by a force, under the named integrator) appends the valid rollouts and their weights to `db`, then
     `train_network` trains `policy` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows.  Returns (err, weights, n_rows, train_loss, val_loss): what
     the two parts return."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
     err, weights, n_rows = collect_rollouts(mpc, layer, db, q0, v0, T, push=push, nominal=nominal, ood_weight=ood_weight,
                                             terminate_mask=terminate_mask, kp=kp, kd=kd, plant=plant, plant_substeps=plant_substeps,
-                                            push_as_force=push_as_force)
+                                            push_as_force=push_as_force, integrator=integrator)
     n = len(db)
     if n == 0:
         raise ValueError("the database is empty: no rollout of the batch was valid")
@@ -89,7 +90,7 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
 def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, tau_ff=None, kp: float = KP,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
                     terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False,
-                    push: Optional[dict] = None):
+                    push: Optional[dict] = None, integrator: Optional[str] = None):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -107,7 +108,12 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     (`BatchedTorqueLayer.set_push`, attached for this call): the substeps round(start / dt) <= s < round(start / dt) +
     round(duration / dt) of the rollout are pushed.  None, or a duration that rounds to no substep: the rollout is the bits it
     is without.  A layer that has a push of the caller's attached already is refused with ValueError: the call would replace
-    it and leave nothing attached."""
+    it and leave nothing attached.
+    integrator: "explicit" or "implicit" sets the layer's integrator first (`BatchedTorqueLayer.set_integrator`; it stays
+    set), None leaves it as it is.  With "implicit", dt = 2e-3 and n_sub = 5 run the same 10 ms control step in a quarter of
+    the substeps."""
+    if integrator is not None:
+        integrator_mode(integrator)                       # an unknown name is refused before anything is attached
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
     if n_steps < 1:
         raise ValueError(f"T = {T} s is shorter than one control step of {n_sub} x {dt} s")
@@ -119,6 +125,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
         states = {k: torch.empty(B, n_steps, layer.n, dtype=torch.float32, device=layer.device) for k in ("Q", "V")}
         layer.set_rollout_states(states["Q"], states["V"])
     try:
+        if integrator is not None:
+            layer.set_integrator(integrator)
         if push is not None:
             layer.set_push(torch.as_tensor(push["force"], dtype=torch.float32, device=layer.device).reshape(-1, 3),
                            start_substep=int(round(float(push["start"]) / float(dt))), n_substeps=int(round(float(push["duration"]) / float(dt))))
@@ -139,7 +147,7 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
 def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, kp: Optional[float] = None,
                      kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
                      n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0,
-                     push: Optional[dict] = None):
+                     push: Optional[dict] = None, integrator: Optional[str] = None):
     """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
         1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
            [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
@@ -152,13 +160,16 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
         4. `train_network` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows, as
            `learning_iteration` does.
     kp, kd: the gains of the policy's PD law and of the labels alike (None: the controller's Kp, Kd), so that an action and
-    its label mean the same torque.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
+    its label mean the same torque.  integrator: the plant's integrator, as `evaluate_policy` takes it.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
     train_loss and val_loss added."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
+    if integrator is not None:
+        integrator_mode(integrator)
     kp, kd = float(mpc.Kp if kp is None else kp), float(mpc.Kd if kd is None else kd)
     out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
-                          terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push)
+                          terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push,
+                          integrator=integrator)
     A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
     S = out["S"]
     B, K = S.shape[:2]

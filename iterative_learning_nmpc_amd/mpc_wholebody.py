@@ -215,7 +215,8 @@ class LocomotionMPC:
     def open_loop_device(self, q0: np.ndarray, v0: np.ndarray, trajectory_time: float, push: Optional[dict] = None,
                          record_sim_steps: bool = True, terminate_mask: int = TERMINATE_DEFAULT,
                          collision_height: float = COLLISION_HEIGHT, torque_layer=None, kp: Optional[float] = None,
-                         kd: Optional[float] = None, plant=None, plant_substeps: int = 2, push_as_force: bool = False):
+                         kd: Optional[float] = None, plant=None, plant_substeps: int = 2, push_as_force: bool = False,
+                         integrator: Optional[str] = None):
         """`open_loop` with the whole rollout on the device (nmpc_wb_rollout_batch): per replan the problem is assembled from
         the plant state by a kernel, solved with the warm-start shift folded in, and the up-sampled plan is followed for
         `replanning_steps` simulation steps -- one host call, no round trip per replan, the whole batch at once.
@@ -236,8 +237,15 @@ class LocomotionMPC:
         the PD target applied from it (RolloutMPC.py:168-258); a robot that falls in the last interval is flagged too.
         push_as_force (needs plant): the push is a force on the trunk of the plant over the substeps its window covers
         (nmpc_wb_rollout_set_plant_push), where the feet and the torque limit answer it, instead of the velocity jump per
-        replanning interval."""
+        replanning interval.
+        integrator (needs plant): "explicit" or "implicit" sets the integrator of torque_layer's plant first
+        (`BatchedTorqueLayer.set_integrator`; it stays set), None leaves it as it is."""
         import torch
+        if integrator is not None:
+            from .torque import integrator_mode
+            integrator_mode(integrator)                   # an unknown name is refused before anything runs
+            if plant is None:
+                raise ValueError("integrator: the integrator is the contact plant's, give plant")
         fs = self.solver
         s = fs._device_solver()
         B, N, dev = self.batch, self.config_opt.n_nodes, s.device
@@ -266,6 +274,8 @@ class LocomotionMPC:
             s.set_rollout_actions(torque_layer, s.to_device(self.id_repeat[:self.replanning_steps], torch.int32), A, kp, kd)
         try:
             if plant is not None:
+                if integrator is not None:
+                    torque_layer.set_integrator(integrator)
                 s.set_rollout_plant(torque_layer, plant, plant_substeps, kp, kd)
             if push_as_force:
                 s.set_rollout_plant_push(True)

@@ -20,6 +20,14 @@ from .config import TERMINATE_DEFAULT, GaitConfigFactory
 from .trajectory_io import KD, KP, N_STATE
 
 NOMINAL_PERIOD = GaitConfigFactory.get("trot").nominal_period      # the recorded phase of a row runs over the gait's nominal period
+INTEGRATORS = {"explicit": _lib.NMPC_INTEGRATOR_EXPLICIT, "implicit": _lib.NMPC_INTEGRATOR_LINEARLY_IMPLICIT}
+
+
+def integrator_mode(name) -> int:
+    """the NMPC_INTEGRATOR_* constant of an integrator's name; ValueError for any other"""
+    if not isinstance(name, str) or name not in INTEGRATORS:
+        raise ValueError(f"integrator: expected one of {sorted(INTEGRATORS)}, got {name!r}")
+    return INTEGRATORS[name]
 
 
 @dataclass(frozen=True)
@@ -27,7 +35,8 @@ class GroundContact:
     """The declared ground-contact law of include/nmpc_torque.h: the plane z = ground_z, Hunt-Crossley normal force
     f_z = stiffness delta max(0, 1 - damping pd_z), regularised Coulomb friction of coefficient mu that is linear below
     slip_velocity, and the torque limit of the step (None: no limit).  The defaults let the 15 kg quadruped stand at
-    dt = 0.5 ms; the explicit step needs mu f_z dt / (slip_velocity m_foot) < 2 and stiffness delta damping dt / m_foot < 2."""
+    dt = 0.5 ms; the explicit step needs mu f_z dt / (slip_velocity m_foot) < 2 and stiffness delta damping dt / m_foot < 2.
+    The linearly implicit integrator (`BatchedTorqueLayer.set_integrator("implicit")`) holds them up to dt = 2 ms."""
     ground_z: float = 0.0
     stiffness: float = 1e4
     damping: float = 3.0
@@ -188,7 +197,8 @@ class BatchedTorqueLayer:
                      ground: GroundContact = GroundContact()):
         """nmpc_contact_step_batch: `step` on the ground -- the contact forces of `ground` re-evaluated from (q, v) in every
         substep, the PD torque clamped to ground.tau_max -> (q, v, a, f, tau): the new state [B, n], and the acceleration
-        [B, n], foot forces [B, n_feet, 3] and clamped torques [B, nu] of the last substep."""
+        [B, n], foot forces [B, n_feet, 3] and clamped torques [B, nu] of the last substep.  The substeps are those of the
+        layer's integrator (`set_integrator`)."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
         tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff"); q_des = self._opt(q_des, (self.nu,), "q_des")
         B = self._batch(q, v, tau_ff, q_des)
@@ -252,6 +262,7 @@ class BatchedTorqueLayer:
         with s_mean, s_std given directly (from column 1 on).  One rollout per layer at a time: the dense actions of a step
         live in a buffer of the layer's handle, which grows (and then synchronises the device) for a larger batch.  Nothing is frozen: a robot whose flags hit terminate_mask is stamped in failed
         (failed >> 8 = 1 + the control step whose observation saw it) and keeps being stepped.
+        The contact steps are those of the layer's integrator (`set_integrator`).
         -> (q, v, S [B, n_steps, 44], A [B, n_steps, 12], failed int32 [B]); S and A are None with record=False."""
         q = self._in(q, (self.n,), "q").clone(); v = self._in(v, (self.n,), "v").clone()
         tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff")
@@ -284,6 +295,18 @@ class BatchedTorqueLayer:
                                                       ptr(failed), stream(self.device)),
                    self._h, "nmpc_policy_rollout_batch", "torque")
         return q, v, S, A, failed
+
+    def set_integrator(self, integrator: str):
+        """nmpc_contact_set_integrator: how `contact_step`, `contact_track`, `policy_rollout` and the expert on the plant take
+        their substeps from now on.  "explicit" (the default): semi-implicit Euler on the explicit contact forces, stable at
+        dt = 0.5 ms on the default ground.  "implicit": the linearly implicit step of include/nmpc_torque.h, which takes ground
+        stiffness and damping, the friction regulariser and the PD law at the end of the substep and holds at dt = 1 - 2 ms
+        (not at 4 ms, and with little gain at slip_velocity = 0.01).  `step`, `forward_dynamics` and `contact_forces` are not
+        affected.  An unknown name is a ValueError; the mode that was set stays.  The three plant calls keep the parameter
+        lists they had: the integrator is the layer's state, set here or through the `integrator=` keyword of
+        `learning.evaluate_policy`, `learning.dagger_iteration` and `open_loop_device(..., plant=...)`."""
+        mode = integrator_mode(integrator)
+        _lib.check(self.lib.nmpc_contact_set_integrator(self._h, mode), self._h, "nmpc_contact_set_integrator", "torque")
 
     def set_rollout_states(self, Q: Optional[torch.Tensor] = None, V: Optional[torch.Tensor] = None):
         """nmpc_policy_rollout_set_states: while Q, V [B, rows, 18] (rows >= n_steps; slices [:, :k] of longer tables are taken
@@ -351,7 +374,8 @@ class BatchedTorqueLayer:
         [:, :n_steps] of a longer table is taken with its stride).  Q, V [B, n_steps, 18]: the state before every control step
         (row 0 is the start state), written into the given tensors (again slices are fine) or into new ones with record=True;
         None with record=False.  skip int32 [B]: robots with skip[b] & skip_mask != 0 are left out, their q, v and rows
-        untouched.  Bit for bit the chain of `contact_step` calls.  -> (q, v, Q, V)."""
+        untouched.  Bit for bit the chain of `contact_step` calls, under either integrator (`set_integrator`).
+        -> (q, v, Q, V)."""
         q = self._state_io(q, "q"); v = self._state_io(v, "v")
         tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff")
         B = self._batch(q, v, tau_ff)

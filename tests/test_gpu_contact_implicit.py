@@ -1,0 +1,360 @@
+"""GPU checks of the linearly implicit integrator of the ground-contact plant (nmpc_contact_set_integrator) against
+tests/implicit_reference.py (itself checked in tests/test_implicit_reference.py).
+
+The accuracy bar is `torque_helpers.bar`: a device result is compared with the fp64 reference under
+    max(1e-5 * scale, 4 x the deviation of the numpy-float32 run of the same reference loop from the fp64 run),
+both computed here or stored by tests/golden/make_golden_implicit_settle.py, never from the code under test.  Bit-for-bit claims
+are `torque_helpers.same`.  Every figure is printed before it is asserted."""
+import copy
+import os
+
+import numpy as np
+import pytest
+
+from tests import contact_reference as cr
+from tests import fd_reference as fr
+from tests import implicit_reference as ir
+from tests import push_reference as pr
+from tests.torque_helpers import Case, branches, ground, held, host, layer, same
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+KP, KD, DT = 20.0, 1.5, 2e-3
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "implicit_settle.npz")
+NAMES = ("q", "v", "a", "f", "tau")
+
+
+def implicit_layer(m):
+    L = layer(m)
+    L.set_integrator("implicit")
+    return L
+
+
+AT = 1e-6          # a foot this close to the plane is "at" it: the tolerance `torque_helpers.Case` places its feet with
+
+
+class Run:
+    """One substep and four of B robots through implicit_step_ref in fp64 and in float32: the four are the one and three more
+    from its end state, so every robot costs four reference substeps per format.  The scheme is discontinuous where a foot is at the plane -- `delta > 0` switches kz from 0 to stiffness g, a
+    jump of about dt stiffness |pd_z| / m_foot in the acceleration -- and there fp64, float32 and the device each decide by their
+    own rounding of delta (|delta| < 1e-7 on the feet `Case` puts at the plane).  A robot with a foot within AT of the plane
+    therefore has one reference per side of that foot, each with its own float32 run: the side whose fp64 acceleration is nearer
+    to the device's is the robot's reference, and the arrays of all robots are then held as `torque_helpers.held` holds them."""
+    def __init__(self, m, g, q, v, tau_ff, q_des):
+        self.m, self.g, self.q, self.v, self.tau_ff, self.q_des = m, g, q, v, tau_ff, q_des
+        arg = lambda x, b: None if x is None else x[b]                                                  # noqa: E731
+        self.sides = []                 # per robot: the candidates of `first_inside`
+        for b in range(len(q)):
+            at = np.abs(g.ground_z - cr.feet(m, q[b])[0][:, 2]) < AT
+            assert at.sum() <= 1
+            self.sides.append([[side if a else None for a in at] for side in (True, False)] if at.any() else [None])
+        self.ref, self.f32 = {1: [], 4: []}, {1: [], 4: []}
+        for b in range(len(q)):
+            for out, dtype in ((self.ref, np.float64), (self.f32, np.float32)):
+                one = [ir.implicit_step_ref(m, g, q[b], v[b], DT, 1, arg(tau_ff, b), arg(q_des, b), KP, KD, dtype=dtype, first_inside=s) for s in self.sides[b]]
+                out[1].append(one)
+                out[4].append([ir.implicit_step_ref(m, g, o[0], o[1], DT, 3, arg(tau_ff, b), arg(q_des, b), KP, KD, dtype=dtype) for o in one])
+        self.ref1 = [np.stack(x) for x in zip(*[r[-1] for r in self.ref[1]])]      # the first substep of every robot, for the counts of the cases
+
+    def device(self, L, n_sub, rows=slice(None)):
+        kw = {k: (None if x is None else x[rows]) for k, x in (("tau_ff", self.tau_ff), ("q_des", self.q_des))}
+        return L.contact_step(self.q[rows], self.v[rows], DT, n_sub, kp=KP, kd=KD, ground=ground(self.g), **kw)
+
+    def holds(self, got, n_sub):
+        side = [int(np.argmin([np.abs(got[2][b] - ref[2]).max() for ref in self.ref[n_sub][b]])) for b in range(len(self.q))]
+        print(f"  feet at the plane: robots {[b for b, s in enumerate(self.sides) if len(s) > 1]}, "
+              f"taken as inside: {[b for b, s in enumerate(self.sides) if len(s) > 1 and side[b] == 0]}")
+        ref = [np.stack(x) for x in zip(*[self.ref[n_sub][b][side[b]] for b in range(len(self.q))])]
+        f32 = [np.stack(x) for x in zip(*[self.f32[n_sub][b][side[b]] for b in range(len(self.q))])]
+        return all([held(name, x, r, f) for name, x, r, f in zip(NAMES, got, ref, f32)])
+
+
+class Worlds(dict):
+    """quadruped: `Case(fr.quadruped(0.1), 33, seed)`, lowest foot at -3 mm / 0 / +2 cm in turn, with a PD target and a torque
+    limit that cuts some joints ("pd") or with the feed-forward torque alone ("ff"); tree23: `fr.random_tree()` at B = 5 on the
+    soft ground at the median foot height (prismatic joints, two feet on one body, a foot on joint 0, every joint actuated)."""
+    def __missing__(self, key):
+        if key == "case":
+            self[key] = Case(fr.quadruped(0.1), 33, seed=41)
+        elif key == "L":
+            self[key] = implicit_layer(self["case"].m)
+        elif key in ("pd", "ff"):
+            c = self["case"]
+            q_des = (c.q[:, 6:] + np.random.default_rng(3).uniform(-0.1, 0.1, (33, 12))).astype(np.float32) if key == "pd" else None
+            g = cr.Ground(tau_max=12.0) if key == "pd" else c.g
+            self[key] = Run(c.m, g, c.q, c.v, c.tau, q_des)
+        elif key == "tree23":
+            m = fr.random_tree()
+            q, v, tau, _ = fr.inputs(m, 5, 5)
+            q_des = (q + np.random.default_rng(4).uniform(-0.1, 0.1, q.shape)).astype(np.float32)
+            g = cr.Ground(**{**pr.general_ground(m, q).__dict__, "tau_max": 15.0})
+            self[key] = Run(m, g, q, v, tau, q_des)
+            self["L23"] = implicit_layer(m)
+        return self[key]
+
+
+@pytest.fixture(scope="module")
+def worlds():
+    return Worlds()
+
+
+# ---- accuracy -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_sub", [1, 4])
+@pytest.mark.parametrize("kind", ["pd", "ff"])
+def test_the_quadruped_step_matches_the_reference(worlds, kind, n_sub):
+    r, c = worlds[kind], worlds["case"]
+    off, pushed, leaving = branches(r.g, c.pos, c.vel, r.ref1[3])
+    print(f"{kind}, {n_sub} substeps of {DT} s, B 33: feet off the ground {off}, pushed {pushed}, leaving {leaving}")
+    assert off and pushed
+    if kind == "pd":
+        cut = int((np.abs(r.ref1[4]) == 12.0).sum())
+        print(f"  torques at the limit: {cut} of {r.ref1[4].size}")
+        assert 0 < cut < r.ref1[4].size
+    got = host(*r.device(worlds["L"], n_sub))
+    assert [x.shape for x in got] == [(33, 18)] * 3 + [(33, 4, 3), (33, 12)]
+    assert r.holds(got, n_sub)
+
+
+@pytest.mark.parametrize("n_sub", [1, 4])
+def test_the_general_tree_step_matches_the_reference(worlds, n_sub):
+    r = worlds["tree23"]
+    pos = np.stack([cr.feet(r.m, r.q[b])[0] for b in range(5)])
+    inside = int((r.g.ground_z - pos[..., 2] > 0).sum())
+    cut = int((np.abs(r.ref1[4]) == 15.0).sum())
+    print(f"tree23, {n_sub} substeps, B 5: feet in the ground {inside} of {pos.shape[0] * pos.shape[1]}, torques at the limit {cut}")
+    assert 0 < inside < pos.shape[0] * pos.shape[1] and cut > 0
+    assert r.holds(host(*r.device(worlds["L23"], n_sub)), n_sub)
+
+
+def test_the_implicit_step_is_not_the_explicit_step(worlds):
+    r = worlds["pd"]
+    L2 = layer(worlds["case"].m)
+    assert not same(r.device(worlds["L"], 1)[1], r.device(L2, 1)[1])
+
+
+# ---- settling -------------------------------------------------------------------------------------------------------------------
+def test_the_drop_settles_at_two_milliseconds():
+    """contact_reference.drop() at dt = 2 ms x 500 (tests/golden/implicit_settle.npz): 400 substeps in one call, then 100 single
+    ones whose velocities are the tail."""
+    d, G = cr.drop(), np.load(GOLDEN)
+    assert np.array_equal(G["q0"], d["q"]) and float(G["dt"]) == DT and int(G["n_sub"]) == 500
+    L = implicit_layer(d["m"])
+    kw = dict(tau_ff=d["tau_ff"][None], q_des=d["q_des"][None], kp=d["kp"], kd=d["kd"], ground=ground(d["g"]))
+    q, v = L.contact_step(d["q"][None], d["v"][None], DT, 400, **kw)[:2]
+    tail = []
+    for _ in range(100):
+        q, v = L.contact_step(q, v, DT, 1, **kw)[:2]
+        tail.append(v)
+    speed = float(torch.stack(tail).abs().max())
+    q, v = host(q, v)
+    print(f"tail |v| {speed:.2e} (fp64 reference {float(G['tail']):.2e}, float32 {float(G['tail32']):.2e}); z {q[0, 2]:.4f}, pitch {q[0, 4]:.4f}")
+    assert held("q", q[0], G["q"], G["q32"]) and held("v", v[0], G["v"], G["v32"])
+    assert speed <= 2e-2
+
+
+# ---- chains, bit for bit ------------------------------------------------------------------------------------------------------------
+N_STEPS, N_SUB, FIRST, COUNT = 3, 2, 3, 2          # the window [3, 5) of 6 substeps starts in the middle of control step 1
+SENTINEL = -77.0
+
+
+class Chains:
+    B = 33
+
+    def __init__(self, worlds):
+        c = worlds["case"]
+        self.L = L = worlds["L"]
+        rng = np.random.default_rng(12)
+        dev = lambda x: torch.as_tensor(np.asarray(x, np.float32), device=L.device)                      # noqa: E731
+        self.q, self.v, self.tau = dev(c.q), dev(c.v), dev(0.1 * c.tau)
+        self.A = dev(fr.STAND[None, None, :] + rng.uniform(-0.05, 0.05, (self.B, N_STEPS + 2, 12)))
+        self.F = dev(rng.uniform(-80, 80, (self.B, 3)))
+        self.g = ground(cr.Ground(tau_max=12.0))
+
+    def chain(self, rows, pushed):
+        L, q, v = self.L, self.q[rows], self.v[rows]
+        Q, V = [], []
+        for k in range(N_STEPS):
+            Q.append(q); V.append(v)
+            if pushed:
+                L.set_push(self.F[rows], FIRST - N_SUB * k, COUNT)
+            q, v = L.contact_step(q, v, DT, N_SUB, tau_ff=self.tau[rows], q_des=self.A[rows, k].contiguous(), kp=KP, kd=KD, ground=self.g)[:2]
+        L.set_push(None)
+        return q, v, torch.stack(Q, 1), torch.stack(V, 1)
+
+    def track(self, rows, pushed, skip=None, skip_mask=0):
+        L, q, v = self.L, self.q[rows].clone(), self.v[rows].clone()
+        Qt, Vt = (torch.full((q.shape[0], N_STEPS + 1, 18), SENTINEL, dtype=torch.float32, device=L.device) for _ in range(2))
+        if pushed:
+            L.set_push(self.F[rows], FIRST, COUNT)
+        try:
+            L.contact_track(q, v, self.A[rows][:, :N_STEPS], DT, N_SUB, tau_ff=self.tau[rows], kp=KP, kd=KD, ground=self.g, Q=Qt[:, :N_STEPS],
+                            V=Vt[:, :N_STEPS], skip=skip, skip_mask=skip_mask)
+        finally:
+            L.set_push(None)
+        return q, v, Qt[:, :N_STEPS], Vt[:, :N_STEPS], Qt, Vt
+
+
+@pytest.fixture(scope="module")
+def chains(worlds):
+    return Chains(worlds)
+
+
+@pytest.mark.parametrize("pushed", [False, True])
+def test_the_implicit_track_is_the_chain_of_implicit_steps(chains, pushed):
+    rows = slice(0, 33)
+    ref, got = chains.chain(rows, pushed), chains.track(rows, pushed)
+    print(f"pushed {pushed}: largest |track - chain| of q, v, Q, V: {[float((a - b).abs().max()) for a, b in zip(got[:4], ref)]}")
+    assert all(same(a, b) for a, b in zip(got[:4], ref))
+    assert bool((got[4][:, N_STEPS:] == SENTINEL).all()) and bool((got[5][:, N_STEPS:] == SENTINEL).all())
+    if pushed:       # rows 0 and 1 are written before the first pushed substep (3 = substep 1 of step 1), row 2 after it
+        plain = chains.chain(rows, False)
+        assert same(got[2][:, :2], plain[2][:, :2]) and not same(got[3][:, 2], plain[3][:, 2]) and not same(got[1], plain[1])
+
+
+def test_a_skipped_robot_is_untouched(chains):
+    B = 33
+    skip = torch.zeros(B, dtype=torch.int32, device=chains.L.device)
+    skip[::3] = 4 | 1
+    skip[1::3] = 1
+    q, v, Q, V, Qt, Vt = chains.track(slice(0, B), True, skip=skip, skip_mask=4)
+    out, kept = torch.arange(B, device=q.device) % 3 == 0, torch.arange(B, device=q.device) % 3 != 0
+    assert same(q[out], chains.q[out]) and same(v[out], chains.v[out])
+    assert bool((Qt[out] == SENTINEL).all()) and bool((Vt[out] == SENTINEL).all())
+    assert all(same(a[kept], b[kept]) for a, b in zip((q, v, Q, V), chains.chain(slice(0, B), True)))
+
+
+def test_rows_do_not_depend_on_the_batch(chains):
+    full = chains.track(slice(0, 33), True)
+    for b in (0, 15, 16, 32):
+        alone = chains.track(slice(b, b + 1), True)
+        assert all(same(a[b:b + 1], x) for a, x in zip(full[:4], alone[:4])), b
+    step = chains.L.contact_step(chains.q, chains.v, DT, 4, tau_ff=chains.tau, q_des=chains.A[:, 0].contiguous(), kp=KP, kd=KD, ground=chains.g)
+    for b in (0, 15, 16, 32):
+        alone = chains.L.contact_step(chains.q[b:b + 1], chains.v[b:b + 1], DT, 4, tau_ff=chains.tau[b:b + 1], q_des=chains.A[b:b + 1, 0].contiguous(),
+                                      kp=KP, kd=KD, ground=chains.g)
+        assert all(same(a[b:b + 1], x) for a, x in zip(step, alone)), b
+
+
+def test_the_implicit_policy_rollout_is_the_chain_of_its_calls(chains):
+    from tests.test_gpu_policy_rollout import device_policy
+    from oracle.policy_oracle import PolicyOracle
+    L, B, K, n_sub, T0, PERIOD = chains.L, 33, 2, 2, 0.37, 0.5
+    rng = np.random.default_rng(11)
+    o = PolicyOracle(44 + 3, 12, 2, 64, True)
+    o.theta = (rng.standard_normal(o.n_theta) * 0.02).astype(np.float32).astype(np.float64)
+    o.view()["b2"][:] = fr.STAND.astype(np.float32)
+    policy = device_policy(o, B)
+    goal = torch.as_tensor(rng.uniform(-0.5, 0.5, (B, 3)).astype(np.float32), device=L.device)
+    dt32 = float(np.float32(DT))
+    q, v = chains.q, chains.v
+    failed = torch.zeros(B, dtype=torch.int32, device=L.device)
+    S, A = [], []
+    for k in range(K):
+        s, x = L.observe(q, v, T0 + (k * n_sub) * dt32, PERIOD, goal, failed=failed, step_index=k, term_mask=0)
+        a = policy.forward(x).clone()
+        q, v = L.contact_step(q, v, DT, n_sub, tau_ff=chains.tau, q_des=a, kp=KP, kd=KD, ground=chains.g)[:2]
+        S.append(s); A.append(a)
+    L.observe(q, v, T0 + (K * n_sub) * dt32, PERIOD, goal, failed=failed, step_index=K, term_mask=0)
+    got = L.policy_rollout(policy, chains.q, chains.v, K, DT, n_sub, goal, tau_ff=chains.tau, kp=KP, kd=KD, ground=chains.g, t0=T0, period=PERIOD,
+                           terminate_mask=0)
+    assert same(got[0], q) and same(got[1], v) and same(got[2], torch.stack(S, 1)) and same(got[3], torch.stack(A, 1))
+    assert torch.equal(got[4], failed)
+    explicit = layer(chains_model(chains)).policy_rollout(policy, chains.q, chains.v, K, DT, n_sub, goal, tau_ff=chains.tau, kp=KP, kd=KD, ground=chains.g,
+                                                          t0=T0, period=PERIOD, terminate_mask=0)
+    assert not same(explicit[1], got[1])
+
+
+def chains_model(chains):
+    return fr.quadruped(0.1)
+
+
+# ---- mode hygiene -----------------------------------------------------------------------------------------------------------------
+def test_back_to_explicit_is_a_layer_that_never_left(chains):
+    m = chains_model(chains)
+    fresh, L = layer(m), layer(m)
+    L.set_integrator("implicit")
+    L.contact_step(chains.q, chains.v, DT, 1)
+    L.set_integrator("explicit")
+    dt, A = 5e-4, chains.A[:, :N_STEPS]
+    kw = dict(tau_ff=chains.tau, q_des=chains.A[:, 0].contiguous(), kp=KP, kd=KD, ground=chains.g)
+    assert all(same(a, b) for a, b in zip(L.contact_step(chains.q, chains.v, dt, 4, **kw), fresh.contact_step(chains.q, chains.v, dt, 4, **kw)))
+    tracks = [X.contact_track(chains.q.clone(), chains.v.clone(), A, dt, 2, tau_ff=chains.tau, kp=KP, kd=KD, ground=chains.g) for X in (L, fresh)]
+    assert all(same(a, b) for a, b in zip(*tracks))
+    pushed = []
+    for X in (L, fresh):
+        X.set_push(chains.F, 1, 2)
+        pushed.append(X.contact_step(chains.q, chains.v, dt, 4, **kw))
+        X.set_push(None)
+    assert all(same(a, b) for a, b in zip(*pushed))
+    # and set again it is the implicit layer, and stays so
+    L.set_integrator("implicit")
+    again = L.contact_step(chains.q, chains.v, DT, 2, **kw)
+    assert all(same(a, b) for a, b in zip(again, chains.L.contact_step(chains.q, chains.v, DT, 2, **kw)))
+    assert all(same(a, b) for a, b in zip(L.contact_step(chains.q, chains.v, DT, 2, **kw), again))
+
+
+def test_the_given_force_step_is_the_same_in_both_modes(chains):
+    f = torch.zeros(33, 4, 3, device=chains.L.device)
+    f[:, :, 2] = 30.0
+    kw = dict(tau_ff=chains.tau, q_des=chains.A[:, 0].contiguous(), kp=KP, kd=KD, f=f)
+    explicit = layer(chains_model(chains)).step(chains.q, chains.v, 5e-4, 3, **kw)
+    assert all(same(a, b) for a, b in zip(chains.L.step(chains.q, chains.v, 5e-4, 3, **kw), explicit))
+    fa = chains.L.forward_dynamics(chains.q, chains.v, chains.tau, f)
+    assert same(fa, layer(chains_model(chains)).forward_dynamics(chains.q, chains.v, chains.tau, f))
+
+
+# ---- refusals and NaN ---------------------------------------------------------------------------------------------------------------
+def test_a_bad_mode_is_refused_and_the_mode_stays(chains):
+    from iterative_learning_nmpc_amd import _lib
+    L = implicit_layer(chains_model(chains))
+    kw = dict(tau_ff=chains.tau, q_des=chains.A[:, 0].contiguous(), kp=KP, kd=KD, ground=chains.g)
+    before = L.contact_step(chains.q, chains.v, DT, 2, **kw)
+    for mode in (2, -1, 7):
+        assert L.lib.nmpc_contact_set_integrator(L._h, mode) == -1
+        assert "integrator" in L.lib.nmpc_torque_last_error(L._h).decode()
+    assert L.lib.nmpc_contact_set_integrator(None, 1) == -1
+    with pytest.raises(ValueError, match="integrator"):
+        L.set_integrator("rk4")
+    with pytest.raises(ValueError, match="integrator"):
+        L.set_integrator("Implicit")
+    assert all(same(a, b) for a, b in zip(L.contact_step(chains.q, chains.v, DT, 2, **kw), before))
+    assert _lib.NMPC_INTEGRATOR_LINEARLY_IMPLICIT == 1
+
+
+def test_the_largest_tree_is_within_the_bound():
+    """The header's bound admits every tree of up to 32 joints: the 32-joint tree is not refused, and its step is finite."""
+    m = fr.random_tree(n=32, seed=14, feet=(4, 31, 31, 17))
+    L = implicit_layer(m)
+    q, v, tau, _ = fr.inputs(m, 17, 7)
+    out = host(*L.contact_step(q, v, DT, 2, tau_ff=tau, q_des=q, kp=KP, kd=KD, ground=ground(pr.general_ground(m, q))))
+    assert all(np.isfinite(x).all() for x in out)
+    ref = ir.implicit_step_ref(m, pr.general_ground(m, q), q[16], v[16], DT, 2, tau[16], q[16], KP, KD)
+    f32 = ir.implicit_step_ref(m, pr.general_ground(m, q), q[16], v[16], DT, 2, tau[16], q[16], KP, KD, dtype=np.float32)
+    assert all([held(name, x[16], r, f) for name, x, r, f in zip(NAMES, out, ref, f32)])
+
+
+def test_unsound_robots_get_nan_rows_and_their_neighbours_keep_their_bits(chains):
+    B = 33
+    kw = dict(tau_ff=chains.tau, q_des=chains.A[:, 0].contiguous(), kp=KP, kd=KD, ground=chains.g)
+    bad = copy.deepcopy(chains_model(chains))
+    bad.mass[17] = 0.0; bad.inertia[17] = 0.0
+    out = host(*implicit_layer(bad).contact_step(chains.q, chains.v, DT, 2, **kw))
+    assert [x.shape for x in out] == [(B, 18)] * 3 + [(B, 4, 3), (B, 12)] and all(np.isnan(x).all() for x in out)
+    # a robot whose own state is not finite: its rows are NaN, every other row is the bits of the clean call
+    clean = chains.L.contact_step(chains.q, chains.v, DT, 2, **kw)
+    q = chains.q.clone()
+    q[16, 9] = float("nan")
+    got = chains.L.contact_step(q, chains.v, DT, 2, **kw)
+    others = torch.arange(B, device=q.device) != 16
+    assert all(bool(torch.isnan(x[16]).all()) for x in got)
+    assert all(same(x[others], y[others]) for x, y in zip(got, clean))
+    Q = chains.L.contact_track(q.clone(), chains.v.clone(), chains.A[:, :N_STEPS], DT, N_SUB, tau_ff=chains.tau, kp=KP, kd=KD, ground=chains.g)
+    assert bool(torch.isnan(Q[0][16]).all()) and bool(torch.isfinite(Q[0][others]).all())
+
+
+def test_an_empty_batch_launches_nothing(chains):
+    L = chains.L
+    assert [tuple(x.shape) for x in L.contact_step(chains.q[:0], chains.v[:0], DT, 3)] == [(0, 18)] * 3 + [(0, 4, 3), (0, 12)]
+    q, v = chains.q[:0].clone(), chains.v[:0].clone()
+    assert L.contact_track(q, v, chains.A[:0, :N_STEPS], DT, N_SUB)[2].shape == (0, N_STEPS, 18)
