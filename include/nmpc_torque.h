@@ -92,6 +92,24 @@ int nmpc_mass_matrix_batch(void *handle, int B, const float *q, float *M, void *
  * model 2's h; Ag [B][6][n_joints] with h = Ag v.  Every output may be NULL, not all; v may be NULL only if h is. */
 int nmpc_centroidal_batch(void *handle, int B, const float *q, const float *v, float *com, float *h, float *Ag, void *stream);
 
+/* How that momentum moves with q (pin.computeCentroidalDynamicsDerivatives' dh_dq, and the bias part of
+ * pin.computeCentroidalMomentumTimeVariation): what a linearisation of h - A_g(q) v needs beside A_g and com.  One thread per
+ * robot, one launch, three passes over the tree in world-frame spatial vectors about a point O at the robot (the origin of the
+ * first frame that carries mass; nothing is taken through the world origin, so the base position does not cost accuracy):
+ *   d h_O / d q_j = S_j x* h^c_j  -  I^c_j (S_j x v_p(j))           at fixed v
+ * with S_j the motion axis of joint j, h^c_j, I^c_j the momentum and inertia of the subtree of body j, v_p(j) the velocity of the
+ * parent body (zero for a root), x / x* the motion / force cross product; then
+ *   d com / d q_j = lin(I^c_j S_j) / m                               (column j of Ag's linear rows over the total mass)
+ *   d k_G / d q_j = d k_O / d q_j - d com / d q_j x l - (com - O) x d l / d q_j
+ *   hdot_bias     = sum_j dh_dq[:, j] v_j  in joint order            (q_dot = v), so that h_dot = Ag a + hdot_bias.
+ * Any tree the handle accepts; nothing is inverted, so a q or v that is not finite gives outputs that are not finite in its own
+ * row only, and massless bodies add nothing.  Every entry of every given output is written.
+ * NMPC_E_ARG, before any launch: B < 0, a NULL q or v, all outputs NULL, a tree whose total mass is zero. */
+/* q, v [B][n_joints]; dh_dq [B][6][n_joints] = d(A_g(q) v)/dq_j, rows in the slot order of h; dcom_dq [B][3][n_joints];
+ * hdot_bias [B][6].  Every output may be NULL, not all. */
+int nmpc_centroidal_derivatives_batch(void *handle, int B, const float *q, const float *v,
+                                      float *dh_dq, float *dcom_dq, float *hdot_bias, void *stream);
+
 /* The ground-contact plant [decl] (the reference's is MuJoCo).  The ground is the plane z = ground_z with normal e_z.  A foot
  * point at world position p with world velocity pd and penetration delta = ground_z - p_z is pushed with
  *   f_z  = stiffness delta max(0, 1 - damping pd_z)  for delta > 0, else 0    (Hunt-Crossley: continuous at touch-down, never pulls)

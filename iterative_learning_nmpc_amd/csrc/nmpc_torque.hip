@@ -16,7 +16,8 @@
 // a table of PD targets tracked on the plant in one launch, and the rows of the states it ran through, are
 // nmpc_torque_track.hip.inc; what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of
 // one composite-rigid-body pass -- is nmpc_torque_crba.hip.inc; the plant's second integrator, which takes the stiff contact and PD
-// terms implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc.
+// terms implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; how the centroidal momentum moves with q --
+// d(A_g v)/dq, d com/dq and the bias of its time derivative -- is nmpc_torque_cmd.hip.inc.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -354,6 +355,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_track.hip.inc"
 #include "nmpc_torque_crba.hip.inc"
 #include "nmpc_torque_implicit.hip.inc"
+#include "nmpc_torque_cmd.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -443,7 +445,17 @@ int allocate(Torque* t) {
     // the implicit plant step: the slice and the triangle of the largest tree at its one width
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(contact_implicit_kernel<IM_W>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)im_lds_bytes(MAXJ)));
+    // the momentum derivatives: the slice of the largest tree at its one width
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(cmd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)cmd_lds_bytes(MAXJ, CD_W)));
     return NMPC_OK;
+}
+
+// the total mass of the handle's tree: the centroidal calls refuse a tree without any
+float total_mass(const Model& m) {
+    float total = 0.0f;
+    for (int i = 0; i < m.n; ++i) total += m.mass[i];
+    return total;
 }
 
 // both composite-inertia entry points: one launch of crba_kernel
@@ -788,13 +800,28 @@ int nmpc_centroidal_batch(void* handle, int B, const float* q, const float* v, f
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || (!com && !h && !Ag)) return fail(t, NMPC_E_ARG, "need B >= 0, q and com, h or Ag");
     if (h && !v) return fail(t, NMPC_E_ARG, "h needs v");
-    float total = 0.0f;
-    for (int i = 0; i < t->host.n; ++i) total += t->host.mass[i];
-    if (!(total > 0.0f)) return fail(t, NMPC_E_ARG, "the tree has no mass: its centre of mass is undefined");
+    if (!(total_mass(t->host) > 0.0f)) return fail(t, NMPC_E_ARG, "the tree has no mass: its centre of mass is undefined");
     NMPC_ENTER(t, t->device);
     CrbaArgs p{};
     p.B = B; p.q = q; p.v = h ? v : nullptr; p.com = com; p.h = h; p.Ag = Ag;
     return launch_crba(t, p, stream);
+}
+
+int nmpc_centroidal_derivatives_batch(void* handle, int B, const float* q, const float* v, float* dh_dq, float* dcom_dq, float* hdot_bias,
+                                      void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0 || !q || !v || (!dh_dq && !dcom_dq && !hdot_bias))
+        return fail(t, NMPC_E_ARG, "need B >= 0, q, v and dh_dq, dcom_dq or hdot_bias");
+    const Model& m = t->host;
+    if (!(total_mass(m) > 0.0f)) return fail(t, NMPC_E_ARG, "the tree has no mass: its centre of mass is undefined");
+    NMPC_ENTER(t, t->device);
+    CmdArgs p{};
+    p.B = B; p.q = q; p.v = v; p.dh = dh_dq; p.dcom = dcom_dq; p.bias = hdot_bias;
+    while (!(m.mass[p.anchor] > 0.0f)) ++p.anchor;      // there is one: the total is positive
+    for (int k = p.anchor; k >= 0; k = m.parent[k]) p.chain |= 1u << k;
+    return launch_step(t, cmd_kernel, CD_W, cmd_lds_bytes(m.n, CD_W), p, stream);
 }
 
 int nmpc_foot_kinematics_batch(void* handle, int B, const float* q, const float* v, float* pos, float* vel, void* stream) {

@@ -170,6 +170,19 @@ class BatchedTorqueLayer:
                    self._h, "nmpc_centroidal_batch", "torque")
         return (com, h, Ag) if jacobian else (com, h)
 
+    def centroidal_derivatives(self, q, v, com_jacobian: bool = False, bias: bool = False):
+        """nmpc_centroidal_derivatives_batch: q, v [B, n] -> dh_dq [B, 6, n], the derivative of `centroidal`'s h = Ag(q) v with
+        respect to q at fixed v (rows in the slot order of h); with com_jacobian=True also dcom_dq [B, 3, n]; with bias=True also
+        hdot_bias [B, 6] = dh_dq v, the part of h_dot that is not Ag a.  A tensor alone, or a tuple in that order."""
+        q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
+        B = self._batch(q, v)
+        new = lambda *shape: torch.empty(B, *shape, dtype=torch.float32, device=self.device)      # noqa: E731
+        dh, dcom, hdot = new(6, self.n), (new(3, self.n) if com_jacobian else None), (new(6) if bias else None)
+        _lib.check(self.lib.nmpc_centroidal_derivatives_batch(self._h, B, ptr(q), ptr(v), ptr(dh), ptr(dcom), ptr(hdot), stream(self.device)),
+                   self._h, "nmpc_centroidal_derivatives_batch", "torque")
+        out = tuple(x for x in (dh, dcom, hdot) if x is not None)
+        return out[0] if len(out) == 1 else out
+
     def foot_kinematics(self, q, v=None):
         """nmpc_foot_kinematics_batch: q, v [B, n] (v None = at rest) -> world position and velocity of every foot point,
         (pos, vel), each [B, n_feet, 3]."""
