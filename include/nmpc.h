@@ -339,6 +339,30 @@ int nmpc_wb_rollout_set_plant(void *handle, void *torque_handle, const nmpc_cont
  * (nmpc_contact_set_push). */
 int nmpc_wb_rollout_set_plant_push(void *handle, int as_force);
 
+/* The momentum model of a NMPC_MODEL_WHOLEBODY handle [decl], per handle; NMPC_WB_MOMENTUM_DECLARED is the default and what
+ * every handle computed before this call existed.
+ *   declared     A_g(q) v = [m rdot ; R I_b E(theta) thetadot]: one rigid body of mass NMPC_MP_MASS and inertia NMPC_MP_I.. whose
+ *                centre of mass is the base origin (torque_handle is not read and may be NULL).
+ *   articulated  com(q) and A_g(q) of the tree of `torque_handle` (nmpc_torque_create, include/nmpc_torque.h; 18 joints in the
+ *                coordinates of model 2: three prismatic joints, yaw, pitch, roll, twelve leg joints, so that qdot = v), total
+ *                mass m_tree = sum m_i of the tree (not NMPC_MP_MASS):
+ *                  consist rows   h - A_g(q) v - yref, dense: d/dq = -d(A_g v)/dq (columns 3..17; 0..2 are zero), d/dv = -A_g, d/dh = I
+ *                  dynamics       h_lin+ = h_lin + dt (sum c_i f_i + m_tree g),  h_ang+ = h_ang + dt sum c_i (p_i(q) - com(q)) x f_i
+ *                The centre of mass is taken from the origin of the first frame of the tree that carries mass (the trunk), which
+ *                is where model 2 has its base position r = q[0..2]; the base position does not enter the arithmetic.  Foot
+ *                kinematics, the contact, swing and pos rows, the friction pyramids and the integrator of q, v stay as declared.
+ *                Every SQP iteration of a solve runs the momentum pass of the torque family on the nodes of the iterate, on the
+ *                solve's stream, in front of the linearisation.  The handle BORROWS the torque handle (as
+ *                nmpc_wb_rollout_set_plant): it must outlive the solves.  The first switch to this mode allocates two buffers
+ *                of B_max (N + 1) records (228 and 216 floats); solves allocate nothing.
+ * nmpc_solve_batch / nmpc_shift_solve_batch solve with the chosen model.  nmpc_wb_rollout_batch and nmpc_wb_label_states_batch
+ * build the momentum of x0 from the declared map: on a handle in the articulated mode they return NMPC_E_STATE and launch nothing.
+ * NMPC_E_ARG: a handle that is not NMPC_MODEL_WHOLEBODY, a model that is neither of the two, and for the articulated model a NULL
+ * torque handle, a tree that does not have 18 joints, a tree without mass, a torque handle on another device. */
+#define NMPC_WB_MOMENTUM_DECLARED    0
+#define NMPC_WB_MOMENTUM_ARTICULATED 1
+int nmpc_wb_set_momentum_model(void *handle, void *torque_handle, int model);
+
 /* DAgger relabelling: the expert's labels for states somebody else's rollout visited (nmpc_policy_rollout_batch with
  * nmpc_policy_rollout_set_states, include/nmpc_torque.h).  For every state (b, k) -- robot b < B, row k < n_rows -- the
  * expert's FIRST solve from that state (cold start, max_sqp iterations at nlp_tol) and the PD target it would apply from it:
@@ -394,6 +418,11 @@ int nmpc_debug_read_tile(void *handle, int b, int k, int which, float *out_host)
  * parts for horizon N: out8 = {records, Js images, Q~ images, K~ images, stage arrays, stride, NS, REC}. */
 int nmpc_debug_read_workspace(void *handle, int b, size_t offset, size_t count, float *out_host);
 int nmpc_debug_wb_layout(int N, size_t *out8);
+/* Test hook of the articulated momentum model: the records of node k <= N of problem b after a solve, each may be NULL --
+ * mrec_host float[228]: A_g [6][18], d(A_g v)/dq [6][18], A_g v [6], com from the base origin [3], padding;
+ * dcons_host float[216]: the sqrt(W)-scaled consistency rows, row i at 36 i: q_3..q_17 [15], v [18], h_i, residual, padding.
+ * NMPC_E_STATE on a handle that was never in the articulated mode.  Synchronises the device. */
+int nmpc_debug_read_momentum(void *handle, int b, int k, float *mrec_host, float *dcons_host);
 
 /* Diagnostic builds (-DNMPC_STAMPS) write cycle counts to dev float[B_max][16]: 8 phases
  * (linearise, IPM update+coefficients, backward, forward, last IPM update, step+write-back, -, -)

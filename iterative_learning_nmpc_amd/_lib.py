@@ -48,6 +48,7 @@ SIGNATURES = {
     "nmpc_wb_rollout_set_actions": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p]),
     "nmpc_wb_rollout_set_plant": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_wb_rollout_set_plant_push": (c_int, [c_void_p, c_int]),
+    "nmpc_wb_set_momentum_model": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_set_ipm": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float]),
     "nmpc_shift_warm_start": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "nmpc_solve_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -122,6 +123,7 @@ SIGNATURES = {
     "nmpc_debug_set_buffer": (c_int, [c_void_p, c_void_p]),
     "nmpc_debug_read_workspace": (c_int, [c_void_p, c_int, c_size_t, c_size_t, POINTER(c_float)]),
     "nmpc_debug_wb_layout": (c_int, [c_int, POINTER(c_size_t)]),
+    "nmpc_debug_read_momentum": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float)]),
 }
 
 

@@ -54,6 +54,11 @@ struct Handle {
         const int* zoh = nullptr;
         float *Aw = nullptr, *Qw = nullptr, *Vw = nullptr;
     } plant;
+    struct {                     // nmpc_wb_set_momentum_model: the articulated momentum model (torque == nullptr: the declared one)
+        void* torque = nullptr;  // borrowed: its tree is the model
+        float* mrec = nullptr;   // [B_max][N+1] momentum records (nmpc_wb_momentum.hpp), written by the momentum pass of every SQP iteration
+        float* dcons = nullptr;  // [B_max][N+1] dense consistency records, linearisation -> QP kernel
+    } momentum;
     bool plant_push_as_force = false;   // nmpc_wb_rollout_set_plant_push: a plant-mode rollout pushes with a force on the plant, not a velocity jump
     bool ws_dirty = false;   // a dense-LQ call left foreign padding in the tile workspace
     bool mp_set = false, w_set = false;
@@ -121,9 +126,11 @@ int clean_workspace(Handle* h, hipStream_t st) {
 
 // The SQP loop of both families.  One iteration = linearise (thread per stage) + QP/step (wave per problem); linearize is
 // absent where the QP kernel linearises itself.  Problems that finish early (converged, NaN, QP failure) set their workspace
-// flag and later launches skip them.
-template <class A>
-int launch_sqp(Handle* h, A a, hipStream_t st, size_t lds_bytes, void (*qp)(const A), void (*linearize)(const A)) {
+// flag and later launches skip them.  `before(a)` runs in front of every iteration's launches with that iteration's arguments and
+// returns a code (the momentum pass of the articulated whole-body model); `extra`: what the kernels take beside the argument block.
+template <class A, class Before, class... Extra>
+int launch_sqp(Handle* h, A a, hipStream_t st, size_t lds_bytes, void (*qp)(const A, const Extra...), void (*linearize)(const A, const Extra...),
+               Before before, const Extra&... extra) {
     if (lds_bytes > 64 * 1024)
         NMPC_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(qp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     const long long nthreads = (long long)a.B * (a.N + 1);
@@ -132,10 +139,15 @@ int launch_sqp(Handle* h, A a, hipStream_t st, size_t lds_bytes, void (*qp)(cons
     for (int it = 0; it < a.max_sqp; ++it) {
         a.it = it;
         a.shift = (it == 0) ? shift : 0;     // later iterations read their own iterate
-        if (linearize) hipLaunchKernelGGL(linearize, dim3(lin_blocks), dim3(64), 0, st, a);
-        hipLaunchKernelGGL(qp, dim3(a.B), dim3(64), lds_bytes, st, a);
+        if (const int rc = before(a)) return rc;
+        if (linearize) hipLaunchKernelGGL(linearize, dim3(lin_blocks), dim3(64), 0, st, a, extra...);
+        hipLaunchKernelGGL(qp, dim3(a.B), dim3(64), lds_bytes, st, a, extra...);
     }
     return launched(h);
+}
+template <class A>
+int launch_sqp(Handle* h, A a, hipStream_t st, size_t lds_bytes, void (*qp)(const A), void (*linearize)(const A)) {
+    return launch_sqp(h, a, st, lds_bytes, qp, linearize, [](const A&) { return (int)NMPC_OK; });
 }
 
 int launch_wb(Handle* h, nmpc::wb::WbArgs a, hipStream_t st) {
@@ -144,8 +156,27 @@ int launch_wb(Handle* h, nmpc::wb::WbArgs a, hipStream_t st) {
     auto misaligned = [](const void* p, unsigned m) { return (reinterpret_cast<uintptr_t>(p) & (m - 1u)) != 0; };
     if (misaligned(a.x0, 8) || misaligned(a.yref, 8) || misaligned(a.yref_e, 8) || misaligned(a.X, 8) || misaligned(a.U, 8) || misaligned(a.params, 16))
         return fail(h, NMPC_E_ARG, "whole-body arrays must be 8 B aligned (params: 16 B)");
-    return launch_sqp(h, a, st, (size_t)nmpc::wb::WbLds(a.N).total * sizeof(float), nmpc::wb::nmpc_wb_qp_kernel,
-                      nmpc::wb::nmpc_wb_linearize_kernel);
+    const size_t lds_bytes = (size_t)nmpc::wb::WbLds(a.N).total * sizeof(float);
+    if (!h->momentum.torque) return launch_sqp(h, a, st, lds_bytes, nmpc::wb::nmpc_wb_qp_kernel, nmpc::wb::nmpc_wb_linearize_kernel);
+    // the articulated momentum model: the momentum pass of the torque family in front of every linearisation (it reads the iterate
+    // through the same warm-start shift and leaves out the same finished problems) and the articulated compilation of both kernels
+    const auto& mm = h->momentum;
+    if (const char* why = nmpc_torque::momentum_refusal(mm.torque, h->device)) return fail(h, NMPC_E_STATE, std::string("momentum model: ") + why);
+    const nmpc::wb::WbArtArgs m{mm.mrec, mm.dcons, nmpc_torque::tree_mass(mm.torque)};
+    const nmpc::wb::WsLayout wl(a.N);
+    auto momentum_pass = [&](const nmpc::wb::WbArgs& w) {
+        const int* done = w.it > 0 ? reinterpret_cast<const int*>(w.ws + wl.flag) : nullptr;      // the finished flag of problem 0
+        const int rc = nmpc_torque::momentum_records(mm.torque, w.B, w.N, w.shift, w.X, w.skip, w.skip_mask, done, wl.stride, mm.mrec, st);
+        return rc ? fail(h, rc, std::string("momentum pass: ") + nmpc_torque_last_error(mm.torque)) : (int)NMPC_OK;
+    };
+    return launch_sqp(h, a, st, lds_bytes, nmpc::wb::nmpc_wb_qp_art_kernel, nmpc::wb::nmpc_wb_linearize_art_kernel, momentum_pass, m);
+}
+
+// the entry points that build x0's momentum from the declared map refuse a handle in the articulated mode
+int check_declared_momentum(Handle* h, const char* who) {
+    return h->momentum.torque ? fail(h, NMPC_E_STATE, std::string(who) + " builds the momentum of x0 from the declared map: not available "
+                                                      "with the articulated momentum model (nmpc_wb_set_momentum_model)")
+                              : NMPC_OK;
 }
 
 // Two variants of the QP kernel (nmpc_solve.hip, Lds).  Resident: stage arrays in the LDS (39.6 KB at N = 50: four waves per CU),
@@ -343,6 +374,8 @@ void nmpc_destroy(void* handle) {
     if (h->ws) (void)hipFree(h->ws);
     if (h->roll) (void)hipFree(h->roll);
     if (h->label_skip) (void)hipFree(h->label_skip);
+    if (h->momentum.mrec) (void)hipFree(h->momentum.mrec);
+    if (h->momentum.dcons) (void)hipFree(h->momentum.dcons);
     delete h;
 }
 
@@ -437,6 +470,25 @@ int nmpc_wb_rollout_set_plant(void* handle, void* torque_handle, const nmpc_cont
         p.torque = torque_handle; p.n_sub = n_sub; p.kp = kp; p.kd = kd; p.zoh = zoh; p.Aw = Aw; p.Qw = Qw; p.Vw = Vw;
         if (ground) { p.ground = *ground; p.ground_set = true; }
     }
+    return NMPC_OK;
+}
+
+int nmpc_wb_set_momentum_model(void* handle, void* torque_handle, int model) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_wb_set_momentum_model needs the whole-body model");
+    if (model != NMPC_WB_MOMENTUM_DECLARED && model != NMPC_WB_MOMENTUM_ARTICULATED)
+        return fail(h, NMPC_E_ARG, "model is NMPC_WB_MOMENTUM_DECLARED or NMPC_WB_MOMENTUM_ARTICULATED");
+    if (model == NMPC_WB_MOMENTUM_DECLARED) {      // the buffers of the articulated mode stay with the handle for the next switch
+        h->momentum.torque = nullptr;
+        return NMPC_OK;
+    }
+    if (const char* why = nmpc_torque::momentum_refusal(torque_handle, h->device)) return fail(h, NMPC_E_ARG, std::string("momentum model: ") + why);
+    NMPC_ENTER(h, h->device);
+    const size_t nodes = (size_t)h->dims.B_max * (h->dims.N + 1);
+    if (!h->momentum.mrec) NMPC_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->momentum.mrec), nodes * nmpc::wb::MR_FLOATS * sizeof(float)));
+    if (!h->momentum.dcons) NMPC_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->momentum.dcons), nodes * nmpc::wb::DC_FLOATS * sizeof(float)));
+    h->momentum.torque = torque_handle;
     return NMPC_OK;
 }
 
@@ -603,6 +655,7 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
     if (!cfg || !gait || !peaks || !nodes || !q || !v || !v_des || !w_des || !ref_state || !joint_ref || !X || !U || !S || !status || !failed)
         return fail(h, NMPC_E_ARG, "null argument");
     if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_wb_rollout_batch needs the whole-body model");
+    if (const int rc = check_declared_momentum(h, "nmpc_wb_rollout_batch")) return rc;
     if (const int rc = check_batch(h, B)) return rc;
     if (cfg->n_replans < 1 || cfg->replanning_steps < 1 || cfg->nodes_per_cycle < 1 || !(cfg->sim_dt > 0) || !(cfg->time_horizon > 0))
         return fail(h, NMPC_E_ARG, "rollout configuration out of range");
@@ -724,6 +777,7 @@ int nmpc_wb_label_states_batch(void* handle, void* torque_handle, int B, const n
         !X || !U)
         return fail(h, NMPC_E_ARG, "null argument");
     if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_wb_label_states_batch needs the whole-body model");
+    if (const int rc = check_declared_momentum(h, "nmpc_wb_label_states_batch")) return rc;
     if (h->line_search) return fail(h, NMPC_E_ARG, "the whole-body model takes full steps (line_search = 0)");
     if (const int rc = check_configured(h)) return rc;
     if (const char* why = nmpc_torque::label_states_refusal(torque_handle, cfg->n_rows, qv_rows, a_rows, zoh, cfg->kp, h->device))
@@ -809,6 +863,21 @@ int nmpc_debug_read_workspace(void* handle, int b, size_t offset, size_t count, 
     NMPC_ENTER(h, h->device);
     NMPC_TRY(h, hipDeviceSynchronize());
     NMPC_TRY(h, hipMemcpy(out_host, h->ws + (size_t)b * h->ws_stride + offset, count * sizeof(float), hipMemcpyDeviceToHost));
+    return NMPC_OK;
+}
+
+int nmpc_debug_read_momentum(void* handle, int b, int k, float* mrec_host, float* dcons_host) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    if (!h->momentum.mrec || !h->momentum.dcons) return fail(h, NMPC_E_STATE, "the handle has never been in the articulated momentum mode");
+    if (b < 0 || b >= h->dims.B_max || k < 0 || k > h->dims.N) return fail(h, NMPC_E_ARG, "index out of range");
+    NMPC_ENTER(h, h->device);
+    NMPC_TRY(h, hipDeviceSynchronize());
+    const size_t node = (size_t)b * (h->dims.N + 1) + k;
+    if (mrec_host)
+        NMPC_TRY(h, hipMemcpy(mrec_host, h->momentum.mrec + node * nmpc::wb::MR_FLOATS, nmpc::wb::MR_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+    if (dcons_host)
+        NMPC_TRY(h, hipMemcpy(dcons_host, h->momentum.dcons + node * nmpc::wb::DC_FLOATS, nmpc::wb::DC_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
     return NMPC_OK;
 }
 

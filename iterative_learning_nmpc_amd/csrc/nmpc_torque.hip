@@ -35,6 +35,7 @@
 #include "nmpc_rollout_common.hpp"
 #include "nmpc_torque_plan.hpp"
 #include "nmpc_wb_plan.hpp"
+#include "nmpc_wb_momentum.hpp"
 
 namespace nmpc_torque {
 
@@ -356,6 +357,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_crba.hip.inc"
 #include "nmpc_torque_implicit.hip.inc"
 #include "nmpc_torque_cmd.hip.inc"
+#include "nmpc_torque_momentum.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -448,6 +450,9 @@ int allocate(Torque* t) {
     // the momentum derivatives: the slice of the largest tree at its one width
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(cmd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)cmd_lds_bytes(MAXJ, CD_W)));
+    // the momentum pass of the whole-body solve: the same slice
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(wb_momentum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)cmd_lds_bytes(MAXJ, MM_W)));
     return NMPC_OK;
 }
 
@@ -678,6 +683,34 @@ const char* nmpc_torque::label_states_refusal(void* handle, int n_rows, int qv_r
     if (qv_rows < n_rows) return "qv_rows must be at least n_rows";
     if (a_rows < n_rows) return "a_rows must be at least n_rows";
     return plan_actions_refusal(handle, 1, zoh, kp, device);
+}
+
+const char* nmpc_torque::momentum_refusal(void* handle, int device) {
+    const Torque* t = static_cast<const Torque*>(handle);
+    if (!t) return "null torque handle";
+    if (t->host.n != 18) return "the articulated momentum model needs a tree in the coordinates of the whole-body model: n_joints = 18";
+    if (!(total_mass(t->host) > 0.0f)) return "the tree has no mass: its centre of mass is undefined";
+    if (device >= 0 && t->device != device) return "the torque handle lives on another device";
+    return nullptr;
+}
+
+float nmpc_torque::tree_mass(void* handle) { return total_mass(static_cast<const Torque*>(handle)->host); }
+
+int nmpc_torque::momentum_records(void* handle, int B, int N, int shift, const float* X, const int* skip, int skip_mask, const int* done,
+                                  size_t done_stride, float* rec, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (const char* why = momentum_refusal(handle, -1)) return fail(t, NMPC_E_ARG, why);
+    const Model& m = t->host;
+    MomentumArgs p{};
+    p.B = B; p.N = N; p.shift = shift; p.X = X; p.rec = rec; p.skip = skip_mask ? skip : nullptr; p.skip_mask = skip_mask;
+    p.done = done; p.done_stride = done_stride;
+    while (!(m.mass[p.anchor] > 0.0f)) ++p.anchor;      // there is one: the total is positive
+    for (int k = p.anchor; k >= 0; k = m.parent[k]) p.chain |= 1u << k;
+    const long long threads = (long long)B * (N + 1);
+    hipLaunchKernelGGL(wb_momentum_kernel, dim3((unsigned)((threads + MM_W - 1) / MM_W)), dim3(MM_W), cmd_lds_bytes(m.n, MM_W),
+                       static_cast<hipStream_t>(stream), t->dev, p);
+    return launched(t);
 }
 
 const char* nmpc_torque::contact_track_refusal(void* handle, const nmpc_contact_cfg* ground, int n_sub, float dt, int device) {

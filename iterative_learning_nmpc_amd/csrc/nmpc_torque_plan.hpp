@@ -29,4 +29,18 @@ int contact_track_pushed(void* handle, int B, int n_steps, int n_sub, float dt, 
                          const float* tau_ff, const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows,
                          const int* skip, int skip_mask, const nmpc_push_cfg& push, void* stream);
 
+// nullptr if the handle's tree can serve the articulated momentum model of a whole-body solver on `device` (-1: any device): 18
+// joints -- the coordinates of model 2 -- and some mass; otherwise the text nmpc_last_error gives
+const char* momentum_refusal(void* handle, int device);
+
+// total mass of the handle's tree (a handle momentum_refusal accepts)
+float tree_mass(void* handle);
+
+// the momentum pass of one SQP iteration (nmpc_torque_momentum.hip.inc): the momentum records (nmpc_wb_momentum.hpp) of the B (N + 1)
+// nodes of the iterate X [B][N+1][42], read through the warm-start shift, into rec; launched on the caller's current device.
+// Left out, as the linearisation leaves them out: problems with skip[b] & skip_mask != 0, and, with `done` given (dev: the
+// finished flag of problem 0, that of problem b `done_stride` words further on), problems whose flag is set
+int momentum_records(void* handle, int B, int N, int shift, const float* X, const int* skip, int skip_mask, const int* done,
+                     size_t done_stride, float* rec, void* stream);
+
 }  // namespace nmpc_torque

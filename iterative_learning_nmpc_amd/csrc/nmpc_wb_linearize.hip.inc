@@ -10,7 +10,16 @@ namespace wb {
 #ifndef WB_LIN_WAVES
 #define WB_LIN_WAVES 1
 #endif
+// The file is compiled once per momentum model (nmpc_wb.hip includes it twice): WB_ART = 0 is the declared model and gives
+// nmpc_wb_linearize_kernel, whose text is what it was before the second model existed; WB_ART = 1 is the articulated model
+// (nmpc_wb_momentum.hpp; DESIGN.md 3.2) and gives nmpc_wb_linearize_art_kernel -- the consistency rows and the momentum rows of
+// the dynamics take the tree's centroidal quantities from the node's momentum record `m.mrec`, and the consistency rows go,
+// dense, into `m.dcons`.
+#if WB_ART
+__global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_art_kernel(const WbArgs a, const WbArtArgs m) {
+#else
 __global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_kernel(const WbArgs a) {
+#endif
     const int N = a.N;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)a.B * (N + 1)) return;
@@ -30,6 +39,11 @@ __global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_kernel(con
     // the C-ABI (nmpc_api.hip, launch_wb).
     float* rec = static_cast<float*>(__builtin_assume_aligned(ws + wl.rec + (size_t)k * REC, 16));
     float* js = ws + wl.js + (size_t)k * CJ_FLOATS;
+#if WB_ART
+    // the node's momentum record (read where it is used): the tree's mass and centre of mass in place of the declared body's
+    const float* mr = static_cast<const float*>(__builtin_assume_aligned(m.mrec + (size_t)t * MR_FLOATS, 16));
+    const float com[3] = {mr[MR_COM], mr[MR_COM + 1], mr[MR_COM + 2]};
+#endif
 
     float x[NX], u[NU], p[NP];
     const float* xk = static_cast<const float*>(__builtin_assume_aligned(Xg + (size_t)shifted_node(k, a.shift, N) * NX, 8));
@@ -182,7 +196,12 @@ __global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_kernel(con
         if (!term) {   // momentum rows of the dynamics
             const float ff[3] = {u[WF + 3 * f], u[WF + 3 * f + 1], u[WF + 3 * f + 2]};
             float tq[3];
+#if WB_ART
+            const float arm[3] = {Rb[0] - com[0], Rb[1] - com[1], Rb[2] - com[2]};      // p_f - com
+            cross(arm, ff, tq);
+#else
             cross(Rb, ff, tq);
+#endif
 #pragma unroll
             for (int i = 0; i < 3; ++i) { F[i] += cf * ff[i]; tau_acc[i] += cf * tq[i]; }
             // d(arm x f)/d xi_c, c = 3..8 (arm = R b does not depend on r)
@@ -194,7 +213,11 @@ __global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_kernel(con
 #pragma unroll
                 for (int i = 0; i < 3; ++i) hq[i][xi_col(f, c) - 3] += dt * cf * tc[i];
             }
+#if WB_ART
+            const float ax[9] = {0.f, -arm[2], arm[1], arm[2], 0.f, -arm[0], -arm[1], arm[0], 0.f};
+#else
             const float ax[9] = {0.f, -Rb[2], Rb[1], Rb[2], 0.f, -Rb[0], -Rb[1], Rb[0], 0.f};
+#endif
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -202,6 +225,37 @@ __global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_kernel(con
             cdt[f] = dt * cf;
         }
     }
+#if WB_ART
+    {
+        // ---- consistency rows  h - A_g(q) v  of the tree: dense over q_3..q_17 (-dh_dq) and v (-A_g), into the node's dense record
+        float* dc = static_cast<float*>(__builtin_assume_aligned(m.dcons + (size_t)t * DC_FLOATS, 16));
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const float w = Wv[r_cs + i], sw = sqrtf(w);
+            const float res = x[WH + i] - mr[MR_AGV + i] - yr[r_cs + i];
+            cost += 0.5f * w * res * res;
+            float row[DC_ROW];
+#pragma unroll
+            for (int j = 0; j < 15; ++j) row[j] = -sw * mr[MR_DH + 18 * i + 3 + j];
+#pragma unroll
+            for (int j = 0; j < 18; ++j) row[DC_V + j] = -sw * mr[MR_AG + 18 * i + j];
+            row[DC_H] = sw; row[DC_RES] = sw * res; row[35] = 0.0f;
+#pragma unroll
+            for (int j = 0; j < DC_ROW; j += 4) *reinterpret_cast<f32x4*>(dc + DC_ROW * i + j) = f32x4{row[j], row[j + 1], row[j + 2], row[j + 3]};
+        }
+        // d h_ang+ / d q_j gains  -dt (d com / d q_j) x sum c_f f_f,  d com / d q_j = A_g[lin][j] / m
+        if (!term) {
+#pragma unroll
+            for (int j = 0; j < 15; ++j) {
+                const float dcq[3] = {mr[MR_AG + 3 + j] / m.m_tree, mr[MR_AG + 18 + 3 + j] / m.m_tree, mr[MR_AG + 36 + 3 + j] / m.m_tree};
+                float tc[3];
+                cross(dcq, F, tc);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) hq[i][j] -= dt * tc[i];
+            }
+        }
+    }
+#else
     // ---- consistency rows  h - A_g(q) v,  A_g v = [m rdot ; R I_b E(theta) thetadot]
     {
         float cb[36];      // the consistency part of the compact Jacobian record
@@ -253,6 +307,7 @@ __global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_kernel(con
         }
         put_cj(CJ_CONS, 36, cb);
     }
+#endif
     // ---- diagonal residuals (base, joint) on x[0..35]: gradient and cost
     {
         float gq[36];
@@ -297,7 +352,11 @@ __global__ __launch_bounds__(64, WB_LIN_WAVES) void nmpc_wb_linearize_kernel(con
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
+#if WB_ART
+            dd[pos_of(WH + i)] = x[WH + i] + dt * (F[i] + (i == 2 ? m.m_tree * mp.gz : 0.0f)) - xn[WH + i];
+#else
             dd[pos_of(WH + i)] = x[WH + i] + dt * (F[i] + (i == 2 ? mp.mass * mp.gz : 0.0f)) - xn[WH + i];
+#endif
             dd[pos_of(WH + 3 + i)] = x[WH + 3 + i] + dt * tau_acc[i] - xn[WH + 3 + i];
         }
         put_rec(R_D, dd);

@@ -37,7 +37,11 @@ class LocomotionMPC:
                  joint_ref: Optional[np.ndarray] = None, interactive_goal: bool = False, sim_dt: float = 1.0e-3,
                  height_offset: float = 0., contact_planner: str = "", print_info: bool = True,
                  compute_timings: bool = True, solve_async: bool = False, batch: int = 1, device="cuda:0",
-                 n_nodes: Optional[int] = None, force_reference: str = "zero"):
+                 n_nodes: Optional[int] = None, force_reference: str = "zero", momentum_model: str = "declared",
+                 torque_layer=None):
+        """momentum_model, torque_layer: as `QuadrupedAcadosSolver` -- "articulated" solves with the centroidal momentum of the
+        tree of `torque_layer` and takes x0's `h` from it; `optimize` and `open_loop` work in that mode, `open_loop_device` and
+        `label_states` (whose kernels build x0 from the declared map) raise."""
         self.batch = int(batch)
         self.config_gait, self.config_opt, self.config_cost = get_quadruped_config(gait_name, robot_name)
         if n_nodes is not None:                      # BASELINE configs[2] asks for N = 30; the reference runs 25
@@ -46,7 +50,9 @@ class LocomotionMPC:
         self.height_offset = height_offset
         self.solver = QuadrupedAcadosSolver(path_urdf, list(feet_frame_names), self.config_opt, self.config_cost,
                                             height_offset, print_info, compute_timings, batch=batch, device=device,
-                                            force_reference=force_reference)
+                                            force_reference=force_reference, momentum_model=momentum_model,
+                                            torque_layer=torque_layer)
+        self.momentum_model = self.solver.momentum_model
         self.nq, self.nv, self.nu, self.n_foot = 18, 18, wb.N_JOINTS, 4
         self.joint_ref = np.asarray(joint_ref, float) if joint_ref is not None else wb.Q_HOME.copy()   # mpc.py:73-81
         self._contact_planner_str = contact_planner
@@ -246,6 +252,7 @@ class LocomotionMPC:
             integrator_mode(integrator)                   # an unknown name is refused before anything runs
             if plant is None:
                 raise ValueError("integrator: the integrator is the contact plant's, give plant")
+        self._declared_momentum_only("open_loop_device")
         fs = self.solver
         s = fs._device_solver()
         B, N, dev = self.batch, self.config_opt.n_nodes, s.device
@@ -343,6 +350,7 @@ class LocomotionMPC:
         -> (A [B, K, 12], status int32 [B, K]) on the device.  Not a replan of the controller: its counters, reference, views
         and `_X_dev` / `_U_dev` are as they were."""
         import torch
+        self._declared_momentum_only("label_states")
         fs = self.solver
         s = fs._device_solver()
         if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] != self.batch:
@@ -360,6 +368,11 @@ class LocomotionMPC:
             step_height=float(self.config_gait.step_height), force_reference_gravity=int(fs.force_reference == "gravity_share"),
             kp=float(self.Kp if kp is None else kp), kd=float(self.Kd if kd is None else kd), terminate_mask=int(TERMINATE_DEFAULT))
         return A, status
+
+    def _declared_momentum_only(self, who: str) -> None:
+        if self.momentum_model != "declared":
+            raise RuntimeError(f"{who}: the device builds the momentum of x0 from the declared map; with momentum_model="
+                               f"\"{self.momentum_model}\" use optimize / open_loop")
 
     def _step(self) -> None:                                                                # mpc.py:183-186
         self.increment_base_ref_position()

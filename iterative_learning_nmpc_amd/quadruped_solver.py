@@ -66,8 +66,9 @@ class QuadrupedDynamics:
     """host side of `mpc_controller/utils/dynamics.py:10-106` for the declared model: names of the symbolic
     quantities and the kinematics the controller asks for between solves"""
 
-    def __init__(self, feet_frame_names: List[str], mass: float, inertia, name: str = "go2"):
+    def __init__(self, feet_frame_names: List[str], mass: float, inertia, name: str = "go2", torque_layer=None):
         self.name = name
+        self.torque_layer = torque_layer      # articulated momentum model: `hg` is the momentum of this layer's tree
         self.q, self.v, self.h, self.a = _Named("q"), _Named("v"), _Named("h"), _Named("a")
         self.base_cost, self.joint_cost = _Named("base_cost"), _Named("joint_cost")       # dynamics.py:35-38
         self.acc_cost, self.swing_cost = _Named("acc_cost"), _Named("sw_cost")
@@ -87,6 +88,9 @@ class QuadrupedDynamics:
 
     @property
     def hg(self) -> np.ndarray:                                                             # pin_data.hg, solver.py:187
+        if self.torque_layer is not None:     # the articulated tree's momentum, from the device (BatchedTorqueLayer.centroidal)
+            h = self.torque_layer.centroidal(np.atleast_2d(self._q), np.atleast_2d(self._v))[1].cpu().numpy().astype(float)
+            return h[0] if self._q.ndim == 1 else h
         if self._q.ndim == 1:
             return wb.centroidal_momentum(self._q, self._v, self.mass, self.inertia)
         return np.stack([wb.centroidal_momentum(q, v, self.mass, self.inertia) for q, v in zip(self._q, self._v)])
@@ -98,7 +102,17 @@ class QuadrupedAcadosSolver:
     def __init__(self, path_urdf: str, feet_frame_names: List[str], config_opt, config_cost,
                  height_offset: float = 0., print_info: bool = False, compute_timings: bool = True,
                  batch: int = 1, device="cuda:0", force_reference: str = "zero",
-                 w_contact: float = W_CONTACT, w_consistency: float = W_CONSISTENCY, strict: bool = False):
+                 w_contact: float = W_CONTACT, w_consistency: float = W_CONSISTENCY, strict: bool = False,
+                 momentum_model: str = "declared", torque_layer=None):
+        """momentum_model: "declared" (the single rigid body of DESIGN.md 3.2, the default) or "articulated" -- the centroidal
+        momentum of the tree of `torque_layer` (a `BatchedTorqueLayer` of 18 joints in the model's coordinates) in the solve
+        (`BatchedNmpcSolver.set_momentum_model`) and in the `h` of x0 (`torque_layer.centroidal`)."""
+        if momentum_model not in ("declared", "articulated"):
+            raise ValueError(f"momentum_model: \"declared\" or \"articulated\", got {momentum_model!r}")
+        if momentum_model == "articulated" and torque_layer is None:
+            raise ValueError("momentum_model=\"articulated\" needs torque_layer")
+        self.momentum_model = momentum_model
+        self.torque_layer = torque_layer if momentum_model == "articulated" else None
         self.feet_frame_names = list(feet_frame_names)
         assert len(self.feet_frame_names) == 4, "the declared model is a quadruped"
         self.config_opt, self.config_cost = config_opt, config_cost
@@ -119,7 +133,7 @@ class QuadrupedAcadosSolver:
         self.mp = model_params(dt=self.dt_nodes, mu=0.8,                                    # mu: solver.py:38
                                p_gain=float(np.asarray(self.config_cost.W_foot_pos_constr_stab)[0]))
         assert np.all(np.asarray(self.config_cost.W_foot_pos_constr_stab) == self.mp[8]), "one Baumgarte gain for all feet"
-        self.dyn = QuadrupedDynamics(self.feet_frame_names, self.mp[1], self.mp[2:5])
+        self.dyn = QuadrupedDynamics(self.feet_frame_names, self.mp[1], self.mp[2:5], torque_layer=self.torque_layer)
         self.default_normal = np.array([0., 0., 1.])
         self.compute_timings = compute_timings
         self.timings = defaultdict(list)
@@ -414,6 +428,7 @@ class QuadrupedAcadosSolver:
             self._dev = BatchedNmpcSolver(MODEL_WHOLEBODY, self.config_opt.n_nodes, self.batch, self.device)
             self._dev.set_model_params(self.mp)
             self._dev.set_cost_weights(self._W, self._W_e, self.config_cost.reg_eps, self.config_cost.reg_eps_e)
+            self._dev.set_momentum_model(self.momentum_model, torque_layer=self.torque_layer)
             self._push_opts()
         return self._dev
 

@@ -52,6 +52,7 @@ class BatchedNmpcSolver:
         self._h = ctypes.c_void_p()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _lib.check(self.lib.nmpc_create(ctypes.byref(dims), dev_index, ctypes.byref(self._h)), None, "nmpc_create")
+        self.momentum_model, self._momentum_layer = "declared", None      # set_momentum_model
         self._opts = dict(max_iter=1, max_qp_iter=6, nlp_tol=0.0, qp_tol=1e-2, line_search=0)
         self._push_opts()
 
@@ -166,6 +167,25 @@ class BatchedNmpcSolver:
         itself) over the substeps of sim_dt / n_sub the window covers; a rollout without a plant is then refused, as is one
         whose torque layer has a push of the caller's attached."""
         _lib.check(self.lib.nmpc_wb_rollout_set_plant_push(self._h, int(bool(as_force))), self._h, "nmpc_wb_rollout_set_plant_push")
+
+    MOMENTUM_MODELS = {"declared": 0, "articulated": 1}      # NMPC_WB_MOMENTUM_* of include/nmpc.h
+
+    def set_momentum_model(self, model: str = "declared", torque_layer=None):
+        """nmpc_wb_set_momentum_model: the momentum map of the whole-body model.  "declared" (the default): one rigid body of
+        the model parameters' mass and inertia at the base origin.  "articulated": com(q) and A_g(q) of the tree of
+        `torque_layer` (a `BatchedTorqueLayer` of 18 joints in the coordinates of the model) in the consistency rows and the
+        momentum rows of the dynamics; the layer is borrowed and kept alive by this object while the mode is on.  `solve` works
+        in both modes; `wb_rollout` and `label_states` build x0's momentum from the declared map and are refused in the
+        articulated mode."""
+        if model not in self.MOMENTUM_MODELS:
+            raise ValueError(f"momentum model: one of {sorted(self.MOMENTUM_MODELS)}, got {model!r}")
+        if model == "articulated" and torque_layer is None:
+            raise ValueError("the articulated momentum model needs torque_layer")
+        layer = torque_layer if model == "articulated" else None
+        _lib.check(self.lib.nmpc_wb_set_momentum_model(self._h, layer._h if layer is not None else None, self.MOMENTUM_MODELS[model]),
+                   self._h, "nmpc_wb_set_momentum_model")
+        self._momentum_layer = layer
+        self.momentum_model = model
 
     def set_ipm(self, mu0=10.0, sigma=0.2, s_min=1.0, gamma=0.995, tau_min=0.1, merit_rho=1e3):
         _lib.check(self.lib.nmpc_set_ipm(self._h, mu0, sigma, s_min, gamma, tau_min, merit_rho),
@@ -384,6 +404,14 @@ class BatchedNmpcSolver:
         out = (ctypes.c_size_t * 8)()
         _lib.check(self.lib.nmpc_debug_wb_layout(self.n_nodes, out), self._h, "nmpc_debug_wb_layout")
         return dict(zip(("rec", "js", "qt", "kt", "arr", "stride", "NS", "REC"), (int(v) for v in out)))
+
+    def debug_momentum(self, b: int, k: int):
+        """(momentum record [228], dense consistency record [216]) of node k of problem b (test hook of the articulated mode)"""
+        fp = ctypes.POINTER(ctypes.c_float)
+        mrec, dcons = np.zeros(228, dtype=np.float32), np.zeros(216, dtype=np.float32)
+        _lib.check(self.lib.nmpc_debug_read_momentum(self._h, b, k, mrec.ctypes.data_as(fp), dcons.ctypes.data_as(fp)),
+                   self._h, "nmpc_debug_read_momentum")
+        return mrec, dcons
 
     @property
     def workspace_bytes(self) -> int:

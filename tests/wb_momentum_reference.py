@@ -1,0 +1,176 @@
+"""Reference of the whole-body model's two momentum models (nmpc_wb_set_momentum_model) -- TEST INFRASTRUCTURE ONLY (helper
+module, not collected by pytest), in numpy float64 with a float32-data variant.
+
+What is whose.  Everything the two models share -- foot kinematics, the contact / swing / pos rows, the integrator, the declared
+momentum rows -- is taken from the frozen oracle's per-node hooks (`Oracle.wb_residuals`, `Oracle.dynamics`: the functions its
+own solve is built from), which this module cannot extend.  What the articulated model changes is stated here in numpy, on
+tests/crba_reference.py and tests/centroidal_derivative_reference.py:
+
+    consist rows     h - A_g(q) v - yref,   d/dq = -dh_dq (columns 0..2 zero),  d/dv = -A_g,  d/dh = I
+    dynamics         h_lin+ = h_lin + dt (sum c_i f_i + m_tree g),   h_ang+ = h_ang + dt sum c_i (p_i(q) - com(q)) x f_i
+                     d h_ang+ / d q_j (j = 3..17) gains -dt d com / d q_j x sum c_i f_i,   d h_ang+ / d f_i = dt c_i [p_i - com]x
+
+com(q) is the tree's centre of mass from the origin of its first frame that carries mass, attached at model 2's base position
+r = q[0..2]: on `workloads.quadruped_tree()` the world centre of mass itself.
+
+  node(...)       (a) the per-node quantities: dynamics defect, A, B, the sqrt(W)-scaled Jacobian Js and residual
+  gn_step(...)    (b) one full Gauss-Newton step without inequalities: the dense KKT solve of
+                      min sum 1/2 |Js [dx; 1]|^2 + 1/2 reg |dx|^2 + input terms   s.t.  dx+ = A dx + B du + d,  dx_0 = x0 - X_0,
+                  then X + dx, U + du: what a solve with max_sqp_iter = 1, max_qp_iter = 0, line_search = 0 computes.
+`data` chooses the number format of the per-node data: "f64" (fp64 oracle hooks, float64 recursions) or "f32" (the fp32
+oracle's hooks and the recursions in float32 on float32 inputs: what the device's format costs); the KKT solve is float64
+either way.
+"""
+import numpy as np
+
+from oracle import torque_oracle as to
+from oracle.oracle import Oracle
+from tests import centroidal_derivative_reference as cdr
+from tests import crba_reference as cr
+
+NX, NU, WQ, WV, WH, WA, WF = 42, 30, 0, 18, 36, 0, 18
+RY_ACC, RY_FREG, RY_CONS, RE_CONS = 36, 52, 76, 52
+_ORACLES = {}
+
+
+def oracle(data):
+    if data not in _ORACLES:
+        _ORACLES[data] = Oracle(data)
+    return _ORACLES[data]
+
+
+def tree_model(tree):
+    return to.TreeModel.from_arrays(tree)
+
+
+def single_body_tree(mass=15.0, inertia=(0.11, 0.27, 0.33)):
+    """model 2's declared body as a tree: three prismatic joints, yaw, pitch, roll, one body of `mass` and principal inertia
+    `inertia` at the base origin, and twelve massless leg joints so that the coordinates are model 2's"""
+    from iterative_learning_nmpc_amd.workloads import quadruped_tree
+    t = {k: np.array(v, copy=True) for k, v in quadruped_tree().items()}
+    t["mass"] = np.zeros(18); t["mass"][5] = mass
+    t["com"] = np.zeros((18, 3))
+    t["inertia"] = np.zeros((18, 6)); t["inertia"][5] = (inertia[0], 0, 0, inertia[1], 0, inertia[2])
+    return t
+
+
+def centroidal(m, q, v, data="f64"):
+    """(com from the base origin [3], A_g [6, 18], dh_dq [6, 18], A_g v [6]) of tree m, float64 arrays of `data` precision"""
+    dt = np.float64 if data == "f64" else np.float32
+    q, v = np.asarray(q, dt), np.asarray(v, dt)
+    _, com, h, Ag = cr.crba(m, q, v, dt)
+    dh, _, _ = cdr.centroidal_derivatives_ref(m, q, v, dt)
+    O = m.forward_kinematics(np.asarray(q, np.float64))[1][cdr.anchor(m)]
+    com_rel = (com.astype(np.float64) - O).astype(dt)
+    return tuple(np.asarray(a, np.float64) for a in (com_rel, Ag, dh, h))
+
+
+def node(mp, x, u, p, yref, W, momentum="declared", m=None, data="f64"):
+    """Per-node quantities at (x, u, p); u = None: the terminal node.  dict with res, J [ny, 42] (unscaled, reference subtracted),
+    Js = sqrt(W) [J | res] [ny, 43], and for a stage xn, A [42, 42], B [42, 30]."""
+    o = oracle(data)
+    dt_ = np.float64 if data == "f64" else np.float32
+    x = np.asarray(x, dt_).astype(np.float64); p = np.asarray(p, np.float64)
+    term = u is None
+    res, J = o.wb_residuals(mp, x, u, p, yref)
+    res, J = res.astype(np.float64), J.astype(np.float64)
+    out = {}
+    if not term:
+        u = np.asarray(u, dt_).astype(np.float64)
+        xn, A, B = (a.astype(np.float64) for a in o.dynamics(2, mp, x, u, p))
+    if momentum == "articulated":
+        q, v = x[WQ:WQ + 18], x[WV:WV + 18]
+        com, Ag, dh, agv = centroidal(m, q, v, data)
+        r_cs = RE_CONS if term else RY_CONS
+        yr = np.asarray(yref, np.float64)
+        J[r_cs:r_cs + 6] = 0.0
+        res[r_cs:r_cs + 6] = x[WH:WH + 6] - agv - yr[r_cs:r_cs + 6]
+        J[r_cs:r_cs + 6, WQ + 3:WQ + 18] = -dh[:, 3:]
+        J[r_cs:r_cs + 6, WV:WV + 18] = -Ag
+        J[r_cs:r_cs + 6, WH:WH + 6] = np.eye(6)
+        if not term:
+            dt, gz, m_tree = float(mp[0]), float(mp[5]), float(np.asarray(m.mass, dt_).sum(dtype=dt_))
+            c = p[:4]
+            f = u[WF:].reshape(4, 3)
+            F = (c[:, None] * f).sum(0)
+            xn[WH + 2] += dt * (m_tree - float(mp[1])) * gz
+            xn[WH + 3:WH + 6] -= dt * np.cross(com, F)
+            S = to._skew(com)
+            for i in range(4):
+                B[WH + 3:WH + 6, WF + 3 * i:WF + 3 * i + 3] -= dt * c[i] * S
+            dcom = Ag[:3] / m_tree
+            for j in range(3, 18):
+                A[WH + 3:WH + 6, WQ + j] -= dt * np.cross(dcom[:, j], F)
+    sw = np.sqrt(np.asarray(W, np.float64))
+    out.update(res=res, J=J, Js=sw[:, None] * np.concatenate([J, res[:, None]], axis=1))
+    if not term:
+        out.update(xn=xn, A=A, B=B)
+    return out
+
+
+def residual_and_next(mp, x, u, p, yref, momentum, m):
+    """(consistency residual [6], h+ [6]) as plain functions of the state: what (a) is differenced against"""
+    n = node(mp, x, u, p, yref, np.ones(len(yref)), momentum, m)
+    r_cs = RE_CONS if u is None else RY_CONS
+    return n["res"][r_cs:r_cs + 6], (None if u is None else n["xn"][WH:WH + 6])
+
+
+def gn_step(w, momentum="declared", m=None, data="f64", b=None):
+    """(X, U) [B, N+1, 42], [B, N, 30] after one full Gauss-Newton step of workload `w` without inequalities (problems `b`)"""
+    reg, reg_e = w.meta.get("reg", 1e-6), w.meta.get("reg_e", 1e-5)
+    N = w.N
+    nz = (N + 1) * NX + N * NU
+    Xs, Us = [], []
+    for bb in (range(w.B) if b is None else b):
+        H, g = np.zeros((nz, nz)), np.zeros(nz)
+        C, e = np.zeros(((N + 1) * NX, nz)), np.zeros((N + 1) * NX)
+        ix = lambda k: slice(k * (NX + NU), k * (NX + NU) + NX)                  # noqa: E731
+        iu = lambda k: slice(k * (NX + NU) + NX, (k + 1) * (NX + NU))            # noqa: E731
+        X, U = np.asarray(w.X[bb], np.float64), np.asarray(w.U[bb], np.float64)
+        C[:NX, ix(0)] = np.eye(NX); e[:NX] = np.asarray(w.x0[bb], np.float64) - X[0]
+        for k in range(N + 1):
+            term = k == N
+            yr = w.yref_e[bb] if term else (w.yref[bb, k] if w.yref.ndim == 3 else w.yref[bb])
+            Wk = np.asarray(w.W_e if term else w.W, np.float64)
+            n = node(w.mp, X[k], None if term else U[k], w.params[bb, k], yr, Wk, momentum, m, data)
+            Js = n["Js"]
+            H[ix(k), ix(k)] = Js[:, :NX].T @ Js[:, :NX] + (reg_e if term else reg) * np.eye(NX)
+            g[ix(k)] = Js[:, :NX].T @ Js[:, NX]
+            if term:
+                break
+            # the input terms: acc on a[6..17], f_reg on f -- a selection (oracle: wb_node_terms)
+            Rd, r = np.full(NU, reg), np.zeros(NU)
+            Rd[WA + 6:WA + 18] += Wk[RY_ACC:RY_ACC + 12]; r[WA + 6:WA + 18] = Wk[RY_ACC:RY_ACC + 12] * n["res"][RY_ACC:RY_ACC + 12]
+            Rd[WF:WF + 12] += Wk[RY_FREG:RY_FREG + 12]; r[WF:WF + 12] = Wk[RY_FREG:RY_FREG + 12] * n["res"][RY_FREG:RY_FREG + 12]
+            H[iu(k), iu(k)] = np.diag(Rd); g[iu(k)] = r
+            rows = slice((k + 1) * NX, (k + 2) * NX)
+            C[rows, ix(k)] = n["A"]; C[rows, iu(k)] = n["B"]; C[rows, ix(k + 1)] = -np.eye(NX)
+            e[rows] = -(n["xn"] - X[k + 1])
+        K = np.block([[H, C.T], [C, np.zeros((C.shape[0], C.shape[0]))]])
+        z = np.linalg.solve(K, np.concatenate([-g, e]))[:nz]
+        dX = np.stack([z[ix(k)] for k in range(N + 1)]); dU = np.stack([z[iu(k)] for k in range(N)])
+        Xs.append(X + dX); Us.append(U + dU)
+    return np.stack(Xs), np.stack(Us)
+
+
+def small_problem(B=3, N=4, seed=0):
+    """A wholebody_trot-shaped problem cut down to B x N with a stance node, both diagonal pairs and a flight node in every
+    problem's window, random forces and accelerations in the warm start, and the iterate off x0."""
+    import dataclasses
+    from iterative_learning_nmpc_amd import workloads as wl
+    w = wl.wholebody_trot(B=B, N=30, seed=seed)
+    rng = np.random.default_rng(seed + 100)
+    pats = np.array([[1, 1, 1, 1], [1, 0, 0, 1], [0, 0, 0, 0], [0, 1, 1, 0], [1, 1, 1, 1]], float)
+    params = w.params[:, :N + 1].copy()
+    for bb in range(B):
+        order = np.roll(np.arange(5), bb)
+        params[bb, :, :4] = pats[order[np.arange(N + 1) % 5]]
+        params[bb, :, 4:8] = 1.0 - params[bb, :, :4]
+    X = w.X[:, :N + 1] + rng.normal(0, 0.02, (B, N + 1, NX))
+    U = w.U[:, :N].copy()
+    U[:, :, :18] = rng.normal(0, 0.5, (B, N, 18))
+    U[:, :, 18:] = rng.normal(0, 8.0, (B, N, 12)) + np.array([0, 0, 30.0] * 4)
+    mp = w.mp.copy(); mp[0] = 0.02
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)                # noqa: E731  inputs exactly representable on the device
+    return dataclasses.replace(w, N=N, mp=f32(mp), x0=f32(w.x0), yref=f32(w.yref[:, :N]), yref_e=f32(w.yref_e), params=f32(params),
+                               X=f32(X), U=f32(U), W=f32(w.W), W_e=f32(w.W_e))
