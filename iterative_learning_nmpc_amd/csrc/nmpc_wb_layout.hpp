@@ -25,7 +25,9 @@ constexpr int HXQ = (HX - 32) >> 2, HXR = (HX - 32) & 3;      // lane row and re
 static_assert(HXR == 2, "the homogeneous row is register 2 of its lane row");
 
 // ---- the scaled residual Jacobian Js = sqrt(W) [J | res] of a node, COMPACT -------------------------------------------------------
-// Js is 30 x 46 with 381 structural non-zeros.  As a dense tile image (6 KB per node, each thread of the linearisation scattering
+// Js is 30 x 46 and the record keeps 381 of its positions: the 288 the model can make non-zero and, because the 3 x 9 foot Jacobian
+// blocks are stored whole, 93 that it never does (d p_f / d r = I and its zero time derivative, d z_f / d yaw = 0, d L_z / d yaw = 0;
+// tests/test_wb_record_layout.py counts both against the oracle).  As a dense tile image (6 KB per node, each thread of the linearisation scattering
 // its ~440 dword stores over its own image) it cost 0.6 of the linearisation's 0.78 ms per launch; it is now a 388-float record
 // in the order the linearisation produces it, written in 16 B pieces, and the QP kernel's prologue gathers its operand tiles
 // from the record through a per-lane index map (cj_index) -- the way the stage sweeps synthesise N~ and B~.
