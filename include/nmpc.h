@@ -356,12 +356,32 @@ int nmpc_wb_rollout_set_plant_push(void *handle, int as_force);
  *                nmpc_wb_rollout_set_plant): it must outlive the solves.  The first switch to this mode allocates two buffers
  *                of B_max (N + 1) records (228 and 216 floats); solves allocate nothing.
  * nmpc_solve_batch / nmpc_shift_solve_batch solve with the chosen model.  nmpc_wb_rollout_batch and nmpc_wb_label_states_batch
- * build the momentum of x0 from the declared map: on a handle in the articulated mode they return NMPC_E_STATE and launch nothing.
+ * build the momentum of x0 from the declared map: on a handle in the articulated mode they return NMPC_E_STATE and launch nothing
+ * until nmpc_wb_set_state_momentum (below) has given x0 the momentum of the tree.  Every call, in either direction, puts that
+ * switch back to NMPC_WB_STATE_MOMENTUM_DECLARED.
  * NMPC_E_ARG: a handle that is not NMPC_MODEL_WHOLEBODY, a model that is neither of the two, and for the articulated model a NULL
  * torque handle, a tree that does not have 18 joints, a tree without mass, a torque handle on another device. */
 #define NMPC_WB_MOMENTUM_DECLARED    0
 #define NMPC_WB_MOMENTUM_ARTICULATED 1
 int nmpc_wb_set_momentum_model(void *handle, void *torque_handle, int model);
+
+/* Where the momentum slots of a measured state come from in nmpc_wb_rollout_batch and nmpc_wb_label_states_batch [decl], per
+ * handle; NMPC_WB_STATE_MOMENTUM_DECLARED is the default and what both calls did before this one existed, refusals included.
+ *   declared   the prepare kernels' own map (one rigid body at the base origin); a handle in the articulated mode is refused.
+ *   tree       h = A_g(q) v of the momentum model's tree: behind its prepare kernel each call launches
+ *              nmpc_state_momentum_batch (include/nmpc_torque.h) on the call's stream and the momentum model's torque handle.  It
+ *              reads the plant state the prepare kernel read (q, v of a rollout; the chunk's rows of Q, V of the labeller), writes
+ *              slots 36..41 of x0[b] and of node 0 of X[b] (the measured state, a fixed point of the warm-start shift), and skips
+ *              what the prepare kernel skips (failed[b] & terminate_mask; the labeller's states behind a termination).  Slots
+ *              0..35, the references and the parameters are the prepare kernel's, bit for bit.  The robot's mass in the weight
+ *              share of the force reference and in the velocity jump of a push is m_tree of the momentum model, the mass its
+ *              dynamics carry, instead of NMPC_MP_MASS.  The calls still allocate nothing and never synchronise.
+ *              The kernel keeps no workspace on the torque handle, so a plant (nmpc_wb_rollout_set_plant) and attached labels
+ *              (nmpc_wb_rollout_set_actions) may use the momentum model's torque handle or another one of the same tree.
+ * NMPC_E_STATE: tree on a handle that is not in the articulated mode.  NMPC_E_ARG: a source that is neither of the two. */
+#define NMPC_WB_STATE_MOMENTUM_DECLARED 0   /* default */
+#define NMPC_WB_STATE_MOMENTUM_TREE     1
+int nmpc_wb_set_state_momentum(void *handle, int source);
 
 /* DAgger relabelling: the expert's labels for states somebody else's rollout visited (nmpc_policy_rollout_batch with
  * nmpc_policy_rollout_set_states, include/nmpc_torque.h).  For every state (b, k) -- robot b < B, row k < n_rows -- the
@@ -423,6 +443,10 @@ int nmpc_debug_wb_layout(int N, size_t *out8);
  * dcons_host float[216]: the sqrt(W)-scaled consistency rows, row i at 36 i: q_3..q_17 [15], v [18], h_i, residual, padding.
  * NMPC_E_STATE on a handle that was never in the articulated mode.  Synchronises the device. */
 int nmpc_debug_read_momentum(void *handle, int b, int k, float *mrec_host, float *dcons_host);
+/* Test hook of the whole-body rollouts and the labeller: what their prepare kernel (and, with NMPC_WB_STATE_MOMENTUM_TREE, the
+ * state-momentum kernel behind it) left for problem b < B_max of the last replan or chunk, each may be NULL --
+ * x0_host float[42]: the initial state of its solve; yref_host float[N * 90]: its stage references.  Synchronises the device. */
+int nmpc_debug_read_rollout_problem(void *handle, int b, float *x0_host, float *yref_host);
 
 /* Diagnostic builds (-DNMPC_STAMPS) write cycle counts to dev float[B_max][16]: 8 phases
  * (linearise, IPM update+coefficients, backward, forward, last IPM update, step+write-back, -, -)

@@ -110,6 +110,23 @@ int nmpc_centroidal_batch(void *handle, int B, const float *q, const float *v, f
 int nmpc_centroidal_derivatives_batch(void *handle, int B, const float *q, const float *v,
                                       float *dh_dq, float *dcom_dq, float *hdot_bias, void *stream);
 
+/* The centroidal momentum of a plant state alone: what a measured state's x0 carries in model 2's momentum slots when the solve
+ * runs the articulated momentum model (nmpc_wb_set_state_momentum of nmpc.h).  One thread per state runs the outward pass of the
+ * call above -- frame rotations, origins from the anchor point O, body velocities, every body's momentum about O, the totals, the
+ * centre of mass -- and nothing else: no inward pass and no columns, 18 floats of LDS per joint and state, no scratch.  Rows are
+ * strided, so the call reads a table of states and writes into the solver's tensors where they lie.  It agrees with
+ * nmpc_centroidal_batch's h to fp32 rounding (another algorithm: not bit for bit) and, like the derivatives, does not see the
+ * base position.  Any tree the handle accepts; a q or v that is not finite gives an h that is not finite in its own row only.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), before any launch: B < 0, a NULL q, v or h, qv_stride < n_joints, h_stride < 6,
+ * h2 with h2_stride < 6, a tree whose total mass is zero. */
+/* h = A_g(q) v of the articulated tree for B plant states: [linear; angular about the centre of mass], world axes,
+ * model 2's slot order.  q, v at q + b*qv_stride (floats, >= n_joints); written to h + b*h_stride and, if h2 is
+ * given, to h2 + b*h2_stride (strides >= 6).  skip: NULL, or dev int[B]; a row with skip[b] & skip_mask != 0 is
+ * neither read nor written. */
+int nmpc_state_momentum_batch(void *handle, int B, const float *q, const float *v, int qv_stride,
+                              float *h, int h_stride, float *h2, int h2_stride,
+                              const int *skip, int skip_mask, void *stream);
+
 /* The ground-contact plant [decl] (the reference's is MuJoCo).  The ground is the plane z = ground_z with normal e_z.  A foot
  * point at world position p with world velocity pd and penetration delta = ground_z - p_z is pushed with
  *   f_z  = stiffness delta max(0, 1 - damping pd_z)  for delta > 0, else 0    (Hunt-Crossley: continuous at touch-down, never pulls)

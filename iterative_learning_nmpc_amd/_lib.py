@@ -49,6 +49,7 @@ SIGNATURES = {
     "nmpc_wb_rollout_set_plant": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_wb_rollout_set_plant_push": (c_int, [c_void_p, c_int]),
     "nmpc_wb_set_momentum_model": (c_int, [c_void_p, c_void_p, c_int]),
+    "nmpc_wb_set_state_momentum": (c_int, [c_void_p, c_int]),
     "nmpc_set_ipm": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float]),
     "nmpc_shift_warm_start": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "nmpc_solve_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -98,6 +99,8 @@ SIGNATURES = {
     "nmpc_mass_matrix_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "nmpc_centroidal_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_centroidal_derivatives_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_state_momentum_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                          c_void_p]),
     "nmpc_foot_kinematics_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_contact_forces_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_contact_step_batch": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
@@ -124,6 +127,7 @@ SIGNATURES = {
     "nmpc_debug_read_workspace": (c_int, [c_void_p, c_int, c_size_t, c_size_t, POINTER(c_float)]),
     "nmpc_debug_wb_layout": (c_int, [c_int, POINTER(c_size_t)]),
     "nmpc_debug_read_momentum": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float)]),
+    "nmpc_debug_read_rollout_problem": (c_int, [c_void_p, c_int, POINTER(c_float), POINTER(c_float)]),
 }
 
 

@@ -58,6 +58,7 @@ struct Handle {
         void* torque = nullptr;  // borrowed: its tree is the model
         float* mrec = nullptr;   // [B_max][N+1] momentum records (nmpc_wb_momentum.hpp), written by the momentum pass of every SQP iteration
         float* dcons = nullptr;  // [B_max][N+1] dense consistency records, linearisation -> QP kernel
+        int state_source = NMPC_WB_STATE_MOMENTUM_DECLARED;   // nmpc_wb_set_state_momentum: where the momentum of a measured state comes from
     } momentum;
     bool plant_push_as_force = false;   // nmpc_wb_rollout_set_plant_push: a plant-mode rollout pushes with a force on the plant, not a velocity jump
     bool ws_dirty = false;   // a dense-LQ call left foreign padding in the tile workspace
@@ -172,11 +173,37 @@ int launch_wb(Handle* h, nmpc::wb::WbArgs a, hipStream_t st) {
     return launch_sqp(h, a, st, lds_bytes, nmpc::wb::nmpc_wb_qp_art_kernel, nmpc::wb::nmpc_wb_linearize_art_kernel, momentum_pass, m);
 }
 
-// the entry points that build x0's momentum from the declared map refuse a handle in the articulated mode
+// the entry points that build x0's momentum from the declared map refuse a handle in the articulated mode, unless the momentum
+// of the tree is put into x0 behind them (nmpc_wb_set_state_momentum)
 int check_declared_momentum(Handle* h, const char* who) {
-    return h->momentum.torque ? fail(h, NMPC_E_STATE, std::string(who) + " builds the momentum of x0 from the declared map: not available "
-                                                      "with the articulated momentum model (nmpc_wb_set_momentum_model)")
-                              : NMPC_OK;
+    if (!h->momentum.torque || h->momentum.state_source != NMPC_WB_STATE_MOMENTUM_DECLARED) return NMPC_OK;
+    return fail(h, NMPC_E_STATE, std::string(who) + " builds the momentum of x0 from the declared map: not available "
+                                                    "with the articulated momentum model (nmpc_wb_set_momentum_model)");
+}
+
+// the whole-body rollouts' and the labeller's carve-up of h->roll: every array starts on a 16 B boundary (launch_wb checks)
+struct WbRoll { float *yref, *yref_e, *params, *x0; };
+WbRoll wb_roll(const Handle* h) {
+    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+    const size_t B_max = (size_t)h->dims.B_max, N = (size_t)h->dims.N;
+    WbRoll r{};
+    r.yref = h->roll;
+    r.yref_e = r.yref + up4(B_max * N * h->ny);
+    r.params = r.yref_e + up4(B_max * h->nye);
+    r.x0 = r.params + up4(B_max * (N + 1) * h->np);
+    return r;
+}
+
+// the momentum model's tree gives x0 its momentum (never without the articulated mode: nmpc_wb_set_momentum_model resets the switch)
+bool tree_state_momentum(const Handle* h) { return h->momentum.torque && h->momentum.state_source == NMPC_WB_STATE_MOMENTUM_TREE; }
+
+// h = A_g(q) v of the momentum model's tree for `count` plant states, into the momentum slots of their x0 and of node 0 of their X
+int launch_state_momentum(Handle* h, int count, const float* q, const float* v, int qv_stride, float* x0, float* X, const int* skip,
+                          int skip_mask, hipStream_t st) {
+    void* torque = h->momentum.torque;
+    const int rc = nmpc_state_momentum_batch(torque, count, q, v, qv_stride, x0 + nmpc::wb::WH, nmpc::wb::NX, X + nmpc::wb::WH,
+                                             (h->dims.N + 1) * nmpc::wb::NX, skip, skip_mask, st);
+    return rc ? fail(h, rc, std::string("nmpc_state_momentum_batch: ") + nmpc_torque_last_error(torque)) : (int)NMPC_OK;
 }
 
 // Two variants of the QP kernel (nmpc_solve.hip, Lds).  Resident: stage arrays in the LDS (39.6 KB at N = 50: four waves per CU),
@@ -251,10 +278,12 @@ int read_tile(Handle* h, int b, int k, int which, float* out) {
 // The replan loop of both device rollouts (LocomotionMPC.open_loop, mpc.py:416-462): per replan  prepare -> solve -> advance,
 // all on the caller's stream.  r: the plant's kernel arguments, its own fields, the carve-up of h->roll and the caller's pointers
 // filled in; a: the arguments of its solve with x0 and status.  plan(i) sets what the plant alone knows of replan i (its node)
-// and returns the warm-start shift of its solve; after_solve(i) runs between the solve and the advance kernel.
-template <class Cfg, class R, class A, class Plan, class AfterSolve>
+// and returns the warm-start shift of its solve; after_prepare() runs between the prepare kernel and the solve, after_solve(i)
+// between the solve and the advance kernel.
+template <class Cfg, class R, class A, class Plan, class AfterPrepare, class AfterSolve>
 int run_rollout(Handle* h, int B, const Cfg* cfg, hipStream_t st, R& r, A& a, void (*prepare)(const R),
-                int (*solve)(Handle*, A, hipStream_t), void (*advance)(const R), Plan plan, AfterSolve after_solve) {
+                int (*solve)(Handle*, A, hipStream_t), void (*advance)(const R), Plan plan, AfterPrepare after_prepare,
+                AfterSolve after_solve) {
     NMPC_ENTER(h, h->device);
     if (const int rc = clean_workspace(h, st)) return rc;
     const int N = h->dims.N;
@@ -282,6 +311,7 @@ int run_rollout(Handle* h, int B, const Cfg* cfg, hipStream_t st, R& r, A& a, vo
                      t_now < (double)cfg->push_start + (double)cfg->push_duration - slack) ? (float)dt_replan : 0.0f;
         const int shift = plan(i);
         hipLaunchKernelGGL(prepare, dim3(B), dim3(64), 0, st, r);
+        if (const int rc = after_prepare()) return rc;
         a.shift = cold ? 0 : (shift > N ? N : shift);             // warm start folded into the solve
         a.max_sqp = cold ? cfg->max_sqp_first : h->max_sqp;
         a.nlp_tol = cold ? cfg->nlp_tol_first : cfg->nlp_tol;
@@ -479,6 +509,7 @@ int nmpc_wb_set_momentum_model(void* handle, void* torque_handle, int model) {
     if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_wb_set_momentum_model needs the whole-body model");
     if (model != NMPC_WB_MOMENTUM_DECLARED && model != NMPC_WB_MOMENTUM_ARTICULATED)
         return fail(h, NMPC_E_ARG, "model is NMPC_WB_MOMENTUM_DECLARED or NMPC_WB_MOMENTUM_ARTICULATED");
+    h->momentum.state_source = NMPC_WB_STATE_MOMENTUM_DECLARED;      // never the tree's x0 with the declared dynamics
     if (model == NMPC_WB_MOMENTUM_DECLARED) {      // the buffers of the articulated mode stay with the handle for the next switch
         h->momentum.torque = nullptr;
         return NMPC_OK;
@@ -489,6 +520,17 @@ int nmpc_wb_set_momentum_model(void* handle, void* torque_handle, int model) {
     if (!h->momentum.mrec) NMPC_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->momentum.mrec), nodes * nmpc::wb::MR_FLOATS * sizeof(float)));
     if (!h->momentum.dcons) NMPC_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->momentum.dcons), nodes * nmpc::wb::DC_FLOATS * sizeof(float)));
     h->momentum.torque = torque_handle;
+    return NMPC_OK;
+}
+
+int nmpc_wb_set_state_momentum(void* handle, int source) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    if (source != NMPC_WB_STATE_MOMENTUM_DECLARED && source != NMPC_WB_STATE_MOMENTUM_TREE)
+        return fail(h, NMPC_E_ARG, "source is NMPC_WB_STATE_MOMENTUM_DECLARED or NMPC_WB_STATE_MOMENTUM_TREE");
+    if (source == NMPC_WB_STATE_MOMENTUM_TREE && !h->momentum.torque)
+        return fail(h, NMPC_E_STATE, "the momentum of the tree in x0 needs the articulated momentum model (nmpc_wb_set_momentum_model)");
+    h->momentum.state_source = source;
     return NMPC_OK;
 }
 
@@ -642,7 +684,7 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
                            r.phase = phase[i];
                            return cfg->nodes_per_replan;
                        },
-                       [](int) { return NMPC_OK; });
+                       [] { return NMPC_OK; }, [](int) { return NMPC_OK; });
 }
 
 int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, const signed char* gait, const signed char* peaks,
@@ -698,16 +740,18 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
         if (plant_push.n_substeps < 0) plant_push.n_substeps = 0;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };       // every array starts on a 16 B boundary (launch_wb checks)
+    const WbRoll roll = wb_roll(h);
     nmpc::wb::WbRolloutArgs r{};
     r.plant = pl.torque ? 1 : 0;
-    r.yref = h->roll;
-    r.yref_e = r.yref + up4((size_t)h->dims.B_max * N * h->ny);
-    r.params = r.yref_e + up4((size_t)h->dims.B_max * h->nye);
-    r.x0 = r.params + up4((size_t)h->dims.B_max * (N + 1) * h->np);
+    r.yref = roll.yref; r.yref_e = roll.yref_e; r.params = roll.params; r.x0 = roll.x0;
     r.force_gravity = cfg->force_reference_gravity ? 1 : 0;
     r.step_height = cfg->step_height;
     r.mp = h->mp;
+    const bool tree_h = tree_state_momentum(h);
+    if (tree_h) {       // the mass of the force reference's weight share and of a push's velocity jump: the one the dynamics carry
+        if (const char* why = nmpc_torque::momentum_refusal(h->momentum.torque, h->device)) return fail(h, NMPC_E_STATE, std::string("momentum model: ") + why);
+        r.mp.mass = nmpc_torque::tree_mass(h->momentum.torque);
+    }
     r.gait = gait; r.peaks = peaks; r.q = q; r.v = v; r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state;
     r.joint_ref = joint_ref; r.push_force = push_force;
     r.X = X; r.U = U; r.S = S; r.status = status; r.failed = failed;
@@ -721,6 +765,10 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
             r.node = last_node = nodes[i];
             if (force_push) r.push_dt = 0.0f;      // the track launch pushes: no velocity jump in the advance kernel
             return shift;
+        },
+        [&] {                 // x0's momentum from the tree, for the rollouts the prepare kernel prepared
+            if (!tree_h) return (int)NMPC_OK;
+            return launch_state_momentum(h, B, q, v, 18, r.x0, X, r.term_mask ? failed : nullptr, r.term_mask, st);
         },
         [&](int i) {          // the labels of this replan's plan, beside the rows the advance kernel is about to record
             if (!lab.A && !pl.torque) return (int)NMPC_OK;
@@ -793,19 +841,21 @@ int nmpc_wb_label_states_batch(void* handle, void* torque_handle, int B, const n
     hipStream_t st = static_cast<hipStream_t>(stream);
     NMPC_ENTER(h, h->device);
     if (const int rc = clean_workspace(h, st)) return rc;
-    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };       // the carve-up of nmpc_wb_rollout_batch
+    const WbRoll roll = wb_roll(h);                                 // the carve-up of nmpc_wb_rollout_batch
     nmpc::wb::WbLabelArgs r{};
     r.K = K; r.N = N; r.npc = cfg->nodes_per_cycle; r.qv_rows = qv_rows;
     r.force_gravity = cfg->force_reference_gravity ? 1 : 0;
     r.step_height = cfg->step_height;
     r.sim_dt = cfg->sim_dt; r.t_horizon = cfg->time_horizon; r.nom_height = cfg->nom_height; r.height_offset = cfg->height_offset;
     r.mp = h->mp;
+    const bool tree_h = tree_state_momentum(h);
+    if (tree_h) {       // as nmpc_wb_rollout_batch: the weight share of the force reference takes the mass of the tree
+        if (const char* why = nmpc_torque::momentum_refusal(h->momentum.torque, h->device)) return fail(h, NMPC_E_STATE, std::string("momentum model: ") + why);
+        r.mp.mass = nmpc_torque::tree_mass(h->momentum.torque);
+    }
     r.gait = gait; r.peaks = peaks; r.node = node; r.ref_steps = ref_steps; r.failed = failed; r.Q = Q; r.V = V; r.joint_ref = joint_ref;
     r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state;
-    r.yref = h->roll;
-    r.yref_e = r.yref + up4((size_t)B_max * N * h->ny);
-    r.params = r.yref_e + up4((size_t)B_max * h->nye);
-    r.x0 = r.params + up4((size_t)B_max * (N + 1) * h->np);
+    r.yref = roll.yref; r.yref_e = roll.yref_e; r.params = roll.params; r.x0 = roll.x0;
     r.X = X; r.U = U; r.skip = h->label_skip;
     nmpc::wb::WbArgs w = wb_args(h);
     w.yref_per_stage = 1; w.shift = 0;
@@ -819,6 +869,17 @@ int nmpc_wb_label_states_batch(void* handle, void* torque_handle, int B, const n
         const int count = (int)(total - m0 < B_max ? total - m0 : B_max);
         r.m0 = (int)m0;
         hipLaunchKernelGGL(nmpc::wb::nmpc_wb_label_prepare_kernel, dim3(count), dim3(64), 0, st, r);
+        // x0's momentum from the tree: problem m = b K + k reads row k of robot b; where the tables have exactly K rows per robot the
+        // chunk's states are one strided run, otherwise robot by robot
+        for (long long m = m0; tree_h && m < m0 + count;) {
+            const long long b = m / K, k = m - b * K;
+            const int run = qv_rows == K ? count : (int)((K - k < m0 + count - m) ? K - k : m0 + count - m);
+            const size_t i = (size_t)(m - m0), row = ((size_t)b * qv_rows + k) * 18;
+            if (const int rc = launch_state_momentum(h, run, Q + row, V + row, 18, r.x0 + i * nmpc::wb::NX, X + i * (N + 1) * nmpc::wb::NX,
+                                                     h->label_skip + i, 1, st))
+                return rc;
+            m += run;
+        }
         w.B = count; w.status = status + m0;
         if (const int rc = launch_wb(h, w, st)) return rc;
         // label row 0 of every plan of the chunk: the target applied from the state its solve started from.  Problem m = b K + k
@@ -878,6 +939,20 @@ int nmpc_debug_read_momentum(void* handle, int b, int k, float* mrec_host, float
         NMPC_TRY(h, hipMemcpy(mrec_host, h->momentum.mrec + node * nmpc::wb::MR_FLOATS, nmpc::wb::MR_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
     if (dcons_host)
         NMPC_TRY(h, hipMemcpy(dcons_host, h->momentum.dcons + node * nmpc::wb::DC_FLOATS, nmpc::wb::DC_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+    return NMPC_OK;
+}
+
+int nmpc_debug_read_rollout_problem(void* handle, int b, float* x0_host, float* yref_host) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_debug_read_rollout_problem needs the whole-body model");
+    if (b < 0 || b >= h->dims.B_max) return fail(h, NMPC_E_ARG, "index out of range");
+    NMPC_ENTER(h, h->device);
+    NMPC_TRY(h, hipDeviceSynchronize());
+    const WbRoll roll = wb_roll(h);
+    if (x0_host) NMPC_TRY(h, hipMemcpy(x0_host, roll.x0 + (size_t)b * h->nx, h->nx * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t per = (size_t)h->dims.N * h->ny;
+    if (yref_host) NMPC_TRY(h, hipMemcpy(yref_host, roll.yref + (size_t)b * per, per * sizeof(float), hipMemcpyDeviceToHost));
     return NMPC_OK;
 }
 

@@ -17,7 +17,9 @@
 // nmpc_torque_track.hip.inc; what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of
 // one composite-rigid-body pass -- is nmpc_torque_crba.hip.inc; the plant's second integrator, which takes the stiff contact and PD
 // terms implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; how the centroidal momentum moves with q --
-// d(A_g v)/dq, d com/dq and the bias of its time derivative -- is nmpc_torque_cmd.hip.inc.
+// d(A_g v)/dq, d com/dq and the bias of its time derivative -- is nmpc_torque_cmd.hip.inc; the momentum pass on the nodes of a
+// whole-body solve is nmpc_torque_momentum.hip.inc, and the momentum A_g(q) v of a plant state alone, which the device rollouts put
+// into x0, is nmpc_torque_state_momentum.hip.inc.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -358,6 +360,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_implicit.hip.inc"
 #include "nmpc_torque_cmd.hip.inc"
 #include "nmpc_torque_momentum.hip.inc"
+#include "nmpc_torque_state_momentum.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -453,6 +456,9 @@ int allocate(Torque* t) {
     // the momentum pass of the whole-body solve: the same slice
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(wb_momentum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)cmd_lds_bytes(MAXJ, MM_W)));
+    // the momentum of a plant state: its own, smaller slice of the largest tree at its one width
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(state_momentum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)sm_lds_bytes(MAXJ, SM_W)));
     return NMPC_OK;
 }
 
@@ -855,6 +861,25 @@ int nmpc_centroidal_derivatives_batch(void* handle, int B, const float* q, const
     while (!(m.mass[p.anchor] > 0.0f)) ++p.anchor;      // there is one: the total is positive
     for (int k = p.anchor; k >= 0; k = m.parent[k]) p.chain |= 1u << k;
     return launch_step(t, cmd_kernel, CD_W, cmd_lds_bytes(m.n, CD_W), p, stream);
+}
+
+int nmpc_state_momentum_batch(void* handle, int B, const float* q, const float* v, int qv_stride, float* h, int h_stride, float* h2,
+                              int h2_stride, const int* skip, int skip_mask, void* stream) {
+    Torque* t = static_cast<Torque*>(handle);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    const Model& m = t->host;
+    if (B < 0 || !q || !v || !h) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, h");
+    if (qv_stride < m.n) return fail(t, NMPC_E_ARG, "qv_stride must be at least n_joints");
+    if (h_stride < 6 || (h2 && h2_stride < 6)) return fail(t, NMPC_E_ARG, "h_stride and h2_stride must be at least 6");
+    if (!(total_mass(m) > 0.0f)) return fail(t, NMPC_E_ARG, "the tree has no mass: its centre of mass is undefined");
+    NMPC_ENTER(t, t->device);
+    StateMomentumArgs p{};
+    p.B = B; p.qv_stride = qv_stride; p.h_stride = h_stride; p.h2_stride = h2_stride; p.skip_mask = skip ? skip_mask : 0;
+    p.q = q; p.v = v; p.h = h; p.h2 = h2; p.skip = p.skip_mask ? skip : nullptr;
+    while (!(m.mass[p.anchor] > 0.0f)) ++p.anchor;      // there is one: the total is positive
+    for (int k = p.anchor; k >= 0; k = m.parent[k]) p.chain |= 1u << k;
+    return launch_step(t, state_momentum_kernel, SM_W, sm_lds_bytes(m.n, SM_W), p, stream);
 }
 
 int nmpc_foot_kinematics_batch(void* handle, int B, const float* q, const float* v, float* pos, float* vel, void* stream) {

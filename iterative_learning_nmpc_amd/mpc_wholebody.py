@@ -41,7 +41,7 @@ class LocomotionMPC:
                  torque_layer=None):
         """momentum_model, torque_layer: as `QuadrupedAcadosSolver` -- "articulated" solves with the centroidal momentum of the
         tree of `torque_layer` and takes x0's `h` from it; `optimize` and `open_loop` work in that mode, `open_loop_device` and
-        `label_states` (whose kernels build x0 from the declared map) raise."""
+        `label_states` (whose kernels build x0 from the declared map) raise until `set_state_momentum("tree")`."""
         self.batch = int(batch)
         self.config_gait, self.config_opt, self.config_cost = get_quadruped_config(gait_name, robot_name)
         if n_nodes is not None:                      # BASELINE configs[2] asks for N = 30; the reference runs 25
@@ -369,8 +369,20 @@ class LocomotionMPC:
             kp=float(self.Kp if kp is None else kp), kd=float(self.Kd if kd is None else kd), terminate_mask=int(TERMINATE_DEFAULT))
         return A, status
 
+    def set_state_momentum(self, source: str = "declared") -> None:
+        """Where `open_loop_device` and `label_states` take the momentum slots of a measured state from
+        (`BatchedNmpcSolver.set_state_momentum`).  "declared" (the default): the declared map, so both raise on an articulated
+        controller.  "tree" (momentum_model="articulated" only): the momentum of the tree, computed on the device behind every
+        prepare kernel -- what `optimize` puts into x0 on the host; the weight share of force_reference="gravity_share" and a
+        push's velocity jump then take the mass of the tree."""
+        self.solver.set_state_momentum(source)
+
+    @property
+    def state_momentum(self) -> str:
+        return self.solver.state_momentum
+
     def _declared_momentum_only(self, who: str) -> None:
-        if self.momentum_model != "declared":
+        if self.momentum_model != "declared" and self.state_momentum == "declared":
             raise RuntimeError(f"{who}: the device builds the momentum of x0 from the declared map; with momentum_model="
                                f"\"{self.momentum_model}\" use optimize / open_loop")
 

@@ -112,6 +112,7 @@ class QuadrupedAcadosSolver:
         if momentum_model == "articulated" and torque_layer is None:
             raise ValueError("momentum_model=\"articulated\" needs torque_layer")
         self.momentum_model = momentum_model
+        self.state_momentum = "declared"      # set_state_momentum
         self.torque_layer = torque_layer if momentum_model == "articulated" else None
         self.feet_frame_names = list(feet_frame_names)
         assert len(self.feet_frame_names) == 4, "the declared model is a quadruped"
@@ -393,7 +394,9 @@ class QuadrupedAcadosSolver:
         if self.force_reference == "gravity_share":
             n_st = np.maximum(act[:, :N].sum(-1, keepdims=True), 1.0)
             f_ref = f_ref.copy()
-            f_ref[:, :, 2::3] += act[:, :N] * (-self.mp[5] * self.mp[1]) / n_st
+            # the robot's mass: the declared one, or with set_state_momentum("tree") the mass the articulated dynamics carry
+            mass = np.float32(self.torque_layer.tree_mass) if self.state_momentum == "tree" else self.mp[1]
+            f_ref[:, :, 2::3] += act[:, :N] * (-self.mp[5] * mass) / n_st
         pos_ref = np.concatenate([t(self.cost_ref[f.pos_cost.name])[..., :2] for f in d.feet], axis=-1)        # [B, N, 8]
         pos_ref_e = np.concatenate([self._b(self.cost_ref_terminal[f.pos_cost.name])[..., :2] for f in d.feet], axis=-1)
         yref = np.concatenate([t(self.cost_ref[d.base_cost.name]), t(self.cost_ref[d.joint_cost.name]),
@@ -429,8 +432,22 @@ class QuadrupedAcadosSolver:
             self._dev.set_model_params(self.mp)
             self._dev.set_cost_weights(self._W, self._W_e, self.config_cost.reg_eps, self.config_cost.reg_eps_e)
             self._dev.set_momentum_model(self.momentum_model, torque_layer=self.torque_layer)
+            self._dev.set_state_momentum(self.state_momentum)
             self._push_opts()
         return self._dev
+
+    def set_state_momentum(self, source: str = "declared") -> None:
+        """`BatchedNmpcSolver.set_state_momentum` of the device solver (now, or when it is created): "tree" lets the device
+        rollouts and the labeller of an articulated controller take x0's `h` from the tree, as `init` does on the host.  The weight
+        share of force_reference="gravity_share" then takes the mass of the tree (`torque_layer.tree_mass`), here and on the
+        device: the mass the articulated dynamics carry, which need not be the declared one (quadruped_tree(): 14.98 kg against 15)."""
+        if source not in ("declared", "tree"):
+            raise ValueError(f"state momentum: \"declared\" or \"tree\", got {source!r}")
+        if source == "tree" and self.momentum_model != "articulated":
+            raise RuntimeError("state momentum: the momentum of the tree in x0 needs momentum_model=\"articulated\"")
+        if self._dev is not None:
+            self._dev.set_state_momentum(source)
+        self.state_momentum = source
 
     def _buffers(self):
         """device tensors of the problem and pinned host mirrors, allocated once: a solve is six asynchronous uploads, the

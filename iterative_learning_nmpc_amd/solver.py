@@ -53,6 +53,7 @@ class BatchedNmpcSolver:
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _lib.check(self.lib.nmpc_create(ctypes.byref(dims), dev_index, ctypes.byref(self._h)), None, "nmpc_create")
         self.momentum_model, self._momentum_layer = "declared", None      # set_momentum_model
+        self.state_momentum = "declared"                                  # set_state_momentum
         self._opts = dict(max_iter=1, max_qp_iter=6, nlp_tol=0.0, qp_tol=1e-2, line_search=0)
         self._push_opts()
 
@@ -176,16 +177,30 @@ class BatchedNmpcSolver:
         `torque_layer` (a `BatchedTorqueLayer` of 18 joints in the coordinates of the model) in the consistency rows and the
         momentum rows of the dynamics; the layer is borrowed and kept alive by this object while the mode is on.  `solve` works
         in both modes; `wb_rollout` and `label_states` build x0's momentum from the declared map and are refused in the
-        articulated mode."""
+        articulated mode until `set_state_momentum("tree")` gives x0 the momentum of the tree."""
         if model not in self.MOMENTUM_MODELS:
             raise ValueError(f"momentum model: one of {sorted(self.MOMENTUM_MODELS)}, got {model!r}")
         if model == "articulated" and torque_layer is None:
             raise ValueError("the articulated momentum model needs torque_layer")
         layer = torque_layer if model == "articulated" else None
+        self.state_momentum = "declared"      # the library puts the switch back with every call, one it then refuses included
         _lib.check(self.lib.nmpc_wb_set_momentum_model(self._h, layer._h if layer is not None else None, self.MOMENTUM_MODELS[model]),
                    self._h, "nmpc_wb_set_momentum_model")
         self._momentum_layer = layer
         self.momentum_model = model
+
+    STATE_MOMENTUM = {"declared": 0, "tree": 1}      # NMPC_WB_STATE_MOMENTUM_* of include/nmpc.h
+
+    def set_state_momentum(self, source: str = "declared"):
+        """nmpc_wb_set_state_momentum: where `wb_rollout` and `label_states` take the momentum slots of a measured state from.
+        "declared" (the default): the declared map, so both are refused while the momentum model is "articulated".  "tree"
+        (articulated mode only): h = A_g(q) v of the momentum model's tree, one `BatchedTorqueLayer.state_momentum` launch behind
+        the prepare kernel of every replan or chunk; the robot's mass in the force reference's weight share and in a push's
+        velocity jump is then the mass of the tree.  `set_momentum_model` puts the source back to "declared"."""
+        if source not in self.STATE_MOMENTUM:
+            raise ValueError(f"state momentum: one of {sorted(self.STATE_MOMENTUM)}, got {source!r}")
+        _lib.check(self.lib.nmpc_wb_set_state_momentum(self._h, self.STATE_MOMENTUM[source]), self._h, "nmpc_wb_set_state_momentum")
+        self.state_momentum = source
 
     def set_ipm(self, mu0=10.0, sigma=0.2, s_min=1.0, gamma=0.995, tau_min=0.1, merit_rho=1e3):
         _lib.check(self.lib.nmpc_set_ipm(self._h, mu0, sigma, s_min, gamma, tau_min, merit_rho),
@@ -412,6 +427,15 @@ class BatchedNmpcSolver:
         _lib.check(self.lib.nmpc_debug_read_momentum(self._h, b, k, mrec.ctypes.data_as(fp), dcons.ctypes.data_as(fp)),
                    self._h, "nmpc_debug_read_momentum")
         return mrec, dcons
+
+    def debug_rollout_problem(self, b: int):
+        """(x0 [42], yref [N, 90]) of problem b as the last replan of `wb_rollout` / the last chunk of `label_states` prepared
+        it (test hook)"""
+        fp = ctypes.POINTER(ctypes.c_float)
+        x0, yref = np.zeros(self.nx, dtype=np.float32), np.zeros((self.n_nodes, self.ny), dtype=np.float32)
+        _lib.check(self.lib.nmpc_debug_read_rollout_problem(self._h, b, x0.ctypes.data_as(fp), yref.ctypes.data_as(fp)),
+                   self._h, "nmpc_debug_read_rollout_problem")
+        return x0, yref
 
     @property
     def workspace_bytes(self) -> int:

@@ -72,6 +72,9 @@ class BatchedTorqueLayer:
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _lib.check(self.lib.nmpc_torque_create(ctypes.byref(m), idx, ctypes.byref(self._h)), None, "nmpc_torque_create", "torque")
         self.n, self.nu, self.n_feet = n, int(n_actuated), nf
+        self.tree_mass = 0.0            # the total mass as the library sums it (float32, in joint order): the m_tree of the articulated model
+        for m_i in arrays["mass"]:
+            self.tree_mass = float(np.float32(np.float32(self.tree_mass) + m_i))
         self._states = None             # set_rollout_states: the attached (Q, V)
         self._push = None               # set_push: the attached force
 
@@ -169,6 +172,30 @@ class BatchedTorqueLayer:
         _lib.check(self.lib.nmpc_centroidal_batch(self._h, B, ptr(q), ptr(v), ptr(com), ptr(h), ptr(Ag), stream(self.device)),
                    self._h, "nmpc_centroidal_batch", "torque")
         return (com, h, Ag) if jacobian else (com, h)
+
+    def state_momentum(self, q, v, out=None, skip=None, skip_mask: int = 0):
+        """nmpc_state_momentum_batch: q, v [B, n] plant states -> h [B, 6] = [linear; angular about com] in world axes, `centroidal`'s
+        h from the outward pass alone (to fp32 rounding, not bit for bit), which is what the device rollouts put into x0
+        (`BatchedNmpcSolver.set_state_momentum`).  q, v may be views whose rows are a common stride >= n apart; out: a float32
+        view [B, 6] to write into (row stride >= 6, last axis dense), otherwise a new tensor; skip int32 [B]: a row with
+        skip[b] & skip_mask != 0 is neither read nor written."""
+        def strided(t, width, like):
+            """t as it is if it is a float32 view [B, width] on `like`'s device with a dense last axis and rows >= width apart"""
+            return (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == width and t.stride(1) == 1
+                    and (t.shape[0] < 2 or t.stride(0) >= width) and (like is None or t.device == like.device))
+        if not (strided(q, self.n, None) and strided(v, self.n, q) and q.stride(0) == v.stride(0) and q.device.type == self.device.type):
+            q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")      # anything else: dense rows
+        B = self._batch(q, v)
+        if out is None:
+            out = torch.empty(B, 6, dtype=torch.float32, device=q.device)
+        if not strided(out, 6, q) or out.shape[0] != B:
+            raise ValueError(f"out: need a float32 view [{B}, 6] on {q.device} with a dense last axis and rows at least 6 apart")
+        self._flags(skip, q, "skip")
+        stride = lambda t, width: max(t.stride(0), width)      # noqa: E731  (the stride of a single row is arbitrary)
+        _lib.check(self.lib.nmpc_state_momentum_batch(self._h, B, ptr(q), ptr(v), stride(q, self.n), ptr(out), stride(out, 6), None, 0,
+                                                      ptr(skip), int(skip_mask), stream(self.device)),
+                   self._h, "nmpc_state_momentum_batch", "torque")
+        return out
 
     def centroidal_derivatives(self, q, v, com_jacobian: bool = False, bias: bool = False):
         """nmpc_centroidal_derivatives_batch: q, v [B, n] -> dh_dq [B, 6, n], the derivative of `centroidal`'s h = Ag(q) v with

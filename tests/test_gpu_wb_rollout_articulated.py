@@ -1,0 +1,385 @@
+"""The device-resident whole-body path under the articulated momentum model: nmpc_wb_set_state_momentum = tree puts
+h = A_g(q) v of the momentum model's tree (nmpc_state_momentum_batch, tests/test_gpu_state_momentum.py) into x0 behind the prepare
+kernels of nmpc_wb_rollout_batch and nmpc_wb_label_states_batch, and the mass of the tree into the force reference and the push.
+
+The references: tests/crba_reference.py in fp64 for x0's momentum, at the layer's bar (torque_helpers.held); the host-driven
+`LocomotionMPC.open_loop` for a whole rollout, at the 2e-5 relative L2 of the declared counterpart
+(test_gpu_wholebody.py::test_wholebody_device_rollout_equals_host_driven_open_loop: the loops differ only in which fp32 routine
+forms x0's h); and the device's own public calls, bit for bit, for labels, plant mode and collection.  Every figure is printed
+before it is asserted.  T = 0.0395 s makes the float clock run exactly one replan of 40 simulation steps, 0.0795 two."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests import crba_reference as cr
+from tests import wb_momentum_reference as mr
+from tests.solve_helpers import dev, rel  # noqa: F401
+from tests.torque_helpers import held, layer, same
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+E_ARG, E_STATE = -1, -3
+STEPS = 40
+ONE, TWO = 0.0395, 0.0795
+COLLISION, SHIFT = 32, 8
+SENTINEL = -7.0
+B, K = 3, 3
+RY_FREG = 52                              # the force rows of a stage reference: base 12, joint 24, acc 12, swing 4, then f_reg 12
+
+
+def controller(dev, L=None, batch=1, n_nodes=None, tree=True):
+    """a gravity_share controller: articulated on layer L with x0's momentum from the tree (tree=False: from the declared map,
+    the state an articulated controller starts in), or declared without a layer"""
+    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
+    kw = dict(momentum_model="articulated", torque_layer=L) if L is not None else {}
+    mpc = LocomotionMPC(print_info=False, device=dev, batch=batch, n_nodes=n_nodes, force_reference="gravity_share", **kw)
+    if L is not None and tree:
+        mpc.set_state_momentum("tree")
+    return mpc
+
+
+def standing(batch, seed=None, moving=0.0):
+    """standing starts [batch, 18] at Q_HOME (seed: + N(0, 0.03) on the joints and a small attitude; moving: the scale of v0),
+    as float32 values"""
+    from iterative_learning_nmpc_amd import wholebody as wbk
+    q = np.zeros((batch, 18)); q[:, 2] = 0.30; q[:, 6:] = wbk.Q_HOME
+    v = np.zeros((batch, 18))
+    if seed is not None:
+        rng = np.random.default_rng(seed)
+        q[:, 3:6] = rng.normal(0, 0.05, (batch, 3)); q[:, 6:] += rng.normal(0, 0.03, (batch, 12))
+        v = rng.normal(0, moving, (batch, 18))
+    return q.astype(np.float32).astype(np.float64), v.astype(np.float32).astype(np.float64)
+
+
+class Rig:
+    """a controller of `batch_max` problems at N = 30 with its device solver and tables, and one replan of nmpc_wb_rollout_batch
+    through the C call itself, so that the flags a rollout comes with can be given"""
+    def __init__(self, dev, m=None, batch_max=16, tree=True):
+        self.m, self.L = m, (layer(m) if m is not None else None)
+        self.mpc = mpc = controller(dev, self.L, batch=batch_max, n_nodes=30, tree=tree)
+        assert mpc.replanning_steps == STEPS
+        self.s = s = mpc.solver._device_solver()
+        self.npc = mpc.contact_planner.nodes_per_cycle
+        self.gait, self.peaks = (s.to_device(t, torch.int8) for t in (mpc.contact_planner.gait_sequence, mpc.contact_planner.peak_swing))
+        self.joint_ref = s.to_device(mpc.joint_ref)
+        c, g = mpc.config_opt, mpc.config_gait
+        self.common = dict(nodes_per_cycle=self.npc, sim_dt=mpc.sim_dt, time_horizon=c.time_horizon, nom_height=g.nom_height,
+                           height_offset=mpc.height_offset, step_height=float(g.step_height), force_reference_gravity=1)
+        self.nlp_tol = c.nlp_tol
+
+    def replan(self, q, v, node=0, failed=None, terminate_mask=0, max_sqp_first=None, A=None, label_layer=None, v_des=(0.2, 0.0, 0.0)):
+        """one first-solve replan from states q, v [M, 18] (numpy or device) at `node`; A [M, STEPS, 12]: labels attached
+        -> dict(X, U, status, failed, q, v)"""
+        from iterative_learning_nmpc_amd._lib import NmpcWbRolloutCfg, check, ptr, stream
+        from iterative_learning_nmpc_amd.config import COLLISION_HEIGHT, N_SQP_FIRST
+        from iterative_learning_nmpc_amd.solver import _cfg
+        s, mpc = self.s, self.mpc
+        q, v = (t.clone() if isinstance(t, torch.Tensor) else s.to_device(np.asarray(t)) for t in (q, v))
+        M = q.shape[0]
+        z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=s.device)      # noqa: E731
+        X, U, status, S = z(M, 31, 42), z(M, 30, 30), z(M, dtype=torch.int32), z(M, STEPS, 44)
+        failed = z(M, dtype=torch.int32) if failed is None else s.to_device(failed, torch.int32)
+        v_des, w_des, ref = s.to_device(np.tile(v_des, (M, 1)), torch.float64), z(M, 3, dtype=torch.float64), z(M, 12, dtype=torch.float64)
+        c = _cfg(NmpcWbRolloutCfg, dict(self.common, n_replans=1, replanning_steps=STEPS, first_solve=1, last_node=0,
+                                        max_sqp_first=N_SQP_FIRST if max_sqp_first is None else max_sqp_first,
+                                        nlp_tol_first=self.nlp_tol / 10.0, nlp_tol=self.nlp_tol, push_start=0.0, push_duration=0.0,
+                                        record_sim_steps=1, nominal_period=float(mpc.config_gait.nominal_period),
+                                        terminate_mask=terminate_mask, collision_height=float(COLLISION_HEIGHT)))
+        nodes = (ctypes.c_int * 1)(node)
+        if A is not None:
+            s.set_rollout_actions(self.L if label_layer is None else label_layer, s.to_device(mpc.id_repeat[:STEPS], torch.int32), A,
+                                  mpc.Kp, mpc.Kd)
+        try:
+            check(s.lib.nmpc_wb_rollout_batch(s._h, M, ctypes.byref(c), ptr(self.gait), ptr(self.peaks), ctypes.cast(nodes, ctypes.c_void_p),
+                                              ptr(q), ptr(v), ptr(v_des), ptr(w_des), ptr(ref), ptr(self.joint_ref), None, ptr(X), ptr(U),
+                                              ptr(S), ptr(status), ptr(failed), stream(s.device)), s._h, "nmpc_wb_rollout_batch")
+        finally:
+            if A is not None:
+                s.set_rollout_actions(None)
+        torch.cuda.synchronize()
+        return dict(X=X, U=U, status=status, failed=failed, q=q, v=v)
+
+    def x0(self, M):
+        return np.stack([self.s.debug_rollout_problem(b)[0] for b in range(M)])
+
+
+@pytest.fixture(scope="module")
+def trees():
+    return {"plain": mr.tree_model(quadruped_tree()), "tilted": mr.tree_model(quadruped_tree(seed=4, perturb=0.1))}
+
+
+@pytest.fixture(scope="module")
+def rig(dev, trees):
+    """the tilted tree in tree mode: shared by the x0 and the label tests"""
+    return Rig(dev, trees["tilted"])
+
+
+# ---- 1. the switch ------------------------------------------------------------------------------------------------------------------
+def test_switch_semantics(dev, trees):
+    from iterative_learning_nmpc_amd._lib import NmpcError
+    L = layer(trees["plain"])
+    q0, v0 = standing(1)
+    fresh = controller(dev)
+    S0 = fresh.open_loop_device(q0, v0, ONE)
+    X0 = fresh._X_dev.clone()
+    # a declared handle: no tree to take the momentum from; an unknown source
+    mpc = controller(dev)
+    s = mpc.solver._device_solver()
+    assert s.state_momentum == "declared"
+    assert s.lib.nmpc_wb_set_state_momentum(s._h, 1) == E_STATE and b"articulated" in s.lib.nmpc_last_error(s._h)
+    assert s.lib.nmpc_wb_set_state_momentum(s._h, 2) == E_ARG
+    with pytest.raises(NmpcError):
+        s.set_state_momentum("tree")
+    with pytest.raises(ValueError):
+        s.set_state_momentum("articulated")
+    assert s.state_momentum == "declared"
+    # a visit to the articulated mode with x0 from the tree: the rollout runs, and is another one
+    s.set_momentum_model("articulated", torque_layer=L)
+    s.set_state_momentum("tree")
+    assert s.state_momentum == "tree"
+    St = mpc.open_loop_device(q0, v0, ONE)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(St).all()) and not same(St, S0)
+    # set_momentum_model in either direction puts the source back: articulated -> articulated refuses the rollout again ...
+    s.set_momentum_model("articulated", torque_layer=L)
+    assert s.state_momentum == "declared"
+    mpc.reset()
+    with pytest.raises(NmpcError, match="declared map"):
+        mpc.open_loop_device(q0, v0, ONE)
+    # ... and articulated -> declared leaves a handle that cannot be given the tree's x0, and that computes what a fresh one does
+    s.set_state_momentum("tree")
+    s.set_momentum_model("declared")
+    assert s.state_momentum == "declared"
+    assert s.lib.nmpc_wb_set_state_momentum(s._h, 1) == E_STATE
+    mpc.reset()
+    S1 = mpc.open_loop_device(q0, v0, ONE)
+    torch.cuda.synchronize()
+    assert same(S1, S0) and same(mpc._X_dev, X0)
+    # the controller: constructed articulated it refuses as before, with the source it does not, and the way back refuses again
+    art = controller(dev, L, tree=False)
+    assert art.state_momentum == "declared"
+    with pytest.raises(RuntimeError, match="declared map"):
+        art.open_loop_device(q0, v0, ONE)
+    art.set_state_momentum("tree")
+    assert art.state_momentum == art.solver.state_momentum == art.solver._device_solver().state_momentum == "tree"
+    assert same(art.open_loop_device(q0, v0, ONE), St)
+    art.set_state_momentum("declared")
+    art.reset()
+    with pytest.raises(RuntimeError, match="declared map"):
+        art.open_loop_device(q0, v0, ONE)
+
+
+# ---- 2. x0 of a rollout ---------------------------------------------------------------------------------------------------------------
+def test_x0_of_a_rollout_carries_the_momentum_of_the_tree(dev, rig, trees):
+    from iterative_learning_nmpc_amd import wholebody as wbm
+    from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT
+    m = trees["tilted"]
+    q, v = standing(B, seed=7, moving=0.3)
+    out = rig.replan(q, v)
+    x0 = rig.x0(B)
+    ref = np.stack([cr.crba(m, q[b], v[b])[2] for b in range(B)])
+    f32 = np.stack([cr.crba(m, q[b], v[b], np.float32)[2] for b in range(B)])
+    assert held("x0 h of a rollout", x0[:, 36:].astype(np.float64), ref, f32)
+    declared_map = np.stack([wbm.centroidal_momentum(q[b], v[b], 15.0, [0.11, 0.27, 0.33]) for b in range(B)])
+    gap = np.abs(x0[:, 36:] - declared_map).max()
+    print(f"  largest |h_tree - h_declared| of x0: {gap:.3e}")
+    assert gap > 1e-2
+    assert not np.isin(out["status"].cpu().numpy(), (1, 4)).any()
+    # slots 0..35 are the prepare kernel's: the bits of a declared handle's x0
+    dec = Rig(dev, None, batch_max=B)
+    dec.replan(q, v)
+    x0d = dec.x0(B)
+    assert np.array_equal(x0[:, :36].view(np.int32), x0d[:, :36].view(np.int32))
+    assert np.abs(x0d[:, 36:] - declared_map).max() < 1e-5
+    # node 0 of the guess carries the same six values: a replan that takes no SQP iteration leaves X as it was prepared
+    cold = rig.replan(q, v, max_sqp_first=0)
+    assert np.array_equal(rig.x0(B).view(np.int32), x0.view(np.int32))
+    assert np.array_equal(cold["X"][:, 0].cpu().numpy().view(np.int32), x0.view(np.int32))
+    assert bool((cold["X"][:, 1:] == 0).all())
+    # a rollout that terminated before the call is skipped: its x0 keeps the bits it had, the others are new
+    q2, v2 = standing(B, seed=8, moving=0.3)
+    flags = [0, COLLISION | (1 << SHIFT), 0]
+    assert TERMINATE_DEFAULT & COLLISION
+    rig.replan(q2, v2, failed=flags, terminate_mask=TERMINATE_DEFAULT)
+    x1 = rig.x0(B)
+    assert np.array_equal(x1[1].view(np.int32), x0[1].view(np.int32))
+    ref2 = np.stack([cr.crba(m, q2[b], v2[b])[2] for b in (0, 2)])
+    f32_2 = np.stack([cr.crba(m, q2[b], v2[b], np.float32)[2] for b in (0, 2)])
+    assert held("x0 h of the rollouts that go on", x1[[0, 2], 36:].astype(np.float64), ref2, f32_2)
+
+
+# ---- 3. the device rollout is the host-driven loop --------------------------------------------------------------------------------------
+def test_device_rollout_equals_host_driven_open_loop(dev, trees):
+    """The articulated counterpart of test_wholebody_device_rollout_equals_host_driven_open_loop, on quadruped_tree(), T = 0.2 s,
+    both loops with the tree as the source of x0's momentum and of the mass in the force reference.  Measured on the MI355X:
+    relative L2 7.0e-7 over 200 rows, last plan 1.7e-7 (the declared counterpart stands at 7e-7)."""
+    from iterative_learning_nmpc_amd import wholebody as wbk
+    L = layer(trees["plain"])
+    T = 0.2
+    q0 = np.zeros(18); q0[2] = 0.30; q0[3] = 0.05; q0[6:] = wbk.Q_HOME
+    v0 = np.zeros(18); v0[0] = 0.1
+    out = {}
+    for mode in ("host", "device"):
+        mpc = controller(dev, L)
+        mpc.set_command(np.array([0.25, 0.05, 0.0]), 0.1)
+        if mode == "host":
+            q_traj = mpc.open_loop(q0, v0, T)
+            out[mode] = (mpc.state_rows(q_traj, mpc.v_traj), mpc.current_opt_node, mpc.solver.last_node, mpc.solver.q_sol_euler.copy())
+        else:
+            S = mpc.open_loop_device(q0, v0, T)
+            torch.cuda.synchronize()
+            out[mode] = (S.cpu().numpy()[0], mpc.current_opt_node, mpc.solver.last_node, mpc.solver.q_sol_euler.copy())
+            assert int(mpc.failed.cpu().numpy()[0] & 0xFF & ~16) == 0
+    (Sh, nh, lh, qh), (Sd, nd, ld, qd) = out["host"], out["device"]
+    assert Sh.shape == Sd.shape and Sh.shape[1] == 44 and Sh.shape[0] >= 200
+    assert (nh, lh) == (nd, ld), ((nh, lh), (nd, ld))                        # same float clock, same replanning nodes
+    assert np.array_equal(Sd[:, 0], Sh[:, 0].astype(np.float32))               # gait phase
+    e, ep = rel(Sd, Sh), rel(qd, qh)
+    print(f"articulated device rollout vs host-driven open_loop: rel-L2 {e:.2e} over {Sh.shape[0]} rows, last plan {ep:.2e}, "
+          f"lowest base height {Sd[:, 19].min():.4f} m")
+    assert e < 2e-5, e
+    assert ep < 2e-5, ep
+    assert Sd[:, 19].min() > 0.22                                              # it stays up
+
+
+# ---- 4. the mass of the tree --------------------------------------------------------------------------------------------------------------
+def test_force_reference_and_push_take_the_mass_of_the_tree(dev):
+    """every mass of the tree x 1.2: the weight share of the force reference is 1.2 x, the velocity jump of a push 1 / 1.2 x.
+    fp32 rounding: the two sums of masses, the product with g, the share, the quotient F dt / m and the sum with the plan's
+    velocity are a handful of roundings of 6e-8 each, inside the 1e-6 the comparison allows."""
+    q0, v0 = standing(2)
+    force = np.array([[0.0, 0.0, 0.0], [60.0, 0.0, 0.0]])
+    got = {}
+    for scale in (1.0, 1.2):
+        t = {k: np.array(x, copy=True) for k, x in quadruped_tree().items()}
+        t["mass"] = t["mass"] * scale
+        L = layer(mr.tree_model(t))
+        mpc = controller(dev, L, batch=2)
+        mpc.open_loop_device(q0, v0, ONE, push=dict(start=0.0, duration=0.04, force=force))
+        torch.cuda.synchronize()
+        yref = mpc.solver._device_solver().debug_rollout_problem(0)[1].astype(np.float64)
+        fz = yref[:, RY_FREG + 2:RY_FREG + 12:3]                               # [N, 4]
+        v = mpc.v_final.cpu().numpy().astype(np.float64)
+        got[scale] = (fz, v[1, :3] - v[0, :3], L.tree_mass)
+    (fz1, jump1, m1), (fz2, jump2, m2) = got[1.0], got[1.2]
+    stance = np.nonzero((fz1 > 0).all(axis=1))[0]
+    assert len(stance) > 0, "no four-foot stance node in the window"
+    k = int(stance[0])
+    assert np.allclose(fz1[k], 9.81 * m1 / 4, rtol=1e-6), (fz1[k], m1)        # a quarter of the tree's weight, not of the declared 15 kg
+    e_f = np.abs(fz2[k] / (1.2 * fz1[k]) - 1).max()
+    e_v = abs(jump2[0] * 1.2 / jump1[0] - 1)
+    print(f"  tree mass {m1:.6f} -> {m2:.6f}: force rows of node {k} {fz1[k][0]:.5f} -> {fz2[k][0]:.5f} (off 1.2 by {e_f:.1e}), "
+          f"velocity jump {jump1[0]:.6f} -> {jump2[0]:.6f} (off 1 / 1.2 by {e_v:.1e})")
+    assert abs(jump1[0] - 60.0 * 0.04 / m1) < 1e-6 * jump1[0] and np.abs(jump1[1:]).max() < 1e-7
+    assert e_f <= 1e-6 and e_v <= 1e-6
+
+
+# ---- 5. labels ------------------------------------------------------------------------------------------------------------------------
+def label(rig, Q, V, node, failed=None, A=None, status=None, X=None, U=None):
+    from iterative_learning_nmpc_amd.config import N_SQP_FIRST, TERMINATE_DEFAULT
+    s, mpc = rig.s, rig.mpc
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=s.device)      # noqa: E731
+    v_des = s.to_device(np.tile([0.2, 0.0, 0.0], (Q.shape[0], 1)), torch.float64)
+    out = s.label_states(rig.L, rig.gait, rig.peaks, s.to_device(node, torch.int32), s.to_device([0] * len(node), torch.int32), Q, V, v_des,
+                         z(Q.shape[0], 3), z(Q.shape[0], 12), rig.joint_ref, s.to_device([0], torch.int32), failed=failed, A=A, status=status,
+                         X=X, U=U, max_sqp=N_SQP_FIRST, nlp_tol=rig.nlp_tol / 10.0, kp=mpc.Kp, kd=mpc.Kd, terminate_mask=TERMINATE_DEFAULT,
+                         **rig.common)
+    torch.cuda.synchronize()
+    return out
+
+
+def test_labels_are_the_first_replan_of_a_rollout_in_tree_mode(dev, rig):
+    s = rig.s
+    q, v = standing(B * K, seed=9, moving=0.05)
+    Q, V = s.to_device(q.reshape(B, K, 18)), s.to_device(v.reshape(B, K, 18))
+    node = [0, 1, rig.npc - 1]
+    A, status, X, U = label(rig, Q, V, node)
+    # x0 of the last chunk's problems carries the tree's momentum (all nine fit one chunk)
+    ref = np.stack([cr.crba(rig.m, q[i], v[i])[2] for i in range(B * K)])
+    f32 = np.stack([cr.crba(rig.m, q[i], v[i], np.float32)[2] for i in range(B * K)])
+    assert held("x0 h of the labeller", rig.x0(B * K)[:, 36:].astype(np.float64), ref, f32)
+    Xr, Ur = X.reshape(B, K, 31, 42), U.reshape(B, K, 30, 30)
+    for k in range(K):                                         # row k of every robot: one replan at node[k] from those states
+        Ah = torch.zeros(B, STEPS, 12, dtype=torch.float32, device=s.device)
+        h = rig.replan(Q[:, k].contiguous(), V[:, k].contiguous(), node=node[k], A=Ah)
+        assert same(A[:, k], Ah[:, 0]) and same(Xr[:, k], h["X"]) and same(Ur[:, k], h["U"]), k
+        assert torch.equal(status[:, k], h["status"]), k
+    assert bool(torch.isfinite(A).all())
+    # tables with more rows than states per robot: the states are read robot by robot, the same labels
+    wideQ, wideV = (torch.full((B, K + 2, 18), float("nan"), dtype=torch.float32, device=s.device) for _ in range(2))
+    wideQ[:, :K] = Q; wideV[:, :K] = V
+    A2, status2, X2, U2 = label(rig, wideQ[:, :K], wideV[:, :K], node)
+    assert same(A2, A) and torch.equal(status2, status) and same(X2, X) and same(U2, U)
+    # chunks of B_max = 4 problems: 4 + 4 + 1, the same labels
+    A4, status4, _, _ = label(Rig(dev, rig.m, batch_max=4), Q, V, node)
+    assert same(A4, A) and torch.equal(status4, status)
+    # with the flags of a policy rollout the states behind a termination keep their sentinels: stamps 0, 2, 1
+    failed = s.to_device([0, (2 << SHIFT) | COLLISION, (1 << SHIFT) | COLLISION], torch.int32)
+    As = torch.full((B, K, 12), SENTINEL, dtype=torch.float32, device=s.device)
+    sts = torch.full((B, K), 99, dtype=torch.int32, device=s.device)
+    Xs = torch.full((B * K, 31, 42), SENTINEL, dtype=torch.float32, device=s.device)
+    Us = torch.full((B * K, 30, 30), SENTINEL, dtype=torch.float32, device=s.device)
+    label(rig, Q, V, node, failed=failed, A=As, status=sts, X=Xs, U=Us)
+    skipped = torch.zeros(B, K, dtype=torch.bool, device=s.device)
+    skipped[1, 1:] = True; skipped[2, :] = True
+    flat = skipped.reshape(-1)
+    assert bool((As[skipped] == SENTINEL).all()) and bool((sts[skipped] == 99).all())
+    assert bool((Xs[flat] == SENTINEL).all()) and bool((Us[flat] == SENTINEL).all())
+    assert same(As[~skipped], A[~skipped]) and torch.equal(sts[~skipped], status[~skipped])
+    assert same(Xs[~flat], X[~flat]) and same(Us[~flat], U[~flat])
+
+
+# ---- 6. plant mode ----------------------------------------------------------------------------------------------------------------------
+def test_plant_mode_on_the_momentum_models_layer_and_on_a_second_one(dev, trees):
+    """the state-momentum kernel keeps no workspace on the torque handle, so the plant and the labels may share the momentum
+    model's handle: that combination is not refused, and gives the bits of the run with a second layer of the same tree"""
+    from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT
+    from iterative_learning_nmpc_amd.torque import GroundContact
+    L, L2 = layer(trees["plain"]), layer(trees["plain"])
+    q0, v0 = standing(2)
+
+    def run(plant_layer):
+        mpc = controller(dev, L, batch=2)
+        assert len(mpc.replan_clock(TWO)[1]) == 2
+        S = mpc.open_loop_device(q0, v0, TWO, torque_layer=plant_layer, plant=GroundContact(), plant_substeps=2)
+        torch.cuda.synchronize()
+        return S, mpc.actions, mpc.failed
+
+    own, other, again = run(L), run(L2), run(L)
+    print("plant mode in tree mode: failed", own[2].tolist(), "base height", float(own[0][:, :, 19].min()), "..", float(own[0][:, :, 19].max()))
+    assert own[0].shape == (2, 2 * STEPS, 44) and own[1].shape == (2, 2 * STEPS, 12)
+    for a, b in ((own, other), (own, again)):
+        assert same(a[0], b[0]) and same(a[1], b[1]) and torch.equal(a[2], b[2])
+    assert bool(torch.isfinite(own[0]).all()) and bool(torch.isfinite(own[1]).all())
+    assert bool(((own[2] & TERMINATE_DEFAULT) == 0).all()) and bool(((own[2] >> SHIFT) == 0).all())
+    # it is the articulated expert that drove the plant: a declared controller's rows differ
+    dec = controller(dev, batch=2)
+    assert not same(dec.open_loop_device(q0, v0, TWO, torque_layer=L2, plant=GroundContact(), plant_substeps=2), own[0])
+
+
+# ---- 7. collection ----------------------------------------------------------------------------------------------------------------------
+def test_collect_rollouts_takes_the_controller_as_it_is(dev, trees):
+    from iterative_learning_nmpc_amd.collect import collect_rollouts
+    from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT
+    from iterative_learning_nmpc_amd.database import DeviceDatabase
+    L = layer(trees["plain"])
+    q0, v0 = standing(2, seed=11)
+    T = 0.1
+    mpc = controller(dev, L, batch=2)
+    mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
+    db = DeviceDatabase(limit=4096, device=dev)
+    err, weights, n_rows = collect_rollouts(mpc, L, db, q0, v0, T)
+    S, A = mpc.states, mpc.actions
+    Kr = S.shape[1]
+    valid = (mpc.failed & TERMINATE_DEFAULT) == 0
+    print("collect in tree mode: valid", valid.tolist(), "rows", n_rows)
+    assert Kr == 100 and valid.tolist() == [True, True] and n_rows == 2 * Kr == len(db)
+    ref = controller(dev, L, batch=2)
+    ref.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
+    Sr = ref.open_loop_device(q0, v0, T, torque_layer=L)
+    torch.cuda.synchronize()
+    assert same(S, Sr.contiguous()) and same(A, ref.actions)
+    assert torch.equal(db.tables["states"][:len(db)], S.reshape(-1, 44)) and torch.equal(db.tables["actions"][:len(db)], A.reshape(-1, 12))
