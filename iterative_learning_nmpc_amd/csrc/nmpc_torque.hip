@@ -16,10 +16,10 @@
 // a table of PD targets tracked on the plant in one launch, and the rows of the states it ran through, are
 // nmpc_torque_track.hip.inc; what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of
 // one composite-rigid-body pass -- is nmpc_torque_crba.hip.inc; the plant's second integrator, which takes the stiff contact and PD
-// terms implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; how the centroidal momentum moves with q --
-// d(A_g v)/dq, d com/dq and the bias of its time derivative -- is nmpc_torque_cmd.hip.inc; the momentum pass on the nodes of a
-// whole-body solve is nmpc_torque_momentum.hip.inc, and the momentum A_g(q) v of a plant state alone, which the device rollouts put
-// into x0, is nmpc_torque_state_momentum.hip.inc.
+// terms implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; the centroidal momentum about an anchor
+// point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
+// d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
+// momentum A_g(q) v of a plant state alone, which the device rollouts put into x0.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -358,9 +358,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_track.hip.inc"
 #include "nmpc_torque_crba.hip.inc"
 #include "nmpc_torque_implicit.hip.inc"
-#include "nmpc_torque_cmd.hip.inc"
-#include "nmpc_torque_momentum.hip.inc"
-#include "nmpc_torque_state_momentum.hip.inc"
+#include "nmpc_torque_centroidal.hip.inc"
 
 }  // namespace nmpc_torque
 
@@ -377,6 +375,8 @@ struct Torque {
     int device = 0;
     int fd_width = 32;                  // robots per block of fd_kernel: fd_block_width(n), or 16 if NMPC_FD_WIDTH=16 asks for it (tools/fd_cost.py)
     int ct_width = 32;                  // robots per block of contact_step_kernel: ct_block_width(n)
+    int anchor = -1;                    // the centroidal kernels' reference frame: the first joint whose body has mass (-1: the tree has none)
+    unsigned chain = 0;                 // bit i: joint i is the anchor or one of its ancestors
     float* act = nullptr;               // [act_rows][nu]: the actions of nmpc_policy_rollout_batch when its caller keeps none
     int act_rows = 0;
     struct {                            // nmpc_policy_rollout_set_states: the plant states beside a policy rollout (Q == nullptr: none)
@@ -418,55 +418,55 @@ const char* step_refusal(int n_sub, float dt) {
 // the tree of the whole-body model, whose state layout the observation and the plan labels read
 bool whole_body_tree(const Model& m) { return m.n == 18 && m.nu == 12 && m.nf == 4; }
 
+// more than the default 64 KB of LDS per block for a kernel: up to `bytes`
+#define LDS_LIMIT(kernel, bytes) \
+    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
+
 // the device side of nmpc_torque_create, on the handle's device; what was allocated before an error is nmpc_torque_destroy's to free
 int allocate(Torque* t) {
     NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&t->dev), sizeof(Model)));
     NMPC_TRY(no_handle, hipMemcpy(t->dev, &t->host, sizeof(Model), hipMemcpyHostToDevice));
-    // more than the default 64 KB of LDS per block
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(id_torques_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)id_lds_bytes(MAXJ)));
-    // the forward dynamics' slice: the most its instantiation can be asked for (25 joints x 32 robots, 32 joints x 16)
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(fd_kernel, t->fd_width)),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(t->fd_width == 32 ? fd_lds_bytes(25, 32) : fd_lds_bytes(MAXJ, 16))));
-    // the contact plant: the kinematics slice of the largest tree, and the most the step's instantiation can be asked for by its
-    // own width rule (ct_block_width: ct_wide_joints() joints x 32 robots, the largest tree x 16)
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(foot_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)fk_lds_bytes(MAXJ)));
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width)),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
-    // the tracked chain of contact steps: the step's slice and width
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_track_kernel, t->ct_width)),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
-    // the pushed substeps of either: the same slice
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_AT_WIDTH(contact_push_kernel, t->ct_width)),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16))));
-    // the composite-inertia pass: the slice of the largest tree at its one width
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(crba_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)crba_lds_bytes(MAXJ, CR_W)));
-    // the implicit plant step: the slice and the triangle of the largest tree at its one width
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(contact_implicit_kernel<IM_W>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)im_lds_bytes(MAXJ)));
-    // the momentum derivatives: the slice of the largest tree at its one width
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(cmd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)cmd_lds_bytes(MAXJ, CD_W)));
-    // the momentum pass of the whole-body solve: the same slice
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(wb_momentum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)cmd_lds_bytes(MAXJ, MM_W)));
-    // the momentum of a plant state: its own, smaller slice of the largest tree at its one width
-    NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(state_momentum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)sm_lds_bytes(MAXJ, SM_W)));
+    // inverse dynamics: the slice of the largest tree; forward dynamics: the most its instantiation can be asked for (25 joints x 32
+    // robots, 32 joints x 16)
+    LDS_LIMIT(id_torques_kernel, id_lds_bytes(MAXJ));
+    LDS_LIMIT(KERNEL_AT_WIDTH(fd_kernel, t->fd_width), t->fd_width == 32 ? fd_lds_bytes(25, 32) : fd_lds_bytes(MAXJ, 16));
+    // the contact plant: the kinematics slice of the largest tree, and for the step, the tracked chain of steps and the pushed substeps
+    // of either the most an instantiation can be asked for by the step's width rule (ct_block_width: ct_wide_joints() joints x 32
+    // robots, the largest tree x 16)
+    LDS_LIMIT(foot_kernel, fk_lds_bytes(MAXJ));
+    const size_t ct_lds = t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16);
+    LDS_LIMIT(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width), ct_lds);
+    LDS_LIMIT(KERNEL_AT_WIDTH(contact_track_kernel, t->ct_width), ct_lds);
+    LDS_LIMIT(KERNEL_AT_WIDTH(contact_push_kernel, t->ct_width), ct_lds);
+    // the composite-inertia pass, the implicit plant step (slice and triangle) and the three entry points of the centroidal kernel:
+    // the slice of the largest tree at the one width each has
+    LDS_LIMIT(crba_kernel, crba_lds_bytes(MAXJ, CR_W));
+    LDS_LIMIT(contact_implicit_kernel<IM_W>, im_lds_bytes(MAXJ));
+    LDS_LIMIT(centroidal_kernel<CmdIo>, centroidal_lds_bytes<CmdIo>(MAXJ));
+    LDS_LIMIT(centroidal_kernel<NodeRecordIo>, centroidal_lds_bytes<NodeRecordIo>(MAXJ));
+    LDS_LIMIT(centroidal_kernel<StateMomentumIo>, centroidal_lds_bytes<StateMomentumIo>(MAXJ));
     return NMPC_OK;
 }
 
-// the total mass of the handle's tree: the centroidal calls refuse a tree without any
+// the total mass of the handle's tree
 float total_mass(const Model& m) {
     float total = 0.0f;
     for (int i = 0; i < m.n; ++i) total += m.mass[i];
     return total;
+}
+
+// why the centroidal quantities of the handle's tree cannot be had (nullptr: they can)
+const char* centroidal_refusal(const Torque* t) {
+    return t->anchor < 0 ? "the tree has no mass: its centre of mass is undefined" : nullptr;
+}
+
+// one entry point of the centroidal kernel on `rows` rows, about the handle's anchor
+template <class Io>
+int launch_centroidal(Torque* t, typename Io::Args p, long long rows, void* stream) {
+    p.anchor = t->anchor; p.chain = t->chain;
+    hipLaunchKernelGGL(centroidal_kernel<Io>, dim3((unsigned)((rows + CD_W - 1) / CD_W)), dim3(CD_W), centroidal_lds_bytes<Io>(t->host.n),
+                       static_cast<hipStream_t>(stream), t->dev, p);
+    return launched(t);
 }
 
 // both composite-inertia entry points: one launch of crba_kernel
@@ -695,7 +695,7 @@ const char* nmpc_torque::momentum_refusal(void* handle, int device) {
     const Torque* t = static_cast<const Torque*>(handle);
     if (!t) return "null torque handle";
     if (t->host.n != 18) return "the articulated momentum model needs a tree in the coordinates of the whole-body model: n_joints = 18";
-    if (!(total_mass(t->host) > 0.0f)) return "the tree has no mass: its centre of mass is undefined";
+    if (const char* why = centroidal_refusal(t)) return why;
     if (device >= 0 && t->device != device) return "the torque handle lives on another device";
     return nullptr;
 }
@@ -707,16 +707,10 @@ int nmpc_torque::momentum_records(void* handle, int B, int N, int shift, const f
     Torque* t = static_cast<Torque*>(handle);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
     if (const char* why = momentum_refusal(handle, -1)) return fail(t, NMPC_E_ARG, why);
-    const Model& m = t->host;
     MomentumArgs p{};
     p.B = B; p.N = N; p.shift = shift; p.X = X; p.rec = rec; p.skip = skip_mask ? skip : nullptr; p.skip_mask = skip_mask;
     p.done = done; p.done_stride = done_stride;
-    while (!(m.mass[p.anchor] > 0.0f)) ++p.anchor;      // there is one: the total is positive
-    for (int k = p.anchor; k >= 0; k = m.parent[k]) p.chain |= 1u << k;
-    const long long threads = (long long)B * (N + 1);
-    hipLaunchKernelGGL(wb_momentum_kernel, dim3((unsigned)((threads + MM_W - 1) / MM_W)), dim3(MM_W), cmd_lds_bytes(m.n, MM_W),
-                       static_cast<hipStream_t>(stream), t->dev, p);
-    return launched(t);
+    return launch_centroidal<NodeRecordIo>(t, p, (long long)B * (N + 1), stream);
 }
 
 const char* nmpc_torque::contact_track_refusal(void* handle, const nmpc_contact_cfg* ground, int n_sub, float dt, int device) {
@@ -766,6 +760,9 @@ int nmpc_torque_create(const nmpc_tree_model* mdl, int device_id, void** handle)
     t->host = m; t->device = device_id;
     t->fd_width = fd_block_width(m.n);
     t->ct_width = ct_block_width(m.n);
+    for (int i = m.n - 1; i >= 0; --i)
+        if (m.mass[i] > 0.0f) t->anchor = i;
+    for (int k = t->anchor; k >= 0; k = m.parent[k]) t->chain |= 1u << k;
     if (const char* w = std::getenv("NMPC_FD_WIDTH"))
         if (!std::strcmp(w, "16")) t->fd_width = 16;
     if (const int rc = allocate(t)) { nmpc_torque_destroy(t); return rc; }
@@ -839,7 +836,7 @@ int nmpc_centroidal_batch(void* handle, int B, const float* q, const float* v, f
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || (!com && !h && !Ag)) return fail(t, NMPC_E_ARG, "need B >= 0, q and com, h or Ag");
     if (h && !v) return fail(t, NMPC_E_ARG, "h needs v");
-    if (!(total_mass(t->host) > 0.0f)) return fail(t, NMPC_E_ARG, "the tree has no mass: its centre of mass is undefined");
+    if (const char* why = centroidal_refusal(t)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     CrbaArgs p{};
     p.B = B; p.q = q; p.v = h ? v : nullptr; p.com = com; p.h = h; p.Ag = Ag;
@@ -853,14 +850,11 @@ int nmpc_centroidal_derivatives_batch(void* handle, int B, const float* q, const
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || !v || (!dh_dq && !dcom_dq && !hdot_bias))
         return fail(t, NMPC_E_ARG, "need B >= 0, q, v and dh_dq, dcom_dq or hdot_bias");
-    const Model& m = t->host;
-    if (!(total_mass(m) > 0.0f)) return fail(t, NMPC_E_ARG, "the tree has no mass: its centre of mass is undefined");
+    if (const char* why = centroidal_refusal(t)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     CmdArgs p{};
     p.B = B; p.q = q; p.v = v; p.dh = dh_dq; p.dcom = dcom_dq; p.bias = hdot_bias;
-    while (!(m.mass[p.anchor] > 0.0f)) ++p.anchor;      // there is one: the total is positive
-    for (int k = p.anchor; k >= 0; k = m.parent[k]) p.chain |= 1u << k;
-    return launch_step(t, cmd_kernel, CD_W, cmd_lds_bytes(m.n, CD_W), p, stream);
+    return launch_centroidal<CmdIo>(t, p, B, stream);
 }
 
 int nmpc_state_momentum_batch(void* handle, int B, const float* q, const float* v, int qv_stride, float* h, int h_stride, float* h2,
@@ -868,18 +862,15 @@ int nmpc_state_momentum_batch(void* handle, int B, const float* q, const float* 
     Torque* t = static_cast<Torque*>(handle);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
     if (B == 0) return NMPC_OK;
-    const Model& m = t->host;
     if (B < 0 || !q || !v || !h) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, h");
-    if (qv_stride < m.n) return fail(t, NMPC_E_ARG, "qv_stride must be at least n_joints");
+    if (qv_stride < t->host.n) return fail(t, NMPC_E_ARG, "qv_stride must be at least n_joints");
     if (h_stride < 6 || (h2 && h2_stride < 6)) return fail(t, NMPC_E_ARG, "h_stride and h2_stride must be at least 6");
-    if (!(total_mass(m) > 0.0f)) return fail(t, NMPC_E_ARG, "the tree has no mass: its centre of mass is undefined");
+    if (const char* why = centroidal_refusal(t)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     StateMomentumArgs p{};
     p.B = B; p.qv_stride = qv_stride; p.h_stride = h_stride; p.h2_stride = h2_stride; p.skip_mask = skip ? skip_mask : 0;
     p.q = q; p.v = v; p.h = h; p.h2 = h2; p.skip = p.skip_mask ? skip : nullptr;
-    while (!(m.mass[p.anchor] > 0.0f)) ++p.anchor;      // there is one: the total is positive
-    for (int k = p.anchor; k >= 0; k = m.parent[k]) p.chain |= 1u << k;
-    return launch_step(t, state_momentum_kernel, SM_W, sm_lds_bytes(m.n, SM_W), p, stream);
+    return launch_centroidal<StateMomentumIo>(t, p, B, stream);
 }
 
 int nmpc_foot_kinematics_batch(void* handle, int B, const float* q, const float* v, float* pos, float* vel, void* stream) {

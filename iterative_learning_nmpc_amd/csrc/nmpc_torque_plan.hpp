@@ -36,7 +36,7 @@ const char* momentum_refusal(void* handle, int device);
 // total mass of the handle's tree (a handle momentum_refusal accepts)
 float tree_mass(void* handle);
 
-// the momentum pass of one SQP iteration (nmpc_torque_momentum.hip.inc): the momentum records (nmpc_wb_momentum.hpp) of the B (N + 1)
+// the momentum pass of one SQP iteration (nmpc_torque_centroidal.hip.inc): the momentum records (nmpc_wb_momentum.hpp) of the B (N + 1)
 // nodes of the iterate X [B][N+1][42], read through the warm-start shift, into rec; launched on the caller's current device.
 // Left out, as the linearisation leaves them out: problems with skip[b] & skip_mask != 0, and, with `done` given (dev: the
 // finished flag of problem 0, that of problem b `done_stride` words further on), problems whose flag is set

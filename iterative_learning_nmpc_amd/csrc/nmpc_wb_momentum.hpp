@@ -1,6 +1,6 @@
 // nmpc_wb_momentum.hpp -- the second momentum model of the whole-body family (NMPC_WB_MOMENTUM_ARTICULATED): sizes,
 // offsets and index maps of what the articulated mode adds to nmpc_wb_layout.hpp -- the per-node momentum record that the torque
-// family's momentum pass writes (nmpc_torque_momentum.hip.inc) and the linearisation reads, the dense consistency record that the
+// family's momentum pass writes (nmpc_torque_centroidal.hip.inc) and the linearisation reads, the dense consistency record that the
 // linearisation writes and the QP kernel's prologue gathers, and the argument block both kernels take beside WbArgs.  No kernel and
 // no arithmetic on data, as nmpc_wb_layout.hpp; the declared mode uses nothing of this file.
 #pragma once

@@ -34,8 +34,12 @@ def solve_digests():
     cases = [("wb", wl.wholebody_trot(B=96, N=30, seed=1), 1), ("wb3", wl.wholebody_trot(B=40, N=25, seed=2), 3),
              ("wbfp", wl.wholebody_trot(B=24, N=30, seed=4, foot_placement=1e3), 2),
              ("c", wl.centroidal_trot(B=128, N=50, seed=1), 1), ("c3", wl.centroidal_trot(B=64, N=50, seed=2), 3)]
+    # the whole-body solve in the articulated momentum model: its iterates carry the bits of the momentum records of every node
+    cases.append(("wb3_articulated", wl.wholebody_trot(B=40, N=25, seed=3), 3))
     for name, w, sqp in cases:
         s = BatchedNmpcSolver(w.model_id, w.N, w.B, "cuda:0")
+        if name.endswith("_articulated"):
+            s.set_momentum_model("articulated", torque_layer=tilted_layer())
         s.set_model_params(w.mp); s.set_cost_weights(w.W, w.W_e, w.meta["reg"], w.meta["reg_e"]); s.set_max_iter(sqp)
         t = {k: s.to_device(getattr(w, k)) for k in ("x0", "yref", "yref_e", "params", "X", "U")}
         X, U, st, stats = s.solve(t["x0"], t["yref"], t["yref_e"], t["params"], t["X"], t["U"])
@@ -43,6 +47,14 @@ def solve_digests():
         torch.cuda.synchronize()
         out[name] = sha(X, U, st, stats)
     return out
+
+
+def tilted_layer():
+    """the torque layer of the tilted quadruped: tilted trees are where fused products show"""
+    from iterative_learning_nmpc_amd.workloads import quadruped_tree
+    from tests import wb_momentum_reference as mr
+    from tests.torque_helpers import layer
+    return layer(mr.tree_model(quadruped_tree(seed=4, perturb=0.1)))
 
 
 def carry_failed(solver):
@@ -98,7 +110,9 @@ def rollout_digests():
             parts += [S, mpc.failed.clone(), mpc.x_final, mpc.base_ref_vel_tracking, mpc.foot_pos, mpc.X, mpc.U, mpc.status]
         out[name] = sha(*parts)
     layer = BatchedTorqueLayer(**quadruped_tree())
-    for name, steps, lab in (("roll_wb_steps_labels", True, layer), ("roll_wb_plain", False, None)):
+    tilted = tilted_layer()
+    for name, steps, lab in (("roll_wb_steps_labels", True, layer), ("roll_wb_plain", False, None),
+                             ("roll_wb_articulated_labels", True, tilted)):
         B, T = 24, 0.8
         rng = np.random.default_rng(2)                   # the batch of test_wholebody_device_rollouts_batch_and_termination
         q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B, 12))
@@ -107,7 +121,10 @@ def rollout_digests():
         force[0] = 0.0
         force[1] = [0.0, 0.0, -70.0]
         q0[[4, 13], 2] = 0.5
-        mpc = LocomotionMPC(print_info=False, device="cuda:0", batch=B, n_nodes=30, force_reference="gravity_share")
+        kw = dict(momentum_model="articulated", torque_layer=tilted) if lab is tilted else {}
+        mpc = LocomotionMPC(print_info=False, device="cuda:0", batch=B, n_nodes=30, force_reference="gravity_share", **kw)
+        if lab is tilted:
+            mpc.set_state_momentum("tree")      # x0's momentum from the tree: one state-momentum launch behind every prepare kernel
         mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
         carry_failed(mpc.solver._device_solver())
         parts = []
@@ -155,6 +172,20 @@ def torque_digests():
                 add("pd_torques", L.compute_pd_torques(q, v, ff, 0.5 * q, 0.5 * v, KP, KD))
                 add("pd_target_action", L.pd_target_action(ff, q, v, KP, KD, list(range(m.nu))[::-1]))
 
+    def centroidal(L, q, v):
+        """the composite-inertia calls (a control: another kernel) and the three entry points of the centroidal kernel"""
+        from iterative_learning_nmpc_amd._lib import check, ptr, stream
+        q, v = (torch.as_tensor(np.array(t), dtype=torch.float32, device=L.device).contiguous() for t in (q, v))
+        B = q.shape[0]
+        add("mass_matrix", L.mass_matrix(q))
+        add("centroidal", *L.centroidal(q, v, jacobian=True))
+        add("centroidal_derivatives", *L.centroidal_derivatives(q, v, com_jacobian=True, bias=True))
+        add("state_momentum", L.state_momentum(q, v))
+        rows = torch.full((2, B, 42), -7.0, dtype=torch.float32, device=q.device)      # as x0 and node 0 of X: h in slots 36..41
+        check(L.lib.nmpc_state_momentum_batch(L._h, B, ptr(q), ptr(v), L.n, ptr(rows[0, :, 36:]), 42, ptr(rows[1, :, 36:]), 42, None, 0,
+                                              stream(L.device)), L._h, "nmpc_state_momentum_batch", "torque")
+        add("state_momentum", rows)
+
     w = World()                                           # its Case is the tilted quadruped of tests/test_gpu_contact.py
     for c in (Case(fr.quadruped(), 257, seed=257), w.c):
         dynamics(c.L, c.m, 257, (257, 7))
@@ -170,6 +201,8 @@ def torque_digests():
     dynamics(L, m, 40, (6,), "_w16")
     q, v, tau, _ = fr.inputs(m, 40, 6)
     add("contact_step_w16", *L.contact_step(q, v, DT, 20, tau_ff=tau, q_des=q, kp=KP, kd=KD, ground=GroundContact(**SOFT)))
+    centroidal(w.c.L, w.c.q, w.c.v)                       # B = 257 on the tilted quadruped, B = 40 on the 30-joint tree
+    centroidal(L, q, v)
     return {k: sha(*v) for k, v in parts.items()}
 
 

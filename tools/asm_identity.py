@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Do two trees compile to the same device code?  (a refactor that claims to leave every kernel as the compiler saw it)
-    python tools/asm_identity.py <csrc dir A> <csrc dir B> [file.hip ...]        default file: nmpc_torque.hip
+    python tools/asm_identity.py [--pair OLD=NEW ...] <csrc dir A> <csrc dir B> [file.hip ...]        default file: nmpc_torque.hip
 Compiles the named files of both directories to gfx950 device assembly with the compile flags of csrc/build.sh plus
 `--cuda-device-only -S`, drops comments, directives and blank lines, numbers the local labels of each function in order of
 appearance and compares the instruction stream function by function.  One line per kernel: its instruction count and `same`
-or the number of differing lines; exit status 1 on any difference.  Each directory has to sit in its tree (the sources
+or the number of differing lines; exit status 1 on any difference.  `--pair OLD=NEW` (demangled names without their arguments,
+as the report prints them) compares function OLD of A with the differently named NEW of B, a kernel that became an instantiation
+of a template for instance; unpaired, one is reported missing and one added.  Each directory has to sit in its tree (the sources
 include ../../include); `git worktree add <dir> <commit>` gives one of another commit.  No GPU is needed."""
 import difflib, os, re, subprocess, sys, tempfile
 
@@ -36,17 +38,28 @@ def differing(a, b):
     return sum(max(i2 - i1, j2 - j1) for tag, i1, i2, j1, j2 in ops if tag != "equal")
 
 
+def demangled(k):
+    name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()
+    return re.sub(r"^void ", "", re.sub(r"\(.*", "", name))
+
+
 def main():
-    if len(sys.argv) < 3:
+    args, pairs = sys.argv[1:], {}
+    while args and args[0] == "--pair":
+        old, new = args[1].split("=", 1)
+        pairs[new], args = old, args[2:]
+    if len(args) < 2:
         sys.exit(__doc__)
-    dir_a, dir_b, files = sys.argv[1], sys.argv[2], sys.argv[3:] or ["nmpc_torque.hip"]
+    dir_a, dir_b, files = args[0], args[1], args[2:] or ["nmpc_torque.hip"]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         for f in files:
             a, b = functions(dir_a, f, tmp), functions(dir_b, f, tmp)
+            mangled = {demangled(k): k for k in a}
+            for new in [k for k in b if pairs.get(demangled(k)) in mangled]:      # NEW of B goes under OLD's mangled name
+                b[mangled[pairs[demangled(new)]]] = b.pop(new)
             for k in sorted(set(a) | set(b)):
-                name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()
-                name = re.sub(r"^void ", "", re.sub(r"\(.*", "", name))
+                name = demangled(k)
                 if k not in a or k not in b:
                     verdict = f"only in {dir_a if k in a else dir_b}"
                 else:
