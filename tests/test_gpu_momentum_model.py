@@ -67,10 +67,7 @@ def node_blocks(w, X, U, m, data):
             Wk = w.W_e if term else w.W
             n = mr.node(w.mp, X[b, k], None if term else U[b, k], w.params[b, k], w.yref_e[b] if term else w.yref[b, k], Wk,
                         "articulated", m, data)
-            r = mr.RE_CONS if term else mr.RY_CONS
-            Js = n["Js"][r:r + 6]
-            dc[b, k, :, :15] = Js[:, 3:18]; dc[b, k, :, 15:33] = Js[:, 18:36]
-            dc[b, k, :, 33] = Js[np.arange(6), 36 + np.arange(6)]; dc[b, k, :, 34] = Js[:, 42]
+            dc[b, k] = mr.reference_dense_consistency(n)[:, :35]
             if not term:
                 xn = np.asarray(X[b, k + 1], np.float32 if data == "f32" else np.float64).astype(np.float64)
                 d[b, k] = n["xn"][36:42] - xn[36:42]

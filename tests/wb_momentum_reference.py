@@ -67,7 +67,8 @@ def centroidal(m, q, v, data="f64"):
 
 def node(mp, x, u, p, yref, W, momentum="declared", m=None, data="f64"):
     """Per-node quantities at (x, u, p); u = None: the terminal node.  dict with res, J [ny, 42] (unscaled, reference subtracted),
-    Js = sqrt(W) [J | res] [ny, 43], and for a stage xn, A [42, 42], B [42, 30]."""
+    Js = sqrt(W) [J | res] [ny, 43], for a stage xn, A [42, 42], B [42, 30], and in the articulated model `centroidal`: the
+    tuple of `centroidal(m, q, v, data)`."""
     o = oracle(data)
     dt_ = np.float64 if data == "f64" else np.float32
     x = np.asarray(x, dt_).astype(np.float64); p = np.asarray(p, np.float64)
@@ -80,7 +81,7 @@ def node(mp, x, u, p, yref, W, momentum="declared", m=None, data="f64"):
         xn, A, B = (a.astype(np.float64) for a in o.dynamics(2, mp, x, u, p))
     if momentum == "articulated":
         q, v = x[WQ:WQ + 18], x[WV:WV + 18]
-        com, Ag, dh, agv = centroidal(m, q, v, data)
+        com, Ag, dh, agv = out["centroidal"] = centroidal(m, q, v, data)
         r_cs = RE_CONS if term else RY_CONS
         yr = np.asarray(yref, np.float64)
         J[r_cs:r_cs + 6] = 0.0
@@ -106,6 +107,26 @@ def node(mp, x, u, p, yref, W, momentum="declared", m=None, data="f64"):
     if not term:
         out.update(xn=xn, A=A, B=B)
     return out
+
+
+def reference_momentum_record(m, q, v, data="f64", quantities=None):
+    """the 228 floats of a node's momentum record (csrc/nmpc_wb_momentum.hpp) from `centroidal`: A_g [6][18] at 0, dh_dq [6][18]
+    at 108, A_g v [6] at 216, com [3] at 222 -- measured from the origin of the base frame, as the header states -- and three
+    floats the record does not use (zeros here; the device writes nothing there).  quantities: the tuple `centroidal` returned
+    for this (m, q, v, data) -- a node dict's "centroidal" -- instead of computing it again"""
+    com, Ag, dh, agv = centroidal(m, q, v, data) if quantities is None else quantities
+    return np.concatenate([Ag.reshape(-1), dh.reshape(-1), agv, com, np.zeros(3)])
+
+
+def reference_dense_consistency(n):
+    """[6, 36]: the scaled consistency rows of node dict `n` (of `node` in the articulated model) in the dense record's order --
+    columns q_3..q_17, v_0..v_17, the row's own momentum slot, the scaled residual -- with slot 35 zero"""
+    r = RY_CONS if "xn" in n else RE_CONS
+    Js = n["Js"][r:r + 6]
+    dc = np.zeros((6, 36))
+    dc[:, :15] = Js[:, 3:18]; dc[:, 15:33] = Js[:, 18:36]
+    dc[:, 33] = Js[np.arange(6), 36 + np.arange(6)]; dc[:, 34] = Js[:, 42]
+    return dc
 
 
 def residual_and_next(mp, x, u, p, yref, momentum, m):

@@ -6,6 +6,8 @@ Jacobian Js = sqrt(W) [J | res] (388 floats, `cj_index`), the node record of the
 images of Q~ (nine 16 x 16 tiles, column-major).  On top of it the references the device tests compare with:
 
   unpack_js / pack_js     compact record <-> Js [30, 46] in column positions
+  unpack_js_art / pack_js_art   the same in the articulated mode (csrc/nmpc_wb_momentum.hpp, restated below: `MR_*`, `DC_*`,
+                          `CJ_ART`, `cj_index_art`): the consistency rows 16..21 come from the dense consistency record
   unpack_q                tile images -> Q~ (symmetrised from the lower tiles for a running node)
   node                    tests/wb_momentum_reference.node (the frozen oracle's per-node hooks) of node (b, k) of a workload,
                           with what the record needs beside it (inputs, weights, pyramid rows)
@@ -112,6 +114,42 @@ CJ_SLOTS = CJ[CJ_ROWS, CJ_COLS]
 # the 80 record slots of the foot-placement rows 22..29
 POS_SLOTS = np.array([CJ_FOOT * f + 68 + j for f in range(4) for j in range(20)])
 
+# ---- csrc/nmpc_wb_momentum.hpp: what the articulated momentum model adds
+# the momentum record of a node: A_g [6][18], dh_dq [6][18], A_g v [6], com from the origin of the base frame [3]
+MR_AG, MR_DH, MR_AGV, MR_COM, MR_FLOATS = 0, 108, 216, 222, 228
+# the dense consistency record of a node: six rows of [q_3..q_17 (15) | v (18) | own h slot | HX | padding]
+DC_ROW, DC_V, DC_H, DC_RES = 36, 15, 33, 34
+DC_FLOATS = 6 * DC_ROW
+CJ_ART = CJ_FLOATS + 4        # where the QP prologue keeps the dense record in its record buffer, behind the zero slot
+LDU = 36                      # the record buffer is the 32 elimination columns of this stride (csrc/nmpc_wb_layout.hpp)
+
+
+def cj_index_art(row, col):
+    """record-buffer index of element (row, column POSITION) of Js in the articulated mode, or -1 for a structural zero"""
+    if row < 16 or row >= 22:
+        return cj_index(row, col)
+    i = row - 16
+    base = CJ_ART + DC_ROW * i
+    if col == HX:
+        return base + DC_RES
+    if col == pos_of(WH + i):
+        return base + DC_H
+    if WQ + 3 <= col < WQ + 18:
+        return base + (col - WQ - 3)
+    if WV <= col < WV + 18:
+        return base + DC_V + (col - WV)
+    return -1
+
+
+CJA = np.array([[cj_index_art(r, c) for c in range(XW)] for r in range(NJR)])      # the articulated map as a table [30, 46]
+_DENSE = np.zeros((NJR, XW), bool)
+_DENSE[16:22] = CJA[16:22] >= 0
+DC_ROWS, DC_COLS = np.nonzero(_DENSE)                      # positions of Js that live in the dense record ...
+DC_SLOTS = CJA[DC_ROWS, DC_COLS] - CJ_ART                  # ... and their slots in it
+_COMPACT = (CJA >= 0) & ~_DENSE
+CA_ROWS, CA_COLS = np.nonzero(_COMPACT)                    # positions that stay in the compact record (rows 0..15, 22..29)
+CA_SLOTS = CJA[CA_ROWS, CA_COLS]
+
 # the node record (float offsets)
 R_D, R_HQ, R_HF, R_CDT, R_R, R_C, R_ACT, R_COST, R_ZERO, R_DT, R_GQ, R_DT2, REC = 0, 48, 96, 132, 136, 168, 184, 185, 186, 187, 188, 224, 228
 
@@ -136,6 +174,27 @@ def pack_js(Js):
     return record
 
 
+def unpack_js_art(js_record, dcons):
+    """[..., 388] compact record and [..., 216] dense consistency record -> Js [..., 30, 46] in column positions (float64):
+    rows 0..15 and 22..29 through cj_index, rows 16..21 from the dense record"""
+    js_record, dcons = np.asarray(js_record), np.asarray(dcons)
+    Js = np.zeros(js_record.shape[:-1] + (NJR, XW))
+    Js[..., CA_ROWS, CA_COLS] = js_record[..., CA_SLOTS]
+    Js[..., DC_ROWS, DC_COLS] = dcons[..., DC_SLOTS]
+    return Js
+
+
+def pack_js_art(Js):
+    """the inverse of unpack_js_art: [..., 30, 46] -> ([..., 388], [..., 216]); zeros in the padding slots, in slot 35 of every
+    dense row and in the 36 consistency slots of the compact record, which this mode does not use"""
+    Js = np.asarray(Js)
+    record = np.zeros(Js.shape[:-2] + (CJ_FLOATS,), Js.dtype)
+    dcons = np.zeros(Js.shape[:-2] + (DC_FLOATS,), Js.dtype)
+    record[..., CA_SLOTS] = Js[..., CA_ROWS, CA_COLS]
+    dcons[..., DC_SLOTS] = Js[..., DC_ROWS, DC_COLS]
+    return record, dcons
+
+
 def unpack_q(images, term, width=XW):
     """[2304] tile images of one node -> Q~ [width, width] (float64; width 48 keeps the two unused positions).  A running node
     has its lower tiles only: the strict upper tiles are filled with their transposes.  For the terminal node all nine tiles
@@ -152,13 +211,13 @@ def unpack_q(images, term, width=XW):
 
 
 # ---------------------------------------------------------------------------------------------------------- references
-def node(w, b, k, X, U, data="f64"):
+def node(w, b, k, X, U, data="f64", momentum="declared", m=None):
     """reference quantities of node k of problem b of workload `w` at the iterate (X, U): wb_momentum_reference.node in the
-    declared model, plus the inputs the record is built from"""
+    momentum model `momentum` (tree `m` for the articulated one), plus the inputs the record is built from"""
     term = k == w.N
     yr = w.yref_e[b] if term else (w.yref[b, k] if w.yref.ndim == 3 else w.yref[b])
     Wk = np.asarray(w.W_e if term else w.W, np.float64)
-    n = mr.node(w.mp, X[b, k], None if term else U[b, k], w.params[b, k], yr, Wk, "declared", None, data)
+    n = mr.node(w.mp, X[b, k], None if term else U[b, k], w.params[b, k], yr, Wk, momentum, m, data)
     dt_ = np.float64 if data == "f64" else np.float32
     n.update(term=term, W=Wk, mp=np.asarray(w.mp, np.float64), p=np.asarray(w.params[b, k], np.float64))
     if not term:
@@ -262,11 +321,14 @@ def contract(Js, precision):
     return lo.T @ h + h.T @ lo + m.T @ m + m.T @ h + h.T @ m + h.T @ h
 
 
-def device_q_reference(js_record, gq, Wk, reg, precision):
+def device_q_reference(js_record, gq, Wk, reg, precision, dcons=None):
     """(Q_ref [46, 46], sum_rows |Js[row, r] Js[row, c]| [46, 46]) of a node from the DEVICE's own records: path `precision` of
     the contraction, + (wdiag + reg) on the state positions (one float32 sum, as the kernel holds it), + gq in row and column
-    HX, (HX, HX) = 0"""
-    Js = unpack_js(np.asarray(js_record, np.float32)).astype(np.float32)
+    HX, (HX, HX) = 0.  dcons: the node's dense consistency record -- the articulated mode, whose rows 16..21 come from it"""
+    if dcons is None:
+        Js = unpack_js(np.asarray(js_record, np.float32)).astype(np.float32)
+    else:
+        Js = unpack_js_art(np.asarray(js_record, np.float32), np.asarray(dcons, np.float32)).astype(np.float32)
     Q = contract(Js, precision)
     wd = np.zeros(NX, np.float32)
     wd[:36] = state_weights(np.asarray(Wk, np.float32))
