@@ -339,6 +339,28 @@ int nmpc_wb_rollout_set_plant(void *handle, void *torque_handle, const nmpc_cont
  * (nmpc_contact_set_push). */
 int nmpc_wb_rollout_set_plant_push(void *handle, int as_force);
 
+/* The clock of a rollout that is continued across calls [decl], per handle.  replan0 = 0 (the default, and what every rollout
+ * did before this call existed): a rollout starts at its call.  While replan0 > 0 is set, replan i of every following
+ * nmpc_wb_rollout_batch of this handle is replan replan0 + i of a longer rollout that started replan0 replanning_steps
+ * simulation steps earlier, and everything the harness forms from time is that rollout's:
+ *   the recorded phase of the rows (plan-following and, through nmpc_observe_rows_batch's t0, on the plant);
+ *   the stamp of failed[b], replan0 + i + 1 -- from the advance kernel, from the step index of the plant's observations, and
+ *     from the flags-only observation after the last replan (time (replan0 + n_replans) replanning_steps sim_dt, step index
+ *     replan0 + n_replans - 1);
+ *   the push window: push_start counts from step 0 of the long rollout, for the velocity jump (t_now = (replan0 + i)
+ *     replanning_steps sim_dt) and for the push as a force (first_substep less (replan0 + i) replanning_steps n_sub).
+ * What the call writes is its own: replan i writes the rows i rows_per_replan .. of this call's S and A, and first_solve,
+ * last_node and nodes[] stay the caller's.  Called with the q, v, ref_state, X, U and failed the previous call left, with
+ * first_solve = 0, its last node as last_node and the long rollout's nodes, a call continues a rollout bit for bit: the rows of
+ * the stretches, one after the other, are the rows of one long call -- for every rollout that is LIVE at entry.  A rollout that
+ * enters a call carrying a stamp stays frozen under the rule of the harness: its rows of that call are its frozen state q, v
+ * (phase 0), not the long call's repeated last row, and its label rows are zeros; the stamp tells a consumer where to cut.
+ * Refused with NMPC_E_ARG, a text in nmpc_last_error and the previous value left in force: a handle of another model,
+ * replan0 < 0; and, by nmpc_wb_rollout_batch before any launch, replan0 + n_replans beyond what the stamp field above
+ * NMPC_ROLLOUT_TERM_SHIFT holds (2^23 - 1).  nmpc_rollout_batch, the centroidal harness, has no clock: its replans count from
+ * its call, bit for bit as before.  nmpc_wb_rollout_cfg is unchanged. */
+int nmpc_wb_rollout_set_clock(void *handle, int replan0);
+
 /* The momentum model of a NMPC_MODEL_WHOLEBODY handle [decl], per handle; NMPC_WB_MOMENTUM_DECLARED is the default and what
  * every handle computed before this call existed.
  *   declared     A_g(q) v = [m rdot ; R I_b E(theta) thetadot]: one rigid body of mass NMPC_MP_MASS and inertia NMPC_MP_I.. whose

@@ -48,6 +48,7 @@ SIGNATURES = {
     "nmpc_wb_rollout_set_actions": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p]),
     "nmpc_wb_rollout_set_plant": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_wb_rollout_set_plant_push": (c_int, [c_void_p, c_int]),
+    "nmpc_wb_rollout_set_clock": (c_int, [c_void_p, c_int]),
     "nmpc_wb_set_momentum_model": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_wb_set_state_momentum": (c_int, [c_void_p, c_int]),
     "nmpc_set_ipm": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float]),

@@ -20,7 +20,8 @@ from .solver import tracking_error
 
 def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = None, nominal: int = 0, ood_weight: float = 5.0,
                      terminate_mask: int = TERMINATE_DEFAULT, kp: Optional[float] = None, kd: Optional[float] = None, plant=None,
-                     plant_substeps: int = 2, push_as_force: bool = False, integrator: Optional[str] = None):
+                     plant_substeps: int = 2, push_as_force: bool = False, integrator: Optional[str] = None,
+                     chunk_replans: Optional[int] = None):
     """One batch of whole-body expert rollouts of `T` seconds into `db`.
 
     mpc: a `LocomotionMPC` (batch B, command set); layer: the robot's `BatchedTorqueLayer`; db: a `DeviceDatabase` with
@@ -36,12 +37,40 @@ def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = No
     plant): the push is a force on the plant's trunk instead of a velocity jump per replanning interval.  integrator (with
     plant): the plant's integrator, as `open_loop_device` takes it (None: as the layer is set).
     After the call `mpc.actions`, `mpc.failed` and the returned S of the rollout are as `open_loop_device` leaves them
-    (`mpc.states` keeps S)."""
-    S = mpc.open_loop_device(q0, v0, T, push=push, record_sim_steps=True, terminate_mask=terminate_mask, torque_layer=layer,
-                             kp=kp, kd=kd, plant=plant, plant_substeps=plant_substeps, push_as_force=push_as_force,
-                             integrator=integrator).contiguous()
+    (`mpc.states` keeps S).
+    chunk_replans (None: one call, as above): the rollout runs as stretches of `chunk_replans` replans, the last one shorter --
+    the first a cold start, the others `open_loop_device(resume=True)` from the state the one before left --, and each
+    stretch's rows, labels and weights are appended before the next one runs, so that S and the labels are never larger than
+    one stretch (`mpc.states`, `mpc.actions`: the last one's).  The replans are those the one call makes for `T`, all of them
+    whole intervals: where `T` ends inside an interval, the stretches run it to its end.  The rows of a stretch are those of the
+    one call, bit for bit, and so are their errors and weights (the nominal rollout is in every stretch); the database
+    holds them stretch by stretch, within a stretch in rollout order.  A stretch appends the rollouts that are valid at its
+    end: a rollout that terminates contributes nothing from that stretch on -- no row at or beyond its stamp -- but keeps the
+    stretches before it, which the one call, seeing the whole rollout invalid, leaves out.  err and weights are the
+    stretches' side by side, [B, K]."""
+    run = dict(push=push, record_sim_steps=True, terminate_mask=terminate_mask, torque_layer=layer, kp=kp, kd=kd, plant=plant,
+               plant_substeps=plant_substeps, push_as_force=push_as_force, integrator=integrator)
+    if chunk_replans is None:
+        S = mpc.open_loop_device(q0, v0, T, **run).contiguous()
+        mpc.states = S
+        return _append_valid(mpc, db, S, nominal, ood_weight, terminate_mask)
+    if int(chunk_replans) < 1:
+        raise ValueError("chunk_replans must be at least 1")
+    total = len(mpc.replan_clock(T)[1])
+    q, v, done, parts = q0, v0, 0, []
+    while done < total:
+        k = min(int(chunk_replans), total - done)
+        S = mpc.open_loop_device(q, v, None, n_replans=k, resume=done > 0, **run).contiguous()
+        mpc.states = S
+        parts.append(_append_valid(mpc, db, S, nominal, ood_weight, terminate_mask))
+        q, v, done = mpc.q_final, mpc.v_final, done + k
+    return torch.cat([p[0] for p in parts], 1), torch.cat([p[1] for p in parts], 1), sum(p[2] for p in parts)
+
+
+def _append_valid(mpc, db, S, nominal: int, ood_weight: float, terminate_mask: int):
+    """the rows S [B, K, 44] of the rollout (or stretch) `mpc` has just run, with `mpc.actions` and their weights, into `db`
+    -> (err, weights, rows appended) of `collect_rollouts`"""
     A = mpc.actions
-    mpc.states = S
     B, K = S.shape[:2]
     threshold = ood_threshold(S.shape[2])                     # 4.0 on the 44-slot row: the reference's number, no mapping
     err, _ = tracking_error(S, S[nominal].contiguous(), threshold=threshold, ood_weight=ood_weight)

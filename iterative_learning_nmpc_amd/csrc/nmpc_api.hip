@@ -2,6 +2,7 @@
 // Single translation unit: kernels are included below.  Build: csrc/build.sh (hipcc, gfx950).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -61,6 +62,7 @@ struct Handle {
         int state_source = NMPC_WB_STATE_MOMENTUM_DECLARED;   // nmpc_wb_set_state_momentum: where the momentum of a measured state comes from
     } momentum;
     bool plant_push_as_force = false;   // nmpc_wb_rollout_set_plant_push: a plant-mode rollout pushes with a force on the plant, not a velocity jump
+    int rollout_replan0 = 0;            // nmpc_wb_rollout_set_clock: replan i of a whole-body rollout is replan rollout_replan0 + i of a longer one
     bool ws_dirty = false;   // a dense-LQ call left foreign padding in the tile workspace
     bool mp_set = false, w_set = false;
     nmpc::ModelParams mp{};
@@ -279,9 +281,11 @@ int read_tile(Handle* h, int b, int k, int which, float* out) {
 // all on the caller's stream.  r: the plant's kernel arguments, its own fields, the carve-up of h->roll and the caller's pointers
 // filled in; a: the arguments of its solve with x0 and status.  plan(i) sets what the plant alone knows of replan i (its node)
 // and returns the warm-start shift of its solve; after_prepare() runs between the prepare kernel and the solve, after_solve(i)
-// between the solve and the advance kernel.
+// between the solve and the advance kernel.  replan0: where replan 0 of this call sits in the rollout (nmpc_wb_rollout_set_clock; the
+// centroidal harness passes 0) -- replan i has the time, the push window and the stamp of replan replan0 + i and writes the rows
+// i * rows_per_replan .. of this call's S.
 template <class Cfg, class R, class A, class Plan, class AfterPrepare, class AfterSolve>
-int run_rollout(Handle* h, int B, const Cfg* cfg, hipStream_t st, R& r, A& a, void (*prepare)(const R),
+int run_rollout(Handle* h, int B, const Cfg* cfg, int replan0, hipStream_t st, R& r, A& a, void (*prepare)(const R),
                 int (*solve)(Handle*, A, hipStream_t), void (*advance)(const R), Plan plan, AfterPrepare after_prepare,
                 AfterSolve after_solve) {
     NMPC_ENTER(h, h->device);
@@ -302,11 +306,11 @@ int run_rollout(Handle* h, int B, const Cfg* cfg, hipStream_t st, R& r, A& a, vo
     for (int i = 0; i < cfg->n_replans; ++i) {
         const bool cold = cfg->first_solve && i == 0;
         r.first = cold ? 1 : 0;
-        r.replan_index = i;
+        r.replan_index = replan0 + i;
         r.row0 = i * rows_per_replan;
         // the push window in replanning intervals, half a simulation step of slack on both ends: with plain float compares
         // 5 * 0.04f = 0.19999999 misses a window that starts at 0.2 (the host loop, in doubles, does not)
-        const double t_now = i * dt_replan;
+        const double t_now = (replan0 + i) * dt_replan;
         r.push_dt = (r.push_force && cfg->push_duration > 0.0f && t_now >= (double)cfg->push_start - slack &&
                      t_now < (double)cfg->push_start + (double)cfg->push_duration - slack) ? (float)dt_replan : 0.0f;
         const int shift = plan(i);
@@ -541,6 +545,15 @@ int nmpc_wb_rollout_set_plant_push(void* handle, int as_force) {
     return NMPC_OK;
 }
 
+int nmpc_wb_rollout_set_clock(void* handle, int replan0) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_wb_rollout_set_clock needs the whole-body model");
+    if (replan0 < 0) return fail(h, NMPC_E_ARG, "rollout clock: replan0 must not be negative");
+    h->rollout_replan0 = replan0;
+    return NMPC_OK;
+}
+
 int nmpc_set_ipm(void* handle, float mu0, float sigma, float s_min, float gamma, float tau_min,
                  float merit_rho) {
     Handle* h = static_cast<Handle*>(handle);
@@ -677,7 +690,7 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
     r.foot_size = cfg->foot_size;
     nmpc::SolveArgs a = base_args(h);
     a.x0 = x; a.status = status;
-    return run_rollout(h, B, cfg, static_cast<hipStream_t>(stream), r, a, nmpc::nmpc_rollout_prepare_kernel,
+    return run_rollout(h, B, cfg, 0, static_cast<hipStream_t>(stream), r, a, nmpc::nmpc_rollout_prepare_kernel,
                        launch_solve<nmpc::Centroidal>, nmpc::nmpc_rollout_advance_kernel,
                        [&](int i) {
                            r.node = cfg->start_node + i * cfg->nodes_per_replan;
@@ -704,6 +717,10 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
     if (const int rc = check_configured(h)) return rc;
     if (h->line_search) return fail(h, NMPC_E_ARG, "the whole-body model takes full steps (line_search = 0)");
     const int N = h->dims.N;
+    // the clock of a continued rollout (nmpc_wb_rollout_set_clock): the stamp of its last replan must fit above the flag bits
+    const int replan0 = h->rollout_replan0;
+    if ((long long)replan0 + cfg->n_replans > (long long)(0x7fffffff >> NMPC_ROLLOUT_TERM_SHIFT))
+        return fail(h, NMPC_E_ARG, "rollout clock: replan0 + n_replans exceeds the stamp field of failed[b]");
     if (cfg->replanning_steps * cfg->sim_dt > cfg->time_horizon) return fail(h, NMPC_E_ARG, "replanning interval longer than the horizon");
     for (int i = 0; i < cfg->n_replans; ++i)
         if (nodes[i] < 0 || (i > 0 && nodes[i] < nodes[i - 1])) return fail(h, NMPC_E_ARG, "nodes must be non-negative and non-decreasing");
@@ -759,7 +776,7 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
     w.x0 = r.x0; w.status = status;
     int last_node = cfg->last_node;
     const int rc = run_rollout(
-        h, B, cfg, st, r, w, nmpc::wb::nmpc_wb_rollout_prepare_kernel, launch_wb, nmpc::wb::nmpc_wb_rollout_advance_kernel,
+        h, B, cfg, replan0, st, r, w, nmpc::wb::nmpc_wb_rollout_prepare_kernel, launch_wb, nmpc::wb::nmpc_wb_rollout_advance_kernel,
         [&](int i) {          // warm_start_solver(i_node): start_node = i_node - last_node (solver.py:304-309)
             const int shift = nodes[i] - last_node;
             r.node = last_node = nodes[i];
@@ -788,9 +805,11 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
             // the expert drives the plant: the label rows as PD targets of `steps` simulation steps, the states before each step
             // into the workspace, and those states as rows row0 .. of S with their flags (no stamp: the advance kernel stamps)
             int trc;
-            if (force_push) {                      // this replan's substeps start at substep i steps n_sub of the rollout
+            if (force_push) {                      // this replan's substeps start at substep (replan0 + i) steps n_sub of the rollout
                 nmpc_push_cfg push = plant_push;
-                push.first_substep -= i * steps * pl.n_sub;
+                // (a window that lies wholly before them, however far, starts n_substeps before: the int holds it)
+                const long long first = (long long)push.first_substep - (long long)(replan0 + i) * steps * pl.n_sub;
+                push.first_substep = (int)std::max(first, -(long long)push.n_substeps);
                 trc = nmpc_torque::contact_track_pushed(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
                                                         rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, push, st);
             } else {
@@ -798,17 +817,17 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
                                                rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, st);
             }
             if (trc) return fail(h, trc, std::string("nmpc_contact_track_batch: ") + nmpc_torque_last_error(pl.torque));
-            const int orc = nmpc_observe_rows_batch(pl.torque, B, steps, pl.Qw, pl.Vw, steps, (double)(i * steps) * cfg->sim_dt, cfg->sim_dt,
+            const int orc = nmpc_observe_rows_batch(pl.torque, B, steps, pl.Qw, pl.Vw, steps, (double)((long long)(replan0 + i) * steps) * cfg->sim_dt, cfg->sim_dt,
                                                     (double)cfg->nominal_period, cfg->collision_height, S + (size_t)r.row0 * 44, r.n_rows,
-                                                    failed, i, 0, skip, r.term_mask, st);
+                                                    failed, replan0 + i, 0, skip, r.term_mask, st);
             if (orc) return fail(h, orc, std::string("nmpc_observe_rows_batch: ") + nmpc_torque_last_error(pl.torque));
             return (int)NMPC_OK;
         });
     if (rc || !pl.torque) return rc;
     // the state the last interval left: a robot that fell in it is flagged and stamped with the last replan
-    const int frc = nmpc_observe_batch(pl.torque, B, q, v, (double)(cfg->n_replans * cfg->replanning_steps) * cfg->sim_dt,
+    const int frc = nmpc_observe_batch(pl.torque, B, q, v, (double)((long long)(replan0 + cfg->n_replans) * cfg->replanning_steps) * cfg->sim_dt,
                                        (double)cfg->nominal_period, nullptr, 0, nullptr, nullptr, 0, cfg->collision_height, nullptr, 0,
-                                       nullptr, failed, cfg->n_replans - 1, cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK, st);
+                                       nullptr, failed, replan0 + cfg->n_replans - 1, cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK, st);
     if (frc) return fail(h, frc, std::string("nmpc_observe_batch: ") + nmpc_torque_last_error(pl.torque));
     return NMPC_OK;
 }

@@ -231,12 +231,12 @@ __global__ void nmpc_wb_rollout_advance_kernel(const WbRolloutArgs a) {
     double q[18], v[18];
     if (!a.record_sim_steps) {
         for (int i = 0; i < 18; ++i) { q[i] = qf[i]; v[i] = vf[i]; }
-        const double tw = a.replan_index * a.replanning_steps * a.sim_dt;
+        const double tw = (long long)a.replan_index * a.replanning_steps * a.sim_dt;      // (a continued rollout's index: no int product)
         record(rows, recorded_phase(tw, period), q, v);       // the state this replan started from
     } else {
         for (int j = 0; j < a.replanning_steps; ++j) {                              // the states the plant runs through
             plan_at((j + 1) * a.sim_dt, q, v);
-            const double tw = (a.replan_index * a.replanning_steps + j + 1) * a.sim_dt;
+            const double tw = ((long long)a.replan_index * a.replanning_steps + j + 1) * a.sim_dt;
             record(rows + j * 44, recorded_phase(tw, period), q, v);
         }
     }

@@ -68,16 +68,17 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
                        ood_weight: float = 5.0, terminate_mask: int = TERMINATE_DEFAULT, kp: Optional[float] = None,
                        kd: Optional[float] = None, n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0,
                        val_fraction: float = 0.0, plant=None, plant_substeps: int = 2, push_as_force: bool = False,
-                       integrator: Optional[str] = None):
+                       integrator: Optional[str] = None, chunk_replans: Optional[int] = None):
     """One DAgger iteration, from rollouts to updated parameters: `collect.collect_rollouts` (its arguments up to `kd`, and
-    `plant` / `plant_substeps` / `push_as_force` / `integrator`: the expert on the ground-contact plant, pushed by a force, under the named integrator) appends the valid rollouts and their weights to `db`, then
+    `plant` / `plant_substeps` / `push_as_force` / `integrator`: the expert on the ground-contact plant, pushed by a force, under the named integrator;
+    `chunk_replans`: the rollout in stretches of that many replans, each appended before the next runs) appends the valid rollouts and their weights to `db`, then
     `train_network` trains `policy` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows.  Returns (err, weights, n_rows, train_loss, val_loss): what
     the two parts return."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
     err, weights, n_rows = collect_rollouts(mpc, layer, db, q0, v0, T, push=push, nominal=nominal, ood_weight=ood_weight,
                                             terminate_mask=terminate_mask, kp=kp, kd=kd, plant=plant, plant_substeps=plant_substeps,
-                                            push_as_force=push_as_force, integrator=integrator)
+                                            push_as_force=push_as_force, integrator=integrator, chunk_replans=chunk_replans)
     n = len(db)
     if n == 0:
         raise ValueError("the database is empty: no rollout of the batch was valid")

@@ -83,6 +83,7 @@ class LocomotionMPC:
             self.solver.reset()
         self.first_solve, self.diverged = True, False
         self.sim_step = self.plan_step = self.current_opt_node = self.delay = 0
+        self.sim_time, self.clock_step = 0.0, 0       # the float clock `open_loop_device` stopped at, and the steps it has summed
         sh = (self.batch, 3) if self.batch > 1 else (3,)
         self.v_des, self.w_des = np.zeros(sh), np.zeros(sh)
         self.base_ref_vel_tracking = np.zeros((self.batch, 12) if self.batch > 1 else 12)
@@ -190,8 +191,14 @@ class LocomotionMPC:
         of its replans) from the controller's current counters -- what `open_loop_device` hands to the device, so that both
         replan at the same nodes (the reference advances the node when the accumulated float time passes a node time,
         mpc.py:171-186, 427-431)."""
-        sim_time, sim_step, node, nodes, steps = 0.0, self.sim_step, self.current_opt_node, [], 0
-        while sim_time <= trajectory_time:
+        steps, nodes, node, _ = self._run_clock(0.0, lambda sim_time, steps: sim_time <= trajectory_time)
+        return steps, nodes, node
+
+    def _run_clock(self, sim_time: float, go_on):
+        """the one text of the float clock: from float time `sim_time` and the controller's counters while go_on(sim_time, steps
+        run) holds -> (steps run, node of each replan, node at the end, float time at the end)"""
+        sim_step, node, nodes, steps = self.sim_step, self.current_opt_node, [], 0
+        while go_on(sim_time, steps):
             if sim_time >= (node + 1) * self.dt_nodes:
                 node += 1
             if sim_step % self.replanning_steps == 0:
@@ -199,7 +206,23 @@ class LocomotionMPC:
             sim_step += 1
             steps += 1
             sim_time = sim_time + self.sim_dt
-        return steps, nodes, node
+        return steps, nodes, node, sim_time
+
+    def replan_clock_intervals(self, n_replans: int, resume: bool = False):
+        """`replan_clock` for exactly `n_replans` whole replanning intervals -> (steps = n_replans * replanning_steps, the node of
+        each replan, the node at the end, the float time at the end).  resume=False: the float time starts at 0, as
+        `replan_clock`'s.  resume=True: it goes on from `self.sim_time`, where the previous `open_loop_device` stopped, summing
+        sim_time = sim_time + sim_dt in the order of one long run -- the doubles, and with them the nodes, of stretches run one
+        after the other are those of one run over all of them.  Nothing of the controller is changed: `open_loop_device` stores
+        what this returns.  The counters must stand on an interval boundary (ValueError)."""
+        n_replans = int(n_replans)
+        if n_replans < 1:
+            raise ValueError("n_replans must be at least 1")
+        if self.sim_step % self.replanning_steps or (resume and self.clock_step % self.replanning_steps):
+            raise ValueError("whole replanning intervals start on an interval boundary: the previous call ended "
+                             f"{self.sim_step % self.replanning_steps} steps into an interval")
+        total = n_replans * self.replanning_steps
+        return self._run_clock(self.sim_time if resume else 0.0, lambda sim_time, steps: steps < total)
 
     def state_rows(self, q_traj: np.ndarray, v_traj: np.ndarray, t0_step: int = 0) -> np.ndarray:
         """states of this controller (Euler layout, [K, 18] each; K, B, 18 for a batch) as the reference's recorded rows
@@ -218,11 +241,11 @@ class LocomotionMPC:
             rows[j] = np.concatenate([[np.round(np.fmod(tw, period) / period, 4)], v_mj, q_mj[2:], bwf])
         return rows
 
-    def open_loop_device(self, q0: np.ndarray, v0: np.ndarray, trajectory_time: float, push: Optional[dict] = None,
+    def open_loop_device(self, q0: np.ndarray, v0: np.ndarray, trajectory_time: Optional[float] = None, push: Optional[dict] = None,
                          record_sim_steps: bool = True, terminate_mask: int = TERMINATE_DEFAULT,
                          collision_height: float = COLLISION_HEIGHT, torque_layer=None, kp: Optional[float] = None,
                          kd: Optional[float] = None, plant=None, plant_substeps: int = 2, push_as_force: bool = False,
-                         integrator: Optional[str] = None):
+                         integrator: Optional[str] = None, n_replans: Optional[int] = None, resume: bool = False):
         """`open_loop` with the whole rollout on the device (nmpc_wb_rollout_batch): per replan the problem is assembled from
         the plant state by a kernel, solved with the warm-start shift folded in, and the up-sampled plan is followed for
         `replanning_steps` simulation steps -- one host call, no round trip per replan, the whole batch at once.
@@ -245,24 +268,46 @@ class LocomotionMPC:
         (nmpc_wb_rollout_set_plant_push), where the feet and the torque limit answer it, instead of the velocity jump per
         replanning interval.
         integrator (needs plant): "explicit" or "implicit" sets the integrator of torque_layer's plant first
-        (`BatchedTorqueLayer.set_integrator`; it stays set), None leaves it as it is."""
+        (`BatchedTorqueLayer.set_integrator`; it stays set), None leaves it as it is.
+        n_replans=K (instead of trajectory_time, which is then None): exactly K whole replanning intervals, K * replanning_steps
+        simulation steps -- S, `self.actions`, the plant state and the counters end on an interval boundary, where a later call
+        can go on.  resume=True (needs n_replans, and a previous call that ended on a boundary; ValueError otherwise): the call
+        CONTINUES the rollout of the previous call instead of starting one -- q0, v0 are the `q_final`, `v_final` it left, the
+        float clock goes on from `self.sim_time` (`replan_clock_intervals`), and the device counts its replans from the replan the
+        rollout has reached (`BatchedNmpcSolver.set_rollout_clock`, set for this call): the recorded phase, the push window --
+        `push` times are those of the whole rollout, counted from its first call -- and the stamps in `self.failed` are the long
+        rollout's, and the stretches' rows, one after the other, are bit for bit the rows of one call over all of them.  The
+        flags the previous call left in `self.failed` are carried on (a copy: the tensor the previous call returned stays as it
+        is): a rollout that entered the call terminated stays frozen, its rows of the call are its frozen state -- cut at its
+        stamp.  Between two stretches the host may `set_command`, look at `self.failed`, save or stop."""
         import torch
+        if (trajectory_time is None) == (n_replans is None):
+            raise ValueError("open_loop_device: give trajectory_time or n_replans, one of them")
+        if resume and n_replans is None:
+            raise ValueError("resume: a continued call runs whole replanning intervals, give n_replans")
         if integrator is not None:
             from .torque import integrator_mode
             integrator_mode(integrator)                   # an unknown name is refused before anything runs
             if plant is None:
                 raise ValueError("integrator: the integrator is the contact plant's, give plant")
+        if n_replans is None:
+            steps, nodes, node_end, time_end = self._run_clock(0.0, lambda sim_time, steps: sim_time <= trajectory_time)
+        else:
+            steps, nodes, node_end, time_end = self.replan_clock_intervals(n_replans, resume)
+        n_replans = len(nodes)
+        clock_step0 = self.clock_step if resume else 0
+        replan0 = clock_step0 // self.replanning_steps
         self._declared_momentum_only("open_loop_device")
         fs = self.solver
         s = fs._device_solver()
         B, N, dev = self.batch, self.config_opt.n_nodes, s.device
-        steps, nodes, node_end = self.replan_clock(trajectory_time)
-        n_replans = len(nodes)
+        failed_in = self.failed.clone() if replan0 else None        # a continued rollout keeps its flags and stamps
         cfg_o = self.config_opt
         s.set_max_iter(cfg_o.max_iter); s.set_nlp_tol(cfg_o.nlp_tol); s.set_max_qp_iter(cfg_o.max_qp_iter)
         fs._opts.update(max_iter=cfg_o.max_iter, nlp_tol=cfg_o.nlp_tol, qp_tol=cfg_o.qp_tol)
         by_rollout = lambda a, dtype=torch.float32: s.to_device(np.asarray(a, np.float64).reshape(B, -1), dtype)   # noqa: E731
-        q, v = by_rollout(q0), by_rollout(v0)
+        # (the q_final, v_final of the call that is continued may be handed over as they are: device tensors, copied)
+        q, v = (a.to(dev, torch.float32).reshape(B, -1).clone() if isinstance(a, torch.Tensor) else by_rollout(a) for a in (q0, v0))
         v_des, w_des, ref_state = (by_rollout(a, torch.float64) for a in (self.v_des, self.w_des, self.base_ref_vel_tracking))
         if getattr(self, "_X_dev", None) is None or self.first_solve:
             self._X_dev = torch.zeros(B, N + 1, 42, dtype=torch.float32, device=dev)
@@ -286,10 +331,11 @@ class LocomotionMPC:
                 s.set_rollout_plant(torque_layer, plant, plant_substeps, kp, kd)
             if push_as_force:
                 s.set_rollout_plant_push(True)
+            s.set_rollout_clock(replan0)
             S, failed = s.wb_rollout(
                 s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
                 nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref), by_rollout(push["force"]) if push else None,
-                self._X_dev, self._U_dev, status,
+                self._X_dev, self._U_dev, status, failed=failed_in,
                 n_replans=n_replans, replanning_steps=self.replanning_steps, nodes_per_cycle=self.contact_planner.nodes_per_cycle,
                 first_solve=int(self.first_solve), last_node=int(fs.last_node), max_sqp_first=N_SQP_FIRST,
                 nlp_tol_first=cfg_o.nlp_tol / 10.0, nlp_tol=cfg_o.nlp_tol, sim_dt=self.sim_dt, time_horizon=cfg_o.time_horizon,
@@ -300,6 +346,7 @@ class LocomotionMPC:
                 nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
                 collision_height=float(collision_height))
         finally:
+            s.set_rollout_clock(0)
             if push_as_force:
                 s.set_rollout_plant_push(False)
             if plant is not None:
@@ -309,6 +356,7 @@ class LocomotionMPC:
         # bookkeeping as open_loop leaves it
         self.first_solve = False
         self.sim_step += steps
+        self.sim_time, self.clock_step = time_end, clock_step0 + steps
         self.current_opt_node = node_end
         fs.last_node = nodes[-1]
         ref = ref_state.cpu().numpy()

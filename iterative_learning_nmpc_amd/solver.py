@@ -169,6 +169,13 @@ class BatchedNmpcSolver:
         whose torque layer has a push of the caller's attached."""
         _lib.check(self.lib.nmpc_wb_rollout_set_plant_push(self._h, int(bool(as_force))), self._h, "nmpc_wb_rollout_set_plant_push")
 
+    def set_rollout_clock(self, replan0: int = 0):
+        """nmpc_wb_rollout_set_clock: while replan0 > 0 is set, replan i of every following `wb_rollout` is replan replan0 + i of
+        a longer rollout -- the recorded phase, the push window (push_start counts from the long rollout's step 0) and the
+        stamp replan0 + i + 1 in `failed` are that rollout's, the rows written are this call's own.  0 (the default): a rollout
+        starts at its call.  A negative value and a handle of another model are refused and leave the previous value in force."""
+        _lib.check(self.lib.nmpc_wb_rollout_set_clock(self._h, int(replan0)), self._h, "nmpc_wb_rollout_set_clock")
+
     MOMENTUM_MODELS = {"declared": 0, "articulated": 1}      # NMPC_WB_MOMENTUM_* of include/nmpc.h
 
     def set_momentum_model(self, model: str = "declared", torque_layer=None):
@@ -306,10 +313,12 @@ class BatchedNmpcSolver:
             stream(self.device)), self._h, "nmpc_rollout_batch")
         return S, failed
 
-    def wb_rollout(self, gait, peaks, nodes, q, v, v_des, w_des, ref_state, joint_ref, push_force, X, U, status, **cfg):
+    def wb_rollout(self, gait, peaks, nodes, q, v, v_des, w_des, ref_state, joint_ref, push_force, X, U, status, failed=None, **cfg):
         """nmpc_wb_rollout_batch: B = q.shape[0] whole-body rollouts from one call.  cfg: every field of
         nmpc_wb_rollout_cfg by name; nodes: host, the optimisation node of each replan.  q, v, ref_state, X, U and status
-        are updated in place.  Returns (S [B, rows, 44], failed [B] int32: NMPC_ROLLOUT_FLAG_* bits)."""
+        are updated in place.  Returns (S [B, rows, 44], failed [B] int32: NMPC_ROLLOUT_FLAG_* bits).  failed (int32 [B] on the
+        device, None: zeros): the flags the rollouts enter the call with, updated in place and returned -- those a previous
+        call left, where this one continues its rollouts (`set_rollout_clock`): a rollout that carries a stamp stays frozen."""
         c = _cfg(_lib.NmpcWbRolloutCfg, cfg)
         B = q.shape[0]
         for t, name in ((gait, "gait"), (peaks, "peaks")):
@@ -317,7 +326,11 @@ class BatchedNmpcSolver:
         self._chk(q, (B, 18), "q")
         self._chk(v, (B, 18), "v")
         self._chk(joint_ref, (12,), "joint_ref")
-        S, failed = self._rollout_io(c, B, v_des, w_des, ref_state, push_force, X, U, status, 44)
+        S, fresh = self._rollout_io(c, B, v_des, w_des, ref_state, push_force, X, U, status, 44)
+        if failed is None:
+            failed = fresh
+        else:
+            self._chk(failed, (B,), "failed", torch.int32)
         assert len(nodes) == c.n_replans
         if getattr(self, "_labels", None) is not None:           # the attached label buffer must be this rollout's size
             _, zoh, A = self._labels
