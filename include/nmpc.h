@@ -361,6 +361,26 @@ int nmpc_wb_rollout_set_plant_push(void *handle, int as_force);
  * its call, bit for bit as before.  nmpc_wb_rollout_cfg is unchanged. */
 int nmpc_wb_rollout_set_clock(void *handle, int replan0);
 
+/* A push window per rollout [decl], per handle (the reference pushes every perturbed rollout at a replanning point of its own for
+ * a duration of its own: data_collection_pretrain_omini_vc_policy_1direction_perturbed.py:191-247).  start, duration: dev float
+ * [rows], seconds from step 0 of the (long) rollout, caller-owned, kept as pointers and read when a rollout runs.  While they are
+ * attached they replace cfg.push_start / cfg.push_duration of every following rollout of the handle: rollout b is pushed with
+ * push_force[b] over its own window, duration[b] <= 0 meaning no push for it.  Rollout b of such a call is bit for bit rollout b
+ * of the same call (same B, same row) made without the arrays and with cfg.push_start = start[b], cfg.push_duration = duration[b].
+ *   The velocity jump: the advance kernel makes, per rollout, the comparison the host makes for the whole batch -- in doubles,
+ *     t_now >= start - sim_dt / 2 and t_now < start + duration - sim_dt / 2, t_now = (replan0 + i) replanning_steps sim_dt.
+ *   The push as a force on the plant (nmpc_wb_rollout_set_plant_push): a kernel at the rollout's entry turns the seconds into
+ *     substeps, first = lround(start n_sub / sim_dt), count = max(0, lround(duration n_sub / sim_dt)), in a buffer of 2 B_max
+ *     ints the handle owns from nmpc_create (the call allocates nothing); every replan's track launch gets these windows
+ *     (nmpc_contact_set_push_windows, include/nmpc_torque.h) and its substep offset (replan0 + i) replanning_steps n_sub.
+ * nmpc_rollout_set_push_windows is for handles of NMPC_MODEL_CENTROIDAL (nmpc_rollout_batch), nmpc_wb_rollout_set_push_windows for
+ * NMPC_MODEL_WHOLEBODY (nmpc_wb_rollout_batch).  With nothing attached the launches of a rollout are exactly what they are without
+ * these calls.  NMPC_E_ARG (text in nmpc_last_error), what was attached staying: a handle of the other model, only one of the two
+ * pointers given, rows < 1; and, by the rollout before any launch: push_force == NULL with windows attached, B > rows.
+ * NULL, NULL detaches.  The cfg structs are unchanged. */
+int nmpc_rollout_set_push_windows(void *handle, const float *start, const float *duration, int rows);
+int nmpc_wb_rollout_set_push_windows(void *handle, const float *start, const float *duration, int rows);
+
 /* The momentum model of a NMPC_MODEL_WHOLEBODY handle [decl], per handle; NMPC_WB_MOMENTUM_DECLARED is the default and what
  * every handle computed before this call existed.
  *   declared     A_g(q) v = [m rdot ; R I_b E(theta) thetadot]: one rigid body of mass NMPC_MP_MASS and inertia NMPC_MP_I.. whose

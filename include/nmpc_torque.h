@@ -174,6 +174,25 @@ int nmpc_contact_step_batch(void *handle, int B, int n_sub, float dt, const nmpc
 typedef struct { const float *force; int force_rows, joint, first_substep, n_substeps; } nmpc_push_cfg;   /* host struct, copied at the call */
 int nmpc_contact_set_push(void *torque, const nmpc_push_cfg *push);
 
+/* A push window per robot [decl] (the reference pushes every perturbed rollout at a replanning point of its own for a duration of
+ * its own: data_collection_pretrain_omini_vc_policy_1direction_perturbed.py:191-247).  first_substep, n_substeps: dev int [rows],
+ * caller-owned, kept as pointers and read in stream order.  While they are attached they replace first_substep / n_substeps of
+ * the attached nmpc_push_cfg in the three calls it acts in: robot b is pushed with force[b] in the substeps
+ *   first_substep[b] <= s < first_substep[b] + n_substeps[b],
+ * s counted exactly as stated there -- per call for nmpc_contact_step_batch, k n_sub + i for nmpc_contact_track_batch and
+ * nmpc_policy_rollout_batch (whose step launches take k n_sub off the windows; the attachment stays), and moved by the call's
+ * substep offset where a rollout makes the call.  A negative first_substep[b] is allowed, and n_substeps[b] <= 0 means no push for
+ * robot b.  Robot b of such a call is bit for bit robot b of the same call (same B, same row) made without the arrays under a
+ * push whose window is b's.
+ * Launches: under the explicit integrator the cut into un-pushed and pushed launches is uniform over the batch and cannot serve
+ * windows that differ, so a call with windows attached is ONE launch of one more kernel for the step and the track alike, in
+ * which every robot takes, substep by substep, either the un-pushed substep (no force term at all) or the pushed one; under the
+ * linearly implicit integrator it is the one launch it is anyway, the window test inside it reading the robot's own window.
+ * With no windows attached every call makes exactly the launches it makes without this entry point.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), what was attached staying: only one of the two pointers given, rows < 1.  At a
+ * plant call, before any launch: windows attached and no push attached, B > rows.  NULL, NULL detaches (the push stays). */
+int nmpc_contact_set_push_windows(void *torque, const int *first_substep, const int *n_substeps, int rows);
+
 /* The integrator of the contact plant [decl].  NMPC_INTEGRATOR_EXPLICIT (the default) is the step stated above, launch for launch.
  * NMPC_INTEGRATOR_LINEARLY_IMPLICIT takes the stiff terms -- ground stiffness and damping, the friction regulariser, the PD law --
  * at the end of the substep, linearised at its start.  One substep from (q, v):

@@ -49,6 +49,8 @@ SIGNATURES = {
     "nmpc_wb_rollout_set_plant": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_wb_rollout_set_plant_push": (c_int, [c_void_p, c_int]),
     "nmpc_wb_rollout_set_clock": (c_int, [c_void_p, c_int]),
+    "nmpc_rollout_set_push_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "nmpc_wb_rollout_set_push_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "nmpc_wb_set_momentum_model": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_wb_set_state_momentum": (c_int, [c_void_p, c_int]),
     "nmpc_set_ipm": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float]),
@@ -107,6 +109,7 @@ SIGNATURES = {
     "nmpc_contact_step_batch": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_contact_set_push": (c_int, [c_void_p, c_void_p]),
+    "nmpc_contact_set_push_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "nmpc_contact_set_integrator": (c_int, [c_void_p, c_int]),
     "nmpc_observe_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -33,7 +33,8 @@ def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = No
     the appended rows go into the database with them (`db.weights`).
     plant (a `torque.GroundContact`, None: the plant follows the plan): the expert runs in closed loop on the ground-contact
     plant with `plant_substeps` substeps per simulation step (`open_loop_device`): the rows are then states of the plant, each
-    with the PD target the expert applied from it.  kp, kd: as `open_loop_device` (None: its defaults).  push_as_force (with
+    with the PD target the expert applied from it.  push: the dict of `mpc.sample_pushes`, whose "start" and "duration" may
+    be arrays of B (a window per rollout, e.g. merged from `mpc.sample_push_windows`), with or without `chunk_replans`.  kp, kd: as `open_loop_device` (None: its defaults).  push_as_force (with
     plant): the push is a force on the plant's trunk instead of a velocity jump per replanning interval.  integrator (with
     plant): the plant's integrator, as `open_loop_device` takes it (None: as the layer is set).
     After the call `mpc.actions`, `mpc.failed` and the returned S of the rollout are as `open_loop_device` leaves them

@@ -63,6 +63,11 @@ struct Handle {
     } momentum;
     bool plant_push_as_force = false;   // nmpc_wb_rollout_set_plant_push: a plant-mode rollout pushes with a force on the plant, not a velocity jump
     int rollout_replan0 = 0;            // nmpc_wb_rollout_set_clock: replan i of a whole-body rollout is replan rollout_replan0 + i of a longer one
+    struct {                            // nmpc_rollout_set_push_windows / nmpc_wb_rollout_set_push_windows (start == nullptr: the cfg's window)
+        const float *start = nullptr, *duration = nullptr;   // dev [rows] seconds, caller-owned
+        int rows = 0;
+    } push_windows;
+    int* push_substeps = nullptr;       // [2][B_max]: the windows in substeps of the plant, first substeps then counts (push as a force)
     bool ws_dirty = false;   // a dense-LQ call left foreign padding in the tile workspace
     bool mp_set = false, w_set = false;
     nmpc::ModelParams mp{};
@@ -311,6 +316,7 @@ int run_rollout(Handle* h, int B, const Cfg* cfg, int replan0, hipStream_t st, R
         // the push window in replanning intervals, half a simulation step of slack on both ends: with plain float compares
         // 5 * 0.04f = 0.19999999 misses a window that starts at 0.2 (the host loop, in doubles, does not)
         const double t_now = (replan0 + i) * dt_replan;
+        r.t_now = t_now; r.win_slack = slack; r.dt_replan = dt_replan;      // with a window per rollout the advance kernel decides (apply_push)
         r.push_dt = (r.push_force && cfg->push_duration > 0.0f && t_now >= (double)cfg->push_start - slack &&
                      t_now < (double)cfg->push_start + (double)cfg->push_duration - slack) ? (float)dt_replan : 0.0f;
         const int shift = plan(i);
@@ -326,6 +332,26 @@ int run_rollout(Handle* h, int B, const Cfg* cfg, int replan0, hipStream_t st, R
     return launched(h);
 }
 
+// why the attached push windows cannot serve a rollout of B rollouts (nullptr: they can, or there are none)
+const char* push_windows_refusal(const Handle* h, int B, const float* push_force) {
+    if (!h->push_windows.start) return nullptr;
+    if (!push_force) return "push windows: the rollout has no push_force";
+    if (B > h->push_windows.rows) return "push windows: B exceeds rows";
+    return nullptr;
+}
+
+// nmpc_rollout_set_push_windows and nmpc_wb_rollout_set_push_windows on a handle of `model_id`
+int set_push_windows(Handle* h, int model_id, const char* who, const float* start, const float* duration, int rows) {
+    if (!h) return NMPC_E_ARG;
+    if (h->dims.model_id != model_id)
+        return fail(h, NMPC_E_ARG, std::string(who) + (model_id == NMPC_MODEL_WHOLEBODY ? " needs the whole-body model" : " needs the centroidal model"));
+    if (!start && !duration) { h->push_windows = {}; return NMPC_OK; }
+    if (!start || !duration) return fail(h, NMPC_E_ARG, "push windows: start and duration come together or not at all");      // what was attached stays
+    if (rows < 1) return fail(h, NMPC_E_ARG, "push windows: rows must be at least 1");
+    h->push_windows.start = start; h->push_windows.duration = duration; h->push_windows.rows = rows;
+    return NMPC_OK;
+}
+
 // the device side of nmpc_create, on the handle's device; what was allocated before an error is nmpc_destroy's to free
 int allocate(Handle* h) {
     NMPC_TRY(no_handle, hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
@@ -336,6 +362,7 @@ int allocate(Handle* h) {
     NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&h->roll), ((size_t)h->dims.B_max * per + 16) * sizeof(float)));   // (+ the 16 B roundings of the carve-up)
     NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&h->label_skip), (size_t)h->dims.B_max * sizeof(int)));
     NMPC_TRY(no_handle, hipMemset(h->label_skip, 0, (size_t)h->dims.B_max * sizeof(int)));
+    NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&h->push_substeps), 2 * (size_t)h->dims.B_max * sizeof(int)));
     return NMPC_OK;
 }
 }  // namespace
@@ -408,6 +435,7 @@ void nmpc_destroy(void* handle) {
     if (h->ws) (void)hipFree(h->ws);
     if (h->roll) (void)hipFree(h->roll);
     if (h->label_skip) (void)hipFree(h->label_skip);
+    if (h->push_substeps) (void)hipFree(h->push_substeps);
     if (h->momentum.mrec) (void)hipFree(h->momentum.mrec);
     if (h->momentum.dcons) (void)hipFree(h->momentum.dcons);
     delete h;
@@ -545,6 +573,14 @@ int nmpc_wb_rollout_set_plant_push(void* handle, int as_force) {
     return NMPC_OK;
 }
 
+int nmpc_rollout_set_push_windows(void* handle, const float* start, const float* duration, int rows) {
+    return set_push_windows(static_cast<Handle*>(handle), NMPC_MODEL_CENTROIDAL, "nmpc_rollout_set_push_windows", start, duration, rows);
+}
+
+int nmpc_wb_rollout_set_push_windows(void* handle, const float* start, const float* duration, int rows) {
+    return set_push_windows(static_cast<Handle*>(handle), NMPC_MODEL_WHOLEBODY, "nmpc_wb_rollout_set_push_windows", start, duration, rows);
+}
+
 int nmpc_wb_rollout_set_clock(void* handle, int replan0) {
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return NMPC_E_ARG;
@@ -676,6 +712,7 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
     if (cfg->record_sim_steps &&
         std::fabs(cfg->nodes_per_replan * (cfg->time_horizon / h->dims.N) - cfg->replanning_steps * cfg->sim_dt) > 1e-9)
         return fail(h, NMPC_E_ARG, "per-step recording needs nodes_per_replan * dt_nodes = replanning_steps * sim_dt");
+    if (const char* why = push_windows_refusal(h, B, push_force)) return fail(h, NMPC_E_ARG, why);
     nmpc::RolloutArgs r{};
     r.yref = h->roll;
     r.yref_e = r.yref + (size_t)h->dims.B_max * h->dims.N * h->ny;
@@ -684,6 +721,7 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
     r.mass = h->mp.mass; r.gz = h->mp.gz;
     r.gait = gait; r.x = x; r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state; r.foot_pos = foot_pos;
     r.push_force = push_force; r.X = X; r.U = U; r.S = S; r.status = status; r.failed = failed;
+    r.win_start = h->push_windows.start; r.win_duration = h->push_windows.duration;
     r.footsteps = cfg->footsteps ? 1 : 0;
     std::memcpy(r.hip_offset, cfg->hip_offset, sizeof(r.hip_offset));
     std::memcpy(r.stance_ratio, cfg->stance_ratio, sizeof(r.stance_ratio));
@@ -749,6 +787,10 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
     const bool force_push = h->plant_push_as_force && push_force;
     if (force_push && nmpc_torque::push_attached(pl.torque))
         return fail(h, NMPC_E_ARG, "plant push: the torque handle has a push of the caller's attached (nmpc_contact_set_push)");
+    if (const char* why = push_windows_refusal(h, B, push_force)) return fail(h, NMPC_E_ARG, why);
+    const auto& pw = h->push_windows;
+    nmpc_torque::PushWindows plant_windows{};      // a window per rollout, pushed as a force: in substeps, from the kernel at the entry below
+    if (force_push && pw.start) plant_windows = {h->push_substeps, h->push_substeps + h->dims.B_max, B};
     nmpc_push_cfg plant_push{};
     if (force_push) {
         plant_push.force = push_force; plant_push.force_rows = B; plant_push.joint = 5;
@@ -772,6 +814,13 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
     r.gait = gait; r.peaks = peaks; r.q = q; r.v = v; r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state;
     r.joint_ref = joint_ref; r.push_force = push_force;
     r.X = X; r.U = U; r.S = S; r.status = status; r.failed = failed;
+    if (pw.start && !force_push) { r.win_start = pw.start; r.win_duration = pw.duration; }      // the velocity jump, decided per rollout
+    if (plant_windows.first) {
+        NMPC_ENTER(h, h->device);
+        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_push_substeps_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, pw.start, pw.duration,
+                           pl.n_sub, cfg->sim_dt, h->push_substeps, h->push_substeps + h->dims.B_max);
+        if (const int rc = launched(h)) return rc;
+    }
     nmpc::wb::WbArgs w = wb_args(h);
     w.x0 = r.x0; w.status = status;
     int last_node = cfg->last_node;
@@ -810,8 +859,10 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
                 // (a window that lies wholly before them, however far, starts n_substeps before: the int holds it)
                 const long long first = (long long)push.first_substep - (long long)(replan0 + i) * steps * pl.n_sub;
                 push.first_substep = (int)std::max(first, -(long long)push.n_substeps);
+                // (with a window per rollout the kernel takes the offset off each: the windows stay as the entry kernel wrote them)
                 trc = nmpc_torque::contact_track_pushed(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
-                                                        rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, push, st);
+                                                        rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, push, plant_windows,
+                                                        (long long)(replan0 + i) * steps * pl.n_sub, st);
             } else {
                 trc = nmpc_contact_track_batch(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
                                                rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, st);

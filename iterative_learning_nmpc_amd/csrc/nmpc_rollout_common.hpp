@@ -34,6 +34,10 @@ struct RolloutCommon {
     float* S;                             // dev [B][n_rows][row width of the plant] recorded states
     const int* status;                    // dev [B] status of the last solve
     int* failed;                          // dev [B] sticky flag bits NMPC_ROLLOUT_FLAG_*, replan of termination above them
+    // a push window per rollout (nmpc_rollout_set_push_windows, nmpc_wb_rollout_set_push_windows); win_start == nullptr: push_dt
+    // above holds for every rollout.  t_now: the time of this replan; win_slack: half a simulation step; dt_replan: the interval.
+    const float *win_start, *win_duration;    // dev [B] seconds
+    double t_now, win_slack, dt_replan;
 };
 
 __device__ inline void rpy_matrix(double roll, double pitch, double yaw, double (&R)[9]) {
@@ -169,11 +173,18 @@ __device__ inline void hold_last_row(float* rows, int width, int rows_per_replan
         for (int i = 0; i < width; ++i) rows[j * width + i] = rows[i - width];
 }
 
-// base push over a replanning interval: v += F * push_dt / m
+// base push over a replanning interval: v += F * push_dt / m.  With a window per rollout, push_dt is decided here as the host
+// loop decides it for the whole batch (run_rollout, nmpc_api.hip): the same comparison in doubles on the rollout's own window.
 __device__ inline void apply_push(float* v3, const RolloutCommon& a, int b, float mass) {
 #pragma clang fp contract(off)
-    if (a.push_dt > 0.0f && a.push_force)
-        for (int i = 0; i < 3; ++i) v3[i] += a.push_force[b * 3 + i] * a.push_dt / mass;
+    float push_dt = a.push_dt;
+    if (a.win_start) {
+        const float start = a.win_start[b], duration = a.win_duration[b];
+        push_dt = (a.push_force && duration > 0.0f && a.t_now >= (double)start - a.win_slack &&
+                   a.t_now < (double)start + (double)duration - a.win_slack) ? (float)a.dt_replan : 0.0f;
+    }
+    if (push_dt > 0.0f && a.push_force)
+        for (int i = 0; i < 3; ++i) v3[i] += a.push_force[b * 3 + i] * push_dt / mass;
 }
 
 // one simulation step of the integrated base reference rs[12] (increment_base_ref_position, mpc.py:204-208)

@@ -384,6 +384,7 @@ struct Torque {
         int rows = 0;
     } states;
     nmpc_push_cfg push{};               // nmpc_contact_set_push: the push of the plant calls (force == nullptr: none)
+    nmpc_torque::PushWindows windows{}; // nmpc_contact_set_push_windows: a window per robot in place of the push's own (first == nullptr: none)
     int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
@@ -438,6 +439,7 @@ int allocate(Torque* t) {
     LDS_LIMIT(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width), ct_lds);
     LDS_LIMIT(KERNEL_AT_WIDTH(contact_track_kernel, t->ct_width), ct_lds);
     LDS_LIMIT(KERNEL_AT_WIDTH(contact_push_kernel, t->ct_width), ct_lds);
+    LDS_LIMIT(KERNEL_AT_WIDTH(contact_window_kernel, t->ct_width), ct_lds);
     // the composite-inertia pass, the implicit plant step (slice and triangle) and the three entry points of the centroidal kernel:
     // the slice of the largest tree at the one width each has
     LDS_LIMIT(crba_kernel, crba_lds_bytes(MAXJ, CR_W));
@@ -537,6 +539,14 @@ Window push_window(const nmpc_push_cfg& push, long long s0, long long total) {
     return w;
 }
 
+// why the windows per robot cannot serve a plant call of B robots under `push` (nullptr: they can, or there are none)
+const char* windows_refusal(const nmpc_torque::PushWindows& wins, const nmpc_push_cfg& push, int B) {
+    if (!wins.first) return nullptr;
+    if (!push.force) return "push windows: no push is attached (nmpc_contact_set_push)";
+    if (B > wins.rows) return "push windows: B exceeds rows";
+    return nullptr;
+}
+
 // A plant call under a push is cut into runs of substeps that are all un-pushed -- launches of the un-pushed kernels, as a call
 // without a push makes them -- and runs that are all pushed, launches of contact_push_kernel (nmpc_torque_track.hip.inc says why).
 
@@ -546,33 +556,46 @@ const char* implicit_refusal(int n) {
     return nullptr;
 }
 
-// both plant calls under the implicit integrator: one launch of contact_implicit_kernel, the push window tested inside it
-int launch_implicit(Torque* t, ImplicitArgs& p, const nmpc_push_cfg& push, const Window& win, void* stream) {
+// both plant calls under the implicit integrator: one launch of contact_implicit_kernel, the push window -- the push's own, or
+// with `wins` the robot's, in a call whose substep 0 is substep s0 of their count -- tested inside it
+int launch_implicit(Torque* t, ImplicitArgs& p, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins, long long s0,
+                    void* stream) {
     if (win.hi > win.lo) { p.force = push.force; p.joint = push.joint; p.push_lo = win.lo; p.push_hi = win.hi; }
+    if (wins.first) { p.force = push.force; p.joint = push.joint; p.win_first = wins.first; p.win_count = wins.count; p.win_s0 = s0; }
     return launch_step(t, contact_implicit_kernel<IM_W>, IM_W, im_lds_bytes(t->host.n), p, stream);
 }
 
 // nmpc_contact_step_batch under an explicit push: the call's substep i is substep s0 + i of the count `push` is stated in.
 // At most three launches: before, inside and after the window; the first reads q, v, the later ones go on in place on q_out,
-// v_out, and the last one writes a_out, f_out, tau_out.
+// v_out, and the last one writes a_out, f_out, tau_out.  With windows per robot (`wins`, stated in the same count): one launch of
+// contact_window_kernel, or of the implicit kernel.
 int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* cfg, const float* q, const float* v, const float* tau_ff,
                  const float* q_des, float kp, float kd, float* q_out, float* v_out, float* a_out, float* f_out, float* tau_out,
-                 const nmpc_push_cfg& push, long long s0, void* stream) {
+                 const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, long long s0, void* stream) {
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
     if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
     if (push.force && B > push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
+    if (const char* why = windows_refusal(wins, push, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     const int w = t->ct_width;
     const size_t lds = ct_lds_bytes(t->host.n, w);
-    const Window win = push_window(push, s0, n_sub);
+    const Window win = wins.first ? Window{} : push_window(push, s0, n_sub);
     if (t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT) {
         ImplicitArgs p{};
         p.B = B; p.n_steps = 1; p.n_sub = n_sub; p.a_rows = 1; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
         p.tau = tau_ff; p.A = q_des; p.q = q_out; p.v = v_out; p.q_in = q; p.v_in = v;
         p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out;
-        return launch_implicit(t, p, push, win, stream);
+        return launch_implicit(t, p, push, win, wins, s0, stream);
+    }
+    if (wins.first) {
+        WindowArgs p{};
+        p.B = B; p.n_steps = 1; p.n_sub = n_sub; p.a_rows = 1; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+        p.tau = tau_ff; p.A = q_des; p.q = q_out; p.v = v_out; p.q_in = q; p.v_in = v;
+        p.force = push.force; p.joint = push.joint; p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out;
+        p.first = wins.first; p.count = wins.count; p.s0 = s0;
+        return launch_step(t, KERNEL_AT_WIDTH(contact_window_kernel, w), w, lds, p, stream);
     }
     const int cuts[4] = {0, (int)win.lo, (int)win.hi, n_sub};
     bool first = true;
@@ -602,10 +625,10 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
 
 // nmpc_contact_track_batch under an explicit push, in substeps s = k * n_sub + i of the call.  Whole control steps of one kind
 // go into one launch; a control step the window starts or ends in is cut at that substep, and only its first piece writes its row
-// of Q, V.
+// of Q, V.  With windows per robot (`wins`), in a call whose substep 0 is substep s0 of their count: one launch, as the step.
 int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v, const float* tau_ff,
                   const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows, const int* skip, int skip_mask,
-                  const nmpc_push_cfg& push, void* stream) {
+                  const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, long long s0, void* stream) {
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || !v) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v");
     if (n_steps < 1) return fail(t, NMPC_E_ARG, "n_steps must be at least 1");
@@ -618,17 +641,26 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
     if (Q && !whole_body_tree(t->host))
         return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
     if (push.force && B > push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
+    if (const char* why = windows_refusal(wins, push, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     const int w = t->ct_width, n = t->host.n, nu = t->host.nu;
     const size_t lds = ct_lds_bytes(n, w);
     const long long total = (long long)n_steps * n_sub;
-    const Window win = push_window(push, 0, total);
+    const Window win = wins.first ? Window{} : push_window(push, 0, total);
     if (t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT) {
         ImplicitArgs p{};
         p.B = B; p.n_steps = n_steps; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
         p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
         p.tau = tau_ff; p.A = A; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v; p.Q = Q; p.V = V;
-        return launch_implicit(t, p, push, win, stream);
+        return launch_implicit(t, p, push, win, wins, s0, stream);
+    }
+    if (wins.first) {
+        WindowArgs p{};
+        p.B = B; p.n_steps = n_steps; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
+        p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
+        p.tau = tau_ff; p.A = A; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v; p.Q = Q; p.V = V;
+        p.force = push.force; p.joint = push.joint; p.first = wins.first; p.count = wins.count; p.s0 = s0;
+        return launch_step(t, KERNEL_AT_WIDTH(contact_window_kernel, w), w, lds, p, stream);
     }
     for (long long s = 0; s < total;) {
         const bool pushed = s >= win.lo && s < win.hi;
@@ -665,11 +697,12 @@ bool nmpc_torque::push_attached(void* handle) { return handle && static_cast<con
 
 int nmpc_torque::contact_track_pushed(void* handle, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v,
                                       const float* tau_ff, const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows,
-                                      const int* skip, int skip_mask, const nmpc_push_cfg& push, void* stream) {
+                                      const int* skip, int skip_mask, const nmpc_push_cfg& push, const PushWindows& windows, long long s0,
+                                      void* stream) {
     Torque* t = static_cast<Torque*>(handle);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
     if (const char* why = push_refusal(push, t->host.n)) return fail(t, NMPC_E_ARG, why);
-    return contact_track(t, B, n_steps, n_sub, dt, cfg, q, v, tau_ff, A, a_rows, kp, kd, Q, V, qv_rows, skip, skip_mask, push, stream);
+    return contact_track(t, B, n_steps, n_sub, dt, cfg, q, v, tau_ff, A, a_rows, kp, kd, Q, V, qv_rows, skip, skip_mask, push, windows, s0, stream);
 }
 
 const char* nmpc_torque::plan_actions_refusal(void* handle, int n_steps, const int* zoh, float kp, int device) {
@@ -901,7 +934,7 @@ int nmpc_contact_step_batch(void* handle, int B, int n_sub, float dt, const nmpc
                             float* f_out, float* tau_out, void* stream) {
     Torque* t = static_cast<Torque*>(handle);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
-    return contact_step(t, B, n_sub, dt, cfg, q, v, tau_ff, q_des, kp, kd, q_out, v_out, a_out, f_out, tau_out, t->push, 0, stream);
+    return contact_step(t, B, n_sub, dt, cfg, q, v, tau_ff, q_des, kp, kd, q_out, v_out, a_out, f_out, tau_out, t->push, t->windows, 0, stream);
 }
 
 int nmpc_contact_set_push(void* torque, const nmpc_push_cfg* push) {
@@ -910,6 +943,17 @@ int nmpc_contact_set_push(void* torque, const nmpc_push_cfg* push) {
     if (push)
         if (const char* why = push_refusal(*push, t->host.n)) return fail(t, NMPC_E_ARG, why);      // what was attached stays
     t->push = push ? *push : nmpc_push_cfg{};
+    return NMPC_OK;
+}
+
+int nmpc_contact_set_push_windows(void* torque, const int* first_substep, const int* n_substeps, int rows) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (!first_substep && !n_substeps) { t->windows = {}; return NMPC_OK; }
+    if (!first_substep || !n_substeps)      // what was attached stays
+        return fail(t, NMPC_E_ARG, "push windows: first_substep and n_substeps come together or not at all");
+    if (rows < 1) return fail(t, NMPC_E_ARG, "push windows: rows must be at least 1");
+    t->windows = {first_substep, n_substeps, rows};
     return NMPC_OK;
 }
 
@@ -946,7 +990,8 @@ int nmpc_contact_track_batch(void* handle, int B, int n_steps, int n_sub, float 
                              const int* skip, int skip_mask, void* stream) {
     Torque* t = static_cast<Torque*>(handle);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null handle");
-    return contact_track(t, B, n_steps, n_sub, dt, cfg, q, v, tau_ff, A, a_rows, kp, kd, Q, V, qv_rows, skip, skip_mask, t->push, stream);
+    return contact_track(t, B, n_steps, n_sub, dt, cfg, q, v, tau_ff, A, a_rows, kp, kd, Q, V, qv_rows, skip, skip_mask, t->push, t->windows, 0,
+                         stream);
 }
 
 int nmpc_observe_rows_batch(void* handle, int B, int n_rows, const float* Q, const float* V, int qv_rows, double t0, double dt_row,
@@ -1004,6 +1049,7 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     if (!rec.Q != !rec.V) return fail(t, NMPC_E_ARG, "states: Q and V come together or not at all");
     if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
     if (t->push.force && B > t->push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
+    if (const char* why = windows_refusal(t->windows, t->push, B)) return fail(t, NMPC_E_ARG, why);
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
         NMPC_ENTER(t, t->device);
@@ -1036,9 +1082,9 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
             NMPC_ENTER(t, t->device);
             if (const int rc = launch_elementwise(t, action_rows_kernel, B, stream, nu, t->act, A + (size_t)k * nu, K * nu)) return rc;
         }
-        // the attached push (if any) with its window moved to this step's substeps: s = k n_sub + i
+        // the attached push (if any) with its window, or the robots' windows, moved to this step's substeps: s = k n_sub + i
         if (const int rc = contact_step(t, B, cfg->n_sub, cfg->dt, ground, q, v, tau_ff, t->act, cfg->kp, cfg->kd, q, v, nullptr, nullptr, nullptr,
-                                        t->push, (long long)k * cfg->n_sub, stream))
+                                        t->push, t->windows, (long long)k * cfg->n_sub, stream))
             return rc;
     }
     return NMPC_OK;

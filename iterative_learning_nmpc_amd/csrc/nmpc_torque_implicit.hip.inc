@@ -14,6 +14,7 @@
 // One kernel serves nmpc_contact_step_batch and nmpc_contact_track_batch (and through them the policy and expert rollouts), with
 // contact_push_kernel's argument conventions, so the integrator has one copy of its substep and a chain of steps is its track
 // bit for bit.  The window of a push is tested per substep inside the kernel: there are no un-pushed bits of another kernel to keep.
+// With windows per robot attached (nmpc_contact_set_push_windows) the same test reads the robot's own window: the launch is the same.
 #pragma once
 
 constexpr int IM_W = 16;                                  // robots per block: the slice and the triangle of the largest tree fit the CU
@@ -31,6 +32,8 @@ struct WindowedPushForces : PushedGroundForces {
 
 struct ImplicitArgs : PushArgs {                          // force == nullptr: no push
     long long push_lo, push_hi;                           // the pushed substeps k * n_sub + s of the launch: [push_lo, push_hi)
+    const int *win_first, *win_count;                     // nmpc_contact_set_push_windows (nullptr: the window above for every robot):
+    long long win_s0;                                     // robot b's window [win_first[b], + win_count[b]) less win_s0 instead
 };
 
 // This thread's packed lower triangle, [entry][W] behind the block's slice.
@@ -228,6 +231,8 @@ __global__ __launch_bounds__(W) void contact_implicit_kernel(const Model* __rest
     float* fo = p.f_out ? p.f_out + (size_t)b * nf3 : nullptr;
     float* to = p.tau_out ? p.tau_out + (size_t)b * nu : nullptr;
     const V3 F = p.force ? v3(p.force + (size_t)b * 3) : V3{0, 0, 0};
+    long long push_lo = p.push_lo, push_hi = p.push_hi;
+    if (p.win_first) { push_lo = (long long)p.win_first[b] - p.win_s0; push_hi = push_lo + p.win_count[b]; }      // count <= 0: never pushed
     const float nan = __builtin_nanf("");
 #pragma clang loop unroll(disable) vectorize(disable)
     for (int i = 0; i < n; ++i) { at(i, FD_Q) = qi[i]; at(i, FD_Q + 1) = vi[i]; }
@@ -244,7 +249,7 @@ __global__ __launch_bounds__(W) void contact_implicit_kernel(const Model* __rest
         for (int s = 0; s < p.n_sub; ++s) {
             const bool last = k == p.n_steps - 1 && s == p.n_sub - 1;
             const long long sub = (long long)k * p.n_sub + s;
-            const bool on = p.force && sub >= p.push_lo && sub < p.push_hi;
+            const bool on = p.force && sub >= push_lo && sub < push_hi;
             unsigned unclamped = 0;
 #pragma clang loop unroll(disable) vectorize(disable)
             for (int i = 0; i < n; ++i) {

@@ -23,11 +23,20 @@ const char* contact_track_refusal(void* handle, const nmpc_contact_cfg* ground, 
 // has the caller attached a push to the handle (nmpc_contact_set_push)
 bool push_attached(void* handle);
 
+// a push window per robot (nmpc_contact_set_push_windows): dev int [rows] each, first == nullptr: none
+struct PushWindows {
+    const int *first = nullptr, *count = nullptr;
+    int rows = 0;
+};
+
 // nmpc_contact_track_batch under the explicit `push` (refused as nmpc_contact_set_push refuses it) in place of whatever is
-// attached to the handle, which is neither read nor rewritten: the track launch of a plant-mode rollout that pushes as a force
+// attached to the handle, which is neither read nor rewritten: the track launch of a plant-mode rollout that pushes as a force.
+// `windows` (if any) replace the window of `push` as the attached ones replace the attached push's; they are stated in a count
+// in which the call's substep 0 is substep s0.
 int contact_track_pushed(void* handle, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v,
                          const float* tau_ff, const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows,
-                         const int* skip, int skip_mask, const nmpc_push_cfg& push, void* stream);
+                         const int* skip, int skip_mask, const nmpc_push_cfg& push, const PushWindows& windows, long long s0,
+                         void* stream);
 
 // nullptr if the handle's tree can serve the articulated momentum model of a whole-body solver on `device` (-1: any device): 18
 // joints -- the coordinates of model 2 -- and some mass; otherwise the text nmpc_last_error gives

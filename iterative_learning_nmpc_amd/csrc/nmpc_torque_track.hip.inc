@@ -89,7 +89,7 @@ __global__ __launch_bounds__(W) void contact_track_kernel(const Model* __restric
 // chain of steps is its track because both run this text.  (A window flag inside one kernel does not give that: the compiler
 // fuses the recursion of such a kernel differently, and its un-pushed substeps are not the un-pushed kernel's bits.)
 // It is one more copy of the substep text: a fix to the PD law, the clamp, the Euler update or the NaN rule goes into
-// contact_step_kernel, contact_track_kernel and here.
+// contact_step_kernel, contact_track_kernel, here and contact_window_kernel below.
 // So it serves both callers: a start state apart from q, v and the outputs of the last substep for the step; a table of
 // targets, rows Q, V and skip flags for the track.
 struct PushArgs : TrackArgs {                             // A == nullptr: no PD target (the step's q_des == NULL)
@@ -146,6 +146,101 @@ __global__ __launch_bounds__(W) void contact_push_kernel(const Model* __restrict
                 at(i, FD_Q + 2) = t;
             }
             sound = fd_accel_body<W, CT_SLOTS>(m, PushedGroundForces{{cfg, last ? fo : nullptr}, F, p.joint}) && sound;
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < n; ++i) {
+                const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);
+                at(i, FD_Q + 1) = v;
+                at(i, FD_Q) = at(i, FD_Q) + p.dt * v;
+            }
+        }
+        if (!sound) {
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < n; ++i) { at(i, FD_Q) = nan; at(i, FD_Q + 1) = nan; }
+        }
+    }
+    // the state, and for the step the outputs of the last substep: NaN rows where the last control step was unsound
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = 0; i < n; ++i) {
+        if (p.a_out) p.a_out[(size_t)b * n + i] = sound ? at(i, FD_Q + 2) : nan;
+        qb[i] = at(i, FD_Q); vb[i] = at(i, FD_Q + 1);
+    }
+    if (!sound) {
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int i = 0; fo && i < nf3; ++i) fo[i] = nan;
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int i = 0; to && i < nu; ++i) to[i] = nan;
+    }
+}
+
+// ---- a window of its own per robot ------------------------------------------------------------------------------------------------
+// nmpc_contact_set_push_windows (DESIGN.md 8d): robot b is pushed in the substeps first[b] <= s0 + k n_sub + i < first[b] + count[b],
+// so the cut of a call into pushed and un-pushed launches, which is uniform over the batch, cannot be made on the host.  One
+// launch per call instead: contact_push_kernel's text, and in every substep the robot takes one of two calls of the recursion --
+// the un-pushed one under GroundForces, which is the call of contact_step_kernel / contact_track_kernel, or the pushed one under
+// PushedGroundForces, which is contact_push_kernel's.  The two are separate inlined copies on the two sides of a branch, not
+// one copy under a flag: each is compiled in blocks of its own, as in the kernel it comes from, and an un-pushed robot runs no
+// instruction of the push.  Robots of one block share its width and its slice layout and nothing else, so lanes whose windows
+// differ in a substep run the two sides one after the other under their execution masks (a substep then costs two recursions
+// for that wave); a wave whose lanes agree skips the other side.  Held bit for bit, robot by robot, to the cut path under
+// that robot's window (tests/test_gpu_push_windows_plant.py).
+// It is a fourth copy of the substep text: a fix to the PD law, the clamp, the Euler update or the NaN rule goes into all four.
+struct WindowArgs : PushArgs {
+    const int *first, *count;                             // robot b's window, in the count the call's substep 0 is substep s0 of
+    long long s0;
+};
+
+template <int W>
+__global__ __launch_bounds__(W) void contact_window_kernel(const Model* __restrict__ mp, const WindowArgs p) {
+    extern __shared__ float body[];                       // [joint][CT_SLOTS][W]
+    const Model& m = *mp;
+    const int n = m.n, nu = m.nu, base = n - nu, nf3 = 3 * m.nf;
+    ContactCfg* cfg = reinterpret_cast<ContactCfg*>(body + n * CT_SLOTS * W);
+    if (threadIdx.x == 0) *cfg = p.c;
+    __syncthreads();
+    const int b = blockIdx.x * W + threadIdx.x;
+    if (b >= p.B) return;
+    if (p.skip && (p.skip[b] & p.skip_mask)) return;
+    const Slice<CT_SLOTS, W> at;
+    float* qb = p.q + (size_t)b * n;
+    float* vb = p.v + (size_t)b * n;
+    const float* qi = p.q_in ? p.q_in + (size_t)b * n : qb;
+    const float* vi = p.v_in ? p.v_in + (size_t)b * n : vb;
+    const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;
+    float* fo = p.f_out ? p.f_out + (size_t)b * nf3 : nullptr;
+    float* to = p.tau_out ? p.tau_out + (size_t)b * nu : nullptr;
+    const V3 F = v3(p.force + (size_t)b * 3);
+    const long long push_lo = (long long)p.first[b] - p.s0, push_hi = push_lo + p.count[b];      // count <= 0: never pushed
+    const float nan = __builtin_nanf("");
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = 0; i < n; ++i) { at(i, FD_Q) = qi[i]; at(i, FD_Q + 1) = vi[i]; }
+    bool sound = true;
+    for (int k = 0; k < p.n_steps; ++k) {
+        if (p.Q) {
+            float* Qk = p.Q + ((size_t)b * p.qv_rows + k) * n;
+            float* Vk = p.V + ((size_t)b * p.qv_rows + k) * n;
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < n; ++i) { Qk[i] = at(i, FD_Q); Vk[i] = at(i, FD_Q + 1); }
+        }
+        const float* db = p.A ? p.A + ((size_t)b * p.a_rows + k) * nu : nullptr;
+        sound = true;
+        for (int s = 0; s < p.n_sub; ++s) {
+            const bool last = k == p.n_steps - 1 && s == p.n_sub - 1;
+            const long long sub = (long long)k * p.n_sub + s;
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int i = 0; i < n; ++i) {
+                float t = 0.0f;
+                if (i >= base) {
+                    t = tb ? tb[i - base] : 0.0f;
+                    if (db) t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
+                    { const float lim = cfg->tau_max; if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t); }   // a NaN stays NaN
+                    if (last && to) to[i - base] = t;
+                }
+                at(i, FD_Q + 2) = t;
+            }
+            if (sub >= push_lo && sub < push_hi)
+                sound = fd_accel_body<W, CT_SLOTS>(m, PushedGroundForces{{cfg, last ? fo : nullptr}, F, p.joint}) && sound;
+            else
+                sound = fd_accel_body<W, CT_SLOTS>(m, GroundForces{cfg, last ? fo : nullptr}) && sound;
 #pragma clang loop unroll(disable) vectorize(disable)
             for (int i = 0; i < n; ++i) {
                 const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);

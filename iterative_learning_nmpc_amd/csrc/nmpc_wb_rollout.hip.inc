@@ -260,5 +260,17 @@ __global__ void nmpc_wb_rollout_hold_actions_kernel(int B, int n_rows, int row0,
     Ab[r] = row0 > 0 ? Ab[(ptrdiff_t)(r % 12) - 12] : 0.0f;
 }
 
+// The push windows of the rollouts (nmpc_wb_rollout_set_push_windows, seconds) in substeps of the plant, for a push as a force:
+// the expressions the host has for the cfg's one window (nmpc_wb_rollout_batch), per rollout, once at the entry of a rollout.
+__global__ void nmpc_wb_push_substeps_kernel(int B, const float* __restrict__ start, const float* __restrict__ duration, int n_sub,
+                                             double sim_dt, int* __restrict__ first, int* __restrict__ count) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    first[b] = (int)lround((double)start[b] * n_sub / sim_dt);
+    const int n = (int)lround((double)duration[b] * n_sub / sim_dt);
+    count[b] = n < 0 ? 0 : n;
+}
+
 }  // namespace wb
 }  // namespace nmpc

@@ -29,6 +29,7 @@ import torch
 
 from ._lib import NMPC_ROLLOUT_TERM_SHIFT, NMPC_STATUS_NAN, NMPC_STATUS_QP
 from .collect import collect_rollouts
+from .mpc import push_windows
 from .config import TERMINATE_DEFAULT
 from .torque import NOMINAL_PERIOD, GroundContact, integrator_mode
 from .trajectory_io import KD, KP
@@ -108,7 +109,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     push: the dict of `mpc.sample_pushes` -- {"start": s, "duration": s, "force": [B, 3] N} -- as a force on the trunk
     (`BatchedTorqueLayer.set_push`, attached for this call): the substeps round(start / dt) <= s < round(start / dt) +
     round(duration / dt) of the rollout are pushed.  None, or a duration that rounds to no substep: the rollout is the bits it
-    is without.  A layer that has a push of the caller's attached already is refused with ValueError: the call would replace
+    is without.  "start" and "duration" may be arrays of B: a window per robot, each converted with the same round(t / dt)
+    (`set_push` with arrays), robot b being the bits it is under the scalar window of its own.  A layer that has a push of the caller's attached already is refused with ValueError: the call would replace
     it and leave nothing attached.
     integrator: "explicit" or "implicit" sets the layer's integrator first (`BatchedTorqueLayer.set_integrator`; it stays
     set), None leaves it as it is.  With "implicit", dt = 2e-3 and n_sub = 5 run the same 10 ms control step in a quarter of
@@ -129,8 +131,14 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
         if integrator is not None:
             layer.set_integrator(integrator)
         if push is not None:
-            layer.set_push(torch.as_tensor(push["force"], dtype=torch.float32, device=layer.device).reshape(-1, 3),
-                           start_substep=int(round(float(push["start"]) / float(dt))), n_substeps=int(round(float(push["duration"]) / float(dt))))
+            force = torch.as_tensor(push["force"], dtype=torch.float32, device=layer.device).reshape(-1, 3)
+            windows = push_windows(push, force.shape[0])
+            if windows is None:
+                layer.set_push(force, start_substep=int(round(float(push["start"]) / float(dt))),
+                               n_substeps=int(round(float(push["duration"]) / float(dt))))
+            else:                                         # a window per robot, each converted as the scalar one is
+                first, count = ([int(round(float(t) / float(dt))) for t in w] for w in windows)
+                layer.set_push(force, start_substep=first, n_substeps=count)
         q, v, S, A, failed = layer.policy_rollout(policy, q0, v0, n_steps, dt, n_sub, goal, tau_ff=tau_ff, kp=kp, kd=kd,
                                                   ground=GroundContact() if ground is None else ground, t0=t0,
                                                   period=NOMINAL_PERIOD if period is None else period, db=db,

@@ -35,15 +35,51 @@ from .solver import (NMPC_ROLLOUT_FLAG_COLLISION as FLAG_COLLISION, NMPC_ROLLOUT
 from .workloads import FEET, HIP_OFFSETS, MODEL_CENTROIDAL, model_params
 
 
-def sample_pushes(n: int, seed, start: float = 0.0, duration: float = 0.3, magnitude=(50.0, 70.0)) -> dict:
+def sample_pushes(n: int, seed, start=0.0, duration=0.3, magnitude=(50.0, 70.0)) -> dict:
     """n base pushes as the reference's data collection draws them (bc_experimental.yaml:32-35,
     data_collection_force_perturbation.py:213-248): direction uniform in the cube, normalised, magnitude uniform in
-    `magnitude` newtons.  seed: anything numpy's SeedSequence takes (e.g. (rank, iteration, attempt))."""
+    `magnitude` newtons.  seed: anything numpy's SeedSequence takes (e.g. (rank, iteration, attempt)).
+    start, duration: seconds, or arrays of n (a window per rollout, e.g. `sample_push_windows`'s), passed through."""
     rng = np.random.default_rng(seed)
     force = rng.uniform(-1.0, 1.0, (n, 3))
     force /= np.linalg.norm(force, axis=1, keepdims=True) + 1e-6
     force *= rng.uniform(magnitude[0], magnitude[1], (n, 1))
-    return dict(start=float(start), duration=float(duration), force=force)
+    if np.ndim(start) == 0 and np.ndim(duration) == 0:
+        return dict(start=float(start), duration=float(duration), force=force)
+    start, duration = push_windows(dict(start=start, duration=duration), n)
+    return dict(start=start, duration=duration, force=force)
+
+
+def sample_push_windows(n: int, seed, period: float, n_points: int = 10, duration=(0.2, 0.4)) -> dict:
+    """A push window per rollout as the reference's data collection draws them
+    (data_collection_pretrain_omini_vc_policy_1direction_perturbed.py:191-247): the start at one of `n_points` equally spaced
+    replanning points of the gait cycle, k period / n_points with k uniform in 0 .. n_points - 1, and a duration uniform in
+    `duration` seconds.  -> {"start": [n], "duration": [n]} (float64), which merges into a push dict:
+    dict(sample_pushes(n, seed), **sample_push_windows(n, seed, period))."""
+    if n_points < 1 or not period > 0.0:
+        raise ValueError("sample_push_windows: need n_points >= 1 and period > 0")
+    rng = np.random.default_rng(seed)
+    point = rng.integers(0, n_points, n)
+    return dict(start=point * (float(period) / n_points), duration=rng.uniform(duration[0], duration[1], n))
+
+
+def push_windows(push: Optional[dict], n: int):
+    """The windows of a push dict whose "start" or "duration" is an array: (start [n], duration [n]) float64, a scalar among the
+    two holding for every rollout; None for a dict with scalar windows (or no dict), which takes the uniform path.  An array
+    of another length than n is refused with ValueError."""
+    if push is None or (np.ndim(push["start"]) == 0 and np.ndim(push["duration"]) == 0):
+        return None
+    out = []
+    for key in ("start", "duration"):
+        a = push[key]
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(n, float(a))
+        if a.shape != (n,):
+            raise ValueError(f"push[{key!r}]: need a scalar or {n} entries (one per rollout), got shape {a.shape}")
+        out.append(a)
+    return out[0], out[1]
 
 
 def state_row_flags(rows: np.ndarray, v_des: np.ndarray, collision_height: float = COLLISION_HEIGHT) -> np.ndarray:
@@ -304,6 +340,14 @@ class BatchedLocomotionMPC:
         times = np.arange(n_replans) * self.replanning_steps * self.sim_dt
         if getattr(self, "_gait_dev", None) is None:
             self._gait_dev = s.to_device(self.contact_planner.gait_sequence, torch.int8)
+        windows = push_windows(push, x.shape[0])
+        if windows is not None:             # a window per rollout: attached for this call, the cfg's own window unused
+            s.set_rollout_push_windows(*windows)
+            try:
+                return self._device_rollout(n_replans, start_node, first_solve, dict(push, start=0.0, duration=0.0), x, v_des, w_des,
+                                            ref_state, foot, X, U, status)
+            finally:
+                s.set_rollout_push_windows(None)
         return s.rollout(
             self._gait_dev, x, v_des, w_des, ref_state, foot, s.to_device(np.asarray(push["force"])) if push else None,
             np.round((times % period) / period, 4), X, U, status,
@@ -356,7 +400,8 @@ class BatchedLocomotionMPC:
         `max_attempts` times in all (the reference loops without a cap); what is still invalid then keeps its flags and
         gets no sampling weight in the learning update (parallel.learning_update).
 
-        push_sampler(n, attempt) -> {"start", "duration", "force": [n, 3]}; the rollouts listed in `nominal` are never
+        push_sampler(n, attempt) -> {"start", "duration", "force": [n, 3]} ("start" and "duration" scalars, or arrays of n: a
+        window per rollout, and then per candidate of a redo pass); the rollouts listed in `nominal` are never
         pushed (and never redone).  `fill_batch` > 0: a redo pass over n rollouts rolls max(1, min(fill_batch, batch) // n) candidates
         of each, every one with its own new push, and keeps the FIRST that runs to the end -- the same distribution as the
         reference's one-after-the-other redo (independent pushes, first success kept), but the late passes over a

@@ -251,7 +251,9 @@ class LocomotionMPC:
         `replanning_steps` simulation steps -- one host call, no round trip per replan, the whole batch at once.
         Returns S [B, K, 44] (device): the recorded rows of `state_rows` -- one per simulation step, K as `open_loop`
         runs, or one per replan (the state it starts from) with record_sim_steps=False.  push = {"start", "duration",
-        "force": [B, 3]}: velocity impulse F dt / m on the base per replanning interval.  The controller's counters,
+        "force": [B, 3]}: velocity impulse F dt / m on the base per replanning interval; "start" and "duration" may be arrays of
+        B, a window per rollout (`BatchedNmpcSolver.set_rollout_push_windows`, attached for this call: rollout b is the bits
+        it is under the scalar window of its own, in every mode below and across resumed calls).  The controller's counters,
         reference and solution views advance as in `open_loop`; `self.failed` holds the NMPC_ROLLOUT_FLAG_* bits,
         `self.q_final` / `self.v_final` the plant state.
         torque_layer (a `BatchedTorqueLayer` of the robot; needs rows per simulation step): the expert's action labels are
@@ -319,6 +321,10 @@ class LocomotionMPC:
             raise ValueError("push_as_force: a push as a force needs the contact plant, give plant")
         kp = (self.Kp if plant is not None else KP) if kp is None else kp
         kd = (self.Kd if plant is not None else KD) if kd is None else kd
+        from .mpc import push_windows
+        windows = push_windows(push, B)               # a window per rollout: attached for this call, the cfg's own window unused
+        if windows is not None:
+            push = dict(push, start=0.0, duration=0.0)
         A = None
         if torque_layer is not None:
             rows = n_replans * (self.replanning_steps if record_sim_steps else 1)
@@ -332,6 +338,8 @@ class LocomotionMPC:
             if push_as_force:
                 s.set_rollout_plant_push(True)
             s.set_rollout_clock(replan0)
+            if windows is not None:
+                s.set_rollout_push_windows(*windows)
             S, failed = s.wb_rollout(
                 s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
                 nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref), by_rollout(push["force"]) if push else None,
@@ -346,6 +354,8 @@ class LocomotionMPC:
                 nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
                 collision_height=float(collision_height))
         finally:
+            if windows is not None:
+                s.set_rollout_push_windows(None)
             s.set_rollout_clock(0)
             if push_as_force:
                 s.set_rollout_plant_push(False)

@@ -176,6 +176,29 @@ class BatchedNmpcSolver:
         starts at its call.  A negative value and a handle of another model are refused and leave the previous value in force."""
         _lib.check(self.lib.nmpc_wb_rollout_set_clock(self._h, int(replan0)), self._h, "nmpc_wb_rollout_set_clock")
 
+    def set_rollout_push_windows(self, start=None, duration=None):
+        """nmpc_rollout_set_push_windows / nmpc_wb_rollout_set_push_windows (by the model of this solver): while start, duration
+        (B entries each, seconds from step 0 of the rollout; arrays or tensors) are attached, rollout b of every following
+        `rollout` / `wb_rollout` is pushed with its push_force over its own window instead of the cfg's push_start /
+        push_duration, duration[b] <= 0 meaning no push for it -- as a velocity jump or, with a plant and
+        `set_rollout_plant_push(True)`, as a force.  Rollout b is the bits it is under the cfg window of its own.
+        `set_rollout_push_windows(None)` detaches.  This object keeps the two tensors alive while they are attached; a rollout
+        of more rollouts than they have entries, or one without a push_force, is refused."""
+        call, name = ((self.lib.nmpc_wb_rollout_set_push_windows, "nmpc_wb_rollout_set_push_windows") if self.model_id == 2
+                      else (self.lib.nmpc_rollout_set_push_windows, "nmpc_rollout_set_push_windows"))
+        if start is None and duration is None:
+            self._push_windows = None
+            _lib.check(call(self._h, None, None, 0), self._h, name)
+            return
+        if start is None or duration is None:
+            raise ValueError("start and duration come together or not at all")
+        start, duration = (torch.as_tensor(np.asarray(x.detach().cpu()) if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64),
+                                           dtype=torch.float32).to(self.device).contiguous() for x in (start, duration))
+        if start.dim() != 1 or start.shape != duration.shape or start.shape[0] < 1:
+            raise ValueError(f"start, duration: need one entry per rollout each, got {tuple(start.shape)} and {tuple(duration.shape)}")
+        self._push_windows = (start, duration)
+        _lib.check(call(self._h, ptr(start), ptr(duration), start.shape[0]), self._h, name)
+
     MOMENTUM_MODELS = {"declared": 0, "articulated": 1}      # NMPC_WB_MOMENTUM_* of include/nmpc.h
 
     def set_momentum_model(self, model: str = "declared", torque_layer=None):

@@ -77,6 +77,7 @@ class BatchedTorqueLayer:
             self.tree_mass = float(np.float32(np.float32(self.tree_mass) + m_i))
         self._states = None             # set_rollout_states: the attached (Q, V)
         self._push = None               # set_push: the attached force
+        self._push_windows = None       # set_push with arrays: the attached (first substeps, counts)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -369,22 +370,59 @@ class BatchedTorqueLayer:
         self._states = (Q, V)
         _lib.check(self.lib.nmpc_policy_rollout_set_states(self._h, ptr(Q), ptr(V), qv_rows), self._h, "nmpc_policy_rollout_set_states", "torque")
 
-    def set_push(self, force: Optional[torch.Tensor] = None, start_substep: int = 0, n_substeps: int = 0, joint: int = 5):
+    def set_push(self, force: Optional[torch.Tensor] = None, start_substep=0, n_substeps=0, joint: int = 5):
         """nmpc_contact_set_push: while force [B, 3] (N, world frame, no moment) is attached, robot b of every `contact_step`,
         `contact_track` and `policy_rollout` of this layer is pushed with force[b] at the origin of the body frame of `joint`
         (5: the trunk) in the substeps start_substep <= s < start_substep + n_substeps, s counted from 0 at the start of each
         call (s = k n_sub + i for substep i of control step k).  start_substep may be negative: the window is cut to the call,
         so a chain of calls with the window moved along is the long call.  Calls with more robots than force has rows are
         refused.  `set_push(None)` detaches; detached, or with a window that misses the call, every call is the bits it is
-        without.  The layer keeps the tensor alive while it is attached."""
+        without.  The layer keeps the tensor alive while it is attached.
+        start_substep and n_substeps may also be integer arrays or tensors of B entries (one of them may stay a scalar, which
+        then holds for every robot): a window per robot (nmpc_contact_set_push_windows), robot b pushed in
+        start_substep[b] <= s < start_substep[b] + n_substeps[b], n_substeps[b] <= 0 meaning no push for it.  Robot b is then
+        the bits it is under the scalar window of its own; the layer keeps the two tensors alive, and `set_push(None)`
+        detaches them with the force.  With scalars the calls made are the ones made before there were arrays."""
         if force is None:
             self._push = None
             _lib.check(self.lib.nmpc_contact_set_push(self._h, None), self._h, "nmpc_contact_set_push", "torque")
+            self._set_push_windows(None, None)
             return
         force = self._in(force, (3,), "force")
+        per_robot = [not isinstance(x, (int, np.integer)) and np.ndim(x) > 0 for x in (start_substep, n_substeps)]
+        first = count = None
+        if any(per_robot):
+            first, count = (self._window(x, force.shape[0], name) for x, name in ((start_substep, "start_substep"), (n_substeps, "n_substeps")))
+            start_substep = n_substeps = 0
         cfg = _lib.NmpcPushCfg(force.data_ptr(), force.shape[0], int(joint), int(start_substep), int(n_substeps))
         _lib.check(self.lib.nmpc_contact_set_push(self._h, ctypes.byref(cfg)), self._h, "nmpc_contact_set_push", "torque")
         self._push = force
+        self._set_push_windows(first, count)
+
+    def _window(self, x, B, name):
+        """x, B window entries (or one for all) as a contiguous int32 [B] tensor on the device"""
+        if isinstance(x, torch.Tensor):
+            if x.is_floating_point() or x.dtype == torch.bool:
+                raise ValueError(f"{name}: need integers")
+            t = x.to(device=self.device, dtype=torch.int32)
+        else:
+            a = np.asarray(x)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"{name}: need integers")
+            t = torch.as_tensor(a.astype(np.int32), device=self.device)
+        if t.dim() == 0:
+            t = t.expand(B)
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"{name}: need {B} entries (one per row of force), got {tuple(t.shape)}")
+        return t.contiguous()
+
+    def _set_push_windows(self, first, count):
+        """attach the windows per robot, or detach them -- a call only where something is or was attached"""
+        if first is None and self._push_windows is None:
+            return
+        self._push_windows = None if first is None else (first, count)
+        _lib.check(self.lib.nmpc_contact_set_push_windows(self._h, ptr(first), ptr(count), 0 if first is None else first.shape[0]),
+                   self._h, "nmpc_contact_set_push_windows", "torque")
 
     def _state_io(self, t, name):
         """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""

@@ -1,0 +1,216 @@
+"""GPU checks of the push windows per robot on the contact plant (nmpc_contact_set_push_windows behind
+`BatchedTorqueLayer.set_push` with arrays): robot b of a call with windows attached is held bit for bit to robot b of the same
+call -- same B, same row -- made with the scalar window set to b's, under both integrators.  The scalar path is the one the
+other push tests hold to the fp64 reference (tests/test_gpu_push_step.py, tests/test_gpu_push_track.py,
+tests/test_gpu_push_policy_rollout.py); under the explicit integrator it is the cut into un-pushed and pushed launches, so the
+comparison is that of the one windowed kernel against the kernels it takes its two substeps from.
+
+The quadruped tree on the default ground from a standing start, every robot with a force and a PD target of its own."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.solve_helpers import dev, policy_pair  # noqa: F401
+from tests.torque_helpers import same
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+KP, KD, DT = 20.0, 1.5, 5e-4
+INTEGRATORS = ("explicit", "implicit")
+# nmpc_contact_step_batch, n_sub = 8: the whole call, inside it, from before it, missing it, none, running past its end
+STEP_SUB, STEP_WINDOWS = 8, [(0, 8), (2, 3), (-2, 4), (8, 3), (5, 0), (6, 10)]
+# the track and the policy rollout, 3 control steps of 4 substeps: inside control step 1, straddling steps 0 and 1, all, none
+K, N_SUB, TRACK_WINDOWS = 3, 4, [(5, 2), (3, 3), (-1, 20), (4, 0)]
+PERIOD, T0, HEIGHT, MASK = 0.5, 0.37, 0.08, 2 | 4 | 8 | 32
+
+
+class World:
+    """the layer, B = 6 standing robots and what drives them: made once, never written to"""
+    B = 6
+
+    def __init__(self, device):
+        from iterative_learning_nmpc_amd import wholebody as wbk
+        from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer, GroundContact
+        self.L = BatchedTorqueLayer(**quadruped_tree(), device=device)
+        self.ground = GroundContact()
+        rng = np.random.default_rng(41)
+        t = lambda x: torch.as_tensor(np.asarray(x, np.float32), device=self.L.device).contiguous()      # noqa: E731
+        q0 = np.zeros((self.B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME
+        self.q, self.v = t(q0), t(np.zeros((self.B, 18)))
+        self.F = t(rng.uniform(-80, 80, (self.B, 3)))
+        self.q_des = t(q0[:, 6:] + rng.uniform(-0.1, 0.1, (self.B, 12)))
+        self.A = t(q0[:, None, 6:] + rng.uniform(-0.1, 0.1, (self.B, K, 12)))
+        self.goal = t(rng.uniform(-0.5, 0.5, (self.B, 3)))
+        self.policy = policy_pair(47, 12, 1, 64, True, 64, seed=5)[0]
+
+    def step(self, B=B):
+        return self.L.contact_step(self.q[:B], self.v[:B], DT, STEP_SUB, q_des=self.q_des[:B], kp=KP, kd=KD, ground=self.ground)
+
+    def track(self, B=4, **kw):
+        q, v = self.q[:B].clone(), self.v[:B].clone()
+        return self.L.contact_track(q, v, self.A[:B], DT, N_SUB, kp=KP, kd=KD, ground=self.ground, **kw)
+
+    def rollout(self, B=4):
+        return self.L.policy_rollout(self.policy, self.q[:B], self.v[:B], K, DT, N_SUB, self.goal[:B], kp=KP, kd=KD, ground=self.ground,
+                                     t0=T0, period=PERIOD, terminate_mask=MASK, collision_height=HEIGHT)
+
+
+@pytest.fixture(scope="module")
+def world(dev):
+    return World(dev)
+
+
+@pytest.fixture()
+def detached(world):
+    """whatever a test attaches or sets is gone after it, also when it fails"""
+    yield
+    world.L.set_push(None)
+    world.L.lib.nmpc_contact_set_push_windows(world.L._h, None, None, 0)
+    world.L.set_integrator("explicit")
+
+
+def arrays(windows):
+    return [w[0] for w in windows], [w[1] for w in windows]
+
+
+def rows_equal(got, ref, b):
+    return all(torch.equal(x[b], y[b]) if x.dtype == torch.int32 else same(x[b], y[b]) for x, y in zip(got, ref))
+
+
+def held_row_by_row(world, windows, call, names):
+    """`call()` with the windows attached against `call()` under each robot's window as the scalar one"""
+    L, B = world.L, len(windows)
+    plain = call()
+    L.set_push(world.F[:B], *arrays(windows))
+    got = call()
+    assert L._push_windows is not None
+    moved = []
+    for b, (first, count) in enumerate(windows):
+        L.set_push(world.F[:B], first, count)
+        assert L._push_windows is None                    # scalars: the windows are gone, the calls are the scalar path's
+        ref = call()
+        for name, x, y in zip(names, got, ref):
+            print(f"  robot {b} window ({first}, {count}) {name}: largest |windowed - uniform| {float((x[b].double() - y[b].double()).abs().max()):.3e}")
+        assert rows_equal(got, ref, b), (b, first, count)
+        moved.append(not rows_equal(ref, plain, b))
+    L.set_push(None)
+    return got, plain, moved
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_contact_step_rows_are_the_uniform_calls(world, detached, integrator):
+    world.L.set_integrator(integrator)
+    got, plain, moved = held_row_by_row(world, STEP_WINDOWS, world.step, ("q", "v", "a", "f", "tau"))
+    # the windows that meet the call push their robot, the two that do not leave it the un-pushed bits
+    assert moved == [True, True, True, False, False, True]
+    for b in (3, 4):
+        assert rows_equal(got, plain, b)
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_contact_track_rows_are_the_uniform_calls(world, detached, integrator):
+    world.L.set_integrator(integrator)
+    got, plain, moved = held_row_by_row(world, TRACK_WINDOWS, world.track, ("q", "v", "Q", "V"))
+    assert moved == [True, True, True, False] and rows_equal(got, plain, 3)
+    # a skipped robot is untouched, the others are the bits they are without the flags
+    L = world.L
+    L.set_push(world.F[:4], *arrays(TRACK_WINDOWS))
+    skip = torch.tensor([0, 1, 0, 0], dtype=torch.int32, device=L.device)
+    Q, V = (torch.full((4, K, 18), -77.0, device=L.device) for _ in range(2))
+    q, v, Q, V = world.track(Q=Q, V=V, skip=skip, skip_mask=1)
+    assert same(q[1], world.q[1]) and same(v[1], world.v[1]) and bool((Q[1] == -77.0).all()) and bool((V[1] == -77.0).all())
+    for b in (0, 2, 3):
+        assert rows_equal((q, v, Q, V), got, b)
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_policy_rollout_rows_are_the_uniform_calls(world, detached, integrator):
+    world.L.set_integrator(integrator)
+    names = ("q", "v", "S", "A", "failed")
+    got, plain, moved = held_row_by_row(world, TRACK_WINDOWS, world.rollout, names)
+    assert moved == [True, True, True, False] and rows_equal(got, plain, 3)
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_three_steps_with_the_windows_moved_along_are_the_track(world, detached, integrator):
+    L, B = world.L, 4
+    L.set_integrator(integrator)
+    first, count = arrays(TRACK_WINDOWS)
+    L.set_push(world.F[:B], first, count)
+    q_t, v_t, Q_t, V_t = world.track()
+    q, v = world.q[:B], world.v[:B]
+    for k in range(K):
+        assert same(q, Q_t[:, k]) and same(v, V_t[:, k]), k
+        L.set_push(world.F[:B], [f - k * N_SUB for f in first], count)
+        q, v = L.contact_step(q, v, DT, N_SUB, q_des=world.A[:B, k], kp=KP, kd=KD, ground=world.ground)[:2]
+    print("largest |chain - track| of q, v:", float((q - q_t).abs().max()), float((v - v_t).abs().max()))
+    assert same(q, q_t) and same(v, v_t)
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_refusals_leave_the_outputs_untouched(world, detached, integrator):
+    from iterative_learning_nmpc_amd import _lib
+    from iterative_learning_nmpc_amd._lib import NmpcError
+    L, B = world.L, world.B
+    L.set_integrator(integrator)
+    lib, ptr = L.lib, _lib.ptr
+    text = lambda: lib.nmpc_torque_last_error(L._h).decode()      # noqa: E731
+    first, count = (torch.as_tensor(x, dtype=torch.int32, device=L.device) for x in arrays(STEP_WINDOWS))
+    outs = [torch.full(s, -77.0, device=L.device) for s in ((B, 18), (B, 18), (B, 18), (B, 4, 3), (B, 12))]
+    cfg, st = world.ground.cfg(), _lib.stream(L.device)
+    step = lambda: lib.nmpc_contact_step_batch(L._h, B, STEP_SUB, DT, ctypes.byref(cfg), ptr(world.q), ptr(world.v), None, ptr(world.q_des),      # noqa: E731
+                                               KP, KD, *[ptr(x) for x in outs], st)
+    untouched = lambda: all(bool((x == -77.0).all()) for x in outs)      # noqa: E731
+    # only one array, or no rows: refused at the attachment, nothing is attached
+    assert lib.nmpc_contact_set_push_windows(L._h, ptr(first), None, B) == -1 and "come together" in text()
+    assert lib.nmpc_contact_set_push_windows(L._h, None, ptr(count), B) == -1 and "come together" in text()
+    assert lib.nmpc_contact_set_push_windows(L._h, ptr(first), ptr(count), 0) == -1 and "rows must be at least 1" in text()
+    plain = world.step()
+    # windows and no push: refused at the plant call, before any launch
+    assert lib.nmpc_contact_set_push_windows(L._h, ptr(first), ptr(count), B) == 0
+    assert step() == -1 and "no push is attached" in text()
+    torch.cuda.synchronize()
+    assert untouched()
+    q, v = world.q[:4].clone(), world.v[:4].clone()
+    with pytest.raises(NmpcError, match="no push is attached"):
+        L.contact_track(q, v, world.A[:4], DT, N_SUB, kp=KP, kd=KD, ground=world.ground)
+    with pytest.raises(NmpcError, match="no push is attached"):
+        world.rollout()
+    assert same(q, world.q[:4]) and same(v, world.v[:4])
+    # more robots than the windows have rows (the force has rows for all)
+    L.set_push(world.F, 0, 1)
+    assert lib.nmpc_contact_set_push_windows(L._h, ptr(first), ptr(count), 4) == 0
+    assert step() == -1 and "B exceeds rows" in text()
+    torch.cuda.synchronize()
+    assert untouched()
+    # a refused attachment leaves the attached windows in force: four robots run under them
+    assert lib.nmpc_contact_set_push_windows(L._h, ptr(first), None, 4) == -1
+    got = world.step(4)
+    L.set_push(world.F, 2, 3)
+    assert lib.nmpc_contact_set_push_windows(L._h, None, None, 0) == 0
+    assert rows_equal(got, world.step(4), 1) and not rows_equal(got, plain, 1)
+    # the Python layer: arrays of another length than the force has rows
+    with pytest.raises(ValueError, match="start_substep"):
+        L.set_push(world.F, [0, 1, 2], 3)
+    with pytest.raises(ValueError, match="n_substeps"):
+        L.set_push(world.F, 0, [1.5] * B)
+    # detached, every call is the un-pushed one again
+    L.set_push(None)
+    assert L._push is None and L._push_windows is None
+    assert all(same(x, y) for x, y in zip(world.step(), plain))
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_after_detaching_the_calls_are_the_unpushed_bits(world, detached, integrator):
+    L = world.L
+    L.set_integrator(integrator)
+    plain = (world.step(), world.track(), world.rollout())
+    L.set_push(world.F, *arrays(STEP_WINDOWS))
+    assert not same(world.step()[1], plain[0][1])
+    L.set_push(None)
+    after = (world.step(), world.track(), world.rollout())
+    for got, ref in zip(after, plain):
+        assert all(torch.equal(x, y) if x.dtype == torch.int32 else same(x, y) for x, y in zip(got, ref))
