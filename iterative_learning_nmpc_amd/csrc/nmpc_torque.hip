@@ -13,10 +13,11 @@
 // is nmpc_torque_fd.hip.inc, included below; the declared ground-contact law, the foot kinematics it needs and the plant step
 // that evaluates it inside that recursion are nmpc_torque_contact.hip.inc; the observation of a plant state for a policy in the
 // loop is nmpc_torque_policy.hip.inc, and the loop itself (nmpc_policy_rollout_batch) is host code at the end of this file;
-// a table of PD targets tracked on the plant in one launch, and the rows of the states it ran through, are
-// nmpc_torque_track.hip.inc; what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of
-// one composite-rigid-body pass -- is nmpc_torque_crba.hip.inc; the plant's second integrator, which takes the stiff contact and PD
-// terms implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; the centroidal momentum about an anchor
+// what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of one composite-rigid-body
+// pass -- is nmpc_torque_crba.hip.inc; the correction of the plant's second integrator, which takes the stiff contact and PD terms
+// implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; the chain of control steps on the plant -- one
+// kernel text, instantiated for a table of PD targets tracked in one launch, for pushed substeps, for a push window per robot
+// and for the implicit integrator -- and the rows of the states it ran through are nmpc_torque_track.hip.inc; the centroidal momentum about an anchor
 // point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
 // momentum A_g(q) v of a plant state alone, which the device rollouts put into x0.
@@ -355,9 +356,9 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_fd.hip.inc"
 #include "nmpc_torque_contact.hip.inc"
 #include "nmpc_torque_policy.hip.inc"
-#include "nmpc_torque_track.hip.inc"
 #include "nmpc_torque_crba.hip.inc"
 #include "nmpc_torque_implicit.hip.inc"
+#include "nmpc_torque_track.hip.inc"
 #include "nmpc_torque_centroidal.hip.inc"
 
 }  // namespace nmpc_torque
@@ -401,6 +402,20 @@ int launch_step(Torque* t, void (*kernel)(const Model*, Args), int width, size_t
     return launched(t);
 }
 
+// the instantiation of contact_chain_kernel for Args at a run-time block width; the implicit chain has the one width IM_W
+template <class Args>
+auto chain_kernel(int w) {
+    if constexpr (Args::implicit) return contact_chain_kernel<IM_W, Args>;
+    else return w == 32 ? contact_chain_kernel<32, Args> : contact_chain_kernel<16, Args>;
+}
+
+// one launch of the chain: at the handle's width of the contact step, or the implicit chain's own with its triangle behind the slice
+template <class Args>
+int launch_chain(Torque* t, const Args& p, void* stream) {
+    const int w = Args::implicit ? IM_W : t->ct_width, n = t->host.n;
+    return launch_step(t, chain_kernel<Args>(w), w, Args::implicit ? im_lds_bytes(n) : ct_lds_bytes(n, w), p, stream);
+}
+
 // one of the element-wise kernels: a thread per entry of a [B][nu] table
 template <class... KArgs, class... Args>
 int launch_elementwise(Torque* t, void (*kernel)(int, KArgs...), int B, void* stream, Args... args) {
@@ -437,13 +452,13 @@ int allocate(Torque* t) {
     LDS_LIMIT(foot_kernel, fk_lds_bytes(MAXJ));
     const size_t ct_lds = t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16);
     LDS_LIMIT(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width), ct_lds);
-    LDS_LIMIT(KERNEL_AT_WIDTH(contact_track_kernel, t->ct_width), ct_lds);
-    LDS_LIMIT(KERNEL_AT_WIDTH(contact_push_kernel, t->ct_width), ct_lds);
-    LDS_LIMIT(KERNEL_AT_WIDTH(contact_window_kernel, t->ct_width), ct_lds);
-    // the composite-inertia pass, the implicit plant step (slice and triangle) and the three entry points of the centroidal kernel:
+    LDS_LIMIT(chain_kernel<TrackArgs>(t->ct_width), ct_lds);
+    LDS_LIMIT(chain_kernel<PushArgs>(t->ct_width), ct_lds);
+    LDS_LIMIT(chain_kernel<WindowArgs>(t->ct_width), ct_lds);
+    // the composite-inertia pass, the implicit chain (slice and triangle) and the three entry points of the centroidal kernel:
     // the slice of the largest tree at the one width each has
     LDS_LIMIT(crba_kernel, crba_lds_bytes(MAXJ, CR_W));
-    LDS_LIMIT(contact_implicit_kernel<IM_W>, im_lds_bytes(MAXJ));
+    LDS_LIMIT(chain_kernel<ImplicitArgs>(IM_W), im_lds_bytes(MAXJ));
     LDS_LIMIT(centroidal_kernel<CmdIo>, centroidal_lds_bytes<CmdIo>(MAXJ));
     LDS_LIMIT(centroidal_kernel<NodeRecordIo>, centroidal_lds_bytes<NodeRecordIo>(MAXJ));
     LDS_LIMIT(centroidal_kernel<StateMomentumIo>, centroidal_lds_bytes<StateMomentumIo>(MAXJ));
@@ -539,8 +554,9 @@ Window push_window(const nmpc_push_cfg& push, long long s0, long long total) {
     return w;
 }
 
-// why the windows per robot cannot serve a plant call of B robots under `push` (nullptr: they can, or there are none)
-const char* windows_refusal(const nmpc_torque::PushWindows& wins, const nmpc_push_cfg& push, int B) {
+// why `push` and the windows per robot cannot serve a plant call of B robots (nullptr: they can, or there are none)
+const char* push_batch_refusal(const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, int B) {
+    if (push.force && B > push.force_rows) return "push: B exceeds force_rows";
     if (!wins.first) return nullptr;
     if (!push.force) return "push windows: no push is attached (nmpc_contact_set_push)";
     if (B > wins.rows) return "push windows: B exceeds rows";
@@ -548,7 +564,7 @@ const char* windows_refusal(const nmpc_torque::PushWindows& wins, const nmpc_pus
 }
 
 // A plant call under a push is cut into runs of substeps that are all un-pushed -- launches of the un-pushed kernels, as a call
-// without a push makes them -- and runs that are all pushed, launches of contact_push_kernel (nmpc_torque_track.hip.inc says why).
+// without a push makes them -- and runs that are all pushed, launches of the PushArgs chain (nmpc_torque_track.hip.inc says why).
 
 // why the implicit integrator cannot run a tree of n joints (nullptr: it can)
 const char* implicit_refusal(int n) {
@@ -556,19 +572,37 @@ const char* implicit_refusal(int n) {
     return nullptr;
 }
 
-// both plant calls under the implicit integrator: one launch of contact_implicit_kernel, the push window -- the push's own, or
-// with `wins` the robot's, in a call whose substep 0 is substep s0 of their count -- tested inside it
-int launch_implicit(Torque* t, ImplicitArgs& p, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins, long long s0,
-                    void* stream) {
+// The arguments every launch of the chain shares; a caller adds what is its own -- the step its start state and the outputs of
+// the last substep, the track its rows and skip flags -- and a launch the push, the windows and the piece of the call it runs.
+PushArgs chain_args(int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg& cfg, const float* tau_ff, const float* A, int a_rows, float kp,
+                    float kd, float* q, float* v) {
+    PushArgs p{};
+    p.B = B; p.n_steps = n_steps; p.n_sub = n_sub; p.a_rows = a_rows; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(cfg);
+    p.tau = tau_ff; p.A = A; p.q = q; p.v = v;
+    return p;
+}
+
+// a plant call under the implicit integrator: one launch of the ImplicitArgs chain, the push window -- the push's own, or with
+// `wins` the robot's, in a call whose substep 0 is substep s0 of their count -- tested inside it
+int launch_implicit(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins,
+                    long long s0, void* stream) {
+    ImplicitArgs p{call};
     if (win.hi > win.lo) { p.force = push.force; p.joint = push.joint; p.push_lo = win.lo; p.push_hi = win.hi; }
     if (wins.first) { p.force = push.force; p.joint = push.joint; p.win_first = wins.first; p.win_count = wins.count; p.win_s0 = s0; }
-    return launch_step(t, contact_implicit_kernel<IM_W>, IM_W, im_lds_bytes(t->host.n), p, stream);
+    return launch_chain(t, p, stream);
+}
+
+// a plant call of the explicit integrator under windows per robot: one launch of the WindowArgs chain
+int launch_windowed(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, long long s0, void* stream) {
+    WindowArgs p{call};
+    p.force = push.force; p.joint = push.joint; p.first = wins.first; p.count = wins.count; p.s0 = s0;
+    return launch_chain(t, p, stream);
 }
 
 // nmpc_contact_step_batch under an explicit push: the call's substep i is substep s0 + i of the count `push` is stated in.
 // At most three launches: before, inside and after the window; the first reads q, v, the later ones go on in place on q_out,
 // v_out, and the last one writes a_out, f_out, tau_out.  With windows per robot (`wins`, stated in the same count): one launch of
-// contact_window_kernel, or of the implicit kernel.
+// the windowed chain, or of the implicit one.
 int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* cfg, const float* q, const float* v, const float* tau_ff,
                  const float* q_des, float kp, float kd, float* q_out, float* v_out, float* a_out, float* f_out, float* tau_out,
                  const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, long long s0, void* stream) {
@@ -576,27 +610,13 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
     if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
     if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
-    if (push.force && B > push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
-    if (const char* why = windows_refusal(wins, push, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = push_batch_refusal(push, wins, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
-    const int w = t->ct_width;
-    const size_t lds = ct_lds_bytes(t->host.n, w);
     const Window win = wins.first ? Window{} : push_window(push, s0, n_sub);
-    if (t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT) {
-        ImplicitArgs p{};
-        p.B = B; p.n_steps = 1; p.n_sub = n_sub; p.a_rows = 1; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
-        p.tau = tau_ff; p.A = q_des; p.q = q_out; p.v = v_out; p.q_in = q; p.v_in = v;
-        p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out;
-        return launch_implicit(t, p, push, win, wins, s0, stream);
-    }
-    if (wins.first) {
-        WindowArgs p{};
-        p.B = B; p.n_steps = 1; p.n_sub = n_sub; p.a_rows = 1; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
-        p.tau = tau_ff; p.A = q_des; p.q = q_out; p.v = v_out; p.q_in = q; p.v_in = v;
-        p.force = push.force; p.joint = push.joint; p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out;
-        p.first = wins.first; p.count = wins.count; p.s0 = s0;
-        return launch_step(t, KERNEL_AT_WIDTH(contact_window_kernel, w), w, lds, p, stream);
-    }
+    PushArgs call = chain_args(B, 1, n_sub, dt, *cfg, tau_ff, q_des, 1, kp, kd, q_out, v_out);
+    call.q_in = q; call.v_in = v; call.a_out = a_out; call.f_out = f_out; call.tau_out = tau_out;
+    if (t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT) return launch_implicit(t, call, push, win, wins, s0, stream);
+    if (wins.first) return launch_windowed(t, call, push, wins, s0, stream);
     const int cuts[4] = {0, (int)win.lo, (int)win.hi, n_sub};
     bool first = true;
     for (int r = 0; r < 3; ++r) {
@@ -605,18 +625,17 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
         const bool last = cuts[r + 1] == n_sub;
         const float *qi = first ? q : q_out, *vi = first ? v : v_out;
         if (r == 1) {
-            PushArgs p{};
-            p.B = B; p.n_steps = 1; p.n_sub = count; p.a_rows = 1; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
-            p.tau = tau_ff; p.A = q_des; p.q = q_out; p.v = v_out; p.q_in = qi; p.v_in = vi;
-            p.force = push.force; p.joint = push.joint;
-            if (last) { p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out; }
-            if (const int rc = launch_step(t, KERNEL_AT_WIDTH(contact_push_kernel, w), w, lds, p, stream)) return rc;
+            PushArgs p = call;
+            p.n_sub = count; p.q_in = qi; p.v_in = vi; p.force = push.force; p.joint = push.joint;
+            if (!last) p.a_out = p.f_out = p.tau_out = nullptr;
+            if (const int rc = launch_chain(t, p, stream)) return rc;
         } else {
+            const int w = t->ct_width;
             ContactArgs p{};
             p.B = B; p.n_sub = count; p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
             p.q = qi; p.v = vi; p.tau = tau_ff; p.q_des = q_des; p.q_out = q_out; p.v_out = v_out;
             if (last) { p.a_out = a_out; p.f_out = f_out; p.tau_out = tau_out; }
-            if (const int rc = launch_step(t, KERNEL_AT_WIDTH(contact_step_kernel, w), w, lds, p, stream)) return rc;
+            if (const int rc = launch_step(t, KERNEL_AT_WIDTH(contact_step_kernel, w), w, ct_lds_bytes(t->host.n, w), p, stream)) return rc;
         }
         first = false;
     }
@@ -640,36 +659,24 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
     if (Q && qv_rows < n_steps) return fail(t, NMPC_E_ARG, "qv_rows must be at least n_steps");
     if (Q && !whole_body_tree(t->host))
         return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
-    if (push.force && B > push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
-    if (const char* why = windows_refusal(wins, push, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = push_batch_refusal(push, wins, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
-    const int w = t->ct_width, n = t->host.n, nu = t->host.nu;
-    const size_t lds = ct_lds_bytes(n, w);
+    const int n = t->host.n, nu = t->host.nu;
     const long long total = (long long)n_steps * n_sub;
     const Window win = wins.first ? Window{} : push_window(push, 0, total);
-    if (t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT) {
-        ImplicitArgs p{};
-        p.B = B; p.n_steps = n_steps; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
-        p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
-        p.tau = tau_ff; p.A = A; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v; p.Q = Q; p.V = V;
-        return launch_implicit(t, p, push, win, wins, s0, stream);
-    }
-    if (wins.first) {
-        WindowArgs p{};
-        p.B = B; p.n_steps = n_steps; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
-        p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
-        p.tau = tau_ff; p.A = A; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v; p.Q = Q; p.V = V;
-        p.force = push.force; p.joint = push.joint; p.first = wins.first; p.count = wins.count; p.s0 = s0;
-        return launch_step(t, KERNEL_AT_WIDTH(contact_window_kernel, w), w, lds, p, stream);
+    PushArgs call = chain_args(B, n_steps, n_sub, dt, *cfg, tau_ff, A, a_rows, kp, kd, q, v);
+    call.qv_rows = qv_rows; call.skip_mask = skip ? skip_mask : 0; call.skip = call.skip_mask ? skip : nullptr;
+    const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
+    if (implicit || wins.first) {                // one launch for the whole table; the cut path below moves A, Q, V piece by piece
+        call.Q = Q; call.V = V;
+        return implicit ? launch_implicit(t, call, push, win, wins, s0, stream) : launch_windowed(t, call, push, wins, s0, stream);
     }
     for (long long s = 0; s < total;) {
         const bool pushed = s >= win.lo && s < win.hi;
         const long long change = s < win.lo ? win.lo : (s < win.hi ? win.hi : total);      // where the kind of substep changes next
         const long long k = s / n_sub, i0 = s % n_sub, step_end = (k + 1) * n_sub;
-        PushArgs p{};
-        p.B = B; p.n_sub = n_sub; p.a_rows = a_rows; p.qv_rows = qv_rows; p.skip_mask = skip ? skip_mask : 0;
-        p.dt = dt; p.kp = kp; p.kd = kd; p.c = device_cfg(*cfg);
-        p.tau = tau_ff; p.A = A + (size_t)k * nu; p.skip = p.skip_mask ? skip : nullptr; p.q = q; p.v = v;
+        PushArgs p = call;
+        p.A = A + (size_t)k * nu;
         if (Q && i0 == 0) { p.Q = Q + (size_t)k * n; p.V = V + (size_t)k * n; }
         if (i0 != 0 || change < step_end) {      // a piece of control step k
             const long long end = change < step_end ? change : step_end;
@@ -682,9 +689,9 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
         int rc;
         if (pushed) {
             p.force = push.force; p.joint = push.joint;
-            rc = launch_step(t, KERNEL_AT_WIDTH(contact_push_kernel, w), w, lds, p, stream);
+            rc = launch_chain(t, p, stream);
         } else {
-            rc = launch_step(t, KERNEL_AT_WIDTH(contact_track_kernel, w), w, lds, static_cast<const TrackArgs&>(p), stream);
+            rc = launch_chain(t, static_cast<const TrackArgs&>(p), stream);
         }
         if (rc) return rc;
     }
@@ -1048,8 +1055,7 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     const auto& rec = t->states;
     if (!rec.Q != !rec.V) return fail(t, NMPC_E_ARG, "states: Q and V come together or not at all");
     if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
-    if (t->push.force && B > t->push.force_rows) return fail(t, NMPC_E_ARG, "push: B exceeds force_rows");
-    if (const char* why = windows_refusal(t->windows, t->push, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = push_batch_refusal(t->push, t->windows, B)) return fail(t, NMPC_E_ARG, why);
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
         NMPC_ENTER(t, t->device);

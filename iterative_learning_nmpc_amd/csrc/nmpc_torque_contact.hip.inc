@@ -137,6 +137,11 @@ struct ContactArgs {
 // written by the last substep as its force and torque are formed (nothing reads them), a_out, q_out, v_out after the last read
 // of the inputs, so q_out, v_out may alias q, v.  The copy loops are kept as written, as fd_kernel's.
 // Both keep their text: as wrappers of one step driver with two plants the bits held, but fd_kernel<32> was 0.7-1.2 % slower.
+// Nor is this kernel an instantiation of contact_chain_kernel (nmpc_torque_track.hip.inc), which states the same substep for
+// every chain of control steps: its arguments are another struct (inputs apart from the outputs, one target row, no table, no
+// skip flags) and it writes NaN on the way out where the chain fills the slice, so joining would take a switch at every one of
+// those places.  That was not tried when the chain became one text (DESIGN.md 8d): a fix to the PD law, the clamp, the Euler
+// update or the NaN rule goes here and into the chain.
 template <int W>
 __global__ __launch_bounds__(W) void contact_step_kernel(const Model* __restrict__ mp, const ContactArgs p) {
     extern __shared__ float body[];                       // [joint][CT_SLOTS][W]

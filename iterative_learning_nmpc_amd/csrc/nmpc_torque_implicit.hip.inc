@@ -1,6 +1,6 @@
 // nmpc_torque_implicit.hip.inc -- the linearly implicit integrator of the ground-contact plant (nmpc_contact_set_integrator of
 // include/nmpc_torque.h, which states the scheme); included by nmpc_torque.hip inside namespace nmpc_torque, after
-// nmpc_torque_track.hip.inc and nmpc_torque_crba.hip.inc.
+// nmpc_torque_contact.hip.inc and nmpc_torque_crba.hip.inc and before nmpc_torque_track.hip.inc, whose chain calls it.
 //
 // One substep: the PD law, the clamp and the explicit acceleration a_exp are the explicit step's own (fd_accel_body under the
 // ground law, the push as one more force); then the stiff terms are taken at the end of the substep, linearised at its start:
@@ -11,10 +11,9 @@
 // between foot k and the root, so J_k^T C J_k couples only joints on one path to the root: A has exactly the sparsity of M, and
 // the L^T D L factorisation that eliminates the leaves first (Featherstone, RBDA table 6.3) fills nothing in.  M and A are a
 // packed lower triangle [entry][W] behind the slice; only the entries (i, j) of joints on one path are ever written or read.
-// One kernel serves nmpc_contact_step_batch and nmpc_contact_track_batch (and through them the policy and expert rollouts), with
-// contact_push_kernel's argument conventions, so the integrator has one copy of its substep and a chain of steps is its track
-// bit for bit.  The window of a push is tested per substep inside the kernel: there are no un-pushed bits of another kernel to keep.
-// With windows per robot attached (nmpc_contact_set_push_windows) the same test reads the robot's own window: the launch is the same.
+// This file is the correction alone.  The control steps around it are contact_chain_kernel's (nmpc_torque_track.hip.inc), whose
+// ImplicitArgs instantiation serves nmpc_contact_step_batch and nmpc_contact_track_batch (and through them the policy and expert
+// rollouts): the integrator has one copy of its substep and a chain of steps is its track bit for bit.
 #pragma once
 
 constexpr int IM_W = 16;                                  // robots per block: the slice and the triangle of the largest tree fit the CU
@@ -28,12 +27,6 @@ static_assert(im_lds_bytes(MAXJ) <= FD_LDS_MAX, "the implicit slice of the large
 struct WindowedPushForces : PushedGroundForces {
     bool on;
     __device__ __forceinline__ bool pushed(int i) const { return on && i == joint; }
-};
-
-struct ImplicitArgs : PushArgs {                          // force == nullptr: no push
-    long long push_lo, push_hi;                           // the pushed substeps k * n_sub + s of the launch: [push_lo, push_hi)
-    const int *win_first, *win_count;                     // nmpc_contact_set_push_windows (nullptr: the window above for every robot):
-    long long win_s0;                                     // robot b's window [win_first[b], + win_count[b]) less win_s0 instead
 };
 
 // This thread's packed lower triangle, [entry][W] behind the block's slice.
@@ -206,88 +199,4 @@ __device__ __forceinline__ bool implicit_accel_body(const Model& m, const Contac
         at(i, FD_Q + 2) = x;
     }
     return sound;
-}
-
-// contact_push_kernel's control steps with the implicit substep: a start state apart from q, v and the outputs of the last
-// substep for the step; a table of targets, rows Q, V and skip flags for the track.  NaN rows as that kernel writes them.
-template <int W>
-__global__ __launch_bounds__(W) void contact_implicit_kernel(const Model* __restrict__ mp, const ImplicitArgs p) {
-    extern __shared__ float body[];                       // [joint][CT_SLOTS][W], then the triangle [entry][W], then the law
-    const Model& m = *mp;
-    const int n = m.n, nu = m.nu, base = n - nu, nf3 = 3 * m.nf;
-    const Triangle<W> tri{body + n * CT_SLOTS * W};
-    ContactCfg* cfg = reinterpret_cast<ContactCfg*>(tri.base + (n * (n + 1) / 2) * W);
-    if (threadIdx.x == 0) *cfg = p.c;
-    __syncthreads();
-    const int b = blockIdx.x * W + threadIdx.x;
-    if (b >= p.B) return;
-    if (p.skip && (p.skip[b] & p.skip_mask)) return;
-    const Slice<CT_SLOTS, W> at;
-    float* qb = p.q + (size_t)b * n;
-    float* vb = p.v + (size_t)b * n;
-    const float* qi = p.q_in ? p.q_in + (size_t)b * n : qb;
-    const float* vi = p.v_in ? p.v_in + (size_t)b * n : vb;
-    const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;
-    float* fo = p.f_out ? p.f_out + (size_t)b * nf3 : nullptr;
-    float* to = p.tau_out ? p.tau_out + (size_t)b * nu : nullptr;
-    const V3 F = p.force ? v3(p.force + (size_t)b * 3) : V3{0, 0, 0};
-    long long push_lo = p.push_lo, push_hi = p.push_hi;
-    if (p.win_first) { push_lo = (long long)p.win_first[b] - p.win_s0; push_hi = push_lo + p.win_count[b]; }      // count <= 0: never pushed
-    const float nan = __builtin_nanf("");
-#pragma clang loop unroll(disable) vectorize(disable)
-    for (int i = 0; i < n; ++i) { at(i, FD_Q) = qi[i]; at(i, FD_Q + 1) = vi[i]; }
-    bool sound = true;
-    for (int k = 0; k < p.n_steps; ++k) {
-        if (p.Q) {
-            float* Qk = p.Q + ((size_t)b * p.qv_rows + k) * n;
-            float* Vk = p.V + ((size_t)b * p.qv_rows + k) * n;
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) { Qk[i] = at(i, FD_Q); Vk[i] = at(i, FD_Q + 1); }
-        }
-        const float* db = p.A ? p.A + ((size_t)b * p.a_rows + k) * nu : nullptr;
-        sound = true;
-        for (int s = 0; s < p.n_sub; ++s) {
-            const bool last = k == p.n_steps - 1 && s == p.n_sub - 1;
-            const long long sub = (long long)k * p.n_sub + s;
-            const bool on = p.force && sub >= push_lo && sub < push_hi;
-            unsigned unclamped = 0;
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) {
-                float t = 0.0f;
-                if (i >= base) {
-                    t = tb ? tb[i - base] : 0.0f;
-                    if (db) t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
-                    const float lim = cfg->tau_max;
-                    if (db && (!(lim > 0.0f) || fabsf(t) < lim)) unclamped |= 1u << i;
-                    if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t);      // a NaN stays NaN
-                    if (last && to) to[i - base] = t;
-                }
-                at(i, FD_Q + 2) = t;
-            }
-            sound = fd_accel_body<W, CT_SLOTS>(m, WindowedPushForces{{{cfg, last ? fo : nullptr}, F, p.joint}, on}) && sound;
-            sound = implicit_accel_body<W>(m, *cfg, tri, p.dt, p.kp, p.kd, unclamped) && sound;
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) {
-                const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);
-                at(i, FD_Q + 1) = v;
-                at(i, FD_Q) = at(i, FD_Q) + p.dt * v;
-            }
-        }
-        if (!sound) {
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) { at(i, FD_Q) = nan; at(i, FD_Q + 1) = nan; }
-        }
-    }
-    // the state, and for the step the outputs of the last substep: NaN rows where the last control step was unsound
-#pragma clang loop unroll(disable) vectorize(disable)
-    for (int i = 0; i < n; ++i) {
-        if (p.a_out) p.a_out[(size_t)b * n + i] = sound ? at(i, FD_Q + 2) : nan;
-        qb[i] = at(i, FD_Q); vb[i] = at(i, FD_Q + 1);
-    }
-    if (!sound) {
-#pragma clang loop unroll(disable) vectorize(disable)
-        for (int i = 0; fo && i < nf3; ++i) fo[i] = nan;
-#pragma clang loop unroll(disable) vectorize(disable)
-        for (int i = 0; to && i < nu; ++i) to[i] = nan;
-    }
 }

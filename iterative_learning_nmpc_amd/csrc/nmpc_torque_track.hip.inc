@@ -1,16 +1,29 @@
-// nmpc_torque_track.hip.inc -- a table of PD targets tracked on the ground-contact plant, and the observation of the states it
-// ran through (nmpc_contact_track_batch, nmpc_observe_rows_batch of include/nmpc_torque.h); included by nmpc_torque.hip inside
-// namespace nmpc_torque, after nmpc_torque_policy.hip.inc.
+// nmpc_torque_track.hip.inc -- the chain of control steps on the ground-contact plant: a table of PD targets tracked in one launch,
+// pushed, under a window per robot or under the implicit integrator, and the observation of the states it ran through
+// (nmpc_contact_track_batch, nmpc_observe_rows_batch of include/nmpc_torque.h, and every launch of nmpc_contact_step_batch but the
+// un-pushed explicit one); included by nmpc_torque.hip inside namespace nmpc_torque, after nmpc_torque_implicit.hip.inc.
 //
 // The whole-body expert on the declared plant (DESIGN.md 8h): the label row of a plan, A = (tau_id + kd v_plan) / kp + q_plan,
 // handed to the contact step as q_des gives tau = tau_id + kp (q_plan - q) + kd (v_plan - v), the reference's
 // _compute_pd_torques on the plan's inverse-dynamics torque (mpc.py:583-599).  So a replanning interval is a chain of contact
-// steps, one per row of the label table; contact_track_kernel runs that chain in one launch with the robot's state resident in
+// steps, one per row of the label table; contact_chain_kernel runs that chain in one launch with the robot's state resident in
 // the LDS, observe_rows_kernel turns the states it went through into the 44-slot rows and the fall predicates.
 // Both are held bit for bit to the chain of public calls they replace (tests/test_gpu_contact_track.py).
 #pragma once
 
+// ---- the arguments of the chain, one struct per instantiation of contact_chain_kernel ---------------------------------------------
+// What a struct's constants switch in the kernel is stated there; the kernel reads nothing of a struct that its constants rule out.
+enum class Forces {
+    ground,                                               // GroundForces in every substep
+    pushed,                                               // PushedGroundForces in every substep
+    either,                                               // per substep and robot one of the two, by the robot's own window
+    windowed                                              // WindowedPushForces: one source, the push switched by the window
+};
+
+// The un-pushed track: the state in q, v goes through n_steps control steps, in place.
 struct TrackArgs {
+    static constexpr bool step_io = false, implicit = false;
+    static constexpr Forces forces = Forces::ground;
     int B, n_steps, n_sub, a_rows, qv_rows, skip_mask;
     float dt, kp, kd;
     ContactCfg c;
@@ -20,181 +33,68 @@ struct TrackArgs {
     float *Q, *V;                                         // both or neither: the state before control step k at + (b * qv_rows + k) * n
 };
 
-// contact_step_kernel's substep, n_steps * n_sub times on the state in the slice: per control step the state goes out to row k
-// of Q, V (if given), the PD target becomes row k of the robot's table, and n_sub substeps follow.  A control step whose
-// recursion met an unsound pivot leaves NaN in the whole state, as the contact step writes it and the next call of a chain
-// reads it back, so the NaN appears in the row of Q, V the chain would first have it in.
-// The substep is a copy of contact_step_kernel's text without f_out / tau_out (DESIGN.md 8h): that kernel and fd_kernel keep
-// theirs, as their comments say, and a driver shared with them would have to be proven bit-neutral for both.
-template <int W>
-__global__ __launch_bounds__(W) void contact_track_kernel(const Model* __restrict__ mp, const TrackArgs p) {
-    extern __shared__ float body[];                       // [joint][CT_SLOTS][W]
-    const Model& m = *mp;
-    const int n = m.n, nu = m.nu, base = n - nu;
-    ContactCfg* cfg = reinterpret_cast<ContactCfg*>(body + n * CT_SLOTS * W);
-    if (threadIdx.x == 0) *cfg = p.c;
-    __syncthreads();
-    const int b = blockIdx.x * W + threadIdx.x;
-    if (b >= p.B) return;
-    if (p.skip && (p.skip[b] & p.skip_mask)) return;
-    const Slice<CT_SLOTS, W> at;
-    float* qb = p.q + (size_t)b * n;
-    float* vb = p.v + (size_t)b * n;
-    const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;
-    const float nan = __builtin_nanf("");
-#pragma clang loop unroll(disable) vectorize(disable)
-    for (int i = 0; i < n; ++i) { at(i, FD_Q) = qb[i]; at(i, FD_Q + 1) = vb[i]; }
-    for (int k = 0; k < p.n_steps; ++k) {
-        if (p.Q) {
-            float* Qk = p.Q + ((size_t)b * p.qv_rows + k) * n;
-            float* Vk = p.V + ((size_t)b * p.qv_rows + k) * n;
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) { Qk[i] = at(i, FD_Q); Vk[i] = at(i, FD_Q + 1); }
-        }
-        const float* db = p.A + ((size_t)b * p.a_rows + k) * nu;
-        bool sound = true;
-        for (int s = 0; s < p.n_sub; ++s) {
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) {
-                float t = 0.0f;
-                if (i >= base) {
-                    t = tb ? tb[i - base] : 0.0f;
-                    t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
-                    { const float lim = cfg->tau_max; if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t); }   // a NaN stays NaN
-                }
-                at(i, FD_Q + 2) = t;
-            }
-            sound = fd_accel_body<W, CT_SLOTS>(m, GroundForces{cfg, nullptr}) && sound;
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) {
-                const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);
-                at(i, FD_Q + 1) = v;
-                at(i, FD_Q) = at(i, FD_Q) + p.dt * v;
-            }
-        }
-        if (!sound) {
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) { at(i, FD_Q) = nan; at(i, FD_Q + 1) = nan; }
-        }
-    }
-#pragma clang loop unroll(disable) vectorize(disable)
-    for (int i = 0; i < n; ++i) { qb[i] = at(i, FD_Q); vb[i] = at(i, FD_Q + 1); }
-}
-
-// ---- the pushed substeps ----------------------------------------------------------------------------------------------------------
-// The one kernel that pushes (DESIGN.md 8d): contact_track_kernel's control steps with PushedGroundForces as the force source,
-// every substep of the launch pushed.  nmpc_torque.hip cuts a plant call into runs of un-pushed substeps, which stay launches of
-// contact_step_kernel / contact_track_kernel as they are, and runs of pushed ones, which are launches of this kernel for the step
-// and for the track alike: an un-pushed substep is the un-pushed kernel's arithmetic because it is that kernel, and a pushed
-// chain of steps is its track because both run this text.  (A window flag inside one kernel does not give that: the compiler
-// fuses the recursion of such a kernel differently, and its un-pushed substeps are not the un-pushed kernel's bits.)
-// It is one more copy of the substep text: a fix to the PD law, the clamp, the Euler update or the NaN rule goes into
-// contact_step_kernel, contact_track_kernel, here and contact_window_kernel below.
-// So it serves both callers: a start state apart from q, v and the outputs of the last substep for the step; a table of
-// targets, rows Q, V and skip flags for the track.
+// The pushed substeps (DESIGN.md 8d), every substep of the launch pushed.  nmpc_torque.hip cuts a plant call into runs of un-pushed
+// substeps, which stay launches of contact_step_kernel / the TrackArgs chain as they are, and runs of pushed ones, which are
+// launches of this chain for the step and for the track alike: an un-pushed substep is the un-pushed kernel's arithmetic because
+// it is that kernel, and a pushed chain of steps is its track because both run this instantiation.  (A window flag inside one
+// kernel does not give that: the compiler fuses the recursion of such a kernel differently, and its un-pushed substeps are not the
+// un-pushed kernel's bits.)  So it serves both callers (step_io): a start state apart from q, v and the outputs of the last
+// substep for the step; a table of targets, rows Q, V and skip flags for the track.
 struct PushArgs : TrackArgs {                             // A == nullptr: no PD target (the step's q_des == NULL)
+    static constexpr bool step_io = true;
+    static constexpr Forces forces = Forces::pushed;
     const float* force;                                   // robot b's world-frame force at force + 3 b
     int joint;
     const float *q_in, *v_in;                             // the start state; nullptr: q, v
     float *a_out, *f_out, *tau_out;                       // of the last substep of the last control step (each may be nullptr)
 };
 
-template <int W>
-__global__ __launch_bounds__(W) void contact_push_kernel(const Model* __restrict__ mp, const PushArgs p) {
-    extern __shared__ float body[];                       // [joint][CT_SLOTS][W]
-    const Model& m = *mp;
-    const int n = m.n, nu = m.nu, base = n - nu, nf3 = 3 * m.nf;
-    ContactCfg* cfg = reinterpret_cast<ContactCfg*>(body + n * CT_SLOTS * W);
-    if (threadIdx.x == 0) *cfg = p.c;
-    __syncthreads();
-    const int b = blockIdx.x * W + threadIdx.x;
-    if (b >= p.B) return;
-    if (p.skip && (p.skip[b] & p.skip_mask)) return;
-    const Slice<CT_SLOTS, W> at;
-    float* qb = p.q + (size_t)b * n;
-    float* vb = p.v + (size_t)b * n;
-    const float* qi = p.q_in ? p.q_in + (size_t)b * n : qb;
-    const float* vi = p.v_in ? p.v_in + (size_t)b * n : vb;
-    const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;
-    float* fo = p.f_out ? p.f_out + (size_t)b * nf3 : nullptr;
-    float* to = p.tau_out ? p.tau_out + (size_t)b * nu : nullptr;
-    const V3 F = v3(p.force + (size_t)b * 3);
-    const float nan = __builtin_nanf("");
-#pragma clang loop unroll(disable) vectorize(disable)
-    for (int i = 0; i < n; ++i) { at(i, FD_Q) = qi[i]; at(i, FD_Q + 1) = vi[i]; }
-    bool sound = true;
-    for (int k = 0; k < p.n_steps; ++k) {
-        if (p.Q) {
-            float* Qk = p.Q + ((size_t)b * p.qv_rows + k) * n;
-            float* Vk = p.V + ((size_t)b * p.qv_rows + k) * n;
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) { Qk[i] = at(i, FD_Q); Vk[i] = at(i, FD_Q + 1); }
-        }
-        const float* db = p.A ? p.A + ((size_t)b * p.a_rows + k) * nu : nullptr;
-        sound = true;
-        for (int s = 0; s < p.n_sub; ++s) {
-            const bool last = k == p.n_steps - 1 && s == p.n_sub - 1;
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) {
-                float t = 0.0f;
-                if (i >= base) {
-                    t = tb ? tb[i - base] : 0.0f;
-                    if (db) t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
-                    { const float lim = cfg->tau_max; if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t); }   // a NaN stays NaN
-                    if (last && to) to[i - base] = t;
-                }
-                at(i, FD_Q + 2) = t;
-            }
-            sound = fd_accel_body<W, CT_SLOTS>(m, PushedGroundForces{{cfg, last ? fo : nullptr}, F, p.joint}) && sound;
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) {
-                const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);
-                at(i, FD_Q + 1) = v;
-                at(i, FD_Q) = at(i, FD_Q) + p.dt * v;
-            }
-        }
-        if (!sound) {
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < n; ++i) { at(i, FD_Q) = nan; at(i, FD_Q + 1) = nan; }
-        }
-    }
-    // the state, and for the step the outputs of the last substep: NaN rows where the last control step was unsound
-#pragma clang loop unroll(disable) vectorize(disable)
-    for (int i = 0; i < n; ++i) {
-        if (p.a_out) p.a_out[(size_t)b * n + i] = sound ? at(i, FD_Q + 2) : nan;
-        qb[i] = at(i, FD_Q); vb[i] = at(i, FD_Q + 1);
-    }
-    if (!sound) {
-#pragma clang loop unroll(disable) vectorize(disable)
-        for (int i = 0; fo && i < nf3; ++i) fo[i] = nan;
-#pragma clang loop unroll(disable) vectorize(disable)
-        for (int i = 0; to && i < nu; ++i) to[i] = nan;
-    }
-}
-
-// ---- a window of its own per robot ------------------------------------------------------------------------------------------------
-// nmpc_contact_set_push_windows (DESIGN.md 8d): robot b is pushed in the substeps first[b] <= s0 + k n_sub + i < first[b] + count[b],
-// so the cut of a call into pushed and un-pushed launches, which is uniform over the batch, cannot be made on the host.  One
-// launch per call instead: contact_push_kernel's text, and in every substep the robot takes one of two calls of the recursion --
-// the un-pushed one under GroundForces, which is the call of contact_step_kernel / contact_track_kernel, or the pushed one under
-// PushedGroundForces, which is contact_push_kernel's.  The two are separate inlined copies on the two sides of a branch, not
-// one copy under a flag: each is compiled in blocks of its own, as in the kernel it comes from, and an un-pushed robot runs no
-// instruction of the push.  Robots of one block share its width and its slice layout and nothing else, so lanes whose windows
-// differ in a substep run the two sides one after the other under their execution masks (a substep then costs two recursions
-// for that wave); a wave whose lanes agree skips the other side.  Held bit for bit, robot by robot, to the cut path under
-// that robot's window (tests/test_gpu_push_windows_plant.py).
-// It is a fourth copy of the substep text: a fix to the PD law, the clamp, the Euler update or the NaN rule goes into all four.
+// A window of its own per robot, nmpc_contact_set_push_windows (DESIGN.md 8d): robot b is pushed in the substeps
+// first[b] <= s0 + k n_sub + i < first[b] + count[b], so the cut of a call into pushed and un-pushed launches, which is uniform over
+// the batch, cannot be made on the host.  One launch per call instead, and in every substep the robot takes one of two calls of
+// the recursion -- the un-pushed one under GroundForces, which is the call of contact_step_kernel / the TrackArgs chain, or the
+// pushed one under PushedGroundForces, which is the PushArgs chain's.  The two are separate inlined copies on the two sides of a
+// branch, not one copy under a flag: each is compiled in blocks of its own, as in the kernel it comes from, and an un-pushed robot
+// runs no instruction of the push.  Robots of one block share its width and its slice layout and nothing else, so lanes whose
+// windows differ in a substep run the two sides one after the other under their execution masks (a substep then costs two
+// recursions for that wave); a wave whose lanes agree skips the other side.  Held bit for bit, robot by robot, to the cut path
+// under that robot's window (tests/test_gpu_push_windows_plant.py).
 struct WindowArgs : PushArgs {
+    static constexpr Forces forces = Forces::either;
     const int *first, *count;                             // robot b's window, in the count the call's substep 0 is substep s0 of
     long long s0;
 };
 
-template <int W>
-__global__ __launch_bounds__(W) void contact_window_kernel(const Model* __restrict__ mp, const WindowArgs p) {
-    extern __shared__ float body[];                       // [joint][CT_SLOTS][W]
+// The linearly implicit integrator (nmpc_torque_implicit.hip.inc): every substep solves twice, and the window of a push is tested
+// per substep inside the one source -- there are no un-pushed bits of another kernel to keep.  With windows per robot attached the
+// same test reads the robot's own window: the launch is the same.  The triangle of implicit_accel_body lies between the slice and
+// the law.
+struct ImplicitArgs : PushArgs {                          // force == nullptr: no push
+    static constexpr bool implicit = true;
+    static constexpr Forces forces = Forces::windowed;
+    long long push_lo, push_hi;                           // the pushed substeps k * n_sub + s of the launch: [push_lo, push_hi)
+    const int *win_first, *win_count;                     // nmpc_contact_set_push_windows (nullptr: the window above for every robot):
+    long long win_s0;                                     // robot b's window [win_first[b], + win_count[b]) less win_s0 instead
+};
+
+// ---- the chain ------------------------------------------------------------------------------------------------------------------
+// contact_step_kernel's substep, n_steps * n_sub times on the state in the slice: per control step the state goes out to row k
+// of Q, V (if given), the PD target becomes row k of the robot's table, and n_sub substeps follow.  A control step whose
+// recursion met an unsound pivot leaves NaN in the whole state, as the contact step writes it and the next call of a chain
+// reads it back, so the NaN appears in the row of Q, V the chain would first have it in.
+// The one text of the PD law, the clamp, the Euler update and the NaN rule for every chain: what the instantiations differ in is
+// switched at compile time by the constants of Args, and each instantiation compiles to the instructions of the kernel that was
+// written out for it before (DESIGN.md 8d has the comparison).  The text stands in the kernel, not in a function the kernels
+// call, and no switch is a run-time one: either reshapes the recursion.  contact_step_kernel and fd_kernel keep their own text,
+// as their comments say.
+template <int W, class Args>
+__global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restrict__ mp, const Args p) {
+    extern __shared__ float body[];                       // [joint][CT_SLOTS][W], under the implicit integrator the triangle [entry][W], then the law
     const Model& m = *mp;
-    const int n = m.n, nu = m.nu, base = n - nu, nf3 = 3 * m.nf;
-    ContactCfg* cfg = reinterpret_cast<ContactCfg*>(body + n * CT_SLOTS * W);
+    const int n = m.n, nu = m.nu, base = n - nu;
+    [[maybe_unused]] const int nf3 = 3 * m.nf;
+    float* const behind = body + n * CT_SLOTS * W;
+    ContactCfg* cfg = reinterpret_cast<ContactCfg*>(Args::implicit ? behind + (n * (n + 1) / 2) * W : behind);
     if (threadIdx.x == 0) *cfg = p.c;
     __syncthreads();
     const int b = blockIdx.x * W + threadIdx.x;
@@ -203,17 +103,28 @@ __global__ __launch_bounds__(W) void contact_window_kernel(const Model* __restri
     const Slice<CT_SLOTS, W> at;
     float* qb = p.q + (size_t)b * n;
     float* vb = p.v + (size_t)b * n;
-    const float* qi = p.q_in ? p.q_in + (size_t)b * n : qb;
-    const float* vi = p.v_in ? p.v_in + (size_t)b * n : vb;
+    const float *qi = qb, *vi = vb;
     const float* tb = p.tau ? p.tau + (size_t)b * nu : nullptr;
-    float* fo = p.f_out ? p.f_out + (size_t)b * nf3 : nullptr;
-    float* to = p.tau_out ? p.tau_out + (size_t)b * nu : nullptr;
-    const V3 F = v3(p.force + (size_t)b * 3);
-    const long long push_lo = (long long)p.first[b] - p.s0, push_hi = push_lo + p.count[b];      // count <= 0: never pushed
+    [[maybe_unused]] float *fo = nullptr, *to = nullptr;
+    [[maybe_unused]] V3 F;                                // set where Args has a push
+    [[maybe_unused]] long long push_lo = 0, push_hi = 0;
+    if constexpr (Args::step_io) {
+        if (p.q_in) qi = p.q_in + (size_t)b * n;
+        if (p.v_in) vi = p.v_in + (size_t)b * n;
+        fo = p.f_out ? p.f_out + (size_t)b * nf3 : nullptr;
+        to = p.tau_out ? p.tau_out + (size_t)b * nu : nullptr;
+    }
+    if constexpr (Args::forces == Forces::pushed || Args::forces == Forces::either) F = v3(p.force + (size_t)b * 3);
+    if constexpr (Args::forces == Forces::either) { push_lo = (long long)p.first[b] - p.s0; push_hi = push_lo + p.count[b]; }      // count <= 0: never pushed
+    if constexpr (Args::forces == Forces::windowed) {
+        F = p.force ? v3(p.force + (size_t)b * 3) : V3{0, 0, 0};
+        push_lo = p.push_lo; push_hi = p.push_hi;
+        if (p.win_first) { push_lo = (long long)p.win_first[b] - p.win_s0; push_hi = push_lo + p.win_count[b]; }
+    }
     const float nan = __builtin_nanf("");
 #pragma clang loop unroll(disable) vectorize(disable)
     for (int i = 0; i < n; ++i) { at(i, FD_Q) = qi[i]; at(i, FD_Q + 1) = vi[i]; }
-    bool sound = true;
+    bool sound = true;                                    // of the last control step
     for (int k = 0; k < p.n_steps; ++k) {
         if (p.Q) {
             float* Qk = p.Q + ((size_t)b * p.qv_rows + k) * n;
@@ -221,26 +132,43 @@ __global__ __launch_bounds__(W) void contact_window_kernel(const Model* __restri
 #pragma clang loop unroll(disable) vectorize(disable)
             for (int i = 0; i < n; ++i) { Qk[i] = at(i, FD_Q); Vk[i] = at(i, FD_Q + 1); }
         }
-        const float* db = p.A ? p.A + ((size_t)b * p.a_rows + k) * nu : nullptr;
+        const float* db = !Args::step_io || p.A ? p.A + ((size_t)b * p.a_rows + k) * nu : nullptr;
         sound = true;
         for (int s = 0; s < p.n_sub; ++s) {
-            const bool last = k == p.n_steps - 1 && s == p.n_sub - 1;
-            const long long sub = (long long)k * p.n_sub + s;
+            [[maybe_unused]] const bool last = k == p.n_steps - 1 && s == p.n_sub - 1;
+            [[maybe_unused]] const long long sub = (long long)k * p.n_sub + s;
+            [[maybe_unused]] bool on = false;             // Forces::windowed: is this substep pushed
+            if constexpr (Args::forces == Forces::windowed) on = p.force && sub >= push_lo && sub < push_hi;
+            [[maybe_unused]] unsigned unclamped = 0;     // bit i: the clamp did not cut the PD torque of joint i
 #pragma clang loop unroll(disable) vectorize(disable)
             for (int i = 0; i < n; ++i) {
                 float t = 0.0f;
                 if (i >= base) {
                     t = tb ? tb[i - base] : 0.0f;
-                    if (db) t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
-                    { const float lim = cfg->tau_max; if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t); }   // a NaN stays NaN
-                    if (last && to) to[i - base] = t;
+                    if (!Args::step_io || db) t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
+                    const float lim = cfg->tau_max;
+                    if constexpr (Args::implicit)
+                        if (db && (!(lim > 0.0f) || fabsf(t) < lim)) unclamped |= 1u << i;
+                    if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t);      // a NaN stays NaN
+                    if constexpr (Args::step_io)
+                        if (last && to) to[i - base] = t;
                 }
                 at(i, FD_Q + 2) = t;
             }
-            if (sub >= push_lo && sub < push_hi)
+            if constexpr (Args::forces == Forces::ground) {
+                sound = fd_accel_body<W, CT_SLOTS>(m, GroundForces{cfg, nullptr}) && sound;
+            } else if constexpr (Args::forces == Forces::pushed) {
                 sound = fd_accel_body<W, CT_SLOTS>(m, PushedGroundForces{{cfg, last ? fo : nullptr}, F, p.joint}) && sound;
-            else
-                sound = fd_accel_body<W, CT_SLOTS>(m, GroundForces{cfg, last ? fo : nullptr}) && sound;
+            } else if constexpr (Args::forces == Forces::either) {
+                if (sub >= push_lo && sub < push_hi)
+                    sound = fd_accel_body<W, CT_SLOTS>(m, PushedGroundForces{{cfg, last ? fo : nullptr}, F, p.joint}) && sound;
+                else
+                    sound = fd_accel_body<W, CT_SLOTS>(m, GroundForces{cfg, last ? fo : nullptr}) && sound;
+            } else {
+                sound = fd_accel_body<W, CT_SLOTS>(m, WindowedPushForces{{{cfg, last ? fo : nullptr}, F, p.joint}, on}) && sound;
+            }
+            if constexpr (Args::implicit)
+                sound = implicit_accel_body<W>(m, *cfg, Triangle<W>{behind}, p.dt, p.kp, p.kd, unclamped) && sound;
 #pragma clang loop unroll(disable) vectorize(disable)
             for (int i = 0; i < n; ++i) {
                 const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);
@@ -256,14 +184,17 @@ __global__ __launch_bounds__(W) void contact_window_kernel(const Model* __restri
     // the state, and for the step the outputs of the last substep: NaN rows where the last control step was unsound
 #pragma clang loop unroll(disable) vectorize(disable)
     for (int i = 0; i < n; ++i) {
-        if (p.a_out) p.a_out[(size_t)b * n + i] = sound ? at(i, FD_Q + 2) : nan;
+        if constexpr (Args::step_io)
+            if (p.a_out) p.a_out[(size_t)b * n + i] = sound ? at(i, FD_Q + 2) : nan;
         qb[i] = at(i, FD_Q); vb[i] = at(i, FD_Q + 1);
     }
-    if (!sound) {
+    if constexpr (Args::step_io) {
+        if (!sound) {
 #pragma clang loop unroll(disable) vectorize(disable)
-        for (int i = 0; fo && i < nf3; ++i) fo[i] = nan;
+            for (int i = 0; fo && i < nf3; ++i) fo[i] = nan;
 #pragma clang loop unroll(disable) vectorize(disable)
-        for (int i = 0; to && i < nu; ++i) to[i] = nan;
+            for (int i = 0; to && i < nu; ++i) to[i] = nan;
+        }
     }
 }
 

@@ -5,13 +5,15 @@ other push tests hold to the fp64 reference (tests/test_gpu_push_step.py, tests/
 tests/test_gpu_push_policy_rollout.py); under the explicit integrator it is the cut into un-pushed and pushed launches, so the
 comparison is that of the one windowed kernel against the kernels it takes its two substeps from.
 
-The quadruped tree on the default ground from a standing start, every robot with a force and a PD target of its own."""
+The quadruped tree on the default ground from a standing start, every robot with a force and a PD target of its own; the
+windowed track once more on a 32-joint tree, which runs 16 robots per block."""
 import ctypes
 
 import numpy as np
 import pytest
 
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests import fd_reference as fr
 from tests.solve_helpers import dev, policy_pair  # noqa: F401
 from tests.torque_helpers import same
 
@@ -124,6 +126,43 @@ def test_contact_track_rows_are_the_uniform_calls(world, detached, integrator):
     assert same(q[1], world.q[1]) and same(v[1], world.v[1]) and bool((Q[1] == -77.0).all()) and bool((V[1] == -77.0).all())
     for b in (0, 2, 3):
         assert rows_equal((q, v, Q, V), got, b)
+
+
+class Tree32:
+    """the 32-joint tree of tests/test_gpu_push_step.py on its own ground, which runs 16 robots per block: B = 17 is a full block
+    and one lane.  Made once, never written to."""
+    B, K, N_SUB = 17, 2, 4
+    # of the 8 substeps of the call: the whole call, inside it, none, before the call, running past its end
+    MIX, PUSHED = [(0, 8), (2, 3), (5, 0), (-6, 4), (6, 10)], [True, True, False, False, True]
+
+    def __init__(self):
+        from tests.test_gpu_push_step import general_case
+        from tests.torque_helpers import ground
+        c = general_case(fr.random_tree(n=32, seed=14, feet=(4, 31, 31, 17)), self.B, 8)
+        self.L, self.ground, m = c.L, ground(c.g), c.m
+        rng = np.random.default_rng(43)
+        t = lambda x: torch.as_tensor(np.array(x, np.float32), device=self.L.device).contiguous()      # noqa: E731
+        self.q, self.v, self.tau = t(c.q), t(c.v), t(c.tau)
+        self.F = t(rng.uniform(-80, 80, (self.B, 3)))
+        self.A = t(c.q[:, None, m.n - m.nu:] + rng.uniform(-0.1, 0.1, (self.B, self.K, m.nu)))
+
+    def track(self):
+        q, v = self.q.clone(), self.v.clone()
+        return self.L.contact_track(q, v, self.A, DT, self.N_SUB, tau_ff=self.tau, kp=KP, kd=KD, ground=self.ground, record=False)[:2]
+
+
+def test_contact_track_rows_are_the_uniform_calls_at_16_robots_per_block(dev):
+    """the windowed chain at its other width, which the quadruped never runs: explicit integrator, no rows (they need the
+    18-joint tree)"""
+    tree = Tree32()
+    windows = [Tree32.MIX[b % 5] for b in range(Tree32.B)]
+    try:
+        got, plain, moved = held_row_by_row(tree, windows, tree.track, ("q", "v"))
+    finally:
+        tree.L.set_push(None)
+    assert moved == [Tree32.PUSHED[b % 5] for b in range(Tree32.B)]
+    for b in range(Tree32.B):
+        assert Tree32.PUSHED[b % 5] or rows_equal(got, plain, b)
 
 
 @pytest.mark.parametrize("integrator", INTEGRATORS)

@@ -145,7 +145,8 @@ def rollout_digests():
 def torque_digests():
     """One digest per entry point of include/nmpc_torque.h (`nmpc_plan_actions_batch` is under roll_wb_steps_labels) on the states
     of the layer's own GPU tests, B = 257 (eight blocks and one lane), 33 and 40 (a full and a ragged block at either width);
-    `_w16`: the 16-robot instantiations, on the 30-joint tree.  Prints what is not finite: NaN bytes compare equal and say less."""
+    `_w16`: the 16-robot instantiations, on the 30-joint tree; the plant calls also pushed, under windows per robot and under the
+    implicit integrator (`plant`).  Prints what is not finite: NaN bytes compare equal and say less."""
     import numpy as np
     import torch
     from tests import fd_reference as fr
@@ -186,6 +187,29 @@ def torque_digests():
                                               stream(L.device)), L._h, "nmpc_state_momentum_batch", "torque")
         add("state_momentum", rows)
 
+    def plant(L, q, v, tau, g, B, tag, integrators, rows):
+        """the chains of control steps: `contact_track` (3 control steps of 8 substeps) un-pushed, under a scalar window that
+        starts and ends inside control steps and under windows per robot -- the whole call, inside it, none, before the call,
+        running past its end, in turn --, and `contact_step` over the same 24 substeps under both pushes; per integrator"""
+        rng, nu = np.random.default_rng(B), tau.shape[1]
+        A, F = q[:B, None, -nu:] + rng.uniform(-0.1, 0.1, (B, 3, nu)), rng.uniform(-80, 80, (B, 3))
+        q, v, tau, A, F = (torch.as_tensor(np.array(x[:B], np.float32), device=L.device).contiguous() for x in (q, v, tau, A, F))
+        mix = [(0, 24), (5, 12), (7, 0), (-9, 4), (18, 20)]
+        pushes = {"pushed": (5, 12), "windowed": tuple([w[i] for w in (mix * B)[:B]] for i in (0, 1))}
+        for integrator in integrators:
+            L.set_integrator(integrator)
+            name = tag + ("_implicit" if integrator == "implicit" else "")
+            for push, window in ((None, None), *pushes.items()):
+                if push:
+                    L.set_push(F, *window)
+                if push or rows:                          # without rows the un-pushed track is left out (the _w16 form)
+                    out = L.contact_track(q.clone(), v.clone(), A, DT, 8, tau_ff=tau, kp=KP, kd=KD, ground=g, record=rows)
+                    add(f"contact_track{'_' + push if push else ''}{name}", *out[:4 if rows else 2])
+                if push:
+                    add(f"contact_step_{push}{name}", *L.contact_step(q, v, DT, 24, tau_ff=tau, q_des=A[:, 0], kp=KP, kd=KD, ground=g))
+                L.set_push(None)
+            L.set_integrator("explicit")
+
     w = World()                                           # its Case is the tilted quadruped of tests/test_gpu_contact.py
     for c in (Case(fr.quadruped(), 257, seed=257), w.c):
         dynamics(c.L, c.m, 257, (257, 7))
@@ -201,6 +225,8 @@ def torque_digests():
     dynamics(L, m, 40, (6,), "_w16")
     q, v, tau, _ = fr.inputs(m, 40, 6)
     add("contact_step_w16", *L.contact_step(q, v, DT, 20, tau_ff=tau, q_des=q, kp=KP, kd=KD, ground=GroundContact(**SOFT)))
+    plant(w.L, w.c.q, w.c.v, w.c.tau, ground(w.c.g), 33, "", ("explicit", "implicit"), True)
+    plant(L, q, v, tau, GroundContact(**SOFT), 40, "_w16", ("explicit",), False)      # rows need the 18-joint tree
     centroidal(w.c.L, w.c.q, w.c.v)                       # B = 257 on the tilted quadruped, B = 40 on the 30-joint tree
     centroidal(L, q, v)
     return {k: sha(*v) for k, v in parts.items()}
