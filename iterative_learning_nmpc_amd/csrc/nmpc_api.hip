@@ -188,6 +188,11 @@ int check_declared_momentum(Handle* h, const char* who) {
                                                     "with the articulated momentum model (nmpc_wb_set_momentum_model)");
 }
 
+// a call of the torque layer (include/nmpc_torque.h) made for an entry point of this one: OK, or its code with "<call>: <the layer's message>"
+int torque_call(Handle* h, int rc, const char* call, void* torque) {
+    return rc ? fail(h, rc, std::string(call) + ": " + nmpc_torque_last_error(torque)) : (int)NMPC_OK;
+}
+
 // the whole-body rollouts' and the labeller's carve-up of h->roll: every array starts on a 16 B boundary (launch_wb checks)
 struct WbRoll { float *yref, *yref_e, *params, *x0; };
 WbRoll wb_roll(const Handle* h) {
@@ -210,7 +215,35 @@ int launch_state_momentum(Handle* h, int count, const float* q, const float* v, 
     void* torque = h->momentum.torque;
     const int rc = nmpc_state_momentum_batch(torque, count, q, v, qv_stride, x0 + nmpc::wb::WH, nmpc::wb::NX, X + nmpc::wb::WH,
                                              (h->dims.N + 1) * nmpc::wb::NX, skip, skip_mask, st);
-    return rc ? fail(h, rc, std::string("nmpc_state_momentum_batch: ") + nmpc_torque_last_error(torque)) : (int)NMPC_OK;
+    return torque_call(h, rc, "nmpc_state_momentum_batch", torque);
+}
+
+// what the prepare kernels of the whole-body rollouts and of the labeller take alike (r: WbRolloutArgs or WbLabelArgs): the carve-up of
+// h->roll and the model parameters -- where the tree gives x0 its momentum with the mass of the tree, the one the dynamics carry, in the
+// force reference's weight share and in a push's velocity jump
+template <class R>
+int set_wb_problem(Handle* h, R& r) {
+    const WbRoll roll = wb_roll(h);
+    r.yref = roll.yref; r.yref_e = roll.yref_e; r.params = roll.params; r.x0 = roll.x0;
+    r.mp = h->mp;
+    if (!tree_state_momentum(h)) return NMPC_OK;
+    if (const char* why = nmpc_torque::momentum_refusal(h->momentum.torque, h->device)) return fail(h, NMPC_E_STATE, std::string("momentum model: ") + why);
+    r.mp.mass = nmpc_torque::tree_mass(h->momentum.torque);
+    return NMPC_OK;
+}
+
+// The labeller's problems m0 .. m0 + count, problem m = b K + k, against a table of `rows` rows per robot: where the table has exactly K
+// rows per robot they are one dense run of it, otherwise one run per robot.  each(i, run, row) -> code: `run` problems from the chunk's
+// problem i on, whose first lies at row `row` of the table; the first code that is not OK ends the walk
+template <class Each>
+int runs_by_robot(long long m0, int count, int K, int rows, Each each) {
+    for (long long m = m0; m < m0 + count;) {
+        const long long b = m / K, k = m - b * K;
+        const int run = rows == K ? count : (int)((K - k < m0 + count - m) ? K - k : m0 + count - m);
+        if (const int rc = each((size_t)(m - m0), run, (size_t)b * rows + k)) return rc;
+        m += run;
+    }
+    return NMPC_OK;
 }
 
 // Two variants of the QP kernel (nmpc_solve.hip, Lds).  Resident: stage arrays in the LDS (39.6 KB at N = 50: four waves per CU),
@@ -738,15 +771,41 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
                        [] { return NMPC_OK; }, [](int) { return NMPC_OK; });
 }
 
-int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, const signed char* gait, const signed char* peaks,
-                          const int* nodes, float* q, float* v, const double* v_des, const double* w_des, double* ref_state,
-                          const float* joint_ref, const float* push_force, float* X, float* U, float* S, int* status,
-                          int* failed, void* stream) {
-    Handle* h = static_cast<Handle*>(handle);
-    if (!h) return NMPC_E_ARG;
-    if (B == 0) return NMPC_OK;
-    if (!cfg || !gait || !peaks || !nodes || !q || !v || !v_des || !w_des || !ref_state || !joint_ref || !X || !U || !S || !status || !failed)
-        return fail(h, NMPC_E_ARG, "null argument");
+}  // extern "C"
+
+namespace {
+
+// One nmpc_wb_rollout_batch call as check_wb_rollout accepted it: what the parts of the call share beside the kernel arguments.
+struct WbRolloutCall {
+    int B = 0, n_replans = 0;
+    // the clock (nmpc_wb_rollout_set_clock): replan i of the call is replan replan0 + i of its rollout; a replan is `steps` simulation
+    // steps of sim_dt, each n_sub substeps of dt_sub on the plant
+    int replan0 = 0, steps = 0, n_sub = 0;
+    double sim_dt = 0.0;
+    float dt_sub = 0.0f;
+    long long sim_step(int i) const { return (long long)(replan0 + i) * steps; }      // where replan i starts: the simulation step,
+    long long substep(int i) const { return sim_step(i) * n_sub; }                    // the substep of the plant
+    double time(int i) const { return (double)sim_step(i) * sim_dt; }                 // and the time; time(n_replans): where the call ends
+    // the labels of a replan's plan, the attached ones (nmpc_wb_rollout_set_actions) or the PD targets of the plant alone: the layer that
+    // writes them (nullptr: neither is attached), its hold table and gains, and the attached table A of n_rows rows per rollout (nullptr:
+    // the plant's workspace Aw of one replan)
+    void* label_torque = nullptr;
+    const int* zoh = nullptr;
+    float kp = 0.0f, kd = 0.0f, *A = nullptr, *Aw = nullptr;
+    template <class R> float* rows(const R& r) const { return A ? A + (size_t)r.row0 * 12 : Aw; }     // where this replan's targets live
+    template <class R> int a_rows(const R& r) const { return A ? r.n_rows : steps; }                  // ... at how many rows per rollout
+    void* plant = nullptr;                        // nmpc_wb_rollout_set_plant (nullptr: plant = plan)
+    bool force_push = false, tree_h = false;      // nmpc_wb_rollout_set_plant_push with a push_force; x0's momentum from the tree
+    nmpc_push_cfg plant_push{};                   // the rollout's own push_force, its window in substeps from the rollout's step 0
+    nmpc_torque::PushWindows plant_windows{};     // a window per rollout, in substeps: written by the kernel at the entry of the call
+    const int* skip = nullptr;                    // terminated rollouts are left out of every launch: failed[b] & term_mask
+    int term_mask = 0;
+};
+
+// Every check of nmpc_wb_rollout_batch behind its null pointers, and what they decide: c, and in r the problem tensors and the model
+// parameters.  After it nothing refuses but a launch.
+int check_wb_rollout(Handle* h, int B, const nmpc_wb_rollout_cfg* cfg, const int* nodes, const float* push_force, const int* failed,
+                     WbRolloutCall& c, nmpc::wb::WbRolloutArgs& r) {
     if (h->dims.model_id != NMPC_MODEL_WHOLEBODY) return fail(h, NMPC_E_ARG, "nmpc_wb_rollout_batch needs the whole-body model");
     if (const int rc = check_declared_momentum(h, "nmpc_wb_rollout_batch")) return rc;
     if (const int rc = check_batch(h, B)) return rc;
@@ -754,10 +813,10 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
         return fail(h, NMPC_E_ARG, "rollout configuration out of range");
     if (const int rc = check_configured(h)) return rc;
     if (h->line_search) return fail(h, NMPC_E_ARG, "the whole-body model takes full steps (line_search = 0)");
-    const int N = h->dims.N;
+    c.B = B; c.n_replans = cfg->n_replans; c.steps = cfg->replanning_steps; c.sim_dt = cfg->sim_dt;
     // the clock of a continued rollout (nmpc_wb_rollout_set_clock): the stamp of its last replan must fit above the flag bits
-    const int replan0 = h->rollout_replan0;
-    if ((long long)replan0 + cfg->n_replans > (long long)(0x7fffffff >> NMPC_ROLLOUT_TERM_SHIFT))
+    c.replan0 = h->rollout_replan0;
+    if ((long long)c.replan0 + cfg->n_replans > (long long)(0x7fffffff >> NMPC_ROLLOUT_TERM_SHIFT))
         return fail(h, NMPC_E_ARG, "rollout clock: replan0 + n_replans exceeds the stamp field of failed[b]");
     if (cfg->replanning_steps * cfg->sim_dt > cfg->time_horizon) return fail(h, NMPC_E_ARG, "replanning interval longer than the horizon");
     for (int i = 0; i < cfg->n_replans; ++i)
@@ -769,118 +828,127 @@ int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, c
             return fail(h, NMPC_E_ARG, std::string("action labels: ") + why);
     }
     const auto& pl = h->plant;
-    const int* const plant_zoh = lab.A ? lab.zoh : pl.zoh;         // the labels' hold table serves both
-    float* const targets = lab.A ? lab.A : pl.Aw;                  // where the PD targets of a replan are written and read
+    c.zoh = lab.A ? lab.zoh : pl.zoh; c.A = lab.A; c.Aw = pl.Aw;      // the labels' hold table serves both
     if (pl.torque) {
+        c.n_sub = pl.n_sub; c.dt_sub = (float)(cfg->sim_dt / (pl.n_sub > 0 ? pl.n_sub : 1));
         if (!cfg->record_sim_steps) return fail(h, NMPC_E_ARG, "a plant records rows per simulation step: record_sim_steps must be 1");
-        if (const char* why = nmpc_torque::plan_actions_refusal(pl.torque, cfg->replanning_steps, plant_zoh, pl.kp, h->device))
+        if (const char* why = nmpc_torque::plan_actions_refusal(pl.torque, cfg->replanning_steps, c.zoh, pl.kp, h->device))
             return fail(h, NMPC_E_ARG, std::string("plant: ") + why);
-        if (const char* why = nmpc_torque::contact_track_refusal(pl.torque, pl.ground_set ? &pl.ground : nullptr, pl.n_sub,
-                                                                 (float)(cfg->sim_dt / (pl.n_sub > 0 ? pl.n_sub : 1)), h->device))
+        if (const char* why = nmpc_torque::contact_track_refusal(pl.torque, pl.ground_set ? &pl.ground : nullptr, pl.n_sub, c.dt_sub, h->device))
             return fail(h, NMPC_E_ARG, std::string("plant: ") + why);
         if (lab.A && (lab.kp != pl.kp || lab.kd != pl.kd))
             return fail(h, NMPC_E_ARG, "plant: the attached action labels must be recorded with the plant's gains kp, kd");
-        if (!targets || !pl.Qw || !pl.Vw) return fail(h, NMPC_E_ARG, "plant: the workspaces Qw, Vw and (without attached labels) Aw are needed");
+        if (!(c.A ? c.A : c.Aw) || !pl.Qw || !pl.Vw) return fail(h, NMPC_E_ARG, "plant: the workspaces Qw, Vw and (without attached labels) Aw are needed");
     }
+    c.plant = pl.torque; c.label_torque = lab.A ? lab.torque : pl.torque;
+    c.kp = lab.A ? lab.kp : pl.kp; c.kd = lab.A ? lab.kd : pl.kd;
     // the push as a force on the plant (nmpc_wb_rollout_set_plant_push): the rollout's own push_force, in substeps of sim_dt / n_sub
     if (h->plant_push_as_force && !pl.torque) return fail(h, NMPC_E_ARG, "plant push: a push as a force needs a plant (nmpc_wb_rollout_set_plant)");
-    const bool force_push = h->plant_push_as_force && push_force;
-    if (force_push && nmpc_torque::push_attached(pl.torque))
+    c.force_push = h->plant_push_as_force && push_force;
+    if (c.force_push && nmpc_torque::push_attached(pl.torque))
         return fail(h, NMPC_E_ARG, "plant push: the torque handle has a push of the caller's attached (nmpc_contact_set_push)");
     if (const char* why = push_windows_refusal(h, B, push_force)) return fail(h, NMPC_E_ARG, why);
-    const auto& pw = h->push_windows;
-    nmpc_torque::PushWindows plant_windows{};      // a window per rollout, pushed as a force: in substeps, from the kernel at the entry below
-    if (force_push && pw.start) plant_windows = {h->push_substeps, h->push_substeps + h->dims.B_max, B};
-    nmpc_push_cfg plant_push{};
-    if (force_push) {
-        plant_push.force = push_force; plant_push.force_rows = B; plant_push.joint = 5;
-        plant_push.first_substep = (int)std::lround((double)cfg->push_start * pl.n_sub / cfg->sim_dt);
-        plant_push.n_substeps = (int)std::lround((double)cfg->push_duration * pl.n_sub / cfg->sim_dt);
-        if (plant_push.n_substeps < 0) plant_push.n_substeps = 0;
+    if (c.force_push) {
+        if (h->push_windows.start) c.plant_windows = {h->push_substeps, h->push_substeps + h->dims.B_max, B};
+        auto& push = c.plant_push;
+        push.force = push_force; push.force_rows = B; push.joint = 5;
+        push.first_substep = (int)std::lround((double)cfg->push_start * pl.n_sub / cfg->sim_dt);
+        push.n_substeps = (int)std::lround((double)cfg->push_duration * pl.n_sub / cfg->sim_dt);
+        if (push.n_substeps < 0) push.n_substeps = 0;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const WbRoll roll = wb_roll(h);
+    c.term_mask = cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK; c.skip = c.term_mask ? failed : nullptr;
+    c.tree_h = tree_state_momentum(h);
+    return set_wb_problem(h, r);
+}
+
+// behind the solve of a replan: the labels of its plan, beside the rows the advance kernel or the plant is about to record -- attached
+// labels where a rollout has terminated hold its last target
+int record_labels(Handle* h, const WbRolloutCall& c, const nmpc::wb::WbRolloutArgs& r, hipStream_t st) {
+    if (!c.label_torque) return NMPC_OK;
+    const int rc = nmpc_plan_actions_batch(c.label_torque, c.B, c.steps, r.N, r.X, r.U, c.zoh, r.dt_nodes, r.sim_dt, c.kp, c.kd, nullptr, c.skip,
+                                           c.term_mask, c.rows(r), c.a_rows(r), st);
+    if (rc) return torque_call(h, rc, "nmpc_plan_actions_batch", c.label_torque);
+    if (c.A && c.term_mask)
+        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_hold_actions_kernel, dim3((unsigned)(((size_t)c.B * c.steps * 12 + 255) / 256)), dim3(256),
+                           0, st, c.B, r.n_rows, r.row0, c.steps, c.term_mask, r.failed, c.A);
+    return NMPC_OK;
+}
+
+// ... and the expert drives the plant through replan i of the call: the label rows as PD targets of `steps` simulation steps, the states
+// before each step into the workspace, and those states as rows row0 .. of S with their flags (no stamp: the advance kernel stamps)
+int drive_plant(Handle* h, const WbRolloutCall& c, const nmpc::wb::WbRolloutArgs& r, int i, hipStream_t st) {
+    if (!c.plant) return NMPC_OK;
+    const auto& pl = h->plant;
+    int rc;
+    if (c.force_push) {
+        nmpc_push_cfg push = c.plant_push;
+        // this replan's substeps start at substep(i) of the rollout (a window that lies wholly before them, however far, starts n_substeps
+        // before: the int holds it); with a window per rollout the kernel takes the offset off each, they stay as the entry kernel wrote them
+        push.first_substep = (int)std::max((long long)push.first_substep - c.substep(i), -(long long)push.n_substeps);
+        rc = nmpc_torque::contact_track_pushed(c.plant, c.B, c.steps, c.n_sub, c.dt_sub, &pl.ground, r.q, r.v, nullptr, c.rows(r), c.a_rows(r),
+                                               pl.kp, pl.kd, pl.Qw, pl.Vw, c.steps, c.skip, c.term_mask, push, c.plant_windows, c.substep(i), st);
+    } else {
+        rc = nmpc_contact_track_batch(c.plant, c.B, c.steps, c.n_sub, c.dt_sub, &pl.ground, r.q, r.v, nullptr, c.rows(r), c.a_rows(r), pl.kp, pl.kd,
+                                      pl.Qw, pl.Vw, c.steps, c.skip, c.term_mask, st);
+    }
+    if (rc) return torque_call(h, rc, "nmpc_contact_track_batch", c.plant);
+    rc = nmpc_observe_rows_batch(c.plant, c.B, c.steps, pl.Qw, pl.Vw, c.steps, c.time(i), c.sim_dt, (double)r.nominal_period, r.collision_height,
+                                 r.S + (size_t)r.row0 * 44, r.n_rows, r.failed, c.replan0 + i, 0, c.skip, c.term_mask, st);
+    return torque_call(h, rc, "nmpc_observe_rows_batch", c.plant);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nmpc_wb_rollout_batch(void* handle, int B, const nmpc_wb_rollout_cfg* cfg, const signed char* gait, const signed char* peaks,
+                          const int* nodes, float* q, float* v, const double* v_des, const double* w_des, double* ref_state,
+                          const float* joint_ref, const float* push_force, float* X, float* U, float* S, int* status,
+                          int* failed, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    if (B == 0) return NMPC_OK;
+    if (!cfg || !gait || !peaks || !nodes || !q || !v || !v_des || !w_des || !ref_state || !joint_ref || !X || !U || !S || !status || !failed)
+        return fail(h, NMPC_E_ARG, "null argument");
+    WbRolloutCall c;
     nmpc::wb::WbRolloutArgs r{};
-    r.plant = pl.torque ? 1 : 0;
-    r.yref = roll.yref; r.yref_e = roll.yref_e; r.params = roll.params; r.x0 = roll.x0;
-    r.force_gravity = cfg->force_reference_gravity ? 1 : 0;
-    r.step_height = cfg->step_height;
-    r.mp = h->mp;
-    const bool tree_h = tree_state_momentum(h);
-    if (tree_h) {       // the mass of the force reference's weight share and of a push's velocity jump: the one the dynamics carry
-        if (const char* why = nmpc_torque::momentum_refusal(h->momentum.torque, h->device)) return fail(h, NMPC_E_STATE, std::string("momentum model: ") + why);
-        r.mp.mass = nmpc_torque::tree_mass(h->momentum.torque);
-    }
+    if (const int rc = check_wb_rollout(h, B, cfg, nodes, push_force, failed, c, r)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    r.plant = c.plant ? 1 : 0; r.force_gravity = cfg->force_reference_gravity ? 1 : 0; r.step_height = cfg->step_height;
     r.gait = gait; r.peaks = peaks; r.q = q; r.v = v; r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state;
     r.joint_ref = joint_ref; r.push_force = push_force;
     r.X = X; r.U = U; r.S = S; r.status = status; r.failed = failed;
-    if (pw.start && !force_push) { r.win_start = pw.start; r.win_duration = pw.duration; }      // the velocity jump, decided per rollout
-    if (plant_windows.first) {
-        NMPC_ENTER(h, h->device);
-        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_push_substeps_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, pw.start, pw.duration,
-                           pl.n_sub, cfg->sim_dt, h->push_substeps, h->push_substeps + h->dims.B_max);
-        if (const int rc = launched(h)) return rc;
-    }
+    const auto& pw = h->push_windows;
+    if (pw.start && !c.force_push) { r.win_start = pw.start; r.win_duration = pw.duration; }      // the velocity jump, decided per rollout
     nmpc::wb::WbArgs w = wb_args(h);
     w.x0 = r.x0; w.status = status;
+    if (c.plant_windows.first) {      // a window per rollout, pushed as a force: into substeps of the plant, once for the call
+        NMPC_ENTER(h, h->device);
+        hipLaunchKernelGGL(nmpc::wb::nmpc_wb_push_substeps_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, pw.start, pw.duration,
+                           c.n_sub, cfg->sim_dt, h->push_substeps, h->push_substeps + h->dims.B_max);
+        if (const int rc = launched(h)) return rc;
+    }
     int last_node = cfg->last_node;
     const int rc = run_rollout(
-        h, B, cfg, replan0, st, r, w, nmpc::wb::nmpc_wb_rollout_prepare_kernel, launch_wb, nmpc::wb::nmpc_wb_rollout_advance_kernel,
+        h, B, cfg, c.replan0, st, r, w, nmpc::wb::nmpc_wb_rollout_prepare_kernel, launch_wb, nmpc::wb::nmpc_wb_rollout_advance_kernel,
         [&](int i) {          // warm_start_solver(i_node): start_node = i_node - last_node (solver.py:304-309)
             const int shift = nodes[i] - last_node;
             r.node = last_node = nodes[i];
-            if (force_push) r.push_dt = 0.0f;      // the track launch pushes: no velocity jump in the advance kernel
+            if (c.force_push) r.push_dt = 0.0f;      // the track launch pushes: no velocity jump in the advance kernel
             return shift;
         },
         [&] {                 // x0's momentum from the tree, for the rollouts the prepare kernel prepared
-            if (!tree_h) return (int)NMPC_OK;
-            return launch_state_momentum(h, B, q, v, 18, r.x0, X, r.term_mask ? failed : nullptr, r.term_mask, st);
+            return c.tree_h ? launch_state_momentum(h, B, q, v, 18, r.x0, X, c.skip, c.term_mask, st) : (int)NMPC_OK;
         },
-        [&](int i) {          // the labels of this replan's plan, beside the rows the advance kernel is about to record
-            if (!lab.A && !pl.torque) return (int)NMPC_OK;
-            const int steps = cfg->replanning_steps;
-            const int* skip = r.term_mask ? failed : nullptr;
-            void* torque = lab.A ? lab.torque : pl.torque;
-            // labels attached: rows row0 .. of the caller's table of n_rows rows per rollout; the plant alone: its workspace of one replan
-            float* rows = lab.A ? lab.A + (size_t)r.row0 * 12 : pl.Aw;
-            const int a_rows = lab.A ? r.n_rows : steps;
-            const int lrc = nmpc_plan_actions_batch(torque, B, steps, N, X, U, plant_zoh, r.dt_nodes, r.sim_dt, lab.A ? lab.kp : pl.kp,
-                                                    lab.A ? lab.kd : pl.kd, nullptr, skip, r.term_mask, rows, a_rows, st);
-            if (lrc) return fail(h, lrc, std::string("nmpc_plan_actions_batch: ") + nmpc_torque_last_error(torque));
-            if (lab.A && r.term_mask)
-                hipLaunchKernelGGL(nmpc::wb::nmpc_wb_rollout_hold_actions_kernel, dim3((unsigned)(((size_t)B * steps * 12 + 255) / 256)),
-                                   dim3(256), 0, st, B, r.n_rows, r.row0, steps, r.term_mask, failed, lab.A);
-            if (!pl.torque) return (int)NMPC_OK;
-            // the expert drives the plant: the label rows as PD targets of `steps` simulation steps, the states before each step
-            // into the workspace, and those states as rows row0 .. of S with their flags (no stamp: the advance kernel stamps)
-            int trc;
-            if (force_push) {                      // this replan's substeps start at substep (replan0 + i) steps n_sub of the rollout
-                nmpc_push_cfg push = plant_push;
-                // (a window that lies wholly before them, however far, starts n_substeps before: the int holds it)
-                const long long first = (long long)push.first_substep - (long long)(replan0 + i) * steps * pl.n_sub;
-                push.first_substep = (int)std::max(first, -(long long)push.n_substeps);
-                // (with a window per rollout the kernel takes the offset off each: the windows stay as the entry kernel wrote them)
-                trc = nmpc_torque::contact_track_pushed(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
-                                                        rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, push, plant_windows,
-                                                        (long long)(replan0 + i) * steps * pl.n_sub, st);
-            } else {
-                trc = nmpc_contact_track_batch(pl.torque, B, steps, pl.n_sub, (float)(cfg->sim_dt / pl.n_sub), &pl.ground, q, v, nullptr,
-                                               rows, a_rows, pl.kp, pl.kd, pl.Qw, pl.Vw, steps, skip, r.term_mask, st);
-            }
-            if (trc) return fail(h, trc, std::string("nmpc_contact_track_batch: ") + nmpc_torque_last_error(pl.torque));
-            const int orc = nmpc_observe_rows_batch(pl.torque, B, steps, pl.Qw, pl.Vw, steps, (double)((long long)(replan0 + i) * steps) * cfg->sim_dt, cfg->sim_dt,
-                                                    (double)cfg->nominal_period, cfg->collision_height, S + (size_t)r.row0 * 44, r.n_rows,
-                                                    failed, replan0 + i, 0, skip, r.term_mask, st);
-            if (orc) return fail(h, orc, std::string("nmpc_observe_rows_batch: ") + nmpc_torque_last_error(pl.torque));
-            return (int)NMPC_OK;
+        [&](int i) {          // behind the solve: the labels of the plan, then the plant through the interval
+            if (const int lrc = record_labels(h, c, r, st)) return lrc;
+            return drive_plant(h, c, r, i, st);
         });
-    if (rc || !pl.torque) return rc;
+    if (rc || !c.plant) return rc;
     // the state the last interval left: a robot that fell in it is flagged and stamped with the last replan
-    const int frc = nmpc_observe_batch(pl.torque, B, q, v, (double)((long long)(replan0 + cfg->n_replans) * cfg->replanning_steps) * cfg->sim_dt,
-                                       (double)cfg->nominal_period, nullptr, 0, nullptr, nullptr, 0, cfg->collision_height, nullptr, 0,
-                                       nullptr, failed, replan0 + cfg->n_replans - 1, cfg->terminate_mask & NMPC_ROLLOUT_FLAG_MASK, st);
-    if (frc) return fail(h, frc, std::string("nmpc_observe_batch: ") + nmpc_torque_last_error(pl.torque));
-    return NMPC_OK;
+    const int frc = nmpc_observe_batch(c.plant, B, q, v, c.time(c.n_replans), (double)cfg->nominal_period, nullptr, 0, nullptr, nullptr, 0,
+                                       cfg->collision_height, nullptr, 0, nullptr, failed, c.replan0 + c.n_replans - 1, c.term_mask, st);
+    return torque_call(h, frc, "nmpc_observe_batch", c.plant);
 }
 
 int nmpc_wb_label_states_batch(void* handle, void* torque_handle, int B, const nmpc_wb_label_cfg* cfg, const signed char* gait,
@@ -911,21 +979,15 @@ int nmpc_wb_label_states_batch(void* handle, void* torque_handle, int B, const n
     hipStream_t st = static_cast<hipStream_t>(stream);
     NMPC_ENTER(h, h->device);
     if (const int rc = clean_workspace(h, st)) return rc;
-    const WbRoll roll = wb_roll(h);                                 // the carve-up of nmpc_wb_rollout_batch
     nmpc::wb::WbLabelArgs r{};
     r.K = K; r.N = N; r.npc = cfg->nodes_per_cycle; r.qv_rows = qv_rows;
     r.force_gravity = cfg->force_reference_gravity ? 1 : 0;
     r.step_height = cfg->step_height;
     r.sim_dt = cfg->sim_dt; r.t_horizon = cfg->time_horizon; r.nom_height = cfg->nom_height; r.height_offset = cfg->height_offset;
-    r.mp = h->mp;
+    if (const int rc = set_wb_problem(h, r)) return rc;             // the carve-up and the mass of nmpc_wb_rollout_batch
     const bool tree_h = tree_state_momentum(h);
-    if (tree_h) {       // as nmpc_wb_rollout_batch: the weight share of the force reference takes the mass of the tree
-        if (const char* why = nmpc_torque::momentum_refusal(h->momentum.torque, h->device)) return fail(h, NMPC_E_STATE, std::string("momentum model: ") + why);
-        r.mp.mass = nmpc_torque::tree_mass(h->momentum.torque);
-    }
     r.gait = gait; r.peaks = peaks; r.node = node; r.ref_steps = ref_steps; r.failed = failed; r.Q = Q; r.V = V; r.joint_ref = joint_ref;
     r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state;
-    r.yref = roll.yref; r.yref_e = roll.yref_e; r.params = roll.params; r.x0 = roll.x0;
     r.X = X; r.U = U; r.skip = h->label_skip;
     nmpc::wb::WbArgs w = wb_args(h);
     w.yref_per_stage = 1; w.shift = 0;
@@ -939,31 +1001,22 @@ int nmpc_wb_label_states_batch(void* handle, void* torque_handle, int B, const n
         const int count = (int)(total - m0 < B_max ? total - m0 : B_max);
         r.m0 = (int)m0;
         hipLaunchKernelGGL(nmpc::wb::nmpc_wb_label_prepare_kernel, dim3(count), dim3(64), 0, st, r);
-        // x0's momentum from the tree: problem m = b K + k reads row k of robot b; where the tables have exactly K rows per robot the
-        // chunk's states are one strided run, otherwise robot by robot
-        for (long long m = m0; tree_h && m < m0 + count;) {
-            const long long b = m / K, k = m - b * K;
-            const int run = qv_rows == K ? count : (int)((K - k < m0 + count - m) ? K - k : m0 + count - m);
-            const size_t i = (size_t)(m - m0), row = ((size_t)b * qv_rows + k) * 18;
-            if (const int rc = launch_state_momentum(h, run, Q + row, V + row, 18, r.x0 + i * nmpc::wb::NX, X + i * (N + 1) * nmpc::wb::NX,
-                                                     h->label_skip + i, 1, st))
+        // x0's momentum from the tree: problem m = b K + k reads row k of robot b of Q, V
+        if (tree_h)
+            if (const int rc = runs_by_robot(m0, count, K, qv_rows, [&](size_t i, int run, size_t row) {
+                    return launch_state_momentum(h, run, Q + row * 18, V + row * 18, 18, r.x0 + i * nmpc::wb::NX, X + i * (N + 1) * nmpc::wb::NX,
+                                                 h->label_skip + i, 1, st);
+                }))
                 return rc;
-            m += run;
-        }
         w.B = count; w.status = status + m0;
         if (const int rc = launch_wb(h, w, st)) return rc;
-        // label row 0 of every plan of the chunk: the target applied from the state its solve started from.  Problem m = b K + k
-        // goes to A[b][k]; where the table has exactly K rows per robot that is row m of a dense table, otherwise robot by robot
-        for (long long m = m0; m < m0 + count;) {
-            const long long b = m / K, k = m - b * K;
-            const int run = a_rows == K ? count : (int)((K - k < m0 + count - m) ? K - k : m0 + count - m);
-            const size_t i = (size_t)(m - m0);
-            const int lrc = nmpc_plan_actions_batch(torque_handle, run, 1, N, X + i * (N + 1) * nmpc::wb::NX, U + i * N * nmpc::wb::NU, zoh, dt_nodes,
-                                                    cfg->sim_dt, cfg->kp, cfg->kd, nullptr, h->label_skip + i, 1,
-                                                    A + ((size_t)b * a_rows + k) * 12, 1, st);
-            if (lrc) return fail(h, lrc, std::string("nmpc_plan_actions_batch: ") + nmpc_torque_last_error(torque_handle));
-            m += run;
-        }
+        // label row 0 of every plan of the chunk: the target applied from the state its solve started from, into A[b][k]
+        if (const int rc = runs_by_robot(m0, count, K, a_rows, [&](size_t i, int run, size_t row) {
+                const int lrc = nmpc_plan_actions_batch(torque_handle, run, 1, N, X + i * (N + 1) * nmpc::wb::NX, U + i * N * nmpc::wb::NU, zoh, dt_nodes,
+                                                        cfg->sim_dt, cfg->kp, cfg->kd, nullptr, h->label_skip + i, 1, A + row * 12, 1, st);
+                return torque_call(h, lrc, "nmpc_plan_actions_batch", torque_handle);
+            }))
+            return rc;
     }
     return launched(h);
 }

@@ -342,25 +342,21 @@ class BatchedLocomotionMPC:
             self._gait_dev = s.to_device(self.contact_planner.gait_sequence, torch.int8)
         windows = push_windows(push, x.shape[0])
         if windows is not None:             # a window per rollout: attached for this call, the cfg's own window unused
-            s.set_rollout_push_windows(*windows)
-            try:
-                return self._device_rollout(n_replans, start_node, first_solve, dict(push, start=0.0, duration=0.0), x, v_des, w_des,
-                                            ref_state, foot, X, U, status)
-            finally:
-                s.set_rollout_push_windows(None)
-        return s.rollout(
-            self._gait_dev, x, v_des, w_des, ref_state, foot, s.to_device(np.asarray(push["force"])) if push else None,
-            np.round((times % period) / period, 4), X, U, status,
-            n_replans=n_replans, nodes_per_replan=self.nodes_per_replan, replanning_steps=self.replanning_steps,
-            nodes_per_cycle=self.contact_planner.nodes_per_cycle, start_node=start_node, first_solve=int(first_solve),
-            max_sqp_first=N_SQP_FIRST, nlp_tol_first=self.config_opt.nlp_tol / 10.0, nlp_tol=self.config_opt.nlp_tol,
-            sim_dt=self.sim_dt, time_horizon=self.config_opt.time_horizon, nom_height=self.config_gait.nom_height,
-            height_offset=self.height_offset, push_start=float(push["start"]) if push else 0.0,
-            push_duration=float(push["duration"]) if push else 0.0, footsteps=int(self.footsteps),
-            record_sim_steps=int(self.record_sim_steps), hip_offset=self.raibert.offset_hip_b[:, :2].ravel().tolist(),
-            stance_ratio=np.asarray(self.config_gait.stance_ratio, float).tolist(), nominal_period=float(period),
-            foot_size=float(self.raibert.foot_size), terminate_mask=int(self.terminate_mask),
-            collision_height=float(self.collision_height))
+            push = dict(push, start=0.0, duration=0.0)
+        with s.rollout_push_windows(windows):
+            return s.rollout(
+                self._gait_dev, x, v_des, w_des, ref_state, foot, s.to_device(np.asarray(push["force"])) if push else None,
+                np.round((times % period) / period, 4), X, U, status,
+                n_replans=n_replans, nodes_per_replan=self.nodes_per_replan, replanning_steps=self.replanning_steps,
+                nodes_per_cycle=self.contact_planner.nodes_per_cycle, start_node=start_node, first_solve=int(first_solve),
+                max_sqp_first=N_SQP_FIRST, nlp_tol_first=self.config_opt.nlp_tol / 10.0, nlp_tol=self.config_opt.nlp_tol,
+                sim_dt=self.sim_dt, time_horizon=self.config_opt.time_horizon, nom_height=self.config_gait.nom_height,
+                height_offset=self.height_offset, push_start=float(push["start"]) if push else 0.0,
+                push_duration=float(push["duration"]) if push else 0.0, footsteps=int(self.footsteps),
+                record_sim_steps=int(self.record_sim_steps), hip_offset=self.raibert.offset_hip_b[:, :2].ravel().tolist(),
+                stance_ratio=np.asarray(self.config_gait.stance_ratio, float).tolist(), nominal_period=float(period),
+                foot_size=float(self.raibert.foot_size), terminate_mask=int(self.terminate_mask),
+                collision_height=float(self.collision_height))
 
     def open_loop_device(self, x0: np.ndarray, trajectory_time: float, push: Optional[dict] = None):
         """`open_loop` with the whole rollout on the device: one C call launches every replanning

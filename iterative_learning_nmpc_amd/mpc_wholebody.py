@@ -17,7 +17,9 @@ the path (C8, C10, C11).
 """
 from __future__ import annotations
 
+import contextlib
 from collections import defaultdict
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import numpy as np
@@ -283,6 +285,8 @@ class LocomotionMPC:
         is): a rollout that entered the call terminated stays frozen, its rows of the call are its frozen state -- cut at its
         stamp.  Between two stretches the host may `set_command`, look at `self.failed`, save or stop."""
         import torch
+        from .mpc import push_windows
+        # 1. what the arguments alone decide, and the clock: a refused call has touched neither the device nor the solver's options
         if (trajectory_time is None) == (n_replans is None):
             raise ValueError("open_loop_device: give trajectory_time or n_replans, one of them")
         if resume and n_replans is None:
@@ -292,92 +296,126 @@ class LocomotionMPC:
             integrator_mode(integrator)                   # an unknown name is refused before anything runs
             if plant is None:
                 raise ValueError("integrator: the integrator is the contact plant's, give plant")
-        if n_replans is None:
-            steps, nodes, node_end, time_end = self._run_clock(0.0, lambda sim_time, steps: sim_time <= trajectory_time)
-        else:
-            steps, nodes, node_end, time_end = self.replan_clock_intervals(n_replans, resume)
-        n_replans = len(nodes)
-        clock_step0 = self.clock_step if resume else 0
-        replan0 = clock_step0 // self.replanning_steps
+        clock = self._device_clock(trajectory_time, n_replans, resume)
+        n_replans, replan0 = len(clock.nodes), clock.clock_step0 // self.replanning_steps
         self._declared_momentum_only("open_loop_device")
-        fs = self.solver
-        s = fs._device_solver()
-        B, N, dev = self.batch, self.config_opt.n_nodes, s.device
-        failed_in = self.failed.clone() if replan0 else None        # a continued rollout keeps its flags and stamps
-        cfg_o = self.config_opt
-        s.set_max_iter(cfg_o.max_iter); s.set_nlp_tol(cfg_o.nlp_tol); s.set_max_qp_iter(cfg_o.max_qp_iter)
-        fs._opts.update(max_iter=cfg_o.max_iter, nlp_tol=cfg_o.nlp_tol, qp_tol=cfg_o.qp_tol)
-        by_rollout = lambda a, dtype=torch.float32: s.to_device(np.asarray(a, np.float64).reshape(B, -1), dtype)   # noqa: E731
-        # (the q_final, v_final of the call that is continued may be handed over as they are: device tensors, copied)
-        q, v = (a.to(dev, torch.float32).reshape(B, -1).clone() if isinstance(a, torch.Tensor) else by_rollout(a) for a in (q0, v0))
-        v_des, w_des, ref_state = (by_rollout(a, torch.float64) for a in (self.v_des, self.w_des, self.base_ref_vel_tracking))
-        if getattr(self, "_X_dev", None) is None or self.first_solve:
-            self._X_dev = torch.zeros(B, N + 1, 42, dtype=torch.float32, device=dev)
-            self._U_dev = torch.zeros(B, N, 30, dtype=torch.float32, device=dev)
-        status = torch.zeros(B, dtype=torch.int32, device=dev)
         if plant is not None and torque_layer is None:
             raise ValueError("plant: the contact plant lives in the torque layer, give torque_layer")
         if push_as_force and plant is None:
             raise ValueError("push_as_force: a push as a force needs the contact plant, give plant")
         kp = (self.Kp if plant is not None else KP) if kp is None else kp
         kd = (self.Kd if plant is not None else KD) if kd is None else kd
-        from .mpc import push_windows
-        windows = push_windows(push, B)               # a window per rollout: attached for this call, the cfg's own window unused
+        windows = push_windows(push, self.batch)      # a window per rollout: attached for this call, the cfg's own window unused
         if windows is not None:
             push = dict(push, start=0.0, duration=0.0)
-        A = None
+        # 2. the device inputs
+        fs, cfg_o = self.solver, self.config_opt
+        s = fs._device_solver()
+        s.set_max_iter(cfg_o.max_iter); s.set_nlp_tol(cfg_o.nlp_tol); s.set_max_qp_iter(cfg_o.max_qp_iter)
+        fs._opts.update(max_iter=cfg_o.max_iter, nlp_tol=cfg_o.nlp_tol, qp_tol=cfg_o.qp_tol)
+        failed_in = self.failed.clone() if replan0 else None        # a continued rollout keeps its flags and stamps
+        q, v, v_des, w_des, ref_state, status = self._device_inputs(s, q0, v0)
+        actions = None
         if torque_layer is not None:
             rows = n_replans * (self.replanning_steps if record_sim_steps else 1)
-            A = torch.zeros(B, rows, 12, dtype=torch.float32, device=dev)
-            s.set_rollout_actions(torque_layer, s.to_device(self.id_repeat[:self.replanning_steps], torch.int32), A, kp, kd)
-        try:
+            A = torch.zeros(self.batch, rows, 12, dtype=torch.float32, device=s.device)
+            actions = (torque_layer, s.to_device(self.id_repeat[:self.replanning_steps], torch.int32), A, kp, kd)
+        # 3. the attachments, 4. the call
+        with self._rollout_attachments(s, actions, integrator, None if plant is None else (torque_layer, plant, plant_substeps, kp, kd),
+                                       push_as_force, replan0, windows):
+            S, failed = s.wb_rollout(
+                *self._gait_tensors(s), clock.nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref),
+                self._by_rollout(s, push["force"]) if push else None,
+                self._X_dev, self._U_dev, status, failed=failed_in, n_replans=n_replans, replanning_steps=self.replanning_steps,
+                first_solve=int(self.first_solve), last_node=int(fs.last_node), max_sqp_first=N_SQP_FIRST,
+                nlp_tol_first=cfg_o.nlp_tol / 10.0, nlp_tol=cfg_o.nlp_tol, push_start=float(push["start"]) if push else 0.0,
+                push_duration=float(push["duration"]) if push else 0.0, record_sim_steps=int(record_sim_steps),
+                nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
+                collision_height=float(collision_height), **self._problem_cfg())
+        # 5. the books
+        self._commit_rollout(clock, q, v, ref_state, status, failed, None if actions is None else actions[2])
+        return S[:, :clock.steps] if record_sim_steps else S
+
+    def _device_clock(self, trajectory_time, n_replans, resume):
+        """the clock of one `open_loop_device` call, from the controller's counters: over `trajectory_time` as `replan_clock` runs
+        it, or over `n_replans` whole intervals (`replan_clock_intervals`, which refuses what cannot be continued) -> steps, nodes,
+        node_end, time_end as `_run_clock` names them, and clock_step0: the steps the rollout it continues has run (0: it starts one)"""
+        if n_replans is None:
+            steps, nodes, node_end, time_end = self._run_clock(0.0, lambda sim_time, steps: sim_time <= trajectory_time)
+        else:
+            steps, nodes, node_end, time_end = self.replan_clock_intervals(n_replans, resume)
+        return SimpleNamespace(steps=steps, nodes=nodes, node_end=node_end, time_end=time_end, clock_step0=self.clock_step if resume else 0)
+
+    def _by_rollout(self, s, a, dtype=None):
+        """a host array with one row per rollout on the device of `s` (float32 unless told otherwise)"""
+        return s.to_device(np.asarray(a, np.float64).reshape(self.batch, -1), *(() if dtype is None else (dtype,)))
+
+    def _device_inputs(self, s, q0, v0):
+        """the tensors of one `open_loop_device` call -> (q, v [B, 18] float32: copies, the plant state the call moves; v_des, w_des,
+        ref_state float64; status int32 [B]); `_X_dev`, `_U_dev` are zeroed for a first solve"""
+        import torch
+        B, N, dev = self.batch, self.config_opt.n_nodes, s.device
+        # (the q_final, v_final of the call that is continued may be handed over as they are: device tensors, copied)
+        q, v = (a.to(dev, torch.float32).reshape(B, -1).clone() if isinstance(a, torch.Tensor) else self._by_rollout(s, a) for a in (q0, v0))
+        v_des, w_des, ref_state = (self._by_rollout(s, a, torch.float64) for a in (self.v_des, self.w_des, self.base_ref_vel_tracking))
+        if getattr(self, "_X_dev", None) is None or self.first_solve:
+            self._X_dev = torch.zeros(B, N + 1, 42, dtype=torch.float32, device=dev)
+            self._U_dev = torch.zeros(B, N, 30, dtype=torch.float32, device=dev)
+        return q, v, v_des, w_des, ref_state, torch.zeros(B, dtype=torch.int32, device=dev)
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _rollout_attachments(s, actions, integrator, plant, push_as_force, replan0, windows):
+        """What one `open_loop_device` call attaches to the device solver `s` for the duration of its rollout: actions and plant
+        (the arguments of `set_rollout_actions` / `set_rollout_plant`, None: not attached; integrator: set on the plant's layer
+        first, where it stays), the push as a force, the clock and the windows per rollout (`rollout_push_windows`) -- in this
+        order, and detached in the reverse one whatever happens, an attach call that raises included: the handle ends with
+        nothing of the call attached."""
+        with contextlib.ExitStack() as detach:
+            if actions is not None:
+                detach.callback(s.set_rollout_actions, None)
+                s.set_rollout_actions(*actions)
             if plant is not None:
                 if integrator is not None:
-                    torque_layer.set_integrator(integrator)
-                s.set_rollout_plant(torque_layer, plant, plant_substeps, kp, kd)
+                    plant[0].set_integrator(integrator)
+                detach.callback(s.set_rollout_plant, None)
+                s.set_rollout_plant(*plant)
             if push_as_force:
+                detach.callback(s.set_rollout_plant_push, False)
                 s.set_rollout_plant_push(True)
+            detach.callback(s.set_rollout_clock, 0)
             s.set_rollout_clock(replan0)
-            if windows is not None:
-                s.set_rollout_push_windows(*windows)
-            S, failed = s.wb_rollout(
-                s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
-                nodes, q, v, v_des, w_des, ref_state, s.to_device(self.joint_ref), by_rollout(push["force"]) if push else None,
-                self._X_dev, self._U_dev, status, failed=failed_in,
-                n_replans=n_replans, replanning_steps=self.replanning_steps, nodes_per_cycle=self.contact_planner.nodes_per_cycle,
-                first_solve=int(self.first_solve), last_node=int(fs.last_node), max_sqp_first=N_SQP_FIRST,
-                nlp_tol_first=cfg_o.nlp_tol / 10.0, nlp_tol=cfg_o.nlp_tol, sim_dt=self.sim_dt, time_horizon=cfg_o.time_horizon,
-                nom_height=self.config_gait.nom_height, height_offset=self.height_offset,
-                step_height=float(self.config_gait.step_height), push_start=float(push["start"]) if push else 0.0,
-                push_duration=float(push["duration"]) if push else 0.0, record_sim_steps=int(record_sim_steps),
-                force_reference_gravity=int(fs.force_reference == "gravity_share"),
-                nominal_period=float(self.config_gait.nominal_period), terminate_mask=int(terminate_mask),
-                collision_height=float(collision_height))
-        finally:
-            if windows is not None:
-                s.set_rollout_push_windows(None)
-            s.set_rollout_clock(0)
-            if push_as_force:
-                s.set_rollout_plant_push(False)
-            if plant is not None:
-                s.set_rollout_plant(None)
-            if torque_layer is not None:
-                s.set_rollout_actions(None)
-        # bookkeeping as open_loop leaves it
+            detach.enter_context(s.rollout_push_windows(windows))
+            yield
+
+    def _commit_rollout(self, clock, q, v, ref_state, status, failed, A) -> None:
+        """the bookkeeping of a rollout that ran, as `open_loop` leaves it"""
+        fs = self.solver
         self.first_solve = False
-        self.sim_step += steps
-        self.sim_time, self.clock_step = time_end, clock_step0 + steps
-        self.current_opt_node = node_end
-        fs.last_node = nodes[-1]
+        self.sim_step += clock.steps
+        self.sim_time, self.clock_step = clock.time_end, clock.clock_step0 + clock.steps
+        self.current_opt_node = clock.node_end
+        fs.last_node = clock.nodes[-1]
         ref = ref_state.cpu().numpy()
         # (open_loop integrates the reference once per simulation step it runs; the device does it per full replanning interval)
         self.base_ref_vel_tracking = ref if self.batch > 1 else ref[0]
         self.failed, self.status_dev = failed, status
         self.q_final, self.v_final = q, v
         if A is not None:
-            self.actions = A[:, :steps]
+            self.actions = A[:, :clock.steps]
         fs.parse_sol(self._X_dev.cpu().numpy().astype(np.float64), self._U_dev.cpu().numpy().astype(np.float64))
-        return S[:, :steps] if record_sim_steps else S
+
+    def _problem_cfg(self) -> dict:
+        """the cfg fields of the problem that `open_loop_device` and `label_states` hand over alike"""
+        return dict(nodes_per_cycle=self.contact_planner.nodes_per_cycle, sim_dt=self.sim_dt, time_horizon=self.config_opt.time_horizon,
+                    nom_height=self.config_gait.nom_height, height_offset=self.height_offset,
+                    step_height=float(self.config_gait.step_height),
+                    force_reference_gravity=int(self.solver.force_reference == "gravity_share"))
+
+    def _gait_tensors(self, s):
+        """(gait_sequence, peak_swing) of the contact planner as int8 on the device of `s`"""
+        import torch
+        return tuple(s.to_device(t, torch.int8) for t in (self.contact_planner.gait_sequence, self.contact_planner.peak_swing))
 
     def label_clock(self, n_rows: int, t0: float, dt_row: float):
         """The float clock of `replan_clock` for rows that are not replans: row k of a table of visited states was reached at
@@ -409,22 +447,17 @@ class LocomotionMPC:
         and `_X_dev` / `_U_dev` are as they were."""
         import torch
         self._declared_momentum_only("label_states")
-        fs = self.solver
-        s = fs._device_solver()
+        s = self.solver._device_solver()
         if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] != self.batch:
             raise ValueError(f"Q: need a float32 tensor [{self.batch}, K, 18] on the GPU")
-        B, K = Q.shape[0], Q.shape[1]
-        nodes, ref_steps = self.label_clock(K, t0, self.replanning_steps * self.sim_dt if dt_row is None else dt_row)
-        cfg_o = self.config_opt
-        by_robot = lambda a: s.to_device(np.asarray(a, np.float64).reshape(B, -1), torch.float64)   # noqa: E731
+        nodes, ref_steps = self.label_clock(Q.shape[1], t0, self.replanning_steps * self.sim_dt if dt_row is None else dt_row)
+        by_robot = lambda a: self._by_rollout(s, a, torch.float64)   # noqa: E731
         A, status, _, _ = s.label_states(
-            torque_layer, s.to_device(self.contact_planner.gait_sequence, torch.int8), s.to_device(self.contact_planner.peak_swing, torch.int8),
-            s.to_device(nodes, torch.int32), s.to_device(ref_steps, torch.int32), Q, V, by_robot(self.v_des), by_robot(self.w_des),
-            by_robot(self.base_ref_vel_tracking), s.to_device(self.joint_ref), s.to_device(self.id_repeat[:1], torch.int32), failed=failed,
-            nodes_per_cycle=self.contact_planner.nodes_per_cycle, max_sqp=N_SQP_FIRST, nlp_tol=cfg_o.nlp_tol / 10.0, sim_dt=self.sim_dt,
-            time_horizon=cfg_o.time_horizon, nom_height=self.config_gait.nom_height, height_offset=self.height_offset,
-            step_height=float(self.config_gait.step_height), force_reference_gravity=int(fs.force_reference == "gravity_share"),
-            kp=float(self.Kp if kp is None else kp), kd=float(self.Kd if kd is None else kd), terminate_mask=int(TERMINATE_DEFAULT))
+            torque_layer, *self._gait_tensors(s), s.to_device(nodes, torch.int32), s.to_device(ref_steps, torch.int32), Q, V,
+            by_robot(self.v_des), by_robot(self.w_des), by_robot(self.base_ref_vel_tracking), s.to_device(self.joint_ref),
+            s.to_device(self.id_repeat[:1], torch.int32), failed=failed, max_sqp=N_SQP_FIRST, nlp_tol=self.config_opt.nlp_tol / 10.0,
+            kp=float(self.Kp if kp is None else kp), kd=float(self.Kd if kd is None else kd), terminate_mask=int(TERMINATE_DEFAULT),
+            **self._problem_cfg())
         return A, status
 
     def set_state_momentum(self, source: str = "declared") -> None:

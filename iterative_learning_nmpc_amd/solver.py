@@ -12,6 +12,7 @@ reported in `status` (acados numbering) instead of exceptions (mpc.py:562-569).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from collections import defaultdict
 from typing import Optional, Tuple
@@ -120,11 +121,7 @@ class BatchedNmpcSolver:
         if not isinstance(A, torch.Tensor) or A.dim() != 3:
             raise ValueError("A: need a float32 tensor [B, rows, 12] on the GPU")
         self._chk(A, (A.shape[0], A.shape[1], 12), "A")
-        if not isinstance(zoh, torch.Tensor) or zoh.dim() != 1:
-            raise ValueError("zoh: need an int32 tensor [replanning_steps] on the GPU")
-        self._chk(zoh, (zoh.shape[0],), "zoh", torch.int32)
-        if not bool(((zoh >= 0) & (zoh < self.n_nodes)).all()):
-            raise ValueError(f"zoh: node indices must lie in [0, {self.n_nodes})")
+        self._chk_zoh(zoh)
         self._labels = (layer, zoh, A)
         _lib.check(self.lib.nmpc_wb_rollout_set_actions(self._h, layer._h, ptr(zoh), float(kp), float(kd), ptr(A)),
                    self._h, "nmpc_wb_rollout_set_actions")
@@ -145,11 +142,7 @@ class BatchedNmpcSolver:
                        "nmpc_wb_rollout_set_plant")
             return
         if zoh is not None:
-            if not isinstance(zoh, torch.Tensor) or zoh.dim() != 1:
-                raise ValueError("zoh: need an int32 tensor [replanning_steps] on the GPU")
-            self._chk(zoh, (zoh.shape[0],), "zoh", torch.int32)
-            if not bool(((zoh >= 0) & (zoh < self.n_nodes)).all()):
-                raise ValueError(f"zoh: node indices must lie in [0, {self.n_nodes})")
+            self._chk_zoh(zoh)
         labels = getattr(self, "_labels", None)
         steps = zoh.shape[0] if zoh is not None else (labels[1].shape[0] if labels is not None else 0)
         if steps < 1:
@@ -198,6 +191,19 @@ class BatchedNmpcSolver:
             raise ValueError(f"start, duration: need one entry per rollout each, got {tuple(start.shape)} and {tuple(duration.shape)}")
         self._push_windows = (start, duration)
         _lib.check(call(self._h, ptr(start), ptr(duration), start.shape[0]), self._h, name)
+
+    @contextlib.contextmanager
+    def rollout_push_windows(self, windows):
+        """`set_rollout_push_windows(*windows)` for the duration of a block: attached at its entry, detached behind it whatever
+        happens in it.  windows None (`mpc.push_windows` of a push with a scalar window): nothing is attached and nothing detached."""
+        if windows is None:
+            yield
+            return
+        try:
+            self.set_rollout_push_windows(*windows)
+            yield
+        finally:
+            self.set_rollout_push_windows(None)
 
     MOMENTUM_MODELS = {"declared": 0, "articulated": 1}      # NMPC_WB_MOMENTUM_* of include/nmpc.h
 
@@ -260,6 +266,17 @@ class BatchedNmpcSolver:
             raise ValueError(f"{name}: need contiguous {dtype} {tuple(shape)} on the GPU, got "
                              f"{t.dtype} {tuple(t.shape)} on {t.device}")
         return t
+
+    def _chk_zoh(self, zoh, shape=None) -> None:
+        """a hold table: int32 of `shape` on the device (None: one entry per simulation step of a replan, any number of them),
+        every entry a node of the horizon"""
+        if shape is None:
+            if not isinstance(zoh, torch.Tensor) or zoh.dim() != 1:
+                raise ValueError("zoh: need an int32 tensor [replanning_steps] on the GPU")
+            shape = (zoh.shape[0],)
+        self._chk(zoh, shape, "zoh", torch.int32)
+        if not bool(((zoh >= 0) & (zoh < self.n_nodes)).all()):
+            raise ValueError(f"zoh: node indices must lie in [0, {self.n_nodes})")
 
     def to_device(self, a, dtype=torch.float32) -> torch.Tensor:
         return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(self.device).contiguous()
@@ -398,9 +415,7 @@ class BatchedNmpcSolver:
         self._chk(w_des, (B, 3), "w_des", torch.float64)
         self._chk(ref_state, (B, 12), "ref_state", torch.float64)
         self._chk(joint_ref, (12,), "joint_ref")
-        self._chk(zoh, (1,), "zoh", torch.int32)
-        if not bool(((zoh >= 0) & (zoh < N)).all()):
-            raise ValueError(f"zoh: node indices must lie in [0, {N})")
+        self._chk_zoh(zoh, (1,))
         if failed is not None:
             self._chk(failed, (B,), "failed", torch.int32)
         chunk = min(B * K, self.batch_max)
