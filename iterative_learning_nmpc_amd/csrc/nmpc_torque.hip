@@ -12,12 +12,13 @@
 // The other direction -- accelerations from torques and given contact forces, and a PD-driven integration step around them --
 // is nmpc_torque_fd.hip.inc, included below; the declared ground-contact law, the foot kinematics it needs and the plant step
 // that evaluates it inside that recursion are nmpc_torque_contact.hip.inc; the observation of a plant state for a policy in the
-// loop is nmpc_torque_policy.hip.inc, and the loop itself (nmpc_policy_rollout_batch) is host code at the end of this file;
+// loop and of the rows of a table of states -- one kernel text, two instantiations -- is nmpc_torque_policy.hip.inc, and the loop
+// itself (nmpc_policy_rollout_batch) is host code at the end of this file;
 // what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of one composite-rigid-body
 // pass -- is nmpc_torque_crba.hip.inc; the correction of the plant's second integrator, which takes the stiff contact and PD terms
 // implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; the chain of control steps on the plant -- one
 // kernel text, instantiated for a table of PD targets tracked in one launch, for pushed substeps, for a push window per robot
-// and for the implicit integrator -- and the rows of the states it ran through are nmpc_torque_track.hip.inc; the centroidal momentum about an anchor
+// and for the implicit integrator -- is nmpc_torque_track.hip.inc; the centroidal momentum about an anchor
 // point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
 // momentum A_g(q) v of a plant state alone, which the device rollouts put into x0.
@@ -201,7 +202,10 @@ __global__ __launch_bounds__(TPB) void id_torques_kernel(const Model* __restrict
 // a(i) of joint i, has_f() and f_at(k), the world-frame force at foot k; out(i, act, tau) takes the torque of actuated joint
 // i = n - nu + act on the way back.  Per-body state in the block's LDS slice [joint][SLOTS][TPB], as above.
 // id_torques_kernel above keeps its own text: routed through this function it compiles to other packed / fused products and
-// rounds differently on tilted trees, and its outputs are held bit for bit.  A change to the recursion goes into both.
+// rounds differently on tilted trees, and its outputs are held bit for bit.  Nor did one __global__ template over a job type
+// (prologue, accessors, sink and epilogue of either kernel, switched at compile time) keep both: its id instantiation gave
+// nmpc_id_torques_batch's bits, but its plan instantiation fused other products than plan_actions_kernel does through this
+// function and changed the labels on tilted trees.  A change to the recursion goes into both.
 template <class In, class Out>
 __device__ __forceinline__ void id_torques_body(const Model& m, const In& in, const Out& out) {
     const int n = m.n;
@@ -988,7 +992,7 @@ int nmpc_observe_batch(void* handle, int B, const float* q, const float* v, doub
     a.t = t; a.period = period; a.collision_height = collision_height;
     a.q = q; a.v = v; a.goal = goal; a.s_mean = s_mean; a.s_std = s_std; a.S = S; a.X = X; a.failed = failed;
     const size_t lds = (S || X) ? ob_lds_bytes(h->host.n) : 0;      // the flags alone run no kinematics and ask for no slice
-    hipLaunchKernelGGL(observe_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream), h->dev, a);
+    hipLaunchKernelGGL(observe_kernel<ObserveArgs>, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream), h->dev, a);
     return launched(h);
 }
 
@@ -1018,7 +1022,7 @@ int nmpc_observe_rows_batch(void* handle, int B, int n_rows, const float* Q, con
     a.t0 = t0; a.dt_row = dt_row; a.period = period; a.collision_height = collision_height;
     a.Q = Q; a.V = V; a.S = S; a.failed = failed; a.skip = a.skip_mask ? skip : nullptr;
     const size_t lds = S ? ob_lds_bytes(h->host.n) : 0;      // the flags alone run no kinematics and ask for no slice
-    hipLaunchKernelGGL(observe_rows_kernel, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream), h->dev, a);
+    hipLaunchKernelGGL(observe_kernel<ObserveRowsArgs>, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream), h->dev, a);
     return launched(h);
 }
 

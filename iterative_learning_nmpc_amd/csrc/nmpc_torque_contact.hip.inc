@@ -140,8 +140,11 @@ struct ContactArgs {
 // Nor is this kernel an instantiation of contact_chain_kernel (nmpc_torque_track.hip.inc), which states the same substep for
 // every chain of control steps: its arguments are another struct (inputs apart from the outputs, one target row, no table, no
 // skip flags) and it writes NaN on the way out where the chain fills the slice, so joining would take a switch at every one of
-// those places.  That was not tried when the chain became one text (DESIGN.md 8d): a fix to the PD law, the clamp, the Euler
-// update or the NaN rule goes here and into the chain.
+// those places.  As the instantiation of the chain for StepArgs : PushArgs with Forces::ground (the step's start state and
+// outputs on the un-pushed recursion) it gave this kernel's bits, but it is another 194 instructions (the control-step loop,
+// the table and the skip flags stay in) and cost the policy rollout 1.6 us of the 150 us of a two-substep step, eight times the
+// parent's own spread (DESIGN.md 8d): a fix to the PD law, the clamp, the Euler update or the NaN rule goes here and into the
+// chain.
 template <int W>
 __global__ __launch_bounds__(W) void contact_step_kernel(const Model* __restrict__ mp, const ContactArgs p) {
     extern __shared__ float body[];                       // [joint][CT_SLOTS][W]

@@ -1,14 +1,15 @@
 // nmpc_torque_track.hip.inc -- the chain of control steps on the ground-contact plant: a table of PD targets tracked in one launch,
-// pushed, under a window per robot or under the implicit integrator, and the observation of the states it ran through
-// (nmpc_contact_track_batch, nmpc_observe_rows_batch of include/nmpc_torque.h, and every launch of nmpc_contact_step_batch but the
-// un-pushed explicit one); included by nmpc_torque.hip inside namespace nmpc_torque, after nmpc_torque_implicit.hip.inc.
+// pushed, under a window per robot or under the implicit integrator (nmpc_contact_track_batch of include/nmpc_torque.h, and every
+// launch of nmpc_contact_step_batch but the un-pushed explicit one); included by nmpc_torque.hip inside namespace nmpc_torque,
+// after nmpc_torque_implicit.hip.inc.
 //
 // The whole-body expert on the declared plant (DESIGN.md 8h): the label row of a plan, A = (tau_id + kd v_plan) / kp + q_plan,
 // handed to the contact step as q_des gives tau = tau_id + kp (q_plan - q) + kd (v_plan - v), the reference's
 // _compute_pd_torques on the plan's inverse-dynamics torque (mpc.py:583-599).  So a replanning interval is a chain of contact
 // steps, one per row of the label table; contact_chain_kernel runs that chain in one launch with the robot's state resident in
-// the LDS, observe_rows_kernel turns the states it went through into the 44-slot rows and the fall predicates.
-// Both are held bit for bit to the chain of public calls they replace (tests/test_gpu_contact_track.py).
+// the LDS, and observe_kernel<ObserveRowsArgs> (nmpc_torque_policy.hip.inc) turns the states it went through into the 44-slot
+// rows and the fall predicates.  Both are held bit for bit to the chain of public calls they replace
+// (tests/test_gpu_contact_track.py).
 #pragma once
 
 // ---- the arguments of the chain, one struct per instantiation of contact_chain_kernel ---------------------------------------------
@@ -198,103 +199,3 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
     }
 }
 
-// ---- the rows of a table of states --------------------------------------------------------------------------------------------
-struct ObserveRowsArgs {
-    int B, n_rows, qv_rows, s_rows, step_index, term_mask, skip_mask;
-    double t0, dt_row, period;
-    float collision_height;
-    const float *Q, *V;                                   // row k of robot b at + (b * qv_rows + k) * 18
-    float* S;                                             // row k of robot b at + (b * s_rows + k) * 44; may be nullptr
-    int* failed;                                          // may be nullptr
-    const int* skip;
-};
-
-// the time of row k, in the two roundings of the host expression t0 + k * dt_row
-__device__ inline double row_time(double t0, int k, double dt_row) {
-#pragma clang fp contract(off)
-    const double d = (double)k * dt_row;
-    return t0 + d;
-}
-
-// observe_kernel's row and flags for every row of the robot's table, one thread per robot: the flags of all rows are gathered
-// in a register and the stamp is set once after them, which is what n_rows calls with one step index leave (the first call
-// that sees a terminating bit stamps, the later ones find the stamp).  The body is observe_kernel's text without the policy
-// input; that kernel keeps its own (nmpc_torque_policy.hip.inc).
-__global__ __launch_bounds__(TPB) void observe_rows_kernel(const Model* __restrict__ mp, const ObserveRowsArgs a) {
-    const Model& m = *mp;
-    const int b = blockIdx.x * TPB + threadIdx.x;
-    if (b >= a.B) return;
-    if (a.skip && (a.skip[b] & a.skip_mask)) return;
-    const int n = m.n;
-    const Slice<OB_SLOTS, TPB> at;
-    int flags = a.failed ? a.failed[b] : 0;
-    for (int r = 0; r < a.n_rows; ++r) {
-        const float* qb = a.Q + ((size_t)b * a.qv_rows + r) * n;
-        const float* vb = a.V + ((size_t)b * a.qv_rows + r) * n;
-        if (a.S) {
-            float* Sb = a.S + ((size_t)b * a.s_rows + r) * OB_STATE;
-            auto put = [&](int j, float s) { Sb[j] = s; };
-            // the outward pass of foot_kernel, positions only
-            for (int i = 0; i < n; ++i) {
-                M3 R; V3 p;
-                joint_transform(m, i, qb[i], R, p);
-                const int par = m.parent[i];
-                V3 pw = p;
-                M3 Rw = R;
-                if (par >= 0) {
-                    M3 Rp;
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) Rp.m[k] = at(par, OB_RW + k);
-                    Rw = mul(Rp, R);
-                    pw = at.get3(par, OB_PW) + mul(Rp, p);
-                }
-#pragma unroll
-                for (int k = 0; k < 9; ++k) at(i, OB_RW + k) = Rw.m[k];
-                at.put3(i, OB_PW, pw);
-            }
-            // the row: [phase, v_lin 3, body rates 3, joint rates 12, z, quaternion wxyz (w >= 0) 4, joints 12, base_wrt_feet 8]
-            put(0, (float)nmpc::recorded_phase(row_time(a.t0, r, a.dt_row), a.period));
-            {   // E(theta) thetadot (wb_body_rates) and the quaternion of `record`, in fp64 from the fp32 state
-                const double yaw = qb[3], pitch = qb[4], roll = qb[5], dyaw = vb[3], dpitch = vb[4], droll = vb[5];
-                const double sy = sin(pitch), cy = cos(pitch), sx = sin(roll), cx = cos(roll);
-                put(4, (float)(-sy * dyaw + droll));
-                put(5, (float)(cy * sx * dyaw + cx * dpitch));
-                put(6, (float)(cx * cy * dyaw - sx * dpitch));
-                const double hy = cos(0.5 * yaw), ky = sin(0.5 * yaw), hp = cos(0.5 * pitch), kp = sin(0.5 * pitch), hr = cos(0.5 * roll), kr = sin(0.5 * roll);
-                double qw = hy * hp * hr + ky * kp * kr, qx = hy * hp * kr - ky * kp * hr, qy = hy * kp * hr + ky * hp * kr, qz = ky * hp * hr - hy * kp * kr;
-                if (qw < 0.0) { qw = -qw; qx = -qx; qy = -qy; qz = -qz; }
-                put(20, (float)qw); put(21, (float)qx); put(22, (float)qy); put(23, (float)qz);
-            }
-            put(19, qb[2]);
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < 3; ++i) put(1 + i, vb[i]);
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int i = 0; i < 12; ++i) { put(7 + i, vb[6 + i]); put(24 + i, qb[6 + i]); }
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int k = 0; k < 4; ++k) {
-                const int j = m.foot_joint[k];
-                M3 Rw;
-#pragma unroll
-                for (int e = 0; e < 9; ++e) Rw.m[e] = at(j, OB_RW + e);
-                const V3 p = at.get3(j, OB_PW) + mul(Rw, v3(m.foot_offset[k]));
-                put(36 + 2 * k, qb[0] - p.x); put(37 + 2 * k, qb[1] - p.y);
-            }
-        }
-        if (a.failed) {
-            // the command handed to the predicates is the state's own velocity: the velocity-tracking bit is never raised here
-            const double own[2] = {(double)vb[0], (double)vb[1]};
-            flags |= nmpc::unsafe_state_flags(qb[5], qb[4], qb[2], vb[0], vb[1], own, a.collision_height);
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int f = 0; f < 4; ++f) {       // joint limits in degrees, as observe_kernel
-                const float dg = 57.29577951308232f;
-                const float hip = qb[6 + 3 * f] * dg, th = qb[7 + 3 * f] * dg, kn = qb[8 + 3 * f] * dg;
-                if (!(hip >= -70.0f && hip <= 70.0f) || !(th >= 25.0f && th <= 115.0f) || !(kn >= -155.0f && kn <= -60.0f))
-                    flags |= NMPC_ROLLOUT_FLAG_JOINT_LIMIT;
-            }
-        }
-    }
-    if (a.failed) {
-        if ((flags & a.term_mask) && !(flags >> NMPC_ROLLOUT_TERM_SHIFT)) flags |= (a.step_index + 1) << NMPC_ROLLOUT_TERM_SHIFT;   // commit_flags' stamp
-        a.failed[b] = flags;
-    }
-}

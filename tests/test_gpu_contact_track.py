@@ -188,6 +188,35 @@ def test_rows_equal_the_calls(world, chain33):
     assert torch.equal(only | start, ref_failed)
 
 
+def test_one_row_equals_the_call(world, chain33):
+    """n_rows = 1 is nmpc_observe_batch of the same state, in S and in failed: one robot skipped, one that comes with a stamp"""
+    L, B = world.L, 33
+    Q, V = chain33[2][:, 1:2].clone(), chain33[3][:, 1:2].clone()
+    Q[:, 0, 6:] = world.dev(fr.STAND)
+    Q[:, 0, 2] = 0.3
+    Q[::4, 0, 2] = 0.05                                                                # every fourth robot lies on the ground
+    Q[2, 0, 6] = 2.0                                                                   # robot 2: a hip beyond its limit
+    goal = torch.zeros(B, 0, dtype=torch.float32, device=L.device)
+    start = torch.zeros(B, dtype=torch.int32, device=L.device)
+    start[4] = (3 << TERM_SHIFT) | COLLISION                                           # stamped by an earlier step: the stamp stays
+    start[7] = KEPT
+    ref_failed = start.clone()
+    ref_S, _ = L.observe(Q[:, 0].contiguous(), V[:, 0].contiguous(), T0, PERIOD, goal, collision_height=HEIGHT, failed=ref_failed, step_index=6,
+                         term_mask=COLLISION)
+    skip = torch.zeros(B, dtype=torch.int32, device=L.device)
+    skip[8] = 1
+    St = torch.full((B, 1, 44), SENTINEL, dtype=torch.float32, device=L.device)
+    failed = start.clone()
+    S = L.observe_rows(Q, V, T0, DT_ROW, PERIOD, collision_height=HEIGHT, S=St, failed=failed, step_index=6, term_mask=COLLISION, skip=skip,
+                       skip_mask=1)
+    kept = torch.arange(B, device=L.device) != 8
+    print(f"largest |S - call| = {float((S[kept, 0] - ref_S[kept]).abs().max())}, failed[:9] = {failed[:9].tolist()}")
+    assert same(S[kept, 0], ref_S[kept]) and torch.equal(failed[kept], ref_failed[kept])
+    assert bool((St[8] == SENTINEL).all()) and int(failed[8]) == 0 and int(ref_failed[8]) != 0
+    f = failed.cpu().numpy()
+    assert (f[0] >> TERM_SHIFT) == 7 and (f[4] >> TERM_SHIFT) == 3 and f[2] & JOINT_LIMIT and (f[2] >> TERM_SHIFT) == 0 and f[7] & KEPT
+
+
 # ---- 4. NaN containment -------------------------------------------------------------------------------------------------------------
 def test_massless_leaf_gives_nan_rows_where_the_chain_has_them_and_the_next_call_is_sound(world, chain33):
     r = slice(0, 33)

@@ -197,9 +197,14 @@ def torque_digests():
     """One digest per entry point of include/nmpc_torque.h (`nmpc_plan_actions_batch` is under roll_wb_steps_labels) on the states
     of the layer's own GPU tests, B = 257 (eight blocks and one lane), 33 and 40 (a full and a ragged block at either width);
     `_w16`: the 16-robot instantiations, on the 30-joint tree; the plant calls also pushed, under windows per robot and under the
-    implicit integrator (`plant`).  Prints what is not finite: NaN bytes compare equal and say less."""
+    implicit integrator (`plant`).  The un-pushed step and track once more at B = 17 (`_b17_w16`), the step written over its own
+    inputs (`contact_step_in_place`), every output combination of the two observation calls, and the two inverse-dynamics calls
+    on the tilted tree.  Prints what is not finite: NaN bytes compare equal and say less."""
+    import ctypes
     import numpy as np
     import torch
+    from iterative_learning_nmpc_amd._lib import check, ptr, stream
+    dev = lambda x: torch.as_tensor(np.array(x, np.float32), device="cuda:0").contiguous()      # noqa: E731
     from tests import fd_reference as fr
     from tests.test_gpu_contact import DT, KD, KP, SOFT, Case, ground, layer
     from tests.test_gpu_policy_rollout import HEIGHT, PERIOD, T0, World
@@ -278,6 +283,52 @@ def torque_digests():
     add("contact_step_w16", *L.contact_step(q, v, DT, 20, tau_ff=tau, q_des=q, kp=KP, kd=KD, ground=GroundContact(**SOFT)))
     plant(w.L, w.c.q, w.c.v, w.c.tau, ground(w.c.g), 33, "", ("explicit", "implicit"), True)
     plant(L, q, v, tau, GroundContact(**SOFT), 40, "_w16", ("explicit",), False)      # rows need the 18-joint tree
+    # the un-pushed step and track at 16 robots per block on a full block and one lane, and the step over its own inputs
+    q17, v17, tau17 = (dev(x[:17]) for x in (q, v, tau))
+    soft = GroundContact(**SOFT)
+    add("contact_step_b17_w16", *L.contact_step(q17, v17, DT, 3, tau_ff=tau17, q_des=q17, kp=KP, kd=KD, ground=soft))
+    add("contact_track_b17_w16", *L.contact_track(q17.clone(), v17.clone(), torch.stack([q17, 0.9 * q17], 1), DT, 3, tau_ff=tau17, kp=KP, kd=KD,
+                                                  ground=soft, record=False)[:2])
+    for Lx, qa, va, tx, gx, name in ((L, q17.clone(), v17.clone(), tau17, soft, "_w16"),
+                                     (w.L, dev(w.c.q[:33]), dev(w.c.v[:33]), dev(w.c.tau[:33]), ground(w.c.g), "")):
+        B = qa.shape[0]
+        outs = [torch.empty_like(qa), torch.empty(B, Lx.n_feet, 3, device=Lx.device), torch.empty(B, Lx.nu, device=Lx.device)]
+        des, cfg = qa[:, Lx.n - Lx.nu:].contiguous(), gx.cfg()
+        check(Lx.lib.nmpc_contact_step_batch(Lx._h, B, 5, DT, ctypes.byref(cfg), ptr(qa), ptr(va), ptr(tx), ptr(des), KP, KD, ptr(qa), ptr(va),
+                                             *(ptr(o) for o in outs), stream(Lx.device)), Lx._h, "nmpc_contact_step_batch", "torque")
+        add("contact_step_in_place" + name, qa, va, *outs)
+    # the observation: a row only, a policy input only, both with statistics from column 3 on, flags only; the rows of a table
+    # with and without S, robots skipped
+    B, wl_ = 33, w.L
+    qo, vo, goal = dev(w.c.q[:B]), dev(w.c.v[:B]), dev(w.goal[:B])
+    mean, std = (torch.as_tensor(x, dtype=torch.float64, device=wl_.device) for x in (w.s_mean, w.s_std))
+    for name, S, X, stats, s_first in (("S", True, False, False, 0), ("X", False, True, False, 0), ("SX", True, True, True, 3),
+                                       ("flags", False, False, False, 0)):
+        S = torch.zeros(B, 44, device=wl_.device) if S else None
+        X = torch.zeros(B, 44 + goal.shape[1], device=wl_.device) if X else None
+        failed = torch.zeros(B, dtype=torch.int32, device=wl_.device)
+        check(wl_.lib.nmpc_observe_batch(wl_._h, B, ptr(qo), ptr(vo), T0, PERIOD, ptr(goal), goal.shape[1], ptr(mean if stats else None),
+                                         ptr(std if stats else None), s_first, HEIGHT, ptr(S), 44, ptr(X), ptr(failed), 2, 0xFF,
+                                         stream(wl_.device)), wl_._h, "nmpc_observe_batch", "torque")
+        add("observe_" + name, *(t for t in (S, X, failed) if t is not None))
+    Qr, Vr = torch.stack([qo, 0.9 * qo, 1.1 * qo], 1), torch.stack([vo, -vo, 0.5 * vo], 1)
+    skip = torch.zeros(B, dtype=torch.int32, device=wl_.device); skip[::5] = 4
+    for name, S in (("S", torch.zeros(B, 3, 44, device=wl_.device)), ("flags", None)):
+        failed = torch.zeros(B, dtype=torch.int32, device=wl_.device)
+        check(wl_.lib.nmpc_observe_rows_batch(wl_._h, B, 3, ptr(Qr), ptr(Vr), 3, T0, 1e-3, PERIOD, HEIGHT, ptr(S), 3, ptr(failed), 2, 0xFF, ptr(skip), 4,
+                                              stream(wl_.device)), wl_._h, "nmpc_observe_rows_batch", "torque")
+        add("observe_rows_" + name, *(t for t in (S, failed) if t is not None))
+    # inverse dynamics on the tilted tree with and without forces; the labels of random plans, permuted and with rollouts skipped
+    from tests.test_gpu_plan_labels import plans
+    tl = tilted_layer()
+    qi, vi, ti, fi = fr.inputs(w.c.m, 257, 9)
+    add("id_torques_tilted", w.L.id_torques(qi, vi, 0.5 * vi, fi), w.L.id_torques(qi, vi, 0.5 * vi))
+    Xp, Up = plans(65, "random", tl.device)
+    zoh = np.sort(np.random.default_rng(3).integers(0, 30, 40)).astype(np.int32)
+    skip = torch.zeros(65, dtype=torch.int32, device=tl.device); skip[::7] = 2
+    add("plan_actions", tl.plan_actions(Xp, Up, zoh, 1.0 / 30, 1e-3, KP, KD),
+        tl.plan_actions(Xp, Up, zoh, 1.0 / 30, 1e-3, KP, KD, actuator_to_joint=[3, 4, 5, 0, 1, 2, 9, 10, 11, 6, 7, 8]),
+        tl.plan_actions(Xp, Up, zoh, 1.0 / 30, 1e-3, KP, KD, skip=skip, skip_mask=2, out=torch.zeros(65, 40, 12, device=tl.device)))
     centroidal(w.c.L, w.c.q, w.c.v)                       # B = 257 on the tilted quadruped, B = 40 on the 30-joint tree
     centroidal(L, q, v)
     return {k: sha(*v) for k, v in parts.items()}
