@@ -108,6 +108,16 @@ def test_plan_actions_match_oracle_labels_and_the_kernel_chain(dev, B, perturb):
         Ap = L.plan_actions(X, U, zoh, dt, sim_dt, KP, KD, actuator_to_joint=perm).cpu().numpy().astype(np.float64)
         want = (tau[..., perm] + KD * v[..., 6:]) / KP + q[..., 6:]
         assert (KP * np.abs(Ap - want) <= bar(tau, q, v)).all()
+        # that list is its own inverse: a scatter through it is the same array.  A rotation is not, and its inverse lies far off
+        turn = [(i + 5) % 12 for i in range(12)]
+        back = [(i + 7) % 12 for i in range(12)]
+        assert all(back[turn[i]] == i for i in range(12)) and sum(turn[turn[i]] != i for i in range(12)) >= 8
+        At = L.plan_actions(X, U, zoh, dt, sim_dt, KP, KD, actuator_to_joint=turn).cpu().numpy().astype(np.float64)
+        want = (tau[..., turn] + KD * v[..., 6:]) / KP + q[..., 6:]
+        apart = float(np.median(np.abs(tau[..., back] - tau[..., turn]) / bar(tau, q, v)))
+        print(f"   rotated actuators: worst ratio {float((KP * np.abs(At - want) / bar(tau, q, v)).max()):.3f}; the inverse a median of {apart:.1e} bars apart")
+        assert apart > 1e3
+        assert (KP * np.abs(At - want) <= bar(tau, q, v)).all()
 
 
 def _controller(B, dev):
