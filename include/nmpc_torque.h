@@ -193,6 +193,28 @@ int nmpc_contact_set_push(void *torque, const nmpc_push_cfg *push);
  * plant call, before any launch: windows attached and no push attached, B > rows.  NULL, NULL detaches (the push stays). */
 int nmpc_contact_set_push_windows(void *torque, const int *first_substep, const int *n_substeps, int rows);
 
+/* A ground and a torque limit per robot [decl] (the declared law has no reference to identify its parameters from: a sweep over
+ * them, and a learner that must not fit one declared floor, want them per robot).  rows: dev [n_rows][6], caller-owned, kept as a
+ * pointer and read in stream order at each launch; row b is robot b's law in the field order of nmpc_contact_cfg -- ground_z,
+ * stiffness, damping, mu, slip_velocity, tau_max (tau_max <= 0: no limit).  While a table is attached
+ *   nmpc_contact_forces_batch, nmpc_contact_step_batch, nmpc_contact_track_batch, nmpc_policy_rollout_batch (through its step
+ *   launches) and nmpc_wb_rollout_* with a plant (through its track launches)
+ * read robot b's parameters from row b and ignore the values of their cfg / ground argument, which is still validated: a call
+ * keeps its error behaviour.  The squared slip velocity is formed on the device as the fp32 product slip_velocity *
+ * slip_velocity, the product the host forms for a cfg, so robot b of such a call is bit for bit robot b of the same call (same B,
+ * same row, same push) made without a table under cfg = row b.
+ * The device does NOT validate the values of a row: a caller who bypasses the Python layer owns them (what nmpc_contact_cfg is refused
+ * for -- a field that is not finite, stiffness, damping or mu < 0, slip_velocity <= 0 -- gives NaN or a ground that pulls).
+ * Launches: each plant call is ONE launch under either integrator, of one more instantiation of the chain kernel per integrator,
+ * in which every lane keeps its law in a slot of its own behind the block's LDS slice (24 bytes per robot); an attached push --
+ * none, one window, or windows per robot -- is tested per substep inside it, and under the explicit integrator every robot then
+ * takes either the un-pushed substep or the pushed one, as under nmpc_contact_set_push_windows.  nmpc_contact_forces_batch
+ * launches a rows-reading variant of its kernel.  With no table attached every call makes exactly the launches it makes without
+ * this entry point.  nmpc_fd_step_batch and nmpc_fd_accel_batch take given forces and are not affected.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), what was attached staying: rows given and n_rows < 1.  At a call of the above,
+ * before any launch: B > n_rows.  rows = NULL detaches. */
+int nmpc_contact_set_grounds(void *torque, const float *rows, int n_rows);
+
 /* The integrator of the contact plant [decl].  NMPC_INTEGRATOR_EXPLICIT (the default) is the step stated above, launch for launch.
  * NMPC_INTEGRATOR_LINEARLY_IMPLICIT takes the stiff terms -- ground stiffness and damping, the friction regulariser, the PD law --
  * at the end of the substep, linearised at its start.  One substep from (q, v):

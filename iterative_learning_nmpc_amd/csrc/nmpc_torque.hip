@@ -17,8 +17,8 @@
 // what the tree's inertia is -- the mass matrix, the centre of mass and the centroidal momentum map of one composite-rigid-body
 // pass -- is nmpc_torque_crba.hip.inc; the correction of the plant's second integrator, which takes the stiff contact and PD terms
 // implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; the chain of control steps on the plant -- one
-// kernel text, instantiated for a table of PD targets tracked in one launch, for pushed substeps, for a push window per robot
-// and for the implicit integrator -- is nmpc_torque_track.hip.inc; the centroidal momentum about an anchor
+// kernel text, instantiated for a table of PD targets tracked in one launch, for pushed substeps, for a push window per robot,
+// for the implicit integrator and for either integrator under a ground per robot -- is nmpc_torque_track.hip.inc; the centroidal momentum about an anchor
 // point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
 // momentum A_g(q) v of a plant state alone, which the device rollouts put into x0.
@@ -380,6 +380,7 @@ struct Torque {
     int device = 0;
     int fd_width = 32;                  // robots per block of fd_kernel: fd_block_width(n), or 16 if NMPC_FD_WIDTH=16 asks for it (tools/fd_cost.py)
     int ct_width = 32;                  // robots per block of contact_step_kernel: ct_block_width(n)
+    int gr_width = 32;                  // and of the explicit chain under a table of grounds: ct_grounds_block_width(n)
     int anchor = -1;                    // the centroidal kernels' reference frame: the first joint whose body has mass (-1: the tree has none)
     unsigned chain = 0;                 // bit i: joint i is the anchor or one of its ancestors
     float* act = nullptr;               // [act_rows][nu]: the actions of nmpc_policy_rollout_batch when its caller keeps none
@@ -390,6 +391,10 @@ struct Torque {
     } states;
     nmpc_push_cfg push{};               // nmpc_contact_set_push: the push of the plant calls (force == nullptr: none)
     nmpc_torque::PushWindows windows{}; // nmpc_contact_set_push_windows: a window per robot in place of the push's own (first == nullptr: none)
+    struct {                            // nmpc_contact_set_grounds: a law per robot in place of the plant calls' cfg (rows == nullptr: none)
+        const float* rows = nullptr;
+        int n_rows = 0;
+    } grounds;
     int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
@@ -413,11 +418,12 @@ auto chain_kernel(int w) {
     else return w == 32 ? contact_chain_kernel<32, Args> : contact_chain_kernel<16, Args>;
 }
 
-// one launch of the chain: at the handle's width of the contact step, or the implicit chain's own with its triangle behind the slice
+// one launch of the chain: at the handle's width of the contact step, or the implicit chain's own with its triangle behind the slice;
+// under a table of grounds at the width its larger footprint allows, a law per lane behind either
 template <class Args>
 int launch_chain(Torque* t, const Args& p, void* stream) {
-    const int w = Args::implicit ? IM_W : t->ct_width, n = t->host.n;
-    return launch_step(t, chain_kernel<Args>(w), w, Args::implicit ? im_lds_bytes(n) : ct_lds_bytes(n, w), p, stream);
+    const int w = Args::implicit ? IM_W : (Args::grounds ? t->gr_width : t->ct_width), n = t->host.n, laws = Args::grounds ? w : 1;
+    return launch_step(t, chain_kernel<Args>(w), w, Args::implicit ? im_lds_bytes(n, laws) : ct_lds_bytes(n, w, laws), p, stream);
 }
 
 // one of the element-wise kernels: a thread per entry of a [B][nu] table
@@ -453,16 +459,19 @@ int allocate(Torque* t) {
     // the contact plant: the kinematics slice of the largest tree, and for the step, the tracked chain of steps and the pushed substeps
     // of either the most an instantiation can be asked for by the step's width rule (ct_block_width: ct_wide_joints() joints x 32
     // robots, the largest tree x 16)
-    LDS_LIMIT(foot_kernel, fk_lds_bytes(MAXJ));
+    LDS_LIMIT(foot_kernel<FootArgs>, fk_lds_bytes(MAXJ));
+    LDS_LIMIT(foot_kernel<FootRowsArgs>, fk_lds_bytes(MAXJ));
     const size_t ct_lds = t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16);
     LDS_LIMIT(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width), ct_lds);
     LDS_LIMIT(chain_kernel<TrackArgs>(t->ct_width), ct_lds);
     LDS_LIMIT(chain_kernel<PushArgs>(t->ct_width), ct_lds);
     LDS_LIMIT(chain_kernel<WindowArgs>(t->ct_width), ct_lds);
+    LDS_LIMIT(chain_kernel<GroundsArgs>(t->gr_width), t->gr_width == 32 ? ct_lds_bytes(ct_grounds_wide_joints(), 32, 32) : ct_lds_bytes(MAXJ, 16, 16));
     // the composite-inertia pass, the implicit chain (slice and triangle) and the three entry points of the centroidal kernel:
     // the slice of the largest tree at the one width each has
     LDS_LIMIT(crba_kernel, crba_lds_bytes(MAXJ, CR_W));
     LDS_LIMIT(chain_kernel<ImplicitArgs>(IM_W), im_lds_bytes(MAXJ));
+    LDS_LIMIT(chain_kernel<ImplicitGroundsArgs>(IM_W), im_lds_bytes(MAXJ, IM_W));
     LDS_LIMIT(centroidal_kernel<CmdIo>, centroidal_lds_bytes<CmdIo>(MAXJ));
     LDS_LIMIT(centroidal_kernel<NodeRecordIo>, centroidal_lds_bytes<NodeRecordIo>(MAXJ));
     LDS_LIMIT(centroidal_kernel<StateMomentumIo>, centroidal_lds_bytes<StateMomentumIo>(MAXJ));
@@ -530,9 +539,15 @@ const char* observe_refusal(const Torque* t, int B, const float* q, const float*
     return nullptr;
 }
 
-// the kinematics pass, with or without the law
+// the kinematics pass, with or without the law; with the law of the attached table of grounds if there is one
 int launch_feet(Torque* t, const FootArgs& a, void* stream) {
-    hipLaunchKernelGGL(foot_kernel, dim3((unsigned)((a.B + TPB - 1) / TPB)), dim3(TPB), fk_lds_bytes(t->host.n),
+    if (a.f && t->grounds.rows) {
+        FootRowsArgs r{};
+        static_cast<FootArgs&>(r) = a;
+        r.rows = t->grounds.rows;
+        return launch_step(t, foot_kernel<FootRowsArgs>, TPB, fk_lds_bytes(t->host.n), r, stream);
+    }
+    hipLaunchKernelGGL(foot_kernel<FootArgs>, dim3((unsigned)((a.B + TPB - 1) / TPB)), dim3(TPB), fk_lds_bytes(t->host.n),
                        static_cast<hipStream_t>(stream), t->dev, a);
     return launched(t);
 }
@@ -567,6 +582,11 @@ const char* push_batch_refusal(const nmpc_push_cfg& push, const nmpc_torque::Pus
     return nullptr;
 }
 
+// why the attached table of grounds cannot serve a plant call of B robots (nullptr: it can, or there is none)
+const char* grounds_batch_refusal(const Torque* t, int B) {
+    return t->grounds.rows && B > t->grounds.n_rows ? "grounds: B exceeds n_rows" : nullptr;
+}
+
 // A plant call under a push is cut into runs of substeps that are all un-pushed -- launches of the un-pushed kernels, as a call
 // without a push makes them -- and runs that are all pushed, launches of the PushArgs chain (nmpc_torque_track.hip.inc says why).
 
@@ -587,10 +607,14 @@ PushArgs chain_args(int B, int n_steps, int n_sub, float dt, const nmpc_contact_
 }
 
 // a plant call under the implicit integrator: one launch of the ImplicitArgs chain, the push window -- the push's own, or with
-// `wins` the robot's, in a call whose substep 0 is substep s0 of their count -- tested inside it
+// `wins` the robot's, in a call whose substep 0 is substep s0 of their count -- tested inside it.  And a plant call of either
+// integrator under a table of grounds (Args: ImplicitGroundsArgs, GroundsArgs), which states its push the same way.
+template <class Args = ImplicitArgs>
 int launch_implicit(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins,
                     long long s0, void* stream) {
-    ImplicitArgs p{call};
+    Args p{};
+    static_cast<PushArgs&>(p) = call;
+    if constexpr (Args::grounds) p.rows = t->grounds.rows;
     if (win.hi > win.lo) { p.force = push.force; p.joint = push.joint; p.push_lo = win.lo; p.push_hi = win.hi; }
     if (wins.first) { p.force = push.force; p.joint = push.joint; p.win_first = wins.first; p.win_count = wins.count; p.win_s0 = s0; }
     return launch_chain(t, p, stream);
@@ -615,11 +639,16 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
     if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = push_batch_refusal(push, wins, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     const Window win = wins.first ? Window{} : push_window(push, s0, n_sub);
     PushArgs call = chain_args(B, 1, n_sub, dt, *cfg, tau_ff, q_des, 1, kp, kd, q_out, v_out);
     call.q_in = q; call.v_in = v; call.a_out = a_out; call.f_out = f_out; call.tau_out = tau_out;
-    if (t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT) return launch_implicit(t, call, push, win, wins, s0, stream);
+    const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
+    if (t->grounds.rows)                         // a law per robot: one launch whatever the push
+        return implicit ? launch_implicit<ImplicitGroundsArgs>(t, call, push, win, wins, s0, stream)
+                        : launch_implicit<GroundsArgs>(t, call, push, win, wins, s0, stream);
+    if (implicit) return launch_implicit(t, call, push, win, wins, s0, stream);
     if (wins.first) return launch_windowed(t, call, push, wins, s0, stream);
     const int cuts[4] = {0, (int)win.lo, (int)win.hi, n_sub};
     bool first = true;
@@ -664,6 +693,7 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
     if (Q && !whole_body_tree(t->host))
         return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
     if (const char* why = push_batch_refusal(push, wins, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     const int n = t->host.n, nu = t->host.nu;
     const long long total = (long long)n_steps * n_sub;
@@ -671,8 +701,11 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
     PushArgs call = chain_args(B, n_steps, n_sub, dt, *cfg, tau_ff, A, a_rows, kp, kd, q, v);
     call.qv_rows = qv_rows; call.skip_mask = skip ? skip_mask : 0; call.skip = call.skip_mask ? skip : nullptr;
     const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
-    if (implicit || wins.first) {                // one launch for the whole table; the cut path below moves A, Q, V piece by piece
+    if (implicit || wins.first || t->grounds.rows) {      // one launch for the whole table; the cut path below moves A, Q, V piece by piece
         call.Q = Q; call.V = V;
+        if (t->grounds.rows)
+            return implicit ? launch_implicit<ImplicitGroundsArgs>(t, call, push, win, wins, s0, stream)
+                            : launch_implicit<GroundsArgs>(t, call, push, win, wins, s0, stream);
         return implicit ? launch_implicit(t, call, push, win, wins, s0, stream) : launch_windowed(t, call, push, wins, s0, stream);
     }
     for (long long s = 0; s < total;) {
@@ -804,6 +837,7 @@ int nmpc_torque_create(const nmpc_tree_model* mdl, int device_id, void** handle)
     t->host = m; t->device = device_id;
     t->fd_width = fd_block_width(m.n);
     t->ct_width = ct_block_width(m.n);
+    t->gr_width = ct_grounds_block_width(m.n);
     for (int i = m.n - 1; i >= 0; --i)
         if (m.mass[i] > 0.0f) t->anchor = i;
     for (int k = t->anchor; k >= 0; k = m.parent[k]) t->chain |= 1u << k;
@@ -934,6 +968,7 @@ int nmpc_contact_forces_batch(void* handle, int B, const nmpc_contact_cfg* cfg, 
     if (B == 0) return NMPC_OK;
     if (B < 0 || !q || !f) return fail(t, NMPC_E_ARG, "need B >= 0 and q, f");
     if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     FootArgs a{};
     a.B = B; a.q = q; a.v = v; a.f = f; a.c = device_cfg(*cfg);
@@ -965,6 +1000,15 @@ int nmpc_contact_set_push_windows(void* torque, const int* first_substep, const 
         return fail(t, NMPC_E_ARG, "push windows: first_substep and n_substeps come together or not at all");
     if (rows < 1) return fail(t, NMPC_E_ARG, "push windows: rows must be at least 1");
     t->windows = {first_substep, n_substeps, rows};
+    return NMPC_OK;
+}
+
+int nmpc_contact_set_grounds(void* torque, const float* rows, int n_rows) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (rows && n_rows < 1) return fail(t, NMPC_E_ARG, "grounds: n_rows must be at least 1");      // what was attached stays
+    t->grounds = {};
+    if (rows) { t->grounds.rows = rows; t->grounds.n_rows = n_rows; }
     return NMPC_OK;
 }
 
@@ -1060,6 +1104,7 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     if (!rec.Q != !rec.V) return fail(t, NMPC_E_ARG, "states: Q and V come together or not at all");
     if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
     if (const char* why = push_batch_refusal(t->push, t->windows, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
         NMPC_ENTER(t, t->device);

@@ -23,6 +23,14 @@ __device__ __forceinline__ V3 contact_law(const ContactCfg& c, V3 p, V3 pd) {
     return {s * pd.x, s * pd.y, fz};
 }
 
+// A ground per robot (nmpc_contact_set_grounds, DESIGN.md 8d): row b of the attached table [n_rows][6] in the field order of
+// nmpc_contact_cfg, as the kernels read a law.  slip2 is the fp32 product device_cfg forms on the host, so a row equal to a
+// uniform struct is that struct's ContactCfg bit for bit.  Nothing of a row is validated here (include/nmpc_torque.h).
+__device__ __forceinline__ ContactCfg ground_row(const float* __restrict__ rows, int b) {
+    const float* r = rows + (size_t)b * 6;
+    return {r[0], r[1], r[2], r[3], r[4] * r[4], r[5]};
+}
+
 // ---- foot kinematics, and the law on them ---------------------------------------------------------------------------------
 constexpr int FK_RW = 0;     // Rw 9
 constexpr int FK_PW = 9;     // world position of the body origin 3
@@ -31,16 +39,25 @@ constexpr int FK_SLOTS = 18;
 constexpr size_t fk_lds_bytes(int n) { return (size_t)n * FK_SLOTS * TPB * sizeof(float); }
 
 struct FootArgs {
+    static constexpr bool grounds = false;
     int B;
     const float *q, *v;                                   // v nullptr: at rest
     float *pos, *vel, *f;                                 // each may be nullptr; f: the law of c on (pos, vel)
     ContactCfg c;
 };
 
+struct FootRowsArgs : FootArgs {                          // the law of robot b's row on (pos, vel); c is not read
+    static constexpr bool grounds = true;
+    const float* rows;
+};
+
 // One outward pass: Rw, the world position of the body origin and the body-coordinate velocity (w, vo); the foot point of a
 // body is then p = p_w + Rw r, pd = Rw (vo + w x r).  One thread per robot, LDS slice [joint][FK_SLOTS][TPB].
 // The pass keeps its text here and in observe_kernel: as one function template called from both, this kernel rounded differently.
-__global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp, const FootArgs a) {
+// Two instantiations, switched at compile time by Args::grounds: foot_kernel<FootArgs> compiles to the instructions foot_kernel
+// had before it was a template (DESIGN.md 8d) -- as a function template called from two kernels of its own it did not.
+template <class Args>
+__global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp, const Args a) {
     const Model& m = *mp;
     const int b = blockIdx.x * TPB + threadIdx.x;
     if (b >= a.B) return;
@@ -71,6 +88,9 @@ __global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp,
         for (int k = 0; k < 9; ++k) at(i, FK_RW + k) = Rw.m[k];
         at.put3(i, FK_PW, pw); at.put3(i, FK_V, w); at.put3(i, FK_V + 3, vo);
     }
+    [[maybe_unused]] ContactCfg own;                      // Args::grounds: this robot's row
+    if constexpr (Args::grounds)
+        if (a.f) own = ground_row(a.rows, b);
     for (int k = 0; k < m.nf; ++k) {
         const int j = m.foot_joint[k];
         M3 Rw;
@@ -82,7 +102,9 @@ __global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp,
         if (a.pos) { a.pos[e] = p.x; a.pos[e + 1] = p.y; a.pos[e + 2] = p.z; }
         if (a.vel) { a.vel[e] = pd.x; a.vel[e + 1] = pd.y; a.vel[e + 2] = pd.z; }
         if (a.f) {
-            const V3 f = contact_law(a.c, p, pd);
+            V3 f;
+            if constexpr (Args::grounds) f = contact_law(own, p, pd);
+            else f = contact_law(a.c, p, pd);
             a.f[e] = f.x; a.f[e + 1] = f.y; a.f[e + 2] = f.z;
         }
     }
@@ -92,19 +114,29 @@ __global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp,
 constexpr int CT_SLOTS = FD_SLOTS + 3;                    // the slice of fd_accel_body and FD_PW, the world position of the body origin
 // the slice, and behind it the parameters of the law: six uniform values that would otherwise live in scalar registers across
 // the whole recursion, which fills the scalar file on its own (they cost 13 SGPR spills there)
-constexpr size_t ct_lds_bytes(int n, int width) { return (size_t)n * CT_SLOTS * width * sizeof(float) + sizeof(ContactCfg); }
+// (`laws`: how many; under a table of grounds every lane has its own, a slot of six words per lane -- 32 lanes at a stride of 6
+// words fall on 32 different banks)
+constexpr size_t ct_lds_bytes(int n, int width, int laws = 1) { return (size_t)n * CT_SLOTS * width * sizeof(float) + laws * sizeof(ContactCfg); }
 // robots per block: 32 where the slice of n joints fits the CU (n <= 23), 16 otherwise (32 joints: 110 616 B)
 constexpr int ct_block_width(int n) { return ct_lds_bytes(n, 32) <= FD_LDS_MAX ? 32 : 16; }
+// and under a table of grounds, by the same rule on the larger footprint (23 joints x 32 robots: 159 744 B, still inside)
+constexpr int ct_grounds_block_width(int n) { return ct_lds_bytes(n, 32, 32) <= FD_LDS_MAX ? 32 : 16; }
+static_assert(ct_lds_bytes(MAXJ, 16, 16) <= FD_LDS_MAX, "the slice of the largest tree and a law per lane no longer fit a CU at 16 robots per block");
 // the largest tree that runs at 32 robots per block: its slice is the most contact_step_kernel<32> can be asked for
 constexpr int ct_wide_joints() {
     int n = MAXJ;
     while (n > 1 && ct_block_width(n) != 32) --n;
     return n;
 }
+constexpr int ct_grounds_wide_joints() {
+    int n = MAXJ;
+    while (n > 1 && ct_grounds_block_width(n) != 32) --n;
+    return n;
+}
 
 // the law as the force source of fd_accel_body; `out` (this robot's row of f_out, or nullptr) takes the forces as they are used
 struct GroundForces {
-    const ContactCfg* c;                                  // in LDS, behind the block's slice
+    const ContactCfg* c;                                  // in LDS, behind the block's slice: the block's, or under a table the lane's
     float* out;
     static constexpr bool kinematic = true;
     __device__ __forceinline__ bool any() const { return true; }

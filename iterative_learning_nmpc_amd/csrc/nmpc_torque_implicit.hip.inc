@@ -20,8 +20,9 @@ constexpr int IM_W = 16;                                  // robots per block: t
 constexpr int IM_J = FD_P;                                // column i of the foot Jacobian in world axes 3 (p^A is spent after the recursion)
 constexpr int IM_R = FD_P + 3;                            // rhs_i, then the solution a_i
 constexpr size_t im_triangle(int n) { return (size_t)n * (n + 1) / 2; }
-constexpr size_t im_lds_bytes(int n) { return ((size_t)n * CT_SLOTS + im_triangle(n)) * IM_W * sizeof(float) + sizeof(ContactCfg); }
-static_assert(im_lds_bytes(MAXJ) <= FD_LDS_MAX, "the implicit slice of the largest tree no longer fits a CU at 16 robots per block");
+// the slice, the triangle, and behind it the law: one for the block, or IM_W of them under a table of grounds (a law per lane)
+constexpr size_t im_lds_bytes(int n, int laws = 1) { return ((size_t)n * CT_SLOTS + im_triangle(n)) * IM_W * sizeof(float) + laws * sizeof(ContactCfg); }
+static_assert(im_lds_bytes(MAXJ, IM_W) <= FD_LDS_MAX, "the implicit slice of the largest tree no longer fits a CU at 16 robots per block");
 
 // the law and a push that acts only in the substeps of its window
 struct WindowedPushForces : PushedGroundForces {

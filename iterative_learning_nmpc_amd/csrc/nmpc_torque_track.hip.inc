@@ -1,6 +1,6 @@
 // nmpc_torque_track.hip.inc -- the chain of control steps on the ground-contact plant: a table of PD targets tracked in one launch,
-// pushed, under a window per robot or under the implicit integrator (nmpc_contact_track_batch of include/nmpc_torque.h, and every
-// launch of nmpc_contact_step_batch but the un-pushed explicit one); included by nmpc_torque.hip inside namespace nmpc_torque,
+// pushed, under a window per robot, under the implicit integrator or under a ground per robot (nmpc_contact_track_batch of
+// include/nmpc_torque.h, and every launch of nmpc_contact_step_batch but the un-pushed explicit one); included by nmpc_torque.hip inside namespace nmpc_torque,
 // after nmpc_torque_implicit.hip.inc.
 //
 // The whole-body expert on the declared plant (DESIGN.md 8h): the label row of a plan, A = (tau_id + kd v_plan) / kp + q_plan,
@@ -23,7 +23,7 @@ enum class Forces {
 
 // The un-pushed track: the state in q, v goes through n_steps control steps, in place.
 struct TrackArgs {
-    static constexpr bool step_io = false, implicit = false;
+    static constexpr bool step_io = false, implicit = false, grounds = false;
     static constexpr Forces forces = Forces::ground;
     int B, n_steps, n_sub, a_rows, qv_rows, skip_mask;
     float dt, kp, kd;
@@ -78,6 +78,22 @@ struct ImplicitArgs : PushArgs {                          // force == nullptr: n
     long long win_s0;                                     // robot b's window [win_first[b], + win_count[b]) less win_s0 instead
 };
 
+// A ground per robot, nmpc_contact_set_grounds (DESIGN.md 8d): c is not read; every lane has a ContactCfg of its own behind the
+// block's slice (under the implicit integrator behind the triangle), filled from row b of the table, and the law and the clamp
+// read it through the pointer they read the block's one law through.  One instantiation per integrator, one launch per call.
+// The explicit one has no cut into launches to lean on either (the table is attached whether or not a push is), so it takes a
+// push as the implicit chain states it -- none, one window for the batch, or the robot's own -- and in every substep one of the
+// two inlined recursions of WindowArgs, for the reason stated there: robot b is then the bits of the uniform launches under its
+// own row (tests/test_gpu_grounds.py).
+struct ImplicitGroundsArgs : ImplicitArgs {
+    static constexpr bool grounds = true;
+    const float* rows;                                    // [>= B][6] in the field order of nmpc_contact_cfg
+};
+struct GroundsArgs : ImplicitGroundsArgs {
+    static constexpr bool implicit = false;
+    static constexpr Forces forces = Forces::either;
+};
+
 // ---- the chain ------------------------------------------------------------------------------------------------------------------
 // contact_step_kernel's substep, n_steps * n_sub times on the state in the slice: per control step the state goes out to row k
 // of Q, V (if given), the PD target becomes row k of the robot's table, and n_sub substeps follow.  A control step whose
@@ -96,11 +112,16 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
     [[maybe_unused]] const int nf3 = 3 * m.nf;
     float* const behind = body + n * CT_SLOTS * W;
     ContactCfg* cfg = reinterpret_cast<ContactCfg*>(Args::implicit ? behind + (n * (n + 1) / 2) * W : behind);
-    if (threadIdx.x == 0) *cfg = p.c;
-    __syncthreads();
+    if constexpr (Args::grounds) {
+        cfg += threadIdx.x;                               // the lane's own slot, which nobody else reads: no barrier
+    } else {
+        if (threadIdx.x == 0) *cfg = p.c;
+        __syncthreads();
+    }
     const int b = blockIdx.x * W + threadIdx.x;
     if (b >= p.B) return;
     if (p.skip && (p.skip[b] & p.skip_mask)) return;
+    if constexpr (Args::grounds) *cfg = ground_row(p.rows, b);
     const Slice<CT_SLOTS, W> at;
     float* qb = p.q + (size_t)b * n;
     float* vb = p.v + (size_t)b * n;
@@ -115,9 +136,10 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
         fo = p.f_out ? p.f_out + (size_t)b * nf3 : nullptr;
         to = p.tau_out ? p.tau_out + (size_t)b * nu : nullptr;
     }
-    if constexpr (Args::forces == Forces::pushed || Args::forces == Forces::either) F = v3(p.force + (size_t)b * 3);
-    if constexpr (Args::forces == Forces::either) { push_lo = (long long)p.first[b] - p.s0; push_hi = push_lo + p.count[b]; }      // count <= 0: never pushed
-    if constexpr (Args::forces == Forces::windowed) {
+    constexpr bool stated = Args::forces == Forces::windowed || Args::grounds;      // the window as ImplicitArgs states it
+    if constexpr (!stated && (Args::forces == Forces::pushed || Args::forces == Forces::either)) F = v3(p.force + (size_t)b * 3);
+    if constexpr (!stated && Args::forces == Forces::either) { push_lo = (long long)p.first[b] - p.s0; push_hi = push_lo + p.count[b]; }      // count <= 0: never pushed
+    if constexpr (stated) {
         F = p.force ? v3(p.force + (size_t)b * 3) : V3{0, 0, 0};
         push_lo = p.push_lo; push_hi = p.push_hi;
         if (p.win_first) { push_lo = (long long)p.win_first[b] - p.win_s0; push_hi = push_lo + p.win_count[b]; }

@@ -92,7 +92,7 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
 def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, tau_ff=None, kp: float = KP,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
                     terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False,
-                    push: Optional[dict] = None, integrator: Optional[str] = None):
+                    push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -114,7 +114,11 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     it and leave nothing attached.
     integrator: "explicit" or "implicit" sets the layer's integrator first (`BatchedTorqueLayer.set_integrator`; it stays
     set), None leaves it as it is.  With "implicit", dt = 2e-3 and n_sub = 5 run the same 10 ms control step in a quarter of
-    the substeps."""
+    the substeps.
+    grounds: a table of grounds, one row per robot (`BatchedTorqueLayer.set_grounds` takes it and validates it; `sample_grounds`
+    draws one), attached for this call: robot b stands on the ground of row b and has its torque limit, and `ground` is
+    ignored.  None: every robot is on `ground`.  A layer that has a table of the caller's attached already is refused with
+    ValueError, as for a push."""
     if integrator is not None:
         integrator_mode(integrator)                       # an unknown name is refused before anything is attached
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
@@ -122,6 +126,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
         raise ValueError(f"T = {T} s is shorter than one control step of {n_sub} x {dt} s")
     if push is not None and layer._push is not None:
         raise ValueError("push: the layer has a push attached already (set_push)")
+    if grounds is not None and layer._grounds is not None:
+        raise ValueError("grounds: the layer has a table of grounds attached already (set_grounds)")
     states = {}
     if record_states:
         B = torch.as_tensor(q0).reshape(-1, layer.n).shape[0]
@@ -130,6 +136,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     try:
         if integrator is not None:
             layer.set_integrator(integrator)
+        if grounds is not None:
+            layer.set_grounds(grounds)
         if push is not None:
             force = torch.as_tensor(push["force"], dtype=torch.float32, device=layer.device).reshape(-1, 3)
             windows = push_windows(push, force.shape[0])
@@ -146,6 +154,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     finally:
         if push is not None:
             layer.set_push(None)
+        if grounds is not None:
+            layer.set_grounds(None)
         if record_states:
             layer.set_rollout_states(None)
     stamp = failed >> NMPC_ROLLOUT_TERM_SHIFT
@@ -156,7 +166,7 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
 def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, kp: Optional[float] = None,
                      kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
                      n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0,
-                     push: Optional[dict] = None, integrator: Optional[str] = None):
+                     push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None):
     """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
         1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
            [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
@@ -169,7 +179,9 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
         4. `train_network` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows, as
            `learning_iteration` does.
     kp, kd: the gains of the policy's PD law and of the labels alike (None: the controller's Kp, Kd), so that an action and
-    its label mean the same torque.  integrator: the plant's integrator, as `evaluate_policy` takes it.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
+    its label mean the same torque.  integrator: the plant's integrator, as `evaluate_policy` takes it.  grounds: a ground per
+    robot for the learner's rollout, as `evaluate_policy` takes it (attached for that call; the labels are the expert's solves and
+    stand on no plant).  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
     train_loss and val_loss added."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
@@ -178,7 +190,7 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     kp, kd = float(mpc.Kp if kp is None else kp), float(mpc.Kd if kd is None else kd)
     out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
                           terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push,
-                          integrator=integrator)
+                          integrator=integrator, grounds=grounds)
     A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
     S = out["S"]
     B, K = S.shape[:2]

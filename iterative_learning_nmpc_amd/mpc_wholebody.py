@@ -268,6 +268,9 @@ class LocomotionMPC:
         sim_dt / plant_substeps per simulation step, and every replan starts from the state the plant is in.  kp, kd then
         default to the controller's Kp, Kd.  Row j of S is the plant state BEFORE simulation step j and `self.actions` row j
         the PD target applied from it (RolloutMPC.py:168-258); a robot that falls in the last interval is flagged too.
+        A ground per rollout takes no keyword here: attach the table on torque_layer (`BatchedTorqueLayer.set_grounds`) before
+        the call -- rollout b then stands on row b, the values of `plant` are ignored, and `collect_rollouts` and
+        `learning_iteration`, which run this call, see the same table.
         push_as_force (needs plant): the push is a force on the trunk of the plant over the substeps its window covers
         (nmpc_wb_rollout_set_plant_push), where the feet and the torque limit answer it, instead of the velocity jump per
         replanning interval.

@@ -49,6 +49,60 @@ class GroundContact:
                                    float(self.slip_velocity), 0.0 if self.tau_max is None else float(self.tau_max))
 
 
+GROUND_COLUMNS = ("ground_z", "stiffness", "damping", "mu", "slip_velocity", "tau_max")      # a row of a table of grounds: nmpc_contact_cfg's fields
+
+
+def ground_table(grounds) -> np.ndarray:
+    """Host input of `BatchedTorqueLayer.set_grounds` as a validated float32 [B, 6] array in the order of GROUND_COLUMNS: a
+    sequence of `GroundContact` (tau_max None -> 0, no limit) or an array [B, 6].  The rules are those a single ground is
+    refused by (contact_cfg_refusal of the library): every value finite, stiffness, damping and mu not negative,
+    slip_velocity positive; a violation, a wrong shape or an empty table is a ValueError naming the first offending row."""
+    if isinstance(grounds, (list, tuple)) and grounds and all(isinstance(g, GroundContact) for g in grounds):
+        grounds = [[g.ground_z, g.stiffness, g.damping, g.mu, g.slip_velocity, 0.0 if g.tau_max is None else g.tau_max] for g in grounds]
+    try:
+        rows = np.ascontiguousarray(np.asarray(grounds, dtype=np.float32))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"grounds: need a sequence of GroundContact or a float array [B, {len(GROUND_COLUMNS)}]") from e
+    if rows.ndim != 2 or rows.shape[1] != len(GROUND_COLUMNS) or rows.shape[0] < 1:
+        raise ValueError(f"grounds: expected [B, {len(GROUND_COLUMNS)}] with B >= 1, got {tuple(rows.shape)}")
+    checks = (("the contact parameters must be finite", ~np.isfinite(rows).all(axis=1)),
+              ("stiffness, damping and mu must not be negative", (rows[:, 1:4] < 0.0).any(axis=1)),
+              ("slip_velocity must be positive", ~(rows[:, 4] > 0.0)))
+    for why, bad in checks:
+        if bad.any():
+            raise ValueError(f"grounds: row {int(np.argmax(bad))}: {why}")
+    return rows
+
+
+def sample_grounds(B: int, rng, base: GroundContact = GroundContact(), mu=None, stiffness=None, damping=None, ground_z=None,
+                   tau_max=None) -> np.ndarray:
+    """A table of grounds for `BatchedTorqueLayer.set_grounds`: float32 [B, 6] in the order of GROUND_COLUMNS.  Each keyword is a
+    range (lo, hi) drawn uniformly per robot from rng (a numpy Generator), or None to keep base's value in that column;
+    slip_velocity is always base's.  Deterministic in rng: the columns are drawn in the order of GROUND_COLUMNS, B values each,
+    and a column that is not drawn takes nothing from rng."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be at least 1")
+    rows = np.repeat(ground_table([base]), B, axis=0)
+    ranges = dict(ground_z=ground_z, stiffness=stiffness, damping=damping, mu=mu, tau_max=tau_max)
+    for col, name in enumerate(GROUND_COLUMNS):
+        r = ranges.get(name)
+        if r is None:
+            continue
+        lo, hi = (float(x) for x in r)
+        if not lo <= hi:
+            raise ValueError(f"{name}: need a range (lo, hi) with lo <= hi, got {r!r}")
+        lo32, hi32 = np.float32(lo), np.float32(hi)      # the float32 values inside [lo, hi] that a rounded draw is held to
+        if lo32 < lo:
+            lo32 = np.nextafter(lo32, np.float32(np.inf))
+        if hi32 > hi:
+            hi32 = np.nextafter(hi32, np.float32(-np.inf))
+        if lo32 > hi32:
+            raise ValueError(f"{name}: the range {r!r} holds no float32 value")
+        rows[:, col] = np.clip(rng.uniform(lo, hi, B).astype(np.float32), lo32, hi32)
+    return ground_table(rows)
+
+
 class BatchedTorqueLayer:
     def __init__(self, parent: Sequence[int], joint_type: Sequence[int], axis, placement_R, placement_p, mass, com, inertia,
                  foot_joint: Sequence[int], foot_offset, n_actuated: int, gravity=(0.0, 0.0, -9.81), device="cuda:0"):
@@ -78,6 +132,7 @@ class BatchedTorqueLayer:
         self._states = None             # set_rollout_states: the attached (Q, V)
         self._push = None               # set_push: the attached force
         self._push_windows = None       # set_push with arrays: the attached (first substeps, counts)
+        self._grounds = None            # set_grounds: the attached table
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -423,6 +478,34 @@ class BatchedTorqueLayer:
         self._push_windows = None if first is None else (first, count)
         _lib.check(self.lib.nmpc_contact_set_push_windows(self._h, ptr(first), ptr(count), 0 if first is None else first.shape[0]),
                    self._h, "nmpc_contact_set_push_windows", "torque")
+
+    def set_grounds(self, grounds=None):
+        """nmpc_contact_set_grounds: a ground and a torque limit of its own per robot.  grounds: a sequence of `GroundContact`, or
+        a float array or tensor [B, 6] in the order of GROUND_COLUMNS (ground_z, stiffness, damping, mu, slip_velocity, tau_max;
+        tau_max <= 0: no limit; `sample_grounds` draws one).  While the table is attached `contact_forces`, `contact_step`,
+        `contact_track`, `policy_rollout` and the expert on the plant (`open_loop_device(..., plant=...)`, and with it
+        `collect_rollouts` and `learning_iteration`, which take no keyword for it: attach the table on the layer they are
+        given) read robot b's law from row b, and their `ground=` / `plant=` argument is ignored (it is still validated).
+        Robot b is then the bits it is in the same call under the uniform ground of its row; every call is one launch under
+        either integrator.  Calls with more robots than the table has rows are refused.
+        Host input is validated by the rules a single ground is refused by (`ground_table`: ValueError) and uploaded; a tensor
+        already on the layer's device is taken as given -- the device validates nothing, a NaN or a negative stiffness there is
+        the caller's -- and in either case the layer keeps the table alive while it is attached.  `set_grounds(None)`
+        detaches; detached, every call makes the launches and gives the bits it gives without."""
+        if grounds is None:
+            self._grounds = None
+            _lib.check(self.lib.nmpc_contact_set_grounds(self._h, None, 0), self._h, "nmpc_contact_set_grounds", "torque")
+            return
+        if isinstance(grounds, torch.Tensor) and grounds.is_cuda:
+            if grounds.dtype != torch.float32 or grounds.dim() != 2 or grounds.shape[1] != len(GROUND_COLUMNS) or grounds.shape[0] < 1 \
+                    or grounds.device != self.device:
+                raise ValueError(f"grounds: a device table must be float32 [B, {len(GROUND_COLUMNS)}] with B >= 1 on {self.device}")
+            rows = grounds.contiguous()
+        else:
+            host = ground_table(grounds.numpy() if isinstance(grounds, torch.Tensor) else grounds)
+            rows = torch.tensor(host, device=self.device)      # a copy: the caller's array may be read-only
+        _lib.check(self.lib.nmpc_contact_set_grounds(self._h, ptr(rows), rows.shape[0]), self._h, "nmpc_contact_set_grounds", "torque")
+        self._grounds = rows
 
     def _state_io(self, t, name):
         """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""
