@@ -215,6 +215,33 @@ int nmpc_contact_set_push_windows(void *torque, const int *first_substep, const 
  * before any launch: B > n_rows.  rows = NULL detaches. */
 int nmpc_contact_set_grounds(void *torque, const float *rows, int n_rows);
 
+/* A payload per robot [decl] (the other half of the randomisation a policy is trained and judged under: the robot itself).  One
+ * rigid point mass per robot on one body of the tree.  rows: dev [n_rows][4], caller-owned, kept as a pointer and read in stream
+ * order at each launch; row b is (m_p, r_x, r_y, r_z): robot b carries the mass m_p >= 0 at r in the frame of body `joint`.
+ * While a table is attached the spatial inertia of that body about its origin is A += m_p (|r|^2 1 - r r^T), B += m_p [r]x,
+ * C += m_p 1 (moment = A dw + B dvo) and its velocity-product force gains v x* (I_p v); gravity needs no term, it is the
+ * acceleration of the world.  That is the tree whose body `joint` has mass m + m_p, centre of mass (m c + m_p r) / (m + m_p) and
+ * the parallel-axis inertia about that point.
+ * The calls that READ the table -- robot b carries row b:
+ *   nmpc_contact_step_batch, nmpc_contact_track_batch, nmpc_policy_rollout_batch (through its step launches) and nmpc_wb_rollout_*
+ *   with a plant (nmpc_wb_rollout_set_plant, through its track launches),
+ * under the explicit and the linearly implicit integrator (whose factorised mass matrix is the payload-carrying one), with or
+ * without a push, windows per robot or a table of grounds.
+ * The calls that do NOT read the table -- they describe the nominal model, which is what the expert knows:
+ *   nmpc_id_torques_batch, nmpc_fd_accel_batch, nmpc_fd_step_batch, nmpc_mass_matrix_batch, nmpc_centroidal_batch,
+ *   nmpc_centroidal_derivatives_batch, nmpc_state_momentum_batch, nmpc_plan_actions_batch, nmpc_wb_label_states_batch, and
+ *   nmpc_contact_forces_batch with nmpc_foot_kinematics_batch (kinematics only).
+ * So only the plant carries the load, and the labels of the states it visits are the nominal expert's.
+ * The device does NOT validate the values of a row: a caller who bypasses the Python layer owns them (a negative or non-finite
+ * mass gives NaN or a body that pushes back).
+ * Launches: each plant call is ONE launch under either integrator, of one more instantiation of the chain kernel per integrator,
+ * in which every lane keeps its law and its payload in a slot of its own behind the block's LDS slice (40 bytes per robot); the
+ * law is row b of the table of grounds if one is attached, else the call's cfg; a push is taken as under a table of grounds.
+ * With no table attached every call makes exactly the launches it makes without this entry point.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), what was attached staying: rows given and n_rows < 1, or joint outside
+ * [0, n_joints).  At a call of the first list, before any launch: B > n_rows.  rows = NULL detaches (n_rows, joint are not read). */
+int nmpc_contact_set_payloads(void *torque, const float *rows, int n_rows, int joint);
+
 /* The integrator of the contact plant [decl].  NMPC_INTEGRATOR_EXPLICIT (the default) is the step stated above, launch for launch.
  * NMPC_INTEGRATOR_LINEARLY_IMPLICIT takes the stiff terms -- ground stiffness and damping, the friction regulariser, the PD law --
  * at the end of the substep, linearised at its start.  One substep from (q, v):

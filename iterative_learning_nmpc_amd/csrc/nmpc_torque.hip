@@ -18,7 +18,7 @@
 // pass -- is nmpc_torque_crba.hip.inc; the correction of the plant's second integrator, which takes the stiff contact and PD terms
 // implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; the chain of control steps on the plant -- one
 // kernel text, instantiated for a table of PD targets tracked in one launch, for pushed substeps, for a push window per robot,
-// for the implicit integrator and for either integrator under a ground per robot -- is nmpc_torque_track.hip.inc; the centroidal momentum about an anchor
+// for the implicit integrator and for either integrator under a ground or a payload per robot -- is nmpc_torque_track.hip.inc; the centroidal momentum about an anchor
 // point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
 // momentum A_g(q) v of a plant state alone, which the device rollouts put into x0.
@@ -381,6 +381,7 @@ struct Torque {
     int fd_width = 32;                  // robots per block of fd_kernel: fd_block_width(n), or 16 if NMPC_FD_WIDTH=16 asks for it (tools/fd_cost.py)
     int ct_width = 32;                  // robots per block of contact_step_kernel: ct_block_width(n)
     int gr_width = 32;                  // and of the explicit chain under a table of grounds: ct_grounds_block_width(n)
+    int pl_width = 32;                  // and under a table of payloads: ct_payloads_block_width(n)
     int anchor = -1;                    // the centroidal kernels' reference frame: the first joint whose body has mass (-1: the tree has none)
     unsigned chain = 0;                 // bit i: joint i is the anchor or one of its ancestors
     float* act = nullptr;               // [act_rows][nu]: the actions of nmpc_policy_rollout_batch when its caller keeps none
@@ -395,6 +396,10 @@ struct Torque {
         const float* rows = nullptr;
         int n_rows = 0;
     } grounds;
+    struct {                            // nmpc_contact_set_payloads: a point mass per robot on body `joint` in the plant calls (rows == nullptr: none)
+        const float* rows = nullptr;
+        int n_rows = 0, joint = 0;
+    } payloads;
     int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
@@ -422,7 +427,10 @@ auto chain_kernel(int w) {
 // under a table of grounds at the width its larger footprint allows, a law per lane behind either
 template <class Args>
 int launch_chain(Torque* t, const Args& p, void* stream) {
-    const int w = Args::implicit ? IM_W : (Args::grounds ? t->gr_width : t->ct_width), n = t->host.n, laws = Args::grounds ? w : 1;
+    const int w = Args::implicit ? IM_W : (Args::payloads ? t->pl_width : (Args::grounds ? t->gr_width : t->ct_width)), n = t->host.n,
+              laws = Args::grounds ? w : 1;
+    if constexpr (Args::payloads)       // a law and a payload per lane behind either
+        return launch_step(t, chain_kernel<Args>(w), w, Args::implicit ? im_payloads_lds_bytes(n) : ct_payloads_lds_bytes(n, w), p, stream);
     return launch_step(t, chain_kernel<Args>(w), w, Args::implicit ? im_lds_bytes(n, laws) : ct_lds_bytes(n, w, laws), p, stream);
 }
 
@@ -472,6 +480,8 @@ int allocate(Torque* t) {
     LDS_LIMIT(crba_kernel, crba_lds_bytes(MAXJ, CR_W));
     LDS_LIMIT(chain_kernel<ImplicitArgs>(IM_W), im_lds_bytes(MAXJ));
     LDS_LIMIT(chain_kernel<ImplicitGroundsArgs>(IM_W), im_lds_bytes(MAXJ, IM_W));
+    LDS_LIMIT(chain_kernel<PayloadsArgs>(t->pl_width), t->pl_width == 32 ? ct_payloads_lds_bytes(ct_payloads_wide_joints(), 32) : ct_payloads_lds_bytes(MAXJ, 16));
+    LDS_LIMIT(chain_kernel<ImplicitPayloadsArgs>(IM_W), im_payloads_lds_bytes(MAXJ));
     LDS_LIMIT(centroidal_kernel<CmdIo>, centroidal_lds_bytes<CmdIo>(MAXJ));
     LDS_LIMIT(centroidal_kernel<NodeRecordIo>, centroidal_lds_bytes<NodeRecordIo>(MAXJ));
     LDS_LIMIT(centroidal_kernel<StateMomentumIo>, centroidal_lds_bytes<StateMomentumIo>(MAXJ));
@@ -587,6 +597,11 @@ const char* grounds_batch_refusal(const Torque* t, int B) {
     return t->grounds.rows && B > t->grounds.n_rows ? "grounds: B exceeds n_rows" : nullptr;
 }
 
+// why the attached table of payloads cannot serve a plant call of B robots (nullptr: it can, or there is none)
+const char* payloads_batch_refusal(const Torque* t, int B) {
+    return t->payloads.rows && B > t->payloads.n_rows ? "payloads: B exceeds n_rows" : nullptr;
+}
+
 // A plant call under a push is cut into runs of substeps that are all un-pushed -- launches of the un-pushed kernels, as a call
 // without a push makes them -- and runs that are all pushed, launches of the PushArgs chain (nmpc_torque_track.hip.inc says why).
 
@@ -608,13 +623,15 @@ PushArgs chain_args(int B, int n_steps, int n_sub, float dt, const nmpc_contact_
 
 // a plant call under the implicit integrator: one launch of the ImplicitArgs chain, the push window -- the push's own, or with
 // `wins` the robot's, in a call whose substep 0 is substep s0 of their count -- tested inside it.  And a plant call of either
-// integrator under a table of grounds (Args: ImplicitGroundsArgs, GroundsArgs), which states its push the same way.
+// integrator under a table of grounds (Args: ImplicitGroundsArgs, GroundsArgs) or of payloads (ImplicitPayloadsArgs, PayloadsArgs),
+// which state their push the same way; under payloads the table of grounds may be absent (rows == nullptr: the call's own law).
 template <class Args = ImplicitArgs>
 int launch_implicit(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins,
                     long long s0, void* stream) {
     Args p{};
     static_cast<PushArgs&>(p) = call;
     if constexpr (Args::grounds) p.rows = t->grounds.rows;
+    if constexpr (Args::payloads) { p.payload_rows = t->payloads.rows; p.payload_joint = t->payloads.joint; }
     if (win.hi > win.lo) { p.force = push.force; p.joint = push.joint; p.push_lo = win.lo; p.push_hi = win.hi; }
     if (wins.first) { p.force = push.force; p.joint = push.joint; p.win_first = wins.first; p.win_count = wins.count; p.win_s0 = s0; }
     return launch_chain(t, p, stream);
@@ -640,11 +657,15 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
     if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = push_batch_refusal(push, wins, B)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = payloads_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     const Window win = wins.first ? Window{} : push_window(push, s0, n_sub);
     PushArgs call = chain_args(B, 1, n_sub, dt, *cfg, tau_ff, q_des, 1, kp, kd, q_out, v_out);
     call.q_in = q; call.v_in = v; call.a_out = a_out; call.f_out = f_out; call.tau_out = tau_out;
     const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
+    if (t->payloads.rows)                        // a payload per robot: one launch whatever the push and the grounds
+        return implicit ? launch_implicit<ImplicitPayloadsArgs>(t, call, push, win, wins, s0, stream)
+                        : launch_implicit<PayloadsArgs>(t, call, push, win, wins, s0, stream);
     if (t->grounds.rows)                         // a law per robot: one launch whatever the push
         return implicit ? launch_implicit<ImplicitGroundsArgs>(t, call, push, win, wins, s0, stream)
                         : launch_implicit<GroundsArgs>(t, call, push, win, wins, s0, stream);
@@ -694,6 +715,7 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
         return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
     if (const char* why = push_batch_refusal(push, wins, B)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = payloads_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     const int n = t->host.n, nu = t->host.nu;
     const long long total = (long long)n_steps * n_sub;
@@ -701,8 +723,11 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
     PushArgs call = chain_args(B, n_steps, n_sub, dt, *cfg, tau_ff, A, a_rows, kp, kd, q, v);
     call.qv_rows = qv_rows; call.skip_mask = skip ? skip_mask : 0; call.skip = call.skip_mask ? skip : nullptr;
     const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
-    if (implicit || wins.first || t->grounds.rows) {      // one launch for the whole table; the cut path below moves A, Q, V piece by piece
+    if (implicit || wins.first || t->grounds.rows || t->payloads.rows) {      // one launch for the whole table; the cut path below moves A, Q, V piece by piece
         call.Q = Q; call.V = V;
+        if (t->payloads.rows)
+            return implicit ? launch_implicit<ImplicitPayloadsArgs>(t, call, push, win, wins, s0, stream)
+                            : launch_implicit<PayloadsArgs>(t, call, push, win, wins, s0, stream);
         if (t->grounds.rows)
             return implicit ? launch_implicit<ImplicitGroundsArgs>(t, call, push, win, wins, s0, stream)
                             : launch_implicit<GroundsArgs>(t, call, push, win, wins, s0, stream);
@@ -838,6 +863,7 @@ int nmpc_torque_create(const nmpc_tree_model* mdl, int device_id, void** handle)
     t->fd_width = fd_block_width(m.n);
     t->ct_width = ct_block_width(m.n);
     t->gr_width = ct_grounds_block_width(m.n);
+    t->pl_width = ct_payloads_block_width(m.n);
     for (int i = m.n - 1; i >= 0; --i)
         if (m.mass[i] > 0.0f) t->anchor = i;
     for (int k = t->anchor; k >= 0; k = m.parent[k]) t->chain |= 1u << k;
@@ -1012,6 +1038,18 @@ int nmpc_contact_set_grounds(void* torque, const float* rows, int n_rows) {
     return NMPC_OK;
 }
 
+int nmpc_contact_set_payloads(void* torque, const float* rows, int n_rows, int joint) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (rows) {                                           // what was attached stays
+        if (n_rows < 1) return fail(t, NMPC_E_ARG, "payloads: n_rows must be at least 1");
+        if (joint < 0 || joint >= t->host.n) return fail(t, NMPC_E_ARG, "payloads: joint must be in [0, n_joints)");
+    }
+    t->payloads = {};
+    if (rows) { t->payloads.rows = rows; t->payloads.n_rows = n_rows; t->payloads.joint = joint; }
+    return NMPC_OK;
+}
+
 int nmpc_contact_set_integrator(void* torque, int mode) {
     Torque* t = static_cast<Torque*>(torque);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
@@ -1105,6 +1143,7 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
     if (const char* why = push_batch_refusal(t->push, t->windows, B)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = payloads_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
         NMPC_ENTER(t, t->device);

@@ -157,6 +157,39 @@ struct PushedGroundForces : GroundForces {
     __device__ __forceinline__ V3 body() const { return F; }
 };
 
+// A payload per robot (nmpc_contact_set_payloads, DESIGN.md 8d): a point mass at r in the frame of one body of the tree, row b of
+// the attached table [n_rows][4] as it is.  Nothing of a row is validated here (include/nmpc_torque.h).
+struct Payload {
+    float mass, x, y, z;
+};
+// what a lane of the payload chains keeps behind the slice: its law and, beside it, its payload (ten words: the 32 lanes of a
+// block at that stride fall on 32 different banks of 64)
+struct LaneLoad {
+    ContactCfg c;
+    Payload load;
+};
+// the footprint and the block width of the explicit chain under a table of payloads, by the rule of the grounds on the larger slot
+// (23 joints x 32 robots: 160 256 B, still inside)
+constexpr size_t ct_payloads_lds_bytes(int n, int width) { return (size_t)n * CT_SLOTS * width * sizeof(float) + width * sizeof(LaneLoad); }
+constexpr int ct_payloads_block_width(int n) { return ct_payloads_lds_bytes(n, 32) <= FD_LDS_MAX ? 32 : 16; }
+static_assert(ct_payloads_lds_bytes(MAXJ, 16) <= FD_LDS_MAX, "the slice of the largest tree, a law and a payload per lane no longer fit a CU at 16 robots per block");
+constexpr int ct_payloads_wide_joints() {
+    int n = MAXJ;
+    while (n > 1 && ct_payloads_block_width(n) != 32) --n;
+    return n;
+}
+
+// a force source of the plant under the lane's payload on body `on`: the hook of fd_accel_body reads the four words where they lie
+template <class Source>
+struct Loaded : Source {
+    const Payload* load;                                  // in LDS, beside the lane's law
+    int on;
+    static constexpr bool loads = true;
+    __device__ __forceinline__ bool loaded(int i) const { return i == on; }
+    __device__ __forceinline__ float load_mass() const { return load->mass; }
+    __device__ __forceinline__ V3 load_at() const { return {load->x, load->y, load->z}; }
+};
+
 struct ContactArgs {
     int B, n_sub;
     float dt, kp, kd;

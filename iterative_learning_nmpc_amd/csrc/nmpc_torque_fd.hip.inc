@@ -62,6 +62,25 @@ template <class Force, class = void>
 struct force_pushes : std::false_type {};
 template <class Force>
 struct force_pushes<Force, std::void_t<decltype(Force::pushes)>> : std::bool_constant<Force::pushes> {};
+// A source may also load a body with a point-mass payload (nmpc_contact_set_payloads, DESIGN.md 8d): with a member
+// `static constexpr bool loads = true` it has `loaded(i)`, does body i carry the payload, `load_mass()`, m_p, and `load_at()`, its
+// position r in that body's frame.  Read under `if constexpr` as the push is: a source without the member compiles to what it did.
+template <class Force, class = void>
+struct force_loads : std::false_type {};
+template <class Force>
+struct force_loads<Force, std::void_t<decltype(Force::loads)>> : std::bool_constant<Force::loads> {};
+
+// the spatial inertia of a point mass mp at r, added to the FD_I slots of body i: A += mp (|r|^2 1 - r r^T), B += mp [r]x, C += mp 1
+template <class At>
+__device__ __forceinline__ void add_point_inertia(const At& at, int i, float mp, V3 r) {
+    const float rr = dot(r, r);
+    at(i, FD_I + 0) += mp * (rr - r.x * r.x); at(i, FD_I + 1) -= mp * r.x * r.y; at(i, FD_I + 2) -= mp * r.x * r.z;
+    at(i, FD_I + 3) += mp * (rr - r.y * r.y); at(i, FD_I + 4) -= mp * r.y * r.z; at(i, FD_I + 5) += mp * (rr - r.z * r.z);
+    const M3 Bm = skew(mp * r);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) at(i, FD_I + 6 + k) += Bm.m[k];
+    at(i, FD_I + 15) += mp; at(i, FD_I + 18) += mp; at(i, FD_I + 20) += mp;
+}
 
 // given forces: f (world-frame foot forces of this robot, or nullptr) is read from memory
 struct GivenForces {
@@ -152,6 +171,20 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
 #pragma unroll
                 for (int k = 0; k < 9; ++k) Rs.m[k] = at(i, FD_RW + k);
                 at.put3(i, FD_P + 3, at.get3(i, FD_P + 3) - mul_t(Rs, force.body()));
+            }
+        }
+        // the payload: I += I_p and p^A += v x* (I_p v) on the loaded body, to the slice and from the slice behind the same
+        // barrier, for the same reason
+        if constexpr (force_loads<Force>::value) {
+            if (force.loaded(i)) {
+                __asm__ volatile("" ::: "memory");
+                const float mp = force.load_mass();
+                const V3 r = force.load_at();
+                add_point_inertia(at, i, mp, r);
+                const V3 ws = at.get3(i, FD_V), vs = at.get3(i, FD_V + 3);
+                const V3 g_l = mp * (vs + cross(ws, r)), g_n = cross(r, g_l);
+                at.put3(i, FD_P, at.get3(i, FD_P) + cross(ws, g_n) + cross(vs, g_l));
+                at.put3(i, FD_P + 3, at.get3(i, FD_P + 3) + cross(ws, g_l));
             }
         }
     }

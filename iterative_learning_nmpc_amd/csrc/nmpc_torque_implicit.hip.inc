@@ -23,6 +23,20 @@ constexpr size_t im_triangle(int n) { return (size_t)n * (n + 1) / 2; }
 // the slice, the triangle, and behind it the law: one for the block, or IM_W of them under a table of grounds (a law per lane)
 constexpr size_t im_lds_bytes(int n, int laws = 1) { return ((size_t)n * CT_SLOTS + im_triangle(n)) * IM_W * sizeof(float) + laws * sizeof(ContactCfg); }
 static_assert(im_lds_bytes(MAXJ, IM_W) <= FD_LDS_MAX, "the implicit slice of the largest tree no longer fits a CU at 16 robots per block");
+// and under a table of payloads: a law and a payload per lane behind the triangle
+constexpr size_t im_payloads_lds_bytes(int n) { return ((size_t)n * CT_SLOTS + im_triangle(n)) * IM_W * sizeof(float) + IM_W * sizeof(LaneLoad); }
+static_assert(im_payloads_lds_bytes(MAXJ) <= FD_LDS_MAX, "the implicit slice of the largest tree, a law and a payload per lane no longer fit a CU");
+
+// no payload: what implicit_accel_body is given by a chain without one
+struct NoLoad {
+    static constexpr bool loads = false;
+};
+// the lane's payload on body `on`
+struct LaneLoaded {
+    const Payload* load;
+    int on;
+    static constexpr bool loads = true;
+};
 
 // the law and a push that acts only in the substeps of its window
 struct WindowedPushForces : PushedGroundForces {
@@ -40,9 +54,10 @@ struct Triangle {
 // The implicit correction of one substep: from q, v, a_exp in slots FD_Q .. FD_Q + 2 of the slice (as fd_accel_body leaves them)
 // to a in slot FD_Q + 2.  unclamped: bit i set for an actuated joint i whose PD torque the clamp did not cut (0 without a PD
 // target).  Returns false if a pivot of the factorisation is not a positive finite number.
-template <int W>
+// load: the payload whose inertia the mass matrix carries (NoLoad: none, and the text below compiles to what it was without it).
+template <int W, class Load = NoLoad>
 __device__ __forceinline__ bool implicit_accel_body(const Model& m, const ContactCfg& c, const Triangle<W> A, float dt, float kp, float kd,
-                                                    unsigned unclamped) {
+                                                    unsigned unclamped, [[maybe_unused]] const Load load = {}) {
     const int n = m.n;
     const Slice<CT_SLOTS, W> at;
 
@@ -73,6 +88,13 @@ __device__ __forceinline__ bool implicit_accel_body(const Model& m, const Contac
 #pragma unroll
         for (int k = 0; k < 9; ++k) at(i, FD_I + 6 + k) = Bm.m[k];
         at(i, FD_I + 15) = mass; at(i, FD_I + 16) = 0.0f; at(i, FD_I + 17) = 0.0f; at(i, FD_I + 18) = mass; at(i, FD_I + 19) = 0.0f; at(i, FD_I + 20) = mass;
+        // the payload, as fd_accel_body adds it: to the slice, from the slice, behind the barrier
+        if constexpr (Load::loads) {
+            if (i == load.on) {
+                __asm__ volatile("" ::: "memory");
+                add_point_inertia(at, i, load.load->mass, V3{load.load->x, load.load->y, load.load->z});
+            }
+        }
     }
 
     // inward (crba_kernel's): I^c of a body goes to its parent's frame, C' = C, B' = B + P C, A' = A - B P + P B'^T  (P = [p]x)

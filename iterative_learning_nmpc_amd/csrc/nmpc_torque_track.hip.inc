@@ -1,5 +1,5 @@
 // nmpc_torque_track.hip.inc -- the chain of control steps on the ground-contact plant: a table of PD targets tracked in one launch,
-// pushed, under a window per robot, under the implicit integrator or under a ground per robot (nmpc_contact_track_batch of
+// pushed, under a window per robot, under the implicit integrator, under a ground or under a payload per robot (nmpc_contact_track_batch of
 // include/nmpc_torque.h, and every launch of nmpc_contact_step_batch but the un-pushed explicit one); included by nmpc_torque.hip inside namespace nmpc_torque,
 // after nmpc_torque_implicit.hip.inc.
 //
@@ -23,7 +23,7 @@ enum class Forces {
 
 // The un-pushed track: the state in q, v goes through n_steps control steps, in place.
 struct TrackArgs {
-    static constexpr bool step_io = false, implicit = false, grounds = false;
+    static constexpr bool step_io = false, implicit = false, grounds = false, payloads = false;
     static constexpr Forces forces = Forces::ground;
     int B, n_steps, n_sub, a_rows, qv_rows, skip_mask;
     float dt, kp, kd;
@@ -94,6 +94,22 @@ struct GroundsArgs : ImplicitGroundsArgs {
     static constexpr Forces forces = Forces::either;
 };
 
+// A payload per robot, nmpc_contact_set_payloads (DESIGN.md 8d): of the family above, so every lane has a slot of its own behind
+// the slice (behind the triangle when implicit), now its law and beside it the four words of row b of the payload table.  The law
+// is row b of the table of grounds if one is attached (rows), else c: both are the ContactCfg the uniform call reads, bit for bit.
+// The recursion runs under Loaded<> sources, whose hook adds the point mass to the inertia and the velocity-product force of body
+// `payload_joint`; the implicit correction forms its mass matrix with the same addition.  One instantiation per integrator, one
+// launch per call, the push stated and taken as under a table of grounds.
+struct ImplicitPayloadsArgs : ImplicitGroundsArgs {
+    static constexpr bool payloads = true;
+    const float* payload_rows;                            // [>= B][4]: m_p, r_x, r_y, r_z
+    int payload_joint;
+};
+struct PayloadsArgs : ImplicitPayloadsArgs {
+    static constexpr bool implicit = false;
+    static constexpr Forces forces = Forces::either;
+};
+
 // ---- the chain ------------------------------------------------------------------------------------------------------------------
 // contact_step_kernel's substep, n_steps * n_sub times on the state in the slice: per control step the state goes out to row k
 // of Q, V (if given), the PD target becomes row k of the robot's table, and n_sub substeps follow.  A control step whose
@@ -112,7 +128,11 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
     [[maybe_unused]] const int nf3 = 3 * m.nf;
     float* const behind = body + n * CT_SLOTS * W;
     ContactCfg* cfg = reinterpret_cast<ContactCfg*>(Args::implicit ? behind + (n * (n + 1) / 2) * W : behind);
-    if constexpr (Args::grounds) {
+    [[maybe_unused]] Payload* load = nullptr;             // Args::payloads: the lane's payload, beside its law
+    if constexpr (Args::payloads) {
+        LaneLoad* const lane = reinterpret_cast<LaneLoad*>(cfg) + threadIdx.x;
+        cfg = &lane->c; load = &lane->load;
+    } else if constexpr (Args::grounds) {
         cfg += threadIdx.x;                               // the lane's own slot, which nobody else reads: no barrier
     } else {
         if (threadIdx.x == 0) *cfg = p.c;
@@ -121,7 +141,13 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
     const int b = blockIdx.x * W + threadIdx.x;
     if (b >= p.B) return;
     if (p.skip && (p.skip[b] & p.skip_mask)) return;
-    if constexpr (Args::grounds) *cfg = ground_row(p.rows, b);
+    if constexpr (Args::payloads) {
+        *cfg = p.rows ? ground_row(p.rows, b) : p.c;
+        const float* r = p.payload_rows + (size_t)b * 4;
+        *load = {r[0], r[1], r[2], r[3]};
+    } else if constexpr (Args::grounds) {
+        *cfg = ground_row(p.rows, b);
+    }
     const Slice<CT_SLOTS, W> at;
     float* qb = p.q + (size_t)b * n;
     float* vb = p.v + (size_t)b * n;
@@ -178,7 +204,14 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
                 }
                 at(i, FD_Q + 2) = t;
             }
-            if constexpr (Args::forces == Forces::ground) {
+            if constexpr (Args::payloads && Args::forces == Forces::either) {
+                if (sub >= push_lo && sub < push_hi)
+                    sound = fd_accel_body<W, CT_SLOTS>(m, Loaded<PushedGroundForces>{{{cfg, last ? fo : nullptr}, F, p.joint}, load, p.payload_joint}) && sound;
+                else
+                    sound = fd_accel_body<W, CT_SLOTS>(m, Loaded<GroundForces>{{cfg, last ? fo : nullptr}, load, p.payload_joint}) && sound;
+            } else if constexpr (Args::payloads) {
+                sound = fd_accel_body<W, CT_SLOTS>(m, Loaded<WindowedPushForces>{{{{cfg, last ? fo : nullptr}, F, p.joint}, on}, load, p.payload_joint}) && sound;
+            } else if constexpr (Args::forces == Forces::ground) {
                 sound = fd_accel_body<W, CT_SLOTS>(m, GroundForces{cfg, nullptr}) && sound;
             } else if constexpr (Args::forces == Forces::pushed) {
                 sound = fd_accel_body<W, CT_SLOTS>(m, PushedGroundForces{{cfg, last ? fo : nullptr}, F, p.joint}) && sound;
@@ -190,7 +223,9 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
             } else {
                 sound = fd_accel_body<W, CT_SLOTS>(m, WindowedPushForces{{{cfg, last ? fo : nullptr}, F, p.joint}, on}) && sound;
             }
-            if constexpr (Args::implicit)
+            if constexpr (Args::implicit && Args::payloads)
+                sound = implicit_accel_body<W>(m, *cfg, Triangle<W>{behind}, p.dt, p.kp, p.kd, unclamped, LaneLoaded{load, p.payload_joint}) && sound;
+            else if constexpr (Args::implicit)
                 sound = implicit_accel_body<W>(m, *cfg, Triangle<W>{behind}, p.dt, p.kp, p.kd, unclamped) && sound;
 #pragma clang loop unroll(disable) vectorize(disable)
             for (int i = 0; i < n; ++i) {

@@ -74,7 +74,8 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
     `plant` / `plant_substeps` / `push_as_force` / `integrator`: the expert on the ground-contact plant, pushed by a force, under the named integrator;
     `chunk_replans`: the rollout in stretches of that many replans, each appended before the next runs) appends the valid rollouts and their weights to `db`, then
     `train_network` trains `policy` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows.  Returns (err, weights, n_rows, train_loss, val_loss): what
-    the two parts return."""
+    the two parts return.  A table of grounds or of payloads attached on `layer` (`set_grounds`, `set_payloads`) is seen by the
+    plant of the rollouts; there is no keyword for either."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
     err, weights, n_rows = collect_rollouts(mpc, layer, db, q0, v0, T, push=push, nominal=nominal, ood_weight=ood_weight,
@@ -92,7 +93,7 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
 def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, tau_ff=None, kp: float = KP,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
                     terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False,
-                    push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None):
+                    push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -118,7 +119,10 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     grounds: a table of grounds, one row per robot (`BatchedTorqueLayer.set_grounds` takes it and validates it; `sample_grounds`
     draws one), attached for this call: robot b stands on the ground of row b and has its torque limit, and `ground` is
     ignored.  None: every robot is on `ground`.  A layer that has a table of the caller's attached already is refused with
-    ValueError, as for a push."""
+    ValueError, as for a push.
+    payloads: a table of payloads, one row (m_p, r) per robot (`BatchedTorqueLayer.set_payloads` takes it and validates it;
+    `sample_payloads` draws one), attached to the trunk for this call: robot b carries row b on the plant.  None: nobody carries
+    anything.  A layer that has a table of the caller's attached already is refused with ValueError in the same way."""
     if integrator is not None:
         integrator_mode(integrator)                       # an unknown name is refused before anything is attached
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
@@ -128,6 +132,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
         raise ValueError("push: the layer has a push attached already (set_push)")
     if grounds is not None and layer._grounds is not None:
         raise ValueError("grounds: the layer has a table of grounds attached already (set_grounds)")
+    if payloads is not None and layer._payloads is not None:
+        raise ValueError("payloads: the layer has a table of payloads attached already (set_payloads)")
     states = {}
     if record_states:
         B = torch.as_tensor(q0).reshape(-1, layer.n).shape[0]
@@ -138,6 +144,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
             layer.set_integrator(integrator)
         if grounds is not None:
             layer.set_grounds(grounds)
+        if payloads is not None:
+            layer.set_payloads(payloads)
         if push is not None:
             force = torch.as_tensor(push["force"], dtype=torch.float32, device=layer.device).reshape(-1, 3)
             windows = push_windows(push, force.shape[0])
@@ -156,6 +164,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
             layer.set_push(None)
         if grounds is not None:
             layer.set_grounds(None)
+        if payloads is not None:
+            layer.set_payloads(None)
         if record_states:
             layer.set_rollout_states(None)
     stamp = failed >> NMPC_ROLLOUT_TERM_SHIFT
@@ -166,7 +176,7 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
 def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, kp: Optional[float] = None,
                      kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
                      n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0,
-                     push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None):
+                     push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None):
     """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
         1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
            [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
@@ -181,7 +191,8 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     kp, kd: the gains of the policy's PD law and of the labels alike (None: the controller's Kp, Kd), so that an action and
     its label mean the same torque.  integrator: the plant's integrator, as `evaluate_policy` takes it.  grounds: a ground per
     robot for the learner's rollout, as `evaluate_policy` takes it (attached for that call; the labels are the expert's solves and
-    stand on no plant).  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
+    stand on no plant).  payloads: a payload per robot for the learner's rollout, in the same way: the plant carries it, the
+    labels are the nominal expert's -- the expert's model does not describe the load, which is the point.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
     train_loss and val_loss added."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
@@ -190,7 +201,7 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     kp, kd = float(mpc.Kp if kp is None else kp), float(mpc.Kd if kd is None else kd)
     out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
                           terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push,
-                          integrator=integrator, grounds=grounds)
+                          integrator=integrator, grounds=grounds, payloads=payloads)
     A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
     S = out["S"]
     B, K = S.shape[:2]

@@ -270,7 +270,9 @@ class LocomotionMPC:
         the PD target applied from it (RolloutMPC.py:168-258); a robot that falls in the last interval is flagged too.
         A ground per rollout takes no keyword here: attach the table on torque_layer (`BatchedTorqueLayer.set_grounds`) before
         the call -- rollout b then stands on row b, the values of `plant` are ignored, and `collect_rollouts` and
-        `learning_iteration`, which run this call, see the same table.
+        `learning_iteration`, which run this call, see the same table.  A payload per rollout likewise
+        (`BatchedTorqueLayer.set_payloads`): the plant of rollout b carries row b, the plans and the labels are those of the
+        nominal model.
         push_as_force (needs plant): the push is a force on the trunk of the plant over the substeps its window covers
         (nmpc_wb_rollout_set_plant_push), where the feet and the torque limit answer it, instead of the velocity jump per
         replanning interval.

@@ -103,6 +103,52 @@ def sample_grounds(B: int, rng, base: GroundContact = GroundContact(), mu=None, 
     return ground_table(rows)
 
 
+PAYLOAD_COLUMNS = ("mass", "r_x", "r_y", "r_z")            # a row of a table of payloads: a point mass m_p at r in the frame of one body
+
+
+def payload_table(payloads, B: int = 1) -> np.ndarray:
+    """Host input of `BatchedTorqueLayer.set_payloads` as a validated float32 array [>= B, 4] in the order of PAYLOAD_COLUMNS:
+    every value finite and the mass not negative; a violation, a wrong shape or fewer than B rows is a ValueError naming the
+    first offending row."""
+    try:
+        rows = np.ascontiguousarray(np.asarray(payloads, dtype=np.float32))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"payloads: need a float array [B, {len(PAYLOAD_COLUMNS)}]") from e
+    B = max(int(B), 1)
+    if rows.ndim != 2 or rows.shape[1] != len(PAYLOAD_COLUMNS) or rows.shape[0] < B:
+        raise ValueError(f"payloads: expected [>= {B}, {len(PAYLOAD_COLUMNS)}], got {tuple(rows.shape)}")
+    for why, bad in (("the payload must be finite", ~np.isfinite(rows).all(axis=1)), ("the mass must not be negative", ~(rows[:, 0] >= 0.0))):
+        if bad.any():
+            raise ValueError(f"payloads: row {int(np.argmax(bad))}: {why}")
+    return rows
+
+
+def sample_payloads(n: int, seed: int, mass=(0.0, 5.0), offset=((-0.1, 0.1), (-0.05, 0.05), (0.0, 0.1))) -> np.ndarray:
+    """A table of payloads for `BatchedTorqueLayer.set_payloads`: float32 [n, 4], the mass drawn uniformly from `mass` (lo, hi) in
+    kg and the position from the box `offset` ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi)) in metres of the body frame.
+    Deterministic in `seed`: the four columns are drawn in the order of PAYLOAD_COLUMNS, n values each."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    ranges = [tuple(float(x) for x in mass)] + [tuple(float(x) for x in side) for side in offset]
+    if len(ranges) != 4 or any(len(r) != 2 for r in ranges):
+        raise ValueError("need mass = (lo, hi) and offset = ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi))")
+    rng = np.random.default_rng(seed)
+    rows = np.zeros((n, 4), np.float32)
+    for col, (name, (lo, hi)) in enumerate(zip(PAYLOAD_COLUMNS, ranges)):
+        if not lo <= hi:
+            raise ValueError(f"{name}: need a range (lo, hi) with lo <= hi, got {(lo, hi)!r}")
+        lo32, hi32 = np.float32(lo), np.float32(hi)      # the float32 values inside [lo, hi] that a rounded draw is held to
+        if lo32 < lo:
+            lo32 = np.nextafter(lo32, np.float32(np.inf))
+        if hi32 > hi:
+            hi32 = np.nextafter(hi32, np.float32(-np.inf))
+        if lo32 > hi32:
+            raise ValueError(f"{name}: the range {(lo, hi)!r} holds no float32 value")
+        rows[:, col] = np.clip(rng.uniform(lo, hi, n).astype(np.float32), lo32, hi32)
+    return payload_table(rows, n)
+
+
 class BatchedTorqueLayer:
     def __init__(self, parent: Sequence[int], joint_type: Sequence[int], axis, placement_R, placement_p, mass, com, inertia,
                  foot_joint: Sequence[int], foot_offset, n_actuated: int, gravity=(0.0, 0.0, -9.81), device="cuda:0"):
@@ -133,6 +179,7 @@ class BatchedTorqueLayer:
         self._push = None               # set_push: the attached force
         self._push_windows = None       # set_push with arrays: the attached (first substeps, counts)
         self._grounds = None            # set_grounds: the attached table
+        self._payloads = None           # set_payloads: the attached table
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -506,6 +553,35 @@ class BatchedTorqueLayer:
             rows = torch.tensor(host, device=self.device)      # a copy: the caller's array may be read-only
         _lib.check(self.lib.nmpc_contact_set_grounds(self._h, ptr(rows), rows.shape[0]), self._h, "nmpc_contact_set_grounds", "torque")
         self._grounds = rows
+
+    def set_payloads(self, payloads=None, joint: Optional[int] = None):
+        """nmpc_contact_set_payloads: a point-mass payload of its own per robot.  payloads: a float array or tensor [B, 4] in the
+        order of PAYLOAD_COLUMNS (m_p >= 0 in kg, then its position r in the frame of body `joint`; `sample_payloads` draws one);
+        joint None: the trunk, the last virtual base joint n - nu - 1.  While the table is attached robot b carries row b in
+        `contact_step`, `contact_track`, `policy_rollout` and the expert on the plant (`open_loop_device(..., plant=...)`, and with
+        it `collect_rollouts` and `learning_iteration`, which take no keyword for it: attach the table on the layer they are
+        given), under either integrator, with or without a push or a table of grounds; every such call is one launch.  It is
+        the plant alone that carries the load: `id_torques`, `forward_dynamics`, `step`, `mass_matrix`, `centroidal`,
+        `state_momentum`, `contact_forces`, `plan_actions` and the expert's labels describe the nominal tree, with or without a
+        table.  Calls with more robots than the table has rows are refused.
+        Host input is validated (`payload_table`: ValueError) and uploaded; a tensor already on the layer's device is taken as
+        given -- the device validates nothing -- and in either case the layer keeps the table alive while it is attached.
+        `set_payloads(None)` detaches; detached, every call makes the launches and gives the bits it gives without."""
+        if payloads is None:
+            self._payloads = None
+            _lib.check(self.lib.nmpc_contact_set_payloads(self._h, None, 0, 0), self._h, "nmpc_contact_set_payloads", "torque")
+            return
+        if isinstance(payloads, torch.Tensor) and payloads.is_cuda:
+            if payloads.dtype != torch.float32 or payloads.dim() != 2 or payloads.shape[1] != len(PAYLOAD_COLUMNS) or payloads.shape[0] < 1 \
+                    or payloads.device != self.device:
+                raise ValueError(f"payloads: a device table must be float32 [B, {len(PAYLOAD_COLUMNS)}] with B >= 1 on {self.device}")
+            rows = payloads.contiguous()
+        else:
+            host = payload_table(payloads.numpy() if isinstance(payloads, torch.Tensor) else payloads)
+            rows = torch.tensor(host, device=self.device)      # a copy: the caller's array may be read-only
+        joint = self.n - self.nu - 1 if joint is None else int(joint)
+        _lib.check(self.lib.nmpc_contact_set_payloads(self._h, ptr(rows), rows.shape[0], joint), self._h, "nmpc_contact_set_payloads", "torque")
+        self._payloads = rows
 
     def _state_io(self, t, name):
         """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""
