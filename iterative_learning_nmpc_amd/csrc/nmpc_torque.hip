@@ -18,7 +18,8 @@
 // pass -- is nmpc_torque_crba.hip.inc; the correction of the plant's second integrator, which takes the stiff contact and PD terms
 // implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; the chain of control steps on the plant -- one
 // kernel text, instantiated for a table of PD targets tracked in one launch, for pushed substeps, for a push window per robot,
-// for the implicit integrator and for either integrator under a ground or a payload per robot -- is nmpc_torque_track.hip.inc; the centroidal momentum about an anchor
+// for the implicit integrator and for either integrator under a ground or a payload per robot -- is nmpc_torque_track.hip.inc, with
+// the one rule of what lies behind an instantiation's slice, its LDS footprint and its block width; the centroidal momentum about an anchor
 // point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
 // momentum A_g(q) v of a plant state alone, which the device rollouts put into x0.
@@ -380,8 +381,6 @@ struct Torque {
     int device = 0;
     int fd_width = 32;                  // robots per block of fd_kernel: fd_block_width(n), or 16 if NMPC_FD_WIDTH=16 asks for it (tools/fd_cost.py)
     int ct_width = 32;                  // robots per block of contact_step_kernel: ct_block_width(n)
-    int gr_width = 32;                  // and of the explicit chain under a table of grounds: ct_grounds_block_width(n)
-    int pl_width = 32;                  // and under a table of payloads: ct_payloads_block_width(n)
     int anchor = -1;                    // the centroidal kernels' reference frame: the first joint whose body has mass (-1: the tree has none)
     unsigned chain = 0;                 // bit i: joint i is the anchor or one of its ancestors
     float* act = nullptr;               // [act_rows][nu]: the actions of nmpc_policy_rollout_batch when its caller keeps none
@@ -392,14 +391,13 @@ struct Torque {
     } states;
     nmpc_push_cfg push{};               // nmpc_contact_set_push: the push of the plant calls (force == nullptr: none)
     nmpc_torque::PushWindows windows{}; // nmpc_contact_set_push_windows: a window per robot in place of the push's own (first == nullptr: none)
-    struct {                            // nmpc_contact_set_grounds: a law per robot in place of the plant calls' cfg (rows == nullptr: none)
+    struct Table {                      // a row per robot (rows == nullptr: none)
         const float* rows = nullptr;
         int n_rows = 0;
-    } grounds;
-    struct {                            // nmpc_contact_set_payloads: a point mass per robot on body `joint` in the plant calls (rows == nullptr: none)
-        const float* rows = nullptr;
-        int n_rows = 0, joint = 0;
-    } payloads;
+    };
+    Table grounds;                      // nmpc_contact_set_grounds: a law per robot in place of the plant calls' cfg
+    Table payloads;                     // nmpc_contact_set_payloads: a point mass per robot on body `payload_joint` in the plant calls
+    int payload_joint = 0;
     int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
@@ -419,19 +417,16 @@ int launch_step(Torque* t, void (*kernel)(const Model*, Args), int width, size_t
 // the instantiation of contact_chain_kernel for Args at a run-time block width; the implicit chain has the one width IM_W
 template <class Args>
 auto chain_kernel(int w) {
+    static_assert(chain_lds_bytes<Args>(MAXJ, chain_block_width<Args>(MAXJ)) <= FD_LDS_MAX, "the largest tree no longer fits a CU at the narrow width of this chain");
     if constexpr (Args::implicit) return contact_chain_kernel<IM_W, Args>;
     else return w == 32 ? contact_chain_kernel<32, Args> : contact_chain_kernel<16, Args>;
 }
 
-// one launch of the chain: at the handle's width of the contact step, or the implicit chain's own with its triangle behind the slice;
-// under a table of grounds at the width its larger footprint allows, a law per lane behind either
+// one launch of the chain, at the width and with the footprint its Args state for the handle's tree
 template <class Args>
 int launch_chain(Torque* t, const Args& p, void* stream) {
-    const int w = Args::implicit ? IM_W : (Args::payloads ? t->pl_width : (Args::grounds ? t->gr_width : t->ct_width)), n = t->host.n,
-              laws = Args::grounds ? w : 1;
-    if constexpr (Args::payloads)       // a law and a payload per lane behind either
-        return launch_step(t, chain_kernel<Args>(w), w, Args::implicit ? im_payloads_lds_bytes(n) : ct_payloads_lds_bytes(n, w), p, stream);
-    return launch_step(t, chain_kernel<Args>(w), w, Args::implicit ? im_lds_bytes(n, laws) : ct_lds_bytes(n, w, laws), p, stream);
+    const int n = t->host.n, w = chain_block_width<Args>(n);
+    return launch_step(t, chain_kernel<Args>(w), w, chain_lds_bytes<Args>(n, w), p, stream);
 }
 
 // one of the element-wise kernels: a thread per entry of a [B][nu] table
@@ -456,6 +451,21 @@ bool whole_body_tree(const Model& m) { return m.n == 18 && m.nu == 12 && m.nf ==
 #define LDS_LIMIT(kernel, bytes) \
     NMPC_TRY(no_handle, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
 
+// the most an instantiation of the chain can be asked for at the width the handle's tree runs it at: chain_wide_joints() joints x 32
+// robots, the largest tree x 16 (the implicit chains: x IM_W)
+template <class Args>
+int chain_lds_limit(Torque* t) {
+    const int w = chain_block_width<Args>(t->host.n);
+    LDS_LIMIT(chain_kernel<Args>(w), w == 32 ? chain_lds_bytes<Args>(chain_wide_joints<Args>(), 32) : chain_lds_bytes<Args>(MAXJ, w));
+    return NMPC_OK;
+}
+template <class... Args>
+int chain_lds_limits(Torque* t, ArgsList<Args...>) {
+    int rc = NMPC_OK;
+    ((rc = rc ? rc : chain_lds_limit<Args>(t)), ...);
+    return rc;
+}
+
 // the device side of nmpc_torque_create, on the handle's device; what was allocated before an error is nmpc_torque_destroy's to free
 int allocate(Torque* t) {
     NMPC_TRY(no_handle, hipMalloc(reinterpret_cast<void**>(&t->dev), sizeof(Model)));
@@ -464,24 +474,15 @@ int allocate(Torque* t) {
     // robots, 32 joints x 16)
     LDS_LIMIT(id_torques_kernel, id_lds_bytes(MAXJ));
     LDS_LIMIT(KERNEL_AT_WIDTH(fd_kernel, t->fd_width), t->fd_width == 32 ? fd_lds_bytes(25, 32) : fd_lds_bytes(MAXJ, 16));
-    // the contact plant: the kinematics slice of the largest tree, and for the step, the tracked chain of steps and the pushed substeps
-    // of either the most an instantiation can be asked for by the step's width rule (ct_block_width: ct_wide_joints() joints x 32
-    // robots, the largest tree x 16)
+    // the contact plant: the kinematics slice of the largest tree, for the step the most its instantiation can be asked for by its
+    // width rule (ct_block_width: ct_wide_joints() joints x 32 robots, the largest tree x 16), and for the chains the same by theirs
     LDS_LIMIT(foot_kernel<FootArgs>, fk_lds_bytes(MAXJ));
     LDS_LIMIT(foot_kernel<FootRowsArgs>, fk_lds_bytes(MAXJ));
-    const size_t ct_lds = t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16);
-    LDS_LIMIT(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width), ct_lds);
-    LDS_LIMIT(chain_kernel<TrackArgs>(t->ct_width), ct_lds);
-    LDS_LIMIT(chain_kernel<PushArgs>(t->ct_width), ct_lds);
-    LDS_LIMIT(chain_kernel<WindowArgs>(t->ct_width), ct_lds);
-    LDS_LIMIT(chain_kernel<GroundsArgs>(t->gr_width), t->gr_width == 32 ? ct_lds_bytes(ct_grounds_wide_joints(), 32, 32) : ct_lds_bytes(MAXJ, 16, 16));
-    // the composite-inertia pass, the implicit chain (slice and triangle) and the three entry points of the centroidal kernel:
-    // the slice of the largest tree at the one width each has
+    LDS_LIMIT(KERNEL_AT_WIDTH(contact_step_kernel, t->ct_width), t->ct_width == 32 ? ct_lds_bytes(ct_wide_joints(), 32) : ct_lds_bytes(MAXJ, 16));
+    if (const int rc = chain_lds_limits(t, ChainArgs{})) return rc;
+    // the composite-inertia pass and the three entry points of the centroidal kernel: the slice of the largest tree at the one
+    // width each has
     LDS_LIMIT(crba_kernel, crba_lds_bytes(MAXJ, CR_W));
-    LDS_LIMIT(chain_kernel<ImplicitArgs>(IM_W), im_lds_bytes(MAXJ));
-    LDS_LIMIT(chain_kernel<ImplicitGroundsArgs>(IM_W), im_lds_bytes(MAXJ, IM_W));
-    LDS_LIMIT(chain_kernel<PayloadsArgs>(t->pl_width), t->pl_width == 32 ? ct_payloads_lds_bytes(ct_payloads_wide_joints(), 32) : ct_payloads_lds_bytes(MAXJ, 16));
-    LDS_LIMIT(chain_kernel<ImplicitPayloadsArgs>(IM_W), im_payloads_lds_bytes(MAXJ));
     LDS_LIMIT(centroidal_kernel<CmdIo>, centroidal_lds_bytes<CmdIo>(MAXJ));
     LDS_LIMIT(centroidal_kernel<NodeRecordIo>, centroidal_lds_bytes<NodeRecordIo>(MAXJ));
     LDS_LIMIT(centroidal_kernel<StateMomentumIo>, centroidal_lds_bytes<StateMomentumIo>(MAXJ));
@@ -551,15 +552,12 @@ const char* observe_refusal(const Torque* t, int B, const float* q, const float*
 
 // the kinematics pass, with or without the law; with the law of the attached table of grounds if there is one
 int launch_feet(Torque* t, const FootArgs& a, void* stream) {
-    if (a.f && t->grounds.rows) {
-        FootRowsArgs r{};
-        static_cast<FootArgs&>(r) = a;
-        r.rows = t->grounds.rows;
-        return launch_step(t, foot_kernel<FootRowsArgs>, TPB, fk_lds_bytes(t->host.n), r, stream);
-    }
-    hipLaunchKernelGGL(foot_kernel<FootArgs>, dim3((unsigned)((a.B + TPB - 1) / TPB)), dim3(TPB), fk_lds_bytes(t->host.n),
-                       static_cast<hipStream_t>(stream), t->dev, a);
-    return launched(t);
+    const size_t lds = fk_lds_bytes(t->host.n);
+    if (!a.f || !t->grounds.rows) return launch_step(t, foot_kernel<FootArgs>, TPB, lds, a, stream);
+    FootRowsArgs r{};
+    static_cast<FootArgs&>(r) = a;
+    r.rows = t->grounds.rows;
+    return launch_step(t, foot_kernel<FootRowsArgs>, TPB, lds, r, stream);
 }
 
 // why a push cannot be attached to a tree of n_joints joints (nullptr: it can)
@@ -583,27 +581,23 @@ Window push_window(const nmpc_push_cfg& push, long long s0, long long total) {
     return w;
 }
 
-// why `push` and the windows per robot cannot serve a plant call of B robots (nullptr: they can, or there are none)
-const char* push_batch_refusal(const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, int B) {
-    if (push.force && B > push.force_rows) return "push: B exceeds force_rows";
-    if (!wins.first) return nullptr;
-    if (!push.force) return "push windows: no push is attached (nmpc_contact_set_push)";
-    if (B > wins.rows) return "push windows: B exceeds rows";
-    return nullptr;
-}
-
-// why the attached table of grounds cannot serve a plant call of B robots (nullptr: it can, or there is none)
+// why the attached table of grounds cannot serve a call of B robots (nullptr: it can, or there is none)
 const char* grounds_batch_refusal(const Torque* t, int B) {
     return t->grounds.rows && B > t->grounds.n_rows ? "grounds: B exceeds n_rows" : nullptr;
 }
 
-// why the attached table of payloads cannot serve a plant call of B robots (nullptr: it can, or there is none)
-const char* payloads_batch_refusal(const Torque* t, int B) {
+// why `push`, the windows per robot and the attached tables cannot serve a plant call of B robots (nullptr: they can, or there are none)
+const char* plant_batch_refusal(const Torque* t, const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, int B) {
+    if (push.force && B > push.force_rows) return "push: B exceeds force_rows";
+    if (wins.first && !push.force) return "push windows: no push is attached (nmpc_contact_set_push)";
+    if (wins.first && B > wins.rows) return "push windows: B exceeds rows";
+    if (const char* why = grounds_batch_refusal(t, B)) return why;
     return t->payloads.rows && B > t->payloads.n_rows ? "payloads: B exceeds n_rows" : nullptr;
 }
 
-// A plant call under a push is cut into runs of substeps that are all un-pushed -- launches of the un-pushed kernels, as a call
-// without a push makes them -- and runs that are all pushed, launches of the PushArgs chain (nmpc_torque_track.hip.inc says why).
+// A plant call that launch_whole below does not take is cut into runs of substeps that are all un-pushed -- launches of the
+// un-pushed kernels, as a call without a push makes them -- and runs that are all pushed, launches of the PushArgs chain
+// (nmpc_torque_track.hip.inc says why).
 
 // why the implicit integrator cannot run a tree of n joints (nullptr: it can)
 const char* implicit_refusal(int n) {
@@ -621,17 +615,16 @@ PushArgs chain_args(int B, int n_steps, int n_sub, float dt, const nmpc_contact_
     return p;
 }
 
-// a plant call under the implicit integrator: one launch of the ImplicitArgs chain, the push window -- the push's own, or with
-// `wins` the robot's, in a call whose substep 0 is substep s0 of their count -- tested inside it.  And a plant call of either
-// integrator under a table of grounds (Args: ImplicitGroundsArgs, GroundsArgs) or of payloads (ImplicitPayloadsArgs, PayloadsArgs),
-// which state their push the same way; under payloads the table of grounds may be absent (rows == nullptr: the call's own law).
-template <class Args = ImplicitArgs>
-int launch_implicit(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins,
-                    long long s0, void* stream) {
+// one launch of a chain that is told its push -- the window `win` of the push's own, or with `wins` the robot's, in a call whose
+// substep 0 is substep s0 of their count -- and tests it per substep: the implicit chain, and either integrator under a table of
+// grounds or of payloads; under payloads the table of grounds may be absent (rows == nullptr: the call's own law).
+template <class Args>
+int launch_stated(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins,
+                  long long s0, void* stream) {
     Args p{};
     static_cast<PushArgs&>(p) = call;
     if constexpr (Args::grounds) p.rows = t->grounds.rows;
-    if constexpr (Args::payloads) { p.payload_rows = t->payloads.rows; p.payload_joint = t->payloads.joint; }
+    if constexpr (Args::payloads) { p.payload_rows = t->payloads.rows; p.payload_joint = t->payload_joint; }
     if (win.hi > win.lo) { p.force = push.force; p.joint = push.joint; p.push_lo = win.lo; p.push_hi = win.hi; }
     if (wins.first) { p.force = push.force; p.joint = push.joint; p.win_first = wins.first; p.win_count = wins.count; p.win_s0 = s0; }
     return launch_chain(t, p, stream);
@@ -644,10 +637,28 @@ int launch_windowed(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, 
     return launch_chain(t, p, stream);
 }
 
-// nmpc_contact_step_batch under an explicit push: the call's substep i is substep s0 + i of the count `push` is stated in.
-// At most three launches: before, inside and after the window; the first reads q, v, the later ones go on in place on q_out,
-// v_out, and the last one writes a_out, f_out, tau_out.  With windows per robot (`wins`, stated in the same count): one launch of
-// the windowed chain, or of the implicit one.
+// Does a plant call run as one launch, and of which instantiation?  It does under a table of payloads (whatever the push and the
+// grounds), under a table of grounds (whatever the push), under the implicit integrator and under windows per robot: then that
+// launch is made, rc is its result and the answer is true.  Otherwise nothing is launched: the caller cuts the call at the window.
+bool launch_whole(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins,
+                  long long s0, void* stream, int& rc) {
+    const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
+    if (t->payloads.rows)
+        rc = implicit ? launch_stated<ImplicitPayloadsArgs>(t, call, push, win, wins, s0, stream) : launch_stated<PayloadsArgs>(t, call, push, win, wins, s0, stream);
+    else if (t->grounds.rows)
+        rc = implicit ? launch_stated<ImplicitGroundsArgs>(t, call, push, win, wins, s0, stream) : launch_stated<GroundsArgs>(t, call, push, win, wins, s0, stream);
+    else if (implicit)
+        rc = launch_stated<ImplicitArgs>(t, call, push, win, wins, s0, stream);
+    else if (wins.first)
+        rc = launch_windowed(t, call, push, wins, s0, stream);
+    else
+        return false;
+    return true;
+}
+
+// nmpc_contact_step_batch: the call's substep i is substep s0 + i of the count `push` and `wins` are stated in.  One launch where
+// launch_whole makes it; else, under an explicit push, at most three: before, inside and after the window; the first reads q, v,
+// the later ones go on in place on q_out, v_out, and the last one writes a_out, f_out, tau_out.
 int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* cfg, const float* q, const float* v, const float* tau_ff,
                  const float* q_des, float kp, float kd, float* q_out, float* v_out, float* a_out, float* f_out, float* tau_out,
                  const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, long long s0, void* stream) {
@@ -655,22 +666,12 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
     if (B < 0 || !q || !v || !q_out || !v_out) return fail(t, NMPC_E_ARG, "need B >= 0 and q, v, q_out, v_out");
     if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = push_batch_refusal(push, wins, B)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = payloads_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = plant_batch_refusal(t, push, wins, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     const Window win = wins.first ? Window{} : push_window(push, s0, n_sub);
     PushArgs call = chain_args(B, 1, n_sub, dt, *cfg, tau_ff, q_des, 1, kp, kd, q_out, v_out);
     call.q_in = q; call.v_in = v; call.a_out = a_out; call.f_out = f_out; call.tau_out = tau_out;
-    const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
-    if (t->payloads.rows)                        // a payload per robot: one launch whatever the push and the grounds
-        return implicit ? launch_implicit<ImplicitPayloadsArgs>(t, call, push, win, wins, s0, stream)
-                        : launch_implicit<PayloadsArgs>(t, call, push, win, wins, s0, stream);
-    if (t->grounds.rows)                         // a law per robot: one launch whatever the push
-        return implicit ? launch_implicit<ImplicitGroundsArgs>(t, call, push, win, wins, s0, stream)
-                        : launch_implicit<GroundsArgs>(t, call, push, win, wins, s0, stream);
-    if (implicit) return launch_implicit(t, call, push, win, wins, s0, stream);
-    if (wins.first) return launch_windowed(t, call, push, wins, s0, stream);
+    if (int rc; launch_whole(t, call, push, win, wins, s0, stream, rc)) return rc;
     const int cuts[4] = {0, (int)win.lo, (int)win.hi, n_sub};
     bool first = true;
     for (int r = 0; r < 3; ++r) {
@@ -696,9 +697,9 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
     return NMPC_OK;
 }
 
-// nmpc_contact_track_batch under an explicit push, in substeps s = k * n_sub + i of the call.  Whole control steps of one kind
-// go into one launch; a control step the window starts or ends in is cut at that substep, and only its first piece writes its row
-// of Q, V.  With windows per robot (`wins`), in a call whose substep 0 is substep s0 of their count: one launch, as the step.
+// nmpc_contact_track_batch, in substeps s = k * n_sub + i of the call, substep 0 being substep s0 of the count `wins` are stated in.
+// One launch where launch_whole makes it; else, under an explicit push, whole control steps of one kind go into one launch, a
+// control step the window starts or ends in is cut at that substep, and only its first piece writes its row of Q, V.
 int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v, const float* tau_ff,
                   const float* A, int a_rows, float kp, float kd, float* Q, float* V, int qv_rows, const int* skip, int skip_mask,
                   const nmpc_push_cfg& push, const nmpc_torque::PushWindows& wins, long long s0, void* stream) {
@@ -713,33 +714,23 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
     if (Q && qv_rows < n_steps) return fail(t, NMPC_E_ARG, "qv_rows must be at least n_steps");
     if (Q && !whole_body_tree(t->host))
         return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
-    if (const char* why = push_batch_refusal(push, wins, B)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = payloads_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = plant_batch_refusal(t, push, wins, B)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
     const int n = t->host.n, nu = t->host.nu;
     const long long total = (long long)n_steps * n_sub;
     const Window win = wins.first ? Window{} : push_window(push, 0, total);
     PushArgs call = chain_args(B, n_steps, n_sub, dt, *cfg, tau_ff, A, a_rows, kp, kd, q, v);
     call.qv_rows = qv_rows; call.skip_mask = skip ? skip_mask : 0; call.skip = call.skip_mask ? skip : nullptr;
-    const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
-    if (implicit || wins.first || t->grounds.rows || t->payloads.rows) {      // one launch for the whole table; the cut path below moves A, Q, V piece by piece
-        call.Q = Q; call.V = V;
-        if (t->payloads.rows)
-            return implicit ? launch_implicit<ImplicitPayloadsArgs>(t, call, push, win, wins, s0, stream)
-                            : launch_implicit<PayloadsArgs>(t, call, push, win, wins, s0, stream);
-        if (t->grounds.rows)
-            return implicit ? launch_implicit<ImplicitGroundsArgs>(t, call, push, win, wins, s0, stream)
-                            : launch_implicit<GroundsArgs>(t, call, push, win, wins, s0, stream);
-        return implicit ? launch_implicit(t, call, push, win, wins, s0, stream) : launch_windowed(t, call, push, wins, s0, stream);
-    }
+    call.Q = Q; call.V = V;                      // one launch takes the whole table; the cut path below moves A, Q, V piece by piece
+    if (int rc; launch_whole(t, call, push, win, wins, s0, stream, rc)) return rc;
     for (long long s = 0; s < total;) {
         const bool pushed = s >= win.lo && s < win.hi;
         const long long change = s < win.lo ? win.lo : (s < win.hi ? win.hi : total);      // where the kind of substep changes next
         const long long k = s / n_sub, i0 = s % n_sub, step_end = (k + 1) * n_sub;
         PushArgs p = call;
         p.A = A + (size_t)k * nu;
-        if (Q && i0 == 0) { p.Q = Q + (size_t)k * n; p.V = V + (size_t)k * n; }
+        p.Q = Q && i0 == 0 ? Q + (size_t)k * n : nullptr;
+        p.V = Q && i0 == 0 ? V + (size_t)k * n : nullptr;
         if (i0 != 0 || change < step_end) {      // a piece of control step k
             const long long end = change < step_end ? change : step_end;
             p.n_steps = 1; p.n_sub = (int)(end - s);
@@ -862,8 +853,6 @@ int nmpc_torque_create(const nmpc_tree_model* mdl, int device_id, void** handle)
     t->host = m; t->device = device_id;
     t->fd_width = fd_block_width(m.n);
     t->ct_width = ct_block_width(m.n);
-    t->gr_width = ct_grounds_block_width(m.n);
-    t->pl_width = ct_payloads_block_width(m.n);
     for (int i = m.n - 1; i >= 0; --i)
         if (m.mass[i] > 0.0f) t->anchor = i;
     for (int k = t->anchor; k >= 0; k = m.parent[k]) t->chain |= 1u << k;
@@ -1034,7 +1023,7 @@ int nmpc_contact_set_grounds(void* torque, const float* rows, int n_rows) {
     if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
     if (rows && n_rows < 1) return fail(t, NMPC_E_ARG, "grounds: n_rows must be at least 1");      // what was attached stays
     t->grounds = {};
-    if (rows) { t->grounds.rows = rows; t->grounds.n_rows = n_rows; }
+    if (rows) t->grounds = {rows, n_rows};
     return NMPC_OK;
 }
 
@@ -1046,7 +1035,7 @@ int nmpc_contact_set_payloads(void* torque, const float* rows, int n_rows, int j
         if (joint < 0 || joint >= t->host.n) return fail(t, NMPC_E_ARG, "payloads: joint must be in [0, n_joints)");
     }
     t->payloads = {};
-    if (rows) { t->payloads.rows = rows; t->payloads.n_rows = n_rows; t->payloads.joint = joint; }
+    if (rows) { t->payloads = {rows, n_rows}; t->payload_joint = joint; }
     return NMPC_OK;
 }
 
@@ -1141,9 +1130,7 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     const auto& rec = t->states;
     if (!rec.Q != !rec.V) return fail(t, NMPC_E_ARG, "states: Q and V come together or not at all");
     if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
-    if (const char* why = push_batch_refusal(t->push, t->windows, B)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = grounds_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
-    if (const char* why = payloads_batch_refusal(t, B)) return fail(t, NMPC_E_ARG, why);
+    if (const char* why = plant_batch_refusal(t, t->push, t->windows, B)) return fail(t, NMPC_E_ARG, why);
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
         NMPC_ENTER(t, t->device);

@@ -114,23 +114,14 @@ __global__ __launch_bounds__(TPB) void foot_kernel(const Model* __restrict__ mp,
 constexpr int CT_SLOTS = FD_SLOTS + 3;                    // the slice of fd_accel_body and FD_PW, the world position of the body origin
 // the slice, and behind it the parameters of the law: six uniform values that would otherwise live in scalar registers across
 // the whole recursion, which fills the scalar file on its own (they cost 13 SGPR spills there)
-// (`laws`: how many; under a table of grounds every lane has its own, a slot of six words per lane -- 32 lanes at a stride of 6
-// words fall on 32 different banks)
-constexpr size_t ct_lds_bytes(int n, int width, int laws = 1) { return (size_t)n * CT_SLOTS * width * sizeof(float) + laws * sizeof(ContactCfg); }
+constexpr size_t ct_lds_bytes(int n, int width) { return (size_t)n * CT_SLOTS * width * sizeof(float) + sizeof(ContactCfg); }
 // robots per block: 32 where the slice of n joints fits the CU (n <= 23), 16 otherwise (32 joints: 110 616 B)
 constexpr int ct_block_width(int n) { return ct_lds_bytes(n, 32) <= FD_LDS_MAX ? 32 : 16; }
-// and under a table of grounds, by the same rule on the larger footprint (23 joints x 32 robots: 159 744 B, still inside)
-constexpr int ct_grounds_block_width(int n) { return ct_lds_bytes(n, 32, 32) <= FD_LDS_MAX ? 32 : 16; }
-static_assert(ct_lds_bytes(MAXJ, 16, 16) <= FD_LDS_MAX, "the slice of the largest tree and a law per lane no longer fit a CU at 16 robots per block");
+static_assert(ct_lds_bytes(MAXJ, 16) == 110616, "the contact step of the largest tree at 16 robots per block");
 // the largest tree that runs at 32 robots per block: its slice is the most contact_step_kernel<32> can be asked for
 constexpr int ct_wide_joints() {
     int n = MAXJ;
     while (n > 1 && ct_block_width(n) != 32) --n;
-    return n;
-}
-constexpr int ct_grounds_wide_joints() {
-    int n = MAXJ;
-    while (n > 1 && ct_grounds_block_width(n) != 32) --n;
     return n;
 }
 
@@ -162,23 +153,12 @@ struct PushedGroundForces : GroundForces {
 struct Payload {
     float mass, x, y, z;
 };
-// what a lane of the payload chains keeps behind the slice: its law and, beside it, its payload (ten words: the 32 lanes of a
-// block at that stride fall on 32 different banks of 64)
+// what a lane of the payload chains keeps behind the slice (nmpc_torque_track.hip.inc has the footprint): its law and, beside it,
+// its payload (ten words: the 32 lanes of a block at that stride fall on 32 different banks of 64)
 struct LaneLoad {
     ContactCfg c;
     Payload load;
 };
-// the footprint and the block width of the explicit chain under a table of payloads, by the rule of the grounds on the larger slot
-// (23 joints x 32 robots: 160 256 B, still inside)
-constexpr size_t ct_payloads_lds_bytes(int n, int width) { return (size_t)n * CT_SLOTS * width * sizeof(float) + width * sizeof(LaneLoad); }
-constexpr int ct_payloads_block_width(int n) { return ct_payloads_lds_bytes(n, 32) <= FD_LDS_MAX ? 32 : 16; }
-static_assert(ct_payloads_lds_bytes(MAXJ, 16) <= FD_LDS_MAX, "the slice of the largest tree, a law and a payload per lane no longer fit a CU at 16 robots per block");
-constexpr int ct_payloads_wide_joints() {
-    int n = MAXJ;
-    while (n > 1 && ct_payloads_block_width(n) != 32) --n;
-    return n;
-}
-
 // a force source of the plant under the lane's payload on body `on`: the hook of fd_accel_body reads the four words where they lie
 template <class Source>
 struct Loaded : Source {

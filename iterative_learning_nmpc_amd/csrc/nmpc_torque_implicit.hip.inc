@@ -20,12 +20,8 @@ constexpr int IM_W = 16;                                  // robots per block: t
 constexpr int IM_J = FD_P;                                // column i of the foot Jacobian in world axes 3 (p^A is spent after the recursion)
 constexpr int IM_R = FD_P + 3;                            // rhs_i, then the solution a_i
 constexpr size_t im_triangle(int n) { return (size_t)n * (n + 1) / 2; }
-// the slice, the triangle, and behind it the law: one for the block, or IM_W of them under a table of grounds (a law per lane)
-constexpr size_t im_lds_bytes(int n, int laws = 1) { return ((size_t)n * CT_SLOTS + im_triangle(n)) * IM_W * sizeof(float) + laws * sizeof(ContactCfg); }
-static_assert(im_lds_bytes(MAXJ, IM_W) <= FD_LDS_MAX, "the implicit slice of the largest tree no longer fits a CU at 16 robots per block");
-// and under a table of payloads: a law and a payload per lane behind the triangle
-constexpr size_t im_payloads_lds_bytes(int n) { return ((size_t)n * CT_SLOTS + im_triangle(n)) * IM_W * sizeof(float) + IM_W * sizeof(LaneLoad); }
-static_assert(im_payloads_lds_bytes(MAXJ) <= FD_LDS_MAX, "the implicit slice of the largest tree, a law and a payload per lane no longer fit a CU");
+// the slice, the triangle, and behind it the block's law (the chains with a slot per lane: chain_lds_bytes, nmpc_torque_track.hip.inc)
+constexpr size_t im_lds_bytes(int n) { return ((size_t)n * CT_SLOTS + im_triangle(n)) * IM_W * sizeof(float) + sizeof(ContactCfg); }
 
 // no payload: what implicit_accel_body is given by a chain without one
 struct NoLoad {

@@ -14,6 +14,8 @@
 
 // ---- the arguments of the chain, one struct per instantiation of contact_chain_kernel ---------------------------------------------
 // What a struct's constants switch in the kernel is stated there; the kernel reads nothing of a struct that its constants rule out.
+// Slot and lane_slots name what lies behind the slice (under the implicit integrator behind the triangle): one Slot for the block,
+// or one per lane; the footprint, the block width and the launch follow from them (chain_lds_bytes below).
 enum class Forces {
     ground,                                               // GroundForces in every substep
     pushed,                                               // PushedGroundForces in every substep
@@ -23,8 +25,9 @@ enum class Forces {
 
 // The un-pushed track: the state in q, v goes through n_steps control steps, in place.
 struct TrackArgs {
-    static constexpr bool step_io = false, implicit = false, grounds = false, payloads = false;
+    static constexpr bool step_io = false, implicit = false, grounds = false, payloads = false, lane_slots = false;
     static constexpr Forces forces = Forces::ground;
+    using Slot = ContactCfg;                              // the block's law
     int B, n_steps, n_sub, a_rows, qv_rows, skip_mask;
     float dt, kp, kd;
     ContactCfg c;
@@ -86,7 +89,7 @@ struct ImplicitArgs : PushArgs {                          // force == nullptr: n
 // two inlined recursions of WindowArgs, for the reason stated there: robot b is then the bits of the uniform launches under its
 // own row (tests/test_gpu_grounds.py).
 struct ImplicitGroundsArgs : ImplicitArgs {
-    static constexpr bool grounds = true;
+    static constexpr bool grounds = true, lane_slots = true;      // the lane's law
     const float* rows;                                    // [>= B][6] in the field order of nmpc_contact_cfg
 };
 struct GroundsArgs : ImplicitGroundsArgs {
@@ -102,6 +105,7 @@ struct GroundsArgs : ImplicitGroundsArgs {
 // launch per call, the push stated and taken as under a table of grounds.
 struct ImplicitPayloadsArgs : ImplicitGroundsArgs {
     static constexpr bool payloads = true;
+    using Slot = LaneLoad;                                // the lane's law and its payload
     const float* payload_rows;                            // [>= B][4]: m_p, r_x, r_y, r_z
     int payload_joint;
 };
@@ -109,6 +113,39 @@ struct PayloadsArgs : ImplicitPayloadsArgs {
     static constexpr bool implicit = false;
     static constexpr Forces forces = Forces::either;
 };
+
+// ---- the footprint of an instantiation ------------------------------------------------------------------------------------------
+template <class... Args>
+struct ArgsList {};
+using ChainArgs = ArgsList<TrackArgs, PushArgs, WindowArgs, ImplicitArgs, GroundsArgs, ImplicitGroundsArgs, PayloadsArgs, ImplicitPayloadsArgs>;
+
+// the LDS of a block of w robots of n joints: the slice, the triangle if implicit, then one slot or a slot per lane (six words
+// per lane fall on 32 different banks, as the ten of a LaneLoad do)
+template <class Args>
+constexpr size_t chain_lds_bytes(int n, int w) {
+    return ((size_t)n * CT_SLOTS + (Args::implicit ? im_triangle(n) : 0)) * w * sizeof(float) + (Args::lane_slots ? w : 1) * sizeof(typename Args::Slot);
+}
+// robots per block: the implicit chain's one width, else 32 where that footprint fits the CU and 16 otherwise
+template <class Args>
+constexpr int chain_block_width(int n) { return Args::implicit ? IM_W : (chain_lds_bytes<Args>(n, 32) <= FD_LDS_MAX ? 32 : 16); }
+// the largest tree that runs at 32 robots per block: its footprint is the most the 32-wide instantiation can be asked for
+template <class Args>
+constexpr int chain_wide_joints() {
+    int n = MAXJ;
+    while (n > 1 && chain_block_width<Args>(n) != 32) --n;
+    return n;
+}
+// the chains that the cut path alternates with contact_step_kernel run at its width
+template <class Args>
+constexpr bool chain_steps_width() {
+    for (int n = 1; n <= MAXJ; ++n)
+        if (chain_block_width<Args>(n) != ct_block_width(n)) return false;
+    return true;
+}
+static_assert(chain_steps_width<TrackArgs>() && chain_steps_width<PushArgs>() && chain_steps_width<WindowArgs>(),
+              "a chain of the cut path no longer runs at the width of contact_step_kernel");
+static_assert(chain_lds_bytes<GroundsArgs>(23, 32) == 159744 && chain_wide_joints<GroundsArgs>() == 23, "a law per lane: 23 joints x 32 robots");
+static_assert(chain_lds_bytes<PayloadsArgs>(23, 32) == 160256 && chain_wide_joints<PayloadsArgs>() == 23, "a law and a payload per lane: 23 joints x 32 robots");
 
 // ---- the chain ------------------------------------------------------------------------------------------------------------------
 // contact_step_kernel's substep, n_steps * n_sub times on the state in the slice: per control step the state goes out to row k

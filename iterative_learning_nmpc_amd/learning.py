@@ -128,12 +128,26 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
     if n_steps < 1:
         raise ValueError(f"T = {T} s is shorter than one control step of {n_sub} x {dt} s")
-    if push is not None and layer._push is not None:
-        raise ValueError("push: the layer has a push attached already (set_push)")
-    if grounds is not None and layer._grounds is not None:
-        raise ValueError("grounds: the layer has a table of grounds attached already (set_grounds)")
-    if payloads is not None and layer._payloads is not None:
-        raise ValueError("payloads: the layer has a table of payloads attached already (set_payloads)")
+
+    def set_push(push):
+        if push is None:
+            return layer.set_push(None)
+        force = torch.as_tensor(push["force"], dtype=torch.float32, device=layer.device).reshape(-1, 3)
+        windows = push_windows(push, force.shape[0])
+        if windows is None:
+            layer.set_push(force, start_substep=int(round(float(push["start"]) / float(dt))),
+                           n_substeps=int(round(float(push["duration"]) / float(dt))))
+        else:                                             # a window per robot, each converted as the scalar one is
+            first, count = ([int(round(float(t) / float(dt))) for t in w] for w in windows)
+            layer.set_push(force, start_substep=first, n_substeps=count)
+
+    # what this call attaches to the layer and takes off again: (name, value, what the layer has attached, setter, in words)
+    parts = [part for part in (("push", push, layer._push, set_push, "a push"),
+                               ("grounds", grounds, layer._grounds, layer.set_grounds, "a table of grounds"),
+                               ("payloads", payloads, layer._payloads, layer.set_payloads, "a table of payloads")) if part[1] is not None]
+    for name, _, attached, _, what in parts:
+        if attached is not None:
+            raise ValueError(f"{name}: the layer has {what} attached already (set_{name})")
     states = {}
     if record_states:
         B = torch.as_tensor(q0).reshape(-1, layer.n).shape[0]
@@ -142,30 +156,15 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     try:
         if integrator is not None:
             layer.set_integrator(integrator)
-        if grounds is not None:
-            layer.set_grounds(grounds)
-        if payloads is not None:
-            layer.set_payloads(payloads)
-        if push is not None:
-            force = torch.as_tensor(push["force"], dtype=torch.float32, device=layer.device).reshape(-1, 3)
-            windows = push_windows(push, force.shape[0])
-            if windows is None:
-                layer.set_push(force, start_substep=int(round(float(push["start"]) / float(dt))),
-                               n_substeps=int(round(float(push["duration"]) / float(dt))))
-            else:                                         # a window per robot, each converted as the scalar one is
-                first, count = ([int(round(float(t) / float(dt))) for t in w] for w in windows)
-                layer.set_push(force, start_substep=first, n_substeps=count)
+        for _, value, _, setter, _ in sorted(parts, key=lambda part: part[0] == "push"):      # the tables, then the push
+            setter(value)
         q, v, S, A, failed = layer.policy_rollout(policy, q0, v0, n_steps, dt, n_sub, goal, tau_ff=tau_ff, kp=kp, kd=kd,
                                                   ground=GroundContact() if ground is None else ground, t0=t0,
                                                   period=NOMINAL_PERIOD if period is None else period, db=db,
                                                   terminate_mask=terminate_mask, collision_height=collision_height)
     finally:
-        if push is not None:
-            layer.set_push(None)
-        if grounds is not None:
-            layer.set_grounds(None)
-        if payloads is not None:
-            layer.set_payloads(None)
+        for _, _, _, setter, _ in parts:
+            setter(None)
         if record_states:
             layer.set_rollout_states(None)
     stamp = failed >> NMPC_ROLLOUT_TERM_SHIFT

@@ -543,16 +543,20 @@ class BatchedTorqueLayer:
             self._grounds = None
             _lib.check(self.lib.nmpc_contact_set_grounds(self._h, None, 0), self._h, "nmpc_contact_set_grounds", "torque")
             return
-        if isinstance(grounds, torch.Tensor) and grounds.is_cuda:
-            if grounds.dtype != torch.float32 or grounds.dim() != 2 or grounds.shape[1] != len(GROUND_COLUMNS) or grounds.shape[0] < 1 \
-                    or grounds.device != self.device:
-                raise ValueError(f"grounds: a device table must be float32 [B, {len(GROUND_COLUMNS)}] with B >= 1 on {self.device}")
-            rows = grounds.contiguous()
-        else:
-            host = ground_table(grounds.numpy() if isinstance(grounds, torch.Tensor) else grounds)
-            rows = torch.tensor(host, device=self.device)      # a copy: the caller's array may be read-only
+        rows = self._table(grounds, "grounds", GROUND_COLUMNS, ground_table)
         _lib.check(self.lib.nmpc_contact_set_grounds(self._h, ptr(rows), rows.shape[0]), self._h, "nmpc_contact_set_grounds", "torque")
         self._grounds = rows
+
+    def _table(self, table, name, columns, validate):
+        """the rows of a table per robot on the device: a device tensor is checked against `columns` and taken as given, host
+        input goes through `validate` and is uploaded; the caller keeps the rows alive while they are attached"""
+        if isinstance(table, torch.Tensor) and table.is_cuda:
+            if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != len(columns) or table.shape[0] < 1 \
+                    or table.device != self.device:
+                raise ValueError(f"{name}: a device table must be float32 [B, {len(columns)}] with B >= 1 on {self.device}")
+            return table.contiguous()
+        host = validate(table.numpy() if isinstance(table, torch.Tensor) else table)
+        return torch.tensor(host, device=self.device)      # a copy: the caller's array may be read-only
 
     def set_payloads(self, payloads=None, joint: Optional[int] = None):
         """nmpc_contact_set_payloads: a point-mass payload of its own per robot.  payloads: a float array or tensor [B, 4] in the
@@ -571,14 +575,7 @@ class BatchedTorqueLayer:
             self._payloads = None
             _lib.check(self.lib.nmpc_contact_set_payloads(self._h, None, 0, 0), self._h, "nmpc_contact_set_payloads", "torque")
             return
-        if isinstance(payloads, torch.Tensor) and payloads.is_cuda:
-            if payloads.dtype != torch.float32 or payloads.dim() != 2 or payloads.shape[1] != len(PAYLOAD_COLUMNS) or payloads.shape[0] < 1 \
-                    or payloads.device != self.device:
-                raise ValueError(f"payloads: a device table must be float32 [B, {len(PAYLOAD_COLUMNS)}] with B >= 1 on {self.device}")
-            rows = payloads.contiguous()
-        else:
-            host = payload_table(payloads.numpy() if isinstance(payloads, torch.Tensor) else payloads)
-            rows = torch.tensor(host, device=self.device)      # a copy: the caller's array may be read-only
+        rows = self._table(payloads, "payloads", PAYLOAD_COLUMNS, payload_table)
         joint = self.n - self.nu - 1 if joint is None else int(joint)
         _lib.check(self.lib.nmpc_contact_set_payloads(self._h, ptr(rows), rows.shape[0], joint), self._h, "nmpc_contact_set_payloads", "torque")
         self._payloads = rows

@@ -197,7 +197,8 @@ def torque_digests():
     """One digest per entry point of include/nmpc_torque.h (`nmpc_plan_actions_batch` is under roll_wb_steps_labels) on the states
     of the layer's own GPU tests, B = 257 (eight blocks and one lane), 33 and 40 (a full and a ragged block at either width);
     `_w16`: the 16-robot instantiations, on the 30-joint tree; the plant calls also pushed, under windows per robot and under the
-    implicit integrator (`plant`).  The un-pushed step and track once more at B = 17 (`_b17_w16`), the step written over its own
+    implicit integrator (`plant`), and all of those, `contact_forces` and the policy rollout under a table of grounds, of payloads
+    and of both.  The un-pushed step and track once more at B = 17 (`_b17_w16`), the step written over its own
     inputs (`contact_step_in_place`), every output combination of the two observation calls, and the two inverse-dynamics calls
     on the tilted tree.  Prints what is not finite: NaN bytes compare equal and say less."""
     import ctypes
@@ -243,28 +244,37 @@ def torque_digests():
                                               stream(L.device)), L._h, "nmpc_state_momentum_batch", "torque")
         add("state_momentum", rows)
 
-    def plant(L, q, v, tau, g, B, tag, integrators, rows):
+    def plant(L, q, v, tau, g, B, tag, integrators, rows, tables=None):
         """the chains of control steps: `contact_track` (3 control steps of 8 substeps) un-pushed, under a scalar window that
         starts and ends inside control steps and under windows per robot -- the whole call, inside it, none, before the call,
-        running past its end, in turn --, and `contact_step` over the same 24 substeps under both pushes; per integrator"""
+        running past its end, in turn --, and `contact_step` over the same 24 substeps under both pushes; per integrator.
+        tables: {name: (table of grounds or None, table of payloads or None, its joint)} -- the same calls under each of them
+        in place of the calls with nothing attached, the un-pushed step among them, and `contact_forces` where grounds are"""
         rng, nu = np.random.default_rng(B), tau.shape[1]
         A, F = q[:B, None, -nu:] + rng.uniform(-0.1, 0.1, (B, 3, nu)), rng.uniform(-80, 80, (B, 3))
         q, v, tau, A, F = (torch.as_tensor(np.array(x[:B], np.float32), device=L.device).contiguous() for x in (q, v, tau, A, F))
         mix = [(0, 24), (5, 12), (7, 0), (-9, 4), (18, 20)]
         pushes = {"pushed": (5, 12), "windowed": tuple([w[i] for w in (mix * B)[:B]] for i in (0, 1))}
-        for integrator in integrators:
-            L.set_integrator(integrator)
-            name = tag + ("_implicit" if integrator == "implicit" else "")
-            for push, window in ((None, None), *pushes.items()):
-                if push:
-                    L.set_push(F, *window)
-                if push or rows:                          # without rows the un-pushed track is left out (the _w16 form)
-                    out = L.contact_track(q.clone(), v.clone(), A, DT, 8, tau_ff=tau, kp=KP, kd=KD, ground=g, record=rows)
-                    add(f"contact_track{'_' + push if push else ''}{name}", *out[:4 if rows else 2])
-                if push:
-                    add(f"contact_step_{push}{name}", *L.contact_step(q, v, DT, 24, tau_ff=tau, q_des=A[:, 0], kp=KP, kd=KD, ground=g))
-                L.set_push(None)
-            L.set_integrator("explicit")
+        for table, (grounds, payloads, joint) in (tables or {"": (None, None, None)}).items():
+            L.set_grounds(grounds)
+            L.set_payloads(payloads, joint=joint)
+            if grounds is not None and tag == "":
+                add(f"contact_forces_{table}", L.contact_forces(q, v, g))
+            for integrator in integrators:
+                L.set_integrator(integrator)
+                name = ("_" + table if table else "") + tag + ("_implicit" if integrator == "implicit" else "")
+                for push, window in ((None, None), *pushes.items()):
+                    if push:
+                        L.set_push(F, *window)
+                    if push or rows or table:                 # without rows or a table the un-pushed track is left out (the _w16 form)
+                        out = L.contact_track(q.clone(), v.clone(), A, DT, 8, tau_ff=tau, kp=KP, kd=KD, ground=g, record=rows)
+                        add(f"contact_track{'_' + push if push else ''}{name}", *out[:4 if rows else 2])
+                    if push or table:
+                        add(f"contact_step{'_' + push if push else ''}{name}", *L.contact_step(q, v, DT, 24, tau_ff=tau, q_des=A[:, 0], kp=KP, kd=KD, ground=g))
+                    L.set_push(None)
+                L.set_integrator("explicit")
+            L.set_payloads(None)
+            L.set_grounds(None)
 
     w = World()                                           # its Case is the tilted quadruped of tests/test_gpu_contact.py
     for c in (Case(fr.quadruped(), 257, seed=257), w.c):
@@ -283,6 +293,28 @@ def torque_digests():
     add("contact_step_w16", *L.contact_step(q, v, DT, 20, tau_ff=tau, q_des=q, kp=KP, kd=KD, ground=GroundContact(**SOFT)))
     plant(w.L, w.c.q, w.c.v, w.c.tau, ground(w.c.g), 33, "", ("explicit", "implicit"), True)
     plant(L, q, v, tau, GroundContact(**SOFT), 40, "_w16", ("explicit",), False)      # rows need the 18-joint tree
+    # the same calls under a table of grounds, of payloads and of both (the four instantiations a table takes; the explicit two at
+    # both widths): B = 33 on the tilted quadruped from the start states of tests/test_gpu_payloads.py, the lowest foot from 2 cm
+    # above the ground to 2 cm inside it; B = 40 on the 30-joint tree, whose every joint is actuated, the payload on body 4
+    from iterative_learning_nmpc_amd.torque import sample_grounds, sample_payloads
+    from tests.test_gpu_payloads import start_states
+    varied = dict(ground_z=(-0.005, 0.005), mu=(0.3, 1.1), tau_max=(15.0, 40.0))
+    gq = sample_grounds(33, np.random.default_rng(33), base=ground(w.c.g), stiffness=(5e3, 2e4), damping=(1.0, 5.0), **varied)
+    gw = sample_grounds(40, np.random.default_rng(40), base=GroundContact(**SOFT), stiffness=(100.0, 300.0), damping=(0.2, 1.0), **varied)
+    qs, vs = start_states(w.c.m, 33, np.random.default_rng(34))
+    plant(w.L, qs, vs, w.c.tau, ground(w.c.g), 33, "", ("explicit", "implicit"), True,
+          {"grounds": (gq, None, None), "payloads": (None, sample_payloads(33, 33), None), "grounds_payloads": (gq, sample_payloads(33, 35), None)})
+    plant(L, q, v, tau, GroundContact(**SOFT), 40, "_w16", ("explicit",), False,
+          {"grounds": (gw, None, None), "payloads": (None, sample_payloads(40, 40), 4), "grounds_payloads": (gw, sample_payloads(40, 41), 4)})
+    # the policy rollout under the tables: every control step is a `contact_step` of the layer's state
+    for table, (grounds, payloads, push) in {"grounds": (gq, None, False), "payloads": (None, sample_payloads(33, 33), False),
+                                             "grounds_payloads_pushed": (gq, sample_payloads(33, 35), True)}.items():
+        w.L.set_grounds(grounds)
+        w.L.set_payloads(payloads)
+        if push:
+            w.L.set_push(dev(np.random.default_rng(36).uniform(-80, 80, (33, 3))), 5, 12)
+        add("policy_rollout_" + table, *w.rollout(33, 4, 5, 0xFF))
+        w.L.set_push(None); w.L.set_payloads(None); w.L.set_grounds(None)
     # the un-pushed step and track at 16 robots per block on a full block and one lane, and the step over its own inputs
     q17, v17, tau17 = (dev(x[:17]) for x in (q, v, tau))
     soft = GroundContact(**SOFT)
