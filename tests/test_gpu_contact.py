@@ -14,20 +14,13 @@ import pytest
 
 from tests import contact_reference as cr
 from tests import fd_reference as fr
-from tests.torque_helpers import Case, bar, branches, ground, held, host, layer
+from tests.plant_helpers import DT, KD, KP
+from tests.torque_helpers import Case, bar, branches, general_tree_case, ground, held, host, layer
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-KP, KD, DT = 20.0, 1.5, 5e-4
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contact_settle.npz")
-
-
-def general_tree_case(m, B, seed):
-    """A tree whose joint 2 is no lift: the ground goes to the median height of the feet, so feet lie on both sides."""
-    q, v, _, _ = fr.inputs(m, B, seed)
-    z = np.median([cr.feet(m, q[b])[0][:, 2] for b in range(B)])
-    return Case(m, B, seed, cr.Ground(ground_z=float(np.float32(z))))
 
 
 class Cases(dict):

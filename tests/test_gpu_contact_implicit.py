@@ -15,23 +15,20 @@ from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import implicit_reference as ir
 from tests import push_reference as pr
+from tests.plant_helpers import AT, KD, KP, NAMES, device_policy
 from tests.torque_helpers import Case, branches, ground, held, host, layer, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-KP, KD, DT = 20.0, 1.5, 2e-3
+DT = 2e-3                                                 # the substep the implicit scheme is held at here: the other plant files have 0.5 and 1 ms
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "implicit_settle.npz")
-NAMES = ("q", "v", "a", "f", "tau")
 
 
 def implicit_layer(m):
     L = layer(m)
     L.set_integrator("implicit")
     return L
-
-
-AT = 1e-6          # a foot this close to the plane is "at" it: the tolerance `torque_helpers.Case` places its feet with
 
 
 class Run:
@@ -237,7 +234,6 @@ def test_rows_do_not_depend_on_the_batch(chains):
 
 
 def test_the_implicit_policy_rollout_is_the_chain_of_its_calls(chains):
-    from tests.test_gpu_policy_rollout import device_policy
     from oracle.policy_oracle import PolicyOracle
     L, B, K, n_sub, T0, PERIOD = chains.L, 33, 2, 2, 0.37, 0.5
     rng = np.random.default_rng(11)

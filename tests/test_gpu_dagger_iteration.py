@@ -1,34 +1,16 @@
 """`learning.dagger_iteration`: the learner's rollout, the expert's labels for the states it visited, the rows that go into the
 database, and the training on them.  B = 4 robots, T = 5 control steps, an untrained policy, one epoch of batches of 8."""
-import numpy as np
 import pytest
 
-from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.plant_helpers import Dagger
 from tests.solve_helpers import dev, policy_pair  # noqa: F401
 from tests.torque_helpers import same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-B, K, DT, N_SUB = 4, 5, 5e-4, 20
-T = K * N_SUB * DT
-SEED, BATCH = 7, 8
-
-
-def setup(dev, lying=None):
-    from iterative_learning_nmpc_amd import wholebody as wbk
-    from iterative_learning_nmpc_amd.database import DeviceDatabase
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    rng = np.random.default_rng(2)
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B, 12))
-    if lying is not None:
-        q0[lying, 2] = 0.05                               # the trunk below the collision height of 0.08 m
-    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
-    mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
-    goal = np.tile(np.float32([0.2, 0.0, 0.0]), (B, 1))
-    return dict(mpc=mpc, layer=BatchedTorqueLayer(**quadruped_tree(), device=dev), db=DeviceDatabase(limit=256, norm_input=False, device=dev),
-                policy=policy_pair(47, 12, 2, 64, False, 64, seed=3)[0], q0=q0, v0=np.zeros((B, 18)), goal=goal)
+B, K, DT, N_SUB, T, SEED, BATCH = Dagger.B, Dagger.K, Dagger.DT, Dagger.N_SUB, Dagger.T, Dagger.SEED, Dagger.BATCH
+setup = Dagger.setup
 
 
 def run(w):

@@ -15,26 +15,22 @@ import ctypes
 import numpy as np
 import pytest
 
-from iterative_learning_nmpc_amd.workloads import quadruped_tree
 from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import implicit_reference as ir
-from tests.solve_helpers import dev, policy_pair  # noqa: F401
-from tests.torque_helpers import bar, branches, ground, held, host, layer, same  # noqa: F401
+from tests import plant_helpers as ph
+from tests.plant_helpers import AT, DT, DT_IMPLICIT, HEIGHT, INTEGRATORS, KD, KP, MASK, N_SUB, NAMES, PERIOD, STEP_SUB, T0, TRACK_NAMES
+from tests.plant_helpers import World, default_policy, detached, expert, held_row_by_row, quadruped_layer, standing_start  # noqa: F401
+from tests.solve_helpers import dev  # noqa: F401
+from tests.torque_helpers import THREE_HEIGHTS, branches, held, host, layer, lower_feet, rows_equal, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-KP, KD, DT, DT_IMPLICIT = 20.0, 1.5, 5e-4, 1e-3
 DT32 = float(np.float32(DT))
 B, SEED = 33, 7
-K, N_SUB = 3, 2                                           # the track and the policy rollout: 3 control steps of 2 substeps
-STEP_SUB = 4
-PERIOD, T0, HEIGHT, MASK = 0.5, 0.37, 0.08, 2 | 4 | 8 | 32
-INTEGRATORS = ("explicit", "implicit")
+K = ph.ROLLOUT_STEPS                                      # the track and the policy rollout: 3 control steps of N_SUB = 2 substeps
 ROBOTS = (0, 31, 32)                                      # first lane, last lane of a block, the ragged tail
-NAMES = ("q", "v", "a", "f", "tau")
-AT = 1e-6                                                 # tests/test_gpu_contact_implicit.py: a foot this close to its plane is "at" it
 
 
 def rows_to_grounds(rows):
@@ -62,18 +58,12 @@ def draw_rows(rng, n, ground_z, stiffness, damping, clamp):
     return rows
 
 
-class Fixture:
-    """The host side: states, inputs, the table and its references.  Built once, never written to; no device is touched, so the
-    conditions on the fixture can be checked on a machine without one."""
+class Fixture(ph.Fixture):
+    """The host side: states, inputs, the table and its references."""
     def __init__(self):
         self.m = m = fr.quadruped(perturb=0.3)
         q, v, tau, _ = fr.inputs(m, 257, 258)
-        q, v, tau = q[:B].copy(), v[:B].copy(), tau[:B].copy()
-        lowest = lambda: np.array([cr.feet(m, q[b])[0][:, 2].min() for b in range(B)])      # noqa: E731
-        want = np.array([-0.003, 0.0, 0.02])[np.arange(B) % 3]
-        lift = (m.forward_kinematics(q[0])[0][2] @ m.axis[2])[2]
-        q[:, 2] += ((want - lowest()) / lift).astype(np.float32)
-        assert np.abs(lowest() - want).max() < 1e-6
+        q, v, tau = lower_feet(m, q[:B], THREE_HEIGHTS[np.arange(B) % 3], tol=1e-6), v[:B].copy(), tau[:B].copy()
         self.q, self.v, self.tau = q.astype(np.float32), v.astype(np.float32), tau.astype(np.float32)
         self.q_des = (self.q[:, 6:] + np.random.default_rng(1).uniform(-0.1, 0.1, (B, 12))).astype(np.float32)
         rng = np.random.default_rng(SEED)
@@ -88,17 +78,13 @@ class Fixture:
         self.f = np.stack([cr.contact_law(self.G[b], self.pos[b], self.vel[b]) for b in range(B)])
         self.f32 = np.stack([cr.contact_law(self.G[b], k32[b][0], k32[b][1]) for b in range(B)])
         assert self.f32.dtype == np.float32
-        self._steps = {}
-        for x in (self.q, self.v, self.tau, self.q_des, self.rows, self.A, self.F, self.goal, self.pos, self.vel, self.f, self.f32):
-            x.setflags(write=False)
+        self.freeze()
 
     def step(self, n_sub):
         """(fp64, float32) outputs of contact_step_ref per robot under its own Ground, stacked"""
-        if n_sub not in self._steps:
-            run = lambda **kw: [np.stack(x) for x in zip(*[cr.contact_step_ref(self.m, self.G[b], self.q[b], self.v[b], DT, n_sub, self.tau[b],  # noqa: E731
-                                                                                   self.q_des[b], KP, KD, **kw) for b in range(B)])]
-            self._steps[n_sub] = (run(), run(fd=fr.aba, dtype=np.float32))
-        return self._steps[n_sub]
+        run = lambda **kw: [np.stack(x) for x in zip(*[cr.contact_step_ref(self.m, self.G[b], self.q[b], self.v[b], DT, n_sub, self.tau[b],  # noqa: E731
+                                                                               self.q_des[b], KP, KD, **kw) for b in range(B)])]
+        return self.cached(n_sub, lambda: (run(), run(fd=fr.aba, dtype=np.float32)))
 
     def track(self, **kw):
         """the chained reference: K control steps of N_SUB substeps with q_des = A[b, k] -> (q, v, Q, V) stacked over the robots"""
@@ -141,38 +127,9 @@ def fx():
     return f
 
 
-class World:
-    """the device side of the fixture: one layer, the inputs as tensors"""
-    def __init__(self, f):
-        self.f, self.L = f, layer(f.m)
-        d = lambda x: torch.as_tensor(np.array(x), device=self.L.device).contiguous()      # noqa: E731
-        self.q, self.v, self.tau, self.q_des, self.A, self.F, self.goal = (d(x) for x in (f.q, f.v, f.tau, f.q_des, f.A, f.F, f.goal))
-
-    def step(self, g=None, n_sub=STEP_SUB, dt=DT):
-        from iterative_learning_nmpc_amd.torque import GroundContact
-        return self.L.contact_step(self.q, self.v, dt, n_sub, tau_ff=self.tau, q_des=self.q_des, kp=KP, kd=KD, ground=g or GroundContact())
-
-    def track(self, g=None):
-        from iterative_learning_nmpc_amd.torque import GroundContact
-        return self.L.contact_track(self.q.clone(), self.v.clone(), self.A, DT, N_SUB, tau_ff=self.tau, kp=KP, kd=KD, ground=g or GroundContact())
-
-    def forces(self, g=None):
-        from iterative_learning_nmpc_amd.torque import GroundContact
-        return (self.L.contact_forces(self.q, self.v, g or GroundContact()),)
-
-
 @pytest.fixture(scope="module")
 def world(fx):
-    return World(fx)
-
-
-@pytest.fixture()
-def detached(world):
-    """whatever a test attaches or sets is gone after it, also when it fails"""
-    yield
-    world.L.set_grounds(None)
-    world.L.set_push(None)
-    world.L.set_integrator("explicit")
+    return World(fx.m, B, q=fx.q, v=fx.v, tau=fx.tau, q_des=fx.q_des, A=fx.A, F=fx.F, goal=fx.goal)
 
 
 # ---- 1. forces, step, track and the implicit step against the reference -----------------------------------------------------------------
@@ -200,7 +157,7 @@ def test_the_track_matches_the_chained_reference(fx, world, detached):
     got = host(*world.track())
     assert [x.shape for x in got] == [(B, 18)] * 2 + [(B, K, 18)] * 2
     print(f"track under the table, {K} control steps of {N_SUB} substeps, B 33")
-    assert all([held(name, x, r, f) for name, x, r, f in zip(("q", "v", "Q", "V"), got, ref, f32)])
+    assert all([held(name, x, r, f) for name, x, r, f in zip(TRACK_NAMES, got, ref, f32)])
 
 
 @pytest.mark.parametrize("n_sub", [1, STEP_SUB])
@@ -219,31 +176,25 @@ COUNT = [1 + b % 3 for b in range(B)]                     # substeps of N_SUB = 
 PUSHES = {"none": None, "one window": {"step": (1, 2), "track": (3, 2)}, "windows": {"step": (FIRST, COUNT), "track": (FIRST, COUNT)}}
 
 
-def rows_equal(got, ref, b):
-    return all(same(x[b], y[b]) for x, y in zip(got, ref))
-
-
 @pytest.mark.parametrize("push", list(PUSHES))
 @pytest.mark.parametrize("integrator", INTEGRATORS)
 def test_robot_b_is_the_uniform_call_under_its_row(fx, world, detached, integrator, push):
     L = world.L
     L.set_integrator(integrator)
-    calls = {"step": (world.step, NAMES), "track": (world.track, ("q", "v", "Q", "V"))}
+    calls = {"step": (world.step, NAMES), "track": (world.track, TRACK_NAMES)}
     if push == "none":
         calls["forces"] = (world.forces, ("f",))
+
+    def uniform_of(b):                                      # nothing attached, and the ground of the call is row b
+        L.set_grounds(None)
+        return dict(g=device_ground(fx.rows[b]))
     for name, (call, outputs) in calls.items():
         if PUSHES[push] is not None:
             L.set_push(world.F, *PUSHES[push][name])
             assert (L._push_windows is not None) == (push == "windows")
-        L.set_grounds(fx.rows)
-        got = call()
-        L.set_grounds(None)
         plain = call()
-        for b in ROBOTS:
-            ref = call(device_ground(fx.rows[b]))
-            for o, x, y in zip(outputs, got, ref):
-                print(f"  {integrator}, push {push}, {name}, robot {b} {o}: largest |table - uniform| {float((x[b].double() - y[b].double()).abs().max()):.3e}")
-            assert rows_equal(got, ref, b), (name, b)
+        got, _ = held_row_by_row(call, lambda: L.set_grounds(fx.rows), uniform_of, ROBOTS, outputs,
+                                 lambda b, o: f"{integrator}, push {push}, {name}, robot {b} {o}: largest |table - uniform|")      # noqa: B023
         assert not all(rows_equal(got, plain, b) for b in ROBOTS), name      # and the rows matter: the default ground gives other bits
         L.set_push(None)
 
@@ -296,12 +247,11 @@ def test_general_trees_step_under_a_table(tree):
 # ---- 5. policy in the loop ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def policy(world):
-    return policy_pair(47, 12, 1, 64, True, 64, seed=5)[0]
+    return default_policy()
 
 
 def rollout(world, policy):
-    return world.L.policy_rollout(policy, world.q, world.v, K, DT, N_SUB, world.goal, tau_ff=world.tau, kp=KP, kd=KD, t0=T0, period=PERIOD,
-                                  terminate_mask=MASK, collision_height=HEIGHT)
+    return world.rollout(policy)
 
 
 def test_the_policy_rollout_is_its_chain_of_public_calls(fx, world, policy, detached):
@@ -341,19 +291,16 @@ def test_evaluate_policy_attaches_and_detaches_the_table(fx, world, policy, deta
 
 
 # ---- 6. the expert on the plant ----------------------------------------------------------------------------------------------------------
-def test_the_expert_on_the_plant_stands_on_each_rollouts_row(dev):
+def test_the_expert_on_the_plant_stands_on_each_rollouts_row(dev, quadruped_layer):
     """B = 3 rollouts, 2 replans (T = 0.0795 s, tests/test_gpu_wb_plant_rollout.py), three different rows: rollout b against
     rollout b of the same call with nothing attached and plant = GroundContact(row b)."""
-    from iterative_learning_nmpc_amd import wholebody as wbk
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer, GroundContact
-    L = BatchedTorqueLayer(**quadruped_tree(), device=dev)
+    from iterative_learning_nmpc_amd.torque import GroundContact
+    L = quadruped_layer
     rows = np.array([[0.0, 1e4, 3.0, 0.8, 0.05, 0.0], [0.004, 1.5e4, 2.0, 0.5, 0.04, 30.0], [-0.003, 8e3, 4.0, 1.1, 0.08, 18.0]], np.float32)
-    q0 = np.zeros((3, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME
-    v0 = np.zeros((3, 18))
+    q0, v0 = standing_start(3)
 
     def run(plant):
-        mpc = LocomotionMPC(print_info=False, device=dev, batch=3, force_reference="gravity_share")
+        mpc = expert(dev, 3)
         S = mpc.open_loop_device(q0, v0, 0.0795, torque_layer=L, plant=plant, plant_substeps=2)
         return S, mpc.actions, mpc.q_final, mpc.v_final, mpc.failed
 
@@ -385,7 +332,7 @@ def test_refusals_detaching_and_the_empty_batch(fx, world, detached):
         with pytest.raises(NmpcError, match="grounds: B exceeds n_rows"):
             call()
     with pytest.raises(NmpcError, match="grounds: B exceeds n_rows"):
-        L.policy_rollout(policy_pair(47, 12, 1, 64, True, 64, seed=5)[0], world.q, world.v, 1, DT, 1, world.goal)
+        L.policy_rollout(default_policy(), world.q, world.v, 1, DT, 1, world.goal)
     assert [tuple(x.shape) for x in L.contact_step(world.q[:4], world.v[:4], DT, 1)] == [(4, 18)] * 3 + [(4, 4, 3), (4, 12)]
     # cfg is still validated under a table
     with pytest.raises(NmpcError, match="slip_velocity must be positive"):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.plant_helpers import expert
 from tests.solve_helpers import dev  # noqa: F401
 from tests.torque_helpers import oracle_labels, same
 
@@ -27,9 +28,8 @@ class Rig:
     """a configured whole-body device solver of `batch_max` problems with the controller's tables, and the 15 states"""
     def __init__(self, dev, batch_max):
         from iterative_learning_nmpc_amd import wholebody as wbk
-        from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
         from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-        self.mpc = mpc = LocomotionMPC(print_info=False, device=dev, batch=batch_max, n_nodes=30, force_reference="gravity_share")
+        self.mpc = mpc = expert(dev, batch_max, n_nodes=30)
         assert mpc.replanning_steps == STEPS
         self.s = s = mpc.solver._device_solver()
         self.L = BatchedTorqueLayer(**quadruped_tree(), device=dev)
@@ -267,8 +267,7 @@ def test_refusals_launch_nothing(dev, rig, mixed):
 def test_controller_label_states_leaves_the_controller_alone(dev, rig, mixed):
     """`LocomotionMPC.label_states`: the clock's nodes and steps, the controller's command and reference, Kp / Kd by default; no
     counter, view or device plan of the controller moves"""
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
-    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
+    mpc = expert(dev, B, n_nodes=30)
     mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
     before = (mpc.sim_step, mpc.current_opt_node, mpc.first_solve, mpc.base_ref_vel_tracking.copy(), mpc.solver.last_node)
     A, status = mpc.label_states(rig.Q, rig.V, rig.L, kp=KP, kd=KD)

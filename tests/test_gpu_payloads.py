@@ -18,19 +18,18 @@ import pytest
 from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import payload_reference as plr
-from tests.solve_helpers import dev, policy_pair  # noqa: F401
-from tests.torque_helpers import bar, host, layer, same
+from tests import plant_helpers as ph
+from tests.plant_helpers import AT, DT, DT_IMPLICIT, HEIGHT, INTEGRATORS, KD, KP, MASK, N_SUB, NAMES, ONE, PERIOD, STEP_SUB, T0, TRACK_NAMES
+from tests.plant_helpers import World, chain_of_public_calls, default_policy, detach, detached, expert, held_row_by_row  # noqa: F401
+from tests.plant_helpers import plant_rollout, quadruped_layer, standing_start  # noqa: F401
+from tests.solve_helpers import dev  # noqa: F401
+from tests.torque_helpers import bar, fractions, host, layer, lower_feet, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-KP, KD, DT, DT_IMPLICIT = 20.0, 1.5, 5e-4, 1e-3
-B, K, N_SUB, STEP_SUB = 33, 5, 2, 4
+B, K = 33, 5                                             # the track: 5 control steps; the policy rollout has the plant's 3
 TRUNK = 5
-PERIOD, T0, HEIGHT, MASK = 0.5, 0.37, 0.08, 2 | 4 | 8 | 32
-INTEGRATORS = ("explicit", "implicit")
-NAMES = ("q", "v", "a", "f", "tau")
-AT = 1e-6                                                 # a foot this close to the plane is "at" it (tests/test_gpu_contact_implicit.py)
 
 
 def draw_payloads(rng, n):
@@ -57,38 +56,12 @@ def start_states(m, n, rng, slide=2):
     # while the bar's floor for a robot that touches at depth d is 1e-5 k d: below d = 3 mm the floor is under what the number
     # format owes and the bar would rest on the luck of the one float32 run that is its other term.
     want = np.concatenate([np.linspace(0.02, 0.001, n // 2), np.linspace(-0.004, -0.02, n - n // 2)]) if n > 1 else np.array([-0.01])
-    lift = (m.forward_kinematics(q[0])[0][slide] @ m.axis[slide])[2]
-    assert m.jtype[slide] == 1 and lift > 0.5
-    q = q.astype(np.float32)
-    for _ in range(2):                                    # the second pass takes out what float32 left of the first
-        lowest = np.array([cr.feet(m, q[b])[0][:, 2].min() for b in range(n)])
-        q[:, slide] += ((want - lowest) / lift).astype(np.float32)
-    return q, v.astype(np.float32)
+    # float32 before the correction, and a second pass that takes out what float32 left of the first
+    return lower_feet(m, q, want, slide, passes=2, dtype=np.float32), v.astype(np.float32)
 
 
-def fractions(what, got, ref, f32):
-    """the bar of tests/test_gpu_torque.py on an array [B, ...]: `bar` of every sample (scale: the sample's largest |ref|) and of
-    every column (scale: the column's largest |ref| over the batch) -> the worst error as a fraction of its bar"""
-    n = ref.shape[0]
-    got, ref, f32 = (np.asarray(x).reshape(n, -1) for x in (got, ref, f32))
-    assert got.shape == ref.shape == f32.shape and np.isfinite(got).all() and np.isfinite(ref).all(), what
-    got = got.astype(np.float64)
-    worst = 0.0
-    for axis, label in ((1, "sample"), (0, "column")):
-        for i in range(ref.shape[1 - axis]):
-            g, r, f = (x[i] if axis == 1 else x[:, i] for x in (got, ref, f32))
-            err, b = np.abs(g - r).max(), bar(r, f)
-            frac = 0.0 if err == 0.0 else (np.inf if b == 0.0 else err / b)
-            if frac > 1.0:
-                print(f"    {what} {label} {i}: error {err:.3e} over its bar {b:.3e}")
-            worst = max(worst, frac)
-    print(f"  {what}: worst error {worst:.3f} of its bar (largest |gpu - ref64| {np.abs(got - ref).max():.3e}, float32 loop "
-          f"{np.abs(f32.astype(np.float64) - ref).max():.3e}, scale {np.abs(ref).max():.3e})")
-    return worst
-
-
-class Fixture:
-    """The host side on the quadruped: states, inputs, the table and its references.  Built once, never written to."""
+class Fixture(ph.Fixture):
+    """The host side on the quadruped: states, inputs, the table and its references."""
     def __init__(self):
         self.m = m = fr.quadruped()
         rng = np.random.default_rng(17)
@@ -104,21 +77,16 @@ class Fixture:
         self.grounds[:, 0] = rng.uniform(-0.005, 0.005, B); self.grounds[:, 1] = rng.uniform(5e3, 2e4, B); self.grounds[:, 3] = rng.uniform(0.3, 1.1, B)
         self.grounds[:, 5] = np.where(np.arange(B) % 2 == 0, 0.0, rng.uniform(15.0, 40.0, B))
         self.g = cr.Ground()
-        self._refs = {}
-        for x in (self.q, self.v, self.tau, self.q_des, self.A, self.rows, self.F, self.goal, self.grounds):
-            x.setflags(write=False)
+        self.freeze()
 
     def ref(self, call, implicit, n_sub=None):
         """(float64, float32) reference of `call` on the baked trees, computed once"""
-        key = (call, implicit, n_sub)
-        if key not in self._refs:
-            dt = DT_IMPLICIT if implicit else DT
-            if call == "step":
-                run = lambda t: plr.step(self.m, self.g, self.rows, TRUNK, self.q, self.v, dt, n_sub, self.tau, self.q_des, KP, KD, t, implicit)      # noqa: E731
-            else:
-                run = lambda t: plr.track(self.m, self.g, self.rows, TRUNK, self.q, self.v, self.A, dt, N_SUB, self.tau, KP, KD, t, implicit)       # noqa: E731
-            self._refs[key] = (run(np.float64), run(np.float32))
-        return self._refs[key]
+        dt = DT_IMPLICIT if implicit else DT
+        if call == "step":
+            run = lambda t: plr.step(self.m, self.g, self.rows, TRUNK, self.q, self.v, dt, n_sub, self.tau, self.q_des, KP, KD, t, implicit)      # noqa: E731
+        else:
+            run = lambda t: plr.track(self.m, self.g, self.rows, TRUNK, self.q, self.v, self.A, dt, N_SUB, self.tau, KP, KD, t, implicit)       # noqa: E731
+        return self.cached((call, implicit, n_sub), lambda: (run(np.float64), run(np.float32)))
 
     def conditions(self):
         pos = np.stack([cr.feet(self.m, self.q[b])[0] for b in range(B)])
@@ -137,47 +105,13 @@ def fx():
     return f
 
 
-class World:
-    """the device side: one layer of tree m, the first n robots of the inputs as tensors"""
-    def __init__(self, m, n, q, v, tau, q_des, A, L=None):
-        self.m, self.n, self.L = m, n, L or layer(m)
-        self.d = lambda x: torch.as_tensor(np.array(x), device=self.L.device).contiguous()      # noqa: E731
-        self.q, self.v, self.tau, self.q_des, self.A = (self.d(x[:n]) for x in (q, v, tau, q_des, A))
-        self.record = m.n == 18 and m.nu == 12              # the rows Q, V need the whole-body tree
-
-    def permuted(self, perm):
-        w = World.__new__(World)
-        w.__dict__.update(self.__dict__)
-        p = torch.as_tensor(perm, device=self.L.device)
-        w.q, w.v, w.tau, w.q_des, w.A = (x[p].contiguous() for x in (self.q, self.v, self.tau, self.q_des, self.A))
-        return w
-
-    def step(self, n_sub=STEP_SUB, dt=DT):
-        return self.L.contact_step(self.q, self.v, dt, n_sub, tau_ff=self.tau, q_des=self.q_des, kp=KP, kd=KD)
-
-    def track(self, dt=DT):
-        out = self.L.contact_track(self.q.clone(), self.v.clone(), self.A, dt, N_SUB, tau_ff=self.tau, kp=KP, kd=KD, record=self.record)
-        return out if self.record else out[:2]
-
-
 def quad_world(fx, n=B, L=None):
-    return World(fx.m, n, fx.q, fx.v, fx.tau, fx.q_des, fx.A, L)
+    return World(L or fx.m, n, q=fx.q, v=fx.v, tau=fx.tau, q_des=fx.q_des, A=fx.A, goal=fx.goal)
 
 
 @pytest.fixture(scope="module")
 def world(fx):
     return quad_world(fx)
-
-
-def detach(L):
-    L.set_payloads(None); L.set_grounds(None); L.set_push(None); L.set_integrator("explicit")
-
-
-@pytest.fixture()
-def detached(world):
-    """whatever a test attaches or sets is gone after it, also when it fails"""
-    yield
-    detach(world.L)
 
 
 # ---- 1. against the reference on the baked trees ------------------------------------------------------------------------------------------
@@ -204,14 +138,13 @@ def test_the_track_matches_the_chained_reference_on_each_robots_baked_tree(fx, w
     got = host(*world.track(dt=DT_IMPLICIT if implicit else DT))
     assert [x.shape for x in got] == [(B, 18)] * 2 + [(B, K, 18)] * 2
     print(f"{integrator} track under the payload table, {K} control steps of {N_SUB} substeps, B {B}")
-    worst = [fractions(name, x, r, f) for name, x, r, f in zip(("q", "v", "Q", "V"), got, ref, f32)]
+    worst = [fractions(name, x, r, f) for name, x, r, f in zip(TRACK_NAMES, got, ref, f32)]
     assert max(worst) <= 1.0
 
 
 # ---- 2. against the device itself: a layer created from the baked tree ------------------------------------------------------------------------
-def rollout(w, policy, goal, dt=DT):
-    return w.L.policy_rollout(policy, w.q, w.v, 3, dt, N_SUB, goal, tau_ff=w.tau, kp=KP, kd=KD, t0=T0, period=PERIOD, terminate_mask=MASK,
-                              collision_height=HEIGHT)
+def rollout(w, policy, dt=DT):
+    return w.rollout(policy, dt)
 
 
 @pytest.mark.parametrize("integrator", INTEGRATORS)
@@ -229,14 +162,13 @@ def test_a_uniform_table_is_the_layer_of_the_baked_tree(fx, world, detached, int
     f32 = plr.step(fx.m, fx.g, uniform, TRUNK, fx.q, fx.v, dt, STEP_SUB, fx.tau, fx.q_des, KP, KD, np.float32, implicit)
     tref = plr.track(fx.m, fx.g, uniform, TRUNK, fx.q, fx.v, fx.A, dt, N_SUB, fx.tau, KP, KD, np.float64, implicit)
     t32 = plr.track(fx.m, fx.g, uniform, TRUNK, fx.q, fx.v, fx.A, dt, N_SUB, fx.tau, KP, KD, np.float32, implicit)
-    policy = policy_pair(47, 12, 1, 64, True, 64, seed=5)[0]
-    goal = world.d(fx.goal)
+    policy = default_policy()
     for w in (world, baked):
         w.L.set_integrator(integrator)
     bare_track = host(*world.track(dt=dt))
     world.L.set_payloads(uniform)
-    hook = host(*world.step(dt=dt)), host(*world.track(dt=dt)), host(*rollout(world, policy, goal, dt)[:4])
-    tree = host(*baked.step(dt=dt)), host(*baked.track(dt=dt)), host(*rollout(baked, policy, goal, dt)[:4])
+    hook = host(*world.step(dt=dt)), host(*world.track(dt=dt)), host(*rollout(world, policy, dt)[:4])
+    tree = host(*baked.step(dt=dt)), host(*baked.track(dt=dt)), host(*rollout(baked, policy, dt)[:4])
     print(f"{integrator}: the nominal layer under a uniform table of 5 kg against the layer of the baked tree, B {B}")
     worst = []
     for name, x, y, r, f in zip(NAMES, hook[0], tree[0], ref, f32):
@@ -291,7 +223,7 @@ def wide_world():
     tau = rng.uniform(-2, 2, (n, m.nu)).astype(np.float32)
     q_des = (q[:, 6:] + rng.uniform(-0.1, 0.1, (n, m.nu))).astype(np.float32)
     A = (q[:, None, 6:] + rng.uniform(-0.05, 0.05, (n, K, m.nu))).astype(np.float32)
-    return World(m, n, q, v, tau, q_des, A)
+    return World(m, n, q=q, v=v, tau=tau, q_des=q_des, A=A)
 
 
 @pytest.fixture(scope="module")
@@ -314,35 +246,38 @@ def test_row_b_is_robot_bs_bit_for_bit(fx, worlds, shape, integrator, extra):
     first, count = np.array([1 + 2 * (b % 2) for b in range(n)]), np.array([1 + b % 3 for b in range(n)])
     perm = rng.permutation(n)
 
-    def attach(rows_, idx, world_=w):
-        """the table rows_ with what `extra` names for the robots idx, then (step, track) of world_"""
+    def attach(rows_, idx):
+        """the table rows_ with what `extra` names for the robots idx"""
         L.set_grounds(grounds[idx] if extra == "grounds" else None)
         if extra == "push":
             L.set_push(w.d(F[idx]), 1, 2)
         elif extra == "windows":
             L.set_push(w.d(F[idx]), first[idx], count[idx])
         L.set_payloads(rows_, joint=TRUNK)
+
+    def run(world_=w):
         return world_.step(dt=dt) + world_.track(dt=dt)
 
     try:
         L.set_integrator(integrator)
         everyone = np.arange(n)
-        got = attach(rows, everyone)
-        # robot b under the uniform table of its row
-        for b in sorted({0, n // 2, n - 1}):
-            ref = attach(np.tile(rows[b], (n, 1)), everyone)      # the same call otherwise: the same grounds, push and windows
-            assert all(same(x[b], y[b]) for x, y in zip(got, ref)), (shape, b)
+        # robot b under the uniform table of its row: the same call otherwise, the same grounds, push and windows
+        got, _ = held_row_by_row(run, lambda: attach(rows, everyone), lambda b: attach(np.tile(rows[b], (n, 1)), everyone), sorted({0, n // 2, n - 1}),
+                                 NAMES + (TRACK_NAMES if w.record else TRACK_NAMES[:2]),
+                                 lambda b, o: f"{shape}, {integrator}, {extra}, robot {b} {o}: largest |table - uniform|")
         # a permutation of robots and rows permutes the outputs
         p = torch.as_tensor(perm, device=L.device)
-        shuffled = attach(rows[perm], perm, w.permuted(perm))
+        attach(rows[perm], perm)
+        shuffled = run(w.permuted(perm))
         assert all(same(x[p], y) for x, y in zip(got, shuffled)), shape
         # spare rows change nothing
-        longer = attach(np.vstack([rows, fx.rows[::-1][:3]]), everyone)
+        attach(np.vstack([rows, fx.rows[::-1][:3]]), everyone)
+        longer = run()
         assert all(same(x, y) for x, y in zip(got, longer)), shape
         # and the rows matter
         if n > 1:
             L.set_payloads(None)
-            assert not all(same(x, y) for x, y in zip(got, w.step(dt=dt) + w.track(dt=dt)))
+            assert not all(same(x, y) for x, y in zip(got, run()))
     finally:
         detach(L)
 
@@ -352,9 +287,8 @@ def test_row_b_is_robot_bs_bit_for_bit(fx, worlds, shape, integrator, extra):
 def test_attach_then_detach_gives_the_bits_from_before(fx, world, detached, integrator):
     L = world.L
     L.set_integrator(integrator)
-    policy = policy_pair(47, 12, 1, 64, True, 64, seed=5)[0]
-    goal = world.d(fx.goal)
-    calls = lambda: world.step() + world.track() + rollout(world, policy, goal)      # noqa: E731
+    policy = default_policy()
+    calls = lambda: world.step() + world.track() + rollout(world, policy)      # noqa: E731
     before = calls()
     L.set_payloads(fx.rows)
     assert L._payloads is not None
@@ -373,10 +307,9 @@ def test_the_nominal_model_does_not_read_the_table(fx, world, detached, dev):
     a = world.d(np.random.default_rng(3).uniform(-5, 5, (B, 18)).astype(np.float32))
     f = world.d(np.random.default_rng(4).uniform(-40, 80, (B, 4, 3)).astype(np.float32))
     tau = world.d(np.random.default_rng(5).uniform(-20, 20, (B, 12)).astype(np.float32))
-    from tests.test_gpu_wb_plant_rollout import ONE, controller, rollout as expert, start
-    mpc = controller(dev, 2)
-    q0, v0 = start(2)
-    o = expert(mpc, L, q0, v0, ONE)
+    mpc = expert(dev, 2)
+    q0, v0 = standing_start(2)
+    o = plant_rollout(mpc, L, q0, v0, ONE)
     zoh = mpc.id_repeat[:40]
 
     def nominal():
@@ -398,12 +331,12 @@ def test_the_nominal_model_does_not_read_the_table(fx, world, detached, dev):
 def test_evaluate_policy_attaches_and_detaches_the_table(fx, world, detached):
     from iterative_learning_nmpc_amd.learning import evaluate_policy
     L = world.L
-    policy = policy_pair(47, 12, 1, 64, True, 64, seed=5)[0]
-    goal = world.d(fx.goal)
+    policy = default_policy()
+    goal = world.goal
     L.set_payloads(fx.rows)
-    q, v, S, A, failed = rollout(world, policy, goal)
+    q, v, S, A, failed = rollout(world, policy)
     L.set_payloads(None)
-    bare = rollout(world, policy, goal)
+    bare = rollout(world, policy)
     kw = dict(dt=DT, n_sub=N_SUB, tau_ff=world.tau, kp=KP, kd=KD, t0=T0, period=PERIOD, terminate_mask=MASK, collision_height=HEIGHT)
     out = evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, payloads=fx.rows, **kw)
     assert same(out["S"], S) and same(out["A"], A) and same(out["q"], q) and same(out["v"], v) and torch.equal(out["failed"], failed)
@@ -413,18 +346,18 @@ def test_evaluate_policy_attaches_and_detaches_the_table(fx, world, detached):
     # also when the rollout raises: a goal of the wrong batch is refused inside the try
     with pytest.raises(Exception):
         evaluate_policy(L, policy, None, world.q, world.v, goal[:5], 3 * N_SUB * DT, payloads=fx.rows, **kw)
-    assert L._payloads is None and same(rollout(world, policy, goal)[0], bare[0])
+    assert L._payloads is None and same(rollout(world, policy)[0], bare[0])
     # a table of the caller's is not replaced
     L.set_payloads(fx.rows)
     mine = L._payloads
     with pytest.raises(ValueError, match="attached already"):
         evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, payloads=fx.rows, **kw)
-    assert L._payloads is mine and same(rollout(world, policy, goal)[0], q)
+    assert L._payloads is mine and same(rollout(world, policy)[0], q)
 
 
 def test_dagger_iteration_labels_with_the_nominal_expert(fx, dev):
     from iterative_learning_nmpc_amd import learning
-    from tests import test_gpu_dagger_iteration as di
+    from tests.plant_helpers import Dagger as di
     w = di.setup(dev)
     rows = fx.rows[1:1 + di.B].copy()
     run = lambda **kw: learning.dagger_iteration(w["mpc"], w["layer"], w["db"], w["policy"], w["q0"], w["v0"], w["goal"], di.T, dt=di.DT,      # noqa: E731
@@ -444,19 +377,16 @@ def test_dagger_iteration_labels_with_the_nominal_expert(fx, dev):
     assert not same(bare["Q"][:, -1], out["Q"][:, -1])
 
 
-def test_the_expert_on_the_plant_carries_the_table_of_its_layer(fx, dev):
+def test_the_expert_on_the_plant_carries_the_table_of_its_layer(fx, dev, quadruped_layer):
     """B = 2, one replan: the plant-mode rollout with a table on its layer is the chain plan labels -> contact_track -> observe_rows
     under the same table (the check of tests/test_gpu_wb_plant_rollout.py), and not the unloaded rollout."""
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    from iterative_learning_nmpc_amd.workloads import quadruped_tree
-    from tests.test_gpu_wb_plant_rollout import ONE, chain_of_public_calls, controller, rollout as expert, start
-    L = BatchedTorqueLayer(**quadruped_tree(), device=dev)
+    L = quadruped_layer
     rows = fx.rows[1:3].copy()
-    q0, v0 = start(2)
-    bare = expert(controller(dev, 2), L, q0, v0, ONE)
+    q0, v0 = standing_start(2)
+    bare = plant_rollout(expert(dev, 2), L, q0, v0, ONE)
     L.set_payloads(rows)
-    mpc = controller(dev, 2)
-    o = expert(mpc, L, q0, v0, ONE)
+    mpc = expert(dev, 2)
+    o = plant_rollout(mpc, L, q0, v0, ONE)
     S, A, q, v, failed = chain_of_public_calls(mpc, L, o["X"], o["U"], q0, v0, o["status"])
     L.set_payloads(None)
     assert o["S"].shape == (2, 40, 44) and bool(torch.isfinite(o["S"]).all())
@@ -473,15 +403,15 @@ def test_refusals_leave_the_handle_as_it_was(fx, world, detached):
     from iterative_learning_nmpc_amd.torque import payload_table
     L, lib = world.L, world.L.lib
     text = lambda: lib.nmpc_torque_last_error(L._h).decode()                           # noqa: E731
-    policy = policy_pair(47, 12, 1, 64, True, 64, seed=5)[0]
-    goal = world.d(fx.goal)
+    policy = default_policy()
+    goal = world.goal
     small = quad_world(fx, 4, L)
     table = world.d(fx.rows[:4])
     L.set_payloads(table)
     assert L._payloads is table                           # a device tensor is taken as given
     kept = small.step()
     # B > n_rows, in every call that reads the table: nothing is launched, what is attached stays
-    for call in (world.step, world.track, lambda: rollout(world, policy, goal)):
+    for call in (world.step, world.track, lambda: rollout(world, policy)):
         with pytest.raises(NmpcError, match="payloads: B exceeds n_rows"):
             call()
     assert all(same(x, y) for x, y in zip(small.step(), kept))

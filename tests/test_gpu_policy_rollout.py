@@ -16,24 +16,16 @@ from oracle.policy_oracle import PolicyOracle
 from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import policy_rollout_reference as pr
+from tests.plant_helpers import DT, KD, KP, device_policy
 from tests.torque_helpers import Case, branches, ground, held, host, layer
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-KP, KD, DT = 20.0, 1.5, 5e-4
 DT32 = float(np.float32(DT))
 PERIOD, T0, HEIGHT = 0.5, 0.37, 0.08
 N_GOAL, HIDDEN, LAYERS = 3, 64, 2
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contact_settle.npz")
-
-
-def device_policy(oracle, batch_max):
-    from iterative_learning_nmpc_amd.policy import DevicePolicy
-    n_in, n_out, L, hidden, bn = oracle.dims
-    p = DevicePolicy(n_in, n_out, L, hidden, bn, batch_max=batch_max, seed=None)
-    p.set_parameters(oracle.theta.astype(np.float32), oracle.running_mean.astype(np.float32), oracle.running_var.astype(np.float32))
-    return p
 
 
 def as32(oracle):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.plant_helpers import expert, standing_start
 from tests.solve_helpers import dev, policy_pair  # noqa: F401
 from tests.torque_helpers import same
 
@@ -18,13 +19,11 @@ START, DURATION = 0.0125, 0.03                 # substeps [25, 85): from inside 
 
 
 def setup(dev):
-    from iterative_learning_nmpc_amd import wholebody as wbk
     from iterative_learning_nmpc_amd.database import DeviceDatabase
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
     from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
     rng = np.random.default_rng(2)
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B, 12))
-    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
+    q0 = standing_start(B)[0]; q0[:, 6:] += rng.normal(0, 0.03, (B, 12))
+    mpc = expert(dev, B, n_nodes=30)
     mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
     goal = np.tile(np.float32([0.2, 0.0, 0.0]), (B, 1))
     return dict(mpc=mpc, layer=BatchedTorqueLayer(**quadruped_tree(), device=dev), db=DeviceDatabase(limit=256, norm_input=False, device=dev),

@@ -14,38 +14,16 @@ replans, and of a rollout of the first replan alone, which is the state between 
 import numpy as np
 import pytest
 
-from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.plant_helpers import N_SUB, ONE, STEPS, TWO
+from tests.plant_helpers import default_plant as plant, expert as controller, plant_rollout, quadruped_layer, standing_start as start  # noqa: F401
 from tests.solve_helpers import dev  # noqa: F401
 from tests.torque_helpers import same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-STEPS, N_SUB, ONE, TWO = 40, 2, 0.0395, 0.0795
 START, DURATION = 0.025, 0.030
 FIRST, COUNT = 50, 60                      # lround(START n_sub / sim_dt), lround(DURATION n_sub / sim_dt)
-
-
-@pytest.fixture(scope="module")
-def layer(dev):
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    return BatchedTorqueLayer(**quadruped_tree(), device=dev)
-
-
-def controller(dev, B=3):
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
-    return LocomotionMPC(print_info=False, device=dev, batch=B, force_reference="gravity_share")
-
-
-def start(B=3):
-    from iterative_learning_nmpc_amd import wholebody as wbk
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME
-    return q0, np.zeros((B, 18))
-
-
-def plant():
-    from iterative_learning_nmpc_amd.torque import GroundContact
-    return GroundContact()
 
 
 def the_push():
@@ -54,15 +32,13 @@ def the_push():
 
 
 def rollout(mpc, L, T=TWO, **kw):
-    q0, v0 = start()
-    S = mpc.open_loop_device(q0, v0, T, torque_layer=L, plant=plant(), plant_substeps=N_SUB, **kw)
-    torch.cuda.synchronize()
-    return dict(S=S, A=mpc.actions, q=mpc.q_final, v=mpc.v_final, failed=mpc.failed)
+    """from the standing start, waited for, without the plans"""
+    return plant_rollout(mpc, L, *start(), T, sync=True, plans=False, **kw)
 
 
-def test_as_a_force_every_replan_is_the_pushed_track_of_its_label_rows(dev, layer):
+def test_as_a_force_every_replan_is_the_pushed_track_of_its_label_rows(dev, quadruped_layer):
     from iterative_learning_nmpc_amd.config import COLLISION_HEIGHT
-    mpc, L, push = controller(dev), layer, the_push()
+    mpc, L, push = controller(dev), quadruped_layer, the_push()
     assert mpc.replanning_steps == STEPS and len(mpc.replan_clock(TWO)[1]) == 2 and abs(mpc.sim_dt - 1e-3) < 1e-12
     assert FIRST == round(START * N_SUB / mpc.sim_dt) and COUNT == round(DURATION * N_SUB / mpc.sim_dt)
     out = rollout(mpc, L, push=push, push_as_force=True)
@@ -96,20 +72,20 @@ def test_as_a_force_every_replan_is_the_pushed_track_of_its_label_rows(dev, laye
     assert not same(plain["v"], out["v"]) and not same(jump["v"], out["v"])
 
 
-def test_the_switch_off_is_the_rollout_it_was(dev, layer):
+def test_the_switch_off_is_the_rollout_it_was(dev, quadruped_layer):
     push = the_push()
-    ref = rollout(controller(dev), layer, T=ONE, push=dict(push, start=0.0))
+    ref = rollout(controller(dev), quadruped_layer, T=ONE, push=dict(push, start=0.0))
     mpc = controller(dev)
     mpc.solver._device_solver().set_rollout_plant_push(False)
-    got = rollout(mpc, layer, T=ONE, push=dict(push, start=0.0))
+    got = rollout(mpc, quadruped_layer, T=ONE, push=dict(push, start=0.0))
     assert all(same(got[k], ref[k]) for k in ("S", "A", "q", "v")) and torch.equal(got["failed"], ref["failed"])
     # the velocity jump is there: the final v differs from the un-pushed rollout's
-    assert not same(rollout(controller(dev), layer, T=ONE)["v"], ref["v"])
+    assert not same(rollout(controller(dev), quadruped_layer, T=ONE)["v"], ref["v"])
 
 
-def test_refusals(dev, layer):
+def test_refusals(dev, quadruped_layer):
     from iterative_learning_nmpc_amd._lib import NmpcError
-    push, L = the_push(), layer
+    push, L = the_push(), quadruped_layer
     q0, v0 = start()
     # the caller's own push on the plant's torque handle and the rollout's as a force: which one is meant
     L.set_push(torch.as_tensor(push["force"], device=L.device), 0, 4)

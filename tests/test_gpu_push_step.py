@@ -13,23 +13,17 @@ import pytest
 from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import push_reference as pr
-from tests.torque_helpers import Case, bar, ground, held, host, layer, same
+from tests.plant_helpers import DT, KD, KP, NAMES, detached  # noqa: F401
+from tests.torque_helpers import Case, bar, general_case, ground, held, host, layer, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-KP, KD, DT, N_SUB, FIRST, COUNT = 20.0, 1.5, 5e-4, 4, 1, 2          # the window [1, 3) of four substeps
-NAMES = ("q", "v", "a", "f", "tau")
+N_SUB, FIRST, COUNT = 4, 1, 2                                       # the window [1, 3) of four substeps
 # tree -> (B, pushed joint): B = 33 leaves the last robot alone in a second block of 32; the 32-joint tree runs 16 robots per
 # block, B = 17 is one block and a robot.  Joint 9 of that tree and joint 7 of tree23 are bodies inside the tree; joint 9 has
 # prismatic joints on its path to the root.
 TREES = {"quadruped": (33, 5), "tree23": (33, 7), "tree32": (17, 9)}
-
-
-def general_case(m, B, seed):
-    q = fr.inputs(m, B, seed)[0]
-    g = pr.general_ground(m, q)
-    return Case(m, B, seed, g)
 
 
 class PushRun:
@@ -62,14 +56,6 @@ class Runs(dict):
 @pytest.fixture(scope="module")
 def runs():
     return Runs()
-
-
-@pytest.fixture()
-def detached(runs):
-    """whatever a test attaches is gone after it, also when it fails"""
-    yield
-    for r in runs.values():
-        r.c.L.set_push(None)
 
 
 CASES = [("quadruped", 1), ("quadruped", 33), ("tree23", 33), ("tree32", 17)]

@@ -8,40 +8,26 @@ replan 0, rollout 1 in replan 1, rollout 2 over replans 1 and 2, rollout 3 not a
 import numpy as np
 import pytest
 
-from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.plant_helpers import N_SUB, STEPS, default_plant as plant, expert, held_row_by_row, quadruped_layer, standing_start  # noqa: F401
 from tests.solve_helpers import dev  # noqa: F401
-from tests.torque_helpers import same
+from tests.torque_helpers import rows_equal, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-B, STEPS, N_SUB, REPLANS = 4, 40, 2, 3
+B, REPLANS = 4, 3
 # the velocity jump acts per replanning interval of 40 ms: windows that open at a replan
 JUMP = dict(start=np.array([0.0, 0.04, 0.04, 0.02]), duration=np.array([0.03, 0.03, 0.05, 0.0]))
 # the force acts per substep of 0.5 ms: windows that open and close inside the intervals
 FORCE = dict(start=np.array([0.0125, 0.045, 0.03, 0.02]), duration=np.array([0.02, 0.03, 0.06, 0.0]))
 
 
-@pytest.fixture(scope="module")
-def layer(dev):
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    return BatchedTorqueLayer(**quadruped_tree(), device=dev)
-
-
 def controller(dev):
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
-    return LocomotionMPC(print_info=False, device=dev, batch=B, force_reference="gravity_share")
+    return expert(dev, B)
 
 
 def start():
-    from iterative_learning_nmpc_amd import wholebody as wbk
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME
-    return q0, np.zeros((B, 18))
-
-
-def plant():
-    from iterative_learning_nmpc_amd.torque import GroundContact
-    return GroundContact()
+    return standing_start(B)
 
 
 def force():
@@ -56,66 +42,61 @@ def rollout(dev, L, push, n_replans=REPLANS, mpc=None, resume=False, **kw):
     return dict(S=S, actions=mpc.actions, q=mpc.q_final, v=mpc.v_final, failed=mpc.failed)
 
 
-def row_equal(got, ref, b, keys):
-    return all(torch.equal(got[k][b], ref[k][b]) if got[k].dtype == torch.int32 else same(got[k][b], ref[k][b]) for k in keys)
-
-
 def held_rollout_by_rollout(dev, L, windows, keys, **kw):
-    push = dict(windows, force=force())
-    got, plain = rollout(dev, L, push, **kw), rollout(dev, L, None, **kw)
+    """the rollout under the windows per rollout against the rollout under the scalar window of each: the push is an argument of
+    the call, so "attaching" sets the one the next call is made with"""
+    use = {}
+    attach = lambda: use.update(push=dict(windows, force=force()))      # noqa: E731
+    attach_window_of = lambda b: use.update(push=dict(use["push"], start=float(windows["start"][b]), duration=float(windows["duration"][b])))      # noqa: E731
+    plain = rollout(dev, L, None, **kw)
+    got, moved = held_row_by_row(lambda: rollout(dev, L, use["push"], **kw), attach, attach_window_of, range(B), keys,
+                                 lambda b, k: f"rollout {b} {k}: largest |windowed - uniform|", plain=plain, moved_by=("v",))
     assert got["S"].shape == (B, REPLANS * STEPS, 44)
-    moved = []
-    for b in range(B):
-        ref = rollout(dev, L, dict(push, start=float(windows["start"][b]), duration=float(windows["duration"][b])), **kw)
-        for k in keys:
-            print(f"  rollout {b} {k}: largest |windowed - uniform| {float((got[k][b].double() - ref[k][b].double()).abs().max()):.3e}")
-        assert row_equal(got, ref, b, keys), b
-        moved.append(not row_equal(ref, plain, b, ("v",)))
     # the pushes are felt, and the rollout without one is its row of the un-pushed run
     assert moved == [True, True, True, False]
-    assert row_equal(got, plain, 3, keys)
+    assert rows_equal(got, plain, 3, keys)
     return got
 
 
-def test_velocity_jumps_per_rollout_are_the_uniform_runs(dev, layer):
+def test_velocity_jumps_per_rollout_are_the_uniform_runs(dev, quadruped_layer):
     mpc = controller(dev)
     assert mpc.replanning_steps == STEPS and abs(mpc.sim_dt - 1e-3) < 1e-12
-    held_rollout_by_rollout(dev, layer, JUMP, ("S", "failed", "q", "v"))
+    held_rollout_by_rollout(dev, quadruped_layer, JUMP, ("S", "failed", "q", "v"))
 
 
 @pytest.mark.parametrize("integrator", ["explicit", "implicit"])
-def test_forces_on_the_plant_per_rollout_are_the_uniform_runs(dev, layer, integrator):
+def test_forces_on_the_plant_per_rollout_are_the_uniform_runs(dev, quadruped_layer, integrator):
     kw = dict(plant=plant(), plant_substeps=N_SUB, push_as_force=True, integrator=integrator)
     try:
-        held_rollout_by_rollout(dev, layer, FORCE, ("S", "failed", "q", "v", "actions"), **kw)
+        held_rollout_by_rollout(dev, quadruped_layer, FORCE, ("S", "failed", "q", "v", "actions"), **kw)
     finally:
-        layer.set_integrator("explicit")
-    assert layer._push is None and layer._push_windows is None
+        quadruped_layer.set_integrator("explicit")
+    assert quadruped_layer._push is None and quadruped_layer._push_windows is None
 
 
-def test_velocity_jumps_on_the_plant_per_rollout_are_the_uniform_runs(dev, layer):
-    held_rollout_by_rollout(dev, layer, JUMP, ("S", "failed", "q", "v", "actions"), plant=plant(), plant_substeps=N_SUB)
+def test_velocity_jumps_on_the_plant_per_rollout_are_the_uniform_runs(dev, quadruped_layer):
+    held_rollout_by_rollout(dev, quadruped_layer, JUMP, ("S", "failed", "q", "v", "actions"), plant=plant(), plant_substeps=N_SUB)
 
 
-def test_resumed_stretches_with_windows_are_the_rows_of_the_one_call(dev, layer):
+def test_resumed_stretches_with_windows_are_the_rows_of_the_one_call(dev, quadruped_layer):
     kw = dict(plant=plant(), plant_substeps=N_SUB, push_as_force=True)
     push = dict(FORCE, force=force())
-    one = rollout(dev, layer, push, **kw)
+    one = rollout(dev, quadruped_layer, push, **kw)
     mpc = controller(dev)
-    first = rollout(dev, layer, push, n_replans=2, mpc=mpc, **kw)
-    second = rollout(dev, layer, push, n_replans=1, mpc=mpc, resume=True, **kw)
+    first = rollout(dev, quadruped_layer, push, n_replans=2, mpc=mpc, **kw)
+    second = rollout(dev, quadruped_layer, push, n_replans=1, mpc=mpc, resume=True, **kw)
     for k in ("S", "actions"):
         assert same(torch.cat([first[k], second[k]], 1), one[k]), k
     assert same(second["q"], one["q"]) and same(second["v"], one["v"]) and torch.equal(second["failed"], one["failed"])
     # and the velocity jump on the same clock
-    one = rollout(dev, layer, dict(JUMP, force=force()))
+    one = rollout(dev, quadruped_layer, dict(JUMP, force=force()))
     mpc = controller(dev)
-    first = rollout(dev, layer, dict(JUMP, force=force()), n_replans=2, mpc=mpc)
-    second = rollout(dev, layer, dict(JUMP, force=force()), n_replans=1, mpc=mpc, resume=True)
+    first = rollout(dev, quadruped_layer, dict(JUMP, force=force()), n_replans=2, mpc=mpc)
+    second = rollout(dev, quadruped_layer, dict(JUMP, force=force()), n_replans=1, mpc=mpc, resume=True)
     assert same(torch.cat([first["S"], second["S"]], 1), one["S"]) and same(second["v"], one["v"])
 
 
-def test_rollout_refusals(dev, layer):
+def test_rollout_refusals(dev, quadruped_layer):
     from iterative_learning_nmpc_amd._lib import NmpcError
     mpc = controller(dev)
     s = mpc.solver._device_solver()
@@ -171,12 +152,12 @@ def test_centroidal_velocity_jumps_per_rollout_are_the_uniform_runs(dev):
     keys, moved = ("S", "failed", "x"), []
     for b in range(B):
         ref = run(dict(start=starts[b], duration=durations[b], force=F))
-        assert row_equal(got, ref, b, keys), b
-        moved.append(not row_equal(ref, plain, b, ("x",)))
-    assert moved == [True, True, True, False] and row_equal(got, plain, 3, keys)
+        assert rows_equal(got, ref, b, keys), b
+        moved.append(not rows_equal(ref, plain, b, ("x",)))
+    assert moved == [True, True, True, False] and rows_equal(got, plain, 3, keys)
 
 
-def test_collection_with_windows_appends_the_rows_and_weights_of_the_uniform_runs(dev, layer):
+def test_collection_with_windows_appends_the_rows_and_weights_of_the_uniform_runs(dev, quadruped_layer):
     from iterative_learning_nmpc_amd.collect import collect_rollouts
     from iterative_learning_nmpc_amd.database import DeviceDatabase
     T = (REPLANS * STEPS - 0.5) * 1.0e-3              # the float clock runs three whole intervals
@@ -188,7 +169,7 @@ def test_collection_with_windows_appends_the_rows_and_weights_of_the_uniform_run
 
     def collect(push, **more):
         mpc, db = controller(dev), DeviceDatabase(limit=1024, norm_input=False, device=dev)
-        err, weights, n_rows = collect_rollouts(mpc, layer, db, *start(), T, push=push, **kw, **more)
+        err, weights, n_rows = collect_rollouts(mpc, quadruped_layer, db, *start(), T, push=push, **kw, **more)
         torch.cuda.synchronize()
         return dict(err=err, weights=weights, n_rows=n_rows, failed=mpc.failed, db=db)
 
@@ -199,7 +180,7 @@ def test_collection_with_windows_appends_the_rows_and_weights_of_the_uniform_run
     rows = 0
     for b in range(B):
         ref = collect(dict(start=float(JUMP["start"][b]), duration=float(JUMP["duration"][b]), force=F))
-        assert row_equal(got, ref, b, ("err", "weights", "failed")), b
+        assert rows_equal(got, ref, b, ("err", "weights", "failed")), b
         assert float(ref["err"][b].max()) > 0.0 or b in (0, 3)        # the pushed rollouts leave the nominal one
         rows += STEPS * REPLANS if float(ref["weights"][b].max()) > 0 else 0      # an invalid rollout has weight 0 and appends nothing
     assert got["n_rows"] == len(got["db"]) == rows

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.plant_helpers import expert, standing_start
 from tests.solve_helpers import policy_pair, rel
 
 pytestmark = pytest.mark.gpu
@@ -242,16 +243,14 @@ def test_the_weight_column_rides_the_ring(tmp_path):
 # 0.8 s, rollout 0 unpushed (the nominal), rollout 1 pushed down at 70 N, the posture predicates in the terminate mask so that
 # some rollouts end early and are left out.
 def _controller(B, dev):
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
-    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
+    mpc = expert(dev, B, n_nodes=30)
     mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
     return mpc
 
 
 def _start(B, seed=2):
-    from iterative_learning_nmpc_amd import wholebody as wbk
     rng = np.random.default_rng(seed)
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B, 12))
+    q0 = standing_start(B)[0]; q0[:, 6:] += rng.normal(0, 0.03, (B, 12))
     return rng, q0, np.zeros((B, 18))
 
 

@@ -12,85 +12,34 @@ survival under the reference's predicates, not only finite rows."""
 import numpy as np
 import pytest
 
-from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.plant_helpers import FIVE, N_SUB, ONE, SHIFT, SOLVER, STEPS, THREE, TWO
+from tests.plant_helpers import chain_of_public_calls, default_plant as plant, expert as controller, plant_rollout as rollout  # noqa: F401
+from tests.plant_helpers import quadruped_layer, standing_start as start  # noqa: F401
 from tests.solve_helpers import dev  # noqa: F401
 from tests.torque_helpers import bits, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-STEPS, N_SUB = 40, 2
-ONE, TWO, THREE, FIVE = 0.0395, 0.0795, 0.1195, 0.1995
-SOLVER, HEIGHT, COLLISION, SHIFT = 1, 8, 32, 8
+HEIGHT, COLLISION = 8, 32                                 # bits of `failed`
 SENTINEL = -77.0
 
 
 @pytest.fixture(scope="module")
-def layer(dev):
-    from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer
-    return BatchedTorqueLayer(**quadruped_tree(), device=dev)
-
-
-def controller(dev, B=3):
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
-    return LocomotionMPC(print_info=False, device=dev, batch=B, force_reference="gravity_share")
-
-
-def start(B=3):
-    from iterative_learning_nmpc_amd import wholebody as wbk
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME
-    return q0, np.zeros((B, 18))
-
-
-def plant():
-    from iterative_learning_nmpc_amd.torque import GroundContact
-    return GroundContact()
-
-
-def rollout(mpc, L, q0, v0, T, **kw):
-    S = mpc.open_loop_device(q0, v0, T, torque_layer=L, plant=plant(), plant_substeps=N_SUB, **kw)
-    return dict(S=S, A=mpc.actions, q=mpc.q_final, v=mpc.v_final, failed=mpc.failed, X=mpc._X_dev.clone(), U=mpc._U_dev.clone(),
-                ref=np.array(mpc.base_ref_vel_tracking), status=mpc.status_dev)
-
-
-@pytest.fixture(scope="module")
-def one(dev, layer):
+def one(dev, quadruped_layer):
     """one replan from the standing start: shared by the tests that compare with it"""
     mpc = controller(dev)
     q0, v0 = start()
     assert mpc.replanning_steps == STEPS and mpc.replan_clock(ONE)[0] == STEPS and len(mpc.replan_clock(ONE)[1]) == 1
-    out = rollout(mpc, layer, q0, v0, ONE)
+    out = rollout(mpc, quadruped_layer, q0, v0, ONE)
     torch.cuda.synchronize()
     return dict(out, mpc=mpc, q0=q0, v0=v0)
 
 
-def chain_of_public_calls(mpc, L, X, U, q0, v0, status, replan=0, mask=None):
-    """labels -> track -> observe of one replan through the Python layer, then the harness' bookkeeping -> S, A, q, v, failed"""
-    from iterative_learning_nmpc_amd.config import COLLISION_HEIGHT, TERMINATE_DEFAULT
-    mask = TERMINATE_DEFAULT if mask is None else mask
-    d = L.device
-    zoh = mpc.id_repeat[:STEPS]
-    A = L.plan_actions(X, U, zoh, mpc.config_opt.time_horizon / mpc.config_opt.n_nodes, mpc.sim_dt, kp=mpc.Kp, kd=mpc.Kd)
-    q = torch.as_tensor(np.array(q0), dtype=torch.float32, device=d).contiguous()
-    v = torch.as_tensor(np.array(v0), dtype=torch.float32, device=d).contiguous()
-    q, v, Q, V = L.contact_track(q, v, A, mpc.sim_dt / N_SUB, N_SUB, kp=mpc.Kp, kd=mpc.Kd, ground=plant())
-    failed = torch.zeros(q.shape[0], dtype=torch.int32, device=d)
-    period = float(mpc.config_gait.nominal_period)
-    S = L.observe_rows(Q, V, replan * STEPS * mpc.sim_dt, mpc.sim_dt, period, collision_height=COLLISION_HEIGHT, failed=failed, step_index=replan)
-    # the advance kernel: the solver bit (status NaN = 1, QP failure = 4), then the one stamping rule
-    failed |= ((status == 1) | (status == 4)).to(torch.int32) * SOLVER
-    stamp = ((failed & mask) != 0) & ((failed >> SHIFT) == 0)
-    failed = torch.where(stamp, failed | ((replan + 1) << SHIFT), failed)
-    # the observation of the final state
-    L.observe(q, v, (replan + 1) * STEPS * mpc.sim_dt, period, torch.zeros(q.shape[0], 0, device=d), collision_height=COLLISION_HEIGHT,
-              failed=failed, step_index=replan, term_mask=mask)
-    return S, A, q, v, failed
-
-
 # ---- 1. one replan is the chain of public calls -------------------------------------------------------------------------------------
-def test_one_replan_is_the_chain_of_public_calls(layer, one):
+def test_one_replan_is_the_chain_of_public_calls(quadruped_layer, one):
     o = one
-    S, A, q, v, failed = chain_of_public_calls(o["mpc"], layer, o["X"], o["U"], o["q0"], o["v0"], o["status"])
+    S, A, q, v, failed = chain_of_public_calls(o["mpc"], quadruped_layer, o["X"], o["U"], o["q0"], o["v0"], o["status"])
     got = (o["S"], o["A"], o["q"], o["v"])
     print("one replan: largest |rollout - chain| of S, A, q, v:", [float((a - b).abs().max()) for a, b in zip(got, (S, A, q, v))],
           "failed", o["failed"].tolist(), "chain", failed.tolist(), "status", o["status"].tolist())
@@ -99,15 +48,15 @@ def test_one_replan_is_the_chain_of_public_calls(layer, one):
     assert torch.equal(o["failed"], failed)
     assert bool(torch.isfinite(o["S"]).all()) and bool(torch.isfinite(o["A"]).all())
     # row 0 is the state the rollout started from, before any simulation step: z and the joints of the start state
-    assert same(o["S"][:, 0, 19], torch.as_tensor(o["q0"][:, 2], dtype=torch.float32, device=layer.device))
-    assert same(o["S"][:, 0, 24:36], torch.as_tensor(o["q0"][:, 6:], dtype=torch.float32, device=layer.device))
+    assert same(o["S"][:, 0, 19], torch.as_tensor(o["q0"][:, 2], dtype=torch.float32, device=quadruped_layer.device))
+    assert same(o["S"][:, 0, 24:36], torch.as_tensor(o["q0"][:, 6:], dtype=torch.float32, device=quadruped_layer.device))
     # and it is not the plan-following rollout
-    plain = controller(layer.device)
+    plain = controller(quadruped_layer.device)
     assert not same(plain.open_loop_device(o["q0"], o["v0"], ONE), o["S"])
 
 
 # ---- 2. replans in one call and in several --------------------------------------------------------------------------------------------
-def test_three_replans_in_one_call_start_as_one_replan_does(dev, layer, one):
+def test_three_replans_in_one_call_start_as_one_replan_does(dev, quadruped_layer, one):
     """Three replans in one call against calls of one replan.  The harness has no bit-for-bit continuation across calls, with
     or without a plant: the host's float clock (`replan_clock`) restarts with every call, so three calls of one replan solve at
     the optimisation nodes [0, 0, 0] where one call of three solves at [0, 1, 2], and the recorded phase and the push window
@@ -119,10 +68,10 @@ def test_three_replans_in_one_call_start_as_one_replan_does(dev, layer, one):
     long = controller(dev)
     steps, nodes, _ = long.replan_clock(THREE)
     assert steps == 3 * STEPS and nodes == [0, 1, 2]
-    lo = rollout(long, layer, q0, v0, THREE)
+    lo = rollout(long, quadruped_layer, q0, v0, THREE)
     assert lo["S"].shape == (3, 3 * STEPS, 44) and lo["A"].shape == (3, 3 * STEPS, 12)
     assert same(lo["S"][:, :STEPS], one["S"]) and same(lo["A"][:, :STEPS], one["A"])
-    row = layer.observe_rows(one["q"][:, None, :], one["v"][:, None, :], STEPS * long.sim_dt, long.sim_dt, float(long.config_gait.nominal_period),
+    row = quadruped_layer.observe_rows(one["q"][:, None, :], one["v"][:, None, :], STEPS * long.sim_dt, long.sim_dt, float(long.config_gait.nominal_period),
                              collision_height=COLLISION_HEIGHT)
     assert same(row[:, 0], lo["S"][:, STEPS])
     assert bool(torch.isfinite(lo["S"]).all()) and bool(torch.isfinite(lo["A"]).all()) and int((lo["failed"] >> SHIFT).max()) == 0
@@ -132,12 +81,12 @@ def test_three_replans_in_one_call_start_as_one_replan_does(dev, layer, one):
 
 
 # ---- 3. termination -------------------------------------------------------------------------------------------------------------------
-def test_a_robot_on_the_ground_terminates_and_freezes_and_the_others_do_not_notice(dev, layer):
+def test_a_robot_on_the_ground_terminates_and_freezes_and_the_others_do_not_notice(dev, quadruped_layer):
     q0, v0 = start()
-    healthy = rollout(controller(dev), layer, q0, v0, THREE)
+    healthy = rollout(controller(dev), quadruped_layer, q0, v0, THREE)
     low = q0.copy(); low[1, 2] = 0.05
-    got = rollout(controller(dev), layer, low, v0, THREE)
-    first = rollout(controller(dev), layer, low, v0, ONE)
+    got = rollout(controller(dev), quadruped_layer, low, v0, THREE)
+    first = rollout(controller(dev), quadruped_layer, low, v0, ONE)
     f = got["failed"].cpu().numpy()
     print("robot 1 starts at 0.05 m: failed", f, "stamps", f >> SHIFT)
     assert f[1] & COLLISION and (f[1] >> SHIFT) == 1
@@ -150,7 +99,7 @@ def test_a_robot_on_the_ground_terminates_and_freezes_and_the_others_do_not_noti
 
 
 # ---- 4. the last interval is observed ---------------------------------------------------------------------------------------------------
-def test_a_robot_that_falls_in_the_last_interval_is_seen(dev, layer):
+def test_a_robot_that_falls_in_the_last_interval_is_seen(dev, quadruped_layer):
     """A robot thrown upwards from z = 0.43 m leaves the height band [0.18, 0.45] at a time that grows as the speed falls; the
     speed at which it does so between the last recorded row (the state before step 39) and the state after step 39 is found
     by bisection on the rollout itself, three speeds per try (a ballistic base crosses at 0.31 m/s with 0.70 m/s at the start:
@@ -163,7 +112,7 @@ def test_a_robot_that_falls_in_the_last_interval_is_seen(dev, layer):
     for attempt in range(6):
         speeds = lo + (hi - lo) * np.array([0.25, 0.5, 0.75])
         v = v0.copy(); v[:, 2] = speeds
-        out = rollout(controller(dev), layer, q0, v, ONE, terminate_mask=mask)
+        out = rollout(controller(dev), quadruped_layer, q0, v, ONE, terminate_mask=mask)
         z_rows, z_end, f = out["S"][:, :, 19].cpu().numpy(), out["q"][:, 2].cpu().numpy(), out["failed"].cpu().numpy()
         above = (z_rows > 0.45).sum(1) + (z_end > 0.45)
         print(f"try {attempt}: speeds {speeds}, states above the band {above}, final z {z_end}, failed {f}")
@@ -182,20 +131,20 @@ def test_a_robot_that_falls_in_the_last_interval_is_seen(dev, layer):
 
 
 # ---- 5. detaching, refusals -----------------------------------------------------------------------------------------------------------
-def test_detach_restores_the_plan_following_rollout(dev, layer):
+def test_detach_restores_the_plan_following_rollout(dev, quadruped_layer):
     q0, v0 = start()
     mpc = controller(dev)
     s = mpc.solver._device_solver()
-    s.set_rollout_plant(layer, plant(), N_SUB, mpc.Kp, mpc.Kd, s.to_device(mpc.id_repeat[:STEPS], torch.int32))
+    s.set_rollout_plant(quadruped_layer, plant(), N_SUB, mpc.Kp, mpc.Kd, s.to_device(mpc.id_repeat[:STEPS], torch.int32))
     s.set_rollout_plant(None)
-    S = mpc.open_loop_device(q0, v0, TWO, torque_layer=layer)
+    S = mpc.open_loop_device(q0, v0, TWO, torque_layer=quadruped_layer)
     fresh = controller(dev)
-    Sf = fresh.open_loop_device(q0, v0, TWO, torque_layer=layer)
+    Sf = fresh.open_loop_device(q0, v0, TWO, torque_layer=quadruped_layer)
     assert same(S, Sf) and same(mpc.actions, fresh.actions) and torch.equal(mpc.failed, fresh.failed)
     assert same(mpc.q_final, fresh.q_final) and same(mpc._X_dev, fresh._X_dev) and same(mpc._U_dev, fresh._U_dev)
 
 
-def test_refusals_launch_nothing(dev, layer, one):
+def test_refusals_launch_nothing(dev, quadruped_layer, one):
     from iterative_learning_nmpc_amd._lib import NmpcError
     from iterative_learning_nmpc_amd.torque import BatchedTorqueLayer, GroundContact
     q0, v0 = one["q0"], one["v0"]
@@ -212,7 +161,7 @@ def test_refusals_launch_nothing(dev, layer, one):
 
     def refused(match, **kw):
         n = len(rows)
-        args = dict(torque_layer=layer, plant=plant(), plant_substeps=N_SUB)
+        args = dict(torque_layer=quadruped_layer, plant=plant(), plant_substeps=N_SUB)
         args.update(kw)
         with pytest.raises(NmpcError, match=match):
             mpc.open_loop_device(q0, v0, ONE, **args)
@@ -233,12 +182,12 @@ def test_refusals_launch_nothing(dev, layer, one):
     s.set_rollout_plant = attach
     # the refused calls left nothing behind: the same controller now does what a fresh one did
     s._rollout_io = io
-    out = rollout(mpc, layer, q0, v0, ONE)
+    out = rollout(mpc, quadruped_layer, q0, v0, ONE)
     assert all(same(out[k], one[k]) for k in ("S", "A", "q", "v", "X", "U")) and torch.equal(out["failed"], one["failed"])
 
 
 # ---- 6. collection, standing ----------------------------------------------------------------------------------------------------------
-def test_collect_rollouts_on_the_plant_fills_the_database(dev, layer):
+def test_collect_rollouts_on_the_plant_fills_the_database(dev, quadruped_layer):
     from iterative_learning_nmpc_amd.collect import collect_rollouts
     from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT
     from iterative_learning_nmpc_amd.database import DeviceDatabase
@@ -246,7 +195,7 @@ def test_collect_rollouts_on_the_plant_fills_the_database(dev, layer):
     low = q0.copy(); low[1, 2] = 0.05                             # one rollout is invalid
     mpc = controller(dev)
     db = DeviceDatabase(limit=4096, device=dev)
-    err, weights, n_rows = collect_rollouts(mpc, layer, db, low, v0, TWO, plant=plant(), plant_substeps=N_SUB)
+    err, weights, n_rows = collect_rollouts(mpc, quadruped_layer, db, low, v0, TWO, plant=plant(), plant_substeps=N_SUB)
     S, A = mpc.states, mpc.actions
     K = S.shape[1]
     valid = (mpc.failed & TERMINATE_DEFAULT) == 0
@@ -254,12 +203,12 @@ def test_collect_rollouts_on_the_plant_fills_the_database(dev, layer):
     assert K == 2 * STEPS and valid.tolist() == [True, False, True] and n_rows == 2 * K and len(db) == 2 * K
     assert torch.equal(db.tables["states"][:len(db)], S[valid].reshape(-1, 44))
     assert torch.equal(db.tables["actions"][:len(db)], A[valid].reshape(-1, 12))
-    reference = rollout(controller(dev), layer, low, v0, TWO)
+    reference = rollout(controller(dev), quadruped_layer, low, v0, TWO)
     assert same(S, reference["S"]) and same(A, reference["A"])
     assert bool((weights[~valid] == 0).all()) and err.shape == (3, K)
 
 
-def test_the_standing_expert_survives_on_the_plant(dev, layer):
+def test_the_standing_expert_survives_on_the_plant(dev, quadruped_layer):
     """the standing case of the measured table at B = 3, T = 0.2 s (5 replans), under the predicates of that table: solver,
     collision, height band [0.18, 0.45] m, roll and pitch within 25 degrees.  The B = 64, 1 s run survives entirely."""
     from iterative_learning_nmpc_amd.config import TERMINATE_DEFAULT
@@ -267,7 +216,7 @@ def test_the_standing_expert_survives_on_the_plant(dev, layer):
     q0, v0 = start()
     mpc = controller(dev)
     assert len(mpc.replan_clock(FIVE)[1]) == 5
-    out = rollout(mpc, layer, q0, v0, FIVE, terminate_mask=mask)
+    out = rollout(mpc, quadruped_layer, q0, v0, FIVE, terminate_mask=mask)
     f = out["failed"].cpu().numpy()
     z = out["S"][:, :, 19]
     survived = (f >> SHIFT) == 0

@@ -15,6 +15,7 @@ import pytest
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
 from tests import crba_reference as cr
 from tests import wb_momentum_reference as mr
+from tests.plant_helpers import expert
 from tests.solve_helpers import dev, rel  # noqa: F401
 from tests.torque_helpers import held, layer, same
 
@@ -33,9 +34,8 @@ RY_FREG = 52                              # the force rows of a stage reference:
 def controller(dev, L=None, batch=1, n_nodes=None, tree=True):
     """a gravity_share controller: articulated on layer L with x0's momentum from the tree (tree=False: from the declared map,
     the state an articulated controller starts in), or declared without a layer"""
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
     kw = dict(momentum_model="articulated", torque_layer=L) if L is not None else {}
-    mpc = LocomotionMPC(print_info=False, device=dev, batch=batch, n_nodes=n_nodes, force_reference="gravity_share", **kw)
+    mpc = expert(dev, batch, n_nodes=n_nodes, **kw)
     if L is not None and tree:
         mpc.set_state_momentum("tree")
     return mpc

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from iterative_learning_nmpc_amd.workloads import quadruped_tree
+from tests.plant_helpers import expert, standing_start
 from tests.solve_helpers import dev  # noqa: F401
 from tests.torque_helpers import same
 
@@ -28,8 +29,7 @@ def layer(dev):
 
 
 def controller(dev):
-    from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
-    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
+    mpc = expert(dev, B, n_nodes=30)
     assert mpc.replanning_steps == STEPS and mpc.sim_dt == 1.0e-3
     return mpc
 
@@ -37,8 +37,7 @@ def controller(dev):
 def start(low=None):
     """standing at Q_HOME, the joints of robot b moved by fixed small amounts; low: that robot lies on the ground (the fixture
     state of tests/test_gpu_wb_plant_rollout.py: base at 0.05 m)"""
-    from iterative_learning_nmpc_amd import wholebody as wbk
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME
+    q0 = standing_start(B)[0]
     for b in range(B):
         q0[b, 6:] += 0.01 * b * np.array([1, -1, 1, -1, 1, -1, 1, 1, -1, -1, 1, 1], float)
     if low is not None:

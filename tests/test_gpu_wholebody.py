@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from iterative_learning_nmpc_amd import workloads as wl  # noqa: E402
+from tests.plant_helpers import expert, standing_start
 from tests.solve_helpers import dev, gpu_solve, make_solver, oracle_solve, rel  # noqa: E402,F401
 
 
@@ -386,13 +387,13 @@ def test_wholebody_device_rollouts_batch_and_termination(dev):
     from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
     B, T = 24, 0.8
     rng = np.random.default_rng(2)
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B, 12))
+    q0 = standing_start(B)[0]; q0[:, 6:] += rng.normal(0, 0.03, (B, 12))
     v0 = np.zeros((B, 18))
     force = rng.uniform(-1, 1, (B, 3)); force /= np.linalg.norm(force, axis=1, keepdims=True); force *= rng.uniform(50, 70, (B, 1))
     force[0] = 0.0
     force[1] = [0.0, 0.0, -70.0]
     push = dict(start=0.2, duration=0.3, force=force)
-    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
+    mpc = expert(dev, B, n_nodes=30)
     mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
     S = mpc.open_loop_device(q0, v0, T, push=push, record_sim_steps=False)
     torch.cuda.synchronize()
@@ -406,7 +407,7 @@ def test_wholebody_device_rollouts_batch_and_termination(dev):
         i = (f[b] >> 8) - 1
         assert (Sn[b, i:] == Sn[b, i]).all() and Sn[b, i, 19] < 0.08
     n = 3
-    small = LocomotionMPC(print_info=False, device=dev, batch=n, n_nodes=30, force_reference="gravity_share")
+    small = expert(dev, n, n_nodes=30)
     small.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
     Ss = small.open_loop_device(q0[:n], v0[:n], T, push=dict(push, force=force[:n]), record_sim_steps=False)
     assert np.array_equal(Ss.cpu().numpy(), Sn[:n]) and np.array_equal(small.failed.cpu().numpy(), f[:n])
@@ -421,14 +422,14 @@ def test_wholebody_device_rollouts_full_size(dev):
     from iterative_learning_nmpc_amd.mpc_wholebody import LocomotionMPC
     B, T = 8192, 2.0
     rng = np.random.default_rng(5)
-    q0 = np.zeros((B, 18)); q0[:, 2] = 0.30; q0[:, 6:] = wbk.Q_HOME + rng.normal(0, 0.03, (B, 12))
+    q0 = standing_start(B)[0]; q0[:, 6:] += rng.normal(0, 0.03, (B, 12))
     v0 = np.zeros((B, 18))
     force = rng.uniform(-1, 1, (B, 3)); force /= np.linalg.norm(force, axis=1, keepdims=True); force *= rng.uniform(50, 70, (B, 1))
     force[0] = 0.0
     copies = np.array([1000, 4095, 4096, 8191])                  # rollout 7, again, in other waves / rounds of the launch
     q0[copies], force[copies] = q0[7], force[7]
     push = dict(start=0.2, duration=0.3, force=force)
-    mpc = LocomotionMPC(print_info=False, device=dev, batch=B, n_nodes=30, force_reference="gravity_share")
+    mpc = expert(dev, B, n_nodes=30)
     mpc.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
     S = mpc.open_loop_device(q0, v0, T, push=push, record_sim_steps=False)
     torch.cuda.synchronize()
@@ -447,7 +448,7 @@ def test_wholebody_device_rollouts_full_size(dev):
     for cidx in copies:
         assert np.array_equal(Sn[cidx], Sn[7]) and f[cidx] == f[7]
     n = 16
-    small = LocomotionMPC(print_info=False, device=dev, batch=n, n_nodes=30, force_reference="gravity_share")
+    small = expert(dev, n, n_nodes=30)
     small.set_command(np.array([0.2, 0.0, 0.0]), 0.0)
     Ss = small.open_loop_device(q0[:n], v0[:n], T, push=dict(push, force=force[:n]), record_sim_steps=False)
     assert np.array_equal(Ss.cpu().numpy(), Sn[:n]) and np.array_equal(small.failed.cpu().numpy(), f[:n])

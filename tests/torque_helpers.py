@@ -1,6 +1,7 @@
 """What the torque-layer tests share (helper module, not collected by pytest): the device layer of an oracle tree, the device
-ground of a reference ground, host copies and bit patterns of tensors, the accuracy bar of the contact plant with the standing
-case it is asserted on, and the fp64 oracle labels of a whole-body plan.  Case tables and assertions stay in the test files."""
+ground of a reference ground, host copies and bit patterns of tensors, the accuracy bar of the contact plant on a whole array
+(`held`) and per sample and column (`fractions`), the cases it is asserted on with the one way to put their feet at a height,
+and the fp64 oracle labels of a whole-body plan.  Case tables and assertions stay in the test files."""
 import os
 
 import numpy as np
@@ -8,6 +9,7 @@ import numpy as np
 from iterative_learning_nmpc_amd import references as refs
 from tests import contact_reference as cr
 from tests import fd_reference as fr
+from tests import push_reference as pr
 
 BAR = 1e-5
 
@@ -41,6 +43,13 @@ def same(a, b):
     return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
+def rows_equal(got, ref, b, keys=None):
+    """row b of every output of two calls (tuples, or dicts read at `keys`) is the same bits; int32 outputs the same values"""
+    import torch
+    pairs = zip(got, ref) if keys is None else ((got[k], ref[k]) for k in keys)
+    return all(torch.equal(x[b], y[b]) if x.dtype == torch.int32 else same(x[b], y[b]) for x, y in pairs)
+
+
 def bar(ref, f32):
     """the accuracy bar of an array: max(1e-5 of its largest |reference|, 4 x the float32 run's deviation)"""
     return max(BAR * np.abs(ref).max(), 4 * np.abs(f32.astype(np.float64) - ref).max())
@@ -52,10 +61,48 @@ def held(name, got, ref, f32):
     return err <= b                     # <=: an array whose reference is all zeros has to come out as zeros
 
 
+def fractions(what, got, ref, f32):
+    """the bar on an array [B, ...], stricter than `held`: `bar` of every sample (scale: the sample's largest |ref|) and of every
+    column (scale: the column's largest |ref| over the batch) -> the worst error as a fraction of its bar"""
+    n = ref.shape[0]
+    got, ref, f32 = (np.asarray(x).reshape(n, -1) for x in (got, ref, f32))
+    assert got.shape == ref.shape == f32.shape and np.isfinite(got).all() and np.isfinite(ref).all(), what
+    got = got.astype(np.float64)
+    worst = 0.0
+    for axis, label in ((1, "sample"), (0, "column")):
+        for i in range(ref.shape[1 - axis]):
+            g, r, f = (x[i] if axis == 1 else x[:, i] for x in (got, ref, f32))
+            err, b = np.abs(g - r).max(), bar(r, f)
+            frac = 0.0 if err == 0.0 else (np.inf if b == 0.0 else err / b)
+            if frac > 1.0:
+                print(f"    {what} {label} {i}: error {err:.3e} over its bar {b:.3e}")
+            worst = max(worst, frac)
+    print(f"  {what}: worst error {worst:.3f} of its bar (largest |gpu - ref64| {np.abs(got - ref).max():.3e}, float32 loop "
+          f"{np.abs(f32.astype(np.float64) - ref).max():.3e}, scale {np.abs(ref).max():.3e})")
+    return worst
+
+
 def branches(g, pos, vel, f):
     """(feet off the ground, feet pushed, feet in the ground that leave too fast to be pushed) of reference kinematics and forces"""
     inside = g.ground_z - pos[..., 2] > 0
     return int((~inside).sum()), int((inside & (f[..., 2] > 0)).sum()), int((inside & (f[..., 2] == 0)).sum())
+
+
+def lower_feet(m, q, want, slide=2, passes=1, dtype=None, tol=None):
+    """q [B, n] with joint `slide` (a vertical slider of the base) moved so that the lowest foot of robot b is at height want[b].
+    The correction is a float32 one; dtype: what q is cast to before it is corrected (None: q as it is), passes: a second pass
+    takes out what float32 left of the first, tol: the result is asserted to it."""
+    lift = (m.forward_kinematics(q[0])[0][slide] @ m.axis[slide])[2]                              # world z per unit of q[slide]
+    assert m.jtype[slide] == 1 and lift > 0.5
+    q = q.copy() if dtype is None else q.astype(dtype)
+    lowest = lambda: np.array([cr.feet(m, q[b])[0][:, 2].min() for b in range(len(q))])         # noqa: E731
+    for _ in range(passes):
+        q[:, slide] += ((want - lowest()) / lift).astype(np.float32)
+    assert tol is None or np.abs(lowest() - want).max() < tol
+    return q
+
+
+THREE_HEIGHTS = np.array([-0.003, 0.0, 0.02])             # the lowest foot of `Case` and of the grounds fixture: in, at, above
 
 
 class Case:
@@ -66,12 +113,7 @@ class Case:
         q, v, tau, _ = fr.inputs(m, B, seed)
         if g is None:                   # the quadruped: joint 2 slides the base, the lowest foot goes to -3 mm, 0, +2 cm in turn
             g = cr.Ground()
-            lowest = lambda: np.array([cr.feet(m, q[b])[0][:, 2].min() for b in range(B)])      # noqa: E731
-            want = np.array([-0.003, 0.0, 0.02])[np.arange(B) % 3]
-            lift = (m.forward_kinematics(q[0])[0][2] @ m.axis[2])[2]                              # world z per unit of q[2]
-            assert m.jtype[2] == 1 and lift > 0.5
-            q[:, 2] += ((want - lowest()) / lift).astype(np.float32)
-            assert np.abs(lowest() - want).max() < 1e-6
+            q = lower_feet(m, q, THREE_HEIGHTS[np.arange(B) % 3], tol=1e-6)
         self.g, self.q, self.v, self.tau = g, q, v, tau
         k64 = [cr.feet(m, q[b], v[b]) for b in range(B)]
         k32 = [cr.feet(m, q[b], v[b], np.float32) for b in range(B)]
@@ -81,6 +123,20 @@ class Case:
         assert self.f32.dtype == np.float32
         for x in (self.q, self.v, self.tau, self.pos, self.vel, self.f, self.pos32, self.vel32, self.f32):
             x.setflags(write=False)
+
+
+def general_case(m, B, seed):
+    """A tree whose joint 2 is no lift, on the soft ground tests/push_reference.py puts under its feet."""
+    q = fr.inputs(m, B, seed)[0]
+    g = pr.general_ground(m, q)
+    return Case(m, B, seed, g)
+
+
+def general_tree_case(m, B, seed):
+    """A tree whose joint 2 is no lift: the ground goes to the median height of the feet, so feet lie on both sides."""
+    q, v, _, _ = fr.inputs(m, B, seed)
+    z = np.median([cr.feet(m, q[b])[0][:, 2] for b in range(B)])
+    return Case(m, B, seed, cr.Ground(ground_z=float(np.float32(z))))
 
 
 # ---- oracle labels of a whole-body plan: plan_rows in fp64 -> oracle/torque_oracle.py on the declared tree -> (tau + kd v_j) / kp + q_j
