@@ -164,7 +164,10 @@ int nmpc_shift_solve_batch(void *handle, int B, int shift, const float *x0, cons
 /* One Riccati sweep on explicit stage data (the LQ core of the solve), dense row-major dev
  * inputs Q[B][N+1][nx][nx] R[B][N][nu][nu] q[B][N+1][nx] r[B][N][nu] A[B][N][nx][nx]
  * B_[B][N][nx][nu] d[B][N][nx] dx0[B][nx]; outputs dX[B][N+1][nx] dU[B][N][nu] status[B].
- * nx <= 15, nu <= 16.  Uses the handle's workspace: Bsz <= B_max, N == dims.N. */
+ * nx <= 15, nu <= 16, N == dims.N, Bsz <= B_max, on a handle of model 0 or 1 (NMPC_E_ARG otherwise).  Keeps two 16x16
+ * images per stage and problem (2 * N * 256 floats) in the handle's workspace, which nmpc_create sizes for B_max such
+ * problems whatever the model's own solve layout takes (nmpc_workspace_bytes >= B_max * 2 * N * 1024); the next solve
+ * on the handle clears the workspace first. */
 int nmpc_riccati_batch(void *handle, int Bsz, int nx, int nu, const float *Q, const float *R,
                        const float *q, const float *r, const float *A, const float *B_,
                        const float *d, const float *dx0, float *dX, float *dU, int *status,

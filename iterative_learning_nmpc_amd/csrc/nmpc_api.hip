@@ -454,7 +454,11 @@ int nmpc_create(const nmpc_dims* dims, int device_id, void** handle) {
     h->ws_stride = (dims->model_id == NMPC_MODEL_DOUBLE_INTEGRATOR) ? ws_floats_per_problem<nmpc::DoubleIntegrator>(dims->N)
                  : (dims->model_id == NMPC_MODEL_CENTROIDAL)      ? ws_floats_per_problem<nmpc::Centroidal>(dims->N)
                                                                   : nmpc::wb::WsLayout(dims->N).stride;
-    h->ws_bytes = (size_t)dims->B_max * h->ws_stride * sizeof(float);
+    // the kernels place problem b at b * ws_stride (their own WsLayout); nmpc_riccati_kernel places it at b * 2N tiles (K~', Acl~'),
+    // more than the double integrator's solve layout from N = 3 on: the allocation holds whichever is larger
+    size_t per_problem = h->ws_stride;
+    if (dims->model_id != NMPC_MODEL_WHOLEBODY) per_problem = std::max(per_problem, nmpc::riccati_ws_floats(dims->N));
+    h->ws_bytes = (size_t)dims->B_max * per_problem * sizeof(float);
     if (const int rc = allocate(h)) { nmpc_destroy(h); return rc; }
     *handle = h;
     return NMPC_OK;

@@ -15,6 +15,8 @@ struct RiccatiArgs {
     int* status;
     float* ws;   // per problem 2N tiles (K~', Acl~')
 };
+// floats of workspace one problem of the Riccati entry takes: what nmpc_create allocates per problem at the least
+__host__ __device__ constexpr size_t riccati_ws_floats(int N) { return (size_t)2 * N * TILE; }
 
 __global__ __launch_bounds__(64) void nmpc_riccati_kernel(const RiccatiArgs a) {
     __shared__ __attribute__((aligned(16))) float conv[CONV_FLOATS];
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(64) void nmpc_riccati_kernel(const RiccatiArgs a) {
     const float* A = a.A + (size_t)b * N * nx * nx;
     const float* Bm = a.Bm + (size_t)b * N * nx * nu;
     const float* d = a.d + (size_t)b * N * nx;
-    float* Kt = a.ws + (size_t)b * 2 * N * TILE;
+    float* Kt = a.ws + (size_t)b * riccati_ws_floats(N);
     float* Ct = Kt + (size_t)N * TILE;
 
     auto tileA = [&](int k, bool transposed) {   // A~ = [A d; 0 1] or its transpose

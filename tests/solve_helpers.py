@@ -20,6 +20,21 @@ def dev():
     return torch.device("cuda:0")
 
 
+def dense_lq(rng, B, nx, nu, N, a_scale=0.3):
+    """(Q, R, q, r, A, Bm, d, dx0) of B dense LQ problems in float64, the arguments of nmpc_riccati_batch and of the
+    oracle's riccati in their order: Q, R positive definite (eigenvalues >= 0.5), A = I + a perturbation of spectral
+    scale `a_scale`, everything else normal.  The draws come in one fixed order, so a seed names a batch."""
+    def spd(n, m):
+        M = rng.normal(0, 1, (B, m, n, n))
+        return M @ M.transpose(0, 1, 3, 2) / n + np.eye(n) * 0.5
+    Q, R = spd(nx, N + 1), spd(nu, N)
+    q, r = rng.normal(0, 1, (B, N + 1, nx)), rng.normal(0, 1, (B, N, nu))
+    A = np.eye(nx) + rng.normal(0, a_scale, (B, N, nx, nx)) / np.sqrt(nx)
+    Bm = rng.normal(0, 0.5, (B, N, nx, nu))
+    d, dx0 = rng.normal(0, 0.1, (B, N, nx)), rng.normal(0, 1, (B, nx))
+    return Q, R, q, r, A, Bm, d, dx0
+
+
 def make_solver(w, B, dev, *, precision=0, max_sqp_iter=1, n_ipm=6, nlp_tol=0.0, line_search=0):
     """A device solver for workload `w` and batches up to B, every option set explicitly (line_search = 0 is the handle's
     default; the whole-body model refuses line_search = 1 at the solve, not here)."""
