@@ -102,7 +102,7 @@ A handle_args(const Handle* h) {
     a.skip = h->skip_mask ? h->skip : nullptr; a.skip_mask = h->skip_mask;
     return a;
 }
-// ... and what each takes alone: the tile family (nmpc_solve.hip)
+// ... and what each takes alone: the tile family (SolveArgs, nmpc_solve_layout.hpp)
 nmpc::SolveArgs base_args(const Handle* h) {
     nmpc::SolveArgs a = handle_args<nmpc::SolveArgs>(h);
     for (int j = 0; j < 16; ++j)
@@ -246,7 +246,7 @@ int runs_by_robot(long long m0, int count, int K, int rows, Each each) {
     return NMPC_OK;
 }
 
-// Two variants of the QP kernel (nmpc_solve.hip, Lds).  Resident: stage arrays in the LDS (39.6 KB at N = 50: four waves per CU),
+// Two variants of the QP kernel (nmpc_qp.hip.inc; Lds, nmpc_solve_layout.hpp).  Resident: stage arrays in the LDS (39.6 KB at N = 50: four waves per CU),
 // pinned to one wave per SIMD -- the choice while the batch fits that many waves (B <= 4 x CUs: 2.2 M solves/s at B = 1024).
 // Lean: stage arrays in the workspace, 17.7 KB, two waves per SIMD -- the choice for larger batches, where the second wave fills
 // the first one's dependency stalls (2.7 M at B = 8192 against 2.3 M resident), for horizons whose resident layout does not

@@ -1,9 +1,9 @@
 // nmpc_wb.hip -- batched NMPC solve of the whole-body model (nx = 42, nu = 30) on gfx950: a blocked Riccati /
-// interior-point kernel family beside the 16x16 single-tile family of nmpc_solve.hip.
+// interior-point kernel family beside the 16x16 single-tile family of nmpc_solve.hip (nmpc_linearize.hip.inc, nmpc_qp.hip.inc).
 //
 // Replaces, for the problem the reference actually solves (q18 + v18 + h6 | a18 + f12, solver.py:88-92,405-418),
 // the per-step solve  QuadrupedAcadosSolver.solve -> acados SQP / HPIPM  (solver.py:396-403).  Two kernels per
-// SQP iteration, as in nmpc_solve.hip:
+// SQP iteration, as in the tile family (nmpc_linearize.hip.inc, nmpc_qp.hip.inc):
 //   nmpc_wb_linearize_kernel  one thread per (problem, node): foot kinematics with first and second
 //        derivatives, dynamics defect and its non-trivial Jacobian blocks, the scaled dense residual Jacobian
 //        Js = sqrt(W) [J | res] of the swing / contact / consistency rows as a compact record (cj_index), gradients of the
@@ -34,7 +34,7 @@
 #include "../../include/nmpc.h"
 #include "nmpc_wb_model.hpp"
 
-// Contraction off from here on (as in the QP kernel of nmpc_solve.hip), for every file of the family: every intended a*b + c is an
+// Contraction off from here on (as in the QP kernel of nmpc_qp.hip.inc), for every file of the family: every intended a*b + c is an
 // fmaf or an MFMA; what the backend would fuse on its own depends on the instantiation.
 #pragma clang fp contract(off)
 

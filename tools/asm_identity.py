@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Do two trees compile to the same device code?  (a refactor that claims to leave every kernel as the compiler saw it)
-    python tools/asm_identity.py [--pair OLD=NEW ...] <csrc dir A> <csrc dir B> [file.hip ...]        default file: nmpc_torque.hip
+    python tools/asm_identity.py [--pair OLD=NEW ...] <csrc dir A> <csrc dir B> [file.hip ...] [-- <compile flag> ...]
+                                                                                                  default file: nmpc_torque.hip
 Compiles the named files of both directories to gfx950 device assembly with the compile flags of csrc/build.sh plus
-`--cuda-device-only -S`, drops comments, directives and blank lines, numbers the local labels of each function in order of
+`--cuda-device-only -S` and whatever follows `--` (a diagnostic build: `-- -DNMPC_STAMPS`), drops comments, directives and blank lines, numbers the local labels of each function in order of
 appearance and compares the instruction stream function by function.  One line per kernel: its instruction count and `same`
 or the number of differing lines; exit status 1 on any difference.  `--pair OLD=NEW` (demangled names without their arguments,
 as the report prints them) compares function OLD of A with the differently named NEW of B, a kernel that became an instantiation
@@ -14,10 +15,15 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", 
          "-mllvm", "-amdgpu-mfma-vgpr-form", "--cuda-device-only", "-S"]
 
 
-def functions(csrc, name, tmp):
+def functions(csrc, name, tmp, extra=()):
     """{mangled name: [instruction lines]} of one source file"""
     asm = os.path.join(tmp, "out.s")
-    subprocess.run(["hipcc", *FLAGS, os.path.join(csrc, name), "-o", asm], check=True)
+    subprocess.run(["hipcc", *FLAGS, *extra, os.path.join(csrc, name), "-o", asm], check=True)
+    return parsed(asm)
+
+
+def parsed(asm):
+    """{mangled name: [instruction lines]} of a file of device assembly"""
     out, cur, labels = {}, None, {}
     for line in open(asm):
         line = re.sub(r"\s*(;|//).*", "", line).strip()
@@ -48,13 +54,16 @@ def main():
     while args and args[0] == "--pair":
         old, new = args[1].split("=", 1)
         pairs[new], args = old, args[2:]
+    extra = []
+    if "--" in args:
+        args, extra = args[:args.index("--")], args[args.index("--") + 1:]
     if len(args) < 2:
         sys.exit(__doc__)
     dir_a, dir_b, files = args[0], args[1], args[2:] or ["nmpc_torque.hip"]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         for f in files:
-            a, b = functions(dir_a, f, tmp), functions(dir_b, f, tmp)
+            a, b = functions(dir_a, f, tmp, extra), functions(dir_b, f, tmp, extra)
             mangled = {demangled(k): k for k in a}
             for new in [k for k in b if pairs.get(demangled(k)) in mangled]:      # NEW of B goes under OLD's mangled name
                 b[mangled[pairs[demangled(new)]]] = b.pop(new)

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # Diagnostic: duration of nmpc_linearize_kernel for timing builds of the library (wrong results, one cost
-# removed each: -DLIN_T_NOFLUSH / NOSTORE / NOTAIL in nmpc_solve.hip).
+# removed each: -DLIN_T_NOFLUSH / NOSTORE / NOTAIL in nmpc_linearize.hip.inc).
 #   tools/lin_timing.sh build     (anywhere: hipcc cross-compiles)  -> iterative_learning_nmpc_amd/libnmpc_t_<VARIANT>.so
 #   tools/lin_timing.sh           (GPU box) rocprofv3 averages per library; delete the variants afterwards
 if [ "${1:-}" = build ]; then
