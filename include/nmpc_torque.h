@@ -242,6 +242,42 @@ int nmpc_contact_set_grounds(void *torque, const float *rows, int n_rows);
  * [0, n_joints).  At a call of the first list, before any launch: B > n_rows.  rows = NULL detaches (n_rows, joint are not read). */
 int nmpc_contact_set_payloads(void *torque, const float *rows, int n_rows, int joint);
 
+/* An actuator per robot [decl] (the last part of the plant that the whole batch shared: a learner that outputs PD targets is
+ * sensitive to the gains those targets meet before anything else, and the nominal joints have neither passive damping nor rotor
+ * inertia).  rows: dev [n_rows][4], caller-owned, kept as a pointer and read in stream order at each launch; row b is
+ * (kp_b, kd_b, damping_b, armature_b) -- N m/rad, N m s/rad, N m s/rad, kg m^2 -- and applies to every actuated joint of robot b.
+ * While a table is attached one substep of robot b is
+ *   1. the motor torque  tau_i = clamp(tau_ff_i + kp_b (q_des_i - q_i) - kd_b v_i), the clamp being the law's tau_max (row b of
+ *      the table of grounds if one is attached, else the cfg); this is what tau_out reports.  kp, kd of the call are validated as
+ *      they are without a table and are not read for the law;
+ *   2. the joint torque handed to the dynamics  t_i = tau_i - damping_b v_i: passive, after the clamp, never cut by it;
+ *   3. the dynamics of the tree whose joint-space inertia is M(q) + armature_b on the diagonal entries of the actuated joints -- in
+ *      the articulated-body recursion the pivot of actuated joint i is S^T I^A S + armature_b; base joints are untouched;
+ *   4. under NMPC_INTEGRATOR_LINEARLY_IMPLICIT, M is M + D_b (D_b = armature_b on the actuated diagonal) in A and in
+ *      rhs = (M + D_b) a_exp - ..., and on the actuated joints the clamp did not cut  A_ii += dt (kd_b + damping_b) + dt^2 kp_b,
+ *      rhs_i -= dt kp_b v_i;  on the others (cut, or no q_des)  A_ii += dt damping_b only.
+ * The calls that READ the table -- robot b is driven by row b:
+ *   nmpc_contact_step_batch, nmpc_contact_track_batch, nmpc_policy_rollout_batch (through its step launches) and nmpc_wb_rollout_*
+ *   with a plant (nmpc_wb_rollout_set_plant, through its track launches),
+ * under either integrator, with or without a push, windows per robot, a table of grounds or a table of payloads.
+ * The calls that do NOT read the table -- they describe the nominal model and the nominal controller:
+ *   nmpc_fd_step_batch, nmpc_fd_accel_batch, nmpc_id_torques_batch, nmpc_mass_matrix_batch, nmpc_centroidal_batch,
+ *   nmpc_centroidal_derivatives_batch, nmpc_state_momentum_batch, nmpc_contact_forces_batch, nmpc_pd_torques_batch,
+ *   nmpc_pd_target_action_batch, nmpc_plan_actions_batch, nmpc_wb_label_states_batch.
+ * So the expert's labels (tau_id + kd v) / kp + q are formed with the nominal gains and the plant answers them with its own: the
+ * torque a label produces on robot b is not the torque the expert meant.  That mismatch is the point -- it is what a learner meets
+ * on a machine whose drives are not the nominal ones.
+ * The device does NOT validate the values of a row: a caller who bypasses the Python layer owns them (kp_b <= 0, a negative kd_b,
+ * damping_b or armature_b, or a value that is not finite gives NaN or a joint that drives itself).
+ * Launches: each plant call is ONE launch under either integrator, of one more instantiation of the chain kernel per integrator,
+ * in which every lane keeps its law, its payload and its actuator in a slot of its own behind the block's LDS slice (56 bytes per
+ * robot); the law is taken as under a table of payloads, the payload is row b of that table or nothing where none is attached, a
+ * push is taken as under a table of grounds.  With no table attached every call makes exactly the launches it makes without this
+ * entry point.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), what was attached staying: rows given and n_rows < 1.  At a call of the first list,
+ * before any launch: B > n_rows.  rows = NULL detaches (n_rows is not read). */
+int nmpc_contact_set_actuators(void *torque, const float *rows, int n_rows);
+
 /* The integrator of the contact plant [decl].  NMPC_INTEGRATOR_EXPLICIT (the default) is the step stated above, launch for launch.
  * NMPC_INTEGRATOR_LINEARLY_IMPLICIT takes the stiff terms -- ground stiffness and damping, the friction regulariser, the PD law --
  * at the end of the substep, linearised at its start.  One substep from (q, v):

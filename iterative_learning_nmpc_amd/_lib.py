@@ -112,6 +112,7 @@ SIGNATURES = {
     "nmpc_contact_set_push_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "nmpc_contact_set_grounds": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_contact_set_payloads": (c_int, [c_void_p, c_void_p, c_int, c_int]),
+    "nmpc_contact_set_actuators": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_contact_set_integrator": (c_int, [c_void_p, c_int]),
     "nmpc_observe_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),

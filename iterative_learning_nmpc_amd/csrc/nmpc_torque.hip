@@ -18,7 +18,7 @@
 // pass -- is nmpc_torque_crba.hip.inc; the correction of the plant's second integrator, which takes the stiff contact and PD terms
 // implicitly and spends that mass matrix on it, is nmpc_torque_implicit.hip.inc; the chain of control steps on the plant -- one
 // kernel text, instantiated for a table of PD targets tracked in one launch, for pushed substeps, for a push window per robot,
-// for the implicit integrator and for either integrator under a ground or a payload per robot -- is nmpc_torque_track.hip.inc, with
+// for the implicit integrator and for either integrator under a ground, a payload or an actuator per robot -- is nmpc_torque_track.hip.inc, with
 // the one rule of what lies behind an instantiation's slice, its LDS footprint and its block width; the centroidal momentum about an anchor
 // point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
@@ -398,6 +398,7 @@ struct Torque {
     Table grounds;                      // nmpc_contact_set_grounds: a law per robot in place of the plant calls' cfg
     Table payloads;                     // nmpc_contact_set_payloads: a point mass per robot on body `payload_joint` in the plant calls
     int payload_joint = 0;
+    Table actuators;                    // nmpc_contact_set_actuators: gains, joint damping and rotor inertia per robot in the plant calls
     int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
@@ -592,7 +593,8 @@ const char* plant_batch_refusal(const Torque* t, const nmpc_push_cfg& push, cons
     if (wins.first && !push.force) return "push windows: no push is attached (nmpc_contact_set_push)";
     if (wins.first && B > wins.rows) return "push windows: B exceeds rows";
     if (const char* why = grounds_batch_refusal(t, B)) return why;
-    return t->payloads.rows && B > t->payloads.n_rows ? "payloads: B exceeds n_rows" : nullptr;
+    if (t->payloads.rows && B > t->payloads.n_rows) return "payloads: B exceeds n_rows";
+    return t->actuators.rows && B > t->actuators.n_rows ? "actuators: B exceeds n_rows" : nullptr;
 }
 
 // A plant call that launch_whole below does not take is cut into runs of substeps that are all un-pushed -- launches of the
@@ -617,7 +619,8 @@ PushArgs chain_args(int B, int n_steps, int n_sub, float dt, const nmpc_contact_
 
 // one launch of a chain that is told its push -- the window `win` of the push's own, or with `wins` the robot's, in a call whose
 // substep 0 is substep s0 of their count -- and tests it per substep: the implicit chain, and either integrator under a table of
-// grounds or of payloads; under payloads the table of grounds may be absent (rows == nullptr: the call's own law).
+// grounds, of payloads or of actuators; under payloads the table of grounds may be absent (rows == nullptr: the call's own law),
+// under actuators the table of payloads too (payload_rows == nullptr: the zero row).
 template <class Args>
 int launch_stated(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins,
                   long long s0, void* stream) {
@@ -625,6 +628,7 @@ int launch_stated(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, co
     static_cast<PushArgs&>(p) = call;
     if constexpr (Args::grounds) p.rows = t->grounds.rows;
     if constexpr (Args::payloads) { p.payload_rows = t->payloads.rows; p.payload_joint = t->payload_joint; }
+    if constexpr (Args::actuators) p.actuator_rows = t->actuators.rows;
     if (win.hi > win.lo) { p.force = push.force; p.joint = push.joint; p.push_lo = win.lo; p.push_hi = win.hi; }
     if (wins.first) { p.force = push.force; p.joint = push.joint; p.win_first = wins.first; p.win_count = wins.count; p.win_s0 = s0; }
     return launch_chain(t, p, stream);
@@ -637,13 +641,15 @@ int launch_windowed(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, 
     return launch_chain(t, p, stream);
 }
 
-// Does a plant call run as one launch, and of which instantiation?  It does under a table of payloads (whatever the push and the
-// grounds), under a table of grounds (whatever the push), under the implicit integrator and under windows per robot: then that
+// Does a plant call run as one launch, and of which instantiation?  It does under a table of actuators (whatever the push, the
+// grounds and the payloads), under a table of payloads (whatever the push and the grounds), under a table of grounds (whatever the push), under the implicit integrator and under windows per robot: then that
 // launch is made, rc is its result and the answer is true.  Otherwise nothing is launched: the caller cuts the call at the window.
 bool launch_whole(Torque* t, const PushArgs& call, const nmpc_push_cfg& push, const Window& win, const nmpc_torque::PushWindows& wins,
                   long long s0, void* stream, int& rc) {
     const bool implicit = t->integrator == NMPC_INTEGRATOR_LINEARLY_IMPLICIT;
-    if (t->payloads.rows)
+    if (t->actuators.rows)
+        rc = implicit ? launch_stated<ImplicitActuatorsArgs>(t, call, push, win, wins, s0, stream) : launch_stated<ActuatorsArgs>(t, call, push, win, wins, s0, stream);
+    else if (t->payloads.rows)
         rc = implicit ? launch_stated<ImplicitPayloadsArgs>(t, call, push, win, wins, s0, stream) : launch_stated<PayloadsArgs>(t, call, push, win, wins, s0, stream);
     else if (t->grounds.rows)
         rc = implicit ? launch_stated<ImplicitGroundsArgs>(t, call, push, win, wins, s0, stream) : launch_stated<GroundsArgs>(t, call, push, win, wins, s0, stream);
@@ -1036,6 +1042,15 @@ int nmpc_contact_set_payloads(void* torque, const float* rows, int n_rows, int j
     }
     t->payloads = {};
     if (rows) { t->payloads = {rows, n_rows}; t->payload_joint = joint; }
+    return NMPC_OK;
+}
+
+int nmpc_contact_set_actuators(void* torque, const float* rows, int n_rows) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (rows && n_rows < 1) return fail(t, NMPC_E_ARG, "actuators: n_rows must be at least 1");      // what was attached stays
+    t->actuators = {};
+    if (rows) t->actuators = {rows, n_rows};
     return NMPC_OK;
 }
 

@@ -170,6 +170,33 @@ struct Loaded : Source {
     __device__ __forceinline__ V3 load_at() const { return {load->x, load->y, load->z}; }
 };
 
+// An actuator per robot (nmpc_contact_set_actuators, DESIGN.md 8d): the gains of the PD law, a passive joint damping and a reflected
+// rotor inertia on every actuated joint, row b of the attached table [n_rows][4] as it is.  Nothing of a row is validated here
+// (include/nmpc_torque.h).
+struct Actuator {
+    float kp, kd, damping, armature;
+};
+// what a lane of the actuator chains keeps behind the slice: its law, its payload (the zero row where no table of payloads is
+// attached) and its actuator.  Fourteen words: on the 64 banks of a wide read the 32 lanes of a block at that stride fall on 32
+// different banks (14 l mod 64 is one-to-one on l < 32); a one-word read or a write is banked on 32 (ds_read_b32 and
+// every ds_write on CDNA), where 14 l mod 32 takes 16 values and a slot word costs one more LDS cycle -- as the six words of a law and the ten
+// of a LaneLoad do (6 l, 10 l mod 32 take 16 values too).  The slot is read a few times per joint and substep beside the
+// hundreds of slice accesses of the recursion.
+struct LaneDrive {
+    ContactCfg c;
+    Payload load;
+    Actuator drive;
+};
+// a force source of the plant under the lane's actuator: the hook of fd_accel_body adds the rotor inertia to the pivot of the
+// actuated joints, i >= base
+template <class Source>
+struct Driven : Source {
+    const Actuator* drive;                                // in LDS, beside the lane's law and payload
+    int base;
+    static constexpr bool arms = true;
+    __device__ __forceinline__ float armature(int i) const { return i >= base ? drive->armature : 0.0f; }
+};
+
 struct ContactArgs {
     int B, n_sub;
     float dt, kp, kd;

@@ -69,6 +69,13 @@ template <class Force, class = void>
 struct force_loads : std::false_type {};
 template <class Force>
 struct force_loads<Force, std::void_t<decltype(Force::loads)>> : std::bool_constant<Force::loads> {};
+// A source may also arm the joints with a reflected rotor inertia (nmpc_contact_set_actuators, DESIGN.md 8d): with a member
+// `static constexpr bool arms = true` it has `armature(i)`, what the pivot of joint i gains (0 on a joint without an actuator):
+// the tree whose joint-space inertia is M(q) + diag(armature).  Read under `if constexpr` as the other two.
+template <class Force, class = void>
+struct force_arms : std::false_type {};
+template <class Force>
+struct force_arms<Force, std::void_t<decltype(Force::arms)>> : std::bool_constant<Force::arms> {};
 
 // the spatial inertia of a point mass mp at r, added to the FD_I slots of body i: A += mp (|r|^2 1 - r r^T), B += mp [r]x, C += mp 1
 template <class At>
@@ -203,7 +210,8 @@ __device__ __forceinline__ bool fd_accel_body(const Model& m, const Force& force
         const bool rev = m.type[i] == 0;
         const V3 U_n = rev ? mul(A, ax) : mul(Bm, ax), U_l = rev ? mul_t(Bm, ax) : mul(C, ax);
         const V3 p_n = at.get3(i, FD_P), p_l = at.get3(i, FD_P + 3);
-        const float d = dot(ax, rev ? U_n : U_l);
+        float d = dot(ax, rev ? U_n : U_l);
+        if constexpr (force_arms<Force>::value) d += force.armature(i);      // the rotor turns with the joint alone: S^T I^A S + armature
         const float u = at(i, FD_Q + 2) - dot(ax, rev ? p_n : p_l);
         sound = sound && d > 0.0f && d < INFINITY;
         at.put3(i, FD_RW, U_n); at.put3(i, FD_RW + 3, U_l);

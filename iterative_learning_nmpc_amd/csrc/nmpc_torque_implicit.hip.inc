@@ -25,13 +25,19 @@ constexpr size_t im_lds_bytes(int n) { return ((size_t)n * CT_SLOTS + im_triangl
 
 // no payload: what implicit_accel_body is given by a chain without one
 struct NoLoad {
-    static constexpr bool loads = false;
+    static constexpr bool loads = false, drives = false;
 };
 // the lane's payload on body `on`
 struct LaneLoaded {
     const Payload* load;
     int on;
-    static constexpr bool loads = true;
+    static constexpr bool loads = true, drives = false;
+};
+// the lane's payload and its actuator (nmpc_contact_set_actuators): the rotor inertia on the diagonal of the mass matrix, the
+// passive damping taken implicitly on every actuated joint; kp, kd of the call below are then the lane's own
+struct LaneDriven : LaneLoaded {
+    const Actuator* drive;
+    static constexpr bool drives = true;
 };
 
 // the law and a push that acts only in the substeps of its window
@@ -50,7 +56,9 @@ struct Triangle {
 // The implicit correction of one substep: from q, v, a_exp in slots FD_Q .. FD_Q + 2 of the slice (as fd_accel_body leaves them)
 // to a in slot FD_Q + 2.  unclamped: bit i set for an actuated joint i whose PD torque the clamp did not cut (0 without a PD
 // target).  Returns false if a pivot of the factorisation is not a positive finite number.
-// load: the payload whose inertia the mass matrix carries (NoLoad: none, and the text below compiles to what it was without it).
+// load: the payload whose inertia the mass matrix carries (NoLoad: none, and the text below compiles to what it was without it);
+// with Load::drives also the lane's actuator: M becomes M + armature on the actuated diagonal, in A and in rhs = (M + D) a_exp, and
+// every actuated joint gains dt damping on the diagonal whether the clamp cut its torque or not.
 template <int W, class Load = NoLoad>
 __device__ __forceinline__ bool implicit_accel_body(const Model& m, const ContactCfg& c, const Triangle<W> A, float dt, float kp, float kd,
                                                     unsigned unclamped, [[maybe_unused]] const Load load = {}) {
@@ -136,7 +144,10 @@ __device__ __forceinline__ bool implicit_accel_body(const Model& m, const Contac
         const V3 ax = v3(m.axis[i]);
         const bool rev = m.type[i] == 0;
         V3 F_n = rev ? mul(Ai, ax) : mul(Bm, ax), F_l = rev ? mul_t(Bm, ax) : mul(Ci, ax);
-        const float a_i = at(i, FD_Q + 2), d = dot(ax, rev ? F_n : F_l);
+        const float a_i = at(i, FD_Q + 2);
+        float d = dot(ax, rev ? F_n : F_l);
+        if constexpr (Load::drives)
+            if (i >= n - m.nu) d += load.drive->armature;
         A(i, i) = d;
         float acc = d * a_i;
         for (int frame = i, j = m.parent[i]; j >= 0; frame = j, j = m.parent[j]) {
@@ -189,8 +200,13 @@ __device__ __forceinline__ bool implicit_accel_body(const Model& m, const Contac
 
     // the PD law on the joints the clamp did not cut
     for (int i = n - m.nu; i < n; ++i) {
-        if (!((unclamped >> i) & 1u)) continue;
-        A(i, i) += dt * kd + dt * dt * kp;
+        if constexpr (Load::drives) {
+            if (!((unclamped >> i) & 1u)) { A(i, i) += dt * load.drive->damping; continue; }
+            A(i, i) += dt * (kd + load.drive->damping) + dt * dt * kp;
+        } else {
+            if (!((unclamped >> i) & 1u)) continue;
+            A(i, i) += dt * kd + dt * dt * kp;
+        }
         at(i, IM_R) -= dt * kp * at(i, FD_Q + 1);
     }
 

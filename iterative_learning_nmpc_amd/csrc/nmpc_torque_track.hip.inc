@@ -25,7 +25,7 @@ enum class Forces {
 
 // The un-pushed track: the state in q, v goes through n_steps control steps, in place.
 struct TrackArgs {
-    static constexpr bool step_io = false, implicit = false, grounds = false, payloads = false, lane_slots = false;
+    static constexpr bool step_io = false, implicit = false, grounds = false, payloads = false, actuators = false, lane_slots = false;
     static constexpr Forces forces = Forces::ground;
     using Slot = ContactCfg;                              // the block's law
     int B, n_steps, n_sub, a_rows, qv_rows, skip_mask;
@@ -114,13 +114,31 @@ struct PayloadsArgs : ImplicitPayloadsArgs {
     static constexpr Forces forces = Forces::either;
 };
 
+// An actuator per robot, nmpc_contact_set_actuators (DESIGN.md 8d): of the same family, the lane's slot now its law, its payload
+// and the four words of row b of the actuator table.  The law is taken as under PayloadsArgs (row b of the table of grounds, else
+// c); the payload is row b of the table of payloads, or the zero row where none is attached (payload_rows == nullptr: the hook adds
+// zeros).  The PD law reads the lane's kp, kd in place of the call's, the joint force loses damping v after the clamp, the
+// recursion runs under Driven<Loaded<>> sources, whose hook adds the rotor inertia to the pivots of the actuated joints, and the
+// implicit correction is handed the same four words.  One instantiation per integrator, one launch per call, the push stated and
+// taken as under a table of grounds.
+struct ImplicitActuatorsArgs : ImplicitPayloadsArgs {
+    static constexpr bool actuators = true;
+    using Slot = LaneDrive;                               // the lane's law, its payload and its actuator
+    const float* actuator_rows;                           // [>= B][4]: kp, kd, damping, armature
+};
+struct ActuatorsArgs : ImplicitActuatorsArgs {
+    static constexpr bool implicit = false;
+    static constexpr Forces forces = Forces::either;
+};
+
 // ---- the footprint of an instantiation ------------------------------------------------------------------------------------------
 template <class... Args>
 struct ArgsList {};
-using ChainArgs = ArgsList<TrackArgs, PushArgs, WindowArgs, ImplicitArgs, GroundsArgs, ImplicitGroundsArgs, PayloadsArgs, ImplicitPayloadsArgs>;
+using ChainArgs = ArgsList<TrackArgs, PushArgs, WindowArgs, ImplicitArgs, GroundsArgs, ImplicitGroundsArgs, PayloadsArgs, ImplicitPayloadsArgs,
+                           ActuatorsArgs, ImplicitActuatorsArgs>;
 
 // the LDS of a block of w robots of n joints: the slice, the triangle if implicit, then one slot or a slot per lane (six words
-// per lane fall on 32 different banks, as the ten of a LaneLoad do)
+// per lane fall on 32 different banks, as the ten of a LaneLoad and the fourteen of a LaneDrive do)
 template <class Args>
 constexpr size_t chain_lds_bytes(int n, int w) {
     return ((size_t)n * CT_SLOTS + (Args::implicit ? im_triangle(n) : 0)) * w * sizeof(float) + (Args::lane_slots ? w : 1) * sizeof(typename Args::Slot);
@@ -146,6 +164,9 @@ static_assert(chain_steps_width<TrackArgs>() && chain_steps_width<PushArgs>() &&
               "a chain of the cut path no longer runs at the width of contact_step_kernel");
 static_assert(chain_lds_bytes<GroundsArgs>(23, 32) == 159744 && chain_wide_joints<GroundsArgs>() == 23, "a law per lane: 23 joints x 32 robots");
 static_assert(chain_lds_bytes<PayloadsArgs>(23, 32) == 160256 && chain_wide_joints<PayloadsArgs>() == 23, "a law and a payload per lane: 23 joints x 32 robots");
+static_assert(sizeof(LaneDrive) == 56, "a law, a payload and an actuator per lane: 14 words");
+static_assert(chain_lds_bytes<ActuatorsArgs>(23, 32) == 160768 && chain_wide_joints<ActuatorsArgs>() == 23, "a law, a payload and an actuator per lane: 23 joints x 32 robots");
+static_assert(chain_lds_bytes<ImplicitActuatorsArgs>(MAXJ, IM_W) == 145280 && MAXJ == 32, "the implicit actuator chain of the largest tree at 16 robots per block");
 
 // ---- the chain ------------------------------------------------------------------------------------------------------------------
 // contact_step_kernel's substep, n_steps * n_sub times on the state in the slice: per control step the state goes out to row k
@@ -166,7 +187,11 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
     float* const behind = body + n * CT_SLOTS * W;
     ContactCfg* cfg = reinterpret_cast<ContactCfg*>(Args::implicit ? behind + (n * (n + 1) / 2) * W : behind);
     [[maybe_unused]] Payload* load = nullptr;             // Args::payloads: the lane's payload, beside its law
-    if constexpr (Args::payloads) {
+    [[maybe_unused]] Actuator* drive = nullptr;           // Args::actuators: the lane's actuator, beside the two
+    if constexpr (Args::actuators) {
+        LaneDrive* const lane = reinterpret_cast<LaneDrive*>(cfg) + threadIdx.x;
+        cfg = &lane->c; load = &lane->load; drive = &lane->drive;
+    } else if constexpr (Args::payloads) {
         LaneLoad* const lane = reinterpret_cast<LaneLoad*>(cfg) + threadIdx.x;
         cfg = &lane->c; load = &lane->load;
     } else if constexpr (Args::grounds) {
@@ -178,7 +203,16 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
     const int b = blockIdx.x * W + threadIdx.x;
     if (b >= p.B) return;
     if (p.skip && (p.skip[b] & p.skip_mask)) return;
-    if constexpr (Args::payloads) {
+    if constexpr (Args::actuators) {
+        *cfg = p.rows ? ground_row(p.rows, b) : p.c;
+        *load = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (p.payload_rows) {
+            const float* r = p.payload_rows + (size_t)b * 4;
+            *load = {r[0], r[1], r[2], r[3]};
+        }
+        const float* r = p.actuator_rows + (size_t)b * 4;
+        *drive = {r[0], r[1], r[2], r[3]};
+    } else if constexpr (Args::payloads) {
         *cfg = p.rows ? ground_row(p.rows, b) : p.c;
         const float* r = p.payload_rows + (size_t)b * 4;
         *load = {r[0], r[1], r[2], r[3]};
@@ -207,6 +241,9 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
         push_lo = p.push_lo; push_hi = p.push_hi;
         if (p.win_first) { push_lo = (long long)p.win_first[b] - p.win_s0; push_hi = push_lo + p.win_count[b]; }
     }
+    // the gains of the PD law: the call's, under Args::actuators the lane's (read where they lie, as the law is)
+    const auto kp = [&]() -> float { if constexpr (Args::actuators) return drive->kp; else return p.kp; };
+    const auto kd = [&]() -> float { if constexpr (Args::actuators) return drive->kd; else return p.kd; };
     const float nan = __builtin_nanf("");
 #pragma clang loop unroll(disable) vectorize(disable)
     for (int i = 0; i < n; ++i) { at(i, FD_Q) = qi[i]; at(i, FD_Q + 1) = vi[i]; }
@@ -231,17 +268,25 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
                 float t = 0.0f;
                 if (i >= base) {
                     t = tb ? tb[i - base] : 0.0f;
-                    if (!Args::step_io || db) t = t + p.kp * (db[i - base] - at(i, FD_Q)) + p.kd * (0.0f - at(i, FD_Q + 1));
+                    if (!Args::step_io || db) t = t + kp() * (db[i - base] - at(i, FD_Q)) + kd() * (0.0f - at(i, FD_Q + 1));
                     const float lim = cfg->tau_max;
                     if constexpr (Args::implicit)
                         if (db && (!(lim > 0.0f) || fabsf(t) < lim)) unclamped |= 1u << i;
                     if (lim > 0.0f) t = t > lim ? lim : (t < -lim ? -lim : t);      // a NaN stays NaN
                     if constexpr (Args::step_io)
                         if (last && to) to[i - base] = t;
+                    if constexpr (Args::actuators) t = t - drive->damping * at(i, FD_Q + 1);      // passive: after the clamp, never cut by it
                 }
                 at(i, FD_Q + 2) = t;
             }
-            if constexpr (Args::payloads && Args::forces == Forces::either) {
+            if constexpr (Args::actuators && Args::forces == Forces::either) {
+                if (sub >= push_lo && sub < push_hi)
+                    sound = fd_accel_body<W, CT_SLOTS>(m, Driven<Loaded<PushedGroundForces>>{{{{cfg, last ? fo : nullptr}, F, p.joint}, load, p.payload_joint}, drive, base}) && sound;
+                else
+                    sound = fd_accel_body<W, CT_SLOTS>(m, Driven<Loaded<GroundForces>>{{{cfg, last ? fo : nullptr}, load, p.payload_joint}, drive, base}) && sound;
+            } else if constexpr (Args::actuators) {
+                sound = fd_accel_body<W, CT_SLOTS>(m, Driven<Loaded<WindowedPushForces>>{{{{{cfg, last ? fo : nullptr}, F, p.joint}, on}, load, p.payload_joint}, drive, base}) && sound;
+            } else if constexpr (Args::payloads && Args::forces == Forces::either) {
                 if (sub >= push_lo && sub < push_hi)
                     sound = fd_accel_body<W, CT_SLOTS>(m, Loaded<PushedGroundForces>{{{cfg, last ? fo : nullptr}, F, p.joint}, load, p.payload_joint}) && sound;
                 else
@@ -260,10 +305,12 @@ __global__ __launch_bounds__(W) void contact_chain_kernel(const Model* __restric
             } else {
                 sound = fd_accel_body<W, CT_SLOTS>(m, WindowedPushForces{{{cfg, last ? fo : nullptr}, F, p.joint}, on}) && sound;
             }
-            if constexpr (Args::implicit && Args::payloads)
-                sound = implicit_accel_body<W>(m, *cfg, Triangle<W>{behind}, p.dt, p.kp, p.kd, unclamped, LaneLoaded{load, p.payload_joint}) && sound;
+            if constexpr (Args::implicit && Args::actuators)
+                sound = implicit_accel_body<W>(m, *cfg, Triangle<W>{behind}, p.dt, kp(), kd(), unclamped, LaneDriven{{load, p.payload_joint}, drive}) && sound;
+            else if constexpr (Args::implicit && Args::payloads)
+                sound = implicit_accel_body<W>(m, *cfg, Triangle<W>{behind}, p.dt, kp(), kd(), unclamped, LaneLoaded{load, p.payload_joint}) && sound;
             else if constexpr (Args::implicit)
-                sound = implicit_accel_body<W>(m, *cfg, Triangle<W>{behind}, p.dt, p.kp, p.kd, unclamped) && sound;
+                sound = implicit_accel_body<W>(m, *cfg, Triangle<W>{behind}, p.dt, kp(), kd(), unclamped) && sound;
 #pragma clang loop unroll(disable) vectorize(disable)
             for (int i = 0; i < n; ++i) {
                 const float v = at(i, FD_Q + 1) + p.dt * at(i, FD_Q + 2);

@@ -272,7 +272,8 @@ class LocomotionMPC:
         the call -- rollout b then stands on row b, the values of `plant` are ignored, and `collect_rollouts` and
         `learning_iteration`, which run this call, see the same table.  A payload per rollout likewise
         (`BatchedTorqueLayer.set_payloads`): the plant of rollout b carries row b, the plans and the labels are those of the
-        nominal model.
+        nominal model.  An actuator per rollout likewise (`BatchedTorqueLayer.set_actuators`): the plant of rollout b answers the
+        labels with the gains, the joint damping and the rotor inertia of row b, the labels are formed with the nominal kp, kd.
         push_as_force (needs plant): the push is a force on the trunk of the plant over the substeps its window covers
         (nmpc_wb_rollout_set_plant_push), where the feet and the torque limit answer it, instead of the velocity jump per
         replanning interval.

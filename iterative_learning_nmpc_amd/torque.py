@@ -149,6 +149,57 @@ def sample_payloads(n: int, seed: int, mass=(0.0, 5.0), offset=((-0.1, 0.1), (-0
     return payload_table(rows, n)
 
 
+ACTUATOR_COLUMNS = ("kp", "kd", "damping", "armature")     # a row of a table of actuators: the gains, the joint damping, the rotor inertia
+
+
+def actuator_table(actuators, B: int = 1) -> np.ndarray:
+    """Host input of `BatchedTorqueLayer.set_actuators` as a validated float32 array [>= B, 4] in the order of ACTUATOR_COLUMNS:
+    every value finite, kp positive, and kd, damping and armature not negative; a violation, a wrong shape or fewer than B rows
+    is a ValueError naming the first offending row."""
+    try:
+        rows = np.ascontiguousarray(np.asarray(actuators, dtype=np.float32))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"actuators: need a float array [B, {len(ACTUATOR_COLUMNS)}]") from e
+    B = max(int(B), 1)
+    if rows.ndim != 2 or rows.shape[1] != len(ACTUATOR_COLUMNS) or rows.shape[0] < B:
+        raise ValueError(f"actuators: expected [>= {B}, {len(ACTUATOR_COLUMNS)}], got {tuple(rows.shape)}")
+    checks = (("the actuator must be finite", ~np.isfinite(rows).all(axis=1)), ("kp must be positive", ~(rows[:, 0] > 0.0)),
+              ("kd must not be negative", ~(rows[:, 1] >= 0.0)), ("damping must not be negative", ~(rows[:, 2] >= 0.0)),
+              ("armature must not be negative", ~(rows[:, 3] >= 0.0)))
+    for why, bad in checks:
+        if bad.any():
+            raise ValueError(f"actuators: row {int(np.argmax(bad))}: {why}")
+    return rows
+
+
+def sample_actuators(n: int, seed: int, kp=(0.5 * KP, 1.5 * KP), kd=(0.5 * KD, 1.5 * KD), damping=(0.0, 0.2), armature=(0.0, 0.02)) -> np.ndarray:
+    """A table of actuators for `BatchedTorqueLayer.set_actuators`: float32 [n, 4], each column drawn uniformly from its range
+    (lo, hi) -- kp in N m/rad and kd in N m s/rad, by default within half of the nominal KP, KD on either side, the passive
+    damping in N m s/rad, the rotor inertia in kg m^2.  Row 0 is the nominal actuator (KP, KD, 0, 0) whatever the ranges.
+    Deterministic in `seed`: the four columns are drawn in the order of ACTUATOR_COLUMNS, n values each."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    ranges = [tuple(float(x) for x in r) for r in (kp, kd, damping, armature)]
+    if any(len(r) != 2 for r in ranges):
+        raise ValueError("need kp, kd, damping and armature as ranges (lo, hi)")
+    rng = np.random.default_rng(seed)
+    rows = np.zeros((n, 4), np.float32)
+    for col, (name, (lo, hi)) in enumerate(zip(ACTUATOR_COLUMNS, ranges)):
+        if not lo <= hi:
+            raise ValueError(f"{name}: need a range (lo, hi) with lo <= hi, got {(lo, hi)!r}")
+        lo32, hi32 = np.float32(lo), np.float32(hi)      # the float32 values inside [lo, hi] that a rounded draw is held to
+        if lo32 < lo:
+            lo32 = np.nextafter(lo32, np.float32(np.inf))
+        if hi32 > hi:
+            hi32 = np.nextafter(hi32, np.float32(-np.inf))
+        if lo32 > hi32:
+            raise ValueError(f"{name}: the range {(lo, hi)!r} holds no float32 value")
+        rows[:, col] = np.clip(rng.uniform(lo, hi, n).astype(np.float32), lo32, hi32)
+    rows[0] = (KP, KD, 0.0, 0.0)
+    return actuator_table(rows, n)
+
+
 class BatchedTorqueLayer:
     def __init__(self, parent: Sequence[int], joint_type: Sequence[int], axis, placement_R, placement_p, mass, com, inertia,
                  foot_joint: Sequence[int], foot_offset, n_actuated: int, gravity=(0.0, 0.0, -9.81), device="cuda:0"):
@@ -180,6 +231,7 @@ class BatchedTorqueLayer:
         self._push_windows = None       # set_push with arrays: the attached (first substeps, counts)
         self._grounds = None            # set_grounds: the attached table
         self._payloads = None           # set_payloads: the attached table
+        self._actuators = None          # set_actuators: the attached table
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -579,6 +631,30 @@ class BatchedTorqueLayer:
         joint = self.n - self.nu - 1 if joint is None else int(joint)
         _lib.check(self.lib.nmpc_contact_set_payloads(self._h, ptr(rows), rows.shape[0], joint), self._h, "nmpc_contact_set_payloads", "torque")
         self._payloads = rows
+
+    def set_actuators(self, actuators=None):
+        """nmpc_contact_set_actuators: an actuator of its own per robot.  actuators: a float array or tensor [B, 4] in the order of
+        ACTUATOR_COLUMNS (kp > 0 and kd >= 0, the gains of the PD law; damping >= 0, a passive joint damping in N m s/rad that
+        acts after the torque limit; armature >= 0, the reflected rotor inertia in kg m^2 on the diagonal of the joint-space
+        inertia; `sample_actuators` draws one); row b applies to every actuated joint of robot b.  While the table is attached
+        `contact_step`, `contact_track`, `policy_rollout` and the expert on the plant (`open_loop_device(..., plant=...)`, and with
+        it `collect_rollouts` and `learning_iteration`, which take no keyword for it: attach the table on the layer they are
+        given) drive robot b by row b, under either integrator, with or without a push, a table of grounds or a table of
+        payloads; every such call is one launch, and its `kp=`, `kd=` are validated as ever and not read for the law.  It is the
+        plant alone that has these drives: `id_torques`, `forward_dynamics`, `step`, `mass_matrix`, `centroidal`,
+        `contact_forces`, `pd_torques`, `pd_target_action`, `plan_actions` and the expert's labels keep the nominal model and the
+        nominal gains, so a label meets gains it was not formed with -- which is the point.  Calls with more robots than the
+        table has rows are refused.
+        Host input is validated (`actuator_table`: ValueError) and uploaded; a tensor already on the layer's device is taken as
+        given -- the device validates nothing -- and in either case the layer keeps the table alive while it is attached.
+        `set_actuators(None)` detaches; detached, every call makes the launches and gives the bits it gives without."""
+        if actuators is None:
+            self._actuators = None
+            _lib.check(self.lib.nmpc_contact_set_actuators(self._h, None, 0), self._h, "nmpc_contact_set_actuators", "torque")
+            return
+        rows = self._table(actuators, "actuators", ACTUATOR_COLUMNS, actuator_table)
+        _lib.check(self.lib.nmpc_contact_set_actuators(self._h, ptr(rows), rows.shape[0]), self._h, "nmpc_contact_set_actuators", "torque")
+        self._actuators = rows
 
     def _state_io(self, t, name):
         """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""

@@ -1,0 +1,488 @@
+"""GPU checks of an actuator per robot on the contact plant (nmpc_contact_set_actuators behind `BatchedTorqueLayer.set_actuators`).
+
+Accuracy: with a table attached, robot b of `contact_step` and `contact_track` under either integrator is held to the float64
+reference of tests/actuator_reference.py under its row, per sample and per column under the bar of tests/test_gpu_torque.py:
+max(1e-5 x scale, 4 x the deviation of the numpy-float32 run of the same reference from the float64 run), both computed here, never
+from the code under test -- once with the table alone, once with a table of grounds, a table of payloads and a push window per
+robot beside it, where the reference runs on the tree with the payload baked in (tests/payload_reference.py) under the row's law.
+The neutral row (KP, KD, 0, 0) is held to the reference of the call without a table.  Bits: robot b of a table call is robot b of
+the call under the uniform table of its row, a permutation of robots and rows permutes the outputs, spare rows change nothing,
+attach-detach restores every call, the track is the chain of its steps and the policy rollout the chain of its public calls, and
+nothing that describes the nominal model or the nominal controller reads the table.  Every figure is printed before it is asserted.
+
+Shapes: the quadruped tree (n = 18) at B = 1, 31, 32, 33 and one 32-joint tree at B = 17 (the 16-wide blocks); at most 5 control
+steps of at most 4 substeps.  Start states: those of tests/test_gpu_payloads.py -- the lowest foot from 2 cm above the ground to
+2 cm inside it, nobody within 3 mm of the surface, |v| <= 2.  Rows: kp in KP x [0.5, 1.5], kd in KD x [0.5, 1.5], damping in
+[0, 0.2] N m s/rad, armature in [0, 0.02] kg m^2; row 0 nominal, row 1 all four at their upper ends, row 2 armature only, row 3
+damping only, all rows distinct.  No sample is left out of any comparison."""
+import numpy as np
+import pytest
+
+from tests import actuator_reference as ar
+from tests import contact_reference as cr
+from tests import fd_reference as fr
+from tests import payload_reference as plr
+from tests import plant_helpers as ph
+from tests.plant_helpers import AT, DT, DT_IMPLICIT, HEIGHT, INTEGRATORS, KD, KP, MASK, N_SUB, NAMES, ONE, PERIOD, STEP_SUB, T0, TRACK_NAMES
+from tests.plant_helpers import World, chain_of_public_calls, default_policy, expert, held_row_by_row, plant_rollout, quadruped_layer, standing_start  # noqa: F401
+from tests.solve_helpers import dev  # noqa: F401
+from tests.test_gpu_payloads import draw_payloads, start_states, wide_world
+from tests.torque_helpers import bar, fractions, host, same
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+DT32 = float(np.float32(DT))
+B, K = 33, 5                                             # the track: 5 control steps; the policy rollout has the plant's 3
+TRUNK = 5
+UPPER = (1.5 * KP, 1.5 * KD, 0.2, 0.02)
+
+
+def draw_actuators(rng, n):
+    """n distinct rows in the ranges of the module's docstring; the first four are the named ones"""
+    rows = np.stack([rng.uniform(0.5 * KP, 1.5 * KP, n), rng.uniform(0.5 * KD, 1.5 * KD, n), rng.uniform(0.0, 0.2, n), rng.uniform(0.0, 0.02, n)], axis=1)
+    named = [(KP, KD, 0.0, 0.0), UPPER, (KP, KD, 0.0, 0.013), (KP, KD, 0.11, 0.0)]
+    rows[:min(n, 4)] = named[:n]
+    return rows.astype(np.float32)
+
+
+def grounds_of(rows):
+    """the reference `Ground` of every row of a float32 table of grounds (tau_max 0: no limit), from the float32 values themselves"""
+    return [cr.Ground(*(float(x) for x in r[:5]), tau_max=float(r[5]) if r[5] > 0 else None) for r in rows]
+
+
+def detach(L):
+    L.set_actuators(None)
+    ph.detach(L)
+
+
+class Fixture(ph.Fixture):
+    """The host side on the quadruped: states, inputs, the tables and their references."""
+    def __init__(self):
+        self.m = m = fr.quadruped()
+        rng = np.random.default_rng(41)
+        self.q, self.v = start_states(m, B, rng)
+        self.tau = rng.uniform(-2, 2, (B, 12)).astype(np.float32)
+        self.q_des = (self.q[:, 6:] + rng.uniform(-0.1, 0.1, (B, 12))).astype(np.float32)
+        self.A = (self.q[:, None, 6:] + rng.uniform(-0.05, 0.05, (B, K, 12))).astype(np.float32)
+        self.rows = draw_actuators(rng, B)
+        self.payloads = draw_payloads(rng, B)
+        self.F = rng.uniform(-60, 60, (B, 3)).astype(np.float32)
+        self.first, self.count = np.array([1 + 2 * (b % 2) for b in range(B)]), np.array([1 + b % 3 for b in range(B)])
+        self.goal = rng.uniform(-0.5, 0.5, (B, 3)).astype(np.float32)
+        # a law per robot on the plane z = 0, so that the start heights stay what they are: stiffness, friction, and a torque
+        # limit for every other robot that the PD law of the fixture does reach
+        self.grounds = np.zeros((B, 6), np.float32)
+        self.grounds[:] = [0.0, 1e4, 3.0, 0.8, 0.05, 0.0]
+        self.grounds[:, 1] = rng.uniform(5e3, 2e4, B); self.grounds[:, 3] = rng.uniform(0.3, 1.1, B)
+        self.grounds[:, 5] = np.where(np.arange(B) % 2 == 0, 0.0, rng.uniform(2.0, 6.0, B))
+        self.g = cr.Ground()
+        self.freeze()
+
+    def extras(self, everything):
+        """(trees, grounds, pushes) of the reference: the nominal ones, or per robot the baked tree, its law and its window"""
+        if not everything:
+            return self.m, self.g, None
+        trees = [plr.baked(self.m, self.payloads[b], TRUNK) for b in range(B)]
+        pushes = [dict(F=self.F[b], joint=TRUNK, first_substep=int(self.first[b]), n_substeps=int(self.count[b])) for b in range(B)]
+        return trees, grounds_of(self.grounds), pushes
+
+    def ref(self, call, implicit, everything, n_sub=None, rows=None, key=None):
+        """(float64, float32) reference of `call` under `rows` (None: the fixture's table), computed once per key"""
+        dt = DT_IMPLICIT if implicit else DT
+        rows = self.rows if rows is None else rows
+        ms, gs, pushes = self.extras(everything)
+        if call == "step":
+            run = lambda t: ar.step_batch(ms, gs, rows, self.q, self.v, dt, n_sub, self.tau, self.q_des, pushes, t, implicit)      # noqa: E731
+        else:
+            run = lambda t: ar.track_batch(ms, gs, rows, self.q, self.v, self.A, dt, N_SUB, self.tau, pushes, t, implicit)       # noqa: E731
+        return self.cached((call, implicit, everything, n_sub, key), lambda: (run(np.float64), run(np.float32)))
+
+    def conditions(self):
+        pos = np.stack([cr.feet(self.m, self.q[b])[0] for b in range(B)])
+        low = pos[..., 2].min(axis=1)
+        r = self.rows
+        print(f"fixture: lowest foot from {low.max():+.4f} to {low.min():+.4f} m, nearest to the surface {np.abs(low).min():.4f} m, feet in the ground "
+              f"{int((pos[..., 2] < 0).sum())} of {pos[..., 2].size}, |v| <= {np.abs(self.v).max():.2f}, kp in [{r[:, 0].min():.2f}, {r[:, 0].max():.2f}], "
+              f"kd in [{r[:, 1].min():.3f}, {r[:, 1].max():.3f}], damping in [{r[:, 2].min():.3f}, {r[:, 2].max():.3f}], armature in [{r[:, 3].min():.4f}, {r[:, 3].max():.4f}]")
+        assert abs(low.max() - 0.02) < 1e-5 and abs(low.min() + 0.02) < 1e-5 and np.abs(low).min() >= 0.001 - 1e-5 and np.abs(self.v).max() <= 2.0
+        assert not ((low < 0) & (low > -0.003)).any()                                  # nobody within 3 mm inside the surface
+        assert (pos[..., 2] < 0).any() and (pos[..., 2] > 0).any() and not (np.abs(pos[..., 2]) < AT).any()
+        f32 = np.float32
+        assert (r[:, 0] >= f32(0.5 * KP)).all() and (r[:, 0] <= f32(1.5 * KP)).all() and (r[:, 1] >= f32(0.5 * KD)).all() and (r[:, 1] <= f32(1.5 * KD)).all()
+        assert (r[:, 2] >= 0).all() and (r[:, 2] <= f32(0.2)).all() and (r[:, 3] >= 0).all() and (r[:, 3] <= f32(0.02)).all()
+        assert tuple(r[0]) == (f32(KP), f32(KD), 0.0, 0.0) and tuple(r[1]) == tuple(f32(x) for x in UPPER)
+        assert tuple(r[2, :3]) == (f32(KP), f32(KD), 0.0) and r[2, 3] > 0 and tuple(r[3, [0, 1, 3]]) == (f32(KP), f32(KD), 0.0) and r[3, 2] > 0
+        assert len({tuple(x) for x in r.tolist()}) == B
+
+
+@pytest.fixture(scope="module")
+def fx():
+    f = Fixture()
+    f.conditions()
+    return f
+
+
+def quad_world(fx, n=B, L=None):
+    return World(L or fx.m, n, q=fx.q, v=fx.v, tau=fx.tau, q_des=fx.q_des, A=fx.A, goal=fx.goal)
+
+
+@pytest.fixture(scope="module")
+def world(fx):
+    return quad_world(fx)
+
+
+@pytest.fixture()
+def detached(world):
+    """whatever a test attaches or sets on the module's layer is gone after it, also when it fails"""
+    yield
+    detach(world.L)
+
+
+def attach_everything(fx, w, idx=None):
+    """a table of grounds, a table of payloads and a push window per robot for the robots idx of the fixture (None: the first w.n)"""
+    idx = np.arange(w.n) if idx is None else idx
+    w.L.set_grounds(fx.grounds[idx])
+    w.L.set_payloads(fx.payloads[idx], joint=TRUNK)
+    w.L.set_push(w.d(fx.F[idx]), fx.first[idx], fx.count[idx])
+
+
+def rollout(w, policy, dt=DT):
+    return w.rollout(policy, dt)
+
+
+# ---- 1. against the reference under each robot's row ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_sub", [1, STEP_SUB])
+@pytest.mark.parametrize("everything", [False, True], ids=["alone", "with grounds, payloads and windows"])
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_the_step_matches_the_reference_under_each_robots_row(fx, world, detached, integrator, everything, n_sub):
+    implicit = integrator == "implicit"
+    ref, f32 = fx.ref("step", implicit, everything, n_sub)
+    world.L.set_integrator(integrator)
+    if everything:
+        attach_everything(fx, world)
+    world.L.set_actuators(fx.rows)
+    got = host(*world.step(n_sub=n_sub, dt=DT_IMPLICIT if implicit else DT))
+    assert [x.shape for x in got] == [(B, 18)] * 3 + [(B, 4, 3), (B, 12)]
+    print(f"{integrator} step under the actuator table{' with everything attached' if everything else ''}, {n_sub} substeps, B {B}")
+    worst = [fractions(name, x, r, f) for name, x, r, f in zip(NAMES, got, ref, f32)]
+    assert max(worst) <= 1.0
+
+
+@pytest.mark.parametrize("everything", [False, True], ids=["alone", "with grounds, payloads and windows"])
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_the_track_matches_the_chained_reference_under_each_robots_row(fx, world, detached, integrator, everything):
+    implicit = integrator == "implicit"
+    ref, f32 = fx.ref("track", implicit, everything)
+    world.L.set_integrator(integrator)
+    if everything:
+        attach_everything(fx, world)
+    world.L.set_actuators(fx.rows)
+    got = host(*world.track(dt=DT_IMPLICIT if implicit else DT))
+    assert [x.shape for x in got] == [(B, 18)] * 2 + [(B, K, 18)] * 2
+    print(f"{integrator} track under the actuator table{' with everything attached' if everything else ''}, {K} control steps of {N_SUB} substeps, B {B}")
+    worst = [fractions(name, x, r, f) for name, x, r, f in zip(TRACK_NAMES, got, ref, f32)]
+    # the guard: the table moves the state after the track by at least 100 bars from the plant without one
+    if not everything:
+        plain, plain32 = fx.ref("track", implicit, False, rows=np.tile(ar.nominal(KP, KD), (B, 1)), key="nominal")
+        for name, x, y, f in zip(("q", "v"), ref[:2], plain[:2], f32[:2]):
+            gap, b = np.abs(x - y).max(), bar(x, f)
+            print(f"  guard: the reference with and without the table differs by {gap:.3e} in {name} = {gap / b:.0f} bars of {b:.3e}")
+            assert gap >= 100 * b
+    assert max(worst) <= 1.0
+
+
+# ---- 2. the neutral row ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_the_neutral_row_is_the_plant_without_a_table(fx, world, detached, integrator):
+    """Under the uniform table (KP, KD, 0, 0) step, track and policy rollout are held to the reference of the call without a table
+    (tests/test_actuator_reference.py: under that row the reference is contact_step_ref / implicit_step_ref); whether they are
+    also its bits is printed and not required -- the zero payload and the zero damping may turn the sign of a zero."""
+    implicit = integrator == "implicit"
+    dt = DT_IMPLICIT if implicit else DT
+    neutral = np.tile(np.float32([KP, KD, 0.0, 0.0]), (B, 1))
+    policy = default_policy()
+    L = world.L
+    L.set_integrator(integrator)
+    bare = world.step(dt=dt) + world.track(dt=dt) + rollout(world, policy, dt)[:4]
+    L.set_actuators(neutral)
+    got = world.step(dt=dt) + world.track(dt=dt) + rollout(world, policy, dt)[:4]
+    names = [f"step {n}" for n in NAMES] + [f"track {n}" for n in TRACK_NAMES] + [f"policy rollout {n}" for n in ("q", "v", "S", "A")]
+    for name, x, y in zip(names, got, bare):
+        print(f"  {integrator}, {name}: bit for bit the call without a table: {same(x, y)}, largest difference {float((x.double() - y.double()).abs().max()):.3e}")
+    ref, f32 = fx.ref("step", implicit, False, STEP_SUB, rows=neutral, key="nominal")
+    tref, t32 = fx.ref("track", implicit, False, rows=neutral, key="nominal")
+    worst = [fractions(f"step {n}", x, r, f) for n, x, r, f in zip(NAMES, host(*got[:5]), ref, f32)]
+    worst += [fractions(f"track {n}", x, r, f) for n, x, r, f in zip(TRACK_NAMES, host(*got[5:9]), tref, t32)]
+    # the policy closes the loop: the rollout is held to the float64 plant without a table under the actions it recorded itself
+    q, v, _, A = host(*got[9:])
+    r = ar.track_batch(fx.m, fx.g, neutral, fx.q, fx.v, A, dt, N_SUB, fx.tau, None, np.float64, implicit)
+    f = ar.track_batch(fx.m, fx.g, neutral, fx.q, fx.v, A, dt, N_SUB, fx.tau, None, np.float32, implicit)
+    worst += [fractions(f"policy rollout {n}", x, rr, ff) for n, x, rr, ff in zip(("q", "v"), (q, v), r, f)]
+    assert max(worst) <= 1.0
+
+
+# ---- 3. row b is robot b's, bit for bit -----------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def worlds(fx, world):
+    return {"B1": quad_world(fx, 1, world.L), "B31": quad_world(fx, 31, world.L), "B32": quad_world(fx, 32, world.L), "B33": world, "tree32 B17": wide_world()}
+
+
+@pytest.mark.parametrize("everything", [False, True], ids=["alone", "with grounds, payloads and windows"])
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+@pytest.mark.parametrize("shape", ["B1", "B31", "B32", "B33", "tree32 B17"])
+def test_row_b_is_robot_bs_bit_for_bit(fx, worlds, shape, integrator, everything):
+    w = worlds[shape]
+    L, n = w.L, w.n
+    dt = DT_IMPLICIT if integrator == "implicit" else DT
+    rows = fx.rows[:n]
+    perm = np.random.default_rng(43).permutation(n)
+
+    def attach(rows_, idx):
+        if everything:
+            attach_everything(fx, w, idx)
+        L.set_actuators(rows_)
+
+    def run(world_=w):
+        return world_.step(dt=dt) + world_.track(dt=dt)
+
+    try:
+        L.set_integrator(integrator)
+        everyone = np.arange(n)
+        got, _ = held_row_by_row(run, lambda: attach(rows, everyone), lambda b: attach(np.tile(rows[b], (n, 1)), everyone), sorted({0, n // 2, n - 1}),
+                                 NAMES + (TRACK_NAMES if w.record else TRACK_NAMES[:2]),
+                                 lambda b, o: f"{shape}, {integrator}, robot {b} {o}: largest |table - uniform|")
+        assert all(bool(torch.isfinite(x).all()) for x in got)
+        # a permutation of robots and rows permutes the outputs
+        p = torch.as_tensor(perm, device=L.device)
+        attach(rows[perm], perm)
+        shuffled = run(w.permuted(perm))
+        assert all(same(x[p], y) for x, y in zip(got, shuffled)), shape
+        # spare rows change nothing
+        attach(np.vstack([rows, fx.rows[::-1][:3]]), everyone)
+        longer = run()
+        assert all(same(x, y) for x, y in zip(got, longer)), shape
+        # and the rows matter
+        if n > 1:
+            L.set_actuators(None)
+            assert not all(same(x, y) for x, y in zip(got, run()))
+    finally:
+        detach(L)
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_attach_then_detach_gives_the_bits_from_before(fx, world, detached, integrator):
+    L = world.L
+    L.set_integrator(integrator)
+    policy = default_policy()
+    calls = lambda: world.step() + world.track() + rollout(world, policy)      # noqa: E731
+    before = calls()
+    L.set_actuators(fx.rows)
+    assert L._actuators is not None
+    during = calls()
+    L.set_actuators(None)
+    assert L._actuators is None
+    after = calls()
+    assert all(same(x, y) if x.is_floating_point() else torch.equal(x, y) for x, y in zip(before, after))
+    assert not all(same(x, y) for x, y in zip(before[:5], during[:5]))
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_the_track_is_the_chain_of_its_steps(fx, world, detached, integrator):
+    L = world.L
+    dt = DT_IMPLICIT if integrator == "implicit" else DT
+    L.set_integrator(integrator)
+    L.set_actuators(fx.rows)
+    q, v, Q, V = world.track(dt=dt)
+    qk, vk = world.q, world.v
+    for k in range(K):
+        assert same(Q[:, k], qk) and same(V[:, k], vk), k
+        qk, vk = L.contact_step(qk, vk, dt, N_SUB, tau_ff=world.tau, q_des=world.A[:, k].contiguous(), kp=KP, kd=KD)[:2]
+    assert same(q, qk) and same(v, vk)
+
+
+@pytest.mark.parametrize("integrator", INTEGRATORS)
+def test_the_policy_rollout_is_its_chain_of_public_calls(fx, world, detached, integrator):
+    L = world.L
+    policy = default_policy()
+    L.set_integrator(integrator)
+    L.set_actuators(fx.rows)
+    q, v = world.q, world.v
+    failed = torch.zeros(B, dtype=torch.int32, device=L.device)
+    S, A = [], []
+    for k in range(ph.ROLLOUT_STEPS):
+        s, x = L.observe(q, v, T0 + (k * N_SUB) * DT32, PERIOD, world.goal, collision_height=HEIGHT, failed=failed, step_index=k, term_mask=MASK)
+        a = policy.forward(x)
+        q, v = L.contact_step(q, v, DT, N_SUB, tau_ff=world.tau, q_des=a, kp=KP, kd=KD)[:2]
+        S.append(s); A.append(a)
+    L.observe(q, v, T0 + (ph.ROLLOUT_STEPS * N_SUB) * DT32, PERIOD, world.goal, collision_height=HEIGHT, failed=failed, step_index=ph.ROLLOUT_STEPS, term_mask=MASK)
+    got = rollout(world, policy)
+    assert all(same(x, y) for x, y in zip(got[:4], (q, v, torch.stack(S, 1), torch.stack(A, 1)))) and torch.equal(got[4], failed)
+    L.set_actuators(None)
+    assert not same(rollout(world, policy)[0], got[0])                                 # the table matters
+
+
+# ---- 4. what it does not touch --------------------------------------------------------------------------------------------------------------
+def test_the_nominal_model_does_not_read_the_table(fx, world, detached, dev):
+    from iterative_learning_nmpc_amd.torque import GroundContact
+    L = world.L
+    a = world.d(np.random.default_rng(3).uniform(-5, 5, (B, 18)).astype(np.float32))
+    f = world.d(np.random.default_rng(4).uniform(-40, 80, (B, 4, 3)).astype(np.float32))
+    tau = world.d(np.random.default_rng(5).uniform(-20, 20, (B, 12)).astype(np.float32))
+    mpc = expert(dev, 2)
+    q0, v0 = standing_start(2)
+    o = plant_rollout(mpc, L, q0, v0, ONE)
+    zoh = mpc.id_repeat[:40]
+    flat = lambda x: torch.cat([y.reshape(B, -1) for y in x], 1) if isinstance(x, (tuple, list)) else x      # noqa: E731
+
+    def nominal():
+        return dict(fd_step=flat(L.step(world.q, world.v, DT, 2, tau_ff=world.tau, q_des=world.q_des, kp=KP, kd=KD, f=f)),
+                    fd_accel=L.forward_dynamics(world.q, world.v, tau, f), id_torques=L.id_torques(world.q, world.v, a, f),
+                    mass_matrix=L.mass_matrix(world.q), centroidal=flat(L.centroidal(world.q, world.v, jacobian=True)),
+                    state_momentum=L.state_momentum(world.q, world.v), contact_forces=L.contact_forces(world.q, world.v, GroundContact()),
+                    pd_target_action=L.pd_target_action(tau, world.q, world.v, kp=KP, kd=KD),
+                    plan_actions=L.plan_actions(o["X"], o["U"], zoh, mpc.config_opt.time_horizon / mpc.config_opt.n_nodes, mpc.sim_dt, kp=mpc.Kp, kd=mpc.Kd))
+
+    without = nominal()
+    bare = world.step()
+    L.set_actuators(fx.rows)
+    driven = nominal()
+    assert not same(world.step()[0], bare[0])             # the table is attached and a plant call takes it
+    for name in without:
+        assert same(without[name], driven[name]), name
+    assert list(without) == ["fd_step", "fd_accel", "id_torques", "mass_matrix", "centroidal", "state_momentum", "contact_forces", "pd_target_action",
+                             "plan_actions"]
+
+
+# ---- 5. through the layers ------------------------------------------------------------------------------------------------------------------
+def test_evaluate_policy_attaches_and_detaches_the_table(fx, world, detached):
+    from iterative_learning_nmpc_amd.learning import evaluate_policy
+    L = world.L
+    policy = default_policy()
+    goal = world.goal
+    before = world.step()
+    L.set_actuators(fx.rows)
+    q, v, S, A, failed = rollout(world, policy)
+    L.set_actuators(None)
+    bare = rollout(world, policy)
+    kw = dict(dt=DT, n_sub=N_SUB, tau_ff=world.tau, kp=KP, kd=KD, t0=T0, period=PERIOD, terminate_mask=MASK, collision_height=HEIGHT)
+    out = evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, actuators=fx.rows, **kw)
+    assert same(out["S"], S) and same(out["A"], A) and same(out["q"], q) and same(out["v"], v) and torch.equal(out["failed"], failed)
+    assert not same(out["q"], bare[0])
+    assert L._actuators is None
+    assert all(same(x, y) for x, y in zip(world.step(), before))                       # after the call the layer's step is the un-attached bits
+    assert same(evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, **kw)["q"], bare[0])
+    # also when the rollout raises: a goal of the wrong batch is refused inside the try
+    with pytest.raises(Exception):
+        evaluate_policy(L, policy, None, world.q, world.v, goal[:5], 3 * N_SUB * DT, actuators=fx.rows, **kw)
+    assert L._actuators is None and same(rollout(world, policy)[0], bare[0])
+    # a table of the caller's is not replaced
+    L.set_actuators(fx.rows)
+    mine = L._actuators
+    with pytest.raises(ValueError, match="attached already"):
+        evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, actuators=fx.rows, **kw)
+    assert L._actuators is mine and same(rollout(world, policy)[0], q)
+
+
+def test_dagger_iteration_labels_with_the_nominal_gains(fx, dev):
+    from iterative_learning_nmpc_amd import learning
+    from tests.plant_helpers import Dagger as di
+    w = di.setup(dev)
+    rows = fx.rows[1:1 + di.B].copy()
+    run = lambda **kw: learning.dagger_iteration(w["mpc"], w["layer"], w["db"], w["policy"], w["q0"], w["v0"], w["goal"], di.T, dt=di.DT,      # noqa: E731
+                                                 n_sub=di.N_SUB, n_epoch=1, batch_size=di.BATCH, lr=1e-3, seed=di.SEED, **kw)
+    out = run(actuators=rows)
+    L = w["layer"]
+    assert L._actuators is None
+    A_ref, st_ref = w["mpc"].label_states(out["Q"], out["V"], L, dt_row=di.N_SUB * di.DT, failed=out["failed"])
+    assert same(A_ref, out["A_star"]) and torch.equal(st_ref, out["status"])
+    L.set_actuators(rows)                                 # A_star of a given Q, V is independent of the table
+    A_driven, st_driven = w["mpc"].label_states(out["Q"], out["V"], L, dt_row=di.N_SUB * di.DT, failed=out["failed"])
+    L.set_actuators(None)
+    assert same(A_driven, out["A_star"]) and torch.equal(st_driven, out["status"])
+    # and the learner's plant did have the drives of the table: the visited states are not those of the nominal rollout
+    bare = learning.evaluate_policy(L, w["policy"], w["db"], w["q0"], w["v0"], w["goal"], di.T, dt=di.DT, n_sub=di.N_SUB, kp=float(w["mpc"].Kp),
+                                    kd=float(w["mpc"].Kd), record_states=True)
+    assert not same(bare["Q"][:, -1], out["Q"][:, -1])
+
+
+def test_the_expert_on_the_plant_meets_the_table_of_its_layer(fx, dev, quadruped_layer):
+    """B = 2, one replan: the plant-mode rollout with a table on its layer is the chain plan labels -> contact_track -> observe_rows
+    under the same table, and not the nominal rollout; the labels are formed with the nominal gains."""
+    L = quadruped_layer
+    rows = fx.rows[1:3].copy()
+    q0, v0 = standing_start(2)
+    try:
+        bare = plant_rollout(expert(dev, 2), L, q0, v0, ONE)
+        L.set_actuators(rows)
+        mpc = expert(dev, 2)
+        o = plant_rollout(mpc, L, q0, v0, ONE)
+        S, A, q, v, failed = chain_of_public_calls(mpc, L, o["X"], o["U"], q0, v0, o["status"])
+    finally:
+        L.set_actuators(None)
+    assert o["S"].shape == (2, 40, 44) and bool(torch.isfinite(o["S"]).all())
+    assert all(same(a, b) for a, b in zip((o["S"], o["A"], o["q"], o["v"]), (S, A, q, v))) and torch.equal(o["failed"], failed)
+    assert same(o["A"], bare["A"])                        # the labels of the first plan are the nominal expert's
+    assert not same(o["q"], bare["q"])                    # the plant answered them with its own drives
+
+
+# ---- 6. refusals ----------------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_handle_as_it_was(fx, world, detached):
+    from iterative_learning_nmpc_amd import _lib
+    from iterative_learning_nmpc_amd._lib import NmpcError
+    from iterative_learning_nmpc_amd.learning import evaluate_policy
+    from iterative_learning_nmpc_amd.torque import actuator_table, sample_actuators
+    L, lib = world.L, world.L.lib
+    text = lambda: lib.nmpc_torque_last_error(L._h).decode()                           # noqa: E731
+    policy = default_policy()
+    goal = world.goal
+    small = quad_world(fx, 4, L)
+    table = world.d(fx.rows[:4])
+    L.set_actuators(table)
+    assert L._actuators is table                          # a device tensor is taken as given
+    kept = small.step()
+    # B > n_rows, in every call that reads the table: nothing is launched, the outputs are untouched, what is attached stays
+    for integrator in INTEGRATORS:
+        L.set_integrator(integrator)
+        for call in (world.step, world.track, lambda: rollout(world, policy)):
+            with pytest.raises(NmpcError, match="actuators: B exceeds n_rows"):
+                call()
+        q, v = world.q.clone(), world.v.clone()
+        Q, V = torch.full((B, K, 18), 7.0, device=L.device), torch.full((B, K, 18), 7.0, device=L.device)
+        with pytest.raises(NmpcError, match="actuators: B exceeds n_rows"):
+            L.contact_track(q, v, world.A, DT, N_SUB, tau_ff=world.tau, kp=KP, kd=KD, Q=Q, V=V)
+        assert same(q, world.q) and same(v, world.v) and bool((Q == 7.0).all()) and bool((V == 7.0).all())
+    L.set_integrator("explicit")
+    assert all(same(x, y) for x, y in zip(small.step(), kept))
+    # n_rows < 1: refused, what was attached stays
+    for n_rows in (0, -3):
+        assert lib.nmpc_contact_set_actuators(L._h, _lib.ptr(table), n_rows) == -1 and "n_rows must be at least 1" in text()
+    assert all(same(x, y) for x, y in zip(small.step(), kept))
+    with pytest.raises(NmpcError, match="actuators: B exceeds n_rows"):
+        world.step()
+    # a NULL handle
+    assert lib.nmpc_contact_set_actuators(None, _lib.ptr(table), 4) == -1 and b"handle" in lib.nmpc_torque_last_error(None)
+    # the Python validators, field by field
+    for col, bads in ((0, (0.0, -1.0, np.nan, np.inf)), (1, (-0.1, np.nan, np.inf)), (2, (-0.01, np.nan, np.inf)), (3, (-0.001, np.nan, np.inf))):
+        for bad in bads:
+            rows = fx.rows.copy(); rows[2, col] = bad
+            with pytest.raises(ValueError, match="actuators: row 2"):
+                actuator_table(rows, B)
+            with pytest.raises(ValueError, match="actuators: row 2"):
+                L.set_actuators(rows)
+            assert L._actuators is table
+    with pytest.raises(ValueError, match="actuators: expected"):
+        actuator_table(fx.rows[:4], B)                    # fewer rows than robots
+    with pytest.raises(ValueError, match="actuators: expected"):
+        actuator_table(fx.rows[:, :3], B)
+    assert actuator_table(fx.rows, B).dtype == np.float32 and np.array_equal(actuator_table(fx.rows, B), fx.rows)
+    drawn = sample_actuators(64, 3)
+    assert drawn.shape == (64, 4) and tuple(drawn[0]) == (np.float32(KP), np.float32(KD), 0.0, 0.0) and np.array_equal(drawn, sample_actuators(64, 3))
+    assert abs(drawn[1:, 0].mean() - KP) < 0.15 * KP and abs(drawn[1:, 1].mean() - KD) < 0.15 * KD and drawn[:, 2:].min() >= 0.0
+    # a second actuators= on a layer that has one
+    with pytest.raises(ValueError, match="attached already"):
+        evaluate_policy(L, policy, None, small.q, small.v, goal[:4], 3 * N_SUB * DT, dt=DT, n_sub=N_SUB, actuators=fx.rows[:4])
+    assert L._actuators is table and all(same(x, y) for x, y in zip(small.step(), kept))
+    # detaching twice is fine
+    L.set_actuators(None); L.set_actuators(None)
+    assert [tuple(x.shape) for x in world.step()] == [(B, 18)] * 3 + [(B, 4, 3), (B, 12)]
