@@ -278,6 +278,58 @@ int nmpc_contact_set_payloads(void *torque, const float *rows, int n_rows, int j
  * before any launch: B > n_rows.  rows = NULL detaches (n_rows is not read). */
 int nmpc_contact_set_actuators(void *torque, const float *rows, int n_rows);
 
+/* An actuation delay per robot [decl] (what the batch still shared, and still had ideal: time.  A real drive chain has a transport
+ * delay between a PD target being issued and the joint answering it -- bus, inference, the solve in flight; the reference
+ * compensates for it, mpc.py:548-551 -- and a policy that outputs PD targets breaks on it before it breaks on friction or load).
+ * delay: dev int [rows], the control steps robot b lags by.  history: dev [rows][depth][n_actuated], a shift register per robot of
+ * the last `depth` issued targets, history[b][j] being the target issued j + 1 control steps before the next one.  work: dev
+ * [rows][work_rows][n_actuated], scratch the applied rows of a call go to.  All three are caller-owned, kept as pointers and read
+ * (history and work also written) in stream order at each launch: the library still never allocates.
+ * The rule.  Feeding n_steps issued rows I[b][0 .. n_steps) gives the applied rows
+ *   d = min(max(delay[b], 0), depth)                      (clamped on the device; nothing else of a row is validated)
+ *   P[b][k] = k >= d ? I[b][k - d] : H[b][d - 1 - k]
+ * and leaves the register holding the new last `depth` issued targets,
+ *   H'[b][j] = n_steps - 1 - j >= 0 ? I[b][n_steps - 1 - j] : H[b][j - n_steps].
+ * It is a pass of copies by a kernel of its own in front of the chain of control steps (one thread per robot and actuated joint);
+ * no plant kernel changes, so a delayed call is bit for bit the un-delayed call on the table P.
+ * While attached:
+ *   nmpc_contact_track_batch (and nmpc_wb_rollout_* with a plant, through its track launches), after all refusals and before the
+ *     first launch of the chain, makes ONE launch A -> work with the call's skip flags and then runs exactly as it does with
+ *     A = work, a_rows = work_rows -- as one launch or cut at a push window alike.
+ *   nmpc_contact_step_batch (and every step of nmpc_policy_rollout_batch) with a q_des feeds one control step, q_des -> work as
+ *     dense [B][n_actuated], and runs on work; without a q_des nothing was issued and the register does not move.  The pass runs
+ *     once per call, never per piece of a call cut at a push window.
+ * What the records hold: A of nmpc_policy_rollout_batch, and the action rows a whole-body rollout records, are the ISSUED
+ * targets -- what the controller said, not what the joint met.
+ * The calls that do NOT read the table -- the nominal model and controller, and the labels: nmpc_plan_actions_batch,
+ * nmpc_wb_label_states_batch, nmpc_pd_*, nmpc_fd_*, and the rest of the second list of nmpc_contact_set_actuators.  The plant alone
+ * is late; the expert and its labels do not know about it, and the learner visits the states the late plant produces.
+ * The unit is the control step of the call: n_sub * dt of a policy rollout or a track (10 ms at the defaults of evaluate_policy),
+ * one simulation step of the expert on the plant.  A delay inside a control step would need the chain kernel to switch targets
+ * mid-step; it is out of scope.
+ * Because the register is the caller's and every call advances it, a chain of calls is the long call: a track of 2 K steps is bit
+ * for bit two tracks of K, and a rollout in stretches (nmpc_wb_rollout_set_clock) is bit for bit the one call.  With nothing
+ * attached every call makes exactly the launches it makes without this entry point; with a table of zeros every output is bit for
+ * bit the un-delayed call's.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), what was attached staying: delay given and depth outside [1, NMPC_DELAY_MAX_DEPTH],
+ * rows < 1, work_rows < 1, a NULL history or work.  At a plant call, before any launch: B > rows; at a track also
+ * n_steps > work_rows, or A overlapping work.  delay = NULL detaches (nothing else is read). */
+#define NMPC_DELAY_MAX_DEPTH 64
+int nmpc_contact_set_delays(void *torque, const int *delay, float *history, int depth,
+                            float *work, int work_rows, int rows);
+
+/* The delay line alone: n_steps issued rows of B robots, robot b's row k at issued + (b * issued_rows + k) * n_actuated, through
+ * the attached delay and history to applied + (b * applied_rows + k) * n_actuated by the rule above; the register moves on.
+ * skip as nmpc_contact_track_batch: a skipped robot's applied rows and history are neither read nor written.  One launch,
+ * stream-ordered, no allocation, no synchronisation; every output word is a copy of an input word.
+ * NMPC_E_ARG before any launch: nothing attached, B > rows, n_steps < 1, issued_rows or applied_rows below n_steps, a NULL issued
+ * or applied, applied overlapping issued (by the extents of the two tables from the first row of robot 0 to the last of robot
+ * B - 1: tables interleaved through their row strides count as overlapping). */
+int nmpc_delay_line_batch(void *torque, int B, int n_steps,
+                          const float *issued, int issued_rows,
+                          float *applied, int applied_rows,
+                          const int *skip, int skip_mask, void *stream);
+
 /* The integrator of the contact plant [decl].  NMPC_INTEGRATOR_EXPLICIT (the default) is the step stated above, launch for launch.
  * NMPC_INTEGRATOR_LINEARLY_IMPLICIT takes the stiff terms -- ground stiffness and damping, the friction regulariser, the PD law --
  * at the end of the substep, linearised at its start.  One substep from (q, v):

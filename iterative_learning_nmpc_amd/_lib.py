@@ -31,6 +31,8 @@ NMPC_ROLLOUT_TERM_SHIFT = 8
 # the integrators of the contact plant (include/nmpc_torque.h, nmpc_contact_set_integrator)
 NMPC_INTEGRATOR_EXPLICIT = 0
 NMPC_INTEGRATOR_LINEARLY_IMPLICIT = 1
+# the deepest shift register of a delay line (include/nmpc_torque.h, nmpc_contact_set_delays)
+NMPC_DELAY_MAX_DEPTH = 64
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -113,6 +115,8 @@ SIGNATURES = {
     "nmpc_contact_set_grounds": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_contact_set_payloads": (c_int, [c_void_p, c_void_p, c_int, c_int]),
     "nmpc_contact_set_actuators": (c_int, [c_void_p, c_void_p, c_int]),
+    "nmpc_contact_set_delays": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int]),
+    "nmpc_delay_line_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "nmpc_contact_set_integrator": (c_int, [c_void_p, c_int]),
     "nmpc_observe_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),

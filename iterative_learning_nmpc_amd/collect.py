@@ -36,8 +36,8 @@ def collect_rollouts(mpc, layer, db, q0, v0, T: float, push: Optional[dict] = No
     with the PD target the expert applied from it.  push: the dict of `mpc.sample_pushes`, whose "start" and "duration" may
     be arrays of B (a window per rollout, e.g. merged from `mpc.sample_push_windows`), with or without `chunk_replans`.  kp, kd: as `open_loop_device` (None: its defaults).  push_as_force (with
     plant): the push is a force on the plant's trunk instead of a velocity jump per replanning interval.  integrator (with
-    plant): the plant's integrator, as `open_loop_device` takes it (None: as the layer is set).  A ground, a payload or an actuator per
-    rollout takes no keyword: a table attached on `layer` (`set_grounds`, `set_payloads`, `set_actuators`) is seen by the plant of this call.
+    plant): the plant's integrator, as `open_loop_device` takes it (None: as the layer is set).  A ground, a payload, an actuator or a delay per
+    rollout takes no keyword: a table attached on `layer` (`set_grounds`, `set_payloads`, `set_actuators`, `set_delays`) is seen by the plant of this call.
     After the call `mpc.actions`, `mpc.failed` and the returned S of the rollout are as `open_loop_device` leaves them
     (`mpc.states` keeps S).
     chunk_replans (None: one call, as above): the rollout runs as stretches of `chunk_replans` replans, the last one shorter --

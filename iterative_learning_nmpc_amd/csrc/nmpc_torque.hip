@@ -22,12 +22,14 @@
 // the one rule of what lies behind an instantiation's slice, its LDS footprint and its block width; the centroidal momentum about an anchor
 // point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
-// momentum A_g(q) v of a plant state alone, which the device rollouts put into x0.
+// momentum A_g(q) v of a plant state alone, which the device rollouts put into x0; the delay line in front of the chain -- a
+// shift register of issued PD targets per robot, a pass of copies -- is nmpc_torque_delay.hip.inc.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
 
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -364,6 +366,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_crba.hip.inc"
 #include "nmpc_torque_implicit.hip.inc"
 #include "nmpc_torque_track.hip.inc"
+#include "nmpc_torque_delay.hip.inc"
 #include "nmpc_torque_centroidal.hip.inc"
 
 }  // namespace nmpc_torque
@@ -399,6 +402,13 @@ struct Torque {
     Table payloads;                     // nmpc_contact_set_payloads: a point mass per robot on body `payload_joint` in the plant calls
     int payload_joint = 0;
     Table actuators;                    // nmpc_contact_set_actuators: gains, joint damping and rotor inertia per robot in the plant calls
+    struct {                            // nmpc_contact_set_delays: a transport delay per robot in front of the plant calls (delay == nullptr: none)
+        const int* delay = nullptr;     // [rows]: control steps robot b lags by
+        float* history = nullptr;       // [rows][depth][nu]: the shift register of issued targets
+        int depth = 0;
+        float* work = nullptr;          // [rows][work_rows][nu]: where the applied rows of a call go
+        int work_rows = 0, rows = 0;
+    } delays;
     int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
@@ -594,7 +604,33 @@ const char* plant_batch_refusal(const Torque* t, const nmpc_push_cfg& push, cons
     if (wins.first && B > wins.rows) return "push windows: B exceeds rows";
     if (const char* why = grounds_batch_refusal(t, B)) return why;
     if (t->payloads.rows && B > t->payloads.n_rows) return "payloads: B exceeds n_rows";
+    if (t->delays.delay && B > t->delays.rows) return "delays: B exceeds rows";
     return t->actuators.rows && B > t->actuators.n_rows ? "actuators: B exceeds n_rows" : nullptr;
+}
+
+// why the attached delay line cannot take n_steps issued rows of B robots to `applied` (nullptr: it can)
+const char* delay_line_refusal(const Torque* t, int B, int n_steps, const float* issued, int issued_rows, const float* applied, int applied_rows) {
+    if (!t->delays.delay) return "delays: no table is attached (nmpc_contact_set_delays)";
+    if (B > t->delays.rows) return "delays: B exceeds rows";
+    if (n_steps < 1) return "delays: n_steps must be at least 1";
+    if (issued_rows < n_steps || applied_rows < n_steps) return "delays: issued_rows and applied_rows must be at least n_steps";
+    if (!issued || !applied) return "delays: issued and applied are needed";
+    const size_t nu = (size_t)t->host.nu;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(issued), a0 = reinterpret_cast<uintptr_t>(applied);
+    const uintptr_t i1 = i0 + (((size_t)B - 1) * issued_rows + n_steps) * nu * sizeof(float);
+    const uintptr_t a1 = a0 + (((size_t)B - 1) * applied_rows + n_steps) * nu * sizeof(float);
+    if (i0 < a1 && a0 < i1) return "delays: applied overlaps issued";
+    return nullptr;
+}
+
+// the one launch of the delay line: what delay_line_refusal accepted, through the attached register
+int launch_delay_line(Torque* t, int B, int n_steps, const float* issued, int issued_rows, float* applied, int applied_rows, const int* skip,
+                      int skip_mask, void* stream) {
+    DelayArgs p{};
+    p.n_steps = n_steps; p.nu = t->host.nu; p.depth = t->delays.depth; p.issued_rows = issued_rows; p.applied_rows = applied_rows;
+    p.skip_mask = skip ? skip_mask : 0; p.skip = p.skip_mask ? skip : nullptr;
+    p.delay = t->delays.delay; p.issued = issued; p.applied = applied; p.history = t->delays.history;
+    return launch_elementwise(t, delay_line_kernel, B, stream, p);
 }
 
 // A plant call that launch_whole below does not take is cut into runs of substeps that are all un-pushed -- launches of the
@@ -673,7 +709,14 @@ int contact_step(Torque* t, int B, int n_sub, float dt, const nmpc_contact_cfg* 
     if (const char* why = step_refusal(n_sub, dt)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = contact_cfg_refusal(cfg)) return fail(t, NMPC_E_ARG, why);
     if (const char* why = plant_batch_refusal(t, push, wins, B)) return fail(t, NMPC_E_ARG, why);
+    const bool delayed = t->delays.delay && q_des;      // without a q_des nothing was issued: the register does not move
+    if (delayed)
+        if (const char* why = delay_line_refusal(t, B, 1, q_des, 1, t->delays.work, 1)) return fail(t, NMPC_E_ARG, why);
     NMPC_ENTER(t, t->device);
+    if (delayed) {                                      // one control step is fed, once per call: the pieces of the cut path share it
+        if (const int rc = launch_delay_line(t, B, 1, q_des, 1, t->delays.work, 1, nullptr, 0, stream)) return rc;
+        q_des = t->delays.work;                         // dense [B][nu]
+    }
     const Window win = wins.first ? Window{} : push_window(push, s0, n_sub);
     PushArgs call = chain_args(B, 1, n_sub, dt, *cfg, tau_ff, q_des, 1, kp, kd, q_out, v_out);
     call.q_in = q; call.v_in = v; call.a_out = a_out; call.f_out = f_out; call.tau_out = tau_out;
@@ -721,7 +764,15 @@ int contact_track(Torque* t, int B, int n_steps, int n_sub, float dt, const nmpc
     if (Q && !whole_body_tree(t->host))
         return fail(t, NMPC_E_ARG, "the rows Q, V need the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
     if (const char* why = plant_batch_refusal(t, push, wins, B)) return fail(t, NMPC_E_ARG, why);
+    if (t->delays.delay) {
+        if (n_steps > t->delays.work_rows) return fail(t, NMPC_E_ARG, "delays: n_steps exceeds work_rows");
+        if (const char* why = delay_line_refusal(t, B, n_steps, A, a_rows, t->delays.work, t->delays.work_rows)) return fail(t, NMPC_E_ARG, why);
+    }
     NMPC_ENTER(t, t->device);
+    if (t->delays.delay) {                              // the issued rows through the register, once per call; the call then runs on the applied ones
+        if (const int rc = launch_delay_line(t, B, n_steps, A, a_rows, t->delays.work, t->delays.work_rows, skip, skip_mask, stream)) return rc;
+        A = t->delays.work; a_rows = t->delays.work_rows;
+    }
     const int n = t->host.n, nu = t->host.nu;
     const long long total = (long long)n_steps * n_sub;
     const Window win = wins.first ? Window{} : push_window(push, 0, total);
@@ -1052,6 +1103,31 @@ int nmpc_contact_set_actuators(void* torque, const float* rows, int n_rows) {
     t->actuators = {};
     if (rows) t->actuators = {rows, n_rows};
     return NMPC_OK;
+}
+
+int nmpc_contact_set_delays(void* torque, const int* delay, float* history, int depth, float* work, int work_rows, int rows) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (delay) {                                          // what was attached stays
+        if (depth < 1 || depth > NMPC_DELAY_MAX_DEPTH) return fail(t, NMPC_E_ARG, "delays: depth must be in [1, NMPC_DELAY_MAX_DEPTH]");
+        if (rows < 1) return fail(t, NMPC_E_ARG, "delays: rows must be at least 1");
+        if (work_rows < 1) return fail(t, NMPC_E_ARG, "delays: work_rows must be at least 1");
+        if (!history || !work) return fail(t, NMPC_E_ARG, "delays: history and work are needed");
+    }
+    t->delays = {};
+    if (delay) { t->delays.delay = delay; t->delays.history = history; t->delays.depth = depth; t->delays.work = work; t->delays.work_rows = work_rows; t->delays.rows = rows; }
+    return NMPC_OK;
+}
+
+int nmpc_delay_line_batch(void* torque, int B, int n_steps, const float* issued, int issued_rows, float* applied, int applied_rows,
+                          const int* skip, int skip_mask, void* stream) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0) return fail(t, NMPC_E_ARG, "need B >= 0");
+    if (const char* why = delay_line_refusal(t, B, n_steps, issued, issued_rows, applied, applied_rows)) return fail(t, NMPC_E_ARG, why);
+    NMPC_ENTER(t, t->device);
+    return launch_delay_line(t, B, n_steps, issued, issued_rows, applied, applied_rows, skip, skip_mask, stream);
 }
 
 int nmpc_contact_set_integrator(void* torque, int mode) {

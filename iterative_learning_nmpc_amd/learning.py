@@ -74,8 +74,8 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
     `plant` / `plant_substeps` / `push_as_force` / `integrator`: the expert on the ground-contact plant, pushed by a force, under the named integrator;
     `chunk_replans`: the rollout in stretches of that many replans, each appended before the next runs) appends the valid rollouts and their weights to `db`, then
     `train_network` trains `policy` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows.  Returns (err, weights, n_rows, train_loss, val_loss): what
-    the two parts return.  A table of grounds, of payloads or of actuators attached on `layer` (`set_grounds`, `set_payloads`,
-    `set_actuators`) is seen by the plant of the rollouts; there is no keyword for any of them."""
+    the two parts return.  A table of grounds, of payloads, of actuators or of delays attached on `layer` (`set_grounds`,
+    `set_payloads`, `set_actuators`, `set_delays`) is seen by the plant of the rollouts; there is no keyword for any of them."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
     err, weights, n_rows = collect_rollouts(mpc, layer, db, q0, v0, T, push=push, nominal=nominal, ood_weight=ood_weight,
@@ -93,7 +93,8 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
 def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, tau_ff=None, kp: float = KP,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
                     terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False,
-                    push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None):
+                    push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None,
+                    delays=None):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -125,7 +126,12 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     anything.  A layer that has a table of the caller's attached already is refused with ValueError in the same way.
     actuators: a table of actuators, one row (kp, kd, damping, armature) per robot (`BatchedTorqueLayer.set_actuators` takes it and
     validates it; `sample_actuators` draws one), attached for this call in the same way: the plant answers the policy's PD targets
-    with the gains of row b, and `kp`, `kd` are not read for the law.  None: every robot has the nominal drive of `kp`, `kd`."""
+    with the gains of row b, and `kp`, `kd` are not read for the law.  None: every robot has the nominal drive of `kp`, `kd`.
+    delays: a table of delays, one integer per robot (`BatchedTorqueLayer.set_delays` takes it and validates it; `sample_delays`
+    draws one), attached for this call in the same way, in control steps of n_sub dt: the plant answers in control step k the
+    target the policy issued in step k - d_b, and A holds the issued targets.  None: nobody is late, unless the layer has a
+    table of the caller's attached, which then stays and is used.  Either way the shift register starts the rollout holding
+    the posture of q0 (`BatchedTorqueLayer.reset_delay_history`)."""
     if integrator is not None:
         integrator_mode(integrator)                       # an unknown name is refused before anything is attached
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
@@ -148,7 +154,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     parts = [part for part in (("push", push, layer._push, set_push, "a push"),
                                ("grounds", grounds, layer._grounds, layer.set_grounds, "a table of grounds"),
                                ("payloads", payloads, layer._payloads, layer.set_payloads, "a table of payloads"),
-                               ("actuators", actuators, layer._actuators, layer.set_actuators, "a table of actuators")) if part[1] is not None]
+                               ("actuators", actuators, layer._actuators, layer.set_actuators, "a table of actuators"),
+                               ("delays", delays, layer._delays, layer.set_delays, "a table of delays")) if part[1] is not None]
     for name, _, attached, _, what in parts:
         if attached is not None:
             raise ValueError(f"{name}: the layer has {what} attached already (set_{name})")
@@ -162,6 +169,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
             layer.set_integrator(integrator)
         for _, value, _, setter, _ in sorted(parts, key=lambda part: part[0] == "push"):      # the tables, then the push
             setter(value)
+        if layer._delays is not None:
+            layer.reset_delay_history(q0)
         q, v, S, A, failed = layer.policy_rollout(policy, q0, v0, n_steps, dt, n_sub, goal, tau_ff=tau_ff, kp=kp, kd=kd,
                                                   ground=GroundContact() if ground is None else ground, t0=t0,
                                                   period=NOMINAL_PERIOD if period is None else period, db=db,
@@ -179,7 +188,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
 def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float = 5e-4, n_sub: int = 20, kp: Optional[float] = None,
                      kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
                      n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0,
-                     push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None):
+                     push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None,
+                     delays=None):
     """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
         1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
            [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
@@ -197,7 +207,8 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     stand on no plant).  payloads: a payload per robot for the learner's rollout, in the same way: the plant carries it, the
     labels are the nominal expert's -- the expert's model does not describe the load, which is the point.  actuators: an actuator per
     robot for the learner's rollout, in the same way: the plant has the drives of the table, the labels are formed with the nominal
-    `kp`, `kd` -- `label_states` on the visited states, with or without the table.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
+    `kp`, `kd` -- `label_states` on the visited states, with or without the table.  delays: a delay per robot for the
+    learner's rollout, in the same way: the plant is late, the expert's labels are those of the visited states and know no delay.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
     train_loss and val_loss added."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
@@ -206,7 +217,7 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     kp, kd = float(mpc.Kp if kp is None else kp), float(mpc.Kd if kd is None else kd)
     out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
                           terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push,
-                          integrator=integrator, grounds=grounds, payloads=payloads, actuators=actuators)
+                          integrator=integrator, grounds=grounds, payloads=payloads, actuators=actuators, delays=delays)
     A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
     S = out["S"]
     B, K = S.shape[:2]

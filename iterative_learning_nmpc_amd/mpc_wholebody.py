@@ -274,6 +274,11 @@ class LocomotionMPC:
         (`BatchedTorqueLayer.set_payloads`): the plant of rollout b carries row b, the plans and the labels are those of the
         nominal model.  An actuator per rollout likewise (`BatchedTorqueLayer.set_actuators`): the plant of rollout b answers the
         labels with the gains, the joint damping and the rotor inertia of row b, the labels are formed with the nominal kp, kd.
+        A delay per rollout likewise (`BatchedTorqueLayer.set_delays`, in simulation steps; its work_rows must hold the
+        `replanning_steps` of one interval, ValueError otherwise): the plant of rollout b answers in simulation step j the label
+        of step j - d_b, `self.actions` holds the labels as issued.  A call that starts a rollout fills the shift register with
+        the posture of q0 (`reset_delay_history`); resume=True leaves it as the previous call left it, so that the stretches are
+        the one call.
         push_as_force (needs plant): the push is a force on the trunk of the plant over the substeps its window covers
         (nmpc_wb_rollout_set_plant_push), where the feet and the torque limit answer it, instead of the velocity jump per
         replanning interval.
@@ -309,6 +314,10 @@ class LocomotionMPC:
             raise ValueError("plant: the contact plant lives in the torque layer, give torque_layer")
         if push_as_force and plant is None:
             raise ValueError("push_as_force: a push as a force needs the contact plant, give plant")
+        delays = getattr(torque_layer, "_delays", None) if plant is not None else None
+        if delays is not None and delays.work_rows < self.replanning_steps:
+            raise ValueError(f"delays: a replanning interval has {self.replanning_steps} simulation steps, the attached table has work_rows = "
+                             f"{delays.work_rows} (set_delays(..., work_rows=))")
         kp = (self.Kp if plant is not None else KP) if kp is None else kp
         kd = (self.Kd if plant is not None else KD) if kd is None else kd
         windows = push_windows(push, self.batch)      # a window per rollout: attached for this call, the cfg's own window unused
@@ -321,6 +330,8 @@ class LocomotionMPC:
         fs._opts.update(max_iter=cfg_o.max_iter, nlp_tol=cfg_o.nlp_tol, qp_tol=cfg_o.qp_tol)
         failed_in = self.failed.clone() if replan0 else None        # a continued rollout keeps its flags and stamps
         q, v, v_des, w_des, ref_state, status = self._device_inputs(s, q0, v0)
+        if delays is not None and not resume:
+            torque_layer.reset_delay_history(q)           # the posture held before the expert spoke
         actions = None
         if torque_layer is not None:
             rows = n_replans * (self.replanning_steps if record_sim_steps else 1)

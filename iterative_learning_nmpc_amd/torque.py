@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional, Sequence
 
 import numpy as np
@@ -200,6 +201,50 @@ def sample_actuators(n: int, seed: int, kp=(0.5 * KP, 1.5 * KP), kd=(0.5 * KD, 1
     return actuator_table(rows, n)
 
 
+DELAY_MAX_DEPTH = _lib.NMPC_DELAY_MAX_DEPTH                # the deepest shift register of a delay line, and so the largest delay
+
+
+def delay_table(delays, B: int = 1) -> np.ndarray:
+    """Host input of `BatchedTorqueLayer.set_delays` as a validated int32 array [>= B]: the control steps every robot lags by,
+    integers with 0 <= d <= DELAY_MAX_DEPTH; a violation, a wrong shape or fewer than B entries is a ValueError naming the first
+    offending row."""
+    try:
+        rows = np.asarray(delays)
+    except (TypeError, ValueError) as e:
+        raise ValueError("delays: need an integer array [B]") from e
+    if rows.dtype.kind not in "iu":
+        raise ValueError(f"delays: need integers (control steps), got {rows.dtype}")
+    B = max(int(B), 1)
+    if rows.ndim != 1 or rows.shape[0] < B:
+        raise ValueError(f"delays: expected [>= {B}], got {tuple(rows.shape)}")
+    bad = (rows < 0) | (rows > DELAY_MAX_DEPTH)
+    if bad.any():
+        raise ValueError(f"delays: row {int(np.argmax(bad))}: the delay must be in [0, {DELAY_MAX_DEPTH}] control steps")
+    return np.ascontiguousarray(rows.astype(np.int32))
+
+
+def sample_delays(n: int, seed: int, steps=(0, 2)) -> np.ndarray:
+    """A table of delays for `BatchedTorqueLayer.set_delays`: int32 [n], each drawn uniformly from the integers lo .. hi of
+    `steps` (both ends included), in control steps of the call that runs on it.  Row 0 has no delay whatever the range.
+    Deterministic in `seed`."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    try:
+        lo, hi = steps
+    except (TypeError, ValueError) as e:
+        raise ValueError("need steps as a range (lo, hi)") from e
+    if any(not isinstance(x, (int, np.integer)) for x in (lo, hi)):
+        raise ValueError(f"steps: need integers, got {steps!r}")
+    if not lo <= hi:
+        raise ValueError(f"steps: need a range (lo, hi) with lo <= hi, got {steps!r}")
+    if lo < 0 or hi > DELAY_MAX_DEPTH:
+        raise ValueError(f"steps: a delay must be in [0, {DELAY_MAX_DEPTH}] control steps, got {steps!r}")
+    rows =np.random.default_rng(seed).integers(int(lo), int(hi) + 1, n)
+    rows[0] = 0
+    return delay_table(rows, n)
+
+
 class BatchedTorqueLayer:
     def __init__(self, parent: Sequence[int], joint_type: Sequence[int], axis, placement_R, placement_p, mass, com, inertia,
                  foot_joint: Sequence[int], foot_offset, n_actuated: int, gravity=(0.0, 0.0, -9.81), device="cuda:0"):
@@ -232,6 +277,7 @@ class BatchedTorqueLayer:
         self._grounds = None            # set_grounds: the attached table
         self._payloads = None           # set_payloads: the attached table
         self._actuators = None          # set_actuators: the attached table
+        self._delays = None             # set_delays: the attached table with its register and scratch
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -656,6 +702,85 @@ class BatchedTorqueLayer:
         _lib.check(self.lib.nmpc_contact_set_actuators(self._h, ptr(rows), rows.shape[0]), self._h, "nmpc_contact_set_actuators", "torque")
         self._actuators = rows
 
+    def set_delays(self, delays=None, depth: Optional[int] = None, work_rows: int = 64):
+        """nmpc_contact_set_delays: an actuation delay of its own per robot.  delays: an integer array or tensor [B], the control
+        steps robot b's drive lags by (0 <= d <= DELAY_MAX_DEPTH; `sample_delays` draws one).  While the table is attached the
+        PD target `contact_step`, `contact_track`, `policy_rollout` and the expert on the plant (`open_loop_device(..., plant=...)`,
+        and with it `collect_rollouts` and `learning_iteration`, which take no keyword for it: attach the table on the layer they
+        are given) apply to robot b in control step k is the one issued in control step k - d_b, and before that what the shift
+        register `delay_history` [B, depth, nu] holds (slot j: the target issued j + 1 control steps before the next one;
+        `reset_delay_history` fills it with a posture).  The unit is the control step of the call: n_sub dt of `contact_track` and
+        `policy_rollout`, one simulation step of the expert on the plant.  Every call advances the register, so a chain of calls
+        is the long call.  A of `policy_rollout` and the expert's recorded actions are the issued targets; `plan_actions`, the
+        labels, `pd_torques` and `step` do not know about the delay -- it is the plant alone that is late.  A delayed call is bit
+        for bit the un-delayed call on the rows `delay_line` gives, under either integrator, push, windows and the other tables.
+        depth: the slots of the register (None: max(1, delays.max())); a delay beyond it is clamped to it on the device.
+        work_rows: the most control steps one `contact_track` (one replanning interval of the expert) may have; the layer
+        allocates and keeps the register (zeros) and the scratch [B, work_rows, nu] the applied rows go to.  Calls with more
+        robots than the table has rows are refused.
+        Host input is validated (`delay_table`: ValueError) and uploaded; an int32 tensor already on the layer's device is taken
+        as given -- the device clamps it into [0, depth] and validates nothing else.  `set_delays(None)` detaches and drops the
+        register; detached, every call makes the launches and gives the bits it gives without."""
+        if delays is None:
+            self._delays = None
+            _lib.check(self.lib.nmpc_contact_set_delays(self._h, None, None, 0, None, 0, 0), self._h, "nmpc_contact_set_delays", "torque")
+            return
+        if isinstance(delays, torch.Tensor) and delays.is_cuda:
+            if delays.dtype != torch.int32 or delays.dim() != 1 or delays.shape[0] < 1 or delays.device != self.device:
+                raise ValueError(f"delays: a device table must be int32 [B] with B >= 1 on {self.device}")
+            rows = delays.contiguous()
+        else:
+            rows = torch.tensor(delay_table(delays.numpy() if isinstance(delays, torch.Tensor) else delays), device=self.device)
+        if depth is None:
+            depth = min(max(1, int(rows.max())), DELAY_MAX_DEPTH)
+        depth, work_rows = int(depth), int(work_rows)
+        if not 1 <= depth <= DELAY_MAX_DEPTH:
+            raise ValueError(f"delays: depth must be in [1, {DELAY_MAX_DEPTH}], got {depth}")
+        if work_rows < 1:
+            raise ValueError(f"delays: work_rows must be at least 1, got {work_rows}")
+        history = torch.zeros(rows.shape[0], depth, self.nu, dtype=torch.float32, device=self.device)
+        work = torch.empty(rows.shape[0], work_rows, self.nu, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nmpc_contact_set_delays(self._h, ptr(rows), ptr(history), depth, ptr(work), work_rows, rows.shape[0]),
+                   self._h, "nmpc_contact_set_delays", "torque")
+        self._delays = SimpleNamespace(rows=rows, history=history, work=work, depth=depth, work_rows=work_rows)
+
+    @property
+    def delay_history(self) -> Optional[torch.Tensor]:
+        """the attached shift register [B, depth, nu] itself (write into it to set it), or None"""
+        return None if self._delays is None else self._delays.history
+
+    def reset_delay_history(self, q):
+        """every slot of robot b's register <- q[b, n - nu:]: the posture held before the controller spoke.  q [B, n], B at most the
+        rows of the attached table; robots beyond B keep their register."""
+        if self._delays is None:
+            raise ValueError("delays: no table is attached (set_delays)")
+        q = self._in(q, (self.n,), "q")
+        history = self._delays.history
+        if q.shape[0] > history.shape[0]:
+            raise ValueError(f"delays: q has {q.shape[0]} rows, the table {history.shape[0]}")
+        history[:q.shape[0]] = q[:, None, self.n - self.nu:]
+
+    def delay_line(self, issued, out: Optional[torch.Tensor] = None, skip: Optional[torch.Tensor] = None, skip_mask: int = 0) -> torch.Tensor:
+        """nmpc_delay_line_batch: issued [B, n_steps, nu] (a slice [:, :n_steps] of a longer table is taken with its stride)
+        through the attached delays and register -> the applied rows [B, n_steps, nu], row k of robot b being the row issued d_b
+        control steps earlier or, before that, what the register held; the register moves on by n_steps.  What `contact_track`
+        does in front of its chain while the table is attached.  out: the tensor the rows go to (None: a new one); skip int32
+        [B]: robots with skip[b] & skip_mask != 0 are left out, their rows of out and their register untouched."""
+        if not isinstance(issued, torch.Tensor) or issued.dim() != 3:
+            raise ValueError(f"issued: need a float32 [B, n_steps, {self.nu}] tensor on {self.device}")
+        B = issued.shape[0]
+        issued, issued_rows = self._rows(issued, self.nu, "issued", B)
+        n_steps = issued.shape[1]
+        if out is None:
+            out = torch.empty(B, n_steps, self.nu, dtype=torch.float32, device=self.device)
+        out, out_rows = self._rows(out, self.nu, "out", B)
+        if out.shape[1] != n_steps:
+            raise ValueError(f"out: need {n_steps} rows, got {out.shape[1]}")
+        self._flags(skip, issued, "skip")
+        _lib.check(self.lib.nmpc_delay_line_batch(self._h, B, n_steps, ptr(issued), issued_rows, ptr(out), out_rows, ptr(skip), int(skip_mask),
+                                                  stream(self.device)), self._h, "nmpc_delay_line_batch", "torque")
+        return out
+
     def _state_io(self, t, name):
         """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != self.n or not t.is_contiguous() \
@@ -684,13 +809,17 @@ class BatchedTorqueLayer:
         [:, :n_steps] of a longer table is taken with its stride).  Q, V [B, n_steps, 18]: the state before every control step
         (row 0 is the start state), written into the given tensors (again slices are fine) or into new ones with record=True;
         None with record=False.  skip int32 [B]: robots with skip[b] & skip_mask != 0 are left out, their q, v and rows
-        untouched.  Bit for bit the chain of `contact_step` calls, under either integrator (`set_integrator`).
+        untouched.  Bit for bit the chain of `contact_step` calls, under either integrator (`set_integrator`).  With a table of
+        delays attached (`set_delays`) A holds the issued targets and at most its work_rows control steps fit one call.
         -> (q, v, Q, V)."""
         q = self._state_io(q, "q"); v = self._state_io(v, "v")
         tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff")
         B = self._batch(q, v, tau_ff)
         A, a_rows = self._rows(A, self.nu, "A", B)
         n_steps = A.shape[1]
+        if self._delays is not None and n_steps > self._delays.work_rows:
+            raise ValueError(f"delays: a track of {n_steps} control steps needs work_rows >= {n_steps}, the attached table has "
+                             f"{self._delays.work_rows} (set_delays(..., work_rows=))")
         if (Q is None) != (V is None):
             raise ValueError("Q and V come together or not at all")
         if Q is None and record:
