@@ -382,7 +382,8 @@ int nmpc_contact_set_integrator(void *torque, int mode);
  *           collision (z < collision_height), joint limits, and the solver bit for a height that is not finite; the velocity-
  *           tracking bit is never raised (there is no command).  If a bit of term_mask is set and failed[b] carries no stamp yet,
  *           (step_index + 1) << NMPC_ROLLOUT_TERM_SHIFT is added.
- * One launch; with S and X NULL the kinematics are not run.  NMPC_E_ARG (text in nmpc_torque_last_error): a tree that is not
+ * One launch (one more behind it, on X, while a table of nmpc_contact_set_noise is attached and X is given); with S and X NULL
+ * the kinematics are not run.  NMPC_E_ARG (text in nmpc_torque_last_error): a tree that is not
  * 18 joints / 12 actuated / 4 feet, a NULL q or v, period <= 0, n_goal < 0, X without goal (n_goal > 0), only one of s_mean /
  * s_std, s_first outside [0, 44], S with s_stride < 44. */
 int nmpc_observe_batch(void *handle, int B, const float *q, const float *v, double t, double period, const float *goal, int n_goal,
@@ -427,6 +428,50 @@ int nmpc_policy_rollout_batch(void *torque, void *policy, int B, const nmpc_poli
  * launches of a rollout are exactly what they are without this call, and nmpc_policy_rollout_cfg is unchanged.  A rollout with
  * only one of Q / V attached, or with qv_rows < n_steps, returns NMPC_E_ARG before any launch. */
 int nmpc_policy_rollout_set_states(void *torque, float *Q, float *V, int qv_rows);
+
+/* Sensor noise and bias per robot on the policy input [decl] (the push, the ground, the payload, the actuator and the delay are
+ * all on the output side of the learner; its input was still ideal: the policy read the plant state to the last bit.  A policy
+ * that outputs PD targets from joint encoders, an IMU and a state estimator never does, and noise is what drives a DAgger
+ * learner into the states the expert is there to label).
+ * noise: dev float [rows][88], caller-owned and kept as a pointer, read in stream order at each launch: row b holds sigma[44] and
+ * then bias[44], in the units of the RAW 44-slot row.  seed: the 64 bits of the key.  first_robot: robot b of a call draws as
+ * robot first_robot + b of the population, so that shards of one population draw distinct streams.  step0: the handle's noise
+ * step from now on.
+ * The rule.  For robot b, r = first_robot + b taken mod 2^32, noise step s taken mod 2^32, slot j, 0 <= j < 44:
+ *   (w0, w1) = the first two words of Philox-4x32-10 with counter (r, s, j, 0) and key (seed lo, seed hi)
+ *   t = (w0 & 0xffff) + (w0 >> 16) + (w1 & 0xffff) + (w1 >> 16) - 131070                   an integer, |t| <= 131070
+ *   g = (float)t * c,  c = (float)(1 / sqrt((2^32 - 1) / 3))                               one fp32 product
+ *   n = (double)bias[j] + (double)sigma[j] * (double)g                                     each operation rounded once, no fma
+ *   X[b][j] <- (float)((double)X[b][j] + n / s_std[j])     where s_std is given and j >= s_first (the normalised columns)
+ *   X[b][j] <- (float)((double)X[b][j] + n)                elsewhere
+ * g is the centred sum of four uniforms on 0 .. 65535 scaled to unit variance: zero mean, |g| < 3.4641, no transcendental, so a
+ * restatement on the host gives the same bits.  A slot with sigma[j] == 0 and bias[j] == 0 is not written; the goal columns
+ * behind slot 43 are never touched.  A kernel of its own, one thread per (robot, slot); nothing else of the table is validated on
+ * the device.
+ * While attached, every nmpc_observe_batch that is given an X makes ONE more launch behind its own -- the rule on that X with
+ * x_stride = 44 + n_goal and the call's s_std, s_first, at the handle's noise step -- and then advances the step by one.  An
+ * observation without an X, such as the last one of a rollout, draws nothing and advances nothing.  nmpc_policy_rollout_batch
+ * inherits this through its observations and stays bit for bit the chain of the public calls; because the step moves on, two
+ * rollouts of K control steps are the rollout of 2 K.
+ * What does not change: S, failed, the rows Q, V of nmpc_policy_rollout_set_states, the plant, the delay register and every label
+ * are the bits they are without a table -- only what the policy is shown moves, and through its actions the states visited.
+ * With nothing attached every call makes exactly the launches it makes without this entry point.
+ * The step is host state of the handle: a captured graph replays the one step value it was captured with.  Capture is out of
+ * scope here.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), what was attached and its step staying: rows < 1.  At nmpc_observe_batch with an X
+ * and at nmpc_policy_rollout_batch, before any launch: B > rows.  noise = NULL detaches (nothing else is read). */
+int nmpc_contact_set_noise(void *torque, const float *noise, int rows, long long seed, long long first_robot, long long step0);
+
+/* The noise step the next observation with an X draws at.  NMPC_E_ARG: a NULL step, nothing attached. */
+int nmpc_contact_noise_step(void *torque, long long *step);
+
+/* The rule alone, on the B rows of X (robot b's at X + b * x_stride, x_stride >= 44; its first 44 slots are read and written), at
+ * the given step: the handle's noise step is neither read nor moved.  s_std: dev double [44] or NULL (X is raw); s_first as
+ * nmpc_observe_batch.  For the chain of the public calls, and for a caller who perturbs a training batch.  One launch,
+ * stream-ordered, no allocation, no synchronisation.
+ * NMPC_E_ARG before any launch: nothing attached, B > rows, a NULL X, x_stride < 44, s_first outside [0, 44]. */
+int nmpc_observe_noise_batch(void *torque, int B, float *X, int x_stride, const double *s_std, int s_first, long long step,
+                             void *stream);
 
 /* A table of PD targets tracked on the contact plant [decl]: n_steps control steps in one launch, control step k being n_sub
  * substeps of nmpc_contact_step_batch's law with q_des = row k of robot b's table, at A + (b * a_rows + k) * 12 (a_rows >=

@@ -117,6 +117,9 @@ SIGNATURES = {
     "nmpc_contact_set_actuators": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_contact_set_delays": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int]),
     "nmpc_delay_line_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "nmpc_contact_set_noise": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong]),
+    "nmpc_contact_noise_step": (c_int, [c_void_p, POINTER(ctypes.c_longlong)]),
+    "nmpc_observe_noise_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     "nmpc_contact_set_integrator": (c_int, [c_void_p, c_int]),
     "nmpc_observe_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -23,7 +23,8 @@
 // point at the robot is nmpc_torque_centroidal.hip.inc, one kernel text with three entry points: how the momentum moves with q --
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
 // momentum A_g(q) v of a plant state alone, which the device rollouts put into x0; the delay line in front of the chain -- a
-// shift register of issued PD targets per robot, a pass of copies -- is nmpc_torque_delay.hip.inc.
+// shift register of issued PD targets per robot, a pass of copies -- is nmpc_torque_delay.hip.inc; sensor noise and bias on the
+// policy input behind the observation -- a counter-based draw per robot, step and slot -- is nmpc_torque_noise.hip.inc.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -39,6 +40,7 @@
 #include "../../include/nmpc.h"
 #include "../../include/nmpc_policy.h"
 #include "../../include/nmpc_torque.h"
+#include "nmpc_batch_row.hpp"
 #include "nmpc_rollout_common.hpp"
 #include "nmpc_torque_plan.hpp"
 #include "nmpc_wb_plan.hpp"
@@ -367,6 +369,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_implicit.hip.inc"
 #include "nmpc_torque_track.hip.inc"
 #include "nmpc_torque_delay.hip.inc"
+#include "nmpc_torque_noise.hip.inc"
 #include "nmpc_torque_centroidal.hip.inc"
 
 }  // namespace nmpc_torque
@@ -409,6 +412,13 @@ struct Torque {
         float* work = nullptr;          // [rows][work_rows][nu]: where the applied rows of a call go
         int work_rows = 0, rows = 0;
     } delays;
+    struct {                            // nmpc_contact_set_noise: sensor noise and bias per robot on the policy input (table == nullptr: none)
+        const float* table = nullptr;   // [rows][88]: sigma[44], bias[44] of robot b, in the units of the raw row
+        int rows = 0;
+        unsigned long long seed = 0;    // the Philox key
+        long long first_robot = 0;      // robot b of a call draws as robot first_robot + b of the population
+        long long step = 0;             // the noise step of the next observation with an X; host state
+    } noise;
     int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
@@ -558,7 +568,30 @@ const char* observe_refusal(const Torque* t, int B, const float* q, const float*
     if (!s_mean != !s_std) return "s_mean and s_std come together or not at all";
     if (s_first < 0 || s_first > OB_STATE) return "s_first must be in [0, 44]";
     if (S && s_stride < OB_STATE) return "s_stride must be at least 44";
+    if (X && t->noise.table && B > t->noise.rows) return "noise: B exceeds rows";
     return nullptr;
+}
+
+// why the attached noise cannot be put on the B rows of X (nullptr: it can)
+const char* observe_noise_refusal(const Torque* t, int B, const float* X, int x_stride, int s_first) {
+    if (!t->noise.table) return "noise: no table is attached (nmpc_contact_set_noise)";
+    if (B > t->noise.rows) return "noise: B exceeds rows";
+    if (!X) return "noise: X is needed";
+    if (x_stride < OB_STATE) return "noise: x_stride must be at least 44";
+    if (s_first < 0 || s_first > OB_STATE) return "noise: s_first must be in [0, 44]";
+    return nullptr;
+}
+
+// the one launch of the noise: what observe_noise_refusal accepted, at noise step `step`
+int launch_observe_noise(Torque* t, int B, float* X, int x_stride, const double* s_std, int s_first, long long step, void* stream) {
+    NoiseArgs p{};
+    p.x_stride = x_stride; p.s_first = s_first;
+    p.first_robot = (unsigned)t->noise.first_robot; p.step = (unsigned)step;
+    p.key0 = (unsigned)t->noise.seed; p.key1 = (unsigned)(t->noise.seed >> 32);
+    p.noise = t->noise.table; p.s_std = s_std; p.X = X;
+    const size_t n = (size_t)B * OB_STATE;
+    hipLaunchKernelGGL(observe_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, p);
+    return launched(t);
 }
 
 // the kinematics pass, with or without the law; with the law of the attached table of grounds if there is one
@@ -1130,6 +1163,34 @@ int nmpc_delay_line_batch(void* torque, int B, int n_steps, const float* issued,
     return launch_delay_line(t, B, n_steps, issued, issued_rows, applied, applied_rows, skip, skip_mask, stream);
 }
 
+int nmpc_contact_set_noise(void* torque, const float* noise, int rows, long long seed, long long first_robot, long long step0) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (noise && rows < 1) return fail(t, NMPC_E_ARG, "noise: rows must be at least 1");      // what was attached stays
+    t->noise = {};
+    if (noise) { t->noise.table = noise; t->noise.rows = rows; t->noise.seed = (unsigned long long)seed; t->noise.first_robot = first_robot; t->noise.step = step0; }
+    return NMPC_OK;
+}
+
+int nmpc_contact_noise_step(void* torque, long long* step) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (!step) return fail(t, NMPC_E_ARG, "noise: step is NULL");
+    if (!t->noise.table) return fail(t, NMPC_E_ARG, "noise: no table is attached (nmpc_contact_set_noise)");
+    *step = t->noise.step;
+    return NMPC_OK;
+}
+
+int nmpc_observe_noise_batch(void* torque, int B, float* X, int x_stride, const double* s_std, int s_first, long long step, void* stream) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0) return fail(t, NMPC_E_ARG, "need B >= 0");
+    if (const char* why = observe_noise_refusal(t, B, X, x_stride, s_first)) return fail(t, NMPC_E_ARG, why);
+    NMPC_ENTER(t, t->device);
+    return launch_observe_noise(t, B, X, x_stride, s_std, s_first, step, stream);
+}
+
 int nmpc_contact_set_integrator(void* torque, int mode) {
     Torque* t = static_cast<Torque*>(torque);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
@@ -1155,7 +1216,12 @@ int nmpc_observe_batch(void* handle, int B, const float* q, const float* v, doub
     a.q = q; a.v = v; a.goal = goal; a.s_mean = s_mean; a.s_std = s_std; a.S = S; a.X = X; a.failed = failed;
     const size_t lds = (S || X) ? ob_lds_bytes(h->host.n) : 0;      // the flags alone run no kinematics and ask for no slice
     hipLaunchKernelGGL(observe_kernel<ObserveArgs>, dim3((unsigned)((B + TPB - 1) / TPB)), dim3(TPB), lds, static_cast<hipStream_t>(stream), h->dev, a);
-    return launched(h);
+    if (const int rc = launched(h)) return rc;
+    if (!X || !h->noise.table) return NMPC_OK;
+    // what the policy is shown: the attached noise on the row's columns of X, at the handle's noise step, which then moves on
+    if (const int rc = launch_observe_noise(h, B, X, OB_STATE + n_goal, s_std, s_first, h->noise.step, stream)) return rc;
+    ++h->noise.step;
+    return NMPC_OK;
 }
 
 int nmpc_contact_track_batch(void* handle, int B, int n_steps, int n_sub, float dt, const nmpc_contact_cfg* cfg, float* q, float* v,

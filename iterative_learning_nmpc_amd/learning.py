@@ -94,7 +94,7 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
                     terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False,
                     push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None,
-                    delays=None):
+                    delays=None, noise=None, noise_seed: int = 0):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -131,7 +131,13 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     draws one), attached for this call in the same way, in control steps of n_sub dt: the plant answers in control step k the
     target the policy issued in step k - d_b, and A holds the issued targets.  None: nobody is late, unless the layer has a
     table of the caller's attached, which then stays and is used.  Either way the shift register starts the rollout holding
-    the posture of q0 (`BatchedTorqueLayer.reset_delay_history`)."""
+    the posture of q0 (`BatchedTorqueLayer.reset_delay_history`).
+    noise: a table of sensor noise, one row (sigma[44], bias[44]) per robot in the units of the raw state row
+    (`BatchedTorqueLayer.set_noise` takes it and validates it; `torque.noise_table` builds one, `sample_noise` draws one), attached
+    for this call in the same way with the key `noise_seed`, first_robot = 0 and the noise step 0: the policy acts on what the
+    sensors of robot b show, while S, failed, Q, V and the plant are those of the true state.  None: the policy reads the true
+    state, unless the layer has a table of the caller's attached, which then stays, is used and keeps counting its own noise
+    step.  A layer that has one attached while `noise` is given is refused with ValueError as for the other tables."""
     if integrator is not None:
         integrator_mode(integrator)                       # an unknown name is refused before anything is attached
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
@@ -155,7 +161,9 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
                                ("grounds", grounds, layer._grounds, layer.set_grounds, "a table of grounds"),
                                ("payloads", payloads, layer._payloads, layer.set_payloads, "a table of payloads"),
                                ("actuators", actuators, layer._actuators, layer.set_actuators, "a table of actuators"),
-                               ("delays", delays, layer._delays, layer.set_delays, "a table of delays")) if part[1] is not None]
+                               ("delays", delays, layer._delays, layer.set_delays, "a table of delays"),
+                               ("noise", noise, layer._noise, lambda table: layer.set_noise(table, seed=noise_seed), "a table of noise"))
+             if part[1] is not None]
     for name, _, attached, _, what in parts:
         if attached is not None:
             raise ValueError(f"{name}: the layer has {what} attached already (set_{name})")
@@ -189,7 +197,7 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
                      kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
                      n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0,
                      push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None,
-                     delays=None):
+                     delays=None, noise=None, noise_seed: int = 0):
     """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
         1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
            [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
@@ -208,7 +216,10 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     labels are the nominal expert's -- the expert's model does not describe the load, which is the point.  actuators: an actuator per
     robot for the learner's rollout, in the same way: the plant has the drives of the table, the labels are formed with the nominal
     `kp`, `kd` -- `label_states` on the visited states, with or without the table.  delays: a delay per robot for the
-    learner's rollout, in the same way: the plant is late, the expert's labels are those of the visited states and know no delay.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
+    learner's rollout, in the same way: the plant is late, the expert's labels are those of the visited states and know no delay.
+    noise, noise_seed: sensor noise per robot for the learner's rollout, in the same way: the learner drives on what its sensors
+    show, the database gets the true rows S and the expert's labels from the true states Q, V -- training on the noisy inputs
+    themselves is not done here.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
     train_loss and val_loss added."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
@@ -217,7 +228,8 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     kp, kd = float(mpc.Kp if kp is None else kp), float(mpc.Kd if kd is None else kd)
     out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
                           terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push,
-                          integrator=integrator, grounds=grounds, payloads=payloads, actuators=actuators, delays=delays)
+                          integrator=integrator, grounds=grounds, payloads=payloads, actuators=actuators, delays=delays,
+                          noise=noise, noise_seed=noise_seed)
     A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
     S = out["S"]
     B, K = S.shape[:2]

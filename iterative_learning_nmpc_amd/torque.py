@@ -245,6 +245,88 @@ def sample_delays(n: int, seed: int, steps=(0, 2)) -> np.ndarray:
     return delay_table(rows, n)
 
 
+# the slots of the 44-slot state row by what measures them; slot 0, the phase, is the controller's own clock and has no sensor
+NOISE_GROUPS = {"v_lin": slice(1, 4), "body_rates": slice(4, 7), "joint_rates": slice(7, 19), "z": slice(19, 20),
+                "quaternion": slice(20, 24), "joints": slice(24, 36), "base_wrt_feet": slice(36, 44)}
+# the default ceilings of `sample_noise` [decl]: declared values in the units of the raw row (m/s, rad/s, rad/s, m, 1, rad, m), the
+# order of magnitude of a legged robot's estimator, IMU and encoders -- not the reference's, which runs its policies on the true state
+NOISE_SIGMA_MAX = {"v_lin": 0.1, "body_rates": 0.05, "joint_rates": 0.5, "z": 0.01, "quaternion": 0.01, "joints": 0.01, "base_wrt_feet": 0.01}
+NOISE_BIAS_MAX = {"v_lin": 0.05, "body_rates": 0.01, "joint_rates": 0.0, "z": 0.01, "quaternion": 0.005, "joints": 0.01, "base_wrt_feet": 0.005}
+
+
+def noise_table(sigma, bias=None, B: int = 1) -> np.ndarray:
+    """Host input of `BatchedTorqueLayer.set_noise` as a validated float32 array [>= B, 88]: row b is sigma[44], then bias[44], of
+    robot b in the units of the raw 44-slot state row.  sigma, bias: [44], the same for all B robots, or [>= B, 44]; bias None:
+    zeros.  sigma must be finite and not negative, bias finite; a violation, a wrong shape or fewer than B rows is a ValueError
+    naming the first offending row."""
+    B = max(int(B), 1)
+    halves = []
+    for name, x in (("sigma", sigma), ("bias", np.zeros(N_STATE, np.float32) if bias is None else bias)):
+        try:
+            x = np.asarray(x, dtype=np.float32)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"noise: {name}: need a float array [{N_STATE}] or [B, {N_STATE}]") from e
+        if x.ndim == 1 and x.shape[0] == N_STATE:
+            x = np.broadcast_to(x, (B, N_STATE))
+        if x.ndim != 2 or x.shape[1] != N_STATE or x.shape[0] < B:
+            raise ValueError(f"noise: {name}: expected [{N_STATE}] or [>= {B}, {N_STATE}], got {tuple(x.shape)}")
+        halves.append(x)
+    sigma, bias = halves
+    if sigma.shape[0] != bias.shape[0]:
+        n = min(sigma.shape[0], bias.shape[0])            # one was broadcast to B, the other given longer
+        sigma, bias = sigma[:n], bias[:n]
+    for why, bad in (("sigma must be finite", ~np.isfinite(sigma).all(axis=1)), ("sigma must not be negative", ~(sigma >= 0.0).all(axis=1)),
+                     ("bias must be finite", ~np.isfinite(bias).all(axis=1))):
+        if bad.any():
+            raise ValueError(f"noise: row {int(np.argmax(bad))}: {why}")
+    return np.ascontiguousarray(np.concatenate([sigma, bias], axis=1))
+
+
+def _noise_rows(table) -> np.ndarray:
+    """a host table [B, 88] as `set_noise` is given it, through the validation of `noise_table`"""
+    try:
+        rows = np.asarray(table, dtype=np.float32)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"noise: need a float array [B, {2 * N_STATE}]") from e
+    if rows.ndim != 2 or rows.shape[1] != 2 * N_STATE or rows.shape[0] < 1:
+        raise ValueError(f"noise: expected [>= 1, {2 * N_STATE}], got {tuple(rows.shape)}")
+    return noise_table(rows[:, :N_STATE], rows[:, N_STATE:], rows.shape[0])
+
+
+def sample_noise(n: int, seed: int, sigma=None, bias=None) -> np.ndarray:
+    """A table of sensor noise for `BatchedTorqueLayer.set_noise`: float32 [n, 88].  Per robot and group of NOISE_GROUPS one
+    standard deviation, drawn uniformly from [0, ceiling of the group] and given to every slot of the group, and per robot and
+    slot a bias drawn uniformly from [-ceiling, +ceiling] of its group.  sigma, bias: dicts of ceilings by group name that
+    replace the defaults NOISE_SIGMA_MAX, NOISE_BIAS_MAX [decl] group by group (None: the defaults).  The phase, slot 0, is
+    always exact, and row 0 is all zero whatever the ceilings: the robot with ideal sensors.  Deterministic in `seed`: the
+    groups are drawn in the order of NOISE_GROUPS, sigma then bias."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    tops = []
+    for name, given, default in (("sigma", sigma, NOISE_SIGMA_MAX), ("bias", bias, NOISE_BIAS_MAX)):
+        given = {} if given is None else dict(given)
+        unknown = sorted(set(given) - set(NOISE_GROUPS))
+        if unknown:
+            raise ValueError(f"{name}: unknown groups {unknown}, expected some of {list(NOISE_GROUPS)}")
+        top = {g: float(given.get(g, default[g])) for g in NOISE_GROUPS}
+        for g, hi in top.items():
+            if not (np.isfinite(hi) and hi >= 0.0):
+                raise ValueError(f"{name}: the ceiling of {g} must be finite and not negative, got {hi!r}")
+        tops.append(top)
+    rng = np.random.default_rng(seed)
+    rows = np.zeros((n, 2 * N_STATE), np.float32)
+    for g, slots in NOISE_GROUPS.items():
+        width = slots.stop - slots.start
+        for half, hi, draw in ((0, tops[0][g], rng.uniform(0.0, tops[0][g], (n, 1))), (1, tops[1][g], rng.uniform(-tops[1][g], tops[1][g], (n, width)))):
+            hi32 = np.float32(hi)                         # the largest float32 inside the ceiling: a rounded draw is held to it
+            if hi32 > hi:
+                hi32 = np.nextafter(hi32, np.float32(-np.inf))
+            rows[:, half * N_STATE + slots.start:half * N_STATE + slots.stop] = np.clip(draw.astype(np.float32), 0.0 if half == 0 else -hi32, hi32)
+    rows[0] = 0.0
+    return _noise_rows(rows)
+
+
 class BatchedTorqueLayer:
     def __init__(self, parent: Sequence[int], joint_type: Sequence[int], axis, placement_R, placement_p, mass, com, inertia,
                  foot_joint: Sequence[int], foot_offset, n_actuated: int, gravity=(0.0, 0.0, -9.81), device="cuda:0"):
@@ -278,6 +360,7 @@ class BatchedTorqueLayer:
         self._payloads = None           # set_payloads: the attached table
         self._actuators = None          # set_actuators: the attached table
         self._delays = None             # set_delays: the attached table with its register and scratch
+        self._noise = None              # set_noise: the attached table
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -475,7 +558,9 @@ class BatchedTorqueLayer:
         (phase over `period`, base_wrt_feet from the tree's own feet) and the policy input [row, goal] with columns
         [s_first, 44) normalised by s_mean, s_std (float64 [44]; None: raw), as `DeviceDatabase.batch` assembles it.  failed:
         int32 [B] on the device, updated in place with the flags the state raises and, where a bit of term_mask is set and
-        no stamp is present, the stamp step_index + 1 (None: nothing is written).  -> (S_row [B, 44], X [B, 44 + n_goal])."""
+        no stamp is present, the stamp step_index + 1 (None: nothing is written).  With a table of noise attached (`set_noise`) X
+        is what the sensors of robot b show -- `observe_noise` at `noise_step`, which then moves on by one; S_row and failed are
+        those of the true state.  -> (S_row [B, 44], X [B, 44 + n_goal])."""
         q = self._in(q, (self.n,), "q"); v = self._in(v, (self.n,), "v")
         B = self._batch(q, v)
         goal = self._goal(goal, B)
@@ -503,7 +588,9 @@ class BatchedTorqueLayer:
         with s_mean, s_std given directly (from column 1 on).  One rollout per layer at a time: the dense actions of a step
         live in a buffer of the layer's handle, which grows (and then synchronises the device) for a larger batch.  Nothing is frozen: a robot whose flags hit terminate_mask is stamped in failed
         (failed >> 8 = 1 + the control step whose observation saw it) and keeps being stepped.
-        The contact steps are those of the layer's integrator (`set_integrator`).
+        The contact steps are those of the layer's integrator (`set_integrator`).  With a table of noise attached (`set_noise`)
+        the policy acts on the perturbed input of each of its n_steps observations and `noise_step` moves on by n_steps; S holds
+        the true rows.
         -> (q, v, S [B, n_steps, 44], A [B, n_steps, 12], failed int32 [B]); S and A are None with record=False."""
         q = self._in(q, (self.n,), "q").clone(); v = self._in(v, (self.n,), "v").clone()
         tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff")
@@ -780,6 +867,63 @@ class BatchedTorqueLayer:
         _lib.check(self.lib.nmpc_delay_line_batch(self._h, B, n_steps, ptr(issued), issued_rows, ptr(out), out_rows, ptr(skip), int(skip_mask),
                                                   stream(self.device)), self._h, "nmpc_delay_line_batch", "torque")
         return out
+
+    def set_noise(self, noise=None, seed: int = 0, first_robot: int = 0, step0: int = 0):
+        """nmpc_contact_set_noise: sensor noise and bias of its own per robot on what the policy is shown.  noise: a float array or
+        tensor [B, 88], row b being sigma[44] then bias[44] of robot b in the units of the raw 44-slot state row (`noise_table`
+        builds one, `sample_noise` draws one).  While the table is attached every `observe`, and so every control step of
+        `policy_rollout`, `learning.evaluate_policy` and `learning.dagger_iteration`, adds bias + sigma g to the row's slots of the
+        policy input X by one more launch behind the observation's own -- g a zero-mean, unit-variance, bounded (|g| < 3.4641)
+        variate that is a pure function of (seed, first_robot + b, noise step, slot), divided by the column's s_std where X is
+        normalised -- and advances the layer's noise step (`noise_step`) by one; a slot whose sigma and bias are zero is not
+        written.  The state rows S, the fall flags, the plant, the rows Q, V of `set_rollout_states`, the delay register and the
+        expert's labels stay on the true state: only what the policy is shown moves.  seed: 64 bits; first_robot: robot b draws
+        as robot first_robot + b of the population, so that shards of a population draw distinct streams and robot b of a batch
+        is the batch of one with first_robot = b; step0: the noise step of the next observation.  Because the step moves on, two
+        rollouts of K control steps are the rollout of 2 K.  Calls with more robots than the table has rows are refused.
+        Host input is validated (`noise_table`: ValueError) and uploaded; a float32 tensor already on the layer's device is taken
+        as given -- the device validates nothing -- and in either case the layer keeps the table alive while it is attached.
+        `set_noise(None)` detaches; detached, every call makes the launches and gives the bits it gives without."""
+        if noise is None:
+            self._noise = None
+            _lib.check(self.lib.nmpc_contact_set_noise(self._h, None, 0, 0, 0, 0), self._h, "nmpc_contact_set_noise", "torque")
+            return
+        rows = self._table(noise, "noise", range(2 * N_STATE), _noise_rows)
+        first_robot, step0 = int(first_robot), int(step0)
+        if not (0 <= first_robot < 2 ** 63 and 0 <= step0 < 2 ** 63):
+            raise ValueError("noise: first_robot and step0 must be in [0, 2^63)")
+        key = int(seed) & (2 ** 64 - 1)                   # the 64 bits of the key, as the signed argument that carries them
+        _lib.check(self.lib.nmpc_contact_set_noise(self._h, ptr(rows), rows.shape[0], key - 2 ** 64 if key >= 2 ** 63 else key, first_robot, step0),
+                   self._h, "nmpc_contact_set_noise", "torque")
+        self._noise = rows
+
+    @property
+    def noise_step(self) -> Optional[int]:
+        """nmpc_contact_noise_step: the noise step the next observation with a policy input draws at, or None with nothing attached"""
+        if self._noise is None:
+            return None
+        step = ctypes.c_longlong()
+        _lib.check(self.lib.nmpc_contact_noise_step(self._h, ctypes.byref(step)), self._h, "nmpc_contact_noise_step", "torque")
+        return step.value
+
+    def observe_noise(self, X, step: int, s_std=None, s_first: int = 1) -> torch.Tensor:
+        """nmpc_observe_noise_batch: the attached noise on the first 44 columns of X, a contiguous float32 [B, >= 44] tensor on
+        the layer's device, IN PLACE, at noise step `step`; the layer's own noise step is neither read nor moved.  s_std: float64
+        [44], the statistics X was normalised with from column s_first on (None: X is raw).  What `observe` does behind its own
+        launch while the table is attached -- for the chain of the public calls, and to perturb a training batch.  -> X."""
+        if not isinstance(X, torch.Tensor) or X.dtype != torch.float32 or X.dim() != 2 or X.shape[1] < N_STATE or not X.is_contiguous() \
+                or X.device != self.device:
+            raise ValueError(f"X: need a contiguous float32 [B, >= {N_STATE}] tensor on {self.device}")
+        if s_std is not None:
+            s_std = torch.as_tensor(s_std, dtype=torch.float64, device=self.device).contiguous()
+            if tuple(s_std.shape) != (N_STATE,):
+                raise ValueError(f"s_std: expected [{N_STATE}]")
+        step = int(step)
+        if not 0 <= step < 2 ** 63:
+            raise ValueError("noise: step must be in [0, 2^63)")
+        _lib.check(self.lib.nmpc_observe_noise_batch(self._h, X.shape[0], ptr(X), X.shape[1], ptr(s_std), int(s_first), step, stream(self.device)),
+                   self._h, "nmpc_observe_noise_batch", "torque")
+        return X
 
     def _state_io(self, t, name):
         """t, a contiguous float32 [B, n] tensor on the device that a call updates in place"""
