@@ -111,6 +111,42 @@ int nmpc_policy_train_epoch(void *handle, const nmpc_batch_source *src, const fl
                             int n_batches, unsigned long long seed, float lr, double *scratch, float *losses,
                             int *idx_out, void *stream);
 
+/* Input noise on the batches of nmpc_policy_train_epoch [decl]: a policy that is deployed behind noisy sensors
+ * (nmpc_contact_set_noise, nmpc_torque.h) is trained on perturbed inputs, and the epoch call assembles its batches inside the
+ * library, so the perturbation is attached to the handle.
+ * sigma: dev float [n], caller-owned and kept as a pointer, read in stream order at each launch, in the units of the RAW input
+ * columns 0 .. n-1, 1 <= n <= n_in.  seed: the 64 bits of the key.  epoch0: the handle's noise epoch from now on.
+ * The rule.  For row i of a call and column j < n:
+ *   (w0, w1) = the first two words of Philox-4x32-10 with counter ((first_sample + i) mod 2^32, epoch mod 2^32, j, 1) and key
+ *              (seed lo, seed hi)
+ *   t, g as in the sensor rule of nmpc_contact_set_noise: t the centred sum of the four 16-bit halves, g = (float)t * c
+ *   nz = (double)sigma[j] * (double)g
+ *   X[i][j] <- (float)((double)X[i][j] + nz / s_std[j])     where s_std is given and j >= s_first (the normalised columns)
+ *   X[i][j] <- (float)((double)X[i][j] + nz)                elsewhere
+ * each operation rounded once, no fma.  A column with sigma[j] == 0 is not written; columns from n on are never addressed.  The
+ * fourth counter word 1 keeps these streams apart from the sensor noise of a rollout (word 0) under a shared seed.  A kernel of
+ * its own, one thread per (row, column); nothing of sigma is validated on the device.
+ * While attached, nmpc_policy_train_epoch makes ONE more launch per batch, between the assembly of the batch and its step, on the
+ * staged x: the rule with first_sample = t * batch for batch t, at the handle's epoch, with s_std and s_first of the call's
+ * nmpc_batch_source.  It needs n <= src->n_state (NMPC_E_ARG before any launch otherwise).  A call with n_batches > 0 then
+ * advances the handle's epoch by one; n_batches == 0 advances nothing.  The epoch is bit for bit the chain: the idx of the epoch,
+ * nmpc_assemble_batch of idx[t], nmpc_policy_input_noise_batch(epoch, first_sample = t * batch), nmpc_policy_train_step.
+ * nmpc_policy_train_step, nmpc_policy_forward and nmpc_policy_loss never draw: validation stays on clean rows.  With nothing
+ * attached every call makes exactly the launches it makes without this entry point.  The epoch is host state of the handle;
+ * graph capture is out of scope.
+ * NMPC_E_ARG, what was attached and its epoch staying: n outside [1, n_in].  sigma = NULL detaches (nothing else is read). */
+int nmpc_policy_set_input_noise(void *policy, const float *sigma, int n, long long seed, long long epoch0);
+
+/* The epoch the next nmpc_policy_train_epoch draws at.  NMPC_E_ARG: a NULL epoch, nothing attached. */
+int nmpc_policy_input_noise_epoch(void *policy, long long *epoch);
+
+/* The rule alone, on the B rows of X (row i at X + i * x_stride; its first n columns are read and written), at the given epoch
+ * and first sample: the handle's epoch is neither read nor moved.  s_std: dev double [>= n] or NULL (X is raw).  One launch,
+ * stream-ordered, no allocation, no synchronisation.
+ * NMPC_E_ARG before any launch: nothing attached, a NULL X, x_stride < n, s_first < 0. */
+int nmpc_policy_input_noise_batch(void *policy, int B, float *X, int x_stride, const double *s_std, int s_first,
+                                  long long epoch, long long first_sample, void *stream);
+
 /* network.eval(); mean |network(X) - Y| over n rows, n of any size >= 1 (the validation loss of
  * train_locosafedagger.py:129-132).  X[n][n_in], Y[n][n_out], loss: device scalar.  Parameters, running statistics
  * and optimiser state are not touched.  The sum runs in a fixed order, in float64 across blocks: the same bits on

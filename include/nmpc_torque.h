@@ -473,6 +473,29 @@ int nmpc_contact_noise_step(void *torque, long long *step);
 int nmpc_observe_noise_batch(void *torque, int B, float *X, int x_stride, const double *s_std, int s_first, long long step,
                              void *stream);
 
+/* The rows the sensors showed [decl]: the raw 44-slot row in the units of the database's state table, as robot b's sensors show
+ * it at noise step `step` -- the handle's own noise step is neither read nor moved.  For robot b (its true row at S + b *
+ * s_stride, its observed row at O + b * o_stride) and slot j < 44, with n exactly the n of nmpc_contact_set_noise's rule at counter
+ * (first_robot + b, step, j, 0), the draw that perturbs X at that step:
+ *   O[b][j] = (float)((double)S[b][j] + n)     where sigma[j] != 0 || bias[j] != 0
+ *   O[b][j] = S[b][j], the same bits           elsewhere, and whenever no table is attached
+ * Where X is raw, the first 44 columns of the perturbed X of that step are this row to the bit; where X is normalised the two
+ * differ by roundings.  O may be S: every element is read and written by its own thread alone.  A kernel of its own, one thread
+ * per (robot, slot): one launch, stream-ordered, no allocation, no synchronisation.
+ * NMPC_E_ARG before any launch: a NULL S or O, a stride below 44, B > rows while a table is attached. */
+int nmpc_observed_rows_batch(void *torque, int B, const float *S, int s_stride, float *O, int o_stride, long long step, void *stream);
+
+/* The observed rows beside a policy rollout, attached as nmpc_policy_rollout_set_states attaches Q, V: O is dev float
+ * [B][o_rows][44], caller-owned and kept as a pointer.  While attached, control step k of every nmpc_policy_rollout_batch of the
+ * handle writes robot b's observed row to O + (b * o_rows + k) * 44 by ONE more launch per control step:
+ * nmpc_observed_rows_batch on the step's true row at the noise step the step's observation drew X at -- read before the
+ * observation advances it, so row k of O and the input the policy acted on in step k are one draw.  With a rollout whose S is
+ * NULL the observation writes the true row into O's row and the launch perturbs it in place.  O is bit for bit the chain
+ * nmpc_contact_noise_step, nmpc_observe_batch, nmpc_observed_rows_batch at the step read; with no table of noise attached it is
+ * S.  S, A, q, v, failed, the Q, V of nmpc_policy_rollout_set_states, the delay register and the noise step are the bits they
+ * are without O.  O = NULL detaches.  A rollout with o_rows < n_steps returns NMPC_E_ARG before any launch. */
+int nmpc_policy_rollout_set_observed(void *torque, float *O, int o_rows);
+
 /* A table of PD targets tracked on the contact plant [decl]: n_steps control steps in one launch, control step k being n_sub
  * substeps of nmpc_contact_step_batch's law with q_des = row k of robot b's table, at A + (b * a_rows + k) * 12 (a_rows >=
  * n_steps; 12 = n_actuated).  With the label rows of nmpc_plan_actions_batch as the table, A = (tau_id + kd v_plan) / kp + q_plan,

@@ -86,6 +86,9 @@ SIGNATURES = {
     "nmpc_policy_train_epoch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_ulonglong, c_float, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
     "nmpc_policy_loss": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nmpc_policy_set_input_noise": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong]),
+    "nmpc_policy_input_noise_epoch": (c_int, [c_void_p, POINTER(ctypes.c_longlong)]),
+    "nmpc_policy_input_noise_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
     # include/nmpc_dataset.h
     "nmpc_dataset_last_error": (ctypes.c_char_p, []),
     "nmpc_ring_append": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
@@ -126,6 +129,8 @@ SIGNATURES = {
     "nmpc_policy_rollout_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nmpc_policy_rollout_set_states": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "nmpc_policy_rollout_set_observed": (c_int, [c_void_p, c_void_p, c_int]),
+    "nmpc_observed_rows_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     "nmpc_contact_track_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "nmpc_observe_rows_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double,

@@ -10,6 +10,7 @@
 
 #include "nmpc_batch_row.hpp"
 #include "nmpc_host.hpp"
+#include "nmpc_noise.hpp"
 
 #include <cmath>
 #include <cstdint>
@@ -472,6 +473,33 @@ __global__ __launch_bounds__(256) void sample_assemble_kernel(const nmpc_batch_s
     for (int e = lane; e < width; e += 64) nmpc_batch::write_element(t, (size_t)r, j, e, x, y);
 }
 
+struct InputNoiseArgs {
+    int n, x_stride, s_first;
+    unsigned first_sample, epoch, key0, key1;
+    const float* sigma;                                   // [n], in the units of the raw columns
+    const double* s_std;                                  // [>= n] or nullptr: X is raw
+    float* X;                                             // row i at X + i * x_stride, its first n columns are touched
+};
+
+// Input noise on a training batch (nmpc_policy_set_input_noise), one thread per (row, column): column j < n of row i gets
+// sigma[j] g added in fp64, g the variate of nmpc_noise.hpp at counter (first_sample + i, epoch, j, 1) -- the fourth word 1 keeps
+// these streams apart from the rollout's sensor noise (word 0) under a shared seed --, divided by the column's s_std where X is
+// normalised; each operation rounded once.  A column with sigma[j] == 0 is not written, columns from n on are never addressed.
+__global__ __launch_bounds__(256) void input_noise_kernel(int B, const InputNoiseArgs p) {
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)B * p.n) return;
+    const size_t i = e / p.n;
+    const int j = (int)(e - i * p.n);
+    const float sigma = p.sigma[j];
+    if (sigma == 0.0f) return;
+    const float g = nmpc_noise::variate(p.first_sample + (unsigned)i, p.epoch, (unsigned)j, 1u, p.key0, p.key1);
+    const double nz = (double)sigma * (double)g;
+    float* x = p.X + i * p.x_stride + j;
+    const double add = (p.s_std && j >= p.s_first) ? nz / p.s_std[j] : nz;
+    *x = (float)((double)*x + add);
+}
+
 // Validation loss, one chunk of rows: slot[block] (+)= sum |P - Y| over the block's 256 elements, in float64.  A slot
 // belongs to one block of every chunk and the chunks follow each other on the stream, so a slot adds its chunks up in
 // chunk order without an atomic; the first chunk overwrites what an earlier call left.
@@ -534,6 +562,12 @@ struct Policy {
     float *sign_count = nullptr;  // int[n_out]: l1_kernel's sign counts (allocated and zeroed with the float buffers)
     float *stage_x = nullptr, *stage_y = nullptr;   // the epoch call's batch [batch_max][n_in], [batch_max][n_out]
     float *eval_slot = nullptr;   // double[blocks of a batch_max chunk]: nmpc_policy_loss's partial sums (allocated with the float buffers)
+    struct {                      // nmpc_policy_set_input_noise: noise on the input columns of the epoch call's batches (sigma == nullptr: none)
+        const float* sigma = nullptr;   // [n], in the units of the raw columns
+        int n = 0;
+        unsigned long long seed = 0;    // the Philox key
+        long long epoch = 0;            // the epoch the next nmpc_policy_train_epoch draws at; host state
+    } input_noise;
     bool grad_dirty = false;   // a step that did not reach adam_kernel left grad non-zero
     long long step = 0;
     std::string err;
@@ -852,6 +886,50 @@ int nmpc_weighted_sample(const float* weights, long long n, int num_samples, uns
     return launched(no_handle);
 }
 
+// the one launch of the input noise on the B rows of X, at the given epoch and first sample
+void launch_input_noise(Policy* p, int B, float* X, int x_stride, const double* s_std, int s_first, long long epoch, long long first_sample,
+                        hipStream_t st) {
+    InputNoiseArgs a{};
+    a.n = p->input_noise.n; a.x_stride = x_stride; a.s_first = s_first;
+    a.first_sample = (unsigned)first_sample; a.epoch = (unsigned)epoch;
+    a.key0 = (unsigned)p->input_noise.seed; a.key1 = (unsigned)(p->input_noise.seed >> 32);
+    a.sigma = p->input_noise.sigma; a.s_std = s_std; a.X = X;
+    hipLaunchKernelGGL(input_noise_kernel, dim3(blocks_for((size_t)B * a.n)), dim3(256), 0, st, B, a);
+}
+
+int nmpc_policy_set_input_noise(void* handle, const float* sigma, int n, long long seed, long long epoch0) {
+    Policy* p = static_cast<Policy*>(handle);
+    if (!p) return fail(p, NMPC_E_ARG, "null handle");
+    if (sigma && (n < 1 || n > p->d.n_in)) return fail(p, NMPC_E_ARG, "input noise: need 1 <= n <= n_in");      // what was attached stays
+    p->input_noise = {};
+    if (sigma) { p->input_noise.sigma = sigma; p->input_noise.n = n; p->input_noise.seed = (unsigned long long)seed; p->input_noise.epoch = epoch0; }
+    return NMPC_OK;
+}
+
+int nmpc_policy_input_noise_epoch(void* handle, long long* epoch) {
+    Policy* p = static_cast<Policy*>(handle);
+    if (!p) return fail(p, NMPC_E_ARG, "null handle");
+    if (!epoch) return fail(p, NMPC_E_ARG, "input noise: epoch is NULL");
+    if (!p->input_noise.sigma) return fail(p, NMPC_E_ARG, "input noise: no table is attached (nmpc_policy_set_input_noise)");
+    *epoch = p->input_noise.epoch;
+    return NMPC_OK;
+}
+
+int nmpc_policy_input_noise_batch(void* handle, int B, float* X, int x_stride, const double* s_std, int s_first, long long epoch,
+                                  long long first_sample, void* stream) {
+    Policy* p = static_cast<Policy*>(handle);
+    if (!p) return fail(p, NMPC_E_ARG, "null handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0) return fail(p, NMPC_E_ARG, "need B >= 0");
+    if (!p->input_noise.sigma) return fail(p, NMPC_E_ARG, "input noise: no table is attached (nmpc_policy_set_input_noise)");
+    if (!X) return fail(p, NMPC_E_ARG, "input noise: X is needed");
+    if (x_stride < p->input_noise.n) return fail(p, NMPC_E_ARG, "input noise: x_stride must be at least n");
+    if (s_first < 0) return fail(p, NMPC_E_ARG, "input noise: s_first must not be negative");
+    NMPC_ENTER(p, p->device);
+    launch_input_noise(p, B, X, x_stride, s_std, s_first, epoch, first_sample, static_cast<hipStream_t>(stream));
+    return launched(p);
+}
+
 size_t nmpc_policy_train_epoch_scratch(long long n_rows) {
     return n_rows < 1 ? 0 : (size_t)n_rows + (size_t)(n_rows / SCAN_CHUNK) + 2;
 }
@@ -873,14 +951,19 @@ int nmpc_policy_train_epoch(void* handle, const nmpc_batch_source* src, const fl
     if (n_batches < 0 || (long long)n_batches * batch > 0x7fffffffLL) return fail(p, NMPC_E_ARG, "need 0 <= n_batches * batch < 2^31");
     if (src->n_rows < 1 || src->n_rows > 0x7fffffffLL) return fail(p, NMPC_E_ARG, "need 1 <= n_rows < 2^31");
     if (!(lr > 0.0f)) return fail(p, NMPC_E_ARG, "learning rate must be positive");
+    const bool noisy = p->input_noise.sigma != nullptr;
+    if (noisy && p->input_noise.n > src->n_state) return fail(p, NMPC_E_ARG, "input noise: n exceeds the n_state of the batch source");
     hipStream_t st = static_cast<hipStream_t>(stream);
     NMPC_ENTER(p, p->device);
     const double* total = build_cdf(st, weights, src->n_rows, scratch);
     for (int t = 0; t < n_batches; ++t) {
         hipLaunchKernelGGL(sample_assemble_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, *src, scratch, total, seed,
                            t * batch, batch, p->stage_x, p->stage_y, idx_out);
+        // the attached input noise on the staged batch, at the handle's epoch: sample t * batch + i of the epoch for row i
+        if (noisy) launch_input_noise(p, batch, p->stage_x, p->d.n_in, src->s_std, src->s_first, p->input_noise.epoch, (long long)t * batch, st);
         if (const int rc = train_step(p, batch, p->stage_x, p->stage_y, lr, losses + t, nullptr, st)) return rc;
     }
+    if (noisy) ++p->input_noise.epoch;
     return launched(p);
 }
 

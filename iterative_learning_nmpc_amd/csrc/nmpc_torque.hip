@@ -24,7 +24,8 @@
 // d(A_g v)/dq, d com/dq and the bias of its time derivative --, the momentum pass on the nodes of a whole-body solve, and the
 // momentum A_g(q) v of a plant state alone, which the device rollouts put into x0; the delay line in front of the chain -- a
 // shift register of issued PD targets per robot, a pass of copies -- is nmpc_torque_delay.hip.inc; sensor noise and bias on the
-// policy input behind the observation -- a counter-based draw per robot, step and slot -- is nmpc_torque_noise.hip.inc.
+// policy input behind the observation -- a counter-based draw per robot, step and slot -- is nmpc_torque_noise.hip.inc, and so are
+// the rows the sensors showed beside a policy rollout.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_host.hpp"
@@ -41,6 +42,7 @@
 #include "../../include/nmpc_policy.h"
 #include "../../include/nmpc_torque.h"
 #include "nmpc_batch_row.hpp"
+#include "nmpc_noise.hpp"
 #include "nmpc_rollout_common.hpp"
 #include "nmpc_torque_plan.hpp"
 #include "nmpc_wb_plan.hpp"
@@ -395,6 +397,10 @@ struct Torque {
         float *Q = nullptr, *V = nullptr;
         int rows = 0;
     } states;
+    struct {                            // nmpc_policy_rollout_set_observed: the rows the sensors showed beside a policy rollout (O == nullptr: none)
+        float* O = nullptr;
+        int rows = 0;
+    } observed;
     nmpc_push_cfg push{};               // nmpc_contact_set_push: the push of the plant calls (force == nullptr: none)
     nmpc_torque::PushWindows windows{}; // nmpc_contact_set_push_windows: a window per robot in place of the push's own (first == nullptr: none)
     struct Table {                      // a row per robot (rows == nullptr: none)
@@ -591,6 +597,26 @@ int launch_observe_noise(Torque* t, int B, float* X, int x_stride, const double*
     p.noise = t->noise.table; p.s_std = s_std; p.X = X;
     const size_t n = (size_t)B * OB_STATE;
     hipLaunchKernelGGL(observe_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, p);
+    return launched(t);
+}
+
+// why the observed rows of S cannot be written to O (nullptr: they can); with no table attached O is S
+const char* observed_rows_refusal(const Torque* t, int B, const float* S, int s_stride, const float* O, int o_stride) {
+    if (!S || !O) return "observed: S and O are needed";
+    if (s_stride < OB_STATE || o_stride < OB_STATE) return "observed: s_stride and o_stride must be at least 44";
+    if (t->noise.table && B > t->noise.rows) return "observed: B exceeds the rows of the noise table";
+    return nullptr;
+}
+
+// the one launch of the observed rows: what observed_rows_refusal accepted, at noise step `step`
+int launch_observed_rows(Torque* t, int B, const float* S, int s_stride, float* O, int o_stride, long long step, void* stream) {
+    ObservedArgs p{};
+    p.s_stride = s_stride; p.o_stride = o_stride;
+    p.first_robot = (unsigned)t->noise.first_robot; p.step = (unsigned)step;
+    p.key0 = (unsigned)t->noise.seed; p.key1 = (unsigned)(t->noise.seed >> 32);
+    p.noise = t->noise.table; p.S = S; p.O = O;
+    const size_t n = (size_t)B * OB_STATE;
+    hipLaunchKernelGGL(observed_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, p);
     return launched(t);
 }
 
@@ -1191,6 +1217,16 @@ int nmpc_observe_noise_batch(void* torque, int B, float* X, int x_stride, const 
     return launch_observe_noise(t, B, X, x_stride, s_std, s_first, step, stream);
 }
 
+int nmpc_observed_rows_batch(void* torque, int B, const float* S, int s_stride, float* O, int o_stride, long long step, void* stream) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (B == 0) return NMPC_OK;
+    if (B < 0) return fail(t, NMPC_E_ARG, "need B >= 0");
+    if (const char* why = observed_rows_refusal(t, B, S, s_stride, O, o_stride)) return fail(t, NMPC_E_ARG, why);
+    NMPC_ENTER(t, t->device);
+    return launch_observed_rows(t, B, S, s_stride, O, o_stride, step, stream);
+}
+
 int nmpc_contact_set_integrator(void* torque, int mode) {
     Torque* t = static_cast<Torque*>(torque);
     if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
@@ -1262,6 +1298,14 @@ int nmpc_policy_rollout_set_states(void* torque, float* Q, float* V, int qv_rows
     return NMPC_OK;
 }
 
+int nmpc_policy_rollout_set_observed(void* torque, float* O, int o_rows) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    t->observed = {};
+    if (O) { t->observed.O = O; t->observed.rows = o_rows; }
+    return NMPC_OK;
+}
+
 int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_policy_rollout_cfg* cfg, const nmpc_contact_cfg* ground,
                               float* q, float* v, const float* tau_ff, const float* goal, const double* s_mean, const double* s_std,
                               float* S, float* A, float* X, int* failed, void* stream) {
@@ -1287,6 +1331,8 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     const auto& rec = t->states;
     if (!rec.Q != !rec.V) return fail(t, NMPC_E_ARG, "states: Q and V come together or not at all");
     if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
+    const auto& seen = t->observed;
+    if (seen.O && seen.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "observed: o_rows must be at least n_steps");
     if (const char* why = plant_batch_refusal(t, t->push, t->windows, B)) return fail(t, NMPC_E_ARG, why);
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
@@ -1300,11 +1346,19 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     for (int k = 0; k <= K; ++k) {
         const double at = cfg->t0 + (double)(k * cfg->n_sub) * (double)cfg->dt;
         const bool rows = k < K;
+        // with O attached and no S, the observation writes the true row into O's row, which is then perturbed in place
+        float* const o_row = rows && seen.O ? seen.O + (size_t)k * OB_STATE : nullptr;
+        float* const s_row = rows && S ? S + (size_t)k * OB_STATE : o_row;
+        const int s_stride = (S || !seen.O) ? K * OB_STATE : seen.rows * OB_STATE;
+        const long long noise_step = t->noise.step;      // the step this observation draws X at, read before it moves on
         if (const int rc = nmpc_observe_batch(t, B, q, v, at, cfg->period, goal, cfg->n_goal, s_mean, s_std, cfg->s_first, cfg->collision_height,
-                                              rows && S ? S + (size_t)k * OB_STATE : nullptr, K * OB_STATE, rows ? X : nullptr, failed, k,
-                                              cfg->term_mask, stream))
+                                              s_row, s_stride, rows ? X : nullptr, failed, k, cfg->term_mask, stream))
             return rc;
         if (!rows) break;
+        if (o_row) {                    // what the sensors showed in control step k: the draw of this step's X on the true row
+            NMPC_ENTER(t, t->device);
+            if (const int rc = launch_observed_rows(t, B, s_row, s_stride, o_row, seen.rows * OB_STATE, noise_step, stream)) return rc;
+        }
         if (rec.Q) {                    // the state before control step k, beside row k of S and A
             NMPC_ENTER(t, t->device);
             const size_t n = (size_t)B * t->host.n;

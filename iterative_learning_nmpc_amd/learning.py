@@ -31,18 +31,26 @@ from ._lib import NMPC_ROLLOUT_TERM_SHIFT, NMPC_STATUS_NAN, NMPC_STATUS_QP
 from .collect import collect_rollouts
 from .mpc import push_windows
 from .config import TERMINATE_DEFAULT
-from .torque import NOMINAL_PERIOD, GroundContact, integrator_mode
+from .torque import N_STATE, NOMINAL_PERIOD, GroundContact, integrator_mode
 from .trajectory_io import KD, KP
 
 
 def train_network(policy, db, n_epoch: int, batch_size: int, lr: float = 1e-3, seed: int = 0,
-                  val_idx: Optional[torch.Tensor] = None):
+                  val_idx: Optional[torch.Tensor] = None, input_noise=None, input_noise_seed: int = 0):
     """`n_epoch` epochs of `policy` (a `DevicePolicy`) on `db` (a `DeviceDatabase`), rows drawn by `db.weights`.
 
     Epoch e is `policy.train_epoch` with seed `seed + e` over ceil(n_train / batch_size) batches, followed by the
     validation loss on the rows `val_idx` (distinct physical ring positions, int32 or int64, host or device), which are
     assembled once with `db.batch` and never trained on.  Returns (train_loss [n_epoch, n_batches], val_loss [n_epoch])
-    on the device; without validation rows val_loss is NaN."""
+    on the device; without validation rows val_loss is NaN.
+    input_noise: a vector sigma [n <= 44] in the units of the raw state columns (`torque.training_sigma` makes one of a table of
+    sensor noise), attached for this call (`DevicePolicy.set_input_noise`) with the key `input_noise_seed` and epoch0 = 0, so
+    that epoch e of the call perturbs its batches with the draws of epoch e; the validation loss stays on clean rows.  It is
+    detached when the call ends, also by an exception.  None: the batches are trained on as they are assembled, unless the
+    policy has a vector of the caller's attached, which then stays, is used and keeps counting its own epoch.  A policy that has
+    one attached while `input_noise` is given is refused with ValueError, as `evaluate_policy` refuses its tables."""
+    if input_noise is not None and policy._input_noise is not None:
+        raise ValueError("input_noise: the policy has input noise attached already (set_input_noise)")
     n = len(db)
     weights = db.weights[:n].clone()
     n_val = 0
@@ -58,10 +66,16 @@ def train_network(policy, db, n_epoch: int, batch_size: int, lr: float = 1e-3, s
     n_batches = -(-n_train // int(batch_size))
     train_loss = torch.empty(n_epoch, n_batches, dtype=torch.float32, device=db.device)
     val_loss = torch.full((n_epoch,), float("nan"), dtype=torch.float32, device=db.device)
-    for e in range(n_epoch):
-        train_loss[e] = policy.train_epoch(db, batch_size, n_batches, lr, seed + e, weights=weights)
-        if n_val:
-            val_loss[e:e + 1] = policy.loss(x_val, y_val)
+    try:
+        if input_noise is not None:
+            policy.set_input_noise(input_noise, seed=input_noise_seed, epoch0=0)
+        for e in range(n_epoch):
+            train_loss[e] = policy.train_epoch(db, batch_size, n_batches, lr, seed + e, weights=weights)
+            if n_val:
+                val_loss[e:e + 1] = policy.loss(x_val, y_val)
+    finally:
+        if input_noise is not None:
+            policy.set_input_noise(None)
     return train_loss, val_loss
 
 
@@ -69,13 +83,15 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
                        ood_weight: float = 5.0, terminate_mask: int = TERMINATE_DEFAULT, kp: Optional[float] = None,
                        kd: Optional[float] = None, n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0,
                        val_fraction: float = 0.0, plant=None, plant_substeps: int = 2, push_as_force: bool = False,
-                       integrator: Optional[str] = None, chunk_replans: Optional[int] = None):
+                       integrator: Optional[str] = None, chunk_replans: Optional[int] = None, train_noise=None, train_noise_seed: int = 0):
     """One DAgger iteration, from rollouts to updated parameters: `collect.collect_rollouts` (its arguments up to `kd`, and
     `plant` / `plant_substeps` / `push_as_force` / `integrator`: the expert on the ground-contact plant, pushed by a force, under the named integrator;
     `chunk_replans`: the rollout in stretches of that many replans, each appended before the next runs) appends the valid rollouts and their weights to `db`, then
     `train_network` trains `policy` on all of `db`, validating on its last floor(val_fraction * len(db)) physical rows.  Returns (err, weights, n_rows, train_loss, val_loss): what
     the two parts return.  A table of grounds, of payloads, of actuators or of delays attached on `layer` (`set_grounds`,
-    `set_payloads`, `set_actuators`, `set_delays`) is seen by the plant of the rollouts; there is no keyword for any of them."""
+    `set_payloads`, `set_actuators`, `set_delays`) is seen by the plant of the rollouts; there is no keyword for any of them.
+    train_noise, train_noise_seed: `train_network`'s input_noise and its key -- the expert's rollouts have no sensor, so a cloned
+    policy meets sensor noise only in the batches it is trained on."""
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
     err, weights, n_rows = collect_rollouts(mpc, layer, db, q0, v0, T, push=push, nominal=nominal, ood_weight=ood_weight,
@@ -86,7 +102,8 @@ def learning_iteration(mpc, layer, db, policy, q0, v0, T: float, push: Optional[
         raise ValueError("the database is empty: no rollout of the batch was valid")
     n_val = int(val_fraction * n)
     val_idx = torch.arange(n - n_val, n, dtype=torch.int32, device=db.device) if n_val else None
-    train_loss, val_loss = train_network(policy, db, n_epoch, batch_size, lr=lr, seed=seed, val_idx=val_idx)
+    train_loss, val_loss = train_network(policy, db, n_epoch, batch_size, lr=lr, seed=seed, val_idx=val_idx, input_noise=train_noise,
+                                         input_noise_seed=train_noise_seed)
     return err, weights, n_rows, train_loss, val_loss
 
 
@@ -94,7 +111,7 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
                     terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False,
                     push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None,
-                    delays=None, noise=None, noise_seed: int = 0):
+                    delays=None, noise=None, noise_seed: int = 0, record_observed: bool = False):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -108,6 +125,9 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
         Q, V            with record_states=True, [B, n_steps, 18]: the plant state before every control step, row k the state
                         row k of S was made of (`BatchedTorqueLayer.set_rollout_states`, attached for this call) -- what
                         `LocomotionMPC.label_states` starts the expert's solves from.
+        O               with record_observed=True, [B, n_steps, 44]: row k the raw state row as the sensors showed it in control
+                        step k -- row k of S under the draw of the noise that the policy's input of that step carried
+                        (`BatchedTorqueLayer.set_rollout_observed`, attached for this call); without noise it is S.
     push: the dict of `mpc.sample_pushes` -- {"start": s, "duration": s, "force": [B, 3] N} -- as a force on the trunk
     (`BatchedTorqueLayer.set_push`, attached for this call): the substeps round(start / dt) <= s < round(start / dt) +
     round(duration / dt) of the rollout are pushed.  None, or a duration that rounds to no substep: the rollout is the bits it
@@ -167,11 +187,17 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     for name, _, attached, _, what in parts:
         if attached is not None:
             raise ValueError(f"{name}: the layer has {what} attached already (set_{name})")
+    if record_observed and layer._observed is not None:
+        raise ValueError("record_observed: the layer has observed rows attached already (set_rollout_observed)")
     states = {}
     if record_states:
         B = torch.as_tensor(q0).reshape(-1, layer.n).shape[0]
         states = {k: torch.empty(B, n_steps, layer.n, dtype=torch.float32, device=layer.device) for k in ("Q", "V")}
         layer.set_rollout_states(states["Q"], states["V"])
+    if record_observed:
+        B = torch.as_tensor(q0).reshape(-1, layer.n).shape[0]
+        states["O"] = torch.empty(B, n_steps, N_STATE, dtype=torch.float32, device=layer.device)
+        layer.set_rollout_observed(states["O"])
     try:
         if integrator is not None:
             layer.set_integrator(integrator)
@@ -188,6 +214,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
             setter(None)
         if record_states:
             layer.set_rollout_states(None)
+        if record_observed:
+            layer.set_rollout_observed(None)
     stamp = failed >> NMPC_ROLLOUT_TERM_SHIFT
     return dict(failed=failed, survived=stamp == 0, steps_survived=torch.where(stamp == 0, torch.full_like(stamp, n_steps), stamp - 1),
                 S=S, A=A, q=q, v=v, **states)
@@ -197,7 +225,7 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
                      kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
                      n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0,
                      push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None,
-                     delays=None, noise=None, noise_seed: int = 0):
+                     delays=None, noise=None, noise_seed: int = 0, store: str = "true", train_noise=None, train_noise_seed: int = 0):
     """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
         1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
            [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
@@ -218,9 +246,14 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     `kp`, `kd` -- `label_states` on the visited states, with or without the table.  delays: a delay per robot for the
     learner's rollout, in the same way: the plant is late, the expert's labels are those of the visited states and know no delay.
     noise, noise_seed: sensor noise per robot for the learner's rollout, in the same way: the learner drives on what its sensors
-    show, the database gets the true rows S and the expert's labels from the true states Q, V -- training on the noisy inputs
-    themselves is not done here.  Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows,
-    train_loss and val_loss added."""
+    show; the expert's labels always come from the true states Q, V.  store: which rows go into the database beside those labels --
+    "true" (the default): the true rows S[b, k]; "observed": O[b, k], the rows the learner's sensors showed
+    (`evaluate_policy(record_observed=True)`, returned as O), with the same choice of rows, so that a policy deployed on noisy
+    inputs is trained on (what it saw, what the expert would do from the true state); any other string is a ValueError before
+    anything runs.  train_noise, train_noise_seed: `train_network`'s input_noise and its key, noise on the batches in training.
+    Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows, train_loss and val_loss added."""
+    if store not in ("true", "observed"):
+        raise ValueError(f"store: expected 'true' or 'observed', got {store!r}")
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
     if integrator is not None:
@@ -229,7 +262,7 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
                           terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push,
                           integrator=integrator, grounds=grounds, payloads=payloads, actuators=actuators, delays=delays,
-                          noise=noise, noise_seed=noise_seed)
+                          noise=noise, noise_seed=noise_seed, record_observed=store == "observed")
     A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
     S = out["S"]
     B, K = S.shape[:2]
@@ -238,11 +271,13 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     n_rows = int(keep.numel())
     if n_rows:
         goals = torch.as_tensor(goal, dtype=torch.float32, device=S.device).reshape(B, -1)
-        db.append(S.reshape(B * K, -1)[keep], A_star.reshape(B * K, -1)[keep], goals.repeat_interleave(K, dim=0)[keep])
+        rows = out["O"] if store == "observed" else S     # what the learner saw, or the true rows; the labels are those of the true states
+        db.append(rows.reshape(B * K, -1)[keep], A_star.reshape(B * K, -1)[keep], goals.repeat_interleave(K, dim=0)[keep])
     n = len(db)
     if n == 0:
         raise ValueError("the database is empty: no visited state of the batch got a label")
     n_val = int(val_fraction * n)
     val_idx = torch.arange(n - n_val, n, dtype=torch.int32, device=db.device) if n_val else None
-    train_loss, val_loss = train_network(policy, db, n_epoch, batch_size, lr=lr, seed=seed, val_idx=val_idx)
+    train_loss, val_loss = train_network(policy, db, n_epoch, batch_size, lr=lr, seed=seed, val_idx=val_idx, input_noise=train_noise,
+                                         input_noise_seed=train_noise_seed)
     return dict(out, A_star=A_star, status=status, n_rows=n_rows, train_loss=train_loss, val_loss=val_loss)

@@ -54,6 +54,7 @@ class DevicePolicy:
         self.items, self.n_theta = parameter_layout(*self.dims)
         assert self.n_theta == self.lib.nmpc_policy_param_count(self._h)
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._input_noise = None        # set_input_noise: the attached sigma
         if seed is not None:
             self.init_weight(seed)
 
@@ -184,6 +185,75 @@ class DevicePolicy:
                                                     int(seed) & (2 ** 64 - 1), float(lr), ptr(scratch), ptr(losses), ptr(idx),
                                                     stream(self.device)), self._h, "nmpc_policy_train_epoch", "policy")
         return (losses, idx) if return_idx else losses
+
+    def set_input_noise(self, sigma=None, seed: int = 0, epoch0: int = 0):
+        """nmpc_policy_set_input_noise: noise on the input columns of the batches `train_epoch` trains on, so that a policy
+        deployed behind noisy sensors (`BatchedTorqueLayer.set_noise`) is trained on inputs like the ones it will see.  sigma: a
+        float array or tensor [n], 1 <= n <= n_in, finite and not negative, in the units of the RAW input columns 0 .. n-1
+        (`torque.training_sigma` makes one of a sensor table).  While attached every `train_epoch` adds sigma[j] g to column j of
+        each staged batch by one more launch per batch -- divided by the column's states_std where the database normalises it --
+        g the variate of the sensor rule at counter (t * batch_size + i, epoch, j, 1) for row i of batch t, and then moves the
+        policy's noise epoch (`input_noise_epoch`) on by one; a column with sigma 0 is not written.  `train_step`, `forward` and
+        `loss` never draw: validation stays on clean rows.  seed: 64 bits; epoch0: the epoch of the next `train_epoch`.
+        Host input is validated (ValueError) and uploaded; the policy keeps the vector alive while it is attached.
+        `set_input_noise(None)` detaches; detached, every call makes the launches and gives the bits it gives without."""
+        if sigma is None:
+            self._input_noise = None
+            _lib.check(self.lib.nmpc_policy_set_input_noise(self._h, None, 0, 0, 0), self._h, "nmpc_policy_set_input_noise", "policy")
+            return
+        try:
+            host = sigma.detach().cpu().numpy() if isinstance(sigma, torch.Tensor) else sigma
+            host = np.asarray(host, dtype=np.float32)
+        except (TypeError, ValueError) as e:
+            raise ValueError("input noise: sigma: need a float array [n]") from e
+        if host.ndim != 1 or not 1 <= host.shape[0] <= self.dims[0]:
+            raise ValueError(f"input noise: sigma: expected [n] with 1 <= n <= {self.dims[0]}, got {tuple(host.shape)}")
+        if not np.isfinite(host).all():
+            raise ValueError("input noise: sigma must be finite")
+        if not (host >= 0.0).all():
+            raise ValueError("input noise: sigma must not be negative")
+        epoch0 = int(epoch0)
+        if not 0 <= epoch0 < 2 ** 63:
+            raise ValueError("input noise: epoch0 must be in [0, 2^63)")
+        key = int(seed) & (2 ** 64 - 1)                   # the 64 bits of the key, as the signed argument that carries them
+        dev = torch.tensor(host, device=self.device)
+        _lib.check(self.lib.nmpc_policy_set_input_noise(self._h, ptr(dev), dev.shape[0], key - 2 ** 64 if key >= 2 ** 63 else key, epoch0),
+                   self._h, "nmpc_policy_set_input_noise", "policy")
+        self._input_noise = dev
+
+    @property
+    def input_noise_epoch(self) -> Optional[int]:
+        """nmpc_policy_input_noise_epoch: the epoch the next `train_epoch` draws its input noise at, or None with nothing attached"""
+        if self._input_noise is None:
+            return None
+        epoch = ctypes.c_longlong()
+        _lib.check(self.lib.nmpc_policy_input_noise_epoch(self._h, ctypes.byref(epoch)), self._h, "nmpc_policy_input_noise_epoch", "policy")
+        return epoch.value
+
+    def input_noise(self, X: torch.Tensor, epoch: int, first_sample: int = 0, s_std=None, s_first: int = 1) -> torch.Tensor:
+        """nmpc_policy_input_noise_batch: the attached input noise on the first n columns of X, a float32 [B, >= n] tensor on the
+        policy's device with dense rows (a slice [:, :k] of a wider contiguous tensor is taken with its stride), IN PLACE, row i
+        as sample first_sample + i of `epoch`; the policy's own epoch is neither read nor moved.  s_std: float64 [>= n], the
+        statistics X was normalised with from column s_first on (None: X is raw).  What `train_epoch` does to batch t with
+        first_sample = t * batch_size while the vector is attached.  -> X."""
+        if not isinstance(X, torch.Tensor) or X.dtype != torch.float32 or X.dim() != 2 or X.device != self.device \
+                or (X.shape[0] > 0 and X.stride(1) != 1) or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
+            raise ValueError(f"X: need a float32 [B, columns] tensor with dense rows on {self.device}")
+        n = 0 if self._input_noise is None else self._input_noise.shape[0]
+        if X.shape[1] < n:
+            raise ValueError(f"X: need at least the {n} columns of the attached sigma, got {X.shape[1]}")
+        if s_std is not None:
+            s_std = torch.as_tensor(s_std, dtype=torch.float64, device=self.device).contiguous()
+            if s_std.dim() != 1 or s_std.shape[0] < n:
+                raise ValueError(f"s_std: expected [>= {n}]")
+        epoch, first_sample = int(epoch), int(first_sample)
+        if not (0 <= epoch < 2 ** 63 and 0 <= first_sample < 2 ** 63):
+            raise ValueError("input noise: epoch and first_sample must be in [0, 2^63)")
+        x_stride = X.stride(0) if X.shape[0] > 1 else X.shape[1]
+        _lib.check(self.lib.nmpc_policy_input_noise_batch(self._h, X.shape[0], ptr(X), x_stride, ptr(s_std), int(s_first), epoch,
+                                                          first_sample, stream(self.device)),
+                   self._h, "nmpc_policy_input_noise_batch", "policy")
+        return X
 
     def loss(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """network.eval(); L1Loss(network(x), y) as a device scalar, for any number of rows (the validation loss of

@@ -327,6 +327,17 @@ def sample_noise(n: int, seed: int, sigma=None, bias=None) -> np.ndarray:
     return _noise_rows(rows)
 
 
+def training_sigma(noise) -> np.ndarray:
+    """The input noise a memoryless learner is trained with under a table of sensor noise: float32 [44] for
+    `DevicePolicy.set_input_noise` / `learning.train_network(input_noise=...)` from a table [B, 88] as `set_noise` takes it
+    (`noise_table`, `sample_noise`).  Per slot the root mean square over the robots of sqrt(sigma^2 + bias^2) [decl]: a policy
+    without memory cannot tell a robot's constant bias from noise, so over the population the bias enters as variance -- the one
+    declared way a per-robot bias enters the training noise; a persistent bias per episode is not drawn in training."""
+    rows = _noise_rows(noise).astype(np.float64)
+    sigma, bias = rows[:, :N_STATE], rows[:, N_STATE:]
+    return np.sqrt((sigma ** 2 + bias ** 2).mean(axis=0)).astype(np.float32)
+
+
 class BatchedTorqueLayer:
     def __init__(self, parent: Sequence[int], joint_type: Sequence[int], axis, placement_R, placement_p, mass, com, inertia,
                  foot_joint: Sequence[int], foot_offset, n_actuated: int, gravity=(0.0, 0.0, -9.81), device="cuda:0"):
@@ -361,6 +372,7 @@ class BatchedTorqueLayer:
         self._actuators = None          # set_actuators: the attached table
         self._delays = None             # set_delays: the attached table with its register and scratch
         self._noise = None              # set_noise: the attached table
+        self._observed = None           # set_rollout_observed: the attached rows O
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -590,7 +602,7 @@ class BatchedTorqueLayer:
         (failed >> 8 = 1 + the control step whose observation saw it) and keeps being stepped.
         The contact steps are those of the layer's integrator (`set_integrator`).  With a table of noise attached (`set_noise`)
         the policy acts on the perturbed input of each of its n_steps observations and `noise_step` moves on by n_steps; S holds
-        the true rows.
+        the true rows, and the rows the sensors showed go to the tensor of `set_rollout_observed` if one is attached.
         -> (q, v, S [B, n_steps, 44], A [B, n_steps, 12], failed int32 [B]); S and A are None with record=False."""
         q = self._in(q, (self.n,), "q").clone(); v = self._in(v, (self.n,), "v").clone()
         tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff")
@@ -610,6 +622,9 @@ class BatchedTorqueLayer:
         states = self._states
         if states is not None and (states[0].shape[0] != B or states[0].shape[1] < n_steps):      # the attached tables must be this rollout's size
             raise ValueError(f"Q, V (set_rollout_states): need [{B}, >= {n_steps}, {self.n}], got {tuple(states[0].shape)}")
+        seen = self._observed
+        if seen is not None and (seen.shape[0] != B or seen.shape[1] < n_steps):
+            raise ValueError(f"O (set_rollout_observed): need [{B}, >= {n_steps}, {N_STATE}], got {tuple(seen.shape)}")
         rows = max(n_steps, 0)
         S = torch.empty(B, rows, N_STATE, dtype=torch.float32, device=self.device) if record else None
         A = torch.empty(B, rows, self.nu, dtype=torch.float32, device=self.device) if record else None
@@ -656,6 +671,47 @@ class BatchedTorqueLayer:
             raise ValueError("Q, V: need the same rows and one layout")
         self._states = (Q, V)
         _lib.check(self.lib.nmpc_policy_rollout_set_states(self._h, ptr(Q), ptr(V), qv_rows), self._h, "nmpc_policy_rollout_set_states", "torque")
+
+    def set_rollout_observed(self, O: Optional[torch.Tensor] = None):
+        """nmpc_policy_rollout_set_observed: while O [B, rows, 44] (rows >= n_steps; a slice [:, :k] of a longer table is taken
+        with its stride) is attached, every `policy_rollout` of this layer writes into row k the raw 44-slot state row as the
+        sensors of robot b showed it in control step k -- `observed_rows` of row k of S at the noise step that step's policy
+        input was drawn at, by one more launch per control step; with no table of noise attached that is S itself.  Every other
+        output of the rollout, and `noise_step`, is the same bits.  `set_rollout_observed(None)` detaches.  The layer keeps O alive
+        while it is attached; a rollout of another batch size than O's is refused."""
+        if O is None:
+            self._observed = None
+            _lib.check(self.lib.nmpc_policy_rollout_set_observed(self._h, None, 0), self._h, "nmpc_policy_rollout_set_observed", "torque")
+            return
+        if not isinstance(O, torch.Tensor) or O.dim() != 3:
+            raise ValueError(f"O: need a float32 [B, rows, {N_STATE}] tensor")
+        O, o_rows = self._rows(O, N_STATE, "O", O.shape[0])
+        self._observed = O
+        _lib.check(self.lib.nmpc_policy_rollout_set_observed(self._h, ptr(O), o_rows), self._h, "nmpc_policy_rollout_set_observed", "torque")
+
+    def observed_rows(self, S: torch.Tensor, step: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """nmpc_observed_rows_batch: the raw state rows S, float32 [B, >= 44] on the layer's device with dense rows, as the sensors
+        of the attached table of noise (`set_noise`) show them at noise step `step`: slot j of robot b is float32(S + bias + sigma
+        g) with the draw `observe` puts on the policy input at that step, and the bits of S where sigma and bias are zero or no
+        table is attached.  The layer's own noise step is neither read nor moved.  out: float32 [B, >= 44] with dense rows to
+        write the first 44 columns of (None: a new [B, 44] tensor; S itself: in place).  -> out."""
+        def dense(t, name):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < N_STATE or t.device != self.device \
+                    or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+                raise ValueError(f"{name}: need a float32 [B, >= {N_STATE}] tensor with dense rows on {self.device}")
+            return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+        s_stride = dense(S, "S")
+        if out is None:
+            out = torch.empty(S.shape[0], N_STATE, dtype=torch.float32, device=self.device)
+        o_stride = dense(out, "out")
+        if out.shape[0] != S.shape[0]:
+            raise ValueError("out: need as many rows as S")
+        step = int(step)
+        if not 0 <= step < 2 ** 63:
+            raise ValueError("observed: step must be in [0, 2^63)")
+        _lib.check(self.lib.nmpc_observed_rows_batch(self._h, S.shape[0], ptr(S), s_stride, ptr(out), o_stride, step, stream(self.device)),
+                   self._h, "nmpc_observed_rows_batch", "torque")
+        return out
 
     def set_push(self, force: Optional[torch.Tensor] = None, start_substep=0, n_substeps=0, joint: int = 5):
         """nmpc_contact_set_push: while force [B, 3] (N, world frame, no moment) is attached, robot b of every `contact_step`,
