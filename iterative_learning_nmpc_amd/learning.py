@@ -23,6 +23,7 @@ Declared choices:
     append (on a ring that has not wrapped: the newest rows)."""
 from __future__ import annotations
 
+from functools import partial
 from typing import Optional
 
 import torch
@@ -31,7 +32,7 @@ from ._lib import NMPC_ROLLOUT_TERM_SHIFT, NMPC_STATUS_NAN, NMPC_STATUS_QP
 from .collect import collect_rollouts
 from .mpc import push_windows
 from .config import TERMINATE_DEFAULT
-from .torque import N_STATE, NOMINAL_PERIOD, GroundContact, integrator_mode
+from .torque import N_STATE, NOMINAL_PERIOD, TABLES, GroundContact, integrator_mode
 from .trajectory_io import KD, KP
 
 
@@ -177,13 +178,12 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
             layer.set_push(force, start_substep=first, n_substeps=count)
 
     # what this call attaches to the layer and takes off again: (name, value, what the layer has attached, setter, in words)
-    parts = [part for part in (("push", push, layer._push, set_push, "a push"),
-                               ("grounds", grounds, layer._grounds, layer.set_grounds, "a table of grounds"),
-                               ("payloads", payloads, layer._payloads, layer.set_payloads, "a table of payloads"),
-                               ("actuators", actuators, layer._actuators, layer.set_actuators, "a table of actuators"),
-                               ("delays", delays, layer._delays, layer.set_delays, "a table of delays"),
-                               ("noise", noise, layer._noise, lambda table: layer.set_noise(table, seed=noise_seed), "a table of noise"))
-             if part[1] is not None]
+    given = dict(grounds=grounds, payloads=payloads, actuators=actuators, delays=delays, noise=noise)      # the keywords are explicit: one entry per name of TABLES
+    keywords = dict(noise=dict(seed=noise_seed))
+    parts = [("push", push, layer._push, set_push, "a push")]
+    parts += [(name, given[name], getattr(layer, "_" + name), partial(getattr(layer, "set_" + name), **keywords.get(name, {})), "a table of " + name)
+              for name in TABLES]
+    parts = [part for part in parts if part[1] is not None]
     for name, _, attached, _, what in parts:
         if attached is not None:
             raise ValueError(f"{name}: the layer has {what} attached already (set_{name})")

@@ -50,6 +50,44 @@ class GroundContact:
                                    float(self.slip_velocity), 0.0 if self.tau_max is None else float(self.tau_max))
 
 
+TABLES = ("grounds", "payloads", "actuators", "delays", "noise")      # per name: layer._<name> is what is attached or None, layer.set_<name>(None) detaches
+
+
+def _draw(rng, n: int, name: str, r) -> np.ndarray:
+    """n uniform draws of rng from the range r = (lo, hi) of column `name`, rounded to float32 and held to the float32 values
+    inside [lo, hi]: one rng.uniform(lo, hi, n)"""
+    lo, hi = (float(x) for x in r)
+    if not lo <= hi:
+        raise ValueError(f"{name}: need a range (lo, hi) with lo <= hi, got {r!r}")
+    lo32, hi32 = np.float32(lo), np.float32(hi)
+    if lo32 < lo:
+        lo32 = np.nextafter(lo32, np.float32(np.inf))
+    if hi32 > hi:
+        hi32 = np.nextafter(hi32, np.float32(-np.inf))
+    if lo32 > hi32:
+        raise ValueError(f"{name}: the range {r!r} holds no float32 value")
+    return np.clip(rng.uniform(lo, hi, n).astype(np.float32), lo32, hi32)
+
+
+def _float_table(name: str, table, width: int, B: int, rules, need=None, expected=None, one_for_all: bool = False) -> np.ndarray:
+    """`table` as contiguous float32 rows [>= B, width] (one_for_all: a single row [width] stands for B of them), or the ValueError
+    of the table `name`: `need` where it is no float array, `expected` where its shape is wrong, and the first of `rules`
+    -- (message, rows -> mask of the rows that break it) -- that a row breaks, with the first such row"""
+    try:
+        rows = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{name}: need {need or f'a float array [B, {width}]'}") from e
+    if one_for_all and rows.shape == (width,):
+        rows = np.broadcast_to(rows, (B, width))
+    if rows.ndim != 2 or rows.shape[1] != width or rows.shape[0] < B:
+        raise ValueError(f"{name}: expected {expected or f'[>= {B}, {width}]'}, got {tuple(rows.shape)}")
+    for why, broken in rules:
+        bad = broken(rows)
+        if bad.any():
+            raise ValueError(f"{name}: row {int(np.argmax(bad))}: {why}")
+    return rows
+
+
 GROUND_COLUMNS = ("ground_z", "stiffness", "damping", "mu", "slip_velocity", "tau_max")      # a row of a table of grounds: nmpc_contact_cfg's fields
 
 
@@ -60,19 +98,12 @@ def ground_table(grounds) -> np.ndarray:
     slip_velocity positive; a violation, a wrong shape or an empty table is a ValueError naming the first offending row."""
     if isinstance(grounds, (list, tuple)) and grounds and all(isinstance(g, GroundContact) for g in grounds):
         grounds = [[g.ground_z, g.stiffness, g.damping, g.mu, g.slip_velocity, 0.0 if g.tau_max is None else g.tau_max] for g in grounds]
-    try:
-        rows = np.ascontiguousarray(np.asarray(grounds, dtype=np.float32))
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"grounds: need a sequence of GroundContact or a float array [B, {len(GROUND_COLUMNS)}]") from e
-    if rows.ndim != 2 or rows.shape[1] != len(GROUND_COLUMNS) or rows.shape[0] < 1:
-        raise ValueError(f"grounds: expected [B, {len(GROUND_COLUMNS)}] with B >= 1, got {tuple(rows.shape)}")
-    checks = (("the contact parameters must be finite", ~np.isfinite(rows).all(axis=1)),
-              ("stiffness, damping and mu must not be negative", (rows[:, 1:4] < 0.0).any(axis=1)),
-              ("slip_velocity must be positive", ~(rows[:, 4] > 0.0)))
-    for why, bad in checks:
-        if bad.any():
-            raise ValueError(f"grounds: row {int(np.argmax(bad))}: {why}")
-    return rows
+    w = len(GROUND_COLUMNS)
+    rules = (("the contact parameters must be finite", lambda r: ~np.isfinite(r).all(axis=1)),
+             ("stiffness, damping and mu must not be negative", lambda r: (r[:, 1:4] < 0.0).any(axis=1)),
+             ("slip_velocity must be positive", lambda r: ~(r[:, 4] > 0.0)))
+    return _float_table("grounds", grounds, w, 1, rules, need=f"a sequence of GroundContact or a float array [B, {w}]",
+                        expected=f"[B, {w}] with B >= 1")
 
 
 def sample_grounds(B: int, rng, base: GroundContact = GroundContact(), mu=None, stiffness=None, damping=None, ground_z=None,
@@ -87,20 +118,8 @@ def sample_grounds(B: int, rng, base: GroundContact = GroundContact(), mu=None, 
     rows = np.repeat(ground_table([base]), B, axis=0)
     ranges = dict(ground_z=ground_z, stiffness=stiffness, damping=damping, mu=mu, tau_max=tau_max)
     for col, name in enumerate(GROUND_COLUMNS):
-        r = ranges.get(name)
-        if r is None:
-            continue
-        lo, hi = (float(x) for x in r)
-        if not lo <= hi:
-            raise ValueError(f"{name}: need a range (lo, hi) with lo <= hi, got {r!r}")
-        lo32, hi32 = np.float32(lo), np.float32(hi)      # the float32 values inside [lo, hi] that a rounded draw is held to
-        if lo32 < lo:
-            lo32 = np.nextafter(lo32, np.float32(np.inf))
-        if hi32 > hi:
-            hi32 = np.nextafter(hi32, np.float32(-np.inf))
-        if lo32 > hi32:
-            raise ValueError(f"{name}: the range {r!r} holds no float32 value")
-        rows[:, col] = np.clip(rng.uniform(lo, hi, B).astype(np.float32), lo32, hi32)
+        if ranges.get(name) is not None:
+            rows[:, col] = _draw(rng, B, name, ranges[name])
     return ground_table(rows)
 
 
@@ -111,17 +130,8 @@ def payload_table(payloads, B: int = 1) -> np.ndarray:
     """Host input of `BatchedTorqueLayer.set_payloads` as a validated float32 array [>= B, 4] in the order of PAYLOAD_COLUMNS:
     every value finite and the mass not negative; a violation, a wrong shape or fewer than B rows is a ValueError naming the
     first offending row."""
-    try:
-        rows = np.ascontiguousarray(np.asarray(payloads, dtype=np.float32))
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"payloads: need a float array [B, {len(PAYLOAD_COLUMNS)}]") from e
-    B = max(int(B), 1)
-    if rows.ndim != 2 or rows.shape[1] != len(PAYLOAD_COLUMNS) or rows.shape[0] < B:
-        raise ValueError(f"payloads: expected [>= {B}, {len(PAYLOAD_COLUMNS)}], got {tuple(rows.shape)}")
-    for why, bad in (("the payload must be finite", ~np.isfinite(rows).all(axis=1)), ("the mass must not be negative", ~(rows[:, 0] >= 0.0))):
-        if bad.any():
-            raise ValueError(f"payloads: row {int(np.argmax(bad))}: {why}")
-    return rows
+    rules = (("the payload must be finite", lambda r: ~np.isfinite(r).all(axis=1)), ("the mass must not be negative", lambda r: ~(r[:, 0] >= 0.0)))
+    return _float_table("payloads", payloads, len(PAYLOAD_COLUMNS), max(int(B), 1), rules)
 
 
 def sample_payloads(n: int, seed: int, mass=(0.0, 5.0), offset=((-0.1, 0.1), (-0.05, 0.05), (0.0, 0.1))) -> np.ndarray:
@@ -136,17 +146,8 @@ def sample_payloads(n: int, seed: int, mass=(0.0, 5.0), offset=((-0.1, 0.1), (-0
         raise ValueError("need mass = (lo, hi) and offset = ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi))")
     rng = np.random.default_rng(seed)
     rows = np.zeros((n, 4), np.float32)
-    for col, (name, (lo, hi)) in enumerate(zip(PAYLOAD_COLUMNS, ranges)):
-        if not lo <= hi:
-            raise ValueError(f"{name}: need a range (lo, hi) with lo <= hi, got {(lo, hi)!r}")
-        lo32, hi32 = np.float32(lo), np.float32(hi)      # the float32 values inside [lo, hi] that a rounded draw is held to
-        if lo32 < lo:
-            lo32 = np.nextafter(lo32, np.float32(np.inf))
-        if hi32 > hi:
-            hi32 = np.nextafter(hi32, np.float32(-np.inf))
-        if lo32 > hi32:
-            raise ValueError(f"{name}: the range {(lo, hi)!r} holds no float32 value")
-        rows[:, col] = np.clip(rng.uniform(lo, hi, n).astype(np.float32), lo32, hi32)
+    for col, (name, r) in enumerate(zip(PAYLOAD_COLUMNS, ranges)):
+        rows[:, col] = _draw(rng, n, name, r)
     return payload_table(rows, n)
 
 
@@ -157,20 +158,10 @@ def actuator_table(actuators, B: int = 1) -> np.ndarray:
     """Host input of `BatchedTorqueLayer.set_actuators` as a validated float32 array [>= B, 4] in the order of ACTUATOR_COLUMNS:
     every value finite, kp positive, and kd, damping and armature not negative; a violation, a wrong shape or fewer than B rows
     is a ValueError naming the first offending row."""
-    try:
-        rows = np.ascontiguousarray(np.asarray(actuators, dtype=np.float32))
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"actuators: need a float array [B, {len(ACTUATOR_COLUMNS)}]") from e
-    B = max(int(B), 1)
-    if rows.ndim != 2 or rows.shape[1] != len(ACTUATOR_COLUMNS) or rows.shape[0] < B:
-        raise ValueError(f"actuators: expected [>= {B}, {len(ACTUATOR_COLUMNS)}], got {tuple(rows.shape)}")
-    checks = (("the actuator must be finite", ~np.isfinite(rows).all(axis=1)), ("kp must be positive", ~(rows[:, 0] > 0.0)),
-              ("kd must not be negative", ~(rows[:, 1] >= 0.0)), ("damping must not be negative", ~(rows[:, 2] >= 0.0)),
-              ("armature must not be negative", ~(rows[:, 3] >= 0.0)))
-    for why, bad in checks:
-        if bad.any():
-            raise ValueError(f"actuators: row {int(np.argmax(bad))}: {why}")
-    return rows
+    rules = (("the actuator must be finite", lambda r: ~np.isfinite(r).all(axis=1)), ("kp must be positive", lambda r: ~(r[:, 0] > 0.0)),
+             ("kd must not be negative", lambda r: ~(r[:, 1] >= 0.0)), ("damping must not be negative", lambda r: ~(r[:, 2] >= 0.0)),
+             ("armature must not be negative", lambda r: ~(r[:, 3] >= 0.0)))
+    return _float_table("actuators", actuators, len(ACTUATOR_COLUMNS), max(int(B), 1), rules)
 
 
 def sample_actuators(n: int, seed: int, kp=(0.5 * KP, 1.5 * KP), kd=(0.5 * KD, 1.5 * KD), damping=(0.0, 0.2), armature=(0.0, 0.02)) -> np.ndarray:
@@ -186,17 +177,8 @@ def sample_actuators(n: int, seed: int, kp=(0.5 * KP, 1.5 * KP), kd=(0.5 * KD, 1
         raise ValueError("need kp, kd, damping and armature as ranges (lo, hi)")
     rng = np.random.default_rng(seed)
     rows = np.zeros((n, 4), np.float32)
-    for col, (name, (lo, hi)) in enumerate(zip(ACTUATOR_COLUMNS, ranges)):
-        if not lo <= hi:
-            raise ValueError(f"{name}: need a range (lo, hi) with lo <= hi, got {(lo, hi)!r}")
-        lo32, hi32 = np.float32(lo), np.float32(hi)      # the float32 values inside [lo, hi] that a rounded draw is held to
-        if lo32 < lo:
-            lo32 = np.nextafter(lo32, np.float32(np.inf))
-        if hi32 > hi:
-            hi32 = np.nextafter(hi32, np.float32(-np.inf))
-        if lo32 > hi32:
-            raise ValueError(f"{name}: the range {(lo, hi)!r} holds no float32 value")
-        rows[:, col] = np.clip(rng.uniform(lo, hi, n).astype(np.float32), lo32, hi32)
+    for col, (name, r) in enumerate(zip(ACTUATOR_COLUMNS, ranges)):
+        rows[:, col] = _draw(rng, n, name, r)
     rows[0] = (KP, KD, 0.0, 0.0)
     return actuator_table(rows, n)
 
@@ -260,37 +242,19 @@ def noise_table(sigma, bias=None, B: int = 1) -> np.ndarray:
     zeros.  sigma must be finite and not negative, bias finite; a violation, a wrong shape or fewer than B rows is a ValueError
     naming the first offending row."""
     B = max(int(B), 1)
-    halves = []
-    for name, x in (("sigma", sigma), ("bias", np.zeros(N_STATE, np.float32) if bias is None else bias)):
-        try:
-            x = np.asarray(x, dtype=np.float32)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"noise: {name}: need a float array [{N_STATE}] or [B, {N_STATE}]") from e
-        if x.ndim == 1 and x.shape[0] == N_STATE:
-            x = np.broadcast_to(x, (B, N_STATE))
-        if x.ndim != 2 or x.shape[1] != N_STATE or x.shape[0] < B:
-            raise ValueError(f"noise: {name}: expected [{N_STATE}] or [>= {B}, {N_STATE}], got {tuple(x.shape)}")
-        halves.append(x)
-    sigma, bias = halves
-    if sigma.shape[0] != bias.shape[0]:
-        n = min(sigma.shape[0], bias.shape[0])            # one was broadcast to B, the other given longer
-        sigma, bias = sigma[:n], bias[:n]
-    for why, bad in (("sigma must be finite", ~np.isfinite(sigma).all(axis=1)), ("sigma must not be negative", ~(sigma >= 0.0).all(axis=1)),
-                     ("bias must be finite", ~np.isfinite(bias).all(axis=1))):
-        if bad.any():
-            raise ValueError(f"noise: row {int(np.argmax(bad))}: {why}")
-    return np.ascontiguousarray(np.concatenate([sigma, bias], axis=1))
+    sigma, bias = (_float_table(f"noise: {name}", x, N_STATE, B, (), need=f"a float array [{N_STATE}] or [B, {N_STATE}]",
+                                expected=f"[{N_STATE}] or [>= {B}, {N_STATE}]", one_for_all=True)
+                   for name, x in (("sigma", sigma), ("bias", np.zeros(N_STATE, np.float32) if bias is None else bias)))
+    n = min(sigma.shape[0], bias.shape[0])                # one may have been broadcast to B, the other given longer
+    return _noise_rows(np.concatenate([sigma[:n], bias[:n]], axis=1))
 
 
 def _noise_rows(table) -> np.ndarray:
-    """a host table [B, 88] as `set_noise` is given it, through the validation of `noise_table`"""
-    try:
-        rows = np.asarray(table, dtype=np.float32)
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"noise: need a float array [B, {2 * N_STATE}]") from e
-    if rows.ndim != 2 or rows.shape[1] != 2 * N_STATE or rows.shape[0] < 1:
-        raise ValueError(f"noise: expected [>= 1, {2 * N_STATE}], got {tuple(rows.shape)}")
-    return noise_table(rows[:, :N_STATE], rows[:, N_STATE:], rows.shape[0])
+    """a host table [B, 88] as `set_noise` is given it, through the rules of `noise_table`"""
+    rules = (("sigma must be finite", lambda r: ~np.isfinite(r[:, :N_STATE]).all(axis=1)),
+             ("sigma must not be negative", lambda r: ~(r[:, :N_STATE] >= 0.0).all(axis=1)),
+             ("bias must be finite", lambda r: ~np.isfinite(r[:, N_STATE:]).all(axis=1)))
+    return _float_table("noise", table, 2 * N_STATE, 1, rules)
 
 
 def sample_noise(n: int, seed: int, sigma=None, bias=None) -> np.ndarray:
@@ -781,23 +745,33 @@ class BatchedTorqueLayer:
         the caller's -- and in either case the layer keeps the table alive while it is attached.  `set_grounds(None)`
         detaches; detached, every call makes the launches and gives the bits it gives without."""
         if grounds is None:
-            self._grounds = None
-            _lib.check(self.lib.nmpc_contact_set_grounds(self._h, None, 0), self._h, "nmpc_contact_set_grounds", "torque")
-            return
-        rows = self._table(grounds, "grounds", GROUND_COLUMNS, ground_table)
-        _lib.check(self.lib.nmpc_contact_set_grounds(self._h, ptr(rows), rows.shape[0]), self._h, "nmpc_contact_set_grounds", "torque")
-        self._grounds = rows
+            return self._detach("grounds", None, 0)
+        rows = self._table(grounds, "grounds", (len(GROUND_COLUMNS),), ground_table)
+        self._attach("grounds", rows, ptr(rows), rows.shape[0])
 
-    def _table(self, table, name, columns, validate):
-        """the rows of a table per robot on the device: a device tensor is checked against `columns` and taken as given, host
-        input goes through `validate` and is uploaded; the caller keeps the rows alive while they are attached"""
+    def _table(self, table, name, shape, validate, dtype=torch.float32):
+        """the rows of a table per robot on the device: a device tensor is checked to be `dtype` [B, *shape] and taken as given,
+        host input goes through `validate` and is uploaded"""
         if isinstance(table, torch.Tensor) and table.is_cuda:
-            if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != len(columns) or table.shape[0] < 1 \
+            if table.dtype != dtype or tuple(table.shape[1:]) != shape or table.dim() != 1 + len(shape) or table.shape[0] < 1 \
                     or table.device != self.device:
-                raise ValueError(f"{name}: a device table must be float32 [B, {len(columns)}] with B >= 1 on {self.device}")
+                raise ValueError(f"{name}: a device table must be {str(dtype).split('.')[-1]} [{', '.join(map(str, ('B',) + shape))}] "
+                                 f"with B >= 1 on {self.device}")
             return table.contiguous()
         host = validate(table.numpy() if isinstance(table, torch.Tensor) else table)
         return torch.tensor(host, device=self.device)      # a copy: the caller's array may be read-only
+
+    def _attach(self, name, kept, *args):
+        """nmpc_contact_set_<name>(*args), checked; then `_<name>` is `kept`, which the layer keeps alive while it is attached"""
+        fn = "nmpc_contact_set_" + name
+        _lib.check(getattr(self.lib, fn)(self._h, *args), self._h, fn, "torque")
+        setattr(self, "_" + name, kept)
+
+    def _detach(self, name, *null):
+        """`_<name>` is None, also where the call then fails; then nmpc_contact_set_<name> with its null arguments, checked"""
+        setattr(self, "_" + name, None)
+        fn = "nmpc_contact_set_" + name
+        _lib.check(getattr(self.lib, fn)(self._h, *null), self._h, fn, "torque")
 
     def set_payloads(self, payloads=None, joint: Optional[int] = None):
         """nmpc_contact_set_payloads: a point-mass payload of its own per robot.  payloads: a float array or tensor [B, 4] in the
@@ -813,13 +787,9 @@ class BatchedTorqueLayer:
         given -- the device validates nothing -- and in either case the layer keeps the table alive while it is attached.
         `set_payloads(None)` detaches; detached, every call makes the launches and gives the bits it gives without."""
         if payloads is None:
-            self._payloads = None
-            _lib.check(self.lib.nmpc_contact_set_payloads(self._h, None, 0, 0), self._h, "nmpc_contact_set_payloads", "torque")
-            return
-        rows = self._table(payloads, "payloads", PAYLOAD_COLUMNS, payload_table)
-        joint = self.n - self.nu - 1 if joint is None else int(joint)
-        _lib.check(self.lib.nmpc_contact_set_payloads(self._h, ptr(rows), rows.shape[0], joint), self._h, "nmpc_contact_set_payloads", "torque")
-        self._payloads = rows
+            return self._detach("payloads", None, 0, 0)
+        rows = self._table(payloads, "payloads", (len(PAYLOAD_COLUMNS),), payload_table)
+        self._attach("payloads", rows, ptr(rows), rows.shape[0], self.n - self.nu - 1 if joint is None else int(joint))
 
     def set_actuators(self, actuators=None):
         """nmpc_contact_set_actuators: an actuator of its own per robot.  actuators: a float array or tensor [B, 4] in the order of
@@ -838,12 +808,9 @@ class BatchedTorqueLayer:
         given -- the device validates nothing -- and in either case the layer keeps the table alive while it is attached.
         `set_actuators(None)` detaches; detached, every call makes the launches and gives the bits it gives without."""
         if actuators is None:
-            self._actuators = None
-            _lib.check(self.lib.nmpc_contact_set_actuators(self._h, None, 0), self._h, "nmpc_contact_set_actuators", "torque")
-            return
-        rows = self._table(actuators, "actuators", ACTUATOR_COLUMNS, actuator_table)
-        _lib.check(self.lib.nmpc_contact_set_actuators(self._h, ptr(rows), rows.shape[0]), self._h, "nmpc_contact_set_actuators", "torque")
-        self._actuators = rows
+            return self._detach("actuators", None, 0)
+        rows = self._table(actuators, "actuators", (len(ACTUATOR_COLUMNS),), actuator_table)
+        self._attach("actuators", rows, ptr(rows), rows.shape[0])
 
     def set_delays(self, delays=None, depth: Optional[int] = None, work_rows: int = 64):
         """nmpc_contact_set_delays: an actuation delay of its own per robot.  delays: an integer array or tensor [B], the control
@@ -865,15 +832,8 @@ class BatchedTorqueLayer:
         as given -- the device clamps it into [0, depth] and validates nothing else.  `set_delays(None)` detaches and drops the
         register; detached, every call makes the launches and gives the bits it gives without."""
         if delays is None:
-            self._delays = None
-            _lib.check(self.lib.nmpc_contact_set_delays(self._h, None, None, 0, None, 0, 0), self._h, "nmpc_contact_set_delays", "torque")
-            return
-        if isinstance(delays, torch.Tensor) and delays.is_cuda:
-            if delays.dtype != torch.int32 or delays.dim() != 1 or delays.shape[0] < 1 or delays.device != self.device:
-                raise ValueError(f"delays: a device table must be int32 [B] with B >= 1 on {self.device}")
-            rows = delays.contiguous()
-        else:
-            rows = torch.tensor(delay_table(delays.numpy() if isinstance(delays, torch.Tensor) else delays), device=self.device)
+            return self._detach("delays", None, None, 0, None, 0, 0)
+        rows = self._table(delays, "delays", (), delay_table, dtype=torch.int32)
         if depth is None:
             depth = min(max(1, int(rows.max())), DELAY_MAX_DEPTH)
         depth, work_rows = int(depth), int(work_rows)
@@ -883,9 +843,8 @@ class BatchedTorqueLayer:
             raise ValueError(f"delays: work_rows must be at least 1, got {work_rows}")
         history = torch.zeros(rows.shape[0], depth, self.nu, dtype=torch.float32, device=self.device)
         work = torch.empty(rows.shape[0], work_rows, self.nu, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.nmpc_contact_set_delays(self._h, ptr(rows), ptr(history), depth, ptr(work), work_rows, rows.shape[0]),
-                   self._h, "nmpc_contact_set_delays", "torque")
-        self._delays = SimpleNamespace(rows=rows, history=history, work=work, depth=depth, work_rows=work_rows)
+        self._attach("delays", SimpleNamespace(rows=rows, history=history, work=work, depth=depth, work_rows=work_rows),
+                     ptr(rows), ptr(history), depth, ptr(work), work_rows, rows.shape[0])
 
     @property
     def delay_history(self) -> Optional[torch.Tensor]:
@@ -941,17 +900,13 @@ class BatchedTorqueLayer:
         as given -- the device validates nothing -- and in either case the layer keeps the table alive while it is attached.
         `set_noise(None)` detaches; detached, every call makes the launches and gives the bits it gives without."""
         if noise is None:
-            self._noise = None
-            _lib.check(self.lib.nmpc_contact_set_noise(self._h, None, 0, 0, 0, 0), self._h, "nmpc_contact_set_noise", "torque")
-            return
-        rows = self._table(noise, "noise", range(2 * N_STATE), _noise_rows)
+            return self._detach("noise", None, 0, 0, 0, 0)
+        rows = self._table(noise, "noise", (2 * N_STATE,), _noise_rows)
         first_robot, step0 = int(first_robot), int(step0)
         if not (0 <= first_robot < 2 ** 63 and 0 <= step0 < 2 ** 63):
             raise ValueError("noise: first_robot and step0 must be in [0, 2^63)")
         key = int(seed) & (2 ** 64 - 1)                   # the 64 bits of the key, as the signed argument that carries them
-        _lib.check(self.lib.nmpc_contact_set_noise(self._h, ptr(rows), rows.shape[0], key - 2 ** 64 if key >= 2 ** 63 else key, first_robot, step0),
-                   self._h, "nmpc_contact_set_noise", "torque")
-        self._noise = rows
+        self._attach("noise", rows, ptr(rows), rows.shape[0], key - 2 ** 64 if key >= 2 ** 63 else key, first_robot, step0)
 
     @property
     def noise_step(self) -> Optional[int]:

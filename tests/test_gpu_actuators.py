@@ -23,37 +23,16 @@ from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import payload_reference as plr
 from tests import plant_helpers as ph
-from tests.plant_helpers import AT, DT, DT_IMPLICIT, HEIGHT, INTEGRATORS, KD, KP, MASK, N_SUB, NAMES, ONE, PERIOD, STEP_SUB, T0, TRACK_NAMES
-from tests.plant_helpers import World, chain_of_public_calls, default_policy, expert, held_row_by_row, plant_rollout, quadruped_layer, standing_start  # noqa: F401
+from tests.plant_helpers import ACTUATOR_UPPER as UPPER
+from tests.plant_helpers import AT, DT, DT_IMPLICIT, INTEGRATORS, KD, KP, N_SUB, NAMES, STEP_SUB, TRACK_NAMES, TRUNK
+from tests.plant_helpers import World, default_policy, detached, draw_actuators, draw_payloads, grounds_of, quadruped_layer, start_states, wide_world  # noqa: F401
 from tests.solve_helpers import dev  # noqa: F401
-from tests.test_gpu_payloads import draw_payloads, start_states, wide_world
 from tests.torque_helpers import bar, fractions, host, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-DT32 = float(np.float32(DT))
 B, K = 33, 5                                             # the track: 5 control steps; the policy rollout has the plant's 3
-TRUNK = 5
-UPPER = (1.5 * KP, 1.5 * KD, 0.2, 0.02)
-
-
-def draw_actuators(rng, n):
-    """n distinct rows in the ranges of the module's docstring; the first four are the named ones"""
-    rows = np.stack([rng.uniform(0.5 * KP, 1.5 * KP, n), rng.uniform(0.5 * KD, 1.5 * KD, n), rng.uniform(0.0, 0.2, n), rng.uniform(0.0, 0.02, n)], axis=1)
-    named = [(KP, KD, 0.0, 0.0), UPPER, (KP, KD, 0.0, 0.013), (KP, KD, 0.11, 0.0)]
-    rows[:min(n, 4)] = named[:n]
-    return rows.astype(np.float32)
-
-
-def grounds_of(rows):
-    """the reference `Ground` of every row of a float32 table of grounds (tau_max 0: no limit), from the float32 values themselves"""
-    return [cr.Ground(*(float(x) for x in r[:5]), tau_max=float(r[5]) if r[5] > 0 else None) for r in rows]
-
-
-def detach(L):
-    L.set_actuators(None)
-    ph.detach(L)
 
 
 class Fixture(ph.Fixture):
@@ -130,13 +109,6 @@ def quad_world(fx, n=B, L=None):
 @pytest.fixture(scope="module")
 def world(fx):
     return quad_world(fx)
-
-
-@pytest.fixture()
-def detached(world):
-    """whatever a test attaches or sets on the module's layer is gone after it, also when it fails"""
-    yield
-    detach(world.L)
 
 
 def attach_everything(fx, w, idx=None):
@@ -233,58 +205,19 @@ def worlds(fx, world):
 @pytest.mark.parametrize("shape", ["B1", "B31", "B32", "B33", "tree32 B17"])
 def test_row_b_is_robot_bs_bit_for_bit(fx, worlds, shape, integrator, everything):
     w = worlds[shape]
-    L, n = w.L, w.n
-    dt = DT_IMPLICIT if integrator == "implicit" else DT
-    rows = fx.rows[:n]
-    perm = np.random.default_rng(43).permutation(n)
 
     def attach(rows_, idx):
         if everything:
             attach_everything(fx, w, idx)
-        L.set_actuators(rows_)
+        w.L.set_actuators(rows_)
 
-    def run(world_=w):
-        return world_.step(dt=dt) + world_.track(dt=dt)
-
-    try:
-        L.set_integrator(integrator)
-        everyone = np.arange(n)
-        got, _ = held_row_by_row(run, lambda: attach(rows, everyone), lambda b: attach(np.tile(rows[b], (n, 1)), everyone), sorted({0, n // 2, n - 1}),
-                                 NAMES + (TRACK_NAMES if w.record else TRACK_NAMES[:2]),
-                                 lambda b, o: f"{shape}, {integrator}, robot {b} {o}: largest |table - uniform|")
-        assert all(bool(torch.isfinite(x).all()) for x in got)
-        # a permutation of robots and rows permutes the outputs
-        p = torch.as_tensor(perm, device=L.device)
-        attach(rows[perm], perm)
-        shuffled = run(w.permuted(perm))
-        assert all(same(x[p], y) for x, y in zip(got, shuffled)), shape
-        # spare rows change nothing
-        attach(np.vstack([rows, fx.rows[::-1][:3]]), everyone)
-        longer = run()
-        assert all(same(x, y) for x, y in zip(got, longer)), shape
-        # and the rows matter
-        if n > 1:
-            L.set_actuators(None)
-            assert not all(same(x, y) for x, y in zip(got, run()))
-    finally:
-        detach(L)
+    ph.row_b_is_robot_bs(w, fx.rows[:w.n], fx.rows[::-1][:3], attach, "actuators", integrator, np.random.default_rng(43).permutation(w.n),
+                         lambda b, o: f"{shape}, {integrator}, robot {b} {o}: largest |table - uniform|")
 
 
 @pytest.mark.parametrize("integrator", INTEGRATORS)
 def test_attach_then_detach_gives_the_bits_from_before(fx, world, detached, integrator):
-    L = world.L
-    L.set_integrator(integrator)
-    policy = default_policy()
-    calls = lambda: world.step() + world.track() + rollout(world, policy)      # noqa: E731
-    before = calls()
-    L.set_actuators(fx.rows)
-    assert L._actuators is not None
-    during = calls()
-    L.set_actuators(None)
-    assert L._actuators is None
-    after = calls()
-    assert all(same(x, y) if x.is_floating_point() else torch.equal(x, y) for x, y in zip(before, after))
-    assert not all(same(x, y) for x, y in zip(before[:5], during[:5]))
+    ph.attach_then_detach_gives_the_bits_from_before(world, "actuators", fx.rows, integrator)
 
 
 @pytest.mark.parametrize("integrator", INTEGRATORS)
@@ -303,85 +236,17 @@ def test_the_track_is_the_chain_of_its_steps(fx, world, detached, integrator):
 
 @pytest.mark.parametrize("integrator", INTEGRATORS)
 def test_the_policy_rollout_is_its_chain_of_public_calls(fx, world, detached, integrator):
-    L = world.L
-    policy = default_policy()
-    L.set_integrator(integrator)
-    L.set_actuators(fx.rows)
-    q, v = world.q, world.v
-    failed = torch.zeros(B, dtype=torch.int32, device=L.device)
-    S, A = [], []
-    for k in range(ph.ROLLOUT_STEPS):
-        s, x = L.observe(q, v, T0 + (k * N_SUB) * DT32, PERIOD, world.goal, collision_height=HEIGHT, failed=failed, step_index=k, term_mask=MASK)
-        a = policy.forward(x)
-        q, v = L.contact_step(q, v, DT, N_SUB, tau_ff=world.tau, q_des=a, kp=KP, kd=KD)[:2]
-        S.append(s); A.append(a)
-    L.observe(q, v, T0 + (ph.ROLLOUT_STEPS * N_SUB) * DT32, PERIOD, world.goal, collision_height=HEIGHT, failed=failed, step_index=ph.ROLLOUT_STEPS, term_mask=MASK)
-    got = rollout(world, policy)
-    assert all(same(x, y) for x, y in zip(got[:4], (q, v, torch.stack(S, 1), torch.stack(A, 1)))) and torch.equal(got[4], failed)
-    L.set_actuators(None)
-    assert not same(rollout(world, policy)[0], got[0])                                 # the table matters
+    ph.policy_rollout_is_its_chain_of_public_calls(world, default_policy(), "actuators", fx.rows, integrator)
 
 
 # ---- 4. what it does not touch --------------------------------------------------------------------------------------------------------------
 def test_the_nominal_model_does_not_read_the_table(fx, world, detached, dev):
-    from iterative_learning_nmpc_amd.torque import GroundContact
-    L = world.L
-    a = world.d(np.random.default_rng(3).uniform(-5, 5, (B, 18)).astype(np.float32))
-    f = world.d(np.random.default_rng(4).uniform(-40, 80, (B, 4, 3)).astype(np.float32))
-    tau = world.d(np.random.default_rng(5).uniform(-20, 20, (B, 12)).astype(np.float32))
-    mpc = expert(dev, 2)
-    q0, v0 = standing_start(2)
-    o = plant_rollout(mpc, L, q0, v0, ONE)
-    zoh = mpc.id_repeat[:40]
-    flat = lambda x: torch.cat([y.reshape(B, -1) for y in x], 1) if isinstance(x, (tuple, list)) else x      # noqa: E731
-
-    def nominal():
-        return dict(fd_step=flat(L.step(world.q, world.v, DT, 2, tau_ff=world.tau, q_des=world.q_des, kp=KP, kd=KD, f=f)),
-                    fd_accel=L.forward_dynamics(world.q, world.v, tau, f), id_torques=L.id_torques(world.q, world.v, a, f),
-                    mass_matrix=L.mass_matrix(world.q), centroidal=flat(L.centroidal(world.q, world.v, jacobian=True)),
-                    state_momentum=L.state_momentum(world.q, world.v), contact_forces=L.contact_forces(world.q, world.v, GroundContact()),
-                    pd_target_action=L.pd_target_action(tau, world.q, world.v, kp=KP, kd=KD),
-                    plan_actions=L.plan_actions(o["X"], o["U"], zoh, mpc.config_opt.time_horizon / mpc.config_opt.n_nodes, mpc.sim_dt, kp=mpc.Kp, kd=mpc.Kd))
-
-    without = nominal()
-    bare = world.step()
-    L.set_actuators(fx.rows)
-    driven = nominal()
-    assert not same(world.step()[0], bare[0])             # the table is attached and a plant call takes it
-    for name in without:
-        assert same(without[name], driven[name]), name
-    assert list(without) == ["fd_step", "fd_accel", "id_torques", "mass_matrix", "centroidal", "state_momentum", "contact_forces", "pd_target_action",
-                             "plan_actions"]
+    ph.nominal_model_does_not_read_the_table(world, dev, "actuators", fx.rows)
 
 
 # ---- 5. through the layers ------------------------------------------------------------------------------------------------------------------
 def test_evaluate_policy_attaches_and_detaches_the_table(fx, world, detached):
-    from iterative_learning_nmpc_amd.learning import evaluate_policy
-    L = world.L
-    policy = default_policy()
-    goal = world.goal
-    before = world.step()
-    L.set_actuators(fx.rows)
-    q, v, S, A, failed = rollout(world, policy)
-    L.set_actuators(None)
-    bare = rollout(world, policy)
-    kw = dict(dt=DT, n_sub=N_SUB, tau_ff=world.tau, kp=KP, kd=KD, t0=T0, period=PERIOD, terminate_mask=MASK, collision_height=HEIGHT)
-    out = evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, actuators=fx.rows, **kw)
-    assert same(out["S"], S) and same(out["A"], A) and same(out["q"], q) and same(out["v"], v) and torch.equal(out["failed"], failed)
-    assert not same(out["q"], bare[0])
-    assert L._actuators is None
-    assert all(same(x, y) for x, y in zip(world.step(), before))                       # after the call the layer's step is the un-attached bits
-    assert same(evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, **kw)["q"], bare[0])
-    # also when the rollout raises: a goal of the wrong batch is refused inside the try
-    with pytest.raises(Exception):
-        evaluate_policy(L, policy, None, world.q, world.v, goal[:5], 3 * N_SUB * DT, actuators=fx.rows, **kw)
-    assert L._actuators is None and same(rollout(world, policy)[0], bare[0])
-    # a table of the caller's is not replaced
-    L.set_actuators(fx.rows)
-    mine = L._actuators
-    with pytest.raises(ValueError, match="attached already"):
-        evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, actuators=fx.rows, **kw)
-    assert L._actuators is mine and same(rollout(world, policy)[0], q)
+    ph.evaluate_policy_attaches_and_detaches_the_table(world, default_policy(), "actuators", fx.rows)
 
 
 def test_dagger_iteration_labels_with_the_nominal_gains(fx, dev):
@@ -407,61 +272,21 @@ def test_dagger_iteration_labels_with_the_nominal_gains(fx, dev):
 
 
 def test_the_expert_on_the_plant_meets_the_table_of_its_layer(fx, dev, quadruped_layer):
-    """B = 2, one replan: the plant-mode rollout with a table on its layer is the chain plan labels -> contact_track -> observe_rows
-    under the same table, and not the nominal rollout; the labels are formed with the nominal gains."""
-    L = quadruped_layer
-    rows = fx.rows[1:3].copy()
-    q0, v0 = standing_start(2)
-    try:
-        bare = plant_rollout(expert(dev, 2), L, q0, v0, ONE)
-        L.set_actuators(rows)
-        mpc = expert(dev, 2)
-        o = plant_rollout(mpc, L, q0, v0, ONE)
-        S, A, q, v, failed = chain_of_public_calls(mpc, L, o["X"], o["U"], q0, v0, o["status"])
-    finally:
-        L.set_actuators(None)
-    assert o["S"].shape == (2, 40, 44) and bool(torch.isfinite(o["S"]).all())
-    assert all(same(a, b) for a, b in zip((o["S"], o["A"], o["q"], o["v"]), (S, A, q, v))) and torch.equal(o["failed"], failed)
-    assert same(o["A"], bare["A"])                        # the labels of the first plan are the nominal expert's
-    assert not same(o["q"], bare["q"])                    # the plant answered them with its own drives
+    ph.expert_on_the_plant_meets_the_table_of_its_layer(dev, quadruped_layer, "actuators", fx.rows[1:3].copy())
 
 
 # ---- 6. refusals ----------------------------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_handle_as_it_was(fx, world, detached):
-    from iterative_learning_nmpc_amd import _lib
-    from iterative_learning_nmpc_amd._lib import NmpcError
     from iterative_learning_nmpc_amd.learning import evaluate_policy
     from iterative_learning_nmpc_amd.torque import actuator_table, sample_actuators
-    L, lib = world.L, world.L.lib
-    text = lambda: lib.nmpc_torque_last_error(L._h).decode()                           # noqa: E731
+    L = world.L
     policy = default_policy()
     goal = world.goal
     small = quad_world(fx, 4, L)
     table = world.d(fx.rows[:4])
     L.set_actuators(table)
-    assert L._actuators is table                          # a device tensor is taken as given
-    kept = small.step()
-    # B > n_rows, in every call that reads the table: nothing is launched, the outputs are untouched, what is attached stays
-    for integrator in INTEGRATORS:
-        L.set_integrator(integrator)
-        for call in (world.step, world.track, lambda: rollout(world, policy)):
-            with pytest.raises(NmpcError, match="actuators: B exceeds n_rows"):
-                call()
-        q, v = world.q.clone(), world.v.clone()
-        Q, V = torch.full((B, K, 18), 7.0, device=L.device), torch.full((B, K, 18), 7.0, device=L.device)
-        with pytest.raises(NmpcError, match="actuators: B exceeds n_rows"):
-            L.contact_track(q, v, world.A, DT, N_SUB, tau_ff=world.tau, kp=KP, kd=KD, Q=Q, V=V)
-        assert same(q, world.q) and same(v, world.v) and bool((Q == 7.0).all()) and bool((V == 7.0).all())
-    L.set_integrator("explicit")
-    assert all(same(x, y) for x, y in zip(small.step(), kept))
-    # n_rows < 1: refused, what was attached stays
-    for n_rows in (0, -3):
-        assert lib.nmpc_contact_set_actuators(L._h, _lib.ptr(table), n_rows) == -1 and "n_rows must be at least 1" in text()
-    assert all(same(x, y) for x, y in zip(small.step(), kept))
-    with pytest.raises(NmpcError, match="actuators: B exceeds n_rows"):
-        world.step()
-    # a NULL handle
-    assert lib.nmpc_contact_set_actuators(None, _lib.ptr(table), 4) == -1 and b"handle" in lib.nmpc_torque_last_error(None)
+    # B > n_rows in every call that reads the table, n_rows < 1, a NULL handle
+    kept = ph.calls_beyond_the_tables_rows_are_refused(world, small, policy, "actuators", table)
     # the Python validators, field by field
     for col, bads in ((0, (0.0, -1.0, np.nan, np.inf)), (1, (-0.1, np.nan, np.inf)), (2, (-0.01, np.nan, np.inf)), (3, (-0.001, np.nan, np.inf))):
         for bad in bads:

@@ -17,10 +17,9 @@ from tests import fd_reference as fr
 from tests import plant_helpers as ph
 from tests.delay_reference import delay_line as reference
 from tests.plant_helpers import DT, DT_IMPLICIT, HEIGHT, KD, KP, MASK, N_SUB, PERIOD, T0
-from tests.plant_helpers import World, default_policy, expert, quadruped_layer, standing_start  # noqa: F401
+from tests.plant_helpers import World, default_policy, detached, draw_actuators, draw_payloads, error_text, expert  # noqa: F401
+from tests.plant_helpers import quadruped_layer, standing_start, start_states  # noqa: F401
 from tests.solve_helpers import dev  # noqa: F401
-from tests.test_gpu_actuators import draw_actuators
-from tests.test_gpu_payloads import draw_payloads, start_states
 from tests.torque_helpers import layer, same
 
 pytestmark = pytest.mark.gpu
@@ -66,19 +65,6 @@ def world(fx):
     return World(fx.m, B, q=fx.q, v=fx.v, tau=fx.tau, A=fx.A, goal=fx.goal)
 
 
-def detach(L):
-    L.set_delays(None)
-    L.set_actuators(None)
-    ph.detach(L)
-
-
-@pytest.fixture()
-def detached(world):
-    """whatever a test attaches or sets on the module's layer is gone after it, also when it fails"""
-    yield
-    detach(world.L)
-
-
 def attach(fx, w, L=None, work_rows=K):
     """the fixture's delays (as a device tensor, taken as given) with the fixture's register"""
     L = L or w.L
@@ -93,10 +79,6 @@ def track(w, A, q=None, v=None, dt=DT, **kw):
 
 def step(w, q, v, q_des, n_sub=N_SUB, dt=DT):
     return w.L.contact_step(q, v, dt, n_sub, tau_ff=w.tau, q_des=q_des, kp=KP, kd=KD)[:2]
-
-
-def error_text(L):
-    return L.lib.nmpc_torque_last_error(L._h).decode()
 
 
 # ---- 1. the delay line against the restatement of its rule ---------------------------------------------------------------------------

@@ -19,7 +19,7 @@ from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import implicit_reference as ir
 from tests import plant_helpers as ph
-from tests.plant_helpers import AT, DT, DT_IMPLICIT, HEIGHT, INTEGRATORS, KD, KP, MASK, N_SUB, NAMES, PERIOD, STEP_SUB, T0, TRACK_NAMES
+from tests.plant_helpers import AT, DT, DT_IMPLICIT, INTEGRATORS, KD, KP, N_SUB, NAMES, STEP_SUB, TRACK_NAMES
 from tests.plant_helpers import World, default_policy, detached, expert, held_row_by_row, quadruped_layer, standing_start  # noqa: F401
 from tests.solve_helpers import dev  # noqa: F401
 from tests.torque_helpers import THREE_HEIGHTS, branches, held, host, layer, lower_feet, rows_equal, same
@@ -27,15 +27,9 @@ from tests.torque_helpers import THREE_HEIGHTS, branches, held, host, layer, low
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-DT32 = float(np.float32(DT))
 B, SEED = 33, 7
 K = ph.ROLLOUT_STEPS                                      # the track and the policy rollout: 3 control steps of N_SUB = 2 substeps
 ROBOTS = (0, 31, 32)                                      # first lane, last lane of a block, the ragged tail
-
-
-def rows_to_grounds(rows):
-    """the reference `Ground` of every row of a float32 table (tau_max 0: no limit), from the float32 values themselves"""
-    return [cr.Ground(*(float(x) for x in r[:5]), tau_max=float(r[5]) if r[5] > 0 else None) for r in rows]
 
 
 def device_ground(row):
@@ -68,7 +62,7 @@ class Fixture(ph.Fixture):
         self.q_des = (self.q[:, 6:] + np.random.default_rng(1).uniform(-0.1, 0.1, (B, 12))).astype(np.float32)
         rng = np.random.default_rng(SEED)
         self.rows = draw_rows(rng, B, 0.0, (5e3, 2e4), (1.0, 5.0), (2.0, 6.0))
-        self.G = rows_to_grounds(self.rows)
+        self.G = ph.grounds_of(self.rows)
         self.A = (self.q[:, None, 6:] + rng.uniform(-0.05, 0.05, (B, K, 12))).astype(np.float32)
         self.F = rng.uniform(-80, 80, (B, 3)).astype(np.float32)
         self.goal = rng.uniform(-0.5, 0.5, (B, 3)).astype(np.float32)
@@ -230,7 +224,7 @@ def test_general_trees_step_under_a_table(tree):
     z = float(np.float32(np.median([cr.feet(m, q[b])[0][:, 2] for b in range(n_robots)])))
     q_des = (q[:, m.n - m.nu:] + np.random.default_rng(3).uniform(-0.1, 0.1, (n_robots, m.nu))).astype(np.float32)
     rows = draw_rows(np.random.default_rng(SEED), n_robots, z, SOFT["stiffness"], SOFT["damping"], (2.0, 6.0))
-    G = rows_to_grounds(rows)
+    G = ph.grounds_of(rows)
     run = lambda **kw: [np.stack(x) for x in zip(*[cr.contact_step_ref(m, G[b], q[b], v[b], DT, 1, tau[b], q_des[b], KP, KD, **kw)  # noqa: E731
                                                    for b in range(n_robots)])]
     ref, f32 = run(), run(fd=fr.aba, dtype=np.float32)
@@ -250,44 +244,12 @@ def policy(world):
     return default_policy()
 
 
-def rollout(world, policy):
-    return world.rollout(policy)
-
-
 def test_the_policy_rollout_is_its_chain_of_public_calls(fx, world, policy, detached):
-    L = world.L
-    L.set_grounds(fx.rows)
-    q, v = world.q, world.v
-    failed = torch.zeros(B, dtype=torch.int32, device=L.device)
-    S, A = [], []
-    for k in range(K):
-        s, x = L.observe(q, v, T0 + (k * N_SUB) * DT32, PERIOD, world.goal, collision_height=HEIGHT, failed=failed, step_index=k, term_mask=MASK)
-        a = policy.forward(x)
-        q, v = L.contact_step(q, v, DT, N_SUB, tau_ff=world.tau, q_des=a, kp=KP, kd=KD)[:2]
-        S.append(s); A.append(a)
-    L.observe(q, v, T0 + (K * N_SUB) * DT32, PERIOD, world.goal, collision_height=HEIGHT, failed=failed, step_index=K, term_mask=MASK)
-    got = rollout(world, policy)
-    assert all(same(x, y) for x, y in zip(got[:4], (q, v, torch.stack(S, 1), torch.stack(A, 1)))) and torch.equal(got[4], failed)
-    L.set_grounds(None)
-    assert not same(rollout(world, policy)[0], got[0])                                 # the table matters
+    ph.policy_rollout_is_its_chain_of_public_calls(world, policy, "grounds", fx.rows)
 
 
 def test_evaluate_policy_attaches_and_detaches_the_table(fx, world, policy, detached):
-    from iterative_learning_nmpc_amd.learning import evaluate_policy
-    L = world.L
-    L.set_grounds(fx.rows)
-    q, v, S, A, failed = rollout(world, policy)
-    L.set_grounds(None)
-    kw = dict(dt=DT, n_sub=N_SUB, tau_ff=world.tau, kp=KP, kd=KD, t0=T0, period=PERIOD, terminate_mask=MASK, collision_height=HEIGHT)
-    out = evaluate_policy(L, policy, None, world.q, world.v, world.goal, K * N_SUB * DT, grounds=fx.rows, **kw)
-    assert same(out["S"], S) and same(out["A"], A) and torch.equal(out["failed"], failed)
-    assert L._grounds is None
-    assert same(rollout(world, policy)[0], evaluate_policy(L, policy, None, world.q, world.v, world.goal, K * N_SUB * DT, **kw)["q"])      # nothing is attached
-    # a table of the caller's is not replaced
-    L.set_grounds(fx.rows)
-    with pytest.raises(ValueError, match="attached already"):
-        evaluate_policy(L, policy, None, world.q, world.v, world.goal, K * N_SUB * DT, grounds=fx.rows, **kw)
-    assert L._grounds is not None
+    ph.evaluate_policy_attaches_and_detaches_the_table(world, policy, "grounds", fx.rows)
 
 
 # ---- 6. the expert on the plant ----------------------------------------------------------------------------------------------------------

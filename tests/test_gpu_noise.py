@@ -18,9 +18,8 @@ from tests import fd_reference as fr
 from tests import noise_reference as nr
 from tests import plant_helpers as ph
 from tests.plant_helpers import DT, HEIGHT, KD, KP, MASK, N_SUB, PERIOD, T0
-from tests.plant_helpers import default_policy
+from tests.plant_helpers import default_policy, detached, error_text, start_states  # noqa: F401
 from tests.solve_helpers import dev  # noqa: F401
-from tests.test_gpu_payloads import start_states
 from tests.torque_helpers import layer, same
 
 pytestmark = pytest.mark.gpu
@@ -67,19 +66,6 @@ def world(fx):
 @pytest.fixture(scope="module")
 def policy(dev):
     return default_policy()
-
-
-@pytest.fixture()
-def detached(world):
-    """whatever a test attaches on the module's layer is gone after it, also when it fails"""
-    yield
-    world.L.set_noise(None)
-    world.L.set_delays(None)
-    ph.detach(world.L)
-
-
-def error_text(L):
-    return L.lib.nmpc_torque_last_error(L._h).decode()
 
 
 def stats_of(fx, stats):

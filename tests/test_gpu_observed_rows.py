@@ -18,8 +18,8 @@ from tests import fd_reference as fr
 from tests import input_noise_reference as ir
 from tests import plant_helpers as ph
 from tests.plant_helpers import DT, HEIGHT, KD, KP, MASK, N_SUB, PERIOD, T0
+from tests.plant_helpers import detached, error_text, start_states  # noqa: F401
 from tests.solve_helpers import dev, policy_pair  # noqa: F401
-from tests.test_gpu_payloads import start_states
 from tests.torque_helpers import same
 
 pytestmark = pytest.mark.gpu
@@ -65,19 +65,6 @@ def world(fx):
 @pytest.fixture(scope="module")
 def policy(dev):
     return policy_pair(47, 12, 1, 16, True, 8, seed=5)[0]
-
-
-@pytest.fixture()
-def detached(world):
-    """whatever a test attaches on the module's layer is gone after it, also when it fails"""
-    yield
-    world.L.set_noise(None)
-    world.L.set_rollout_observed(None)
-    ph.detach(world.L)
-
-
-def error_text(L):
-    return L.lib.nmpc_torque_last_error(L._h).decode()
 
 
 def rollout(w, policy, fx, n, stats, n_steps=K):

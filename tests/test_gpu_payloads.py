@@ -19,45 +19,15 @@ from tests import contact_reference as cr
 from tests import fd_reference as fr
 from tests import payload_reference as plr
 from tests import plant_helpers as ph
-from tests.plant_helpers import AT, DT, DT_IMPLICIT, HEIGHT, INTEGRATORS, KD, KP, MASK, N_SUB, NAMES, ONE, PERIOD, STEP_SUB, T0, TRACK_NAMES
-from tests.plant_helpers import World, chain_of_public_calls, default_policy, detach, detached, expert, held_row_by_row  # noqa: F401
-from tests.plant_helpers import plant_rollout, quadruped_layer, standing_start  # noqa: F401
+from tests.plant_helpers import AT, DT, DT_IMPLICIT, INTEGRATORS, KD, KP, N_SUB, NAMES, STEP_SUB, TRACK_NAMES, TRUNK
+from tests.plant_helpers import World, default_policy, detached, draw_payloads, quadruped_layer, start_states, wide_world  # noqa: F401
 from tests.solve_helpers import dev  # noqa: F401
-from tests.torque_helpers import bar, fractions, host, layer, lower_feet, same
+from tests.torque_helpers import bar, fractions, host, layer, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 B, K = 33, 5                                             # the track: 5 control steps; the policy rollout has the plant's 3
-TRUNK = 5
-
-
-def draw_payloads(rng, n):
-    """n rows: m_p in [0, 5] kg -- robot 0 carries nothing, robot 1 the full 5 kg --, r uniform in direction with |r| <= 0.15 m"""
-    rows = np.zeros((n, 4), np.float32)
-    rows[:, 0] = rng.uniform(0.0, 5.0, n)
-    rows[0, 0] = 0.0
-    if n > 1:
-        rows[1, 0] = 5.0
-    r = rng.standard_normal((n, 3))
-    rows[:, 1:] = r / np.linalg.norm(r, axis=1, keepdims=True) * rng.uniform(0.0, 0.149, (n, 1))
-    assert np.linalg.norm(rows[:, 1:].astype(np.float64), axis=1).max() <= 0.15
-    return rows
-
-
-def start_states(m, n, rng, slide=2):
-    """the standing pose with +-0.1 rad on every joint and +-0.05 on the base attitude, velocities within +-1, and joint `slide`
-    (the vertical base slider) set so that the lowest foot is at +2 cm ... -2 cm over the robots"""
-    q = np.zeros((n, m.n)); q[:, 3:6] = rng.uniform(-0.05, 0.05, (n, 3)); q[:, 6:] = fr.STAND + rng.uniform(-0.1, 0.1, (n, 12))
-    q[:, :2] = rng.uniform(-0.2, 0.2, (n, 2)); q[:, slide] = 0.3
-    v = rng.uniform(-1.0, 1.0, (n, m.n))
-    # Above the ground from 2 cm down to 1 mm, inside it from 4 mm to 2 cm, and nobody in between: a foot z of 0.3 m of kinematics
-    # carries an error of a float32 ulp or two (2^-25 m), which the law turns into k x that = 3e-4 N of force whatever the depth,
-    # while the bar's floor for a robot that touches at depth d is 1e-5 k d: below d = 3 mm the floor is under what the number
-    # format owes and the bar would rest on the luck of the one float32 run that is its other term.
-    want = np.concatenate([np.linspace(0.02, 0.001, n // 2), np.linspace(-0.004, -0.02, n - n // 2)]) if n > 1 else np.array([-0.01])
-    # float32 before the correction, and a second pass that takes out what float32 left of the first
-    return lower_feet(m, q, want, slide, passes=2, dtype=np.float32), v.astype(np.float32)
 
 
 class Fixture(ph.Fixture):
@@ -195,37 +165,6 @@ def test_a_uniform_table_is_the_layer_of_the_baked_tree(fx, world, detached, int
 
 
 # ---- 3. row b is robot b's, bit for bit -----------------------------------------------------------------------------------------------------
-def tree32():
-    """a 32-joint tree for the 16-wide blocks: the quadruped with 14 more one-joint bodies (a tail and a neck of revolute and
-    prismatic joints in turn) hanging on its trunk, all behind the legs in joint order so the base and the feet stay where they are"""
-    m = fr.quadruped()
-    rng = np.random.default_rng(23)
-    extra = 32 - m.n
-    parent = list(m.parent) + [TRUNK if i % 7 == 0 else m.n + i - 1 for i in range(extra)]
-    jtype = list(m.jtype) + [i % 2 for i in range(extra)]
-    axis = rng.standard_normal((extra, 3)); axis /= np.linalg.norm(axis, axis=1, keepdims=True)
-    inertia = np.tile([2e-4, 0, 0, 2e-4, 0, 2e-4], (extra, 1))
-    from oracle import torque_oracle as to
-    return to.TreeModel(parent, jtype, np.vstack([m.axis, axis]), np.concatenate([m.R_fix, np.tile(np.eye(3), (extra, 1, 1))]),
-                        np.vstack([m.p_fix, 0.05 * rng.standard_normal((extra, 3))]), np.concatenate([m.mass, rng.uniform(0.05, 0.2, extra)]),
-                        np.vstack([m.com, 0.02 * rng.standard_normal((extra, 3))]), np.vstack([m.inertia, inertia]), m.foot_joint, m.foot_offset,
-                        n_actuated=12 + extra, gravity=m.gravity)
-
-
-def wide_world():
-    """B = 17 on the 32-joint tree: the first 18 coordinates are the quadruped's start states, the appended joints start in +-0.3"""
-    m = tree32()
-    rng = np.random.default_rng(29)
-    n, extra = 17, m.n - 18
-    q18, v18 = start_states(fr.quadruped(), n, rng)
-    q = np.hstack([q18, rng.uniform(-0.3, 0.3, (n, extra)).astype(np.float32)])
-    v = np.hstack([v18, rng.uniform(-1, 1, (n, extra)).astype(np.float32)])
-    tau = rng.uniform(-2, 2, (n, m.nu)).astype(np.float32)
-    q_des = (q[:, 6:] + rng.uniform(-0.1, 0.1, (n, m.nu))).astype(np.float32)
-    A = (q[:, None, 6:] + rng.uniform(-0.05, 0.05, (n, K, m.nu))).astype(np.float32)
-    return World(m, n, q=q, v=v, tau=tau, q_des=q_des, A=A)
-
-
 @pytest.fixture(scope="module")
 def worlds(fx, world):
     return {"B1": quad_world(fx, 1, world.L), "B31": quad_world(fx, 31, world.L), "B32": quad_world(fx, 32, world.L), "B33": world, "tree32 B17": wide_world()}
@@ -240,11 +179,8 @@ EXTRAS = ("none", "grounds", "push", "windows")
 def test_row_b_is_robot_bs_bit_for_bit(fx, worlds, shape, integrator, extra):
     w = worlds[shape]
     L, n = w.L, w.n
-    dt = DT_IMPLICIT if integrator == "implicit" else DT
-    rng = np.random.default_rng(31)
-    rows, grounds, F = fx.rows[:n], fx.grounds[:n], fx.F[:n]
+    grounds, F = fx.grounds[:n], fx.F[:n]
     first, count = np.array([1 + 2 * (b % 2) for b in range(n)]), np.array([1 + b % 3 for b in range(n)])
-    perm = rng.permutation(n)
 
     def attach(rows_, idx):
         """the table rows_ with what `extra` names for the robots idx"""
@@ -255,104 +191,24 @@ def test_row_b_is_robot_bs_bit_for_bit(fx, worlds, shape, integrator, extra):
             L.set_push(w.d(F[idx]), first[idx], count[idx])
         L.set_payloads(rows_, joint=TRUNK)
 
-    def run(world_=w):
-        return world_.step(dt=dt) + world_.track(dt=dt)
-
-    try:
-        L.set_integrator(integrator)
-        everyone = np.arange(n)
-        # robot b under the uniform table of its row: the same call otherwise, the same grounds, push and windows
-        got, _ = held_row_by_row(run, lambda: attach(rows, everyone), lambda b: attach(np.tile(rows[b], (n, 1)), everyone), sorted({0, n // 2, n - 1}),
-                                 NAMES + (TRACK_NAMES if w.record else TRACK_NAMES[:2]),
-                                 lambda b, o: f"{shape}, {integrator}, {extra}, robot {b} {o}: largest |table - uniform|")
-        # a permutation of robots and rows permutes the outputs
-        p = torch.as_tensor(perm, device=L.device)
-        attach(rows[perm], perm)
-        shuffled = run(w.permuted(perm))
-        assert all(same(x[p], y) for x, y in zip(got, shuffled)), shape
-        # spare rows change nothing
-        attach(np.vstack([rows, fx.rows[::-1][:3]]), everyone)
-        longer = run()
-        assert all(same(x, y) for x, y in zip(got, longer)), shape
-        # and the rows matter
-        if n > 1:
-            L.set_payloads(None)
-            assert not all(same(x, y) for x, y in zip(got, run()))
-    finally:
-        detach(L)
+    ph.row_b_is_robot_bs(w, fx.rows[:n], fx.rows[::-1][:3], attach, "payloads", integrator, np.random.default_rng(31).permutation(n),
+                         lambda b, o: f"{shape}, {integrator}, {extra}, robot {b} {o}: largest |table - uniform|")
 
 
 # ---- 4. attach, then detach -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("integrator", INTEGRATORS)
 def test_attach_then_detach_gives_the_bits_from_before(fx, world, detached, integrator):
-    L = world.L
-    L.set_integrator(integrator)
-    policy = default_policy()
-    calls = lambda: world.step() + world.track() + rollout(world, policy)      # noqa: E731
-    before = calls()
-    L.set_payloads(fx.rows)
-    assert L._payloads is not None
-    during = calls()
-    L.set_payloads(None)
-    assert L._payloads is None
-    after = calls()
-    assert all(same(x, y) if x.is_floating_point() else torch.equal(x, y) for x, y in zip(before, after))
-    assert not all(same(x, y) for x, y in zip(before[:5], during[:5]))
+    ph.attach_then_detach_gives_the_bits_from_before(world, "payloads", fx.rows, integrator)
 
 
 # ---- 5. what it does not touch --------------------------------------------------------------------------------------------------------------
 def test_the_nominal_model_does_not_read_the_table(fx, world, detached, dev):
-    from iterative_learning_nmpc_amd.torque import GroundContact
-    L = world.L
-    a = world.d(np.random.default_rng(3).uniform(-5, 5, (B, 18)).astype(np.float32))
-    f = world.d(np.random.default_rng(4).uniform(-40, 80, (B, 4, 3)).astype(np.float32))
-    tau = world.d(np.random.default_rng(5).uniform(-20, 20, (B, 12)).astype(np.float32))
-    mpc = expert(dev, 2)
-    q0, v0 = standing_start(2)
-    o = plant_rollout(mpc, L, q0, v0, ONE)
-    zoh = mpc.id_repeat[:40]
-
-    def nominal():
-        return dict(id_torques=L.id_torques(world.q, world.v, a, f), fd_accel=L.forward_dynamics(world.q, world.v, tau, f),
-                    mass_matrix=L.mass_matrix(world.q), centroidal=torch.cat([x.reshape(B, -1) for x in L.centroidal(world.q, world.v, jacobian=True)], 1),
-                    state_momentum=L.state_momentum(world.q, world.v), contact_forces=L.contact_forces(world.q, world.v, GroundContact()),
-                    plan_actions=L.plan_actions(o["X"], o["U"], zoh, mpc.config_opt.time_horizon / mpc.config_opt.n_nodes, mpc.sim_dt, kp=mpc.Kp, kd=mpc.Kd))
-
-    without = nominal()
-    L.set_payloads(fx.rows)
-    loaded = nominal()
-    assert world.step()[0] is not None                    # the table is attached and a plant call takes it
-    for name in without:
-        assert same(without[name], loaded[name]), name
-    assert list(without) == ["id_torques", "fd_accel", "mass_matrix", "centroidal", "state_momentum", "contact_forces", "plan_actions"]
+    ph.nominal_model_does_not_read_the_table(world, dev, "payloads", fx.rows)
 
 
 # ---- 6. rollout paths -----------------------------------------------------------------------------------------------------------------------
 def test_evaluate_policy_attaches_and_detaches_the_table(fx, world, detached):
-    from iterative_learning_nmpc_amd.learning import evaluate_policy
-    L = world.L
-    policy = default_policy()
-    goal = world.goal
-    L.set_payloads(fx.rows)
-    q, v, S, A, failed = rollout(world, policy)
-    L.set_payloads(None)
-    bare = rollout(world, policy)
-    kw = dict(dt=DT, n_sub=N_SUB, tau_ff=world.tau, kp=KP, kd=KD, t0=T0, period=PERIOD, terminate_mask=MASK, collision_height=HEIGHT)
-    out = evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, payloads=fx.rows, **kw)
-    assert same(out["S"], S) and same(out["A"], A) and same(out["q"], q) and same(out["v"], v) and torch.equal(out["failed"], failed)
-    assert not same(out["q"], bare[0])
-    assert L._payloads is None
-    assert same(evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, **kw)["q"], bare[0])      # nothing is attached
-    # also when the rollout raises: a goal of the wrong batch is refused inside the try
-    with pytest.raises(Exception):
-        evaluate_policy(L, policy, None, world.q, world.v, goal[:5], 3 * N_SUB * DT, payloads=fx.rows, **kw)
-    assert L._payloads is None and same(rollout(world, policy)[0], bare[0])
-    # a table of the caller's is not replaced
-    L.set_payloads(fx.rows)
-    mine = L._payloads
-    with pytest.raises(ValueError, match="attached already"):
-        evaluate_policy(L, policy, None, world.q, world.v, goal, 3 * N_SUB * DT, payloads=fx.rows, **kw)
-    assert L._payloads is mine and same(rollout(world, policy)[0], q)
+    ph.evaluate_policy_attaches_and_detaches_the_table(world, default_policy(), "payloads", fx.rows)
 
 
 def test_dagger_iteration_labels_with_the_nominal_expert(fx, dev):
@@ -378,21 +234,7 @@ def test_dagger_iteration_labels_with_the_nominal_expert(fx, dev):
 
 
 def test_the_expert_on_the_plant_carries_the_table_of_its_layer(fx, dev, quadruped_layer):
-    """B = 2, one replan: the plant-mode rollout with a table on its layer is the chain plan labels -> contact_track -> observe_rows
-    under the same table (the check of tests/test_gpu_wb_plant_rollout.py), and not the unloaded rollout."""
-    L = quadruped_layer
-    rows = fx.rows[1:3].copy()
-    q0, v0 = standing_start(2)
-    bare = plant_rollout(expert(dev, 2), L, q0, v0, ONE)
-    L.set_payloads(rows)
-    mpc = expert(dev, 2)
-    o = plant_rollout(mpc, L, q0, v0, ONE)
-    S, A, q, v, failed = chain_of_public_calls(mpc, L, o["X"], o["U"], q0, v0, o["status"])
-    L.set_payloads(None)
-    assert o["S"].shape == (2, 40, 44) and bool(torch.isfinite(o["S"]).all())
-    assert all(same(a, b) for a, b in zip((o["S"], o["A"], o["q"], o["v"]), (S, A, q, v))) and torch.equal(o["failed"], failed)
-    assert same(o["A"], bare["A"])                        # the labels of the first plan are the nominal expert's
-    assert not same(o["q"], bare["q"])                    # the plant carried the load
+    ph.expert_on_the_plant_meets_the_table_of_its_layer(dev, quadruped_layer, "payloads", fx.rows[1:3].copy())
 
 
 # ---- 7. refusals ----------------------------------------------------------------------------------------------------------------------------
@@ -402,31 +244,20 @@ def test_refusals_leave_the_handle_as_it_was(fx, world, detached):
     from iterative_learning_nmpc_amd.learning import evaluate_policy
     from iterative_learning_nmpc_amd.torque import payload_table
     L, lib = world.L, world.L.lib
-    text = lambda: lib.nmpc_torque_last_error(L._h).decode()                           # noqa: E731
     policy = default_policy()
     goal = world.goal
     small = quad_world(fx, 4, L)
     table = world.d(fx.rows[:4])
     L.set_payloads(table)
-    assert L._payloads is table                           # a device tensor is taken as given
-    kept = small.step()
-    # B > n_rows, in every call that reads the table: nothing is launched, what is attached stays
-    for call in (world.step, world.track, lambda: rollout(world, policy)):
-        with pytest.raises(NmpcError, match="payloads: B exceeds n_rows"):
-            call()
-    assert all(same(x, y) for x, y in zip(small.step(), kept))
-    # joint out of range, n_rows < 1: refused, what was attached stays
+    # B > n_rows in every call that reads the table, n_rows < 1, a NULL handle
+    kept = ph.calls_beyond_the_tables_rows_are_refused(world, small, policy, "payloads", table, TRUNK)
+    # joint out of range: refused, and the table and the joint the library holds stay what they were
     for joint in (-1, 18, 99):
-        assert lib.nmpc_contact_set_payloads(L._h, _lib.ptr(table), 4, joint) == -1 and "joint must be in [0, n_joints)" in text()
+        assert lib.nmpc_contact_set_payloads(L._h, _lib.ptr(table), 4, joint) == -1 and "joint must be in [0, n_joints)" in ph.error_text(L)
         with pytest.raises(NmpcError, match="joint must be in"):
             L.set_payloads(table, joint=joint)
         assert L._payloads is table
-    assert lib.nmpc_contact_set_payloads(L._h, _lib.ptr(table), 0, TRUNK) == -1 and "n_rows must be at least 1" in text()
     assert all(same(x, y) for x, y in zip(small.step(), kept))
-    with pytest.raises(NmpcError, match="payloads: B exceeds n_rows"):
-        world.step()
-    # a NULL handle
-    assert lib.nmpc_contact_set_payloads(None, _lib.ptr(table), 4, TRUNK) == -1 and b"handle" in lib.nmpc_torque_last_error(None)
     # negative or non-finite mass on the host
     for bad in (-0.1, np.nan, np.inf):
         rows = fx.rows.copy(); rows[2, 0] = bad

@@ -297,7 +297,7 @@ def torque_digests():
     # both widths): B = 33 on the tilted quadruped from the start states of tests/test_gpu_payloads.py, the lowest foot from 2 cm
     # above the ground to 2 cm inside it; B = 40 on the 30-joint tree, whose every joint is actuated, the payload on body 4
     from iterative_learning_nmpc_amd.torque import sample_grounds, sample_payloads
-    from tests.test_gpu_payloads import start_states
+    from tests.plant_helpers import start_states
     varied = dict(ground_z=(-0.005, 0.005), mu=(0.3, 1.1), tau_max=(15.0, 40.0))
     gq = sample_grounds(33, np.random.default_rng(33), base=ground(w.c.g), stiffness=(5e3, 2e4), damping=(1.0, 5.0), **varied)
     gw = sample_grounds(40, np.random.default_rng(40), base=GroundContact(**SOFT), stiffness=(100.0, 300.0), damping=(0.2, 1.0), **varied)
