@@ -496,6 +496,72 @@ int nmpc_observed_rows_batch(void *torque, int B, const float *S, int s_stride, 
  * are without O.  O = NULL detaches.  A rollout with o_rows < n_steps returns NMPC_E_ARG before any launch. */
 int nmpc_policy_rollout_set_observed(void *torque, float *O, int o_rows);
 
+/* Observation and action history on the policy input [decl] (a robot's ground, payload, actuator, delay and sensor bias do not
+ * stand in one 44-slot row: they show in how successive rows and the issued PD targets relate, so a memoryless policy cannot
+ * identify them).  With n_obs >= 1 observed rows and n_act >= 0 previous actions, n_wide = 44 n_obs + 12 n_act, and the raw wide
+ * row of robot b in control step k is
+ *   W_k = [ O_k | O_{k-1} | ... | O_{k-n_obs+1} | A_{k-1} | ... | A_{k-n_act} ]
+ * O_j the raw 44-slot row as the robot's sensors showed it in step j (nmpc_observed_rows_batch of the true row at that step's
+ * noise step; S_j to the bit without a table of noise), A_j the PD target ISSUED in step j (what A records, not what a delayed
+ * joint met).  Before step 0 an entry is whatever the register held.  The policy input is X_k = [normalise(W_k), goal]: column c
+ * in [s_first, n_wide) is (float)(((double)w - s_mean[c]) / s_std[c]), the others are raw, the goal follows raw -- the expression
+ * of nmpc_assemble_batch on a table of n_state = n_wide, so what a database makes of a stored wide row is bit for bit what the
+ * policy was shown.  With a table of noise X_k[:44] is normalise(O_k), the quotient taken once on the perturbed row; that differs
+ * by roundings from the memoryless input normalise(S) + n / s_std of nmpc_contact_set_noise.  With a history attached deployment
+ * and training see identical inputs.
+ * Two registers, both dev float, caller-owned and kept as pointers; the library still never allocates:
+ *   hist [rows][n_obs][44]   slot 0 is the incoming slot: the caller or the rollout writes step k's observed row there (for
+ *                            example nmpc_observed_rows_batch with o_stride = 44 n_obs); slot h is the row of h steps ago
+ *   act  [rows][n_act][12]   slot i is the target issued i + 1 steps before the next one, the delay register's convention
+ * NMPC_HISTORY_MAX bounds both depths. */
+#define NMPC_HISTORY_MAX 16
+
+/* The wide row of B robots out of their registers, then the observed rows age.  One launch, one thread per (robot, column of
+ * 44 + 12 + n_goal).  Thread (b, j < 44) reads column j of all n_obs slots of robot b, writes the n_obs entries of W (robot b's
+ * row at W + b * w_stride, w_stride >= n_wide; the words behind n_wide are not touched) and of X ([B][n_wide + n_goal], dense)
+ * that are made of them, and ages its column in place, slot h + 1 <- slot h from the oldest down; slot 0 keeps its content.
+ * Thread (b, 44 + i) writes the n_act entries of joint i and moves nothing (nmpc_history_push_actions_batch moves them); the goal
+ * threads copy the goal [B][n_goal] behind the wide row of X.  Either of W and X may be NULL, not both.  s_mean, s_std: dev double
+ * [n_wide] or both NULL (X is raw); the quotient is taken in fp64 as nmpc_assemble_batch takes it.  Every word of W is a copy of an
+ * input word; no thread reads a word another thread writes, provided W and X overlap neither register.  Stream-ordered, no
+ * allocation, no synchronisation.
+ * NMPC_E_ARG before any launch (text in nmpc_torque_last_error): a NULL hist, a NULL act with n_act > 0, W and X both NULL; B < 1;
+ * n_obs outside [1, 16], n_act outside [0, 16]; w_stride < n_wide with a W; only one of s_mean / s_std; s_first outside
+ * [0, n_wide]; n_goal < 0; an X with n_goal > 0 and no goal; a tree that is not 18 / 12 / 4. */
+int nmpc_history_push_batch(void *torque, int B, float *hist, int n_obs, const float *act, int n_act, const float *goal, int n_goal,
+                            const double *s_mean, const double *s_std, int s_first, float *W, int w_stride, float *X, void *stream);
+
+/* The action register of B robots moves on by one control step: slot s <- slot s - 1 from the oldest down, then slot 0 <- the
+ * target just issued, robot b's at A + b * a_stride (a_stride >= 12).  One launch, one thread per (robot, joint); every word is a
+ * copy.  NMPC_E_ARG before any launch: a NULL act or A; B < 1; n_act outside [1, 16]; a_stride < 12; a tree that is not 18 / 12 / 4. */
+int nmpc_history_push_actions_batch(void *torque, int B, float *act, int n_act, const float *A, int a_stride, void *stream);
+
+/* The history on the policy input of a policy rollout, attached as nmpc_policy_rollout_set_observed attaches O.  While hist
+ * [rows][n_obs][44] and act [rows][n_act][12] are attached, nmpc_policy_rollout_batch takes a policy of n_wide + n_goal inputs, a
+ * workspace X [B][n_wide + n_goal] and statistics s_mean, s_std [n_wide], and its control step k is bit for bit this chain of the
+ * public calls:
+ *   1. nmpc_contact_noise_step (with a table of noise attached);
+ *   2. nmpc_observe_batch exactly as without a history: its narrow X [B][44 + n_goal] goes into the head of the workspace, with a
+ *      table of noise it draws and the noise step moves on by one;
+ *   3. nmpc_observed_rows_batch of the step's true row into slot 0 of hist (o_stride = 44 n_obs) at the step read -- in addition
+ *      to the launch into an attached O; in a rollout with neither S nor O the observation writes the true row into slot 0 and it is
+ *      perturbed in place;
+ *   4. nmpc_history_push_batch into row k of W (robot b's at W + (b * w_rows + k) * n_wide) if W is given, and into the workspace
+ *      X, overwriting it;
+ *   5. nmpc_policy_forward;
+ *   6. the contact step as without a history, the delay line included;
+ *   7. nmpc_history_push_actions_batch of the issued dense actions, if n_act > 0.
+ * Two or three more launches per control step.  S, failed, the Q, V of nmpc_policy_rollout_set_states, the delay register, O and
+ * the noise step are the bits they are without a history when the policy is fed the same input; at (n_obs, n_act) = (1, 0) without
+ * noise the rollout is the one without a history and W is S.  Both registers move with every step, so two rollouts of K control
+ * steps are the rollout of 2 K; the caller fills them before the first (a posture and its row, say).  W: dev float
+ * [rows][w_rows][n_wide] or NULL.  hist = NULL detaches (nothing else is read); detached, every call makes exactly the launches
+ * it makes without this entry point.  Capture into a graph is out of scope, as for the noise step.
+ * NMPC_E_ARG (text in nmpc_torque_last_error), what was attached staying: n_obs outside [1, 16]; n_act outside [0, 16]; a NULL act
+ * with n_act > 0; rows < 1; w_rows < 1 with a W.  At nmpc_policy_rollout_batch, before any launch: B > rows; w_rows < n_steps; a
+ * policy whose n_in != n_wide + n_goal. */
+int nmpc_policy_rollout_set_history(void *torque, float *hist, int n_obs, float *act, int n_act, float *W, int w_rows, int rows);
+
 /* A table of PD targets tracked on the contact plant [decl]: n_steps control steps in one launch, control step k being n_sub
  * substeps of nmpc_contact_step_batch's law with q_des = row k of robot b's table, at A + (b * a_rows + k) * 12 (a_rows >=
  * n_steps; 12 = n_actuated).  With the label rows of nmpc_plan_actions_batch as the table, A = (tau_id + kd v_plan) / kp + q_plan,

@@ -33,6 +33,8 @@ NMPC_INTEGRATOR_EXPLICIT = 0
 NMPC_INTEGRATOR_LINEARLY_IMPLICIT = 1
 # the deepest shift register of a delay line (include/nmpc_torque.h, nmpc_contact_set_delays)
 NMPC_DELAY_MAX_DEPTH = 64
+# the deepest observation or action history on the policy input (include/nmpc_torque.h, nmpc_policy_rollout_set_history)
+NMPC_HISTORY_MAX = 16
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -131,6 +133,10 @@ SIGNATURES = {
     "nmpc_policy_rollout_set_states": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "nmpc_policy_rollout_set_observed": (c_int, [c_void_p, c_void_p, c_int]),
     "nmpc_observed_rows_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
+    "nmpc_history_push_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_int, c_void_p, c_void_p]),
+    "nmpc_history_push_actions_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "nmpc_policy_rollout_set_history": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int]),
     "nmpc_contact_track_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "nmpc_observe_rows_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double,

@@ -372,6 +372,7 @@ __global__ void pd_target_action_kernel(int B, int n, int nu, const float* __res
 #include "nmpc_torque_track.hip.inc"
 #include "nmpc_torque_delay.hip.inc"
 #include "nmpc_torque_noise.hip.inc"
+#include "nmpc_torque_history.hip.inc"
 #include "nmpc_torque_centroidal.hip.inc"
 
 }  // namespace nmpc_torque
@@ -425,6 +426,15 @@ struct Torque {
         long long first_robot = 0;      // robot b of a call draws as robot first_robot + b of the population
         long long step = 0;             // the noise step of the next observation with an X; host state
     } noise;
+    struct {                            // nmpc_policy_rollout_set_history: observation and action history on the policy input (hist == nullptr: none)
+        float* hist = nullptr;          // [rows][n_obs][44]: slot 0 the incoming slot, slot h the observed row of h control steps ago
+        int n_obs = 0;
+        float* act = nullptr;           // [rows][n_act][12]: slot i the target issued i + 1 control steps before the next one
+        int n_act = 0;
+        float* W = nullptr;             // [rows][w_rows][n_wide]: the raw wide rows beside a policy rollout, or nullptr
+        int w_rows = 0, rows = 0;
+        int n_wide() const { return OB_STATE * n_obs + HIST_NU * n_act; }
+    } history;
     int integrator = NMPC_INTEGRATOR_EXPLICIT;      // nmpc_contact_set_integrator: how the plant calls take their substeps
     std::string err;
 };
@@ -618,6 +628,47 @@ int launch_observed_rows(Torque* t, int B, const float* S, int s_stride, float* 
     const size_t n = (size_t)B * OB_STATE;
     hipLaunchKernelGGL(observed_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, p);
     return launched(t);
+}
+
+// why registers of these depths cannot be a history (nullptr: they can): what the attach call and the two pushes share
+const char* history_depth_refusal(const float* hist, int n_obs, const float* act, int n_act) {
+    if (n_obs < 1 || n_obs > NMPC_HISTORY_MAX) return "history: n_obs must be in [1, NMPC_HISTORY_MAX]";
+    if (n_act < 0 || n_act > NMPC_HISTORY_MAX) return "history: n_act must be in [0, NMPC_HISTORY_MAX]";
+    if (!hist) return "history: hist is needed";
+    if (n_act > 0 && !act) return "history: act is needed with n_act > 0";
+    return nullptr;
+}
+
+// why the wide row of B robots cannot be pushed out of these registers (nullptr: it can)
+const char* history_push_refusal(const Torque* t, int B, const float* hist, int n_obs, const float* act, int n_act, const float* goal, int n_goal,
+                                 const double* s_mean, const double* s_std, int s_first, const float* W, int w_stride, const float* X) {
+    if (!whole_body_tree(t->host)) return "history: the wide row needs the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4";
+    if (B < 1) return "history: need B >= 1";
+    if (const char* why = history_depth_refusal(hist, n_obs, act, n_act)) return why;
+    const int n_wide = OB_STATE * n_obs + HIST_NU * n_act;
+    if (!W && !X) return "history: W or X is needed";
+    if (W && w_stride < n_wide) return "history: w_stride must be at least n_wide";
+    if (n_goal < 0) return "history: n_goal must not be negative";
+    if (!s_mean != !s_std) return "history: s_mean and s_std come together or not at all";
+    if (s_first < 0 || s_first > n_wide) return "history: s_first must be in [0, n_wide]";
+    if (X && n_goal > 0 && !goal) return "history: X needs goal";
+    return nullptr;
+}
+
+// the one launch of the wide row: what history_push_refusal accepted
+int launch_history_push(Torque* t, int B, float* hist, int n_obs, const float* act, int n_act, const float* goal, int n_goal, const double* s_mean,
+                        const double* s_std, int s_first, float* W, int w_stride, float* X, void* stream) {
+    HistoryPushArgs p{};
+    p.n_obs = n_obs; p.n_act = n_act; p.n_goal = n_goal; p.s_first = s_first; p.w_stride = w_stride;
+    p.hist = hist; p.act = act; p.goal = goal; p.s_mean = s_mean; p.s_std = s_std; p.W = W; p.X = X;
+    const size_t n = (size_t)B * (HIST_COLS + n_goal);
+    hipLaunchKernelGGL(history_push_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, p);
+    return launched(t);
+}
+
+// the one launch of the action register: slot 0 <- the dense or strided rows A
+int launch_history_push_actions(Torque* t, int B, float* act, int n_act, const float* A, int a_stride, void* stream) {
+    return launch_elementwise(t, history_push_actions_kernel, B, stream, n_act, act, A, a_stride);
 }
 
 // the kinematics pass, with or without the law; with the law of the attached table of grounds if there is one
@@ -1306,6 +1357,44 @@ int nmpc_policy_rollout_set_observed(void* torque, float* O, int o_rows) {
     return NMPC_OK;
 }
 
+int nmpc_policy_rollout_set_history(void* torque, float* hist, int n_obs, float* act, int n_act, float* W, int w_rows, int rows) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (hist) {                                           // what was attached stays
+        if (const char* why = history_depth_refusal(hist, n_obs, act, n_act)) return fail(t, NMPC_E_ARG, why);
+        if (rows < 1) return fail(t, NMPC_E_ARG, "history: rows must be at least 1");
+        if (W && w_rows < 1) return fail(t, NMPC_E_ARG, "history: w_rows must be at least 1");
+    }
+    t->history = {};
+    if (hist) {
+        t->history.hist = hist; t->history.n_obs = n_obs; t->history.act = n_act > 0 ? act : nullptr; t->history.n_act = n_act;
+        t->history.W = W; t->history.w_rows = W ? w_rows : 0; t->history.rows = rows;
+    }
+    return NMPC_OK;
+}
+
+int nmpc_history_push_batch(void* torque, int B, float* hist, int n_obs, const float* act, int n_act, const float* goal, int n_goal,
+                            const double* s_mean, const double* s_std, int s_first, float* W, int w_stride, float* X, void* stream) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (const char* why = history_push_refusal(t, B, hist, n_obs, act, n_act, goal, n_goal, s_mean, s_std, s_first, W, w_stride, X))
+        return fail(t, NMPC_E_ARG, why);
+    NMPC_ENTER(t, t->device);
+    return launch_history_push(t, B, hist, n_obs, act, n_act, goal, n_goal, s_mean, s_std, s_first, W, w_stride, X, stream);
+}
+
+int nmpc_history_push_actions_batch(void* torque, int B, float* act, int n_act, const float* A, int a_stride, void* stream) {
+    Torque* t = static_cast<Torque*>(torque);
+    if (!t) return fail(no_handle, NMPC_E_ARG, "null torque handle");
+    if (!whole_body_tree(t->host)) return fail(t, NMPC_E_ARG, "history: the action register needs the whole-body tree: n_joints = 18, n_actuated = 12, n_feet = 4");
+    if (B < 1) return fail(t, NMPC_E_ARG, "history: need B >= 1");
+    if (n_act < 1 || n_act > NMPC_HISTORY_MAX) return fail(t, NMPC_E_ARG, "history: n_act must be in [1, NMPC_HISTORY_MAX] to push an action");
+    if (!act || !A) return fail(t, NMPC_E_ARG, "history: act and A are needed");
+    if (a_stride < HIST_NU) return fail(t, NMPC_E_ARG, "history: a_stride must be at least 12");
+    NMPC_ENTER(t, t->device);
+    return launch_history_push_actions(t, B, act, n_act, A, a_stride, stream);
+}
+
 int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_policy_rollout_cfg* cfg, const nmpc_contact_cfg* ground,
                               float* q, float* v, const float* tau_ff, const float* goal, const double* s_mean, const double* s_std,
                               float* S, float* A, float* X, int* failed, void* stream) {
@@ -1324,7 +1413,10 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     nmpc_policy_dims d{};
     int policy_device = -1;
     if (nmpc_policy_get_dims(policy, &d, &policy_device) != NMPC_OK) return fail(t, NMPC_E_ARG, "policy is not a policy handle");
-    if (d.n_in != OB_STATE + cfg->n_goal || d.n_out != t->host.nu)
+    const auto& hs = t->history;
+    if (hs.hist && (d.n_in != hs.n_wide() + cfg->n_goal || d.n_out != t->host.nu))
+        return fail(t, NMPC_E_ARG, "history: the policy must map n_wide + n_goal inputs to 12 actions");
+    if (!hs.hist && (d.n_in != OB_STATE + cfg->n_goal || d.n_out != t->host.nu))
         return fail(t, NMPC_E_ARG, "the policy must map 44 + n_goal inputs to 12 actions");
     if (B > d.batch_max) return fail(t, NMPC_E_ARG, "B exceeds the policy's batch_max");
     if (policy_device != t->device) return fail(t, NMPC_E_ARG, "the policy lives on another device");
@@ -1333,6 +1425,8 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
     if (rec.Q && rec.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "states: qv_rows must be at least n_steps");
     const auto& seen = t->observed;
     if (seen.O && seen.rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "observed: o_rows must be at least n_steps");
+    if (hs.hist && B > hs.rows) return fail(t, NMPC_E_ARG, "history: B exceeds rows");
+    if (hs.W && hs.w_rows < cfg->n_steps) return fail(t, NMPC_E_ARG, "history: w_rows must be at least n_steps");
     if (const char* why = plant_batch_refusal(t, t->push, t->windows, B)) return fail(t, NMPC_E_ARG, why);
     const int nu = t->host.nu, K = cfg->n_steps;
     if (B > t->act_rows) {              // the dense [B][12] actions of a step (nmpc_policy_forward writes dense rows): grown once per larger batch
@@ -1348,13 +1442,19 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
         const bool rows = k < K;
         // with O attached and no S, the observation writes the true row into O's row, which is then perturbed in place
         float* const o_row = rows && seen.O ? seen.O + (size_t)k * OB_STATE : nullptr;
-        float* const s_row = rows && S ? S + (size_t)k * OB_STATE : o_row;
-        const int s_stride = (S || !seen.O) ? K * OB_STATE : seen.rows * OB_STATE;
+        // with a history attached and neither S nor O, it writes it into slot 0 of the register, which is perturbed in place alike
+        float* const h_row = rows ? hs.hist : nullptr;
+        float* const s_row = rows && S ? S + (size_t)k * OB_STATE : (o_row ? o_row : h_row);
+        const int s_stride = (S || !seen.O) ? (!S && h_row ? hs.n_obs * OB_STATE : K * OB_STATE) : seen.rows * OB_STATE;
         const long long noise_step = t->noise.step;      // the step this observation draws X at, read before it moves on
         if (const int rc = nmpc_observe_batch(t, B, q, v, at, cfg->period, goal, cfg->n_goal, s_mean, s_std, cfg->s_first, cfg->collision_height,
                                               s_row, s_stride, rows ? X : nullptr, failed, k, cfg->term_mask, stream))
             return rc;
         if (!rows) break;
+        if (h_row) {                    // the same draw into the incoming slot of the register, in front of O's launch: o_row may hold the true row
+            NMPC_ENTER(t, t->device);
+            if (const int rc = launch_observed_rows(t, B, s_row, s_stride, h_row, hs.n_obs * OB_STATE, noise_step, stream)) return rc;
+        }
         if (o_row) {                    // what the sensors showed in control step k: the draw of this step's X on the true row
             NMPC_ENTER(t, t->device);
             if (const int rc = launch_observed_rows(t, B, s_row, s_stride, o_row, seen.rows * OB_STATE, noise_step, stream)) return rc;
@@ -1365,6 +1465,13 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
             hipLaunchKernelGGL(state_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, t->host.n,
                                q, v, rec.Q + (size_t)k * t->host.n, rec.V + (size_t)k * t->host.n, (size_t)rec.rows * t->host.n);
             if (const int rc = launched(t)) return rc;
+        }
+        if (h_row) {                    // the wide row of control step k into row k of W and, normalised, over the workspace X; the register ages
+            NMPC_ENTER(t, t->device);
+            const int n_wide = hs.n_wide();
+            if (const int rc = launch_history_push(t, B, hs.hist, hs.n_obs, hs.act, hs.n_act, goal, cfg->n_goal, s_mean, s_std, cfg->s_first,
+                                                   hs.W ? hs.W + (size_t)k * n_wide : nullptr, hs.w_rows * n_wide, X, stream))
+                return rc;
         }
         if (const int rc = nmpc_policy_forward(policy, B, X, t->act, stream)) {
             const char* why = nmpc_policy_last_error(policy);
@@ -1378,6 +1485,10 @@ int nmpc_policy_rollout_batch(void* torque, void* policy, int B, const nmpc_poli
         if (const int rc = contact_step(t, B, cfg->n_sub, cfg->dt, ground, q, v, tau_ff, t->act, cfg->kp, cfg->kd, q, v, nullptr, nullptr, nullptr,
                                         t->push, t->windows, (long long)k * cfg->n_sub, stream))
             return rc;
+        if (h_row && hs.n_act > 0) {    // the target just issued into slot 0 of the action register
+            NMPC_ENTER(t, t->device);
+            if (const int rc = launch_history_push_actions(t, B, hs.act, hs.n_act, t->act, nu, stream)) return rc;
+        }
     }
     return NMPC_OK;
 }

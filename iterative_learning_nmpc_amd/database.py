@@ -26,6 +26,7 @@ from . import _lib
 from ._lib import ptr, stream
 
 FIELDS = ("states", "vc_goals", "cc_goals", "actions")
+STATS_MAX_COLS = 64                                       # the widest table nmpc_column_stats takes in one call (include/nmpc_dataset.h)
 
 
 def column_stats(table: torch.Tensor, rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -34,6 +35,17 @@ def column_stats(table: torch.Tensor, rows: Optional[int] = None) -> Tuple[torch
     assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2
     rows = table.shape[0] if rows is None else int(rows)
     cols = table.shape[1]
+    if cols > STATS_MAX_COLS:
+        # a table wider than the kernel takes (the wide rows of a history policy): the statistics of a column depend on that column
+        # alone, so the table goes through in pieces of columns, each a dense copy -- runs of 44 first, the kernel's state width
+        widths = [44] * (cols // 44)
+        rest = cols - sum(widths)
+        widths += [STATS_MAX_COLS] * (rest // STATS_MAX_COLS) + [rest % STATS_MAX_COLS] * (rest % STATS_MAX_COLS > 0)
+        pieces, c0 = [], 0
+        for w in widths:
+            pieces.append(column_stats(table[:rows, c0:c0 + w].contiguous()))
+            c0 += w
+        return torch.cat([p[0] for p in pieces]), torch.cat([p[1] for p in pieces])
     out = torch.empty(2, cols, dtype=torch.float64, device=table.device)
     scratch = torch.empty(lib.nmpc_column_stats_scratch(cols), dtype=torch.float64, device=table.device)
     _lib.check(lib.nmpc_column_stats(ptr(table), rows, cols, ptr(out[0]), ptr(out[1]), ptr(scratch), stream(table.device)),

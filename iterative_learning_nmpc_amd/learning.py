@@ -32,7 +32,7 @@ from ._lib import NMPC_ROLLOUT_TERM_SHIFT, NMPC_STATUS_NAN, NMPC_STATUS_QP
 from .collect import collect_rollouts
 from .mpc import push_windows
 from .config import TERMINATE_DEFAULT
-from .torque import N_STATE, NOMINAL_PERIOD, TABLES, GroundContact, integrator_mode
+from .torque import N_STATE, NOMINAL_PERIOD, TABLES, GroundContact, history_width, integrator_mode
 from .trajectory_io import KD, KP
 
 
@@ -112,7 +112,7 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
                     kd: float = KD, ground=None, t0: float = 0.0, period: Optional[float] = None,
                     terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08, record_states: bool = False,
                     push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None,
-                    delays=None, noise=None, noise_seed: int = 0, record_observed: bool = False):
+                    delays=None, noise=None, noise_seed: int = 0, record_observed: bool = False, history=None):
     """`policy` (a `DevicePolicy`) in the loop on the ground-contact plant of `layer` (a `BatchedTorqueLayer`) for T seconds
     from q0, v0 [B, 18]: round(T / (n_sub dt)) control steps of `layer.policy_rollout`, the policy input normalised as `db`
     (a `DeviceDatabase`, or None: raw) normalises its batches (DAgger/utils/RolloutPolicy.py, PolicyController, on the
@@ -158,9 +158,19 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
     for this call in the same way with the key `noise_seed`, first_robot = 0 and the noise step 0: the policy acts on what the
     sensors of robot b show, while S, failed, Q, V and the plant are those of the true state.  None: the policy reads the true
     state, unless the layer has a table of the caller's attached, which then stays, is used and keeps counting its own noise
-    step.  A layer that has one attached while `noise` is given is refused with ValueError as for the other tables."""
+    step.  A layer that has one attached while `noise` is given is refused with ValueError as for the other tables.
+    history: (n_obs, n_act), observation and action history on the policy input (`BatchedTorqueLayer.set_history`), attached for
+    this call: `policy` has 44 n_obs + 12 n_act + n_goal inputs and `db` (or None: raw) the state width 44 n_obs + 12 n_act; the
+    registers start holding the true row of (q0, v0, t0) and the posture of q0 (`reset_history`), and the dict has
+        W               [B, n_steps, n_wide]: row k the raw wide row the policy was shown in control step k
+                        (`BatchedTorqueLayer.set_rollout_wide`), what a database of that width stores.
+    None: the policy is memoryless, unless the layer has a history of the caller's attached, which then stays, is used and keeps
+    its registers as they are.  A layer that has one attached while `history` is given is refused with ValueError as for the tables."""
     if integrator is not None:
         integrator_mode(integrator)                       # an unknown name is refused before anything is attached
+    if history is not None:
+        n_obs, n_act = (int(x) for x in history)
+        n_wide = history_width(*layer._history_depths(n_obs, n_act))      # bad depths are refused before anything is attached
     n_steps = int(round(float(T) / (int(n_sub) * float(dt))))
     if n_steps < 1:
         raise ValueError(f"T = {T} s is shorter than one control step of {n_sub} x {dt} s")
@@ -189,6 +199,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
             raise ValueError(f"{name}: the layer has {what} attached already (set_{name})")
     if record_observed and layer._observed is not None:
         raise ValueError("record_observed: the layer has observed rows attached already (set_rollout_observed)")
+    if history is not None and layer._history is not None:
+        raise ValueError("history: the layer has a history attached already (set_history)")
     states = {}
     if record_states:
         B = torch.as_tensor(q0).reshape(-1, layer.n).shape[0]
@@ -205,6 +217,16 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
             setter(value)
         if layer._delays is not None:
             layer.reset_delay_history(q0)
+        if history is not None:
+            q_start, v_start = layer._in(q0, (layer.n,), "q0"), layer._in(v0, (layer.n,), "v0")
+            B = layer._batch(q_start, v_start)
+            layer.set_history(n_obs, n_act, batch=B)
+            states["W"] = torch.empty(B, n_steps, n_wide, dtype=torch.float32, device=layer.device)
+            layer.set_rollout_wide(states["W"])
+            # the true row of the start state: the flags-free observation of one row, which draws no noise and moves no noise step
+            S0 = layer.observe_rows(q_start[:, None, :], v_start[:, None, :], t0, int(n_sub) * float(dt), NOMINAL_PERIOD if period is None else period,
+                                    collision_height=collision_height)
+            layer.reset_history(S0[:, 0], q_start)
         q, v, S, A, failed = layer.policy_rollout(policy, q0, v0, n_steps, dt, n_sub, goal, tau_ff=tau_ff, kp=kp, kd=kd,
                                                   ground=GroundContact() if ground is None else ground, t0=t0,
                                                   period=NOMINAL_PERIOD if period is None else period, db=db,
@@ -216,6 +238,8 @@ def evaluate_policy(layer, policy, db, q0, v0, goal, T: float, dt: float = 5e-4,
             layer.set_rollout_states(None)
         if record_observed:
             layer.set_rollout_observed(None)
+        if history is not None:
+            layer.set_history(None)
     stamp = failed >> NMPC_ROLLOUT_TERM_SHIFT
     return dict(failed=failed, survived=stamp == 0, steps_survived=torch.where(stamp == 0, torch.full_like(stamp, n_steps), stamp - 1),
                 S=S, A=A, q=q, v=v, **states)
@@ -225,7 +249,8 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
                      kd: Optional[float] = None, ground=None, terminate_mask: int = TERMINATE_DEFAULT, collision_height: float = 0.08,
                      n_epoch: int = 1, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, val_fraction: float = 0.0,
                      push: Optional[dict] = None, integrator: Optional[str] = None, grounds=None, payloads=None, actuators=None,
-                     delays=None, noise=None, noise_seed: int = 0, store: str = "true", train_noise=None, train_noise_seed: int = 0):
+                     delays=None, noise=None, noise_seed: int = 0, store: str = "true", train_noise=None, train_noise_seed: int = 0,
+                     history=None):
     """One DAgger iteration proper: the LEARNER drives, the expert says what it would have done where the learner went.
         1. `evaluate_policy(record_states=True)`: `policy` drives the ground-contact plant of `layer` for T seconds from q0, v0
            [B, 18] under `goal` [B, 3] (the velocity command the controller `mpc` -- a `LocomotionMPC` of batch B -- has been
@@ -251,9 +276,17 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     (`evaluate_policy(record_observed=True)`, returned as O), with the same choice of rows, so that a policy deployed on noisy
     inputs is trained on (what it saw, what the expert would do from the true state); any other string is a ValueError before
     anything runs.  train_noise, train_noise_seed: `train_network`'s input_noise and its key, noise on the batches in training.
+    history: (n_obs, n_act), as `evaluate_policy` takes it: the learner is shown the wide row of every step, and W[b, k], the raw wide
+    row, is appended in place of S[b, k] with the same choice of rows -- `store` is not read, the wide row is what the sensors
+    showed -- so that `db.batch` of an appended row is bit for bit the input the learner acted on, under the statistics the rollout
+    used.  A `db` whose state width is not 44 n_obs + 12 n_act is refused with ValueError before anything runs.
     Returns `evaluate_policy`'s dict with A_star [B, K, 12], status int32 [B, K], n_rows, train_loss and val_loss added."""
     if store not in ("true", "observed"):
         raise ValueError(f"store: expected 'true' or 'observed', got {store!r}")
+    if history is not None:
+        n_wide = history_width(*layer._history_depths(*history))
+        if db.widths["states"] != n_wide:
+            raise ValueError(f"history: the database stores states of width {db.widths['states']}, the wide row has {n_wide}")
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
     if integrator is not None:
@@ -262,7 +295,7 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     out = evaluate_policy(layer, policy, db, q0, v0, goal, T, dt=dt, n_sub=n_sub, kp=kp, kd=kd, ground=ground,
                           terminate_mask=terminate_mask, collision_height=collision_height, record_states=True, push=push,
                           integrator=integrator, grounds=grounds, payloads=payloads, actuators=actuators, delays=delays,
-                          noise=noise, noise_seed=noise_seed, record_observed=store == "observed")
+                          noise=noise, noise_seed=noise_seed, record_observed=store == "observed" and history is None, history=history)
     A_star, status = mpc.label_states(out["Q"], out["V"], layer, dt_row=int(n_sub) * float(dt), failed=out["failed"], kp=kp, kd=kd)
     S = out["S"]
     B, K = S.shape[:2]
@@ -271,7 +304,8 @@ def dagger_iteration(mpc, layer, db, policy, q0, v0, goal, T: float, dt: float =
     n_rows = int(keep.numel())
     if n_rows:
         goals = torch.as_tensor(goal, dtype=torch.float32, device=S.device).reshape(B, -1)
-        rows = out["O"] if store == "observed" else S     # what the learner saw, or the true rows; the labels are those of the true states
+        # what the learner saw (its wide row, or its one observed row), or the true rows; the labels are those of the true states
+        rows = out["W"] if history is not None else out["O"] if store == "observed" else S
         db.append(rows.reshape(B * K, -1)[keep], A_star.reshape(B * K, -1)[keep], goals.repeat_interleave(K, dim=0)[keep])
     n = len(db)
     if n == 0:

@@ -302,6 +302,15 @@ def training_sigma(noise) -> np.ndarray:
     return np.sqrt((sigma ** 2 + bias ** 2).mean(axis=0)).astype(np.float32)
 
 
+HISTORY_MAX = _lib.NMPC_HISTORY_MAX                        # the deepest history of observed rows, and of issued targets, on the policy input
+
+
+def history_width(n_obs: int, n_act: int, nu: int = 12) -> int:
+    """n_wide = 44 n_obs + 12 n_act: the width of the row a policy with a history is shown (`BatchedTorqueLayer.set_history`), and
+    the state width of the database that stores such rows"""
+    return N_STATE * int(n_obs) + int(nu) * int(n_act)
+
+
 class BatchedTorqueLayer:
     def __init__(self, parent: Sequence[int], joint_type: Sequence[int], axis, placement_R, placement_p, mass, com, inertia,
                  foot_joint: Sequence[int], foot_offset, n_actuated: int, gravity=(0.0, 0.0, -9.81), device="cuda:0"):
@@ -337,6 +346,7 @@ class BatchedTorqueLayer:
         self._delays = None             # set_delays: the attached table with its register and scratch
         self._noise = None              # set_noise: the attached table
         self._observed = None           # set_rollout_observed: the attached rows O
+        self._history = None            # set_history: the attached registers, their depths and the wide rows W of set_rollout_wide
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -511,15 +521,15 @@ class BatchedTorqueLayer:
                                                     ptr(tau_out), stream(self.device)), self._h, "nmpc_contact_step_batch", "torque")
         return q_out, v_out, a_out, f_out, tau_out
 
-    def _stats(self, s_mean, s_std):
-        """the column statistics of the state rows as float64 device vectors [44], or (None, None)"""
+    def _stats(self, s_mean, s_std, width: int = N_STATE):
+        """the column statistics of the state rows as float64 device vectors [width], or (None, None)"""
         if (s_mean is None) != (s_std is None):
             raise ValueError("s_mean and s_std come together or not at all")
         if s_mean is None:
             return None, None
         out = [torch.as_tensor(x, dtype=torch.float64, device=self.device).contiguous() for x in (s_mean, s_std)]
-        if any(tuple(x.shape) != (N_STATE,) for x in out):
-            raise ValueError(f"s_mean, s_std: expected [{N_STATE}]")
+        if any(tuple(x.shape) != (width,) for x in out):
+            raise ValueError(f"s_mean, s_std: expected [{width}]")
         return out
 
     def _goal(self, goal, B):
@@ -567,6 +577,9 @@ class BatchedTorqueLayer:
         The contact steps are those of the layer's integrator (`set_integrator`).  With a table of noise attached (`set_noise`)
         the policy acts on the perturbed input of each of its n_steps observations and `noise_step` moves on by n_steps; S holds
         the true rows, and the rows the sensors showed go to the tensor of `set_rollout_observed` if one is attached.
+        With a history attached (`set_history`) the policy has n_wide + n_goal inputs and is shown the wide row of every step,
+        normalised with the statistics of a db whose state width is n_wide (or s_mean, s_std [n_wide]); the raw wide rows go to the
+        tensor of `set_rollout_wide` if one is attached, and both registers move on by n_steps.
         -> (q, v, S [B, n_steps, 44], A [B, n_steps, 12], failed int32 [B]); S and A are None with record=False."""
         q = self._in(q, (self.n,), "q").clone(); v = self._in(v, (self.n,), "v").clone()
         tau_ff = self._opt(tau_ff, (self.nu,), "tau_ff")
@@ -581,8 +594,12 @@ class BatchedTorqueLayer:
                 if db.states_mean is None:
                     raise ValueError("the database is empty: it has no statistics to normalise with")
                 s_mean, s_std = db.states_mean, db.states_std
-        s_mean, s_std = self._stats(s_mean, s_std)
+        hs = self._history
+        n_in = N_STATE if hs is None else hs.n_wide      # the width of the row the policy is shown, and of its statistics
+        s_mean, s_std = self._stats(s_mean, s_std, n_in)
         n_steps, n_goal = int(n_steps), goal.shape[1]
+        if hs is not None and hs.W is not None and (hs.W.shape[0] != B or hs.W.shape[1] < n_steps):
+            raise ValueError(f"W (set_rollout_wide): need [{B}, >= {n_steps}, {hs.n_wide}], got {tuple(hs.W.shape)}")
         states = self._states
         if states is not None and (states[0].shape[0] != B or states[0].shape[1] < n_steps):      # the attached tables must be this rollout's size
             raise ValueError(f"Q, V (set_rollout_states): need [{B}, >= {n_steps}, {self.n}], got {tuple(states[0].shape)}")
@@ -592,7 +609,7 @@ class BatchedTorqueLayer:
         rows = max(n_steps, 0)
         S = torch.empty(B, rows, N_STATE, dtype=torch.float32, device=self.device) if record else None
         A = torch.empty(B, rows, self.nu, dtype=torch.float32, device=self.device) if record else None
-        X = torch.empty(B, N_STATE + n_goal, dtype=torch.float32, device=self.device)
+        X = torch.empty(B, n_in + n_goal, dtype=torch.float32, device=self.device)
         failed = torch.zeros(B, dtype=torch.int32, device=self.device)
         cfg = _lib.NmpcPolicyRolloutCfg(n_steps, int(n_sub), float(dt), float(kp), float(kd), float(t0), float(period),
                                         float(collision_height), int(terminate_mask), n_goal, 1)
@@ -676,6 +693,169 @@ class BatchedTorqueLayer:
         _lib.check(self.lib.nmpc_observed_rows_batch(self._h, S.shape[0], ptr(S), s_stride, ptr(out), o_stride, step, stream(self.device)),
                    self._h, "nmpc_observed_rows_batch", "torque")
         return out
+
+    @staticmethod
+    def _history_depths(n_obs, n_act):
+        n_obs, n_act = int(n_obs), int(n_act)
+        if not 1 <= n_obs <= HISTORY_MAX:
+            raise ValueError(f"history: n_obs must be in [1, {HISTORY_MAX}], got {n_obs}")
+        if not 0 <= n_act <= HISTORY_MAX:
+            raise ValueError(f"history: n_act must be in [0, {HISTORY_MAX}], got {n_act}")
+        return n_obs, n_act
+
+    def _history_registers(self, n_obs, n_act, batch):
+        """zeroed registers hist [batch, n_obs, 44] and act [batch, n_act, 12] (None with n_act = 0) with their depths and n_wide"""
+        n_obs, n_act = self._history_depths(n_obs, n_act)
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f"history: batch must be at least 1, got {batch}")
+        hist = torch.zeros(batch, n_obs, N_STATE, dtype=torch.float32, device=self.device)
+        act = torch.zeros(batch, n_act, self.nu, dtype=torch.float32, device=self.device) if n_act else None
+        return SimpleNamespace(hist=hist, act=act, n_obs=n_obs, n_act=n_act, n_wide=history_width(n_obs, n_act), W=None, w_rows=0)
+
+    def _attach_history(self, hs):
+        """nmpc_policy_rollout_set_history with what `hs` holds, checked; then `_history` is hs"""
+        _lib.check(self.lib.nmpc_policy_rollout_set_history(self._h, ptr(hs.hist), hs.n_obs, ptr(hs.act), hs.n_act, ptr(hs.W), hs.w_rows,
+                                                            hs.hist.shape[0]), self._h, "nmpc_policy_rollout_set_history", "torque")
+        self._history = hs
+
+    def set_history(self, n_obs: Optional[int] = 1, n_act: int = 0, batch: Optional[int] = None):
+        """nmpc_policy_rollout_set_history: observation and action history on the policy input.  While attached, a policy of
+        `policy_rollout` has n_wide + n_goal inputs, n_wide = 44 n_obs + 12 n_act (`history_width`), and is shown in control step k
+        the wide row [O_k | O_{k-1} | ... | O_{k-n_obs+1} | A_{k-1} | ... | A_{k-n_act}] -- O_j the raw 44-slot row as the sensors of
+        the robot showed it in step j (`observed_rows`; S_j without a table of noise), A_j the PD target issued in step j --,
+        normalised as `DeviceDatabase.batch` normalises a stored row of width n_wide, by two or three more launches per control
+        step.  The layer allocates and keeps the two shift registers for `batch` robots (zeros; `reset_history` fills them,
+        `history` and `action_history` are the tensors themselves); they move with every control step, so two rollouts of K steps
+        are the rollout of 2 K.  Every other output of a rollout is the bits it is without a history when the policy is fed the
+        same input.  Rollouts of more robots than `batch` are refused.  `set_history(None)` detaches and drops the registers and
+        the wide rows of `set_rollout_wide`; detached, every call makes the launches and gives the bits it gives without."""
+        if n_obs is None:
+            self._history = None
+            _lib.check(self.lib.nmpc_policy_rollout_set_history(self._h, None, 0, None, 0, None, 0, 0), self._h,
+                       "nmpc_policy_rollout_set_history", "torque")
+            return
+        if batch is None:
+            raise ValueError("history: batch is needed, the robots the registers are allocated for")
+        self._attach_history(self._history_registers(n_obs, n_act, batch))
+
+    def _attached_history(self):
+        if self._history is None:
+            raise ValueError("history: nothing is attached (set_history)")
+        return self._history
+
+    @property
+    def history(self) -> Optional[torch.Tensor]:
+        """the attached register of observed rows [batch, n_obs, 44] itself (slot 0: the incoming slot; write into it to set it), or None"""
+        return None if self._history is None else self._history.hist
+
+    @property
+    def action_history(self) -> Optional[torch.Tensor]:
+        """the attached register of issued targets [batch, n_act, 12] itself, or None (nothing attached, or n_act = 0)"""
+        return None if self._history is None else self._history.act
+
+    def _reset_history(self, hs, S0, q):
+        S0 = self._in(S0, (N_STATE,), "S0"); q = self._in(q, (self.n,), "q")
+        B = self._batch(S0, q)
+        if B > hs.hist.shape[0]:
+            raise ValueError(f"history: S0 has {B} rows, the registers {hs.hist.shape[0]}")
+        hs.hist[:B] = S0[:, None, :]
+        if hs.act is not None:
+            hs.act[:B] = q[:, None, self.n - self.nu:]
+
+    def reset_history(self, S0, q):
+        """every slot of robot b's register of observed rows <- S0[b] [44], every slot of its action register <- q[b, n - nu:]: the
+        row and the posture held before the controller spoke.  S0 [B, 44], q [B, n], B at most the registers' batch; robots beyond
+        B keep theirs."""
+        self._reset_history(self._attached_history(), S0, q)
+
+    def _history_push(self, hs, goal, s_mean, s_std, s_first, W, want_x=True):
+        goal = torch.as_tensor(goal, dtype=torch.float32, device=self.device).contiguous()
+        if goal.dim() != 2:
+            raise ValueError(f"goal: expected [B, n_goal], got {tuple(goal.shape)}")
+        B, n_goal = goal.shape
+        if B > hs.hist.shape[0]:
+            raise ValueError(f"history: goal has {B} rows, the registers {hs.hist.shape[0]}")
+        s_mean, s_std = self._stats(s_mean, s_std, hs.n_wide)
+        w_stride = 0
+        if W is not None:
+            if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.dim() != 2 or W.shape != (B, W.shape[1]) or W.shape[1] < hs.n_wide \
+                    or W.device != self.device or W.stride(1) != 1 or (B > 1 and W.stride(0) < W.shape[1]):
+                raise ValueError(f"W: need a float32 [{B}, >= {hs.n_wide}] tensor with dense rows on {self.device}")
+            w_stride = W.stride(0) if B > 1 else W.shape[1]
+        X = torch.empty(B, hs.n_wide + n_goal, dtype=torch.float32, device=self.device) if want_x else None
+        _lib.check(self.lib.nmpc_history_push_batch(self._h, B, ptr(hs.hist), hs.n_obs, ptr(hs.act), hs.n_act, ptr(goal), n_goal, ptr(s_mean),
+                                                    ptr(s_std), int(s_first), ptr(W), w_stride, ptr(X), stream(self.device)),
+                   self._h, "nmpc_history_push_batch", "torque")
+        return X
+
+    def history_push(self, goal, s_mean=None, s_std=None, s_first: int = 1, W: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """nmpc_history_push_batch on the attached registers: the wide row of the first B robots (B the rows of goal [B, n_goal])
+        -> the policy input X [B, n_wide + n_goal], columns [s_first, n_wide) normalised by s_mean, s_std (float64 [n_wide]; None:
+        raw), the goal behind it raw; then the observed rows age by one slot, slot 0 keeping its content.  W: a float32
+        [B, >= n_wide] tensor with dense rows that takes the raw wide row in its first n_wide columns, or None.  What control step k
+        of `policy_rollout` does behind its observation while a history is attached."""
+        return self._history_push(self._attached_history(), goal, s_mean, s_std, s_first, W)
+
+    def _history_push_actions(self, hs, A):
+        if hs.act is None:
+            raise ValueError("history: n_act is 0, there is no action register")
+        if not isinstance(A, torch.Tensor) or A.dtype != torch.float32 or A.dim() != 2 or A.shape[1] != self.nu or A.device != self.device \
+                or A.stride(1) != 1 or (A.shape[0] > 1 and A.stride(0) < self.nu):
+            raise ValueError(f"A: need a float32 [B, {self.nu}] tensor with dense rows on {self.device}")
+        B = A.shape[0]
+        if B > hs.act.shape[0]:
+            raise ValueError(f"history: A has {B} rows, the registers {hs.act.shape[0]}")
+        _lib.check(self.lib.nmpc_history_push_actions_batch(self._h, B, ptr(hs.act), hs.n_act, ptr(A), A.stride(0) if B > 1 else self.nu,
+                                                            stream(self.device)), self._h, "nmpc_history_push_actions_batch", "torque")
+
+    def history_push_actions(self, A: torch.Tensor):
+        """nmpc_history_push_actions_batch on the attached action register: every slot of the first B robots moves up by one and
+        slot 0 takes A [B, 12] (dense rows; a row A[:, k] of a table is taken with its stride), the target just issued.  What
+        `policy_rollout` does behind its contact step while a history with n_act > 0 is attached."""
+        self._history_push_actions(self._attached_history(), A)
+
+    def set_rollout_wide(self, W: Optional[torch.Tensor] = None):
+        """the raw wide rows beside a policy rollout: while W [B, rows, n_wide] (rows >= n_steps; a slice [:, :k] of a longer table
+        is taken with its stride) is attached to the attached history, control step k of every `policy_rollout` writes robot b's
+        raw wide row into W[b, k] -- the row a database of state width n_wide stores, of which `DeviceDatabase.batch` makes the
+        bits the policy was shown.  `set_rollout_wide(None)` takes W off and leaves the history; the layer keeps W alive while it
+        is attached; a rollout of another batch size than W's is refused."""
+        hs = self._attached_history()
+        w_rows = 0
+        if W is not None:
+            if not isinstance(W, torch.Tensor) or W.dim() != 3:
+                raise ValueError(f"W: need a float32 [B, rows, {hs.n_wide}] tensor")
+            W, w_rows = self._rows(W, hs.n_wide, "W", W.shape[0])
+        self._attach_history(SimpleNamespace(**{**vars(hs), "W": W, "w_rows": w_rows}))
+
+    def history_table(self, O: torch.Tensor, A: torch.Tensor, S0, q0, n_obs: Optional[int] = None, n_act: Optional[int] = None) -> torch.Tensor:
+        """the wide rows of recorded rollouts: O [B, K, 44] (the rows the sensors showed, or the state rows) and A [B, K, 12] (the
+        issued targets) -> W [B, K, n_wide], row k being [O_k | ... | O_{k-n_obs+1} | A_{k-1} | ... | A_{k-n_act}] with S0[b] [44]
+        and q0[b, n - nu:] where the rollout had not begun -- K chained `history_push` / `history_push_actions` from
+        `reset_history(S0, q0)` on scratch registers of the call's own, so W is what a `policy_rollout` from those registers
+        leaves in `set_rollout_wide`.  For an expert's rollouts that are to train a history policy.  n_obs, n_act: the depths (None:
+        those of the attached history); the attachment and its registers are not touched."""
+        if n_obs is None or n_act is None:
+            hs = self._attached_history()
+            n_obs, n_act = hs.n_obs if n_obs is None else n_obs, hs.n_act if n_act is None else n_act
+        if not isinstance(O, torch.Tensor) or O.dim() != 3:
+            raise ValueError(f"O: need a float32 [B, K, {N_STATE}] tensor")
+        B, K = O.shape[:2]
+        O, _ = self._rows(O, N_STATE, "O", B)
+        A, _ = self._rows(A, self.nu, "A", B)
+        if A.shape[1] != K:
+            raise ValueError(f"A: need {K} rows, got {A.shape[1]}")
+        reg = self._history_registers(n_obs, n_act, max(B, 1))
+        self._reset_history(reg, S0, q0)
+        W = torch.empty(B, K, reg.n_wide, dtype=torch.float32, device=self.device)
+        goal = torch.empty(B, 0, dtype=torch.float32, device=self.device)
+        for k in range(K if B else 0):
+            reg.hist[:, 0] = O[:, k]
+            self._history_push(reg, goal, None, None, 0, W[:, k], want_x=False)
+            if reg.act is not None:
+                self._history_push_actions(reg, A[:, k])
+        return W
 
     def set_push(self, force: Optional[torch.Tensor] = None, start_substep=0, n_substeps=0, joint: int = 5):
         """nmpc_contact_set_push: while force [B, 3] (N, world frame, no moment) is attached, robot b of every `contact_step`,
