@@ -492,6 +492,12 @@ int nmpc_debug_read_momentum(void *handle, int b, int k, float *mrec_host, float
  * state-momentum kernel behind it) left for problem b < B_max of the last replan or chunk, each may be NULL --
  * x0_host float[42]: the initial state of its solve; yref_host float[N * 90]: its stage references.  Synchronises the device. */
 int nmpc_debug_read_rollout_problem(void *handle, int b, float *x0_host, float *yref_host);
+/* Test hook of the centroidal rollouts: what nmpc_rollout_prepare_kernel left for problem b < B_max of the last replan of the last
+ * nmpc_rollout_batch call, each may be NULL -- yref_host float[N * 24]: the stage references [base reference (12), force
+ * references (4 x 3)]; yref_e_host float[12]: the terminal reference; params_host float[(N + 1) * 16]: per node the contact
+ * flags (4) and the foot locations (4 x 3).  NMPC_E_ARG on a handle of another model, NMPC_E_STATE on one that never ran a
+ * rollout.  Synchronises the device. */
+int nmpc_debug_read_centroidal_rollout_problem(void *handle, int b, float *yref_host, float *yref_e_host, float *params_host);
 
 /* Diagnostic builds (-DNMPC_STAMPS) write cycle counts to dev float[B_max][16]: 8 phases
  * (linearise, IPM update+coefficients, backward, forward, last IPM update, step+write-back, -, -)

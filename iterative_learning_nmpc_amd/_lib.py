@@ -153,6 +153,7 @@ SIGNATURES = {
     "nmpc_debug_wb_layout": (c_int, [c_int, POINTER(c_size_t)]),
     "nmpc_debug_read_momentum": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float)]),
     "nmpc_debug_read_rollout_problem": (c_int, [c_void_p, c_int, POINTER(c_float), POINTER(c_float)]),
+    "nmpc_debug_read_centroidal_rollout_problem": (c_int, [c_void_p, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
 }
 
 

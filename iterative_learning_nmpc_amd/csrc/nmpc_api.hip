@@ -34,6 +34,7 @@ struct Handle {
     size_t ws_stride = 0;    // floats per problem
     float* dbg = nullptr;    // diagnostic builds only (nmpc_debug_set_buffer)
     float* roll = nullptr;   // rollout problem tensors: x0 alias, yref, yref_e, params (B_max sized)
+    bool rolled = false;     // nmpc_rollout_batch has prepared problems in `roll` (nmpc_debug_read_centroidal_rollout_problem)
     int* label_skip = nullptr;   // nmpc_wb_label_states_batch: per-problem skip flags of a chunk (B_max sized)
     int n_cu = 256;          // compute units of the device
     int force_variant = 0;   // NMPC_QP_VARIANT: 0 chosen per call by batch size and horizon (launch_solve), 1 resident, 2 lean (tests, tuning)
@@ -203,6 +204,17 @@ WbRoll wb_roll(const Handle* h) {
     r.yref_e = r.yref + up4(B_max * N * h->ny);
     r.params = r.yref_e + up4(B_max * h->nye);
     r.x0 = r.params + up4(B_max * (N + 1) * h->np);
+    return r;
+}
+
+// the centroidal rollouts' carve-up of h->roll: the three arrays back to back
+struct CentroidalRoll { float *yref, *yref_e, *params; };
+CentroidalRoll centroidal_roll(const Handle* h) {
+    const size_t B_max = (size_t)h->dims.B_max, N = (size_t)h->dims.N;
+    CentroidalRoll r{};
+    r.yref = h->roll;
+    r.yref_e = r.yref + B_max * N * h->ny;
+    r.params = r.yref_e + B_max * h->nye;
     return r;
 }
 
@@ -751,9 +763,8 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
         return fail(h, NMPC_E_ARG, "per-step recording needs nodes_per_replan * dt_nodes = replanning_steps * sim_dt");
     if (const char* why = push_windows_refusal(h, B, push_force)) return fail(h, NMPC_E_ARG, why);
     nmpc::RolloutArgs r{};
-    r.yref = h->roll;
-    r.yref_e = r.yref + (size_t)h->dims.B_max * h->dims.N * h->ny;
-    r.params = r.yref_e + (size_t)h->dims.B_max * h->nye;
+    const CentroidalRoll roll = centroidal_roll(h);
+    r.yref = roll.yref; r.yref_e = roll.yref_e; r.params = roll.params;
     r.nodes_per_replan = cfg->nodes_per_replan;
     r.mass = h->mp.mass; r.gz = h->mp.gz;
     r.gait = gait; r.x = x; r.v_des = v_des; r.w_des = w_des; r.ref_state = ref_state; r.foot_pos = foot_pos;
@@ -765,14 +776,16 @@ int nmpc_rollout_batch(void* handle, int B, const nmpc_rollout_cfg* cfg, const s
     r.foot_size = cfg->foot_size;
     nmpc::SolveArgs a = base_args(h);
     a.x0 = x; a.status = status;
-    return run_rollout(h, B, cfg, 0, static_cast<hipStream_t>(stream), r, a, nmpc::nmpc_rollout_prepare_kernel,
-                       launch_solve<nmpc::Centroidal>, nmpc::nmpc_rollout_advance_kernel,
-                       [&](int i) {
-                           r.node = cfg->start_node + i * cfg->nodes_per_replan;
-                           r.phase = phase[i];
-                           return cfg->nodes_per_replan;
-                       },
-                       [] { return NMPC_OK; }, [](int) { return NMPC_OK; });
+    const int rc = run_rollout(h, B, cfg, 0, static_cast<hipStream_t>(stream), r, a, nmpc::nmpc_rollout_prepare_kernel,
+                               launch_solve<nmpc::Centroidal>, nmpc::nmpc_rollout_advance_kernel,
+                               [&](int i) {
+                                   r.node = cfg->start_node + i * cfg->nodes_per_replan;
+                                   r.phase = phase[i];
+                                   return cfg->nodes_per_replan;
+                               },
+                               [] { return NMPC_OK; }, [](int) { return NMPC_OK; });
+    if (rc == NMPC_OK) h->rolled = true;      // every replan was launched: `roll` holds what the last prepare kernel wrote
+    return rc;
 }
 
 }  // extern "C"
@@ -1080,6 +1093,22 @@ int nmpc_debug_read_rollout_problem(void* handle, int b, float* x0_host, float* 
     if (x0_host) NMPC_TRY(h, hipMemcpy(x0_host, roll.x0 + (size_t)b * h->nx, h->nx * sizeof(float), hipMemcpyDeviceToHost));
     const size_t per = (size_t)h->dims.N * h->ny;
     if (yref_host) NMPC_TRY(h, hipMemcpy(yref_host, roll.yref + (size_t)b * per, per * sizeof(float), hipMemcpyDeviceToHost));
+    return NMPC_OK;
+}
+
+int nmpc_debug_read_centroidal_rollout_problem(void* handle, int b, float* yref_host, float* yref_e_host, float* params_host) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return NMPC_E_ARG;
+    if (h->dims.model_id != NMPC_MODEL_CENTROIDAL) return fail(h, NMPC_E_ARG, "nmpc_debug_read_centroidal_rollout_problem needs the centroidal model");
+    if (b < 0 || b >= h->dims.B_max) return fail(h, NMPC_E_ARG, "index out of range");
+    if (!h->rolled) return fail(h, NMPC_E_STATE, "the handle has never run a rollout");
+    NMPC_ENTER(h, h->device);
+    NMPC_TRY(h, hipDeviceSynchronize());
+    const CentroidalRoll roll = centroidal_roll(h);
+    const size_t N = (size_t)h->dims.N, n_yref = N * h->ny, n_params = (N + 1) * h->np;
+    if (yref_host) NMPC_TRY(h, hipMemcpy(yref_host, roll.yref + (size_t)b * n_yref, n_yref * sizeof(float), hipMemcpyDeviceToHost));
+    if (yref_e_host) NMPC_TRY(h, hipMemcpy(yref_e_host, roll.yref_e + (size_t)b * h->nye, h->nye * sizeof(float), hipMemcpyDeviceToHost));
+    if (params_host) NMPC_TRY(h, hipMemcpy(params_host, roll.params + (size_t)b * n_params, n_params * sizeof(float), hipMemcpyDeviceToHost));
     return NMPC_OK;
 }
 

@@ -110,7 +110,9 @@ class BatchedLocomotionMPC:
                  collision_height: float = COLLISION_HEIGHT):
         """footsteps: stance feet anchored, touch-downs at Raibert targets (False: the feet stay under the initial hips
         for the whole rollout -- the stance-frozen rollouts of round 1).  record_sim_steps: one state row per
-        simulation step (the plan up-sampled as mpc.py:371-414) instead of one per replan."""
+        simulation step (the plan up-sampled as mpc.py:371-414) instead of one per replan.
+        device None: the host side alone -- the configuration, the planners and the host helpers (`build_problem`,
+        `plan_foot_locations`, `sim_step_rows`, `record_state`, ...), no solver and no tensors: nothing that solves or rolls."""
         self.batch = int(batch)
         self.footsteps, self.record_sim_steps = bool(footsteps), bool(record_sim_steps)
         # early termination (include/nmpc.h, nmpc_rollout_cfg.terminate_mask): a rollout that raises one of these flags is
@@ -134,6 +136,10 @@ class BatchedLocomotionMPC:
         self.timings = defaultdict(list)
 
         self.mp = model_params(dt=self.dt_nodes, mass=mass, Ixx=inertia[0], Iyy=inertia[1], Izz=inertia[2])
+        self.solver = self.device = None
+        if device is None:
+            self.reset()
+            return
         self.solver = BatchedNmpcSolver(MODEL_CENTROIDAL, self.n_nodes, self.batch, device, compute_timings)
         self.solver.set_contact_patterns(gait_sequence=self.contact_planner.gait_sequence)   # kernel by gait
         self.device = self.solver.device
@@ -145,8 +151,8 @@ class BatchedLocomotionMPC:
         self.reset()
 
     # -- state ------------------------------------------------------------------------------------
-    def reset(self) -> None:
-        B, N = self.batch, self.n_nodes
+    def _reset_host(self) -> None:
+        B = self.batch
         self.first_solve = True
         self.sim_step = 0
         self.current_opt_node = 0
@@ -154,11 +160,17 @@ class BatchedLocomotionMPC:
         self.w_des = np.zeros((B, 3))
         self.base_ref_vel_tracking = np.zeros((B, 12))
         self.foot_pos = None
+        self.timings = defaultdict(list)
+
+    def reset(self) -> None:
+        B, N = self.batch, self.n_nodes
+        self._reset_host()
+        if self.solver is None:
+            return
         self.X = torch.zeros(B, N + 1, 12, dtype=torch.float32, device=self.device)
         self.U = torch.zeros(B, N, 12, dtype=torch.float32, device=self.device)
         self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.stats = torch.zeros(B, 4, dtype=torch.float32, device=self.device)
-        self.timings = defaultdict(list)
         self.solver.last_node = 0
 
     def set_command(self, v_des=np.zeros(3), w_yaw=0.0) -> None:

@@ -488,6 +488,17 @@ class BatchedNmpcSolver:
                    self._h, "nmpc_debug_read_rollout_problem")
         return x0, yref
 
+    def debug_centroidal_rollout_problem(self, b: int):
+        """(yref [N, 24], yref_e [12], params [N + 1, 16]) of problem b as the prepare kernel of the last replan of `rollout`
+        left them (test hook)"""
+        fp = ctypes.POINTER(ctypes.c_float)
+        N = self.n_nodes
+        yref, yref_e, params = (np.zeros(s, dtype=np.float32) for s in ((N, 24), (12,), (N + 1, 16)))
+        _lib.check(self.lib.nmpc_debug_read_centroidal_rollout_problem(self._h, b, yref.ctypes.data_as(fp), yref_e.ctypes.data_as(fp),
+                                                                      params.ctypes.data_as(fp)),
+                   self._h, "nmpc_debug_read_centroidal_rollout_problem")
+        return yref, yref_e, params
+
     @property
     def workspace_bytes(self) -> int:
         return int(self.lib.nmpc_workspace_bytes(self._h))
